@@ -1,22 +1,33 @@
 #!/usr/bin/env python3
 """bench.py — training samples/sec of the 3D vessel CausalVAE step on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                         (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = zero_grad -> forward -> ELBO -> backward -> (RCCL SUM all-reduce of the flat gradient bucket) -> Adam, on one
 batch of synthetic 128^3 volumes (B = 4 per GPU, bf16 conv arithmetic, fp32 heads/losses/master weights).  Inputs are
-resident in HBM before the timed region.  The timed region is EXACTLY K steps between barrier + synchronize brackets; it is
-repeated until >= 0.2 s have been timed and the MEDIAN repetition is reported (`timed_reps`, min / max alongside): one
-repetition of 20 steps is 19 ms, the same order as box-to-box noise.  Rank 0 prints ONE JSON line with the whole-job throughput plus
+resident in HBM before the timed region.  A plain run sets up, runs W warm-up steps, times EXACTLY K steps between barrier +
+synchronize brackets and prints ONE JSON line (rank 0) with the whole-job throughput (`value`) and `ms_per_step`.  `--min-timed-s S`
+repeats the K-step region until S seconds have been timed and reports the MEDIAN repetition (`timed_reps`, min / max alongside).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32): the step's loss
+scalars (the decoded volume for --workload decode) and the model's parameters after it, flattened in named_parameters() order.  An
+array of more than DUMP_CAP elements is written as a fixed, seeded sample of DUMP_CAP of them (sorted flat positions drawn from
+DUMP_SEED).  The inputs, the initial weights and the sampled positions are seeded: two builds run with the same arguments can be
+compared file by file.
+
+--full adds the report legs, each of which takes runs of its own:
   roofline     : the kernel family with the largest total time per step (HIP events around each of its launches, on the stream
                  they are launched on, over eager steps run right after the timed region): algorithmic FLOP/s against the dense
-                 bf16 MFMA peak of /opt/skills/guides/MI355X_MICROARCH.md (2.5 PFLOP/s); `traffic` = HBM bytes per launch from
+                 bf16 MFMA peak of the MI355X (2.5 PFLOP/s); `traffic` = HBM bytes per launch from
                  the committed rocprofv3 --pmc passes of THIS round's kernels (file and commit named in the line); `step` = the
                  whole step's algorithmic FLOPs and bytes against both peaks; `top` = the five heaviest launches;
   cpu_baseline : the CPU oracle's train step (oracle/, pinned to the reference by golden vectors) timed on this node's
                  host cores on a bounded sample of the same workload — a reported baseline, not the target;
   elbo_rel_err / elbo_rel_err_after_k : ELBO of the first batch at the initial weights, and after K = 5 Adam steps with injected
-                 noise, against the oracle's.
+                 noise, against the oracle's;
+  secondary    : (vol128, N = 1) compact lines of the other BASELINE.json configurations;
+  fp8 decode   : rel-L2 of the fp8 decode against the bf16 one.
 
 Other workloads of BASELINE.json (`--workload`): vol64-f32 (configs[2]), mnist (configs[1]), decode (configs[4]: 240 stacked
 counterfactual decodes per rank), vol128-vessel (the vessel recipe's loss on binary ~10 % volumes).
@@ -40,6 +51,8 @@ PEAK_F32_FLOPS = 157.3e12    # fp32 MFMA / vector peak
 PEAK_HBM = 8.0e12            # HBM3E spec (6.3 TB/s achievable)
 METRIC = "training samples/sec on 128^3 vessel volumes (3D CausalVAE train step)"
 TRAFFIC_FILE = os.path.join("profiles", "r03_pmc_traffic.json")
+DUMP_CAP = 1 << 22           # --dump-outputs: at most 4 Mi elements (16 MiB of float32) per array
+DUMP_SEED = 20240607
 
 
 def conv_flops(name):
@@ -197,6 +210,25 @@ def timed_region(step, steps, warmup, world, dev, min_total_s):
             return reps, out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (name, tensor) as out_dir/<name>.npy in float32 (float64 stays float64); an array larger than DUMP_CAP
+    elements as the DUMP_CAP elements at fixed, seeded flat positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays:
+        v = v.detach().flatten()
+        if v.numel() > DUMP_CAP:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, v.numel(), (DUMP_CAP,), generator=g).sort().values
+            v = v[idx.to(v.device)]
+        v = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def flat_parameters(model):
+    return torch.cat([p.detach().flatten().float() for p in model.parameters()])
+
+
 def timing_fields(reps, steps, samples_per_step):
     srt = sorted(reps)
     med = srt[len(srt) // 2]
@@ -316,11 +348,13 @@ def run_volume(args, rank, world, dev):
         def eager_step():
             return train_step(model, opt, x, m, t, grad_hook=reducer)
 
-    # ELBO of the first batch at the initial weights (compared with the oracle's below, rank 0 / N = 1)
-    with torch.no_grad():
-        out = model(x, m, t, eps=eps)
-        elbo0 = float(loss_function(out[0], x, out[1], m, out[2], out[3])[0])
-    del out
+    cpu_leg = args.full and world == 1 and args.cpu_seconds > 0 and not vessel
+    if cpu_leg:
+        # ELBO of the first batch at the initial weights (compared with the oracle's below, rank 0 / N = 1)
+        with torch.no_grad():
+            out = model(x, m, t, eps=eps)
+            elbo0 = float(loss_function(out[0], x, out[1], m, out[2], out[3])[0])
+        del out
 
     use_graph = not args.no_graph
     n_pre, want_split, capture_fallback = 0, False, None
@@ -353,10 +387,13 @@ def run_volume(args, rank, world, dev):
 
     reps, out = timed_region(step, args.steps, max(args.warmup - n_pre, 1), world, dev, args.min_timed_s)
     final_loss = out[0].clone()
+    if args.dump_outputs and rank == 0:
+        names = ("loss", "recon", "morph") if vessel else ("loss", "recon_loss", "m_loss")
+        dump_outputs(args.dump_outputs, list(zip(names, out)) + [("parameters", flat_parameters(model))])
     # ---- roofline leg: the same step issued eagerly with HIP events around every conv launch (events cannot sit inside a
     # replayed graph); same process, same buffers, directly after the timed region ----
     timer = None
-    if not args.no_kernel_timer and args.roofline_steps > 0:
+    if args.full and not args.no_kernel_timer and args.roofline_steps > 0:
         _ops.FORK_BACKWARD = False                                   # one stream: every launch is timed alone
         timer = _lib.KernelTimer()
         eager_step()
@@ -409,7 +446,7 @@ def run_volume(args, rank, world, dev):
         res["conv_ms_per_step"] = sum(v["ms_per_step"] for v in fams.values())
         res["families"] = fams
         res["kernels"] = kernels
-    if world == 1 and args.cpu_seconds > 0 and not vessel:
+    if cpu_leg:
         info = cpu_info()
         # torch.set_num_threads(all physical cores of the node) plus an 8-thread figure.  "All physical cores" are the distinct
         # thread-sibling sets inside this process's affinity mask — but a GPU box also carries a cgroup CPU quota (16 CPUs per GPU on this pool), and
@@ -472,25 +509,31 @@ def run_mnist(args, rank, world, dev):
     if not args.no_graph:
         gs = GraphedCallable(eager, warmup=3)
         n_pre = 3
-        step = lambda: (gs()["loss"],)
+        step = gs
     else:
-        step = lambda: (eager()["loss"],)
+        step = eager
     reps, out = timed_region(step, args.steps, max(args.warmup - n_pre, 1), world, dev, args.min_timed_s)
-    timer = _lib.KernelTimer()
-    eager(); torch.cuda.synchronize()
-    _lib.TIMER = timer
-    for _ in range(args.roofline_steps):
-        eager()
-    torch.cuda.synchronize()
-    _lib.TIMER = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, list(out.items()) + [("vae_parameters", flat_parameters(vae)), ("disc_parameters", flat_parameters(disc))])
+    timer = None
+    if args.full:
+        timer = _lib.KernelTimer()
+        eager(); torch.cuda.synchronize()
+        _lib.TIMER = timer
+        for _ in range(args.roofline_steps):
+            eager()
+        torch.cuda.synchronize()
+        _lib.TIMER = None
     res = {"metric": "training samples/sec, MNIST CausalMorphVAE12 adversarial step (BASELINE.json configs[1])", "unit": "samples/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic"}
     res.update(timing_fields(reps, args.steps, B))
     res["config"] = {"workload": f"MNIST CausalMorphVAE12 adversarial step (D step + VAE step, mnist_test/01_baseline_causal_vae/train.py:34-93), batch {B}, "
                                  f"{args.dtype} convs" + (" and large linears (bf16 MFMA operands, fp32 accumulate; small heads fp32)" if lin_bf16 else ", fp32 linears"),
                      "global_batch": B, "params": sum(p.numel() for p in vae.parameters()) + sum(p.numel() for p in disc.parameters())}
-    res["final_loss"] = float(out[0])
+    res["final_loss"] = float(out["loss"])
     res["hip_graph"] = not args.no_graph
+    if timer is None:
+        return res
     # algorithmic FLOPs of the step: 3 VAE forwards' worth is NOT what runs — one no-grad forward (D step), one forward + backward (VAE step)
     n_params = res["config"]["params"]
     fwd = 2.0 * B * (14 * 14 * 32 * 16 + 7 * 7 * 64 * 32 * 16 + 3158 * 512 + 512 * 20 + 10 * 128 + 128 * 12 + 22 * 3136 + 7 * 7 * 64 * 32 * 16 + 14 * 14 * 32 * 16)
@@ -521,24 +564,29 @@ def run_decode(args, rank, world, dev):
     plan, fp8_err = None, None
     if fp8:                                                   # static per-tensor scales from one bf16 pass over the first sample's 60 rows
         plan = model.calibrate_fp8_decoder(z_rep[:60], m_cf[:60])
-        with torch.no_grad():
-            a, b = model.decode(z_rep[-60:], m_cf[-60:], None, fp8_plan=plan), model.decode(z_rep[-60:], m_cf[-60:], None)
-            fp8_err = float(((a - b).norm() / b.norm()).item())
-        del a, b
+        if args.full:
+            with torch.no_grad():
+                a, b = model.decode(z_rep[-60:], m_cf[-60:], None, fp8_plan=plan), model.decode(z_rep[-60:], m_cf[-60:], None)
+                fp8_err = float(((a - b).norm() / b.norm()).item())
+            del a, b
 
     def step():
         with torch.no_grad():
             return (model.decode(z_rep, m_cf, size, fp8_plan=plan),)
     reps, out = timed_region(step, args.steps, max(args.warmup, 1), world, dev, args.min_timed_s)
     shape = tuple(out[0].shape)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("decoded", out[0])])
     del out
-    timer = _lib.KernelTimer()
-    step(); torch.cuda.synchronize()
-    _lib.TIMER = timer
-    for _ in range(args.roofline_steps):
-        step()
-    torch.cuda.synchronize()
-    _lib.TIMER = None
+    timer = None
+    if args.full:
+        timer = _lib.KernelTimer()
+        step(); torch.cuda.synchronize()
+        _lib.TIMER = timer
+        for _ in range(args.roofline_steps):
+            step()
+        torch.cuda.synchronize()
+        _lib.TIMER = None
     if rank != 0:
         return None
     res = {"metric": "counterfactual decodes/sec (batched M-sweep decode, BASELINE.json configs[4])", "unit": "decodes/s", "n_gpus": world, "steps": args.steps,
@@ -556,6 +604,8 @@ def run_decode(args, rank, world, dev):
     if fp8:
         res["fp8"] = {"format": "OCP e4m3, static per-tensor scales (calibrated on the first sample's 60 rows), fp32 accumulate; the dec_input linear stays bf16; the 1-channel output layer reads the fp8 "
                                 "codes of the layer before it and multiplies them with bf16 weights", "rel_l2_vs_bf16_decode_on_last_60_rows": fp8_err}
+    if timer is None:
+        return res
     roof, kernels, fams = roofline_from_timer(timer, args.roofline_steps, "bf16" if fp8 else args.dtype, res["ms_per_step"], fl, byt)
     if fp8 and roof is not None:
         f8fl = 2.0 * rows * 64 * (4 ** 3 * 256 * 128 + 8 ** 3 * 128 * 64 + 16 ** 3 * 64 * 32)
@@ -570,7 +620,7 @@ SECONDARY = (("mnist", "mnist", None, {}), ("vol64-f32", "vol64-f32", None, {}),
 
 
 def secondary_lines(args, dev):
-    """The other BASELINE.json configurations, measured in the SAME default run (so the driver's record carries them): configs[1] MNIST bf16
+    """The other BASELINE.json configurations, measured in the SAME --full run (so its record carries them): configs[1] MNIST bf16
     batch 1024, configs[2] 64^3 fp32 batch 16, configs[4] the 240-row counterfactual decode in bf16 and fp8 (and, with the fp8 train step,
     its train leg).  Same timed-region protocol as the headline (barrier + synchronize brackets, median repetition); compact fields only —
     the full line of each is `python bench.py --workload ...`."""
@@ -581,7 +631,7 @@ def secondary_lines(args, dev):
         a = copy.copy(args)
         dsz, dB, ddt = WORKLOAD_DEFAULTS[workload]
         a.workload, a.size, a.batch, a.dtype = workload, dsz, dB, dtype or ddt
-        a.cpu_seconds, a.roofline_steps, a.min_timed_s, a.steps, a.warmup = 0.0, 2, 0.2, 20, 5
+        a.cpu_seconds, a.roofline_steps, a.min_timed_s, a.steps, a.warmup, a.dump_outputs = 0.0, 2, 0.2, 20, 5, None
         for k, v in extra.items():
             setattr(a, k, v)
         gc.collect()
@@ -612,8 +662,12 @@ def main():
     ap.add_argument("--size", type=int, default=None, help="volume edge (default: the workload's)")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (default: the workload's)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "f32", "fp8"], help="fp8 (e4m3 conv operands): the decode workload, or vol128 = the bf16 train step with its C_in >= 32 forward convs on fp8")
-    ap.add_argument("--min-timed-s", type=float, default=0.2, help="repeat the K-step timed region until this much has been timed; the median repetition is reported")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg: half for the main figure, a quarter each for the 8-thread and all-physical-cores ones (0 disables)")
+    ap.add_argument("--min-timed-s", type=float, default=0.0, help="repeat the K-step timed region until this much has been timed; the median repetition is reported "
+                    "(default: exactly one region of --steps steps)")
+    ap.add_argument("--full", action="store_true", help="also run the report legs: roofline / per-kernel timing, CPU baseline and ELBO checks against the oracle, "
+                    "the secondary configurations, the fp8 decode error")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (and the parameters after it) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: budget of the cpu_baseline leg: half for the main figure, a quarter each for the 8-thread and all-physical-cores ones (0 disables)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the main cpu_baseline leg (0 = min(physical cores in the affinity mask, cgroup CPU quota))")
     ap.add_argument("--lr", type=float, default=1e-4, help="Adam learning rate (the reference uses 1e-3, causal_cascade/main.py:50, at which the 3D lift diverges on step 3 in the oracle too: DESIGN.md)")
     ap.add_argument("--no-kernel-timer", action="store_true")
@@ -627,10 +681,10 @@ def main():
     ap.add_argument("--no-defer-wgrad", action="store_true", help="compute every conv weight gradient in its own launch (A/B of the grouped end-of-backward launch)")
     ap.add_argument("--no-overlap-exchange", action="store_true", help="N > 1: one all-reduce after the whole backward instead of the split backward")
     ap.add_argument("--force-overlap-exchange", action="store_true", help="take the split-backward capture also at N = 1 (no exchange happens)")
-    ap.add_argument("--roofline-steps", type=int, default=5, help="eager steps with per-launch HIP events after the timed region")
+    ap.add_argument("--roofline-steps", type=int, default=5, help="--full: eager steps with per-launch HIP events after the timed region")
     ap.add_argument("--exchange", default="torch", choices=["torch", "abi"], help="N > 1: gradient exchange through torch.distributed's all_reduce on RCCL (default) or through "
                     "the C ABI of include/cvae_dp.h (libcvae_dp.so: reduce-scatter + all-gather on RCCL directly)")
-    ap.add_argument("--no-secondary", action="store_true", help="default vol128 run at N = 1: skip the compact lines of the other BASELINE.json configurations")
+    ap.add_argument("--no-secondary", action="store_true", help="--full vol128 run at N = 1: skip the compact lines of the other BASELINE.json configurations")
     ap.add_argument("--decode-native", action="store_true", help="decode workload: stop at the decoder's native 64^3 (no resize)")
     args = ap.parse_args()
     dsz, dB, ddt = WORKLOAD_DEFAULTS[args.workload]
@@ -664,7 +718,7 @@ def main():
         res = run_decode(args, rank, world, dev)
     else:
         res = run_volume(args, rank, world, dev)
-    if args.workload == "vol128" and world == 1 and not args.no_secondary and args.cpu_seconds > 0 and res is not None:      # the full-report run (A/B runs pass --cpu-seconds 0)
+    if args.full and args.workload == "vol128" and world == 1 and not args.no_secondary and args.cpu_seconds > 0 and res is not None:      # the full-report run
         res["secondary"] = secondary_lines(args, dev)
     if rank == 0:
         print(json.dumps(res))

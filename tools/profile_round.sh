@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 P=$R/gpurun_out/prof
 rm -rf $P; mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $P/stats -o run --output-format csv -- python3 $R/bench.py --cpu-seconds 0 > $P/bench_under_rocprof.json 2> $P/stats.err
+rocprofv3 --kernel-trace --stats -d $P/stats -o run --output-format csv -- python3 $R/bench.py --full --cpu-seconds 0 > $P/bench_under_rocprof.json 2> $P/stats.err
 echo "stats pass done"
 PMCARGS="--no-graph --steps 3 --warmup 2 --roofline-steps 0 --cpu-seconds 0 --min-timed-s 0"
 rocprofv3 --pmc FETCH_SIZE -d $P/pmc_fetch -o run --output-format csv -- python3 $R/bench.py $PMCARGS > /dev/null 2> $P/pmc_fetch.err
@@ -29,7 +29,7 @@ for w in mnist vol64-f32 decode decode-fp8 vol128-fp8; do
     vol128-fp8) ARGS="--dtype fp8";;
     *) ARGS="--workload $w";;
   esac
-  rocprofv3 --kernel-trace --stats -d $P/stats_$w -o run --output-format csv -- python3 $R/bench.py $ARGS --cpu-seconds 0 --no-secondary > $P/bench_${w}_under_rocprof.json 2> $P/stats_$w.err
+  rocprofv3 --kernel-trace --stats -d $P/stats_$w -o run --output-format csv -- python3 $R/bench.py $ARGS --full --cpu-seconds 0 --no-secondary > $P/bench_${w}_under_rocprof.json 2> $P/stats_$w.err
   find $P/stats_$w -name "*kernel_trace.csv" -delete; find $P/stats_$w -name "*agent_info.csv" -delete
   echo "$w stats done"
 done
