@@ -37,28 +37,20 @@ SIGNATURES = {
     "cvae_ncs_to_nsc": [_p, _p, _i64, _i64, _i64, _i, _i, _p],
     "cvae_nsc_to_ncs": [_p, _p, _i64, _i64, _i64, _i, _i, _p],
     "cvae_cast": [_p, _p, _i64, _i, _i, _p],
-    "cvae_copy_panel": [_p, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "cvae_copy_panels": [_p, _p, _p, _i, _p, _i64, _i64, _i64, _i, _p],
     "cvae_onehot_panel": [_p, _p, _i64, _i64, _i64, _i64, _p],
-    "cvae_conv_packed_weight_bytes": [_i64, _i64, _i, _i],
     "cvae_conv_pack_weight": [_p, _p, _i64, _i64, _i, _i, _i, _p],
-    "cvae_conv_pack_weights": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "cvae_conv_pack_weight_pairs": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "cvae_conv_pack_weight_pairs": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "cvae_conv_data_workspace_bytes": [_i64] * 9 + [_i, _i],
-    "cvae_conv_down": [_p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _p],
-    "cvae_conv_up": [_p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _p],
-    "cvae_quantize_fp8": [_p, _i, _p, _i64, _f, _p],
+    "cvae_conv_down": [_p] * 7 + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _p],
+    "cvae_conv_up": [_p] * 7 + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _i, _i64, _p],
+    "cvae_quantize_fp8": [_p, _i, _p, _i64, _f, _p, _p, _p],
     "cvae_conv_pack_weight_fp8": [_p, _p, _i64, _i64, _i, _i, _f, _p],
-    "cvae_conv_up_fp8": [_p, _p, _p, _p, _i, _f, _f] + [_i64] * 9 + [_i, _i, _p],
     "cvae_conv_up_c1_fp8in": [_p, _p, _p, _p, _f, _i64, _i64, _i64, _i64, _i64, _i, _i, _p],
-    "cvae_quantize_fp8_dev": [_p, _i, _p, _i64, _p, _p, _p],
     "cvae_absmax": [_p, _i, _i64, _p, _p],
     "cvae_conv_pack_weights_fp8": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
     "cvae_conv_fp8": [_i, _p, _p, _p, _p, _i, _p, _p, _f, _f, _p] + [_i64] * 9 + [_i, _i, _p, _sz, _i, _p, _p],
-    "cvae_conv_down_bits": [_p, _p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _p],
-    "cvae_conv_up_bits": [_p, _p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _p],
     "cvae_fp8_scale_update": [_p, _p, _p, _i, _f, _p, _p, _p, _i, _p, _p, _p],
-    "cvae_conv_pack_weight_pairs_f8": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "cvae_conv_down_image_f8": [_p, _i, _p, _p, _p, _p, _p, _p, _p] + [_i64] * 8 + [_i, _i, _p],
     "cvae_conv_image_supported": [_p, _i64, _i, _i],
     "cvae_conv_down_image": [_p, _i, _p, _p, _p, _p] + [_i64] * 8 + [_i, _i, _i, _p],
@@ -75,20 +67,14 @@ SIGNATURES = {
     "cvae_upsample_linear_fwd": [_p, _p] + [_i64] * 8 + [_i, _p],
     "cvae_upsample_linear_bwd": [_p, _p] + [_i64] * 8 + [_i, _p],
     "cvae_linear_workspace_bytes": [_i64, _i64, _i64, _i],
-    "cvae_linear_fwd": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _sz, _p],
-    "cvae_linear_bwd_data": [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i, _p, _sz, _p],
-    "cvae_linear_bwd_weight": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i, _p, _sz, _p],
-    "cvae_conv_up_variant": [_p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _i, _i64, _p],
-    "cvae_conv_down_variant": [_p, _p, _p, _p, _p] + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _p],
-    "cvae_linear_fwd_bf16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _sz, _p],
-    "cvae_linear_bwd_data_bf16": [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _sz, _p],
+    "cvae_linear_fwd": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _sz, _p],
+    "cvae_linear_bwd_data": [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i, _p, _i64, _i, _i, _p, _sz, _p],
+    "cvae_linear_bwd_weight": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i, _i, _p, _sz, _p],
     "cvae_small_dense_supported": [_i64, _i64, _i64],
     "cvae_small_dense_workspace_bytes": [_i64, _i64, _i64],
     "cvae_small_dense_fwd": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p],
     "cvae_small_dense_bwd_data": [_p, _p, _p, _p, _i, _p, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "cvae_small_dense_bwd_weight": [_p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _sz, _p],
-    "cvae_linear_bwd_data_inact": [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _i, _i, _p, _sz, _p],
-    "cvae_linear_bwd_weight_bf16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _sz, _p],
     "cvae_bn1d_train_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _p],
     "cvae_bn1d_train_bwd": [_p] * 8 + [_i64, _i64, _p],
     "cvae_bn1d_eval_fwd": [_p] * 6 + [_i64, _i64, _f, _p],
@@ -139,15 +125,12 @@ SIGNATURES = {
     "cvae_bn2d_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _i, _p, _sz, _p],
     "cvae_bn2d_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
     "cvae_bottleneck_sizes": [_p, _p, _p, _p, _p, _p],
-    "cvae_bottleneck_fwd": [_p] * 10 + [_f, _f, _i, _p, _p, _p, _p, _p, _i, _p],
-    "cvae_bottleneck_bwd": [_p] * 12 + [_i, _p, _p, _p, _p, _i, _p],
+    "cvae_bottleneck_fwd": [_p] * 10 + [_f, _f, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p],
+    "cvae_bottleneck_bwd": [_p] * 12 + [_i, _p, _p, _p, _p, _i, _p, _p, _p],
     "cvae_bottleneck_bn_local_stats": [_p] * 5 + [_i64, _i64, _i64, _p],
-    "cvae_bottleneck_fwd_sync": [_p] * 10 + [_f, _f, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p],
-    "cvae_bottleneck_fwd_ex": [_p] * 10 + [_f, _f, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p],
-    "cvae_bottleneck_bwd_sync": [_p] * 12 + [_i, _p, _p, _p, _p, _i, _p, _p, _p],
     "cvae_bottleneck_bn_bwd_finish": [_p] * 7 + [_i, _p],
 }
-_RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_packed_weight_bytes": _sz, "cvae_conv_wgrad_workspace_bytes": _sz,
+_RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz}

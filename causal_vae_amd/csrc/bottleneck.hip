@@ -1104,25 +1104,9 @@ extern "C" int cvae_bottleneck_bn_local_stats(const float* Wm0, const float* bm0
 }
 
 extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const void* y_cl, const float* m, float* t_onehot,
-                                   const int64_t* t_labels, const float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float bn_eps,
-                                   int bn_training, float* xcat, float* partial, float* dzm_acc, const cvae_bottleneck_saved* sv, void* dec_cl, int dtype,
-                                   void* stream) {
-    return cvae_bottleneck_fwd_ex(q, w, y_cl, m, t_onehot, t_labels, (float*)eps, running_mean, running_var, num_batches_tracked, momentum, bn_eps, bn_training, xcat, partial,
-                                  dzm_acc, sv, dec_cl, dtype, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int cvae_bottleneck_fwd_sync(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const void* y_cl, const float* m, float* t_onehot,
-                                        const int64_t* t_labels, const float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
-                                        float bn_eps, int bn_training, float* xcat, float* partial, float* dzm_acc, const cvae_bottleneck_saved* sv, void* dec_cl, int dtype,
-                                        const float* bn_rank_stats, int bn_ranks, void* stream) {
-    return cvae_bottleneck_fwd_ex(q, w, y_cl, m, t_onehot, t_labels, (float*)eps, running_mean, running_var, num_batches_tracked, momentum, bn_eps, bn_training, xcat, partial,
-                                  dzm_acc, sv, dec_cl, dtype, bn_rank_stats, bn_ranks, nullptr, stream);
-}
-
-extern "C" int cvae_bottleneck_fwd_ex(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const void* y_cl, const float* m, float* t_onehot,
-                                      const int64_t* t_labels, float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
-                                      float bn_eps, int bn_training, float* xcat, float* partial, float* dzm_acc, const cvae_bottleneck_saved* sv, void* dec_cl, int dtype,
-                                      const float* bn_rank_stats, int bn_ranks, const cvae_bottleneck_noise* noise, void* stream) {
+                                   const int64_t* t_labels, float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
+                                   float bn_eps, int bn_training, float* xcat, float* partial, float* dzm_acc, const cvae_bottleneck_saved* sv, void* dec_cl, int dtype,
+                                   const float* bn_rank_stats, int bn_ranks, const cvae_bottleneck_noise* noise, void* stream) {
     if (!dims_ok(q)) return CVAE_E_BADSHAPE;
     if (noise && !noise->call_counter) return CVAE_E_NULLPTR;
     const NoiseDraw nz = noise ? NoiseDraw{eps, (int)(q->M * q->Z), noise->seed, noise->subsequence, noise->call_counter} : NoiseDraw{nullptr, 0, 0, 0, nullptr};
@@ -1162,14 +1146,6 @@ extern "C" int cvae_bottleneck_fwd_ex(const cvae_bottleneck_dims* q, const cvae_
     return CVAE_OK;
 }
 
-extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const cvae_bottleneck_grads* gr, const cvae_bottleneck_saved* sv,
-                                   const void* g_dec_cl, const float* g_mu, const float* g_logvar, const float* g_mhat, const float* t_onehot, const float* eps,
-                                   const float* xcat, const void* y_cl, int relu_mask, float* dzm_partial, float* g1, float* dx_partial, void* dy_cl, int dtype,
-                                   void* stream) {
-    return cvae_bottleneck_bwd_sync(q, w, gr, sv, g_dec_cl, g_mu, g_logvar, g_mhat, t_onehot, eps, xcat, y_cl, relu_mask, dzm_partial, g1, dx_partial, dy_cl, dtype, nullptr,
-                                    nullptr, stream);
-}
-
 extern "C" int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const cvae_bottleneck_grads* gr, const cvae_bottleneck_saved* sv,
                                              const float* t_onehot, const float* bn_dy, const float* bn_sums, int bn_ranks, void* stream) {
     if (!dims_ok(q) || bn_ranks < 1) return CVAE_E_BADSHAPE;
@@ -1184,10 +1160,10 @@ extern "C" int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* q, cons
     return CVAE_OK;
 }
 
-extern "C" int cvae_bottleneck_bwd_sync(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const cvae_bottleneck_grads* gr, const cvae_bottleneck_saved* sv,
-                                        const void* g_dec_cl, const float* g_mu, const float* g_logvar, const float* g_mhat, const float* t_onehot, const float* eps,
-                                        const float* xcat, const void* y_cl, int relu_mask, float* dzm_partial, float* g1, float* dx_partial, void* dy_cl, int dtype,
-                                        float* bn_dy, float* bn_local_sums, void* stream) {
+extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const cvae_bottleneck_grads* gr, const cvae_bottleneck_saved* sv,
+                                   const void* g_dec_cl, const float* g_mu, const float* g_logvar, const float* g_mhat, const float* t_onehot, const float* eps,
+                                   const float* xcat, const void* y_cl, int relu_mask, float* dzm_partial, float* g1, float* dx_partial, void* dy_cl, int dtype,
+                                   float* bn_dy, float* bn_local_sums, void* stream) {
     if (!dims_ok(q)) return CVAE_E_BADSHAPE;
     if ((bn_dy == nullptr) != (bn_local_sums == nullptr)) return CVAE_E_NULLPTR;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;

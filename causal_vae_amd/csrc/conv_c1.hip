@@ -1028,7 +1028,7 @@ int cvae_conv_down_c1(const void* L, int l_dtype, const float* w, const float* b
 
 int cvae_conv_up_c1(const void* S, const float* w, const float* bias, const void* mask, void* L, int64_t B, int64_t sd, int64_t sh, int64_t sw,
                     int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, int act, hipStream_t stream, long long walk_units_arg) {
-    const long long walk_min_units = walk_units_arg > 0 ? walk_units_arg : CVAE_C1U_WALK_MIN_UNITS;     // per call (cvae_conv_up_variant), no process-wide state
+    const long long walk_min_units = walk_units_arg > 0 ? walk_units_arg : CVAE_C1U_WALK_MIN_UNITS;     // per call (cvae_conv_up c1_walk_units), no process-wide state
     if (Cs != 32) return CVAE_E_UNSUPPORTED;
     const int64_t n = B * sd * sh * sw;                     // one thread per (source voxel, channel half)
     if (n >= ((int64_t)1 << 30) || (nd == 3 && ld != 2 * sd) || lh != 2 * sh || lw != 2 * sw) return CVAE_E_UNSUPPORTED;   // exact 2x only (depth counts in 3D)

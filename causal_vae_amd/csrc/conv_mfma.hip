@@ -777,7 +777,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const float* __
 #ifndef CVAE_XPAIR_2D_MIN_WGS
 #define CVAE_XPAIR_2D_MIN_WGS 512
 #endif
-// Kernel-form selection of one `up` launch.  The library picks by launch size (-1 / 0 = automatic); cvae_conv_up_variant and cvae_conv_fp8 let a caller
+// Kernel-form selection of one `up` launch.  The library picks by launch size (-1 / 0 = automatic); cvae_conv_up and cvae_conv_fp8 let a caller
 // force a form for ONE call — the tests run every narrow case through both forms that way.  No process-wide state.
 struct UpVariant {
     int upfull = -1;            // conv_up_full_kernel: -1 by grid size (CVAE_UPFULL_MIN_GRID), 0 never, 1 whenever the shape fits it
@@ -1312,34 +1312,6 @@ __global__ __launch_bounds__(256) void absmax_kernel(const void* __restrict__ sr
     amax_publish_wg(slots, amx, blockIdx.x, red);
 }
 
-// All conv weights of a model packed in ONE launch (the table rides in the kernel arguments): the per-step re-pack of the
-// fp32 masters is ~12 tiny tensors, i.e. pure launch latency when issued one by one.
-#define PACK_MAX 24
-struct PackTable {
-    const float* w[PACK_MAX];
-    void* out[PACK_MAX];
-    int Cs[PACK_MAX], Cl[PACK_MAX], for_up[PACK_MAX], blk_start[PACK_MAX + 1];
-    int count, taps;
-};
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weight_multi_kernel(PackTable tb) {
-    int ti = 0;
-    while (ti + 1 < tb.count && (int)blockIdx.x >= tb.blk_start[ti + 1]) ++ti;
-    const int Cs = tb.Cs[ti], Cl = tb.Cl[ti], taps = tb.taps, for_up = tb.for_up[ti];
-    const float* w = tb.w[ti];
-    T* out = (T*)tb.out[ti];
-    const int64_t n = (int64_t)Cs * Cl * taps;
-    const int nb = tb.blk_start[ti + 1] - tb.blk_start[ti];
-    for (int64_t i = ((int64_t)blockIdx.x - tb.blk_start[ti]) * 256 + threadIdx.x; i < n; i += (int64_t)nb * 256) {
-        const int e = (int)(i & 15);
-        int64_t rr = i >> 4;
-        int cs, cl, tap;
-        if (!for_up) { cs = (int)(rr % Cs); rr /= Cs; const int ch = (int)(rr % (Cl / 16)); tap = (int)(rr / (Cl / 16)); cl = ch * 16 + e; }
-        else { cl = (int)(rr % Cl); rr /= Cl; const int ch = (int)(rr % (Cs / 16)); tap = (int)(rr / (Cs / 16)); cs = ch * 16 + e; }
-        out[i] = from_f32<T>(w[((int64_t)cs * Cl + cl) * taps + tap]);
-    }
-}
-
 // Both directions of every weight in one launch, through an LDS transpose: a block takes a 16 cs x 16 cl x 16 taps tile of one fp32
 // master (64-byte runs, float4 loads), and writes the `down` panel ([tap][cl / 16][cs][16 cl]) and the `up` panel
 // ([tap][cs / 16][cl][16 cs]) in 512-byte (bf16) runs — the gather form above reads every source line 16 times.  3D weights
@@ -1864,14 +1836,9 @@ extern "C" int cvae_debug_stamps(unsigned long long* host, size_t count) {
 }
 #endif
 
-extern "C" size_t cvae_conv_packed_weight_bytes(int64_t Cs, int64_t Cl, int nd, int dtype) {
-    const int64_t taps = (nd == 3) ? 64 : 16;
-    return (size_t)(Cs * Cl * taps) * (dtype == CVAE_BF16 ? 2 : 4);
-}
-
 extern "C" int cvae_conv_pack_weight(const float* w, void* packed, int64_t Cs, int64_t Cl, int nd, int for_up, int dtype, void* stream) {
     if ((nd != 2 && nd != 3) || Cs <= 0 || Cl <= 0) return CVAE_E_BADSHAPE;
-    if ((!for_up && Cl % 16) || (for_up && (Cs % 16 || Cl % 32))) return CVAE_E_UNSUPPORTED;      // what cvae_conv_up_fp8 accepts
+    if ((!for_up && Cl % 16) || (for_up && (Cs % 16 || Cl % 32))) return CVAE_E_UNSUPPORTED;      // what cvae_conv_up accepts
     if (!w || !packed) return CVAE_E_NULLPTR;
     const int taps = (nd == 3) ? 64 : 16;
     const int64_t n = Cs * Cl * taps;
@@ -1882,43 +1849,11 @@ extern "C" int cvae_conv_pack_weight(const float* w, void* packed, int64_t Cs, i
     return CVAE_OK;
 }
 
-extern "C" int cvae_conv_pack_weights(const float* const* w, void* const* packed, const int64_t* Cs, const int64_t* Cl, const int* for_up,
-                                       int count, int nd, int dtype, void* stream) {
-    if ((nd != 2 && nd != 3) || count < 0) return CVAE_E_BADSHAPE;
-    if (count == 0) return CVAE_OK;
-    if (!w || !packed || !Cs || !Cl || !for_up) return CVAE_E_NULLPTR;
-    if (dtype != CVAE_BF16 && dtype != CVAE_F32) return CVAE_E_DTYPE;
-    for (int c0 = 0; c0 < count; c0 += PACK_MAX) {
-        PackTable tb;
-        const int cnt = (count - c0 < PACK_MAX) ? count - c0 : PACK_MAX;
-        tb.taps = (nd == 3) ? 64 : 16;
-        int blocks = 0;
-        for (int i = 0; i < cnt; ++i) {
-            const int64_t cs = Cs[c0 + i], cl = Cl[c0 + i];
-            if (cs <= 0 || cl <= 0) return CVAE_E_BADSHAPE;
-            if ((!for_up[c0 + i] && cl % 16) || (for_up[c0 + i] && cs % 16)) return CVAE_E_UNSUPPORTED;
-            if (!w[c0 + i] || !packed[c0 + i]) return CVAE_E_NULLPTR;
-            tb.w[i] = w[c0 + i]; tb.out[i] = packed[c0 + i]; tb.Cs[i] = (int)cs; tb.Cl[i] = (int)cl; tb.for_up[i] = for_up[c0 + i];
-            tb.blk_start[i] = blocks;
-            int64_t nb = (cs * cl * tb.taps + 256 * 8 - 1) / (256 * 8);
-            if (nb > 1024) nb = 1024;
-            if (nb < 1) nb = 1;
-            blocks += (int)nb;
-        }
-        tb.blk_start[cnt] = blocks;
-        tb.count = cnt;
-        if (dtype == CVAE_BF16) hipLaunchKernelGGL(pack_weight_multi_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tb);
-        else hipLaunchKernelGGL(pack_weight_multi_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tb);
-        CVAE_CHECK_LAUNCH();
-    }
-    return CVAE_OK;
-}
-
 // channel counts an fp8 product accepts (cvae_conv_fp8): conv C_in % 32, C_out % 64; ConvTranspose C_in % 32, C_out % 32, C_out > 1
 static bool fp8_pack_ok(int64_t Cs, int64_t Cl, int for_up) { return for_up ? (Cs % 32 == 0 && Cl % 32 == 0 && Cl > 1) : (Cl % 32 == 0 && Cs % 64 == 0); }
-extern "C" int cvae_conv_pack_weight_pairs_f8(const float* const* w, void* const* packed_down, void* const* packed_up, const int64_t* Cs, const int64_t* Cl,
-                                              const int* f8dir, void* const* f8out, const float* const* inv_scale_dev, void* const* amax_slots,
-                                              int count, int nd, int dtype, void* stream) {
+extern "C" int cvae_conv_pack_weight_pairs(const float* const* w, void* const* packed_down, void* const* packed_up, const int64_t* Cs, const int64_t* Cl,
+                                           const int* f8dir, void* const* f8out, const float* const* inv_scale_dev, void* const* amax_slots,
+                                           int count, int nd, int dtype, void* stream) {
     if ((nd != 2 && nd != 3) || count < 0) return CVAE_E_BADSHAPE;
     if (count == 0) return CVAE_OK;
     if (!w || !packed_down || !packed_up || !Cs || !Cl) return CVAE_E_NULLPTR;
@@ -1962,10 +1897,6 @@ extern "C" int cvae_conv_pack_weight_pairs_f8(const float* const* w, void* const
     }
     return CVAE_OK;
 }
-extern "C" int cvae_conv_pack_weight_pairs(const float* const* w, void* const* packed_down, void* const* packed_up, const int64_t* Cs, const int64_t* Cl,
-                                           int count, int nd, int dtype, void* stream) {
-    return cvae_conv_pack_weight_pairs_f8(w, packed_down, packed_up, Cs, Cl, nullptr, nullptr, nullptr, nullptr, count, nd, dtype, stream);
-}
 
 #define GEOM_INIT() ConvGeom g{(int)B, (int)sd, (int)sh, (int)sw, (int)Cs, (int)ld, (int)lh, (int)lw, (int)Cl, 0, 0, 0}
 
@@ -1982,10 +1913,20 @@ extern "C" size_t cvae_conv_data_workspace_bytes(int64_t B, int64_t sd, int64_t 
     return nd == 3 ? data_workspace_bytes<3, true, 256, 32>(g) : data_workspace_bytes<2, true, 256, 32>(g);
 }
 
-static int conv_down_impl(const void* L, const void* w, const float* bias, const void* mask, void* S,
-                          int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                          int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                          void* workspace, size_t workspace_bytes, void* stream, F8Side side, UpVariant var = UpVariant{}) {
+// ReLU masks as BITS (F8Side, common.h): mask_bits replaces `mask` (1 bit per element of the result instead of the saved activation: 1/16 of the
+// bytes the backward launch reads for it), relu_bits_out receives the mask of THIS launch's result for the backward pass to come.
+static bool bits_ok(int64_t Cout) { return Cout % 32 == 0; }
+extern "C" int cvae_conv_down(const void* L, const void* w, const float* bias, const void* mask, const void* mask_bits, void* S, void* relu_bits_out,
+                              int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
+                              int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
+                              void* workspace, size_t workspace_bytes, int xpair, void* stream) {
+    if (xpair < -1 || xpair > 1 || (mask && mask_bits)) return CVAE_E_BADSHAPE;
+    if ((mask_bits || relu_bits_out) && !bits_ok(Cs)) return CVAE_E_UNSUPPORTED;
+    if (Cl == 1 && mask_bits && !(dtype == CVAE_BF16)) return CVAE_E_UNSUPPORTED;
+    F8Side side{nullptr, nullptr, nullptr};
+    side.mask_bits = (const unsigned*)mask_bits; side.bits_out = (unsigned*)relu_bits_out;
+    UpVariant var;
+    var.xpair = xpair;
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
@@ -2002,36 +1943,6 @@ static int conv_down_impl(const void* L, const void* w, const float* bias, const
                                            : launch_data<bf16, 2, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side);
     return nd == 3 ? launch_data<float, 3, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side)
                    : launch_data<float, 2, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side);
-}
-
-extern "C" int cvae_conv_down(const void* L, const void* w, const float* bias, const void* mask, void* S,
-                              int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                              int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    return conv_down_impl(L, w, bias, mask, S, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, F8Side{nullptr, nullptr, nullptr});
-}
-// cvae_conv_down with the two-samples-per-tile form forced on (1) or off (0) for this call (the tests run every narrow case through both)
-extern "C" int cvae_conv_down_variant(const void* L, const void* w, const float* bias, const void* mask, void* S,
-                                      int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                                      int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                                      void* workspace, size_t workspace_bytes, int xpair, void* stream) {
-    if (xpair < -1 || xpair > 1) return CVAE_E_BADSHAPE;
-    UpVariant var;
-    var.xpair = xpair;
-    return conv_down_impl(L, w, bias, mask, S, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, F8Side{nullptr, nullptr, nullptr}, var);
-}
-// cvae_conv_down / cvae_conv_up with ReLU masks as BITS (F8Side, common.h): mask_bits replaces `mask` (1 bit per element of the result instead of the saved
-// activation: 1/16 of the bytes the backward launch reads for it), relu_bits_out receives the mask of THIS launch's result for the backward pass to come.
-static bool bits_ok(int64_t Cout) { return Cout % 32 == 0; }
-extern "C" int cvae_conv_down_bits(const void* L, const void* w, const float* bias, const void* mask_bits, void* S, void* relu_bits_out,
-                                   int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                                   int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-    if ((mask_bits || relu_bits_out) && !bits_ok(Cs)) return CVAE_E_UNSUPPORTED;
-    if (Cl == 1 && mask_bits && !(dtype == CVAE_BF16)) return CVAE_E_UNSUPPORTED;
-    F8Side side{nullptr, nullptr, nullptr};
-    side.mask_bits = (const unsigned*)mask_bits; side.bits_out = (unsigned*)relu_bits_out;
-    return conv_down_impl(L, w, bias, nullptr, S, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, side);
 }
 // ---- the single-channel image end of the network, image read in the dtype it is stored in (no cast pass in front of the first conv) ----
 extern "C" int cvae_conv_image_supported(const void* L, int64_t lw, int l_dtype, int dtype) {
@@ -2074,10 +1985,16 @@ extern "C" int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, 
     return cvae_conv_wgrad_c1(S, L, l_dtype, dW, dbias, nullptr, workspace, workspace_bytes, B, sd, sh, sw, Cs, ld, lh, lw, nd, dtype, (hipStream_t)stream);
 }
 
-static int conv_up_impl(const void* S, const void* w, const float* bias, const void* mask, void* L,
-                        int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                        int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                        void* workspace, size_t workspace_bytes, void* stream, UpVariant var, F8Side side = F8Side{nullptr, nullptr, nullptr}) {
+extern "C" int cvae_conv_up(const void* S, const void* w, const float* bias, const void* mask, const void* mask_bits, void* L, void* relu_bits_out,
+                            int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
+                            int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
+                            void* workspace, size_t workspace_bytes, int upfull, int xpair, int64_t c1_walk_units, void* stream) {
+    if (upfull < -1 || upfull > 1 || xpair < -1 || xpair > 1 || c1_walk_units < 0 || c1_walk_units >= ((int64_t)1 << 30) || (mask && mask_bits)) return CVAE_E_BADSHAPE;
+    if ((mask_bits || relu_bits_out) && (!bits_ok(Cl) || Cl == 1)) return CVAE_E_UNSUPPORTED;
+    F8Side side{nullptr, nullptr, nullptr};
+    side.mask_bits = (const unsigned*)mask_bits; side.bits_out = (unsigned*)relu_bits_out;
+    UpVariant var;
+    var.upfull = upfull; var.xpair = xpair; var.walk_units = c1_walk_units;
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
@@ -2102,31 +2019,6 @@ static int conv_up_impl(const void* S, const void* w, const float* bias, const v
     }
     if (nd == 3) return wide ? launch_data<float, 3, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<float, 3, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
     return wide ? launch_data<float, 2, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<float, 2, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
-}
-
-extern "C" int cvae_conv_up(const void* S, const void* w, const float* bias, const void* mask, void* L,
-                            int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                            int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-    return conv_up_impl(S, w, bias, mask, L, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, UpVariant{});
-}
-extern "C" int cvae_conv_up_bits(const void* S, const void* w, const float* bias, const void* mask_bits, void* L, void* relu_bits_out,
-                                 int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                                 int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-    if ((mask_bits || relu_bits_out) && (!bits_ok(Cl) || Cl == 1)) return CVAE_E_UNSUPPORTED;
-    F8Side side{nullptr, nullptr, nullptr};
-    side.mask_bits = (const unsigned*)mask_bits; side.bits_out = (unsigned*)relu_bits_out;
-    return conv_up_impl(S, w, bias, nullptr, L, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, UpVariant{}, side);
-}
-extern "C" int cvae_conv_up_variant(const void* S, const void* w, const float* bias, const void* mask, void* L,
-                                    int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                                    int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                                    void* workspace, size_t workspace_bytes, int upfull, int xpair, int64_t c1_walk_units, void* stream) {
-    if (upfull < -1 || upfull > 1 || xpair < -1 || xpair > 1 || c1_walk_units < 0 || c1_walk_units >= ((int64_t)1 << 30)) return CVAE_E_BADSHAPE;
-    UpVariant var;
-    var.upfull = upfull; var.xpair = xpair; var.walk_units = c1_walk_units;
-    return conv_up_impl(S, w, bias, mask, L, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, dtype, act, workspace, workspace_bytes, stream, var);
 }
 
 extern "C" size_t cvae_conv_wgrad_workspace_bytes(int64_t Cs, int64_t Cl, int nd) {
@@ -2266,21 +2158,12 @@ __global__ void quantize_fp8_kernel(const void* __restrict__ src, int src_dtype,
     __shared__ float red[4];
     if (amax) amax_publish_wg(amax, amx, blockIdx.x, red);
 }
-extern "C" int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int64_t n, float inv_scale, void* stream) {
-    if (n < 0 || !(inv_scale > 0.f)) return CVAE_E_BADSHAPE;
+extern "C" int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int64_t n, float inv_scale, const float* inv_scale_dev, void* amax_slots, void* stream) {
+    if (n < 0 || (!inv_scale_dev && !(inv_scale > 0.f))) return CVAE_E_BADSHAPE;
     if (src_dtype != CVAE_F32 && src_dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (n == 0) return CVAE_OK;
     if (!src || !dst) return CVAE_E_NULLPTR;
-    hipLaunchKernelGGL(quantize_fp8_kernel, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, (fp8*)dst, n, inv_scale, (const float*)nullptr, (unsigned*)nullptr);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
-}
-extern "C" int cvae_quantize_fp8_dev(const void* src, int src_dtype, void* dst, int64_t n, const float* inv_scale_dev, void* amax_slots, void* stream) {
-    if (n < 0) return CVAE_E_BADSHAPE;
-    if (src_dtype != CVAE_F32 && src_dtype != CVAE_BF16) return CVAE_E_DTYPE;
-    if (n == 0) return CVAE_OK;
-    if (!src || !dst || !inv_scale_dev) return CVAE_E_NULLPTR;
-    hipLaunchKernelGGL(quantize_fp8_kernel, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, (fp8*)dst, n, 1.f, inv_scale_dev, (unsigned*)amax_slots);
+    hipLaunchKernelGGL(quantize_fp8_kernel, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, (fp8*)dst, n, inv_scale, inv_scale_dev, (unsigned*)amax_slots);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
@@ -2392,13 +2275,6 @@ extern "C" int cvae_conv_fp8(int up, const void* in8, const void* w8, const floa
     if (nd == 3) return up ? F8D(3, true) : F8D(3, false);
     return up ? F8D(2, true) : F8D(2, false);
 #undef F8D
-}
-// the inference entry point of round 2, kept: static scales by value, result as bf16 or as codes
-extern "C" int cvae_conv_up_fp8(const void* S, const void* w, const float* bias, void* L, int out_dtype, float acc_scale, float out_inv_scale,
-                                int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int act,
-                                void* stream) {
-    return cvae_conv_fp8(1, S, w, bias, L, out_dtype, nullptr, nullptr, acc_scale, out_dtype == CVAE_FP8 ? out_inv_scale : 1.f, nullptr, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, act,
-                         nullptr, 0, -1, nullptr, stream);
 }
 
 extern "C" int cvae_conv_up_c1_fp8in(const void* S8, const float* w, const float* bias, void* L, float in_scale, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int nd,

@@ -98,22 +98,6 @@ extern "C" int cvae_nsc_to_ncs(const void* src, void* dst, int64_t B, int64_t C,
 }
 
 // ------------------------------------------------------------------------------------- concat panels
-__global__ void copy_panel_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t B, int64_t cols,
-                                  int64_t ss, int64_t ds, int64_t col0) {
-    const int64_t n = B * cols;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t b = i / cols, j = i - b * cols;
-        dst[b * ds + col0 + j] = src[b * ss + j];
-    }
-}
-extern "C" int cvae_copy_panel(const float* src, float* dst, int64_t B, int64_t cols, int64_t ss, int64_t ds, int64_t col0, void* stream) {
-    if (B < 0 || cols < 0 || ss < cols || col0 < 0 || ds < col0 + cols) return CVAE_E_BADSHAPE;
-    if (B * cols == 0) return CVAE_OK;
-    if (!src || !dst) return CVAE_E_NULLPTR;
-    hipLaunchKernelGGL(copy_panel_kernel, dim3(cvae_grid_1d(B * cols, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, B, cols, ss, ds, col0);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
-}
 // Several panels in ONE launch (torch.cat of 2-3 small matrices was 2-3 launches of < 5 us): gather == 0 writes panel i = src[i] ([B, w_i], row
 // stride ss[i]) into dst[:, col0 + sum_{k<i} w_k ..]; gather != 0 copies those column ranges of the wide matrix out into the panels (cat's backward).
 #define PANELS_MAX 8

@@ -649,10 +649,15 @@ extern "C" size_t cvae_linear_workspace_bytes(int64_t M, int64_t K, int64_t N, i
     }
     return splits > 1 ? (size_t)splits * elems * sizeof(float) : 0;
 }
+// bf16_math: bf16 MFMA operands (gemm_bf16_kernel) for batches above the skinny range only; fp32 in, fp32 out, the bias gradient stays an fp32 column
+// sum.  Workspace: cvae_linear_workspace_bytes (same tiles and split-K as the fp32 form).
 extern "C" int cvae_linear_fwd(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N,
-                               int64_t x_stride, int64_t y_stride, int act, void* workspace, size_t workspace_bytes, void* stream) {
+                               int64_t x_stride, int64_t y_stride, int act, int bf16_math, void* workspace, size_t workspace_bytes, void* stream) {
     if (x_stride < K) return CVAE_E_BADSHAPE;
-    if (M > 0 && M <= SK_M && N > 0 && K >= 64 && y_stride >= N) {
+    if (bf16_math) {
+        if (y_stride < N) return CVAE_E_BADSHAPE;
+        if (M <= SK_M) return CVAE_E_UNSUPPORTED;
+    } else if (M > 0 && M <= SK_M && N > 0 && K >= 64 && y_stride >= N) {
         if (!x || !W || !y) return CVAE_E_NULLPTR;
         hipStream_t st = (hipStream_t)stream;
         int64_t kchunk;
@@ -668,15 +673,24 @@ extern "C" int cvae_linear_fwd(const float* x, const float* W, const float* b, f
         }
         return CVAE_OK;
     }
-    return gemm_f32(x, W, y, b, M, N, K, x_stride, 1, 1, K, y_stride, act, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+    return gemm_f32(x, W, y, b, M, N, K, x_stride, 1, 1, K, y_stride, act, (float*)workspace, workspace_bytes, (hipStream_t)stream, bf16_math != 0);
 }
-extern "C" int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N,
-                                    int64_t dy_stride, int64_t dx_stride, const float* y_act, int act, void* workspace, size_t workspace_bytes, void* stream) {
+// in_act: dx = (dy . W) * act'(x_in), the data gradient through this layer AND through the activation that produced this layer's input x_in [M][K] (act' from
+// the activation's output, i.e. from x_in itself) in the GEMM's epilogue — the previous layer then skips its own activation-gradient pass.  Batches above the
+// skinny range.
+extern "C" int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
+                                    const float* y_act, int act, const float* x_in, int64_t x_stride, int in_act, int bf16_math,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
     if (dy_stride < N) return CVAE_E_BADSHAPE;
     if (act == CVAE_ACT_NONE) y_act = nullptr;
     if (y_act && !(M > 0 && M <= SK_M)) return CVAE_E_UNSUPPORTED;      // fused activation gradient: skinny path only
-    // skinny path: wide layers (K >= 1024) always; narrow ones when the activation gradient is fused (materialise-free)
-    if (M > 0 && M <= SK_M && N > 0 && dx_stride >= K && (K >= 1024 || y_act)) {
+    const bool epi = in_act != CVAE_ACT_NONE;
+    if (bf16_math || epi) {                                              // GEMM path only
+        if (dx_stride < K || (epi && x_stride < K)) return CVAE_E_BADSHAPE;
+        if (M <= SK_M) return CVAE_E_UNSUPPORTED;
+        if (epi && !x_in) return CVAE_E_NULLPTR;
+    } else if (M > 0 && M <= SK_M && N > 0 && dx_stride >= K && (K >= 1024 || y_act)) {
+        // skinny path: wide layers (K >= 1024) always; narrow ones when the activation gradient is fused (materialise-free)
         if (!dy || !W || !dx) return CVAE_E_NULLPTR;
         hipStream_t st = (hipStream_t)stream;
         const int64_t kb = (K + 255) / 256;
@@ -692,14 +706,17 @@ extern "C" int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, 
         }
         return CVAE_OK;
     }
-    return gemm_f32(dy, W, dx, nullptr, M, K, N, dy_stride, 1, K, 1, dx_stride, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+    const EpiMul em = epi ? EpiMul{x_in, x_stride, in_act} : EpiMul{nullptr, 0, 0};
+    return gemm_f32(dy, W, dx, nullptr, M, K, N, dy_stride, 1, K, 1, dx_stride, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, bf16_math != 0, em);
 }
 extern "C" int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW, float* db, int64_t M, int64_t K, int64_t N,
-                                      int64_t dy_stride, int64_t x_stride, const float* y_act, int act, void* workspace, size_t workspace_bytes, void* stream) {
-    if (dy_stride < N || x_stride < K || M <= 0) return CVAE_E_BADSHAPE;
+                                      int64_t dy_stride, int64_t x_stride, const float* y_act, int act, int bf16_math, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (dy_stride < N || x_stride < K) return CVAE_E_BADSHAPE;
+    if (bf16_math && M <= SK_M) return CVAE_E_UNSUPPORTED;
+    if (M <= 0) return CVAE_E_BADSHAPE;
     if (act == CVAE_ACT_NONE) y_act = nullptr;
     if (y_act && M > SK_M) return CVAE_E_UNSUPPORTED;
-    int rc = CVAE_OK;
     if (M <= SK_M && N > 0 && K > 0) {
         if (!dy || !x || !dW) return CVAE_E_NULLPTR;
         if (K >= 256 && N <= 65535) {
@@ -710,50 +727,12 @@ extern "C" int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW
         }
         CVAE_CHECK_LAUNCH();
         return CVAE_OK;
-    } else {
-        rc = gemm_f32(dy, x, dW, nullptr, N, K, M, 1, dy_stride, x_stride, 1, K, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream);
     }
+    const int rc = gemm_f32(dy, x, dW, nullptr, N, K, M, 1, dy_stride, x_stride, 1, K, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, bf16_math != 0);
     if (rc != CVAE_OK) return rc;
     if (db) {
         if (dy_stride != N) return CVAE_E_UNSUPPORTED;
         return cvae_channel_sum(dy, db, M, N, CVAE_F32, workspace, workspace_bytes, stream);    // stream order: the GEMM's slabs are consumed by then
-    }
-    return CVAE_OK;
-}
-
-// ---- the three linear products with bf16 MFMA operands (gemm_bf16_kernel): batches above the skinny range only; fp32 in, fp32 out, the bias
-// gradient stays an fp32 column sum.  Workspace: cvae_linear_workspace_bytes (same tiles and split-K as the fp32 form). ----
-extern "C" int cvae_linear_fwd_bf16(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N, int64_t x_stride, int64_t y_stride,
-                                    int act, void* workspace, size_t workspace_bytes, void* stream) {
-    if (x_stride < K || y_stride < N) return CVAE_E_BADSHAPE;
-    if (M <= SK_M) return CVAE_E_UNSUPPORTED;
-    return gemm_f32(x, W, y, b, M, N, K, x_stride, 1, 1, K, y_stride, act, (float*)workspace, workspace_bytes, (hipStream_t)stream, true);
-}
-extern "C" int cvae_linear_bwd_data_bf16(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
-                                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (dy_stride < N || dx_stride < K) return CVAE_E_BADSHAPE;
-    if (M <= SK_M) return CVAE_E_UNSUPPORTED;
-    return gemm_f32(dy, W, dx, nullptr, M, K, N, dy_stride, 1, K, 1, dx_stride, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, true);
-}
-// dx = (dy . W) * act'(x_in): the data gradient through this layer AND through the activation that produced this layer's input x_in [M][K] (act' from the
-// activation's output, i.e. from x_in itself) in the GEMM's epilogue — the previous layer then skips its own activation-gradient pass.  Batches above the skinny range.
-extern "C" int cvae_linear_bwd_data_inact(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
-                                          const float* x_in, int64_t x_stride, int in_act, int bf16_math, void* workspace, size_t workspace_bytes, void* stream) {
-    if (dy_stride < N || dx_stride < K || x_stride < K) return CVAE_E_BADSHAPE;
-    if (M <= SK_M) return CVAE_E_UNSUPPORTED;
-    if (in_act != CVAE_ACT_NONE && !x_in) return CVAE_E_NULLPTR;
-    const EpiMul em = (in_act == CVAE_ACT_NONE) ? EpiMul{nullptr, 0, 0} : EpiMul{x_in, x_stride, in_act};
-    return gemm_f32(dy, W, dx, nullptr, M, K, N, dy_stride, 1, K, 1, dx_stride, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, bf16_math != 0, em);
-}
-extern "C" int cvae_linear_bwd_weight_bf16(const float* dy, const float* x, float* dW, float* db, int64_t M, int64_t K, int64_t N, int64_t dy_stride,
-                                           int64_t x_stride, void* workspace, size_t workspace_bytes, void* stream) {
-    if (dy_stride < N || x_stride < K) return CVAE_E_BADSHAPE;
-    if (M <= SK_M) return CVAE_E_UNSUPPORTED;
-    const int rc = gemm_f32(dy, x, dW, nullptr, N, K, M, 1, dy_stride, x_stride, 1, K, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, true);
-    if (rc != CVAE_OK) return rc;
-    if (db) {
-        if (dy_stride != N) return CVAE_E_UNSUPPORTED;
-        return cvae_channel_sum(dy, db, M, N, CVAE_F32, workspace, workspace_bytes, stream);
     }
     return CVAE_OK;
 }

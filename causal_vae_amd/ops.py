@@ -338,11 +338,8 @@ def pack_weights(weights, nd, dtype, f8spec=None):
     k = len(ws)
     if k:
         vp = lambda v: (C.c_void_p * k)(*v)
-        if any(fd):
-            check(lib.cvae_conv_pack_weight_pairs_f8(vp(ws), vp(pd), vp(pu), (C.c_int64 * k)(*cs), (C.c_int64 * k)(*cl), (C.c_int * k)(*fd), vp(fo), vp(fi), vp(fa),
-                                                     k, nd, L.dtype_code(dtype), stream()), "conv_pack_weight_pairs_f8")
-        else:
-            check(lib.cvae_conv_pack_weight_pairs(vp(ws), vp(pd), vp(pu), (C.c_int64 * k)(*cs), (C.c_int64 * k)(*cl), k, nd, L.dtype_code(dtype), stream()), "conv_pack_weight_pairs")
+        check(lib.cvae_conv_pack_weight_pairs(vp(ws), vp(pd), vp(pu), (C.c_int64 * k)(*cs), (C.c_int64 * k)(*cl), (C.c_int * k)(*fd), vp(fo), vp(fi), vp(fa),
+                                              k, nd, L.dtype_code(dtype), stream()), "conv_pack_weight_pairs")
     return outs
 
 
@@ -417,21 +414,18 @@ def _conv_down(Lt, wp, bias, mask, Cs, nd, act, out_dtype=None, mask_bits=None, 
     c1_ok = Cl != 1 or (Lt.dtype == torch.bfloat16 and lw % 8 == 0)
     bits = _bits_for(S) if (want_bits and Cl != 1 and Cs % 64 == 0 and Cl % 16 == 0) else None
     use_mb = mask_bits if (mask_bits is not None and c1_ok) else None      # the bit form of the mask wins over the tensor form when the launch can read it
-    if use_mb is None and mask is not None:
-        bits = None                                          # a tensor mask: the plain entry point (backward launches want no bits of their own anyway)
-    if DOWN_VARIANT is not None and Cl != 1 and use_mb is None:
-        check(lib.cvae_conv_down_variant(ptr(Lt), ptr(wp), ptr(bias), ptr(mask), ptr(S), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(Lt.dtype), L.act_code(act),
-                                         ptr(ws), nbytes, int(DOWN_VARIANT), stream()), "conv_down_variant")
-        return (S, None) if want_bits is not None else S
-    if use_mb is not None or bits is not None:
-        check(L.timed(label, lib.cvae_conv_down_bits, ptr(Lt), ptr(wp), ptr(bias), ptr(use_mb), ptr(S), ptr(bits), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(Lt.dtype),
-                      L.act_code(act), ptr(ws), nbytes, stream()), "conv_down_bits")
-        BITS_STATS["produced"] += bits is not None
-        BITS_STATS["consumed"] += use_mb is not None
-        return (S, bits) if want_bits is not None else S
-    check(L.timed(label, lib.cvae_conv_down, ptr(Lt), ptr(wp), ptr(bias), ptr(mask), ptr(S),
-                  B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(Lt.dtype), L.act_code(act), ptr(ws), nbytes, stream()), "conv_down")
-    return (S, None) if want_bits is not None else S
+    if use_mb is not None:
+        mask = None
+    elif mask is not None:
+        bits = None                                          # a tensor mask: no bits (backward launches want no bits of their own anyway)
+    variant = DOWN_VARIANT is not None and Cl != 1 and use_mb is None
+    if variant:
+        bits = None                                          # the test hook forces a kernel form: the tensor form of the mask, no bits
+    check(L.timed(label, lib.cvae_conv_down, ptr(Lt), ptr(wp), ptr(bias), ptr(mask), ptr(use_mb), ptr(S), ptr(bits), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd,
+                  L.dtype_code(Lt.dtype), L.act_code(act), ptr(ws), nbytes, int(DOWN_VARIANT) if variant else -1, stream()), "conv_down")
+    BITS_STATS["produced"] += bits is not None
+    BITS_STATS["consumed"] += use_mb is not None
+    return (S, bits) if want_bits is not None else S
 
 
 _GRAD_AT_APPLY = [True]
@@ -455,8 +449,8 @@ class _GradModeAtApply:
             _GRAD_AT_APPLY[0] = True
 
 
-DOWN_VARIANT = None  # test hook: xpair (0 / 1) for cvae_conv_down_variant — two samples per tile off / on for every multi-channel `down` launch; None = automatic
-UP_VARIANT = None    # test hook: (upfull, xpair, c1_walk_units) for cvae_conv_up_variant / the xpair of cvae_conv_fp8; None = the library's automatic choice
+DOWN_VARIANT = None  # test hook: xpair (0 / 1) for cvae_conv_down — two samples per tile off / on for every multi-channel `down` launch; None = automatic
+UP_VARIANT = None    # test hook: (upfull, xpair, c1_walk_units) for cvae_conv_up / the xpair of cvae_conv_fp8; None = the library's automatic choice
 
 
 def _conv_up(St, wp, bias, mask, Cl, nd, act, l_dims=None, mask_bits=None, want_bits=None):
@@ -466,23 +460,18 @@ def _conv_up(St, wp, bias, mask, Cl, nd, act, l_dims=None, mask_bits=None, want_
     ld, lh, lw = ((2 * sd if nd == 3 else 1), 2 * sh, 2 * sw) if l_dims is None else tuple(int(v) for v in l_dims)
     Lt = _empty((B, ld, lh, lw, Cl), St.dtype, St)
     ws, nbytes = _conv_data_workspace(St.device, B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, 1)
-    if UP_VARIANT is not None:
-        check(lib.cvae_conv_up_variant(ptr(St), ptr(wp), ptr(bias), ptr(mask), ptr(Lt), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(St.dtype), L.act_code(act),
-                                       ptr(ws), nbytes, int(UP_VARIANT[0]), int(UP_VARIANT[1]), int(UP_VARIANT[2]), stream()), "conv_up_variant")
-        return (Lt, None) if want_bits is not None else Lt
     label = f"conv_up nd{nd} B{B} S{sd}x{sh}x{sw}x{Cs} -> L{Cl}"
-    bits_ok = Cl != 1 and Cl % 32 == 0 and Cs % 16 == 0
+    bits_ok = UP_VARIANT is None and Cl != 1 and Cl % 32 == 0 and Cs % 16 == 0     # the test hook forces a kernel form: the tensor form of the mask, no bits
     use_mb = mask_bits if (mask_bits is not None and bits_ok) else None
     bits = _bits_for(Lt) if (want_bits and bits_ok and (mask is None or use_mb is not None)) else None
-    if use_mb is not None or bits is not None:
-        check(L.timed(label, lib.cvae_conv_up_bits, ptr(St), ptr(wp), ptr(bias), ptr(use_mb), ptr(Lt), ptr(bits), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(St.dtype),
-                      L.act_code(act), ptr(ws), nbytes, stream()), "conv_up_bits")
-        BITS_STATS["produced"] += bits is not None
-        BITS_STATS["consumed"] += use_mb is not None
-        return (Lt, bits) if want_bits is not None else Lt
-    check(L.timed(label, lib.cvae_conv_up, ptr(St), ptr(wp), ptr(bias), ptr(mask), ptr(Lt),
-                  B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd, L.dtype_code(St.dtype), L.act_code(act), ptr(ws), nbytes, stream()), "conv_up")
-    return (Lt, None) if want_bits is not None else Lt
+    if use_mb is not None:
+        mask = None
+    upfull, xpair, walk = (-1, -1, 0) if UP_VARIANT is None else (int(v) for v in UP_VARIANT)
+    check(L.timed(label, lib.cvae_conv_up, ptr(St), ptr(wp), ptr(bias), ptr(mask), ptr(use_mb), ptr(Lt), ptr(bits), B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd,
+                  L.dtype_code(St.dtype), L.act_code(act), ptr(ws), nbytes, upfull, xpair, walk, stream()), "conv_up")
+    BITS_STATS["produced"] += bits is not None
+    BITS_STATS["consumed"] += use_mb is not None
+    return (Lt, bits) if want_bits is not None else Lt
 
 
 DEFER_WGRAD = True     # weight gradients of the MFMA conv layers are queued during a backward pass and computed by ONE grouped launch (+ one
@@ -742,7 +731,7 @@ def quantize_fp8(x, scale):
     L.require_gpu(x)
     x = x.contiguous()
     q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    check(lib.cvae_quantize_fp8(ptr(x), L.dtype_code(x.dtype), ptr(q), x.numel(), 1.0 / float(scale), stream()), "quantize_fp8")
+    check(lib.cvae_quantize_fp8(ptr(x), L.dtype_code(x.dtype), ptr(q), x.numel(), 1.0 / float(scale), None, None, stream()), "quantize_fp8")
     return q
 
 
@@ -828,7 +817,7 @@ def quantize_fp8_dev(x, inv_scale_dev, amax=None):
     L.require_gpu(x)
     x = x.contiguous()
     q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    check(lib.cvae_quantize_fp8_dev(ptr(x), L.dtype_code(x.dtype), ptr(q), x.numel(), ptr(inv_scale_dev), ptr(amax), stream()), "quantize_fp8_dev")
+    check(lib.cvae_quantize_fp8(ptr(x), L.dtype_code(x.dtype), ptr(q), x.numel(), 1.0, ptr(inv_scale_dev), ptr(amax), stream()), "quantize_fp8")
     return q
 
 
@@ -1007,7 +996,7 @@ class Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, math=None, in_act=None, grad_premasked=False):
         """in_act: x is the OUTPUT of that activation and this layer is its only consumer — the data gradient leaves this layer's backward already multiplied by
-        the activation's derivative (cvae_linear_bwd_data_inact); grad_premasked: the gradient arriving at this layer's output already carries act'(y) (the next
+        the activation's derivative (cvae_linear_bwd_data's in_act); grad_premasked: the gradient arriving at this layer's output already carries act'(y) (the next
         layer was given in_act = act).  layers.MLP sets the pair for consecutive layers at batch sizes above 16: one elementwise launch fewer per layer."""
         L.require_gpu(x, weight, bias)
         if x.dtype != torch.float32:
@@ -1028,11 +1017,8 @@ class Linear(torch.autograd.Function):
             return y
         ctx.small = False
         _t, wp, wb = _scratch(lib.cvae_linear_workspace_bytes(M, K, N, 0), x)
-        if b16:
-            check(L.timed(f"linear_fwd M{M} K{K} N{N} bf16", lib.cvae_linear_fwd_bf16, ptr(x), ptr(weight), ptr(bias), ptr(y), M, K, N, K, N, L.act_code(act), wp, wb, stream()),
-                  "linear_fwd_bf16")
-        else:
-            check(L.timed(f"linear_fwd M{M} K{K} N{N}", lib.cvae_linear_fwd, ptr(x), ptr(weight), ptr(bias), ptr(y), M, K, N, K, N, L.act_code(act), wp, wb, stream()), "linear_fwd")
+        check(L.timed(f"linear_fwd M{M} K{K} N{N}" + (" bf16" if b16 else ""), lib.cvae_linear_fwd, ptr(x), ptr(weight), ptr(bias), ptr(y), M, K, N, K, N, L.act_code(act),
+                      int(b16), wp, wb, stream()), "linear_fwd")
         ctx.save_for_backward(x, weight, y)
         if (in_act not in (None, "none") or grad_premasked) and M <= 16:
             raise L.CvaeError("Linear: in_act / grad_premasked are for batches above 16 (the skinny kernels fuse the activation gradient on the consuming side)")
@@ -1079,24 +1065,15 @@ class Linear(torch.autograd.Function):
                 if has_bias and ctx.needs_input_grad[2]:
                     db = _empty((N,), torch.float32, g)
                 _t, wp, wb = _scratch(lib.cvae_linear_workspace_bytes(M, K, N, 2), g)
-                if b16:
-                    check(L.timed(f"linear_bwd_weight M{M} K{K} N{N} bf16", lib.cvae_linear_bwd_weight_bf16, ptr(g), ptr(x), ptr(dw), ptr(db), M, K, N, N, K, wp, wb, stream()),
-                          "linear_bwd_weight_bf16")
-                else:
-                    check(L.timed(f"linear_bwd_weight M{M} K{K} N{N}", lib.cvae_linear_bwd_weight, ptr(g), ptr(x), ptr(dw), ptr(db), M, K, N, N, K, ya, ac, wp, wb, stream()),
-                          "linear_bwd_weight")
+                check(L.timed(f"linear_bwd_weight M{M} K{K} N{N}" + (" bf16" if b16 else ""), lib.cvae_linear_bwd_weight, ptr(g), ptr(x), ptr(dw), ptr(db), M, K, N, N, K,
+                              ya, ac, int(b16), wp, wb, stream()), "linear_bwd_weight")
             elif has_bias and ctx.needs_input_grad[2]:
                 db = _channel_sum(_act_bwd(g, y, act) if fused else g)
         if ctx.needs_input_grad[0]:
             dx = _empty((M, K), torch.float32, g)
             _t2, wp2, wb2 = _scratch(lib.cvae_linear_workspace_bytes(M, K, N, 1), g)
-            if in_act is not None:
-                check(L.timed(f"linear_bwd_data M{M} K{K} N{N}" + (" bf16" if b16 else ""), lib.cvae_linear_bwd_data_inact, ptr(g), ptr(weight), ptr(dx), M, K, N, N, K, ptr(x), K,
-                              L.act_code(in_act), int(b16), wp2, wb2, stream()), "linear_bwd_data_inact")
-            elif b16:
-                check(L.timed(f"linear_bwd_data M{M} K{K} N{N} bf16", lib.cvae_linear_bwd_data_bf16, ptr(g), ptr(weight), ptr(dx), M, K, N, N, K, wp2, wb2, stream()), "linear_bwd_data_bf16")
-            else:
-                check(L.timed(f"linear_bwd_data M{M} K{K} N{N}", lib.cvae_linear_bwd_data, ptr(g), ptr(weight), ptr(dx), M, K, N, N, K, ya, ac, wp2, wb2, stream()), "linear_bwd_data")
+            check(L.timed(f"linear_bwd_data M{M} K{K} N{N}" + (" bf16" if b16 else ""), lib.cvae_linear_bwd_data, ptr(g), ptr(weight), ptr(dx), M, K, N, N, K, ya, ac,
+                          ptr(x) if in_act is not None else None, K, L.act_code(in_act), int(b16), wp2, wb2, stream()), "linear_bwd_data")
         fork.join(dw, db)
         return dx, dw, db, None, None, None, None
 
@@ -1689,9 +1666,9 @@ class BioBottleneck(torch.autograd.Function):
             if noise[2].dtype != torch.int32 or noise[2].device != dev:
                 raise L.CvaeError("BioBottleneck: the noise call counter must be an int32 tensor on the activations' device")
             nstruct = C_.byref(L.BottleneckNoise(int(noise[0]), int(noise[1]), ptr(noise[2])))
-        check(lib.cvae_bottleneck_fwd_ex(C_.byref(dims), C_.byref(pstruct), ptr(y_cl), ptr(m), ptr(t_onehot), ptr(t_labels), ptr(eps), ptr(rm), ptr(rv), ptr(nbt), float(momentum),
-                                         float(bn_eps), 1, ptr(xcat), ptr(partial), ptr(dzm_acc), C_.byref(sstruct), ptr(dec_cl), L.dtype_code(y_cl.dtype), ptr(rank_stats), ranks,
-                                         nstruct, stream()), "bottleneck_fwd")
+        check(lib.cvae_bottleneck_fwd(C_.byref(dims), C_.byref(pstruct), ptr(y_cl), ptr(m), ptr(t_onehot), ptr(t_labels), ptr(eps), ptr(rm), ptr(rv), ptr(nbt), float(momentum),
+                                      float(bn_eps), 1, ptr(xcat), ptr(partial), ptr(dzm_acc), C_.byref(sstruct), ptr(dec_cl), L.dtype_code(y_cl.dtype), ptr(rank_stats), ranks,
+                                      nstruct, stream()), "bottleneck_fwd")
         ctx.dims, ctx.scratch = dims, n_dx
         ctx.sync = None if sync is None else (sync[0], ranks)
         ctx.save_for_backward(y_cl, t_onehot, eps, xcat, *params, *[saved[k] for k in L.BOTTLENECK_SAVED], dzm_acc)
@@ -1717,9 +1694,9 @@ class BioBottleneck(torch.autograd.Function):
         bn_dy = bn_sums = None
         if ctx.sync is not None:
             bn_dy, bn_sums = torch.empty(dims.M, dims.HM, dtype=f32, device=dev), torch.empty(2, dims.HM, dtype=f32, device=dev)
-        check(lib.cvae_bottleneck_bwd_sync(C_.byref(dims), C_.byref(pstruct), C_.byref(gstruct), C_.byref(sstruct), ptr(g_dec), ptr(g_mu), ptr(g_logvar), ptr(g_mhat),
-                                           ptr(t_onehot), ptr(eps), ptr(xcat), ptr(y_cl), 1, ptr(dzm_part), ptr(g1), ptr(dx_part), ptr(dy_cl),
-                                           L.dtype_code(y_cl.dtype), ptr(bn_dy), ptr(bn_sums), stream()), "bottleneck_bwd")
+        check(lib.cvae_bottleneck_bwd(C_.byref(dims), C_.byref(pstruct), C_.byref(gstruct), C_.byref(sstruct), ptr(g_dec), ptr(g_mu), ptr(g_logvar), ptr(g_mhat),
+                                      ptr(t_onehot), ptr(eps), ptr(xcat), ptr(y_cl), 1, ptr(dzm_part), ptr(g1), ptr(dx_part), ptr(dy_cl),
+                                      L.dtype_code(y_cl.dtype), ptr(bn_dy), ptr(bn_sums), stream()), "bottleneck_bwd")
         if ctx.sync is not None:
             group, ranks = ctx.sync
             _all_reduce_sum(bn_sums, group)                  # 2 * HM floats: sum(dy), sum(dy * xhat) over the global batch

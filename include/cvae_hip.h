@@ -66,8 +66,6 @@ const char* cvae_strerror(int code);
 int cvae_ncs_to_nsc(const void* src, void* dst, int64_t B, int64_t C, int64_t S, int src_dtype, int dst_dtype, void* stream);
 int cvae_nsc_to_ncs(const void* src, void* dst, int64_t B, int64_t C, int64_t S, int src_dtype, int dst_dtype, void* stream);
 int cvae_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);
-/* dst[b, col0 + j] = src[b, j] for j < cols (fp32): writes one panel of a concatenated [B, dst_stride] matrix. */
-int cvae_copy_panel(const float* src, float* dst, int64_t B, int64_t cols, int64_t src_stride, int64_t dst_stride, int64_t col0, void* stream);
 /* Up to 8 panels in one launch (host arrays of device pointers / widths / row strides): gather == 0: wide[b][col0 + off_i + j] = panels[i][b * strides[i] + j]
  * with off_i = widths[0] + .. + widths[i-1] (torch.cat(dim=1)); gather != 0: the reverse copy (the column ranges of `wide` out into the panels: cat's backward). */
 int cvae_copy_panels(float* const* panels, const int64_t* widths, const int64_t* strides, int count, float* wide, int64_t B, int64_t wide_stride, int64_t col0,
@@ -80,15 +78,14 @@ int cvae_onehot_panel(const int64_t* t, float* dst, int64_t B, int64_t n_classes
  *   for_up == 0: [tap][Cl/16][Cs][16]   (down: N = Cs, K = (tap, cl))
  *   for_up == 1: [tap][Cs/16][Cl][16]   (up  : N = Cl, K = (tap, cs))
  * Not needed (pass the fp32 W itself as `w`) when Cl == 1. */
-size_t cvae_conv_packed_weight_bytes(int64_t Cs, int64_t Cl, int nd, int dtype);
 int cvae_conv_pack_weight(const float* w, void* packed, int64_t Cs, int64_t Cl, int nd, int for_up, int dtype, void* stream);
 
-/* The same packing for a LIST of weights in one launch (host arrays of `count` entries; all tensors share nd and dtype). */
-int cvae_conv_pack_weights(const float* const* w, void* const* packed, const int64_t* Cs, const int64_t* Cl, const int* for_up,
-                           int count, int nd, int dtype, void* stream);
-
-/* Both packings (for_up = 0 and 1) of a LIST of weights in one launch through an LDS transpose (Cs and Cl multiples of 16). */
+/* Both packings (for_up = 0 and 1) of a LIST of weights in one launch through an LDS transpose (Cs and Cl multiples of 16).
+ * For a training step with fp8 forward products: f8dir[i] = 1 / 2 writes the `down` / `up` panel of weight i as fp8 codes of w * *inv_scale_dev[i] into
+ * f8out[i] (layout of cvae_conv_pack_weight_fp8) INSTEAD of its bf16 panel (packed_down[i] / packed_up[i] may then be NULL), and records max |w| in
+ * amax_slots[i] (optional); f8dir[i] = 0 (or f8dir == NULL, f8out / inv_scale_dev / amax_slots then unused): both bf16 / fp32 panels. */
 int cvae_conv_pack_weight_pairs(const float* const* w, void* const* packed_down, void* const* packed_up, const int64_t* Cs, const int64_t* Cl,
+                                const int* f8dir, void* const* f8out, const float* const* inv_scale_dev, void* const* amax_slots,
                                 int count, int nd, int dtype, void* stream);
 
 /* Optional scratch for cvae_conv_down (for_up = 0) / cvae_conv_up (for_up = 1): layers whose output grid is too small to fill
@@ -96,30 +93,31 @@ int cvae_conv_pack_weight_pairs(const float* const* w, void* const* packed_down,
  * Returns 0 when the launch needs none.  Passing NULL / a smaller buffer is always valid: the launch then runs unsplit. */
 size_t cvae_conv_data_workspace_bytes(int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
                                       int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int for_up);
-/* S = act(gather(L, w) + bias) [then * (mask > 0) if mask != NULL].  bias fp32 [Cs] or NULL; mask has S's shape/dtype. */
-int cvae_conv_down(const void* L, const void* w, const float* bias, const void* mask, void* S,
-                   int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                   int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                   void* workspace, size_t workspace_bytes, void* stream);
-/* L = act(scatter(S, w) + bias) [then * (mask > 0) if mask != NULL].  bias fp32 [Cl] or NULL; mask has L's shape/dtype. */
-int cvae_conv_up(const void* S, const void* w, const float* bias, const void* mask, void* L,
-                 int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                 int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                 void* workspace, size_t workspace_bytes, void* stream);
-/* ReLU masks as BITS.  The backward-data launch of a layer whose input was a ReLU output zeroes its result where that activation was not positive
- * (`mask` above = the saved activation, read in full: 67 MB for enc_conv[2]'s backward at 4 x 128^3).  In the bit form the PRODUCING forward launch leaves
+/* cvae_conv_down: S = act(gather(L, w) + bias) [then * (mask > 0) if mask != NULL].  bias fp32 [Cs] or NULL; mask has S's shape/dtype.
+ * cvae_conv_up:   L = act(scatter(S, w) + bias) [then * (mask > 0) if mask != NULL].  bias fp32 [Cl] or NULL; mask has L's shape/dtype.
+ * ReLU masks as BITS.  The backward-data launch of a layer whose input was a ReLU output zeroes its result where that activation was not positive
+ * (`mask` = the saved activation, read in full: 67 MB for enc_conv[2]'s backward at 4 x 128^3).  In the bit form the PRODUCING forward launch leaves
  * one bit per element of its result — dword i covers elements 32 i .. 32 i + 31 in memory order (a position's 32-channel block; channel counts % 32 == 0),
  * bit set <=> element > 0 — and the backward launch reads those (1/16 of the bf16 bytes).
- *   relu_bits_out (optional): numel / 32 dwords that receive the mask of THIS launch's result;  mask_bits (optional): the mask to apply (replaces `mask`).
- * Same arithmetic as cvae_conv_down / cvae_conv_up otherwise. */
-int cvae_conv_down_bits(const void* L, const void* w, const float* bias, const void* mask_bits, void* S, void* relu_bits_out,
-                        int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                        int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                        void* workspace, size_t workspace_bytes, void* stream);
-int cvae_conv_up_bits(const void* S, const void* w, const float* bias, const void* mask_bits, void* L, void* relu_bits_out,
-                      int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                      int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                      void* workspace, size_t workspace_bytes, void* stream);
+ *   relu_bits_out (optional): numel / 32 dwords that receive the mask of THIS launch's result;  mask_bits (optional): the mask to apply, in place of
+ *                 `mask` (passing both is CVAE_E_BADSHAPE).  Either bit pointer needs the result's channel count % 32 == 0 and, in `up`, Cl > 1;
+ *                 `down` with Cl == 1 reads mask_bits in bf16 only (CVAE_E_UNSUPPORTED otherwise).
+ * Kernel forms, chosen by launch size unless the CALLER forces one for this call (the library keeps no process-wide tuning state).  Every form computes
+ * the same products in the same order (bit-identical results; the tests run each narrow case through both):
+ *   xpair         -1 automatic; 0 / 1: one sample per tile / two side by side — layers at most half a tile wide: 2D grids up to 8 wide (the 7 x 7 maps
+ *                 of the MNIST model; automatic from 512 workgroups up) and, in `up`, 3D layers at most 4 source voxels wide (the decoder's 4^3 input;
+ *                 automatic from 2048 workgroups up);
+ *   upfull        -1 automatic; 0 / 1: never / whenever it fits — the whole-K `up` kernel (bf16, 64 / 128 / 256 input channels, 32 output channels).
+ *                 It has no bit form: with mask_bits or relu_bits_out the launch takes the bit form and upfull has no effect;
+ *   c1_walk_units  0 automatic; > 0: the single-channel output layer (bf16, 3D) walks z columns when the launch has at least 2 x this many tiles. */
+int cvae_conv_down(const void* L, const void* w, const float* bias, const void* mask, const void* mask_bits, void* S, void* relu_bits_out,
+                   int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
+                   int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
+                   void* workspace, size_t workspace_bytes, int xpair, void* stream);
+int cvae_conv_up(const void* S, const void* w, const float* bias, const void* mask, const void* mask_bits, void* L, void* relu_bits_out,
+                 int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
+                 int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
+                 void* workspace, size_t workspace_bytes, int upfull, int xpair, int64_t c1_walk_units, void* stream);
 /* The first conv of the encoder (Cl == 1) with the IMAGE read in the dtype it is stored in (l_dtype) while S is written in the compute
  * dtype (`dtype`): the fp32 input volume of a bf16 model feeds the kernels directly — no cast pass, no bf16 copy of the batch
  * (causal_cascade/models.py:13: nn.Conv2d(img_channels, 32, 4, 2, 1) on the fp32 batch).  cvae_conv_down_image = cvae_conv_down with
@@ -137,8 +135,8 @@ int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, float* dW, 
  * A tensor x is held as fp8 codes q with a per-tensor scale s kept by the caller: x ~ s * q.  Products accumulate in fp32 on the block-scaled
  * CDNA4 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, unit block scales): twice the bf16 FLOPs per clock.  Channel counts: C_in % 32 == 0,
  * C_out % 64 == 0 (conv) / C_out % 32 == 0, C_out > 1 (ConvTranspose).
- *   cvae_quantize_fp8           dst[i] = fp8(src[i] * inv_scale)               (src fp32 or bf16; saturating)
- *   cvae_quantize_fp8_dev       the same with 1 / s read from DEVICE memory; amax_slots (optional): records max |src| (see below)
+ *   cvae_quantize_fp8           dst[i] = fp8(src[i] * inv_scale)               (src fp32 or bf16; saturating); inv_scale_dev (optional): 1 / s read from
+ *                               DEVICE memory instead of the by-value inv_scale; amax_slots (optional): records max |src| (see below)
  *   cvae_absmax                 max |src| into amax_slots (calibration of the first step)
  *   cvae_conv_pack_weight_fp8   fp32 [Cs][Cl][taps] -> operand panels [tap][C_in / 32][C_out][32] of fp8(w * inv_scale)
  *   cvae_conv_pack_weights_fp8  the same for a list of layers in one launch, 1 / s_w read from device memory, max |w| recorded
@@ -147,9 +145,8 @@ int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, float* dW, 
  *                               the next fp8 layer; out_dtype CVAE_FP8: `out` holds the codes only.  dscale (optional, device): {acc_scale,
  *                               out8_inv_scale} read at run time instead of the two by-value arguments (delayed scaling under graph replay).
  *                               amax_slots (optional): records max |out|.  workspace: cvae_conv_data_workspace_bytes of the same geometry (split-K
- *                               of the small `down` grids; NULL = unsplit).  xpair: as in cvae_conv_up_variant (-1 = automatic).  relu_bits_out
- *                               (optional): the ReLU mask of `out` as bits (cvae_conv_down_bits).
- *   cvae_conv_up_fp8            = cvae_conv_fp8(up = 1) with by-value scales and no side outputs (round-2 entry point, kept)
+ *                               of the small `down` grids; NULL = unsplit).  xpair: as in cvae_conv_down / cvae_conv_up (-1 = automatic).  relu_bits_out
+ *                               (optional): the ReLU mask of `out` as bits (as in cvae_conv_down / cvae_conv_up).
  *   cvae_fp8_scale_update       once per step: for each of n tracked tensors, scale[i] = headroom * amax_i / 448 (amax_i = the largest value
  *                               recorded in its CVAE_AMAX_SLOTS words since the last call; the words are cleared; nothing recorded = scale kept),
  *                               inv_scale[i] = 1 / scale[i]; then for each fp8 layer l: dscale[2l] = scale[layer_in[l]] * scale[layer_w[l]],
@@ -158,8 +155,7 @@ int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, float* dW, 
  * An amax record is CVAE_AMAX_SLOTS unsigned words holding float bits (non-negative floats order like unsigned integers; atomicMax, so the
  * result does not depend on the order of arrival; one word per workgroup of the producing launch, modulo the slot count); the caller zero-fills it once. */
 #define CVAE_AMAX_SLOTS 4096
-int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int64_t n, float inv_scale, void* stream);
-int cvae_quantize_fp8_dev(const void* src, int src_dtype, void* dst, int64_t n, const float* inv_scale_dev, void* amax_slots, void* stream);
+int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int64_t n, float inv_scale, const float* inv_scale_dev, void* amax_slots, void* stream);
 int cvae_absmax(const void* src, int dtype, int64_t n, void* amax_slots, void* stream);
 int cvae_conv_pack_weight_fp8(const float* w, void* packed, int64_t Cs, int64_t Cl, int nd, int for_up, float inv_scale, void* stream);
 int cvae_conv_pack_weights_fp8(const float* const* w, void* const* packed, const int64_t* Cs, const int64_t* Cl, const int* for_up,
@@ -167,28 +163,19 @@ int cvae_conv_pack_weights_fp8(const float* const* w, void* const* packed, const
 int cvae_conv_fp8(int up, const void* in8, const void* w8, const float* bias, void* out, int out_dtype, void* out8, const float* dscale, float acc_scale,
                   float out8_inv_scale, void* amax_slots, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int64_t Cl,
                   int nd, int act, void* workspace, size_t workspace_bytes, int xpair, void* relu_bits_out, void* stream);
-int cvae_conv_up_fp8(const void* S, const void* w, const float* bias, void* L, int out_dtype, float acc_scale, float out_inv_scale,
-                     int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int act,
-                     void* stream);
 /* The decode sweep's last layer fed by the fp8 layer before it: nn.ConvTranspose3d(32, 1, 4, 2, 1) (causal_cascade/models.py:54 lifted to 3D) of S8 [B][sd][sh][sw][32] e4m3
- * codes (activation / in_scale, e.g. the codes cvae_conv_up_fp8 leaves with out_dtype CVAE_FP8), fp32 master weight w [32][1][64] and bias as they are: L [B][2sd][2sh][2sw][1] bf16 =
+ * codes (activation / in_scale, e.g. the codes cvae_conv_fp8 leaves with out_dtype CVAE_FP8), fp32 master weight w [32][1][64] and bias as they are: L [B][2sd][2sh][2sw][1] bf16 =
  * act(in_scale * (S8 (*) w) + bias).  The 32-channel tensor between the last two layers travels at one byte per element and is never widened in memory.  3D, Cs == 32 only. */
 int cvae_conv_up_c1_fp8in(const void* S8, const float* w, const float* bias, void* L, float in_scale, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int nd, int act,
                           void* stream);
 /* cvae_conv_down_image with bf16 S and the fp8 side channel of a training forward whose next conv runs on fp8 operands: S8 (optional) = fp8(S * *inv_scale_dev),
- * amax_slots (optional) records max |S|, relu_bits_out (optional) receives the ReLU mask of S as bits (cvae_conv_down_bits; this entry point also serves a
+ * amax_slots (optional) records max |S|, relu_bits_out (optional) receives the ReLU mask of S as bits (as in cvae_conv_down; this entry point also serves a
  * bf16 step that only wants the bits: S8 = NULL).  Needs the 16-byte-row form (cvae_conv_image_supported). */
 int cvae_conv_down_image_f8(const void* L, int l_dtype, const float* w, const float* bias, void* S, void* S8, const float* inv_scale_dev, void* amax_slots,
                             void* relu_bits_out, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int act,
                             void* stream);
 int cvae_fp8_scale_update(void* amax_slots, float* scale, float* inv_scale, int n, float headroom, const int* layer_in, const int* layer_w, const int* layer_out,
                           int n_layers, float* dscale, void* ticket, void* stream);
-/* cvae_conv_pack_weight_pairs for a training step with fp8 forward products: f8dir[i] = 1 / 2 writes the `down` / `up` panel of weight i as fp8 codes of
- * w * *inv_scale_dev[i] into f8out[i] (layout of cvae_conv_pack_weight_fp8) INSTEAD of its bf16 panel (packed_down[i] / packed_up[i] may then be NULL), and
- * records max |w| in amax_slots[i] (optional); f8dir[i] = 0 (or f8dir == NULL): both bf16 / fp32 panels as cvae_conv_pack_weight_pairs. */
-int cvae_conv_pack_weight_pairs_f8(const float* const* w, void* const* packed_down, void* const* packed_up, const int64_t* Cs, const int64_t* Cl,
-                                   const int* f8dir, void* const* f8out, const float* const* inv_scale_dev, void* const* amax_slots,
-                                   int count, int nd, int dtype, void* stream);
 /* ---- Exact-2x linear resize (decoder output d x h x w, one channel -> 2d x 2h x 2w; D == d == 1 for 2D) fused with the ELBO ----
  * causal_cascade/models.py:84-87 + train.py:5-17: the resized volume is recomputed from the small tensor wherever it is needed
  * instead of being written and re-read (csrc/recon_loss.hip).  cvae_up2x_supported: 1 when the shapes qualify (w % 4 == 0). */
@@ -262,18 +249,23 @@ int cvae_bottleneck_sizes(const cvae_bottleneck_dims* dims, int64_t* K1, int64_t
  * model's outputs) and dec_cl [M][OD][OH][OW][C] (conv dtype) = dec_input(cat(z, m_hat)) viewed [M, C, 4..] channels-last.
  * dzm_acc: scratch of dzm_partial_floats (cvae_bottleneck_sizes) the BACKWARD fills with per-workgroup partials of d(zm) (one slot per
  * workgroup, plain stores, summed in index order: no float atomics); the forward does not touch it (kept in the signature so one
- * buffer can serve the pair). */
+ * buffer can serve the pair).  bn_rank_stats (optional): mechanism_net's BatchNorm1d over the global batch of bn_ranks ranks (SyncBatchNorm, below).
+ * noise (optional): the reparameterisation noise drawn by the first launch: eps [M][Z] becomes an OUTPUT holding exactly the numbers
+ * cvae_philox_normal_advance(eps, M * Z, seed, 0, subsequence, call_counter) would have written, and *call_counter is incremented the same way (one
+ * launch fewer per step; the reference draws torch.randn_like in reparameterize, causal_cascade/models.py:65-68). */
+typedef struct { uint64_t seed, subsequence; int* call_counter; } cvae_bottleneck_noise;
 int cvae_bottleneck_fwd(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const void* y_cl, const float* m, float* t_onehot,
-                        const int64_t* t_labels, const float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float bn_eps,
-                        int bn_training, float* xcat, float* fwd_partial, float* dzm_acc, const cvae_bottleneck_saved* saved, void* dec_cl, int dtype,
-                        void* stream);
+                        const int64_t* t_labels, float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
+                        float bn_eps, int bn_training, float* xcat, float* fwd_partial, float* dzm_acc, const cvae_bottleneck_saved* saved, void* dec_cl, int dtype,
+                        const float* bn_rank_stats, int bn_ranks, const cvae_bottleneck_noise* noise, void* stream);
 /* Backward (training-mode BatchNorm only).  g_dec_cl: gradient of dec_cl; g_mu / g_logvar / g_mhat: gradients arriving at the
  * three outputs (NULL = zero).  Writes every parameter gradient and dy_cl, the gradient of y_cl (zeroed where y_cl <= 0 when
- * relu_mask).  g1 is scratch of M*(N1+N2) floats; dzm_partial: dzm_partial_floats of scratch (any contents on entry). */
+ * relu_mask).  g1 is scratch of M*(N1+N2) floats; dzm_partial: dzm_partial_floats of scratch (any contents on entry).
+ * bn_dy / bn_local_sums (both or neither): SyncBatchNorm, below. */
 int cvae_bottleneck_bwd(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const cvae_bottleneck_grads* grads,
                         const cvae_bottleneck_saved* saved, const void* g_dec_cl, const float* g_mu, const float* g_logvar, const float* g_mhat,
                         const float* t_onehot, const float* eps, const float* xcat, const void* y_cl, int relu_mask, float* dzm_partial, float* g1,
-                        float* dx_partial, void* dy_cl, int dtype, void* stream);
+                        float* dx_partial, void* dy_cl, int dtype, float* bn_dy, float* bn_local_sums, void* stream);
 
 /* ---- The same pair with mechanism_net's BatchNorm1d normalising over the GLOBAL batch of `bn_ranks` data-parallel ranks (SyncBatchNorm; replaces what
  * nn.SyncBatchNorm.convert_sync_batchnorm does to causal_cascade/models.py:36 under DDP).  The library runs no collective itself; the caller moves
@@ -281,30 +273,13 @@ int cvae_bottleneck_bwd(const cvae_bottleneck_dims* dims, const cvae_bottleneck_
  *   1. cvae_bottleneck_bn_local_stats: local_stats [2][HM] = this rank's (sum, squared deviations from its own mean) of mechanism_net.0's output
  *      (it depends on t only, so it can run — and the all-gather can travel — before the encoder).  Wm0 [HM][t_dim], bm0 [HM]; t_onehot [M][t_dim] or t_labels [M]
  *      (either may be NULL);
- *   2. all-gather -> bn_rank_stats [bn_ranks][2][HM]; cvae_bottleneck_fwd_sync combines them in rank order (Chan's update: identical bits on every rank),
- *      normalises with the global mean / variance and updates the running statistics with the global unbiased variance.  bn_rank_stats NULL: cvae_bottleneck_fwd;
- *   3. cvae_bottleneck_bwd_sync: as cvae_bottleneck_bwd, but mechanism_net's backward stops at the BatchNorm: bn_dy [M][HM] = the masked gradient at its output,
+ *   2. all-gather -> bn_rank_stats [bn_ranks][2][HM]; cvae_bottleneck_fwd combines them in rank order (Chan's update: identical bits on every rank),
+ *      normalises with the global mean / variance and updates the running statistics with the global unbiased variance;
+ *   3. cvae_bottleneck_bwd with bn_dy / bn_local_sums: mechanism_net's backward stops at the BatchNorm: bn_dy [M][HM] = the masked gradient at its output,
  *      bn_local_sums [2][HM] = this rank's (sum dy, sum dy * xhat) (also written to dbeta / dgamma: the rank's share, summed by the gradient exchange);
- *      both NULL: cvae_bottleneck_bwd;
  *   4. all-reduce (sum) of bn_local_sums -> bn_sums; cvae_bottleneck_bn_bwd_finish writes dWm0 / dbm0 from bn_dy and the global sums (one small launch). */
 int cvae_bottleneck_bn_local_stats(const float* Wm0, const float* bm0, const float* t_onehot, const int64_t* t_labels, float* local_stats, int64_t M, int64_t t_dim,
                                    int64_t HM, void* stream);
-int cvae_bottleneck_fwd_sync(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const void* y_cl, const float* m, float* t_onehot,
-                             const int64_t* t_labels, const float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
-                             float bn_eps, int bn_training, float* xcat, float* fwd_partial, float* dzm_acc, const cvae_bottleneck_saved* saved, void* dec_cl, int dtype,
-                             const float* bn_rank_stats, int bn_ranks, void* stream);
-/* The general forward: as cvae_bottleneck_fwd_sync, plus (noise != NULL) the reparameterisation noise drawn by the first launch: eps [M][Z] becomes an OUTPUT
- * holding exactly the numbers cvae_philox_normal_advance(eps, M * Z, seed, 0, subsequence, call_counter) would have written, and *call_counter is incremented
- * the same way (one launch fewer per step; the reference draws torch.randn_like in reparameterize, causal_cascade/models.py:65-68). */
-typedef struct { uint64_t seed, subsequence; int* call_counter; } cvae_bottleneck_noise;
-int cvae_bottleneck_fwd_ex(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const void* y_cl, const float* m, float* t_onehot,
-                           const int64_t* t_labels, float* eps, float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
-                           float bn_eps, int bn_training, float* xcat, float* fwd_partial, float* dzm_acc, const cvae_bottleneck_saved* saved, void* dec_cl, int dtype,
-                           const float* bn_rank_stats, int bn_ranks, const cvae_bottleneck_noise* noise, void* stream);
-int cvae_bottleneck_bwd_sync(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const cvae_bottleneck_grads* grads,
-                             const cvae_bottleneck_saved* saved, const void* g_dec_cl, const float* g_mu, const float* g_logvar, const float* g_mhat,
-                             const float* t_onehot, const float* eps, const float* xcat, const void* y_cl, int relu_mask, float* dzm_partial, float* g1,
-                             float* dx_partial, void* dy_cl, int dtype, float* bn_dy, float* bn_local_sums, void* stream);
 int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* dims, const cvae_bottleneck_params* params, const cvae_bottleneck_grads* grads,
                                   const cvae_bottleneck_saved* saved, const float* t_onehot, const float* bn_dy, const float* bn_sums, int bn_ranks, void* stream);
 
@@ -353,18 +328,25 @@ int cvae_upsample_linear_bwd(const float* ddst, void* dsrc, int64_t B, int64_t d
 /* ---- fp32 linear layers ------------------------------------------------------------------------------ */
 /* Long reductions over few output tiles (the 16415-wide encoder layer at batch 4) are split across workgroups; each split leaves its
  * partial tile in a slab of `workspace` (cvae_linear_workspace_bytes(M, K, N, op); op 0 = fwd, 1 = bwd_data, 2 = bwd_weight) and a finish
- * launch adds the slabs in index order — no float atomics.  workspace may be NULL / smaller: the product then runs unsplit. */
+ * launch adds the slabs in index order — no float atomics.  workspace may be NULL / smaller: the product then runs unsplit.
+ * bf16_math != 0: bf16 MFMA operands (fp32 tensors in memory, rounded to bf16 on the way into LDS, fp32 accumulate and output): 16x the matrix rate of
+ * the exact-fp32 form, relative error ~2^-9 per operand.  M > 16 only (smaller batches are HBM-bound skinny kernels: CVAE_E_UNSUPPORTED). */
 size_t cvae_linear_workspace_bytes(int64_t M, int64_t K, int64_t N, int op);
 /* y[M, N] = act(x[M, K] @ W[N, K]^T + b). */
 int cvae_linear_fwd(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N,
-                    int64_t x_stride, int64_t y_stride, int act, void* workspace, size_t workspace_bytes, void* stream);
-/* dx[M, K] = g[M, N] @ W[N, K] with g = dy * act'(y_act) (y_act = the layer's saved OUTPUT, same shape/stride as dy; pass
- * NULL / CVAE_ACT_NONE for g = dy).  The fused activation gradient is available for M <= 16 (the model's batch sizes). */
-int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N,
-                         int64_t dy_stride, int64_t dx_stride, const float* y_act, int act, void* workspace, size_t workspace_bytes, void* stream);
+                    int64_t x_stride, int64_t y_stride, int act, int bf16_math, void* workspace, size_t workspace_bytes, void* stream);
+/* dx[M, K] = (g[M, N] @ W[N, K]) * in_act'(x_in) with g = dy * act'(y_act) (y_act = the layer's saved OUTPUT, same shape/stride as dy; pass
+ * NULL / CVAE_ACT_NONE for g = dy).  The fused activation gradient is available for M <= 16 (the model's batch sizes; CVAE_E_UNSUPPORTED above).
+ * x_in [M][K] (row stride x_stride) / in_act: the derivative of the activation that produced this layer's INPUT (taken from its output, i.e. from x_in:
+ * ReLU / LeakyReLU / Sigmoid) applied in the GEMM's epilogue (or its split-K slab sum) — in an MLP the previous layer then needs no activation-gradient
+ * pass of its own (causal_cascade/models.py:24-31's Linear-ReLU-Linear chains).  M > 16 only (CVAE_E_UNSUPPORTED below); NULL / CVAE_ACT_NONE: none. */
+int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
+                         const float* y_act, int act, const float* x_in, int64_t x_stride, int in_act, int bf16_math,
+                         void* workspace, size_t workspace_bytes, void* stream);
 /* dW[N, K] = g^T x ; db[N] = column sums of g (db may be NULL).  Both overwritten.  g as above. */
 int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW, float* db, int64_t M, int64_t K, int64_t N,
-                           int64_t dy_stride, int64_t x_stride, const float* y_act, int act, void* workspace, size_t workspace_bytes, void* stream);
+                           int64_t dy_stride, int64_t x_stride, const float* y_act, int act, int bf16_math, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---- BatchNorm1d --------------------------------------------------------------------------------------- */
 /* train: batch statistics (biased var) normalise; running stats updated with momentum (unbiased var). B >= 2. */
@@ -440,13 +422,6 @@ int cvae_softmax_ce_bwd(const float* logits, const int64_t* target, const float*
 int cvae_uniform_kl_fwd(const float* logits, float* out, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
 int cvae_uniform_kl_bwd(const float* logits, const float* gout, float* dlogits, int64_t B, int64_t C, void* stream);
 
-/* The same three products with bf16 MFMA operands (fp32 tensors in memory, rounded to bf16 on the way into LDS, fp32 accumulate and output):
- * 16x the matrix rate of the exact-fp32 form, relative error ~2^-9 per operand.  M > 16 only (smaller batches are HBM-bound skinny kernels:
- * CVAE_E_UNSUPPORTED); no fused activation gradient; workspace as for the fp32 entry points (cvae_linear_workspace_bytes). */
-int cvae_linear_fwd_bf16(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N, int64_t x_stride, int64_t y_stride,
-                         int act, void* workspace, size_t workspace_bytes, void* stream);
-int cvae_linear_bwd_data_bf16(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
-                              void* workspace, size_t workspace_bytes, void* stream);
 /* ---- nn.Linear (+ activation) for SMALL layers at LARGE batch (csrc/small_dense.hip): M > 16 rows, K, N <= 512 and N * K <= 12288 weights — the MLP heads of
  * mnist_test/01_baseline_causal_vae/models.py:24-37, 93-111 at batch 1024.  The weight lives in LDS; one launch forward, one for the data gradient, two for the
  * weight + bias gradient (per-workgroup partials in `workspace`, summed in index order: no atomics).  fp32 throughout.
@@ -460,31 +435,6 @@ int cvae_small_dense_bwd_data(const float* dy, const float* W, float* dx, const 
                               int64_t dy_stride, int64_t dx_stride, int64_t y_stride, int64_t x_stride, void* stream);
 int cvae_small_dense_bwd_weight(const float* dy, const float* x, float* dW, float* db, const float* y_act, int act, int64_t M, int64_t K, int64_t N, int64_t dy_stride,
                                 int64_t x_stride, int64_t y_stride, void* workspace, size_t workspace_bytes, void* stream);
-
-/* dx = (dy . W) * act'(x_in): cvae_linear_bwd_data(_bf16) with the derivative of the activation that produced this layer's INPUT x_in [M][K] (taken from its output,
- * i.e. from x_in: ReLU / LeakyReLU / Sigmoid) applied in the GEMM's epilogue (or its split-K slab sum) — in an MLP the previous layer then needs no activation-gradient
- * pass of its own (causal_cascade/models.py:24-31's Linear-ReLU-Linear chains; one launch fewer per layer at batch sizes above 16).  bf16_math as cvae_linear_*_bf16. */
-int cvae_linear_bwd_data_inact(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
-                               const float* x_in, int64_t x_stride, int in_act, int bf16_math, void* workspace, size_t workspace_bytes, void* stream);
-int cvae_linear_bwd_weight_bf16(const float* dy, const float* x, float* dW, float* db, int64_t M, int64_t K, int64_t N, int64_t dy_stride,
-                                int64_t x_stride, void* workspace, size_t workspace_bytes, void* stream);
-
-/* cvae_conv_down with the two-samples-per-tile form (layers at most half a tile wide: 2D grids up to 8 wide — the 7 x 7 maps of the MNIST model —, used
- * automatically from 512 workgroups up) forced off (0) / on (1) for this call, -1 = automatic.  Same products in the same order: bit-identical results. */
-int cvae_conv_down_variant(const void* L, const void* w, const float* bias, const void* mask, void* S,
-                           int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                           int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                           void* workspace, size_t workspace_bytes, int xpair, void* stream);
-/* cvae_conv_up with the kernel form chosen by the CALLER for this one call instead of by launch size (the library keeps no process-wide tuning state):
- *   upfull        -1 automatic; 0 / 1: never / whenever it fits — the whole-K `up` kernel (bf16, 64 / 128 / 256 input channels, 32 output channels);
- *   xpair         -1 automatic; 0 / 1: one sample per tile / two side by side — 3D layers at most 4 source voxels wide (the decoder's 4^3 input), 2D layers
- *                 at most 8 wide (automatic from 2048 / 512 workgroups up);
- *   c1_walk_units  0 automatic; > 0: the single-channel output layer (bf16, 3D) walks z columns when the launch has at least 2 x this many tiles.
- * Every form computes the same products in the same order (bit-identical results; the tests run each narrow case through both). */
-int cvae_conv_up_variant(const void* S, const void* w, const float* bias, const void* mask, void* L,
-                         int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
-                         int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
-                         void* workspace, size_t workspace_bytes, int upfull, int xpair, int64_t c1_walk_units, void* stream);
 
 /* ---- optimiser ---------------------------------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay / amsgrad) on flat fp32 buffers; bias corrections bc1 = 1-b1^t, bc2 = 1-b2^t

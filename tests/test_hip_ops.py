@@ -76,7 +76,7 @@ def split_k(request):
     threshold of the whole-K `up` kernel to 0, so the narrow bf16 cases (64 -> 32 channels) run through conv_up_full_kernel there and through
     conv_data_kernel<UP> in the other arm."""
     old, ops.SPLIT_K = ops.SPLIT_K, request.param
-    prev, ops.UP_VARIANT = ops.UP_VARIANT, (None if request.param else (1, -1, 0))        # cvae_conv_up_variant(upfull = 1): per call, no library state
+    prev, ops.UP_VARIANT = ops.UP_VARIANT, (None if request.param else (1, -1, 0))        # cvae_conv_up(upfull = 1): per call, no library state
     yield request.param
     ops.SPLIT_K = old
     ops.UP_VARIANT = prev
@@ -230,7 +230,7 @@ def test_conv_up_c1_walking_z_columns_is_bit_identical(B, ssize, act):
     prev = ops.UP_VARIANT
     try:
         for name, units in [("none", 1 << 29), ("whole", 1), ("ragged", max(1, ntiles // 3)), ("pairs", max(1, ntiles // 2))]:
-            ops.UP_VARIANT = (-1, -1, units)                       # cvae_conv_up_variant(c1_walk_units)
+            ops.UP_VARIANT = (-1, -1, units)                       # cvae_conv_up(c1_walk_units)
             with torch.no_grad():
                 outs[name] = ops.ConvUp.apply(xg, wg, bg, 3, act, False, False).clone()
     finally:
@@ -263,7 +263,7 @@ def test_conv_up_two_samples_per_tile_is_bit_identical(B, Cs, Cl, ssize, act, ma
     prev = ops.UP_VARIANT
     try:
         for name, xp in [("single", 0), ("paired", 1)]:
-            ops.UP_VARIANT = (-1, xp, 0)                           # cvae_conv_up_variant(xpair)
+            ops.UP_VARIANT = (-1, xp, 0)                           # cvae_conv_up(xpair)
             outs[name] = ops._conv_up(xg, wp, bg, mg, Cl, 3, act).clone()
     finally:
         ops.UP_VARIANT = prev
@@ -303,7 +303,7 @@ def test_conv_2d_two_samples_per_tile_is_bit_identical(kind, B, Cbig, Csmall, ss
     prev_u, prev_d = ops.UP_VARIANT, ops.DOWN_VARIANT
     try:
         for name, xp in [("single", 0), ("paired", 1)]:
-            ops.UP_VARIANT, ops.DOWN_VARIANT = (0, xp, 0), xp       # cvae_conv_up_variant(xpair) / cvae_conv_down_variant(xpair)
+            ops.UP_VARIANT, ops.DOWN_VARIANT = (0, xp, 0), xp       # cvae_conv_up(xpair) / cvae_conv_down(xpair)
             outs[name] = (ops._conv_down(xg, wp, bg, mg, Csmall, 2, act) if kind == "down" else ops._conv_up(xg, wp, bg, mg, Cbig, 2, act)).clone()
     finally:
         ops.UP_VARIANT, ops.DOWN_VARIANT = prev_u, prev_d
@@ -343,7 +343,7 @@ def xpair(request):
 @pytest.mark.parametrize("nd,B,Cl,Cs,ssize,act,q_out", [(3, 2, 128, 256, (4, 4, 4), "relu", True), (3, 3, 64, 128, (8, 8, 8), "relu", False), (3, 1, 32, 64, (5, 6, 9), None, True),
                                                         (2, 2, 32, 64, (12, 20), "relu", False), (3, 3, 128, 256, (4, 4, 3), "relu", False)])
 def test_conv_up_fp8_matches_dequantised_reference(nd, B, Cl, Cs, ssize, act, q_out, xpair):
-    """cvae_conv_up_fp8 on fp8 codes == conv_transpose (fp32, CPU) of the DEQUANTISED operands: the kernel adds no error beyond the quantisation it is
+    """cvae_conv_fp8 (up = 1) on fp8 codes == conv_transpose (fp32, CPU) of the DEQUANTISED operands: the kernel adds no error beyond the quantisation it is
     given (fp32 accumulation; the result is rounded once to bf16, 2^-8, or to e4m3 codes, 2^-4 relative)."""
     g = torch.Generator().manual_seed(5)
     convT = F.conv_transpose2d if nd == 2 else F.conv_transpose3d
@@ -485,7 +485,7 @@ def test_fp8_scale_update_and_weight_pack_from_device_scales():
         assert torch.equal(out, ops.pack_weight_fp8(w, 3, for_up, sw))
         assert abs(float(st.amax[1].cpu().view(torch.float32).max()) - float(w.abs().max())) < 1e-7
         st.amax.zero_()
-        # the model's one weight-pack launch writes the same fp8 panel in place of the bf16 one of that direction (cvae_conv_pack_weight_pairs_f8)
+        # the model's one weight-pack launch writes the same fp8 panel in place of the bf16 one of that direction (cvae_conv_pack_weight_pairs with f8dir)
         panel = torch.zeros(w.numel(), dtype=torch.uint8, device=DEV)
         w2 = (torch.randn(128, 64, 4, 4, 4, generator=g) * 0.05).to(DEV)
         outs = ops.pack_weights([w, w2], 3, torch.bfloat16, f8spec={id(w): (2 if for_up else 1, panel, st.inv_scale[1:2], st.amax[1])})
@@ -513,7 +513,7 @@ def test_conv_up_fp8_bad_arguments_fail_loudly():
 @pytest.mark.parametrize("kind,nd,B,Cl,Cs,size", [("down", 3, 2, 32, 64, (16, 16, 16)), ("down", 3, 1, 128, 256, (8, 8, 8)), ("down", 2, 3, 32, 64, (30, 44)), ("down", 3, 2, 1, 32, (16, 24, 32)),
                                                     ("up", 3, 2, 64, 128, (16, 16, 16)), ("up", 3, 3, 128, 256, (8, 8, 8)), ("up", 3, 1, 32, 64, (10, 12, 18)), ("up", 2, 2, 32, 64, (24, 40))])
 def test_relu_masks_as_bits(kind, nd, B, Cl, Cs, size, dtype, split_k):
-    """cvae_conv_down_bits / cvae_conv_up_bits / cvae_conv_down_image_f8: the producing launch leaves its ReLU mask as bits (bit i of the flat result <=> result[i] > 0),
+    """cvae_conv_down / cvae_conv_up (relu_bits_out, mask_bits) / cvae_conv_down_image_f8: the producing launch leaves its ReLU mask as bits (bit i of the flat result <=> result[i] > 0),
     and a launch that applies a mask given as bits returns exactly what it returns for the same mask given as the saved activation."""
     g = torch.Generator().manual_seed(31)
     if kind == "down":
@@ -531,7 +531,7 @@ def test_relu_masks_as_bits(kind, nd, B, Cl, Cs, size, dtype, split_k):
         b = torch.randn(Cl, generator=g).to(DEV)
         wp = ops.pack_weight(w, nd, True, dtype)
         y, bits = ops._conv_up(x, wp, b, None, Cl, nd, "relu", want_bits=True)
-    if bits is None:                                               # the `unsplit` arm forces the whole-K `up` kernel (cvae_conv_up_variant), which has no bit form
+    if bits is None:                                               # the `unsplit` arm forces the whole-K `up` kernel (cvae_conv_up(upfull = 1)), which has no bit form
         assert kind == "up" and ops.UP_VARIANT is not None
         return
     assert bits.dtype == torch.int32 and bits.numel() * 32 == y.numel()
@@ -758,7 +758,7 @@ def test_linear_bf16_math_forward_backward(M, K, N, act):
                                                (1024, (3158, 512, 256, 24), ("relu", "relu", None), torch.bfloat16), (128, (64, 64, 10), ("relu", None), None)])
 def test_mlp_activation_gradient_in_the_next_layers_gemm_is_bit_identical(M, dims, acts, math_):
     """layers.MLP at batch sizes above 16: the data gradient of layer l + 1 leaves its GEMM already multiplied by act'(output of layer l)
-    (cvae_linear_bwd_data_inact: in the epilogue, or in the split-K slab sum) and layer l skips its activation-gradient launch.  The same fp32 products:
+    (cvae_linear_bwd_data(in_act): in the epilogue, or in the split-K slab sum) and layer l skips its activation-gradient launch.  The same fp32 products:
     every gradient is bit-identical to the layer-by-layer form, in the exact-fp32 and the bf16-operand GEMMs, split-K and whole-K, ragged tiles."""
     from causal_vae_amd import layers
     g = torch.Generator().manual_seed(31)

@@ -12,9 +12,9 @@ ws = [torch.empty(max(1, int(lib.cvae_linear_workspace_bytes(M, K, N, op)) // 4)
 st = torch.cuda.current_stream().cuda_stream
 p = L.ptr
 calls = {
-    "fwd": lambda: lib.cvae_linear_fwd_bf16(p(x), p(W), p(b), p(y), M, K, N, K, N, 0, p(ws[0]), ws[0].numel() * 4, st),
-    "bwd_data": lambda: lib.cvae_linear_bwd_data_bf16(p(g), p(W), p(dx), M, K, N, N, K, p(ws[1]), ws[1].numel() * 4, st),
-    "bwd_weight": lambda: lib.cvae_linear_bwd_weight_bf16(p(g), p(x), p(dW), p(db), M, K, N, N, K, p(ws[2]), ws[2].numel() * 4, st),
+    "fwd": lambda: lib.cvae_linear_fwd(p(x), p(W), p(b), p(y), M, K, N, K, N, 0, 1, p(ws[0]), ws[0].numel() * 4, st),
+    "bwd_data": lambda: lib.cvae_linear_bwd_data(p(g), p(W), p(dx), M, K, N, N, K, None, 0, None, K, 0, 1, p(ws[1]), ws[1].numel() * 4, st),
+    "bwd_weight": lambda: lib.cvae_linear_bwd_weight(p(g), p(x), p(dW), p(db), M, K, N, N, K, None, 0, 1, p(ws[2]), ws[2].numel() * 4, st),
 }
 for name, f in calls.items():
     for _ in range(5):
