@@ -124,6 +124,10 @@ SIGNATURES = {
     "cvae_bn2d_workspace_bytes": [_i64, _i64],
     "cvae_bn2d_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _i, _p, _sz, _p],
     "cvae_bn2d_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
+    "cvae_fold_bn_conv": [_i] + [_p] * 11 + [_p],
+    "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
+    "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
+    "cvae_stack_mean_std": [_p, _i, _p, _p, _i64, _p],
     "cvae_bottleneck_sizes": [_p, _p, _p, _p, _p, _p],
     "cvae_bottleneck_fwd": [_p] * 10 + [_f, _f, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p],
     "cvae_bottleneck_bwd": [_p] * 12 + [_i, _p, _p, _p, _p, _i, _p, _p, _p],
@@ -133,7 +137,7 @@ SIGNATURES = {
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
-            "cvae_small_dense_workspace_bytes": _sz}
+            "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

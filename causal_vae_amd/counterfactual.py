@@ -20,10 +20,23 @@ def sweep_inputs(z, m, features, values):
     return z_rep, m_cf.reshape(B * F * V, M).contiguous()
 
 
+def _decode_rows(model, z_rep, m_cf, size, fp8_plan, precision):
+    if getattr(type(model), "decode_signature", None) == "z_m":       # CausalVesselVAE.decode(z, m): explicit, never inferred from attributes
+        if size is not None or precision == "fp8":
+            raise ValueError(f"{type(model).__name__}: the sweep decodes at the model's native size, in fp32 or bf16 (no size, no fp8 plan)")
+        return model.decode(z_rep, m_cf)
+    if hasattr(model, "dec_input"):
+        return model.decode(z_rep, m_cf, size, fp8_plan=fp8_plan) if precision == "fp8" else model.decode(z_rep, m_cf, size)
+    return model.decode(m_cf, z_rep)
+
+
 @torch.no_grad()
-def batched_counterfactual(model, z, m, features, values, size=None, fp8_plan=None, precision=None):
-    """Decode every intervention do(m_f = v) in one call.  Works with CausalBioVAE / CausalBioVAE3D (decode(z, m, size)) and
-    CausalMorphVAE12 (decode(m, z)).  Returns [B, n_features, n_values, C, (D,) H, W].
+def batched_counterfactual(model, z, m, features, values, size=None, fp8_plan=None, precision=None, chunk_rows=None):
+    """Decode every intervention do(m_f = v) in one call.  Works with CausalBioVAE / CausalBioVAE3D (decode(z, m, size)),
+    CausalMorphVAE12 (decode(m, z)) and CausalVesselVAE (decode(z, m), eval mode: the BatchNorm-folded decoder).  Returns [B, n_features, n_values, C, (D,) H, W].
+
+    chunk_rows — decode the stacked rows in slices of at most this many (None: all at once).  The 768 x 1280 vessel decoder holds a
+    31 MB fp32 intermediate per row (384 x 640 x 32), so a sweep of hundreds of rows is decoded in slices into one output.
 
     precision — what the sweep is FOR decides it.  A sweep is read through differences decode(z, m') - decode(z, m); a low-precision decode
     carries an error of eps * |output| in every row, so the error relative to an effect of size f * |output| is eps / f
@@ -47,10 +60,18 @@ def batched_counterfactual(model, z, m, features, values, size=None, fp8_plan=No
     try:
         if want is not None and hasattr(model, "set_compute_dtype") and any(p_ != want for p_ in prev):
             model.set_compute_dtype(want)
-        if hasattr(model, "dec_input"):
-            out = model.decode(z_rep, m_cf, size, fp8_plan=fp8_plan) if precision == "fp8" else model.decode(z_rep, m_cf, size)
+        rows = z_rep.shape[0]
+        if chunk_rows is None or chunk_rows >= rows:
+            out = _decode_rows(model, z_rep, m_cf, size, fp8_plan, precision)
         else:
-            out = model.decode(m_cf, z_rep)
+            if int(chunk_rows) < 1:
+                raise ValueError(f"chunk_rows must be a positive row count, got {chunk_rows}")
+            out = None
+            for r0 in range(0, rows, int(chunk_rows)):
+                part = _decode_rows(model, z_rep[r0:r0 + chunk_rows], m_cf[r0:r0 + chunk_rows], size, fp8_plan, precision)
+                if out is None:
+                    out = torch.empty((rows,) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
+                out[r0:r0 + part.shape[0]].copy_(part)
     finally:
         if want is not None and hasattr(model, "set_compute_dtype") and prev and any(p_ != want for p_ in prev):
             model.set_compute_dtype(prev[0])

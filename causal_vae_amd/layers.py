@@ -374,6 +374,29 @@ class BNConvStack(nn.Sequential):
             raise CvaeError("BNConvStack: trailing Flatten expected")
         return ops.FromChannelsLast.apply(h, 2).flatten(1)
 
+    def forward_folded(self, x):
+        """Eval-mode forward with every BatchNorm2d folded into its conv: ONE cvae_fold_bn_conv launch for the stack, then each conv with the folded
+        weight and bias and LeakyReLU(0.2) in its epilogue — no BatchNorm pass.  Folded on every call (the fold is one launch; a cache could not see
+        the optimizer and bn2d_fwd rewrite parameters and running statistics through raw pointers).  Forward-only."""
+        require_gpu(x)
+        mods = list(self)
+        table, acts = [], []
+        for i in range(0, len(mods) - 1, 3):
+            conv, bn, act = mods[i], mods[i + 1], _act_of(mods[i + 2]) if i + 2 < len(mods) else None
+            if not isinstance(conv, Conv2d) or not isinstance(bn, BatchNorm2d) or act is None:
+                raise CvaeError("BNConvStack: Conv2d, BatchNorm2d, activation triples expected")
+            if bn.training or not bn.track_running_stats:
+                raise CvaeError("BNConvStack.forward_folded: eval-mode BatchNorm2d on running statistics only")
+            table.append((conv.weight, ops.FOLD_CONV_K4, conv.bias, bn))
+            acts.append(act)
+        if len(mods) != 3 * len(table) + 1 or not isinstance(mods[-1], nn.Flatten):
+            raise CvaeError("BNConvStack: trailing Flatten expected")
+        folded = ops.fold_bn_conv(table)
+        h, first_dtype = _image_cl(x, self.compute_dtype)
+        for j, ((w, b), act) in enumerate(zip(folded, acts)):
+            h = ops.ConvDown.apply(h, w, b, 2, act, False, False, None, first_dtype if j == 0 else None)
+        return ops.FromChannelsLast.apply(h, 2).flatten(1)
+
 
 class UpConvStack(nn.Sequential):
     """Decoder of CausalVesselVAE: [Upsample(x2, nearest), Conv2d(k3,s1,p1), BatchNorm2d, ReLU]* + Upsample, Conv2d(k3), Sigmoid.
@@ -400,6 +423,31 @@ class UpConvStack(nn.Sequential):
     def forward(self, h):
         require_gpu(h)
         return ops.FromChannelsLast.apply(self.forward_cl(h), 2)
+
+    def forward_folded(self, h):
+        """Eval-mode forward with every BatchNorm2d folded into its conv: ONE cvae_fold_bn_conv launch turns all seven k3 weights into folded
+        transposed k4 weights (the last, BatchNorm-free layer: the plain transform), then each Upsample + Conv2d pair runs as one ConvUp with ReLU /
+        Sigmoid in its epilogue — no BatchNorm pass, no Conv3ToK4 launch.  Folded on every call (see BNConvStack.forward_folded).  Forward-only."""
+        require_gpu(h)
+        mods = list(self)
+        table, acts, i = [], [], 0
+        while i < len(mods):
+            up, conv = mods[i], mods[i + 1]
+            if not isinstance(up, nn.Upsample) or up.mode != "nearest" or float(up.scale_factor) != 2.0 or not isinstance(conv, UpConv2dK3):
+                raise CvaeError("UpConvStack: Upsample(scale_factor=2, mode='nearest') + Conv2d(k3) pairs expected")
+            bn = mods[i + 2] if i + 2 < len(mods) and isinstance(mods[i + 2], BatchNorm2d) else None
+            if bn is not None and (bn.training or not bn.track_running_stats):
+                raise CvaeError("UpConvStack.forward_folded: eval-mode BatchNorm2d on running statistics only")
+            j = i + (3 if bn is not None else 2)
+            act = _act_of(mods[j]) if j < len(mods) else None
+            table.append((conv.weight, ops.FOLD_UPCONV_K3, conv.bias, bn))
+            acts.append(act)
+            i = j + (1 if act else 0)
+        folded = ops.fold_bn_conv(table)
+        x = ops.ToChannelsLast.apply(h, self.compute_dtype)
+        for (k4, b), act in zip(folded, acts):
+            x = ops.ConvUp.apply(x, k4, b, 2, act, False, False, None)
+        return ops.FromChannelsLast.apply(x, 2)
 
 
 def set_linear_math(module, dtype):

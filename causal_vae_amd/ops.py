@@ -1811,3 +1811,97 @@ class Conv3ToK4(torch.autograd.Function):
         dw3 = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=g.device)
         check(lib.cvae_k4_to_conv3_grad(ptr(g), ptr(dw3), Cout, Cin, stream()), "k4_to_conv3_grad")
         return dw3
+
+
+# ------------------------------------------------------------------------------------------------ CausalVesselVAE inference (csrc/vessel_infer.hip)
+# Forward-only helpers of the eval-mode decode and the analysis sweeps: they enqueue their kernels and return plain tensors; asked for a gradient
+# they raise (the reference consumers run them under no_grad).
+FOLD_CONV_K4, FOLD_UPCONV_K3 = 0, 1        # CVAE_FOLD_CONV_K4 / CVAE_FOLD_UPCONV_K3
+
+
+def _forward_only(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise L.CvaeError(f"{what} is forward-only (eval-mode inference): call it under torch.no_grad()")
+
+
+def fold_bn_conv(entries):
+    """Fold eval-mode BatchNorm2d into the convs in front of it, for up to 16 layers in ONE launch (cvae_fold_bn_conv).
+    entries: (weight, kind, bias, bn) with kind FOLD_CONV_K4 (nn.Conv2d k4 weight, layout kept) or FOLD_UPCONV_K3 (the Conv2d(k3) of an Upsample x2 +
+    Conv2d pair -> its transposed k4 weight [Cin][Cout][4][4]) and bn an nn.BatchNorm2d on running statistics, or None (plain transform, bias copied).
+    Returns [(w_out, b_out)] fp32, all views of one fresh buffer."""
+    import ctypes as C
+    k = len(entries)
+    if not 1 <= k <= 16:
+        raise L.CvaeError(f"fold_bn_conv: 1 to 16 layers per launch, got {k}")
+    for w, kind, bias, bn in entries:
+        L.require_gpu(w, bias)
+        _forward_only("fold_bn_conv", w, bias, *((bn.weight, bn.bias) if bn is not None else ()))
+        if bn is not None and (bn.running_mean is None or bn.weight is None):
+            raise L.CvaeError("fold_bn_conv: the BatchNorm2d needs running statistics and an affine weight (eval mode, track_running_stats, affine)")
+    sizes = []
+    for w, kind, _b, _bn in entries:
+        if kind not in (FOLD_CONV_K4, FOLD_UPCONV_K3) or w.dim() != 4 or tuple(w.shape[2:]) != ((4, 4) if kind == FOLD_CONV_K4 else (3, 3)):
+            raise L.CvaeError(f"fold_bn_conv: kind {kind} does not match a weight of shape {tuple(w.shape)}")
+        sizes.append((w.shape[0] * w.shape[1] * 16, w.shape[0]))
+    pad = lambda n: (n + 3) // 4 * 4                      # every piece starts on 16 bytes
+    buf = torch.empty(sum(pad(a) + pad(b) for a, b in sizes), dtype=torch.float32, device=entries[0][0].device)
+    outs, off = [], 0
+    for (w, kind, _b, _bn), (nw, nb) in zip(entries, sizes):
+        shape = tuple(w.shape[:2]) + (4, 4) if kind == FOLD_CONV_K4 else (w.shape[1], w.shape[0], 4, 4)
+        wo = buf[off:off + nw].view(shape)
+        off += pad(nw)
+        bo = buf[off:off + nb]
+        off += pad(nb)
+        outs.append((wo, bo))
+    ws = [w.contiguous() for w, _k, _b, _bn in entries]
+    vp = lambda v: (C.c_void_p * k)(*v)
+    dims = [d for w in ws for d in (w.shape[0], w.shape[1])]
+    bns = [bn for _w, _k, _b, bn in entries]
+    f32 = lambda t: None if t is None else t.detach().float().contiguous()
+    keep = [(f32(bn.weight), f32(bn.bias), f32(bn.running_mean), f32(bn.running_var)) if bn is not None else (None,) * 4 for bn in bns]
+    biases = [f32(b) for _w, _k, b, _bn in entries]
+    check(lib.cvae_fold_bn_conv(k, vp([w.data_ptr() for w in ws]), (C.c_int * k)(*[kind for _w, kind, _b, _bn in entries]), (C.c_int64 * (2 * k))(*dims),
+                                vp([ptr(b) for b in biases]), vp([ptr(t[0]) for t in keep]), vp([ptr(t[1]) for t in keep]), vp([ptr(t[2]) for t in keep]),
+                                vp([ptr(t[3]) for t in keep]), (C.c_float * k)(*[float(bn.eps) if bn is not None else 0.0 for bn in bns]),
+                                vp([o[0].data_ptr() for o in outs]), vp([o[1].data_ptr() for o in outs]), stream()), "fold_bn_conv")
+    return outs
+
+
+def row_diff_norms(a, b, ref=None, want_mean_abs=False):
+    """l2[r] = ||a[r] - b[ref[r]]||_2 (and mean |a[r] - b[ref[r]]| when asked) over rows = a.shape[0], each row flattened (cvae_row_diff_norms).
+    a, b: fp32 or bf16 (the same), contiguous; ref: int64 [rows] indices into b's rows (None: row r of b).  Fixed-order sums: bit-reproducible.
+    Returns (l2, mean_abs or None), fp32 [rows]."""
+    L.require_gpu(a, b, ref)
+    _forward_only("row_diff_norms", a, b)
+    if a.dtype != b.dtype or a.shape[1:] != b.shape[1:]:
+        raise L.CvaeError(f"row_diff_norms: a {tuple(a.shape)} {a.dtype} and b {tuple(b.shape)} {b.dtype} must share dtype and row shape")
+    a, b = a.contiguous(), b.contiguous()
+    rows, n = a.shape[0], a[0].numel()
+    if ref is not None:
+        ref = ref.to(device=a.device, dtype=torch.int64).contiguous()
+        if ref.shape != (rows,):
+            raise L.CvaeError(f"row_diff_norms: ref must be [{rows}], got {tuple(ref.shape)}")
+    l2 = _empty((rows,), torch.float32, a)
+    ma = _empty((rows,), torch.float32, a) if want_mean_abs else None
+    dt = L.dtype_code(a.dtype)
+    _t, wp, wb = _scratch(lib.cvae_row_diff_norms_workspace_bytes(rows, n, dt), a)
+    check(lib.cvae_row_diff_norms(ptr(a), ptr(b), ptr(ref), ptr(l2), ptr(ma), rows, b.shape[0], n, dt, wp, wb, stream()), "row_diff_norms")
+    return l2, ma
+
+
+def stack_mean_std(tensors):
+    """(torch.stack(tensors).mean(0), torch.stack(tensors).std(0)) for up to 16 equal-shape fp32 tensors, without the stacked copy
+    (cvae_stack_mean_std; two-pass: mean, then squared deviations).  One tensor gives a NaN std, as torch does."""
+    import ctypes as C
+    k = len(tensors)
+    if not 1 <= k <= 16:
+        raise L.CvaeError(f"stack_mean_std: 1 to 16 tensors, got {k}")
+    L.require_gpu(*tensors)
+    _forward_only("stack_mean_std", *tensors)
+    shape = tensors[0].shape
+    if any(t.shape != shape or t.dtype != torch.float32 for t in tensors):
+        raise L.CvaeError("stack_mean_std: fp32 tensors of one shape expected")
+    xs = [t.contiguous() for t in tensors]
+    mean, std = _empty(shape, torch.float32, xs[0]), _empty(shape, torch.float32, xs[0])
+    check(lib.cvae_stack_mean_std((C.c_void_p * k)(*[t.data_ptr() for t in xs]), k, ptr(mean), ptr(std), xs[0].numel(), stream()), "stack_mean_std")
+    return mean, std

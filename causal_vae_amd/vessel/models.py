@@ -16,6 +16,9 @@ from .config import CONFIG
 
 
 class CausalVesselVAE(nn.Module):
+    # decode(z, m): how counterfactual.batched_counterfactual calls this model's decoder (it dispatches on this name, never on attribute probing)
+    decode_signature = "z_m"
+
     def __init__(self):
         super().__init__()
         self.m_dim, self.t_dim, self.z_dim = CONFIG["M_DIM"], CONFIG["T_DIM"], CONFIG["Z_DIM"]
@@ -53,10 +56,33 @@ class CausalVesselVAE(nn.Module):
             eps = self._eps.draw(mu)
         return ops.Reparameterize.apply(mu, logvar, eps)
 
-    def forward(self, x, m, t, eps=None):
+    def _check_image(self, x):
         if x.dim() != 4 or x.shape[1] != 1 or tuple(x.shape[2:]) != (CONFIG["IMG_HEIGHT"], CONFIG["IMG_WIDTH"]):
             raise RuntimeError(f"CausalVesselVAE expects [B, 1, {CONFIG['IMG_HEIGHT']}, {CONFIG['IMG_WIDTH']}] (the 512 x 6 x 10 latent map is hard-wired, "
                                f"models.py:45,162), got {tuple(x.shape)}")
+
+    @torch.no_grad()
+    def encode(self, x, m, t, folded=True):
+        """(mu, logvar) of q(z | x, m, t), clamped as forward clamps them (models.py:148-149).  Inference entry point (no_grad).  In eval mode with
+        folded=True the encoder's BatchNorm2d layers are folded into its convs (layers.BNConvStack.forward_folded); in training mode or with
+        folded=False it runs forward's own layer path, bit for bit.  enc_fc (Linear + BatchNorm1d) runs as in forward either way."""
+        self._check_image(x)
+        x_feat = self.enc_conv.forward_folded(x) if (folded and not self.training) else self.enc_conv(x)
+        mu, logvar = self.enc_fc(ops.cat([x_feat, m, t])).chunk(2, dim=1)
+        return ops.Clamp.apply(mu, -100.0, 100.0), ops.Clamp.apply(logvar, -10.0, 10.0)
+
+    @torch.no_grad()
+    def decode(self, z, m, folded=True):
+        """dec_conv(dec_fc(cat[m, z]).view(-1, 512, 6, 10)) — the decoder expression of the reference's consumers (analyze_vessel.py:90-91,103-104,
+        check_mechanism_z_perm.py:121-122) -> [B, 1, 768, 1280].  Note the argument order: z first, m second; the concatenation is [m, z] as in
+        forward (:161).  Inference entry point (no_grad); folded as in encode (layers.UpConvStack.forward_folded)."""
+        if z.dim() != 2 or m.dim() != 2 or z.shape[0] != m.shape[0] or z.shape[1] != self.z_dim or m.shape[1] != self.m_dim:
+            raise RuntimeError(f"CausalVesselVAE.decode(z [B, {self.z_dim}], m [B, {self.m_dim}]): got z {tuple(z.shape)}, m {tuple(m.shape)}")
+        h_dec = self.dec_fc(ops.cat([m, z])).view(-1, 512, 6, 10)
+        return self.dec_conv.forward_folded(h_dec) if (folded and not self.training) else self.dec_conv(h_dec)
+
+    def forward(self, x, m, t, eps=None):
+        self._check_image(x)
         x_feat = self.enc_conv(x)
         mu, logvar = self.enc_fc(ops.cat([x_feat, m, t])).chunk(2, dim=1)
         logvar = ops.Clamp.apply(logvar, -10.0, 10.0)                      # :148

@@ -222,6 +222,34 @@ int cvae_bn2d_fwd(const void* x, const float* gamma, const float* beta, void* y,
 int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
                   float* dbeta, int64_t P, int64_t C, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CausalVesselVAE inference (csrc/vessel_infer.hip): eval-mode BatchNorm2d folded into the convs, sweep reductions ---------------------
+ * Fold a table of `count` (1..16, else CVAE_E_UNSUPPORTED) conv layers with the eval-mode BatchNorm2d behind them in ONE launch (host arrays
+ * of device pointers, dims = count rows of {Cout, Cin}).  Per output channel c: s = gamma[c] rsqrt(var[c] + eps[k]),
+ * w_out[c] = w[c] s, b_out[c] = (bias[c] - mean[c]) s + beta[c] — the conv then runs with the activation in its epilogue and no BatchNorm pass.
+ *   kind CVAE_FOLD_CONV_K4:   w = nn.Conv2d(k4) weight [Cout][Cin][4][4], w_out in the same layout;
+ *   kind CVAE_FOLD_UPCONV_K3: w = the Conv2d(k3) of an Upsample(x2, nearest) + Conv2d pair [Cout][Cin][3][3], w_out the transposed k4 weight
+ *                             [Cin][Cout][4][4] = A W3 A^T of cvae_conv3_to_k4 (same sums, same order).
+ * gamma NULL (the array, or its entry k): no BatchNorm — the plain transform, bias copied (a NULL bias entry counts as zeros); otherwise beta /
+ * mean / var entries are required.  w and w_out 16-byte aligned (an UpConv2dK3 with Cin % 4 != 0: w_out only), else CVAE_E_UNSUPPORTED.
+ * Outputs fp32. */
+#define CVAE_FOLD_CONV_K4   0
+#define CVAE_FOLD_UPCONV_K3 1
+int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
+                      const float* const* beta, const float* const* mean, const float* const* var, const float* eps, float* const* w_out,
+                      float* const* b_out, void* stream);
+/* l2[r] = ||a[r] - b[ref[r]]||_2 and (mean_abs != NULL) mean_abs[r] = mean |a[r] - b[ref[r]]| over rows of n elements; a holds `rows` rows,
+ * b holds b_rows rows; ref: device int64[rows] (NULL: ref[r] = r, needs b_rows >= rows); a ref outside [0, b_rows) gives NaN for that row,
+ * nothing is read.  dtype CVAE_F32 or CVAE_BF16 (a and b alike); sums in fp32.  workspace: cvae_row_diff_norms_workspace_bytes(rows, n, dtype) —
+ * per-(row, chunk) partial sums, added by a second launch in a fixed order (no float atomics: the bits do not change from run to run, nor with
+ * the number of rows in the call). */
+size_t cvae_row_diff_norms_workspace_bytes(int64_t rows, int64_t n, int dtype);
+int cvae_row_diff_norms(const void* a, const void* b, const int64_t* ref, float* l2, float* mean_abs, int64_t rows, int64_t b_rows, int64_t n,
+                        int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* Element-wise over `count` (1..16, else CVAE_E_UNSUPPORTED) fp32 tensors of n elements (host array of device pointers):
+ * mean = (x_0 + .. + x_{K-1}) / K, std = sqrt(sum_k (x_k - mean)^2 / (K - 1)) — torch.stack(x).mean(0) / .std(0) in the two-pass form;
+ * K = 1 gives NaN std, as torch does.  Fixed order, no reductions across elements. */
+int cvae_stack_mean_std(const float* const* x, int count, float* mean, float* std, int64_t n, void* stream);
+
 /* ---- The dense bottleneck of CausalBioVAE in 5 + 5 launches (batch M <= 16, fp32 arithmetic) --------------------------------
  * Replaces, between the last encoder conv and the first decoder conv (causal_cascade/models.py:57-79):
  *   AdaptiveAvgPool + Flatten, cat([x_feat, m, t]), enc_fc (Linear-ReLU-Linear-ReLU), fc_mu, fc_logvar, reparameterize,
