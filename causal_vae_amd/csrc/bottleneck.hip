@@ -27,7 +27,7 @@
 
 namespace {
 
-struct TailDims { int M, N1, N2, Z, T, HM, DM, KS, P, NZ; }; // N1 = 512, N2 = 256, Z = latent, T = t_dim, HM = 64, DM = m_dim, NZ = d(zm) partial slots
+struct TailDims { int M, N1, N2, Z, T, HM, DM, KS, P, NZ; }; // widths (model: N1 = 512, N2 = 256, HM = 64), Z = latent, T = t_dim, DM = m_dim, NZ = d(zm) partial slots
 struct TailParams {
     const float *b1, *W2, *b2, *Wmu, *bmu, *Wlv, *blv, *Wm0, *bm0, *gamma, *beta, *Wm3, *bm3, *Wm5, *bm5;
 };
@@ -1039,17 +1039,70 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
 
 size_t mech_fwd_lds(const TailDims& d) { return sizeof(float) * (size_t)d.M * (d.T + 2 * d.HM); }
 size_t mech_bwd_lds(const TailDims& d) { return sizeof(float) * ((size_t)d.M * (d.Z + d.DM + d.DM + 5 * d.HM + d.T) + 4 * 256 + 4); }   // + load_dzm's scratch (16-byte aligned)
+size_t fc2_fwd_lds(const TailDims& d) { return sizeof(float) * (size_t)d.M * d.N1; }
+size_t mulv_fwd_lds(const TailDims& d) { return sizeof(float) * (size_t)d.M * d.N2; }
+size_t mulv_bwd_lds(const TailDims& d) { return sizeof(float) * ((size_t)d.M * (d.Z + d.DM) + 2 * (size_t)d.M * d.Z + 17 * (size_t)d.M * 16 + 4 * 256 + 4); }
+size_t fc2_bwd_lds(const TailDims& d) { return sizeof(float) * ((size_t)d.M * d.N2 + 17 * (size_t)d.M * 16); }
+size_t bn_finish_lds(const TailDims& d) { return sizeof(float) * (size_t)d.M * (d.HM + d.T); }
+size_t dec_input_fwd_lds(int M, int K4) { return sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)4 * M * 64); }
+size_t dec_input_bwd_lds(int M, int K4) { return sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)M * 64); }
+int mt_of(int M) { return M <= 4 ? 4 : (M <= 8 ? 8 : 16); }                // the skinny kernels' row template (launch_fwd_partial / launch_bwd_colwise)
+
+// LDS of a workgroup on gfx950 (dynamic + static).  A launch above the default dynamic limit (64 KiB) raises its kernel's limit to what the
+// static part leaves of 160 KiB — once per kernel, checked, before the call's first launch (as conv_mfma.hip / small_dense.hip do), so a failure
+// leaves nothing written.  The model's shapes stay below 64 KiB and never get here.
+constexpr size_t BN_LDS_MAX = 160 * 1024, BN_LDS_DEFAULT = 64 * 1024;
+template <typename KERN> int bn_allow_lds(KERN kern, size_t dyn, size_t static_bytes, bool* done) {
+    if (dyn <= BN_LDS_DEFAULT || *done) return CVAE_OK;
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BN_LDS_MAX - static_bytes)) != hipSuccess) return CVAE_E_LAUNCH;
+    *done = true;
+    return CVAE_OK;
+}
+bool lds_fwd_partial[3], lds_bwd_colwise[3], lds_fc2_fwd, lds_mulv_fwd, lds_fc2_bwd, lds_bn_finish;
+// static LDS of the two skinny kernels: skinny_fwd_partial's red[4][4 * MT], skinny_bwd_colwise's gs[MT][64]
+constexpr size_t fwd_partial_static(int MT) { return sizeof(float) * 4 * 4 * MT; }
+constexpr size_t bwd_colwise_static(int MT) { return sizeof(float) * 64 * MT; }
+int fwd_lds_ready(const TailDims& d) {
+    int rc;
+    switch (mt_of(d.M)) {
+        case 4: rc = bn_allow_lds(skinny_fwd_partial_kernel<4>, mech_fwd_lds(d), fwd_partial_static(4), &lds_fwd_partial[0]); break;
+        case 8: rc = bn_allow_lds(skinny_fwd_partial_kernel<8>, mech_fwd_lds(d), fwd_partial_static(8), &lds_fwd_partial[1]); break;
+        default: rc = bn_allow_lds(skinny_fwd_partial_kernel<16>, mech_fwd_lds(d), fwd_partial_static(16), &lds_fwd_partial[2]); break;
+    }
+    if (rc == CVAE_OK) rc = bn_allow_lds(fc2_fwd_kernel, fc2_fwd_lds(d), 0, &lds_fc2_fwd);
+    if (rc == CVAE_OK) rc = bn_allow_lds(mulv_fwd_kernel, mulv_fwd_lds(d), 0, &lds_mulv_fwd);
+    return rc;
+}
+int bwd_lds_ready(const TailDims& d) {
+    int rc;
+    switch (mt_of(d.M)) {
+        case 4: rc = bn_allow_lds(skinny_bwd_colwise_kernel<4>, mech_bwd_lds(d), bwd_colwise_static(4), &lds_bwd_colwise[0]); break;
+        case 8: rc = bn_allow_lds(skinny_bwd_colwise_kernel<8>, mech_bwd_lds(d), bwd_colwise_static(8), &lds_bwd_colwise[1]); break;
+        default: rc = bn_allow_lds(skinny_bwd_colwise_kernel<16>, mech_bwd_lds(d), bwd_colwise_static(16), &lds_bwd_colwise[2]); break;
+    }
+    if (rc == CVAE_OK) rc = bn_allow_lds(fc2_bwd_kernel, fc2_bwd_lds(d), 0, &lds_fc2_bwd);
+    return rc;                                               // mulv_bwd and the dec_input pair stay below 64 KiB for every accepted shape
+}
 
 }  // namespace
 
 // Host-side description of the bottleneck (plain C struct of the C ABI, see include/cvae_hip.h).
+static TailDims tail_dims(const cvae_bottleneck_dims* q, int KS, int P);
 static bool dims_ok(const cvae_bottleneck_dims* q) {
     if (!q) return false;
     if (q->M < 1 || q->M > BN_MAXM) return false;
     if (q->C < 64 || q->C % 64 || q->D < 1 || q->H < 1 || q->W < 1 || q->OD < 1 || q->OH < 1 || q->OW < 1) return false;
     if (q->D % q->OD || q->H % q->OH || q->W % q->OW) return false;
     if (q->m_dim < 1 || q->t_dim < 1 || q->N1 < 4 || q->N2 < 1 || q->Z < 1 || q->HM < 1 || q->HM > 1024) return false;
-    if (q->Z + q->m_dim > 128 || q->N1 > 4096 || q->N2 > 2048) return false;            // LDS / register budgets of the level kernels
+    if (q->Z + q->m_dim > 128 || q->N1 > 4096 || q->N2 > 2048 || q->t_dim > 65536) return false;     // register budgets of the level kernels
+    // every level launch's LDS (its dynamic part grows with M and the widths) must fit in a workgroup's 160 KiB: checked here, before anything runs,
+    // so a refused shape leaves every output and the running statistics untouched
+    const TailDims d = tail_dims(q, 0, 0);
+    const int MT = mt_of(d.M), K4 = d.Z + d.DM;
+    const size_t need[] = {mech_fwd_lds(d) + fwd_partial_static(MT), fc2_fwd_lds(d), mulv_fwd_lds(d), dec_input_fwd_lds(d.M, K4), dec_input_bwd_lds(d.M, K4),
+                           mulv_bwd_lds(d), fc2_bwd_lds(d), mech_bwd_lds(d) + bwd_colwise_static(MT), bn_finish_lds(d)};
+    for (size_t b : need)
+        if (b > BN_LDS_MAX) return false;
     return true;
 }
 static TailDims tail_dims(const cvae_bottleneck_dims* q, int KS, int P) {
@@ -1115,6 +1168,7 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     if (!w || !sv || !y_cl || !m || !t_onehot || !eps || !xcat || !partial || !dec_cl) return CVAE_E_NULLPTR;
     if (bn_training && q->M * (bn_rank_stats ? bn_ranks : 1) < 2) return CVAE_E_BADSHAPE;
     if (!bn_training && (!running_mean || !running_var)) return CVAE_E_NULLPTR;
+    if (fwd_lds_ready(tail_dims(q, 0, 0)) != CVAE_OK) return CVAE_E_LAUNCH;     // before the first launch: a failure writes nothing
     hipStream_t st = (hipStream_t)stream;
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), KS = fwd_ksplit(K1);
@@ -1133,11 +1187,11 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     else if (M <= 8) launch_fwd_partial<8>(xcat, w->W1, partial, M, K1, (int)q->N1, KS, d, p, s, ma, st);
     else launch_fwd_partial<16>(xcat, w->W1, partial, M, K1, (int)q->N1, KS, d, p, s, ma, st);
     CVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fc2_fwd_kernel, dim3((unsigned)((q->N2 + 3) / 4)), dim3(256), sizeof(float) * (size_t)M * q->N1, st, d, p, s, (const float*)partial);
+    hipLaunchKernelGGL(fc2_fwd_kernel, dim3((unsigned)((q->N2 + 3) / 4)), dim3(256), fc2_fwd_lds(d), st, d, p, s, (const float*)partial);
     CVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mulv_fwd_kernel, dim3((unsigned)((q->Z + 3) / 4)), dim3(256), sizeof(float) * (size_t)M * q->N2, st, d, p, s, eps);
+    hipLaunchKernelGGL(mulv_fwd_kernel, dim3((unsigned)((q->Z + 3) / 4)), dim3(256), mulv_fwd_lds(d), st, d, p, s, eps);
     CVAE_CHECK_LAUNCH();
-    const size_t lds_d = sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)4 * M * 64);
+    const size_t lds_d = dec_input_fwd_lds(M, K4);
     if (dtype == CVAE_BF16)
         hipLaunchKernelGGL(dec_input_fwd_kernel<bf16>, dim3(C * S / 64), dim3(256), lds_d, st, (const float*)sv->zm, w->Wd, w->bd, (bf16*)dec_cl, M, K4, S, C);
     else
@@ -1154,7 +1208,8 @@ extern "C" int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* q, cons
     const TailParams p{w->b1, w->W2, w->b2, w->Wmu, w->bmu, w->Wlv, w->blv, w->Wm0, w->bm0, w->gamma, w->beta, w->Wm3, w->bm3, w->Wm5, w->bm5};
     const TailGrads g{gr->db1, gr->dW2, gr->db2, gr->dWmu, gr->dbmu, gr->dWlv, gr->dblv, gr->dWm0, gr->dbm0, gr->dgamma, gr->dbeta, gr->dWm3, gr->dbm3, gr->dWm5, gr->dbm5};
     const TailSaved s{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm};
-    hipLaunchKernelGGL(mech_bn_finish_kernel, dim3(1), dim3(256), sizeof(float) * (size_t)q->M * (size_t)(q->HM + q->t_dim), (hipStream_t)stream, d, p, g, s, t_onehot, bn_dy, bn_sums,
+    if (bn_allow_lds(mech_bn_finish_kernel, bn_finish_lds(d), 0, &lds_bn_finish) != CVAE_OK) return CVAE_E_LAUNCH;
+    hipLaunchKernelGGL(mech_bn_finish_kernel, dim3(1), dim3(256), bn_finish_lds(d), (hipStream_t)stream, d, p, g, s, t_onehot, bn_dy, bn_sums,
                        bn_ranks);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -1168,10 +1223,11 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
     if ((bn_dy == nullptr) != (bn_local_sums == nullptr)) return CVAE_E_NULLPTR;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (!w || !gr || !sv || !g_dec_cl || !t_onehot || !eps || !xcat || !y_cl || !dzm_partial || !g1 || !dx_partial || !dy_cl) return CVAE_E_NULLPTR;
+    if (bwd_lds_ready(tail_dims(q, 0, 0)) != CVAE_OK) return CVAE_E_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), NS = bwd_nsplit(q->N1), P = S;
-    const size_t lds_d = sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)M * 64);
+    const size_t lds_d = dec_input_bwd_lds(M, K4);
     if (dtype == CVAE_BF16)
         hipLaunchKernelGGL(dec_input_bwd_kernel<bf16>, dim3(F / 64), dim3(256), lds_d, st, (const bf16*)g_dec_cl, (const float*)sv->zm, w->Wd, gr->dWd, gr->dbd,
                            dzm_partial, M, K4, S, C);
@@ -1184,10 +1240,10 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
     const TailGrads g{gr->db1, gr->dW2, gr->db2, gr->dWmu, gr->dbmu, gr->dWlv, gr->dblv, gr->dWm0, gr->dbm0, gr->dgamma, gr->dbeta, gr->dWm3, gr->dbm3, gr->dWm5, gr->dbm5};
     const TailSaved s{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm};
     float* dh2 = g1 + (size_t)M * q->N1;                     // second part of the g1 scratch
-    hipLaunchKernelGGL(mulv_bwd_kernel, dim3((unsigned)((q->N2 + 15) / 16)), dim3(256), sizeof(float) * ((size_t)M * K4 + 2 * (size_t)M * q->Z + 17 * (size_t)M * 16 + 4 * 256 + 4), st,
+    hipLaunchKernelGGL(mulv_bwd_kernel, dim3((unsigned)((q->N2 + 15) / 16)), dim3(256), mulv_bwd_lds(d), st,
                        d, p, g, s, (const float*)dzm_partial, g_mu, g_logvar, eps, dh2);
     CVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fc2_bwd_kernel, dim3((unsigned)((q->N1 + 15) / 16)), dim3(256), sizeof(float) * ((size_t)M * q->N2 + 17 * (size_t)M * 16), st, d, p, g, s,
+    hipLaunchKernelGGL(fc2_bwd_kernel, dim3((unsigned)((q->N1 + 15) / 16)), dim3(256), fc2_bwd_lds(d), st, d, p, g, s,
                        (const float*)dh2, g1);
     CVAE_CHECK_LAUNCH();
     const MechBwdArgs mb{dzm_partial, g_mhat, t_onehot, bn_dy, bn_local_sums};

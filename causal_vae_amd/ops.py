@@ -1621,10 +1621,16 @@ class BioBottleneck(torch.autograd.Function):
     """
 
     @staticmethod
-    def supported(y_cl, out_size, training):
+    def supported(y_cl, out_size, training, widths=None):
+        """widths (optional) = (m_dim, t_dim, N1, N2, Z, HM): also ask the library (cvae_bottleneck_sizes), which refuses widths whose level
+        launches would not fit in a workgroup's LDS at this batch (include/cvae_hip.h).  Without it only the batch, channels and windows are checked."""
         B, D, H, W, C = y_cl.shape
         OD, OH, OW = out_size
-        return training and 2 <= B <= 16 and C % 64 == 0 and D % OD == 0 and H % OH == 0 and W % OW == 0
+        ok = training and 2 <= B <= 16 and C % 64 == 0 and D % OD == 0 and H % OH == 0 and W % OW == 0
+        if ok and widths is not None:
+            dims = L.BottleneckDims(B, D, H, W, C, OD, OH, OW, *widths)
+            ok = lib.cvae_bottleneck_sizes(C_.byref(dims), None, None, None, None, None) == 0
+        return ok
 
     @staticmethod
     def forward(ctx, y_cl, m, t_onehot, eps, *rest):

@@ -256,7 +256,10 @@ int cvae_stack_mean_std(const float* const* x, int count, float* mean, float* st
  *   mechanism_net (Linear, BatchNorm1d, ReLU, Linear, ReLU, Linear), cat([z, m_hat]), dec_input (+ the NC(D)HW -> channels-last
  *   move into the decoder).  All pointers are device pointers; weights are the nn.Linear / BatchNorm1d tensors as they are.
  * y_cl: last encoder activation [M][D][H][W][C] (conv dtype), pooled to OD x OH x OW windows (D % OD == 0 etc.).
- * N1 / N2: widths of enc_fc.0 / enc_fc.2; Z: latent; HM: mechanism_net width; K1 = C*OD*OH*OW + m_dim + t_dim; K4 = Z + m_dim. */
+ * N1 / N2: widths of enc_fc.0 / enc_fc.2; Z: latent; HM: mechanism_net width; K1 = C*OD*OH*OW + m_dim + t_dim; K4 = Z + m_dim.
+ * Accepted: 1 <= M <= 16, C % 64 == 0, non-overlapping windows, 4 <= N1 <= 4096, N2 <= 2048, Z + m_dim <= 128, HM <= 1024, t_dim <= 65536, and
+ * every level launch's LDS within a workgroup's 160 KiB — about 4 M N1, 4 M (t_dim + 2 HM) and 4 M (Z + 2 m_dim + 5 HM + t_dim) bytes (so N1 = 4096
+ * needs M <= 10, HM = 1024 M <= 7).  Anything else is CVAE_E_BADSHAPE from every entry, before any launch. */
 typedef struct { int64_t M, D, H, W, C, OD, OH, OW, m_dim, t_dim, N1, N2, Z, HM; } cvae_bottleneck_dims;
 typedef struct {                 /* parameters (fp32, torch layouts [out][in]) */
     const float *W1, *b1, *W2, *b2, *Wmu, *bmu, *Wlv, *blv, *Wm0, *bm0, *gamma, *beta, *Wm3, *bm3, *Wm5, *bm5, *Wd, *bd;

@@ -928,22 +928,28 @@ def test_gaussian_head_adversarial_step_matches_oracle():
         adam_close(v, sd_d[k], k)
 
 
-@pytest.mark.parametrize("cls,shape,dtype", [("3d", (3, 1, 32, 32, 32), torch.float32), ("3d", (4, 1, 64, 64, 64), torch.bfloat16),
-                                             ("2d", (5, 1, 64, 96), torch.float32), ("3d", (16, 1, 32, 32, 32), torch.float32)])
-def test_fused_bottleneck_equals_layer_by_layer_path(cls, shape, dtype):
-    """ops.BioBottleneck (4 + 4 launches) against the same model run layer by layer: outputs, every gradient, BN buffers."""
+@pytest.mark.parametrize("cls,shape,dtype", [("3d", (3, 1, 64, 64, 64), torch.float32), ("3d", (4, 1, 64, 64, 64), torch.bfloat16),
+                                             ("2d", (5, 1, 64, 128), torch.float32), ("3d", (16, 1, 64, 64, 64), torch.float32)])
+def test_fused_bottleneck_equals_layer_by_layer_path(cls, shape, dtype, monkeypatch):
+    """ops.BioBottleneck (5 + 5 launches) against the same model run layer by layer: outputs, every gradient, BN buffers.  Every shape reaches
+    the fused path (extents / 16 tile into 4^nd windows), and the fused run is checked to have called it, the unfused run not."""
     Model = CausalBioVAE3D if cls == "3d" else CausalBioVAE
     g = torch.Generator().manual_seed(11)
     B = shape[0]
     x, m = torch.randn(*shape, generator=g).to(DEV), torch.rand(B, 12, generator=g).to(DEV)
     t = torch.randint(0, 19, (B,), generator=g).to(DEV)
     eps = torch.randn(B, 64, generator=g).to(DEV)
+    calls = []
+    apply = ops_mod.BioBottleneck.apply
+    monkeypatch.setattr(ops_mod.BioBottleneck, "apply", lambda *a: calls.append(1) or apply(*a))
     runs = {}
     for fused in (False, True):
         torch.manual_seed(42)
         model = Model().to(DEV).train().set_compute_dtype(dtype)
         model.fuse_bottleneck = fused
+        calls.clear()
         recon, m_hat, mu, logvar = model(x, m, t, eps=eps)
+        assert len(calls) == (1 if fused else 0), f"fuse_bottleneck={fused}: ops.BioBottleneck called {len(calls)} times"
         loss = ((recon - x) ** 2).sum() + 3.0 * ((m_hat - m) ** 2).sum() - 0.5 * torch.sum(1 + logvar - mu.pow(2) - logvar.exp())
         loss.backward()
         bn = model.mechanism_net[1]
