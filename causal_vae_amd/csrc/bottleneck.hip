@@ -27,6 +27,13 @@
 
 namespace {
 
+// ---- tunables: each may be overridden for an A/B build with make EXTRA=-DCVAE_<NAME>=<n> (CVAE_TUNABLE, common.h) ----
+CVAE_TUNABLE(BN_NT, 0);                 // passes over enc_fc.0's weight: bit 0 = nontemporal loads, bit 1 = nontemporal stores (ld_stream / st_stream)
+CVAE_TUNABLE(BN_FWD_UNROLL, 2);         // skinny forward: unrolled k iterations
+CVAE_TUNABLE(BN_BWD_UNROLL, 8);         // skinny backward: unrolled rows (MT < 16)
+CVAE_TUNABLE(BN_FWD_SLICE, 4096);       // forward: columns of K per slice (fwd_ksplit); halving this and BN_BWD_ROWS measured +10 us per step
+CVAE_TUNABLE(BN_BWD_ROWS, 16);          // backward: rows of N1 per workgroup (bwd_nsplit)
+
 struct TailDims { int M, N1, N2, Z, T, HM, DM, KS, P, NZ; }; // widths (model: N1 = 512, N2 = 256, HM = 64), Z = latent, T = t_dim, DM = m_dim, NZ = d(zm) partial slots
 struct TailParams {
     const float *b1, *W2, *b2, *Wmu, *bmu, *Wlv, *blv, *Wm0, *bm0, *gamma, *beta, *Wm3, *bm3, *Wm5, *bm5;
@@ -40,21 +47,18 @@ struct MechFwdArgs { const float* t_onehot; float *running_mean, *running_var; l
                      const float* sync_stats; int sync_ranks; };       // SyncBatchNorm: [ranks][2][HM] (sum, squared deviations from the rank's own mean) of every rank's batch
 struct MechBwdArgs { const float *dzm_part, *g_mhat, *t_onehot; float *sync_dy, *sync_local; };      // SyncBatchNorm: the backward stops at the BatchNorm (see mech_bwd)
 struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };       // float4 at dword alignment
-// streaming (nontemporal) forms of the dword-aligned 16-byte / 8-byte accesses, for the two passes over enc_fc.0's weight (-DCVAE_BN_NT=1 / 2 / 3: loads / stores / both)
-#ifndef CVAE_BN_NT
-#define CVAE_BN_NT 0
-#endif
+// streaming (nontemporal) forms of the dword-aligned 16-byte / 8-byte accesses, for the two passes over enc_fc.0's weight (BN_NT = 1 / 2 / 3: loads / stores / both)
 typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float v2f_u __attribute__((ext_vector_type(2), aligned(4)));
 struct F2U;
 template <typename V> __device__ __forceinline__ V ld_stream(const float* p) {
-    if constexpr (CVAE_BN_NT & 1) {
+    if constexpr (BN_NT & 1) {
         if constexpr (sizeof(V) == 16) { const v4f_u v = __builtin_nontemporal_load((const v4f_u*)p); V r; __builtin_memcpy(&r, &v, 16); return r; }
         else { const v2f_u v = __builtin_nontemporal_load((const v2f_u*)p); V r; __builtin_memcpy(&r, &v, 8); return r; }
     } else return *(const V*)p;
 }
 template <typename V> __device__ __forceinline__ void st_stream(float* p, const V& val) {
-    if constexpr (CVAE_BN_NT & 2) {
+    if constexpr (BN_NT & 2) {
         if constexpr (sizeof(V) == 16) { v4f_u v; __builtin_memcpy(&v, &val, 16); __builtin_nontemporal_store(v, (v4f_u*)p); }
         else { v2f_u v; __builtin_memcpy(&v, &val, 8); __builtin_nontemporal_store(v, (v2f_u*)p); }
     } else *(V*)p = val;
@@ -147,12 +151,6 @@ __global__ __launch_bounds__(256) void pool_cat_fwd_kernel(const T* __restrict__
     }
 }
 
-#ifndef CVAE_BN_FWD_UNROLL
-#define CVAE_BN_FWD_UNROLL 2
-#endif
-#ifndef CVAE_BN_BWD_UNROLL
-#define CVAE_BN_BWD_UNROLL 8
-#endif
 // ------------------------------------------------------------------------------------------------ skinny_fwd_partial
 // partial[ks][m][n] = sum_{k in slice ks} x[m][k] W[n][k].  grid (N / 4, KS), 256 threads: 4 weight rows per workgroup share one
 // pass over the x slice; rows are read with coalesced 4-byte loads (K is odd in the model: rows are not 16-byte aligned).
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(256) void skinny_fwd_partial_kernel(const float* __
     for (int r = 0; r < R; ++r) wr[r] = Wt + (size_t)min(n0 + r, N - 1) * K;
     // 16-byte loads at dword alignment (rows of odd length are not 16-byte aligned); the < 4-element tail of the slice goes scalar
     const int kvec = k0 + ((k1 - k0) & ~3);
-#pragma unroll CVAE_BN_FWD_UNROLL
+#pragma unroll BN_FWD_UNROLL
     for (int k = k0 + 4 * threadIdx.x; k < kvec; k += 1024) {
         F4U xv[MT], wv[R];
 #pragma unroll
@@ -944,7 +942,7 @@ __global__ __launch_bounds__(256) void skinny_bwd_colwise_kernel(const float* __
         }
         __syncthreads();
         if (nk == CPT) {
-            constexpr int UNR = MT >= 16 ? 2 : CVAE_BN_BWD_UNROLL;      // an unrolled row holds MT values of g: 8 rows of 16 are 128 registers by themselves
+            constexpr int UNR = MT >= 16 ? 2 : BN_BWD_UNROLL;      // an unrolled row holds MT values of g: 8 rows of 16 are 128 registers by themselves
 #pragma unroll UNR
             for (int j = 0; j < cnt; ++j) {
                 typename SkinnyBwdCols<MT>::vec w = ld_stream<typename SkinnyBwdCols<MT>::vec>(Wt + (size_t)(nb + j) * K + k0), dw;
@@ -1111,14 +1109,8 @@ static TailDims tail_dims(const cvae_bottleneck_dims* q, int KS, int P) {
 // Split factors of the two passes over enc_fc.0's weight: the forward slices K into parts of >= 4096 columns (<= 8), the backward gives a
 // workgroup 1024 columns x 16 rows (32 partial d(xcat) slabs).  Measured in the step (A/B of two builds in one session): halving both
 // (2048 columns / 8 rows: twice the workgroups, half the bytes each) costs +10 us per step, the extra partial slabs outweigh the parallelism.
-#ifndef CVAE_BN_FWD_SLICE
-#define CVAE_BN_FWD_SLICE 4096
-#endif
-#ifndef CVAE_BN_BWD_ROWS
-#define CVAE_BN_BWD_ROWS 16
-#endif
-static int fwd_ksplit(int64_t K1) { int ks = (int)(K1 / CVAE_BN_FWD_SLICE); return ks < 1 ? 1 : (ks > 8 ? 8 : ks); }
-static int bwd_nsplit(int64_t N1) { int ns = (int)(N1 / CVAE_BN_BWD_ROWS); return ns < 1 ? 1 : (ns > 64 ? 64 : ns); }
+static int fwd_ksplit(int64_t K1) { int ks = (int)(K1 / BN_FWD_SLICE); return ks < 1 ? 1 : (ks > 8 ? 8 : ks); }
+static int bwd_nsplit(int64_t N1) { int ns = (int)(N1 / BN_BWD_ROWS); return ns < 1 ? 1 : (ns > 64 ? 64 : ns); }
 
 extern "C" int cvae_bottleneck_sizes(const cvae_bottleneck_dims* q, int64_t* K1, int64_t* K4, int64_t* fwd_partial_floats, int64_t* dzm_partial_floats,
                                      int64_t* dx_partial_floats) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/cvae_hip.h"
 
 typedef __bf16 bf16;
@@ -17,6 +18,23 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
         hipError_t e__ = hipGetLastError();                   \
         if (e__ != hipSuccess) return CVAE_E_LAUNCH;          \
     } while (0)
+
+// CVAE_TUNABLE(WG_TILES, 16): the constant WG_TILES is 16 unless the build passes -DCVAE_WG_TILES=<non-negative integer> (make EXTRA=-D..., then
+// tools/ab.sh with CVAE_HIP_LIB).  Every file keeps its tunables in ONE block at its top, one line each.  `text` is the macro's name stringified after
+// expansion: still the name when no -D defined it, the override's digits otherwise.
+constexpr long long cvae_tunable(const char* name, const char* text, long long value) {
+    int i = 0;
+    while (name[i] && name[i] == text[i]) ++i;
+    if (!name[i] && !text[i]) return value;
+    long long v = 0;
+    for (i = 0; text[i]; ++i) v = (text[i] >= '0' && text[i] <= '9' && v >= 0) ? v * 10 + (text[i] - '0') : -1;
+    return i ? v : -1;
+}
+#define CVAE_STR_(x) #x
+#define CVAE_STR(x) CVAE_STR_(x)
+#define CVAE_TUNABLE(name, value)                                                                 \
+    constexpr long long name = cvae_tunable("CVAE_" #name, CVAE_STR(CVAE_##name), value); \
+    static_assert(name >= 0, "-DCVAE_" #name " takes a non-negative integer")
 
 static inline int cvae_grid_1d(int64_t n, int block, int max_blocks = 256 * 8) {
     int64_t g = (n + block - 1) / block;
@@ -135,6 +153,13 @@ template <int EPI> __device__ __forceinline__ float apply_act_t(float v, int act
     return apply_act(v, act);
 }
 #define CVAE_EPI_OF(act) ((act) == CVAE_ACT_NONE ? 0 : ((act) == CVAE_ACT_RELU ? 1 : 2))
+// Runtime -> template lifting on the host, each written once: f receives the value as a std::integral_constant (nd, EPI, a flag) or as a value of the
+// element type (dtype), e.g.  with_epi(act, [&](auto epi) { launch<decltype(epi)::value>(...); return CVAE_OK; })
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename F> auto with_nd(int nd, F&& f) { return nd == 3 ? f(Int<3>{}) : f(Int<2>{}); }
+template <typename F> auto with_dtype(int dtype, F&& f) { return dtype == CVAE_BF16 ? f(bf16{}) : f(float{}); }
+template <typename F> auto with_epi(int act, F&& f) { return CVAE_EPI_OF(act) == 0 ? f(Int<0>{}) : (CVAE_EPI_OF(act) == 1 ? f(Int<1>{}) : f(Int<2>{})); }
+template <typename F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 // derivative expressed through the activation OUTPUT y
 __device__ __forceinline__ float act_grad_from_out(float y, int act) {
     switch (act) {

@@ -162,15 +162,9 @@ __global__ __launch_bounds__(256) void down_c1_kernel(const T* __restrict__ L, c
 #define C1W_TD3 2
 #define C1W_TH3 2
 #define C1W_TW3 32
-#ifndef CVAE_C1_MAX_WG
-#define CVAE_C1_MAX_WG 1024
-#endif
-#ifndef CVAE_C1U_WALK
-#define CVAE_C1U_WALK 1                 // up, Cl == 1, 3D: walk z columns when the launch has enough tiles
-#endif
-#ifndef CVAE_C1U_WALK_MIN_UNITS
-#define CVAE_C1U_WALK_MIN_UNITS 1024
-#endif
+// ---- tunables: each may be overridden for an A/B build with make EXTRA=-DCVAE_<NAME>=<n> (CVAE_TUNABLE, common.h) ----
+CVAE_TUNABLE(C1_MAX_WG, 1024);          // workgroups of the tile-walking single-channel kernels at most: <= 4 resident per CU, each walks ntiles / grid tiles
+CVAE_TUNABLE(C1U_WALK_MIN_UNITS, 1024); // up, Cl == 1, 3D: z columns are walked (up_c1_mfma_walk_kernel) once that leaves this many work units
 template <int ND, int MS> struct TileC1V;
 template <int MS> struct TileC1V<3, MS> { static constexpr int TD = MS / 2, TH = 8, TW = 32; };   // wide in x: a halo row is 160-288 contiguous bytes, an output row 2 KB
 template <int MS> struct TileC1V<2, MS> { static constexpr int TD = 1, TH = 8 * MS, TW = 16; };
@@ -993,7 +987,7 @@ int cvae_conv_down_c1(const void* L, int l_dtype, const float* w, const float* b
         const long long ntiles_ll = (long long)B * tiles_d * tiles_h * tiles_w;
         if (ntiles_ll > 0x7fffffff) return CVAE_E_BADSHAPE;
         const int ntiles = (int)ntiles_ll;
-        dim3 grid((unsigned)(ntiles < CVAE_C1_MAX_WG ? ntiles : CVAE_C1_MAX_WG), 1, 1);       // <= 4 resident workgroups per CU; each walks ntiles / grid tiles
+        dim3 grid((unsigned)(ntiles < C1_MAX_WG ? ntiles : C1_MAX_WG), 1, 1);       // <= 4 resident workgroups per CU; each walks ntiles / grid tiles
 #define LAUNCH_DOWN_VEC__(TLT, ND, EPI, MASKED, MS, SIDE)                                                                                              \
     hipLaunchKernelGGL((down_c1_vec_kernel<TLT, ND, EPI, MASKED, MS, SIDE>), grid, dim3(256), 0, stream, (const TLT*)L, w, bias, (const bf16*)mask, (bf16*)S, (int)sd, (int)sh, \
                        (int)sw, (int)ld, (int)lh, (int)lw, tiles_d, tiles_h, tiles_w, ntiles, act, f8)
@@ -1028,7 +1022,7 @@ int cvae_conv_down_c1(const void* L, int l_dtype, const float* w, const float* b
 
 int cvae_conv_up_c1(const void* S, const float* w, const float* bias, const void* mask, void* L, int64_t B, int64_t sd, int64_t sh, int64_t sw,
                     int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, int act, hipStream_t stream, long long walk_units_arg) {
-    const long long walk_min_units = walk_units_arg > 0 ? walk_units_arg : CVAE_C1U_WALK_MIN_UNITS;     // per call (cvae_conv_up c1_walk_units), no process-wide state
+    const long long walk_min_units = walk_units_arg > 0 ? walk_units_arg : C1U_WALK_MIN_UNITS;     // per call (cvae_conv_up c1_walk_units), no process-wide state
     if (Cs != 32) return CVAE_E_UNSUPPORTED;
     const int64_t n = B * sd * sh * sw;                     // one thread per (source voxel, channel half)
     if (n >= ((int64_t)1 << 30) || (nd == 3 && ld != 2 * sd) || lh != 2 * sh || lw != 2 * sw) return CVAE_E_UNSUPPORTED;   // exact 2x only (depth counts in 3D)
@@ -1038,32 +1032,26 @@ int cvae_conv_up_c1(const void* S, const float* w, const float* bias, const void
         const long long ntiles_ll = (long long)B * tiles_d * tiles_h * tiles_w;
         if (ntiles_ll > 0x7fffffff) return CVAE_E_BADSHAPE;
         const int ntiles = (int)ntiles_ll;
-        dim3 mgrid((unsigned)(ntiles < CVAE_C1_MAX_WG ? ntiles : CVAE_C1_MAX_WG), 1, 1);      // a workgroup walks ntiles / grid tiles with one set of weight fragments
-        const int epi = CVAE_EPI_OF(act);
-#if CVAE_C1U_WALK
+        dim3 mgrid((unsigned)(ntiles < C1_MAX_WG ? ntiles : C1_MAX_WG), 1, 1);      // a workgroup walks ntiles / grid tiles with one set of weight fragments
         if (nd == 3 && ntiles >= 2 * walk_min_units && tiles_d > 1) {   // long z columns: walk them, the shared halo planes stay in LDS
             int walk = (int)(ntiles / walk_min_units);
             if (walk > tiles_d) walk = tiles_d;
             const int segs = (tiles_d + walk - 1) / walk;
             const int nunits = (int)B * segs * tiles_h * tiles_w;
-            dim3 wgrid((unsigned)(nunits < CVAE_C1_MAX_WG ? nunits : CVAE_C1_MAX_WG), 1, 1);
-#define LAUNCH_UP_WALK_(EPI, MASKED) hipLaunchKernelGGL((up_c1_mfma_walk_kernel<EPI, MASKED>), wgrid, dim3(256), 0, stream, (const bf16*)S, w, bias, (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, 1.f)
-#define LAUNCH_UP_WALK(EPI) do { if (mask) LAUNCH_UP_WALK_(EPI, true); else LAUNCH_UP_WALK_(EPI, false); } while (0)
-            if (epi == 0) LAUNCH_UP_WALK(0); else if (epi == 1) LAUNCH_UP_WALK(1); else LAUNCH_UP_WALK(2);
-#undef LAUNCH_UP_WALK
-#undef LAUNCH_UP_WALK_
+            dim3 wgrid((unsigned)(nunits < C1_MAX_WG ? nunits : C1_MAX_WG), 1, 1);
+            return with_epi(act, [&](auto epi) { return with_bool(mask != nullptr, [&](auto masked) {
+                hipLaunchKernelGGL((up_c1_mfma_walk_kernel<decltype(epi)::value, decltype(masked)::value>), wgrid, dim3(256), 0, stream, (const bf16*)S, w, bias,
+                                   (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, 1.f);
+                CVAE_CHECK_LAUNCH();
+                return CVAE_OK;
+            }); });
+        }
+        return with_nd(nd, [&](auto n) { return with_epi(act, [&](auto epi) { return with_bool(mask != nullptr, [&](auto masked) {
+            hipLaunchKernelGGL((up_c1_mfma_kernel<decltype(n)::value, decltype(epi)::value, decltype(masked)::value>), mgrid, dim3(256), 0, stream, (const bf16*)S, w, bias,
+                               (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, ntiles, act);
             CVAE_CHECK_LAUNCH();
             return CVAE_OK;
-        }
-#endif
-#define LAUNCH_UP_MFMA_(ND, EPI, MASKED) hipLaunchKernelGGL((up_c1_mfma_kernel<ND, EPI, MASKED>), mgrid, dim3(256), 0, stream, (const bf16*)S, w, bias, (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, ntiles, act)
-#define LAUNCH_UP_MFMA(ND, EPI) do { if (mask) LAUNCH_UP_MFMA_(ND, EPI, true); else LAUNCH_UP_MFMA_(ND, EPI, false); } while (0)
-        if (nd == 3) { if (epi == 0) LAUNCH_UP_MFMA(3, 0); else if (epi == 1) LAUNCH_UP_MFMA(3, 1); else LAUNCH_UP_MFMA(3, 2); }
-        else { if (epi == 0) LAUNCH_UP_MFMA(2, 0); else if (epi == 1) LAUNCH_UP_MFMA(2, 1); else LAUNCH_UP_MFMA(2, 2); }
-#undef LAUNCH_UP_MFMA
-#undef LAUNCH_UP_MFMA_
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        }); }); });
     }
     dim3 grid((unsigned)((2 * n + 255) / 256));
 #define LAUNCH_UP_C1(T, ND)                                                                                                          \
@@ -1084,18 +1072,18 @@ int cvae_conv_up_c1_fp8in_impl(const void* S8, const float* w, const float* bias
     const int tiles_d = (int)((sd + td - 1) / td), tiles_h = (int)((sh + th - 1) / th), tiles_w = (int)((sw + tw - 1) / tw);
     const long long ntiles = (long long)B * tiles_d * tiles_h * tiles_w;
     if (ntiles > 0x7fffffff) return CVAE_E_BADSHAPE;
-    int walk = (int)(ntiles / CVAE_C1U_WALK_MIN_UNITS);
+    int walk = (int)(ntiles / C1U_WALK_MIN_UNITS);
     if (walk < 1) walk = 1;
     if (walk > tiles_d) walk = tiles_d;
     const int segs = (tiles_d + walk - 1) / walk;
     const int nunits = (int)B * segs * tiles_h * tiles_w;
-    dim3 wgrid((unsigned)(nunits < CVAE_C1_MAX_WG ? nunits : CVAE_C1_MAX_WG), 1, 1);
-    const int epi = CVAE_EPI_OF(act);
-#define LAUNCH_UP_WALK8(EPI) hipLaunchKernelGGL((up_c1_mfma_walk_kernel<EPI, false, fp8>), wgrid, dim3(256), 0, stream, (const fp8*)S8, w, bias, (const bf16*)nullptr, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, in_scale)
-    if (epi == 0) LAUNCH_UP_WALK8(0); else if (epi == 1) LAUNCH_UP_WALK8(1); else LAUNCH_UP_WALK8(2);
-#undef LAUNCH_UP_WALK8
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    dim3 wgrid((unsigned)(nunits < C1_MAX_WG ? nunits : C1_MAX_WG), 1, 1);
+    return with_epi(act, [&](auto epi) {
+        hipLaunchKernelGGL((up_c1_mfma_walk_kernel<decltype(epi)::value, false, fp8>), wgrid, dim3(256), 0, stream, (const fp8*)S8, w, bias, (const bf16*)nullptr, (bf16*)L,
+                           (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, in_scale);
+        CVAE_CHECK_LAUNCH();
+        return CVAE_OK;
+    });
 }
 
 size_t cvae_conv_wgrad_c1_workspace_bytes(int64_t Cs, int nd) {
@@ -1116,11 +1104,7 @@ int cvae_conv_wgrad_c1(const void* S, const void* L, int l_dtype, float* dW, flo
     const long long total = (long long)B * tiles_d * tiles_h * tiles_w;
     // 2 workgroups per CU (256 CUs): measured in the step at 256 / 384 / 512 / 640 / 768 / 1024 / 2048 workgroups: 58 / 45 / 36 / 49 / 43 / 39 / 44 us
     // for enc1 — whole multiples of the CU count, and as few slabs as keep the loads in flight; slabs leave with plain stores
-#ifdef CVAE_TUNE                                             // tuning builds only (make EXTRA=-DCVAE_TUNE); clamped to the validated workspace
-    static const int c1_wgs = getenv("CVAE_TUNE_C1_SLABS") ? (atoi(getenv("CVAE_TUNE_C1_SLABS")) > 2048 ? 2048 : atoi(getenv("CVAE_TUNE_C1_SLABS"))) : 512;
-#else
     constexpr int c1_wgs = 512;
-#endif
     long long n_split = c1_wgs / (Cs / 32);
     if (n_split > total) n_split = total;
     if (n_split < 1) n_split = 1;

@@ -11,10 +11,12 @@
 //     materialised and each input byte crosses L2->LDS ~1.8x instead of 8x.
 //   * `up` is the transposed conv in its parity form: the 2x2x2 output parity classes are 8 independent k2/s1
 //     sub-convolutions (8 taps each), so no zero-insertion FLOPs are spent.
-//   * B (weights, pre-packed [tap][K/16][N][16] by cvae_conv_pack_weight): bf16 tiles of 2 x 2 waves fetch their fragments per wave straight
-//     from the packed global panels into a register ring ("BD"); the other forms stream them through a double-buffered LDS panel, 4 taps
-//     per barrier.  A second `up` kernel (conv_up_full_kernel) stages the halo of ALL input channels once and walks the output parities
-//     inside the workgroup; it serves the large grids of the decode sweep.
+//   * B (weights, pre-packed [tap][K/16][N][16] by cvae_conv_pack_weight): the 64-channel-tile forms of bf16 (and of fp8 3D `up`) run 1 x 2 waves x 2 K-split
+//     groups that fetch their fragments per wave straight from the packed global panels into a register ring ("BD", "TS"); every other form (fp32, 32-channel
+//     tiles, the remaining fp8 products) streams them through a double-buffered LDS panel, 4 taps per barrier.  DataForm (below the kernels) is the ONE table of
+//     which instance serves which product; dispatch_conv is the one place that lifts act / stage depth into template arguments.  A second `up` kernel
+//     (conv_up_full_kernel) stages the halo of ALL input channels once and walks the output parities inside the workgroup; it serves the large grids of the
+//     decode sweep (32-channel tiles only).
 //   * bf16: v_mfma_f32_32x32x16_bf16 (fp32 accumulate);  fp32: v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chain);  fp8: v_mfma_scale_f32_32x32x64_f8f6f4.
 //   * epilogue fuses bias + ReLU/Sigmoid (forward use) or the ReLU mask of the saved activation (backward use).
 // wgrad — M = Cs, N = Cl, K = positions.  Both operands are [position][channel] in memory, i.e. K-strided: bf16 uses
@@ -22,8 +24,6 @@
 //   one element per lane and needs no transpose.  Every workgroup leaves ONE fp32 slab [kh][kw][64 cs][32 cl] of partial sums with
 //   plain stores; wgrad_reduce_kernel adds the slabs in index order and writes the reference [Cs][Cl][taps] layout (no atomics).
 #include "common.h"
-#include <cstdlib>
-#include <type_traits>
 
 // Development aid (make EXTRA=-DCVAE_STAMP, tools/stamp_probe.py): thread 0 of every workgroup of conv_data_kernel records the
 // shader clock at its phase boundaries into a device array that cvae_debug_stamps() copies out.  Not compiled by default.
@@ -41,39 +41,16 @@ __device__ unsigned long long g_stamp[(size_t)CVAE_STAMP_WGS * CVAE_STAMP_SLOTS]
 
 namespace {
 
-#ifndef CVAE_BDIRECT
-#define CVAE_BDIRECT 1                  // bf16 data kernels fetch their weight fragments per wave (BD, below): 0.867 -> 0.832 ms/step at 128^3 B=4
-#endif
-#ifndef CVAE_WG_TILES
-#define CVAE_WG_TILES 16
-#endif
-#ifndef CVAE_WG_MIN_WG
-#define CVAE_WG_MIN_WG 64
-#endif
-#ifndef CVAE_KSPLIT_WAVES
-#define CVAE_KSPLIT_WAVES 1             // bf16 64-channel tiles: 2 x 2 waves = (K split) x (N sub-tile) instead of (M half) x (N sub-tile): 0.793 -> 0.785 ms/step
-#endif
-#ifndef CVAE_BD_GS
-#define CVAE_BD_GS 8
-#endif
-#ifndef CVAE_BD_HPRE
-#define CVAE_BD_HPRE 0
-#endif
-#ifndef CVAE_APIPE
-#define CVAE_APIPE 3
-#endif
-#ifndef CVAE_UPFULL
-#define CVAE_UPFULL 1
-#endif
-#ifndef CVAE_UPFULL_WIDE
-#define CVAE_UPFULL_WIDE 0
-#endif
-#ifndef CVAE_UPFULL_MIN_GRID
-#define CVAE_UPFULL_MIN_GRID 2048        // (tiles x channel blocks x batch) from which conv_up_full_kernel is used: many rounds of one workgroup per CU (the 240-row decode
-#endif                                   // sweep: -12 % on its 64 -> 32 channel layer); at the training step's 512 it measured +-0 against conv_data_kernel<UP>
-#ifndef CVAE_UPFULL_MIN_WG
-#define CVAE_UPFULL_MIN_WG 512
-#endif
+// ---- tunables: each may be overridden for an A/B build with make EXTRA=-DCVAE_<NAME>=<n> (CVAE_TUNABLE, common.h) ----
+CVAE_TUNABLE(BD_GS, 8);                 // k-steps per weight register group of the BD tap loop, chunks of >= 64 k-steps (3D down)
+CVAE_TUNABLE(APIPE, 3);                 // k-steps the activation ds_reads are issued ahead of their MFMAs (MI = 2 forms and conv_up_full_kernel)
+CVAE_TUNABLE(UPFULL_MIN_GRID, 2048);    // workgroups (tiles x channel blocks x batch) from which conv_up_full_kernel is used: many rounds of one workgroup per CU (the
+                                        // 240-row decode sweep: -12 % on its 64 -> 32 channel layer); at the training step's 512 it measured +-0 against conv_data_kernel<UP>
+CVAE_TUNABLE(UPFULL_MIN_WG, 512);       // workgroups below which conv_up_full_kernel spreads a tile's parity classes over sibling workgroups (~2 per CU)
+CVAE_TUNABLE(XPAIR_MIN_WGS, 2048);      // workgroups from which a 3D `up` layer at most half a tile wide puts two samples in one tile (XB = 2): the decode sweep's 4^3 -> 8^3 layer
+CVAE_TUNABLE(XPAIR_2D_MIN_WGS, 512);    // the same for 2D layers, `down` and `up` (the 7 x 7 grids of the MNIST model at batch 1024)
+CVAE_TUNABLE(WG_TILES, 16);             // wgrad: tiles of 128 positions summed into one slab
+CVAE_TUNABLE(WG_MIN_WG, 64);            // wgrad: workgroups a layer gets at least, whatever WG_TILES says
 
 struct ConvGeom {
     int B;
@@ -372,7 +349,7 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
     // With TS = 2 a wave walks its OWN steps u = 0 .. STEPS - 1 <-> stage step 2 u + ts.  The ts part never enters the loops: for KH = 1 it is the
     // tap's low bit (down: the odd-x halo plane and the next weight tap; up: one slot to the right and weight tap kw - 2), for KH = 2 the second
     // 16-channel half of the stage — a constant offset of this wave's LDS and weight base addresses.
-    constexpr int STEPS = NG * 4 * KH / TS, GS = STEPS >= 64 ? CVAE_BD_GS : (STEPS >= 16 ? (MI >= 4 ? 4 : 8) : STEPS / 2), NGRP = STEPS / GS;      // MI = 4: a step is 4 MFMAs, 4 steps are as long as 8
+    constexpr int STEPS = NG * 4 * KH / TS, GS = STEPS >= 64 ? BD_GS : (STEPS >= 16 ? (MI >= 4 ? 4 : 8) : STEPS / 2), NGRP = STEPS / GS;      // MI = 4: a step is 4 MFMAs, 4 steps are as long as 8
     static_assert(!BD || (NGRP % 2 == 0 && GS * NGRP == STEPS && (GS * TS) % KH == 0), "BD walks the groups in pairs");
     static_assert(TS == 1 || KH <= 2, "K split: one or two k-steps per stage");
     const long long w_tap = (long long)nch16 * Cout * 16;     // elements between two taps of the packed panels
@@ -453,14 +430,14 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
     // UP with 32-channel stages (long K loops on small grids): the NEXT stage's halo is requested right after this stage's LDS image is
     // complete and lands under the tap loop (-5 %).  Elsewhere the prefetch loses: DOWN stages 14 pieces per thread (registers), and the
     // Cin = 64 `up` launches fill the chip, where the co-resident workgroups already hide the stage (+4 % measured).
-    constexpr bool HPRE = (UP && KH == 2) || (BD && CVAE_BD_HPRE);
+    constexpr bool HPRE = UP && KH == 2;
     // Groups gp (weights in qa) and gp + 1 (qb) as ONE run of 2 GS k-steps; the group after them goes back into qa once qa is spent.  The activation
     // fragments are software-pipelined by hand: the ds_reads of step i + APD are issued in front of the MFMAs of step i (APD + 1 register slots), so an
     // MFMA never waits for a read issued right before it — left to itself the compiler emits read / s_waitcnt / MFMA per step and the loop runs at
     // LDS latency (~35 % of the MFMA rate by the stamp probes, one wave per SIMD).
     auto bd_pair = [&](int chunk, int gp) {
         // in MFMA steps (fp8: one step = two k-steps).  MI = 4: 4 reads per k-step, 2 k-steps ahead is as many in flight
-        constexpr int NS = 2 * GSX, APW = (MI >= 4) ? 2 / PW : (CVAE_APIPE + PW - 1) / PW, APD = APW < NS ? APW : NS - 1;
+        constexpr int NS = 2 * GSX, APW = (MI >= 4) ? 2 / PW : (APIPE + PW - 1) / PW, APD = APW < NS ? APW : NS - 1;
         load_q(qb, chunk, gp + 1);
         SF ar[APD + 1][MI];
         auto lda = [&](int slot, int ix) {
@@ -765,24 +742,12 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const float* __
     if (f8.amax) amax_publish_wg(f8.amax, amx, blockIdx.x, red);
 }
 
-#ifndef CVAE_XPAIR
-#define CVAE_XPAIR 1                    // two samples per tile (XB = 2) for layers at most half a tile wide
-#endif
-#ifndef CVAE_XPAIR_MIN_WGS
-#define CVAE_XPAIR_MIN_WGS 2048
-#endif
-#ifndef CVAE_XPAIR_2D
-#define CVAE_XPAIR_2D 1                 // the same for 2D layers, `down` and `up`
-#endif
-#ifndef CVAE_XPAIR_2D_MIN_WGS
-#define CVAE_XPAIR_2D_MIN_WGS 512
-#endif
 // Kernel-form selection of one `up` launch.  The library picks by launch size (-1 / 0 = automatic); cvae_conv_up and cvae_conv_fp8 let a caller
 // force a form for ONE call — the tests run every narrow case through both forms that way.  No process-wide state.
 struct UpVariant {
-    int upfull = -1;            // conv_up_full_kernel: -1 by grid size (CVAE_UPFULL_MIN_GRID), 0 never, 1 whenever the shape fits it
-    int xpair = -1;             // two samples per tile for layers at most half a tile wide: -1 by grid size (CVAE_XPAIR_MIN_WGS), 0 never, 1 always
-    long long walk_units = 0;   // single-channel output layer: 0 = by launch size (CVAE_C1U_WALK_MIN_UNITS), > 0 = that many units
+    int upfull = -1;            // conv_up_full_kernel: -1 by grid size (UPFULL_MIN_GRID), 0 never, 1 whenever the shape fits it
+    int xpair = -1;             // two samples per tile for layers at most half a tile wide: -1 by grid size (XPAIR_MIN_WGS / XPAIR_2D_MIN_WGS), 0 never, 1 always
+    long long walk_units = 0;   // single-channel output layer: 0 = by launch size (C1U_WALK_MIN_UNITS, conv_c1.hip), > 0 = that many units
 };
 
 // Split-K factor for a launch of `nwg` workgroups over `nchunks` channel chunks: the layers with 8^3 / 4^3 grids fill a fraction
@@ -800,29 +765,60 @@ static int pick_ksplit(bool up, long long nwg, int nchunks) {
     return best;
 }
 
-template <typename T, int ND, bool UP, int WM, int WN, int MI, int NI, int EPI, int KH = 1, typename TO = T, bool BD = (CVAE_BDIRECT && sizeof(T) == 2 && WM <= 2), int TS = 1, int XB = 1>
-int launch_data_epi(const void* in, const void* wp, const float* bias, const void* mask, void* out, ConvGeom g, int act, void* workspace,
-                    size_t workspace_bytes, hipStream_t stream, float acc_scale = 1.f, float out_scale = 1.f, F8Side f8 = F8Side{nullptr, nullptr, nullptr},
-                    UpVariant var = UpVariant{}) {
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    using TL = Tile<ND, BM>;
+// THE tile form of conv_data_kernel that serves (T, ND, UP, output channel tile): WIDE = 64-channel tiles (Cout % 64 == 0; every `down`), else 32.
+//   * KSPLIT forms (bf16; fp8 3D `up`): 1 x 2 waves x 2 K-split groups, MI = 4, weights fetched per wave (BD).  bf16: 0.867 -> 0.832 ms/step at 128^3 B = 4 for BD
+//     against LDS weight panels, 0.793 -> 0.785 for (K split) x (N sub-tile) against (M half) x (N sub-tile) waves.  fp8 (rocprofv3 device durations, 4 x 128^3
+//     shapes, profiles/r03_fp8_forms.txt): `up` keeps the bf16 form (dec1 9.9 vs 11.2 us, dec2 8.1 vs 8.4 us); `down` wants its weights on LDS panels, since the
+//     per-wave fetch needs > 256 VGPRs with 8-register fp8 operands (59 spilled; enc2 57 us against 36 us).
+//   * otherwise weights through LDS panels: 2 x 2 waves (64-channel tiles) or 4 x 1 waves (32-channel tiles, 256 rows), MI = 2.
+template <typename T, int ND, bool UP, bool WIDE> struct DataForm {
+    static constexpr bool KSPLIT = WIDE && (std::is_same<T, bf16>::value || (IsF8<T>::value && UP && ND == 3));
+    static constexpr int WM = KSPLIT ? 1 : (WIDE ? 2 : 4), WN = WIDE ? 2 : 1, MI = KSPLIT ? 4 : 2, NI = 1, TS = KSPLIT ? 2 : 1;
+    static constexpr bool BD = KSPLIT;
+    static constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
+    // 32-channel stages (KH = 2): bf16 `up` only, where the K loop is long and the grid small (measured: Cin 256: -12 %, 128: -5 %, 64: +2 %)
+    static constexpr int KH_MAX = (UP && std::is_same<T, bf16>::value) ? 2 : 1;
+    static int kh(const ConvGeom& g) { return (KH_MAX == 2 && g.Cs >= 128 && (g.Cs % 32) == 0) ? 2 : 1; }
+    // XB = 2 (two samples per tile) exists for these forms; launch_data_epi takes it by layer width and launch size
+    static constexpr bool XPAIR = sizeof(T) <= 2 && ((UP && ND == 3 && (TS == 2 || IsF8<T>::value)) || ND == 2);
+};
+
+struct ConvArgs {
+    const void *in, *wp;
+    const float* bias;
+    const void* mask;
+    void* out;
+    ConvGeom g;
+    int act;
+    void* ws;
+    size_t ws_bytes;
+    hipStream_t stream;
+    float acc_scale = 1.f, out_scale = 1.f;
+    F8Side f8 = F8Side{nullptr, nullptr, nullptr};
+    UpVariant var = UpVariant{};
+};
+
+template <typename T, int ND, bool UP, bool WIDE, int EPI, int KH, typename TO, int XB = 1>
+int launch_data_epi(const ConvArgs& a) {
+    using F = DataForm<T, ND, UP, WIDE>;
+    using TL = Tile<ND, F::BM>;
+    ConvGeom g = a.g;
     constexpr int ID = (ND == 3) ? (UP ? TL::TD + 1 : 2 * TL::TD + 2) : 1;
-    constexpr int IH = UP ? TL::TH + 1 : 2 * TL::TH + 2, IW = UP ? TL::TW + 1 : 2 * TL::TW + 2;
+    constexpr int IH = UP ? TL::TH + 1 : 2 * TL::TH + 2;
     constexpr int FB = 8 * sizeof(T);
-    static_assert(IW >= 0, "");
-    constexpr size_t LDS_MAIN = (size_t)2 * KH * (UP ? 1 : 2) * ID * IH * HaloPitch<ND, UP>::RS * FB + (BD ? 0 : (size_t)2 * 4 * KH * 2 * BN * FB);
-    constexpr size_t LDS_X = TS == 2 ? (size_t)WM * WN * TS * (MI / 2) * NI * 16 * 64 * sizeof(float) : 0;      // the K split's accumulator exchange
+    constexpr size_t LDS_MAIN = (size_t)2 * KH * (UP ? 1 : 2) * ID * IH * HaloPitch<ND, UP>::RS * FB + (F::BD ? 0 : (size_t)2 * 4 * KH * 2 * F::BN * FB);
+    constexpr size_t LDS_X = F::TS == 2 ? (size_t)F::WM * F::WN * F::TS * (F::MI / 2) * F::NI * 16 * 64 * sizeof(float) : 0;      // the K split's accumulator exchange
     constexpr size_t LDS = LDS_MAIN > LDS_X ? LDS_MAIN : LDS_X;
     static_assert(LDS <= 160 * 1024, "LDS tile exceeds the 160 KiB of a CDNA4 CU");
     const int md = UP ? ((ND == 3) ? (g.ld + 1) / 2 : 1) : g.sd, mh = UP ? (g.lh + 1) / 2 : g.sh, mw = UP ? (g.lw + 1) / 2 : g.sw;
-    if constexpr (CVAE_XPAIR && XB == 1 && sizeof(T) <= 2 && ((UP && ND == 3 && (TS == 2 || IsF8<T>::value)) || (ND == 2 && CVAE_XPAIR_2D))) {
+    if constexpr (F::XPAIR && XB == 1) {
         // a layer at most half a tile wide, on a launch that fills the chip several times over (the decode sweep's 4^3 -> 8^3 layer; round 3: the 7 x 7 grids of the
         // MNIST model at batch 1024, where one image fills 49 of a tile's 128 positions, in both directions): two samples per tile
-        const long long wgs = (long long)((md + TL::TD - 1) / TL::TD) * ((mh + TL::TH - 1) / TL::TH) * ((UP ? g.Cl : g.Cs) / BN) * (UP ? (ND == 3 ? 8 : 4) : 1) * g.B;
-        if (mw <= TL::TW / 2 && g.B >= 2 && (var.xpair == 1 || (var.xpair < 0 && wgs >= (ND == 3 ? CVAE_XPAIR_MIN_WGS : CVAE_XPAIR_2D_MIN_WGS))))
-            return launch_data_epi<T, ND, UP, WM, WN, MI, NI, EPI, KH, TO, BD, TS, 2>(in, wp, bias, mask, out, g, act, workspace, workspace_bytes, stream, acc_scale, out_scale, f8, var);
+        const long long wgs = (long long)((md + TL::TD - 1) / TL::TD) * ((mh + TL::TH - 1) / TL::TH) * ((UP ? g.Cl : g.Cs) / F::BN) * (UP ? (ND == 3 ? 8 : 4) : 1) * g.B;
+        if (mw <= TL::TW / 2 && g.B >= 2 && (a.var.xpair == 1 || (a.var.xpair < 0 && wgs >= (ND == 3 ? XPAIR_MIN_WGS : XPAIR_2D_MIN_WGS))))
+            return launch_data_epi<T, ND, UP, WIDE, EPI, KH, TO, 2>(a);
     }
-    auto kern = conv_data_kernel<T, ND, UP, WM, WN, MI, NI, EPI, KH, TO, BD, TS, XB>;
+    auto kern = conv_data_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
@@ -832,49 +828,46 @@ int launch_data_epi(const void* in, const void* wp, const float* bias, const voi
     const int Cout = UP ? g.Cl : g.Cs, Cin = (UP ? g.Cs : g.Cl) / (IsF8<T>::value ? 2 : 1);
     const int npar = UP ? ((ND == 3) ? 8 : 4) : 1;
     const long long tiles = (long long)g.tiles_d * g.tiles_h * g.tiles_w;
-    long long gy = (long long)(Cout / BN) * npar;
+    long long gy = (long long)(Cout / F::BN) * npar;
     const int64_t total = (int64_t)g.B * (UP ? (int64_t)g.ld * g.lh * g.lw : (int64_t)g.sd * g.sh * g.sw) * Cout;
     int ksplit = pick_ksplit(UP, tiles * gy * g.B, Cin / (16 * KH));
-    if (!workspace || workspace_bytes < (size_t)ksplit * total * sizeof(float)) ksplit = 1;     // no (or too small a) workspace: unsplit
+    if (!a.ws || a.ws_bytes < (size_t)ksplit * total * sizeof(float)) ksplit = 1;     // no (or too small a) workspace: unsplit
     if (IsF8<T>::value && sizeof(TO) != 2) ksplit = 1;       // the finish pass writes bf16
     gy *= ksplit;
     if (gy > 65535 || g.B > 65535) return CVAE_E_BADSHAPE;
     dim3 grid((unsigned)tiles, (unsigned)gy, (unsigned)((g.B + XB - 1) / XB));
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * TS * 64), LDS, stream, (const T*)in, (const T*)wp, bias, (const TO*)mask, (TO*)out, g, act, (float*)workspace, ksplit,
-                       acc_scale, out_scale, f8);
+    hipLaunchKernelGGL(kern, grid, dim3(F::WM * F::WN * F::TS * 64), LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const TO*)a.mask, (TO*)a.out, g, a.act,
+                       (float*)a.ws, ksplit, a.acc_scale, a.out_scale, a.f8);
     CVAE_CHECK_LAUNCH();
     if constexpr (sizeof(TO) != 1) if (ksplit > 1) {
-        hipLaunchKernelGGL((conv_splitk_finish_kernel<TO, EPI>), dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, stream, (const float*)workspace, bias,
-                           (const TO*)mask, (TO*)out, total, Cout, ksplit, act, IsF8<T>::value ? acc_scale : 1.f, f8);
+        hipLaunchKernelGGL((conv_splitk_finish_kernel<TO, EPI>), dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, a.stream, (const float*)a.ws, a.bias,
+                           (const TO*)a.mask, (TO*)a.out, total, Cout, ksplit, a.act, IsF8<T>::value ? a.acc_scale : 1.f, a.f8);
         CVAE_CHECK_LAUNCH();
     }
     return CVAE_OK;
 }
 
-template <typename T, int ND, bool UP, int WM, int WN, int MI, int NI, int TS = 1>
-int launch_data(const void* in, const void* wp, const float* bias, const void* mask, void* out, ConvGeom g, int act, void* ws, size_t wsb, hipStream_t stream, UpVariant var = UpVariant{}, F8Side side = F8Side{nullptr, nullptr, nullptr}) {
-    constexpr bool BDX = CVAE_BDIRECT && sizeof(T) == 2 && WM <= 2;
-    // 32-channel stages pay where the K loop is long and the grid small (measured: Cin 256: -12 %, 128: -5 %, 64: +2 %)
-    if (UP && sizeof(T) == 2 && g.Cs >= 128 && (g.Cs % 32) == 0) {
-        constexpr int KH2 = (UP && sizeof(T) == 2) ? 2 : 1;
-        if (act == CVAE_ACT_NONE) return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 0, KH2, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
-        if (act == CVAE_ACT_RELU) return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 1, KH2, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
-        return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 2, KH2, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
-    }
-    if (act == CVAE_ACT_NONE) return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 0, 1, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
-    if (act == CVAE_ACT_RELU) return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 1, 1, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
-    return launch_data_epi<T, ND, UP, WM, WN, MI, NI, 2, 1, T, BDX, TS>(in, wp, bias, mask, out, g, act, ws, wsb, stream, 1.f, 1.f, side, var);
+// One `down` / `up` product through conv_data_kernel: the form from DataForm, act -> EPI and the stage depth KH lifted here and nowhere else.
+template <typename T, int ND, bool UP, bool WIDE, typename TO = T>
+int dispatch_conv(const ConvArgs& a) {
+    using F = DataForm<T, ND, UP, WIDE>;
+    return with_epi(a.act, [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        return F::kh(a.g) == 2 ? launch_data_epi<T, ND, UP, WIDE, EPI, F::KH_MAX, TO>(a) : launch_data_epi<T, ND, UP, WIDE, EPI, 1, TO>(a);
+    });
 }
 
-// Workspace the split-K path of launch_data would use for this geometry (0: the launch fills the chip without it).
-template <int ND, bool UP, int BM, int BN>
+// Workspace the split-K path of dispatch_conv would use for this geometry (0: the launch fills the chip without it).  The tile extents do not depend on the dtype.
+template <int ND, bool UP, bool WIDE>
 size_t data_workspace_bytes(const ConvGeom& g) {
-    using TL = Tile<ND, BM>;
+    using F = DataForm<float, ND, UP, WIDE>;
+    static_assert(F::BM == DataForm<bf16, ND, UP, WIDE>::BM && F::BN == DataForm<bf16, ND, UP, WIDE>::BN, "one workspace size for both dtypes");
+    using TL = Tile<ND, F::BM>;
     const int md = UP ? ((ND == 3) ? (g.ld + 1) / 2 : 1) : g.sd, mh = UP ? (g.lh + 1) / 2 : g.sh, mw = UP ? (g.lw + 1) / 2 : g.sw;
     const long long tiles = (long long)((md + TL::TD - 1) / TL::TD) * ((mh + TL::TH - 1) / TL::TH) * ((mw + TL::TW - 1) / TL::TW);
     const int Cout = UP ? g.Cl : g.Cs, Cin = UP ? g.Cs : g.Cl;
     const int npar = UP ? ((ND == 3) ? 8 : 4) : 1;
-    const int ksplit = pick_ksplit(UP, tiles * (Cout / BN) * npar * g.B, Cin / 16);
+    const int ksplit = pick_ksplit(UP, tiles * (Cout / F::BN) * npar * g.B, Cin / 16);
     if (ksplit <= 1) return 0;
     return (size_t)ksplit * g.B * (UP ? (size_t)g.ld * g.lh * g.lw : (size_t)g.sd * g.sh * g.sw) * Cout * sizeof(float);
 }
@@ -889,7 +882,7 @@ size_t data_workspace_bytes(const ConvGeom& g) {
 // buffers, ONE barrier per half panel, fetched two half panels ahead: a per-wave fetch of the same fragments by every wave ran into the
 // L2 -> L1 bandwidth, 22 B/clk/CU).  What the stamp probes and the ISA showed about the inner loop, with one wave per SIMD:
 //   * the compiler sinks every ds_read to just in front of the MFMA that uses it (read / s_waitcnt / MFMA per step): the reads are issued
-//     CVAE_APIPE steps ahead by hand and pinned with sched_barrier;
+//     APIPE steps ahead by hand and pinned with sched_barrier;
 //   * with in-order issue every non-MFMA instruction between two MFMAs costs issue time the MFMA pipe idles for once there are more than
 //     ~6 per MFMA: the LDS image is position-major ([halo slot][8-channel piece], pitch NPC + 1 pieces: the odd pitch keeps the reads
 //     conflict-free exactly as the plane-major image did, and the pieces of one position, stored by consecutive lanes, hit different banks),
@@ -973,7 +966,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __r
     f32x16 acc[MI][NI];
     const char* abase[MI];                                   // per parity: LDS address of (lane position + parity shift, piece h)
     auto compute_hp = [&](const char* wb, int th) {          // HTAP * KCH k-steps, both operands from LDS, reads APD steps ahead of their MFMAs
-        constexpr int NS = HTAP * KCH, APD = CVAE_APIPE < NS ? CVAE_APIPE : NS - 1;
+        constexpr int NS = HTAP * KCH, APD = APIPE < NS ? APIPE : NS - 1;
         Frag<T> ar[APD + 1][MI], br[APD + 1][NI];
         const char* bb0 = wb + (size_t)(h * BN + wn * NI * 32 + r) * FB;
         auto ld = [&](int slot, int i) {
@@ -1141,57 +1134,51 @@ template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH> constexpr
     return ((size_t)(ID * IH * HaloPitch<ND, true>::RS) * (2 * KCH + 1) + (size_t)2 * (((ND == 3) ? 8 : 4) / 2) * KCH * 2 * (WN * NI * 32)) * 8 * sizeof(T);
 }
 
-// Launch of conv_up_full_kernel; CVAE_E_UNSUPPORTED when this (tile, channel count) pair does not fit the LDS (the caller falls back to launch_data<UP>).
-template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH, typename TO = T>
-int launch_up_full(const void* in, const void* wp, const float* bias, const void* mask, void* out, ConvGeom g, int act, hipStream_t stream,
-                   UpVariant var, float acc_scale = 1.f, float out_scale = 1.f) {
+// Launch of conv_up_full_kernel; CVAE_E_UNSUPPORTED when this channel count does not fit the LDS or the grid is below UPFULL_MIN_GRID (the caller falls back
+// to dispatch_conv<UP>).  Only the 32-channel tile form (DataForm<.., WIDE = false>) goes here: on 64-channel tiles the kernel measured slower than
+// conv_data_kernel<UP> with BD.
+template <typename T, int ND, int KCH>
+int launch_up_full(const ConvArgs& a) {
+    using F = DataForm<T, ND, true, false>;
+    constexpr int WM = F::WM, WN = F::WN, MI = F::MI, NI = F::NI;
     constexpr size_t LDS = up_full_lds_bytes<T, ND, WM, WN, MI, NI, KCH>();
-    if constexpr (LDS > 160 * 1024 || (KCH * 2 * WN * NI * 32) % (WM * WN * 64) != 0) {
+    if constexpr (LDS > 160 * 1024 || (KCH * 2 * F::BN) % (WM * WN * 64) != 0) {
         return CVAE_E_UNSUPPORTED;
     } else {
-        constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-        using TL = Tile<ND, BM>;
+        using TL = Tile<ND, F::BM>;
+        ConvGeom g = a.g;
         const int md = (ND == 3) ? (g.ld + 1) / 2 : 1, mh = (g.lh + 1) / 2, mw = (g.lw + 1) / 2;
         g.tiles_d = (md + TL::TD - 1) / TL::TD; g.tiles_h = (mh + TL::TH - 1) / TL::TH; g.tiles_w = (mw + TL::TW - 1) / TL::TW;
         const long long tiles = (long long)g.tiles_d * g.tiles_h * g.tiles_w;
-        const int npar = (ND == 3) ? 8 : 4, nblocks = g.Cl / BN;
-        if (var.upfull == 0 || (var.upfull < 0 && tiles * nblocks * g.B < CVAE_UPFULL_MIN_GRID)) return CVAE_E_UNSUPPORTED;
+        const int npar = (ND == 3) ? 8 : 4, nblocks = g.Cl / F::BN;
+        if (a.var.upfull == 0 || (a.var.upfull < 0 && tiles * nblocks * g.B < UPFULL_MIN_GRID)) return CVAE_E_UNSUPPORTED;
         // parity classes per workgroup: all of them (one halo stage per tile) once the grid has ~2 workgroups per CU without splitting them
         int psplit = 1;
-        while (psplit < npar && tiles * nblocks * g.B * psplit < CVAE_UPFULL_MIN_WG) psplit *= 2;
+        while (psplit < npar && tiles * nblocks * g.B * psplit < UPFULL_MIN_WG) psplit *= 2;
         const long long gy = (long long)nblocks * psplit;
         if (gy > 65535 || g.B > 65535) return CVAE_E_BADSHAPE;
-        const int e = (act == CVAE_ACT_NONE) ? 0 : (act == CVAE_ACT_RELU ? 1 : 2);
         dim3 grid((unsigned)tiles, (unsigned)gy, (unsigned)g.B), block(WM * WN * 64);
-#define UPFULL_LAUNCH(EPI)                                                                                                                          \
-        {                                                                                                                                           \
-            auto kern = conv_up_full_kernel<T, ND, WM, WN, MI, NI, KCH, EPI, TO>;                                                                   \
-            static bool attr_set = false;                                                                                                           \
-            if (!attr_set) {                                                                                                                        \
-                if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH; \
-                attr_set = true;                                                                                                                    \
-            }                                                                                                                                       \
-            hipLaunchKernelGGL(kern, grid, block, LDS, stream, (const T*)in, (const T*)wp, bias, (const TO*)mask, (TO*)out, g, act, npar / psplit,   \
-                               acc_scale, out_scale);                                                                                               \
-        }
-        if (e == 0) UPFULL_LAUNCH(0) else if (e == 1) UPFULL_LAUNCH(1) else UPFULL_LAUNCH(2)
-#undef UPFULL_LAUNCH
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_epi(a.act, [&](auto epi) {
+            auto kern = conv_up_full_kernel<T, ND, WM, WN, MI, NI, KCH, decltype(epi)::value, T>;
+            static bool attr_set = false;
+            if (!attr_set) {
+                if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
+                attr_set = true;
+            }
+            hipLaunchKernelGGL(kern, grid, block, LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const T*)a.mask, (T*)a.out, g, a.act, npar / psplit,
+                               a.acc_scale, a.out_scale);
+            CVAE_CHECK_LAUNCH();
+            return CVAE_OK;
+        });
     }
 }
 
 // `up` through the whole-K kernel when the input channel count is one it is built for (64 / 128 / 256 where the halo fits): CVAE_E_UNSUPPORTED otherwise.
-template <typename T, int ND, int WM, int WN, int MI, int NI, typename TO = T>
-int try_up_full(const void* in, const void* wp, const float* bias, const void* mask, void* out, const ConvGeom& g, int act, hipStream_t stream,
-                UpVariant var, float acc_scale = 1.f, float out_scale = 1.f) {
-    if constexpr (!CVAE_UPFULL || (WN * NI > 1 && !CVAE_UPFULL_WIDE)) {      // the 64-channel-tile form measured slower than conv_data_kernel<UP> with BD: not instantiated
-        return CVAE_E_UNSUPPORTED;
-    } else {
-        if (g.Cs == 64) return launch_up_full<T, ND, WM, WN, MI, NI, 4, TO>(in, wp, bias, mask, out, g, act, stream, var, acc_scale, out_scale);
-        if (g.Cs == 128) return launch_up_full<T, ND, WM, WN, MI, NI, 8, TO>(in, wp, bias, mask, out, g, act, stream, var, acc_scale, out_scale);
-        if (g.Cs == 256) return launch_up_full<T, ND, WM, WN, MI, NI, 16, TO>(in, wp, bias, mask, out, g, act, stream, var, acc_scale, out_scale);
-    }
+template <typename T, int ND>
+int try_up_full(const ConvArgs& a) {
+    if (a.g.Cs == 64) return launch_up_full<T, ND, 4>(a);
+    if (a.g.Cs == 128) return launch_up_full<T, ND, 8>(a);
+    if (a.g.Cs == 256) return launch_up_full<T, ND, 16>(a);
     return CVAE_E_UNSUPPORTED;
 }
 
@@ -1719,9 +1706,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradReduceTable tb) 
 }
 
 #define WGRAD_MAX_WG 512
-#ifndef CVAE_WGRAD_XPAIR
-#define CVAE_WGRAD_XPAIR 1
-#endif
 template <typename T, int ND> constexpr size_t wgrad_lds_bytes() {
     using TL = Tile<ND, 128>;
     return (size_t)128 * 64 * sizeof(T) + (size_t)TL::TD * (2 * TL::TH + 2) * (2 * TL::TW + 2 + (ND == 2 ? 2 : 0)) * 32 * sizeof(T);
@@ -1733,7 +1717,7 @@ int plan_wgrad(const void* S, const void* L, float* ws, float* dW, float* dbias,
     using TL = Tile<ND, 128>;
     g.tiles_d = (g.sd + TL::TD - 1) / TL::TD; g.tiles_h = (g.sh + TL::TH - 1) / TL::TH; g.tiles_w = (g.sw + TL::TW - 1) / TL::TW;
     // 2D layers at most half a tile wide (7 x 7, 4 x 4 maps): two samples per tile — a property of the layer's shape alone, like the slab count below
-    const int xb = (CVAE_WGRAD_XPAIR && ND == 2 && g.sw <= TL::TW / 2 && g.B >= 2) ? 1 : 0;
+    const int xb = (ND == 2 && g.sw <= TL::TW / 2 && g.B >= 2) ? 1 : 0;
     const long long total_tiles = (long long)(xb ? (g.B + 1) / 2 : g.B) * g.tiles_d * g.tiles_h * g.tiles_w;
     const int cb = (g.Cs / 64) * (g.Cl / 32), tg = (ND == 3) ? 4 : 1;
     // each workgroup ends with a 128 KB slab: ~2 workgroups per CU at most, and >= 4 tiles of work per slab
@@ -1745,16 +1729,12 @@ int plan_wgrad(const void* S, const void* L, float* ws, float* dW, float* dbias,
     long long by_tiles = total_tiles / 4;
     if (by_tiles < floor_split) by_tiles = floor_split;
     if (n_split > by_tiles) n_split = by_tiles;
-#ifdef CVAE_TUNE                                             // tuning builds only (make EXTRA=-DCVAE_TUNE, tools/kbench.py): never in the shipped library
-    if (const char* e = getenv("CVAE_TUNE_WGRAD_NSPLIT")) n_split = atoll(e);
-    if (n_split * cb * tg > WGRAD_MAX_WG && n_split > 1) n_split = WGRAD_MAX_WG / ((long long)cb * tg) > 0 ? WGRAD_MAX_WG / ((long long)cb * tg) : 1;   // stay inside the validated workspace
-#endif
-    {   // ~CVAE_WG_TILES tiles of 128 positions per slab, at least CVAE_WG_MIN_WG workgroups: a function of THIS layer only, the same whether the layer
+    {   // ~WG_TILES tiles of 128 positions per slab, at least WG_MIN_WG workgroups: a function of THIS layer only, the same whether the layer
         // is launched alone (cvae_conv_wgrad) or as one entry of a grouped launch (cvae_conv_wgrad_multi) — the summation order, and with it every bit
         // of the gradient, does not depend on how the caller batches its launches
-        long long req = (total_tiles + CVAE_WG_TILES - 1) / CVAE_WG_TILES;
+        long long req = (total_tiles + WG_TILES - 1) / WG_TILES;
         const long long groups = (long long)cb * tg;
-        if (req * groups < CVAE_WG_MIN_WG) req = (CVAE_WG_MIN_WG + groups - 1) / groups;
+        if (req * groups < WG_MIN_WG) req = (WG_MIN_WG + groups - 1) / groups;
         if (req < n_split) n_split = req;
     }
     if (n_split_req > 0 && n_split_req < n_split) n_split = n_split_req;
@@ -1904,13 +1884,11 @@ extern "C" size_t cvae_conv_data_workspace_bytes(int64_t B, int64_t sd, int64_t 
                                                   int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int for_up) {
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd) || B == 0 || Cl == 1) return 0;
     GEOM_INIT();
-    if (!for_up) {
-        if (Cl % 16 || Cs % 64) return 0;
-        return nd == 3 ? data_workspace_bytes<3, false, 128, 64>(g) : data_workspace_bytes<2, false, 128, 64>(g);
-    }
-    if (Cs % 16 || Cl % 32) return 0;
-    if (Cl % 64 == 0) return nd == 3 ? data_workspace_bytes<3, true, 128, 64>(g) : data_workspace_bytes<2, true, 128, 64>(g);
-    return nd == 3 ? data_workspace_bytes<3, true, 256, 32>(g) : data_workspace_bytes<2, true, 256, 32>(g);
+    const bool wide = !for_up || Cl % 64 == 0;
+    if (for_up ? (Cs % 16 || Cl % 32) : (Cl % 16 || Cs % 64)) return 0;
+    return with_nd(nd, [&](auto n) { return with_bool(for_up != 0, [&](auto up) { return with_bool(wide, [&](auto wd) {
+        return data_workspace_bytes<decltype(n)::value, decltype(up)::value, decltype(wd)::value>(g);
+    }); }); });
 }
 
 // ReLU masks as BITS (F8Side, common.h): mask_bits replaces `mask` (1 bit per element of the result instead of the saved activation: 1/16 of the
@@ -1935,14 +1913,8 @@ extern "C" int cvae_conv_down(const void* L, const void* w, const float* bias, c
     if (Cl == 1) return cvae_conv_down_c1(L, dtype, (const float*)w, bias, mask, S, B, sd, sh, sw, Cs, ld, lh, lw, nd, dtype, act, st, side);
     if (Cl % 16 || Cs % 64) return CVAE_E_UNSUPPORTED;
     GEOM_INIT();
-#if CVAE_KSPLIT_WAVES
-    if (dtype == CVAE_BF16) return nd == 3 ? launch_data<bf16, 3, false, 1, 2, 4, 1, 2>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side)
-                                           : launch_data<bf16, 2, false, 1, 2, 4, 1, 2>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side);
-#endif
-    if (dtype == CVAE_BF16) return nd == 3 ? launch_data<bf16, 3, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side)
-                                           : launch_data<bf16, 2, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side);
-    return nd == 3 ? launch_data<float, 3, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side)
-                   : launch_data<float, 2, false, 2, 2, 2, 1>(L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, var, side);
+    const ConvArgs a{L, w, bias, mask, S, g, act, workspace, workspace_bytes, st, 1.f, 1.f, side, var};
+    return with_dtype(dtype, [&](auto t) { return with_nd(nd, [&](auto n) { return dispatch_conv<decltype(t), decltype(n)::value, false, true>(a); }); });
 }
 // ---- the single-channel image end of the network, image read in the dtype it is stored in (no cast pass in front of the first conv) ----
 extern "C" int cvae_conv_image_supported(const void* L, int64_t lw, int l_dtype, int dtype) {
@@ -2003,22 +1975,18 @@ extern "C" int cvae_conv_up(const void* S, const void* w, const float* bias, con
     if (Cl == 1) return cvae_conv_up_c1(S, (const float*)w, bias, mask, L, B, sd, sh, sw, Cs, ld, lh, lw, nd, dtype, act, st, var.walk_units);
     if (Cs % 16 || Cl % 32) return CVAE_E_UNSUPPORTED;
     GEOM_INIT();
-    const bool wide = (Cl % 64) == 0;     // N tile 64 (2x2 waves, 128 rows) else N tile 32 (4x1 waves, 256 rows)
-    if (dtype == CVAE_BF16) {
-        int rc = CVAE_E_UNSUPPORTED;
-        if (side.mask_bits || side.bits_out) {}      // the whole-K kernel knows the tensor form of the mask only (inference sweeps: no mask at all)
-        else if (nd == 3) rc = wide ? try_up_full<bf16, 3, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, st, var) : try_up_full<bf16, 3, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, st, var);
-        else rc = wide ? try_up_full<bf16, 2, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, st, var) : try_up_full<bf16, 2, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, st, var);
-        if (rc != CVAE_E_UNSUPPORTED) return rc;
-#if CVAE_KSPLIT_WAVES
-        if (wide) return nd == 3 ? launch_data<bf16, 3, true, 1, 2, 4, 1, 2>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side)
-                                 : launch_data<bf16, 2, true, 1, 2, 4, 1, 2>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
-#endif
-        if (nd == 3) return wide ? launch_data<bf16, 3, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<bf16, 3, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
-        return wide ? launch_data<bf16, 2, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<bf16, 2, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
-    }
-    if (nd == 3) return wide ? launch_data<float, 3, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<float, 3, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
-    return wide ? launch_data<float, 2, true, 2, 2, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side) : launch_data<float, 2, true, 4, 1, 2, 1>(S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, var, side);
+    const bool wide = (Cl % 64) == 0;     // 64-channel output tiles, else 32 (DataForm)
+    const ConvArgs a{S, w, bias, mask, L, g, act, workspace, workspace_bytes, st, 1.f, 1.f, side, var};
+    return with_dtype(dtype, [&](auto t) { return with_nd(nd, [&](auto n) {
+        using T = decltype(t);
+        constexpr int ND = decltype(n)::value;
+        // the whole-K kernel: bf16, 32-channel tiles, and the tensor form of the mask only (inference sweeps: no mask at all)
+        if constexpr (std::is_same<T, bf16>::value) if (!wide && !side.mask_bits && !side.bits_out) {
+            const int rc = try_up_full<T, ND>(a);
+            if (rc != CVAE_E_UNSUPPORTED) return rc;
+        }
+        return with_bool(wide, [&](auto wd) { return dispatch_conv<T, ND, true, decltype(wd)::value>(a); });
+    }); });
 }
 
 extern "C" size_t cvae_conv_wgrad_workspace_bytes(int64_t Cs, int64_t Cl, int nd) {
@@ -2081,7 +2049,7 @@ static int wgrad_multi_t(int count, const void* const* S, const void* const* L, 
     int mb = 0, rb = 0;
     // Together the layers need ~2-3 workgroups per CU, not 2 each: every workgroup ends with a 128 KB slab, and 6 x 512 slabs (384 MB) no longer fit
     // the 256 MB Infinity Cache between the main pass and the reduction (measured: the grouped reduction 77 us against 64 us for six separate
-    // ones).  The slab count of a layer depends on THAT layer only — ~CVAE_WG_TILES tiles of 128 positions per slab, at least CVAE_WG_MIN_WG
+    // ones).  The slab count of a layer depends on THAT layer only — ~WG_TILES tiles of 128 positions per slab, at least WG_MIN_WG
     // workgroups — never on what else rides in the launch: the split-backward capture flushes decoder and encoder separately, and its
     // gradients must have the summation order (the bits) of the single-launch step.
     using TLm = Tile<ND, 128>;
@@ -2092,8 +2060,8 @@ static int wgrad_multi_t(int count, const void* const* S, const void* const* L, 
         const int64_t* d = dims + 9 * i;
         const long long tiles = d[0] * ((d[1] + TLm::TD - 1) / TLm::TD) * ((d[2] + TLm::TH - 1) / TLm::TH) * ((d[3] + TLm::TW - 1) / TLm::TW);
         const long long groups = (d[4] / 64) * (d[8] / 32) * ((ND == 3) ? 4 : 1);            // workgroups per slab index
-        req[i] = (tiles + CVAE_WG_TILES - 1) / CVAE_WG_TILES;
-        if (req[i] * groups < CVAE_WG_MIN_WG) req[i] = (CVAE_WG_MIN_WG + groups - 1) / groups;
+        req[i] = (tiles + WG_TILES - 1) / WG_TILES;
+        if (req[i] * groups < WG_MIN_WG) req[i] = (WG_MIN_WG + groups - 1) / groups;
         if (req[i] > tiles) req[i] = tiles;
         key[i] = (tiles + req[i] - 1) / req[i];
         int k = i;
@@ -2233,25 +2201,10 @@ extern "C" int cvae_fp8_scale_update(void* amax_slots, float* scale, float* inv_
 template <int ND, bool UP, typename TO>
 static int conv_fp8_t(const void* in, const void* w, const float* bias, void* out, ConvGeom g, int act, float acc_scale, float out_scale, F8Side f8, void* ws, size_t wsb, hipStream_t st,
                       UpVariant var) {
-    const int Cout = UP ? g.Cl : g.Cs;
-    const bool wide = (Cout % 64) == 0;
-    // the bf16 launches' tile shapes: 64-channel tiles as (K split) x (N sub-tile) waves with the per-wave weight fetch, 32-channel tiles as 4 x 1 waves on LDS panels
-#ifndef CVAE_F8_FORM
-#define CVAE_F8_FORM 0      // 64-channel tiles: 0 = (K split) x (N sub-tile) waves with the per-wave weight fetch (the bf16 form), 1 = 2 x 2 waves on LDS weight panels,
-#endif                      // 2 = 2 x 2 waves with the per-wave fetch
-#define F8L(WM, WN, MI, TS, BDX, EPI) launch_data_epi<f8x2, ND, UP, WM, WN, MI, 1, EPI, 1, TO, BDX, TS>(in, w, bias, nullptr, out, g, act, ws, wsb, st, acc_scale, out_scale, f8, var)
-#define F8E(WM, WN, MI, TS, BDX) (act == CVAE_ACT_NONE ? F8L(WM, WN, MI, TS, BDX, 0) : (act == CVAE_ACT_RELU ? F8L(WM, WN, MI, TS, BDX, 1) : F8L(WM, WN, MI, TS, BDX, 2)))
-    if (wide) {
-        // measured (rocprofv3 device durations, 4 x 128^3 shapes, profiles/r03_fp8_forms.txt): the `down` products want their weights on LDS panels — the
-        // per-wave fetch form needs > 256 VGPRs with 8-register fp8 operands (59 spilled; enc2 57 us against 36 us) — the `up` products keep the bf16
-        // launch's (K split) x (N sub-tile) waves with the per-wave fetch (dec1 9.9 vs 11.2 us, dec2 8.1 vs 8.4 us)
-        if constexpr (UP && ND == 3 && CVAE_F8_FORM == 0) return F8E(1, 2, 4, 2, true);
-        else return F8E(2, 2, 2, 1, (CVAE_F8_FORM == 2));
-    }
-    if constexpr (UP) return F8E(4, 1, 2, 1, false);
+    const ConvArgs a{in, w, bias, nullptr, out, g, act, ws, wsb, st, acc_scale, out_scale, f8, var};
+    if ((UP ? g.Cl : g.Cs) % 64 == 0) return dispatch_conv<f8x2, ND, UP, true, TO>(a);
+    if constexpr (UP) return dispatch_conv<f8x2, ND, UP, false, TO>(a);
     else return CVAE_E_UNSUPPORTED;
-#undef F8E
-#undef F8L
 }
 extern "C" int cvae_conv_fp8(int up, const void* in8, const void* w8, const float* bias, void* out, int out_dtype, void* out8, const float* dscale, float acc_scale,
                              float out8_inv_scale, void* amax_slots, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int64_t Cl,
@@ -2270,11 +2223,15 @@ extern "C" int cvae_conv_fp8(int up, const void* in8, const void* w8, const floa
     f8.bits_out = (unsigned*)relu_bits_out;
     UpVariant var;
     var.xpair = xpair;
-#define F8D(ND_, UP_) (out_dtype == CVAE_FP8 ? conv_fp8_t<ND_, UP_, fp8>(in8, w8, bias, out, g, act, acc_scale, out8_inv_scale, f8, nullptr, 0, st, var) \
-                                             : conv_fp8_t<ND_, UP_, bf16>(in8, w8, bias, out, g, act, acc_scale, out8_inv_scale, f8, workspace, workspace_bytes, st, var))
-    if (nd == 3) return up ? F8D(3, true) : F8D(3, false);
-    return up ? F8D(2, true) : F8D(2, false);
-#undef F8D
+    return with_nd(nd, [&](auto n) {
+        constexpr int ND = decltype(n)::value;
+        auto run = [&](auto to, void* ws, size_t wsb) {      // codes-only output: no split-K (its finish pass writes bf16), hence no workspace
+            using TO = decltype(to);
+            return up ? conv_fp8_t<ND, true, TO>(in8, w8, bias, out, g, act, acc_scale, out8_inv_scale, f8, ws, wsb, st, var)
+                      : conv_fp8_t<ND, false, TO>(in8, w8, bias, out, g, act, acc_scale, out8_inv_scale, f8, ws, wsb, st, var);
+        };
+        return out_dtype == CVAE_FP8 ? run(fp8{}, nullptr, 0) : run(bf16{}, workspace, workspace_bytes);
+    });
 }
 
 extern "C" int cvae_conv_up_c1_fp8in(const void* S8, const float* w, const float* bias, void* L, float in_scale, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int nd,

@@ -24,6 +24,12 @@ __device__ __forceinline__ float epi_mul(float v, const EpiMul& em, int64_t gm, 
     return em.src ? v * act_grad_from_out(em.src[gm * em.ld + gn], em.act) : v;
 }
 
+// ---- tunables: each may be overridden for an A/B build with make EXTRA=-DCVAE_<NAME>=<n> (CVAE_TUNABLE, common.h) ----
+CVAE_TUNABLE(GEMM_T128_DEPTH, 2);         // gemm_bf16_t128_kernel: stages in flight (register + LDS ring)
+CVAE_TUNABLE(GEMM_T128_BK, 32);           // gemm_bf16_t128_kernel: k per stage
+CVAE_TUNABLE(GEMM_T128_WGS, 256);         // 128-tile form: workgroups up to which K is split (one per CU)
+CVAE_TUNABLE(GEMM_SPLIT_MIN_KSTEPS, 8);   // gemm_f32: 16-wide k-steps from which a small result splits K
+
 #define LT 64
 #define LK 16
 #define AS_STRIDE 17   // As[64][17]  : A-fragment reads (lane -> row) conflict-free
@@ -177,18 +183,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const float* __restrict_
     }
 }
 
-#ifndef CVAE_GEMM_T128
-#define CVAE_GEMM_T128 1
-#endif
-#ifndef CVAE_GEMM_T128_DEPTH
-#define CVAE_GEMM_T128_DEPTH 2
-#endif
-#ifndef CVAE_GEMM_T128_BK
-#define CVAE_GEMM_T128_BK 32
-#endif
-#ifndef CVAE_GEMM_T128_WGS
-#define CVAE_GEMM_T128_WGS 256
-#endif
 // The large-product form of the bf16-operand GEMM (M, N >= 128): 128 x 128 tiles, 4 waves of 64 x 64 (2 x 2 MFMA tiles: every fragment read feeds two
 // MFMAs), fp32 operands fetched as 16-byte vectors along whichever dimension is contiguous and written to LDS as 8-byte bf16 quads:
 //   * an operand that is k-contiguous in memory (x, W in the forward) gets a [row][k] image (pitch BK + 8) read with ds_read_b128;
@@ -243,7 +237,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_t128_kernel(const float* __rest
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     // DEPTH stages of both operands in flight in registers: a workgroup has ~10 stages of 32 k and one workgroup sits on a CU, so with a single
     // stage in flight every stage cost a full global round trip (2 us per stage measured: 26 us for the 1024 x 3158 x 512 forward)
-    constexpr int DEPTH = CVAE_GEMM_T128_DEPTH;
+    constexpr int DEPTH = GEMM_T128_DEPTH;
     F4U ra[DEPTH][NL], rb[DEPTH][NL];
     // one operand's stage: P[row * s_row + k * s_k], rows row0 .. row0 + 127 (< R), k in [k0, k0 + BK) (< kend)
     // Every load is an unconditional 16-byte vector from an address clamped into the operand (rows to R - 1 / R - 4, k to K - 4 / kend - 1); what the
@@ -361,7 +355,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_t128_kernel(const float* __rest
             const float4 v4 = *(const float4*)(stage + lr * SPITCH + 4 * c4);
             float v[4] = {v4.x, v4.y, v4.z, v4.w};
             if (gm < M && gn < N) {
-#ifndef CVAE_GEMM_T128_NOSTORE
                 float* dst = slabs ? slabs + ((size_t)split * M + gm) * N + gn : C + gm * ldc + gn;
                 if (!slabs) {
 #pragma unroll
@@ -376,26 +369,23 @@ __global__ __launch_bounds__(256) void gemm_bf16_t128_kernel(const float* __rest
 #pragma unroll
                     for (int e = 0; e < 3; ++e) if (gn + e < N) dst[e] = v[e];
                 }
-#else
-                if (v[0] == 123.456f) C[0] = 1.f;            // probe build: the epilogue's stores removed
-#endif
             }
         }
         __syncthreads();
     }
 }
-// split-K of the 128-tile form: until ~CVAE_GEMM_T128_WGS workgroups exist, >= 4 stages per split
+// split-K of the 128-tile form: until ~GEMM_T128_WGS workgroups exist, >= 4 stages per split
 static int64_t gemm_t128_splits(int64_t M, int64_t N, int64_t K, int64_t* k_per_split_out) {
-    const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128), stages = (K + CVAE_GEMM_T128_BK - 1) / CVAE_GEMM_T128_BK;
-    int64_t splits = CVAE_GEMM_T128_WGS / tiles;
+    const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128), stages = (K + GEMM_T128_BK - 1) / GEMM_T128_BK;
+    int64_t splits = GEMM_T128_WGS / tiles;
     if (splits > stages / 4) splits = stages / 4;
     if (splits < 1) splits = 1;
-    const int64_t kps = ((stages + splits - 1) / splits) * CVAE_GEMM_T128_BK;
+    const int64_t kps = ((stages + splits - 1) / splits) * GEMM_T128_BK;
     if (k_per_split_out) *k_per_split_out = kps;
     return (K + kps - 1) / kps;
 }
 static bool gemm_t128_ok(int64_t M, int64_t N, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn) {
-    return CVAE_GEMM_T128 && M >= 128 && N >= 128 && (sak == 1 || sam == 1) && (sbk == 1 || sbn == 1);     // (the caller adds K >= 128: a one-stage product is all output)
+    return M >= 128 && N >= 128 && (sak == 1 || sam == 1) && (sbk == 1 || sbn == 1);     // (the caller adds K >= 128: a one-stage product is all output)
 }
 
 // C[m][c] = act(sum_s slabs[s][m][c] + bias[c]), s in index order
@@ -420,14 +410,11 @@ __global__ void slab_sum_bias_act_kernel(const float* __restrict__ slabs, int sp
 // split-K factor of gemm_f32 for an [M][N] result over K: until ~2 workgroups per CU exist, keeping >= 4 K-steps (64 k) per split.  A small result
 // over a long reduction (the weight gradients of the MLP heads over a 1024-row batch: 1 - 8 tiles, K = 1024) is otherwise ONE workgroup walking
 // the whole reduction.
-#ifndef CVAE_GEMM_SPLIT_MIN_KSTEPS
-#define CVAE_GEMM_SPLIT_MIN_KSTEPS 8
-#endif
 static int64_t gemm_splits(int64_t M, int64_t N, int64_t K, int64_t* k_per_split_out) {
     const int64_t tm = (M + LT - 1) / LT, tn = (N + LT - 1) / LT;
     int64_t splits = 1;
     const int64_t ksteps = (K + LK - 1) / LK;
-    if (tm * tn < 512 && ksteps >= CVAE_GEMM_SPLIT_MIN_KSTEPS) {
+    if (tm * tn < 512 && ksteps >= GEMM_SPLIT_MIN_KSTEPS) {
         splits = 512 / (tm * tn);
         if (splits > ksteps / 4) splits = ksteps / 4;
         if (splits < 1) splits = 1;
@@ -446,14 +433,14 @@ static int gemm_f32(const float* A, const float* Bm, float* C, const float* bias
     if (bf16_math && K >= 128 && gemm_t128_ok(M, N, sam, sak, sbk, sbn) && (M * sam + K * sak) < ((int64_t)1 << 31) && (N * sbn + K * sbk) < ((int64_t)1 << 31)) {      // (32-bit element offsets inside the kernel)
         int64_t kps;
         int64_t sp = gemm_t128_splits(M, N, K, &kps);
-        if (sp > 1 && (!ws || ws_bytes < (size_t)sp * M * N * sizeof(float))) { sp = 1; kps = ((K + CVAE_GEMM_T128_BK - 1) / CVAE_GEMM_T128_BK) * CVAE_GEMM_T128_BK; }
+        if (sp > 1 && (!ws || ws_bytes < (size_t)sp * M * N * sizeof(float))) { sp = 1; kps = ((K + GEMM_T128_BK - 1) / GEMM_T128_BK) * GEMM_T128_BK; }
         float* sl = sp > 1 ? ws : nullptr;
         const int64_t tn128 = (N + 127) / 128, tm128 = (M + 127) / 128;
         if (tn128 * tm128 * sp > 0x7fffffff) return CVAE_E_BADSHAPE;
         const dim3 grid((unsigned)(tn128 * tm128 * sp));
         const bool akc = sak == 1, bkc = sbk == 1;
         const int n_slow = N > M;
-#define T128(AK, BKC) hipLaunchKernelGGL((gemm_bf16_t128_kernel<AK, BKC, CVAE_GEMM_T128_BK>), grid, dim3(256), 0, stream, A, Bm, C, bias, M, N, K, sam, sak, sbk, sbn, ldc, kps, act, sl, (int)tn128, (int)tm128, n_slow, sl ? EpiMul{nullptr, 0, 0} : em)
+#define T128(AK, BKC) hipLaunchKernelGGL((gemm_bf16_t128_kernel<AK, BKC, GEMM_T128_BK>), grid, dim3(256), 0, stream, A, Bm, C, bias, M, N, K, sam, sak, sbk, sbn, ldc, kps, act, sl, (int)tn128, (int)tm128, n_slow, sl ? EpiMul{nullptr, 0, 0} : em)
         if (akc) { if (bkc) T128(true, true); else T128(true, false); } else { if (bkc) T128(false, true); else T128(false, false); }
 #undef T128
         CVAE_CHECK_LAUNCH();

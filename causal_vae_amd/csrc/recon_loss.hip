@@ -56,12 +56,8 @@ __device__ __forceinline__ void load4_f32(const bf16* p, float* o) {
     o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u); o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
 }
 
-#ifndef CVAE_UP2X_TILE
-#define CVAE_UP2X_TILE 1
-#endif
-#ifndef CVAE_UP2X_STREAM_BYTES
-#define CVAE_UP2X_STREAM_BYTES ((int64_t)256 << 20)          // cvae_up2x_fwd outputs from this size on use nontemporal stores (decode sweep: 707 -> 490 us with the vector loads)
-#endif
+// ---- tunables: each may be overridden for an A/B build with make EXTRA=-DCVAE_<NAME>=<n> (CVAE_TUNABLE, common.h) ----
+CVAE_TUNABLE(UP2X_STREAM_BYTES, 256 << 20);   // cvae_up2x_fwd outputs from this size on use nontemporal stores (decode sweep: 707 -> 490 us with the vector loads)
 
 // Exact 2x taps.  lin_tap() gives, for an even output o = 2 i: (i - 1, i) with weights (0.25, 0.75) — except o = 0: (0, 1) with
 // weights (1, 0) — and for an odd output o = 2 i + 1: (i, i + 1) with weights (0.75, 0.25), the upper index clamped to in - 1.
@@ -440,8 +436,7 @@ extern "C" int cvae_up2x_fwd(const void* src, float* dst, int64_t B, int64_t d, 
     if (!up2x_ok(B, d, h, w, D, H, W)) return CVAE_E_UNSUPPORTED;
     if (!src || !dst) return CVAE_E_NULLPTR;
     const unsigned grid = (unsigned)((B * d * h * (w / 4) + 255) / 256);
-    const bool stream_out = B * D * H * W * 4 >= CVAE_UP2X_STREAM_BYTES;
-#if CVAE_UP2X_TILE
+    const bool stream_out = B * D * H * W * 4 >= UP2X_STREAM_BYTES;
     if (D == 2 * d && d % 2 == 0 && h % 8 == 0 && w % 64 == 0 && (dtype == CVAE_BF16 || dtype == CVAE_F32)) {      // rows of 64: the LDS-tiled form
         const dim3 tgrid((unsigned)(B * (d / 2) * (h / 8) * (w / 64)));
         hipStream_t st = (hipStream_t)stream;
@@ -452,7 +447,6 @@ extern "C" int cvae_up2x_fwd(const void* src, float* dst, int64_t B, int64_t d, 
         CVAE_CHECK_LAUNCH();
         return CVAE_OK;
     }
-#endif
 #define UP2X_FWD(T, MODE) hipLaunchKernelGGL((up2x_block_kernel<T, MODE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, nullptr, dst, nullptr, nullptr, 0.f, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W, SmallBwd{}, ElboFinish{})
     if (dtype == CVAE_BF16) { if (stream_out) UP2X_FWD(bf16, 4); else UP2X_FWD(bf16, 0); }
     else if (dtype == CVAE_F32) { if (stream_out) UP2X_FWD(float, 4); else UP2X_FWD(float, 0); }

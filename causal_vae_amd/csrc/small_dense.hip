@@ -15,10 +15,7 @@ namespace {
 
 constexpr int SD_ROWS = 16;            // batch rows per workgroup
 constexpr int SD_MAX_NK = 12288;       // weights that fit: 48 KB of LDS
-#ifndef CVAE_SD_MAX_DIM
-#define CVAE_SD_MAX_DIM 128
-#endif
-constexpr int SD_MAX_DIM = CVAE_SD_MAX_DIM;   // beyond 128 inputs / outputs the per-thread dot products get long and the tiled GEMM wins (512 -> 20: 17 / 27 / 16 us here against 12 / 10 / 15)
+CVAE_TUNABLE(SD_MAX_DIM, 128);         // (make EXTRA=-DCVAE_SD_MAX_DIM=<n>) beyond 128 inputs / outputs the per-thread dot products get long and the tiled GEMM wins (512 -> 20: 17 / 27 / 16 us here against 12 / 10 / 15)
 
 // dst[r * pitch + c] = src[r * src_stride + c] for r < rows: every load of the thread is issued before its first LDS store.  A contiguous, 16-byte aligned
 // source (the weight: src_stride == cols) goes as float4s, 12 per thread = the whole 48 KB in ONE pass of the workgroup.
