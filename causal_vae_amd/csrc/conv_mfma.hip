@@ -693,7 +693,7 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
 // fp8 product (x * 1.0f is exact: the other dtypes' bits do not change), whose side channel (second fp8 output, amax) is served here too.
 template <typename T, int EPI>
 __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const float* __restrict__ ws, const float* __restrict__ bias, const T* __restrict__ mask,
-                                                                  T* __restrict__ out, int64_t total, int Cout, int ksplit, int act, float acc_scale, F8Side f8) {
+                                                                  T* __restrict__ out, int64_t total, int Cout, int ksplit, int act, float acc_scale, float out_scale, F8Side f8) {
     const int64_t i8 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
     float amx = 0.f;
     if (i8 < total) {
@@ -736,7 +736,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const float* __
         }
         piece_store<T>(op, (char*)(out + i8));
         if (f8.bits_out) ((unsigned char*)f8.bits_out)[i8 >> 3] = (unsigned char)mask_byte_of(v);
-        if (f8.out8) *(uint2*)(f8.out8 + i8) = pack8_fp8(v, f8.dscale ? f8.dscale[1] : 1.f);
+        if (f8.out8) *(uint2*)(f8.out8 + i8) = pack8_fp8(v, f8.dscale ? f8.dscale[1] : out_scale);     // by value when the caller keeps no device scales
     }
     __shared__ float red[4];
     if (f8.amax) amax_publish_wg(f8.amax, amx, blockIdx.x, red);
@@ -841,7 +841,7 @@ int launch_data_epi(const ConvArgs& a) {
     CVAE_CHECK_LAUNCH();
     if constexpr (sizeof(TO) != 1) if (ksplit > 1) {
         hipLaunchKernelGGL((conv_splitk_finish_kernel<TO, EPI>), dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, a.stream, (const float*)a.ws, a.bias,
-                           (const TO*)a.mask, (TO*)a.out, total, Cout, ksplit, a.act, IsF8<T>::value ? a.acc_scale : 1.f, a.f8);
+                           (const TO*)a.mask, (TO*)a.out, total, Cout, ksplit, a.act, IsF8<T>::value ? a.acc_scale : 1.f, a.out_scale, a.f8);
         CVAE_CHECK_LAUNCH();
     }
     return CVAE_OK;
