@@ -14,8 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVAE_HIP_LIB") or os.path.join(_HERE, "libcvae_hip.so")
 
 F32, BF16, FP8 = 0, 1, 2
-ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY02 = 0, 1, 2, 3
-_ACT = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "leaky02": ACT_LEAKY02}
+ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY02, ACT_LEAKY001 = 0, 1, 2, 3, 4
+_ACT = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "leaky02": ACT_LEAKY02, "leaky001": ACT_LEAKY001}
 
 
 class CvaeError(RuntimeError):
@@ -125,6 +125,10 @@ SIGNATURES = {
     "cvae_bn2d_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _i, _p, _sz, _p],
     "cvae_bn2d_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
     "cvae_fold_bn_conv": [_i] + [_p] * 11 + [_p],
+    "cvae_vit_tokens": [_p, _i, _p, _p, _p, _i64, _i64, _p],
+    "cvae_layernorm256": [_p, _i64, _p, _p, _p, _i64, _f, _i, _p],
+    "cvae_token_gemm": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
+    "cvae_mhsa_fwd": [_p] * 4 + [_i64] * 9 + [_i, _p],
     "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
     "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
     "cvae_stack_mean_std": [_p, _i, _p, _p, _i64, _p],

@@ -134,6 +134,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
         case CVAE_ACT_RELU: return v > 0.f ? v : 0.f;
         case CVAE_ACT_SIGMOID: return 1.f / (1.f + __expf(-v));
         case CVAE_ACT_LEAKY02: return v > 0.f ? v : 0.2f * v;
+        case CVAE_ACT_LEAKY001: return v > 0.f ? v : 0.01f * v;
         default: return v;
     }
 }
@@ -166,6 +167,7 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
         case CVAE_ACT_RELU: return y > 0.f ? 1.f : 0.f;
         case CVAE_ACT_SIGMOID: return y * (1.f - y);
         case CVAE_ACT_LEAKY02: return y > 0.f ? 1.f : 0.2f;
+        case CVAE_ACT_LEAKY001: return y > 0.f ? 1.f : 0.01f;
         default: return 1.f;
     }
 }

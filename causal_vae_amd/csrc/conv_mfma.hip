@@ -2238,6 +2238,6 @@ extern "C" int cvae_conv_up_c1_fp8in(const void* S8, const float* w, const float
                                      int act, void* stream) {
     if (!S8 || !w || !L) return CVAE_E_NULLPTR;
     if (nd != 3 || B < 1 || sd < 1 || sh < 1 || sw < 1) return CVAE_E_UNSUPPORTED;
-    if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY02) return CVAE_E_BADSHAPE;
+    if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_BADSHAPE;
     return cvae_conv_up_c1_fp8in_impl(S8, w, bias, L, in_scale, B, sd, sh, sw, Cs, act, (hipStream_t)stream);
 }

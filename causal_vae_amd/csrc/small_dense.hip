@@ -203,7 +203,7 @@ template <typename KERN> int sd_allow_lds(KERN kern, bool* done) {
     }
     return CVAE_OK;
 }
-bool sd_act_ok(int act) { return act >= CVAE_ACT_NONE && act <= CVAE_ACT_LEAKY02; }
+bool sd_act_ok(int act) { return act >= CVAE_ACT_NONE && act <= CVAE_ACT_LEAKY001; }
 
 }  // namespace
 

@@ -6,7 +6,8 @@
 // The fold, per output channel c:  s = gamma[c] rsqrt(var[c] + eps),  w'[c] = w[c] s,  b'[c] = (b[c] - mean[c]) s + beta[c]
 // (the same rsqrt(var + eps) form as BatchNorm2dAct's eval branch).  A Conv2d(k4) weight [Cout][Cin][4][4] keeps its layout; an
 // UpConv2dK3 weight [Cout][Cin][3][3] leaves as the transposed k4 weight [Cin][Cout][4][4] = A W3 A^T of cvae_conv3_to_k4 (same sums in the
-// same order, so an entry without BatchNorm reproduces cvae_conv3_to_k4's bits).
+// same order, so an entry without BatchNorm reproduces cvae_conv3_to_k4's bits).  A Conv2d(k3, s2, p1) weight [Cout][Cin][3][3] (the ViT-VAE stem) leaves as
+// the k4/s2/p1 weight [Cout][Cin][4][4] whose fourth row and column are zero: both read in[2o - 1 + k], so the products are the same.
 #include "common.h"
 
 namespace {
@@ -74,6 +75,25 @@ __global__ __launch_bounds__(256) void fold_bn_conv_kernel(const FoldTable T) {
             if (g < n4) {
                 const float s = fold_scale(E, (int)(g / per_c));
                 ((float4*)E.w_out)[g] = make_float4(v[u].x * s, v[u].y * s, v[u].z * s, v[u].w * s);
+            }
+        }
+        return;
+    }
+    if (E.kind == CVAE_FOLD_CONV_K3S2) {
+        // [Cout][Cin][3][3] -> [Cout][Cin][4][4] with a zero fourth row and column: a float4 group is the 4 kw taps of one (cout, cin, kh)
+        const int64_t n4 = (int64_t)E.cout * E.cin * 4, per_c = (int64_t)E.cin * 4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t g = (int64_t)blk * FOLD_K4_PER_BLOCK + t + u * 256;
+            if (g < n4) {
+                const int kh = (int)(g & 3);
+                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (kh < 3) {
+                    const float* w3 = E.w + (g >> 2) * 9 + kh * 3;
+                    const float s = fold_scale(E, (int)(g / per_c));
+                    o = make_float4(w3[0] * s, w3[1] * s, w3[2] * s, 0.f);
+                }
+                ((float4*)E.w_out)[g] = o;
             }
         }
         return;
@@ -280,7 +300,7 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         FoldEntry& E = T.e[k];
         const int64_t Cout = dims[2 * k], Cin = dims[2 * k + 1];
         if (Cout <= 0 || Cin <= 0 || Cout * Cin > ((int64_t)1 << 28)) return CVAE_E_BADSHAPE;
-        if (kind[k] != CVAE_FOLD_CONV_K4 && kind[k] != CVAE_FOLD_UPCONV_K3) return CVAE_E_UNSUPPORTED;
+        if (kind[k] != CVAE_FOLD_CONV_K4 && kind[k] != CVAE_FOLD_UPCONV_K3 && kind[k] != CVAE_FOLD_CONV_K3S2) return CVAE_E_UNSUPPORTED;
         if (!w[k] || !w_out[k] || !b_out[k]) return CVAE_E_NULLPTR;
         const bool bn = gamma && gamma[k];
         if (bn && (!beta || !beta[k] || !mean || !mean[k] || !var || !var[k])) return CVAE_E_NULLPTR;
@@ -295,7 +315,7 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         E.eps = eps[k];
         E.kind = kind[k];
         E.cout = (int)Cout; E.cin = (int)Cin;
-        E.wblocks = kind[k] == CVAE_FOLD_CONV_K4 ? (int)((Cout * Cin * 4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
+        E.wblocks = kind[k] != CVAE_FOLD_UPCONV_K3 ? (int)((Cout * Cin * 4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
                                                  : (int)(((Cout + FOLD_K3_TILE - 1) / FOLD_K3_TILE) * ((Cin + FOLD_K3_TILE - 1) / FOLD_K3_TILE));
         E.bblocks = (int)((Cout + 255) / 256);
         blocks += E.wblocks + E.bblocks;

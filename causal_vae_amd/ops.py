@@ -1822,7 +1822,7 @@ class Conv3ToK4(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------ CausalVesselVAE inference (csrc/vessel_infer.hip)
 # Forward-only helpers of the eval-mode decode and the analysis sweeps: they enqueue their kernels and return plain tensors; asked for a gradient
 # they raise (the reference consumers run them under no_grad).
-FOLD_CONV_K4, FOLD_UPCONV_K3 = 0, 1        # CVAE_FOLD_CONV_K4 / CVAE_FOLD_UPCONV_K3
+FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2 = 0, 1, 3        # CVAE_FOLD_CONV_K4 / CVAE_FOLD_UPCONV_K3 / CVAE_FOLD_CONV_K3S2
 
 
 def _forward_only(what, *tensors):
@@ -1832,8 +1832,9 @@ def _forward_only(what, *tensors):
 
 def fold_bn_conv(entries):
     """Fold eval-mode BatchNorm2d into the convs in front of it, for up to 16 layers in ONE launch (cvae_fold_bn_conv).
-    entries: (weight, kind, bias, bn) with kind FOLD_CONV_K4 (nn.Conv2d k4 weight, layout kept) or FOLD_UPCONV_K3 (the Conv2d(k3) of an Upsample x2 +
-    Conv2d pair -> its transposed k4 weight [Cin][Cout][4][4]) and bn an nn.BatchNorm2d on running statistics, or None (plain transform, bias copied).
+    entries: (weight, kind, bias, bn) with kind FOLD_CONV_K4 (nn.Conv2d k4 weight, layout kept), FOLD_UPCONV_K3 (the Conv2d(k3) of an Upsample x2 +
+    Conv2d pair -> its transposed k4 weight [Cin][Cout][4][4]) or FOLD_CONV_K3S2 (nn.Conv2d(k3, s2, p1) weight -> the k4/s2/p1 weight [Cout][Cin][4][4]
+    with a zero fourth row and column) and bn an nn.BatchNorm2d on running statistics, or None (plain transform, bias copied).
     Returns [(w_out, b_out)] fp32, all views of one fresh buffer."""
     import ctypes as C
     k = len(entries)
@@ -1846,14 +1847,14 @@ def fold_bn_conv(entries):
             raise L.CvaeError("fold_bn_conv: the BatchNorm2d needs running statistics and an affine weight (eval mode, track_running_stats, affine)")
     sizes = []
     for w, kind, _b, _bn in entries:
-        if kind not in (FOLD_CONV_K4, FOLD_UPCONV_K3) or w.dim() != 4 or tuple(w.shape[2:]) != ((4, 4) if kind == FOLD_CONV_K4 else (3, 3)):
+        if kind not in (FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2) or w.dim() != 4 or tuple(w.shape[2:]) != ((4, 4) if kind == FOLD_CONV_K4 else (3, 3)):
             raise L.CvaeError(f"fold_bn_conv: kind {kind} does not match a weight of shape {tuple(w.shape)}")
         sizes.append((w.shape[0] * w.shape[1] * 16, w.shape[0]))
     pad = lambda n: (n + 3) // 4 * 4                      # every piece starts on 16 bytes
     buf = torch.empty(sum(pad(a) + pad(b) for a, b in sizes), dtype=torch.float32, device=entries[0][0].device)
     outs, off = [], 0
     for (w, kind, _b, _bn), (nw, nb) in zip(entries, sizes):
-        shape = tuple(w.shape[:2]) + (4, 4) if kind == FOLD_CONV_K4 else (w.shape[1], w.shape[0], 4, 4)
+        shape = tuple(w.shape[:2]) + (4, 4) if kind != FOLD_UPCONV_K3 else (w.shape[1], w.shape[0], 4, 4)
         wo = buf[off:off + nw].view(shape)
         off += pad(nw)
         bo = buf[off:off + nb]
@@ -1911,3 +1912,80 @@ def stack_mean_std(tensors):
     mean, std = _empty(shape, torch.float32, xs[0]), _empty(shape, torch.float32, xs[0])
     check(lib.cvae_stack_mean_std((C.c_void_p * k)(*[t.data_ptr() for t in xs]), k, ptr(mean), ptr(std), xs[0].numel(), stream()), "stack_mean_std")
     return mean, std
+
+
+# ---- ViT-VAE encoder (csrc/vit.hip): forward-only building blocks on raw tensors -------------------------------------------------
+GEMM_EPI = {None: 0, "gelu": 1, "residual": 2}      # CVAE_GEMM_EPI_*
+
+
+def _rows2d(t, what, cols=None):
+    if t.dim() != 2 or t.stride(1) != 1 or (cols is not None and t.shape[1] != cols):
+        raise L.CvaeError(f"{what}: a [rows, {cols or 'cols'}] tensor with unit column stride expected, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def vit_tokens(stem_cl, cls_token, pos):
+    """fp32 residual stream [B, n + 1, 256]: row 0 = cls + pos[0], row 1 + i = stem[b, i] + pos[1 + i] (cvae_vit_tokens).  stem_cl: the channels-last
+    output of the last stem conv [B, 1, h, w, 256] (fp32 or bf16) — already `rearrange("b c h w -> b (h w) c")`; pos: [n + 1, 256] fp32."""
+    L.require_gpu(stem_cl, cls_token, pos)
+    _forward_only("vit_tokens", stem_cl, cls_token, pos)
+    B, n = stem_cl.shape[0], stem_cl[0].numel() // 256
+    if stem_cl.shape[-1] != 256 or not stem_cl.is_contiguous() or pos.shape != (n + 1, 256) or cls_token.numel() != 256:
+        raise L.CvaeError(f"vit_tokens: stem {tuple(stem_cl.shape)}, pos {tuple(pos.shape)}, cls {tuple(cls_token.shape)} do not form [B, n + 1, 256] tokens")
+    tokens = _empty((B, n + 1, 256), torch.float32, stem_cl)
+    check(lib.cvae_vit_tokens(ptr(stem_cl), L.dtype_code(stem_cl.dtype), ptr(cls_token.detach().contiguous()), ptr(pos.detach().contiguous()), ptr(tokens), B, n, stream()),
+          "vit_tokens")
+    return tokens
+
+
+def layernorm256(x, weight, bias, eps, out_dtype):
+    """nn.LayerNorm(256) of the rows of x (fp32 [rows, 256], any row stride that is a multiple of 4) -> [rows, 256] in out_dtype (cvae_layernorm256)."""
+    L.require_gpu(x, weight, bias)
+    _forward_only("layernorm256", x, weight, bias)
+    _rows2d(x, "layernorm256", 256)
+    if x.dtype != torch.float32:
+        raise L.CvaeError("layernorm256: fp32 input expected (the residual stream)")
+    y = _empty((x.shape[0], 256), out_dtype, x)
+    check(lib.cvae_layernorm256(ptr(x), x.stride(0), ptr(weight.detach()), ptr(bias.detach()), ptr(y), x.shape[0], float(eps), L.dtype_code(out_dtype), stream()), "layernorm256")
+    return y
+
+
+def token_gemm(x, weight, bias, epilogue=None, resid=None, out=None):
+    """epi(x @ weight.T + bias) (cvae_token_gemm).  x [M, K] fp32 or bf16 (the arithmetic mode), weight [N, K] / bias [N] the fp32 nn.Linear tensors.
+    epilogue None / "gelu": result in x's dtype; "residual": fp32 resid + (x W^T + b), written to `out` (default: resid itself, in place)."""
+    L.require_gpu(x, weight, bias, resid, out)
+    _forward_only("token_gemm", x, weight, bias, resid)
+    _rows2d(x, "token_gemm")
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in GEMM_EPI:
+        raise L.CvaeError(f"token_gemm: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r}")
+    if epilogue == "residual":
+        if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm resid", N).shape[0] != M:
+            raise L.CvaeError("token_gemm: the residual epilogue needs a fp32 [M, N] residual")
+        out = resid if out is None else out
+    elif out is None:
+        out = _empty((M, N), x.dtype, x)
+    _rows2d(out, "token_gemm out", N)
+    check(lib.cvae_token_gemm(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out),
+                              out.stride(0), M, K, N, GEMM_EPI[epilogue], L.dtype_code(x.dtype), stream()), "token_gemm")
+    return out
+
+
+def mhsa(q, k, v, n_query_rows=None):
+    """Fused 8-head self-attention of width 256 (cvae_mhsa_fwd): q [B, >= n_query_rows, 256], k / v [B, N, 256] — views with unit column stride, e.g. the
+    three column panels of the packed in-projection output [B, N, 768].  The first n_query_rows tokens are the queries (default: all N).
+    Returns [B, n_query_rows, 256] in the operands' dtype."""
+    L.require_gpu(q, k, v)
+    _forward_only("mhsa", q, k, v)
+    B, N = k.shape[0], k.shape[1]
+    nq = N if n_query_rows is None else int(n_query_rows)
+    for t in (q, k, v):
+        if t.dim() != 3 or t.shape[2] != 256 or t.stride(2) != 1 or t.dtype != q.dtype or t.shape[0] != B:
+            raise L.CvaeError(f"mhsa: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
+    if v.shape[1] != N or not 1 <= nq <= N or q.shape[1] < nq:
+        raise L.CvaeError(f"mhsa: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, n_query_rows {nq}")
+    out = _empty((B, nq, 256), q.dtype, q)
+    check(lib.cvae_mhsa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq,
+                            L.dtype_code(q.dtype), stream()), "mhsa_fwd")
+    return out

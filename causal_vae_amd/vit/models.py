@@ -1,0 +1,199 @@
+"""ViTVAEEncoder — the encoder half of the reference's ViTVAE (vessel_analysis/00_core/vit_backbone.py:50-179; the same class in
+latent_translator/models.py) for eval-mode inference on MI355X: image -> CLS feature -> (mu, log_var).
+
+Same constructor order as the reference up to fc_var (its decoder is built AFTER these, so `torch.manual_seed(s); ViTVAEEncoder(...)` draws the
+reference's encoder weights), same attribute tree and state_dict keys: stem.{0,1,3,4,..}, pos_embedding, cls_token, transformer.{i}.{norm1,
+attn.in_proj_weight, attn.in_proj_bias, attn.out_proj, norm2, mlp.0, mlp.3}, to_latent, fc_mu, fc_var.  The torch modules only hold the parameters;
+the arithmetic runs in libcvae_hip.so:
+  stem        5 x [Conv2d(k3, s2, p1) + BatchNorm2d + LeakyReLU(0.01)]: BatchNorm folded, k3 zero-embedded into k4/s2/p1 (ONE cvae_fold_bn_conv launch),
+              then cvae_conv_down with the activation in its epilogue; its channels-last output [B, h, w, 256] IS `rearrange("b c h w -> b (h w) c")`
+  tokens      cvae_vit_tokens: CLS + patches + position embedding -> fp32 residual stream
+  block       cvae_layernorm256, cvae_token_gemm (packed QKV), cvae_mhsa_fwd, cvae_token_gemm (+ residual), cvae_layernorm256,
+              cvae_token_gemm (GELU), cvae_token_gemm (+ residual): 7 launches
+  last block  encode reads x[:, 0] only: K and V of all tokens, everything else for the CLS row alone (n_query_rows = 1)
+decode / forward are not built (the ViT decoder needs kernels this library does not have), hence the class name.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import layers as hl
+from .. import ops
+from .._lib import CvaeError, require_gpu
+
+STEM_CHANNELS = (32, 64, 128, 256, 256)
+
+
+class _Block(nn.Module):
+    """Parameter holder with the reference ViTBlock's children (vit_backbone.py:22-38), built in its order."""
+
+    def __init__(self, dim, heads, mlp_dim, dropout=0.1):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim)
+        self.attn = nn.MultiheadAttention(embed_dim=dim, num_heads=heads, dropout=dropout, batch_first=True)
+        self.norm2 = nn.LayerNorm(dim)
+        self.mlp = nn.Sequential(nn.Linear(dim, mlp_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(mlp_dim, dim), nn.Dropout(dropout))
+
+
+class ViTVAEEncoder(nn.Module):
+    compute_dtype = torch.float32
+    _cls_only_last_block = True     # private (tests): False: the last block runs for every token like the others (same CLS row, bit for bit; tests compare the two)
+
+    def __init__(self, in_channels=1, latent_dim=128, img_size=(768, 1280), patch_size=32, embed_dim=256, depth=6, heads=8, mlp_dim=512):
+        super().__init__()
+        H, W = (int(v) for v in img_size)
+        if (embed_dim, heads, mlp_dim, patch_size, in_channels) != (256, 8, 512, 32, 1) or H < 32 or W < 32 or H % 32 or W % 32 or depth < 1 or latent_dim < 1:
+            raise CvaeError("ViTVAEEncoder: the gfx950 kernels implement embed_dim 256, 8 heads, mlp_dim 512, patch_size 32, one input channel, image height "
+                            f"and width multiples of 32 (got embed_dim={embed_dim}, heads={heads}, mlp_dim={mlp_dim}, patch_size={patch_size}, "
+                            f"in_channels={in_channels}, img_size={tuple(img_size)}, depth={depth}, latent_dim={latent_dim})")
+        self.latent_dim, self.embed_dim, self.patch_size, self.depth = latent_dim, embed_dim, patch_size, depth
+        self.img_height, self.img_width = H, W
+        stem, cin = [], in_channels
+        for cout in STEM_CHANNELS:
+            stem += [nn.Conv2d(cin, cout, kernel_size=3, stride=2, padding=1), nn.BatchNorm2d(cout), nn.LeakyReLU()]
+            cin = cout
+        self.stem = nn.Sequential(*stem)
+        self.grid_h, self.grid_w = H // 32, W // 32
+        self.num_patches = self.grid_h * self.grid_w
+        self.pos_embedding = nn.Parameter(torch.randn(1, self.num_patches + 1, embed_dim))
+        self.cls_token = nn.Parameter(torch.randn(1, 1, embed_dim))
+        self.transformer = nn.Sequential(*[_Block(embed_dim, heads, mlp_dim) for _ in range(depth)])
+        self.to_latent = nn.LayerNorm(embed_dim)
+        self.fc_mu = nn.Linear(embed_dim, latent_dim)
+        self.fc_var = nn.Linear(embed_dim, latent_dim)
+
+    def set_compute_dtype(self, dtype):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise CvaeError(f"compute dtype must be float32 or bfloat16, got {dtype}")
+        self.compute_dtype = dtype
+        return self
+
+    # ---- the pipeline -------------------------------------------------------------------------------------------------------------
+    def _check(self, x):
+        if self.training:
+            raise RuntimeError("ViTVAEEncoder: put the model in eval mode first (model.eval()): dropout and batch-statistics BatchNorm2d are not "
+                               "implemented, the encoder runs inference only")
+        if x.dim() != 4 or tuple(x.shape[1:]) != (1, self.img_height, self.img_width) or x.dtype != torch.float32:
+            raise CvaeError(f"ViTVAEEncoder expects a float32 [B, 1, {self.img_height}, {self.img_width}] batch, got {tuple(x.shape)} {x.dtype}")
+        require_gpu(x, self.cls_token)
+
+    def _stem_cl(self, x):
+        mods = list(self.stem)
+        table = [(mods[i].weight, ops.FOLD_CONV_K3S2, mods[i].bias, mods[i + 1]) for i in range(0, len(mods), 3)]
+        folded = ops.fold_bn_conv(table)
+        h, first_dtype = hl._image_cl(x, self.compute_dtype)
+        for j, (w, b) in enumerate(folded):
+            h = ops.ConvDown.apply(h, w, b, 2, "leaky001", False, False, None, first_dtype if j == 0 else None)
+        return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
+
+    def _block(self, blk, tokens, cls_only):
+        """One transformer block on the fp32 residual stream `tokens` [B, N, 256], in place.  cls_only: returns the block's CLS rows [B, 256]
+        (fp32) and leaves `tokens` as it was; the same sums in the same order as the full block's row 0."""
+        B, N, D = tokens.shape
+        dt = self.compute_dtype
+        X = tokens.view(B * N, D)
+        a = blk.attn
+        y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
+        if not cls_only:
+            qkv = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D)
+            att = ops.mhsa(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
+            ops.token_gemm(att.view(B * N, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=X)
+            y2 = ops.layernorm256(X, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
+            hid = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu")
+            ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X)
+            return tokens[:, 0]
+        kv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
+        qc = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D])
+        att = ops.mhsa(qc.view(B, 1, D), kv[:, :, :D], kv[:, :, D:], n_query_rows=1)
+        cls = torch.empty(B, D, dtype=torch.float32, device=tokens.device)
+        ops.token_gemm(att.view(B, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=tokens[:, 0], out=cls)
+        y2 = ops.layernorm256(cls, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
+        hid = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu")
+        ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=cls)
+        return cls
+
+    @torch.no_grad()
+    def cls_features(self, x):
+        """to_latent(transformer(tokens)[:, 0]) -> [B, 256] fp32: steps A-D of CausalViTVAE.forward (vessel_analysis/00_core/models.py:262-278)."""
+        return self._cls_features(x)
+
+    @torch.no_grad()
+    def _cls_features(self, x, collect=None):
+        """collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual
+        stream after every block that ran for all tokens)."""
+        self._check(x)
+        stem = self._stem_cl(x)
+        tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
+        if collect is not None:
+            collect["stem"], collect["cls_rows"], collect["tokens"] = stem, [], []
+        for i, blk in enumerate(self.transformer):
+            cls = self._block(blk, tokens, cls_only=self._cls_only_last_block and i == self.depth - 1)
+            if collect is not None:
+                collect["cls_rows"].append(cls.clone())
+                if not (self._cls_only_last_block and i == self.depth - 1):
+                    collect["tokens"].append(tokens.clone())
+        return ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
+
+    @torch.no_grad()
+    def encode(self, x):
+        """(mu, log_var) = (fc_mu, fc_var)(cls_features(x)), as ViTVAE.encode (vit_backbone.py:158-179) in eval mode; both [B, latent_dim] fp32."""
+        c = self.cls_features(x)
+        return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
+
+
+def resize_pos_embedding(pos, src_grid, dst_grid):
+    """A position embedding [1, 1 + hs * ws, D] for another patch grid: the CLS row is kept, the grid rows are laid out as a [D, hs, ws] image and
+    resized bicubically (align_corners=False) to dst_grid — what the reference's latent_translator does when it loads a 768 x 1280 checkpoint into
+    a 384 x 640 model.  Host-side torch, run once at load."""
+    (hs, ws), (hd, wd) = src_grid, dst_grid
+    if pos.dim() != 3 or pos.shape[0] != 1 or pos.shape[1] != 1 + hs * ws:
+        raise CvaeError(f"resize_pos_embedding: {tuple(pos.shape)} is not [1, 1 + {hs} * {ws}, D]")
+    if (hs, ws) == (hd, wd):
+        return pos
+    D = pos.shape[2]
+    grid = pos[:, 1:].transpose(1, 2).reshape(1, D, hs, ws)
+    grid = F.interpolate(grid.float(), size=(hd, wd), mode="bicubic", align_corners=False)
+    return torch.cat([pos[:, :1], grid.flatten(2).transpose(1, 2).to(pos.dtype)], dim=1)
+
+
+def _source_grid(n, dst_grid):
+    """The patch grid of a checkpoint's n position rows: the one with the target's aspect ratio."""
+    hd, wd = dst_grid
+    for hs in range(1, n + 1):
+        if n % hs == 0 and hs * wd == (n // hs) * hd:
+            return hs, n // hs
+    raise CvaeError(f"load_vitvae_state_dict: cannot tell the patch grid of a pos_embedding with {n} grid rows from the model's {hd} x {wd} grid "
+                    "(different aspect ratio): pass src_grid=(h, w)")
+
+
+def load_vitvae_state_dict(model, state_dict, src_grid=None):
+    """Load a full reference ViTVAE checkpoint into the encoder.  Decoder keys (decoder_input.*, decoder.*) are dropped and returned as a sorted
+    list; a pos_embedding of another patch grid is resized (resize_pos_embedding; src_grid = the checkpoint's (h, w) grid when it does not share
+    the model's aspect ratio); every other missing, unexpected or mis-shaped key is an error."""
+    own = model.state_dict()
+    dropped = sorted(k for k in state_dict if k.startswith(("decoder_input.", "decoder.")))
+    sd = {k: v for k, v in state_dict.items() if k not in set(dropped)}
+    unexpected, missing = sorted(set(sd) - set(own)), sorted(set(own) - set(sd))
+    if unexpected or missing:
+        raise CvaeError(f"load_vitvae_state_dict: unexpected keys {unexpected}, missing keys {missing}")
+    pos = sd["pos_embedding"]
+    if tuple(pos.shape) != tuple(own["pos_embedding"].shape):
+        if pos.dim() != 3 or pos.shape[0] != 1 or pos.shape[2] != model.embed_dim:
+            raise CvaeError(f"load_vitvae_state_dict: pos_embedding {tuple(pos.shape)} cannot be resized to {tuple(own['pos_embedding'].shape)}")
+        dst = (model.grid_h, model.grid_w)
+        sd["pos_embedding"] = resize_pos_embedding(pos.detach().cpu(), src_grid or _source_grid(pos.shape[1] - 1, dst), dst)
+    bad = [k for k, v in sd.items() if tuple(v.shape) != tuple(own[k].shape)]
+    if bad:
+        raise CvaeError(f"load_vitvae_state_dict: shape mismatch for {bad}")
+    model.load_state_dict(sd, strict=True)
+    return dropped
+
+
+@torch.no_grad()
+def extract_vit_latents(model, loader, device):
+    """The reference's latent_translator/engine.py:38-52: eval mode, mu of every batch["x"], stacked as one numpy array.  The per-batch results stay on the
+    device; one host copy is made at the end."""
+    model.eval()
+    zs = [model.encode(batch["x"].to(device))[0] for batch in loader]
+    return torch.cat(zs, dim=0).cpu().numpy() if zs else np.zeros((0, model.latent_dim), dtype=np.float32)

@@ -57,6 +57,7 @@ extern "C" {
 #define CVAE_ACT_RELU    1
 #define CVAE_ACT_SIGMOID 2
 #define CVAE_ACT_LEAKY02 3   /* LeakyReLU(0.2) */
+#define CVAE_ACT_LEAKY001 4  /* LeakyReLU() with torch's default slope 0.01 */
 
 int         cvae_version(void);
 const char* cvae_strerror(int code);
@@ -228,12 +229,16 @@ int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gam
  * w_out[c] = w[c] s, b_out[c] = (bias[c] - mean[c]) s + beta[c] — the conv then runs with the activation in its epilogue and no BatchNorm pass.
  *   kind CVAE_FOLD_CONV_K4:   w = nn.Conv2d(k4) weight [Cout][Cin][4][4], w_out in the same layout;
  *   kind CVAE_FOLD_UPCONV_K3: w = the Conv2d(k3) of an Upsample(x2, nearest) + Conv2d pair [Cout][Cin][3][3], w_out the transposed k4 weight
- *                             [Cin][Cout][4][4] = A W3 A^T of cvae_conv3_to_k4 (same sums, same order).
+ *                             [Cin][Cout][4][4] = A W3 A^T of cvae_conv3_to_k4 (same sums, same order);
+ *   kind CVAE_FOLD_CONV_K3S2: w = nn.Conv2d(k3, s2, p1) weight [Cout][Cin][3][3] (the ViT-VAE stem), w_out the k4/s2/p1 weight [Cout][Cin][4][4] with
+ *                             w_out[..][kh][kw] = w[..][kh][kw] s for kh, kw < 3 and a zero fourth row and column: both kernels read in[2 o - 1 + k] and
+ *                             give equal output extents on even inputs, so cvae_conv_down with w_out computes the k3 layer (16 taps issued for 9).
  * gamma NULL (the array, or its entry k): no BatchNorm — the plain transform, bias copied (a NULL bias entry counts as zeros); otherwise beta /
  * mean / var entries are required.  w and w_out 16-byte aligned (an UpConv2dK3 with Cin % 4 != 0: w_out only), else CVAE_E_UNSUPPORTED.
  * Outputs fp32. */
 #define CVAE_FOLD_CONV_K4   0
 #define CVAE_FOLD_UPCONV_K3 1
+#define CVAE_FOLD_CONV_K3S2 3   /* 2 stays unassigned */
 int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
                       const float* const* beta, const float* const* mean, const float* const* var, const float* eps, float* const* w_out,
                       float* const* b_out, void* stream);
@@ -249,6 +254,31 @@ int cvae_row_diff_norms(const void* a, const void* b, const int64_t* ref, float*
  * mean = (x_0 + .. + x_{K-1}) / K, std = sqrt(sum_k (x_k - mean)^2 / (K - 1)) — torch.stack(x).mean(0) / .std(0) in the two-pass form;
  * K = 1 gives NaN std, as torch does.  Fixed order, no reductions across elements. */
 int cvae_stack_mean_std(const float* const* x, int count, float* mean, float* std, int64_t n, void* stream);
+
+/* ---- ViT-VAE encoder, eval mode (csrc/vit.hip; vessel_analysis/00_core/vit_backbone.py:158-179, latent_translator/models.py:95-110) ----------------
+ * Transformer width 256, 8 heads x 32.  dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16 (bf16 operands); accumulation, softmax, LayerNorm statistics and the
+ * residual stream are fp32 in both.  No atomics: fixed-order sums, bit-reproducible, and a row's bits do not depend on the other rows of the launch.
+ * Pointers 16-byte aligned, strides (in elements) multiples of 16 bytes, else CVAE_E_UNSUPPORTED.
+ *   cvae_vit_tokens     tokens fp32 [B][n_patches + 1][256]: row 0 = cls + pos[0], row 1 + i = stem[b][i] + pos[1 + i]; stem [B][n_patches][256] (the channels-last
+ *                       output of the last stem conv, stem_dtype fp32 or bf16), cls [256], pos [n_patches + 1][256]
+ *   cvae_layernorm256   y[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over 256 columns (biased variance, two-pass); x fp32 with row stride x_stride,
+ *                       y [rows][256] in out_dtype
+ *   cvae_token_gemm     y[M][N] = epi(x[M][K] W[N][K]^T + bias), (K, N) in {(256, 768), (256, 256), (256, 512), (512, 256)}; x in `dtype`, W / bias the fp32
+ *                       nn.Linear tensors (W is rounded to bf16 on its way into LDS in bf16 mode).  epilogue NONE / GELU (exact erf): y in `dtype`;
+ *                       RESIDUAL: y fp32 = resid + (x W^T + bias), resid fp32 with row stride resid_stride (y == resid: the residual stream in place)
+ *   cvae_mhsa_fwd       out [B][n_query_rows][256] = softmax(q k^T / sqrt(32)) v per head, for the FIRST n_query_rows tokens as queries against all n_tokens
+ *                       keys (n_query_rows = n_tokens: plain self-attention; 1: the CLS row of the last block).  q / k / v: row strides and batch strides in
+ *                       elements, head h in columns 32 h .. 32 h + 31 (the packed in-projection output [B][n_tokens][768]: q, q + 256, q + 512, strides 768).
+ *                       Online softmax over 64-key tiles; in bf16 mode P is rounded to bf16 for the P V product while its row sum stays fp32. */
+#define CVAE_GEMM_EPI_NONE     0
+#define CVAE_GEMM_EPI_GELU     1
+#define CVAE_GEMM_EPI_RESIDUAL 2
+int cvae_vit_tokens(const void* stem, int stem_dtype, const float* cls, const float* pos, float* tokens, int64_t B, int64_t n_patches, void* stream);
+int cvae_layernorm256(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* y, int64_t rows, float eps, int out_dtype, void* stream);
+int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y, int64_t y_stride,
+                    int64_t M, int64_t K, int64_t N, int epilogue, int dtype, void* stream);
+int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
+                  int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream);
 
 /* ---- The dense bottleneck of CausalBioVAE in 5 + 5 launches (batch M <= 16, fp32 arithmetic) --------------------------------
  * Replaces, between the last encoder conv and the first decoder conv (causal_cascade/models.py:57-79):
@@ -336,7 +366,7 @@ int cvae_conv_wgrad_multi(int count, const void* const* S, const void* const* L,
  * the rows of one channel group are summed by ONE workgroup (same result bits for a given geometry, slower for large P). */
 size_t cvae_channel_sum_workspace_bytes(int64_t P, int64_t C, int dtype);
 int cvae_channel_sum(const void* x, float* out, int64_t P, int64_t C, int dtype, void* workspace, size_t workspace_bytes, void* stream);
-/* y = act(x) elementwise (nn.ReLU / nn.Sigmoid / nn.LeakyReLU(0.2) when not fused into a producer). */
+/* y = act(x) elementwise (nn.ReLU / nn.Sigmoid / nn.LeakyReLU(0.2) / nn.LeakyReLU() when not fused into a producer). */
 int cvae_act_fwd(const void* x, void* y, int64_t n, int act, int dtype, void* stream);
 /* dx = dy * act'(y) elementwise (y = saved activation OUTPUT); dtype applies to all three. */
 int cvae_act_bwd(const void* dy, const void* y, void* dx, int64_t n, int act, int dtype, void* stream);

@@ -9,6 +9,7 @@ What is imported from /root/reference (read-only, nothing is written there):
   * mnist_test/01_baseline_causal_vae/{config,models}.py -> CausalMorphVAE12, LatentDiscriminator (a8)
   * mnist_test/06_model_experiment/{config,models}.py    -> Gaussian-head CausalMorphVAE12
   * vessel_analysis/00_core/models.py: the text of ``CausalVesselVAE`` is compiled with its two unimportable imports dropped (a11)
+  * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode, encode only; `python tools/make_golden.py vitvae`)
   * vessel_analysis/01_train/train.py: only the text of ``loss_function`` is compiled (the module
     itself cannot be imported: it pulls tifffile/torchvision through ``dataset``) (a10)
 The MNIST adversarial loop body (mnist_test/01_baseline_causal_vae/train.py:34-93) cannot be imported
@@ -45,12 +46,12 @@ def digest(t):
     return torch.cat([torch.stack([f.sum(), f.abs().sum(), (f * f).sum()]), head, tail]).numpy()
 
 
-def pack(prefix, named, store):
+def pack(prefix, named, store, full_limit=None):
     for k, v in named.items():
         v = v.detach()
         store[f"{prefix}/{k}#digest"] = digest(v)
         store[f"{prefix}/{k}#shape"] = np.array(v.shape, dtype=np.int64)
-        if v.numel() <= FULL_LIMIT:
+        if v.numel() <= (FULL_LIMIT if full_limit is None else full_limit):
             store[f"{prefix}/{k}"] = v.numpy().copy()
 
 
@@ -315,8 +316,54 @@ def vessel2d_case(name, B=4, seed_data=4321):
     print(name + "_eval", "total", float(total), "keys", len(ev))
 
 
+def vitvae_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, full):
+    """ViTVAE.encode in eval mode at random init (no pretrained file exists offline).  The encoder weights are the seed's draws (the product class
+    constructs the same modules in the same order, so the fixture keeps digests only); the five stem BatchNorm2d layers get non-trivial statistics and
+    affine parameters from a second seed (tests/vit_reference.py:randomize_stem_bn; stored whole: 4 x 736 values).  full: keep the stem output and the
+    token stream after every block (the LAST block's stream as a digest plus its CLS row: three whole [B, N, 256] tensors would pass the size of the
+    largest fixture); otherwise only the CLS row after every block."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_reference import randomize_stem_bn, vit_inputs
+    (vb,) = import_from(os.path.join(REF, "vessel_analysis", "00_core"), "vit_backbone")
+    torch.manual_seed(seed_model)
+    model = vb.ViTVAE(in_channels=1, latent_dim=128, img_size=(H, W), depth=depth)
+    randomize_stem_bn(model.stem, seed_bn)
+    model.eval()
+    x = vit_inputs(B, H, W, seed_data)
+    acts = {}
+    hooks = [model.stem.register_forward_hook(lambda _m, _i, o: acts.__setitem__("stem", o.detach().clone())),
+             model.to_latent.register_forward_hook(lambda _m, _i, o: acts.__setitem__("cls_out", o.detach().clone()))]
+    for i, blk in enumerate(model.transformer):
+        hooks.append(blk.register_forward_hook(lambda _m, _i, o, k=i: acts.__setitem__(f"block{k}", o.detach().clone())))
+    with torch.no_grad():
+        mu, log_var = model.encode(x)
+    for h in hooks:
+        h.remove()
+    store = {"in/seed": np.array([B, H, W, depth, seed_model, seed_bn, seed_data], dtype=np.int64)}
+    pack("sd0", {k: v for k, v in model.state_dict().items() if not k.startswith(("decoder_input.", "decoder."))}, store)
+    pack("in", dict(x=x), store)
+    if full:
+        store["in/x_bits"] = np.packbits(x.numpy().astype(np.uint8).reshape(-1))
+    named = dict(mu=mu, log_var=log_var, cls_out=acts["cls_out"])
+    for i in range(depth):
+        named[f"cls_row{i}"] = acts[f"block{i}"][:, 0]
+        if full and i < depth - 1:
+            named[f"tokens{i}"] = acts[f"block{i}"]
+    if full:
+        named["stem"] = acts["stem"]
+    pack("out", named, store, full_limit=1 << 20)
+    if full:
+        pack("out", {f"tokens{depth - 1}": acts[f"block{depth - 1}"]}, store)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "vitvae":
+        vitvae_case("vitvae_enc_256x320", 3, 256, 320, 2, 42, 4242, 1301, full=True)       # 81 tokens
+        vitvae_case("vitvae_enc_768x1280", 2, 768, 1280, 6, 42, 4242, 1302, full=False)    # 961 tokens
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "vessel2d":
         vessel2d_case("vessel2d_b4")
         return
