@@ -129,6 +129,11 @@ SIGNATURES = {
     "cvae_layernorm256": [_p, _i64, _p, _p, _p, _i64, _f, _i, _p],
     "cvae_token_gemm": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
     "cvae_mhsa_fwd": [_p] * 4 + [_i64] * 9 + [_i, _p],
+    "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
+    "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
+    "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],
+    "cvae_conv_s1_c1": [_p] * 4 + [_i64] * 4 + [_i, _i, _p],
+    "cvae_latent_to_grid": [_p] * 4 + [_i64] * 4 + [_i, _p],
     "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
     "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
     "cvae_stack_mean_std": [_p, _i, _p, _p, _i64, _p],
@@ -141,7 +146,8 @@ SIGNATURES = {
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
-            "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz}
+            "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
+            "cvae_conv_s1_weight_elems": _i64}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

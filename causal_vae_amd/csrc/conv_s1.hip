@@ -1,0 +1,419 @@
+// conv_s1.hip — the stride-1 window convolutions and the latent-to-grid GEMM of the ViT-VAE decoder in eval mode
+// (vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193 of the reference):
+//   * cvae_conv_s1: halo-tiled implicit GEMM on the MFMA over channels-last [B][H][W][C] tensors, two window forms from one template:
+//       K3        Conv2d(k3, s1, p1), Cin = Cout in {32, 64, 128} (the ResBlock convs): 3 x 3 centred window, zero padding of one;
+//       SUBPIXEL  ConvTranspose2d(k3, s2, p1, output_padding 1) with Cout = 16, Cin in {32, 16}, as a stride-1 conv with a 2 x 2 FORWARD window (input
+//                 padded by one at the right and bottom) to N = 4 Cout channels (py, px, co) and a pixel-shuffle store: out[2y + py][2x + px][co].
+//                 o = 2i - 1 + k gives, per direction: parity 0 reads in[y] with k = 1; parity 1 reads in[y] with k = 2 and in[y + 1] with k = 0.
+//     The weight is the GEMM matrix [N][KT] in the compute dtype, k = tap * Cin + ci, KT = K rounded up to 64 with zero columns (what cvae_fold_bn_conv's
+//     kinds CVAE_FOLD_CONV_K3S1 / CVAE_FOLD_CONVT_K3S2_SUBPIXEL write in fp32; cvae_conv_s1_pack_weights casts a list of them to bf16 in one launch).
+//     Workgroup = 4 waves = 8 x 16 output positions (a wave owns two rows of 16); the tile plus its halo is staged in LDS ONCE at full channel depth, then
+//     K is walked in 128-byte chunks of the weight rows (64 bf16 / 32 fp32) through LDS, the next chunk's global loads in flight while the MFMAs of the
+//     current one run.  D = W x^T as in csrc/vit.hip: A = weight rows (output channels), B = positions, so a lane owns ONE position and four consecutive
+//     channels per register group.  bf16 operands on v_mfma_f32_32x32x16_bf16, exact fp32 on v_mfma_f32_32x32x2_f32; accumulation fp32 in a fixed order
+//     (no atomics, no split-K; the tile geometry does not depend on B, so a sample's bits do not depend on the batch it travels in).
+//     Epilogue in fp32 before the one rounding: + bias, + residual (optional, the output's shape and dtype), activation.  Stores are 16 bytes: fp32 as
+//     they are; bf16 after one v_permlane32_swap per dword that hands lane half 0 channels 0-7 and lane half 1 channels 8-15 of a 16-channel block.
+//   * cvae_conv_s1_c1: Conv2d(16 -> 1, k3, s1, p1) to an fp32 [B][1][H][W] image: bandwidth-bound, one thread per four output pixels of a row, 16-byte loads.
+//   * cvae_latent_to_grid: out[b][p][c] = sum_k W[c P + p][k] z[b][k] + bias[c P + p]: nn.Linear(latent, C P) + view(B, C, gh, gw) written channels-last
+//     in the compute dtype.  W is the fp32 nn.Linear tensor, read ONCE per launch with 16-byte loads for up to 16 batch rows (z sits in LDS).
+#include "common.h"
+
+namespace {
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));          // a 16-byte piece that stays in registers when held in an array
+
+__device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
+    const float4 q = *(const float4*)p;
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+__device__ __forceinline__ void ld4(const bf16* p, float (&v)[4]) {
+    const bf16x4 q = *(const bf16x4*)p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (float)q[i];
+}
+
+// 16 consecutive channels in 16-byte loads: four float4 / two bf16x8
+__device__ __forceinline__ void ld16(const float* p, float (&v)[16]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 f = ((const float4*)p)[q];
+        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
+    }
+}
+__device__ __forceinline__ void ld16(const bf16* p, float (&v)[16]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const bf16x8 f = ((const bf16x8*)p)[q];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[8 * q + e] = (float)f[e];
+    }
+}
+
+// f(Int<0>{}) .. f(Int<N - 1>{}): a loop whose index is a compile-time constant in every iteration (register arrays stay in registers)
+template <int N, typename Fn> __device__ __forceinline__ void static_for(Fn&& f) {
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(Int<N - 1>{});
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ stride-1 window conv on the MFMA
+#define S1_TH 8
+#define S1_TW 16
+#define S1_KPAD 64                 // K is padded to a multiple of this many elements in the packed weight (both dtypes)
+
+template <typename T, int CIN, int FORM> struct S1Geom {
+    static constexpr int WIN = FORM == CVAE_CONV_S1_K3 ? 3 : 2;
+    static constexpr int PADL = FORM == CVAE_CONV_S1_K3 ? 1 : 0;       // the window starts at output position - PADL
+    static constexpr int TAPS = WIN * WIN;
+    static constexpr int K = TAPS * CIN;
+    static constexpr int KT = (K + S1_KPAD - 1) / S1_KPAD * S1_KPAD;
+    static constexpr int HR = S1_TH + WIN - 1, HC = S1_TW + WIN - 1;
+    static constexpr int E16 = 16 / sizeof(T);
+    static constexpr int PITCH = CIN + E16;                            // halo position pitch in elements: + 16 bytes (rows fall 4 banks apart mod 32)
+    static constexpr int KC = 128 / sizeof(T);                         // k elements per weight chunk
+    static constexpr int WPITCH = KC + E16;                            // 144 bytes
+    static constexpr int PPP = CIN / E16;                              // 16-byte pieces per position
+};
+
+template <typename T, int CIN, int NT, int FORM>
+__global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, const T* resid, T* y,
+                                                      int H, int W, int act) {
+    using G = S1Geom<T, CIN, FORM>;
+    constexpr bool BF = std::is_same<T, bf16>::value;
+    constexpr int N = 32 * NT;
+    constexpr int COUT = FORM == CVAE_CONV_S1_K3 ? N : N / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    T* hs = (T*)smem;                                                   // [HR * HC + 1][PITCH]: the last row is zeros, read for the zero-padded k >= K
+    T* ws = hs + (G::HR * G::HC + 1) * G::PITCH;                        // [N][WPITCH]
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int x0 = blockIdx.x * S1_TW, y0 = blockIdx.y * S1_TH;
+    const int64_t b = blockIdx.z;
+    const T* xb = x + b * (int64_t)H * W * CIN;
+
+    u32x4 rw[NT];
+    const T* wt = w + (int64_t)(t >> 3) * G::KT + (t & 7) * G::E16;      // this thread's piece of weight rows (t >> 3) + 32 i
+    static_for<NT>([&](auto iv) { constexpr int i = decltype(iv)::value; rw[i] = *(const u32x4*)(wt + (int64_t)32 * i * G::KT); });
+    // the tile and its halo, once, at full channel depth; positions outside the image are zeros (the conv's padding)
+    for (int i = t; i < (G::HR * G::HC + 1) * G::PPP; i += 256) {
+        const int pos = i / G::PPP, piece = i - pos * G::PPP;
+        const int hy = pos / G::HC, hx = pos - hy * G::HC;
+        const int gy = y0 - G::PADL + hy, gx = x0 - G::PADL + hx;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (pos < G::HR * G::HC && gy >= 0 && gy < H && gx >= 0 && gx < W) v = *(const uint4*)(xb + ((int64_t)gy * W + gx) * CIN + piece * G::E16);
+        *(uint4*)(hs + pos * G::PITCH + piece * G::E16) = v;
+    }
+    f32x16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    const int ly = wave * 2 + (r >> 4), lx = r & 15;                    // this lane's output position in the tile
+    for (int k0 = 0; k0 < G::KT; k0 += G::KC) {
+        __syncthreads();                                                // the previous chunk's fragment reads are done (first pass: nothing pending)
+        static_for<NT>([&](auto iv) {
+            constexpr int i = decltype(iv)::value;
+            *(u32x4*)(ws + ((t >> 3) + 32 * i) * G::WPITCH + (t & 7) * G::E16) = rw[i];
+        });
+        __syncthreads();                                                // weights of this chunk (and, on the first pass, the halo) are visible
+        if (k0 + G::KC < G::KT)
+            static_for<NT>([&](auto iv) { constexpr int i = decltype(iv)::value; rw[i] = *(const u32x4*)(wt + (int64_t)32 * i * G::KT + k0 + G::KC); });
+        if constexpr (BF) {
+#pragma unroll
+            for (int s = 0; s < G::KC / 16; ++s) {
+                const int kk = k0 + 16 * s + 8 * h;
+                const int tap = kk / CIN, ci = kk - tap * CIN;
+                const int dy = tap / G::WIN, dx = tap - dy * G::WIN;
+                const int pos = tap < G::TAPS ? (ly + dy) * G::HC + lx + dx : G::HR * G::HC;      // zero-padded weight columns meet the zero row: exact zeros
+                const bf16x8 bv = *(const bf16x8*)(hs + pos * G::PITCH + ci);
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    const bf16x8 av = *(const bf16x8*)(ws + (j * 32 + r) * G::WPITCH + 16 * s + 8 * h);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[j], 0, 0, 0);
+                }
+            }
+        } else {
+            // 32x32x2: the instruction's k index is the lane half; step (c, u) multiplies k = 16 h + 4 c + u of the chunk
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int kk = k0 + 16 * h + 4 * c;
+                const int tap = kk / CIN, ci = kk - tap * CIN;
+                const int dy = tap / G::WIN, dx = tap - dy * G::WIN;
+                const int pos = tap < G::TAPS ? (ly + dy) * G::HC + lx + dx : G::HR * G::HC;
+                float bv[4], av[NT][4];
+                ld4(hs + pos * G::PITCH + ci, bv);
+#pragma unroll
+                for (int j = 0; j < NT; ++j) ld4(ws + (j * 32 + r) * G::WPITCH + 16 * h + 4 * c, av[j]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][u], bv[u], acc[j], 0, 0, 0);
+            }
+        }
+    }
+    // epilogue: lane (r, h) holds, for its position, channels j 32 + 8 g + 4 h + e in register 4 g + e of acc[j]
+    const int gy = y0 + ly, gx = x0 + lx;
+    const bool live = gy < H && gx < W;                                 // lanes r and r + 32 share a position: the swap below pairs equals
+    auto out_index = [&](int n) -> int64_t {                            // element index of channel n of this position in y (and resid)
+        if (FORM == CVAE_CONV_S1_K3) return ((b * H + gy) * (int64_t)W + gx) * COUT + n;
+        const int q = n / COUT, co = n - q * COUT;
+        return ((b * 2 * H + 2 * gy + (q >> 1)) * (int64_t)(2 * W) + 2 * gx + (q & 1)) * COUT + co;
+    };
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+            float v[2][4];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int g = 2 * gp + q, n = j * 32 + 8 * g + 4 * h;
+                float bv[4];
+                ld4(bias + (n % COUT), bv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[q][e] = acc[j][4 * g + e] + bv[e];
+                if (resid && live) {
+                    float rv[4];
+                    ld4(resid + out_index(n), rv);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[q][e] += rv[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[q][e] = apply_act(v[q][e], act);
+            }
+            if constexpr (BF) {
+                const uint2 a = make_uint2(pack2_bf16(v[0][0], v[0][1]), pack2_bf16(v[0][2], v[0][3]));
+                const uint2 c = make_uint2(pack2_bf16(v[1][0], v[1][1]), pack2_bf16(v[1][2], v[1][3]));
+                const auto sx = __builtin_amdgcn_permlane32_swap(a.x, c.x, false, false);
+                const auto sy = __builtin_amdgcn_permlane32_swap(a.y, c.y, false, false);
+                if (live) *(uint4*)(y + out_index(j * 32 + 16 * gp + 8 * h)) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+            } else if (live) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+                    *(float4*)(y + out_index(j * 32 + 8 * (2 * gp + q) + 4 * h)) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
+            }
+        }
+}
+
+template <typename T, int CIN, int NT, int FORM>
+int conv_s1_launch(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int act, hipStream_t st) {
+    using G = S1Geom<T, CIN, FORM>;
+    auto kern = conv_s1_kernel<T, CIN, NT, FORM>;
+    constexpr size_t LDS = ((size_t)(G::HR * G::HC + 1) * G::PITCH + (size_t)32 * NT * G::WPITCH) * sizeof(T);
+    static_assert(LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
+    // set on every launch: the attribute belongs to the current device's copy of the kernel, and a flag would be shared by devices and host threads
+    if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    const dim3 grid((unsigned)((W + S1_TW - 1) / S1_TW), (unsigned)((H + S1_TH - 1) / S1_TH), (unsigned)B);
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)x, (const T*)w, bias, (const T*)resid, (T*)y, (int)H, (int)W, act);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+// fp32 -> bf16 for a list of tensors in one launch (the packed weights of the bf16 decoder)
+#define S1_PACK_MAX 16
+struct PackTable {
+    const float* src[S1_PACK_MAX];
+    bf16* dst[S1_PACK_MAX];
+    int end[S1_PACK_MAX];             // exclusive prefix sums of blocks
+    int64_t n4[S1_PACK_MAX];          // float4 groups
+    int count;
+};
+__global__ __launch_bounds__(256) void conv_s1_pack_kernel(const PackTable T) {
+    int k = 0;
+    while (k < T.count - 1 && (int)blockIdx.x >= T.end[k]) ++k;
+    const int64_t g = ((int64_t)blockIdx.x - (k ? T.end[k - 1] : 0)) * 256 + threadIdx.x;
+    if (g >= T.n4[k]) return;
+    const float4 v = ((const float4*)T.src[k])[g];
+    ((uint2*)T.dst[k])[g] = make_uint2(pack2_bf16(v.x, v.y), pack2_bf16(v.z, v.w));
+}
+
+// ------------------------------------------------------------------------------------------------ Conv2d(16 -> 1, k3, s1, p1) -> fp32 image
+// One thread per four consecutive output pixels of a row: 3 rows x 6 columns of 16 channels, each read with 16-byte loads; every output pixel adds
+// its 144 products in (ky, kx, ci) order.  Weights sit in LDS as [tap][ci] fp32 (rounded to bf16 first in bf16 mode).
+#define C1_CIN 16
+template <typename T>
+__global__ __launch_bounds__(256) void conv_s1_c1_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y,
+                                                         int64_t B, int H, int W, int act) {
+    __shared__ float wsm[9][C1_CIN];
+    if (threadIdx.x < 9 * C1_CIN) {
+        const int tap = threadIdx.x / C1_CIN, ci = threadIdx.x % C1_CIN;
+        const float v = w[ci * 9 + tap];
+        wsm[tap][ci] = std::is_same<T, bf16>::value ? (float)(bf16)v : v;
+    }
+    __syncthreads();
+    const int W4 = (W + 3) >> 2;
+    const int64_t total = B * H * W4, g = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (g >= total) return;
+    const int xq = (int)(g % W4), yy = (int)((g / W4) % H);
+    const int64_t b = g / ((int64_t)W4 * H);
+    const int xs = xq * 4;
+    const float b0 = bias ? bias[0] : 0.f;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const int gy = yy - 1 + dy;
+        if (gy < 0 || gy >= H) continue;
+        const T* row = x + (b * H + gy) * (int64_t)W * C1_CIN;
+#pragma unroll
+        for (int cx = 0; cx < 6; ++cx) {
+            const int gx = xs - 1 + cx;
+            if (gx < 0 || gx >= W) continue;
+            float v[C1_CIN];
+            ld16(row + (int64_t)gx * C1_CIN, v);
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const int dx = cx - o;
+                if (dx < 0 || dx > 2) continue;
+#pragma unroll
+                for (int ci = 0; ci < C1_CIN; ++ci) acc[o] = fmaf(v[ci], wsm[dy * 3 + dx][ci], acc[o]);
+            }
+        }
+    }
+    float* out = y + (b * H + yy) * (int64_t)W + xs;
+    if ((W & 3) == 0) {
+        *(float4*)out = make_float4(apply_act(acc[0] + b0, act), apply_act(acc[1] + b0, act), apply_act(acc[2] + b0, act), apply_act(acc[3] + b0, act));
+    } else {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+            if (xs + o < W) out[o] = apply_act(acc[o] + b0, act);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ latent -> channels-last grid
+// One wave per (grid position p, block of 32 channels): four steps of 8 channels, 8 lanes per weight row W[c P + p][0 .. K) (16-byte loads, k = 4 l + 32 i
+// per lane), each batch row's dot product summed per lane in k order and then over the 8 lanes by xor shuffles (a fixed tree: a row's bits do not
+// depend on the other rows of the launch).  z [nb <= 16][K] sits in LDS.
+#define L2G_BT 16
+#define L2G_KMAX 512
+template <typename T>
+__global__ __launch_bounds__(256) void latent_to_grid_kernel(const float* __restrict__ z, const float* __restrict__ Wt, const float* __restrict__ bias, T* __restrict__ out,
+                                                             int nb, int K, int64_t P, int C) {
+    __shared__ __attribute__((aligned(16))) float zs[L2G_BT * L2G_KMAX];
+    for (int i = threadIdx.x; i < nb * (K >> 2); i += 256) ((float4*)zs)[i] = ((const float4*)z)[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, l8 = lane & 7, grp = lane >> 3;
+    const int cblocks = C >> 5;
+    const int64_t task = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
+    if (task >= P * cblocks) return;
+    const int64_t p = task / cblocks;
+    const int cb = (int)(task - p * cblocks);
+    const int steps = (K + 31) >> 5;
+    for (int s = 0; s < 4; ++s) {
+        const int c = cb * 32 + s * 8 + grp;
+        const int64_t n = (int64_t)c * P + p;
+        const float* wr = Wt + n * K;
+        float4 wv[L2G_KMAX / 32];
+#pragma unroll
+        for (int i = 0; i < L2G_KMAX / 32; ++i) {
+            const int k = 4 * l8 + 32 * i;
+            wv[i] = (i < steps && k < K) ? *(const float4*)(wr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const float bn = bias ? bias[n] : 0.f;
+        float keep[2] = {0.f, 0.f};
+        for (int bb = 0; bb < nb; ++bb) {
+            float a = 0.f;
+#pragma unroll
+            for (int i = 0; i < L2G_KMAX / 32; ++i) {
+                const int k = 4 * l8 + 32 * i;
+                if (i < steps && k < K) {
+                    const float4 zv = *(const float4*)(zs + bb * K + k);
+                    a = fmaf(wv[i].x, zv.x, a); a = fmaf(wv[i].y, zv.y, a); a = fmaf(wv[i].z, zv.z, a); a = fmaf(wv[i].w, zv.w, a);
+                }
+            }
+            a += __shfl_xor(a, 1, 64);
+            a += __shfl_xor(a, 2, 64);
+            a += __shfl_xor(a, 4, 64);
+            if ((bb & 7) == l8) keep[bb >> 3] = a + bn;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int bb = l8 + 8 * q;
+            if (bb < nb) out[((int64_t)bb * P + p) * C + c] = from_f32<T>(keep[q]);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form) {
+    if (form == CVAE_CONV_S1_K3) return (Cin == Cout && (Cin == 32 || Cin == 64 || Cin == 128)) ? Cout * ((9 * Cin + S1_KPAD - 1) / S1_KPAD * S1_KPAD) : 0;
+    if (form == CVAE_CONV_S1_SUBPIXEL) return (Cout == 16 && (Cin == 32 || Cin == 16)) ? 4 * Cout * ((4 * Cin + S1_KPAD - 1) / S1_KPAD * S1_KPAD) : 0;
+    return 0;
+}
+
+extern "C" int cvae_conv_s1_pack_weights(int count, const float* const* w, void* const* packed, const int64_t* n, void* stream) {
+    if (count <= 0) return CVAE_E_BADSHAPE;
+    if (count > S1_PACK_MAX) return CVAE_E_UNSUPPORTED;
+    if (!w || !packed || !n) return CVAE_E_NULLPTR;
+    PackTable T{};
+    T.count = count;
+    int64_t blocks = 0;
+    for (int k = 0; k < count; ++k) {
+        if (n[k] <= 0 || (n[k] & 3) || n[k] > ((int64_t)1 << 30)) return CVAE_E_BADSHAPE;
+        if (!w[k] || !packed[k]) return CVAE_E_NULLPTR;
+        if (!aligned16(w[k]) || ((uintptr_t)packed[k] & 7)) return CVAE_E_UNSUPPORTED;
+        T.src[k] = w[k]; T.dst[k] = (bf16*)packed[k]; T.n4[k] = n[k] >> 2;
+        blocks += (T.n4[k] + 255) / 256;
+        T.end[k] = (int)blocks;
+    }
+    hipLaunchKernelGGL(conv_s1_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                            int form, int dtype, int act, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || H > 65535 * S1_TH || B > 65535 || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL) return CVAE_E_UNSUPPORTED;
+    if (cvae_conv_s1_weight_elems(Cin, Cout, form) == 0) return CVAE_E_UNSUPPORTED;
+    if (act != CVAE_ACT_NONE && act != CVAE_ACT_LEAKY02 && act != CVAE_ACT_LEAKY001 && act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!x || !w || !bias || !y) return CVAE_E_NULLPTR;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(bias) || !aligned16(y) || !aligned16(resid)) return CVAE_E_UNSUPPORTED;
+    const hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        if (form == CVAE_CONV_S1_K3) {
+            if (Cin == 32) return conv_s1_launch<T, 32, 1, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
+            if (Cin == 64) return conv_s1_launch<T, 64, 2, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
+            return conv_s1_launch<T, 128, 4, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
+        }
+        if (Cin == 32) return conv_s1_launch<T, 32, 2, CVAE_CONV_S1_SUBPIXEL>(x, w, bias, resid, y, B, H, W, act, st);
+        return conv_s1_launch<T, 16, 2, CVAE_CONV_S1_SUBPIXEL>(x, w, bias, resid, y, B, H, W, act, st);
+    });
+}
+
+extern "C" int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act,
+                               void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || H > ((int64_t)1 << 24) || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!x || !w || !y) return CVAE_E_NULLPTR;
+    if (!aligned16(x) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    const int64_t total = B * H * ((W + 3) >> 2), blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
+    const hipStream_t st = (hipStream_t)stream;
+    if (dtype == CVAE_BF16) hipLaunchKernelGGL(conv_s1_c1_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16*)x, w, bias, y, B, (int)H, (int)W, act);
+    else hipLaunchKernelGGL(conv_s1_c1_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, w, bias, y, B, (int)H, (int)W, act);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_latent_to_grid(const float* z, const float* W, const float* bias, void* out, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream) {
+    if (B < 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (B > L2G_BT || K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!z || !W || !out) return CVAE_E_NULLPTR;
+    if (!aligned16(z) || !aligned16(W)) return CVAE_E_UNSUPPORTED;
+    const int64_t blocks = (P * (C >> 5) + 3) / 4;
+    if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
+    const hipStream_t st = (hipStream_t)stream;
+    if (dtype == CVAE_BF16) hipLaunchKernelGGL(latent_to_grid_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (bf16*)out, (int)B, (int)K, P, (int)C);
+    else hipLaunchKernelGGL(latent_to_grid_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (float*)out, (int)B, (int)K, P, (int)C);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}

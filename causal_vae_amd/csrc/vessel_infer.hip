@@ -8,6 +8,8 @@
 // UpConv2dK3 weight [Cout][Cin][3][3] leaves as the transposed k4 weight [Cin][Cout][4][4] = A W3 A^T of cvae_conv3_to_k4 (same sums in the
 // same order, so an entry without BatchNorm reproduces cvae_conv3_to_k4's bits).  A Conv2d(k3, s2, p1) weight [Cout][Cin][3][3] (the ViT-VAE stem) leaves as
 // the k4/s2/p1 weight [Cout][Cin][4][4] whose fourth row and column are zero: both read in[2o - 1 + k], so the products are the same.
+// The ViT-VAE decoder adds three kinds: a ConvTranspose2d(k3, s2, p1, output_padding 1) weight zero-embedded into the transposed k4 weight (scale per
+// Cout = dimension 1), and the GEMM matrices csrc/conv_s1.hip reads for a Conv2d(k3, s1, p1) and for the sub-pixel form of the narrow transposed convs.
 #include "common.h"
 
 namespace {
@@ -94,6 +96,61 @@ __global__ __launch_bounds__(256) void fold_bn_conv_kernel(const FoldTable T) {
                     o = make_float4(w3[0] * s, w3[1] * s, w3[2] * s, 0.f);
                 }
                 ((float4*)E.w_out)[g] = o;
+            }
+        }
+        return;
+    }
+    if (E.kind == CVAE_FOLD_CONVT_K3S2) {
+        // ConvTranspose2d(k3, s2, p1, output_padding 1) [Cin][Cout][3][3] -> the transposed k4/s2/p1 weight [Cin][Cout][4][4] with a zero fourth row and column
+        // (both scatter in[i] to out[2 i - 1 + k]; the k4 extent 2 n is the k3 extent with output_padding 1); the scale runs over Cout, dimension 1
+        const int64_t n4 = (int64_t)E.cout * E.cin * 4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t g = (int64_t)blk * FOLD_K4_PER_BLOCK + t + u * 256;
+            if (g < n4) {
+                const int kh = (int)(g & 3);
+                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (kh < 3) {
+                    const float* w3 = E.w + (g >> 2) * 9 + kh * 3;
+                    const float s = fold_scale(E, (int)((g >> 2) % E.cout));
+                    o = make_float4(w3[0] * s, w3[1] * s, w3[2] * s, 0.f);
+                }
+                ((float4*)E.w_out)[g] = o;
+            }
+        }
+        return;
+    }
+    if (E.kind == CVAE_FOLD_CONV_K3S1 || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL) {
+        // the GEMM matrix [N][KT] of cvae_conv_s1 (csrc/conv_s1.hip), k = tap * Cin + ci, KT = K rounded up to 64 with zero columns; a float4 group is 4
+        // consecutive ci of one (n, tap).  K3S1: Conv2d [Cout][Cin][3][3], N = Cout, tap = ky * 3 + kx.  SUBPIXEL: ConvTranspose2d [Cin][Cout][3][3],
+        // N = 4 Cout with n = (py * 2 + px) * Cout + co, tap = dy * 2 + dx, k index per direction: parity 0: {d 0 -> k 1}; parity 1: {d 0 -> k 2, d 1 -> k 0}
+        const bool sp = E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL;
+        const int taps = sp ? 4 : 9, N = sp ? 4 * E.cout : E.cout;
+        const int K = taps * E.cin, KT = (K + 63) / 64 * 64, kt4 = KT >> 2;
+        const int64_t n4 = (int64_t)N * kt4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t g = (int64_t)blk * FOLD_K4_PER_BLOCK + t + u * 256;
+            if (g < n4) {
+                const int n = (int)(g / kt4), k = (int)(g - (int64_t)n * kt4) * 4;
+                float o[4] = {0.f, 0.f, 0.f, 0.f};
+                if (k < K) {
+                    const int tap = k / E.cin, ci = k - tap * E.cin;
+                    if (!sp) {
+                        const float s = fold_scale(E, n);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = E.w[((size_t)n * E.cin + ci + e) * 9 + tap] * s;
+                    } else {
+                        const int q = n / E.cout, co = n - q * E.cout, py = q >> 1, px = q & 1, dy = tap >> 1, dx = tap & 1;
+                        const int ky = py ? (dy ? 0 : 2) : (dy ? -1 : 1), kx = px ? (dx ? 0 : 2) : (dx ? -1 : 1);
+                        if (ky >= 0 && kx >= 0) {
+                            const float s = fold_scale(E, co);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[e] = E.w[((size_t)(ci + e) * E.cout + co) * 9 + ky * 3 + kx] * s;
+                        }
+                    }
+                }
+                ((float4*)E.w_out)[g] = make_float4(o[0], o[1], o[2], o[3]);
             }
         }
         return;
@@ -300,7 +357,11 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         FoldEntry& E = T.e[k];
         const int64_t Cout = dims[2 * k], Cin = dims[2 * k + 1];
         if (Cout <= 0 || Cin <= 0 || Cout * Cin > ((int64_t)1 << 28)) return CVAE_E_BADSHAPE;
-        if (kind[k] != CVAE_FOLD_CONV_K4 && kind[k] != CVAE_FOLD_UPCONV_K3 && kind[k] != CVAE_FOLD_CONV_K3S2) return CVAE_E_UNSUPPORTED;
+        if (kind[k] != CVAE_FOLD_CONV_K4 && kind[k] != CVAE_FOLD_UPCONV_K3 && kind[k] != CVAE_FOLD_CONV_K3S2 && kind[k] != CVAE_FOLD_CONVT_K3S2 &&
+            kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL)
+            return CVAE_E_UNSUPPORTED;
+        const bool gemm_form = kind[k] == CVAE_FOLD_CONV_K3S1 || kind[k] == CVAE_FOLD_CONVT_K3S2_SUBPIXEL;
+        if (gemm_form && (Cin & 3)) return CVAE_E_UNSUPPORTED;
         if (!w[k] || !w_out[k] || !b_out[k]) return CVAE_E_NULLPTR;
         const bool bn = gamma && gamma[k];
         if (bn && (!beta || !beta[k] || !mean || !mean[k] || !var || !var[k])) return CVAE_E_NULLPTR;
@@ -315,7 +376,9 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         E.eps = eps[k];
         E.kind = kind[k];
         E.cout = (int)Cout; E.cin = (int)Cin;
-        E.wblocks = kind[k] != CVAE_FOLD_UPCONV_K3 ? (int)((Cout * Cin * 4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
+        const int64_t gemm_kt = ((kind[k] == CVAE_FOLD_CONV_K3S1 ? 9 : 4) * Cin + 63) / 64 * 64;
+        E.wblocks = gemm_form ? (int)(((kind[k] == CVAE_FOLD_CONV_K3S1 ? 1 : 4) * Cout * (gemm_kt / 4) + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
+                  : kind[k] != CVAE_FOLD_UPCONV_K3 ? (int)((Cout * Cin * 4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
                                                  : (int)(((Cout + FOLD_K3_TILE - 1) / FOLD_K3_TILE) * ((Cin + FOLD_K3_TILE - 1) / FOLD_K3_TILE));
         E.bblocks = (int)((Cout + 255) / 256);
         blocks += E.wblocks + E.bblocks;

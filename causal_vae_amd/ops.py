@@ -1823,6 +1823,9 @@ class Conv3ToK4(torch.autograd.Function):
 # Forward-only helpers of the eval-mode decode and the analysis sweeps: they enqueue their kernels and return plain tensors; asked for a gradient
 # they raise (the reference consumers run them under no_grad).
 FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2 = 0, 1, 3        # CVAE_FOLD_CONV_K4 / CVAE_FOLD_UPCONV_K3 / CVAE_FOLD_CONV_K3S2
+FOLD_CONVT_K3S2, FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL = 4, 5, 6      # the ViT-VAE decoder's kinds (CVAE_FOLD_CONVT_K3S2 / _CONV_K3S1 / _CONVT_K3S2_SUBPIXEL)
+_FOLD_CONVT = (FOLD_CONVT_K3S2, FOLD_CONVT_K3S2_SUBPIXEL)     # weight [Cin][Cout][3][3]: the BatchNorm's channels are dimension 1
+_FOLD_GEMM = (FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL)       # w_out is the [N][KT] matrix of conv_s1
 
 
 def _forward_only(what, *tensors):
@@ -1835,6 +1838,9 @@ def fold_bn_conv(entries):
     entries: (weight, kind, bias, bn) with kind FOLD_CONV_K4 (nn.Conv2d k4 weight, layout kept), FOLD_UPCONV_K3 (the Conv2d(k3) of an Upsample x2 +
     Conv2d pair -> its transposed k4 weight [Cin][Cout][4][4]) or FOLD_CONV_K3S2 (nn.Conv2d(k3, s2, p1) weight -> the k4/s2/p1 weight [Cout][Cin][4][4]
     with a zero fourth row and column) and bn an nn.BatchNorm2d on running statistics, or None (plain transform, bias copied).
+    The ViT-VAE decoder's kinds: FOLD_CONVT_K3S2 (nn.ConvTranspose2d(k3, s2, p1, output_padding 1) weight [Cin][Cout][3][3] -> the transposed k4 weight
+    [Cin][Cout][4][4], zero fourth row and column, scaled per Cout), FOLD_CONV_K3S1 (nn.Conv2d(k3, s1, p1) weight -> conv_s1's matrix [Cout][KT]) and
+    FOLD_CONVT_K3S2_SUBPIXEL (the ConvTranspose2d weight -> conv_s1's sub-pixel matrix [4 Cout][KT]).
     Returns [(w_out, b_out)] fp32, all views of one fresh buffer."""
     import ctypes as C
     k = len(entries)
@@ -1847,14 +1853,22 @@ def fold_bn_conv(entries):
             raise L.CvaeError("fold_bn_conv: the BatchNorm2d needs running statistics and an affine weight (eval mode, track_running_stats, affine)")
     sizes = []
     for w, kind, _b, _bn in entries:
-        if kind not in (FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2) or w.dim() != 4 or tuple(w.shape[2:]) != ((4, 4) if kind == FOLD_CONV_K4 else (3, 3)):
+        if (kind not in (FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2) + _FOLD_CONVT + _FOLD_GEMM or w.dim() != 4
+                or tuple(w.shape[2:]) != ((4, 4) if kind == FOLD_CONV_K4 else (3, 3))):
             raise L.CvaeError(f"fold_bn_conv: kind {kind} does not match a weight of shape {tuple(w.shape)}")
-        sizes.append((w.shape[0] * w.shape[1] * 16, w.shape[0]))
+        cout = w.shape[1] if kind in _FOLD_CONVT else w.shape[0]
+        if kind in _FOLD_GEMM:
+            cin, taps, rows = (w.shape[0], 4, 4 * cout) if kind in _FOLD_CONVT else (w.shape[1], 9, cout)
+            sizes.append((rows * ((taps * cin + 63) // 64 * 64), cout))
+        else:
+            sizes.append((w.shape[0] * w.shape[1] * 16, cout))
     pad = lambda n: (n + 3) // 4 * 4                      # every piece starts on 16 bytes
     buf = torch.empty(sum(pad(a) + pad(b) for a, b in sizes), dtype=torch.float32, device=entries[0][0].device)
     outs, off = [], 0
     for (w, kind, _b, _bn), (nw, nb) in zip(entries, sizes):
         shape = tuple(w.shape[:2]) + (4, 4) if kind != FOLD_UPCONV_K3 else (w.shape[1], w.shape[0], 4, 4)
+        if kind in _FOLD_GEMM:
+            shape = (4 * nb if kind in _FOLD_CONVT else nb, -1)
         wo = buf[off:off + nw].view(shape)
         off += pad(nw)
         bo = buf[off:off + nb]
@@ -1862,7 +1876,7 @@ def fold_bn_conv(entries):
         outs.append((wo, bo))
     ws = [w.contiguous() for w, _k, _b, _bn in entries]
     vp = lambda v: (C.c_void_p * k)(*v)
-    dims = [d for w in ws for d in (w.shape[0], w.shape[1])]
+    dims = [d for w, (_w, kind, _b, _bn) in zip(ws, entries) for d in ((w.shape[1], w.shape[0]) if kind in _FOLD_CONVT else (w.shape[0], w.shape[1]))]
     bns = [bn for _w, _k, _b, bn in entries]
     f32 = lambda t: None if t is None else t.detach().float().contiguous()
     keep = [(f32(bn.weight), f32(bn.bias), f32(bn.running_mean), f32(bn.running_var)) if bn is not None else (None,) * 4 for bn in bns]
@@ -1988,4 +2002,90 @@ def mhsa(q, k, v, n_query_rows=None):
     out = _empty((B, nq, 256), q.dtype, q)
     check(lib.cvae_mhsa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq,
                             L.dtype_code(q.dtype), stream()), "mhsa_fwd")
+    return out
+
+
+# ---- ViT-VAE decoder (csrc/conv_s1.hip): forward-only building blocks on raw tensors -------------------------------------------------
+CONV_S1_K3, CONV_S1_SUBPIXEL = 0, 1      # CVAE_CONV_S1_*
+
+
+def conv_s1_pack_weights(mats):
+    """bf16 copies of up to 16 fp32 conv_s1 matrices (fold_bn_conv's FOLD_CONV_K3S1 / FOLD_CONVT_K3S2_SUBPIXEL outputs) in ONE launch
+    (cvae_conv_s1_pack_weights); views of one fresh buffer."""
+    import ctypes as C
+    k = len(mats)
+    if not 1 <= k <= 16:
+        raise L.CvaeError(f"conv_s1_pack_weights: 1 to 16 matrices per launch, got {k}")
+    L.require_gpu(*mats)
+    _forward_only("conv_s1_pack_weights", *mats)
+    if any(m.dtype != torch.float32 or not m.is_contiguous() or m.numel() % 8 for m in mats):
+        raise L.CvaeError("conv_s1_pack_weights: contiguous fp32 matrices with a multiple of 8 elements expected")
+    buf = torch.empty(sum(m.numel() for m in mats), dtype=torch.bfloat16, device=mats[0].device)
+    outs, off = [], 0
+    for m in mats:
+        outs.append(buf[off:off + m.numel()].view(m.shape))
+        off += m.numel()
+    vp = lambda v: (C.c_void_p * k)(*v)
+    check(lib.cvae_conv_s1_pack_weights(k, vp([m.data_ptr() for m in mats]), vp([o.data_ptr() for o in outs]), (C.c_int64 * k)(*[m.numel() for m in mats]), stream()),
+          "conv_s1_pack_weights")
+    return outs
+
+
+def conv_s1(x, wmat, bias, form, act=None, resid=None):
+    """act(conv(x) + bias + resid) on a channels-last [B, H, W, Cin] tensor (cvae_conv_s1; fp32 or bf16 = the arithmetic mode).  form CONV_S1_K3:
+    nn.Conv2d(C, C, 3, 1, 1), C in {32, 64, 128} -> [B, H, W, C]; CONV_S1_SUBPIXEL: nn.ConvTranspose2d(Cin, 16, 3, 2, 1, output_padding=1), Cin in {32, 16}
+    -> [B, 2H, 2W, 16].  wmat: the matrix fold_bn_conv wrote for the layer, in x's dtype (conv_s1_pack_weights for bf16); bias fp32 [Cout];
+    resid (optional): the output's shape and dtype, added in fp32 before the activation."""
+    L.require_gpu(x, wmat, bias, resid)
+    _forward_only("conv_s1", x, wmat, bias, resid)
+    if x.dim() != 4 or not x.is_contiguous() or form not in (CONV_S1_K3, CONV_S1_SUBPIXEL):
+        raise L.CvaeError(f"conv_s1: a contiguous channels-last [B, H, W, C] tensor expected, got {tuple(x.shape)}")
+    B, H, W, Cin = x.shape
+    Cout = bias.numel()
+    n = lib.cvae_conv_s1_weight_elems(Cin, Cout, form)
+    if n == 0:
+        raise L.CvaeError(f"conv_s1: {Cin} -> {Cout} channels in form {form}: {L.strerror(-3)}")
+    if wmat.dtype != x.dtype or wmat.numel() != n or not wmat.is_contiguous() or bias.dtype != torch.float32:
+        raise L.CvaeError(f"conv_s1: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {Cin} -> {Cout} channels in {x.dtype} ({n} elements)")
+    oshape = (B, H, W, Cout) if form == CONV_S1_K3 else (B, 2 * H, 2 * W, Cout)
+    if resid is not None and (tuple(resid.shape) != oshape or resid.dtype != x.dtype or not resid.is_contiguous()):
+        raise L.CvaeError(f"conv_s1: the residual must be a contiguous {oshape} {x.dtype} tensor")
+    y = _empty(oshape, x.dtype, x)
+    check(lib.cvae_conv_s1(ptr(x), ptr(wmat), ptr(bias.detach().contiguous()), ptr(resid), ptr(y), B, H, W, Cin, Cout, form, L.dtype_code(x.dtype), L.act_code(act),
+                           stream()), "conv_s1")
+    return y
+
+
+def conv_s1_c1(x, weight, bias, act=None):
+    """nn.Conv2d(16, 1, 3, 1, 1) of a channels-last [B, H, W, 16] tensor (fp32 or bf16) with the fp32 module weight [1, 16, 3, 3] as it is
+    -> fp32 [B, 1, H, W] (cvae_conv_s1_c1)."""
+    L.require_gpu(x, weight, bias)
+    _forward_only("conv_s1_c1", x, weight, bias)
+    if x.dim() != 4 or not x.is_contiguous() or tuple(weight.shape) != (1, x.shape[3], 3, 3) or weight.dtype != torch.float32:
+        raise L.CvaeError(f"conv_s1_c1: x {tuple(x.shape)}, weight {tuple(weight.shape)} {weight.dtype}")
+    B, H, W, Cin = x.shape
+    y = _empty((B, 1, H, W), torch.float32, x)
+    check(lib.cvae_conv_s1_c1(ptr(x), ptr(weight.detach().contiguous()), ptr(bias.detach()) if bias is not None else None, ptr(y), B, H, W, Cin,
+                              L.dtype_code(x.dtype), L.act_code(act), stream()), "conv_s1_c1")
+    return y
+
+
+LATENT_TO_GRID_ROWS = 16     # batch rows per cvae_latent_to_grid launch
+
+
+def latent_to_grid(z, weight, bias, channels, out_dtype):
+    """nn.Linear(K, channels * P)(z).view(B, channels, gh, gw) written channels-last: [B, P, channels] in out_dtype (cvae_latent_to_grid).  z fp32 [B, K];
+    weight / bias the fp32 nn.Linear tensors, read as they are; products and sums fp32.  Batches above 16 rows run as several launches."""
+    L.require_gpu(z, weight, bias)
+    _forward_only("latent_to_grid", z, weight, bias)
+    _rows2d(z, "latent_to_grid")
+    B, K = z.shape
+    if z.dtype != torch.float32 or weight.dtype != torch.float32 or weight.dim() != 2 or weight.shape[1] != K or weight.shape[0] % channels:
+        raise L.CvaeError(f"latent_to_grid: z {tuple(z.shape)} {z.dtype}, weight {tuple(weight.shape)}, channels {channels}")
+    P = weight.shape[0] // channels
+    z, w, b = z.contiguous(), weight.detach().contiguous(), (bias.detach().contiguous() if bias is not None else None)
+    out = _empty((B, P, channels), out_dtype, z)
+    for b0 in range(0, max(B, 1), LATENT_TO_GRID_ROWS):
+        nb = min(LATENT_TO_GRID_ROWS, B - b0)
+        check(lib.cvae_latent_to_grid(ptr(z[b0:]), ptr(w), ptr(b), ptr(out[b0:]), nb, K, P, channels, L.dtype_code(out_dtype), stream()), "latent_to_grid")
     return out

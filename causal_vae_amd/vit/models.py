@@ -11,7 +11,17 @@ the arithmetic runs in libcvae_hip.so:
   block       cvae_layernorm256, cvae_token_gemm (packed QKV), cvae_mhsa_fwd, cvae_token_gemm (+ residual), cvae_layernorm256,
               cvae_token_gemm (GELU), cvae_token_gemm (+ residual): 7 launches
   last block  encode reads x[:, 0] only: K and V of all tokens, everything else for the CLS row alone (n_query_rows = 1)
-decode / forward are not built (the ViT decoder needs kernels this library does not have), hence the class name.
+ViTVAEEncoder stops there (encode only; it carries no decoder parameters).
+
+ViTVAE(ViTVAEEncoder) adds the decoder half (vit_backbone.py:115-156, 181-199): decoder_input and decoder are built AFTER the encoder's modules, in the
+reference's order and with its attribute tree (decoder.{0,1,4,5,8,9,12,13,15,16,18}, decoder.{3,7,11}.conv.{0,1,3,4}), so `torch.manual_seed(s); ViTVAE(...)`
+draws the reference's weights and the state_dict key sets are equal.  decode, per call:
+  fold           every BatchNorm2d of the decoder folded into the conv in front of it, ONE cvae_fold_bn_conv launch (11 layers), on every call
+  decoder_input  cvae_latent_to_grid: the fp32 nn.Linear weight read once, output already channels-last [B, gh, gw, 256] (no view, no transposition)
+  256->128->64->32   ConvTranspose2d(k3, s2, p1, op1) zero-embedded into the transposed k4 weight: cvae_conv_up with LeakyReLU(0.01) in its epilogue
+  ResBlock(C)    two cvae_conv_s1 launches (3 x 3 window): LeakyReLU(0.2) in the first, the block input as the residual of the second
+  32->16, 16->16 cvae_conv_s1 in sub-pixel form (2 x 2 forward window to 64 channels, pixel-shuffle store), LeakyReLU(0.01)
+  16->1          cvae_conv_s1_c1 -> fp32 [B, 1, H, W]
 """
 import numpy as np
 import torch
@@ -142,6 +152,113 @@ class ViTVAEEncoder(nn.Module):
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
 
+class _ResBlock(nn.Module):
+    """Parameter holder with the reference ResBlock's child (vit_backbone.py:7-19): x + conv(x)."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.conv = nn.Sequential(nn.Conv2d(channels, channels, 3, 1, 1), nn.BatchNorm2d(channels), nn.LeakyReLU(0.2, inplace=True),
+                                  nn.Conv2d(channels, channels, 3, 1, 1), nn.BatchNorm2d(channels))
+
+
+DECODER_CHANNELS = (128, 64, 32, 16, 16)     # outputs of the five transposed convs; a ResBlock follows each of the first three
+
+
+class ViTVAE(ViTVAEEncoder):
+    """The reference's ViTVAE for eval-mode inference: encode (ViTVAEEncoder), decode, reparameterize, forward, reconstruct."""
+
+    def __init__(self, in_channels=1, latent_dim=128, img_size=(768, 1280), patch_size=32, embed_dim=256, depth=6, heads=8, mlp_dim=512):
+        super().__init__(in_channels, latent_dim, img_size, patch_size, embed_dim, depth, heads, mlp_dim)
+        self.decoder_input = nn.Linear(latent_dim, embed_dim * self.grid_h * self.grid_w)
+        dec, cin = [], embed_dim
+        for i, cout in enumerate(DECODER_CHANNELS):
+            dec += [nn.ConvTranspose2d(cin, cout, kernel_size=3, stride=2, padding=1, output_padding=1), nn.BatchNorm2d(cout), nn.LeakyReLU()]
+            if i < 3:
+                dec.append(_ResBlock(cout))
+            cin = cout
+        dec.append(nn.Conv2d(cin, in_channels, kernel_size=3, padding=1))
+        self.decoder = nn.Sequential(*dec)
+
+    def _decoder_plan(self):
+        """[(kind, modules)] in execution order: ("up", convT, bn) / ("sub", convT, bn) / ("res", block) and the output conv last."""
+        mods, plan, i = list(self.decoder), [], 0
+        while i < len(mods) - 1:
+            if isinstance(mods[i], _ResBlock):
+                plan.append(("res", mods[i]))
+                i += 1
+            else:
+                plan.append(("up" if mods[i].out_channels % 32 == 0 else "sub", mods[i], mods[i + 1]))
+                i += 3
+        return plan, mods[-1]
+
+    @torch.no_grad()
+    def decode(self, z):
+        """ViTVAE.decode (vit_backbone.py:186-193) in eval mode: [B, latent_dim] fp32 -> [B, 1, H, W] fp32."""
+        return self._decode(z)
+
+    @torch.no_grad()
+    def _decode(self, z, collect=None):
+        """collect (a dict, for tests): receives `grid` (decoder_input's output, channels-last [B, gh, gw, 256]) and `stages` (the channels-last
+        activation after each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order)."""
+        if self.training:
+            raise RuntimeError("ViTVAE: put the model in eval mode first (model.eval()): batch-statistics BatchNorm2d is not implemented, the decoder "
+                               "runs inference only")
+        if z.dim() != 2 or z.shape[1] != self.latent_dim or z.dtype != torch.float32:
+            raise CvaeError(f"ViTVAE.decode expects a float32 [B, {self.latent_dim}] batch, got {tuple(z.shape)} {z.dtype}")
+        require_gpu(z, self.decoder_input.weight)
+        dt = self.compute_dtype
+        plan, out_conv = self._decoder_plan()
+        table = []
+        for st in plan:
+            if st[0] == "res":
+                c = st[1].conv
+                table += [(c[0].weight, ops.FOLD_CONV_K3S1, c[0].bias, c[1]), (c[3].weight, ops.FOLD_CONV_K3S1, c[3].bias, c[4])]
+            else:
+                table.append((st[1].weight, ops.FOLD_CONVT_K3S2 if st[0] == "up" else ops.FOLD_CONVT_K3S2_SUBPIXEL, st[1].bias, st[2]))
+        folded = ops.fold_bn_conv(table)                               # one launch, on every call: parameters may have been rewritten
+        gemm = [i for i, e in enumerate(table) if e[1] != ops.FOLD_CONVT_K3S2]
+        mats = {i: folded[i][0] for i in gemm}
+        if dt == torch.bfloat16:
+            mats = dict(zip(gemm, ops.conv_s1_pack_weights([folded[i][0] for i in gemm])))
+        B = z.shape[0]
+        h = ops.latent_to_grid(z, self.decoder_input.weight, self.decoder_input.bias, self.embed_dim, dt).view(B, self.grid_h, self.grid_w, self.embed_dim)
+        if collect is not None:
+            collect["grid"], collect["stages"] = h, []
+        k = 0
+        for st in plan:
+            if st[0] == "up":
+                w, b = folded[k]
+                _B, hh, ww, c = h.shape
+                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), w, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, w.shape[1])
+                k += 1
+            elif st[0] == "sub":
+                h = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, "leaky001")
+                k += 1
+            else:
+                y = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_K3, "leaky02")
+                h = ops.conv_s1(y, mats[k + 1], folded[k + 1][1], ops.CONV_S1_K3, None, resid=h)
+                k += 2
+            if collect is not None:
+                collect["stages"].append(h)
+        return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias)
+
+    def reparameterize(self, mu, log_var):
+        """vit_backbone.py:181-184: mu + randn_like(std) * std on torch's generator."""
+        std = torch.exp(0.5 * log_var)
+        return mu + torch.randn_like(std) * std
+
+    @torch.no_grad()
+    def forward(self, x):
+        """(recons, x, mu, log_var) as ViTVAE.forward (vit_backbone.py:195-199), eval mode."""
+        mu, log_var = self.encode(x)
+        return self.decode(self.reparameterize(mu, log_var)), x, mu, log_var
+
+    @torch.no_grad()
+    def reconstruct(self, x):
+        """decode(mu(x)): the deterministic reconstruction."""
+        return self.decode(self.encode(x)[0])
+
+
 def resize_pos_embedding(pos, src_grid, dst_grid):
     """A position embedding [1, 1 + hs * ws, D] for another patch grid: the CLS row is kept, the grid rows are laid out as a [D, hs, ws] image and
     resized bicubically (align_corners=False) to dst_grid — what the reference's latent_translator does when it loads a 768 x 1280 checkpoint into
@@ -168,11 +285,13 @@ def _source_grid(n, dst_grid):
 
 
 def load_vitvae_state_dict(model, state_dict, src_grid=None):
-    """Load a full reference ViTVAE checkpoint into the encoder.  Decoder keys (decoder_input.*, decoder.*) are dropped and returned as a sorted
-    list; a pos_embedding of another patch grid is resized (resize_pos_embedding; src_grid = the checkpoint's (h, w) grid when it does not share
-    the model's aspect ratio); every other missing, unexpected or mis-shaped key is an error."""
+    """Load a full reference ViTVAE checkpoint.  Into a ViTVAE every key is loaded and the returned list is empty; into a ViTVAEEncoder the decoder keys
+    (decoder_input.*, decoder.*) are dropped and returned as a sorted list.  A pos_embedding of another patch grid is resized (resize_pos_embedding;
+    src_grid = the checkpoint's (h, w) grid when it does not share the model's aspect ratio; decoder_input then has another shape, so this serves the
+    encoder only); every other missing, unexpected or mis-shaped key is an error."""
     own = model.state_dict()
-    dropped = sorted(k for k in state_dict if k.startswith(("decoder_input.", "decoder.")))
+    owns_decoder = any(k.startswith(("decoder_input.", "decoder.")) for k in own)
+    dropped = [] if owns_decoder else sorted(k for k in state_dict if k.startswith(("decoder_input.", "decoder.")))
     sd = {k: v for k, v in state_dict.items() if k not in set(dropped)}
     unexpected, missing = sorted(set(sd) - set(own)), sorted(set(own) - set(sd))
     if unexpected or missing:

@@ -239,6 +239,19 @@ int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gam
 #define CVAE_FOLD_CONV_K4   0
 #define CVAE_FOLD_UPCONV_K3 1
 #define CVAE_FOLD_CONV_K3S2 3   /* 2 stays unassigned */
+/* The ViT-VAE decoder's kinds (dims rows stay {Cout, Cin} with Cout the BatchNorm's channel count; outputs fp32):
+ *   kind CVAE_FOLD_CONVT_K3S2:          w = nn.ConvTranspose2d(k3, s2, p1, output_padding 1) weight [Cin][Cout][3][3], w_out the transposed k4/s2/p1 weight
+ *                                       [Cin][Cout][4][4] of cvae_conv_up with w_out[..][kh][kw] = w[..][kh][kw] s[cout] for kh, kw < 3 and a zero fourth row and
+ *                                       column: both scatter in[i] to out[2 i - 1 + k], and the k4 extent 2 n is the k3 extent with output_padding 1;
+ *   kind CVAE_FOLD_CONV_K3S1:           w = nn.Conv2d(k3, s1, p1) weight [Cout][Cin][3][3], w_out the GEMM matrix [Cout][KT] of cvae_conv_s1 (form
+ *                                       CVAE_CONV_S1_K3): w_out[co][(ky 3 + kx) Cin + ci] = w[co][ci][ky][kx] s[co], KT = 9 Cin rounded up to 64, zero columns behind;
+ *   kind CVAE_FOLD_CONVT_K3S2_SUBPIXEL: w as CVAE_FOLD_CONVT_K3S2, w_out the GEMM matrix [4 Cout][KT] of cvae_conv_s1 (form CVAE_CONV_S1_SUBPIXEL): row
+ *                                       (py 2 + px) Cout + co, column (dy 2 + dx) Cin + ci holds w[ci][co][ky][kx] s[co] with, per direction, parity 0: {d 0 -> k 1},
+ *                                       parity 1: {d 0 -> k 2, d 1 -> k 0} and zero elsewhere; KT = 4 Cin rounded up to 64.
+ * The two GEMM kinds need Cin % 4 == 0 (else CVAE_E_UNSUPPORTED). */
+#define CVAE_FOLD_CONVT_K3S2          4
+#define CVAE_FOLD_CONV_K3S1           5
+#define CVAE_FOLD_CONVT_K3S2_SUBPIXEL 6
 int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
                       const float* const* beta, const float* const* mean, const float* const* var, const float* eps, float* const* w_out,
                       float* const* b_out, void* stream);
@@ -279,6 +292,34 @@ int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float
                     int64_t M, int64_t K, int64_t N, int epilogue, int dtype, void* stream);
 int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
                   int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream);
+
+/* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
+ * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
+ * (no atomics, no split-K): bit-reproducible, and a sample's bits do not depend on the batch it travels in.  Pointers 16-byte aligned, else CVAE_E_UNSUPPORTED;
+ * channel counts outside the lists are CVAE_E_UNSUPPORTED; B == 0 is CVAE_OK (nothing is launched).
+ *   cvae_conv_s1         y = act(conv(x, w) + bias + resid), everything after the products in fp32 before the one rounding to `dtype`.
+ *                        form CVAE_CONV_S1_K3:       nn.Conv2d(C, C, 3, 1, 1), Cin == Cout in {32, 64, 128}; x, y, resid [B][H][W][C];
+ *                        form CVAE_CONV_S1_SUBPIXEL: nn.ConvTranspose2d(Cin, 16, 3, 2, 1, output_padding 1), Cin in {32, 16}, as a 2 x 2 forward-window conv
+ *                                                    to 64 channels with a pixel-shuffle store; x [B][H][W][Cin], y and resid [B][2H][2W][16].
+ *                        w: the GEMM matrix in `dtype` (cvae_conv_s1_weight_elems elements; fp32: what cvae_fold_bn_conv's kinds CVAE_FOLD_CONV_K3S1 /
+ *                        CVAE_FOLD_CONVT_K3S2_SUBPIXEL write; bf16: that, through cvae_conv_s1_pack_weights); bias fp32 [Cout] (required); resid optional (NULL);
+ *                        act CVAE_ACT_NONE / RELU / LEAKY02 / LEAKY001.
+ *   cvae_conv_s1_weight_elems   elements of that matrix, 0 for an unsupported (Cin, Cout, form)
+ *   cvae_conv_s1_pack_weights   fp32 -> bf16 for `count` (1..16) matrices of n[i] elements (n[i] % 4 == 0) in ONE launch (host arrays of device pointers)
+ *   cvae_conv_s1_c1      nn.Conv2d(16, 1, 3, 1, 1): x [B][H][W][16] in `dtype`, w the fp32 weight [1][16][3][3] as it is (rounded to bf16 on its way into LDS
+ *                        in bf16 mode), bias fp32 [1] or NULL; y fp32 [B][1][H][W] = act(conv + bias).  Cin != 16: CVAE_E_UNSUPPORTED.
+ *   cvae_latent_to_grid  out[b][p][c] = sum_k W[c P + p][k] z[b][k] + bias[c P + p]: nn.Linear(K, C P) followed by view(B, C, gh, gw), written channels-last
+ *                        [B][P][C] in `dtype`.  z fp32 [B][K], W / bias the fp32 nn.Linear tensors, read once per launch with 16-byte loads and never cast;
+ *                        products and sums fp32.  B <= 16 per launch (the caller chunks larger batches), K <= 512 and K % 4 == 0, C % 32 == 0, else
+ *                        CVAE_E_UNSUPPORTED. */
+#define CVAE_CONV_S1_K3       0
+#define CVAE_CONV_S1_SUBPIXEL 1
+int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form);
+int cvae_conv_s1_pack_weights(int count, const float* const* w, void* const* packed, const int64_t* n, void* stream);
+int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                 int form, int dtype, int act, void* stream);
+int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act, void* stream);
+int cvae_latent_to_grid(const float* z, const float* W, const float* bias, void* out, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream);
 
 /* ---- The dense bottleneck of CausalBioVAE in 5 + 5 launches (batch M <= 16, fp32 arithmetic) --------------------------------
  * Replaces, between the last encoder conv and the first decoder conv (causal_cascade/models.py:57-79):

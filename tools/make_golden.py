@@ -9,7 +9,7 @@ What is imported from /root/reference (read-only, nothing is written there):
   * mnist_test/01_baseline_causal_vae/{config,models}.py -> CausalMorphVAE12, LatentDiscriminator (a8)
   * mnist_test/06_model_experiment/{config,models}.py    -> Gaussian-head CausalMorphVAE12
   * vessel_analysis/00_core/models.py: the text of ``CausalVesselVAE`` is compiled with its two unimportable imports dropped (a11)
-  * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode, encode only; `python tools/make_golden.py vitvae`)
+  * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode; encode: `python tools/make_golden.py vitvae`, decode: `... vitvae_dec`)
   * vessel_analysis/01_train/train.py: only the text of ``loss_function`` is compiled (the module
     itself cannot be imported: it pulls tifffile/torchvision through ``dataset``) (a10)
 The MNIST adversarial loop body (mnist_test/01_baseline_causal_vae/train.py:34-93) cannot be imported
@@ -358,8 +358,48 @@ def vitvae_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, full):
     print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
 
 
+def vitvae_dec_case(name, B, H, W, depth, seed_model, seed_bn, seed_dec_bn, seed_z, whole):
+    """ViTVAE.decode in eval mode at random init.  The weights are the seed's draws (digests only: the product class draws the same); the stem BatchNorms
+    are randomised as in vitvae_case, ALL decoder BatchNorm2d layers (the ones nested in the ResBlocks included) from a further seed
+    (tests/vit_decoder_reference.py:randomize_decoder_bn).  Stored: z, the activation after decoder_input (viewed NCHW) and after each of the 8 stages,
+    and the image — the names in `whole` as arrays, everything else (the state_dict included) as digests, so that a fixture stays below the largest
+    existing one."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_reference import randomize_stem_bn
+    from vit_decoder_reference import randomize_decoder_bn, dec_inputs, STAGES
+    (vb,) = import_from(os.path.join(REF, "vessel_analysis", "00_core"), "vit_backbone")
+    torch.manual_seed(seed_model)
+    model = vb.ViTVAE(in_channels=1, latent_dim=128, img_size=(H, W), depth=depth)
+    randomize_stem_bn(model.stem, seed_bn)
+    randomize_decoder_bn(model.decoder, seed_dec_bn)
+    model.eval()
+    z = dec_inputs(B, 128, seed_z)
+    acts = {}
+    hooks = [model.decoder_input.register_forward_hook(lambda _m, _i, o: acts.__setitem__("grid", o.detach().view(-1, 256, H // 32, W // 32).clone()))]
+    for i, (kind, idx) in enumerate(STAGES):
+        mod = model.decoder[idx + 2] if kind == "up" else model.decoder[idx]         # the LeakyReLU behind a transposed conv / the ResBlock
+        hooks.append(mod.register_forward_hook(lambda _m, _i, o, k=i: acts.__setitem__(f"stage{k}", o.detach().clone())))
+    with torch.no_grad():
+        acts["image"] = model.decode(z)
+    for h in hooks:
+        h.remove()
+    store = {"in/seed": np.array([B, H, W, depth, seed_model, seed_bn, seed_dec_bn, seed_z], dtype=np.int64)}
+    pack("sd0", model.state_dict(), store, full_limit=0)
+    pack("in", dict(z=z), store)
+    pack("out", {k: v for k, v in acts.items() if k not in whole}, store, full_limit=0)
+    pack("out", {k: v for k, v in acts.items() if k in whole}, store, full_limit=1 << 30)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    print(name, "image[0,0,0,:3]", acts["image"][0, 0, 0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "vitvae_dec":
+        # grid 2 x 3: the image and every stage but the last two whole (stage6 / stage7 are 0.3 / 1.2 MB as arrays: digests)
+        vitvae_dec_case("vitvae_dec_64x96", 3, 64, 96, 1, 42, 4242, 4343, 1311, whole={"grid", "image"} | {f"stage{i}" for i in range(6)})
+        vitvae_dec_case("vitvae_dec_256x320", 2, 256, 320, 1, 42, 4242, 4343, 1312, whole={"image"})       # grid 8 x 10: the image whole
+        vitvae_dec_case("vitvae_dec_768x1280", 1, 768, 1280, 1, 42, 4242, 4343, 1313, whole=set())         # digests only
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "vitvae":
         vitvae_case("vitvae_enc_256x320", 3, 256, 320, 2, 42, 4242, 1301, full=True)       # 81 tokens
         vitvae_case("vitvae_enc_768x1280", 2, 768, 1280, 6, 42, 4242, 1302, full=False)    # 961 tokens
