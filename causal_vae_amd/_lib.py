@@ -134,6 +134,7 @@ SIGNATURES = {
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],
     "cvae_conv_s1_c1": [_p] * 4 + [_i64] * 4 + [_i, _i, _p],
     "cvae_latent_to_grid": [_p] * 4 + [_i64] * 4 + [_i, _p],
+    "cvae_mlp_heads_fwd": [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
     "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
     "cvae_stack_mean_std": [_p, _i, _p, _p, _i64, _p],
@@ -177,6 +178,20 @@ class BottleneckSaved(C.Structure):
 class BottleneckNoise(C.Structure):
     """cvae_bottleneck_noise"""
     _fields_ = [("seed", _u64), ("subsequence", _u64), ("call_counter", _p)]
+
+
+HEADS_MAX_PANELS, HEADS_MAX_LAYERS, HEADS_MAX_WIDTH = 3, 3, 512      # CVAE_HEADS_MAX_*
+
+
+class HeadsPanel(C.Structure):
+    """cvae_heads_panel"""
+    _fields_ = [("ptr", _p), ("width", _i64), ("stride", _i64)]
+
+
+class HeadsLayer(C.Structure):
+    """cvae_heads_layer"""
+    _fields_ = [("W", _p), ("b", _p), ("W2", _p), ("b2", _p), ("out", _i64), ("out_first", _i64), ("bn_weight", _p), ("bn_bias", _p), ("bn_mean", _p),
+                ("bn_var", _p), ("bn_eps", _f), ("leaky", _i), ("slope", _f)]
 
 
 class KernelTimer:

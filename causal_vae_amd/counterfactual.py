@@ -33,7 +33,7 @@ def _decode_rows(model, z_rep, m_cf, size, fp8_plan, precision):
 @torch.no_grad()
 def batched_counterfactual(model, z, m, features, values, size=None, fp8_plan=None, precision=None, chunk_rows=None):
     """Decode every intervention do(m_f = v) in one call.  Works with CausalBioVAE / CausalBioVAE3D (decode(z, m, size)),
-    CausalMorphVAE12 (decode(m, z)) and CausalVesselVAE (decode(z, m), eval mode: the BatchNorm-folded decoder).  Returns [B, n_features, n_values, C, (D,) H, W].
+    CausalMorphVAE12 (decode(m, z)), CausalVesselVAE (decode(z, m), eval mode: the BatchNorm-folded decoder) and vit.CausalViTVAE (decode(z, m), eval mode).  Returns [B, n_features, n_values, C, (D,) H, W].
 
     chunk_rows — decode the stacked rows in slices of at most this many (None: all at once).  The 768 x 1280 vessel decoder holds a
     31 MB fp32 intermediate per row (384 x 640 x 32), so a sweep of hundreds of rows is decoded in slices into one output.
@@ -56,6 +56,8 @@ def batched_counterfactual(model, z, m, features, values, size=None, fp8_plan=No
         raise ValueError("precision 'fp8' needs fp8_plan = model.calibrate_fp8_decoder(...)")
     stacks = [s_ for s_ in (getattr(model, "enc_conv", None), getattr(model, "dec_conv", None)) if s_ is not None and hasattr(s_, "compute_dtype")]
     prev = [s_.compute_dtype for s_ in stacks]
+    if not stacks and hasattr(model, "compute_dtype"):        # a model that keeps one compute dtype of its own (vit.CausalViTVAE: its backbone's)
+        prev = [model.compute_dtype]
     want = {"fp32": torch.float32, "bf16": torch.bfloat16}.get(precision)
     try:
         if want is not None and hasattr(model, "set_compute_dtype") and any(p_ != want for p_ in prev):

@@ -2089,3 +2089,82 @@ def latent_to_grid(z, weight, bias, channels, out_dtype):
         nb = min(LATENT_TO_GRID_ROWS, B - b0)
         check(lib.cvae_latent_to_grid(ptr(z[b0:]), ptr(w), ptr(b), ptr(out[b0:]), nb, K, P, channels, L.dtype_code(out_dtype), stream()), "latent_to_grid")
     return out
+
+
+# ---- The dense heads of CausalViTVAE (csrc/heads.hip): a whole head in one launch ----------------------------------------------------
+def _heads_rows(t):
+    """t [B, w] as the heads kernel addresses it (ptr + row * stride + col): unit column stride and rows that do not overlap.  A column slice of a wider
+    matrix qualifies as it is; an expanded row (stride 0) or a transposed view is copied once."""
+    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def mlp_heads(panels, layers, split=None, clamp0=None, clamp1=None, eps=None):
+    """One fused head (cvae_mlp_heads_fwd), fp32, forward-only.
+    panels  1..3 fp32 [B, w_i] matrices; the head reads torch.cat(panels, 1) without building it.  A panel with unit column stride and a row stride of
+            at least its width (a column slice of a wider matrix) is read in place; any other view (an expanded row, a transpose) is copied first.
+    layers  1..3 entries (linear, bn, slope): linear = an nn.Linear, or — last layer only — a pair of nn.Linear holding the first and second
+            group of output columns (read from the two weight tensors, no stacked copy); bn = an nn.BatchNorm1d applied on its running
+            statistics, read on every call, or None; slope = the LeakyReLU slope applied after it, or None.
+    split   output columns [0, split) form the first result, [split, N) the second (default: the first linear's width of a pair, else N: one result)
+    clamp0 / clamp1  (lo, hi) of torch.clamp for the two results, or None
+    eps     [B, split] fp32, read in place or copied by the same rule as a panel: also returns z = first + eps * exp(0.5 * second) from the clamped values (needs N == 2 split)
+    Returns (first, second or None, z or None)."""
+    import ctypes as C
+    if not 1 <= len(panels) <= L.HEADS_MAX_PANELS or not 1 <= len(layers) <= L.HEADS_MAX_LAYERS:
+        raise L.CvaeError(f"mlp_heads: 1..{L.HEADS_MAX_PANELS} input panels and 1..{L.HEADS_MAX_LAYERS} layers, got {len(panels)} and {len(layers)}: {L.strerror(-3)}")
+    if any(t.dim() != 2 for t in panels):
+        raise L.CvaeError(f"mlp_heads: every panel must be a [B, w] matrix, got shapes {[tuple(t.shape) for t in panels]}")
+    B = panels[0].shape[0]
+    for t in panels:
+        if t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] < 1:
+            raise L.CvaeError(f"mlp_heads: every panel must be float32 with {B} rows (the first panel's) and at least one column, got {tuple(t.shape)} {t.dtype}")
+    panels = [_heads_rows(t) for t in panels]
+    K = sum(t.shape[1] for t in panels)
+    keep, rows, width = [], (L.HeadsLayer * len(layers))(), K
+    for i, (lin, bn, slope) in enumerate(layers):
+        pair = lin if isinstance(lin, (tuple, list)) else (lin,)
+        if len(pair) > 2 or (len(pair) == 2 and i != len(layers) - 1):
+            raise L.CvaeError("mlp_heads: only the last layer may be held by two nn.Linear modules")
+        ts = [t.detach().contiguous() for p in pair for t in (p.weight, p.bias)]
+        L.require_gpu(*ts, *panels)
+        _forward_only("mlp_heads", *[t for p in pair for t in (p.weight, p.bias)], *panels)
+        if any(p.weight.dtype != torch.float32 or p.weight.dim() != 2 or p.weight.shape[1] != width or p.bias is None for p in pair):
+            raise L.CvaeError(f"mlp_heads: layer {i} must be fp32 nn.Linear({width}, n) with a bias, got weights {[tuple(p.weight.shape) for p in pair]}")
+        r = rows[i]
+        r.W, r.b, r.out_first = ts[0].data_ptr(), ts[1].data_ptr(), pair[0].weight.shape[0]
+        r.out = sum(p.weight.shape[0] for p in pair)
+        if len(pair) == 2:
+            r.W2, r.b2 = ts[2].data_ptr(), ts[3].data_ptr()
+        if bn is not None:
+            if bn.running_var is None or bn.weight is None or bn.num_features != r.out:
+                raise L.CvaeError(f"mlp_heads: layer {i}'s BatchNorm1d needs running statistics, an affine weight and {r.out} features")
+            bts = [t.detach().float().contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+            L.require_gpu(*bts)
+            r.bn_weight, r.bn_bias, r.bn_mean, r.bn_var = (t.data_ptr() for t in bts)
+            r.bn_eps = float(bn.eps)
+            ts += bts
+        if slope is not None:
+            r.leaky, r.slope = 1, float(slope)
+        keep.append(ts)
+        width = r.out
+    if K > L.HEADS_MAX_WIDTH or any(r.out > L.HEADS_MAX_WIDTH for r in rows):
+        raise L.CvaeError(f"mlp_heads: input width {K} / layer widths {[r.out for r in rows]} above {L.HEADS_MAX_WIDTH}: {L.strerror(-3)}")
+    N = width
+    if split is None:
+        split = rows[len(layers) - 1].out_first
+    if not 1 <= split <= N:
+        raise L.CvaeError(f"mlp_heads: split {split} outside 1..{N}")
+    first = _empty((B, split), torch.float32, panels[0])
+    second = _empty((B, N - split), torch.float32, panels[0]) if split < N else None
+    z = None
+    if eps is not None:
+        L.require_gpu(eps)
+        if N != 2 * split or eps.dtype != torch.float32 or tuple(eps.shape) != (B, split):
+            raise L.CvaeError(f"mlp_heads: eps must be fp32 [{B}, {split}] and the head's width 2 * split, got {tuple(eps.shape)} {eps.dtype}, width {N}")
+        eps = _heads_rows(eps)
+        z = _empty((B, split), torch.float32, panels[0])
+    pan = (L.HeadsPanel * len(panels))(*[L.HeadsPanel(t.data_ptr(), t.shape[1], max(t.stride(0), t.shape[1])) for t in panels])
+    cl = lambda c: None if c is None else (C.c_float * 2)(float(c[0]), float(c[1]))
+    check(lib.cvae_mlp_heads_fwd(pan, len(panels), rows, len(layers), split, cl(clamp0), cl(clamp1), ptr(eps), max(eps.stride(0), split) if eps is not None else 0,
+                                 ptr(first), split, ptr(second), N - split, ptr(z), split, B, stream()), "mlp_heads")
+    return first, second, z

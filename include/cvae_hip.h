@@ -321,6 +321,35 @@ int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* re
 int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act, void* stream);
 int cvae_latent_to_grid(const float* z, const float* W, const float* bias, void* out, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream);
 
+/* ---- The dense heads of CausalViTVAE, eval mode (csrc/heads.hip; vessel_analysis/00_core/models.py:225-250, 281-302) ------------------------------------------
+ * One launch = one whole head: the logical concatenation of n_panels (1..3) fp32 row panels {ptr, width, row stride in elements} (torch.cat(dim=1), never
+ * materialised) through n_layers (1..3) fp32 nn.Linear layers (W [out][in], b [out] as they are; hidden rows stay in LDS), then per layer and in this order:
+ *   eval-mode BatchNorm1d  when bn_var != NULL: y = (v - bn_mean) * (bn_weight / sqrt(bn_var + bn_eps)) + bn_bias, computed from the LIVE tensors on every
+ *                          call (nothing is cached across calls: parameters may be rewritten through raw pointers);
+ *   LeakyReLU(slope)       when leaky != 0.
+ * The LAST layer may be held by two weight tensors: rows 0 .. out_first - 1 in (W, b), rows out_first .. out - 1 in (W2 [out - out_first][in], b2)
+ * (morph_predictor_mu / morph_predictor_logvar: no stacked copy); other layers have out_first == out.  Epilogue: output columns 0 .. split - 1 go to out0
+ * [B][split], columns split .. out - 1 to out1 [B][out - split] (split == out: out1 unused); clamp0 / clamp1: NULL, or HOST {lo, hi} of torch.clamp for that
+ * panel; z (optional, needs out == 2 split and eps [B][split]): z = out0 + eps * exp(0.5 * out1) from the clamped values.  All strides in elements.
+ * fp32 throughout; every output value is one fmaf chain over the inputs in index order (no atomics, no split sums): a row's bits do not depend on B nor on the
+ * row's position in the batch.  Limits: the concatenated input width and every layer's `out` at most CVAE_HEADS_MAX_WIDTH, else CVAE_E_UNSUPPORTED (the heads
+ * served: 287 -> 512 -> 256, 140 -> 256 -> 512, 19 -> 64 -> 64 -> 12 + 12).  B == 0 is CVAE_OK (nothing is launched). */
+#define CVAE_HEADS_MAX_PANELS 3
+#define CVAE_HEADS_MAX_LAYERS 3
+#define CVAE_HEADS_MAX_WIDTH  512
+typedef struct { const float* ptr; int64_t width, stride; } cvae_heads_panel;
+typedef struct {
+    const float *W, *b, *W2, *b2;
+    int64_t out, out_first;
+    const float *bn_weight, *bn_bias, *bn_mean, *bn_var;
+    float bn_eps;
+    int leaky;
+    float slope;
+} cvae_heads_layer;
+int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t split,
+                       const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0, int64_t out0_stride,
+                       float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* stream);
+
 /* ---- The dense bottleneck of CausalBioVAE in 5 + 5 launches (batch M <= 16, fp32 arithmetic) --------------------------------
  * Replaces, between the last encoder conv and the first decoder conv (causal_cascade/models.py:57-79):
  *   AdaptiveAvgPool + Flatten, cat([x_feat, m, t]), enc_fc (Linear-ReLU-Linear-ReLU), fc_mu, fc_logvar, reparameterize,

@@ -10,6 +10,7 @@ What is imported from /root/reference (read-only, nothing is written there):
   * mnist_test/06_model_experiment/{config,models}.py    -> Gaussian-head CausalMorphVAE12
   * vessel_analysis/00_core/models.py: the text of ``CausalVesselVAE`` is compiled with its two unimportable imports dropped (a11)
   * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode; encode: `python tools/make_golden.py vitvae`, decode: `... vitvae_dec`)
+  * vessel_analysis/00_core/models.py: the text of ``CausalViTVAE`` is compiled around that ViTVAE (eval mode; `... causal_vitvae`)
   * vessel_analysis/01_train/train.py: only the text of ``loss_function`` is compiled (the module
     itself cannot be imported: it pulls tifffile/torchvision through ``dataset``) (a10)
 The MNIST adversarial loop body (mnist_test/01_baseline_causal_vae/train.py:34-93) cannot be imported
@@ -392,6 +393,57 @@ def vitvae_dec_case(name, B, H, W, depth, seed_model, seed_bn, seed_dec_bn, seed
     print(name, "image[0,0,0,:3]", acts["image"][0, 0, 0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
 
 
+def causal_vitvae_case(name, B, H, W, seed_model, seed_bn, seed_dec_bn, seed_head_bn, seed_data, crop):
+    """CausalViTVAE (vessel_analysis/00_core/models.py:181-307) in eval mode at random init.  The class text (from `class CausalViTVAE` on) is compiled
+    with CONFIG and the reference's own ViTVAE injected, as vessel2d_case does for the older model (the module's torchvision / bare `config` imports are
+    never executed).  Weights are the seed's draws (digests and the key list only: the product class draws the same); every BatchNorm gets non-trivial
+    statistics from recorded seeds — stem and decoder BatchNorm2d as in the ViTVAE cases, the adapters' BatchNorm1d by
+    tests/causal_vit_reference.py:randomize_head_bn; eps is injected.  Stored whole: m, t, eps, x as packed bits, cls_out, mu, logvar, z, z_vit, m_mu,
+    m_logvar and the crop [y0:y1, x0:x1] of recon_x; recon_x itself as a digest."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_reference import randomize_stem_bn
+    from vit_decoder_reference import randomize_decoder_bn
+    from causal_vit_reference import randomize_head_bn, causal_inputs
+    sys.modules.setdefault("torchvision", types.ModuleType("torchvision"))
+    (vb,) = import_from(os.path.join(REF, "vessel_analysis", "00_core"), "vit_backbone")
+    src = open(os.path.join(REF, "vessel_analysis", "00_core", "models.py")).read()
+    ns = {"torch": torch, "nn": torch.nn, "F": F, "ViTVAE": vb.ViTVAE,
+          "CONFIG": {"M_DIM": 12, "T_DIM": 19, "Z_DIM": 128, "IMG_HEIGHT": H, "IMG_WIDTH": W, "DEVICE": "cpu"}}
+    exec(compile(src[src.index("class CausalViTVAE"):], "<reference vessel models.py: CausalViTVAE>", "exec"), ns)
+    torch.manual_seed(seed_model)
+    model = ns["CausalViTVAE"]()
+    randomize_stem_bn(model.backbone.stem, seed_bn)
+    randomize_decoder_bn(model.backbone.decoder, seed_dec_bn)
+    randomize_head_bn(model, seed_head_bn)
+    model.eval()
+    x, m, t, eps = causal_inputs(B, H, W, seed_data)
+    acts = {}
+
+    def reparam(mu, logvar):                                    # :252-255 with the draw injected
+        acts["z"] = mu + eps * torch.exp(0.5 * logvar)
+        return acts["z"]
+    model.reparameterize = reparam
+    hooks = [model.backbone.to_latent.register_forward_hook(lambda _m, _i, o: acts.__setitem__("cls_out", o.detach().clone())),
+             model.dec_adapter.register_forward_hook(lambda _m, _i, o: acts.__setitem__("z_vit", o.detach().clone()))]
+    with torch.no_grad():
+        recon_x, m_hat, mu, logvar, m_mu, m_logvar = model(x, m, t)
+    for h in hooks:
+        h.remove()
+    assert m_hat is m_mu
+    y0, y1, x0, x1 = crop
+    store = {"in/seed": np.array([B, H, W, seed_model, seed_bn, seed_dec_bn, seed_head_bn, seed_data], dtype=np.int64), "in/m": m.numpy(), "in/t": t.numpy(),
+             "in/eps": eps.numpy(), "in/x_bits": np.packbits(x.numpy().astype(np.uint8).reshape(-1)), "in/crop": np.array(crop, dtype=np.int64),
+             "sd0_keys": np.array(list(model.state_dict().keys()))}
+    pack("sd0", model.state_dict(), store, full_limit=0)
+    pack("in", dict(x=x), store, full_limit=0)
+    pack("out", dict(cls_out=acts["cls_out"], mu=mu, logvar=logvar, z=acts["z"], z_vit=acts["z_vit"], m_mu=m_mu, m_logvar=m_logvar,
+                     recon_crop=recon_x[:, :, y0:y1, x0:x1].contiguous()), store, full_limit=1 << 30)
+    pack("out", dict(recon_x=recon_x), store, full_limit=0)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    print(name, "mu[0,:3]", mu[0, :3].tolist(), "recon[0,0,0,:3]", recon_x[0, 0, 0, :3].tolist(), "keys", len(store), "bytes",
+          os.path.getsize(os.path.join(OUT, name + ".npz")))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if len(sys.argv) > 1 and sys.argv[1] == "vitvae_dec":
@@ -399,6 +451,9 @@ def main():
         vitvae_dec_case("vitvae_dec_64x96", 3, 64, 96, 1, 42, 4242, 4343, 1311, whole={"grid", "image"} | {f"stage{i}" for i in range(6)})
         vitvae_dec_case("vitvae_dec_256x320", 2, 256, 320, 1, 42, 4242, 4343, 1312, whole={"image"})       # grid 8 x 10: the image whole
         vitvae_dec_case("vitvae_dec_768x1280", 1, 768, 1280, 1, 42, 4242, 4343, 1313, whole=set())         # digests only
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "causal_vitvae":
+        causal_vitvae_case("causal_vitvae_768x1280", 2, 768, 1280, 42, 4242, 4343, 4444, 1321, crop=(352, 416, 608, 672))
         return
     if len(sys.argv) > 1 and sys.argv[1] == "vitvae":
         vitvae_case("vitvae_enc_256x320", 3, 256, 320, 2, 42, 4242, 1301, full=True)       # 81 tokens
