@@ -96,9 +96,6 @@ __device__ __forceinline__ void copy_rows_g2l(float* __restrict__ ws, const floa
     }
 }
 
-__device__ __forceinline__ int pool_lo(int o, int in, int out) { return (o * in) / out; }
-__device__ __forceinline__ int pool_hi(int o, int in, int out) { return ((o + 1) * in + out - 1) / out; }
-
 // ------------------------------------------------------------------------------------------------ pool_cat_fwd
 // grid (S + 1, M): block (s, b) averages window s of sample b for all C channels (coalesced along c) and writes
 // xcat[b][c * S + s]; block (S, b) copies m and t behind the features.  Block (S, 0) can also draw the step's reparameterisation noise

@@ -66,6 +66,55 @@ template <> __device__ __forceinline__ fp8 from_f32<fp8>(float x) {             
     x = fminf(fmaxf(x, -CVAE_FP8_MAX), CVAE_FP8_MAX);
     return fp8{(unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff)};
 }
+// N consecutive fp32 / bf16 elements <-> N floats, moved in 16-byte pieces (one 8-byte piece for four bf16); p is aligned to the piece
+template <int N> __device__ __forceinline__ void load_f32(const float* p, float (&v)[N]) {
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) {
+        const float4 f = ((const float4*)p)[q];
+        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
+    }
+}
+template <int N> __device__ __forceinline__ void load_f32(const bf16* p, float (&v)[N]) {
+    typedef bf16 vec __attribute__((ext_vector_type(N), aligned(N < 8 ? 8 : 16)));
+    const vec q = *(const vec*)p;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = (float)q[i];
+}
+template <int N> __device__ __forceinline__ void store_from_f32(float* p, const float (&v)[N]) {
+#pragma unroll
+    for (int q = 0; q < N / 4; ++q) ((float4*)p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+template <int N> __device__ __forceinline__ void store_from_f32(bf16* p, const float (&v)[N]) {
+    typedef uint32_t vec __attribute__((ext_vector_type(N / 2), aligned(N < 8 ? 8 : 16)));
+    vec q;
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) q[i] = pack2_bf16(v[2 * i], v[2 * i + 1]);
+    *(vec*)p = q;
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// Block-wide sum; result valid in thread 0. `red` must hold blockDim.x/64 floats.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    float r = 0.f;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < nw; ++i) r += red[i];
+    return r;
+}
 
 // 8 floats -> 8 fp8 (e4m3) codes of v * mul, saturating at +-448 (v_cvt_pk_fp8_f32 alone would produce NaN past the range)
 __device__ __forceinline__ uint2 pack8_fp8(const float (&v)[8], float mul) {
@@ -118,7 +167,7 @@ __device__ __forceinline__ unsigned mask_byte_of(const float (&v)[8]) {
 // its 23 us: same-address atomics serialise at the memory side at ~100 ns each.)  Every thread of the workgroup must call this.
 __device__ __forceinline__ void amax_publish_wg(unsigned* slots, float amx, unsigned wg, float* red) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
+    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));       // not wave_max(): the call form reorders two instructions in every conv epilogue
     const int nw = (blockDim.x + 63) >> 6;
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amx;
     __syncthreads();
@@ -172,25 +221,6 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Block-wide sum; result valid in thread 0. `red` must hold blockDim.x/64 floats.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    float r = 0.f;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < nw; ++i) r += red[i];
-    return r;
-}
-
 // 8 fp8 (e4m3) codes -> 8 bf16 (exact: every e4m3 value is a bf16 value)
 __device__ __forceinline__ uint4 fp8x8_to_bf16x8(uint2 c) {
     const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, true);
@@ -216,4 +246,41 @@ __device__ __forceinline__ void philox_normal4(uint64_t ctr, uint64_t subseq, ui
     sincosf(6.283185307179586f * u1, &v[1], &v[0]);
     sincosf(6.283185307179586f * u3, &v[3], &v[2]);
     v[0] *= r0; v[1] *= r0; v[2] *= r1; v[3] *= r1;
+}
+
+// Adaptive average pooling (torch): output index o of `out` averages inputs [pool_lo, pool_hi) of `in`
+template <typename I> __device__ __forceinline__ I pool_lo(I o, I in, I out) { return (o * in) / out; }
+template <typename I> __device__ __forceinline__ I pool_hi(I o, I in, I out) { return ((o + 1) * in + out - 1) / out; }
+
+// torch upsample_{bi,tri}linear, align_corners=False: src = scale * (dst + 0.5) - 0.5 clamped at 0, scale = in / out (float).  I = the index width of the
+// calling kernel (int or int64_t); the weights do not depend on it.
+template <typename I> struct LinTap { I i0, i1; float w0, w1; };
+template <typename I> __device__ __forceinline__ LinTap<I> lin_tap(I o, I in, float scale) {
+    float s = scale * ((float)o + 0.5f) - 0.5f;
+    if (s < 0.f) s = 0.f;
+    LinTap<I> t;
+    t.i0 = (I)s;
+    if (t.i0 > in - 1) t.i0 = in - 1;
+    t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
+    t.w1 = s - (float)t.i0;
+    t.w0 = 1.f - t.w1;
+    return t;
+}
+// weights with which outputs j0 .. j0 + 3 (j0 = 2 i - 1) of a 2x-resized axis read source index i; an unstrided axis (2D depth) reads itself
+struct Win4 { int j0; float w[4]; };
+template <typename I> __device__ __forceinline__ Win4 win4(int i, int in, int out, float scale, bool strided) {
+    Win4 r;
+    if (!strided) { r.j0 = i; r.w[0] = 1.f; r.w[1] = r.w[2] = r.w[3] = 0.f; return r; }
+    r.j0 = 2 * i - 1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = r.j0 + c;
+        float wv = 0.f;
+        if (j >= 0 && j < out) {
+            const LinTap<I> t = lin_tap<I>(j, in, scale);
+            wv = (t.i0 == i ? t.w0 : 0.f) + (t.i1 == i ? t.w1 : 0.f);
+        }
+        r.w[c] = wv;
+    }
+    return r;
 }

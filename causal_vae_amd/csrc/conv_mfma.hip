@@ -1263,7 +1263,7 @@ __global__ __launch_bounds__(1024) void fp8_scale_update_kernel(unsigned* __rest
     a4[t] = make_uint4(0u, 0u, 0u, 0u);
     float a = fmaxf(fmaxf(__uint_as_float(v.x), __uint_as_float(v.y)), fmaxf(__uint_as_float(v.z), __uint_as_float(v.w)));
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));         // not wave_max(): see amax_publish_wg (common.h)
     if (lane == 0) red[wave] = a;
     __syncthreads();
     if (t == 0) {

@@ -21,35 +21,7 @@
 
 namespace {
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));          // a 16-byte piece that stays in registers when held in an array
-
-__device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-}
-__device__ __forceinline__ void ld4(const bf16* p, float (&v)[4]) {
-    const bf16x4 q = *(const bf16x4*)p;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)q[i];
-}
-
-// 16 consecutive channels in 16-byte loads: four float4 / two bf16x8
-__device__ __forceinline__ void ld16(const float* p, float (&v)[16]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 f = ((const float4*)p)[q];
-        v[4 * q] = f.x; v[4 * q + 1] = f.y; v[4 * q + 2] = f.z; v[4 * q + 3] = f.w;
-    }
-}
-__device__ __forceinline__ void ld16(const bf16* p, float (&v)[16]) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const bf16x8 f = ((const bf16x8*)p)[q];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[8 * q + e] = (float)f[e];
-    }
-}
 
 // f(Int<0>{}) .. f(Int<N - 1>{}): a loop whose index is a compile-time constant in every iteration (register arrays stay in registers)
 template <int N, typename Fn> __device__ __forceinline__ void static_for(Fn&& f) {
@@ -143,9 +115,9 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
                 const int dy = tap / G::WIN, dx = tap - dy * G::WIN;
                 const int pos = tap < G::TAPS ? (ly + dy) * G::HC + lx + dx : G::HR * G::HC;
                 float bv[4], av[NT][4];
-                ld4(hs + pos * G::PITCH + ci, bv);
+                load_f32(hs + pos * G::PITCH + ci, bv);
 #pragma unroll
-                for (int j = 0; j < NT; ++j) ld4(ws + (j * 32 + r) * G::WPITCH + 16 * h + 4 * c, av[j]);
+                for (int j = 0; j < NT; ++j) load_f32(ws + (j * 32 + r) * G::WPITCH + 16 * h + 4 * c, av[j]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -170,12 +142,12 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
             for (int q = 0; q < 2; ++q) {
                 const int g = 2 * gp + q, n = j * 32 + 8 * g + 4 * h;
                 float bv[4];
-                ld4(bias + (n % COUT), bv);
+                load_f32(bias + (n % COUT), bv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[q][e] = acc[j][4 * g + e] + bv[e];
                 if (resid && live) {
                     float rv[4];
-                    ld4(resid + out_index(n), rv);
+                    load_f32(resid + out_index(n), rv);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[q][e] += rv[e];
                 }
@@ -260,7 +232,7 @@ __global__ __launch_bounds__(256) void conv_s1_c1_kernel(const T* __restrict__ x
             const int gx = xs - 1 + cx;
             if (gx < 0 || gx >= W) continue;
             float v[C1_CIN];
-            ld16(row + (int64_t)gx * C1_CIN, v);
+            load_f32(row + (int64_t)gx * C1_CIN, v);
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 const int dx = cx - o;

@@ -372,9 +372,6 @@ extern "C" int cvae_channel_sum(const void* x, float* out, int64_t P, int64_t C,
 }
 
 // ------------------------------------------------------------------------------------- adaptive avg pool
-__device__ __forceinline__ int64_t pool_start(int64_t o, int64_t I, int64_t O) { return (o * I) / O; }
-__device__ __forceinline__ int64_t pool_end(int64_t o, int64_t I, int64_t O) { return ((o + 1) * I + O - 1) / O; }
-
 template <typename T>
 __global__ void avgpool_fwd_kernel(const T* __restrict__ x, float* __restrict__ out, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
                                    int64_t OD, int64_t OH, int64_t OW, int64_t out_stride) {
@@ -382,9 +379,9 @@ __global__ void avgpool_fwd_kernel(const T* __restrict__ x, float* __restrict__ 
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t c = i % C, o = (i / C) % OV, b = i / (C * OV);
         const int64_t ow = o % OW, oh = (o / OW) % OH, od = o / (OW * OH);
-        const int64_t d0 = pool_start(od, D, OD), d1 = pool_end(od, D, OD);
-        const int64_t h0 = pool_start(oh, H, OH), h1 = pool_end(oh, H, OH);
-        const int64_t w0 = pool_start(ow, W, OW), w1 = pool_end(ow, W, OW);
+        const int64_t d0 = pool_lo(od, D, OD), d1 = pool_hi(od, D, OD);
+        const int64_t h0 = pool_lo(oh, H, OH), h1 = pool_hi(oh, H, OH);
+        const int64_t w0 = pool_lo(ow, W, OW), w1 = pool_hi(ow, W, OW);
         float acc = 0.f;
         for (int64_t d = d0; d < d1; ++d)
             for (int64_t h = h0; h < h1; ++h)
@@ -475,13 +472,13 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dout, const T* __re
         if (!mask || to_f32(mask[i]) > 0.f) {
             const int64_t odc = (d * OD) / D, ohc = (h * OH) / H, owc = (w * OW) / W;
             for (int64_t od = max(odc - 1, (int64_t)0); od <= min(odc + 1, OD - 1); ++od) {
-                const int64_t d0 = pool_start(od, D, OD), d1 = pool_end(od, D, OD);
+                const int64_t d0 = pool_lo(od, D, OD), d1 = pool_hi(od, D, OD);
                 if (d < d0 || d >= d1) continue;
                 for (int64_t oh = max(ohc - 1, (int64_t)0); oh <= min(ohc + 1, OH - 1); ++oh) {
-                    const int64_t h0 = pool_start(oh, H, OH), h1 = pool_end(oh, H, OH);
+                    const int64_t h0 = pool_lo(oh, H, OH), h1 = pool_hi(oh, H, OH);
                     if (h < h0 || h >= h1) continue;
                     for (int64_t ow = max(owc - 1, (int64_t)0); ow <= min(owc + 1, OW - 1); ++ow) {
-                        const int64_t w0 = pool_start(ow, W, OW), w1 = pool_end(ow, W, OW);
+                        const int64_t w0 = pool_lo(ow, W, OW), w1 = pool_hi(ow, W, OW);
                         if (w < w0 || w >= w1) continue;
                         acc += dout[b * dstride + c * OV + (od * OH + oh) * OW + ow] / (float)((d1 - d0) * (h1 - h0) * (w1 - w0));
                     }
@@ -515,19 +512,6 @@ extern "C" int cvae_adaptive_avgpool_bwd(const float* dout, const void* mask, vo
 
 // ------------------------------------------------------------------------------------- linear resize
 // torch upsample_{bi,tri}linear, align_corners=False: src = scale*(dst+0.5)-0.5 clamped at 0, scale = in/out (float).
-struct LinTap { int64_t i0, i1; float w0, w1; };
-__device__ __forceinline__ LinTap lin_tap(int64_t o, int64_t in, float scale) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    LinTap t;
-    t.i0 = (int64_t)s;
-    if (t.i0 > in - 1) t.i0 = in - 1;
-    t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
-    t.w1 = s - (float)t.i0;
-    t.w0 = 1.f - t.w1;
-    return t;
-}
-
 template <typename T>
 __global__ void upsample_fwd_kernel(const T* __restrict__ src, float* __restrict__ dst, int64_t B, int64_t d, int64_t h, int64_t w,
                                     int64_t D, int64_t H, int64_t W, int64_t C) {
@@ -540,7 +524,7 @@ __global__ void upsample_fwd_kernel(const T* __restrict__ src, float* __restrict
         const int64_t oh = r % H; r /= H;
         const int64_t od = r % D;
         const int64_t b = r / D;
-        const LinTap td = lin_tap(od, d, sd), th = lin_tap(oh, h, sh), tw = lin_tap(ow, w, sw);
+        const LinTap<int64_t> td = lin_tap(od, d, sd), th = lin_tap(oh, h, sh), tw = lin_tap(ow, w, sw);
         auto at = [&](int64_t z, int64_t y, int64_t x) { return to_f32(src[(((b * d + z) * h + y) * w + x) * C + c]); };
         // same association as aten's CPU kernel: depth, then height, then width taps
         float v = td.w0 * (th.w0 * (tw.w0 * at(td.i0, th.i0, tw.i0) + tw.w1 * at(td.i0, th.i0, tw.i1)) +
@@ -564,7 +548,7 @@ __global__ void upsample2x_fwd_kernel(const T* __restrict__ src, float* __restri
         const int oh = r % H; r /= H;
         const int od = r % D;
         const int b = r / D;
-        const LinTap td = lin_tap(od, d, sd), th = lin_tap(oh, h, sh);
+        const LinTap<int64_t> td = lin_tap<int64_t>(od, d, sd), th = lin_tap<int64_t>(oh, h, sh);
         const T* p00 = src + ((size_t)(b * d + (int)td.i0) * h + (int)th.i0) * w;
         const T* p01 = src + ((size_t)(b * d + (int)td.i0) * h + (int)th.i1) * w;
         const T* p10 = src + ((size_t)(b * d + (int)td.i1) * h + (int)th.i0) * w;
@@ -572,7 +556,7 @@ __global__ void upsample2x_fwd_kernel(const T* __restrict__ src, float* __restri
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const LinTap tw = lin_tap(ow0 + j, w, sw);
+            const LinTap<int64_t> tw = lin_tap<int64_t>(ow0 + j, w, sw);
             const int x0 = (int)tw.i0, x1 = (int)tw.i1;
             o[j] = td.w0 * (th.w0 * (tw.w0 * to_f32(p00[x0]) + tw.w1 * to_f32(p00[x1])) + th.w1 * (tw.w0 * to_f32(p01[x0]) + tw.w1 * to_f32(p01[x1]))) +
                    td.w1 * (th.w0 * (tw.w0 * to_f32(p10[x0]) + tw.w1 * to_f32(p10[x1])) + th.w1 * (tw.w0 * to_f32(p11[x0]) + tw.w1 * to_f32(p11[x1])));
@@ -581,23 +565,6 @@ __global__ void upsample2x_fwd_kernel(const T* __restrict__ src, float* __restri
     }
 }
 
-struct Win4 { int j0; float w[4]; };
-__device__ __forceinline__ Win4 win4(int i, int in, int out, float scale, bool strided) {
-    Win4 r;
-    if (!strided) { r.j0 = i; r.w[0] = 1.f; r.w[1] = r.w[2] = r.w[3] = 0.f; return r; }     // unstrided dim (2D depth)
-    r.j0 = 2 * i - 1;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = r.j0 + c;
-        float wv = 0.f;
-        if (j >= 0 && j < out) {
-            const LinTap t = lin_tap(j, in, scale);
-            wv = (t.i0 == i ? t.w0 : 0.f) + (t.i1 == i ? t.w1 : 0.f);
-        }
-        r.w[c] = wv;
-    }
-    return r;
-}
 template <typename T>
 __global__ void upsample2x_bwd_kernel(const float* __restrict__ ddst, T* __restrict__ dsrc, int B, int d, int h, int w, int D, int H, int W) {
     const float sd = (float)d / (float)D, sh = (float)h / (float)H, sw = (float)w / (float)W;
@@ -608,7 +575,7 @@ __global__ void upsample2x_bwd_kernel(const float* __restrict__ ddst, T* __restr
         const int y = r % h; r /= h;
         const int z = r % d;
         const int b = r / d;
-        const Win4 wz = win4(z, d, D, sd, D != d), wy = win4(y, h, H, sh, true), wx = win4(x, w, W, sw, true);
+        const Win4 wz = win4<int64_t>(z, d, D, sd, D != d), wy = win4<int64_t>(y, h, H, sh, true), wx = win4<int64_t>(x, w, W, sw, true);
         // the 4 x 4 x 4 gradient values around this voxel are requested first, unconditionally, from clamped indices (a value whose weight is 0 — beyond the
         // volume, or the unstrided depth axis — is loaded and not used): with the loads behind the weight tests every one of them was a dependent round trip
         // (42 us for 33.5 MB at 4 x 128^3)
@@ -693,16 +660,16 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ ddst, T* __restric
         cand_range(x, W, sw, wlo, whi);
         float acc = 0.f;
         for (int64_t od = dlo; od <= dhi; ++od) {
-            const LinTap td = lin_tap(od, d, sd);
+            const LinTap<int64_t> td = lin_tap(od, d, sd);
             const float wd = (td.i0 == z ? td.w0 : 0.f) + (td.i1 == z ? td.w1 : 0.f);
             if (wd == 0.f) continue;
             for (int64_t oh = hlo; oh <= hhi; ++oh) {
-                const LinTap th = lin_tap(oh, h, sh);
+                const LinTap<int64_t> th = lin_tap(oh, h, sh);
                 const float wh = (th.i0 == y ? th.w0 : 0.f) + (th.i1 == y ? th.w1 : 0.f);
                 if (wh == 0.f) continue;
                 float row = 0.f;
                 for (int64_t ow = wlo; ow <= whi; ++ow) {
-                    const LinTap tw = lin_tap(ow, w, sw);
+                    const LinTap<int64_t> tw = lin_tap(ow, w, sw);
                     const float ww = (tw.i0 == x ? tw.w0 : 0.f) + (tw.i1 == x ? tw.w1 : 0.f);
                     if (ww != 0.f) row += ww * ddst[(((b * D + od) * H + oh) * W + ow) * C + c];
                 }

@@ -401,9 +401,7 @@ __global__ void row_softmax_loss_kernel(const float* __restrict__ logits, const 
     const float g = (dlogits && gout) ? *gout : 1.f;
     for (int64_t b = row0; b < B; b += nrow) {
         const float v = (lane < C) ? logits[b * C + lane] : -INFINITY;
-        float mx = v;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        const float mx = wave_max(v);
         const float e = (lane < C) ? expf(v - mx) : 0.f;
         const float se = wave_sum(e);
         const float logp = v - mx - logf(se);             // log_softmax

@@ -12,44 +12,14 @@
 //                              backward used to re-read it, 33.5 MB, in a launch of its own)
 //   up2x_bwd_b_kernel          d src = 2 g U_d^T U_h^T t1          (ELBO backward; g = the incoming loss gradient, read on the device)
 // A thread owns 4 consecutive source voxels along w and their 2 x 2 x 8 block of outputs; the 3 x 3 x 6 source neighbourhood is
-// loaded once (1.7 loads per output instead of 8).  The tap weights are the values lin_tap() of the generic kernels produces and the
-// interpolation keeps aten's association (w, then h, then d), so MODE 0 returns the same numbers as cvae_upsample_linear_fwd.
+// loaded once (1.7 loads per output instead of 8).  The tap weights are the values of lin_tap() (common.h), the one function the generic kernels of
+// elementwise.hip call too, and the interpolation keeps aten's association (w, then h, then d), so MODE 0 returns the same numbers as
+// cvae_upsample_linear_fwd.
 #include "common.h"
 
 namespace {
 
-struct LinTap { int i0, i1; float w0, w1; };
-// torch upsample_linear, align_corners=False: src = scale * (dst + 0.5) - 0.5 clamped at 0, scale = in / out (float)
-__device__ __forceinline__ LinTap lin_tap(int o, int in, float scale) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    if (s < 0.f) s = 0.f;
-    LinTap t;
-    t.i0 = (int)s;
-    if (t.i0 > in - 1) t.i0 = in - 1;
-    t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
-    t.w1 = s - (float)t.i0;
-    t.w0 = 1.f - t.w1;
-    return t;
-}
-// weights with which outputs j0 .. j0 + 3 (j0 = 2 i - 1) of a 2x-resized axis read source index i
-struct Win4 { int j0; float w[4]; };
-__device__ __forceinline__ Win4 win4(int i, int in, int out, float scale, bool strided) {
-    Win4 r;
-    if (!strided) { r.j0 = i; r.w[0] = 1.f; r.w[1] = r.w[2] = r.w[3] = 0.f; return r; }
-    r.j0 = 2 * i - 1;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j = r.j0 + c;
-        float wv = 0.f;
-        if (j >= 0 && j < out) {
-            const LinTap t = lin_tap(j, in, scale);
-            wv = (t.i0 == i ? t.w0 : 0.f) + (t.i1 == i ? t.w1 : 0.f);
-        }
-        r.w[c] = wv;
-    }
-    return r;
-}
-
+// kept beside load_f32 (common.h): its bf16 body (shift and mask) and the cast of the shared 4-wide load each change the machine code of the other's kernels
 __device__ __forceinline__ void load4_f32(const float* p, float* o) { const float4 v = *(const float4*)p; o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 __device__ __forceinline__ void load4_f32(const bf16* p, float* o) {
     const uint2 v = *(const uint2*)p;
@@ -165,7 +135,7 @@ __global__ __launch_bounds__(256) void up2x_block_kernel(const T* __restrict__ s
         Win4 wx[4];
         if (MODE == 3) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) wx[q] = win4(x0 + q, w, W, sw, true);
+            for (int q = 0; q < 4; ++q) wx[q] = win4<int>(x0 + q, w, W, sw, true);
         }
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
@@ -376,7 +346,7 @@ __global__ __launch_bounds__(256) void up2x_bwd_b_kernel(const float* __restrict
     const int y = r % h; r /= h;
     const int z = r % d;
     const int b = r / d;
-    const Win4 wz = win4(z, d, D, sd, D != d), wy = win4(y, h, H, sh, true);
+    const Win4 wz = win4<int>(z, d, D, sd, D != d), wy = win4<int>(y, h, H, sh, true);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     // all 16 rows of t1 this voxel group reads are requested first, unconditionally, from clamped row indices (a row with weight 0 — beyond the volume, or
     // the unstrided depth axis — is loaded and not used): with the loads inside the weight tests every row was a dependent round trip of a one-round grid

@@ -325,7 +325,6 @@ void stack_launch(int count, const StackPtrs& P, float* mean, float* stdv, int64
     hipLaunchKernelGGL(stack_mean_std_kernel<K>, dim3(blocks), dim3(256), 0, st, P, mean, stdv, n, vec);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename T>
 int row_diff_t(const T* a, const T* b, const int64_t* ref, float* l2, float* mean_abs, int64_t rows, int64_t b_rows, int64_t n, float* ws, hipStream_t st) {

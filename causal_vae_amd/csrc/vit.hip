@@ -20,19 +20,6 @@ namespace {
 #define VIT_HD 32
 
 __device__ __forceinline__ int crow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ void load4(const float* p, float (&v)[4]) {
-    const float4 q = *(const float4*)p;
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-}
-__device__ __forceinline__ void load4(const bf16* p, float (&v)[4]) {
-    const bf16x4 q = *(const bf16x4*)p;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)q[i];
-}
-__device__ __forceinline__ void store4(float* p, const float (&v)[4]) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void store4(bf16* p, const float (&v)[4]) { *(uint2*)p = make_uint2(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])); }
 
 // ------------------------------------------------------------------------------------------------ token assembly
 // tokens[b][0] = cls + pos[0]; tokens[b][1 + i] = stem[b][i] + pos[1 + i]  (torch.cat((cls, x), 1) + pos_embedding, one fp32 add per element)
@@ -44,12 +31,12 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const T* __restrict__ s
         const int c4 = (int)(g & (VIT_DIM / 4 - 1));
         const int64_t row = g >> 6, b = row / (Np + 1), i = row - b * (Np + 1);
         float v[4], p[4];
-        load4(pos + i * VIT_DIM + c4 * 4, p);
-        if (i == 0) load4(cls + c4 * 4, v);
-        else load4(stem + (b * Np + i - 1) * VIT_DIM + c4 * 4, v);
+        load_f32(pos + i * VIT_DIM + c4 * 4, p);
+        if (i == 0) load_f32(cls + c4 * 4, v);
+        else load_f32(stem + (b * Np + i - 1) * VIT_DIM + c4 * 4, v);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += p[e];
-        store4(tokens + row * VIT_DIM + c4 * 4, v);
+        store_from_f32(tokens + row * VIT_DIM + c4 * 4, v);
     }
 }
 
@@ -62,9 +49,9 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* __restr
     const int64_t row = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     float v[4], g[4], b[4];
-    load4(x + row * ldx + lane * 4, v);
-    load4(gamma + lane * 4, g);
-    load4(beta + lane * 4, b);
+    load_f32(x + row * ldx + lane * 4, v);
+    load_f32(gamma + lane * 4, g);
+    load_f32(beta + lane * 4, b);
     const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.f / VIT_DIM);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] -= mean;
@@ -72,7 +59,7 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* __restr
     const float rstd = 1.f / sqrtf(var + eps);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = v[e] * rstd * g[e] + b[e];
-    store4(y + row * VIT_DIM + lane * 4, v);
+    store_from_f32(y + row * VIT_DIM + lane * 4, v);
 }
 
 // ------------------------------------------------------------------------------------------------ token GEMM
@@ -156,9 +143,9 @@ __global__ __launch_bounds__(256) void vit_gemm_kernel(const T* __restrict__ x, 
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float b[4], a[2][4];
-                load4(xs + (wave * 32 + r) * G::PITCH + 16 * h + 4 * c, b);
+                load_f32(xs + (wave * 32 + r) * G::PITCH + 16 * h + 4 * c, b);
 #pragma unroll
-                for (int j = 0; j < 2; ++j) load4(ws + (j * 32 + r) * G::PITCH + 16 * h + 4 * c, a[j]);
+                for (int j = 0; j < 2; ++j) load_f32(ws + (j * 32 + r) * G::PITCH + 16 * h + 4 * c, a[j]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -174,21 +161,21 @@ __global__ __launch_bounds__(256) void vit_gemm_kernel(const T* __restrict__ x, 
         for (int g = 0; g < 4; ++g) {
             const int n = n0 + j * 32 + 8 * g + 4 * h;
             float v[4], bv[4];
-            load4(bias + n, bv);
+            load_f32(bias + n, bv);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[j][4 * g + e] + bv[e];
             if (EPI == GEMM_EPI_RESID) {
                 float rv[4];
-                load4(resid + gm * ldr + n, rv);
+                load_f32(resid + gm * ldr + n, rv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e];
-                store4((float*)yv + gm * ldy + n, v);
+                store_from_f32((float*)yv + gm * ldy + n, v);
             } else {
                 if (EPI == GEMM_EPI_GELU) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
                 }
-                store4((T*)yv + gm * ldy + n, v);
+                store_from_f32((T*)yv + gm * ldy + n, v);
             }
         }
 }
@@ -316,7 +303,7 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const T* __restrict_
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     float a[4];
-                    load4((const float*)Ks + (sub * 32 + r) * G::KP + 16 * h + 4 * c, a);
+                    load_f32((const float*)Ks + (sub * 32 + r) * G::KP + 16 * h + 4 * c, a);
 #pragma unroll
                     for (int u = 0; u < 4; ++u) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], qs[4 * c + u], sc, 0, 0, 0);
                 }
@@ -368,7 +355,7 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const T* __restrict_
         float w[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[e] = o[4 * g + e] / l;
-        store4(op + 8 * g + 4 * h, w);
+        store_from_f32(op + 8 * g + 4 * h, w);
     }
 }
 
