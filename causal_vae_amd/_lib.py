@@ -134,6 +134,10 @@ SIGNATURES = {
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],
     "cvae_conv_s1_c1": [_p] * 4 + [_i64] * 4 + [_i, _i, _p],
     "cvae_latent_to_grid": [_p] * 4 + [_i64] * 4 + [_i, _p],
+    "cvae_conv_s1_bwd_data": [_p] * 5 + [_i64] * 4 + [_i, _i, _i, _p],
+    "cvae_conv_s1_c1_bwd_data": [_p] * 4 + [_i64] * 4 + [_i, _i, _p],
+    "cvae_latent_to_grid_bwd_workspace_bytes": [_i64] * 4,
+    "cvae_latent_to_grid_bwd": [_p] * 3 + [_i64] * 4 + [_i, _p, _sz, _p],
     "cvae_mlp_heads_fwd": [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
     "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
@@ -148,7 +152,7 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
-            "cvae_conv_s1_weight_elems": _i64}
+            "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

@@ -17,6 +17,15 @@
 //   * cvae_conv_s1_c1: Conv2d(16 -> 1, k3, s1, p1) to an fp32 [B][1][H][W] image: bandwidth-bound, one thread per four output pixels of a row, 16-byte loads.
 //   * cvae_latent_to_grid: out[b][p][c] = sum_k W[c P + p][k] z[b][k] + bias[c P + p]: nn.Linear(latent, C P) + view(B, C, gh, gw) written channels-last
 //     in the compute dtype.  W is the fp32 nn.Linear tensor, read ONCE per launch with 16-byte loads for up to 16 batch rows (z sits in LDS).
+// The input-gradient path of the same (frozen, eval-mode) decoder:
+//   * cvae_conv_s1_bwd_data: dx = (conv(g, w^T) + resid) * act'(gate) from the SAME kernel template (BWD = true: no bias, the gate in the epilogue):
+//       K3          the input gradient of Conv2d(C, C, 3, 1, 1) is a K3 conv with the taps flipped and the channels transposed: only the matrix differs;
+//       SUBPIXEL_T  the input gradient of ConvTranspose2d(Cin, 16, 3, 2, 1, output_padding 1), dx[y][x] = sum_k g[2y - 1 + ky][2x - 1 + kx] w[..][ky][kx]:
+//                   g [B][2H][2W][16] read space-to-depth as [B][H][W][64 = (py, px, co)] with a 2 x 2 BACKWARD window (positions y - 1, y: the zero row
+//                   and column sit at the top and left), K = 256 of which 9/16 are taps, N = 32 rows (Cin = 16: the upper 16 rows are zeros, not stored).
+//   * cvae_conv_s1_c1_bwd_data: the 1 -> 16 gradient of the output conv, one thread per pixel, gated by the conv's input, 16-byte stores.
+//   * cvae_latent_to_grid_bwd: dz[b][k] = sum_{p, c} g[b][p][c] W[c P + p][k]: W streamed once in slabs of 32 channels x 8 positions, per-slab partial
+//     sums in the caller's workspace, added in slab order by a second launch (no float atomics).
 #include "common.h"
 
 namespace {
@@ -32,13 +41,15 @@ template <int N, typename Fn> __device__ __forceinline__ void static_for(Fn&& f)
 }
 
 // ------------------------------------------------------------------------------------------------ stride-1 window conv on the MFMA
+// the factor a backward epilogue applies where the gate (the activation's output) is not positive: torch's rule x > 0 ? 1 : slope, once per launch
+__device__ __forceinline__ float gate_slope(int act) { return act == CVAE_ACT_LEAKY02 ? 0.2f : (act == CVAE_ACT_LEAKY001 ? 0.01f : (act == CVAE_ACT_RELU ? 0.f : 1.f)); }
 #define S1_TH 8
 #define S1_TW 16
 #define S1_KPAD 64                 // K is padded to a multiple of this many elements in the packed weight (both dtypes)
 
 template <typename T, int CIN, int FORM> struct S1Geom {
     static constexpr int WIN = FORM == CVAE_CONV_S1_K3 ? 3 : 2;
-    static constexpr int PADL = FORM == CVAE_CONV_S1_K3 ? 1 : 0;       // the window starts at output position - PADL
+    static constexpr int PADL = FORM == CVAE_CONV_S1_SUBPIXEL ? 0 : 1; // the window starts at output position - PADL
     static constexpr int TAPS = WIN * WIN;
     static constexpr int K = TAPS * CIN;
     static constexpr int KT = (K + S1_KPAD - 1) / S1_KPAD * S1_KPAD;
@@ -50,13 +61,14 @@ template <typename T, int CIN, int FORM> struct S1Geom {
     static constexpr int PPP = CIN / E16;                              // 16-byte pieces per position
 };
 
-template <typename T, int CIN, int NT, int FORM>
+// BWD (cvae_conv_s1_bwd_data): x is the incoming gradient, no bias, y = (acc + resid) * act'(gate); COUT_T = the channels stored in form SUBPIXEL_T
+template <typename T, int CIN, int NT, int FORM, bool BWD = false, int COUT_T = 0>
 __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, const T* resid, T* y,
-                                                      int H, int W, int act) {
+                                                      int H, int W, int act, const T* gate) {
     using G = S1Geom<T, CIN, FORM>;
     constexpr bool BF = std::is_same<T, bf16>::value;
     constexpr int N = 32 * NT;
-    constexpr int COUT = FORM == CVAE_CONV_S1_K3 ? N : N / 4;
+    constexpr int COUT = FORM == CVAE_CONV_S1_K3 ? N : (FORM == CVAE_CONV_S1_SUBPIXEL ? N / 4 : COUT_T);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T* hs = (T*)smem;                                                   // [HR * HC + 1][PITCH]: the last row is zeros, read for the zero-padded k >= K
     T* ws = hs + (G::HR * G::HC + 1) * G::PITCH;                        // [N][WPITCH]
@@ -74,7 +86,14 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
         const int hy = pos / G::HC, hx = pos - hy * G::HC;
         const int gy = y0 - G::PADL + hy, gx = x0 - G::PADL + hx;
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (pos < G::HR * G::HC && gy >= 0 && gy < H && gx >= 0 && gx < W) v = *(const uint4*)(xb + ((int64_t)gy * W + gx) * CIN + piece * G::E16);
+        if (pos < G::HR * G::HC && gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            if constexpr (FORM == CVAE_CONV_S1_SUBPIXEL_T) {            // channel (py, px, co) of position (gy, gx) is g[2 gy + py][2 gx + px][co]
+                const int e = piece * G::E16, q = e >> 4;
+                v = *(const uint4*)(xb + (((int64_t)(2 * gy + (q >> 1)) * (2 * W)) + 2 * gx + (q & 1)) * 16 + (e & 15));
+            } else {
+                v = *(const uint4*)(xb + ((int64_t)gy * W + gx) * CIN + piece * G::E16);
+            }
+        }
         *(uint4*)(hs + pos * G::PITCH + piece * G::E16) = v;
     }
     f32x16 acc[NT];
@@ -127,9 +146,10 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
     }
     // epilogue: lane (r, h) holds, for its position, channels j 32 + 8 g + 4 h + e in register 4 g + e of acc[j]
     const int gy = y0 + ly, gx = x0 + lx;
+    [[maybe_unused]] const float slope = BWD ? gate_slope(act) : 0.f;
     const bool live = gy < H && gx < W;                                 // lanes r and r + 32 share a position: the swap below pairs equals
     auto out_index = [&](int n) -> int64_t {                            // element index of channel n of this position in y (and resid)
-        if (FORM == CVAE_CONV_S1_K3) return ((b * H + gy) * (int64_t)W + gx) * COUT + n;
+        if (FORM != CVAE_CONV_S1_SUBPIXEL) return ((b * H + gy) * (int64_t)W + gx) * COUT + n;
         const int q = n / COUT, co = n - q * COUT;
         return ((b * 2 * H + 2 * gy + (q >> 1)) * (int64_t)(2 * W) + 2 * gx + (q & 1)) * COUT + co;
     };
@@ -137,22 +157,37 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
     for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int gp = 0; gp < 2; ++gp) {
+            if (FORM == CVAE_CONV_S1_SUBPIXEL_T && j * 32 + 16 * gp >= COUT) continue;      // zero rows of the matrix: nothing to store (uniform: no lane skips the swap alone)
             float v[2][4];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int g = 2 * gp + q, n = j * 32 + 8 * g + 4 * h;
-                float bv[4];
-                load_f32(bias + (n % COUT), bv);
+                if constexpr (BWD) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[q][e] = acc[j][4 * g + e] + bv[e];
+                    for (int e = 0; e < 4; ++e) v[q][e] = acc[j][4 * g + e];
+                } else {
+                    float bv[4];
+                    load_f32(bias + (n % COUT), bv);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[q][e] = acc[j][4 * g + e] + bv[e];
+                }
                 if (resid && live) {
                     float rv[4];
                     load_f32(resid + out_index(n), rv);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[q][e] += rv[e];
                 }
+                if constexpr (BWD) {
+                    if (gate && live) {                                 // torch's rule: x > 0 ? 1 : slope, read off the activation's OUTPUT (LeakyReLU keeps the sign)
+                        float gv[4];
+                        load_f32(gate + out_index(n), gv);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[q][e] = apply_act(v[q][e], act);
+                        for (int e = 0; e < 4; ++e) v[q][e] *= gv[e] > 0.f ? 1.f : slope;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[q][e] = apply_act(v[q][e], act);
+                }
             }
             if constexpr (BF) {
                 const uint2 a = make_uint2(pack2_bf16(v[0][0], v[0][1]), pack2_bf16(v[0][2], v[0][3]));
@@ -177,7 +212,20 @@ int conv_s1_launch(const void* x, const void* w, const float* bias, const void* 
     // set on every launch: the attribute belongs to the current device's copy of the kernel, and a flag would be shared by devices and host threads
     if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
     const dim3 grid((unsigned)((W + S1_TW - 1) / S1_TW), (unsigned)((H + S1_TH - 1) / S1_TH), (unsigned)B);
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)x, (const T*)w, bias, (const T*)resid, (T*)y, (int)H, (int)W, act);
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)x, (const T*)w, bias, (const T*)resid, (T*)y, (int)H, (int)W, act, (const T*)nullptr);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+template <typename T, int CIN, int NT, int FORM, int COUT_T>
+int conv_s1_bwd_launch(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int act, hipStream_t st) {
+    using G = S1Geom<T, CIN, FORM>;
+    auto kern = conv_s1_kernel<T, CIN, NT, FORM, true, COUT_T>;
+    constexpr size_t LDS = ((size_t)(G::HR * G::HC + 1) * G::PITCH + (size_t)32 * NT * G::WPITCH) * sizeof(T);
+    static_assert(LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
+    if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    const dim3 grid((unsigned)((W + S1_TW - 1) / S1_TW), (unsigned)((H + S1_TH - 1) / S1_TH), (unsigned)B);
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)g, (const T*)w, (const float*)nullptr, (const T*)resid, (T*)dx, (int)H, (int)W, act, (const T*)gate);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
@@ -306,11 +354,138 @@ __global__ __launch_bounds__(256) void latent_to_grid_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------ input gradient of Conv2d(16 -> 1, k3, s1, p1)
+// One thread per pixel: dx[y][x][ci] = (sum_{ky, kx} g[y + 1 - ky][x + 1 - kx] w[ci][ky][kx]) * act'(gate[y][x][ci]), the 9 products of a channel added
+// in (ky, kx) order; 16 channels leave as 16-byte stores (four fp32 / two bf16 pieces per thread, consecutive threads consecutive pixels).  g is the fp32
+// image cotangent; the weights as the forward reads them (rounded to bf16 first in bf16 mode).
+template <typename T>
+__global__ __launch_bounds__(256) void conv_s1_c1_bwd_kernel(const float* __restrict__ g, const float* __restrict__ w, const T* __restrict__ gate, T* __restrict__ dx,
+                                                             int64_t B, int H, int W, int act) {
+    __shared__ float wsm[9][C1_CIN];
+    if (threadIdx.x < 9 * C1_CIN) {
+        const int tap = threadIdx.x / C1_CIN, ci = threadIdx.x % C1_CIN;
+        const float v = w[ci * 9 + tap];
+        wsm[tap][ci] = std::is_same<T, bf16>::value ? (float)(bf16)v : v;
+    }
+    __syncthreads();
+    const int64_t total = B * H * W, i = blockIdx.x * (int64_t)256 + threadIdx.x;
+    if (i >= total) return;
+    const int xx = (int)(i % W), yy = (int)((i / W) % H);
+    const float* gb = g + (i / ((int64_t)W * H)) * (int64_t)H * W;
+    float gv[9];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int sy = yy + 1 - ky, sx = xx + 1 - kx;
+            gv[ky * 3 + kx] = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? gb[(int64_t)sy * W + sx] : 0.f;
+        }
+    float acc[C1_CIN], gt[C1_CIN];
+#pragma unroll
+    for (int ci = 0; ci < C1_CIN; ++ci) acc[ci] = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int ci = 0; ci < C1_CIN; ++ci) acc[ci] = fmaf(gv[tap], wsm[tap][ci], acc[ci]);
+    if (gate) {
+        const float slope = gate_slope(act);
+        load_f32(gate + i * C1_CIN, gt);
+#pragma unroll
+        for (int ci = 0; ci < C1_CIN; ++ci) acc[ci] *= gt[ci] > 0.f ? 1.f : slope;
+    }
+    store_from_f32(dx + i * C1_CIN, acc);
+}
+
+// ------------------------------------------------------------------------------------------------ channels-last grid gradient -> latent gradient
+// dz[b][k] = sum_n G[b][n] W[n][k], n = c P + p, G[b][c P + p] = g[b][p][c].  A slab = 32 channels x 8 positions = 256 rows of W (per channel 8 consecutive
+// rows: 8 K floats contiguous); the slab list depends on C and P only.  One workgroup per slab: its g values (all rows of the launch) go to LDS with
+// coalesced reads of 32 consecutive channels and are transposed there to [b][cl][pl]; thread (kq, rp) owns columns 4 kq .. 4 kq + 3 and walks the
+// 4-row groups rp, rp + RP, .. of the slab, two groups (eight 16-byte loads of W) issued before the first is used, every batch row's 4 sums in
+// registers, added in row order.  The RP phases are then added in phase order through LDS -> part[slab][b][K]; l2g_bwd_finish adds the slabs in slab order.
+#define L2GB_CB 32
+#define L2GB_PB 8
+#define L2GB_ROWS (L2GB_CB * L2GB_PB)
+template <typename T>
+__global__ __launch_bounds__(256) void l2g_bwd_kernel(const T* __restrict__ g, const float* __restrict__ Wt, float* __restrict__ part, int nb, int K, int64_t P, int C,
+                                                      int kq_pad) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* gs = (float*)smem;                                           // [nb][256]: row cl * 8 + pl
+    float* red = gs + nb * L2GB_ROWS;                                   // [RP][nb][K]
+    const int t = threadIdx.x;
+    const int pblocks = (int)((P + L2GB_PB - 1) / L2GB_PB);
+    const int cb = blockIdx.x / pblocks, pb = blockIdx.x - cb * pblocks;
+    const int64_t p0 = (int64_t)pb * L2GB_PB;
+    for (int i = t; i < nb * L2GB_ROWS; i += 256) {                     // i = (b, pl, cl): 32 consecutive channels per read
+        const int b = i / L2GB_ROWS, r = i - b * L2GB_ROWS, pl = r / L2GB_CB, cl = r - pl * L2GB_CB;
+        const int64_t p = p0 + pl;
+        gs[b * L2GB_ROWS + cl * L2GB_PB + pl] = p < P ? to_f32(g[((int64_t)b * P + p) * C + cb * L2GB_CB + cl]) : 0.f;
+    }
+    __syncthreads();
+    const int kq = t % kq_pad, rp = t / kq_pad, RP = 256 / kq_pad;
+    const bool col = 4 * kq < K;
+    float acc[L2G_BT][4];
+#pragma unroll
+    for (int b = 0; b < L2G_BT; ++b) acc[b][0] = acc[b][1] = acc[b][2] = acc[b][3] = 0.f;
+    if (col) {
+        for (int rg = rp; rg < L2GB_ROWS / 4; rg += 2 * RP) {           // 64 row groups; RP divides 32
+            float4 wv[2][4];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int lr = (rg + u * RP) * 4, cl = lr / L2GB_PB, pl = lr - cl * L2GB_PB;
+                const float* wr = Wt + ((int64_t)(cb * L2GB_CB + cl) * P + p0 + pl) * K + 4 * kq;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) wv[u][e] = p0 + pl + e < P ? *(const float4*)(wr + (int64_t)e * K) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int lr = (rg + u * RP) * 4;
+#pragma unroll
+                for (int b = 0; b < L2G_BT; ++b)
+                    if (b < nb) {
+                        const float4 gv = *(const float4*)(gs + b * L2GB_ROWS + lr);
+                        const float ge[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            acc[b][0] = fmaf(ge[e], wv[u][e].x, acc[b][0]); acc[b][1] = fmaf(ge[e], wv[u][e].y, acc[b][1]);
+                            acc[b][2] = fmaf(ge[e], wv[u][e].z, acc[b][2]); acc[b][3] = fmaf(ge[e], wv[u][e].w, acc[b][3]);
+                        }
+                    }
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < L2G_BT; ++b)
+            if (b < nb) *(float4*)(red + ((int64_t)rp * nb + b) * K + 4 * kq) = make_float4(acc[b][0], acc[b][1], acc[b][2], acc[b][3]);
+    }
+    __syncthreads();
+    float* out = part + (int64_t)blockIdx.x * nb * K;
+    for (int i = t; i < nb * K; i += 256) {
+        float s = red[i];
+        for (int q = 1; q < RP; ++q) s += red[q * nb * K + i];
+        out[i] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void l2g_bwd_finish_kernel(const float* __restrict__ part, float* __restrict__ dz, int n, int slabs) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int q = 0; q < slabs; ++q) s += part[(int64_t)q * n + i];
+    dz[i] = s;
+}
+
+int l2g_bwd_kq_pad(int64_t K) {                                         // threads across a row of W: the power of two at or above K / 4, 8 .. 128
+    int v = 8;
+    while (4 * v < K) v <<= 1;
+    return v;
+}
+int64_t l2g_bwd_slabs(int64_t P, int64_t C) { return (C / L2GB_CB) * ((P + L2GB_PB - 1) / L2GB_PB); }
+
 }  // namespace
 
 extern "C" int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form) {
     if (form == CVAE_CONV_S1_K3) return (Cin == Cout && (Cin == 32 || Cin == 64 || Cin == 128)) ? Cout * ((9 * Cin + S1_KPAD - 1) / S1_KPAD * S1_KPAD) : 0;
     if (form == CVAE_CONV_S1_SUBPIXEL) return (Cout == 16 && (Cin == 32 || Cin == 16)) ? 4 * Cout * ((4 * Cin + S1_KPAD - 1) / S1_KPAD * S1_KPAD) : 0;
+    if (form == CVAE_CONV_S1_SUBPIXEL_T) return (Cout == 16 && (Cin == 32 || Cin == 16)) ? 32 * 256 : 0;      // the backward matrix [32][4 taps x 64]
     return 0;
 }
 
@@ -386,6 +561,83 @@ extern "C" int cvae_latent_to_grid(const float* z, const float* W, const float* 
     const hipStream_t st = (hipStream_t)stream;
     if (dtype == CVAE_BF16) hipLaunchKernelGGL(latent_to_grid_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (bf16*)out, (int)B, (int)K, P, (int)C);
     else hipLaunchKernelGGL(latent_to_grid_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (float*)out, (int)B, (int)K, P, (int)C);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_conv_s1_bwd_data(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t C, int form,
+                                     int dtype, int gate_act, void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || H > 65535 * S1_TH || B > 65535 || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL_T) return CVAE_E_UNSUPPORTED;
+    if (cvae_conv_s1_weight_elems(C, form == CVAE_CONV_S1_K3 ? C : 16, form) == 0) return CVAE_E_UNSUPPORTED;
+    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_LEAKY02 && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!g || !w || !dx || (gate_act != CVAE_ACT_NONE && !gate)) return CVAE_E_NULLPTR;
+    if (!aligned16(g) || !aligned16(w) || !aligned16(dx) || !aligned16(resid) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
+    if (gate_act == CVAE_ACT_NONE) gate = nullptr;
+    const hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        if (form == CVAE_CONV_S1_K3) {
+            if (C == 32) return conv_s1_bwd_launch<T, 32, 1, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+            if (C == 64) return conv_s1_bwd_launch<T, 64, 2, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+            return conv_s1_bwd_launch<T, 128, 4, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+        }
+        if (C == 32) return conv_s1_bwd_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, 32>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+        return conv_s1_bwd_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, 16>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+    });
+}
+
+extern "C" int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int gate_act,
+                                        void* stream) {
+    if (B < 0 || H <= 0 || W <= 0 || H > ((int64_t)1 << 24) || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
+    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_LEAKY02 && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!g || !w || !dx || (gate_act != CVAE_ACT_NONE && !gate)) return CVAE_E_NULLPTR;
+    if (!aligned16(dx) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
+    if (gate_act == CVAE_ACT_NONE) gate = nullptr;
+    const int64_t blocks = (B * H * W + 255) / 256;
+    if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
+    const hipStream_t st = (hipStream_t)stream;
+    if (dtype == CVAE_BF16) hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const bf16*)gate, (bf16*)dx, B, (int)H, (int)W, gate_act);
+    else hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const float*)gate, (float*)dx, B, (int)H, (int)W, gate_act);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" size_t cvae_latent_to_grid_bwd_workspace_bytes(int64_t B, int64_t K, int64_t P, int64_t C) {
+    if (B <= 0 || B > L2G_BT || K <= 0 || K > L2G_KMAX || P <= 0 || C <= 0 || (C & 31) || P * C > ((int64_t)1 << 40)) return 0;
+    return (size_t)l2g_bwd_slabs(P, C) * B * K * sizeof(float);
+}
+
+extern "C" int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (B < 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (B > L2G_BT || K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!g || !W || !dz) return CVAE_E_NULLPTR;
+    if (!aligned16(W) || !aligned16(workspace)) return CVAE_E_UNSUPPORTED;
+    const int64_t slabs = l2g_bwd_slabs(P, C);
+    if (slabs > 0x7fffffff) return CVAE_E_BADSHAPE;
+    if (!workspace || workspace_bytes < cvae_latent_to_grid_bwd_workspace_bytes(B, K, P, C)) return CVAE_E_WORKSPACE;
+    const int kq_pad = l2g_bwd_kq_pad(K), RP = 256 / kq_pad;
+    const size_t lds = ((size_t)B * L2GB_ROWS + (size_t)RP * B * K) * sizeof(float);         // at most 16 KB + 64 KB
+    const hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    if (dtype == CVAE_BF16) {
+        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
+        hipLaunchKernelGGL(l2g_bwd_kernel<bf16>, dim3((unsigned)slabs), dim3(256), lds, st, (const bf16*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
+    } else {
+        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
+        hipLaunchKernelGGL(l2g_bwd_kernel<float>, dim3((unsigned)slabs), dim3(256), lds, st, (const float*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
+    }
+    CVAE_CHECK_LAUNCH();
+    const int n = (int)(B * K);
+    hipLaunchKernelGGL(l2g_bwd_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)part, dz, n, (int)slabs);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }

@@ -120,17 +120,43 @@ __global__ __launch_bounds__(256) void fold_bn_conv_kernel(const FoldTable T) {
         }
         return;
     }
-    if (E.kind == CVAE_FOLD_CONV_K3S1 || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL) {
+    if (E.kind == CVAE_FOLD_CONV_K3S1 || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL || E.kind == CVAE_FOLD_CONV_K3S1_GRAD || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD) {
         // the GEMM matrix [N][KT] of cvae_conv_s1 (csrc/conv_s1.hip), k = tap * Cin + ci, KT = K rounded up to 64 with zero columns; a float4 group is 4
         // consecutive ci of one (n, tap).  K3S1: Conv2d [Cout][Cin][3][3], N = Cout, tap = ky * 3 + kx.  SUBPIXEL: ConvTranspose2d [Cin][Cout][3][3],
         // N = 4 Cout with n = (py * 2 + px) * Cout + co, tap = dy * 2 + dx, k index per direction: parity 0: {d 0 -> k 1}; parity 1: {d 0 -> k 2, d 1 -> k 0}
-        const bool sp = E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL;
+        // The _GRAD kinds append the input gradient's matrix (cvae_conv_s1_bwd_data) behind the forward one.  K3: [Cin][KTb], k = tap' * Cout + co,
+        // w[co][ci][8 - tap'] s[co] (taps flipped, channels transposed).  SUBPIXEL: [32][256], k = (dy 2 + dx) 64 + (py 2 + px) 16 + co over the
+        // space-to-depth view of the gradient, tap index per direction 2 d + parity - 1 (negative: no tap), rows ci >= Cin zero.
+        const bool sp = E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD;
+        const bool grad = E.kind == CVAE_FOLD_CONV_K3S1_GRAD || E.kind == CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD;
+        const int ktb4 = sp ? 64 : ((9 * E.cout + 63) / 64 * 64) >> 2;
+        const int64_t nb4 = grad ? (int64_t)(sp ? 32 : E.cin) * ktb4 : 0;
         const int taps = sp ? 4 : 9, N = sp ? 4 * E.cout : E.cout;
         const int K = taps * E.cin, KT = (K + 63) / 64 * 64, kt4 = KT >> 2;
         const int64_t n4 = (int64_t)N * kt4;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int64_t g = (int64_t)blk * FOLD_K4_PER_BLOCK + t + u * 256;
+            if (g >= n4 && g < n4 + nb4) {
+                const int64_t gb = g - n4;
+                const int ci = (int)(gb / ktb4), k = (int)(gb - (int64_t)ci * ktb4) * 4;
+                float o[4] = {0.f, 0.f, 0.f, 0.f};
+                if (!sp) {
+                    const int tap = k / E.cout, co = k - tap * E.cout;
+                    if (tap < 9) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = E.w[((size_t)(co + e) * E.cin + ci) * 9 + 8 - tap] * fold_scale(E, co + e);
+                    }
+                } else {
+                    const int tap = k >> 6, q = (k >> 4) & 3, co = k & 15;
+                    const int ky = 2 * (tap >> 1) + (q >> 1) - 1, kx = 2 * (tap & 1) + (q & 1) - 1;
+                    if (ci < E.cin && ky >= 0 && kx >= 0) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = E.w[((size_t)ci * E.cout + co + e) * 9 + ky * 3 + kx] * fold_scale(E, co + e);
+                    }
+                }
+                ((float4*)E.w_out)[g] = make_float4(o[0], o[1], o[2], o[3]);
+            }
             if (g < n4) {
                 const int n = (int)(g / kt4), k = (int)(g - (int64_t)n * kt4) * 4;
                 float o[4] = {0.f, 0.f, 0.f, 0.f};
@@ -357,10 +383,14 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         const int64_t Cout = dims[2 * k], Cin = dims[2 * k + 1];
         if (Cout <= 0 || Cin <= 0 || Cout * Cin > ((int64_t)1 << 28)) return CVAE_E_BADSHAPE;
         if (kind[k] != CVAE_FOLD_CONV_K4 && kind[k] != CVAE_FOLD_UPCONV_K3 && kind[k] != CVAE_FOLD_CONV_K3S2 && kind[k] != CVAE_FOLD_CONVT_K3S2 &&
-            kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL)
+            kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL && kind[k] != CVAE_FOLD_CONV_K3S1_GRAD &&
+            kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD)
             return CVAE_E_UNSUPPORTED;
-        const bool gemm_form = kind[k] == CVAE_FOLD_CONV_K3S1 || kind[k] == CVAE_FOLD_CONVT_K3S2_SUBPIXEL;
+        const bool k3_form = kind[k] == CVAE_FOLD_CONV_K3S1 || kind[k] == CVAE_FOLD_CONV_K3S1_GRAD;
+        const bool grad_form = kind[k] == CVAE_FOLD_CONV_K3S1_GRAD || kind[k] == CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD;
+        const bool gemm_form = k3_form || kind[k] == CVAE_FOLD_CONVT_K3S2_SUBPIXEL || grad_form;
         if (gemm_form && (Cin & 3)) return CVAE_E_UNSUPPORTED;
+        if (grad_form && (k3_form ? (Cout & 3) != 0 : (Cout != 16 || Cin > 32))) return CVAE_E_UNSUPPORTED;
         if (!w[k] || !w_out[k] || !b_out[k]) return CVAE_E_NULLPTR;
         const bool bn = gamma && gamma[k];
         if (bn && (!beta || !beta[k] || !mean || !mean[k] || !var || !var[k])) return CVAE_E_NULLPTR;
@@ -375,8 +405,9 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         E.eps = eps[k];
         E.kind = kind[k];
         E.cout = (int)Cout; E.cin = (int)Cin;
-        const int64_t gemm_kt = ((kind[k] == CVAE_FOLD_CONV_K3S1 ? 9 : 4) * Cin + 63) / 64 * 64;
-        E.wblocks = gemm_form ? (int)(((kind[k] == CVAE_FOLD_CONV_K3S1 ? 1 : 4) * Cout * (gemm_kt / 4) + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
+        const int64_t gemm_kt = ((k3_form ? 9 : 4) * Cin + 63) / 64 * 64;
+        const int64_t grad4 = !grad_form ? 0 : (k3_form ? Cin * ((9 * Cout + 63) / 64 * 64 / 4) : 32 * 64);        // float4 groups of the appended backward matrix
+        E.wblocks = gemm_form ? (int)(((k3_form ? 1 : 4) * Cout * (gemm_kt / 4) + grad4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
                   : kind[k] != CVAE_FOLD_UPCONV_K3 ? (int)((Cout * Cin * 4 + FOLD_K4_PER_BLOCK - 1) / FOLD_K4_PER_BLOCK)
                                                  : (int)(((Cout + FOLD_K3_TILE - 1) / FOLD_K3_TILE) * ((Cin + FOLD_K3_TILE - 1) / FOLD_K3_TILE));
         E.bblocks = (int)((Cout + 255) / 256);

@@ -1824,8 +1824,10 @@ class Conv3ToK4(torch.autograd.Function):
 # they raise (the reference consumers run them under no_grad).
 FOLD_CONV_K4, FOLD_UPCONV_K3, FOLD_CONV_K3S2 = 0, 1, 3        # CVAE_FOLD_CONV_K4 / CVAE_FOLD_UPCONV_K3 / CVAE_FOLD_CONV_K3S2
 FOLD_CONVT_K3S2, FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL = 4, 5, 6      # the ViT-VAE decoder's kinds (CVAE_FOLD_CONVT_K3S2 / _CONV_K3S1 / _CONVT_K3S2_SUBPIXEL)
-_FOLD_CONVT = (FOLD_CONVT_K3S2, FOLD_CONVT_K3S2_SUBPIXEL)     # weight [Cin][Cout][3][3]: the BatchNorm's channels are dimension 1
-_FOLD_GEMM = (FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL)       # w_out is the [N][KT] matrix of conv_s1
+FOLD_CONV_K3S1_GRAD, FOLD_CONVT_K3S2_SUBPIXEL_GRAD = 7, 8     # kinds 5 / 6 with the input gradient's matrix appended (CVAE_FOLD_*_GRAD)
+_FOLD_GRAD = (FOLD_CONV_K3S1_GRAD, FOLD_CONVT_K3S2_SUBPIXEL_GRAD)
+_FOLD_CONVT = (FOLD_CONVT_K3S2, FOLD_CONVT_K3S2_SUBPIXEL, FOLD_CONVT_K3S2_SUBPIXEL_GRAD)     # weight [Cin][Cout][3][3]: the BatchNorm's channels are dimension 1
+_FOLD_GEMM = (FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL) + _FOLD_GRAD      # w_out is the [N][KT] matrix of conv_s1
 
 
 def _forward_only(what, *tensors):
@@ -1840,7 +1842,9 @@ def fold_bn_conv(entries):
     with a zero fourth row and column) and bn an nn.BatchNorm2d on running statistics, or None (plain transform, bias copied).
     The ViT-VAE decoder's kinds: FOLD_CONVT_K3S2 (nn.ConvTranspose2d(k3, s2, p1, output_padding 1) weight [Cin][Cout][3][3] -> the transposed k4 weight
     [Cin][Cout][4][4], zero fourth row and column, scaled per Cout), FOLD_CONV_K3S1 (nn.Conv2d(k3, s1, p1) weight -> conv_s1's matrix [Cout][KT]) and
-    FOLD_CONVT_K3S2_SUBPIXEL (the ConvTranspose2d weight -> conv_s1's sub-pixel matrix [4 Cout][KT]).
+    FOLD_CONVT_K3S2_SUBPIXEL (the ConvTranspose2d weight -> conv_s1's sub-pixel matrix [4 Cout][KT]).  FOLD_CONV_K3S1_GRAD / FOLD_CONVT_K3S2_SUBPIXEL_GRAD:
+    the same forward matrix (the same bits) and, from the same launch, the matrix of the layer's input gradient for conv_s1_bwd_data ([Cin][KT] resp.
+    [32][256]): these entries return (w_out, b_out, w_grad).
     Returns [(w_out, b_out)] fp32, all views of one fresh buffer."""
     import ctypes as C
     k = len(entries)
@@ -1859,21 +1863,23 @@ def fold_bn_conv(entries):
         cout = w.shape[1] if kind in _FOLD_CONVT else w.shape[0]
         if kind in _FOLD_GEMM:
             cin, taps, rows = (w.shape[0], 4, 4 * cout) if kind in _FOLD_CONVT else (w.shape[1], 9, cout)
-            sizes.append((rows * ((taps * cin + 63) // 64 * 64), cout))
+            nbwd = 0 if kind not in _FOLD_GRAD else (32 * 256 if kind in _FOLD_CONVT else cin * ((9 * cout + 63) // 64 * 64))
+            sizes.append((rows * ((taps * cin + 63) // 64 * 64), cout, nbwd))
         else:
-            sizes.append((w.shape[0] * w.shape[1] * 16, cout))
+            sizes.append((w.shape[0] * w.shape[1] * 16, cout, 0))
     pad = lambda n: (n + 3) // 4 * 4                      # every piece starts on 16 bytes
-    buf = torch.empty(sum(pad(a) + pad(b) for a, b in sizes), dtype=torch.float32, device=entries[0][0].device)
+    buf = torch.empty(sum(pad(a + g) + pad(b) for a, b, g in sizes), dtype=torch.float32, device=entries[0][0].device)
     outs, off = [], 0
-    for (w, kind, _b, _bn), (nw, nb) in zip(entries, sizes):
+    for (w, kind, _b, _bn), (nw, nb, ng) in zip(entries, sizes):
         shape = tuple(w.shape[:2]) + (4, 4) if kind != FOLD_UPCONV_K3 else (w.shape[1], w.shape[0], 4, 4)
         if kind in _FOLD_GEMM:
             shape = (4 * nb if kind in _FOLD_CONVT else nb, -1)
         wo = buf[off:off + nw].view(shape)
-        off += pad(nw)
+        wg = buf[off + nw:off + nw + ng].view((32 if kind in _FOLD_CONVT else w.shape[1], -1)) if ng else None      # the forward matrix's size is a multiple of 64
+        off += pad(nw + ng)
         bo = buf[off:off + nb]
         off += pad(nb)
-        outs.append((wo, bo))
+        outs.append((wo, bo, wg) if ng else (wo, bo))
     ws = [w.contiguous() for w, _k, _b, _bn in entries]
     vp = lambda v: (C.c_void_p * k)(*v)
     dims = [d for w, (_w, kind, _b, _bn) in zip(ws, entries) for d in ((w.shape[1], w.shape[0]) if kind in _FOLD_CONVT else (w.shape[0], w.shape[1]))]
@@ -2006,7 +2012,7 @@ def mhsa(q, k, v, n_query_rows=None):
 
 
 # ---- ViT-VAE decoder (csrc/conv_s1.hip): forward-only building blocks on raw tensors -------------------------------------------------
-CONV_S1_K3, CONV_S1_SUBPIXEL = 0, 1      # CVAE_CONV_S1_*
+CONV_S1_K3, CONV_S1_SUBPIXEL, CONV_S1_SUBPIXEL_T = 0, 1, 2      # CVAE_CONV_S1_* (SUBPIXEL_T: conv_s1_bwd_data only)
 
 
 def conv_s1_pack_weights(mats):
@@ -2070,7 +2076,82 @@ def conv_s1_c1(x, weight, bias, act=None):
     return y
 
 
+def conv_s1_bwd_data(g, wmat, form, resid=None, gate=None, gate_act=None):
+    """(conv(g, w^T) + resid) * act'(gate): the input gradient of conv_s1's layer through a frozen weight (cvae_conv_s1_bwd_data), channels-last, fp32 or bf16.
+    form CONV_S1_K3: g [B, H, W, C] -> [B, H, W, C]; CONV_S1_SUBPIXEL_T (the narrow transposed convs): g [B, 2H, 2W, 16] -> [B, H, W, Cin], Cin = the
+    second argument of the pair (wmat, Cin) passed as wmat.  wmat: the third element fold_bn_conv returns for a FOLD_*_GRAD entry, in g's dtype.  resid / gate
+    (optional): the result's shape and dtype; gate is the OUTPUT of the activation whose derivative is applied (LeakyReLU keeps the sign): gate > 0 ? 1 : slope."""
+    cin = None
+    if isinstance(wmat, tuple):
+        wmat, cin = wmat
+    L.require_gpu(g, wmat, resid, gate)
+    _forward_only("conv_s1_bwd_data", g, wmat, resid, gate)
+    if g.dim() != 4 or not g.is_contiguous() or form not in (CONV_S1_K3, CONV_S1_SUBPIXEL_T) or (form == CONV_S1_SUBPIXEL_T) != (cin is not None):
+        raise L.CvaeError(f"conv_s1_bwd_data: a contiguous channels-last [B, H, W, C] gradient expected, got {tuple(g.shape)} in form {form}")
+    B, H, W, Cg = g.shape
+    if form == CONV_S1_SUBPIXEL_T:
+        if Cg != 16 or H % 2 or W % 2:
+            raise L.CvaeError(f"conv_s1_bwd_data: the sub-pixel form takes a [B, 2H, 2W, 16] gradient, got {tuple(g.shape)}")
+        H, W, C = H // 2, W // 2, int(cin)
+    else:
+        C = Cg
+    n = lib.cvae_conv_s1_weight_elems(C, C if form == CONV_S1_K3 else 16, form)
+    if n == 0:
+        raise L.CvaeError(f"conv_s1_bwd_data: {C} channels in form {form}: {L.strerror(-3)}")
+    if wmat.dtype != g.dtype or wmat.numel() != n or not wmat.is_contiguous():
+        raise L.CvaeError(f"conv_s1_bwd_data: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {C} channels in {g.dtype} ({n} elements)")
+    oshape = (B, H, W, C)
+    for name, t in (("residual", resid), ("gate", gate)):
+        if t is not None and (tuple(t.shape) != oshape or t.dtype != g.dtype or not t.is_contiguous()):
+            raise L.CvaeError(f"conv_s1_bwd_data: the {name} must be a contiguous {oshape} {g.dtype} tensor")
+    if (gate is None) != (gate_act in (None, "none")):
+        raise L.CvaeError("conv_s1_bwd_data: gate and gate_act come together")
+    dx = _empty(oshape, g.dtype, g)
+    check(lib.cvae_conv_s1_bwd_data(ptr(g), ptr(wmat), ptr(resid), ptr(gate), ptr(dx), B, H, W, C, form, L.dtype_code(g.dtype), L.act_code(gate_act), stream()),
+          "conv_s1_bwd_data")
+    return dx
+
+
+def conv_s1_c1_bwd_data(g, weight, gate, gate_act, out_dtype):
+    """The input gradient of nn.Conv2d(16, 1, 3, 1, 1) (cvae_conv_s1_c1_bwd_data): g fp32 [B, 1, H, W], the fp32 module weight as it is -> channels-last
+    [B, H, W, 16] in out_dtype, times act'(gate) (gate: the conv's input, [B, H, W, 16] in out_dtype, or None)."""
+    L.require_gpu(g, weight, gate)
+    _forward_only("conv_s1_c1_bwd_data", g, weight, gate)
+    if g.dim() != 4 or g.shape[1] != 1 or g.dtype != torch.float32 or tuple(weight.shape) != (1, 16, 3, 3) or weight.dtype != torch.float32:
+        raise L.CvaeError(f"conv_s1_c1_bwd_data: g {tuple(g.shape)} {g.dtype}, weight {tuple(weight.shape)} {weight.dtype}")
+    B, _one, H, W = g.shape
+    if gate is not None and (tuple(gate.shape) != (B, H, W, 16) or gate.dtype != out_dtype or not gate.is_contiguous()):
+        raise L.CvaeError(f"conv_s1_c1_bwd_data: the gate must be a contiguous {(B, H, W, 16)} {out_dtype} tensor")
+    if (gate is None) != (gate_act in (None, "none")):
+        raise L.CvaeError("conv_s1_c1_bwd_data: gate and gate_act come together")
+    dx = _empty((B, H, W, 16), out_dtype, g)
+    check(lib.cvae_conv_s1_c1_bwd_data(ptr(g.contiguous()), ptr(weight.detach().contiguous()), ptr(gate), ptr(dx), B, H, W, 16, L.dtype_code(out_dtype),
+                                       L.act_code(gate_act), stream()), "conv_s1_c1_bwd_data")
+    return dx
+
+
 LATENT_TO_GRID_ROWS = 16     # batch rows per cvae_latent_to_grid launch
+
+
+def latent_to_grid_bwd(g, weight):
+    """dz [B, K] fp32 = the gradient of latent_to_grid with respect to z: sum over (p, c) of g[b][p][c] weight[c P + p][k] (cvae_latent_to_grid_bwd).
+    g: channels-last [B, P, C] fp32 or bf16; weight the fp32 nn.Linear tensor [C P, K], read once per launch of up to 16 rows."""
+    L.require_gpu(g, weight)
+    _forward_only("latent_to_grid_bwd", g, weight)
+    if g.dim() != 3 or not g.is_contiguous() or weight.dim() != 2 or weight.dtype != torch.float32 or weight.shape[0] != g.shape[1] * g.shape[2]:
+        raise L.CvaeError(f"latent_to_grid_bwd: g {tuple(g.shape)}, weight {tuple(weight.shape)} {weight.dtype}")
+    B, P, C = g.shape
+    K = weight.shape[1]
+    w = weight.detach().contiguous()
+    dz = _empty((B, K), torch.float32, g)
+    for b0 in range(0, B, LATENT_TO_GRID_ROWS):
+        nb = min(LATENT_TO_GRID_ROWS, B - b0)
+        nbytes = lib.cvae_latent_to_grid_bwd_workspace_bytes(nb, K, P, C)
+        if not nbytes:
+            raise L.CvaeError(f"latent_to_grid_bwd: K {K}, P {P}, C {C}: {L.strerror(-3)}")
+        _t, wp, wb = _scratch(nbytes, g)
+        check(lib.cvae_latent_to_grid_bwd(ptr(g[b0:]), ptr(w), ptr(dz[b0:]), nb, K, P, C, L.dtype_code(g.dtype), wp, wb, stream()), "latent_to_grid_bwd")
+    return dz
 
 
 def latent_to_grid(z, weight, bias, channels, out_dtype):

@@ -22,6 +22,9 @@ draws the reference's weights and the state_dict key sets are equal.  decode, pe
   ResBlock(C)    two cvae_conv_s1 launches (3 x 3 window): LeakyReLU(0.2) in the first, the block input as the residual of the second
   32->16, 16->16 cvae_conv_s1 in sub-pixel form (2 x 2 forward window to 64 channels, pixel-shuffle store), LeakyReLU(0.01)
   16->1          cvae_conv_s1_c1 -> fp32 [B, 1, H, W]
+decode_with_grad / decode_vjp add the gradient of that image with respect to z through the FROZEN eval-mode decoder: the forward issues
+decode's launches (the fold also writes the backward matrices) and keeps five gate activations and the three ResBlock inner activations; the backward is
+cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
 """
 import numpy as np
 import torch
@@ -242,6 +245,120 @@ class ViTVAE(ViTVAEEncoder):
                 collect["stages"].append(h)
         return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias)
 
+    # ---- the gradient with respect to the latent (frozen decoder, eval mode) -----------------------------------------------------
+    def freeze_decoder(self):
+        """requires_grad_(False) on decoder_input and decoder: what decode_with_grad asks for (it returns no weight gradients)."""
+        self.decoder_input.requires_grad_(False)
+        self.decoder.requires_grad_(False)
+        return self
+
+    def _check_grad_path(self, z):
+        if self.training:
+            raise RuntimeError("ViTVAE: put the model in eval mode first (model.eval()): batch-statistics BatchNorm2d is not implemented, the decoder's "
+                               "gradient path runs through eval-mode BatchNorm only")
+        if z.dim() != 2 or z.shape[1] != self.latent_dim or z.dtype != torch.float32:
+            raise CvaeError(f"ViTVAE.decode expects a float32 [B, {self.latent_dim}] batch, got {tuple(z.shape)} {z.dtype}")
+        live = sorted(f"{root}.{k}" for root in ("decoder_input", "decoder") for k, p in getattr(self, root).named_parameters() if p.requires_grad)
+        if live:
+            raise CvaeError("ViTVAE.decode_with_grad returns the gradient with respect to z only, through a frozen decoder: these parameters ask for a gradient "
+                            f"that would silently stay None: {live} (call model.freeze_decoder())")
+        require_gpu(z, self.decoder_input.weight)
+
+    def _decode_saving(self, z, collect=None):
+        """_decode's launches with the fold's _GRAD kinds (the same forward matrices, bit for bit, plus the backward ones from the same launch).  Returns
+        (image, saved): saved = dict(stages = {i: gate activation h_i for i in 0, 2, 4, 6, 7}, inner = the three ResBlock inner activations, mats = the
+        backward matrix per GEMM table entry, k4 = the folded k4 weight per wide transposed conv).  collect: as _decode, and `res_inner`."""
+        dt = self.compute_dtype
+        plan, out_conv = self._decoder_plan()
+        table = []
+        for st in plan:
+            if st[0] == "res":
+                c = st[1].conv
+                table += [(c[0].weight, ops.FOLD_CONV_K3S1_GRAD, c[0].bias, c[1]), (c[3].weight, ops.FOLD_CONV_K3S1_GRAD, c[3].bias, c[4])]
+            else:
+                table.append((st[1].weight, ops.FOLD_CONVT_K3S2 if st[0] == "up" else ops.FOLD_CONVT_K3S2_SUBPIXEL_GRAD, st[1].bias, st[2]))
+        folded = ops.fold_bn_conv(table)
+        gemm = [i for i, e in enumerate(table) if e[1] != ops.FOLD_CONVT_K3S2]
+        mats, bmats = {i: folded[i][0] for i in gemm}, {i: folded[i][2] for i in gemm}
+        if dt == torch.bfloat16:                                       # one launch for the forward and the backward matrices (16 of them)
+            packed = ops.conv_s1_pack_weights([folded[i][0] for i in gemm] + [folded[i][2] for i in gemm])
+            mats, bmats = dict(zip(gemm, packed[:len(gemm)])), dict(zip(gemm, packed[len(gemm):]))
+        B = z.shape[0]
+        h = ops.latent_to_grid(z, self.decoder_input.weight, self.decoder_input.bias, self.embed_dim, dt).view(B, self.grid_h, self.grid_w, self.embed_dim)
+        if collect is not None:
+            collect["grid"], collect["stages"], collect["res_inner"] = h, [], []
+        saved = {"stages": {}, "inner": [], "mats": bmats, "k4": {}}
+        k = 0
+        for i, st in enumerate(plan):
+            if st[0] == "up":
+                w, b = folded[k]
+                _B, hh, ww, c = h.shape
+                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), w, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, w.shape[1])
+                saved["k4"][k] = w
+                k += 1
+            elif st[0] == "sub":
+                h = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, "leaky001")
+                k += 1
+            else:
+                y = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_K3, "leaky02")
+                h = ops.conv_s1(y, mats[k + 1], folded[k + 1][1], ops.CONV_S1_K3, None, resid=h)
+                saved["inner"].append(y)
+                if collect is not None:
+                    collect["res_inner"].append(y)
+                k += 2
+            if st[0] != "res":
+                saved["stages"][i] = h
+            if collect is not None:
+                collect["stages"].append(h)
+        return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias), saved
+
+    def _decode_backward(self, saved, g_img):
+        """dz [B, latent_dim] fp32 from the image cotangent [B, 1, H, W] fp32: the chain of DESIGN §13.  `g` is the gradient with respect to a transposed
+        conv's PRE-activation (the producing epilogue applied leaky001' from the saved output) or to a ResBlock's output; no activation-backward launch."""
+        plan, out_conv = self._decoder_plan()
+        dt = self.compute_dtype
+        stages, mats = saved["stages"], saved["mats"]
+        B = g_img.shape[0]
+        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, stages[len(plan) - 1], "leaky001", dt)
+        k = sum(2 if st[0] == "res" else 1 for st in plan)
+        inner = list(saved["inner"])
+        for i in range(len(plan) - 1, -1, -1):
+            st = plan[i]
+            gate = stages.get(i - 1)                                    # the stage's input when it is a LeakyReLU(0.01) output; a ResBlock sum / the grid: None
+            act = "leaky001" if gate is not None else None
+            if st[0] == "sub":
+                k -= 1
+                g = ops.conv_s1_bwd_data(g, (mats[k], st[1].in_channels), ops.CONV_S1_SUBPIXEL_T, gate=gate, gate_act=act)
+            elif st[0] == "res":
+                k -= 2
+                t = ops.conv_s1_bwd_data(g, mats[k + 1], ops.CONV_S1_K3, gate=inner.pop(), gate_act="leaky02")
+                g = ops.conv_s1_bwd_data(t, mats[k], ops.CONV_S1_K3, resid=g, gate=gate, gate_act=act)
+            else:
+                k -= 1
+                w = saved["k4"][k]
+                _B, hh, ww, c = g.shape
+                g = ops._conv_down(g.view(B, 1, hh, ww, c), ops.pack_weight(w, 2, False, dt), None, None, w.shape[0], 2, None).view(B, hh // 2, ww // 2, w.shape[0])
+        return ops.latent_to_grid_bwd(g.view(B, self.grid_h * self.grid_w, self.embed_dim), self.decoder_input.weight)
+
+    def decode_with_grad(self, z, collect=None):
+        """decode(z) (the same launches, the same bits) as a differentiable function of z: backward returns d image / d z through the frozen eval-mode
+        decoder, and nothing else — a decoder parameter with requires_grad=True is an error (freeze_decoder()).  Not twice differentiable."""
+        self._check_grad_path(z)
+        return _DecodeWithGrad.apply(z, self, collect)
+
+    @torch.no_grad()
+    def decode_vjp(self, z, grad_image):
+        """dz = (d decode(z) / d z)^T grad_image, fp32 [B, latent_dim]: the explicit form of decode_with_grad's backward (capturable in a graph)."""
+        self._check_grad_path(z)
+        if tuple(grad_image.shape) != (z.shape[0], 1, self.img_height, self.img_width) or grad_image.dtype != torch.float32:
+            raise CvaeError(f"ViTVAE.decode_vjp expects a float32 [{z.shape[0]}, 1, {self.img_height}, {self.img_width}] cotangent, got "
+                            f"{tuple(grad_image.shape)} {grad_image.dtype}")
+        require_gpu(grad_image)
+        if z.shape[0] == 0:
+            return torch.zeros_like(z)
+        _image, saved = self._decode_saving(z.detach())
+        return self._decode_backward(saved, grad_image.contiguous())
+
     def reparameterize(self, mu, log_var):
         """vit_backbone.py:181-184: mu + randn_like(std) * std on torch's generator."""
         std = torch.exp(0.5 * log_var)
@@ -257,6 +374,43 @@ class ViTVAE(ViTVAEEncoder):
     def reconstruct(self, x):
         """decode(mu(x)): the deterministic reconstruction."""
         return self.decode(self.encode(x)[0])
+
+
+class _DecodeWithGrad(torch.autograd.Function):
+    """ViTVAE.decode_with_grad: z -> image, with dz as the only gradient."""
+
+    @staticmethod
+    def forward(ctx, z, model, collect):
+        image, saved = model._decode_saving(z.detach(), collect)
+        ctx.model, ctx.saved = model, saved                            # activations and folded matrices of this call: private to the node, freed with it
+        return image
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g.shape[0] == 0:
+            return g.new_zeros(0, ctx.model.latent_dim), None, None
+        return ctx.model._decode_backward(ctx.saved, g.contiguous()), None, None
+
+
+def fit_latent(model, x, z0, steps, lr, loss="sse"):
+    """Fit a latent to images: Adam on z through decode_with_grad and the project's losses.  x [B, 1, H, W] fp32, z0 [B, latent_dim] fp32 (not modified);
+    loss "sse" (ops.sse) or "vessel" (ops.VesselRecon: recon + sparsity, vessel_analysis/01_train/train.py:27-46).  Returns (z, losses): the fitted
+    latent and the loss BEFORE each of the `steps` updates as a list of floats (read from the device once, at the end)."""
+    if loss not in ("sse", "vessel"):
+        raise CvaeError(f"fit_latent: loss must be 'sse' or 'vessel', got {loss!r}")
+    require_gpu(x, z0)
+    z = z0.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([z], lr=lr)
+    losses = []
+    for _ in range(int(steps)):
+        opt.zero_grad(set_to_none=True)
+        recon = model.decode_with_grad(z)
+        value = ops.sse(recon, x) if loss == "sse" else sum(ops.VesselRecon.apply(recon, x))
+        value.backward()
+        opt.step()
+        losses.append(value.detach())
+    return z.detach(), [float(v) for v in torch.stack(losses).cpu()] if losses else []
 
 
 def resize_pos_embedding(pos, src_grid, dst_grid):

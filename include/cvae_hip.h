@@ -252,6 +252,14 @@ int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gam
 #define CVAE_FOLD_CONVT_K3S2          4
 #define CVAE_FOLD_CONV_K3S1           5
 #define CVAE_FOLD_CONVT_K3S2_SUBPIXEL 6
+/* The same two GEMM kinds with the matrix of the layer's INPUT GRADIENT (cvae_conv_s1_bwd_data) written behind the forward matrix, w_out = [forward | backward]
+ * (the forward part bit for bit what kinds 5 / 6 write; the BatchNorm scale s[co] sits on the backward matrix's K side):
+ *   kind CVAE_FOLD_CONV_K3S1_GRAD:           + [Cin][KT]: column (ky 3 + kx) Cout + co of row ci holds w[co][ci][2 - ky][2 - kx] s[co] (taps flipped, channels
+ *                                            transposed), KT = 9 Cout rounded up to 64;
+ *   kind CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD: + [32][256]: column (dy 2 + dx) 64 + (py 2 + px) 16 + co of row ci holds w[ci][co][2 dy + py - 1][2 dx + px - 1] s[co]
+ *                                            where both tap indices are >= 0, zero elsewhere and in rows ci >= Cin (Cout = 16 only, else CVAE_E_UNSUPPORTED). */
+#define CVAE_FOLD_CONV_K3S1_GRAD           7
+#define CVAE_FOLD_CONVT_K3S2_SUBPIXEL_GRAD 8
 int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
                       const float* const* beta, const float* const* mean, const float* const* var, const float* eps, float* const* w_out,
                       float* const* b_out, void* stream);
@@ -314,12 +322,34 @@ int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_
  *                        CVAE_E_UNSUPPORTED. */
 #define CVAE_CONV_S1_K3       0
 #define CVAE_CONV_S1_SUBPIXEL 1
+#define CVAE_CONV_S1_SUBPIXEL_T 2   /* cvae_conv_s1_bwd_data only */
 int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form);
 int cvae_conv_s1_pack_weights(int count, const float* const* w, void* const* packed, const int64_t* n, void* stream);
 int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                  int form, int dtype, int act, void* stream);
 int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act, void* stream);
 int cvae_latent_to_grid(const float* z, const float* W, const float* bias, void* out, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream);
+/* The decoder's input-gradient path (frozen weights, eval-mode BatchNorm; the same tiling, fixed summation order and batch-independent bits as the forward):
+ *   cvae_conv_s1_bwd_data     dx = (conv(g, w^T) + resid) * act'(gate), epilogue in fp32 before the one rounding; resid and gate optional (NULL), both of dx's
+ *                             shape and dtype; act'(gate) = gate > 0 ? 1 : slope of gate_act (CVAE_ACT_NONE / RELU / LEAKY02 / LEAKY001), read off the
+ *                             activation's OUTPUT.  dx [B][H][W][C].
+ *                             form CVAE_CONV_S1_K3:         input gradient of nn.Conv2d(C, C, 3, 1, 1), C in {32, 64, 128}; g [B][H][W][C];
+ *                             form CVAE_CONV_S1_SUBPIXEL_T: input gradient of nn.ConvTranspose2d(C, 16, 3, 2, 1, output_padding 1), C in {32, 16}; g [B][2H][2W][16].
+ *                             w: the backward matrix of cvae_fold_bn_conv's kinds CVAE_FOLD_*_GRAD in `dtype` (cvae_conv_s1_weight_elems(C, C, K3) resp.
+ *                             cvae_conv_s1_weight_elems(C, 16, SUBPIXEL_T) = 32 x 256 elements).
+ *   cvae_conv_s1_c1_bwd_data  input gradient of nn.Conv2d(16, 1, 3, 1, 1): g fp32 [B][1][H][W], w the fp32 weight [1][16][3][3] (rounded to bf16 in bf16 mode, as
+ *                             the forward reads it), dx [B][H][W][16] in `dtype` = conv^T(g) * act'(gate), gate optional, of dx's shape and dtype.
+ *   cvae_latent_to_grid_bwd   dz[b][k] = sum_{p, c} g[b][p][c] W[c P + p][k], fp32: g [B][P][C] in `dtype`, W the fp32 nn.Linear tensor, read ONCE per launch
+ *                             with 16-byte loads for B <= 16 rows.  Slabs of 256 rows of W per workgroup (a split that depends on C and P only), per-slab partial
+ *                             sums in `workspace` (cvae_latent_to_grid_bwd_workspace_bytes; CVAE_E_WORKSPACE below it), added in slab order by a second launch:
+ *                             no float atomics, and a row's bits do not depend on B.  Limits as cvae_latent_to_grid. */
+int cvae_conv_s1_bwd_data(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t C, int form,
+                          int dtype, int gate_act, void* stream);
+int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int gate_act,
+                             void* stream);
+size_t cvae_latent_to_grid_bwd_workspace_bytes(int64_t B, int64_t K, int64_t P, int64_t C);
+int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ---- The dense heads of CausalViTVAE, eval mode (csrc/heads.hip; vessel_analysis/00_core/models.py:225-250, 281-302) ------------------------------------------
  * One launch = one whole head: the logical concatenation of n_panels (1..3) fp32 row panels {ptr, width, row stride in elements} (torch.cat(dim=1), never
