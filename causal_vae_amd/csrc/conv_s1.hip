@@ -203,32 +203,30 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
         }
 }
 
-template <typename T, int CIN, int NT, int FORM>
-int conv_s1_launch(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int act, hipStream_t st) {
+// one launch of the template: the forward passes gate = nullptr, the backward (BWD) bias = nullptr; `act` is the backward's gate activation
+struct S1Args { const void *x, *w; const float* bias; const void *resid, *gate; void* y; int64_t B, H, W; int act; hipStream_t st; };
+template <typename T, int CIN, int NT, int FORM, bool BWD = false, int COUT_T = 0> int conv_s1_launch(const S1Args& a) {
     using G = S1Geom<T, CIN, FORM>;
-    auto kern = conv_s1_kernel<T, CIN, NT, FORM>;
+    auto kern = conv_s1_kernel<T, CIN, NT, FORM, BWD, COUT_T>;
     constexpr size_t LDS = ((size_t)(G::HR * G::HC + 1) * G::PITCH + (size_t)32 * NT * G::WPITCH) * sizeof(T);
     static_assert(LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
     // set on every launch: the attribute belongs to the current device's copy of the kernel, and a flag would be shared by devices and host threads
     if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
-    const dim3 grid((unsigned)((W + S1_TW - 1) / S1_TW), (unsigned)((H + S1_TH - 1) / S1_TH), (unsigned)B);
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)x, (const T*)w, bias, (const T*)resid, (T*)y, (int)H, (int)W, act, (const T*)nullptr);
+    const dim3 grid((unsigned)((a.W + S1_TW - 1) / S1_TW), (unsigned)((a.H + S1_TH - 1) / S1_TH), (unsigned)a.B);
+    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, a.st, (const T*)a.x, (const T*)a.w, a.bias, (const T*)a.resid, (T*)a.y, (int)a.H, (int)a.W, a.act, (const T*)a.gate);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
-
-template <typename T, int CIN, int NT, int FORM, int COUT_T>
-int conv_s1_bwd_launch(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int act, hipStream_t st) {
-    using G = S1Geom<T, CIN, FORM>;
-    auto kern = conv_s1_kernel<T, CIN, NT, FORM, true, COUT_T>;
-    constexpr size_t LDS = ((size_t)(G::HR * G::HC + 1) * G::PITCH + (size_t)32 * NT * G::WPITCH) * sizeof(T);
-    static_assert(LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
-    if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
-    const dim3 grid((unsigned)((W + S1_TW - 1) / S1_TW), (unsigned)((H + S1_TH - 1) / S1_TH), (unsigned)B);
-    hipLaunchKernelGGL(kern, grid, dim3(256), LDS, st, (const T*)g, (const T*)w, (const float*)nullptr, (const T*)resid, (T*)dx, (int)H, (int)W, act, (const T*)gate);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+// the K3 ladder: C = Cin = Cout in {32, 64, 128} (checked by the caller through cvae_conv_s1_weight_elems), one 32-row block of the matrix per 32 channels
+template <typename T, bool BWD> int conv_s1_k3(int64_t C, const S1Args& a) {
+    if (C == 32) return conv_s1_launch<T, 32, 1, CVAE_CONV_S1_K3, BWD>(a);
+    if (C == 64) return conv_s1_launch<T, 64, 2, CVAE_CONV_S1_K3, BWD>(a);
+    return conv_s1_launch<T, 128, 4, CVAE_CONV_S1_K3, BWD>(a);
 }
+// argument checks the entries share
+bool s1_dims_ok(int64_t B, int64_t H, int64_t W) { return B >= 0 && H > 0 && W > 0 && H <= 65535 * S1_TH && B <= 65535 && W <= ((int64_t)1 << 24); }
+bool c1_dims_ok(int64_t B, int64_t H, int64_t W) { return B >= 0 && H > 0 && W > 0 && H <= ((int64_t)1 << 24) && W <= ((int64_t)1 << 24); }
+bool s1_act_ok(int act) { return act == CVAE_ACT_NONE || act == CVAE_ACT_LEAKY02 || act == CVAE_ACT_LEAKY001 || act == CVAE_ACT_RELU; }
 
 // fp32 -> bf16 for a list of tensors in one launch (the packed weights of the bf16 decoder)
 #define S1_PACK_MAX 16
@@ -511,30 +509,25 @@ extern "C" int cvae_conv_s1_pack_weights(int count, const float* const* w, void*
 
 extern "C" int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                             int form, int dtype, int act, void* stream) {
-    if (B < 0 || H <= 0 || W <= 0 || H > 65535 * S1_TH || B > 65535 || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (!s1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL) return CVAE_E_UNSUPPORTED;
-    if (cvae_conv_s1_weight_elems(Cin, Cout, form) == 0) return CVAE_E_UNSUPPORTED;
-    if (act != CVAE_ACT_NONE && act != CVAE_ACT_LEAKY02 && act != CVAE_ACT_LEAKY001 && act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (cvae_conv_s1_weight_elems(Cin, Cout, form) == 0 || !s1_act_ok(act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!x || !w || !bias || !y) return CVAE_E_NULLPTR;
     if (!aligned16(x) || !aligned16(w) || !aligned16(bias) || !aligned16(y) || !aligned16(resid)) return CVAE_E_UNSUPPORTED;
-    const hipStream_t st = (hipStream_t)stream;
+    const S1Args a{x, w, bias, resid, nullptr, y, B, H, W, act, (hipStream_t)stream};
     return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
-        if (form == CVAE_CONV_S1_K3) {
-            if (Cin == 32) return conv_s1_launch<T, 32, 1, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
-            if (Cin == 64) return conv_s1_launch<T, 64, 2, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
-            return conv_s1_launch<T, 128, 4, CVAE_CONV_S1_K3>(x, w, bias, resid, y, B, H, W, act, st);
-        }
-        if (Cin == 32) return conv_s1_launch<T, 32, 2, CVAE_CONV_S1_SUBPIXEL>(x, w, bias, resid, y, B, H, W, act, st);
-        return conv_s1_launch<T, 16, 2, CVAE_CONV_S1_SUBPIXEL>(x, w, bias, resid, y, B, H, W, act, st);
+        if (form == CVAE_CONV_S1_K3) return conv_s1_k3<T, false>(Cin, a);
+        if (Cin == 32) return conv_s1_launch<T, 32, 2, CVAE_CONV_S1_SUBPIXEL>(a);
+        return conv_s1_launch<T, 16, 2, CVAE_CONV_S1_SUBPIXEL>(a);
     });
 }
 
 extern "C" int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act,
                                void* stream) {
-    if (B < 0 || H <= 0 || W <= 0 || H > ((int64_t)1 << 24) || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (!c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
@@ -543,8 +536,10 @@ extern "C" int cvae_conv_s1_c1(const void* x, const float* w, const float* bias,
     const int64_t total = B * H * ((W + 3) >> 2), blocks = (total + 255) / 256;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL(conv_s1_c1_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16*)x, w, bias, y, B, (int)H, (int)W, act);
-    else hipLaunchKernelGGL(conv_s1_c1_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, w, bias, y, B, (int)H, (int)W, act);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(conv_s1_c1_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, w, bias, y, B, (int)H, (int)W, act);
+    });
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
@@ -559,42 +554,39 @@ extern "C" int cvae_latent_to_grid(const float* z, const float* W, const float* 
     const int64_t blocks = (P * (C >> 5) + 3) / 4;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL(latent_to_grid_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (bf16*)out, (int)B, (int)K, P, (int)C);
-    else hipLaunchKernelGGL(latent_to_grid_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (float*)out, (int)B, (int)K, P, (int)C);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(latent_to_grid_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (T*)out, (int)B, (int)K, P, (int)C);
+    });
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
 
 extern "C" int cvae_conv_s1_bwd_data(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t C, int form,
                                      int dtype, int gate_act, void* stream) {
-    if (B < 0 || H <= 0 || W <= 0 || H > 65535 * S1_TH || B > 65535 || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (!s1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL_T) return CVAE_E_UNSUPPORTED;
-    if (cvae_conv_s1_weight_elems(C, form == CVAE_CONV_S1_K3 ? C : 16, form) == 0) return CVAE_E_UNSUPPORTED;
-    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_LEAKY02 && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (cvae_conv_s1_weight_elems(C, form == CVAE_CONV_S1_K3 ? C : 16, form) == 0 || !s1_act_ok(gate_act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!g || !w || !dx || (gate_act != CVAE_ACT_NONE && !gate)) return CVAE_E_NULLPTR;
     if (!aligned16(g) || !aligned16(w) || !aligned16(dx) || !aligned16(resid) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
     if (gate_act == CVAE_ACT_NONE) gate = nullptr;
-    const hipStream_t st = (hipStream_t)stream;
+    const S1Args a{g, w, nullptr, resid, gate, dx, B, H, W, gate_act, (hipStream_t)stream};
     return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
-        if (form == CVAE_CONV_S1_K3) {
-            if (C == 32) return conv_s1_bwd_launch<T, 32, 1, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
-            if (C == 64) return conv_s1_bwd_launch<T, 64, 2, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
-            return conv_s1_bwd_launch<T, 128, 4, CVAE_CONV_S1_K3, 0>(g, w, resid, gate, dx, B, H, W, gate_act, st);
-        }
-        if (C == 32) return conv_s1_bwd_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, 32>(g, w, resid, gate, dx, B, H, W, gate_act, st);
-        return conv_s1_bwd_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, 16>(g, w, resid, gate, dx, B, H, W, gate_act, st);
+        if (form == CVAE_CONV_S1_K3) return conv_s1_k3<T, true>(C, a);
+        if (C == 32) return conv_s1_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, true, 32>(a);
+        return conv_s1_launch<T, 64, 1, CVAE_CONV_S1_SUBPIXEL_T, true, 16>(a);
     });
 }
 
 extern "C" int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int gate_act,
                                         void* stream) {
-    if (B < 0 || H <= 0 || W <= 0 || H > ((int64_t)1 << 24) || W > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+    if (!c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
-    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_LEAKY02 && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_RELU) return CVAE_E_UNSUPPORTED;
+    if (!s1_act_ok(gate_act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!g || !w || !dx || (gate_act != CVAE_ACT_NONE && !gate)) return CVAE_E_NULLPTR;
     if (!aligned16(dx) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
@@ -602,8 +594,10 @@ extern "C" int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const vo
     const int64_t blocks = (B * H * W + 255) / 256;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<bf16>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const bf16*)gate, (bf16*)dx, B, (int)H, (int)W, gate_act);
-    else hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const float*)gate, (float*)dx, B, (int)H, (int)W, gate_act);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const T*)gate, (T*)dx, B, (int)H, (int)W, gate_act);
+    });
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
@@ -628,14 +622,14 @@ extern "C" int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz,
     const size_t lds = ((size_t)B * L2GB_ROWS + (size_t)RP * B * K) * sizeof(float);         // at most 16 KB + 64 KB
     const hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    if (dtype == CVAE_BF16) {
-        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
-        hipLaunchKernelGGL(l2g_bwd_kernel<bf16>, dim3((unsigned)slabs), dim3(256), lds, st, (const bf16*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
-    } else {
-        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
-        hipLaunchKernelGGL(l2g_bwd_kernel<float>, dim3((unsigned)slabs), dim3(256), lds, st, (const float*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
-    }
-    CVAE_CHECK_LAUNCH();
+    const int rc = with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
+        hipLaunchKernelGGL(l2g_bwd_kernel<T>, dim3((unsigned)slabs), dim3(256), lds, st, (const T*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
+        CVAE_CHECK_LAUNCH();
+        return CVAE_OK;
+    });
+    if (rc != CVAE_OK) return rc;
     const int n = (int)(B * K);
     hipLaunchKernelGGL(l2g_bwd_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)part, dz, n, (int)slabs);
     CVAE_CHECK_LAUNCH();

@@ -2037,6 +2037,24 @@ def conv_s1_pack_weights(mats):
     return outs
 
 
+def _conv_s1_operands(what, x, wmat, form, forms, geom, **like_out):
+    """The operand checks conv_s1 and conv_s1_bwd_data share: x a contiguous channels-last [B, H, W, C] tensor and form one of `forms`; wmat the matrix of
+    the layer geom(B, H, W, C) -> (Cin, Cout, output shape) in x's dtype, contiguous, cvae_conv_s1_weight_elems long; every like_out tensor (name = tensor
+    or None) contiguous, of the output's shape and x's dtype.  Returns geom's triple."""
+    if x.dim() != 4 or not x.is_contiguous() or form not in forms:
+        raise L.CvaeError(f"{what}: a contiguous channels-last [B, H, W, C] tensor expected, got {tuple(x.shape)} in form {form}")
+    cin, cout, oshape = geom(*x.shape)
+    n = lib.cvae_conv_s1_weight_elems(cin, cout, form)
+    if n == 0:
+        raise L.CvaeError(f"{what}: {cin} -> {cout} channels in form {form}: {L.strerror(-3)}")
+    if wmat.dtype != x.dtype or wmat.numel() != n or not wmat.is_contiguous():
+        raise L.CvaeError(f"{what}: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {cin} -> {cout} channels in {x.dtype} ({n} elements)")
+    for name, t in like_out.items():
+        if t is not None and (tuple(t.shape) != oshape or t.dtype != x.dtype or not t.is_contiguous()):
+            raise L.CvaeError(f"{what}: the {name} must be a contiguous {oshape} {x.dtype} tensor")
+    return cin, cout, oshape
+
+
 def conv_s1(x, wmat, bias, form, act=None, resid=None):
     """act(conv(x) + bias + resid) on a channels-last [B, H, W, Cin] tensor (cvae_conv_s1; fp32 or bf16 = the arithmetic mode).  form CONV_S1_K3:
     nn.Conv2d(C, C, 3, 1, 1), C in {32, 64, 128} -> [B, H, W, C]; CONV_S1_SUBPIXEL: nn.ConvTranspose2d(Cin, 16, 3, 2, 1, output_padding=1), Cin in {32, 16}
@@ -2044,18 +2062,12 @@ def conv_s1(x, wmat, bias, form, act=None, resid=None):
     resid (optional): the output's shape and dtype, added in fp32 before the activation."""
     L.require_gpu(x, wmat, bias, resid)
     _forward_only("conv_s1", x, wmat, bias, resid)
-    if x.dim() != 4 or not x.is_contiguous() or form not in (CONV_S1_K3, CONV_S1_SUBPIXEL):
-        raise L.CvaeError(f"conv_s1: a contiguous channels-last [B, H, W, C] tensor expected, got {tuple(x.shape)}")
-    B, H, W, Cin = x.shape
-    Cout = bias.numel()
-    n = lib.cvae_conv_s1_weight_elems(Cin, Cout, form)
-    if n == 0:
-        raise L.CvaeError(f"conv_s1: {Cin} -> {Cout} channels in form {form}: {L.strerror(-3)}")
-    if wmat.dtype != x.dtype or wmat.numel() != n or not wmat.is_contiguous() or bias.dtype != torch.float32:
-        raise L.CvaeError(f"conv_s1: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {Cin} -> {Cout} channels in {x.dtype} ({n} elements)")
-    oshape = (B, H, W, Cout) if form == CONV_S1_K3 else (B, 2 * H, 2 * W, Cout)
-    if resid is not None and (tuple(resid.shape) != oshape or resid.dtype != x.dtype or not resid.is_contiguous()):
-        raise L.CvaeError(f"conv_s1: the residual must be a contiguous {oshape} {x.dtype} tensor")
+    up = 2 if form == CONV_S1_SUBPIXEL else 1
+    Cin, Cout, oshape = _conv_s1_operands("conv_s1", x, wmat, form, (CONV_S1_K3, CONV_S1_SUBPIXEL),
+                                          lambda B, H, W, C: (C, bias.numel(), (B, up * H, up * W, bias.numel())), residual=resid)
+    if bias.dtype != torch.float32:
+        raise L.CvaeError(f"conv_s1: an fp32 bias expected, got {bias.dtype}")
+    B, H, W, _C = x.shape
     y = _empty(oshape, x.dtype, x)
     check(lib.cvae_conv_s1(ptr(x), ptr(wmat), ptr(bias.detach().contiguous()), ptr(resid), ptr(y), B, H, W, Cin, Cout, form, L.dtype_code(x.dtype), L.act_code(act),
                            stream()), "conv_s1")
@@ -2076,36 +2088,25 @@ def conv_s1_c1(x, weight, bias, act=None):
     return y
 
 
-def conv_s1_bwd_data(g, wmat, form, resid=None, gate=None, gate_act=None):
+def conv_s1_bwd_data(g, wmat, form, cin=None, resid=None, gate=None, gate_act=None):
     """(conv(g, w^T) + resid) * act'(gate): the input gradient of conv_s1's layer through a frozen weight (cvae_conv_s1_bwd_data), channels-last, fp32 or bf16.
-    form CONV_S1_K3: g [B, H, W, C] -> [B, H, W, C]; CONV_S1_SUBPIXEL_T (the narrow transposed convs): g [B, 2H, 2W, 16] -> [B, H, W, Cin], Cin = the
-    second argument of the pair (wmat, Cin) passed as wmat.  wmat: the third element fold_bn_conv returns for a FOLD_*_GRAD entry, in g's dtype.  resid / gate
-    (optional): the result's shape and dtype; gate is the OUTPUT of the activation whose derivative is applied (LeakyReLU keeps the sign): gate > 0 ? 1 : slope."""
-    cin = None
-    if isinstance(wmat, tuple):
-        wmat, cin = wmat
+    form CONV_S1_K3: g [B, H, W, C] -> [B, H, W, C] (no cin: it is C); CONV_S1_SUBPIXEL_T (the narrow transposed convs): g [B, 2H, 2W, 16] -> [B, H, W, cin],
+    cin = the layer's input channels (32 or 16: the matrix has 32 rows either way).  wmat: the third element fold_bn_conv returns for a FOLD_*_GRAD entry, in g's
+    dtype.  resid / gate (optional): the result's shape and dtype; gate is the OUTPUT of the activation whose derivative is applied (LeakyReLU keeps the sign):
+    gate > 0 ? 1 : slope."""
     L.require_gpu(g, wmat, resid, gate)
     _forward_only("conv_s1_bwd_data", g, wmat, resid, gate)
-    if g.dim() != 4 or not g.is_contiguous() or form not in (CONV_S1_K3, CONV_S1_SUBPIXEL_T) or (form == CONV_S1_SUBPIXEL_T) != (cin is not None):
-        raise L.CvaeError(f"conv_s1_bwd_data: a contiguous channels-last [B, H, W, C] gradient expected, got {tuple(g.shape)} in form {form}")
-    B, H, W, Cg = g.shape
-    if form == CONV_S1_SUBPIXEL_T:
-        if Cg != 16 or H % 2 or W % 2:
-            raise L.CvaeError(f"conv_s1_bwd_data: the sub-pixel form takes a [B, 2H, 2W, 16] gradient, got {tuple(g.shape)}")
-        H, W, C = H // 2, W // 2, int(cin)
-    else:
-        C = Cg
-    n = lib.cvae_conv_s1_weight_elems(C, C if form == CONV_S1_K3 else 16, form)
-    if n == 0:
-        raise L.CvaeError(f"conv_s1_bwd_data: {C} channels in form {form}: {L.strerror(-3)}")
-    if wmat.dtype != g.dtype or wmat.numel() != n or not wmat.is_contiguous():
-        raise L.CvaeError(f"conv_s1_bwd_data: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {C} channels in {g.dtype} ({n} elements)")
-    oshape = (B, H, W, C)
-    for name, t in (("residual", resid), ("gate", gate)):
-        if t is not None and (tuple(t.shape) != oshape or t.dtype != g.dtype or not t.is_contiguous()):
-            raise L.CvaeError(f"conv_s1_bwd_data: the {name} must be a contiguous {oshape} {g.dtype} tensor")
+    sub = form == CONV_S1_SUBPIXEL_T
+    if sub != (cin is not None):
+        raise L.CvaeError(f"conv_s1_bwd_data: cin goes with form CONV_S1_SUBPIXEL_T and with no other, got cin={cin} in form {form}")
+    C, _Cout, oshape = _conv_s1_operands("conv_s1_bwd_data", g, wmat, form, (CONV_S1_K3, CONV_S1_SUBPIXEL_T),
+                                         lambda B, H, W, Cg: (int(cin), 16, (B, H // 2, W // 2, int(cin))) if sub else (Cg, Cg, (B, H, W, Cg)),
+                                         residual=resid, gate=gate)
+    if sub and (g.shape[3] != 16 or g.shape[1] % 2 or g.shape[2] % 2):
+        raise L.CvaeError(f"conv_s1_bwd_data: the sub-pixel form takes a [B, 2H, 2W, 16] gradient, got {tuple(g.shape)}")
     if (gate is None) != (gate_act in (None, "none")):
         raise L.CvaeError("conv_s1_bwd_data: gate and gate_act come together")
+    B, H, W, _C = oshape
     dx = _empty(oshape, g.dtype, g)
     check(lib.cvae_conv_s1_bwd_data(ptr(g), ptr(wmat), ptr(resid), ptr(gate), ptr(dx), B, H, W, C, form, L.dtype_code(g.dtype), L.act_code(gate_act), stream()),
           "conv_s1_bwd_data")

@@ -26,6 +26,8 @@ decode_with_grad / decode_vjp add the gradient of that image with respect to z t
 decode's launches (the fold also writes the backward matrices) and keeps five gate activations and the three ResBlock inner activations; the backward is
 cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -165,6 +167,12 @@ class _ResBlock(nn.Module):
 
 
 DECODER_CHANNELS = (128, 64, 32, 16, 16)     # outputs of the five transposed convs; a ResBlock follows each of the first three
+# One decoder stage: kind "up" (wide transposed conv, cvae_conv_up), "sub" (narrow one, sub-pixel conv_s1) or "res" (ResBlock); layers = its (conv, bn)
+# pairs; fold = their positions in the fold table; gates = its output is a LeakyReLU(0.01) output: the gate in the backward of whatever reads it.
+_Stage = namedtuple("_Stage", "kind layers fold gates")
+# What _decode_walk keeps of a stage for _decode_backward: gate_in (the stage's input when the stage before it gates, else None), inner (a ResBlock's inner
+# activation), mats (the backward matrix of every GEMM layer, in layer order), k4 (an "up" stage's folded k4 weight).
+_Step = namedtuple("_Step", "stage gate_in inner mats k4")
 
 
 class ViTVAE(ViTVAEEncoder):
@@ -183,67 +191,80 @@ class ViTVAE(ViTVAEEncoder):
         self.decoder = nn.Sequential(*dec)
 
     def _decoder_plan(self):
-        """[(kind, modules)] in execution order: ("up", convT, bn) / ("sub", convT, bn) / ("res", block) and the output conv last."""
-        mods, plan, i = list(self.decoder), [], 0
+        """([_Stage] in execution order, the output conv).  A stage's `fold` holds the positions of its layers in the fold table: the one place they are counted."""
+        mods, plan, i, n = list(self.decoder), [], 0, 0
         while i < len(mods) - 1:
             if isinstance(mods[i], _ResBlock):
-                plan.append(("res", mods[i]))
-                i += 1
+                c = mods[i].conv
+                kind, layers, step = "res", ((c[0], c[1]), (c[3], c[4])), 1
             else:
-                plan.append(("up" if mods[i].out_channels % 32 == 0 else "sub", mods[i], mods[i + 1]))
-                i += 3
+                kind, layers, step = "up" if mods[i].out_channels % 32 == 0 else "sub", ((mods[i], mods[i + 1]),), 3
+            plan.append(_Stage(kind, layers, tuple(range(n, n + len(layers))), kind != "res"))
+            i, n = i + step, n + len(layers)
         return plan, mods[-1]
 
-    @torch.no_grad()
-    def decode(self, z):
-        """ViTVAE.decode (vit_backbone.py:186-193) in eval mode: [B, latent_dim] fp32 -> [B, 1, H, W] fp32."""
-        return self._decode(z)
+    @staticmethod
+    def _fold_table(plan, grad):
+        """ops.fold_bn_conv's entries for the plan; grad: the _GRAD kinds (the same forward matrices, bit for bit, plus the backward ones from the same launch)."""
+        kinds = {"up": ops.FOLD_CONVT_K3S2, "sub": ops.FOLD_CONVT_K3S2_SUBPIXEL_GRAD if grad else ops.FOLD_CONVT_K3S2_SUBPIXEL,
+                 "res": ops.FOLD_CONV_K3S1_GRAD if grad else ops.FOLD_CONV_K3S1}
+        return [(conv.weight, kinds[st.kind], conv.bias, bn) for st in plan for conv, bn in st.layers]
 
-    @torch.no_grad()
-    def _decode(self, z, collect=None):
-        """collect (a dict, for tests): receives `grid` (decoder_input's output, channels-last [B, gh, gw, 256]) and `stages` (the channels-last
-        activation after each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order)."""
+    def _check_latent(self, z, what="the decoder runs inference only"):
         if self.training:
-            raise RuntimeError("ViTVAE: put the model in eval mode first (model.eval()): batch-statistics BatchNorm2d is not implemented, the decoder "
-                               "runs inference only")
+            raise RuntimeError(f"ViTVAE: put the model in eval mode first (model.eval()): batch-statistics BatchNorm2d is not implemented, {what}")
         if z.dim() != 2 or z.shape[1] != self.latent_dim or z.dtype != torch.float32:
             raise CvaeError(f"ViTVAE.decode expects a float32 [B, {self.latent_dim}] batch, got {tuple(z.shape)} {z.dtype}")
+
+    @torch.no_grad()
+    def decode(self, z, collect=None):
+        """ViTVAE.decode (vit_backbone.py:186-193) in eval mode: [B, latent_dim] fp32 -> [B, 1, H, W] fp32.  collect: as _decode_walk."""
+        self._check_latent(z)
         require_gpu(z, self.decoder_input.weight)
+        return self._decode_walk(z, False, collect)[0]
+
+    @torch.no_grad()
+    def _decode_walk(self, z, save, collect=None):
+        """The decoder's launches -> (image, saved).  save=False: the forward fold kinds, in bf16 one pack of the 8 GEMM matrices, saved = None.  save=True: the
+        same launches with the fold's _GRAD kinds (one pack of 16: forward and backward matrices) and saved = ([_Step per stage], the output conv, its gate)
+        for _decode_backward: DESIGN §13's set (the gates are the outputs of stages 0, 2, 4, 6 and 7; a ResBlock sum and the grid are no gates).
+        collect (a dict, for tests): receives `grid` (decoder_input's output, channels-last [B, gh, gw, 256]), `stages` (the channels-last activation after
+        each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order) and `res_inner` (the three ResBlock inner activations)."""
         dt = self.compute_dtype
         plan, out_conv = self._decoder_plan()
-        table = []
-        for st in plan:
-            if st[0] == "res":
-                c = st[1].conv
-                table += [(c[0].weight, ops.FOLD_CONV_K3S1, c[0].bias, c[1]), (c[3].weight, ops.FOLD_CONV_K3S1, c[3].bias, c[4])]
-            else:
-                table.append((st[1].weight, ops.FOLD_CONVT_K3S2 if st[0] == "up" else ops.FOLD_CONVT_K3S2_SUBPIXEL, st[1].bias, st[2]))
-        folded = ops.fold_bn_conv(table)                               # one launch, on every call: parameters may have been rewritten
-        gemm = [i for i, e in enumerate(table) if e[1] != ops.FOLD_CONVT_K3S2]
-        mats = {i: folded[i][0] for i in gemm}
-        if dt == torch.bfloat16:
-            mats = dict(zip(gemm, ops.conv_s1_pack_weights([folded[i][0] for i in gemm])))
+        folded = ops.fold_bn_conv(self._fold_table(plan, save))        # one launch, on every call: parameters may have been rewritten
+        gemm = [k for st in plan if st.kind != "up" for k in st.fold]
+        fwd, bwd = [folded[k][0] for k in gemm], [folded[k][2] for k in gemm] if save else []
+        if dt == torch.bfloat16:                                       # one launch for all of them
+            packed = ops.conv_s1_pack_weights(fwd + bwd)
+            fwd, bwd = packed[:len(gemm)], packed[len(gemm):]
+        mats, bmats = dict(zip(gemm, fwd)), dict(zip(gemm, bwd))
         B = z.shape[0]
         h = ops.latent_to_grid(z, self.decoder_input.weight, self.decoder_input.bias, self.embed_dim, dt).view(B, self.grid_h, self.grid_w, self.embed_dim)
         if collect is not None:
-            collect["grid"], collect["stages"] = h, []
-        k = 0
+            collect["grid"], collect["stages"], collect["res_inner"] = h, [], []
+        steps, gate = [], None                                         # gate: the stage's input when that is a LeakyReLU(0.01) output
         for st in plan:
-            if st[0] == "up":
-                w, b = folded[k]
+            y = k4 = None
+            if st.kind == "up":
+                k4, b = folded[st.fold[0]]
                 _B, hh, ww, c = h.shape
-                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), w, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, w.shape[1])
-                k += 1
-            elif st[0] == "sub":
+                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), k4, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, k4.shape[1])
+            elif st.kind == "sub":
+                k, = st.fold
                 h = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, "leaky001")
-                k += 1
             else:
-                y = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_K3, "leaky02")
-                h = ops.conv_s1(y, mats[k + 1], folded[k + 1][1], ops.CONV_S1_K3, None, resid=h)
-                k += 2
+                k0, k1 = st.fold
+                y = ops.conv_s1(h, mats[k0], folded[k0][1], ops.CONV_S1_K3, "leaky02")
+                h = ops.conv_s1(y, mats[k1], folded[k1][1], ops.CONV_S1_K3, None, resid=h)
+                if collect is not None:
+                    collect["res_inner"].append(y)
+            if save:
+                steps.append(_Step(st, gate, y, [bmats[k] for k in st.fold if k in bmats], k4))
+            gate = h if st.gates else None
             if collect is not None:
                 collect["stages"].append(h)
-        return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias)
+        return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias), ((steps, out_conv, gate) if save else None)
 
     # ---- the gradient with respect to the latent (frozen decoder, eval mode) -----------------------------------------------------
     def freeze_decoder(self):
@@ -253,89 +274,30 @@ class ViTVAE(ViTVAEEncoder):
         return self
 
     def _check_grad_path(self, z):
-        if self.training:
-            raise RuntimeError("ViTVAE: put the model in eval mode first (model.eval()): batch-statistics BatchNorm2d is not implemented, the decoder's "
-                               "gradient path runs through eval-mode BatchNorm only")
-        if z.dim() != 2 or z.shape[1] != self.latent_dim or z.dtype != torch.float32:
-            raise CvaeError(f"ViTVAE.decode expects a float32 [B, {self.latent_dim}] batch, got {tuple(z.shape)} {z.dtype}")
+        self._check_latent(z, "the decoder's gradient path runs through eval-mode BatchNorm only")
         live = sorted(f"{root}.{k}" for root in ("decoder_input", "decoder") for k, p in getattr(self, root).named_parameters() if p.requires_grad)
         if live:
             raise CvaeError("ViTVAE.decode_with_grad returns the gradient with respect to z only, through a frozen decoder: these parameters ask for a gradient "
                             f"that would silently stay None: {live} (call model.freeze_decoder())")
         require_gpu(z, self.decoder_input.weight)
 
-    def _decode_saving(self, z, collect=None):
-        """_decode's launches with the fold's _GRAD kinds (the same forward matrices, bit for bit, plus the backward ones from the same launch).  Returns
-        (image, saved): saved = dict(stages = {i: gate activation h_i for i in 0, 2, 4, 6, 7}, inner = the three ResBlock inner activations, mats = the
-        backward matrix per GEMM table entry, k4 = the folded k4 weight per wide transposed conv).  collect: as _decode, and `res_inner`."""
-        dt = self.compute_dtype
-        plan, out_conv = self._decoder_plan()
-        table = []
-        for st in plan:
-            if st[0] == "res":
-                c = st[1].conv
-                table += [(c[0].weight, ops.FOLD_CONV_K3S1_GRAD, c[0].bias, c[1]), (c[3].weight, ops.FOLD_CONV_K3S1_GRAD, c[3].bias, c[4])]
-            else:
-                table.append((st[1].weight, ops.FOLD_CONVT_K3S2 if st[0] == "up" else ops.FOLD_CONVT_K3S2_SUBPIXEL_GRAD, st[1].bias, st[2]))
-        folded = ops.fold_bn_conv(table)
-        gemm = [i for i, e in enumerate(table) if e[1] != ops.FOLD_CONVT_K3S2]
-        mats, bmats = {i: folded[i][0] for i in gemm}, {i: folded[i][2] for i in gemm}
-        if dt == torch.bfloat16:                                       # one launch for the forward and the backward matrices (16 of them)
-            packed = ops.conv_s1_pack_weights([folded[i][0] for i in gemm] + [folded[i][2] for i in gemm])
-            mats, bmats = dict(zip(gemm, packed[:len(gemm)])), dict(zip(gemm, packed[len(gemm):]))
-        B = z.shape[0]
-        h = ops.latent_to_grid(z, self.decoder_input.weight, self.decoder_input.bias, self.embed_dim, dt).view(B, self.grid_h, self.grid_w, self.embed_dim)
-        if collect is not None:
-            collect["grid"], collect["stages"], collect["res_inner"] = h, [], []
-        saved = {"stages": {}, "inner": [], "mats": bmats, "k4": {}}
-        k = 0
-        for i, st in enumerate(plan):
-            if st[0] == "up":
-                w, b = folded[k]
-                _B, hh, ww, c = h.shape
-                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), w, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, w.shape[1])
-                saved["k4"][k] = w
-                k += 1
-            elif st[0] == "sub":
-                h = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, "leaky001")
-                k += 1
-            else:
-                y = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_K3, "leaky02")
-                h = ops.conv_s1(y, mats[k + 1], folded[k + 1][1], ops.CONV_S1_K3, None, resid=h)
-                saved["inner"].append(y)
-                if collect is not None:
-                    collect["res_inner"].append(y)
-                k += 2
-            if st[0] != "res":
-                saved["stages"][i] = h
-            if collect is not None:
-                collect["stages"].append(h)
-        return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias), saved
-
     def _decode_backward(self, saved, g_img):
-        """dz [B, latent_dim] fp32 from the image cotangent [B, 1, H, W] fp32: the chain of DESIGN §13.  `g` is the gradient with respect to a transposed
-        conv's PRE-activation (the producing epilogue applied leaky001' from the saved output) or to a ResBlock's output; no activation-backward launch."""
-        plan, out_conv = self._decoder_plan()
+        """dz [B, latent_dim] fp32 from the image cotangent [B, 1, H, W] fp32: the chain of DESIGN §13, _decode_walk's steps in reverse.  `g` is the gradient
+        with respect to a transposed conv's PRE-activation (the producing epilogue applied leaky001' from the saved output) or to a ResBlock's output; no
+        activation-backward launch."""
+        steps, out_conv, out_gate = saved
         dt = self.compute_dtype
-        stages, mats = saved["stages"], saved["mats"]
         B = g_img.shape[0]
-        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, stages[len(plan) - 1], "leaky001", dt)
-        k = sum(2 if st[0] == "res" else 1 for st in plan)
-        inner = list(saved["inner"])
-        for i in range(len(plan) - 1, -1, -1):
-            st = plan[i]
-            gate = stages.get(i - 1)                                    # the stage's input when it is a LeakyReLU(0.01) output; a ResBlock sum / the grid: None
-            act = "leaky001" if gate is not None else None
-            if st[0] == "sub":
-                k -= 1
-                g = ops.conv_s1_bwd_data(g, (mats[k], st[1].in_channels), ops.CONV_S1_SUBPIXEL_T, gate=gate, gate_act=act)
-            elif st[0] == "res":
-                k -= 2
-                t = ops.conv_s1_bwd_data(g, mats[k + 1], ops.CONV_S1_K3, gate=inner.pop(), gate_act="leaky02")
-                g = ops.conv_s1_bwd_data(t, mats[k], ops.CONV_S1_K3, resid=g, gate=gate, gate_act=act)
+        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, out_gate, "leaky001", dt)
+        for s in reversed(steps):
+            act = "leaky001" if s.gate_in is not None else None
+            if s.stage.kind == "sub":
+                g = ops.conv_s1_bwd_data(g, s.mats[0], ops.CONV_S1_SUBPIXEL_T, cin=s.stage.layers[0][0].in_channels, gate=s.gate_in, gate_act=act)
+            elif s.stage.kind == "res":
+                t = ops.conv_s1_bwd_data(g, s.mats[1], ops.CONV_S1_K3, gate=s.inner, gate_act="leaky02")
+                g = ops.conv_s1_bwd_data(t, s.mats[0], ops.CONV_S1_K3, resid=g, gate=s.gate_in, gate_act=act)
             else:
-                k -= 1
-                w = saved["k4"][k]
+                w = s.k4
                 _B, hh, ww, c = g.shape
                 g = ops._conv_down(g.view(B, 1, hh, ww, c), ops.pack_weight(w, 2, False, dt), None, None, w.shape[0], 2, None).view(B, hh // 2, ww // 2, w.shape[0])
         return ops.latent_to_grid_bwd(g.view(B, self.grid_h * self.grid_w, self.embed_dim), self.decoder_input.weight)
@@ -356,7 +318,7 @@ class ViTVAE(ViTVAEEncoder):
         require_gpu(grad_image)
         if z.shape[0] == 0:
             return torch.zeros_like(z)
-        _image, saved = self._decode_saving(z.detach())
+        _image, saved = self._decode_walk(z.detach(), True)
         return self._decode_backward(saved, grad_image.contiguous())
 
     def reparameterize(self, mu, log_var):
@@ -381,7 +343,7 @@ class _DecodeWithGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, model, collect):
-        image, saved = model._decode_saving(z.detach(), collect)
+        image, saved = model._decode_walk(z.detach(), True, collect)
         ctx.model, ctx.saved = model, saved                            # activations and folded matrices of this call: private to the node, freed with it
         return image
 

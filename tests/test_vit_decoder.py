@@ -186,7 +186,7 @@ def build(golden, name, dtype=F32):
 
 def collected(model, z):
     col = {}
-    image = model._decode(z.to(DEV), collect=col)
+    image, _saved = model._decode_walk(z.to(DEV), save=False, collect=col)
     got = {"grid": col["grid"].permute(0, 3, 1, 2), "image": image}
     got.update({f"stage{i}": s.permute(0, 3, 1, 2) for i, s in enumerate(col["stages"])})
     assert len(col["stages"]) == 8

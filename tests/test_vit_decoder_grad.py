@@ -90,7 +90,7 @@ def test_conv_s1_bwd_subpixel_t_against_float64(dtype, Cin, B, H, W):
     gate = gate_like(B, Cin, H, W, seed=33)
     mat = grad_matrix(w, o.FOLD_CONVT_K3S2_SUBPIXEL_GRAD, dtype)
     for act in ("leaky001", None):
-        got = o.conv_s1_bwd_data(to_cl(g, dtype), (mat, Cin), o.CONV_S1_SUBPIXEL_T, gate=to_cl(gate, dtype) if act else None, gate_act=act)
+        got = o.conv_s1_bwd_data(to_cl(g, dtype), mat, o.CONV_S1_SUBPIXEL_T, cin=Cin, gate=to_cl(gate, dtype) if act else None, gate_act=act)
         fac = torch.where(gate > 0, 1.0, SLOPE[act]).double() if act else 1.0
         ref = F.conv2d(g.double(), w.double(), stride=2, padding=1) * fac
         terms = F.conv2d(g.double().abs(), w.double().abs(), stride=2, padding=1) * fac
@@ -260,11 +260,29 @@ def test_decode_with_grad_bits(golden, dtype):
     assert image.requires_grad and torch.equal(image, r["image"])
     image.backward(cot)
     assert torch.equal(zg.grad, r["dz"]) and torch.equal(model.decode_vjp(zd, cot), r["dz"])
-    _img, saved = model._decode_saving(zd)
-    assert sorted(saved["stages"]) == [0, 2, 4, 6, 7] and len(saved["inner"]) == 3 and len(saved["mats"]) == 8 and len(saved["k4"]) == 3
+    _img, (steps, _out_conv, out_gate) = model._decode_walk(zd, save=True)
+    gates = [s.gate_in for s in steps[1:]] + [out_gate]                  # entry i: the output of stage i where something downstream is gated by it
+    assert [i for i, t in enumerate(gates) if t is not None] == [0, 2, 4, 6, 7] and steps[0].gate_in is None
+    assert sum(s.inner is not None for s in steps) == 3 and sum(len(s.mats) for s in steps) == 8 and sum(s.k4 is not None for s in steps) == 3
     with pytest.raises(RuntimeError):
         torch.autograd.grad(model.decode_with_grad(zg).sum(), zg, create_graph=True)[0].sum().backward()      # once differentiable
     assert model.decode_vjp(zd[:0], cot[:0]).shape == (0, 128)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_decode_and_decode_with_grad_agree_at_every_stage(golden, dtype):
+    """One walk issues both: the grid, all 8 stage activations and the image of decode and of decode_with_grad are the same bits, not the image alone."""
+    r = whole(golden, CASES[0], dtype, 2)
+    model, zd = r["model"], r["z"].to(DEV)
+    assert CASES[0] == "vitvae_dec_64x96" and zd.shape[0] == 2 and model.compute_dtype == dtype
+    plain, grad = {}, {}
+    image = model.decode(zd, collect=plain)
+    image_g = model.decode_with_grad(zd, collect=grad)
+    assert len(plain["stages"]) == 8 and len(grad["stages"]) == 8
+    assert torch.equal(plain["grid"], grad["grid"])
+    for i, (a, b) in enumerate(zip(plain["stages"], grad["stages"])):
+        assert torch.equal(a, b), i
+    assert torch.equal(image, image_g)
 
 
 def test_row_of_a_batch_of_four_equals_the_row_alone(golden):

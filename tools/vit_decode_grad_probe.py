@@ -105,7 +105,7 @@ def main():
         for B in (1, 8):
             z, cot = rnd(B, a.latent), rnd(B, 1, 768, 1280)
             with torch.no_grad():
-                _img, saved = model._decode_saving(z)
+                _img, saved = model._decode_walk(z, save=True)
                 fns = [lambda: model.decode(z), lambda: model._decode_backward(saved, cot)]
                 if a.no_eager:
                     r = interleaved(fns, a.reps, a.warmup)
