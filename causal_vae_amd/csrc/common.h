@@ -162,6 +162,18 @@ __device__ __forceinline__ unsigned mask_byte_of(const float (&v)[8]) {
     for (int q = 0; q < 8; ++q) b |= (v[q] > 0.f ? 1u : 0u) << q;
     return b;
 }
+// ---- epilogue of a 32x32 MFMA whose A operand was the WEIGHT fragment: D rows are output channels, D columns are positions.  Lane (r, h) holds, for
+// position r, channels (e & 3) + 8 (e >> 2) + 4 h of the 32-channel block in acc[e].  Two v_permlane32_swap per register pair regroup them so that the lane
+// owns two 8-channel pieces, v[j] = channels 16 j + 8 h .. + 7 (float v[2][8]): each ONE 16-byte (bf16) store and ONE 16-byte mask load instead of eight
+// 2-byte ones.  Every lane of the wave must take part.  A macro, not a function: every function form tried (accumulator by reference, by value) moved
+// instructions in the epilogues that use it.
+#define REGROUP_D32(acc, v)                                                                                                                      \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                                                           \
+        const auto lo_ = __builtin_amdgcn_permlane32_swap(__float_as_uint((acc)[i_]), __float_as_uint((acc)[4 + i_]), false, false);              \
+        const auto hi_ = __builtin_amdgcn_permlane32_swap(__float_as_uint((acc)[8 + i_]), __float_as_uint((acc)[12 + i_]), false, false);         \
+        (v)[0][i_] = __uint_as_float(lo_[0]); (v)[0][4 + i_] = __uint_as_float(lo_[1]);                                                          \
+        (v)[1][i_] = __uint_as_float(hi_[0]); (v)[1][4 + i_] = __uint_as_float(hi_[1]);                                                          \
+    }
 // max |.| of the workgroup (`red`: one float per wave, in LDS), then ONE atomicMax per WORKGROUP on the slot of its linear index: with
 // CVAE_AMAX_SLOTS = 4096 the workgroups of a launch rarely share a word.  (One atomic per wave on 64 slots cost the 64 -> 32 channel layer 14 of
 // its 23 us: same-address atomics serialise at the memory side at ~100 ns each.)  Every thread of the workgroup must call this.

@@ -111,20 +111,12 @@ __global__ __launch_bounds__(256) void down_c1_kernel(const T* __restrict__ L, c
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) OP::template mma_block<IW>(acc, halo, pb + kb * IH * IW, h, bfr[kb]);
-        // D rows are channels, columns positions: lane (r, h) holds channels (e & 3) + 8 (e >> 2) + 4 h of position r.  Two
-        // v_permlane32_swap per register pair regroup them into channels 8h..8h+7 and 16+8h..23+8h: 16-byte stores and mask loads.
         const int mo = (wave * 2 + ms) * 32 + r;
         const int ow = o0w + mo % TW, oh = o0h + mo / TW % TH, od = o0d + mo / (TW * TH);
         const bool ok = od < sd && oh < sh && ow < sw;
         const size_t pidx = ((((size_t)b * sd + od) * sh + oh) * sw + ow) * CS;
         float v[2][8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const auto lo = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i]), __float_as_uint(acc[4 + i]), false, false);
-            const auto hi = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 + i]), __float_as_uint(acc[12 + i]), false, false);
-            v[0][i] = __uint_as_float(lo[0]); v[0][4 + i] = __uint_as_float(lo[1]);
-            v[1][i] = __uint_as_float(hi[0]); v[1][4 + i] = __uint_as_float(hi[1]);
-        }
+        REGROUP_D32(acc, v)
         if (ok) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -272,18 +264,11 @@ __global__ __launch_bounds__(256) void down_c1_vec_kernel(const TL* __restrict__
             const int ow = o0w + w0, oh = o0h + hh, od = o0d + d;
             const bool ok = od < sd && oh < sh && ow < sw;
             const int loff = ((d * sh + hh) * sw + w0) * CS;      // 32-bit offset inside the tile; the tile's origin is uniform (scalar registers)
-            // the activation on the MFMA's own registers, then two v_permlane32_swap per register pair regroup D (rows = channels) into channels
-            // 8h..8h+7 and 16+8h..23+8h of this lane's position
+            // the activation on the MFMA's own registers, before the regroup
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[e] = apply_act_t<EPI>(acc[e], act);
             float v[2][8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const auto lo = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[i]), __float_as_uint(acc[4 + i]), false, false);
-                const auto hi = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[8 + i]), __float_as_uint(acc[12 + i]), false, false);
-                v[0][i] = __uint_as_float(lo[0]); v[0][4 + i] = __uint_as_float(lo[1]);
-                v[1][i] = __uint_as_float(hi[0]); v[1][4 + i] = __uint_as_float(hi[1]);
-            }
+            REGROUP_D32(acc, v)
             if (ok) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {

@@ -35,8 +35,25 @@ __device__ unsigned long long g_stamp[(size_t)CVAE_STAMP_WGS * CVAE_STAMP_SLOTS]
     do {                                                                                                                 \
         if (t == 0 && stamp_wg < CVAE_STAMP_WGS) g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + (i)] = __builtin_readcyclecounter(); \
     } while (0)
+// head of a probed kernel (declares stamp_wg; `t` is the thread index): wall clock into slot 30, hardware id registers into slot 29, then STAMP(0)
+#define STAMP_BEGIN()                                                                                                    \
+    const unsigned stamp_wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);                            \
+    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) {                                                                           \
+        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 30] = wall_clock64();                                              \
+        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 29] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492); \
+    }                                                                                                                    \
+    STAMP(0)
+// its tail: once the stores have left the wave (vmcnt(0)), STAMP(27) and the wall clock into slot 31
+#define STAMP_END()                                                                                                      \
+    do {                                                                                                                 \
+        __builtin_amdgcn_s_waitcnt(0);                                                                                   \
+        STAMP(27);                                                                                                       \
+        if (t == 0 && stamp_wg < CVAE_STAMP_WGS) g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 31] = wall_clock64();     \
+    } while (0)
 #else
 #define STAMP(i)
+#define STAMP_BEGIN()
+#define STAMP_END()
 #endif
 
 namespace {
@@ -234,14 +251,7 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
     char* bt = smem + HALO_BYTES;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#ifdef CVAE_STAMP
-    const unsigned stamp_wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) {
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 30] = wall_clock64();
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 29] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492);
-    }
-#endif
-    STAMP(0);
+    STAMP_BEGIN();
     const int ts = wave / (WM * WN), wv = wave % (WM * WN);      // K-split group (0 when TS == 1)
     const int wm = wv / WN, wn = wv % WN;
     const int r = lane & 31, h = lane >> 5;
@@ -551,11 +561,8 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
     }
     STAMP(26);
 
-    // ---- epilogue.  The MFMAs ran with the WEIGHT fragment as the A operand, so D rows are output channels and D columns are
-    // positions: lane (r, h) holds, for position r of each M sub-tile, channels (e & 3) + 8 (e >> 2) + 4 h of each 32-channel N
-    // sub-tile.  Two v_permlane32_swap per register pair regroup them so that the lane owns channels 8h..8h+7 and 16+8h..23+8h:
-    // two 8-channel pieces, each ONE 16-byte (bf16) store and ONE 16-byte mask load instead of eight 2-byte ones.
-    // the exchange and the epilogue index the accumulators with ts: written once as a generic lambda and called with the wave's ts as a compile-time
+    // ---- epilogue.  The MFMAs ran with the WEIGHT fragment as the A operand (D rows are output channels, D columns positions): REGROUP_D32, common.h.
+    // The exchange and the epilogue index the accumulators with ts: written once as a generic lambda and called with the wave's ts as a compile-time
     // constant (a run-time index would put the accumulator array in scratch memory)
     float amx = 0.f;                                          // fp8 side channel: largest |result| this lane stored
     const float accs = (F8 && f8.dscale) ? f8.dscale[0] : acc_scale, o8s = (F8 && f8.dscale) ? f8.dscale[1] : out_scale;
@@ -601,13 +608,7 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
             float v[2][8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const auto lo = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][i]), __float_as_uint(acc[mi][ni][4 + i]), false, false);
-                const auto hi = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][8 + i]), __float_as_uint(acc[mi][ni][12 + i]), false, false);
-                v[0][i] = __uint_as_float(lo[0]); v[0][4 + i] = __uint_as_float(lo[1]);
-                v[1][i] = __uint_as_float(hi[0]); v[1][4 + i] = __uint_as_float(hi[1]);
-            }
+            REGROUP_D32(acc[mi][ni], v)
             if (ksplit > 1) {
                 // split-K: this workgroup saw only its slice of the input channels; leave the raw fp32 partial sums in slab ks of
                 // the workspace ([ks][B][positions][Cout]); conv_splitk_finish_kernel adds the slabs, bias, activation and mask.
@@ -682,11 +683,7 @@ __global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kerne
             amax_publish_wg(f8.amax, amx, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (float*)smem);
         }
     }
-#ifdef CVAE_STAMP
-    __builtin_amdgcn_s_waitcnt(0);                         // vmcnt(0): the stores have left the wave
-    STAMP(27);
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 31] = wall_clock64();
-#endif
+    STAMP_END();
 }
 
 // out[p][c] = act(acc_scale * sum_ks ws[ks][p][c] + bias[c]) (* mask > 0): 8 channels per thread, 16-byte bf16 stores.  acc_scale is 1 except behind an
@@ -910,14 +907,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __r
     char* wbuf = smem + (size_t)NSLOT * SPITCH * FB;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#ifdef CVAE_STAMP
-    const unsigned stamp_wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) {
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 30] = wall_clock64();
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 29] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492);
-    }
-#endif
-    STAMP(0);
+    STAMP_BEGIN();
     const int wm = wave / WN, wn = wave % WN;
     const int r = lane & 31, h = lane >> 5;
     const int b = blockIdx.z;
@@ -1060,7 +1050,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __r
                 for (int j = 0; j < 2; ++j) piece_load_raw<TO>(mpre[mi][ni][j], mask + pidx + n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h);
         }
     };
-    auto epilogue = [&](int par) {                           // conv_data_kernel's: permlane32_swap regroup, 16-byte stores
+    auto epilogue = [&](int par) {                           // as conv_data_kernel's, but its own text: one sample per workgroup (no b + sx), the mask as pieces of the saved activation, no side channel
         const int prd = (ND == 3) ? ((par >> 2) & 1) : 0, prh = (par >> 1) & 1, prw = par & 1;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
@@ -1072,13 +1062,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __r
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni) {
                 float v[2][8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const auto lo = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][i]), __float_as_uint(acc[mi][ni][4 + i]), false, false);
-                    const auto hi = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][8 + i]), __float_as_uint(acc[mi][ni][12 + i]), false, false);
-                    v[0][i] = __uint_as_float(lo[0]); v[0][4 + i] = __uint_as_float(lo[1]);
-                    v[1][i] = __uint_as_float(hi[0]); v[1][4 + i] = __uint_as_float(hi[1]);
-                }
+                REGROUP_D32(acc[mi][ni], v)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
@@ -1121,11 +1105,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __r
         STAMP(5 + hpi);
         __syncthreads();
     }
-#ifdef CVAE_STAMP
-    __builtin_amdgcn_s_waitcnt(0);
-    STAMP(27);
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 31] = wall_clock64();
-#endif
+    STAMP_END();
 }
 
 template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH> constexpr size_t up_full_lds_bytes() {
@@ -1436,15 +1416,10 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
     auto s_byte = [](int m, int c) -> int { return m * SROW + ((((c >> 3) ^ (((m >> 1) & 1) << 2)) << 3) + (c & 7)) * (int)sizeof(T); };
     auto l_row = [](int line, int x) -> int { return (x & 1) * LPLANE + line * LHALF + (x >> 1); };
     const int tiles_per_b = g.tiles_d * g.tiles_h * g.tiles_w, total_tiles = (xb ? (g.B + 1) / 2 : g.B) * tiles_per_b;
+    STAMP_BEGIN();                                           // a 1D grid: stamp_wg = blockIdx.x
 #ifdef CVAE_STAMP
-    const unsigned stamp_wg = blockIdx.x;
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) {
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 30] = wall_clock64();
-        g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 29] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | __builtin_amdgcn_s_getreg(63492);
-    }
     int stamp_it = 0;
 #endif
-    STAMP(0);
 
     f32x16 acc[4];
 #pragma unroll
@@ -1633,11 +1608,7 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
         const int row = sg * 32 + (e & 3) + 8 * (e >> 2) + 4 * hq;
         *(float4*)(slab + ((kh * 64 + row) * 32 + col) * 4) = make_float4(acc[0][e], acc[1][e], acc[2][e], acc[3][e]);
     }
-#ifdef CVAE_STAMP
-    __builtin_amdgcn_s_waitcnt(0);
-    STAMP(27);
-    if (t == 0 && stamp_wg < CVAE_STAMP_WGS) g_stamp[(size_t)stamp_wg * CVAE_STAMP_SLOTS + 31] = wall_clock64();
-#endif
+    STAMP_END();
 }
 
 // dW[cs][cl][kd][kh][0..3] = sum over the n_split slabs of group (kd, channel block).  One thread per (kd, kh, cs, cl)
