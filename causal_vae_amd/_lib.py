@@ -139,6 +139,10 @@ SIGNATURES = {
     "cvae_latent_to_grid_bwd_workspace_bytes": [_i64] * 4,
     "cvae_latent_to_grid_bwd": [_p] * 3 + [_i64] * 4 + [_i, _p, _sz, _p],
     "cvae_mlp_heads_fwd": [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p],
+    "cvae_mlp_heads_train_workspace_bytes": [_p, _i, _p, _i, _i64],
+    "cvae_mlp_heads_bwd_workspace_bytes": [_p, _i, _p, _i, _i64],
+    "cvae_mlp_heads_train_fwd": [_p, _i, _p, _i, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _sz, _p],
+    "cvae_mlp_heads_bwd": [_p, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _sz, _p, _sz, _p],
     "cvae_row_diff_norms_workspace_bytes": [_i64, _i64, _i],
     "cvae_row_diff_norms": [_p] * 5 + [_i64, _i64, _i64, _i, _p, _sz, _p],
     "cvae_stack_mean_std": [_p, _i, _p, _p, _i64, _p],
@@ -152,6 +156,7 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
+            "cvae_mlp_heads_train_workspace_bytes": _sz, "cvae_mlp_heads_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
@@ -196,6 +201,16 @@ class HeadsLayer(C.Structure):
     """cvae_heads_layer"""
     _fields_ = [("W", _p), ("b", _p), ("W2", _p), ("b2", _p), ("out", _i64), ("out_first", _i64), ("bn_weight", _p), ("bn_bias", _p), ("bn_mean", _p),
                 ("bn_var", _p), ("bn_eps", _f), ("leaky", _i), ("slope", _f)]
+
+
+class HeadsBnTrain(C.Structure):
+    """cvae_heads_bn_train"""
+    _fields_ = [("running_mean", _p), ("running_var", _p), ("num_batches_tracked", _p), ("momentum", _f)]
+
+
+class HeadsLayerGrad(C.Structure):
+    """cvae_heads_layer_grad"""
+    _fields_ = [(n, _p) for n in ("dW", "db", "dW2", "db2", "dgamma", "dbeta")]
 
 
 class KernelTimer:

@@ -6,6 +6,7 @@ activations are channels-last [B, D, H, W, C] (D = 1 for 2D) in the compute dtyp
 losses, BN and sampling are fp32.
 """
 import ctypes as C_
+import math
 
 import torch
 
@@ -2250,3 +2251,152 @@ def mlp_heads(panels, layers, split=None, clamp0=None, clamp1=None, eps=None):
     check(lib.cvae_mlp_heads_fwd(pan, len(panels), rows, len(layers), split, cl(clamp0), cl(clamp1), ptr(eps), max(eps.stride(0), split) if eps is not None else 0,
                                  ptr(first), split, ptr(second), N - split, ptr(z), split, B, stream()), "mlp_heads")
     return first, second, z
+
+
+# ---- The same heads in training mode (cvae_mlp_heads_train_fwd / cvae_mlp_heads_bwd) ------------------------------------------------------
+def heads_saved_layout(widths, bn_flags, B):
+    """name -> (offset, shape) in floats of what cvae_mlp_heads_train_fwd leaves in its `saved` buffer (include/cvae_hip.h): per hidden layer l `mean{l}`,
+    `rstd{l}`, `xhat{l}` (BatchNorm layers), `pre{l}` (the pre-LeakyReLU value), `act{l}`; then `preclamp`.  widths: every layer's `out`."""
+    out, o = {}, 0
+    for l, n in enumerate(widths[:-1]):
+        if bn_flags[l]:
+            out[f"mean{l}"], out[f"rstd{l}"], out[f"xhat{l}"] = (o, (n,)), (o + n, (n,)), (o + 2 * n, (B, n))
+            o += 2 * n + B * n
+        out[f"pre{l}"], out[f"act{l}"] = (o, (B, n)), (o + B * n, (B, n))
+        o += 2 * B * n
+    out["preclamp"] = (o, (B, widths[-1]))
+    return out, o + B * widths[-1]
+
+
+class _HeadsCall:
+    """The C structures of one head and the tensors that keep their pointers alive."""
+
+    def __init__(self, panels, layers, split, clamp0, clamp1, eps):
+        import ctypes as C
+        if not 1 <= len(panels) <= L.HEADS_MAX_PANELS or not 1 <= len(layers) <= L.HEADS_MAX_LAYERS:
+            raise L.CvaeError(f"mlp_heads_train: 1..{L.HEADS_MAX_PANELS} input panels and 1..{L.HEADS_MAX_LAYERS} layers, got {len(panels)} and {len(layers)}: {L.strerror(-3)}")
+        if any(t.dim() != 2 for t in panels):
+            raise L.CvaeError(f"mlp_heads_train: every panel must be a [B, w] matrix, got shapes {[tuple(t.shape) for t in panels]}")
+        B = self.B = panels[0].shape[0]
+        for t in panels:
+            if t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] < 1:
+                raise L.CvaeError(f"mlp_heads_train: every panel must be float32 with {B} rows and at least one column, got {tuple(t.shape)} {t.dtype}")
+        self.panels = [_heads_rows(t.detach()) for t in panels]
+        width = sum(t.shape[1] for t in self.panels)
+        self.rows, self.bn_rows = (L.HeadsLayer * len(layers))(), (L.HeadsBnTrain * len(layers))()
+        self.params, self.slots, self.keep, self.bns = [], [], [], []      # params: the tensors that may ask for a gradient; slots: (layer, HeadsLayerGrad field) of each
+        for i, (lin, bn, slope) in enumerate(layers):
+            pair = lin if isinstance(lin, (tuple, list)) else (lin,)
+            last = i == len(layers) - 1
+            if len(pair) > 2 or (len(pair) == 2 and not last):
+                raise L.CvaeError("mlp_heads_train: only the last layer may be held by two nn.Linear modules")
+            if last and (bn is not None or slope is not None):
+                raise L.CvaeError(f"mlp_heads_train: the last layer is a plain Linear: {L.strerror(-3)}")
+            if any(p.weight.dtype != torch.float32 or p.weight.dim() != 2 or p.weight.shape[1] != width or p.bias is None or not p.weight.is_contiguous() for p in pair):
+                raise L.CvaeError(f"mlp_heads_train: layer {i} must be contiguous fp32 nn.Linear({width}, n) with a bias, got weights {[tuple(p.weight.shape) for p in pair]}")
+            r = self.rows[i]
+            r.W, r.b, r.out_first = pair[0].weight.data_ptr(), pair[0].bias.data_ptr(), pair[0].weight.shape[0]
+            r.out = sum(p.weight.shape[0] for p in pair)
+            self.params += [pair[0].weight, pair[0].bias]
+            self.slots += [(i, "dW"), (i, "db")]
+            if len(pair) == 2:
+                r.W2, r.b2 = pair[1].weight.data_ptr(), pair[1].bias.data_ptr()
+                self.params += [pair[1].weight, pair[1].bias]
+                self.slots += [(i, "dW2"), (i, "db2")]
+            if bn is not None:
+                if bn.weight is None or bn.num_features != r.out or bn.weight.dtype != torch.float32 or (bn.momentum is None and bn.track_running_stats):
+                    raise L.CvaeError(f"mlp_heads_train: layer {i}'s BatchNorm1d needs fp32 affine parameters, {r.out} features and a float momentum")
+                if B < 2:
+                    raise L.CvaeError(f"mlp_heads_train: batch statistics need more than one row, got {B}: {L.strerror(-1)}")
+                r.bn_weight, r.bn_bias, r.bn_eps = bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps)
+                s = self.bn_rows[i]
+                if bn.track_running_stats:
+                    L.require_gpu(bn.running_mean)
+                    s.running_mean, s.running_var, s.num_batches_tracked = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
+                    s.momentum = float(bn.momentum)
+                self.params += [bn.weight, bn.bias]
+                self.slots += [(i, "dgamma"), (i, "dbeta")]
+                self.bns.append(bn)
+            if slope is not None:
+                r.leaky, r.slope = 1, float(slope)
+            width = r.out
+        L.require_gpu(*self.params, *self.panels)
+        self.widths, self.bn_flags = [r.out for r in self.rows], [bool(r.bn_weight) for r in self.rows]
+        K = sum(t.shape[1] for t in self.panels)
+        if K > L.HEADS_MAX_WIDTH or any(w > L.HEADS_MAX_WIDTH for w in self.widths):
+            raise L.CvaeError(f"mlp_heads_train: input width {K} / layer widths {self.widths} above {L.HEADS_MAX_WIDTH}: {L.strerror(-3)}")
+        N = self.N = width
+        self.split = self.rows[len(layers) - 1].out_first if split is None else split
+        if not 1 <= self.split <= N:
+            raise L.CvaeError(f"mlp_heads_train: split {self.split} outside 1..{N}")
+        self.eps = None
+        if eps is not None:
+            L.require_gpu(eps)
+            if N != 2 * self.split or eps.dtype != torch.float32 or tuple(eps.shape) != (B, self.split):
+                raise L.CvaeError(f"mlp_heads_train: eps must be fp32 [{B}, {self.split}] and the head's width 2 * split, got {tuple(eps.shape)} {eps.dtype}, width {N}")
+            self.eps = _heads_rows(eps.detach())
+        self.pan = (L.HeadsPanel * len(self.panels))(*[L.HeadsPanel(t.data_ptr(), t.shape[1], max(t.stride(0), t.shape[1])) for t in self.panels])
+        cl = lambda c: None if c is None else (C.c_float * 2)(float(c[0]), float(c[1]))
+        self.clamp0, self.clamp1 = cl(clamp0), cl(clamp1)
+        self.eps_stride = max(self.eps.stride(0), self.split) if self.eps is not None else 0
+
+
+class _MlpHeadsTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, call, collect, *tensors):
+        c, B, S, N = call, call.B, call.split, call.N
+        like = c.panels[0]
+        first = _empty((B, S), torch.float32, like)
+        second = _empty((B, N - S), torch.float32, like) if S < N else None
+        z = _empty((B, S), torch.float32, like) if c.eps is not None else None
+        layout, total = heads_saved_layout(c.widths, c.bn_flags, B)
+        if B and lib.cvae_mlp_heads_train_workspace_bytes(c.pan, len(c.panels), c.rows, len(c.rows), B) != 4 * total:
+            raise L.CvaeError("mlp_heads_train: heads_saved_layout and cvae_mlp_heads_train_workspace_bytes disagree")
+        saved = _empty((max(total, 1),), torch.float32, like)
+        check(lib.cvae_mlp_heads_train_fwd(c.pan, len(c.panels), c.rows, len(c.rows), c.bn_rows, S, c.clamp0, c.clamp1, ptr(c.eps), c.eps_stride,
+                                           ptr(first), S, ptr(second), N - S, ptr(z), S, B, ptr(saved), 4 * total, stream()), "mlp_heads_train")
+        if collect is not None:
+            for k, (o, shape) in layout.items():
+                collect[k] = saved[o:o + math.prod(shape)].view(shape)
+        ctx.call, ctx.saved, ctx.total = c, saved, total
+        ctx.save_for_backward(*tensors)             # the kernels read panels and parameters through raw pointers: autograd's version check guards them
+        ctx.set_materialize_grads(False)
+        return first, second, z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g0, g1, gz):
+        import ctypes as C
+        ctx.saved_tensors                           # raises if a panel or parameter was modified in place since the forward
+        c, B, S, N = ctx.call, ctx.call.B, ctx.call.split, ctx.call.N
+        like, np_ = c.panels[0], len(c.panels)
+        grads = (L.HeadsLayerGrad * len(c.rows))()
+        outs = []
+        for p, (l, field) in zip(c.params, c.slots):
+            t = torch.empty_like(p, memory_format=torch.contiguous_format)
+            setattr(grads[l], field, t.data_ptr())
+            outs.append(t)
+        pg = [_empty(tuple(t.shape), torch.float32, like) if ctx.needs_input_grad[2 + i] else None for i, t in enumerate(c.panels)]
+        pgp = (C.c_void_p * np_)(*[ptr(t) for t in pg])
+        pgs = (C.c_int64 * np_)(*[t.shape[1] for t in c.panels])
+        cot = [None if g is None else _heads_rows(g.float()) for g in (g0, g1, gz)]
+        cs = [0 if g is None else max(g.stride(0), g.shape[1]) for g in cot]
+        nbytes = lib.cvae_mlp_heads_bwd_workspace_bytes(c.pan, np_, c.rows, len(c.rows), B)
+        _t, wp, wb = _scratch(nbytes, like)
+        check(lib.cvae_mlp_heads_bwd(c.pan, np_, pgp, pgs, c.rows, len(c.rows), grads, S, c.clamp0, c.clamp1, ptr(c.eps), c.eps_stride, ptr(cot[0]), cs[0],
+                                     ptr(cot[1]), cs[1], ptr(cot[2]), cs[2], B, ptr(ctx.saved), 4 * ctx.total, wp, wb, stream()), "mlp_heads_bwd")
+        if B == 0:
+            outs = [torch.zeros_like(t) for t in outs]
+        need = ctx.needs_input_grad[2 + np_:]
+        return (None, None, *pg, *[t if n else None for t, n in zip(outs, need)])
+
+
+def mlp_heads_train(panels, layers, split=None, clamp0=None, clamp1=None, eps=None, collect=None):
+    """ops.mlp_heads in TRAINING mode, differentiable (cvae_mlp_heads_train_fwd / cvae_mlp_heads_bwd; once_differentiable): a BatchNorm1d layer normalises with
+    the statistics of this batch and its running_mean, running_var and num_batches_tracked are updated in place, as torch does (unbiased variance, float
+    momentum).  Same arguments as mlp_heads; the last layer is a plain Linear (or pair).  Returns (first, second or None, z or None) as outputs of one
+    autograd.Function: gradients go to the Linear and BatchNorm1d parameters that require grad and to the panels that require grad (eps gets none).
+    collect (a dict, for tests): receives views of the saved buffer by heads_saved_layout's names: mean{l}, rstd{l}, xhat{l}, pre{l} (the pre-LeakyReLU
+    values), act{l}, preclamp (the last layer's output before the clamps)."""
+    call = _HeadsCall(panels, layers, split, clamp0, clamp1, eps)
+    return _MlpHeadsTrain.apply(call, collect, *panels, *call.params)

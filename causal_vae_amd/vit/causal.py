@@ -9,7 +9,12 @@ hold the parameters; per call:
   predict_morph  ONE launch: t -> morph_predictor_shared -> morph_predictor_mu | morph_predictor_logvar (clamp +-10), the two last-layer weights read in place
   decode         ONE launch: [m | z] -> dec_adapter -> z_vit, then backbone.decode
 The heads are fp32 in both compute dtypes (they set mu and z_vit and take no time); set_compute_dtype switches the backbone only.
-No cat, BatchNorm1d, clamp, chunk or element-wise launch sits between the backbone's launches and the three heads launches."""
+No cat, BatchNorm1d, clamp, chunk or element-wise launch sits between the backbone's launches and the three heads launches.
+
+Training the adapters (train_adapters, forward_train): the three heads run in training mode (batch-statistics BatchNorm1d, running statistics updated) and
+are differentiable (ops.mlp_heads_train); the gradient reaches them through backbone.decode_with_grad.  The ONE difference from the reference: its
+`vae.train()` also puts the backbone's dropout and BatchNorm2d in training mode and its optimizer updates backbone weights; here the backbone is frozen and
+stays in eval mode."""
 import torch
 import torch.nn as nn
 
@@ -55,7 +60,10 @@ class _SharedTrunk(nn.Sequential):
 
 
 class CausalViTVAE(nn.Module):
-    """Eval-mode inference only.  Differences from the reference class, all stated here:
+    """Eval-mode inference, and training of the adapter heads on the frozen eval-mode backbone (train_adapters / forward_train).  Differences from the
+    reference class, all stated here:
+      * training: the reference's `vae.train()` also puts the backbone's dropout and BatchNorm2d in training mode and updates backbone weights; here the
+        backbone is frozen and in eval mode, and only the three heads learn.
       * pretrained_path: the reference loads the backbone checkpoint with strict=False and so ignores any mismatch; here a missing, unexpected or mis-shaped
         key is an error that names the keys (load_vitvae_state_dict).  The one exception is load_vitvae_state_dict's own: a pos_embedding of another
         patch grid is resized to this model's grid (it matters only with img_size=; decoder_input.weight of another grid is still a shape error).  The file
@@ -63,7 +71,7 @@ class CausalViTVAE(nn.Module):
       * keyword-only img_size / depth build a smaller backbone (tests); the defaults are the reference's.
       * forward / reparameterize take an optional eps [B, Z]; without it they draw torch.randn_like, as the reference does.
       * m, t, z and eps may be any float32 [B, w] views: m0.expand(B, -1) or one eps draw expanded over the rows is copied before the launch.
-      * every entry runs under no_grad and raises in training mode."""
+      * every entry but forward_train runs under no_grad and raises in training mode."""
     decode_signature = "z_m"       # decode(z, m): counterfactual.batched_counterfactual and vessel.analysis dispatch on this name
 
     def __init__(self, pretrained_path=None, *, img_size=None, depth=6):
@@ -81,6 +89,50 @@ class CausalViTVAE(nn.Module):
         self.morph_predictor_shared = _SharedTrunk(nn.Linear(self.t_dim, 64), nn.LeakyReLU(0.2), nn.Linear(64, 64), nn.LeakyReLU(0.2))
         self.morph_predictor_mu = nn.Linear(64, self.m_dim)
         self.morph_predictor_logvar = nn.Linear(64, self.m_dim)
+
+    # ---- training the adapters on the frozen backbone -----------------------------------------------------------------------------
+    _adapters_only = False
+
+    def head_parameters(self):
+        return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
+                for p in mod.parameters()]
+
+    def train_adapters(self):
+        """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
+        heads go to training mode.  Returns the list of head parameters, for the optimizer."""
+        self.backbone.requires_grad_(False)
+        self._adapters_only = True
+        self.train()
+        return self.head_parameters()
+
+    def train(self, mode=True):
+        """nn.Module.train; after train_adapters() the backbone stays in eval mode whatever `mode` is."""
+        super().train(mode)
+        if self._adapters_only:
+            self.backbone.eval()
+        return self
+
+    def forward_train(self, x, m, t, eps=None):
+        """The reference 6-tuple (recon_x, m_mu, mu, logvar, m_mu, m_logvar) attached to the autograd graph of the head parameters: backbone.cls_features
+        under no_grad, enc_adapter, the morph predictor and dec_adapter in training mode (ops.mlp_heads_train: batch statistics, running statistics updated),
+        then backbone.decode_with_grad.  The backbone is fp32 or bf16; the heads are fp32.  Needs train_adapters() first."""
+        live = [k for k, p in self.backbone.named_parameters() if p.requires_grad]
+        if self.backbone.training or live:
+            raise RuntimeError("CausalViTVAE.forward_train trains the adapter heads on a frozen eval-mode backbone: call model.train_adapters() first "
+                               f"(backbone.training={self.backbone.training}, {len(live)} backbone parameters require grad)")
+        B = x.shape[0]
+        m, t = self._rows("m", m, self.m_dim, B), self._rows("t", t, self.t_dim, B)
+        eps = torch.randn(B, self.my_z_dim, dtype=torch.float32, device=x.device) if eps is None else self._rows("eps", eps, self.my_z_dim, B)
+        cls_out = self.backbone.cls_features(x)
+        mu, logvar, z = ops.mlp_heads_train([cls_out, m, t], self.enc_adapter.head_layers(), split=self.my_z_dim, clamp0=(-100.0, 100.0),
+                                            clamp1=(-10.0, 10.0), eps=eps)
+        m_mu, m_logvar, _z = ops.mlp_heads_train([t], self.morph_layers(), clamp1=(-10.0, 10.0))
+        z_vit, _s, _z = ops.mlp_heads_train([m, z], self.dec_adapter.head_layers())
+        return self.backbone.decode_with_grad(z_vit), m_mu, mu, logvar, m_mu, m_logvar
+
+    def morph_layers(self):
+        s = self.morph_predictor_shared
+        return [(s[0], None, s[1].negative_slope), (s[2], None, s[3].negative_slope), ((self.morph_predictor_mu, self.morph_predictor_logvar), None, None)]
 
     def set_compute_dtype(self, dtype):
         """float32 or bfloat16 for the backbone; the heads stay fp32."""
@@ -123,9 +175,7 @@ class CausalViTVAE(nn.Module):
         """(m_mu, m_logvar) of p(m | t), m_logvar clamped to +-10 (models.py:291-294): one launch."""
         self._require_eval()
         t = self._rows("t", t, self.t_dim)
-        s = self.morph_predictor_shared
-        m_mu, m_logvar, _z = ops.mlp_heads([t], [(s[0], None, s[1].negative_slope), (s[2], None, s[3].negative_slope),
-                                                 ((self.morph_predictor_mu, self.morph_predictor_logvar), None, None)], clamp1=(-10.0, 10.0))
+        m_mu, m_logvar, _z = ops.mlp_heads([t], self.morph_layers(), clamp1=(-10.0, 10.0))
         return m_mu, m_logvar
 
     @torch.no_grad()

@@ -380,6 +380,41 @@ int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_
                        const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0, int64_t out0_stride,
                        float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* stream);
 
+/* ---- The same heads in TRAINING mode, and their backward (csrc/heads.hip) ---------------------------------------------------------------
+ * cvae_mlp_heads_train_fwd: cvae_mlp_heads_fwd's arguments and limits with training-mode semantics.  A hidden layer is a BatchNorm1d layer when its
+ * bn_weight != NULL (bn_bias required; the layer's bn_mean / bn_var are NOT read): it normalises with the statistics of the B rows of this call, mean first,
+ * then sum (v - mean)^2 (two passes, one thread per column walking the rows in order), the biased variance, rstd = 1 / sqrt(var + bn_eps), and updates
+ * bn[l] as torch does: running = (1 - momentum) running + momentum batch with the UNBIASED variance, *num_batches_tracked += 1 (each of the three pointers
+ * may be NULL: not tracked).  B < 2 with a BatchNorm layer is CVAE_E_BADSHAPE.  The last layer is a plain Linear (BatchNorm or LeakyReLU there:
+ * CVAE_E_UNSUPPORTED).  `bn` [n_layers] is read for BatchNorm layers only and may be NULL without one.
+ * `saved` (cvae_mlp_heads_train_workspace_bytes; below it CVAE_E_WORKSPACE) receives what the backward reads, fp32, in this order: for every hidden layer l
+ * of width N_l: { mean [N_l], rstd [N_l], the normalised pre-activation x^ [B][N_l] } when it is a BatchNorm layer, then the pre-LeakyReLU value [B][N_l]
+ * (gamma x^ + beta, or the Linear output), then the activation [B][N_l]; after the hidden layers the PRE-CLAMP last-layer output [B][out].
+ * One launch per stretch of layers between BatchNorm layers plus one statistics launch per BatchNorm layer (an adapter: 3, the morph predictor: 1).
+ *
+ * cvae_mlp_heads_bwd: cotangents g0 [B][split], g1 [B][out - split], gz [B][split] of the first result, the second result and z (each may be NULL = zero;
+ * gz needs eps and out == 2 split) -> grads[l] for every layer (dW, db as the weights are laid out; dW2, db2 for the last layer's second tensor; dgamma,
+ * dbeta for a BatchNorm layer: all required) and, for every panel p with panel_grads[p] != NULL, the input gradient [B][width_p] at row stride
+ * panel_grad_strides[p] (panel_grads NULL: none).  Chain: g_mu += g_z, g_lv += g_z eps 0.5 exp(lv / 2) from the clamped lv; the clamp passes where
+ * lo <= pre-clamp <= hi; Linear dW = g^T a, db = sum_rows g, da = g W; LeakyReLU y > 0 ? 1 : slope from the saved activation (exact zero: slope);
+ * BatchNorm dbeta = sum dy, dgamma = sum dy x^, dv = gamma rstd (dy - dbeta / B - x^ dgamma / B).  Every cross-row sum is ONE chain over rows 0 .. B-1 in one
+ * thread (dW: fmaf): no atomics, two runs give identical bits.  `saved` as the forward wrote it; `workspace` (cvae_mlp_heads_bwd_workspace_bytes) holds
+ * the per-layer output gradients.  Launches: an adapter 3, the morph predictor 2.  Rows >= B are never read or written.  Both workspace queries return 0
+ * for a head the entries refuse. */
+typedef struct { float *running_mean, *running_var; int64_t* num_batches_tracked; float momentum; } cvae_heads_bn_train;
+typedef struct { float *dW, *db, *dW2, *db2, *dgamma, *dbeta; } cvae_heads_layer_grad;
+size_t cvae_mlp_heads_train_workspace_bytes(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B);
+size_t cvae_mlp_heads_bwd_workspace_bytes(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B);
+int cvae_mlp_heads_train_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, const cvae_heads_bn_train* bn,
+                             int64_t split, const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0,
+                             int64_t out0_stride, float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* saved,
+                             size_t saved_bytes, void* stream);
+int cvae_mlp_heads_bwd(const cvae_heads_panel* panels, int n_panels, float* const* panel_grads, const int64_t* panel_grad_strides,
+                       const cvae_heads_layer* layers, int n_layers, const cvae_heads_layer_grad* grads, int64_t split, const float* clamp0,
+                       const float* clamp1, const float* eps, int64_t eps_stride, const float* g0, int64_t g0_stride, const float* g1,
+                       int64_t g1_stride, const float* gz, int64_t gz_stride, int64_t B, const void* saved, size_t saved_bytes, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- The dense bottleneck of CausalBioVAE in 5 + 5 launches (batch M <= 16, fp32 arithmetic) --------------------------------
  * Replaces, between the last encoder conv and the first decoder conv (causal_cascade/models.py:57-79):
  *   AdaptiveAvgPool + Flatten, cat([x_feat, m, t]), enc_fc (Linear-ReLU-Linear-ReLU), fc_mu, fc_logvar, reparameterize,
