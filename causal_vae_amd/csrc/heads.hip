@@ -171,19 +171,21 @@ __global__ __launch_bounds__(THREADS) void mlp_heads_kernel(const HeadsArgs a) {
         }
     }
 }
-}  // namespace
 
-extern "C" int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t split,
-                                  const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0, int64_t out0_stride,
-                                  float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* stream) {
+// ---- what the three entries check, once ----
+// A layer counts as BatchNorm1d by bn_var in eval (running statistics are what eval needs) and by bn_weight in training and backward (batch statistics
+// need none; gamma is what both have).
+enum HeadsMode { HEADS_EVAL, HEADS_TRAIN, HEADS_BWD };
+inline bool has_bn(const HeadsMode m, const cvae_heads_layer& L) { return m == HEADS_EVAL ? L.bn_var != nullptr : L.bn_weight != nullptr; }
+
+// shapes and limits: refused before the B == 0 return, and by the workspace queries; *K0 receives the concatenated input width
+int heads_check_shape(const HeadsMode m, const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B, int64_t* K0) {
     if (n_panels < 1 || n_panels > CVAE_HEADS_MAX_PANELS || n_layers < 1 || n_layers > CVAE_HEADS_MAX_LAYERS) return CVAE_E_UNSUPPORTED;
     if (!panels || !layers) return CVAE_E_NULLPTR;
     if (B < 0 || B > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
-    HeadsArgs a = {};
     int64_t K = 0;
     for (int p = 0; p < n_panels; ++p) {
         if (panels[p].width < 1 || panels[p].stride < panels[p].width) return CVAE_E_BADSHAPE;
-        a.panels[p] = panels[p];
         K += panels[p].width;
     }
     if (K > CVAE_HEADS_MAX_WIDTH) return CVAE_E_UNSUPPORTED;
@@ -192,26 +194,58 @@ extern "C" int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, 
         if (L.out < 1 || L.out > CVAE_HEADS_MAX_WIDTH) return CVAE_E_UNSUPPORTED;
         if (L.out_first < 1 || L.out_first > L.out) return CVAE_E_BADSHAPE;
         if (L.out_first < L.out && l != n_layers - 1) return CVAE_E_UNSUPPORTED;         // two weight tensors: the last layer's column halves only
-        a.layers[l] = L;
+        if (m == HEADS_EVAL) continue;
+        if (l == n_layers - 1 && (L.bn_weight || L.leaky)) return CVAE_E_UNSUPPORTED;     // training: the output layer is a plain Linear
+        if (L.bn_weight && B < 2) return CVAE_E_BADSHAPE;                                 // batch statistics of one row: torch raises too
     }
+    *K0 = K;
+    return CVAE_OK;
+}
+
+// HeadsArgs of a head whose shape passed, and the split and stride rules (still before the B == 0 return).  paired: z (forward) or its cotangent (backward)
+// is wanted, which needs N == 2 split and eps; the backward passes no outputs.
+int heads_fill(const HeadsMode m, HeadsArgs& a, const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t split,
+               const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0, int64_t out0_stride, float* out1,
+               int64_t out1_stride, float* z, int64_t z_stride, int64_t B, bool paired) {
     const int64_t N = layers[n_layers - 1].out;
-    if (split < 1 || split > N || (z && 2 * split != N)) return CVAE_E_BADSHAPE;
-    if (out0_stride < split || (split < N && out1_stride < N - split) || (z && (z_stride < split || eps_stride < split))) return CVAE_E_BADSHAPE;
-    if (B == 0) return CVAE_OK;
-    for (int p = 0; p < n_panels; ++p)
-        if (!panels[p].ptr) return CVAE_E_NULLPTR;
-    for (int l = 0; l < n_layers; ++l) {
-        const cvae_heads_layer& L = layers[l];
-        if (!L.W || !L.b || (L.out_first < L.out && (!L.W2 || !L.b2))) return CVAE_E_NULLPTR;
-        if (L.bn_var && (!L.bn_weight || !L.bn_bias || !L.bn_mean)) return CVAE_E_NULLPTR;
-    }
-    if (!out0 || (split < N && !out1) || (z && !eps)) return CVAE_E_NULLPTR;
+    if (split < 1 || split > N || (paired && 2 * split != N)) return CVAE_E_BADSHAPE;
+    if (m != HEADS_BWD && (out0_stride < split || (split < N && out1_stride < N - split) || (z && z_stride < split))) return CVAE_E_BADSHAPE;
+    if (paired && eps_stride < split) return CVAE_E_BADSHAPE;
+    for (int p = 0; p < n_panels; ++p) a.panels[p] = panels[p];
+    for (int l = 0; l < n_layers; ++l) a.layers[l] = layers[l];
     a.n_panels = n_panels; a.n_layers = n_layers; a.split = split; a.B = B;
     if (clamp0) { a.clamp0 = 1; a.lo0 = clamp0[0]; a.hi0 = clamp0[1]; }
     if (clamp1) { a.clamp1 = 1; a.lo1 = clamp1[0]; a.hi1 = clamp1[1]; }
     a.eps = eps; a.eps_stride = eps_stride;
     a.out0 = out0; a.out1 = out1; a.z = z;
     a.out0_stride = out0_stride; a.out1_stride = out1_stride; a.z_stride = z_stride;
+    return CVAE_OK;
+}
+
+// the pointers a launch would read or write: checked after the B == 0 return
+int heads_check_ptrs(const HeadsMode m, const HeadsArgs& a, bool paired) {
+    for (int p = 0; p < a.n_panels; ++p)
+        if (!a.panels[p].ptr) return CVAE_E_NULLPTR;
+    for (int l = 0; l < a.n_layers; ++l) {
+        const cvae_heads_layer& L = a.layers[l];
+        if (!L.W || !L.b || (L.out_first < L.out && (!L.W2 || !L.b2))) return CVAE_E_NULLPTR;
+        if (has_bn(m, L) && (!L.bn_weight || !L.bn_bias || (m == HEADS_EVAL && !L.bn_mean))) return CVAE_E_NULLPTR;
+    }
+    if (m != HEADS_BWD && (!a.out0 || (a.split < a.layers[a.n_layers - 1].out && !a.out1))) return CVAE_E_NULLPTR;
+    return paired && !a.eps ? CVAE_E_NULLPTR : CVAE_OK;
+}
+}  // namespace
+
+extern "C" int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t split,
+                                  const float* clamp0, const float* clamp1, const float* eps, int64_t eps_stride, float* out0, int64_t out0_stride,
+                                  float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* stream) {
+    int64_t K0;
+    HeadsArgs a = {};
+    int rc = heads_check_shape(HEADS_EVAL, panels, n_panels, layers, n_layers, B, &K0);
+    if (rc == CVAE_OK) rc = heads_fill(HEADS_EVAL, a, panels, n_panels, layers, n_layers, split, clamp0, clamp1, eps, eps_stride, out0, out0_stride, out1,
+                                       out1_stride, z, z_stride, B, z != nullptr);
+    if (rc != CVAE_OK || B == 0) return rc;
+    if ((rc = heads_check_ptrs(HEADS_EVAL, a, z != nullptr)) != CVAE_OK) return rc;
     // on every call: the attribute belongs to the current device, and a flag kept here would be shared by every device and thread of the process
     if (hipFuncSetAttribute((const void*)mlp_heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return CVAE_E_LAUNCH;
     hipLaunchKernelGGL(mlp_heads_kernel, dim3((unsigned)((B + ROWS - 1) / ROWS)), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, a);
@@ -261,29 +295,6 @@ struct TrainArgs {
     float* saved;
     TrainLayout lay;
 };
-
-// what both training entries and the workspace queries check of a head's shape; *K0 receives the concatenated input width
-int train_shape_check(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B, int64_t* K0) {
-    if (n_panels < 1 || n_panels > CVAE_HEADS_MAX_PANELS || n_layers < 1 || n_layers > CVAE_HEADS_MAX_LAYERS) return CVAE_E_UNSUPPORTED;
-    if (!panels || !layers) return CVAE_E_NULLPTR;
-    if (B < 0 || B > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
-    int64_t K = 0;
-    for (int p = 0; p < n_panels; ++p) {
-        if (panels[p].width < 1 || panels[p].stride < panels[p].width) return CVAE_E_BADSHAPE;
-        K += panels[p].width;
-    }
-    if (K > CVAE_HEADS_MAX_WIDTH) return CVAE_E_UNSUPPORTED;
-    for (int l = 0; l < n_layers; ++l) {
-        const cvae_heads_layer& L = layers[l];
-        if (L.out < 1 || L.out > CVAE_HEADS_MAX_WIDTH) return CVAE_E_UNSUPPORTED;
-        if (L.out_first < 1 || L.out_first > L.out) return CVAE_E_BADSHAPE;
-        if (l != n_layers - 1 && L.out_first < L.out) return CVAE_E_UNSUPPORTED;
-        if (l == n_layers - 1 && (L.bn_weight || L.leaky)) return CVAE_E_UNSUPPORTED;     // the output layer is a plain Linear
-        if (L.bn_weight && B < 2) return CVAE_E_BADSHAPE;                                 // batch statistics of one row: torch raises too
-    }
-    *K0 = K;
-    return CVAE_OK;
-}
 
 // acc + cmp += w h with the rounding errors of the product and of the sum kept in cmp (TwoProduct by fma, TwoSum; the _rn forms are never contracted): the
 // Linear in front of a BatchNorm1d layer.  Batch statistics subtract nearly equal values — at B = 2, x^ = d / sqrt(d^2 + eps) with d = (v0 - v1) / 2, and
@@ -481,7 +492,8 @@ struct BwdArgs {
     int sums;                                      // sums role: the BatchNorm layer whose dgamma / dbeta this launch writes, or -1
 };
 
-__device__ __forceinline__ int in_width(const BwdArgs& a, int l) { return l == 0 ? a.K0 : (int)a.h.layers[l - 1].out; }
+// the width of layer l's input; with wgrad_items also what bwd_launch counts blocks by
+__host__ __device__ __forceinline__ int in_width(const BwdArgs& a, int l) { return l == 0 ? a.K0 : (int)a.h.layers[l - 1].out; }
 
 // the input of layer l, row r, column k
 __device__ __forceinline__ float layer_input(const BwdArgs& a, int l, int64_t r, int k) {
@@ -632,7 +644,7 @@ __device__ void bwd_wgrad(const BwdArgs& a, const int l, const bool fly, const i
     }
 }
 
-__device__ __forceinline__ int wgrad_items(const BwdArgs& a, int l) { return (((int)a.h.layers[l].out + WN - 1) / WN) * ((in_width(a, l) + BT - 1) / BT); }
+__host__ __device__ __forceinline__ int wgrad_items(const BwdArgs& a, int l) { return (((int)a.h.layers[l].out + WN - 1) / WN) * ((in_width(a, l) + BT - 1) / BT); }
 
 __global__ __launch_bounds__(BT) void heads_bwd_kernel(const BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -662,7 +674,7 @@ constexpr size_t BWD_LDS = (size_t)2 * ROWS * AST * sizeof(float);
 
 int bwd_launch(BwdArgs& a, hipStream_t stream) {
     unsigned blocks = (unsigned)a.n_row_blocks;
-    for (int l = a.wl_lo; l <= a.wl_hi; ++l) blocks += (unsigned)((((int)a.h.layers[l].out + WN - 1) / WN) * (((l == 0 ? a.K0 : (int)a.h.layers[l - 1].out) + BT - 1) / BT));
+    for (int l = a.wl_lo; l <= a.wl_hi; ++l) blocks += (unsigned)wgrad_items(a, l);
     if (a.sums >= 0) blocks += (unsigned)(((int)a.h.layers[a.sums].out + BT - 1) / BT);
     if (!blocks) return CVAE_OK;
     hipLaunchKernelGGL(heads_bwd_kernel, dim3(blocks), dim3(BT), BWD_LDS, stream, a);
@@ -673,13 +685,13 @@ int bwd_launch(BwdArgs& a, hipStream_t stream) {
 
 extern "C" size_t cvae_mlp_heads_train_workspace_bytes(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B) {
     int64_t K0;
-    if (train_shape_check(panels, n_panels, layers, n_layers, B, &K0) != CVAE_OK) return 0;
+    if (heads_check_shape(HEADS_TRAIN, panels, n_panels, layers, n_layers, B, &K0) != CVAE_OK) return 0;
     return (size_t)train_layout(layers, n_layers, B).total * sizeof(float);
 }
 
 extern "C" size_t cvae_mlp_heads_bwd_workspace_bytes(const cvae_heads_panel* panels, int n_panels, const cvae_heads_layer* layers, int n_layers, int64_t B) {
     int64_t K0, o = 0;
-    if (train_shape_check(panels, n_panels, layers, n_layers, B, &K0) != CVAE_OK) return 0;
+    if (heads_check_shape(HEADS_BWD, panels, n_panels, layers, n_layers, B, &K0) != CVAE_OK) return 0;
     for (int l = 0; l < n_layers; ++l) o += B * layers[l].out;
     return (size_t)o * sizeof(float);
 }
@@ -689,35 +701,21 @@ extern "C" int cvae_mlp_heads_train_fwd(const cvae_heads_panel* panels, int n_pa
                                         int64_t out0_stride, float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* saved,
                                         size_t saved_bytes, void* stream) {
     int64_t K0;
-    const int rc = train_shape_check(panels, n_panels, layers, n_layers, B, &K0);
-    if (rc != CVAE_OK) return rc;
     TrainArgs t = {};
-    HeadsArgs& a = t.h;
-    const int64_t N = layers[n_layers - 1].out;
-    if (split < 1 || split > N || (z && 2 * split != N)) return CVAE_E_BADSHAPE;
-    if (out0_stride < split || (split < N && out1_stride < N - split) || (z && (z_stride < split || eps_stride < split))) return CVAE_E_BADSHAPE;
-    if (B == 0) return CVAE_OK;
-    for (int p = 0; p < n_panels; ++p) {
-        if (!panels[p].ptr) return CVAE_E_NULLPTR;
-        a.panels[p] = panels[p];
-    }
+    int rc = heads_check_shape(HEADS_TRAIN, panels, n_panels, layers, n_layers, B, &K0);
+    if (rc == CVAE_OK) rc = heads_fill(HEADS_TRAIN, t.h, panels, n_panels, layers, n_layers, split, clamp0, clamp1, eps, eps_stride, out0, out0_stride, out1,
+                                       out1_stride, z, z_stride, B, z != nullptr);
+    if (rc != CVAE_OK || B == 0) return rc;
+    if ((rc = heads_check_ptrs(HEADS_TRAIN, t.h, z != nullptr)) != CVAE_OK) return rc;
     for (int l = 0; l < n_layers; ++l) {
-        const cvae_heads_layer& L = layers[l];
-        if (!L.W || !L.b || (L.out_first < L.out && (!L.W2 || !L.b2))) return CVAE_E_NULLPTR;
-        if (L.bn_weight && (!L.bn_bias || !bn)) return CVAE_E_NULLPTR;
-        a.layers[l] = L;
-        if (L.bn_weight) t.bn[l] = bn[l];
+        if (!layers[l].bn_weight) continue;
+        if (!bn) return CVAE_E_NULLPTR;
+        t.bn[l] = bn[l];
     }
-    if (!out0 || (split < N && !out1) || (z && !eps) || !saved) return CVAE_E_NULLPTR;
+    if (!saved) return CVAE_E_NULLPTR;
     t.lay = train_layout(layers, n_layers, B);
     if (saved_bytes < (size_t)t.lay.total * sizeof(float)) return CVAE_E_WORKSPACE;
     t.saved = (float*)saved;
-    a.n_panels = n_panels; a.n_layers = n_layers; a.split = split; a.B = B;
-    if (clamp0) { a.clamp0 = 1; a.lo0 = clamp0[0]; a.hi0 = clamp0[1]; }
-    if (clamp1) { a.clamp1 = 1; a.lo1 = clamp1[0]; a.hi1 = clamp1[1]; }
-    a.eps = eps; a.eps_stride = eps_stride;
-    a.out0 = out0; a.out1 = out1; a.z = z;
-    a.out0_stride = out0_stride; a.out1_stride = out1_stride; a.z_stride = z_stride;
     if (hipFuncSetAttribute((const void*)heads_train_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return CVAE_E_LAUNCH;
     const dim3 grid((unsigned)((B + ROWS - 1) / ROWS));
     for (int l_begin = 0;;) {
@@ -741,42 +739,33 @@ extern "C" int cvae_mlp_heads_bwd(const cvae_heads_panel* panels, int n_panels, 
                                   int64_t g1_stride, const float* gz, int64_t gz_stride, int64_t B, const void* saved, size_t saved_bytes, void* workspace,
                                   size_t workspace_bytes, void* stream) {
     int64_t K0;
-    const int rc = train_shape_check(panels, n_panels, layers, n_layers, B, &K0);
-    if (rc != CVAE_OK) return rc;
-    if (!grads) return CVAE_E_NULLPTR;
     BwdArgs a = {};
     HeadsArgs& h = a.h;
-    const int64_t N = layers[n_layers - 1].out;
-    if (split < 1 || split > N || (gz && 2 * split != N)) return CVAE_E_BADSHAPE;
-    if ((g0 && g0_stride < split) || (g1 && g1_stride < N - split) || (gz && (gz_stride < split || eps_stride < split))) return CVAE_E_BADSHAPE;
+    int rc = heads_check_shape(HEADS_BWD, panels, n_panels, layers, n_layers, B, &K0);
+    if (rc != CVAE_OK) return rc;
+    if (!grads) return CVAE_E_NULLPTR;
+    rc = heads_fill(HEADS_BWD, h, panels, n_panels, layers, n_layers, split, clamp0, clamp1, eps, eps_stride, nullptr, 0, nullptr, 0, nullptr, 0, B, gz != nullptr);
+    if (rc != CVAE_OK) return rc;
+    if ((g0 && g0_stride < split) || (g1 && g1_stride < layers[n_layers - 1].out - split) || (gz && gz_stride < split)) return CVAE_E_BADSHAPE;
     for (int p = 0; p < n_panels; ++p)
         if (panel_grads && panel_grads[p] && (!panel_grad_strides || panel_grad_strides[p] < panels[p].width)) return CVAE_E_BADSHAPE;
     if (B == 0) return CVAE_OK;
-    for (int p = 0; p < n_panels; ++p) {
-        if (!panels[p].ptr) return CVAE_E_NULLPTR;
-        h.panels[p] = panels[p];
+    if ((rc = heads_check_ptrs(HEADS_BWD, h, gz != nullptr)) != CVAE_OK) return rc;
+    for (int p = 0; p < n_panels; ++p)
         if (panel_grads && panel_grads[p]) { a.pgrad[p] = panel_grads[p]; a.pgrad_stride[p] = panel_grad_strides[p]; }
-    }
     int64_t o = 0;
     for (int l = 0; l < n_layers; ++l) {
         const cvae_heads_layer& L = layers[l];
         const cvae_heads_layer_grad& G = grads[l];
-        if (!L.W || !L.b || (L.out_first < L.out && (!L.W2 || !L.b2))) return CVAE_E_NULLPTR;
-        if (!G.dW || !G.db || (L.out_first < L.out && (!G.dW2 || !G.db2))) return CVAE_E_NULLPTR;
-        if (L.bn_weight && (!L.bn_bias || !G.dgamma || !G.dbeta)) return CVAE_E_NULLPTR;
-        h.layers[l] = L;
+        if (!G.dW || !G.db || (L.out_first < L.out && (!G.dW2 || !G.db2)) || (L.bn_weight && (!G.dgamma || !G.dbeta))) return CVAE_E_NULLPTR;
         a.grads[l] = G;
         a.goff[l] = o;
         o += B * L.out;
     }
-    if ((gz && !eps) || !saved || !workspace) return CVAE_E_NULLPTR;
+    if (!saved || !workspace) return CVAE_E_NULLPTR;
     a.lay = train_layout(layers, n_layers, B);
     if (saved_bytes < (size_t)a.lay.total * sizeof(float) || workspace_bytes < (size_t)o * sizeof(float)) return CVAE_E_WORKSPACE;
     a.saved = (const float*)saved; a.ws = (float*)workspace; a.K0 = (int)K0;
-    h.n_panels = n_panels; h.n_layers = n_layers; h.split = split; h.B = B;
-    if (clamp0) { h.clamp0 = 1; h.lo0 = clamp0[0]; h.hi0 = clamp0[1]; }
-    if (clamp1) { h.clamp1 = 1; h.lo1 = clamp1[0]; h.hi1 = clamp1[1]; }
-    h.eps = eps; h.eps_stride = eps_stride;
     a.g0 = g0; a.g1 = g1; a.gz = gz; a.g0_stride = g0_stride; a.g1_stride = g1_stride; a.gz_stride = gz_stride;
     if (hipFuncSetAttribute((const void*)heads_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS) != hipSuccess) return CVAE_E_LAUNCH;
     const int row_blocks = (int)((B + ROWS - 1) / ROWS);

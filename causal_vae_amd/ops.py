@@ -2181,6 +2181,110 @@ def _heads_rows(t):
     return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
 
 
+class _HeadsCall:
+    """The C structures of one head and the tensors that keep their pointers alive.  what: the caller's name in error messages.  Eval (train=False)
+    is forward-only, reads detached fp32 contiguous copies of the parameters and needs running statistics; training reads the parameters in place
+    (contiguous fp32, a float momentum), refuses a decorated last layer and batch statistics of one row, and records what may ask for a gradient."""
+
+    __slots__ = ("B", "N", "split", "panels", "pan", "rows", "bn_rows", "params", "slots", "keep", "widths", "bn_flags", "eps", "eps_stride", "clamp0", "clamp1")
+
+    def __init__(self, what, train, panels, layers, split, clamp0, clamp1, eps):
+        import ctypes as C
+        if not 1 <= len(panels) <= L.HEADS_MAX_PANELS or not 1 <= len(layers) <= L.HEADS_MAX_LAYERS:
+            raise L.CvaeError(f"{what}: 1..{L.HEADS_MAX_PANELS} input panels and 1..{L.HEADS_MAX_LAYERS} layers, got {len(panels)} and {len(layers)}: {L.strerror(-3)}")
+        if any(t.dim() != 2 for t in panels):
+            raise L.CvaeError(f"{what}: every panel must be a [B, w] matrix, got shapes {[tuple(t.shape) for t in panels]}")
+        B = self.B = panels[0].shape[0]
+        for t in panels:
+            if t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] < 1:
+                rows = f"{B} rows" if train else f"{B} rows (the first panel's)"
+                raise L.CvaeError(f"{what}: every panel must be float32 with {rows} and at least one column, got {tuple(t.shape)} {t.dtype}")
+        self.panels = [_heads_rows(t.detach() if train else t) for t in panels]
+        K = width = sum(t.shape[1] for t in self.panels)
+        self.rows = (L.HeadsLayer * len(layers))()
+        self.bn_rows = (L.HeadsBnTrain * len(layers))() if train else None
+        # params: the tensors that may ask for a gradient; slots: (layer, HeadsLayerGrad field) of each; keep: eval's copies, alive until the call is enqueued
+        self.params, self.slots, self.keep = [], [], []
+        self.widths, self.bn_flags = [], []
+        if not train:
+            L.require_gpu(*self.panels)
+            _forward_only(what, *panels)
+        for i, (lin, bn, slope) in enumerate(layers):
+            pair = lin if isinstance(lin, (tuple, list)) else (lin,)
+            last = i == len(layers) - 1
+            if len(pair) > 2 or (len(pair) == 2 and not last):
+                raise L.CvaeError(f"{what}: only the last layer may be held by two nn.Linear modules")
+            if train and last and (bn is not None or slope is not None):
+                raise L.CvaeError(f"{what}: the last layer is a plain Linear: {L.strerror(-3)}")
+            ts = [t for p in pair for t in (p.weight, p.bias)]
+            if not train:
+                L.require_gpu(*ts)
+                _forward_only(what, *ts)
+            if any(p.weight.dtype != torch.float32 or p.weight.dim() != 2 or p.weight.shape[1] != width or p.bias is None or (train and not p.weight.is_contiguous()) for p in pair):
+                raise L.CvaeError(f"{what}: layer {i} must be {'contiguous ' if train else ''}fp32 nn.Linear({width}, n) with a bias, got weights {[tuple(p.weight.shape) for p in pair]}")
+            if train:
+                self.params += ts
+                self.slots += [(i, f) for f in ("dW", "db", "dW2", "db2")[:len(ts)]]
+            else:
+                ts = [t.detach().contiguous() for t in ts]
+                self.keep += ts
+            r, ptrs = self.rows[i], [t.data_ptr() for t in ts]
+            r.W, r.b, r.out_first = ptrs[0], ptrs[1], pair[0].weight.shape[0]
+            r.out = sum(p.weight.shape[0] for p in pair)
+            if len(pair) == 2:
+                r.W2, r.b2 = ptrs[2:]
+            if bn is not None and train:
+                if bn.weight is None or bn.num_features != r.out or bn.weight.dtype != torch.float32 or (bn.momentum is None and bn.track_running_stats):
+                    raise L.CvaeError(f"{what}: layer {i}'s BatchNorm1d needs fp32 affine parameters, {r.out} features and a float momentum")
+                if B < 2:
+                    raise L.CvaeError(f"{what}: batch statistics need more than one row, got {B}: {L.strerror(-1)}")
+                r.bn_weight, r.bn_bias, r.bn_eps = bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps)
+                if bn.track_running_stats:
+                    L.require_gpu(bn.running_mean)
+                    s = self.bn_rows[i]
+                    s.running_mean, s.running_var, s.num_batches_tracked = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
+                    s.momentum = float(bn.momentum)
+                self.params += [bn.weight, bn.bias]
+                self.slots += [(i, "dgamma"), (i, "dbeta")]
+            elif bn is not None:
+                if bn.running_var is None or bn.weight is None or bn.num_features != r.out:
+                    raise L.CvaeError(f"{what}: layer {i}'s BatchNorm1d needs running statistics, an affine weight and {r.out} features")
+                bts = [t.detach().float().contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+                L.require_gpu(*bts)
+                self.keep += bts
+                r.bn_weight, r.bn_bias, r.bn_mean, r.bn_var = (t.data_ptr() for t in bts)
+                r.bn_eps = float(bn.eps)
+            if slope is not None:
+                r.leaky, r.slope = 1, float(slope)
+            width = r.out
+            self.widths.append(width)
+            self.bn_flags.append(bn is not None)
+        if train:
+            L.require_gpu(*self.params, *self.panels)
+        if K > L.HEADS_MAX_WIDTH or any(w > L.HEADS_MAX_WIDTH for w in self.widths):
+            raise L.CvaeError(f"{what}: input width {K} / layer widths {self.widths} above {L.HEADS_MAX_WIDTH}: {L.strerror(-3)}")
+        N = self.N = width
+        self.split = self.rows[len(layers) - 1].out_first if split is None else split
+        if not 1 <= self.split <= N:
+            raise L.CvaeError(f"{what}: split {self.split} outside 1..{N}")
+        self.eps = None
+        if eps is not None:
+            L.require_gpu(eps)
+            if N != 2 * self.split or eps.dtype != torch.float32 or tuple(eps.shape) != (B, self.split):
+                raise L.CvaeError(f"{what}: eps must be fp32 [{B}, {self.split}] and the head's width 2 * split, got {tuple(eps.shape)} {eps.dtype}, width {N}")
+            self.eps = _heads_rows(eps.detach() if train else eps)
+        self.pan = (L.HeadsPanel * len(self.panels))(*[L.HeadsPanel(t.data_ptr(), t.shape[1], max(t.stride(0), t.shape[1])) for t in self.panels])
+        cl = lambda c: None if c is None else (C.c_float * 2)(float(c[0]), float(c[1]))
+        self.clamp0, self.clamp1 = cl(clamp0), cl(clamp1)
+        self.eps_stride = max(self.eps.stride(0), self.split) if self.eps is not None else 0
+
+    def outputs(self):
+        """first [B, split], second [B, N - split] or None, z [B, split] or None (with eps)"""
+        like, B, S, N = self.panels[0], self.B, self.split, self.N
+        return (_empty((B, S), torch.float32, like), _empty((B, N - S), torch.float32, like) if S < N else None,
+                _empty((B, S), torch.float32, like) if self.eps is not None else None)
+
+
 def mlp_heads(panels, layers, split=None, clamp0=None, clamp1=None, eps=None):
     """One fused head (cvae_mlp_heads_fwd), fp32, forward-only.
     panels  1..3 fp32 [B, w_i] matrices; the head reads torch.cat(panels, 1) without building it.  A panel with unit column stride and a row stride of
@@ -2192,64 +2296,10 @@ def mlp_heads(panels, layers, split=None, clamp0=None, clamp1=None, eps=None):
     clamp0 / clamp1  (lo, hi) of torch.clamp for the two results, or None
     eps     [B, split] fp32, read in place or copied by the same rule as a panel: also returns z = first + eps * exp(0.5 * second) from the clamped values (needs N == 2 split)
     Returns (first, second or None, z or None)."""
-    import ctypes as C
-    if not 1 <= len(panels) <= L.HEADS_MAX_PANELS or not 1 <= len(layers) <= L.HEADS_MAX_LAYERS:
-        raise L.CvaeError(f"mlp_heads: 1..{L.HEADS_MAX_PANELS} input panels and 1..{L.HEADS_MAX_LAYERS} layers, got {len(panels)} and {len(layers)}: {L.strerror(-3)}")
-    if any(t.dim() != 2 for t in panels):
-        raise L.CvaeError(f"mlp_heads: every panel must be a [B, w] matrix, got shapes {[tuple(t.shape) for t in panels]}")
-    B = panels[0].shape[0]
-    for t in panels:
-        if t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] < 1:
-            raise L.CvaeError(f"mlp_heads: every panel must be float32 with {B} rows (the first panel's) and at least one column, got {tuple(t.shape)} {t.dtype}")
-    panels = [_heads_rows(t) for t in panels]
-    K = sum(t.shape[1] for t in panels)
-    keep, rows, width = [], (L.HeadsLayer * len(layers))(), K
-    for i, (lin, bn, slope) in enumerate(layers):
-        pair = lin if isinstance(lin, (tuple, list)) else (lin,)
-        if len(pair) > 2 or (len(pair) == 2 and i != len(layers) - 1):
-            raise L.CvaeError("mlp_heads: only the last layer may be held by two nn.Linear modules")
-        ts = [t.detach().contiguous() for p in pair for t in (p.weight, p.bias)]
-        L.require_gpu(*ts, *panels)
-        _forward_only("mlp_heads", *[t for p in pair for t in (p.weight, p.bias)], *panels)
-        if any(p.weight.dtype != torch.float32 or p.weight.dim() != 2 or p.weight.shape[1] != width or p.bias is None for p in pair):
-            raise L.CvaeError(f"mlp_heads: layer {i} must be fp32 nn.Linear({width}, n) with a bias, got weights {[tuple(p.weight.shape) for p in pair]}")
-        r = rows[i]
-        r.W, r.b, r.out_first = ts[0].data_ptr(), ts[1].data_ptr(), pair[0].weight.shape[0]
-        r.out = sum(p.weight.shape[0] for p in pair)
-        if len(pair) == 2:
-            r.W2, r.b2 = ts[2].data_ptr(), ts[3].data_ptr()
-        if bn is not None:
-            if bn.running_var is None or bn.weight is None or bn.num_features != r.out:
-                raise L.CvaeError(f"mlp_heads: layer {i}'s BatchNorm1d needs running statistics, an affine weight and {r.out} features")
-            bts = [t.detach().float().contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-            L.require_gpu(*bts)
-            r.bn_weight, r.bn_bias, r.bn_mean, r.bn_var = (t.data_ptr() for t in bts)
-            r.bn_eps = float(bn.eps)
-            ts += bts
-        if slope is not None:
-            r.leaky, r.slope = 1, float(slope)
-        keep.append(ts)
-        width = r.out
-    if K > L.HEADS_MAX_WIDTH or any(r.out > L.HEADS_MAX_WIDTH for r in rows):
-        raise L.CvaeError(f"mlp_heads: input width {K} / layer widths {[r.out for r in rows]} above {L.HEADS_MAX_WIDTH}: {L.strerror(-3)}")
-    N = width
-    if split is None:
-        split = rows[len(layers) - 1].out_first
-    if not 1 <= split <= N:
-        raise L.CvaeError(f"mlp_heads: split {split} outside 1..{N}")
-    first = _empty((B, split), torch.float32, panels[0])
-    second = _empty((B, N - split), torch.float32, panels[0]) if split < N else None
-    z = None
-    if eps is not None:
-        L.require_gpu(eps)
-        if N != 2 * split or eps.dtype != torch.float32 or tuple(eps.shape) != (B, split):
-            raise L.CvaeError(f"mlp_heads: eps must be fp32 [{B}, {split}] and the head's width 2 * split, got {tuple(eps.shape)} {eps.dtype}, width {N}")
-        eps = _heads_rows(eps)
-        z = _empty((B, split), torch.float32, panels[0])
-    pan = (L.HeadsPanel * len(panels))(*[L.HeadsPanel(t.data_ptr(), t.shape[1], max(t.stride(0), t.shape[1])) for t in panels])
-    cl = lambda c: None if c is None else (C.c_float * 2)(float(c[0]), float(c[1]))
-    check(lib.cvae_mlp_heads_fwd(pan, len(panels), rows, len(layers), split, cl(clamp0), cl(clamp1), ptr(eps), max(eps.stride(0), split) if eps is not None else 0,
-                                 ptr(first), split, ptr(second), N - split, ptr(z), split, B, stream()), "mlp_heads")
+    c = _HeadsCall("mlp_heads", False, panels, layers, split, clamp0, clamp1, eps)
+    first, second, z = c.outputs()
+    check(lib.cvae_mlp_heads_fwd(c.pan, len(c.panels), c.rows, len(c.rows), c.split, c.clamp0, c.clamp1, ptr(c.eps), c.eps_stride,
+                                 ptr(first), c.split, ptr(second), c.N - c.split, ptr(z), c.split, c.B, stream()), "mlp_heads")
     return first, second, z
 
 
@@ -2268,87 +2318,12 @@ def heads_saved_layout(widths, bn_flags, B):
     return out, o + B * widths[-1]
 
 
-class _HeadsCall:
-    """The C structures of one head and the tensors that keep their pointers alive."""
-
-    def __init__(self, panels, layers, split, clamp0, clamp1, eps):
-        import ctypes as C
-        if not 1 <= len(panels) <= L.HEADS_MAX_PANELS or not 1 <= len(layers) <= L.HEADS_MAX_LAYERS:
-            raise L.CvaeError(f"mlp_heads_train: 1..{L.HEADS_MAX_PANELS} input panels and 1..{L.HEADS_MAX_LAYERS} layers, got {len(panels)} and {len(layers)}: {L.strerror(-3)}")
-        if any(t.dim() != 2 for t in panels):
-            raise L.CvaeError(f"mlp_heads_train: every panel must be a [B, w] matrix, got shapes {[tuple(t.shape) for t in panels]}")
-        B = self.B = panels[0].shape[0]
-        for t in panels:
-            if t.dtype != torch.float32 or t.shape[0] != B or t.shape[1] < 1:
-                raise L.CvaeError(f"mlp_heads_train: every panel must be float32 with {B} rows and at least one column, got {tuple(t.shape)} {t.dtype}")
-        self.panels = [_heads_rows(t.detach()) for t in panels]
-        width = sum(t.shape[1] for t in self.panels)
-        self.rows, self.bn_rows = (L.HeadsLayer * len(layers))(), (L.HeadsBnTrain * len(layers))()
-        self.params, self.slots, self.keep, self.bns = [], [], [], []      # params: the tensors that may ask for a gradient; slots: (layer, HeadsLayerGrad field) of each
-        for i, (lin, bn, slope) in enumerate(layers):
-            pair = lin if isinstance(lin, (tuple, list)) else (lin,)
-            last = i == len(layers) - 1
-            if len(pair) > 2 or (len(pair) == 2 and not last):
-                raise L.CvaeError("mlp_heads_train: only the last layer may be held by two nn.Linear modules")
-            if last and (bn is not None or slope is not None):
-                raise L.CvaeError(f"mlp_heads_train: the last layer is a plain Linear: {L.strerror(-3)}")
-            if any(p.weight.dtype != torch.float32 or p.weight.dim() != 2 or p.weight.shape[1] != width or p.bias is None or not p.weight.is_contiguous() for p in pair):
-                raise L.CvaeError(f"mlp_heads_train: layer {i} must be contiguous fp32 nn.Linear({width}, n) with a bias, got weights {[tuple(p.weight.shape) for p in pair]}")
-            r = self.rows[i]
-            r.W, r.b, r.out_first = pair[0].weight.data_ptr(), pair[0].bias.data_ptr(), pair[0].weight.shape[0]
-            r.out = sum(p.weight.shape[0] for p in pair)
-            self.params += [pair[0].weight, pair[0].bias]
-            self.slots += [(i, "dW"), (i, "db")]
-            if len(pair) == 2:
-                r.W2, r.b2 = pair[1].weight.data_ptr(), pair[1].bias.data_ptr()
-                self.params += [pair[1].weight, pair[1].bias]
-                self.slots += [(i, "dW2"), (i, "db2")]
-            if bn is not None:
-                if bn.weight is None or bn.num_features != r.out or bn.weight.dtype != torch.float32 or (bn.momentum is None and bn.track_running_stats):
-                    raise L.CvaeError(f"mlp_heads_train: layer {i}'s BatchNorm1d needs fp32 affine parameters, {r.out} features and a float momentum")
-                if B < 2:
-                    raise L.CvaeError(f"mlp_heads_train: batch statistics need more than one row, got {B}: {L.strerror(-1)}")
-                r.bn_weight, r.bn_bias, r.bn_eps = bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps)
-                s = self.bn_rows[i]
-                if bn.track_running_stats:
-                    L.require_gpu(bn.running_mean)
-                    s.running_mean, s.running_var, s.num_batches_tracked = bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr()
-                    s.momentum = float(bn.momentum)
-                self.params += [bn.weight, bn.bias]
-                self.slots += [(i, "dgamma"), (i, "dbeta")]
-                self.bns.append(bn)
-            if slope is not None:
-                r.leaky, r.slope = 1, float(slope)
-            width = r.out
-        L.require_gpu(*self.params, *self.panels)
-        self.widths, self.bn_flags = [r.out for r in self.rows], [bool(r.bn_weight) for r in self.rows]
-        K = sum(t.shape[1] for t in self.panels)
-        if K > L.HEADS_MAX_WIDTH or any(w > L.HEADS_MAX_WIDTH for w in self.widths):
-            raise L.CvaeError(f"mlp_heads_train: input width {K} / layer widths {self.widths} above {L.HEADS_MAX_WIDTH}: {L.strerror(-3)}")
-        N = self.N = width
-        self.split = self.rows[len(layers) - 1].out_first if split is None else split
-        if not 1 <= self.split <= N:
-            raise L.CvaeError(f"mlp_heads_train: split {self.split} outside 1..{N}")
-        self.eps = None
-        if eps is not None:
-            L.require_gpu(eps)
-            if N != 2 * self.split or eps.dtype != torch.float32 or tuple(eps.shape) != (B, self.split):
-                raise L.CvaeError(f"mlp_heads_train: eps must be fp32 [{B}, {self.split}] and the head's width 2 * split, got {tuple(eps.shape)} {eps.dtype}, width {N}")
-            self.eps = _heads_rows(eps.detach())
-        self.pan = (L.HeadsPanel * len(self.panels))(*[L.HeadsPanel(t.data_ptr(), t.shape[1], max(t.stride(0), t.shape[1])) for t in self.panels])
-        cl = lambda c: None if c is None else (C.c_float * 2)(float(c[0]), float(c[1]))
-        self.clamp0, self.clamp1 = cl(clamp0), cl(clamp1)
-        self.eps_stride = max(self.eps.stride(0), self.split) if self.eps is not None else 0
-
-
 class _MlpHeadsTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, call, collect, *tensors):
         c, B, S, N = call, call.B, call.split, call.N
         like = c.panels[0]
-        first = _empty((B, S), torch.float32, like)
-        second = _empty((B, N - S), torch.float32, like) if S < N else None
-        z = _empty((B, S), torch.float32, like) if c.eps is not None else None
+        first, second, z = c.outputs()
         layout, total = heads_saved_layout(c.widths, c.bn_flags, B)
         if B and lib.cvae_mlp_heads_train_workspace_bytes(c.pan, len(c.panels), c.rows, len(c.rows), B) != 4 * total:
             raise L.CvaeError("mlp_heads_train: heads_saved_layout and cvae_mlp_heads_train_workspace_bytes disagree")
@@ -2398,5 +2373,5 @@ def mlp_heads_train(panels, layers, split=None, clamp0=None, clamp1=None, eps=No
     autograd.Function: gradients go to the Linear and BatchNorm1d parameters that require grad and to the panels that require grad (eps gets none).
     collect (a dict, for tests): receives views of the saved buffer by heads_saved_layout's names: mean{l}, rstd{l}, xhat{l}, pre{l} (the pre-LeakyReLU
     values), act{l}, preclamp (the last layer's output before the clamps)."""
-    call = _HeadsCall(panels, layers, split, clamp0, clamp1, eps)
+    call = _HeadsCall("mlp_heads_train", True, panels, layers, split, clamp0, clamp1, eps)
     return _MlpHeadsTrain.apply(call, collect, *panels, *call.params)

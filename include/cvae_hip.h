@@ -363,7 +363,8 @@ int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz, int64_t B,
  * panel; z (optional, needs out == 2 split and eps [B][split]): z = out0 + eps * exp(0.5 * out1) from the clamped values.  All strides in elements.
  * fp32 throughout; every output value is one fmaf chain over the inputs in index order (no atomics, no split sums): a row's bits do not depend on B nor on the
  * row's position in the batch.  Limits: the concatenated input width and every layer's `out` at most CVAE_HEADS_MAX_WIDTH, else CVAE_E_UNSUPPORTED (the heads
- * served: 287 -> 512 -> 256, 140 -> 256 -> 512, 19 -> 64 -> 64 -> 12 + 12).  B == 0 is CVAE_OK (nothing is launched). */
+ * served: 287 -> 512 -> 256, 140 -> 256 -> 512, 19 -> 64 -> 64 -> 12 + 12).  B == 0 is CVAE_OK (nothing is launched).  Shape and limit errors are reported
+ * before that return, NULL pointers after it; the training entries below are checked by the same code. */
 #define CVAE_HEADS_MAX_PANELS 3
 #define CVAE_HEADS_MAX_LAYERS 3
 #define CVAE_HEADS_MAX_WIDTH  512
@@ -381,7 +382,7 @@ int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, const cvae_
                        float* out1, int64_t out1_stride, float* z, int64_t z_stride, int64_t B, void* stream);
 
 /* ---- The same heads in TRAINING mode, and their backward (csrc/heads.hip) ---------------------------------------------------------------
- * cvae_mlp_heads_train_fwd: cvae_mlp_heads_fwd's arguments and limits with training-mode semantics.  A hidden layer is a BatchNorm1d layer when its
+ * cvae_mlp_heads_train_fwd: cvae_mlp_heads_fwd's arguments, limits and checks (the same code) with training-mode semantics.  A hidden layer is a BatchNorm1d layer when its
  * bn_weight != NULL (bn_bias required; the layer's bn_mean / bn_var are NOT read): it normalises with the statistics of the B rows of this call, mean first,
  * then sum (v - mean)^2 (two passes, one thread per column walking the rows in order), the biased variance, rstd = 1 / sqrt(var + bn_eps), and updates
  * bn[l] as torch does: running = (1 - momentum) running + momentum batch with the UNBIASED variance, *num_batches_tracked += 1 (each of the three pointers

@@ -187,6 +187,45 @@ def test_training_entry_point_limits():
     assert bwd(*head(widths=(287, 513, 256)), 8) == -3
 
 
+FAULTS = {  # name -> (panel (width, stride) list, n_panels passed, layer (out, out_first) list, n_layers passed, split, the code include/cvae_hip.h gives it)
+    "no_panel": ([(19, 19)], 0, [(64, 64), (24, 24)], 2, 12, -3),
+    "four_panels": ([(19, 19)] * 4, 4, [(64, 64), (24, 24)], 2, 12, -3),
+    "four_layers": ([(19, 19)], 1, [(64, 64)] * 3 + [(24, 24)], 4, 12, -3),
+    "stride_below_width": ([(19, 18)], 1, [(64, 64), (24, 24)], 2, 12, -1),
+    "layer_above_512": ([(19, 19)], 1, [(513, 513), (24, 24)], 2, 12, -3),
+    "input_above_512": ([(300, 300), (213, 213)], 2, [(64, 64), (24, 24)], 2, 12, -3),
+    "out_first_zero": ([(19, 19)], 1, [(64, 64), (24, 0)], 2, 12, -1),
+    "out_first_above_out": ([(19, 19)], 1, [(64, 64), (24, 25)], 2, 12, -1),
+    "pair_on_hidden_layer": ([(19, 19)], 1, [(64, 32), (24, 24)], 2, 12, -3),
+    "split_zero": ([(19, 19)], 1, [(64, 64), (24, 12)], 2, 0, -1),
+    "split_above_width": ([(19, 19)], 1, [(64, 64), (24, 12)], 2, 25, -1),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(FAULTS))
+def test_three_entries_refuse_a_faulty_head_alike(fault):
+    """One faulty description, three entries (cvae_mlp_heads_fwd, cvae_mlp_heads_train_fwd, cvae_mlp_heads_bwd): the same code from each.  The head has no
+    BatchNorm and every pointer is a non-null dummy that is never read: each case ends in the shape checks, before a launch."""
+    from causal_vae_amd import _lib as L
+    panels, n_panels, layers, n_layers, split, code = FAULTS[fault]
+    one, B = ctypes.c_void_p(16), 8
+    pan = (L.HeadsPanel * len(panels))(*[L.HeadsPanel(one, w, s) for w, s in panels])
+    lay = (L.HeadsLayer * len(layers))()
+    gr = (L.HeadsLayerGrad * len(layers))()
+    for i, (out, out_first) in enumerate(layers):
+        lay[i].W, lay[i].b, lay[i].W2, lay[i].b2, lay[i].out, lay[i].out_first = one, one, one, one, out, out_first
+        if i < len(layers) - 1:
+            lay[i].leaky, lay[i].slope = 1, 0.2
+        gr[i].dW, gr[i].db, gr[i].dW2, gr[i].db2 = one, one, one, one
+    st = (L.HeadsBnTrain * len(layers))()
+    big = 1 << 40
+    got = {"fwd": L.lib.cvae_mlp_heads_fwd(pan, n_panels, lay, n_layers, split, None, None, None, 0, one, 512, one, 512, None, 0, B, None),
+           "train_fwd": L.lib.cvae_mlp_heads_train_fwd(pan, n_panels, lay, n_layers, st, split, None, None, None, 0, one, 512, one, 512, None, 0, B, one, big, None),
+           "bwd": L.lib.cvae_mlp_heads_bwd(pan, n_panels, None, None, lay, n_layers, gr, split, None, None, None, 0, one, 512, one, 512, None, 0, B, one, big,
+                                           one, big, None)}
+    assert got == {"fwd": code, "train_fwd": code, "bwd": code}, (fault, got)
+
+
 def test_forward_train_guards_and_frozen_backbone():
     from causal_vae_amd.vit import CausalViTVAE
     model = CausalViTVAE(img_size=(64, 96), depth=1)
