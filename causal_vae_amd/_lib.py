@@ -125,6 +125,7 @@ SIGNATURES = {
     "cvae_bn2d_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _i, _p, _sz, _p],
     "cvae_bn2d_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
     "cvae_fold_bn_conv": [_i] + [_p] * 11 + [_p],
+    "cvae_fold_bn_conv_bwd": [_i] + [_p] * 14 + [_p],
     "cvae_vit_tokens": [_p, _i, _p, _p, _p, _i64, _i64, _p],
     "cvae_layernorm256": [_p, _i64, _p, _p, _p, _i64, _f, _i, _p],
     "cvae_token_gemm": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
@@ -138,6 +139,11 @@ SIGNATURES = {
     "cvae_conv_s1_c1_bwd_data": [_p] * 4 + [_i64] * 4 + [_i, _i, _p],
     "cvae_latent_to_grid_bwd_workspace_bytes": [_i64] * 4,
     "cvae_latent_to_grid_bwd": [_p] * 3 + [_i64] * 4 + [_i, _p, _sz, _p],
+    "cvae_conv_s1_wgrad_workspace_bytes": [_i64] * 4 + [_i],
+    "cvae_conv_s1_wgrad": [_p] * 4 + [_i64] * 4 + [_i, _i, _p, _sz, _p],
+    "cvae_conv_s1_c1_wgrad_workspace_bytes": [_i64] * 3,
+    "cvae_conv_s1_c1_wgrad": [_p] * 4 + [_i64] * 4 + [_i, _p, _sz, _p],
+    "cvae_latent_to_grid_wgrad": [_p] * 4 + [_i64] * 4 + [_i, _p],
     "cvae_mlp_heads_fwd": [_p, _i, _p, _i, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "cvae_mlp_heads_train_workspace_bytes": [_p, _i, _p, _i, _i64],
     "cvae_mlp_heads_bwd_workspace_bytes": [_p, _i, _p, _i, _i64],
@@ -157,7 +163,8 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
             "cvae_mlp_heads_train_workspace_bytes": _sz, "cvae_mlp_heads_bwd_workspace_bytes": _sz,
-            "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz}
+            "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,
+            "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

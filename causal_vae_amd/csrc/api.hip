@@ -1,7 +1,7 @@
 // api.hip — version / error strings of the C ABI (include/cvae_hip.h).
 #include "common.h"
 
-extern "C" int cvae_version(void) { return 204; }   // 0.2.4
+extern "C" int cvae_version(void) { return 205; }   // 0.2.5
 
 extern "C" const char* cvae_strerror(int code) {
     switch (code) {

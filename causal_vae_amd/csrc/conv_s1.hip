@@ -478,7 +478,400 @@ int l2g_bwd_kq_pad(int64_t K) {                                         // threa
 }
 int64_t l2g_bwd_slabs(int64_t P, int64_t C) { return (C / L2GB_CB) * ((P + L2GB_PB - 1) / L2GB_PB); }
 
+// ------------------------------------------------------------------------------------------------ weight gradient of the stride-1 window convs
+// dWmat[n][tap][ci] = sum over pixels of g[pixel][n] x[pixel + tap][ci]: a GEMM whose K runs over the B H W pixels.  The matrix is cut into 32 x 32 blocks
+// (n block nb, ci block cb: a "pair") times the taps; channel counts below 32 are padded with zero channels in LDS.  A workgroup stages the family's 8 x 16
+// tile of x with its halo and the tile of g (zeros outside the image) channels-last, as the forward does; a wave owns one pair and every TS-th tap and keeps
+// those blocks in registers while the workgroup walks tiles blockIdx.x, + slabs, ..: the pixel index is the MFMA's k, A = g (rows n), B = x (columns ci).
+//   C = 128: 16 pairs, 4 per workgroup (one n block, the four ci blocks), grid.y = 4: the split over (tap, co) that keeps a slab's owner count low
+//   C = 64:  4 pairs, one workgroup        C = 32, 16: one pair, the 9 taps dealt over the 4 waves        SUBPIXEL: 2 pairs (py), 2 waves each over the 4 taps
+// The blocks leave as part[slab][pair][tap][32][32] (only rows and columns that exist are written); s1w_finish adds the slabs in slab order and writes the torch
+// layout; the bias gradient rides along: thread t < GN adds channel t of the staged g tile, pixel by pixel, as a compensated (Kahan) fp32 sum — a plain chain
+// over the 10^5 .. 10^7 pixels of a channel loses digits an eager sum keeps; sum and compensation both leave in the slab, and s1w_finish adds them the same way.
+struct KahanSum {
+    float s = 0.f, c = 0.f;                                             // the value is s - c
+    __device__ __forceinline__ void add(float v) {
+        const float y = v - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+template <typename T, int C, int FORM> struct S1WGeom {
+    static constexpr bool SUB = FORM == CVAE_CONV_S1_SUBPIXEL;
+    static constexpr int WIN = SUB ? 2 : 3, PADL = SUB ? 0 : 1, TAPS = WIN * WIN;
+    static constexpr int N = SUB ? 64 : C;                              // rows of the matrix: (py, px, co) in the sub-pixel form
+    static constexpr int COUT = SUB ? 16 : C;
+    static constexpr int CP = C < 32 ? 32 : C, NP = N < 32 ? 32 : N;
+    static constexpr int CB = CP / 32, NB = NP / 32, PAIRS = NB * CB;
+    static constexpr int PW = PAIRS >= 4 ? 4 : PAIRS, TS = 4 / PW;       // pairs per workgroup, waves per pair
+    static constexpr int NTW = (TAPS + TS - 1) / TS;                    // accumulator blocks per wave
+    static constexpr int GROUPS = PAIRS / PW;                           // grid.y
+    static constexpr int GN = GROUPS > 1 ? 32 : NP;                     // channels of g a workgroup stages
+    static_assert(GROUPS == 1 || PW == CB, "a workgroup of a split layer owns one n block");
+    static constexpr int HR = S1_TH + WIN - 1, HC = S1_TW + WIN - 1;
+    static constexpr int E16 = 16 / sizeof(T);
+    static constexpr int XPITCH = CP + E16, GPITCH = GN + E16;
+    static constexpr int SLAB = PAIRS * TAPS * 1024;
+    static constexpr size_t LDS = ((size_t)HR * HC * XPITCH + (size_t)S1_TH * S1_TW * GPITCH) * sizeof(T);
+    static constexpr int MAX_SLABS = C >= 128 ? 64 : (C == 64 ? 256 : 512);
+};
+
+template <typename T, int C, int FORM>
+__global__ __launch_bounds__(256) void conv_s1_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ g, float* __restrict__ part, float* __restrict__ pbias,
+                                                            int H, int W, int tiles_x, int tiles_y, int tiles, int slabs) {
+    using G = S1WGeom<T, C, FORM>;
+    constexpr bool BF = std::is_same<T, bf16>::value;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    T* hs = (T*)smem;                                                   // [HR * HC][XPITCH]
+    T* gs = hs + G::HR * G::HC * G::XPITCH;                             // [128][GPITCH]
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int ts = wave % G::TS, pair = blockIdx.y * G::PW + wave / G::TS, nb = pair / G::CB, cb = pair % G::CB;
+    const int goff = G::GROUPS > 1 ? blockIdx.y * 32 : 0;               // first channel of g this workgroup stages
+    const int arow = nb * 32 - goff + r, bcol = cb * 32 + r;
+    f32x16 acc[G::NTW];
+#pragma unroll
+    for (int i = 0; i < G::NTW; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+    KahanSum bsum;
+    for (int tile = blockIdx.x; tile < tiles; tile += slabs) {
+        const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y;
+        const int64_t b = tile / (tiles_x * tiles_y);
+        const int x0 = tx * S1_TW, y0 = ty * S1_TH;
+        const T* xb = x + b * (int64_t)H * W * C;
+        __syncthreads();                                                // the previous tile's fragment reads are done
+        constexpr int XPP = G::CP / G::E16, GPP = G::GN / G::E16;
+        for (int i = t; i < G::HR * G::HC * XPP; i += 256) {
+            const int pos = i / XPP, piece = i - pos * XPP;
+            const int hy = pos / G::HC, hx = pos - hy * G::HC;
+            const int gy = y0 - G::PADL + hy, gx = x0 - G::PADL + hx;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (piece * G::E16 < C && gy >= 0 && gy < H && gx >= 0 && gx < W) v = *(const uint4*)(xb + ((int64_t)gy * W + gx) * C + piece * G::E16);
+            *(uint4*)(hs + pos * G::XPITCH + piece * G::E16) = v;
+        }
+        for (int i = t; i < S1_TH * S1_TW * GPP; i += 256) {
+            const int p = i / GPP, piece = i - p * GPP;
+            const int gy = y0 + (p >> 4), gx = x0 + (p & 15), ch = goff + piece * G::E16;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (ch < G::N && gy < H && gx < W) {
+                if constexpr (G::SUB) {                                 // channel (py, px, co) of position (gy, gx) is g[2 gy + py][2 gx + px][co]
+                    const int q = ch >> 4;
+                    v = *(const uint4*)(g + (((b * 2 * H + 2 * gy + (q >> 1)) * (int64_t)(2 * W)) + 2 * gx + (q & 1)) * 16 + (ch & 15));
+                } else {
+                    v = *(const uint4*)(g + ((b * H + gy) * (int64_t)W + gx) * C + ch);
+                }
+            }
+            *(uint4*)(gs + p * G::GPITCH + piece * G::E16) = v;
+        }
+        __syncthreads();
+        if (t < G::GN)
+            for (int p = 0; p < S1_TH * S1_TW; ++p) bsum.add(to_f32(gs[p * G::GPITCH + t]));
+        if constexpr (BF) {
+            // step s = tile row s: lane half h holds pixels (s, 8 h + j), j = 0 .. 7, in the instruction's k slots of both operands
+#pragma unroll 1
+            for (int s = 0; s < S1_TH; ++s) {
+                bf16x8 av;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) av[j] = gs[(16 * s + 8 * h + j) * G::GPITCH + arow];
+#pragma unroll
+                for (int i = 0; i < G::NTW; ++i) {
+                    const int tap = ts + i * G::TS;
+                    if (tap < G::TAPS) {                                // the same for the whole wave
+                        const int dy = tap / G::WIN, dx = tap - dy * G::WIN;
+                        bf16x8 bv;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bv[j] = hs[((s + dy) * G::HC + 8 * h + j + dx) * G::XPITCH + bcol];
+                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i], 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+            // 32x32x2: the instruction's k index is the lane half: pixel 2 pp + h
+#pragma unroll 2
+            for (int pp = 0; pp < S1_TH * S1_TW / 2; ++pp) {
+                const int p = 2 * pp + h, ly = p >> 4, lx = p & 15;
+                const float av = gs[p * G::GPITCH + arow];
+#pragma unroll
+                for (int i = 0; i < G::NTW; ++i) {
+                    const int tap = ts + i * G::TS;
+                    if (tap < G::TAPS) {
+                        const int dy = tap / G::WIN, dx = tap - dy * G::WIN;
+                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, hs[((ly + dy) * G::HC + lx + dx) * G::XPITCH + bcol], acc[i], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    // lane (r, h) holds rows 8 g + 4 h + e (n) of column r (ci) in register 4 g + e
+    float* out = part + ((int64_t)blockIdx.x * G::PAIRS + pair) * G::TAPS * 1024;
+#pragma unroll
+    for (int i = 0; i < G::NTW; ++i) {
+        const int tap = ts + i * G::TS;
+        if (tap < G::TAPS && bcol < C) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = 8 * (e >> 2) + 4 * h + (e & 3);
+                if (nb * 32 + row < G::N) out[(tap * 32 + row) * 32 + r] = acc[i][e];
+            }
+        }
+    }
+    if (t < G::GN && goff + t < G::N) {
+        pbias[((int64_t)blockIdx.x * 2) * G::NP + goff + t] = bsum.s;
+        pbias[((int64_t)blockIdx.x * 2 + 1) * G::NP + goff + t] = -bsum.c;
+    }
+}
+
+// one thread per element of a slab: the slabs added in slab order, the sum written to the torch layout; the last block adds the bias partials
+template <int C, int FORM>
+__global__ __launch_bounds__(256) void s1w_finish_kernel(const float* __restrict__ part, const float* __restrict__ pbias, float* __restrict__ dW, float* __restrict__ db,
+                                                         int slabs) {
+    using G = S1WGeom<float, C, FORM>;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == G::SLAB / 256) {
+        const int co = threadIdx.x;
+        if (co >= G::COUT || !db) return;
+        KahanSum s;
+        for (int q = 0; q < 2 * slabs; ++q)                             // rows 2 q, 2 q + 1 of slab q: the sum and its compensation
+            for (int u = 0; u < G::N / G::COUT; ++u) s.add(pbias[(int64_t)q * G::NP + u * G::COUT + co]);
+        db[co] = s.s - s.c;
+        return;
+    }
+    const int col = idx & 31, row = (idx >> 5) & 31, ut = idx >> 10, tap = ut % G::TAPS, pair = ut / G::TAPS;
+    const int n = (pair / G::CB) * 32 + row, ci = (pair % G::CB) * 32 + col;
+    if (n >= G::N || ci >= C) return;
+    int o;
+    if constexpr (G::SUB) {
+        const int q = n >> 4, co = n & 15, py = q >> 1, px = q & 1, dy = tap >> 1, dx = tap & 1;
+        const int ky = py ? (dy ? 0 : 2) : (dy ? -1 : 1), kx = px ? (dx ? 0 : 2) : (dx ? -1 : 1);
+        if (ky < 0 || kx < 0) return;                                   // no tap of the transposed conv
+        o = (ci * 16 + co) * 9 + ky * 3 + kx;
+    } else {
+        o = (n * C + ci) * 9 + tap;
+    }
+    float s = 0.f;
+    for (int q = 0; q < slabs; ++q) s += part[(int64_t)q * G::SLAB + idx];
+    dW[o] = s;
+}
+
+struct S1WArgs { const void *x, *g; float *dW, *db, *ws; int64_t B, H, W; hipStream_t st; };
+int64_t s1w_tiles(int64_t B, int64_t H, int64_t W) { return B * ((H + S1_TH - 1) / S1_TH) * ((W + S1_TW - 1) / S1_TW); }
+template <typename T, int C, int FORM> int conv_s1_wgrad_launch(const S1WArgs& a) {
+    using G = S1WGeom<T, C, FORM>;
+    static_assert(G::LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
+    auto kern = conv_s1_wgrad_kernel<T, C, FORM>;
+    if (G::LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    const int tiles_x = (int)((a.W + S1_TW - 1) / S1_TW), tiles_y = (int)((a.H + S1_TH - 1) / S1_TH), tiles = (int)s1w_tiles(a.B, a.H, a.W);
+    const int slabs = tiles < G::MAX_SLABS ? tiles : G::MAX_SLABS;
+    float* pbias = a.ws + (int64_t)slabs * G::SLAB;
+    hipLaunchKernelGGL(kern, dim3((unsigned)slabs, G::GROUPS), dim3(256), G::LDS, a.st, (const T*)a.x, (const T*)a.g, a.ws, pbias, (int)a.H, (int)a.W, tiles_x, tiles_y,
+                       tiles, slabs);
+    CVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((s1w_finish_kernel<C, FORM>), dim3(G::SLAB / 256 + 1), dim3(256), 0, a.st, (const float*)a.ws, (const float*)pbias, a.dW, a.db, slabs);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+// f(Int<C>{}, Int<FORM>{}) for a supported (C, form); false otherwise
+template <typename F> bool s1w_with_layer(int64_t C, int form, F&& f) {
+    if (form == CVAE_CONV_S1_K3) {
+        if (C == 16) return f(Int<16>{}, Int<CVAE_CONV_S1_K3>{}), true;
+        if (C == 32) return f(Int<32>{}, Int<CVAE_CONV_S1_K3>{}), true;
+        if (C == 64) return f(Int<64>{}, Int<CVAE_CONV_S1_K3>{}), true;
+        if (C == 128) return f(Int<128>{}, Int<CVAE_CONV_S1_K3>{}), true;
+    } else if (form == CVAE_CONV_S1_SUBPIXEL) {
+        if (C == 16) return f(Int<16>{}, Int<CVAE_CONV_S1_SUBPIXEL>{}), true;
+        if (C == 32) return f(Int<32>{}, Int<CVAE_CONV_S1_SUBPIXEL>{}), true;
+    }
+    return false;
+}
+
+// ------------------------------------------------------------------------------------------------ weight gradient of Conv2d(16 -> 1, k3, s1, p1)
+// dW[ci][ky][kx] = sum over pixels q of x[q][ci] g[q - (ky - 1, kx - 1)], dbias = sum g: 145 sums over all pixels.  A thread walks pixels i, i + 256 blocks, ..
+// with its 145 sums in registers (x read once with 16-byte loads, the nine g values from the cache); a workgroup adds its threads' sums in a fixed tree and
+// leaves 145 partials; c1w_finish adds the workgroups in order.
+#define C1W_MAX_BLOCKS 1024
+#define C1W_SUMS (9 * C1_CIN + 1)
+#define C1W_PITCH 148
+template <typename T>
+__global__ __launch_bounds__(256) void conv_s1_c1_wgrad_kernel(const T* __restrict__ x, const float* __restrict__ g, float* __restrict__ part, int64_t B, int H, int W) {
+    __shared__ float red[4][C1W_SUMS];
+    float acc[9][C1_CIN], bs = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int ci = 0; ci < C1_CIN; ++ci) acc[tap][ci] = 0.f;
+    const int64_t total = B * H * W;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int xx = (int)(i % W), yy = (int)((i / W) % H);
+        const float* gb = g + (i / ((int64_t)W * H)) * (int64_t)H * W;
+        float xv[C1_CIN];
+        load_f32(x + i * C1_CIN, xv);
+        bs += gb[(int64_t)yy * W + xx];
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int sy = yy + 1 - ky, sx = xx + 1 - kx;
+                const float gv = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? gb[(int64_t)sy * W + sx] : 0.f;
+#pragma unroll
+                for (int ci = 0; ci < C1_CIN; ++ci) acc[ky * 3 + kx][ci] = fmaf(xv[ci], gv, acc[ky * 3 + kx][ci]);
+            }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int ci = 0; ci < C1_CIN; ++ci) {
+            const float v = wave_sum(acc[tap][ci]);
+            if (lane == 0) red[wave][tap * C1_CIN + ci] = v;
+        }
+    bs = wave_sum(bs);
+    if (lane == 0) red[wave][9 * C1_CIN] = bs;
+    __syncthreads();
+    if (threadIdx.x < C1W_SUMS) part[(int64_t)blockIdx.x * C1W_PITCH + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+__global__ __launch_bounds__(256) void c1w_finish_kernel(const float* __restrict__ part, float* __restrict__ dW, float* __restrict__ db, int blocks) {
+    const int i = threadIdx.x;
+    if (i >= C1W_SUMS) return;
+    float s = 0.f;
+    for (int q = 0; q < blocks; ++q) s += part[(int64_t)q * C1W_PITCH + i];
+    if (i == 9 * C1_CIN) {
+        if (db) db[0] = s;
+    } else {
+        dW[(i % C1_CIN) * 9 + i / C1_CIN] = s;                         // [1][ci][ky][kx]
+    }
+}
+int64_t c1w_blocks(int64_t B, int64_t H, int64_t W) {
+    const int64_t n = (B * H * W + 255) / 256;
+    return n < C1W_MAX_BLOCKS ? n : C1W_MAX_BLOCKS;
+}
+
+// ------------------------------------------------------------------------------------------------ weight gradient of latent -> grid
+// dW[n][k] = sum_b G[b][n] z[b][k], n = c P + p, G[b][c P + p] = g[b][p][c]; dbias[n] = sum_b G[b][n].  A workgroup owns 16 consecutive rows n: thread i
+// holds float4 pieces i, i + 256, .. of the 16 x K block in registers and adds the batch rows in order, 16 at a time through LDS (z and the 16 x 16 g values);
+// the block leaves once, 16-byte stores along the rows.
+#define L2GW_ROWS 16
+template <typename T>
+__global__ __launch_bounds__(256) void l2g_wgrad_kernel(const T* __restrict__ g, const float* __restrict__ z, float* __restrict__ dW, float* __restrict__ db, int64_t B,
+                                                        int K, int64_t P, int C) {
+    __shared__ __attribute__((aligned(16))) float zs[L2G_BT * L2G_KMAX];
+    __shared__ float gsm[L2G_BT][L2GW_ROWS];
+    const int t = threadIdx.x, k4 = K >> 2, items = L2GW_ROWS * k4;
+    const int64_t n0 = (int64_t)blockIdx.x * L2GW_ROWS, N = P * C;
+    constexpr int PER = L2GW_ROWS * (L2G_KMAX / 4) / 256;
+    float4 acc[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float bsum = 0.f;
+    for (int64_t b0 = 0; b0 < B; b0 += L2G_BT) {
+        const int nb = (int)(B - b0 < L2G_BT ? B - b0 : L2G_BT);
+        __syncthreads();
+        for (int i = t; i < nb * k4; i += 256) ((float4*)zs)[i] = ((const float4*)(z + b0 * K))[i];
+        {
+            const int bb = t >> 4, rr = t & 15;
+            const int64_t n = n0 + rr;
+            gsm[bb][rr] = (bb < nb && n < N) ? to_f32(g[((b0 + bb) * P + n % P) * C + n / P]) : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = t + 256 * j;
+            if (i < items) {
+                const int row = i / k4, kq = i - row * k4;
+                for (int bb = 0; bb < nb; ++bb) {
+                    const float gv = gsm[bb][row];
+                    const float4 zv = ((const float4*)zs)[bb * k4 + kq];
+                    acc[j].x = fmaf(gv, zv.x, acc[j].x); acc[j].y = fmaf(gv, zv.y, acc[j].y);
+                    acc[j].z = fmaf(gv, zv.z, acc[j].z); acc[j].w = fmaf(gv, zv.w, acc[j].w);
+                }
+            }
+        }
+        if (t < L2GW_ROWS)
+            for (int bb = 0; bb < nb; ++bb) bsum += gsm[bb][t];
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = t + 256 * j;
+        if (i < items) {
+            const int row = i / k4, kq = i - row * k4;
+            if (n0 + row < N) ((float4*)(dW + (n0 + row) * K))[kq] = acc[j];
+        }
+    }
+    if (db && t < L2GW_ROWS && n0 + t < N) db[n0 + t] = bsum;
+}
+
 }  // namespace
+
+extern "C" size_t cvae_conv_s1_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int form) {
+    if (B <= 0 || !s1_dims_ok(B, H, W) || s1w_tiles(B, H, W) > 0x7fffffff) return 0;
+    size_t n = 0;
+    s1w_with_layer(C, form, [&](auto cv, auto fv) {
+        using G = S1WGeom<float, decltype(cv)::value, decltype(fv)::value>;
+        const int64_t tiles = s1w_tiles(B, H, W), slabs = tiles < G::MAX_SLABS ? tiles : G::MAX_SLABS;
+        n = (size_t)slabs * (G::SLAB + 2 * G::NP) * sizeof(float);
+    });
+    return n;
+}
+
+extern "C" int cvae_conv_s1_wgrad(const void* x, const void* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, int form, int dtype,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (B <= 0 || !s1_dims_ok(B, H, W) || s1w_tiles(B, H, W) > 0x7fffffff) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    const size_t need = cvae_conv_s1_wgrad_workspace_bytes(B, H, W, C, form);
+    if (need == 0) return CVAE_E_UNSUPPORTED;
+    if (!x || !g || !dW) return CVAE_E_NULLPTR;
+    if (!aligned16(x) || !aligned16(g) || !aligned16(workspace)) return CVAE_E_UNSUPPORTED;
+    if (!workspace || workspace_bytes < need) return CVAE_E_WORKSPACE;
+    const S1WArgs a{x, g, dW, dbias, (float*)workspace, B, H, W, (hipStream_t)stream};
+    int rc = CVAE_E_UNSUPPORTED;
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        s1w_with_layer(C, form, [&](auto cv, auto fv) { rc = conv_s1_wgrad_launch<T, decltype(cv)::value, decltype(fv)::value>(a); });
+    });
+    return rc;
+}
+
+extern "C" size_t cvae_conv_s1_c1_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W) {
+    if (B <= 0 || !c1_dims_ok(B, H, W)) return 0;
+    return (size_t)c1w_blocks(B, H, W) * C1W_PITCH * sizeof(float);
+}
+
+extern "C" int cvae_conv_s1_c1_wgrad(const void* x, const float* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    if (B <= 0 || !c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
+    if (!x || !g || !dW) return CVAE_E_NULLPTR;
+    if (!aligned16(x)) return CVAE_E_UNSUPPORTED;
+    if (!workspace || workspace_bytes < cvae_conv_s1_c1_wgrad_workspace_bytes(B, H, W)) return CVAE_E_WORKSPACE;
+    const int blocks = (int)c1w_blocks(B, H, W);
+    const hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(conv_s1_c1_wgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, g, part, B, (int)H, (int)W);
+    });
+    CVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(c1w_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)part, dW, dbias, blocks);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_latent_to_grid_wgrad(const void* g, const float* z, float* dW, float* dbias, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream) {
+    if (B <= 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
+    if (!g || !z || !dW) return CVAE_E_NULLPTR;
+    if (!aligned16(z) || !aligned16(dW)) return CVAE_E_UNSUPPORTED;
+    const int64_t blocks = (P * C + L2GW_ROWS - 1) / L2GW_ROWS;
+    if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
+    const hipStream_t st = (hipStream_t)stream;
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(l2g_wgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)g, z, dW, dbias, B, (int)K, P, (int)C);
+    });
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
 
 extern "C" int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form) {
     if (form == CVAE_CONV_S1_K3) return (Cin == Cout && (Cin == 32 || Cin == 64 || Cin == 128)) ? Cout * ((9 * Cin + S1_KPAD - 1) / S1_KPAD * S1_KPAD) : 0;

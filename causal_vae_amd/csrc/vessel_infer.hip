@@ -301,6 +301,50 @@ __global__ __launch_bounds__(64) void row_diff_finish_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the way back through the fold
+// One workgroup per (layer, BatchNorm channel c): thread t walks elements t, t + 256, .. of the channel's Cin x 9 weights (dw = s dwf written on the way, the
+// products dwf w added in that order), then a fixed tree over the workgroup; thread 0 finishes db, dgamma and dbeta.
+struct FoldBwdEntry {
+    const float *w, *bias, *gamma, *mean, *var, *dwf, *dbf;
+    float *dw, *db, *dgamma, *dbeta;
+    float eps;
+    int kind, cout, cin;
+};
+struct FoldBwdTable {
+    FoldBwdEntry e[FOLD_MAX];
+    int end[FOLD_MAX];            // exclusive prefix sums of cout
+    int count;
+};
+
+__global__ __launch_bounds__(256) void fold_bn_conv_bwd_kernel(const FoldBwdTable T) {
+    __shared__ float red[4];
+    int k = 0;
+    while (k < T.count - 1 && (int)blockIdx.x >= T.end[k]) ++k;
+    const FoldBwdEntry& E = T.e[k];
+    const int c = (int)blockIdx.x - (k ? T.end[k - 1] : 0), t = threadIdx.x;
+    const bool convt = E.kind != CVAE_FOLD_CONV_K3S1, k4 = E.kind == CVAE_FOLD_CONVT_K3S2;
+    const float rstd = E.gamma ? rsqrtf(E.var[c] + E.eps) : 1.f, s = E.gamma ? E.gamma[c] * rstd : 1.f;
+    float part = 0.f;
+    for (int i = t; i < E.cin * 9; i += 256) {
+        const int ci = i / 9, tap = i - ci * 9;
+        const size_t pair = convt ? (size_t)ci * E.cout + c : (size_t)c * E.cin + ci;
+        const float gv = E.dwf[k4 ? pair * 16 + (tap / 3) * 4 + tap % 3 : pair * 9 + tap];
+        E.dw[pair * 9 + tap] = s * gv;
+        part = fmaf(gv, E.w[pair * 9 + tap], part);
+    }
+    part = wave_sum(part);
+    if ((t & 63) == 0) red[t >> 6] = part;
+    __syncthreads();
+    if (t == 0) {
+        const float tot = ((red[0] + red[1]) + red[2]) + red[3], b = E.bias ? E.bias[c] : 0.f, gb = E.dbf[c];
+        if (E.db) E.db[c] = s * gb;
+        if (E.gamma) {
+            E.dgamma[c] = rstd * (tot + gb * (b - E.mean[c]));
+            E.dbeta[c] = gb;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ stack mean / std
 // One thread per group of 4 elements: the K <= 16 inputs' loads issued together (K a template argument), mean = (x_0 + .. + x_{K-1}) / K, then
 // std = sqrt(sum_k (x_k - mean)^2 / (K - 1)) — the two-pass form; K = 1 gives 0 / 0 = NaN, as torch.std does.
@@ -416,6 +460,42 @@ extern "C" int cvae_fold_bn_conv(int count, const float* const* w, const int* ki
         T.end[k] = (int)blocks;
     }
     hipLaunchKernelGGL(fold_bn_conv_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_fold_bn_conv_bwd(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
+                                     const float* const* mean, const float* const* var, const float* eps, const float* const* dwf, const float* const* dbf,
+                                     float* const* dw, float* const* db, float* const* dgamma, float* const* dbeta, void* stream) {
+    if (count <= 0) return CVAE_E_BADSHAPE;
+    if (count > FOLD_MAX) return CVAE_E_UNSUPPORTED;
+    if (!w || !kind || !dims || !dwf || !dbf || !dw || !eps) return CVAE_E_NULLPTR;
+    FoldBwdTable T{};
+    T.count = count;
+    int64_t blocks = 0;
+    for (int k = 0; k < count; ++k) {
+        FoldBwdEntry& E = T.e[k];
+        const int64_t Cout = dims[2 * k], Cin = dims[2 * k + 1];
+        if (Cout <= 0 || Cin <= 0 || Cout * Cin > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
+        if (kind[k] != CVAE_FOLD_CONVT_K3S2 && kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL) return CVAE_E_UNSUPPORTED;
+        if (!w[k] || !dwf[k] || !dbf[k] || !dw[k]) return CVAE_E_NULLPTR;
+        const bool bn = gamma && gamma[k];
+        if (bn && (!mean || !mean[k] || !var || !var[k] || !dgamma || !dgamma[k] || !dbeta || !dbeta[k])) return CVAE_E_NULLPTR;
+        E.w = w[k]; E.dwf = dwf[k]; E.dbf = dbf[k]; E.dw = dw[k];
+        E.bias = bias ? bias[k] : nullptr;
+        E.db = db ? db[k] : nullptr;
+        E.gamma = bn ? gamma[k] : nullptr;
+        E.mean = bn ? mean[k] : nullptr;
+        E.var = bn ? var[k] : nullptr;
+        E.dgamma = bn ? dgamma[k] : nullptr;
+        E.dbeta = bn ? dbeta[k] : nullptr;
+        E.eps = eps[k];
+        E.kind = kind[k];
+        E.cout = (int)Cout; E.cin = (int)Cin;
+        blocks += Cout;
+        T.end[k] = (int)blocks;
+    }
+    hipLaunchKernelGGL(fold_bn_conv_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }

@@ -2038,21 +2038,31 @@ def conv_s1_pack_weights(mats):
     return outs
 
 
+def _cl_operand(what, x, form, forms):
+    """x must be a contiguous channels-last [B, H, W, C] tensor and form one of `forms` (shared by the forward, input-gradient and weight-gradient wrappers)"""
+    if x.dim() != 4 or not x.is_contiguous() or form not in forms:
+        raise L.CvaeError(f"{what}: a contiguous channels-last [B, H, W, C] tensor expected, got {tuple(x.shape)} in form {form}")
+
+
+def _like_operands(what, oshape, dtype, **tensors):
+    """every tensor (name = tensor or None) must be contiguous, of shape oshape and of dtype"""
+    for name, t in tensors.items():
+        if t is not None and (tuple(t.shape) != tuple(oshape) or t.dtype != dtype or not t.is_contiguous()):
+            raise L.CvaeError(f"{what}: the {name} must be a contiguous {tuple(oshape)} {dtype} tensor")
+
+
 def _conv_s1_operands(what, x, wmat, form, forms, geom, **like_out):
     """The operand checks conv_s1 and conv_s1_bwd_data share: x a contiguous channels-last [B, H, W, C] tensor and form one of `forms`; wmat the matrix of
     the layer geom(B, H, W, C) -> (Cin, Cout, output shape) in x's dtype, contiguous, cvae_conv_s1_weight_elems long; every like_out tensor (name = tensor
     or None) contiguous, of the output's shape and x's dtype.  Returns geom's triple."""
-    if x.dim() != 4 or not x.is_contiguous() or form not in forms:
-        raise L.CvaeError(f"{what}: a contiguous channels-last [B, H, W, C] tensor expected, got {tuple(x.shape)} in form {form}")
+    _cl_operand(what, x, form, forms)
     cin, cout, oshape = geom(*x.shape)
     n = lib.cvae_conv_s1_weight_elems(cin, cout, form)
     if n == 0:
         raise L.CvaeError(f"{what}: {cin} -> {cout} channels in form {form}: {L.strerror(-3)}")
     if wmat.dtype != x.dtype or wmat.numel() != n or not wmat.is_contiguous():
         raise L.CvaeError(f"{what}: weight matrix {tuple(wmat.shape)} {wmat.dtype} does not fit {cin} -> {cout} channels in {x.dtype} ({n} elements)")
-    for name, t in like_out.items():
-        if t is not None and (tuple(t.shape) != oshape or t.dtype != x.dtype or not t.is_contiguous()):
-            raise L.CvaeError(f"{what}: the {name} must be a contiguous {oshape} {x.dtype} tensor")
+    _like_operands(what, oshape, x.dtype, **like_out)
     return cin, cout, oshape
 
 
@@ -2172,6 +2182,99 @@ def latent_to_grid(z, weight, bias, channels, out_dtype):
         nb = min(LATENT_TO_GRID_ROWS, B - b0)
         check(lib.cvae_latent_to_grid(ptr(z[b0:]), ptr(w), ptr(b), ptr(out[b0:]), nb, K, P, channels, L.dtype_code(out_dtype), stream()), "latent_to_grid")
     return out
+
+
+# ---- the decoder's weight gradients (eval-mode BatchNorm): fp32 results, fixed-order sums, B >= 1 ------------------------------------------
+def _wgrad_operands(what, x, form, forms, gshape, gdtype=None):
+    """_conv_s1_operands' checks for a weight gradient (there is no weight matrix to check): x a contiguous channels-last [B, H, W, C] fp32 or bf16 tensor with
+    B >= 1, form one of `forms`, and the cotangent g contiguous, of shape gshape(B, H, W, C) and of x's dtype (gdtype: another one)."""
+    _cl_operand(what, x, form, forms)
+    if x.shape[0] < 1 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise L.CvaeError(f"{what}: B >= 1 rows in float32 or bfloat16 expected, got {tuple(x.shape)} {x.dtype}")
+    return lambda g: _like_operands(what, gshape(*x.shape), gdtype or x.dtype, cotangent=g)
+
+
+def conv_s1_wgrad(x, g, form):
+    """(dW, dbias) fp32 of conv_s1's layer from its input x [B, H, W, C] and the (already gated) cotangent g of its pre-activation (cvae_conv_s1_wgrad).
+    form CONV_S1_K3: nn.Conv2d(C, C, 3, 1, 1), C in {16, 32, 64, 128}, g [B, H, W, C] -> dW [C, C, 3, 3]; CONV_S1_SUBPIXEL: nn.ConvTranspose2d(C, 16, 3, 2, 1,
+    output_padding=1), C in {32, 16}, g [B, 2H, 2W, 16] -> dW [C, 16, 3, 3].  The gradient of the weight the conv ran with (the folded one), torch layout."""
+    L.require_gpu(x, g)
+    _forward_only("conv_s1_wgrad", x, g)
+    sub = form == CONV_S1_SUBPIXEL
+    _wgrad_operands("conv_s1_wgrad", x, form, (CONV_S1_K3, CONV_S1_SUBPIXEL), lambda B, H, W, Cc: (B, 2 * H, 2 * W, 16) if sub else (B, H, W, Cc))(g)
+    B, H, W, Cc = x.shape
+    nbytes = lib.cvae_conv_s1_wgrad_workspace_bytes(B, H, W, Cc, form)
+    if not nbytes:
+        raise L.CvaeError(f"conv_s1_wgrad: {Cc} channels in form {form} on {B} x {H} x {W}: {L.strerror(-3)}")
+    dW = _empty((Cc, 16 if sub else Cc, 3, 3), torch.float32, x)
+    db = _empty((16 if sub else Cc,), torch.float32, x)
+    _t, wp, wb = _scratch(nbytes, x)
+    check(lib.cvae_conv_s1_wgrad(ptr(x), ptr(g), ptr(dW), ptr(db), B, H, W, Cc, form, L.dtype_code(x.dtype), wp, wb, stream()), "conv_s1_wgrad")
+    return dW, db
+
+
+def conv_s1_c1_wgrad(x, g):
+    """(dW [1, 16, 3, 3], dbias [1]) fp32 of nn.Conv2d(16, 1, 3, 1, 1) from its channels-last input x [B, H, W, 16] (fp32 or bf16) and the fp32 image
+    cotangent g [B, 1, H, W] (cvae_conv_s1_c1_wgrad)."""
+    L.require_gpu(x, g)
+    _forward_only("conv_s1_c1_wgrad", x, g)
+    _wgrad_operands("conv_s1_c1_wgrad", x, CONV_S1_K3, (CONV_S1_K3,), lambda B, H, W, Cc: (B, 1, H, W), torch.float32)(g)
+    B, H, W, Cc = x.shape
+    if Cc != 16:
+        raise L.CvaeError(f"conv_s1_c1_wgrad: 16 input channels expected, got {tuple(x.shape)}: {L.strerror(-3)}")
+    dW, db = _empty((1, 16, 3, 3), torch.float32, x), _empty((1,), torch.float32, x)
+    _t, wp, wb = _scratch(lib.cvae_conv_s1_c1_wgrad_workspace_bytes(B, H, W), x)
+    check(lib.cvae_conv_s1_c1_wgrad(ptr(x), ptr(g), ptr(dW), ptr(db), B, H, W, 16, L.dtype_code(x.dtype), wp, wb, stream()), "conv_s1_c1_wgrad")
+    return dW, db
+
+
+def latent_to_grid_wgrad(g, z):
+    """(dW [C P, K], dbias [C P]) fp32 of latent_to_grid's nn.Linear: dW[c P + p][k] = sum_b g[b][p][c] z[b][k], rows in order (cvae_latent_to_grid_wgrad).
+    g: channels-last [B, P, C] fp32 or bf16 (the grid gradient as the backward chain holds it); z fp32 [B, K].  One launch for any B >= 1."""
+    L.require_gpu(g, z)
+    _forward_only("latent_to_grid_wgrad", g, z)
+    if (g.dim() != 3 or not g.is_contiguous() or g.shape[0] < 1 or g.dtype not in (torch.float32, torch.bfloat16) or z.dim() != 2 or z.dtype != torch.float32
+            or z.shape[0] != g.shape[0]):
+        raise L.CvaeError(f"latent_to_grid_wgrad: g {tuple(g.shape)} {g.dtype}, z {tuple(z.shape)} {z.dtype}")
+    B, P, Cc = g.shape
+    K = z.shape[1]
+    if K > 512 or K % 4 or Cc % 32:                                  # cvae_latent_to_grid's limits
+        raise L.CvaeError(f"latent_to_grid_wgrad: K {K}, C {Cc}: K <= 512, K % 4 == 0 and C % 32 == 0 expected: {L.strerror(-3)}")
+    dW, db = _empty((Cc * P, K), torch.float32, g), _empty((Cc * P,), torch.float32, g)
+    check(lib.cvae_latent_to_grid_wgrad(ptr(g), ptr(z.contiguous()), ptr(dW), ptr(db), B, K, P, Cc, L.dtype_code(g.dtype), stream()), "latent_to_grid_wgrad")
+    return dW, db
+
+
+def fold_bn_conv_bwd(entries):
+    """The way back through fold_bn_conv for up to 16 layers in ONE launch (cvae_fold_bn_conv_bwd).  entries: (weight, kind, bias, bn, dwf, dbf) with kind
+    FOLD_CONVT_K3S2 (dwf: the gradient of the k4 weight [Cin, Cout, 4, 4]), FOLD_CONV_K3S1 (dwf [Cout, Cin, 3, 3]) or FOLD_CONVT_K3S2_SUBPIXEL (dwf [Cin, Cout, 3, 3]),
+    dbf the folded bias's gradient [Cout], bn an eval-mode nn.BatchNorm2d (running statistics are constants).  Returns [(dw, db, dgamma, dbeta)] fp32, each of
+    its parameter's shape: dw = s dwf, db = s dbf, dgamma = rstd (sum dwf w + dbf (bias - mean)), dbeta = dbf with s = gamma rstd."""
+    import ctypes as C
+    k = len(entries)
+    if not 1 <= k <= 16:
+        raise L.CvaeError(f"fold_bn_conv_bwd: 1 to 16 layers per launch, got {k}")
+    rows, outs = [], []
+    for w, kind, bias, bn, dwf, dbf in entries:
+        L.require_gpu(w, bias, dwf, dbf)
+        _forward_only("fold_bn_conv_bwd", w, bias, dwf, dbf, bn.weight, bn.bias)
+        if kind not in (FOLD_CONVT_K3S2, FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL) or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+            raise L.CvaeError(f"fold_bn_conv_bwd: kind {kind} does not match a weight of shape {tuple(w.shape)}")
+        cout, cin = (w.shape[1], w.shape[0]) if kind in _FOLD_CONVT else (w.shape[0], w.shape[1])
+        want = tuple(w.shape[:2]) + ((4, 4) if kind == FOLD_CONVT_K3S2 else (3, 3))
+        if (tuple(dwf.shape) != want or tuple(dbf.shape) != (cout,) or dwf.dtype != torch.float32 or dbf.dtype != torch.float32 or not dwf.is_contiguous()
+                or bias is None or bn.running_mean is None or bn.weight is None or bn.num_features != cout):
+            raise L.CvaeError(f"fold_bn_conv_bwd: kind {kind}, weight {tuple(w.shape)}: gradients {tuple(dwf.shape)} / {tuple(dbf.shape)} (fp32 {want} / ({cout},) "
+                              "expected), a conv bias and an affine BatchNorm2d with running statistics")
+        f32 = lambda t: t.detach().float().contiguous()
+        rows.append((f32(w), kind, cout, cin, f32(bias), f32(bn.weight), f32(bn.running_mean), f32(bn.running_var), float(bn.eps), dwf, dbf.contiguous()))
+        outs.append((torch.empty_like(rows[-1][0]), _empty((cout,), torch.float32, w), _empty((cout,), torch.float32, w), _empty((cout,), torch.float32, w)))
+    vp = lambda v: (C.c_void_p * k)(*[t.data_ptr() for t in v])
+    col = lambda i: [r[i] for r in rows]
+    check(lib.cvae_fold_bn_conv_bwd(k, vp(col(0)), (C.c_int * k)(*col(1)), (C.c_int64 * (2 * k))(*[d for r in rows for d in (r[2], r[3])]), vp(col(4)), vp(col(5)),
+                                    vp(col(6)), vp(col(7)), (C.c_float * k)(*col(8)), vp(col(9)), vp(col(10)), vp([o[0] for o in outs]), vp([o[1] for o in outs]),
+                                    vp([o[2] for o in outs]), vp([o[3] for o in outs]), stream()), "fold_bn_conv_bwd")
+    return outs
 
 
 # ---- The dense heads of CausalViTVAE (csrc/heads.hip): a whole head in one launch ----------------------------------------------------

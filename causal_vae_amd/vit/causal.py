@@ -92,18 +92,26 @@ class CausalViTVAE(nn.Module):
 
     # ---- training the adapters on the frozen backbone -----------------------------------------------------------------------------
     _adapters_only = False
+    _train_decoder = False
 
     def head_parameters(self):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self):
+    def train_adapters(self, decoder=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
-        heads go to training mode.  Returns the list of head parameters, for the optimizer."""
+        heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
+        a default call after a decoder=True one switches the decoder's gradients off again).
+        decoder=True: the backbone's decoder learns too (backbone.train_decoder(): decoder_input and decoder ask for gradients, still in eval mode: BatchNorm2d on
+        its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters."""
         self.backbone.requires_grad_(False)
-        self._adapters_only = True
+        self.backbone.freeze_decoder()
+        self._adapters_only, self._train_decoder = True, bool(decoder)
         self.train()
-        return self.head_parameters()
+        if not decoder:
+            return self.head_parameters()
+        self.backbone.train_decoder()
+        return self.head_parameters() + list(self.backbone.decoder_input.parameters()) + list(self.backbone.decoder.parameters())
 
     def train(self, mode=True):
         """nn.Module.train; after train_adapters() the backbone stays in eval mode whatever `mode` is."""
@@ -115,8 +123,9 @@ class CausalViTVAE(nn.Module):
     def forward_train(self, x, m, t, eps=None):
         """The reference 6-tuple (recon_x, m_mu, mu, logvar, m_mu, m_logvar) attached to the autograd graph of the head parameters: backbone.cls_features
         under no_grad, enc_adapter, the morph predictor and dec_adapter in training mode (ops.mlp_heads_train: batch statistics, running statistics updated),
-        then backbone.decode_with_grad.  The backbone is fp32 or bf16; the heads are fp32.  Needs train_adapters() first."""
-        live = [k for k, p in self.backbone.named_parameters() if p.requires_grad]
+        then backbone.decode_with_grad.  The backbone is fp32 or bf16; the heads are fp32.  Needs train_adapters() first; after train_adapters(decoder=True)
+        the backbone's decoder parameters (and only those) may ask for gradients, and backward accumulates them (eval-mode decoder)."""
+        live = [k for k, p in self.backbone.named_parameters() if p.requires_grad and not (self._train_decoder and k.startswith(("decoder_input.", "decoder.")))]
         if self.backbone.training or live:
             raise RuntimeError("CausalViTVAE.forward_train trains the adapter heads on a frozen eval-mode backbone: call model.train_adapters() first "
                                f"(backbone.training={self.backbone.training}, {len(live)} backbone parameters require grad)")

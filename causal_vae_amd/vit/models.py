@@ -171,8 +171,9 @@ DECODER_CHANNELS = (128, 64, 32, 16, 16)     # outputs of the five transposed co
 # pairs; fold = their positions in the fold table; gates = its output is a LeakyReLU(0.01) output: the gate in the backward of whatever reads it.
 _Stage = namedtuple("_Stage", "kind layers fold gates")
 # What _decode_walk keeps of a stage for _decode_backward: gate_in (the stage's input when the stage before it gates, else None), inner (a ResBlock's inner
-# activation), mats (the backward matrix of every GEMM layer, in layer order), k4 (an "up" stage's folded k4 weight).
-_Step = namedtuple("_Step", "stage gate_in inner mats k4")
+# activation), mats (the backward matrix of every GEMM layer, in layer order), k4 (an "up" stage's folded k4 weight), x (the stage's input, kept only when
+# weight gradients are wanted: a ResBlock sum and the grid are no gates, so gate_in does not cover them).
+_Step = namedtuple("_Step", "stage gate_in inner mats k4 x")
 
 
 class ViTVAE(ViTVAEEncoder):
@@ -224,10 +225,11 @@ class ViTVAE(ViTVAEEncoder):
         return self._decode_walk(z, False, collect)[0]
 
     @torch.no_grad()
-    def _decode_walk(self, z, save, collect=None):
+    def _decode_walk(self, z, save, collect=None, keep_inputs=False):
         """The decoder's launches -> (image, saved).  save=False: the forward fold kinds, in bf16 one pack of the 8 GEMM matrices, saved = None.  save=True: the
         same launches with the fold's _GRAD kinds (one pack of 16: forward and backward matrices) and saved = ([_Step per stage], the output conv, its gate)
         for _decode_backward: DESIGN §13's set (the gates are the outputs of stages 0, 2, 4, 6 and 7; a ResBlock sum and the grid are no gates).
+        keep_inputs (with save): every step also keeps its stage's input, what the weight gradients are multiplied with; the launches are the same.
         collect (a dict, for tests): receives `grid` (decoder_input's output, channels-last [B, gh, gw, 256]), `stages` (the channels-last activation after
         each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order) and `res_inner` (the three ResBlock inner activations)."""
         dt = self.compute_dtype
@@ -246,6 +248,7 @@ class ViTVAE(ViTVAEEncoder):
         steps, gate = [], None                                         # gate: the stage's input when that is a LeakyReLU(0.01) output
         for st in plan:
             y = k4 = None
+            x_in = h if keep_inputs else None
             if st.kind == "up":
                 k4, b = folded[st.fold[0]]
                 _B, hh, ww, c = h.shape
@@ -260,57 +263,105 @@ class ViTVAE(ViTVAEEncoder):
                 if collect is not None:
                     collect["res_inner"].append(y)
             if save:
-                steps.append(_Step(st, gate, y, [bmats[k] for k in st.fold if k in bmats], k4))
+                steps.append(_Step(st, gate, y, [bmats[k] for k in st.fold if k in bmats], k4, x_in))
             gate = h if st.gates else None
             if collect is not None:
                 collect["stages"].append(h)
         return ops.conv_s1_c1(h, out_conv.weight, out_conv.bias), ((steps, out_conv, gate) if save else None)
 
     # ---- the gradient with respect to the latent (frozen decoder, eval mode) -----------------------------------------------------
+    _decoder_grads = False          # train_decoder(): decode_with_grad also accumulates the decoder parameters' gradients
+
     def freeze_decoder(self):
-        """requires_grad_(False) on decoder_input and decoder: what decode_with_grad asks for (it returns no weight gradients)."""
+        """requires_grad_(False) on decoder_input and decoder: what decode_with_grad asks for when it is to return no weight gradients."""
         self.decoder_input.requires_grad_(False)
         self.decoder.requires_grad_(False)
+        self._decoder_grads = False
         return self
+
+    def train_decoder(self):
+        """The counterpart of freeze_decoder(): requires_grad_(True) on decoder_input and decoder, and decode_with_grad from now on accumulates `.grad` on every
+        decoder parameter next to dz (DESIGN §15).  The decoder stays in EVAL mode: BatchNorm2d normalises with its running statistics, which are not updated;
+        its weight and bias learn, and so do the conv weights and biases, through the fold.  (The reference's vae.train() uses batch statistics: the one
+        difference of this path.)"""
+        self.decoder_input.requires_grad_(True)
+        self.decoder.requires_grad_(True)
+        self._decoder_grads = True
+        return self
+
+    def _decoder_params(self):
+        """The decoder's parameters in the order _DecodeWithGrad takes them and returns their gradients: decoder_input's weight and bias, then (conv weight, conv
+        bias, BatchNorm weight, BatchNorm bias) per fold-table entry, then the output conv's weight and bias."""
+        plan, out_conv = self._decoder_plan()
+        ps = [self.decoder_input.weight, self.decoder_input.bias]
+        for st in plan:
+            for conv, bn in st.layers:
+                ps += [conv.weight, conv.bias, bn.weight, bn.bias]
+        return ps + [out_conv.weight, out_conv.bias]
 
     def _check_grad_path(self, z):
         self._check_latent(z, "the decoder's gradient path runs through eval-mode BatchNorm only")
         live = sorted(f"{root}.{k}" for root in ("decoder_input", "decoder") for k, p in getattr(self, root).named_parameters() if p.requires_grad)
-        if live:
+        if live and not self._decoder_grads:
             raise CvaeError("ViTVAE.decode_with_grad returns the gradient with respect to z only, through a frozen decoder: these parameters ask for a gradient "
-                            f"that would silently stay None: {live} (call model.freeze_decoder())")
+                            f"that would silently stay None: {live} (call model.freeze_decoder(), or model.train_decoder() for their gradients)")
         require_gpu(z, self.decoder_input.weight)
 
-    def _decode_backward(self, saved, g_img):
+    def _decode_backward(self, saved, g_img, z=None):
         """dz [B, latent_dim] fp32 from the image cotangent [B, 1, H, W] fp32: the chain of DESIGN §13, _decode_walk's steps in reverse.  `g` is the gradient
         with respect to a transposed conv's PRE-activation (the producing epilogue applied leaky001' from the saved output) or to a ResBlock's output; no
-        activation-backward launch."""
+        activation-backward launch.
+        z (the walk's latent; the walk ran with keep_inputs): returns (dz, gradients of _decoder_params() in that order) — the same launches for dz, and next to
+        them each layer's weight gradient from its input and the `g` of its pre-activation, then ONE launch back through the fold."""
         steps, out_conv, out_gate = saved
         dt = self.compute_dtype
         B = g_img.shape[0]
+        folded = {}                                                    # fold-table position -> (gradient of the folded weight, of the folded bias)
+        d_out = ops.conv_s1_c1_wgrad(out_gate, g_img) if z is not None else None
         g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, out_gate, "leaky001", dt)
         for s in reversed(steps):
             act = "leaky001" if s.gate_in is not None else None
             if s.stage.kind == "sub":
+                if z is not None:
+                    folded[s.stage.fold[0]] = ops.conv_s1_wgrad(s.x, g, ops.CONV_S1_SUBPIXEL)
                 g = ops.conv_s1_bwd_data(g, s.mats[0], ops.CONV_S1_SUBPIXEL_T, cin=s.stage.layers[0][0].in_channels, gate=s.gate_in, gate_act=act)
             elif s.stage.kind == "res":
                 t = ops.conv_s1_bwd_data(g, s.mats[1], ops.CONV_S1_K3, gate=s.inner, gate_act="leaky02")
+                if z is not None:
+                    folded[s.stage.fold[1]] = ops.conv_s1_wgrad(s.inner, g, ops.CONV_S1_K3)
+                    folded[s.stage.fold[0]] = ops.conv_s1_wgrad(s.x, t, ops.CONV_S1_K3)
                 g = ops.conv_s1_bwd_data(t, s.mats[0], ops.CONV_S1_K3, resid=g, gate=s.gate_in, gate_act=act)
             else:
                 w = s.k4
                 _B, hh, ww, c = g.shape
+                if z is not None:
+                    folded[s.stage.fold[0]] = ops._conv_wgrad(s.x.view(B, 1, hh // 2, ww // 2, w.shape[0]), g.view(B, 1, hh, ww, c), 2, w.shape, want_lbias=True)
                 g = ops._conv_down(g.view(B, 1, hh, ww, c), ops.pack_weight(w, 2, False, dt), None, None, w.shape[0], 2, None).view(B, hh // 2, ww // 2, w.shape[0])
-        return ops.latent_to_grid_bwd(g.view(B, self.grid_h * self.grid_w, self.embed_dim), self.decoder_input.weight)
+        g = g.view(B, self.grid_h * self.grid_w, self.embed_dim)
+        dz = ops.latent_to_grid_bwd(g, self.decoder_input.weight)
+        if z is None:
+            return dz
+        grads = list(ops.latent_to_grid_wgrad(g, z))
+        kinds = {"up": ops.FOLD_CONVT_K3S2, "sub": ops.FOLD_CONVT_K3S2_SUBPIXEL, "res": ops.FOLD_CONV_K3S1}
+        table = [(conv.weight, kinds[s.stage.kind], conv.bias, bn) + tuple(folded[k]) for s in steps for (conv, bn), k in zip(s.stage.layers, s.stage.fold)]
+        for quad in ops.fold_bn_conv_bwd(table):
+            grads += quad
+        return dz, grads + list(d_out)
 
     def decode_with_grad(self, z, collect=None):
         """decode(z) (the same launches, the same bits) as a differentiable function of z: backward returns d image / d z through the frozen eval-mode
-        decoder, and nothing else — a decoder parameter with requires_grad=True is an error (freeze_decoder()).  Not twice differentiable."""
+        decoder, and nothing else — a decoder parameter with requires_grad=True is an error (freeze_decoder()).  Not twice differentiable.
+        After train_decoder(): the same image and the same dz, bit for bit (the same walk, the same launches), and backward also accumulates `.grad` on every
+        decoder parameter: the decoder in eval mode (running statistics, not updated), conv and BatchNorm parameters learning through the fold."""
         self._check_grad_path(z)
+        if self._decoder_grads:
+            return _DecodeWithGrad.apply(z, self, collect, *self._decoder_params())
         return _DecodeWithGrad.apply(z, self, collect)
 
     @torch.no_grad()
     def decode_vjp(self, z, grad_image):
-        """dz = (d decode(z) / d z)^T grad_image, fp32 [B, latent_dim]: the explicit form of decode_with_grad's backward (capturable in a graph)."""
+        """dz = (d decode(z) / d z)^T grad_image, fp32 [B, latent_dim]: the explicit form of decode_with_grad's backward (capturable in a graph).  dz only, also
+        after train_decoder()."""
         self._check_grad_path(z)
         if tuple(grad_image.shape) != (z.shape[0], 1, self.img_height, self.img_width) or grad_image.dtype != torch.float32:
             raise CvaeError(f"ViTVAE.decode_vjp expects a float32 [{z.shape[0]}, 1, {self.img_height}, {self.img_width}] cotangent, got "
@@ -339,20 +390,28 @@ class ViTVAE(ViTVAEEncoder):
 
 
 class _DecodeWithGrad(torch.autograd.Function):
-    """ViTVAE.decode_with_grad: z -> image, with dz as the only gradient."""
+    """ViTVAE.decode_with_grad: z -> image, with dz as the only gradient; after train_decoder() the decoder's parameters (ViTVAE._decoder_params()) are inputs
+    too, so autograd accumulates their gradients, zero_grad works and a parameter rewritten between forward and backward is an error."""
 
     @staticmethod
-    def forward(ctx, z, model, collect):
-        image, saved = model._decode_walk(z.detach(), True, collect)
+    def forward(ctx, z, model, collect, *params):
+        zd = z.detach()
+        image, saved = model._decode_walk(zd, True, collect, keep_inputs=bool(params))
         ctx.model, ctx.saved = model, saved                            # activations and folded matrices of this call: private to the node, freed with it
+        ctx.z = zd.contiguous() if params else None
+        ctx.save_for_backward(*params)
         return image
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
+        params = ctx.saved_tensors                                     # raises if a parameter was modified in place since the forward
         if g.shape[0] == 0:
-            return g.new_zeros(0, ctx.model.latent_dim), None, None
-        return ctx.model._decode_backward(ctx.saved, g.contiguous()), None, None
+            return (g.new_zeros(0, ctx.model.latent_dim), None, None) + tuple(torch.zeros_like(p) for p in params)
+        if not params:
+            return ctx.model._decode_backward(ctx.saved, g.contiguous()), None, None
+        dz, grads = ctx.model._decode_backward(ctx.saved, g.contiguous(), ctx.z)
+        return (dz, None, None) + tuple(d.view(p.shape) for d, p in zip(grads, params))
 
 
 def fit_latent(model, x, z0, steps, lr, loss="sse"):

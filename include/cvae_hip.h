@@ -263,6 +263,15 @@ int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gam
 int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
                       const float* const* beta, const float* const* mean, const float* const* var, const float* eps, float* const* w_out,
                       float* const* b_out, void* stream);
+/* The way back through the fold, for `count` (1..16) layers in ONE launch: from the gradient of the FOLDED weight dwf and bias dbf [Cout] to the gradients of
+ * the module's parameters, with s = gamma rsqrt(var + eps) per BatchNorm channel (running statistics: constants):
+ *   dw = s dwf,  db = s dbf,  dgamma = rsqrt(var + eps) (sum dwf w + dbf (bias - mean)),  dbeta = dbf.
+ * kind CVAE_FOLD_CONVT_K3S2: dwf is the gradient of the k4 weight [Cin][Cout][4][4], of which the 3 x 3 taps are read; CVAE_FOLD_CONV_K3S1: dwf [Cout][Cin][3][3];
+ * CVAE_FOLD_CONVT_K3S2_SUBPIXEL: dwf [Cin][Cout][3][3] — both as cvae_conv_s1_wgrad writes them.  dw in w's layout.  One workgroup per (layer, channel): a
+ * thread's ordered chain, then a fixed tree.  bias entries may be NULL (zeros; db then too); gamma NULL: no BatchNorm (dw = dwf, db = dbf, nothing else). */
+int cvae_fold_bn_conv_bwd(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
+                          const float* const* mean, const float* const* var, const float* eps, const float* const* dwf, const float* const* dbf,
+                          float* const* dw, float* const* db, float* const* dgamma, float* const* dbeta, void* stream);
 /* l2[r] = ||a[r] - b[ref[r]]||_2 and (mean_abs != NULL) mean_abs[r] = mean |a[r] - b[ref[r]]| over rows of n elements; a holds `rows` rows,
  * b holds b_rows rows; ref: device int64[rows] (NULL: ref[r] = r, needs b_rows >= rows); a ref outside [0, b_rows) gives NaN for that row,
  * nothing is read.  dtype CVAE_F32 or CVAE_BF16 (a and b alike); sums in fp32.  workspace: cvae_row_diff_norms_workspace_bytes(rows, n, dtype) —
@@ -350,6 +359,26 @@ int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const void* gate, v
 size_t cvae_latent_to_grid_bwd_workspace_bytes(int64_t B, int64_t K, int64_t P, int64_t C);
 int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* workspace, size_t workspace_bytes,
                             void* stream);
+/* The decoder's weight-gradient path (eval-mode BatchNorm: running statistics, not updated).  Activations and cotangents in `dtype`, every gradient fp32;
+ * fp32 sums in a fixed order, no float atomics: two runs give the same bits.  B >= 1; all checks come before the first launch.
+ *   cvae_conv_s1_wgrad        dW and dbias = sum g of the layer's FOLDED weight, in the torch layout, from the layer's input x [B][H][W][C] and the gated
+ *                             cotangent g of its pre-activation.  A GEMM over the B H W pixels on the MFMA: 8 x 16 pixel tiles with the halo staged once,
+ *                             a workgroup walks tiles s, s + slabs, .. and leaves its partial sums in slab s of `workspace`
+ *                             (cvae_conv_s1_wgrad_workspace_bytes; CVAE_E_WORKSPACE below it); a second launch adds the slabs in slab order.
+ *                             form CVAE_CONV_S1_K3:       nn.Conv2d(C, C, 3, 1, 1), C in {16, 32, 64, 128}; g [B][H][W][C]; dW [C][C][3][3], dbias [C];
+ *                             form CVAE_CONV_S1_SUBPIXEL: nn.ConvTranspose2d(C, 16, 3, 2, 1, output_padding 1), C in {32, 16}; g [B][2H][2W][16], read in the
+ *                                                         forward's sub-pixel form; dW [C][16][3][3] (the 9 real taps per (ci, co)), dbias [16].
+ *   cvae_conv_s1_c1_wgrad     nn.Conv2d(16, 1, 3, 1, 1): x [B][H][W][16] in `dtype`, g fp32 [B][1][H][W]; dW [1][16][3][3], dbias [1]; per-workgroup partial
+ *                             sums in `workspace` (cvae_conv_s1_c1_wgrad_workspace_bytes), added in workgroup order by a second launch.
+ *   cvae_latent_to_grid_wgrad dW[c P + p][k] = sum_b g[b][p][c] z[b][k] (rows b in order), dbias[c P + p] = sum_b g[b][p][c]: g [B][P][C] in `dtype`, z fp32
+ *                             [B][K]; dW [C P][K] written once with 16-byte stores; any B >= 1, K <= 512 and K % 4 == 0, C % 32 == 0. */
+size_t cvae_conv_s1_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t C, int form);
+int cvae_conv_s1_wgrad(const void* x, const void* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, int form, int dtype, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t cvae_conv_s1_c1_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int cvae_conv_s1_c1_wgrad(const void* x, const float* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int cvae_latent_to_grid_wgrad(const void* g, const float* z, float* dW, float* dbias, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream);
 
 /* ---- The dense heads of CausalViTVAE, eval mode (csrc/heads.hip; vessel_analysis/00_core/models.py:225-250, 281-302) ------------------------------------------
  * One launch = one whole head: the logical concatenation of n_panels (1..3) fp32 row panels {ptr, width, row stride in elements} (torch.cat(dim=1), never
