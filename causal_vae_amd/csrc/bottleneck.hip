@@ -1041,43 +1041,40 @@ size_t fc2_bwd_lds(const TailDims& d) { return sizeof(float) * ((size_t)d.M * d.
 size_t bn_finish_lds(const TailDims& d) { return sizeof(float) * (size_t)d.M * (d.HM + d.T); }
 size_t dec_input_fwd_lds(int M, int K4) { return sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)4 * M * 64); }
 size_t dec_input_bwd_lds(int M, int K4) { return sizeof(float) * ((size_t)64 * (K4 | 1) + (size_t)M * K4 + (size_t)M * 64); }
-int mt_of(int M) { return M <= 4 ? 4 : (M <= 8 ? 8 : 16); }                // the skinny kernels' row template (launch_fwd_partial / launch_bwd_colwise)
+// the skinny kernels' row template: f receives Int<4 | 8 | 16> (as with_dtype / with_bool, common.h)
+template <typename F> auto with_mt(int M, F&& f) { return M <= 4 ? f(Int<4>{}) : (M <= 8 ? f(Int<8>{}) : f(Int<16>{})); }
+int mt_of(int M) { return with_mt(M, [](auto mt) { return (int)decltype(mt)::value; }); }
 
-// LDS of a workgroup on gfx950 (dynamic + static).  A launch above the default dynamic limit (64 KiB) raises its kernel's limit to what the
-// static part leaves of 160 KiB — once per kernel, checked, before the call's first launch (as conv_mfma.hip / small_dense.hip do), so a failure
-// leaves nothing written.  The model's shapes stay below 64 KiB and never get here.
-constexpr size_t BN_LDS_MAX = 160 * 1024, BN_LDS_DEFAULT = 64 * 1024;
-template <typename KERN> int bn_allow_lds(KERN kern, size_t dyn, size_t static_bytes, bool* done) {
-    if (dyn <= BN_LDS_DEFAULT || *done) return CVAE_OK;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BN_LDS_MAX - static_bytes)) != hipSuccess) return CVAE_E_LAUNCH;
-    *done = true;
-    return CVAE_OK;
-}
-bool lds_fwd_partial[3], lds_bwd_colwise[3], lds_fc2_fwd, lds_mulv_fwd, lds_fc2_bwd, lds_bn_finish;
 // static LDS of the two skinny kernels: skinny_fwd_partial's red[4][4 * MT], skinny_bwd_colwise's gs[MT][64]
 constexpr size_t fwd_partial_static(int MT) { return sizeof(float) * 4 * 4 * MT; }
 constexpr size_t bwd_colwise_static(int MT) { return sizeof(float) * 64 * MT; }
+// The level launches whose dynamic LDS can pass the opt-in threshold (cvae_allow_lds, common.h), asked for before the entry point's first launch so that
+// a failure leaves nothing written.  The model's shapes stay far below it; mulv_bwd and the dec_input pair stay below the runtime's default limit (64 KiB)
+// for every accepted shape and need no opt-in.
 int fwd_lds_ready(const TailDims& d) {
-    int rc;
-    switch (mt_of(d.M)) {
-        case 4: rc = bn_allow_lds(skinny_fwd_partial_kernel<4>, mech_fwd_lds(d), fwd_partial_static(4), &lds_fwd_partial[0]); break;
-        case 8: rc = bn_allow_lds(skinny_fwd_partial_kernel<8>, mech_fwd_lds(d), fwd_partial_static(8), &lds_fwd_partial[1]); break;
-        default: rc = bn_allow_lds(skinny_fwd_partial_kernel<16>, mech_fwd_lds(d), fwd_partial_static(16), &lds_fwd_partial[2]); break;
-    }
-    if (rc == CVAE_OK) rc = bn_allow_lds(fc2_fwd_kernel, fc2_fwd_lds(d), 0, &lds_fc2_fwd);
-    if (rc == CVAE_OK) rc = bn_allow_lds(mulv_fwd_kernel, mulv_fwd_lds(d), 0, &lds_mulv_fwd);
+    int rc = with_mt(d.M, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return cvae_allow_lds<skinny_fwd_partial_kernel<MT>>(mech_fwd_lds(d), fwd_partial_static(MT));
+    });
+    if (rc == CVAE_OK) rc = cvae_allow_lds<fc2_fwd_kernel>(fc2_fwd_lds(d));
+    if (rc == CVAE_OK) rc = cvae_allow_lds<mulv_fwd_kernel>(mulv_fwd_lds(d));
     return rc;
 }
 int bwd_lds_ready(const TailDims& d) {
-    int rc;
-    switch (mt_of(d.M)) {
-        case 4: rc = bn_allow_lds(skinny_bwd_colwise_kernel<4>, mech_bwd_lds(d), bwd_colwise_static(4), &lds_bwd_colwise[0]); break;
-        case 8: rc = bn_allow_lds(skinny_bwd_colwise_kernel<8>, mech_bwd_lds(d), bwd_colwise_static(8), &lds_bwd_colwise[1]); break;
-        default: rc = bn_allow_lds(skinny_bwd_colwise_kernel<16>, mech_bwd_lds(d), bwd_colwise_static(16), &lds_bwd_colwise[2]); break;
-    }
-    if (rc == CVAE_OK) rc = bn_allow_lds(fc2_bwd_kernel, fc2_bwd_lds(d), 0, &lds_fc2_bwd);
-    return rc;                                               // mulv_bwd and the dec_input pair stay below 64 KiB for every accepted shape
+    const int rc = with_mt(d.M, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value;
+        return cvae_allow_lds<skinny_bwd_colwise_kernel<MT>>(mech_bwd_lds(d), bwd_colwise_static(MT));
+    });
+    return rc == CVAE_OK ? cvae_allow_lds<fc2_bwd_kernel>(fc2_bwd_lds(d)) : rc;
 }
+// the kernels' views of the C ABI's structs
+TailParams tail_params(const cvae_bottleneck_params* w) {
+    return TailParams{w->b1, w->W2, w->b2, w->Wmu, w->bmu, w->Wlv, w->blv, w->Wm0, w->bm0, w->gamma, w->beta, w->Wm3, w->bm3, w->Wm5, w->bm5};
+}
+TailGrads tail_grads(const cvae_bottleneck_grads* gr) {
+    return TailGrads{gr->db1, gr->dW2, gr->db2, gr->dWmu, gr->dbmu, gr->dWlv, gr->dblv, gr->dWm0, gr->dbm0, gr->dgamma, gr->dbeta, gr->dWm3, gr->dbm3, gr->dWm5, gr->dbm5};
+}
+TailSaved tail_saved(const cvae_bottleneck_saved* sv) { return TailSaved{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm}; }
 
 }  // namespace
 
@@ -1097,7 +1094,7 @@ static bool dims_ok(const cvae_bottleneck_dims* q) {
     const size_t need[] = {mech_fwd_lds(d) + fwd_partial_static(MT), fc2_fwd_lds(d), mulv_fwd_lds(d), dec_input_fwd_lds(d.M, K4), dec_input_bwd_lds(d.M, K4),
                            mulv_bwd_lds(d), fc2_bwd_lds(d), mech_bwd_lds(d) + bwd_colwise_static(MT), bn_finish_lds(d)};
     for (size_t b : need)
-        if (b > BN_LDS_MAX) return false;
+        if (b > CVAE_LDS_MAX) return false;
     return true;
 }
 static TailDims tail_dims(const cvae_bottleneck_dims* q, int KS, int P) {
@@ -1119,21 +1116,6 @@ extern "C" int cvae_bottleneck_sizes(const cvae_bottleneck_dims* q, int64_t* K1,
     if (dzm_partial_floats) *dzm_partial_floats = (F / 64) * q->M * k4;       // one slot per dec_input_bwd workgroup
     if (dx_partial_floats) *dx_partial_floats = (int64_t)bwd_nsplit(q->N1) * q->M * F;
     return CVAE_OK;
-}
-
-template <int MT>
-static void launch_fwd_partial(const float* x, const float* W1, float* partial, int M, int K, int N, int KS, const TailDims& d, const TailParams& p, const TailSaved& sv,
-                               const MechFwdArgs& ma, hipStream_t st) {
-    const int kslice = (K + KS - 1) / KS;
-    hipLaunchKernelGGL(skinny_fwd_partial_kernel<MT>, dim3((unsigned)((N + 3) / 4), (unsigned)(KS + 1)), dim3(256), mech_fwd_lds(d), st, x, W1, partial, M, K, N, kslice,
-                       KS, d, p, sv, ma);
-}
-template <int MT>
-static void launch_bwd_colwise(const float* g, const float* x, const float* W1, float* dW, float* dxp, int M, int K, int N, int NS, int F, int S, const TailDims& d,
-                               const TailParams& p, const TailGrads& tg, const TailSaved& sv, const MechBwdArgs& mb, hipStream_t st) {
-    const int nslice = (N + NS - 1) / NS;
-    hipLaunchKernelGGL(skinny_bwd_colwise_kernel<MT>, dim3((unsigned)((K + 256 * SkinnyBwdCols<MT>::value - 1) / (256 * SkinnyBwdCols<MT>::value)), (unsigned)(NS + 1)), dim3(256), mech_bwd_lds(d), st, g, x, W1, dW, dxp, M, K, N,
-                       nslice, F, S, NS, d, p, tg, sv, mb);
 }
 
 extern "C" int cvae_bottleneck_bn_local_stats(const float* Wm0, const float* bm0, const float* t_onehot, const int64_t* t_labels, float* local_stats, int64_t M, int64_t t_dim,
@@ -1161,30 +1143,30 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     hipStream_t st = (hipStream_t)stream;
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), KS = fwd_ksplit(K1);
-    if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(pool_cat_fwd_kernel<bf16>, dim3(S + 1, M), dim3(256), 0, st, (const bf16*)y_cl, m, t_onehot, (const long long*)t_labels, xcat, (int)q->D, (int)q->H, (int)q->W, C,
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(pool_cat_fwd_kernel<T>, dim3(S + 1, M), dim3(256), 0, st, (const T*)y_cl, m, t_onehot, (const long long*)t_labels, xcat, (int)q->D, (int)q->H, (int)q->W, C,
                            (int)q->OD, (int)q->OH, (int)q->OW, (int)q->m_dim, (int)q->t_dim, K1, nz);
-    else
-        hipLaunchKernelGGL(pool_cat_fwd_kernel<float>, dim3(S + 1, M), dim3(256), 0, st, (const float*)y_cl, m, t_onehot, (const long long*)t_labels, xcat, (int)q->D, (int)q->H, (int)q->W, C,
-                           (int)q->OD, (int)q->OH, (int)q->OW, (int)q->m_dim, (int)q->t_dim, K1, nz);
+    });
     CVAE_CHECK_LAUNCH();
     const TailDims d = tail_dims(q, KS, 0);
-    const TailParams p{w->b1, w->W2, w->b2, w->Wmu, w->bmu, w->Wlv, w->blv, w->Wm0, w->bm0, w->gamma, w->beta, w->Wm3, w->bm3, w->Wm5, w->bm5};
-    const TailSaved s{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm};
+    const TailParams p = tail_params(w);
+    const TailSaved s = tail_saved(sv);
     const MechFwdArgs ma{t_onehot, running_mean, running_var, num_batches_tracked, momentum, bn_eps, bn_training, bn_rank_stats, bn_ranks};
-    if (M <= 4) launch_fwd_partial<4>(xcat, w->W1, partial, M, K1, (int)q->N1, KS, d, p, s, ma, st);
-    else if (M <= 8) launch_fwd_partial<8>(xcat, w->W1, partial, M, K1, (int)q->N1, KS, d, p, s, ma, st);
-    else launch_fwd_partial<16>(xcat, w->W1, partial, M, K1, (int)q->N1, KS, d, p, s, ma, st);
+    with_mt(M, [&](auto mt) {
+        hipLaunchKernelGGL(skinny_fwd_partial_kernel<decltype(mt)::value>, dim3((unsigned)((q->N1 + 3) / 4), (unsigned)(KS + 1)), dim3(256), mech_fwd_lds(d), st,
+                           (const float*)xcat, w->W1, partial, M, K1, (int)q->N1, (K1 + KS - 1) / KS, KS, d, p, s, ma);
+    });
     CVAE_CHECK_LAUNCH();
     hipLaunchKernelGGL(fc2_fwd_kernel, dim3((unsigned)((q->N2 + 3) / 4)), dim3(256), fc2_fwd_lds(d), st, d, p, s, (const float*)partial);
     CVAE_CHECK_LAUNCH();
     hipLaunchKernelGGL(mulv_fwd_kernel, dim3((unsigned)((q->Z + 3) / 4)), dim3(256), mulv_fwd_lds(d), st, d, p, s, eps);
     CVAE_CHECK_LAUNCH();
     const size_t lds_d = dec_input_fwd_lds(M, K4);
-    if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(dec_input_fwd_kernel<bf16>, dim3(C * S / 64), dim3(256), lds_d, st, (const float*)sv->zm, w->Wd, w->bd, (bf16*)dec_cl, M, K4, S, C);
-    else
-        hipLaunchKernelGGL(dec_input_fwd_kernel<float>, dim3(C * S / 64), dim3(256), lds_d, st, (const float*)sv->zm, w->Wd, w->bd, (float*)dec_cl, M, K4, S, C);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(dec_input_fwd_kernel<T>, dim3(C * S / 64), dim3(256), lds_d, st, (const float*)sv->zm, w->Wd, w->bd, (T*)dec_cl, M, K4, S, C);
+    });
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }
@@ -1194,10 +1176,10 @@ extern "C" int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* q, cons
     if (!dims_ok(q) || bn_ranks < 1) return CVAE_E_BADSHAPE;
     if (!w || !gr || !sv || !t_onehot || !bn_dy || !bn_sums) return CVAE_E_NULLPTR;
     const TailDims d = tail_dims(q, 0, 0);
-    const TailParams p{w->b1, w->W2, w->b2, w->Wmu, w->bmu, w->Wlv, w->blv, w->Wm0, w->bm0, w->gamma, w->beta, w->Wm3, w->bm3, w->Wm5, w->bm5};
-    const TailGrads g{gr->db1, gr->dW2, gr->db2, gr->dWmu, gr->dbmu, gr->dWlv, gr->dblv, gr->dWm0, gr->dbm0, gr->dgamma, gr->dbeta, gr->dWm3, gr->dbm3, gr->dWm5, gr->dbm5};
-    const TailSaved s{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm};
-    if (bn_allow_lds(mech_bn_finish_kernel, bn_finish_lds(d), 0, &lds_bn_finish) != CVAE_OK) return CVAE_E_LAUNCH;
+    const TailParams p = tail_params(w);
+    const TailGrads g = tail_grads(gr);
+    const TailSaved s = tail_saved(sv);
+    if (cvae_allow_lds<mech_bn_finish_kernel>(bn_finish_lds(d)) != CVAE_OK) return CVAE_E_LAUNCH;
     hipLaunchKernelGGL(mech_bn_finish_kernel, dim3(1), dim3(256), bn_finish_lds(d), (hipStream_t)stream, d, p, g, s, t_onehot, bn_dy, bn_sums,
                        bn_ranks);
     CVAE_CHECK_LAUNCH();
@@ -1217,17 +1199,15 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), NS = bwd_nsplit(q->N1), P = S;
     const size_t lds_d = dec_input_bwd_lds(M, K4);
-    if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(dec_input_bwd_kernel<bf16>, dim3(F / 64), dim3(256), lds_d, st, (const bf16*)g_dec_cl, (const float*)sv->zm, w->Wd, gr->dWd, gr->dbd,
-                           dzm_partial, M, K4, S, C);
-    else
-        hipLaunchKernelGGL(dec_input_bwd_kernel<float>, dim3(F / 64), dim3(256), lds_d, st, (const float*)g_dec_cl, (const float*)sv->zm, w->Wd, gr->dWd, gr->dbd,
-                           dzm_partial, M, K4, S, C);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(dec_input_bwd_kernel<T>, dim3(F / 64), dim3(256), lds_d, st, (const T*)g_dec_cl, (const float*)sv->zm, w->Wd, gr->dWd, gr->dbd, dzm_partial, M, K4, S, C);
+    });
     CVAE_CHECK_LAUNCH();
     const TailDims d = tail_dims(q, 0, P);
-    const TailParams p{w->b1, w->W2, w->b2, w->Wmu, w->bmu, w->Wlv, w->blv, w->Wm0, w->bm0, w->gamma, w->beta, w->Wm3, w->bm3, w->Wm5, w->bm5};
-    const TailGrads g{gr->db1, gr->dW2, gr->db2, gr->dWmu, gr->dbmu, gr->dWlv, gr->dblv, gr->dWm0, gr->dbm0, gr->dgamma, gr->dbeta, gr->dWm3, gr->dbm3, gr->dWm5, gr->dbm5};
-    const TailSaved s{sv->h1, sv->h2, sv->mu, sv->logvar, sv->xhat, sv->invstd, sv->a1n, sv->a2, sv->m_hat, sv->zm};
+    const TailParams p = tail_params(w);
+    const TailGrads g = tail_grads(gr);
+    const TailSaved s = tail_saved(sv);
     float* dh2 = g1 + (size_t)M * q->N1;                     // second part of the g1 scratch
     hipLaunchKernelGGL(mulv_bwd_kernel, dim3((unsigned)((q->N2 + 15) / 16)), dim3(256), mulv_bwd_lds(d), st,
                        d, p, g, s, (const float*)dzm_partial, g_mu, g_logvar, eps, dh2);
@@ -1236,16 +1216,17 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
                        (const float*)dh2, g1);
     CVAE_CHECK_LAUNCH();
     const MechBwdArgs mb{dzm_partial, g_mhat, t_onehot, bn_dy, bn_local_sums};
-    if (M <= 4) launch_bwd_colwise<4>(g1, xcat, w->W1, gr->dW1, dx_partial, M, K1, (int)q->N1, NS, F, S, d, p, g, s, mb, st);
-    else if (M <= 8) launch_bwd_colwise<8>(g1, xcat, w->W1, gr->dW1, dx_partial, M, K1, (int)q->N1, NS, F, S, d, p, g, s, mb, st);
-    else launch_bwd_colwise<16>(g1, xcat, w->W1, gr->dW1, dx_partial, M, K1, (int)q->N1, NS, F, S, d, p, g, s, mb, st);
+    with_mt(M, [&](auto mt) {
+        constexpr int MT = decltype(mt)::value, COLS = 256 * SkinnyBwdCols<MT>::value;     // columns of W1 per workgroup
+        hipLaunchKernelGGL(skinny_bwd_colwise_kernel<MT>, dim3((unsigned)((K1 + COLS - 1) / COLS), (unsigned)(NS + 1)), dim3(256), mech_bwd_lds(d), st, (const float*)g1, xcat,
+                           w->W1, gr->dW1, dx_partial, M, K1, (int)q->N1, ((int)q->N1 + NS - 1) / NS, F, S, NS, d, p, g, s, mb);
+    });
     CVAE_CHECK_LAUNCH();
-    if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(pool_bwd_kernel<bf16>, dim3(S, M), dim3(256), 0, st, (const float*)dx_partial, (const bf16*)y_cl, (bf16*)dy_cl, NS, M, (int)q->D, (int)q->H,
-                           (int)q->W, C, (int)q->OD, (int)q->OH, (int)q->OW, relu_mask);
-    else
-        hipLaunchKernelGGL(pool_bwd_kernel<float>, dim3(S, M), dim3(256), 0, st, (const float*)dx_partial, (const float*)y_cl, (float*)dy_cl, NS, M, (int)q->D, (int)q->H,
-                           (int)q->W, C, (int)q->OD, (int)q->OH, (int)q->OW, relu_mask);
+    with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(pool_bwd_kernel<T>, dim3(S, M), dim3(256), 0, st, (const float*)dx_partial, (const T*)y_cl, (T*)dy_cl, NS, M, (int)q->D, (int)q->H, (int)q->W, C,
+                           (int)q->OD, (int)q->OH, (int)q->OW, relu_mask);
+    });
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }

@@ -19,6 +19,20 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
         if (e__ != hipSuccess) return CVAE_E_LAUNCH;          \
     } while (0)
 
+// Dynamic LDS above the runtime's default limit: a kernel has to have its limit raised first, and that attribute belongs to the CURRENT DEVICE's copy
+// of the kernel.  Every launch that may need it calls cvae_allow_lds<kernel>(dynamic bytes[, the kernel's static LDS]) before its entry point's first
+// launch, so that a refusal leaves nothing written.  At or below 48 KiB nothing is done; above, the limit becomes all that the static part leaves of a
+// workgroup's 160 KiB, whatever this launch needs: one value, good for every later launch of the kernel on that device.  Stateless on purpose: the
+// runtime call takes ~70 ns of host time, its own current-device query ~55 ns, so a per-device "already done" mask would save nothing, and a flag that
+// ignores the device or the host thread is wrong (profiles/launch_lds.md).  The kernel is a template ARGUMENT, not a function
+// argument: instances of one kernel template share their pointer type.
+constexpr size_t CVAE_LDS_MAX = 160 * 1024, CVAE_LDS_OPT_IN = 48 * 1024;
+template <auto KERN> int cvae_allow_lds(size_t dynamic_bytes, size_t static_bytes = 0) {
+    if (dynamic_bytes <= CVAE_LDS_OPT_IN) return CVAE_OK;
+    const int limit = (int)(CVAE_LDS_MAX - static_bytes);
+    return hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, limit) == hipSuccess ? CVAE_OK : CVAE_E_LAUNCH;
+}
+
 // CVAE_TUNABLE(WG_TILES, 16): the constant WG_TILES is 16 unless the build passes -DCVAE_WG_TILES=<non-negative integer> (make EXTRA=-D..., then
 // tools/ab.sh with CVAE_HIP_LIB).  Every file keeps its tunables in ONE block at its top, one line each.  `text` is the macro's name stringified after
 // expansion: still the name when no -D defined it, the override's digits otherwise.

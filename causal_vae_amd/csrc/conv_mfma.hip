@@ -806,7 +806,7 @@ int launch_data_epi(const ConvArgs& a) {
     constexpr size_t LDS_MAIN = (size_t)2 * KH * (UP ? 1 : 2) * ID * IH * HaloPitch<ND, UP>::RS * FB + (F::BD ? 0 : (size_t)2 * 4 * KH * 2 * F::BN * FB);
     constexpr size_t LDS_X = F::TS == 2 ? (size_t)F::WM * F::WN * F::TS * (F::MI / 2) * F::NI * 16 * 64 * sizeof(float) : 0;      // the K split's accumulator exchange
     constexpr size_t LDS = LDS_MAIN > LDS_X ? LDS_MAIN : LDS_X;
-    static_assert(LDS <= 160 * 1024, "LDS tile exceeds the 160 KiB of a CDNA4 CU");
+    static_assert(LDS <= CVAE_LDS_MAX, "LDS tile exceeds the 160 KiB of a CDNA4 CU");
     const int md = UP ? ((ND == 3) ? (g.ld + 1) / 2 : 1) : g.sd, mh = UP ? (g.lh + 1) / 2 : g.sh, mw = UP ? (g.lw + 1) / 2 : g.sw;
     if constexpr (F::XPAIR && XB == 1) {
         // a layer at most half a tile wide, on a launch that fills the chip several times over (the decode sweep's 4^3 -> 8^3 layer; round 3: the 7 x 7 grids of the
@@ -815,12 +815,8 @@ int launch_data_epi(const ConvArgs& a) {
         if (mw <= TL::TW / 2 && g.B >= 2 && (a.var.xpair == 1 || (a.var.xpair < 0 && wgs >= (ND == 3 ? XPAIR_MIN_WGS : XPAIR_2D_MIN_WGS))))
             return launch_data_epi<T, ND, UP, WIDE, EPI, KH, TO, 2>(a);
     }
-    auto kern = conv_data_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
-        attr_set = true;
-    }
+    constexpr auto kern = conv_data_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
+    if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     g.tiles_d = (md + TL::TD - 1) / TL::TD; g.tiles_h = (mh + TL::TH - 1) / TL::TH; g.tiles_w = (mw + TL::TW - 1) / TL::TW;
     const int Cout = UP ? g.Cl : g.Cs, Cin = (UP ? g.Cs : g.Cl) / (IsF8<T>::value ? 2 : 1);
     const int npar = UP ? ((ND == 3) ? 8 : 4) : 1;
@@ -1122,7 +1118,7 @@ int launch_up_full(const ConvArgs& a) {
     using F = DataForm<T, ND, true, false>;
     constexpr int WM = F::WM, WN = F::WN, MI = F::MI, NI = F::NI;
     constexpr size_t LDS = up_full_lds_bytes<T, ND, WM, WN, MI, NI, KCH>();
-    if constexpr (LDS > 160 * 1024 || (KCH * 2 * F::BN) % (WM * WN * 64) != 0) {
+    if constexpr (LDS > CVAE_LDS_MAX || (KCH * 2 * F::BN) % (WM * WN * 64) != 0) {
         return CVAE_E_UNSUPPORTED;
     } else {
         using TL = Tile<ND, F::BM>;
@@ -1139,12 +1135,8 @@ int launch_up_full(const ConvArgs& a) {
         if (gy > 65535 || g.B > 65535) return CVAE_E_BADSHAPE;
         dim3 grid((unsigned)tiles, (unsigned)gy, (unsigned)g.B), block(WM * WN * 64);
         return with_epi(a.act, [&](auto epi) {
-            auto kern = conv_up_full_kernel<T, ND, WM, WN, MI, NI, KCH, decltype(epi)::value, T>;
-            static bool attr_set = false;
-            if (!attr_set) {
-                if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
-                attr_set = true;
-            }
+            constexpr auto kern = conv_up_full_kernel<T, ND, WM, WN, MI, NI, KCH, decltype(epi)::value, T>;
+            if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
             hipLaunchKernelGGL(kern, grid, block, LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const T*)a.mask, (T*)a.out, g, a.act, npar / psplit,
                                a.acc_scale, a.out_scale);
             CVAE_CHECK_LAUNCH();
@@ -1729,13 +1721,9 @@ int plan_wgrad(const void* S, const void* L, float* ws, float* dW, float* dbias,
 template <typename T, int ND>
 int launch_wgrad_tables(WgradTable& mt, WgradReduceTable& rt, hipStream_t stream) {
     constexpr size_t LDS = wgrad_lds_bytes<T, ND>();
-    static_assert(LDS <= 160 * 1024, "LDS tile exceeds the 160 KiB of a CDNA4 CU");
-    auto kern = conv_wgrad_kernel<T, ND>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
-        attr_set = true;
-    }
+    static_assert(LDS <= CVAE_LDS_MAX, "LDS tile exceeds the 160 KiB of a CDNA4 CU");
+    constexpr auto kern = conv_wgrad_kernel<T, ND>;
+    if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     rt.taps = (ND == 3) ? 64 : 16;
     hipLaunchKernelGGL(kern, dim3((unsigned)mt.blk_start[mt.count]), dim3(512), LDS, stream, mt);
     CVAE_CHECK_LAUNCH();

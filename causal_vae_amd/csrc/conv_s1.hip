@@ -207,11 +207,10 @@ __global__ __launch_bounds__(256) void conv_s1_kernel(const T* __restrict__ x, c
 struct S1Args { const void *x, *w; const float* bias; const void *resid, *gate; void* y; int64_t B, H, W; int act; hipStream_t st; };
 template <typename T, int CIN, int NT, int FORM, bool BWD = false, int COUT_T = 0> int conv_s1_launch(const S1Args& a) {
     using G = S1Geom<T, CIN, FORM>;
-    auto kern = conv_s1_kernel<T, CIN, NT, FORM, BWD, COUT_T>;
+    constexpr auto kern = conv_s1_kernel<T, CIN, NT, FORM, BWD, COUT_T>;
     constexpr size_t LDS = ((size_t)(G::HR * G::HC + 1) * G::PITCH + (size_t)32 * NT * G::WPITCH) * sizeof(T);
-    static_assert(LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
-    // set on every launch: the attribute belongs to the current device's copy of the kernel, and a flag would be shared by devices and host threads
-    if (LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    static_assert(LDS <= CVAE_LDS_MAX, "tile does not fit a workgroup's LDS");
+    if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     const dim3 grid((unsigned)((a.W + S1_TW - 1) / S1_TW), (unsigned)((a.H + S1_TH - 1) / S1_TH), (unsigned)a.B);
     hipLaunchKernelGGL(kern, grid, dim3(256), LDS, a.st, (const T*)a.x, (const T*)a.w, a.bias, (const T*)a.resid, (T*)a.y, (int)a.H, (int)a.W, a.act, (const T*)a.gate);
     CVAE_CHECK_LAUNCH();
@@ -657,9 +656,9 @@ struct S1WArgs { const void *x, *g; float *dW, *db, *ws; int64_t B, H, W; hipStr
 int64_t s1w_tiles(int64_t B, int64_t H, int64_t W) { return B * ((H + S1_TH - 1) / S1_TH) * ((W + S1_TW - 1) / S1_TW); }
 template <typename T, int C, int FORM> int conv_s1_wgrad_launch(const S1WArgs& a) {
     using G = S1WGeom<T, C, FORM>;
-    static_assert(G::LDS <= 160 * 1024, "tile does not fit a workgroup's LDS");
-    auto kern = conv_s1_wgrad_kernel<T, C, FORM>;
-    if (G::LDS > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    static_assert(G::LDS <= CVAE_LDS_MAX, "tile does not fit a workgroup's LDS");
+    constexpr auto kern = conv_s1_wgrad_kernel<T, C, FORM>;
+    if (cvae_allow_lds<kern>(G::LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     const int tiles_x = (int)((a.W + S1_TW - 1) / S1_TW), tiles_y = (int)((a.H + S1_TH - 1) / S1_TH), tiles = (int)s1w_tiles(a.B, a.H, a.W);
     const int slabs = tiles < G::MAX_SLABS ? tiles : G::MAX_SLABS;
     float* pbias = a.ws + (int64_t)slabs * G::SLAB;
@@ -1017,7 +1016,7 @@ extern "C" int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz,
     float* part = (float*)workspace;
     const int rc = with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
-        if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2g_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CVAE_E_LAUNCH;
+        if (cvae_allow_lds<l2g_bwd_kernel<T>>(lds) != CVAE_OK) return CVAE_E_LAUNCH;
         hipLaunchKernelGGL(l2g_bwd_kernel<T>, dim3((unsigned)slabs), dim3(256), lds, st, (const T*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
         CVAE_CHECK_LAUNCH();
         return CVAE_OK;

@@ -33,7 +33,7 @@ constexpr int NC = (int)HEADS_NC, KC = (int)HEADS_KC, RG = (int)HEADS_RG, RPT = 
 constexpr int THREADS = NC * RG, ROWS = RG * RPT, WST = KC + 1, AST = CVAE_HEADS_MAX_WIDTH + 4, PF = NC * KC / THREADS;
 static_assert(KC % 64 == 0 && NC % 64 == 0 && THREADS <= 1024 && (NC * KC) % THREADS == 0, "heads.hip: tile shape");
 constexpr size_t LDS_BYTES = (size_t)(NC * WST + 2 * ROWS * AST) * sizeof(float);
-static_assert(LDS_BYTES <= 160 * 1024, "heads.hip: a workgroup's LDS");
+static_assert(LDS_BYTES <= CVAE_LDS_MAX, "heads.hip: a workgroup's LDS");
 
 struct HeadsArgs {
     cvae_heads_panel panels[CVAE_HEADS_MAX_PANELS];
@@ -246,8 +246,7 @@ extern "C" int cvae_mlp_heads_fwd(const cvae_heads_panel* panels, int n_panels, 
                                        out1_stride, z, z_stride, B, z != nullptr);
     if (rc != CVAE_OK || B == 0) return rc;
     if ((rc = heads_check_ptrs(HEADS_EVAL, a, z != nullptr)) != CVAE_OK) return rc;
-    // on every call: the attribute belongs to the current device, and a flag kept here would be shared by every device and thread of the process
-    if (hipFuncSetAttribute((const void*)mlp_heads_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return CVAE_E_LAUNCH;
+    if (cvae_allow_lds<mlp_heads_kernel>(LDS_BYTES) != CVAE_OK) return CVAE_E_LAUNCH;
     hipLaunchKernelGGL(mlp_heads_kernel, dim3((unsigned)((B + ROWS - 1) / ROWS)), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, a);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -716,7 +715,7 @@ extern "C" int cvae_mlp_heads_train_fwd(const cvae_heads_panel* panels, int n_pa
     t.lay = train_layout(layers, n_layers, B);
     if (saved_bytes < (size_t)t.lay.total * sizeof(float)) return CVAE_E_WORKSPACE;
     t.saved = (float*)saved;
-    if (hipFuncSetAttribute((const void*)heads_train_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return CVAE_E_LAUNCH;
+    if (cvae_allow_lds<heads_train_rows_kernel>(LDS_BYTES) != CVAE_OK) return CVAE_E_LAUNCH;
     const dim3 grid((unsigned)((B + ROWS - 1) / ROWS));
     for (int l_begin = 0;;) {
         hipLaunchKernelGGL(heads_train_rows_kernel, grid, dim3(THREADS), LDS_BYTES, (hipStream_t)stream, t, l_begin);
@@ -767,7 +766,7 @@ extern "C" int cvae_mlp_heads_bwd(const cvae_heads_panel* panels, int n_panels, 
     if (saved_bytes < (size_t)a.lay.total * sizeof(float) || workspace_bytes < (size_t)o * sizeof(float)) return CVAE_E_WORKSPACE;
     a.saved = (const float*)saved; a.ws = (float*)workspace; a.K0 = (int)K0;
     a.g0 = g0; a.g1 = g1; a.gz = gz; a.g0_stride = g0_stride; a.g1_stride = g1_stride; a.gz_stride = gz_stride;
-    if (hipFuncSetAttribute((const void*)heads_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS) != hipSuccess) return CVAE_E_LAUNCH;
+    if (cvae_allow_lds<heads_bwd_kernel>(BWD_LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     const int row_blocks = (int)((B + ROWS - 1) / ROWS);
     // segments between BatchNorm layers, from the output down: rows (top) [+ the wgrad of `top` with dv on the fly], then the wgrads below it and the next sums
     for (int top = n_layers - 1;;) {

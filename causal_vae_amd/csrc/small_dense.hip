@@ -195,14 +195,6 @@ __global__ __launch_bounds__(256) void sd_bwd_weight_finish_kernel(const float* 
 }
 
 bool sd_shape_ok(int64_t M, int64_t K, int64_t N) { return M > 16 && K >= 1 && N >= 1 && K <= SD_MAX_DIM && N <= SD_MAX_DIM && N * K <= SD_MAX_NK && M < ((int64_t)1 << 30); }
-constexpr int SD_LDS_MAX = 112 * 1024;                   // 48 KB of weights + 16 rows of the two activations (+ pitch padding)
-template <typename KERN> int sd_allow_lds(KERN kern, bool* done) {
-    if (!*done) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS_MAX) != hipSuccess) return CVAE_E_LAUNCH;
-        *done = true;
-    }
-    return CVAE_OK;
-}
 bool sd_act_ok(int act) { return act >= CVAE_ACT_NONE && act <= CVAE_ACT_LEAKY001; }
 
 }  // namespace
@@ -219,8 +211,7 @@ extern "C" int cvae_small_dense_fwd(const float* x, const float* W, const float*
     if (!sd_shape_ok(M, K, N) || x_stride < K || y_stride < N || !sd_act_ok(act)) return CVAE_E_BADSHAPE;
     if (!x || !W || !y) return CVAE_E_NULLPTR;
     const size_t lds = sizeof(float) * ((size_t)N * (K | 1) + (size_t)SD_ROWS * K);
-    static bool attr = false;
-    if (sd_allow_lds(sd_fwd_kernel, &attr) != CVAE_OK) return CVAE_E_LAUNCH;
+    if (cvae_allow_lds<sd_fwd_kernel>(lds) != CVAE_OK) return CVAE_E_LAUNCH;       // at most 48 KB of weights + 16 rows of the two activations (+ pitch padding)
     hipLaunchKernelGGL(sd_fwd_kernel, dim3((unsigned)((M + SD_ROWS - 1) / SD_ROWS)), dim3(256), lds, (hipStream_t)stream, x, W, b, y, M, (int)K, (int)N, x_stride, y_stride, act);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -234,8 +225,7 @@ extern "C" int cvae_small_dense_bwd_data(const float* dy, const float* W, float*
     if (in_act == CVAE_ACT_NONE) x_in = nullptr;
     if ((y_act && y_stride < N) || (x_in && x_stride < K)) return CVAE_E_BADSHAPE;
     const size_t lds = sizeof(float) * ((size_t)N * K + (size_t)SD_ROWS * N);
-    static bool attr = false;
-    if (sd_allow_lds(sd_bwd_data_kernel, &attr) != CVAE_OK) return CVAE_E_LAUNCH;
+    if (cvae_allow_lds<sd_bwd_data_kernel>(lds) != CVAE_OK) return CVAE_E_LAUNCH;
     hipLaunchKernelGGL(sd_bwd_data_kernel, dim3((unsigned)((M + SD_ROWS - 1) / SD_ROWS)), dim3(256), lds, (hipStream_t)stream, dy, W, dx, y_act, act, x_in, in_act, M, (int)K,
                        (int)N, dy_stride, dx_stride, y_stride, x_stride);
     CVAE_CHECK_LAUNCH();

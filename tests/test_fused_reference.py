@@ -135,6 +135,8 @@ SPECS = [
     ("N1_4096_M10", 10, (2, 2, 2), 64, (1, 1, 1), dict(m_dim=12, t_dim=19, N1=4096, N2=33, Z=64, HM=64)),  # the largest N1 at its largest M
     ("HM_1024_M7", 7, (2, 2, 2), 64, (1, 1, 1), dict(m_dim=12, t_dim=40, N1=100, N2=256, Z=7, HM=1024)),  # the largest HM at its largest M
     ("N2_2048_M16", 16, (2, 2, 2), 64, (2, 1, 1), dict(m_dim=12, t_dim=19, N1=512, N2=2048, Z=64, HM=64)),
+    # the mechanism FORWARD past the large-LDS opt-in: 4 M (t_dim + 2 HM) = 68544 bytes (its backward: 159540 + 2048 static of the 163840)
+    ("HM_1024_M7_T400", 7, (2, 2, 2), 64, (1, 1, 1), dict(m_dim=12, t_dim=400, N1=100, N2=256, Z=7, HM=1024)),
 ]
 
 
