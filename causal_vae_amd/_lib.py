@@ -130,6 +130,16 @@ SIGNATURES = {
     "cvae_layernorm256": [_p, _i64, _p, _p, _p, _i64, _f, _i, _p],
     "cvae_token_gemm": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _i, _p],
     "cvae_mhsa_fwd": [_p] * 4 + [_i64] * 9 + [_i, _p],
+    "cvae_mhsa_fwd_train": [_p] * 5 + [_i64] * 9 + [_i, _p],
+    "cvae_mhsa_bwd_workspace_bytes": [_i64, _i64],
+    "cvae_mhsa_bwd": [_p] * 9 + [_i64] * 15 + [_i, _p, _sz, _p],
+    "cvae_token_gemm_gelu_train": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _p],
+    "cvae_token_gemm_bwd_data": [_p, _i64, _i, _p, _p, _i64, _p, _i64, _p, _i64, _i, _i64, _i64, _i64, _i, _p],
+    "cvae_token_gemm_wgrad_workspace_bytes": [_i64] * 3,
+    "cvae_token_gemm_wgrad": [_p, _i64, _i, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _p, _sz, _p],
+    "cvae_layernorm256_bwd_workspace_bytes": [_i64],
+    "cvae_layernorm256_bwd": [_p, _i64, _i, _p, _i64, _p, _p, _i64, _i, _p, _p, _i64, _f, _p, _sz, _p],
+    "cvae_vit_tokens_bwd": [_p, _p, _p, _p, _i, _i64, _i64, _p],
     "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
     "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],
@@ -164,7 +174,8 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
             "cvae_mlp_heads_train_workspace_bytes": _sz, "cvae_mlp_heads_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,
-            "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz}
+            "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz, "cvae_mhsa_bwd_workspace_bytes": _sz,
+            "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

@@ -3,6 +3,10 @@
 //   * LayerNorm(256): one wave per row, two-pass (mean, then squared deviations), xor-shuffle wave sums;
 //   * token GEMM y = epi(x W^T + b) with epilogues none / exact-erf GELU / + residual, K <= 512 walked in LDS chunks (no split-K, no finish launch);
 //   * fused multi-head self-attention (8 heads x 32): online softmax over 64-key tiles, scores never leave the registers.
+// And its backward, for training the transformer in eval mode on a frozen stem (second half of the file): the training forms of attention (+ one
+// fp32 row statistic) and of the GELU GEMM (+ the pre-activation), a recompute-style attention backward in two passes, the token GEMM's data and weight gradients,
+// the LayerNorm backward and the token assembly's; slabs plus ordered finish launches wherever a sum crosses workgroups.
+// The token GEMM's and the attention's forward kernels live in vit_gemm.inc / vit_attention.inc, each included twice: the inference kernel and its training form.
 // Two arithmetic modes from one template: bf16 operands on v_mfma_f32_32x32x16_bf16, or exact fp32 on v_mfma_f32_32x32x2_f32 (the form the conv family uses
 // for fp32); accumulation, softmax, LayerNorm statistics and the residual stream are fp32 in both.  No atomics anywhere: every sum has a fixed order,
 // and an output element's bits do not depend on which other rows share its launch (row r of a one-row call equals row r of a full call: the CLS-only
@@ -71,6 +75,7 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* __restr
 #define GEMM_EPI_NONE 0
 #define GEMM_EPI_GELU 1
 #define GEMM_EPI_RESID 2
+#define GEMM_EPI_GELU_SAVE 3                              // GELU, and the pre-activation stored next to it (the training forward: the backward's gate)
 
 template <typename T> struct GemmGeom {
     static constexpr int KC = 128 / sizeof(T);            // k elements per chunk
@@ -84,108 +89,25 @@ __device__ __forceinline__ void lds_put_w(float* dst, float4 w) { *(float4*)dst 
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 
-template <typename T, int EPI>
-__global__ __launch_bounds__(256) void vit_gemm_kernel(const T* __restrict__ x, int64_t ldx, const float* __restrict__ W, const float* __restrict__ bias,
-                                                       const float* resid, int64_t ldr, void* yv, int64_t ldy, int64_t M, int K, int N) {
-    using G = GemmGeom<T>;
-    __shared__ __attribute__((aligned(16))) T xs[GEMM_BM * G::PITCH];
-    __shared__ __attribute__((aligned(16))) T ws[GEMM_BN * G::PITCH];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t m0 = blockIdx.x * (int64_t)GEMM_BM;
-    const int n0 = blockIdx.y * GEMM_BN;
-    uint4 rx[4];
-    float4 rw[G::WP];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = t + 256 * i, row = p >> 3, piece = p & 7;
-            const int64_t gm = m0 + row;
-            rx[i] = gm < M ? *(const uint4*)(x + gm * ldx + k0 + piece * G::E16) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < G::WP; ++i) {
-            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
-            rw[i] = *(const float4*)(W + (int64_t)(n0 + row) * K + k0 + piece * 4);
-        }
-    };
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-    fetch(0);
-    for (int k0 = 0; k0 < K; k0 += G::KC) {
-        __syncthreads();                                    // the previous chunk's fragment reads are done
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = t + 256 * i, row = p >> 3, piece = p & 7;
-            *(uint4*)(xs + row * G::PITCH + piece * G::E16) = rx[i];
-        }
-#pragma unroll
-        for (int i = 0; i < G::WP; ++i) {
-            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
-            lds_put_w(ws + row * G::PITCH + piece * 4, rw[i]);
-        }
-        __syncthreads();
-        if (k0 + G::KC < K) fetch(k0 + G::KC);
-        if constexpr (std::is_same<T, bf16>::value) {
-#pragma unroll
-            for (int s = 0; s < G::KC / 16; ++s) {
-                const bf16x8 b = *(const bf16x8*)(xs + (wave * 32 + r) * G::PITCH + 16 * s + 8 * h);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const bf16x8 a = *(const bf16x8*)(ws + (j * 32 + r) * G::PITCH + 16 * s + 8 * h);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
-                }
-            }
-        } else {
-            // 32x32x2: the instruction's k index is the lane half; step (c, u) multiplies k = 16 h + 4 c + u of the chunk (any k order gives the product)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float b[4], a[2][4];
-                load_f32(xs + (wave * 32 + r) * G::PITCH + 16 * h + 4 * c, b);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) load_f32(ws + (j * 32 + r) * G::PITCH + 16 * h + 4 * c, a[j]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j][u], b[u], acc[j], 0, 0, 0);
-            }
-        }
-    }
-    const int64_t gm = m0 + wave * 32 + r;
-    if (gm >= M) return;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = n0 + j * 32 + 8 * g + 4 * h;
-            float v[4], bv[4];
-            load_f32(bias + n, bv);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[j][4 * g + e] + bv[e];
-            if (EPI == GEMM_EPI_RESID) {
-                float rv[4];
-                load_f32(resid + gm * ldr + n, rv);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e];
-                store_from_f32((float*)yv + gm * ldy + n, v);
-            } else {
-                if (EPI == GEMM_EPI_GELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-                }
-                store_from_f32((T*)yv + gm * ldy + n, v);
-            }
-        }
-}
+#define VIT_GEMM_KERNEL vit_gemm_kernel
+#define VIT_GEMM_TRAIN 0
+#include "vit_gemm.inc"
+#undef VIT_GEMM_KERNEL
+#undef VIT_GEMM_TRAIN
+#define VIT_GEMM_KERNEL vit_gemm_train_kernel
+#define VIT_GEMM_TRAIN 1
+#include "vit_gemm.inc"
+#undef VIT_GEMM_KERNEL
+#undef VIT_GEMM_TRAIN
 
 template <typename T>
 int gemm_launch(const T* x, int64_t ldx, const float* W, const float* bias, const float* resid, int64_t ldr, void* y, int64_t ldy, int64_t M, int K, int N,
-                int epi, hipStream_t st) {
+                int epi, void* prev, int64_t ldp, hipStream_t st) {
     const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(N / GEMM_BN));
     if (epi == GEMM_EPI_NONE) hipLaunchKernelGGL((vit_gemm_kernel<T, GEMM_EPI_NONE>), grid, dim3(256), 0, st, x, ldx, W, bias, resid, ldr, y, ldy, M, K, N);
     else if (epi == GEMM_EPI_GELU) hipLaunchKernelGGL((vit_gemm_kernel<T, GEMM_EPI_GELU>), grid, dim3(256), 0, st, x, ldx, W, bias, resid, ldr, y, ldy, M, K, N);
+    else if (epi == GEMM_EPI_GELU_SAVE)
+        hipLaunchKernelGGL((vit_gemm_train_kernel<T, GEMM_EPI_GELU_SAVE>), grid, dim3(256), 0, st, x, ldx, W, bias, resid, ldr, y, ldy, M, K, N, (T*)prev, ldp);
     else hipLaunchKernelGGL((vit_gemm_kernel<T, GEMM_EPI_RESID>), grid, dim3(256), 0, st, x, ldx, W, bias, resid, ldr, y, ldy, M, K, N);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -214,148 +136,567 @@ template <> struct AttGeom<float> {
     static constexpr int NR = 2;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void vit_attention_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
-                                                            int64_t ldq, int64_t ldk, int64_t ldv, int64_t bsq, int64_t bsk, int64_t bsv, int N, int Nq,
-                                                            float scale_log2e) {
-    using G = AttGeom<T>;
-    constexpr bool BF = std::is_same<T, bf16>::value;
-    __shared__ __attribute__((aligned(16))) T Ks[G::KS];
-    __shared__ __attribute__((aligned(16))) T Vs[G::VS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int head = blockIdx.y;
-    const int64_t b = blockIdx.z;
-    const int qrow = blockIdx.x * 128 + wave * 32 + r;
-    const int qld = qrow < Nq ? qrow : Nq - 1;
-    const T* kb = k + b * bsk + head * VIT_HD;
-    const T* vb = v + b * bsv + head * VIT_HD;
+#define VIT_ATT_KERNEL vit_attention_kernel
+#define VIT_ATT_TRAIN 0
+#include "vit_attention.inc"
+#undef VIT_ATT_KERNEL
+#undef VIT_ATT_TRAIN
+#define VIT_ATT_KERNEL vit_attention_train_kernel
+#define VIT_ATT_TRAIN 1
+#include "vit_attention.inc"
+#undef VIT_ATT_KERNEL
+#undef VIT_ATT_TRAIN
 
-    // Q fragment of this lane, kept for the whole key loop: bf16 k order natural (16 s + 8 h + j), fp32 k = 16 h + i
-    bf16x8 qf[2];
-    float qs[16];
-    {
-        const T* qp = q + b * bsq + (int64_t)qld * ldq + head * VIT_HD;
-        if constexpr (BF) {
-            qf[0] = *(const bf16x8*)(qp + 8 * h);
-            qf[1] = *(const bf16x8*)(qp + 16 + 8 * h);
+// ================================================================================================ backward (training the transformer)
+// Compensated (Kahan) running sum: the value is s - c.
+__device__ __forceinline__ void kahan_add(float& s, float& c, float v) {
+    const float y = v - c, t = s + y;
+    c = (t - s) - y;
+    s = t;
+}
+
+// ------------------------------------------------------------------------------------------------ token assembly, backward
+// dpos[i] = sum_b dtokens[b][i] (b in order), dcls = dpos[0], dstem[b][i] = dtokens[b][1 + i] in the stem's dtype
+template <typename T>
+__global__ __launch_bounds__(256) void vit_tokens_bwd_kernel(const float* __restrict__ dtok, float* __restrict__ dpos, float* __restrict__ dcls,
+                                                             T* __restrict__ dstem, int64_t B, int64_t Np) {
+    const int64_t total = (Np + 1) * (VIT_DIM / 4);
+    for (int64_t g = blockIdx.x * (int64_t)256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int c4 = (int)(g & (VIT_DIM / 4 - 1));
+        const int64_t i = g >> 6;
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t b = 0; b < B; ++b) {
+            float v[4];
+            load_f32(dtok + (b * (Np + 1) + i) * VIT_DIM + c4 * 4, v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += v[e];
+            if (i > 0) store_from_f32(dstem + (b * Np + i - 1) * VIT_DIM + c4 * 4, v);
+        }
+        store_from_f32(dpos + i * VIT_DIM + c4 * 4, s);
+        if (i == 0) store_from_f32(dcls + c4 * 4, s);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ LayerNorm(256), backward
+// One wave per row, statistics recomputed two-pass from the saved fp32 input as the forward computes them: xh = (x - mean) rstd, a = gamma g,
+// dx = rstd (a - mean(a) - xh mean(a xh)), written or added to dx.  dgamma = sum_rows g xh, dbeta = sum_rows g: a workgroup owns LN_SLAB rows (a wave adds its
+// 8 rows in row order, the 4 waves are added in wave order) and leaves one partial row pair; vit_colsum_finish_kernel adds the partials in slab order.
+#define LN_SLAB 32
+template <typename TG>
+__global__ __launch_bounds__(256) void vit_layernorm_bwd_kernel(const TG* __restrict__ g, int64_t ldg, const float* __restrict__ x, int64_t ldx,
+                                                                const float* __restrict__ gamma, float* dx, int64_t lddx, float* __restrict__ part,
+                                                                int64_t rows, float eps, int accumulate) {
+    __shared__ float red[4][2][VIT_DIM];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float gm[4], dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+    load_f32(gamma + lane * 4, gm);
+    for (int i = 0; i < LN_SLAB / 4; ++i) {
+        const int64_t row = blockIdx.x * (int64_t)LN_SLAB + wave + 4 * i;
+        if (row >= rows) break;
+        float v[4], gv[4], a[4];
+        load_f32(x + row * ldx + lane * 4, v);
+        load_f32(g + row * ldg + lane * 4, gv);
+        const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.f / VIT_DIM);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] -= mean;
+        const float var = wave_sum((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) * (1.f / VIT_DIM);
+        const float rstd = 1.f / sqrtf(var + eps);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[e] *= rstd;
+            a[e] = gm[e] * gv[e];
+            dg[e] += gv[e] * v[e];
+            db[e] += gv[e];
+        }
+        const float m1 = wave_sum((a[0] + a[1]) + (a[2] + a[3])) * (1.f / VIT_DIM);
+        const float m2 = wave_sum((a[0] * v[0] + a[1] * v[1]) + (a[2] * v[2] + a[3] * v[3])) * (1.f / VIT_DIM);
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = rstd * ((a[e] - m1) - v[e] * m2);
+        float* dp = dx + row * lddx + lane * 4;
+        if (accumulate) {
+            float old[4];
+            load_f32(dp, old);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = old[e] + o[e];
+        }
+        store_from_f32(dp, o);
+    }
+    store_from_f32(&red[wave][0][lane * 4], dg);
+    store_from_f32(&red[wave][1][lane * 4], db);
+    __syncthreads();
+    const int c = threadIdx.x;
+#pragma unroll
+    for (int w = 0; w < 2; ++w)
+        part[(blockIdx.x * (int64_t)2 + w) * VIT_DIM + c] = ((red[0][w][c] + red[1][w][c]) + red[2][w][c]) + red[3][w][c];
+}
+
+// out0[c] = sum_s part[s][0][c], out1[c] = sum_s part[s][1][c], slabs in order (compensated: the slab count grows with the row count)
+__global__ __launch_bounds__(512) void vit_colsum_finish_kernel(const float* __restrict__ part, int64_t nslab, float* __restrict__ out0, float* __restrict__ out1) {
+    const int w = threadIdx.x >> 8, c = threadIdx.x & 255;
+    float s = 0.f, k = 0.f;
+    for (int64_t i = 0; i < nslab; ++i) kahan_add(s, k, part[(i * 2 + w) * VIT_DIM + c]);
+    (w ? out1 : out0)[c] = s - k;
+}
+
+// ------------------------------------------------------------------------------------------------ token GEMM, data gradient
+// dx[M][K] = (g[M][N] W[N][K]) * gelu'(pre) + resid: vit_gemm_kernel's tile and MFMA maps (token on the lane) with the roles of W's two indices exchanged.
+// W stays the fp32 nn.Linear tensor [N][K]: a chunk of KC reduction rows n x 64 output columns k is read along k and written TRANSPOSED into LDS
+// (ws[k][n], rounded to bf16 in bf16 mode), so no transposed or cast copy exists in HBM.  g may be fp32 in bf16 mode (the residual-stream gradient): it is
+// rounded to bf16 on its way into LDS as W is.  TO: bf16 / fp32 result (fp32: a stream-side gradient, the only form that takes the residual).
+__device__ __forceinline__ float gelu_erf_grad(float v) {
+    return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
+
+template <typename T, typename TG, typename TO>
+__global__ __launch_bounds__(256) void vit_gemm_bwd_data_kernel(const TG* __restrict__ g, int64_t ldg, const float* __restrict__ W, const T* __restrict__ pre,
+                                                                int64_t ldp, const float* resid, int64_t ldr, TO* dx, int64_t lddx, int64_t M, int K, int N) {
+    using G = GemmGeom<T>;
+    constexpr int NP = G::KC / 8;                         // 4-element pieces of g per thread and chunk
+    __shared__ __attribute__((aligned(16))) T xs[GEMM_BM * G::PITCH];
+    __shared__ __attribute__((aligned(16))) T ws[GEMM_BN * G::PITCH];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int64_t m0 = blockIdx.x * (int64_t)GEMM_BM;
+    const int k0 = blockIdx.y * GEMM_BN;                  // output columns of this workgroup
+    float rg[NP][4];
+    float4 rw[G::WP];
+    auto fetch = [&](int n0) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
+            const int64_t gm = m0 + row;
+            if (gm < M) load_f32(g + gm * ldg + n0 + piece * 4, rg[i]);
+            else rg[i][0] = rg[i][1] = rg[i][2] = rg[i][3] = 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < G::WP; ++i) {
+            const int p = t + 256 * i, n = p >> 4, piece = p & 15;
+            rw[i] = *(const float4*)(W + (int64_t)(n0 + n) * K + k0 + piece * 4);
+        }
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    fetch(0);
+    for (int n0 = 0; n0 < N; n0 += G::KC) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
+            lds_put_w(xs + row * G::PITCH + piece * 4, make_float4(rg[i][0], rg[i][1], rg[i][2], rg[i][3]));
+        }
+#pragma unroll
+        for (int i = 0; i < G::WP; ++i) {
+            const int p = t + 256 * i, n = p >> 4, piece = p & 15;
+            ws[(piece * 4 + 0) * G::PITCH + n] = from_f32<T>(rw[i].x);
+            ws[(piece * 4 + 1) * G::PITCH + n] = from_f32<T>(rw[i].y);
+            ws[(piece * 4 + 2) * G::PITCH + n] = from_f32<T>(rw[i].z);
+            ws[(piece * 4 + 3) * G::PITCH + n] = from_f32<T>(rw[i].w);
+        }
+        __syncthreads();
+        if (n0 + G::KC < N) fetch(n0 + G::KC);
+        if constexpr (std::is_same<T, bf16>::value) {
+#pragma unroll
+            for (int s = 0; s < G::KC / 16; ++s) {
+                const bf16x8 b = *(const bf16x8*)(xs + (wave * 32 + r) * G::PITCH + 16 * s + 8 * h);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const bf16x8 a = *(const bf16x8*)(ws + (j * 32 + r) * G::PITCH + 16 * s + 8 * h);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
+                }
+            }
         } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                float4 a = *(const float4*)(qp + 16 * h + 4 * c);
-                qs[4 * c] = a.x; qs[4 * c + 1] = a.y; qs[4 * c + 2] = a.z; qs[4 * c + 3] = a.w;
+                float b[4], a[2][4];
+                load_f32(xs + (wave * 32 + r) * G::PITCH + 16 * h + 4 * c, b);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) load_f32(ws + (j * 32 + r) * G::PITCH + 16 * h + 4 * c, a[j]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j][u], b[u], acc[j], 0, 0, 0);
             }
         }
     }
-    uint4 rk[G::NR], rv[G::NR];
-    auto fetch = [&](int kt0) {
+    const int64_t gm = m0 + wave * 32 + r;
+    if (gm >= M) return;
 #pragma unroll
-        for (int i = 0; i < G::NR; ++i) {
-            const int p = t + 256 * i;
-            const int key = BF ? (p >> 2) : (p >> 3), piece = BF ? (p & 3) : (p & 7);
-            const int gk = kt0 + key;
-            if (gk < N) {
-                rk[i] = *(const uint4*)(kb + (int64_t)gk * ldk + piece * (16 / (int)sizeof(T)));
-                rv[i] = *(const uint4*)(vb + (int64_t)gk * ldv + piece * (16 / (int)sizeof(T)));
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = k0 + j * 32 + 8 * q + 4 * h;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = acc[j][4 * q + e];
+            if (pre) {
+                float pv[4];
+                load_f32(pre + gm * ldp + k, pv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(pv[e]);
+            }
+            if (resid) {
+                float rv[4];
+                load_f32(resid + gm * ldr + k, rv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e];
+            }
+            store_from_f32(dx + gm * lddx + k, v);
+        }
+}
+
+// ------------------------------------------------------------------------------------------------ token GEMM, weight gradient
+// dW[N][K] = sum_m g[m][n] x[m][k], db[n] = sum_m g[m][n].  An MFMA GEMM whose reduction index is the token: D = x^T g, so lane (r, h) owns output row
+// n = r and, per register group, four consecutive k (16-byte stores).  Workgroup = a 64 (n) x 64 (k) tile of ONE slab of WG_SLAB tokens (the slab cut
+// depends on M only), 4 waves of 32 x 32, tokens walked in chunks of 64.  bf16: both operands are written transposed into LDS ([feature][token]) so that a
+// fragment is 8 consecutive tokens; fp32 (32x32x2, the token pair on the lane halves): natural layout.  Each workgroup writes its partial tile once;
+// vit_wgrad_finish_kernel adds the slabs in slab order.  Bias: the workgroups of k tile 0 keep a compensated sum per thread (its 4 columns, its tokens in
+// order), join the 16 threads of a column in thread order, and leave (sum, compensation) in the slab.
+#define WG_SLAB 512
+#define WG_CHUNK 64
+template <typename T> struct WgradGeom;
+template <> struct WgradGeom<bf16> { static constexpr int ROWS = 64, PITCH = WG_CHUNK + 8; };     // [feature][token], 144-byte rows
+template <> struct WgradGeom<float> { static constexpr int ROWS = WG_CHUNK, PITCH = 64 + 4; };   // [token][feature], 272-byte rows
+
+template <typename T, typename TG>
+__global__ __launch_bounds__(256) void vit_gemm_wgrad_kernel(const TG* __restrict__ g, int64_t ldg, const T* __restrict__ x, int64_t ldx,
+                                                             float* __restrict__ part, float* __restrict__ bpart, int64_t M, int K, int N) {
+    using G = WgradGeom<T>;
+    constexpr bool BF = std::is_same<T, bf16>::value;
+    __shared__ __attribute__((aligned(16))) T gs[G::ROWS * G::PITCH];
+    __shared__ __attribute__((aligned(16))) T xs[G::ROWS * G::PITCH];
+    __shared__ float bred[16][64][2];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5, wn = wave >> 1, wk = wave & 1;
+    const int n0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
+    const int64_t slab = blockIdx.z, mbeg = slab * WG_SLAB, mend = mbeg + WG_SLAB < M ? mbeg + WG_SLAB : M;
+    const int tok = t >> 4, piece = t & 15;               // this thread's pieces: tokens tok + 16 i of the chunk, columns 4 piece .. 4 piece + 3
+    const bool want_bias = blockIdx.y == 0;
+    float bs[4] = {0.f, 0.f, 0.f, 0.f}, bc[4] = {0.f, 0.f, 0.f, 0.f};
+    float rg[4][4], rx[4][4];
+    auto fetch = [&](int64_t mc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t m = mc + tok + 16 * i;
+            if (m < mend) {
+                load_f32(g + m * ldg + n0 + piece * 4, rg[i]);
+                load_f32(x + m * ldx + k0 + piece * 4, rx[i]);
             } else {
-                rk[i] = make_uint4(0, 0, 0, 0);
-                rv[i] = make_uint4(0, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rg[i][e] = rx[i][e] = 0.f;
             }
         }
     };
-    f32x16 o;
+    f32x16 acc;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.f;
-    float m_run = -__builtin_inff(), l_run = 0.f;
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    fetch(mbeg);
+    for (int64_t mc = mbeg; mc < mend; mc += WG_CHUNK) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (BF) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    gs[(piece * 4 + e) * G::PITCH + tok + 16 * i] = (bf16)rg[i][e];
+                    xs[(piece * 4 + e) * G::PITCH + tok + 16 * i] = (bf16)rx[i][e];
+                }
+            } else {
+                store_from_f32(gs + (tok + 16 * i) * G::PITCH + piece * 4, rg[i]);
+                store_from_f32(xs + (tok + 16 * i) * G::PITCH + piece * 4, rx[i]);
+            }
+            if (want_bias) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) kahan_add(bs[e], bc[e], rg[i][e]);
+            }
+        }
+        __syncthreads();
+        if (mc + WG_CHUNK < mend) fetch(mc + WG_CHUNK);
+        if constexpr (BF) {
+#pragma unroll
+            for (int s = 0; s < WG_CHUNK / 16; ++s) {
+                const bf16x8 a = *(const bf16x8*)(xs + (wk * 32 + r) * G::PITCH + 16 * s + 8 * h);
+                const bf16x8 b = *(const bf16x8*)(gs + (wn * 32 + r) * G::PITCH + 16 * s + 8 * h);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+            }
+        } else {
+#pragma unroll 8
+            for (int s = 0; s < WG_CHUNK / 2; ++s) {
+                const float a = xs[(2 * s + h) * G::PITCH + wk * 32 + r], b = gs[(2 * s + h) * G::PITCH + wn * 32 + r];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        }
+    }
+    float* pt = part + (slab * N + n0 + wn * 32 + r) * K + k0 + wk * 32;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = acc[4 * q + e];
+        store_from_f32(pt + 8 * q + 4 * h, v);
+    }
+    if (!want_bias) return;                               // uniform over the workgroup
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        bred[tok][piece * 4 + e][0] = bs[e];
+        bred[tok][piece * 4 + e][1] = bc[e];
+    }
+    __syncthreads();
+    if (t < 64) {
+        float s = 0.f, c = 0.f;
+        for (int j = 0; j < 16; ++j) {
+            kahan_add(s, c, bred[j][t][0]);
+            kahan_add(s, c, -bred[j][t][1]);
+        }
+        bpart[(slab * N + n0 + t) * 2] = s;
+        bpart[(slab * N + n0 + t) * 2 + 1] = c;
+    }
+}
+
+__global__ __launch_bounds__(256) void vit_wgrad_finish_kernel(const float* __restrict__ part, const float* __restrict__ bpart, float* __restrict__ dW,
+                                                               float* __restrict__ db, int64_t nslab, int64_t NK, int N) {
+    const int64_t id = blockIdx.x * (int64_t)256 + threadIdx.x;
+    for (int64_t p = id; p < NK / 4; p += (int64_t)gridDim.x * 256) {
+        float s[4];
+        load_f32(part + p * 4, s);
+        for (int64_t i = 1; i < nslab; ++i) {
+            float v[4];
+            load_f32(part + i * NK + p * 4, v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += v[e];
+        }
+        store_from_f32(dW + p * 4, s);
+    }
+    if (id < N) {
+        float s = 0.f, c = 0.f;
+        for (int64_t i = 0; i < nslab; ++i) {
+            kahan_add(s, c, bpart[(i * N + id) * 2]);
+            kahan_add(s, c, -bpart[(i * N + id) * 2 + 1]);
+        }
+        db[id] = s - c;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ fused attention, backward
+// Recompute-style (no N x N matrix leaves the registers): P = 2^(s log2e / sqrt(32) - lse) from the forward's saved row statistic,
+// dP = dO V^T, dS = P (dP - delta) / sqrt(32) with delta = rowsum(dO * O) in fp32, dQ = dS K, dK = dS^T Q, dV = P^T dO.  No atomics: two passes of ONE kernel
+// template, each the forward's loop with the roles of the two token axes chosen so that the OWNED token is the lane:
+//   dq pass  (DKV = false): a workgroup owns 128 query rows (own pair = Q, dO) and walks the key tiles (walk pair = K, V); it also computes delta for its
+//            rows and leaves it in the workspace;
+//   dkv pass (DKV = true):  a workgroup owns 128 key rows (own pair = K, V) and walks the query tiles (walk pair = Q, dO), reading lse and delta per tile.
+// Per 32-row walk sub-tile: S = W1 own1^T and dP = W2 own2^T (A = the walk tile from LDS, B = the lane's own fragment, as the forward's S^T = K Q^T), then
+// acc1 += W1^T dS (dQ^T resp. dK^T) and, in the dkv pass, acc2 += W2^T P (dV^T), with the score registers as the B operand (as the forward's O^T = V^T P^T).
+// bf16: both walk tensors are staged twice, natural and transposed; P and dS are rounded to bf16 for their products.  Walk rows past the end are zeros
+// with P = 0; own rows past the end are clamped on load and never stored.
+struct AttBwdArgs {
+    const void *own1, *own2, *walk1, *walk2, *out;
+    int64_t ld_o1, ld_o2, ld_w1, ld_w2, bs_o1, bs_o2, bs_w1, bs_w2;
+    const float* lse;
+    float* delta;
+    void *g1, *g2;
+    int64_t ld_g1, ld_g2, bs_g1, bs_g2;
+    int n_own, n_walk, Nq;
+    float scale_log2e, scale;
+};
+template <typename T> struct AttBwdGeom;
+template <> struct AttBwdGeom<bf16> { static constexpr int NP = 40, TP = 72, NS = ATT_KT * NP, TS = VIT_HD * TP, NR = 1; };
+template <> struct AttBwdGeom<float> { static constexpr int NP = 40, TP = 0, NS = ATT_KT * NP, TS = 4, NR = 2; };
+
+template <typename T, bool DKV>
+__global__ __launch_bounds__(256) void vit_attention_bwd_kernel(const AttBwdArgs a) {
+    using G = AttBwdGeom<T>;
+    constexpr bool BF = std::is_same<T, bf16>::value;
+    __shared__ __attribute__((aligned(16))) T W1n[G::NS];
+    __shared__ __attribute__((aligned(16))) T W2n[G::NS];
+    __shared__ __attribute__((aligned(16))) T W1t[G::TS];
+    __shared__ __attribute__((aligned(16))) T W2t[G::TS];
+    __shared__ float Ls[ATT_KT], Ds[ATT_KT];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y;
+    const int64_t b = blockIdx.z;
+    const int orow = blockIdx.x * 128 + wave * 32 + r;
+    const int old = orow < a.n_own ? orow : a.n_own - 1;
+    const T* w1 = (const T*)a.walk1 + b * a.bs_w1 + head * VIT_HD;
+    const T* w2 = (const T*)a.walk2 + b * a.bs_w2 + head * VIT_HD;
+    const int64_t stat0 = (b * VIT_HEADS + head) * a.Nq;
+
+    // own fragments, kept for the whole walk: bf16 k order natural (16 s + 8 h + j), fp32 k = 16 h + i
+    bf16x8 f1[2], f2[2];
+    float s1[16], s2[16];
+    float lse_own = 0.f, delta_own = 0.f;
+    {
+        const T* p1 = (const T*)a.own1 + b * a.bs_o1 + (int64_t)old * a.ld_o1 + head * VIT_HD;
+        const T* p2 = (const T*)a.own2 + b * a.bs_o2 + (int64_t)old * a.ld_o2 + head * VIT_HD;
+        if constexpr (BF) {
+            f1[0] = *(const bf16x8*)(p1 + 8 * h);
+            f1[1] = *(const bf16x8*)(p1 + 16 + 8 * h);
+            f2[0] = *(const bf16x8*)(p2 + 8 * h);
+            f2[1] = *(const bf16x8*)(p2 + 16 + 8 * h);
+        } else {
+            load_f32(p1 + 16 * h, s1);
+            load_f32(p2 + 16 * h, s2);
+        }
+        if constexpr (!DKV) {                             // delta of this lane's query row: its half of the 32 columns, then the other half's
+            const T* po = (const T*)a.out + (b * a.Nq + old) * VIT_DIM + head * VIT_HD;
+            float d = 0.f;
+            if constexpr (BF) {
+                float o0[8], o1[8];
+                load_f32(po + 8 * h, o0);
+                load_f32(po + 16 + 8 * h, o1);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d += (float)f2[0][j] * o0[j];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d += (float)f2[1][j] * o1[j];
+            } else {
+                float o[16];
+                load_f32(po + 16 * h, o);
+#pragma unroll
+                for (int j = 0; j < 16; ++j) d += s2[j] * o[j];
+            }
+            delta_own = d + __shfl_xor(d, 32, 64);
+            lse_own = a.lse[stat0 + old];
+            if (h == 0 && orow < a.n_own) a.delta[stat0 + orow] = delta_own;
+        }
+    }
+    uint4 r1[G::NR], r2[G::NR];
+    float rl = 0.f, rd = 0.f;
+    auto fetch = [&](int wt0) {
+#pragma unroll
+        for (int i = 0; i < G::NR; ++i) {
+            const int p = t + 256 * i;
+            const int row = BF ? (p >> 2) : (p >> 3), piece = BF ? (p & 3) : (p & 7);
+            const int gr = wt0 + row;
+            if (gr < a.n_walk) {
+                r1[i] = *(const uint4*)(w1 + (int64_t)gr * a.ld_w1 + piece * (16 / (int)sizeof(T)));
+                r2[i] = *(const uint4*)(w2 + (int64_t)gr * a.ld_w2 + piece * (16 / (int)sizeof(T)));
+            } else {
+                r1[i] = make_uint4(0, 0, 0, 0);
+                r2[i] = make_uint4(0, 0, 0, 0);
+            }
+        }
+        if (DKV && t < ATT_KT) {
+            const int gr = wt0 + t;
+            rl = gr < a.n_walk ? a.lse[stat0 + gr] : 0.f;
+            rd = gr < a.n_walk ? a.delta[stat0 + gr] : 0.f;
+        }
+    };
+    f32x16 acc1, acc2;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc1[e] = acc2[e] = 0.f;
     fetch(0);
-    for (int kt0 = 0; kt0 < N; kt0 += ATT_KT) {
+    for (int wt0 = 0; wt0 < a.n_walk; wt0 += ATT_KT) {
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < G::NR; ++i) {
             const int p = t + 256 * i;
             if constexpr (BF) {
-                const int key = p >> 2, piece = p & 3;
-                *(uint4*)(Ks + key * G::KP + piece * 8) = rk[i];
-                const bf16x8 vv = __builtin_bit_cast(bf16x8, rv[i]);
+                const int row = p >> 2, piece = p & 3;
+                *(uint4*)(W1n + row * G::NP + piece * 8) = r1[i];
+                *(uint4*)(W2n + row * G::NP + piece * 8) = r2[i];
+                const bf16x8 v1 = __builtin_bit_cast(bf16x8, r1[i]), v2 = __builtin_bit_cast(bf16x8, r2[i]);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) Vs[(piece * 8 + e) * G::VP + key] = vv[e];
+                for (int e = 0; e < 8; ++e) {
+                    W1t[(piece * 8 + e) * G::TP + row] = v1[e];
+                    if (DKV) W2t[(piece * 8 + e) * G::TP + row] = v2[e];
+                }
             } else {
-                const int key = p >> 3, piece = p & 7;
-                *(uint4*)(Ks + key * G::KP + piece * 4) = rk[i];
-                *(uint4*)(Vs + key * G::VP + piece * 4) = rv[i];
+                const int row = p >> 3, piece = p & 7;
+                *(uint4*)(W1n + row * G::NP + piece * 4) = r1[i];
+                *(uint4*)(W2n + row * G::NP + piece * 4) = r2[i];
             }
         }
+        if (DKV && t < ATT_KT) {
+            Ls[t] = rl;
+            Ds[t] = rd;
+        }
         __syncthreads();
-        if (kt0 + ATT_KT < N) fetch(kt0 + ATT_KT);
+        if (wt0 + ATT_KT < a.n_walk) fetch(wt0 + ATT_KT);
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
-            const int key0 = kt0 + sub * 32;
-            if (key0 >= N) break;                           // uniform over the workgroup
-            f32x16 sc;
+            const int row0 = wt0 + sub * 32;
+            if (row0 >= a.n_walk) break;                    // uniform over the workgroup
+            f32x16 sc, dp;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) sc[e] = 0.f;
+            for (int e = 0; e < 16; ++e) sc[e] = dp[e] = 0.f;
             if constexpr (BF) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const bf16x8 a = *(const bf16x8*)(Ks + (sub * 32 + r) * G::KP + 16 * s + 8 * h);
-                    sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[s], sc, 0, 0, 0);
+                    const bf16x8 x1 = *(const bf16x8*)(W1n + (sub * 32 + r) * G::NP + 16 * s + 8 * h);
+                    const bf16x8 x2 = *(const bf16x8*)(W2n + (sub * 32 + r) * G::NP + 16 * s + 8 * h);
+                    sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, f1[s], sc, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, f2[s], dp, 0, 0, 0);
                 }
             } else {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    float a[4];
-                    load_f32((const float*)Ks + (sub * 32 + r) * G::KP + 16 * h + 4 * c, a);
+                    float x1[4], x2[4];
+                    load_f32((const float*)W1n + (sub * 32 + r) * G::NP + 16 * h + 4 * c, x1);
+                    load_f32((const float*)W2n + (sub * 32 + r) * G::NP + 16 * h + 4 * c, x2);
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], qs[4 * c + u], sc, 0, 0, 0);
+                    for (int u = 0; u < 4; ++u) {
+                        sc = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[u], s1[4 * c + u], sc, 0, 0, 0);
+                        dp = __builtin_amdgcn_mfma_f32_32x32x2f32(x2[u], s2[4 * c + u], dp, 0, 0, 0);
+                    }
                 }
             }
-            float p[16];
-            float mx = -__builtin_inff();
+            float p[16], ds[16];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                p[e] = (key0 + crow(e, h) < N) ? sc[e] * scale_log2e : -__builtin_inff();
-                mx = fmaxf(mx, p[e]);
+                const int wr = sub * 32 + crow(e, h);
+                const float lv = DKV ? Ls[wr] : lse_own, dv = DKV ? Ds[wr] : delta_own;
+                p[e] = (wt0 + wr < a.n_walk) ? exp2f(sc[e] * a.scale_log2e - lv) : 0.f;
+                ds[e] = p[e] * (dp[e] - dv) * a.scale;
             }
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);           // finite: key0 < N, so the sub-tile has at least one live key
-            const float alpha = exp2f(m_run - m_new);       // first tile: exp2(-inf) = 0
-            float ls = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                p[e] = exp2f(p[e] - m_new);
-                ls += p[e];
-            }
-            l_run = l_run * alpha + ls;
-            m_run = m_new;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[e] *= alpha;
             if constexpr (BF) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const uint4 pk = make_uint4(pack2_bf16(p[8 * s], p[8 * s + 1]), pack2_bf16(p[8 * s + 2], p[8 * s + 3]),
-                                                pack2_bf16(p[8 * s + 4], p[8 * s + 5]), pack2_bf16(p[8 * s + 6], p[8 * s + 7]));
-                    const uint2 v0 = *(const uint2*)(Vs + r * G::VP + sub * 32 + 16 * s + 4 * h);
-                    const uint2 v1 = *(const uint2*)(Vs + r * G::VP + sub * 32 + 16 * s + 8 + 4 * h);
-                    const bf16x8 a = __builtin_bit_cast(bf16x8, make_uint4(v0.x, v0.y, v1.x, v1.y));
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, pk), o, 0, 0, 0);
+                    const uint4 dk = make_uint4(pack2_bf16(ds[8 * s], ds[8 * s + 1]), pack2_bf16(ds[8 * s + 2], ds[8 * s + 3]),
+                                                pack2_bf16(ds[8 * s + 4], ds[8 * s + 5]), pack2_bf16(ds[8 * s + 6], ds[8 * s + 7]));
+                    const uint2 u0 = *(const uint2*)(W1t + r * G::TP + sub * 32 + 16 * s + 4 * h);
+                    const uint2 u1 = *(const uint2*)(W1t + r * G::TP + sub * 32 + 16 * s + 8 + 4 * h);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y)), __builtin_bit_cast(bf16x8, dk),
+                                                                   acc1, 0, 0, 0);
+                    if constexpr (DKV) {
+                        const uint4 pk = make_uint4(pack2_bf16(p[8 * s], p[8 * s + 1]), pack2_bf16(p[8 * s + 2], p[8 * s + 3]),
+                                                    pack2_bf16(p[8 * s + 4], p[8 * s + 5]), pack2_bf16(p[8 * s + 6], p[8 * s + 7]));
+                        const uint2 v0 = *(const uint2*)(W2t + r * G::TP + sub * 32 + 16 * s + 4 * h);
+                        const uint2 v1 = *(const uint2*)(W2t + r * G::TP + sub * 32 + 16 * s + 8 + 4 * h);
+                        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(v0.x, v0.y, v1.x, v1.y)),
+                                                                       __builtin_bit_cast(bf16x8, pk), acc2, 0, 0, 0);
+                    }
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const float a = ((const float*)Vs)[(sub * 32 + crow(e, h)) * G::VP + r];
-                    o = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[e], o, 0, 0, 0);
+                    const float x1 = ((const float*)W1n)[(sub * 32 + crow(e, h)) * G::NP + r];
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, ds[e], acc1, 0, 0, 0);
+                    if constexpr (DKV) {
+                        const float x2 = ((const float*)W2n)[(sub * 32 + crow(e, h)) * G::NP + r];
+                        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x2, p[e], acc2, 0, 0, 0);
+                    }
                 }
             }
         }
     }
-    const float l = l_run + __shfl_xor(l_run, 32, 64);
-    if (qrow >= Nq) return;
-    T* op = out + (b * Nq + qrow) * VIT_DIM + head * VIT_HD;
+    if (orow >= a.n_own) return;
+    T* o1 = (T*)a.g1 + b * a.bs_g1 + (int64_t)orow * a.ld_g1 + head * VIT_HD;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
+    for (int q = 0; q < 4; ++q) {
         float w[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = o[4 * g + e] / l;
-        store_from_f32(op + 8 * g + 4 * h, w);
+        for (int e = 0; e < 4; ++e) w[e] = acc1[4 * q + e];
+        store_from_f32(o1 + 8 * q + 4 * h, w);
+    }
+    if constexpr (DKV) {
+        T* o2 = (T*)a.g2 + b * a.bs_g2 + (int64_t)orow * a.ld_g2 + head * VIT_HD;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] = acc2[4 * q + e];
+            store_from_f32(o2 + 8 * q + 4 * h, w);
+        }
     }
 }
 
@@ -387,23 +728,38 @@ extern "C" int cvae_layernorm256(const float* x, int64_t x_stride, const float* 
     return CVAE_OK;
 }
 
-extern "C" int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y,
-                               int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, int dtype, void* stream) {
+static int token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y, int64_t y_stride,
+                      int64_t M, int64_t K, int64_t N, int epilogue, int max_epilogue, int dtype, void* pre, int64_t pre_stride, void* stream) {
     if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
-    if (epilogue < CVAE_GEMM_EPI_NONE || epilogue > CVAE_GEMM_EPI_RESIDUAL) return CVAE_E_BADSHAPE;
+    if (epilogue < GEMM_EPI_NONE || epilogue > max_epilogue) return CVAE_E_BADSHAPE;
     if (!((K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256))) return CVAE_E_UNSUPPORTED;
     if (!x || !W || !bias || !y) return CVAE_E_NULLPTR;
     if (epilogue == CVAE_GEMM_EPI_RESIDUAL && (!resid || resid_stride < N || (resid_stride & 3) || !aligned16(resid))) return resid ? CVAE_E_BADSHAPE : CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4, ye16 = (epilogue == CVAE_GEMM_EPI_RESIDUAL || dtype == CVAE_F32) ? 4 : 8;
     if ((x_stride % e16) || (y_stride % ye16) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    if (epilogue == GEMM_EPI_GELU_SAVE) {
+        if (!pre) return CVAE_E_NULLPTR;
+        if (pre_stride < N) return CVAE_E_BADSHAPE;
+        if ((pre_stride % e16) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) return gemm_launch<bf16>((const bf16*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, st);
-    return gemm_launch<float>((const float*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, st);
+    if (dtype == CVAE_BF16) return gemm_launch<bf16>((const bf16*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
+    return gemm_launch<float>((const float*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
 }
 
-extern "C" int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
-                             int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream) {
+extern "C" int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y,
+                               int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, int dtype, void* stream) {
+    return token_gemm(x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, K, N, epilogue, CVAE_GEMM_EPI_RESIDUAL, dtype, nullptr, 0, stream);
+}
+
+extern "C" int cvae_token_gemm_gelu_train(const void* x, int64_t x_stride, const float* W, const float* bias, void* pre, int64_t pre_stride, void* y, int64_t y_stride,
+                                          int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
+    return token_gemm(x, x_stride, W, bias, nullptr, 0, y, y_stride, M, K, N, GEMM_EPI_GELU_SAVE, GEMM_EPI_GELU_SAVE, dtype, pre, pre_stride, stream);
+}
+
+static int mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
+                    int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, float* lse, void* stream) {
     if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
     if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (!q || !k || !v || !out) return CVAE_E_NULLPTR;
@@ -414,12 +770,166 @@ extern "C" int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* 
         return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
     const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // 1 / sqrt(32) * log2(e)
-    if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(vit_attention_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, q_stride,
-                           k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e);
+    hipStream_t st = (hipStream_t)stream;
+#define ATT_ARGS(T) (const T*)q, (const T*)k, (const T*)v, (T*)out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, (int)n_tokens, \
+                    (int)n_query_rows, scale_log2e
+    if (dtype == CVAE_BF16 && lse) hipLaunchKernelGGL(vit_attention_train_kernel<bf16>, grid, dim3(256), 0, st, ATT_ARGS(bf16), lse);
+    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(vit_attention_kernel<bf16>, grid, dim3(256), 0, st, ATT_ARGS(bf16));
+    else if (lse) hipLaunchKernelGGL(vit_attention_train_kernel<float>, grid, dim3(256), 0, st, ATT_ARGS(float), lse);
+    else hipLaunchKernelGGL(vit_attention_kernel<float>, grid, dim3(256), 0, st, ATT_ARGS(float));
+#undef ATT_ARGS
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
+                             int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream) {
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, nullptr, stream);
+}
+
+extern "C" int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                   int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype,
+                                   void* stream) {
+    if (!lse) return CVAE_E_NULLPTR;
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, lse, stream);
+}
+
+// ---- backward entries.  Every argument check precedes the first launch; workspaces are the caller's.
+static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
+static bool is_dtype(int d) { return d == CVAE_F32 || d == CVAE_BF16; }
+
+extern "C" int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, int64_t B, int64_t n_patches, void* stream) {
+    if (B < 1 || n_patches < 1 || B * (n_patches + 1) > ((int64_t)1 << 32)) return CVAE_E_BADSHAPE;
+    if (!is_dtype(stem_dtype)) return CVAE_E_DTYPE;
+    if (!dtokens || !dpos || !dcls || !dstem) return CVAE_E_NULLPTR;
+    if (!aligned16(dtokens) || !aligned16(dpos) || !aligned16(dcls) || !aligned16(dstem)) return CVAE_E_UNSUPPORTED;
+    const int blocks = cvae_grid_1d((n_patches + 1) * (VIT_DIM / 4), 256, 256 * 32);
+    if (stem_dtype == CVAE_BF16)
+        hipLaunchKernelGGL(vit_tokens_bwd_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (bf16*)dstem, B, n_patches);
     else
-        hipLaunchKernelGGL(vit_attention_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)q, (const float*)k, (const float*)v, (float*)out,
-                           q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e);
+        hipLaunchKernelGGL(vit_tokens_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (float*)dstem, B, n_patches);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" size_t cvae_layernorm256_bwd_workspace_bytes(int64_t rows) {
+    return rows < 1 ? 0 : (size_t)((rows + LN_SLAB - 1) / LN_SLAB) * 2 * VIT_DIM * sizeof(float);
+}
+
+extern "C" int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtype, const float* x, int64_t x_stride, const float* gamma, float* dx, int64_t dx_stride,
+                                     int accumulate, float* dgamma, float* dbeta, int64_t rows, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+    if (rows < 1 || rows > ((int64_t)1 << 32) || x_stride < VIT_DIM || (x_stride & 3) || dx_stride < VIT_DIM || (dx_stride & 3) || g_stride < VIT_DIM) return CVAE_E_BADSHAPE;
+    if (!is_dtype(g_dtype)) return CVAE_E_DTYPE;
+    if (!g || !x || !gamma || !dx || !dgamma || !dbeta || !workspace) return CVAE_E_NULLPTR;
+    if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || !aligned16(g) || !aligned16(x) || !aligned16(gamma) || !aligned16(dx) || !aligned16(workspace)) return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_layernorm256_bwd_workspace_bytes(rows)) return CVAE_E_WORKSPACE;
+    const int64_t nslab = (rows + LN_SLAB - 1) / LN_SLAB;
+    hipStream_t st = (hipStream_t)stream;
+    if (g_dtype == CVAE_BF16)
+        hipLaunchKernelGGL(vit_layernorm_bwd_kernel<bf16>, dim3((unsigned)nslab), dim3(256), 0, st, (const bf16*)g, g_stride, x, x_stride, gamma, dx, dx_stride,
+                           (float*)workspace, rows, eps, accumulate);
+    else
+        hipLaunchKernelGGL(vit_layernorm_bwd_kernel<float>, dim3((unsigned)nslab), dim3(256), 0, st, (const float*)g, g_stride, x, x_stride, gamma, dx, dx_stride,
+                           (float*)workspace, rows, eps, accumulate);
+    CVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vit_colsum_finish_kernel, dim3(1), dim3(512), 0, st, (const float*)workspace, nslab, dgamma, dbeta);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
+                                        int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
+    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K) return CVAE_E_BADSHAPE;
+    if (!is_dtype(dtype) || !is_dtype(g_dtype) || !is_dtype(dx_dtype)) return CVAE_E_DTYPE;
+    if (dtype == CVAE_F32 && (g_dtype != CVAE_F32 || dx_dtype != CVAE_F32)) return CVAE_E_DTYPE;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
+    if (!g || !W || !dx) return CVAE_E_NULLPTR;
+    if (resid && (dx_dtype != CVAE_F32 || resid_stride < K || (resid_stride & 3))) return CVAE_E_BADSHAPE;
+    if (pre && pre_stride < K) return CVAE_E_BADSHAPE;
+    const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
+    if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || (dx_stride % (dx_dtype == CVAE_BF16 ? 8 : 4)) || (pre && (pre_stride % e16)) || !aligned16(g) || !aligned16(W) ||
+        !aligned16(dx) || !aligned16(pre) || !aligned16(resid))
+        return CVAE_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
+    hipStream_t st = (hipStream_t)stream;
+#define BWD_DATA(T, TG, TO)                                                                                                                                   \
+    hipLaunchKernelGGL((vit_gemm_bwd_data_kernel<T, TG, TO>), grid, dim3(256), 0, st, (const TG*)g, g_stride, W, (const T*)pre, pre_stride, resid, resid_stride, \
+                       (TO*)dx, dx_stride, M, (int)K, (int)N)
+    if (dtype == CVAE_F32) BWD_DATA(float, float, float);
+    else if (g_dtype == CVAE_BF16 && dx_dtype == CVAE_BF16) BWD_DATA(bf16, bf16, bf16);
+    else if (g_dtype == CVAE_BF16) BWD_DATA(bf16, bf16, float);
+    else if (dx_dtype == CVAE_BF16) BWD_DATA(bf16, float, bf16);
+    else BWD_DATA(bf16, float, float);
+#undef BWD_DATA
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" size_t cvae_token_gemm_wgrad_workspace_bytes(int64_t M, int64_t K, int64_t N) {
+    if (M < 1 || M > (int64_t)65535 * WG_SLAB || !gemm_shape_ok(K, N)) return 0;
+    return (size_t)((M + WG_SLAB - 1) / WG_SLAB) * (size_t)(N * K + 2 * N) * sizeof(float);
+}
+
+extern "C" int cvae_token_gemm_wgrad(const void* g, int64_t g_stride, int g_dtype, const void* x, int64_t x_stride, float* dW, float* db, int64_t M, int64_t K,
+                                     int64_t N, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (M < 1 || M > (int64_t)65535 * WG_SLAB || g_stride < N || x_stride < K) return CVAE_E_BADSHAPE;      // the slab index is grid.z
+    if (!is_dtype(dtype) || !is_dtype(g_dtype) || (dtype == CVAE_F32 && g_dtype != CVAE_F32)) return CVAE_E_DTYPE;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
+    if (!g || !x || !dW || !db || !workspace) return CVAE_E_NULLPTR;
+    if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || (x_stride % (dtype == CVAE_BF16 ? 8 : 4)) || !aligned16(g) || !aligned16(x) || !aligned16(dW) || !aligned16(workspace))
+        return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_token_gemm_wgrad_workspace_bytes(M, K, N)) return CVAE_E_WORKSPACE;
+    const int64_t nslab = (M + WG_SLAB - 1) / WG_SLAB;
+    float* part = (float*)workspace;
+    float* bpart = part + nslab * N * K;
+    const dim3 grid((unsigned)(N / 64), (unsigned)(K / 64), (unsigned)nslab);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CVAE_F32)
+        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<float, float>), grid, dim3(256), 0, st, (const float*)g, g_stride, (const float*)x, x_stride, part, bpart, M, (int)K, (int)N);
+    else if (g_dtype == CVAE_BF16)
+        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<bf16, bf16>), grid, dim3(256), 0, st, (const bf16*)g, g_stride, (const bf16*)x, x_stride, part, bpart, M, (int)K, (int)N);
+    else
+        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<bf16, float>), grid, dim3(256), 0, st, (const float*)g, g_stride, (const bf16*)x, x_stride, part, bpart, M, (int)K, (int)N);
+    CVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vit_wgrad_finish_kernel, dim3((unsigned)(N * K / 4 / 256)), dim3(256), 0, st, (const float*)part, (const float*)bpart, dW, db, nslab, N * K, (int)N);
+    CVAE_CHECK_LAUNCH();
+    return CVAE_OK;
+}
+
+extern "C" size_t cvae_mhsa_bwd_workspace_bytes(int64_t B, int64_t n_query_rows) {
+    return (B < 1 || n_query_rows < 1) ? 0 : (size_t)(B * VIT_HEADS * n_query_rows) * sizeof(float);
+}
+
+extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* dout, void* dq, void* dk, void* dv,
+                             int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                             int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
+                             int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+    if (!is_dtype(dtype)) return CVAE_E_DTYPE;
+    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !workspace) return CVAE_E_NULLPTR;
+    const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
+    const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
+                                 dq_batch_stride, dk_batch_stride, dv_batch_stride};
+    for (int i = 0; i < 12; ++i)
+        if (strides[i] < (i < 6 ? VIT_DIM : 0)) return CVAE_E_BADSHAPE;
+    for (int i = 0; i < 12; ++i)
+        if (strides[i] % e16) return CVAE_E_UNSUPPORTED;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv)) return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_mhsa_bwd_workspace_bytes(B, n_query_rows)) return CVAE_E_WORKSPACE;
+    const int N = (int)n_tokens, Nq = (int)n_query_rows;
+    const int64_t ob = (int64_t)Nq * VIT_DIM;
+    const float scale = 0.17677669529663688110f, scale_log2e = scale * 1.44269504088896340736f;
+    const AttBwdArgs aq = {q, dout, k, v, out, q_stride, VIT_DIM, k_stride, v_stride, q_batch_stride, ob, k_batch_stride, v_batch_stride, lse, (float*)workspace,
+                           dq, nullptr, dq_stride, 0, dq_batch_stride, 0, Nq, N, Nq, scale_log2e, scale};
+    const AttBwdArgs ak = {k, v, q, dout, out, k_stride, v_stride, q_stride, VIT_DIM, k_batch_stride, v_batch_stride, q_batch_stride, ob, lse, (float*)workspace,
+                           dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
+    const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CVAE_BF16) hipLaunchKernelGGL((vit_attention_bwd_kernel<bf16, false>), gq, dim3(256), 0, st, aq);
+    else hipLaunchKernelGGL((vit_attention_bwd_kernel<float, false>), gq, dim3(256), 0, st, aq);
+    CVAE_CHECK_LAUNCH();
+    if (dtype == CVAE_BF16) hipLaunchKernelGGL((vit_attention_bwd_kernel<bf16, true>), gk, dim3(256), 0, st, ak);
+    else hipLaunchKernelGGL((vit_attention_bwd_kernel<float, true>), gk, dim3(256), 0, st, ak);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }

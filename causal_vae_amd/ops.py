@@ -2012,6 +2012,169 @@ def mhsa(q, k, v, n_query_rows=None):
     return out
 
 
+# ---- ViT-VAE encoder, training the transformer (csrc/vit.hip): the backward building blocks, on raw tensors as the ones above ---------
+def _mhsa_views(what, B, rows, *ts):
+    for t, n in zip(ts, rows):
+        if t.dim() != 3 or t.shape[2] != 256 or t.stride(2) != 1 or t.dtype != ts[0].dtype or t.shape[0] != B or t.shape[1] < n:
+            raise L.CvaeError(f"{what}: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
+
+
+def _overlap(a, b):
+    """do two [B, tokens, 256] views with unit column stride share an element?  Panels of one packed buffer interleave: same storage, the same row and batch
+    strides and column ranges that meet; anything else is compared by its address range."""
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+    if a.stride() == b.stride() and a.stride(1) >= 256:
+        off = (b.storage_offset() - a.storage_offset()) % a.stride(1)
+        if min(off, a.stride(1) - off) >= 256:
+            return False                                                    # disjoint column panels of the same rows
+    span = lambda t: (t.storage_offset(), t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride())))
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 <= b1 and b0 <= a1
+
+
+def mhsa_train(q, k, v, n_query_rows=None):
+    """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train)."""
+    L.require_gpu(q, k, v)
+    _forward_only("mhsa_train", q, k, v)
+    B, N = k.shape[0], k.shape[1]
+    nq = N if n_query_rows is None else int(n_query_rows)
+    if not 1 <= nq <= N or v.shape[1] != N:
+        raise L.CvaeError(f"mhsa_train: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, n_query_rows {nq}")
+    _mhsa_views("mhsa_train", B, (nq, N, N), q, k, v)
+    out, lse = _empty((B, nq, 256), q.dtype, q), _empty((B, 8, nq), torch.float32, q)
+    check(lib.cvae_mhsa_fwd_train(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq,
+                                  L.dtype_code(q.dtype), stream()), "mhsa_fwd_train")
+    return out, lse
+
+
+def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv):
+    """The gradients of mhsa_train's operands, written into dq [B, n_query_rows, 256] and dk / dv [B, N, 256] — views with unit column stride, e.g. the
+    column panels of the packed in-projection cotangent [B, N, 768] (cvae_mhsa_bwd).  out / dout: contiguous [B, n_query_rows, 256]."""
+    L.require_gpu(q, k, v, out, lse, dout, dq, dk, dv)
+    _forward_only("mhsa_bwd", q, k, v, out, dout)
+    B, N, nq = k.shape[0], k.shape[1], out.shape[1]
+    _mhsa_views("mhsa_bwd", B, (nq, N, N, nq, nq, nq, N, N), q, k, v, out, dout, dq, dk, dv)
+    if (not out.is_contiguous() or not dout.is_contiguous() or dout.shape != out.shape or lse.shape != (B, 8, nq) or lse.dtype != torch.float32
+            or not lse.is_contiguous() or v.shape[1] != N or dq.shape[1] != nq or dk.shape[1] != N or dv.shape[1] != N or not 1 <= nq <= N):
+        raise L.CvaeError(f"mhsa_bwd: q {tuple(q.shape)}, k {tuple(k.shape)}, out {tuple(out.shape)}, dout {tuple(dout.shape)}, lse {tuple(lse.shape)}, "
+                          f"dq {tuple(dq.shape)}, dk {tuple(dk.shape)}, dv {tuple(dv.shape)}")
+    outs = (dq, dk, dv)
+    if any(_overlap(a, b) for i, a in enumerate(outs) for b in outs[i + 1:] + (q, k, v, out, dout)):
+        raise L.CvaeError("mhsa_bwd: dq, dk and dv must not overlap each other or an operand")
+    _t, wp, wb = _scratch(lib.cvae_mhsa_bwd_workspace_bytes(B, nq), q)
+    check(lib.cvae_mhsa_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1), q.stride(0),
+                            k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0), B, N, nq,
+                            L.dtype_code(q.dtype), wp, wb, stream()), "mhsa_bwd")
+    return dq, dk, dv
+
+
+def token_gemm_gelu_train(x, weight, bias):
+    """(gelu(x W^T + b), x W^T + b), both in x's dtype: token_gemm's "gelu" output, bit for bit, and the pre-activation (cvae_token_gemm_gelu_train)."""
+    L.require_gpu(x, weight, bias)
+    _forward_only("token_gemm_gelu_train", x, weight, bias)
+    _rows2d(x, "token_gemm_gelu_train")
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32:
+        raise L.CvaeError(f"token_gemm_gelu_train: x {tuple(x.shape)}, weight {tuple(weight.shape)}")
+    y, pre = _empty((M, N), x.dtype, x), _empty((M, N), x.dtype, x)
+    check(lib.cvae_token_gemm_gelu_train(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(pre), N, ptr(y), N, M, K, N,
+                                         L.dtype_code(x.dtype), stream()), "token_gemm_gelu_train")
+    return y, pre
+
+
+def _gemm_mode(what, g, mode):
+    """The arithmetic mode of a backward GEMM: fp32 mode takes fp32 cotangents only; bf16 mode takes bf16 ones or the fp32 stream gradient."""
+    if mode not in (torch.float32, torch.bfloat16) or g.dtype not in (torch.float32, mode):
+        raise L.CvaeError(f"{what}: a {g.dtype} cotangent in {mode} arithmetic")
+
+
+def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=None, out=None):
+    """dx [M, K] = (g [M, N] @ weight [N, K]) * gelu'(gate_pre) + resid (cvae_token_gemm_bwd_data).  weight: the fp32 nn.Linear tensor or a row slice of it;
+    mode: the arithmetic (torch.float32 / torch.bfloat16); g fp32 or `mode`; gate_pre [M, K] in `mode`: the saved pre-activation; resid fp32 [M, K] (any row
+    stride): added, result fp32, written to `out` (default: resid itself, in place).  out_dtype (default `mode`): the result's dtype without resid."""
+    L.require_gpu(g, weight, gate_pre, resid, out)
+    _forward_only("token_gemm_bwd_data", g, weight, gate_pre, resid)
+    _rows2d(g, "token_gemm_bwd_data")
+    _gemm_mode("token_gemm_bwd_data", g, mode)
+    M, N = g.shape
+    K = weight.shape[1] if weight.dim() == 2 else -1
+    if weight.dim() != 2 or weight.shape[0] != N or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise L.CvaeError(f"token_gemm_bwd_data: g {tuple(g.shape)}, weight {tuple(weight.shape)} {weight.dtype} (contiguous fp32 [N, K] rows expected)")
+    if gate_pre is not None and (gate_pre.dtype != mode or _rows2d(gate_pre, "token_gemm_bwd_data gate_pre", K).shape[0] != M):
+        raise L.CvaeError(f"token_gemm_bwd_data: gate_pre {tuple(gate_pre.shape)} {gate_pre.dtype}")
+    if resid is not None:
+        if resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_bwd_data resid", K).shape[0] != M or out_dtype not in (None, torch.float32):
+            raise L.CvaeError("token_gemm_bwd_data: the residual needs a fp32 [M, K] tensor and a fp32 result")
+        out = resid if out is None else out
+    elif out is None:
+        out = _empty((M, K), out_dtype or mode, g)
+    if _rows2d(out, "token_gemm_bwd_data out", K).shape[0] != M or out.dtype not in (torch.float32, mode) or (resid is not None and out.dtype != torch.float32):
+        raise L.CvaeError(f"token_gemm_bwd_data: out {tuple(out.shape)} {out.dtype}")
+    check(lib.cvae_token_gemm_bwd_data(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
+                                       ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), L.dtype_code(out.dtype), M, K, N,
+                                       L.dtype_code(mode), stream()), "token_gemm_bwd_data")
+    return out
+
+
+def token_gemm_wgrad(g, x, dW=None, db=None):
+    """(dW [N, K], db [N]) fp32 of token_gemm's nn.Linear from its input x [M, K] (fp32 or bf16: the arithmetic mode) and the cotangent g [M, N] of its output
+    (x's dtype, or the fp32 stream gradient) (cvae_token_gemm_wgrad).  dW / db: where to write, e.g. a row slice of the packed in-projection gradient."""
+    L.require_gpu(g, x, dW, db)
+    _forward_only("token_gemm_wgrad", g, x)
+    _rows2d(g, "token_gemm_wgrad g")
+    _rows2d(x, "token_gemm_wgrad x")
+    _gemm_mode("token_gemm_wgrad", g, x.dtype)
+    (M, N), K = g.shape, x.shape[1]
+    nbytes = lib.cvae_token_gemm_wgrad_workspace_bytes(M, K, N)
+    if x.shape[0] != M or not nbytes:
+        raise L.CvaeError(f"token_gemm_wgrad: g {tuple(g.shape)}, x {tuple(x.shape)}: {L.strerror(-3)}")
+    dW = _empty((N, K), torch.float32, x) if dW is None else dW
+    db = _empty((N,), torch.float32, x) if db is None else db
+    if dW.shape != (N, K) or db.shape != (N,) or dW.dtype != torch.float32 or db.dtype != torch.float32 or not dW.is_contiguous() or not db.is_contiguous():
+        raise L.CvaeError(f"token_gemm_wgrad: contiguous fp32 dW [{N}, {K}] and db [{N}] expected, got {tuple(dW.shape)} and {tuple(db.shape)}")
+    _t, wp, wb = _scratch(nbytes, x)
+    check(lib.cvae_token_gemm_wgrad(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(dW), ptr(db), M, K, N, L.dtype_code(x.dtype), wp, wb, stream()),
+          "token_gemm_wgrad")
+    return dW, db
+
+
+def layernorm256_bwd(g, x, weight, eps, dx=None, accumulate=False):
+    """(dx, dgamma, dbeta) of layernorm256 from its fp32 input x [rows, 256] (any row stride) and the cotangent g [rows, 256] of its output (fp32 or bf16)
+    (cvae_layernorm256_bwd).  dx: fp32 [rows, 256] with any row stride, written — or, with accumulate, added to (the stream gradient takes the LayerNorm
+    branch next to the skip); default: a fresh tensor."""
+    L.require_gpu(g, x, weight, dx)
+    _forward_only("layernorm256_bwd", g, x, weight)
+    _rows2d(g, "layernorm256_bwd g", 256)
+    _rows2d(x, "layernorm256_bwd x", 256)
+    rows = x.shape[0]
+    if weight.shape != (256,) or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise L.CvaeError(f"layernorm256_bwd: a contiguous fp32 [256] weight expected, got {tuple(weight.shape)} {weight.dtype}")
+    if x.dtype != torch.float32 or g.shape[0] != rows or g.dtype not in (torch.float32, torch.bfloat16) or (dx is None and accumulate):
+        raise L.CvaeError(f"layernorm256_bwd: x {tuple(x.shape)} {x.dtype}, g {tuple(g.shape)} {g.dtype}, accumulate {accumulate} into {None if dx is None else tuple(dx.shape)}")
+    dx = _empty((rows, 256), torch.float32, x) if dx is None else dx
+    if dx.dtype != torch.float32 or _rows2d(dx, "layernorm256_bwd dx", 256).shape[0] != rows:
+        raise L.CvaeError(f"layernorm256_bwd: dx {tuple(dx.shape)} {dx.dtype}")
+    dgamma, dbeta = _empty((256,), torch.float32, x), _empty((256,), torch.float32, x)
+    _t, wp, wb = _scratch(lib.cvae_layernorm256_bwd_workspace_bytes(rows), x)
+    check(lib.cvae_layernorm256_bwd(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(weight.detach()), ptr(dx), dx.stride(0), int(bool(accumulate)),
+                                    ptr(dgamma), ptr(dbeta), rows, float(eps), wp, wb, stream()), "layernorm256_bwd")
+    return dx, dgamma, dbeta
+
+
+def vit_tokens_bwd(dtokens, stem_dtype):
+    """(dpos [n + 1, 256], dcls [256], dstem [B, n, 256] in stem_dtype) from the fp32 residual-stream gradient [B, n + 1, 256] (cvae_vit_tokens_bwd)."""
+    L.require_gpu(dtokens)
+    _forward_only("vit_tokens_bwd", dtokens)
+    if dtokens.dim() != 3 or dtokens.shape[1] < 2 or dtokens.shape[2] != 256 or dtokens.dtype != torch.float32 or not dtokens.is_contiguous():
+        raise L.CvaeError(f"vit_tokens_bwd: a contiguous fp32 [B, n + 1, 256] gradient expected, got {tuple(dtokens.shape)} {dtokens.dtype}")
+    B, n = dtokens.shape[0], dtokens.shape[1] - 1
+    dpos, dcls, dstem = _empty((n + 1, 256), torch.float32, dtokens), _empty((256,), torch.float32, dtokens), _empty((B, n, 256), stem_dtype, dtokens)
+    check(lib.cvae_vit_tokens_bwd(ptr(dtokens), ptr(dpos), ptr(dcls), ptr(dstem), L.dtype_code(stem_dtype), B, n, stream()), "vit_tokens_bwd")
+    return dpos, dcls, dstem
+
+
 # ---- ViT-VAE decoder (csrc/conv_s1.hip): forward-only building blocks on raw tensors -------------------------------------------------
 CONV_S1_K3, CONV_S1_SUBPIXEL, CONV_S1_SUBPIXEL_T = 0, 1, 2      # CVAE_CONV_S1_* (SUBPIXEL_T: conv_s1_bwd_data only)
 

@@ -93,25 +93,33 @@ class CausalViTVAE(nn.Module):
     # ---- training the adapters on the frozen backbone -----------------------------------------------------------------------------
     _adapters_only = False
     _train_decoder = False
+    _train_transformer = False
 
     def head_parameters(self):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self, decoder=False):
+    def train_adapters(self, decoder=False, transformer=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
         heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
         a default call after a decoder=True one switches the decoder's gradients off again).
         decoder=True: the backbone's decoder learns too (backbone.train_decoder(): decoder_input and decoder ask for gradients, still in eval mode: BatchNorm2d on
-        its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters."""
+        its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters.
+        transformer=True: the backbone's transformer learns too (backbone.train_transformer(): pos_embedding, cls_token, transformer, to_latent; eval mode, no
+        dropout; the conv stem stays frozen).  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
+        backbone's (mu, log_var), so no gradient ever reaches them.  Returns head plus transformer parameters (plus the decoder's with decoder=True)."""
         self.backbone.requires_grad_(False)
         self.backbone.freeze_decoder()
-        self._adapters_only, self._train_decoder = True, bool(decoder)
+        self.backbone.freeze_transformer()
+        self._adapters_only, self._train_decoder, self._train_transformer = True, bool(decoder), bool(transformer)
         self.train()
-        if not decoder:
-            return self.head_parameters()
-        self.backbone.train_decoder()
-        return self.head_parameters() + list(self.backbone.decoder_input.parameters()) + list(self.backbone.decoder.parameters())
+        params = self.head_parameters()
+        if transformer:
+            params += self.backbone.train_transformer(heads=False)
+        if decoder:
+            self.backbone.train_decoder()
+            params += list(self.backbone.decoder_input.parameters()) + list(self.backbone.decoder.parameters())
+        return params
 
     def train(self, mode=True):
         """nn.Module.train; after train_adapters() the backbone stays in eval mode whatever `mode` is."""
@@ -124,15 +132,18 @@ class CausalViTVAE(nn.Module):
         """The reference 6-tuple (recon_x, m_mu, mu, logvar, m_mu, m_logvar) attached to the autograd graph of the head parameters: backbone.cls_features
         under no_grad, enc_adapter, the morph predictor and dec_adapter in training mode (ops.mlp_heads_train: batch statistics, running statistics updated),
         then backbone.decode_with_grad.  The backbone is fp32 or bf16; the heads are fp32.  Needs train_adapters() first; after train_adapters(decoder=True)
-        the backbone's decoder parameters (and only those) may ask for gradients, and backward accumulates them (eval-mode decoder)."""
-        live = [k for k, p in self.backbone.named_parameters() if p.requires_grad and not (self._train_decoder and k.startswith(("decoder_input.", "decoder.")))]
+        the backbone's decoder parameters may ask for gradients, and backward accumulates them (eval-mode decoder); after
+        train_adapters(transformer=True) cls_features_with_grad takes cls_features' place and the transformer's parameters learn through enc_adapter's cls_out
+        panel."""
+        roots = (("decoder_input", "decoder") if self._train_decoder else ()) + (self.backbone._TRANSFORMER_ROOTS if self._train_transformer else ())
+        live = [k for k, p in self.backbone.named_parameters() if p.requires_grad and k.split(".")[0] not in roots]
         if self.backbone.training or live:
             raise RuntimeError("CausalViTVAE.forward_train trains the adapter heads on a frozen eval-mode backbone: call model.train_adapters() first "
                                f"(backbone.training={self.backbone.training}, {len(live)} backbone parameters require grad)")
         B = x.shape[0]
         m, t = self._rows("m", m, self.m_dim, B), self._rows("t", t, self.t_dim, B)
         eps = torch.randn(B, self.my_z_dim, dtype=torch.float32, device=x.device) if eps is None else self._rows("eps", eps, self.my_z_dim, B)
-        cls_out = self.backbone.cls_features(x)
+        cls_out = self.backbone.cls_features_with_grad(x) if self._train_transformer else self.backbone.cls_features(x)
         mu, logvar, z = ops.mlp_heads_train([cls_out, m, t], self.enc_adapter.head_layers(), split=self.my_z_dim, clamp0=(-100.0, 100.0),
                                             clamp1=(-10.0, 10.0), eps=eps)
         m_mu, m_logvar, _z = ops.mlp_heads_train([t], self.morph_layers(), clamp1=(-10.0, 10.0))

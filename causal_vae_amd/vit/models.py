@@ -157,6 +157,176 @@ class ViTVAEEncoder(nn.Module):
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
 
+    # ---- training the transformer (eval mode, frozen stem) -------------------------------------------------------------
+    _transformer_grads = False      # train_transformer(): cls_features_with_grad / encode_with_grad accumulate the transformer's gradients
+    _TRANSFORMER_ROOTS = ("pos_embedding", "cls_token", "transformer", "to_latent", "fc_mu", "fc_var")
+
+    def _transformer_named(self, heads=True):
+        """(name, parameter) of everything train_transformer() trains, in named_parameters order; heads=False: without fc_mu / fc_var (what the one
+        autograd.Function over the transformer takes: the two output layers are ops.Linear nodes of their own)."""
+        roots = self._TRANSFORMER_ROOTS if heads else self._TRANSFORMER_ROOTS[:4]
+        return [(k, p) for k, p in self.named_parameters() if k.split(".")[0] in roots]
+
+    def freeze_transformer(self):
+        """requires_grad_(False) on everything train_transformer() switched on; cls_features_with_grad then equals cls_features and saves nothing."""
+        for _k, p in self._transformer_named():
+            p.requires_grad_(False)
+        self._transformer_grads = False
+        return self
+
+    def train_transformer(self, heads=True):
+        """The counterpart of freeze_transformer(): requires_grad_(True) on transformer.*, pos_embedding, cls_token, to_latent.*, fc_mu.* and fc_var.*
+        (heads=False: without fc_mu / fc_var, for a consumer of the cls features that never reaches them; they are frozen), and
+        cls_features_with_grad / encode_with_grad from now on accumulate their `.grad`.  Returns those parameters in named_parameters order.  The model stays in
+        EVAL mode (no dropout: the one difference from the reference's vae.train(), next to the stem) and the conv stem stays a frozen feature extractor: a stem
+        parameter that asks for a gradient is an error here, not a gradient that silently stays None."""
+        if self.training:
+            raise RuntimeError("ViTVAEEncoder.train_transformer: put the model in eval mode first (model.eval()): the transformer trains without dropout, "
+                               "on an eval-mode stem")
+        live = [f"stem.{k}" for k, p in self.stem.named_parameters() if p.requires_grad]
+        if live:
+            raise RuntimeError(f"ViTVAEEncoder.train_transformer: the stem is a frozen feature extractor, but these parameters ask for a gradient: {live} "
+                               "(model.stem.requires_grad_(False))")
+        self.freeze_transformer()
+        for _k, p in self._transformer_named(heads):
+            p.requires_grad_(True)
+        self._transformer_grads = True
+        return [p for _k, p in self._transformer_named(heads)]
+
+    def cls_features_with_grad(self, x, collect=None):
+        """cls_features(x) (the same launches up to two extra outputs, the same bits) as a differentiable function of the transformer's parameters: ONE
+        autograd.Function over tokens, blocks and to_latent whose backward accumulates `.grad` on pos_embedding, cls_token, transformer.* and to_latent.*.
+        x gets no gradient (the stem is frozen).  Needs train_transformer(); when autograd is off or no parameter asks, this is cls_features and nothing is saved.
+        collect (a dict, for tests and for the stem's later backward): the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype."""
+        named = self._transformer_named(heads=False)
+        if not (torch.is_grad_enabled() and any(p.requires_grad for _k, p in named)):
+            return self._cls_features(x)
+        if not self._transformer_grads:
+            raise CvaeError("ViTVAEEncoder.cls_features_with_grad: transformer parameters ask for a gradient but train_transformer() was not called "
+                            "(or call freeze_transformer())")
+        self._check(x)
+        return _ClsFeaturesWithGrad.apply(x, self, collect, tuple(k for k, _p in named), *[p for _k, p in named])
+
+    def encode_with_grad(self, x, collect=None):
+        """encode(x) with gradients: (mu, log_var) from cls_features_with_grad through the differentiable ops.Linear (fc_mu, fc_var)."""
+        c = self.cls_features_with_grad(x, collect)
+        return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
+
+    def _block_train(self, blk, tokens, cls_only):
+        """_block's launches (attention and the GELU GEMM in their training forms: the same values plus lse / the pre-activation) -> (the next stream
+        [B, N, 256], or the CLS rows [B, 256] with cls_only; what _block_backward reads).  The residual GEMMs write fresh tensors instead of the stream in
+        place: the block's input and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied."""
+        B, N, D = tokens.shape
+        dt = self.compute_dtype
+        X = tokens.view(B * N, D)
+        a = blk.attn
+        y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
+        if not cls_only:
+            qkv = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D)
+            att, lse = ops.mhsa_train(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
+            att2, X1 = att.view(B * N, D), torch.empty_like(X)
+            ops.token_gemm(att2, a.out_proj.weight, a.out_proj.bias, "residual", resid=X, out=X1)
+        else:
+            qkv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
+            qc = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D]).view(B, 1, D)
+            att, lse = ops.mhsa_train(qc, qkv[:, :, :D], qkv[:, :, D:], n_query_rows=1)
+            att2, X1 = att.view(B, D), torch.empty(B, D, dtype=torch.float32, device=tokens.device)
+            ops.token_gemm(att2, a.out_proj.weight, a.out_proj.bias, "residual", resid=tokens[:, 0], out=X1)
+        y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
+        hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias)
+        X2 = torch.empty_like(X1)
+        ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=X2)
+        saved = dict(X=X, y=y, qkv=qkv, q=None if not cls_only else qc, att=att, lse=lse, X1=X1, y2=y2, pre=pre, hid=hid, shape=(B, N))
+        return (X2 if cls_only else X2.view(B, N, D)), saved
+
+    def _block_backward(self, blk, name, s, G, grads):
+        """One block's backward: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in place where it can be;
+        returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names."""
+        B, N = s["shape"]
+        D, dt, a = self.embed_dim, self.compute_dtype, blk.attn
+        cls_only = s["q"] is not None
+        dpre = ops.token_gemm_bwd_data(G, blk.mlp[3].weight, dt, gate_pre=s["pre"])
+        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(G, s["hid"])
+        dy2 = ops.token_gemm_bwd_data(dpre, blk.mlp[0].weight, dt)
+        grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s["y2"])
+        _dx, grads[name + "norm2.weight"], grads[name + "norm2.bias"] = ops.layernorm256_bwd(dy2, s["X1"], blk.norm2.weight, blk.norm2.eps, dx=G, accumulate=True)
+        datt = ops.token_gemm_bwd_data(G, a.out_proj.weight, dt)
+        grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s["att"].view(-1, D))
+        qkv, y = s["qkv"], s["y"]
+        dqkv = torch.empty_like(qkv)
+        if not cls_only:
+            ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s["att"], s["lse"], datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:])
+            dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 3 * D), a.in_proj_weight, dt)
+            grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = ops.token_gemm_wgrad(dqkv.view(B * N, 3 * D), y)
+            _dx, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s["X"], blk.norm1.weight, blk.norm1.eps, dx=G, accumulate=True)
+            return G
+        dq = torch.empty_like(s["q"])
+        ops.mhsa_bwd(s["q"], qkv[:, :, :D], qkv[:, :, D:], s["att"], s["lse"], datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:])
+        dW, db = torch.empty_like(a.in_proj_weight), torch.empty_like(a.in_proj_bias)
+        ops.token_gemm_wgrad(dq.view(B, D), y.view(B, N, D)[:, 0], dW[:D], db[:D])
+        ops.token_gemm_wgrad(dqkv.view(B * N, 2 * D), y, dW[D:], db[D:])
+        grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = dW, db
+        dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 2 * D), a.in_proj_weight[D:], dt, out_dtype=torch.float32)
+        ops.token_gemm_bwd_data(dq.view(B, D), a.in_proj_weight[:D], dt, resid=dy.view(B, N, D)[:, 0])       # the one q row joins the kv rows' gradient, in place
+        Gin, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s["X"], blk.norm1.weight, blk.norm1.eps)
+        Gin.view(B, N, D)[:, 0].add_(G)                                 # the skip: only the CLS rows left this block
+        return Gin
+
+    @torch.no_grad()
+    def _train_walk(self, x):
+        """_cls_features' launches in their training forms -> (cls features [B, 256] fp32, what _train_backward reads)."""
+        stem = self._stem_cl(x)
+        tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
+        B, N, _D = tokens.shape
+        steps = []
+        for i, blk in enumerate(self.transformer):
+            tokens, s = self._block_train(blk, tokens, cls_only=self._cls_only_last_block and i == self.depth - 1)
+            steps.append(s)
+        cls = tokens if tokens.dim() == 2 else tokens[:, 0]
+        out = ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
+        return out, (steps, cls, stem.dtype, B, N)
+
+    @torch.no_grad()
+    def _train_backward(self, saved, g):
+        """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features."""
+        steps, cls, stem_dtype, B, N = saved
+        D, grads = self.embed_dim, {}
+        if steps[-1]["q"] is not None:                                  # the forward ran a CLS-only last block: the stream gradient starts as its [B, 256] rows
+            G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
+        else:
+            G = torch.zeros(B * N, D, dtype=torch.float32, device=g.device)
+            _dx, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps, dx=G.view(B, N, D)[:, 0])
+        for i in reversed(range(self.depth)):
+            G = self._block_backward(self.transformer[i], f"transformer.{i}.", steps[i], G, grads)
+        dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
+        grads["pos_embedding"], grads["cls_token"] = dpos.view(1, N, D), dcls.view(1, 1, D)
+        return grads
+
+
+class _ClsFeaturesWithGrad(torch.autograd.Function):
+    """ViTVAEEncoder.cls_features_with_grad: the transformer's parameters are inputs, so autograd accumulates their gradients, zero_grad works and a parameter
+    rewritten between forward and backward is an error.  x gets no gradient: the stem is a frozen feature extractor (its backward starts from `dstem`)."""
+
+    @staticmethod
+    def forward(ctx, x, model, collect, names, *params):
+        out, saved = model._train_walk(x)
+        ctx.model, ctx.saved, ctx.collect, ctx.names = model, saved, collect, names      # activations of this call: private to the node, freed with it
+        ctx.save_for_backward(*params)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        params = ctx.saved_tensors                                     # raises if a parameter was modified in place since the forward
+        if g is None:
+            return (None,) * (4 + len(params))
+        grads = ctx.model._train_backward(ctx.saved, g.contiguous())
+        if ctx.collect is not None:
+            ctx.collect["dstem"] = grads["dstem"]
+        return (None, None, None, None) + tuple(grads[k].view(p.shape) if need else None for k, p, need in zip(ctx.names, params, ctx.needs_input_grad[4:]))
+
+
 class _ResBlock(nn.Module):
     """Parameter holder with the reference ResBlock's child (vit_backbone.py:7-19): x + conv(x)."""
 

@@ -310,6 +310,47 @@ int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float
 int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
                   int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream);
 
+/* ---- ViT-VAE encoder, training the transformer (csrc/vit.hip) ---------------------------------------------------------------------
+ * The backward of the entries above, in both arithmetic modes, under the same contract: fp32 accumulation, no atomics, every cross-row or cross-workgroup
+ * sum in a fixed order (slabs that depend on the row count only, then an ordered finish launch), bit-reproducible; every check precedes the first launch;
+ * workspaces belong to the caller (*_workspace_bytes).  The residual-stream gradient is fp32 in both modes, cotangents of tensors the forward stores in
+ * bf16 are bf16, every parameter gradient is fp32.
+ *   cvae_mhsa_fwd_train         cvae_mhsa_fwd (the same `out`, bit for bit) that also leaves lse fp32 [B][8][n_query_rows]: log2 of the row's sum of
+ *                               2^(score log2(e) / sqrt(32)), the one statistic the backward needs
+ *   cvae_mhsa_bwd               dq [.][n_query_rows][256], dk / dv [.][n_tokens][256] (each with its own row and batch stride: the packed [B][N][768]
+ *                               cotangent of the in-projection is written in place) from q, k, v, out, lse and dout [B][n_query_rows][256] (contiguous, as out).
+ *                               Recompute-style: P = 2^(s - lse), delta = rowsum(dout * out) in fp32, dS = P (dP - delta) / sqrt(32); two launches (query
+ *                               tiles walk the keys for dq and leave delta in the workspace; key tiles walk the queries for dk, dv).  bf16: P and dS are
+ *                               rounded to bf16 for their MFMA products.
+ *   cvae_token_gemm_gelu_train  cvae_token_gemm's GELU epilogue (the same y, bit for bit) that also stores the pre-activation x W^T + bias in `dtype`
+ *   cvae_token_gemm_bwd_data    dx[M][K] = (g[M][N] W[N][K]) * gelu'(pre) + resid.  W is the fp32 nn.Linear tensor (or a row slice of it: N rows),
+ *                               transposed and rounded on its way into LDS; g in g_dtype (fp32 g in bf16 mode: the stream gradient, rounded on its way
+ *                               into LDS), dx in dx_dtype; pre (optional, `dtype`): exact-erf GELU derivative; resid (optional, fp32, needs fp32 dx; may be dx)
+ *   cvae_token_gemm_wgrad       dW[N][K] = sum_m g[m][n] x[m][k], db[n] = sum_m g[m][n] (compensated), fp32, nn.Linear layout; slabs of 512 rows (M <= 65535 x 512)
+ *   cvae_layernorm256_bwd       dx = rstd (gamma g - mean(gamma g) - xh mean(gamma g xh)) written or (accumulate != 0) added to dx (row stride dx_stride);
+ *                               statistics recomputed two-pass from the saved fp32 input x (nothing but x is saved); dgamma = sum_rows g xh, dbeta = sum_rows g
+ *                               over slabs of 32 rows, then in slab order
+ *   cvae_vit_tokens_bwd         dpos[i] = sum_b dtokens[b][i], dcls = sum_b dtokens[b][0] (b in order), dstem[b][i] = dtokens[b][1 + i] in stem_dtype */
+int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                        int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype,
+                        void* stream);
+size_t cvae_mhsa_bwd_workspace_bytes(int64_t B, int64_t n_query_rows);
+int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* dout, void* dq, void* dk, void* dv, int64_t q_stride,
+                  int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride,
+                  int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                  int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_token_gemm_gelu_train(const void* x, int64_t x_stride, const float* W, const float* bias, void* pre, int64_t pre_stride, void* y, int64_t y_stride, int64_t M,
+                               int64_t K, int64_t N, int dtype, void* stream);
+int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
+                             int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, void* stream);
+size_t cvae_token_gemm_wgrad_workspace_bytes(int64_t M, int64_t K, int64_t N);
+int cvae_token_gemm_wgrad(const void* g, int64_t g_stride, int g_dtype, const void* x, int64_t x_stride, float* dW, float* db, int64_t M, int64_t K, int64_t N,
+                          int dtype, void* workspace, size_t workspace_bytes, void* stream);
+size_t cvae_layernorm256_bwd_workspace_bytes(int64_t rows);
+int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtype, const float* x, int64_t x_stride, const float* gamma, float* dx, int64_t dx_stride,
+                          int accumulate, float* dgamma, float* dbeta, int64_t rows, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, int64_t B, int64_t n_patches, void* stream);
+
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
  * (no atomics, no split-K): bit-reproducible, and a sample's bits do not depend on the batch it travels in.  Pointers 16-byte aligned, else CVAE_E_UNSUPPORTED;

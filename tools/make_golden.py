@@ -359,6 +359,51 @@ def vitvae_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, full):
     print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
 
 
+GRAD_ROWS = 6               # rows of every weight-matrix gradient kept by vitvae_grad_case: evenly spaced, first and last included
+
+
+def grad_rows(n):
+    """the fixed row subset of an [n, ...] weight gradient that the encoder-gradient fixture stores"""
+    return sorted({round(i * (n - 1) / (GRAD_ROWS - 1)) for i in range(GRAD_ROWS)})
+
+
+def vitvae_grad_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, seed_cot):
+    """The gradients of ViTVAE.encode in eval mode at random init, from a seeded cotangent on (mu, log_var): loss = sum(mu g_mu) + sum(log_var g_lv), one
+    backward through the reference class (fp32, CPU).  Weights and stem statistics as vitvae_case (digests).  Stored: the cotangents and the stem output
+    whole, the fp32 gradients of the small tensors whole (biases, LayerNorm parameters, cls_token, pos_embedding) and rows grad_rows(n) of each weight
+    matrix's gradient.  The stem's own gradients are not stored (the product trains the transformer on a frozen stem)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_reference import randomize_stem_bn, vit_inputs
+    (vb,) = import_from(os.path.join(REF, "vessel_analysis", "00_core"), "vit_backbone")
+    torch.manual_seed(seed_model)
+    model = vb.ViTVAE(in_channels=1, latent_dim=128, img_size=(H, W), depth=depth)
+    randomize_stem_bn(model.stem, seed_bn)
+    model.eval()
+    x = vit_inputs(B, H, W, seed_data)
+    g = torch.Generator().manual_seed(seed_cot)
+    g_mu, g_lv = torch.randn(B, 128, generator=g), torch.randn(B, 128, generator=g)
+    acts = {}
+    hook = model.stem.register_forward_hook(lambda _m, _i, o: acts.__setitem__("stem", o.detach().clone()))
+    mu, log_var = model.encode(x)
+    hook.remove()
+    torch.autograd.backward([mu, log_var], [g_mu, g_lv])
+    store = {"in/seed": np.array([B, H, W, depth, seed_model, seed_bn, seed_data], dtype=np.int64), "in/seed_cot": np.array([seed_cot], dtype=np.int64)}
+    pack("sd0", {k: v for k, v in model.state_dict().items() if not k.startswith(("decoder_input.", "decoder."))}, store)
+    pack("in", dict(x=x, g_mu=g_mu, g_lv=g_lv), store)
+    pack("out", dict(mu=mu, log_var=log_var, stem=acts["stem"]), store)
+    for k, p in model.named_parameters():
+        if k.startswith(("stem.", "decoder_input.", "decoder.")):
+            continue
+        if p.dim() == 2:
+            rows = grad_rows(p.shape[0])
+            store[f"grad/{k}#rows"] = np.array(rows, dtype=np.int64)
+            store[f"grad/{k}"] = p.grad[rows].numpy().copy()
+        else:
+            store[f"grad/{k}"] = p.grad.numpy().copy()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
+
+
 def vitvae_dec_case(name, B, H, W, depth, seed_model, seed_bn, seed_dec_bn, seed_z, whole):
     """ViTVAE.decode in eval mode at random init.  The weights are the seed's draws (digests only: the product class draws the same); the stem BatchNorms
     are randomised as in vitvae_case, ALL decoder BatchNorm2d layers (the ones nested in the ResBlocks included) from a further seed
@@ -458,6 +503,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "vitvae":
         vitvae_case("vitvae_enc_256x320", 3, 256, 320, 2, 42, 4242, 1301, full=True)       # 81 tokens
         vitvae_case("vitvae_enc_768x1280", 2, 768, 1280, 6, 42, 4242, 1302, full=False)    # 961 tokens
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "vitvae_grad":
+        vitvae_grad_case("vitvae_enc_grad_64x96", 2, 64, 96, 2, 42, 4242, 1303, 1304)      # 7 tokens
         return
     if len(sys.argv) > 1 and sys.argv[1] == "vessel2d":
         vessel2d_case("vessel2d_b4")
