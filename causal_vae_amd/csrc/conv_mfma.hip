@@ -18,7 +18,9 @@
 //     (conv_up_full_kernel) stages the halo of ALL input channels once and walks the output parities inside the workgroup; it serves the large grids of the
 //     decode sweep (32-channel tiles only).
 //   * bf16: v_mfma_f32_32x32x16_bf16 (fp32 accumulate);  fp32: v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chain);  fp8: v_mfma_scale_f32_32x32x64_f8f6f4.
-//   * epilogue fuses bias + ReLU/Sigmoid (forward use) or the ReLU mask of the saved activation (backward use).
+//   * epilogue fuses bias + ReLU/Sigmoid (forward use) or the ReLU mask of the saved activation (backward use).  The three kernels with that mask
+//     (conv_data_kernel, conv_splitk_finish_kernel, conv_up_full_kernel) live in .inc files included twice: the second, "gated" instance multiplies by a
+//     LeakyReLU slope where the first one zeroes (cvae_conv_down_bwd_data: the ViT-VAE stem's input gradients).
 // wgrad — M = Cs, N = Cl, K = positions.  Both operands are [position][channel] in memory, i.e. K-strided: bf16 uses
 //   the gfx950 transposing LDS read (ds_read_b64_tr_b16) to build K-contiguous fragments; fp32's 32x32x2 MFMA takes
 //   one element per lane and needs no transpose.  Every workgroup leaves ONE fp32 slab [kh][kw][64 cs][32 cl] of partial sums with
@@ -212,532 +214,30 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
 // TS ("K split", BD only): TS = 2 wave groups of WM x WN waves each own every second k-step (odd / even taps for KH = 1, the two 16-channel halves
 // of a stage for KH = 2) of the WHOLE tile and add their accumulators through LDS once, before the epilogue.  With WM = 1 no two waves fetch the
 // same weight fragment, and a fetched fragment feeds MI = 4 MFMAs: half the bytes per MFMA on the vector-memory path the BD tap loop is bound by.
-template <typename T, int ND, bool UP, int WM, int WN, int MI, int NI, int EPI, int KH = 1, typename TO = T, bool BD = false, int TS = 1, int XB = 1>
-__global__ __launch_bounds__(WM * WN * TS * 64, BD ? 2 : 1) void conv_data_kernel(const T* __restrict__ in, const T* __restrict__ wp, const float* __restrict__ bias,
-                                                                  const TO* __restrict__ mask, TO* __restrict__ out, ConvGeom g, int act,
-                                                                  float* __restrict__ ws, int ksplit, float acc_scale, float out_scale, F8Side f8) {
-    constexpr bool F8 = IsF8<T>::value;
-    static_assert(!F8 || sizeof(TO) <= 2, "fp8 products leave as bf16 or as fp8 codes");
-    static_assert(TS == 1 || (TS == 2 && BD && MI % 2 == 0), "the K split needs the per-wave weight fetch and an even number of M sub-tiles");
-    constexpr int NT = WM * WN * TS * 64;
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    using TL = Tile<ND, BM>;
-    constexpr int TD = TL::TD, TH = TL::TH, TW = TL::TW;
-    constexpr int STR = UP ? 1 : 2;
-    // UP: an output parity class reads q - 1 + pr + {0, 1} per dimension, so its halo box is (T + 1)^nd with the origin shifted by the
-    // parity — 405 instead of the parity-independent 600 positions for 4 x 8 x 8 tiles (the halo loads are the largest single cost of
-    // the `up` launches: 29 of 78 us on enc2's backward-data by ablation).
-    constexpr int ID = (ND == 3) ? (UP ? TD + 1 : 2 * TD + 2) : 1;
-    // XB == 2: a layer at most TW / 2 wide puts two samples side by side in x (the 4^3 decoder input would leave half of every MFMA row tile
-    // empty): sample s owns tile columns [s TW / 2, (s + 1) TW / 2) and its own HWS halo columns, so a row of the halo is two sample rows with
-    // the zero padding of each in place; a tile column w reads slot w + s (+ tap), which is one more term in the per-lane base.
-    static_assert(XB == 1 || XB == 2, "one sample per tile, or two side by side in x");
-    constexpr int IH = UP ? TH + 1 : 2 * TH + 2, IW = (UP ? TW + 1 : 2 * TW + 2) + (XB - 1) * (UP ? 1 : 2), HWS = IW / XB;
-    constexpr int NPOS = ID * IH * IW;
-    constexpr int FB = 8 * sizeof(T);                    // bytes of one fragment piece (8 channels)
-    constexpr int NG = UP ? (ND == 3 ? 2 : 1) : (ND == 3 ? 16 : 4);   // tap groups of 4
-    using ST = SubTile<ND>;
-    constexpr int RS = HaloPitch<ND, UP>::RS, NROWS = ID * IH;
-    constexpr int PLANE = (UP ? 1 : 2) * NROWS * RS;     // slots of one k-half plane (down: even-x rows then odd-x rows)
-    static_assert(RS >= (UP ? IW : IW / 2), "halo pitch too small");
-    constexpr int HALO_BYTES = 2 * KH * PLANE * FB;           // planes: (k-step, k-half)
-    // slot of halo position (z, y, x) inside a k-half plane
-    auto hslot = [](int z, int y, int x) -> int {
-        return UP ? (z * IH + y) * RS + x : ((x & 1) * NROWS + z * IH + y) * RS + (x >> 1);
-    };
-    constexpr int BT_BYTES = BD ? 0 : 4 * KH * 2 * BN * FB;       // one B buffer: [4 taps][KH k-steps][2 halves][BN]
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* halo = smem;
-    char* bt = smem + HALO_BYTES;
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    STAMP_BEGIN();
-    const int ts = wave / (WM * WN), wv = wave % (WM * WN);      // K-split group (0 when TS == 1)
-    const int wm = wv / WN, wn = wv % WN;
-    const int r = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z * XB;
-    const int Cin = (UP ? g.Cs : g.Cl) / (F8 ? 2 : 1), Cout = UP ? g.Cl : g.Cs;      // fp8: input channels counted in 2-channel elements
-    const int nblocks = Cout / BN;
-    constexpr int NPAR = UP ? (ND == 3 ? 8 : 4) : 1;
-    // blockIdx.y = (ks * NPAR + par) * nblocks + nb; par: output parity class (UP only); ks: split-K slice of the channel chunks
-    const int nb = blockIdx.y % nblocks, par = (blockIdx.y / nblocks) % NPAR, ks = blockIdx.y / (nblocks * NPAR);
-    const int prd = (UP && ND == 3) ? ((par >> 2) & 1) : 0, prh = UP ? ((par >> 1) & 1) : 0, prw = UP ? (par & 1) : 0;
-    const int n0 = nb * BN;
-    int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int tw_i = tile % g.tiles_w; tile /= g.tiles_w;
-    const int th_i = tile % g.tiles_h; tile /= g.tiles_h;
-    const int td_i = tile;
-    const int o0d = td_i * TD, o0h = th_i * TH, o0w = tw_i * TW;       // tile origin in the M grid
-    // input dims
-    const int in_d = UP ? g.sd : g.ld, in_h = UP ? g.sh : g.lh, in_w = UP ? g.sw : g.lw;
-    const int g0d = (ND == 3) ? (UP ? o0d - 1 + prd : 2 * o0d - 1) : 0;
-    const int g0h = UP ? o0h - 1 + prh : 2 * o0h - 1, g0w = UP ? o0w - 1 + prw : 2 * o0w - 1;
-    const int nchunks = Cin / (16 * KH);                    // stages; the packed weights are indexed in 16-channel chunks (nch16)
-    const int nch16 = Cin / 16;
-
-    // per-lane halo base position of each M sub-tile row
-    // sub-tile ms of the workgroup tile covers d = ms / HB, h in [(ms % HB) * SH, +SH), all of w (SW == TW)
-    static_assert(ST::SW == TW && TH % ST::SH == 0, "sub-tile must tile the workgroup tile");
-    constexpr int HB = TH / ST::SH;
-    int pbase[MI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-        const int ms = wm * MI + mi;
-        const int w = ST::w_of(r), hh = (ms % HB) * ST::SH + ST::h_of(r), d = ms / HB;
-        pbase[mi] = (UP ? (d * IH + hh) * RS + w : ((2 * d) * IH + 2 * hh) * RS + w) + ((XB == 2 && w >= TW / 2) ? 1 : 0);
-    }
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
-
-    auto tap_halo_off = [&](int grp, int j) -> int {
-        if (!UP) {
-            const int kd = (ND == 3) ? (grp >> 2) : 0, kh = (ND == 3) ? (grp & 3) : grp;
-            return ((j & 1) * NROWS + kd * IH + kh) * RS + (j >> 1);      // kw = j: x-parity plane j & 1, slot shift j >> 1
-        } else {
-            const int a = (ND == 3) ? grp : 0, bb = j >> 1, c = j & 1;
-            return (a * IH + bb) * RS + c;                                 // the halo origin already carries the parity
-        }
-    };
-    auto tap_weight_idx = [&](int grp, int j) -> int {
-        if (!UP) return grp * 4 + j;
-        const int a = (ND == 3) ? grp : 0, bb = j >> 1, c = j & 1;
-        const int kd = (ND == 3) ? (3 - prd - 2 * a) : 0, kh = 3 - prh - 2 * bb, kw = 3 - prw - 2 * c;
-        return (kd * 4 + kh) * 4 + kw;
-    };
-    // ---- halo staging plan: the (position, half) pieces this thread moves are the same for every channel chunk ----
-    constexpr int PPP = 2 * KH;                            // 8-channel pieces per position per stage
-    constexpr int HN = (NPOS * PPP + NT - 1) / NT;
-    int hoff[HN];                                          // element offset of the piece at chunk 0, or -1 (zero fill)
-    int hdst[HN];                                          // its LDS byte offset, or -1 (past the halo box)
-    {
-        // piece t + i NT = (position t / PPP + i PSTEP, half t % PPP): the position's (x, y, z) is stepped, not divided (the divisions were
-        // ~3 k cycles at the head of every workgroup, 10-15 % of the lifetime of the small layers' workgroups)
-        static_assert(NT % PPP == 0, "a position's pieces stay in one pass");
-        constexpr int PSTEP = NT / PPP, DX = PSTEP % IW, DY = (PSTEP / IW) % IH, DZ = PSTEP / (IW * IH);
-        const int half = t % PPP, pos0 = t / PPP;
-        int x = pos0 % IW, y = (pos0 / IW) % IH, z = pos0 / (IW * IH);
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int sx = (XB == 2 && x >= HWS) ? 1 : 0;   // sample of this halo column (its columns restart at the sample's own left padding)
-            const int gz = g0d + z, gy = g0h + y, gx = g0w + x - sx * HWS;
-            const bool inbox = z < ID;
-            const bool ok = inbox & (gz >= 0) & (gz < in_d) & (gy >= 0) & (gy < in_h) & (gx >= 0) & (gx < in_w) & (b + sx < g.B);
-            hoff[i] = ok ? ((((sx * in_d + gz) * in_h + gy) * in_w + gx) * Cin + 8 * half) : -1;
-            hdst[i] = inbox ? (half * PLANE + hslot(z, y, x)) * FB : -1;
-            x += DX; if (x >= IW) { x -= IW; y += 1; }
-            y += DY; if (y >= IH) { y -= IH; z += 1; }
-            if (y >= IH) { y -= IH; z += 1; }
-            z += DZ;
-        }
-    }
-    const T* in_b = in + (size_t)b * in_d * in_h * in_w * Cin;
-    constexpr int BP = (4 * KH * 2 * BN) / NT;             // weight pieces per thread per tap group
-    static_assert((4 * KH * 2 * BN) % NT == 0, "weight panel must divide evenly over the workgroup");
-    auto load_b = [&](Piece<T> (&pb)[BP], int chunk, int grp) {
-#pragma unroll
-        for (int i = 0; i < BP; ++i) {
-            const int it = t + i * NT, half = it & 1, n = (it >> 1) % BN, kk = it / (2 * BN) % KH, j = it / (2 * BN * KH);
-            const int wt = tap_weight_idx(grp, j);
-            piece_load<T>(pb[i], wp + (((size_t)wt * nch16 + chunk * KH + kk) * Cout + n0 + n) * 16 + 8 * half, true);
-        }
-    };
-    auto store_b = [&](const Piece<T> (&pb)[BP], int buf) {
-#pragma unroll
-        for (int i = 0; i < BP; ++i) {
-            const int it = t + i * NT, half = it & 1, n = (it >> 1) % BN, kk = it / (2 * BN) % KH, j = it / (2 * BN * KH);
-            piece_store<T>(pb[i], bt + buf * BT_BYTES + (((j * KH + kk) * 2 + half) * BN + n) * FB);
-        }
-    };
-
-    // ---- BD: k-steps of a chunk in the order the LDS form walks them (tap group, tap, k-step), cut into NGRP groups of GS steps; group g + 1
-    // (or the next chunk's group 0) is in flight while group g feeds the MFMAs ----
-    // With TS = 2 a wave walks its OWN steps u = 0 .. STEPS - 1 <-> stage step 2 u + ts.  The ts part never enters the loops: for KH = 1 it is the
-    // tap's low bit (down: the odd-x halo plane and the next weight tap; up: one slot to the right and weight tap kw - 2), for KH = 2 the second
-    // 16-channel half of the stage — a constant offset of this wave's LDS and weight base addresses.
-    constexpr int STEPS = NG * 4 * KH / TS, GS = STEPS >= 64 ? BD_GS : (STEPS >= 16 ? (MI >= 4 ? 4 : 8) : STEPS / 2), NGRP = STEPS / GS;      // MI = 4: a step is 4 MFMAs, 4 steps are as long as 8
-    static_assert(!BD || (NGRP % 2 == 0 && GS * NGRP == STEPS && (GS * TS) % KH == 0), "BD walks the groups in pairs");
-    static_assert(TS == 1 || KH <= 2, "K split: one or two k-steps per stage");
-    const long long w_tap = (long long)nch16 * Cout * 16;     // elements between two taps of the packed panels
-    const long long w_ts = (TS == 1) ? 0 : (KH == 2 ? (long long)ts * Cout * 16 : (UP ? -2 * ts * w_tap : ts * w_tap));
-    const int a_ts = (TS == 1) ? 0 : (KH == 2 ? ts * 2 * PLANE : (UP ? ts : ts * NROWS * RS));
-    const T* wl = wp + ((size_t)(n0 + wn * NI * 32 + r)) * 16 + 8 * h + w_ts;
-    const char* halo_a = halo + (size_t)a_ts * FB;
-    constexpr int PW = StepFrag<T>::PW;                       // k-steps per MFMA (fp8: 2)
-    using SF = typename StepFrag<T>::type;
-    constexpr int GSX = GS / PW;                              // MFMAs (per accumulator) of a weight group
-    static_assert(GS % PW == 0, "a weight group holds whole MFMA steps");
-    SF qa[BD ? GSX : 1][NI], qb[BD ? GSX : 1][NI];
-    auto load_q = [&](SF (&q)[BD ? GSX : 1][NI], int chunk, int gidx) {
-#pragma unroll
-        for (int ix = 0; ix < GSX; ++ix) {
-            const T* wsrc[2];
-#pragma unroll
-            for (int u = 0; u < PW; ++u) {
-                const int i = ix * PW + u;
-                const int kk = (i * TS) % KH, tj = gidx * (GS * TS / KH) + (i * TS) / KH;
-                const int wt = tap_weight_idx(tj >> 2, tj & 3);
-                wsrc[u] = wl + (size_t)(wt * nch16 + chunk * KH + kk) * Cout * 16;
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) load_step(q[ix][ni], (const char*)(wsrc[0] + (size_t)ni * 32 * 16), (const char*)(wsrc[PW - 1] + (size_t)ni * 32 * 16));
-        }
-    };
-    STAMP(1);
-    const int chunk_per = nchunks / ksplit;                 // host guarantees ksplit divides nchunks
-    // what the epilogue needs from memory — this lane's bias values and ReLU-mask pieces — is requested now, not in the epilogue, where each was
-    // an exposed global round trip at the end of every workgroup
-    constexpr int MO = MI / TS;                               // M sub-tiles this wave finishes (TS = 2: the other half goes to its partner wave)
-    const int mi0 = ts * MO;
-    float bpre[NI][2][8];
-    unsigned mbw[MO][NI];                                    // ReLU mask of this lane's channels, as bits of the position's 32-channel block dword
-    const bool masked = !F8 && (mask || f8.mask_bits);
-    const int out_d = UP ? g.ld : g.sd, out_h = UP ? g.lh : g.sh, out_w = UP ? g.lw : g.sw;
-    if (ksplit == 1) {
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) bpre[ni][j][q] = bias ? bias[c + q] : 0.f;
-            }
-        if (masked) {                                        // fp8 products are forward products: no mask
-#pragma unroll
-            for (int mo = 0; mo < MO; ++mo) {
-                const int mi = mi0 + mo, ms = wm * MI + mi;
-                const int wt = ST::w_of(r), sx = (XB == 2 && wt >= TW / 2) ? 1 : 0, w = wt - sx * (TW / 2);
-                const int hh = (ms % HB) * ST::SH + ST::h_of(r), d = ms / HB;
-                int od, oh, ow;
-                if (UP) { od = (ND == 3) ? 2 * (o0d + d) + prd : 0; oh = 2 * (o0h + hh) + prh; ow = 2 * (o0w + w) + prw; }
-                else { od = o0d + d; oh = o0h + hh; ow = o0w + w; }
-                const bool ok = od < out_d && oh < out_h && ow < out_w && b + sx < g.B;
-                const size_t pidx = ok ? ((((size_t)(b + sx) * out_d + od) * out_h + oh) * out_w + ow) * Cout : 0;
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) {
-                    if (f8.mask_bits) {                      // one dword per (position, 32-channel block) instead of two 16-byte pieces of the saved activation
-                        mbw[mo][ni] = f8.mask_bits[(pidx + n0 + (wn * NI + ni) * 32) >> 5];
-                    } else {                                 // the activation itself as the mask (callers without the bit form): turned into bits here
-                        unsigned wbits = 0;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            Piece<TO> mp;
-                            piece_load_raw<TO>(mp, mask + pidx + n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h);
-                            const TO* mv = (const TO*)&mp;
-#pragma unroll
-                            for (int q = 0; q < 8; ++q) wbits |= (to_f32(mv[q]) > 0.f ? 1u : 0u) << (16 * j + 8 * h + q);
-                        }
-                        mbw[mo][ni] = wbits;
-                    }
-                }
-            }
-        }
-    }
-    // UP with 32-channel stages (long K loops on small grids): the NEXT stage's halo is requested right after this stage's LDS image is
-    // complete and lands under the tap loop (-5 %).  Elsewhere the prefetch loses: DOWN stages 14 pieces per thread (registers), and the
-    // Cin = 64 `up` launches fill the chip, where the co-resident workgroups already hide the stage (+4 % measured).
-    constexpr bool HPRE = UP && KH == 2;
-    // Groups gp (weights in qa) and gp + 1 (qb) as ONE run of 2 GS k-steps; the group after them goes back into qa once qa is spent.  The activation
-    // fragments are software-pipelined by hand: the ds_reads of step i + APD are issued in front of the MFMAs of step i (APD + 1 register slots), so an
-    // MFMA never waits for a read issued right before it — left to itself the compiler emits read / s_waitcnt / MFMA per step and the loop runs at
-    // LDS latency (~35 % of the MFMA rate by the stamp probes, one wave per SIMD).
-    auto bd_pair = [&](int chunk, int gp) {
-        // in MFMA steps (fp8: one step = two k-steps).  MI = 4: 4 reads per k-step, 2 k-steps ahead is as many in flight
-        constexpr int NS = 2 * GSX, APW = (MI >= 4) ? 2 / PW : (APIPE + PW - 1) / PW, APD = APW < NS ? APW : NS - 1;
-        load_q(qb, chunk, gp + 1);
-        SF ar[APD + 1][MI];
-        auto lda = [&](int slot, int ix) {
-            int off[2];
-#pragma unroll
-            for (int u = 0; u < PW; ++u) {
-                const int i = ix * PW + u;
-                const int gidx = gp + i / GS, ii = i % GS;
-                const int kk = (ii * TS) % KH, tj = gidx * (GS * TS / KH) + (ii * TS) / KH;
-                off[u] = (kk * 2 + h) * PLANE + tap_halo_off(tj >> 2, tj & 3);
-            }
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) load_step(ar[slot][mi], halo_a + (size_t)(off[0] + pbase[mi]) * FB, halo_a + (size_t)(off[PW - 1] + pbase[mi]) * FB);
-        };
-#pragma unroll
-        for (int d = 0; d < APD; ++d) lda(d, d);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            if (i + APD < NS) lda((i + APD) % (APD + 1), i + APD);
-            if (i == GSX) {
-                const bool wrap = gp + 2 >= NGRP;
-                if (!wrap || chunk + 1 < (ks + 1) * chunk_per) load_q(qa, wrap ? chunk + 1 : chunk, wrap ? 0 : gp + 2);
-            }
-            __builtin_amdgcn_sched_barrier(0);             // keep the reads where they are written: the scheduler would sink them back to their uses
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma(acc[mi][ni], (i < GSX ? qa[i % GSX] : qb[i % GSX])[ni], ar[i % (APD + 1)][mi]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    auto bd_chunk = [&](int chunk) {
-        if constexpr (NGRP > 2) {                           // 3D down: 64 taps; rolled, or the unrolled LDS reads spill
-#pragma unroll 1
-            for (int gp = 0; gp < NGRP; gp += 2) bd_pair(chunk, gp);
-        } else {
-            bd_pair(chunk, 0);
-        }
-    };
-    if constexpr (BD) load_q(qa, ks * chunk_per, 0);
-    Piece<T> hp[HN];
-    if (HPRE) {
-#pragma unroll
-        for (int i = 0; i < HN; ++i) piece_load<T>(hp[i], in_b + (hoff[i] < 0 ? 0 : hoff[i]) + ks * chunk_per * (16 * KH), hoff[i] >= 0);
-    }
-    for (int chunk = ks * chunk_per; chunk < (ks + 1) * chunk_per; ++chunk) {
-        {
-            Piece<T> pb0[BP];
-            if (!HPRE) {
-#pragma unroll
-                for (int i = 0; i < HN; ++i) piece_load<T>(hp[i], in_b + (hoff[i] < 0 ? 0 : hoff[i]) + chunk * (16 * KH), hoff[i] >= 0);
-            }
-            if constexpr (!BD) load_b(pb0, chunk, 0);
-            __syncthreads();                               // previous chunk's readers are done with halo + B buffers
-            if (chunk - ks * chunk_per < 8) STAMP(2 + 3 * (chunk - ks * chunk_per));
-#pragma unroll
-            for (int i = 0; i < HN; ++i)
-                if (hdst[i] >= 0) piece_store<T>(hp[i], halo + hdst[i]);
-            if constexpr (!BD) store_b(pb0, 0);
-        }
-        __syncthreads();
-        if (chunk - ks * chunk_per < 8) STAMP(3 + 3 * (chunk - ks * chunk_per));
-        if (HPRE && chunk + 1 < (ks + 1) * chunk_per) {
-#pragma unroll
-            for (int i = 0; i < HN; ++i) piece_load<T>(hp[i], in_b + (hoff[i] < 0 ? 0 : hoff[i]) + (chunk + 1) * (16 * KH), hoff[i] >= 0);
-        }
-        if constexpr (BD) {
-            bd_chunk(chunk);
-        } else {
-            // Weight panels ride a 2-deep ring: the panel of group g+2 is loaded into registers at the start of group g and
-            // stored to LDS at the end of group g+1, so every panel load has two groups of MFMA work to land (one group is
-            // shorter than the L2 latency).  The loop is unrolled by two so the register sets pbA / pbB stay static.
-            auto taps = [&](int grp, const char* btb) {
-    #pragma unroll
-                for (int sp = 0; sp < 4 * KH; sp += PW) {   // k-steps (tap j, k-step kk); fp8 feeds one K = 64 instruction per pair
-                    SF a[MI], bf[NI];
-                    int aoff[2], boff[2];
-    #pragma unroll
-                    for (int u = 0; u < PW; ++u) {
-                        const int j = (sp + u) / KH, kk = (sp + u) % KH;
-                        aoff[u] = (kk * 2 + h) * PLANE + tap_halo_off(grp, j);
-                        boff[u] = ((j * KH + kk) * 2 + h) * BN;
-                    }
-    #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi) load_step(a[mi], halo + (size_t)(aoff[0] + pbase[mi]) * FB, halo + (size_t)(aoff[PW - 1] + pbase[mi]) * FB);
-    #pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) load_step(bf[ni], btb + (boff[0] + (wn * NI + ni) * 32 + r) * FB, btb + (boff[PW - 1] + (wn * NI + ni) * 32 + r) * FB);
-    #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-    #pragma unroll
-                        for (int ni = 0; ni < NI; ++ni) mma(acc[mi][ni], bf[ni], a[mi]);     // D = W^T x X^T: rows = channels (see epilogue)
-                }
-            };
-            Piece<T> pbA[BP], pbB[BP];
-            if (NG > 1) load_b(pbA, chunk, 1);
-    #pragma unroll 1
-            for (int grp = 0; grp < NG; grp += 2) {
-                if (grp + 2 < NG) load_b(pbB, chunk, grp + 2);
-                taps(grp, bt);
-                if (grp + 1 < NG) store_b(pbA, 1);
-                __syncthreads();
-                if (grp + 1 < NG) {
-                    if (grp + 3 < NG) load_b(pbA, chunk, grp + 3);
-                    taps(grp + 1, bt + BT_BYTES);
-                    if (grp + 2 < NG) store_b(pbB, 0);
-                    __syncthreads();
-                }
-            }
-        }
-        if (chunk - ks * chunk_per < 8) STAMP(4 + 3 * (chunk - ks * chunk_per));
-    }
-    STAMP(26);
-
-    // ---- epilogue.  The MFMAs ran with the WEIGHT fragment as the A operand (D rows are output channels, D columns positions): REGROUP_D32, common.h.
-    // The exchange and the epilogue index the accumulators with ts: written once as a generic lambda and called with the wave's ts as a compile-time
-    // constant (a run-time index would put the accumulator array in scratch memory)
-    float amx = 0.f;                                          // fp8 side channel: largest |result| this lane stored
-    const float accs = (F8 && f8.dscale) ? f8.dscale[0] : acc_scale, o8s = (F8 && f8.dscale) ? f8.dscale[1] : out_scale;
-    auto finish = [&](auto TSV) {
-        constexpr int tsc = decltype(TSV)::value, mi0c = tsc * MO;
-        if constexpr (TS == 2) {
-            // each wave hands the accumulators of the partner's M sub-tiles over through LDS (the halo is spent) and adds what the partner hands it
-            __syncthreads();
-            float4* xb = (float4*)smem;
-            const int pw = wave ^ (WM * WN);
-#pragma unroll
-            for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                    for (int e4 = 0; e4 < 4; ++e4) {
-                        const f32x16& a = acc[(1 - tsc) * MO + mo][ni];
-                        xb[(((size_t)wave * MO + mo) * NI + ni) * 4 * 64 + e4 * 64 + lane] = make_float4(a[4 * e4], a[4 * e4 + 1], a[4 * e4 + 2], a[4 * e4 + 3]);
-                    }
-            __syncthreads();
-#pragma unroll
-            for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                    for (int e4 = 0; e4 < 4; ++e4) {
-                        const float4 v = xb[(((size_t)pw * MO + mo) * NI + ni) * 4 * 64 + e4 * 64 + lane];
-                        f32x16& a = acc[mi0c + mo][ni];
-                        a[4 * e4] += v.x; a[4 * e4 + 1] += v.y; a[4 * e4 + 2] += v.z; a[4 * e4 + 3] += v.w;
-                    }
-        }
-#pragma unroll
-    for (int mo = 0; mo < MO; ++mo) {
-        const int mi = mi0c + mo;
-        const int ms = wm * MI + mi;                                            // same lane -> position map as pbase
-        const int wt = ST::w_of(r), sx = (XB == 2 && wt >= TW / 2) ? 1 : 0, w = wt - sx * (TW / 2);
-        const int hh = (ms % HB) * ST::SH + ST::h_of(r), d = ms / HB;
-        int od, oh, ow;
-        if (UP) { od = (ND == 3) ? 2 * (o0d + d) + prd : 0; oh = 2 * (o0h + hh) + prh; ow = 2 * (o0w + w) + prw; }
-        else { od = o0d + d; oh = o0h + hh; ow = o0w + w; }
-        const bool ok = od < out_d && oh < out_h && ow < out_w && b + sx < g.B;
-        const size_t pidx = ((((size_t)(b + sx) * out_d + od) * out_h + oh) * out_w + ow) * Cout;
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-            float v[2][8];
-            REGROUP_D32(acc[mi][ni], v)
-            if (ksplit > 1) {
-                // split-K: this workgroup saw only its slice of the input channels; leave the raw fp32 partial sums in slab ks of
-                // the workspace ([ks][B][positions][Cout]); conv_splitk_finish_kernel adds the slabs, bias, activation and mask.
-                if (ok) {
-                    float* wrow = ws + (size_t)ks * g.B * out_d * out_h * out_w * Cout + pidx;
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
-                        *(float4*)(wrow + c) = make_float4(v[j][0], v[j][1], v[j][2], v[j][3]);
-                        *(float4*)(wrow + c + 4) = make_float4(v[j][4], v[j][5], v[j][6], v[j][7]);
-                    }
-                }
-                continue;
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    float x = (F8 ? v[j][q] * accs : v[j][q]) + bpre[ni][j][q];
-                    if (EPI == 1) x = relu_f32(x);
-                    else if (EPI == 2) x = apply_act(x, act);
-                    v[j][q] = x;
-                }
-                if (!ok) continue;
-                if (masked) {
-                    const unsigned mb = mbw[mo][ni] >> (16 * j + 8 * h);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        if (!((mb >> q) & 1u)) v[j][q] = 0.f;
-                }
-                if constexpr (F8) {
-                    if (f8.amax) {
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) amx = fmaxf(amx, fabsf(v[j][q]));
-                    }
-                }
-                if constexpr (sizeof(TO) == 2 && sizeof(T) == 2) {           // bf16: one v_cvt_pk_bf16_f32 per pair
-                    *(uint4*)(out + pidx + c) = make_uint4(pack2_bf16(v[j][0], v[j][1]), pack2_bf16(v[j][2], v[j][3]), pack2_bf16(v[j][4], v[j][5]), pack2_bf16(v[j][6], v[j][7]));
-                } else if constexpr (F8) {                                   // fp8 codes only (the inference chain between two fp8 layers): below, 16 bytes per lane
-                } else {
-                    Piece<TO> op;
-                    TO* ov = (TO*)&op;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) ov[q] = from_f32<TO>(v[j][q]);
-                    piece_store<TO>(op, (char*)(out + pidx + c));
-                }
-            }
-            if (f8.bits_out) {                               // uniform: every lane takes part in the lane swap; lanes h = 0 store the block's dword
-                const unsigned dw = mask_bytes_to_dword(mask_byte_of(v[0]), mask_byte_of(v[1]));
-                if (ok && h == 0) f8.bits_out[(pidx + n0 + (wn * NI + ni) * 32) >> 5] = dw;
-            }
-            if constexpr (F8) {
-                // the fp8 copy of this 32-channel block: 16 bytes per lane (all lanes take part in the lane swap; `ok` only guards the store)
-                fp8* o8 = sizeof(TO) == 1 ? (fp8*)out : f8.out8;
-                if (o8) {
-                    const uint4 q16 = fp8_pair_to_16(pack8_fp8(v[0], o8s), pack8_fp8(v[1], o8s));
-                    if (ok) *(uint4*)(o8 + pidx + n0 + (wn * NI + ni) * 32 + 16 * h) = q16;
-                }
-            }
-        }
-    }
-    };
-    if constexpr (TS == 2) {
-        if (ts == 0) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 1>{});
-    } else {
-        finish(std::integral_constant<int, 0>{});
-    }
-    if constexpr (F8) {
-        if (f8.amax && ksplit == 1) {                          // uniform over the workgroup
-            __syncthreads();                                   // the LDS image (halo / accumulator exchange) is spent
-            amax_publish_wg(f8.amax, amx, blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), (float*)smem);
-        }
-    }
-    STAMP_END();
-}
+// The three kernels below live in .inc files, each included twice: as it was (CONV_GATED 0) and in its gated form (CONV_GATED 1), see conv_data_kernel.inc.
+#define CONV_GATE_PARAM_0
+#define CONV_GATE_PARAM_1 , float gate_slope
+#define CONV_GATE_OFF_0(x) 0.f
+#define CONV_GATE_OFF_1(x) ((x) * gate_slope)
+#define CONV_CAT_(a, b) a##b
+#define CONV_CAT(a, b) CONV_CAT_(a, b)
+#define CONV_GATE_PARAM CONV_CAT(CONV_GATE_PARAM_, CONV_GATED)
+#define CONV_GATE_OFF(x) CONV_CAT(CONV_GATE_OFF_, CONV_GATED)(x)
+#define CONV_GATED 0
+#include "conv_data_kernel.inc"
+#undef CONV_GATED
+#define CONV_GATED 1
+#include "conv_data_kernel.inc"
+#undef CONV_GATED
 
 // out[p][c] = act(acc_scale * sum_ks ws[ks][p][c] + bias[c]) (* mask > 0): 8 channels per thread, 16-byte bf16 stores.  acc_scale is 1 except behind an
 // fp8 product (x * 1.0f is exact: the other dtypes' bits do not change), whose side channel (second fp8 output, amax) is served here too.
-template <typename T, int EPI>
-__global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const float* __restrict__ ws, const float* __restrict__ bias, const T* __restrict__ mask,
-                                                                  T* __restrict__ out, int64_t total, int Cout, int ksplit, int act, float acc_scale, float out_scale, F8Side f8) {
-    const int64_t i8 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
-    float amx = 0.f;
-    if (i8 < total) {
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = 0.f;
-        constexpr int U = 8;                                 // slab loads in flight (clamped index, predicated add: same order of the sum)
-        for (int k0 = 0; k0 < ksplit; k0 += U) {
-            float4 a[U], b[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float* p = ws + (size_t)min(k0 + u, ksplit - 1) * total + i8;
-                a[u] = *(const float4*)p; b[u] = *(const float4*)(p + 4);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (k0 + u < ksplit) { v[0] += a[u].x; v[1] += a[u].y; v[2] += a[u].z; v[3] += a[u].w; v[4] += b[u].x; v[5] += b[u].y; v[6] += b[u].z; v[7] += b[u].w; }
-        }
-        const float accs = f8.dscale ? f8.dscale[0] : acc_scale;
-        const int c = (int)(i8 % Cout);
-        Piece<T> mp, op;
-        unsigned mb = 0xffu;
-        if (f8.mask_bits) mb = ((const unsigned char*)f8.mask_bits)[i8 >> 3];
-        else if (mask) {
-            piece_load_raw<T>(mp, mask + i8);
-            const T* mv = (const T*)&mp;
-            mb = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) mb |= (to_f32(mv[q]) > 0.f ? 1u : 0u) << q;
-        }
-        T* ov = (T*)&op;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            float x = v[q] * accs + (bias ? bias[c + q] : 0.f);
-            x = apply_act_t<EPI>(x, act);
-            if (!((mb >> q) & 1u)) x = 0.f;
-            v[q] = x;
-            ov[q] = from_f32<T>(x);
-            amx = fmaxf(amx, fabsf(x));
-        }
-        piece_store<T>(op, (char*)(out + i8));
-        if (f8.bits_out) ((unsigned char*)f8.bits_out)[i8 >> 3] = (unsigned char)mask_byte_of(v);
-        if (f8.out8) *(uint2*)(f8.out8 + i8) = pack8_fp8(v, f8.dscale ? f8.dscale[1] : out_scale);     // by value when the caller keeps no device scales
-    }
-    __shared__ float red[4];
-    if (f8.amax) amax_publish_wg(f8.amax, amx, blockIdx.x, red);
-}
+#define CONV_GATED 0
+#include "conv_splitk_finish_kernel.inc"
+#undef CONV_GATED
+#define CONV_GATED 1
+#include "conv_splitk_finish_kernel.inc"
+#undef CONV_GATED
 
 // Kernel-form selection of one `up` launch.  The library picks by launch size (-1 / 0 = automatic); cvae_conv_up and cvae_conv_fp8 let a caller
 // force a form for ONE call — the tests run every narrow case through both forms that way.  No process-wide state.
@@ -793,9 +293,10 @@ struct ConvArgs {
     float acc_scale = 1.f, out_scale = 1.f;
     F8Side f8 = F8Side{nullptr, nullptr, nullptr};
     UpVariant var = UpVariant{};
+    float gate_slope = 0.f;     // GATED launches only: `mask` is the gate, the value where it is not positive is multiplied by this instead of zeroed
 };
 
-template <typename T, int ND, bool UP, bool WIDE, int EPI, int KH, typename TO, int XB = 1>
+template <typename T, int ND, bool UP, bool WIDE, int EPI, int KH, typename TO, int XB = 1, bool GATED = false>
 int launch_data_epi(const ConvArgs& a) {
     using F = DataForm<T, ND, UP, WIDE>;
     using TL = Tile<ND, F::BM>;
@@ -813,9 +314,12 @@ int launch_data_epi(const ConvArgs& a) {
         // MNIST model at batch 1024, where one image fills 49 of a tile's 128 positions, in both directions): two samples per tile
         const long long wgs = (long long)((md + TL::TD - 1) / TL::TD) * ((mh + TL::TH - 1) / TL::TH) * ((UP ? g.Cl : g.Cs) / F::BN) * (UP ? (ND == 3 ? 8 : 4) : 1) * g.B;
         if (mw <= TL::TW / 2 && g.B >= 2 && (a.var.xpair == 1 || (a.var.xpair < 0 && wgs >= (ND == 3 ? XPAIR_MIN_WGS : XPAIR_2D_MIN_WGS))))
-            return launch_data_epi<T, ND, UP, WIDE, EPI, KH, TO, 2>(a);
+            return launch_data_epi<T, ND, UP, WIDE, EPI, KH, TO, 2, GATED>(a);
     }
-    constexpr auto kern = conv_data_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
+    constexpr auto kern = [] {                               // GATED: the second instance of the same text (conv_data_kernel.inc), one more argument
+        if constexpr (GATED) return conv_data_gated_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
+        else return conv_data_kernel<T, ND, UP, F::WM, F::WN, F::MI, F::NI, EPI, KH, TO, F::BD, F::TS, XB>;
+    }();
     if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
     g.tiles_d = (md + TL::TD - 1) / TL::TD; g.tiles_h = (mh + TL::TH - 1) / TL::TH; g.tiles_w = (mw + TL::TW - 1) / TL::TW;
     const int Cout = UP ? g.Cl : g.Cs, Cin = (UP ? g.Cs : g.Cl) / (IsF8<T>::value ? 2 : 1);
@@ -829,12 +333,21 @@ int launch_data_epi(const ConvArgs& a) {
     gy *= ksplit;
     if (gy > 65535 || g.B > 65535) return CVAE_E_BADSHAPE;
     dim3 grid((unsigned)tiles, (unsigned)gy, (unsigned)((g.B + XB - 1) / XB));
-    hipLaunchKernelGGL(kern, grid, dim3(F::WM * F::WN * F::TS * 64), LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const TO*)a.mask, (TO*)a.out, g, a.act,
-                       (float*)a.ws, ksplit, a.acc_scale, a.out_scale, a.f8);
+    if constexpr (GATED)
+        hipLaunchKernelGGL(kern, grid, dim3(F::WM * F::WN * F::TS * 64), LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const TO*)a.mask, (TO*)a.out, g, a.act,
+                           (float*)a.ws, ksplit, a.acc_scale, a.out_scale, a.f8, a.gate_slope);
+    else
+        hipLaunchKernelGGL(kern, grid, dim3(F::WM * F::WN * F::TS * 64), LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const TO*)a.mask, (TO*)a.out, g, a.act,
+                           (float*)a.ws, ksplit, a.acc_scale, a.out_scale, a.f8);
     CVAE_CHECK_LAUNCH();
     if constexpr (sizeof(TO) != 1) if (ksplit > 1) {
-        hipLaunchKernelGGL((conv_splitk_finish_kernel<TO, EPI>), dim3((unsigned)((total / 8 + 255) / 256)), dim3(256), 0, a.stream, (const float*)a.ws, a.bias,
-                           (const TO*)a.mask, (TO*)a.out, total, Cout, ksplit, a.act, IsF8<T>::value ? a.acc_scale : 1.f, a.out_scale, a.f8);
+        const dim3 fgrid((unsigned)((total / 8 + 255) / 256));
+        if constexpr (GATED)                                 // unreachable today: GATED launches are `up` launches, and pick_ksplit returns 1 for every `up`
+            hipLaunchKernelGGL((conv_splitk_finish_gated_kernel<TO, EPI>), fgrid, dim3(256), 0, a.stream, (const float*)a.ws, a.bias, (const TO*)a.mask, (TO*)a.out, total,
+                               Cout, ksplit, a.act, 1.f, a.out_scale, a.f8, a.gate_slope);
+        else
+            hipLaunchKernelGGL((conv_splitk_finish_kernel<TO, EPI>), fgrid, dim3(256), 0, a.stream, (const float*)a.ws, a.bias,
+                               (const TO*)a.mask, (TO*)a.out, total, Cout, ksplit, a.act, IsF8<T>::value ? a.acc_scale : 1.f, a.out_scale, a.f8);
         CVAE_CHECK_LAUNCH();
     }
     return CVAE_OK;
@@ -848,6 +361,13 @@ int dispatch_conv(const ConvArgs& a) {
         constexpr int EPI = decltype(epi)::value;
         return F::kh(a.g) == 2 ? launch_data_epi<T, ND, UP, WIDE, EPI, F::KH_MAX, TO>(a) : launch_data_epi<T, ND, UP, WIDE, EPI, 1, TO>(a);
     });
+}
+
+// The gated `up` product (cvae_conv_down_bwd_data): no bias, no activation (EPI 0), so only the stage depth is lifted.
+template <typename T, int ND, bool WIDE>
+int dispatch_conv_gated(const ConvArgs& a) {
+    using F = DataForm<T, ND, true, WIDE>;
+    return F::kh(a.g) == 2 ? launch_data_epi<T, ND, true, WIDE, 0, F::KH_MAX, T, 1, true>(a) : launch_data_epi<T, ND, true, WIDE, 0, 1, T, 1, true>(a);
 }
 
 // Workspace the split-K path of dispatch_conv would use for this geometry (0: the launch fills the chip without it).  The tile extents do not depend on the dtype.
@@ -881,228 +401,12 @@ size_t data_workspace_bytes(const ConvGeom& g) {
 //     conflict-free exactly as the plane-major image did, and the pieces of one position, stored by consecutive lanes, hit different banks),
 //     so that every read of a parity is `ds_read_b128 base, offset:imm` off two per-parity base registers — no address VALU in the loop;
 //   * bias and the ReLU mask of a parity are fetched before its taps, not in the epilogue.
-template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH, int EPI, typename TO = T>
-__global__ __launch_bounds__(WM * WN * 64) void conv_up_full_kernel(const T* __restrict__ in, const T* __restrict__ wp, const float* __restrict__ bias,
-                                                                     const TO* __restrict__ mask, TO* __restrict__ out, ConvGeom g, int act, int ppw,
-                                                                     float acc_scale, float out_scale) {
-    constexpr int NT = WM * WN * 64;
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    using TL = Tile<ND, BM>;
-    constexpr int TD = TL::TD, TH = TL::TH, TW = TL::TW;
-    constexpr int ID = (ND == 3) ? TD + 2 : 1, IH = TH + 2, IW = TW + 2, NPOS = ID * IH * IW;
-    constexpr int FB = 8 * sizeof(T);
-    using ST = SubTile<ND>;
-    constexpr int RS = HaloPitch<ND, true>::RS, NROWS = ID * IH, NSLOT = NROWS * RS;
-    static_assert(RS >= IW, "halo pitch too small");
-    constexpr int NPC = 2 * KCH, SPITCH = NPC + 1;           // 8-channel pieces per position; slot pitch in pieces (odd)
-    constexpr int NTAP = (ND == 3) ? 8 : 4;                  // taps per parity class (= number of parity classes)
-    constexpr int HTAP = NTAP / 2, PT = KCH * 2 * BN, HP_PIECES = HTAP * PT, HP_BYTES = HP_PIECES * FB, HPP = HP_PIECES / NT;
-    static_assert(PT % NT == 0, "a tap's weight pieces must be a whole number of workgroup passes");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* halo = smem;
-    char* wbuf = smem + (size_t)NSLOT * SPITCH * FB;
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    STAMP_BEGIN();
-    const int wm = wave / WN, wn = wave % WN;
-    const int r = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z;
-    const int Cin = g.Cs, Cout = g.Cl;
-    const int nblocks = Cout / BN;
-    const int nb = blockIdx.y % nblocks, pg = blockIdx.y / nblocks;
-    const int n0 = nb * BN;
-    int tile = xcd_remap(blockIdx.x, gridDim.x);
-    const int tw_i = tile % g.tiles_w; tile /= g.tiles_w;
-    const int th_i = tile % g.tiles_h; tile /= g.tiles_h;
-    const int o0d = tile * TD, o0h = th_i * TH, o0w = tw_i * TW;
-    const int g0d = (ND == 3) ? o0d - 1 : 0, g0h = o0h - 1, g0w = o0w - 1;
-    static_assert(ST::SW == TW && TH % ST::SH == 0, "sub-tile must tile the workgroup tile");
-    constexpr int HB = TH / ST::SH;
-    int pbase[MI];                                           // halo slot of this lane's position in each M sub-tile, parity (0, 0, 0), tap (0, 0, 0)
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-        const int ms = wm * MI + mi;
-        pbase[mi] = ((ms / HB) * IH + (ms % HB) * ST::SH + ST::h_of(r)) * RS + ST::w_of(r);
-    }
-    const int par0 = pg * ppw, nhp = 2 * ppw;
-    auto tap_abc = [](int tap, int& a, int& bb, int& c) { a = (ND == 3) ? (tap >> 2) : 0; bb = (tap >> 1) & 1; c = tap & 1; };
-    // ---- weight half panels: hpi -> (parity par0 + hpi / 2, taps (hpi & 1) * HTAP ..); LDS image [tap][k-step][half][n] ----
-    const unsigned w_lane = (unsigned)((((t / (2 * BN)) * Cout + (t >> 1) % BN) * 16 + 8 * (t & 1)) * sizeof(T));     // the thread's piece inside a pass
-    const int w_slot = (t / (2 * BN)) * (2 * BN) + (t & 1) * BN + (t >> 1) % BN;
-    struct HalfPanel { Piece<T> p[HPP]; };                   // by value: as reference parameters of the lambdas the two register sets ended up in scratch
-    auto load_hp = [&](int hpi) -> HalfPanel {
-        HalfPanel wr;
-        const int par = par0 + (hpi >> 1), th = hpi & 1;
-        const int prd = (ND == 3) ? ((par >> 2) & 1) : 0, prh = (par >> 1) & 1, prw = par & 1;
-#pragma unroll
-        for (int i = 0; i < HPP; ++i) {
-            const int tl = (i * NT) / PT, k0 = ((i * NT) % PT) / (2 * BN);       // pass i: tap tl of the half, k-steps k0 .. k0 + NT / (2 BN) - 1
-            int a, bb, c;
-            tap_abc(th * HTAP + tl, a, bb, c);
-            const int kd = (ND == 3) ? (3 - prd - 2 * a) : 0, kh = 3 - prh - 2 * bb, kw = 3 - prw - 2 * c;
-            const T* wu = wp + ((size_t)(((kd * 4 + kh) * 4 + kw) * KCH + k0) * Cout + n0) * 16;     // uniform
-            piece_load_raw<T>(wr.p[i], (const T*)((const char*)wu + w_lane));
-        }
-        return wr;
-    };
-    auto store_hp = [&](const HalfPanel& wr, int buf) {
-#pragma unroll
-        for (int i = 0; i < HPP; ++i) piece_store<T>(wr.p[i], wbuf + (size_t)buf * HP_BYTES + (size_t)(i * NT + w_slot) * FB);
-    };
-    f32x16 acc[MI][NI];
-    const char* abase[MI];                                   // per parity: LDS address of (lane position + parity shift, piece h)
-    auto compute_hp = [&](const char* wb, int th) {          // HTAP * KCH k-steps, both operands from LDS, reads APD steps ahead of their MFMAs
-        constexpr int NS = HTAP * KCH, APD = APIPE < NS ? APIPE : NS - 1;
-        Frag<T> ar[APD + 1][MI], br[APD + 1][NI];
-        const char* bb0 = wb + (size_t)(h * BN + wn * NI * 32 + r) * FB;
-        auto ld = [&](int slot, int i) {
-            const int tl = i / KCH, kk = i % KCH;
-            int a, bb, c;
-            tap_abc(tl, a, bb, c);                            // th * HTAP + tl: the half only moves the first tap coordinate (a in 3D, bb in 2D)
-            const int tapc = (ND == 3) ? ((a + th) * IH + bb) * RS + c : (bb + th) * RS + c;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) lds_load(ar[slot][mi], abase[mi] + (size_t)(tapc * SPITCH + 2 * kk) * FB);
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) lds_load(br[slot][ni], bb0 + (size_t)((tl * KCH + kk) * 2 * BN + ni * 32) * FB);
-        };
-#pragma unroll
-        for (int d = 0; d < APD; ++d) ld(d, d);
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            if (i + APD < NS) ld((i + APD) % (APD + 1), i + APD);
-            __builtin_amdgcn_sched_barrier(0);              // keep the reads where they are written: the scheduler would sink them back to their uses
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) mma(acc[mi][ni], br[i % (APD + 1)][ni], ar[i % (APD + 1)][mi]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    STAMP(1);
-    HalfPanel wra = load_hp(0), wrb = wra;
-    // ---- stage the whole halo (all channels), once: thread t moves piece t % NPC of positions t / NPC + i * (NT / NPC) ----
-    {
-        static_assert(NT % NPC == 0, "pieces of a position must stay in one pass");
-        constexpr int PSTEP = NT / NPC, HN = (NPOS + PSTEP - 1) / PSTEP;
-        constexpr int DX = PSTEP % IW, DY = (PSTEP / IW) % IH, DZ = PSTEP / (IW * IH);
-        const T* in_b = in + (size_t)b * g.sd * g.sh * g.sw * Cin;
-        const int pc = t % NPC, pos0 = t / NPC;
-        int x = pos0 % IW, y = (pos0 / IW) % IH, z = pos0 / (IW * IH);
-        Piece<T> hp[HN];
-        int hs[HN];
-#pragma unroll
-        for (int i = 0; i < HN; ++i) {
-            const int gz = g0d + z, gy = g0h + y, gx = g0w + x;
-            const bool in_tile = z < ID;
-            const bool ok = in_tile & (gz >= 0) & (gz < g.sd) & (gy >= 0) & (gy < g.sh) & (gx >= 0) & (gx < g.sw);
-            piece_load<T>(hp[i], in_b + (ok ? (((size_t)gz * g.sh + gy) * g.sw + gx) * Cin + 8 * pc : 0), ok);
-            hs[i] = in_tile ? ((z * IH + y) * RS + x) * SPITCH + pc : -1;
-            x += DX; if (x >= IW) { x -= IW; y += 1; }
-            y += DY; if (y >= IH) { y -= IH; z += 1; }
-            z += DZ;
-        }
-        STAMP(2);
-#pragma unroll
-        for (int i = 0; i < HN; ++i)
-            if (hs[i] >= 0) piece_store<T>(hp[i], halo + (size_t)hs[i] * FB);
-    }
-    store_hp(wra, 0);
-    wra = load_hp(1);
-    __syncthreads();
-    STAMP(3);
-
-    const int out_d = g.ld, out_h = g.lh, out_w = g.lw;
-    Piece<TO> mpre[MI][NI][2];
-    float bpre[NI][2][8];
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) bpre[ni][j][q] = bias ? bias[c + q] : 0.f;
-        }
-    auto parity_begin = [&](int par) {                       // accumulators, LDS base of the parity's reads, its mask pieces
-        const int prd = (ND == 3) ? ((par >> 2) & 1) : 0, prh = (par >> 1) & 1, prw = par & 1;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-            abase[mi] = halo + (size_t)((pbase[mi] + (prd * IH + prh) * RS + prw) * SPITCH + h) * FB;
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
-        }
-        if (!mask) return;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-            const int ms = wm * MI + mi;
-            const int w = ST::w_of(r), hh = (ms % HB) * ST::SH + ST::h_of(r), d = ms / HB;
-            const int od = (ND == 3) ? 2 * (o0d + d) + prd : 0, oh = 2 * (o0h + hh) + prh, ow = 2 * (o0w + w) + prw;
-            const bool ok = od < out_d && oh < out_h && ow < out_w;
-            const size_t pidx = ok ? ((((size_t)b * out_d + od) * out_h + oh) * out_w + ow) * Cout : 0;
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) piece_load_raw<TO>(mpre[mi][ni][j], mask + pidx + n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h);
-        }
-    };
-    auto epilogue = [&](int par) {                           // as conv_data_kernel's, but its own text: one sample per workgroup (no b + sx), the mask as pieces of the saved activation, no side channel
-        const int prd = (ND == 3) ? ((par >> 2) & 1) : 0, prh = (par >> 1) & 1, prw = par & 1;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-            const int ms = wm * MI + mi;
-            const int w = ST::w_of(r), hh = (ms % HB) * ST::SH + ST::h_of(r), d = ms / HB;
-            const int od = (ND == 3) ? 2 * (o0d + d) + prd : 0, oh = 2 * (o0h + hh) + prh, ow = 2 * (o0w + w) + prw;
-            const bool ok = od < out_d && oh < out_h && ow < out_w;
-            const size_t pidx = ((((size_t)b * out_d + od) * out_h + oh) * out_w + ow) * Cout;
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-                float v[2][8];
-                REGROUP_D32(acc[mi][ni], v)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int c = n0 + (wn * NI + ni) * 32 + 16 * j + 8 * h;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        float x = (sizeof(T) == 1 ? v[j][q] * acc_scale : v[j][q]) + bpre[ni][j][q];
-                        if (EPI == 1) x = relu_f32(x);
-                        else if (EPI == 2) x = apply_act(x, act);
-                        v[j][q] = x;
-                    }
-                    if (!ok) continue;
-                    if (mask) {
-                        const TO* mv = (const TO*)&mpre[mi][ni][j];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q)
-                            if (!(to_f32(mv[q]) > 0.f)) v[j][q] = 0.f;
-                    }
-                    Piece<TO> op;
-                    TO* ov = (TO*)&op;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) ov[q] = from_f32<TO>(sizeof(T) == 1 ? v[j][q] * out_scale : v[j][q]);
-                    piece_store<TO>(op, (char*)(out + pidx + c));
-                }
-            }
-        }
-    };
-    // half panels in pairs = one parity per iteration; panel hpi + 1 sits in wra, hpi + 2 is requested into wrb at the top
-    for (int hpi = 0; hpi < nhp; hpi += 2) {
-        const int par = par0 + (hpi >> 1);
-        if (hpi + 2 < nhp) wrb = load_hp(hpi + 2);
-        parity_begin(par);
-        compute_hp(wbuf, 0);
-        store_hp(wra, 1);
-        __syncthreads();
-        if (hpi + 3 < nhp) wra = load_hp(hpi + 3);
-        compute_hp(wbuf + HP_BYTES, 1);
-        if (hpi + 2 < nhp) store_hp(wrb, 0);
-        STAMP(4 + hpi);
-        epilogue(par);
-        STAMP(5 + hpi);
-        __syncthreads();
-    }
-    STAMP_END();
-}
+#define CONV_GATED 0
+#include "conv_up_full_kernel.inc"
+#undef CONV_GATED
+#define CONV_GATED 1
+#include "conv_up_full_kernel.inc"
+#undef CONV_GATED
 
 template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH> constexpr size_t up_full_lds_bytes() {
     using TL = Tile<ND, WM * MI * 32>;
@@ -1113,7 +417,7 @@ template <typename T, int ND, int WM, int WN, int MI, int NI, int KCH> constexpr
 // Launch of conv_up_full_kernel; CVAE_E_UNSUPPORTED when this channel count does not fit the LDS or the grid is below UPFULL_MIN_GRID (the caller falls back
 // to dispatch_conv<UP>).  Only the 32-channel tile form (DataForm<.., WIDE = false>) goes here: on 64-channel tiles the kernel measured slower than
 // conv_data_kernel<UP> with BD.
-template <typename T, int ND, int KCH>
+template <typename T, int ND, int KCH, bool GATED = false>
 int launch_up_full(const ConvArgs& a) {
     using F = DataForm<T, ND, true, false>;
     constexpr int WM = F::WM, WN = F::WN, MI = F::MI, NI = F::NI;
@@ -1134,6 +438,14 @@ int launch_up_full(const ConvArgs& a) {
         const long long gy = (long long)nblocks * psplit;
         if (gy > 65535 || g.B > 65535) return CVAE_E_BADSHAPE;
         dim3 grid((unsigned)tiles, (unsigned)gy, (unsigned)g.B), block(WM * WN * 64);
+        if constexpr (GATED) {                               // cvae_conv_down_bwd_data: no bias, no activation (EPI 0)
+            constexpr auto kern = conv_up_full_gated_kernel<T, ND, WM, WN, MI, NI, KCH, 0, T>;
+            if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
+            hipLaunchKernelGGL(kern, grid, block, LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const T*)a.mask, (T*)a.out, g, a.act, npar / psplit,
+                               a.acc_scale, a.out_scale, a.gate_slope);
+            CVAE_CHECK_LAUNCH();
+            return CVAE_OK;
+        } else
         return with_epi(a.act, [&](auto epi) {
             constexpr auto kern = conv_up_full_kernel<T, ND, WM, WN, MI, NI, KCH, decltype(epi)::value, T>;
             if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
@@ -1146,11 +458,11 @@ int launch_up_full(const ConvArgs& a) {
 }
 
 // `up` through the whole-K kernel when the input channel count is one it is built for (64 / 128 / 256 where the halo fits): CVAE_E_UNSUPPORTED otherwise.
-template <typename T, int ND>
+template <typename T, int ND, bool GATED = false>
 int try_up_full(const ConvArgs& a) {
-    if (a.g.Cs == 64) return launch_up_full<T, ND, 4>(a);
-    if (a.g.Cs == 128) return launch_up_full<T, ND, 8>(a);
-    if (a.g.Cs == 256) return launch_up_full<T, ND, 16>(a);
+    if (a.g.Cs == 64) return launch_up_full<T, ND, 4, GATED>(a);
+    if (a.g.Cs == 128) return launch_up_full<T, ND, 8, GATED>(a);
+    if (a.g.Cs == 256) return launch_up_full<T, ND, 16, GATED>(a);
     return CVAE_E_UNSUPPORTED;
 }
 
@@ -1946,6 +1258,38 @@ extern "C" int cvae_conv_up(const void* S, const void* w, const float* bias, con
         }
         return with_bool(wide, [&](auto wd) { return dispatch_conv<T, ND, true, decltype(wd)::value>(a); });
     }); });
+}
+
+// dx = scatter(g, w) * act'(gate): cvae_conv_up's product, forms and dispatch.  act' is 1 (NONE: no gate read) or a 0 / 1 mask (RELU) through cvae_conv_up
+// itself — the same launches, the same bits — and a LeakyReLU slope through the gated instances of the three kernels.
+extern "C" int cvae_conv_down_bwd_data(const void* grad, const void* w, const void* gate, void* dx, int64_t B, int64_t sh, int64_t sw, int64_t Cs, int64_t lh, int64_t lw,
+                                       int64_t Cl, int nd, int dtype, int gate_act, void* workspace, size_t workspace_bytes, int upfull, int xpair, void* stream) {
+    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_RELU && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_LEAKY02) return CVAE_E_UNSUPPORTED;
+    if (nd != 2 || Cs <= 0 || Cl <= 0 || Cs % 16 || Cl % 32) return CVAE_E_UNSUPPORTED;
+    if (gate_act != CVAE_ACT_NONE && !gate && B > 0) return CVAE_E_NULLPTR;
+    if (gate_act == CVAE_ACT_NONE || gate_act == CVAE_ACT_RELU)
+        return cvae_conv_up(grad, w, nullptr, gate_act == CVAE_ACT_RELU ? gate : nullptr, nullptr, dx, nullptr, B, 1, sh, sw, Cs, 1, lh, lw, Cl, 2, dtype, CVAE_ACT_NONE,
+                            workspace, workspace_bytes, upfull, xpair, 0, stream);
+    if (upfull < -1 || upfull > 1 || xpair < -1 || xpair > 1) return CVAE_E_BADSHAPE;
+    const int64_t sd = 1, ld = 1;
+    if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
+    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (B == 0) return CVAE_OK;
+    if (!grad || !w || !dx) return CVAE_E_NULLPTR;
+    UpVariant var;
+    var.upfull = upfull; var.xpair = xpair;
+    GEOM_INIT();
+    const bool wide = (Cl % 64) == 0;
+    ConvArgs a{grad, w, nullptr, gate, dx, g, CVAE_ACT_NONE, workspace, workspace_bytes, (hipStream_t)stream, 1.f, 1.f, F8Side{nullptr, nullptr, nullptr}, var};
+    a.gate_slope = gate_act == CVAE_ACT_LEAKY02 ? 0.2f : 0.01f;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (std::is_same<T, bf16>::value) if (!wide) {            // the whole-K kernel, as in cvae_conv_up
+            const int rc = try_up_full<T, 2, true>(a);
+            if (rc != CVAE_E_UNSUPPORTED) return rc;
+        }
+        return with_bool(wide, [&](auto wd) { return dispatch_conv_gated<T, 2, decltype(wd)::value>(a); });
+    });
 }
 
 extern "C" size_t cvae_conv_wgrad_workspace_bytes(int64_t Cs, int64_t Cl, int nd) {

@@ -322,7 +322,8 @@ __global__ __launch_bounds__(256) void fold_bn_conv_bwd_kernel(const FoldBwdTabl
     while (k < T.count - 1 && (int)blockIdx.x >= T.end[k]) ++k;
     const FoldBwdEntry& E = T.e[k];
     const int c = (int)blockIdx.x - (k ? T.end[k - 1] : 0), t = threadIdx.x;
-    const bool convt = E.kind != CVAE_FOLD_CONV_K3S1, k4 = E.kind == CVAE_FOLD_CONVT_K3S2;
+    // weight layout [Cin][Cout] (the transposed convs) or [Cout][Cin]; dwf with 16 taps per pair (the k4 weight gradients: 3 x 3 of 4 x 4 read) or 9
+    const bool convt = E.kind != CVAE_FOLD_CONV_K3S1 && E.kind != CVAE_FOLD_CONV_K3S2, k4 = E.kind == CVAE_FOLD_CONVT_K3S2 || E.kind == CVAE_FOLD_CONV_K3S2;
     const float rstd = E.gamma ? rsqrtf(E.var[c] + E.eps) : 1.f, s = E.gamma ? E.gamma[c] * rstd : 1.f;
     float part = 0.f;
     for (int i = t; i < E.cin * 9; i += 256) {
@@ -477,7 +478,8 @@ extern "C" int cvae_fold_bn_conv_bwd(int count, const float* const* w, const int
         FoldBwdEntry& E = T.e[k];
         const int64_t Cout = dims[2 * k], Cin = dims[2 * k + 1];
         if (Cout <= 0 || Cin <= 0 || Cout * Cin > ((int64_t)1 << 24)) return CVAE_E_BADSHAPE;
-        if (kind[k] != CVAE_FOLD_CONVT_K3S2 && kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL) return CVAE_E_UNSUPPORTED;
+        if (kind[k] != CVAE_FOLD_CONVT_K3S2 && kind[k] != CVAE_FOLD_CONV_K3S1 && kind[k] != CVAE_FOLD_CONVT_K3S2_SUBPIXEL && kind[k] != CVAE_FOLD_CONV_K3S2)
+            return CVAE_E_UNSUPPORTED;
         if (!w[k] || !dwf[k] || !dbf[k] || !dw[k]) return CVAE_E_NULLPTR;
         const bool bn = gamma && gamma[k];
         if (bn && (!mean || !mean[k] || !var || !var[k] || !dgamma || !dgamma[k] || !dbeta || !dbeta[k])) return CVAE_E_NULLPTR;

@@ -156,10 +156,11 @@ __device__ __forceinline__ void kahan_add(float& s, float& c, float v) {
 }
 
 // ------------------------------------------------------------------------------------------------ token assembly, backward
-// dpos[i] = sum_b dtokens[b][i] (b in order), dcls = dpos[0], dstem[b][i] = dtokens[b][1 + i] in the stem's dtype
+// dpos[i] = sum_b dtokens[b][i] (b in order), dcls = dpos[0], dstem[b][i] = dtokens[b][1 + i] (* act'(gate[b][i]) with a gate: the fp32 product, one
+// rounding) in the stem's dtype.  The sums take the ungated values.
 template <typename T>
 __global__ __launch_bounds__(256) void vit_tokens_bwd_kernel(const float* __restrict__ dtok, float* __restrict__ dpos, float* __restrict__ dcls,
-                                                             T* __restrict__ dstem, int64_t B, int64_t Np) {
+                                                             T* __restrict__ dstem, int64_t B, int64_t Np, const T* __restrict__ gate, float slope) {
     const int64_t total = (Np + 1) * (VIT_DIM / 4);
     for (int64_t g = blockIdx.x * (int64_t)256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
         const int c4 = (int)(g & (VIT_DIM / 4 - 1));
@@ -170,7 +171,15 @@ __global__ __launch_bounds__(256) void vit_tokens_bwd_kernel(const float* __rest
             load_f32(dtok + (b * (Np + 1) + i) * VIT_DIM + c4 * 4, v);
 #pragma unroll
             for (int e = 0; e < 4; ++e) s[e] += v[e];
-            if (i > 0) store_from_f32(dstem + (b * Np + i - 1) * VIT_DIM + c4 * 4, v);
+            if (i > 0) {
+                if (gate) {
+                    float gt[4];
+                    load_f32(gate + (b * Np + i - 1) * VIT_DIM + c4 * 4, gt);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] *= gt[e] > 0.f ? 1.f : slope;
+                }
+                store_from_f32(dstem + (b * Np + i - 1) * VIT_DIM + c4 * 4, v);
+            }
         }
         store_from_f32(dpos + i * VIT_DIM + c4 * 4, s);
         if (i == 0) store_from_f32(dcls + c4 * 4, s);
@@ -798,16 +807,21 @@ extern "C" int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, 
 static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
 static bool is_dtype(int d) { return d == CVAE_F32 || d == CVAE_BF16; }
 
-extern "C" int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, int64_t B, int64_t n_patches, void* stream) {
+extern "C" int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, const void* gate, int gate_act, int64_t B,
+                                   int64_t n_patches, void* stream) {
     if (B < 1 || n_patches < 1 || B * (n_patches + 1) > ((int64_t)1 << 32)) return CVAE_E_BADSHAPE;
     if (!is_dtype(stem_dtype)) return CVAE_E_DTYPE;
     if (!dtokens || !dpos || !dcls || !dstem) return CVAE_E_NULLPTR;
-    if (!aligned16(dtokens) || !aligned16(dpos) || !aligned16(dcls) || !aligned16(dstem)) return CVAE_E_UNSUPPORTED;
+    if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_RELU && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_LEAKY02) return CVAE_E_UNSUPPORTED;
+    if (gate_act == CVAE_ACT_NONE) gate = nullptr;                          // not read: whatever the caller passed
+    else if (!gate) return CVAE_E_NULLPTR;
+    if (!aligned16(dtokens) || !aligned16(dpos) || !aligned16(dcls) || !aligned16(dstem) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
+    const float slope = gate_act == CVAE_ACT_LEAKY02 ? 0.2f : (gate_act == CVAE_ACT_LEAKY001 ? 0.01f : 0.f);
     const int blocks = cvae_grid_1d((n_patches + 1) * (VIT_DIM / 4), 256, 256 * 32);
     if (stem_dtype == CVAE_BF16)
-        hipLaunchKernelGGL(vit_tokens_bwd_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (bf16*)dstem, B, n_patches);
+        hipLaunchKernelGGL(vit_tokens_bwd_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (bf16*)dstem, B, n_patches, (const bf16*)gate, slope);
     else
-        hipLaunchKernelGGL(vit_tokens_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (float*)dstem, B, n_patches);
+        hipLaunchKernelGGL(vit_tokens_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (float*)dstem, B, n_patches, (const float*)gate, slope);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
 }

@@ -475,6 +475,41 @@ def _conv_up(St, wp, bias, mask, Cl, nd, act, l_dims=None, mask_bits=None, want_
     return (Lt, bits) if want_bits is not None else Lt
 
 
+_GATE_ACTS = (None, "none", "relu", "leaky001", "leaky02")
+
+
+def conv_down_bwd_data(g, w_packed_up, gate, gate_act, variant=None):
+    """scatter(g, w) * act'(gate): the input gradient of a 2D k4/s2/p1 `down` conv with the derivative of the activation that PRODUCED its input in the
+    epilogue (cvae_conv_down_bwd_data) — one launch where _conv_up + _act_bwd are two.  g channels-last [B, 1, sh, sw, Cs] or [B, sh, sw, Cs], fp32 or bf16;
+    w_packed_up = pack_weight(w, 2, True, g.dtype) of the k4 weight [Cs, Cl, 4, 4]; gate: the conv's input [B, (1,) 2 sh, 2 sw, Cl] in g's dtype, the OUTPUT of
+    the activation gate_act (None / "relu" / "leaky001" / "leaky02"; LeakyReLU keeps the sign): gate > 0 ? 1 : slope, multiplied on the fp32 sum before the one
+    rounding.  Returns a tensor of gate's shape (2 sh x 2 sw without a gate).  variant (tests): (upfull, xpair), the per-call kernel form of cvae_conv_up."""
+    L.require_gpu(g, w_packed_up, gate)
+    _forward_only("conv_down_bwd_data", g, w_packed_up, gate)
+    if gate_act not in _GATE_ACTS:
+        raise L.CvaeError(f"conv_down_bwd_data: gate_act must be one of {_GATE_ACTS[2:]} or None, got {gate_act!r}")
+    if (gate is None) != (gate_act in (None, "none")):
+        raise L.CvaeError("conv_down_bwd_data: gate and gate_act come together")
+    if g.dim() not in (4, 5) or (g.dim() == 5 and g.shape[1] != 1) or not g.is_contiguous() or g.dtype not in (torch.float32, torch.bfloat16):
+        raise L.CvaeError(f"conv_down_bwd_data: a contiguous channels-last [B, sh, sw, Cs] fp32 or bf16 gradient expected, got {tuple(g.shape)} {g.dtype}")
+    B, sh, sw, Cs = g.shape[0], g.shape[-3], g.shape[-2], g.shape[-1]
+    if w_packed_up.dtype != g.dtype or not w_packed_up.is_contiguous() or w_packed_up.numel() % (16 * Cs):
+        raise L.CvaeError(f"conv_down_bwd_data: packed weight {tuple(w_packed_up.shape)} {w_packed_up.dtype} does not fit {Cs} channels in {g.dtype}")
+    Cl = w_packed_up.numel() // (16 * Cs)
+    oshape = tuple(g.shape[:-3]) + (2 * sh, 2 * sw, Cl) if gate is None else tuple(gate.shape)
+    if gate is not None:
+        if gate.dim() != g.dim() or gate.shape[0] != B or gate.shape[-1] != Cl or gate.shape[-3] // 2 != sh or gate.shape[-2] // 2 != sw:
+            raise L.CvaeError(f"conv_down_bwd_data: a gate of shape {tuple(gate.shape)} does not belong to a gradient of shape {tuple(g.shape)} and {Cl} channels")
+        _like_operands("conv_down_bwd_data", oshape, g.dtype, gate=gate)
+    lh, lw = oshape[-3], oshape[-2]
+    dx = _empty(oshape, g.dtype, g)
+    ws, nbytes = _conv_data_workspace(g.device, B, 1, sh, sw, Cs, 1, lh, lw, Cl, 2, 1)
+    upfull, xpair = (-1, -1) if variant is None else (int(v) for v in variant)
+    check(L.timed(f"conv_down_bwd_data B{B} S{sh}x{sw}x{Cs} -> L{Cl}", lib.cvae_conv_down_bwd_data, ptr(g), ptr(w_packed_up), ptr(gate), ptr(dx), B, sh, sw, Cs, lh, lw, Cl,
+                  2, L.dtype_code(g.dtype), L.act_code(gate_act), ptr(ws), nbytes, upfull, xpair, stream()), "conv_down_bwd_data")
+    return dx
+
+
 DEFER_WGRAD = True     # weight gradients of the MFMA conv layers are queued during a backward pass and computed by ONE grouped launch (+ one
                        # reduce launch) at its end (cvae_conv_wgrad_multi): the small layers run in the shadow of the large ones
 _WG_PENDING = []
@@ -2163,15 +2198,22 @@ def layernorm256_bwd(g, x, weight, eps, dx=None, accumulate=False):
     return dx, dgamma, dbeta
 
 
-def vit_tokens_bwd(dtokens, stem_dtype):
-    """(dpos [n + 1, 256], dcls [256], dstem [B, n, 256] in stem_dtype) from the fp32 residual-stream gradient [B, n + 1, 256] (cvae_vit_tokens_bwd)."""
-    L.require_gpu(dtokens)
-    _forward_only("vit_tokens_bwd", dtokens)
+def vit_tokens_bwd(dtokens, stem_dtype, gate=None, gate_act=None):
+    """(dpos [n + 1, 256], dcls [256], dstem [B, n, 256] in stem_dtype) from the fp32 residual-stream gradient [B, n + 1, 256] (cvae_vit_tokens_bwd).
+    gate / gate_act (optional, together): the stem's output [B, n, 256] in stem_dtype, the output of the activation gate_act; dstem is then multiplied by
+    act'(gate) = gate > 0 ? 1 : slope in fp32 before its one rounding — the gradient of the stem's last PRE-activation.  dpos and dcls are never gated."""
+    L.require_gpu(dtokens, gate)
+    _forward_only("vit_tokens_bwd", dtokens, gate)
+    if (gate is None) != (gate_act in (None, "none")) or gate_act not in _GATE_ACTS:
+        raise L.CvaeError(f"vit_tokens_bwd: gate and gate_act ({_GATE_ACTS[2:]}) come together, got gate_act={gate_act!r}")
     if dtokens.dim() != 3 or dtokens.shape[1] < 2 or dtokens.shape[2] != 256 or dtokens.dtype != torch.float32 or not dtokens.is_contiguous():
         raise L.CvaeError(f"vit_tokens_bwd: a contiguous fp32 [B, n + 1, 256] gradient expected, got {tuple(dtokens.shape)} {dtokens.dtype}")
     B, n = dtokens.shape[0], dtokens.shape[1] - 1
     dpos, dcls, dstem = _empty((n + 1, 256), torch.float32, dtokens), _empty((256,), torch.float32, dtokens), _empty((B, n, 256), stem_dtype, dtokens)
-    check(lib.cvae_vit_tokens_bwd(ptr(dtokens), ptr(dpos), ptr(dcls), ptr(dstem), L.dtype_code(stem_dtype), B, n, stream()), "vit_tokens_bwd")
+    if gate is not None:
+        _like_operands("vit_tokens_bwd", (B, n, 256), stem_dtype, gate=gate)
+    check(lib.cvae_vit_tokens_bwd(ptr(dtokens), ptr(dpos), ptr(dcls), ptr(dstem), L.dtype_code(stem_dtype), ptr(gate), L.act_code(gate_act), B, n, stream()),
+          "vit_tokens_bwd")
     return dpos, dcls, dstem
 
 
@@ -2410,7 +2452,8 @@ def latent_to_grid_wgrad(g, z):
 
 def fold_bn_conv_bwd(entries):
     """The way back through fold_bn_conv for up to 16 layers in ONE launch (cvae_fold_bn_conv_bwd).  entries: (weight, kind, bias, bn, dwf, dbf) with kind
-    FOLD_CONVT_K3S2 (dwf: the gradient of the k4 weight [Cin, Cout, 4, 4]), FOLD_CONV_K3S1 (dwf [Cout, Cin, 3, 3]) or FOLD_CONVT_K3S2_SUBPIXEL (dwf [Cin, Cout, 3, 3]),
+    FOLD_CONVT_K3S2 (dwf: the gradient of the k4 weight [Cin, Cout, 4, 4]), FOLD_CONV_K3S1 (dwf [Cout, Cin, 3, 3]), FOLD_CONVT_K3S2_SUBPIXEL (dwf [Cin, Cout, 3, 3])
+    or FOLD_CONV_K3S2 (the ViT-VAE stem; dwf: the gradient of the k4 weight [Cout, Cin, 4, 4] as _conv_wgrad writes it, fourth row and column ignored; any Cin),
     dbf the folded bias's gradient [Cout], bn an eval-mode nn.BatchNorm2d (running statistics are constants).  Returns [(dw, db, dgamma, dbeta)] fp32, each of
     its parameter's shape: dw = s dwf, db = s dbf, dgamma = rstd (sum dwf w + dbf (bias - mean)), dbeta = dbf with s = gamma rstd."""
     import ctypes as C
@@ -2421,10 +2464,10 @@ def fold_bn_conv_bwd(entries):
     for w, kind, bias, bn, dwf, dbf in entries:
         L.require_gpu(w, bias, dwf, dbf)
         _forward_only("fold_bn_conv_bwd", w, bias, dwf, dbf, bn.weight, bn.bias)
-        if kind not in (FOLD_CONVT_K3S2, FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL) or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        if kind not in (FOLD_CONVT_K3S2, FOLD_CONV_K3S1, FOLD_CONVT_K3S2_SUBPIXEL, FOLD_CONV_K3S2) or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
             raise L.CvaeError(f"fold_bn_conv_bwd: kind {kind} does not match a weight of shape {tuple(w.shape)}")
         cout, cin = (w.shape[1], w.shape[0]) if kind in _FOLD_CONVT else (w.shape[0], w.shape[1])
-        want = tuple(w.shape[:2]) + ((4, 4) if kind == FOLD_CONVT_K3S2 else (3, 3))
+        want = tuple(w.shape[:2]) + ((4, 4) if kind in (FOLD_CONVT_K3S2, FOLD_CONV_K3S2) else (3, 3))
         if (tuple(dwf.shape) != want or tuple(dbf.shape) != (cout,) or dwf.dtype != torch.float32 or dbf.dtype != torch.float32 or not dwf.is_contiguous()
                 or bias is None or bn.running_mean is None or bn.weight is None or bn.num_features != cout):
             raise L.CvaeError(f"fold_bn_conv_bwd: kind {kind}, weight {tuple(w.shape)}: gradients {tuple(dwf.shape)} / {tuple(dbf.shape)} (fp32 {want} / ({cout},) "

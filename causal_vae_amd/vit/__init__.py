@@ -1,6 +1,9 @@
 """ViT-VAE inference (the reference's ViTVAE, vessel_analysis/00_core/vit_backbone.py:50-199 and latent_translator/models.py), eval mode only:
 ViTVAEEncoder: image -> (mu, log_var) / CLS features; ViTVAE: the same plus decode / forward / reconstruct; CausalViTVAE (vessel_analysis/00_core/models.py:181-307): that backbone
 between the fused adapter heads of the (x, m, t) -> z -> (z, m) -> x model; CausalViTVAE.train_adapters / forward_train train those heads on the frozen
-eval-mode backbone (the reference's vae.train() also trains the backbone and runs its dropout and BatchNorm2d in training mode: here it stays frozen)."""
-from .models import ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, resize_pos_embedding, fit_latent   # noqa: F401
+eval-mode backbone (the reference's vae.train() also trains the backbone and runs its dropout and BatchNorm2d in training mode: here it stays frozen, or
+learns in eval mode: train_decoder / train_transformer / train_stem).  ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae: the reference's ViTVAE
+training loop (latent_translator/engine.py:6-36) end to end, in that eval-mode regime."""
+from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, resize_pos_embedding, fit_latent,   # noqa: F401
+                     vit_vae_loss, train_vit_vae)
 from .causal import AdapterMLP, CausalViTVAE   # noqa: F401

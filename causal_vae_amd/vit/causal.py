@@ -94,12 +94,13 @@ class CausalViTVAE(nn.Module):
     _adapters_only = False
     _train_decoder = False
     _train_transformer = False
+    _train_stem = False
 
     def head_parameters(self):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self, decoder=False, transformer=False):
+    def train_adapters(self, decoder=False, transformer=False, stem=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
         heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
         a default call after a decoder=True one switches the decoder's gradients off again).
@@ -107,13 +108,20 @@ class CausalViTVAE(nn.Module):
         its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters.
         transformer=True: the backbone's transformer learns too (backbone.train_transformer(): pos_embedding, cls_token, transformer, to_latent; eval mode, no
         dropout; the conv stem stays frozen).  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
-        backbone's (mu, log_var), so no gradient ever reaches them.  Returns head plus transformer parameters (plus the decoder's with decoder=True)."""
+        backbone's (mu, log_var), so no gradient ever reaches them.  Returns head plus transformer parameters (plus the decoder's with decoder=True).
+        stem=True (needs transformer=True): the backbone's conv stem learns too (backbone.train_stem(): eval-mode BatchNorm2d on its running statistics;
+        DESIGN §17), the whole backbone is then fine-tuned as vessel_analysis/01_train/train.py does; its parameters are returned too."""
+        if stem and not transformer:
+            raise CvaeError("CausalViTVAE.train_adapters: stem=True needs transformer=True (the stem's gradient arrives through the transformer)")
         self.backbone.requires_grad_(False)
         self.backbone.freeze_decoder()
         self.backbone.freeze_transformer()
-        self._adapters_only, self._train_decoder, self._train_transformer = True, bool(decoder), bool(transformer)
+        self.backbone.freeze_stem()
+        self._adapters_only, self._train_decoder, self._train_transformer, self._train_stem = True, bool(decoder), bool(transformer), bool(stem)
         self.train()
         params = self.head_parameters()
+        if stem:
+            params += self.backbone.train_stem()
         if transformer:
             params += self.backbone.train_transformer(heads=False)
         if decoder:
@@ -135,7 +143,8 @@ class CausalViTVAE(nn.Module):
         the backbone's decoder parameters may ask for gradients, and backward accumulates them (eval-mode decoder); after
         train_adapters(transformer=True) cls_features_with_grad takes cls_features' place and the transformer's parameters learn through enc_adapter's cls_out
         panel."""
-        roots = (("decoder_input", "decoder") if self._train_decoder else ()) + (self.backbone._TRANSFORMER_ROOTS if self._train_transformer else ())
+        roots = ((("decoder_input", "decoder") if self._train_decoder else ()) + (self.backbone._TRANSFORMER_ROOTS if self._train_transformer else ())
+                 + (("stem",) if self._train_stem else ()))
         live = [k for k, p in self.backbone.named_parameters() if p.requires_grad and k.split(".")[0] not in roots]
         if self.backbone.training or live:
             raise RuntimeError("CausalViTVAE.forward_train trains the adapter heads on a frozen eval-mode backbone: call model.train_adapters() first "

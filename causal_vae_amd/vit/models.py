@@ -25,6 +25,10 @@ draws the reference's weights and the state_dict key sets are equal.  decode, pe
 decode_with_grad / decode_vjp add the gradient of that image with respect to z through the FROZEN eval-mode decoder: the forward issues
 decode's launches (the fold also writes the backward matrices) and keeps five gate activations and the three ResBlock inner activations; the backward is
 cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
+Training, all in eval mode (no dropout, BatchNorm2d on its running statistics): train_decoder, train_transformer (§16) and train_stem (§17: the
+stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then per layer cvae_conv_wgrad and cvae_conv_down_bwd_data with the LeakyReLU
+derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
+are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
 """
 from collections import namedtuple
 
@@ -93,13 +97,22 @@ class ViTVAEEncoder(nn.Module):
             raise CvaeError(f"ViTVAEEncoder expects a float32 [B, 1, {self.img_height}, {self.img_width}] batch, got {tuple(x.shape)} {x.dtype}")
         require_gpu(x, self.cls_token)
 
-    def _stem_cl(self, x):
+    def _stem_layers(self):
+        """The stem's five (conv, BatchNorm2d) pairs."""
         mods = list(self.stem)
-        table = [(mods[i].weight, ops.FOLD_CONV_K3S2, mods[i].bias, mods[i + 1]) for i in range(0, len(mods), 3)]
-        folded = ops.fold_bn_conv(table)
+        return [(mods[i], mods[i + 1]) for i in range(0, len(mods), 3)]
+
+    def _stem_cl(self, x, keep=None):
+        """keep (a dict, the stem's backward): receives `x` (the first conv's operand: the image as it is read), `ys` (the five layer outputs: each the next
+        layer's input, its weight-gradient operand and its gate) and `k4` (the folded k4 weights).  The launches do not depend on it."""
+        folded = ops.fold_bn_conv([(conv.weight, ops.FOLD_CONV_K3S2, conv.bias, bn) for conv, bn in self._stem_layers()])
         h, first_dtype = hl._image_cl(x, self.compute_dtype)
+        if keep is not None:
+            keep["x"], keep["ys"], keep["k4"] = h, [], [w for w, _b in folded]
         for j, (w, b) in enumerate(folded):
             h = ops.ConvDown.apply(h, w, b, 2, "leaky001", False, False, None, first_dtype if j == 0 else None)
+            if keep is not None:
+                keep["ys"].append(h)
         return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
 
     def _block(self, blk, tokens, cls_only):
@@ -157,7 +170,58 @@ class ViTVAEEncoder(nn.Module):
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
 
-    # ---- training the transformer (eval mode, frozen stem) -------------------------------------------------------------
+    # ---- training the conv stem (eval mode: BatchNorm2d on its running statistics) -------------------------------------
+    _stem_grads = False             # train_stem(): cls_features_with_grad / encode_with_grad accumulate the stem's gradients
+
+    def _stem_named(self):
+        """(name, parameter) of the 20 stem tensors (conv weight and bias, BatchNorm2d weight and bias per layer) in named_parameters order."""
+        return [(f"stem.{k}", p) for k, p in self.stem.named_parameters()]
+
+    def freeze_stem(self):
+        """requires_grad_(False) on everything train_stem() switched on: the stem is a frozen feature extractor again and its activations are not kept."""
+        self.stem.requires_grad_(False)
+        self._stem_grads = False
+        return self
+
+    def train_stem(self):
+        """The counterpart of freeze_stem(): requires_grad_(True) on the stem's 20 tensors, and cls_features_with_grad / encode_with_grad from now on accumulate
+        their `.grad`.  Returns those parameters in named_parameters order.  The model stays in EVAL mode: BatchNorm2d normalises with its running
+        statistics, which are not updated; its weight and bias learn, and so do the conv weights and biases, through the fold.  (The reference's vae.train() uses
+        batch statistics: the one difference of this path, as in train_decoder().)  Independent of train_transformer(): alone it gives stem gradients only — at
+        the cost of the whole backward all the same: the gradient reaches the stem through the transformer, and the one backward chain computes the
+        transformer's weight gradients on its way and drops them."""
+        if self.training:
+            raise RuntimeError("ViTVAEEncoder.train_stem: put the model in eval mode first (model.eval()): the stem trains on eval-mode BatchNorm2d "
+                               "(running statistics); batch statistics are not implemented")
+        self.stem.requires_grad_(True)
+        self._stem_grads = True
+        return [p for _k, p in self._stem_named()]
+
+    @torch.no_grad()
+    def _stem_backward(self, kept, g, collect=None):
+        """{state_dict name: gradient} of the 20 stem tensors from g = the gradient of the LAST layer's pre-activation [B, n, 256] (vit_tokens_bwd with the stem
+        output as its gate), compute dtype.  Per layer, last to first: the folded k4 weight's and bias's gradient from (g_j, the layer's input) at once, then
+        g_{j-1} = conv_down_bwd_data(g_j) with leaky001' of the layer's input in the epilogue: no activation-backward launch.  Then ONE launch back through the
+        fold.  The image gets no gradient.  collect: receives `stem_g` = [g_0 .. g_4]."""
+        ys, k4, dt = kept["ys"], kept["k4"], self.compute_dtype
+        g = g.view(ys[-1].shape)
+        folded, gs = [None] * len(ys), [None] * len(ys)
+        for j in reversed(range(len(ys))):
+            gs[j] = g
+            folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept["x"], 2, k4[j].shape, want_sbias=True)
+            if j:
+                g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), ys[j - 1], "leaky001")
+        if collect is not None:
+            collect["stem_g"] = gs
+        layers = self._stem_layers()
+        quads = ops.fold_bn_conv_bwd([(conv.weight, ops.FOLD_CONV_K3S2, conv.bias, bn) + tuple(folded[j]) for j, (conv, bn) in enumerate(layers)])
+        grads = {}
+        for j, quad in enumerate(quads):
+            for name, d in zip((f"stem.{3 * j}.weight", f"stem.{3 * j}.bias", f"stem.{3 * j + 1}.weight", f"stem.{3 * j + 1}.bias"), quad):
+                grads[name] = d
+        return grads
+
+    # ---- training the transformer (eval mode; DESIGN §16) -----------------------------------------------------------------------------
     _transformer_grads = False      # train_transformer(): cls_features_with_grad / encode_with_grad accumulate the transformer's gradients
     _TRANSFORMER_ROOTS = ("pos_embedding", "cls_token", "transformer", "to_latent", "fc_mu", "fc_var")
 
@@ -178,15 +242,16 @@ class ViTVAEEncoder(nn.Module):
         """The counterpart of freeze_transformer(): requires_grad_(True) on transformer.*, pos_embedding, cls_token, to_latent.*, fc_mu.* and fc_var.*
         (heads=False: without fc_mu / fc_var, for a consumer of the cls features that never reaches them; they are frozen), and
         cls_features_with_grad / encode_with_grad from now on accumulate their `.grad`.  Returns those parameters in named_parameters order.  The model stays in
-        EVAL mode (no dropout: the one difference from the reference's vae.train(), next to the stem) and the conv stem stays a frozen feature extractor: a stem
-        parameter that asks for a gradient is an error here, not a gradient that silently stays None."""
+        EVAL mode (no dropout: the one difference from the reference's vae.train(), next to BatchNorm2d's running statistics) and, unless train_stem() was
+        called, the conv stem stays a frozen feature extractor: a stem parameter that asks for a gradient is then an error here, not a gradient that silently
+        stays None."""
         if self.training:
             raise RuntimeError("ViTVAEEncoder.train_transformer: put the model in eval mode first (model.eval()): the transformer trains without dropout, "
                                "on an eval-mode stem")
-        live = [f"stem.{k}" for k, p in self.stem.named_parameters() if p.requires_grad]
-        if live:
+        live = [k for k, p in self._stem_named() if p.requires_grad]
+        if live and not self._stem_grads:
             raise RuntimeError(f"ViTVAEEncoder.train_transformer: the stem is a frozen feature extractor, but these parameters ask for a gradient: {live} "
-                               "(model.stem.requires_grad_(False))")
+                               "(model.stem.requires_grad_(False), or model.train_stem() for their gradients)")
         self.freeze_transformer()
         for _k, p in self._transformer_named(heads):
             p.requires_grad_(True)
@@ -194,17 +259,25 @@ class ViTVAEEncoder(nn.Module):
         return [p for _k, p in self._transformer_named(heads)]
 
     def cls_features_with_grad(self, x, collect=None):
-        """cls_features(x) (the same launches up to two extra outputs, the same bits) as a differentiable function of the transformer's parameters: ONE
-        autograd.Function over tokens, blocks and to_latent whose backward accumulates `.grad` on pos_embedding, cls_token, transformer.* and to_latent.*.
-        x gets no gradient (the stem is frozen).  Needs train_transformer(); when autograd is off or no parameter asks, this is cls_features and nothing is saved.
-        collect (a dict, for tests and for the stem's later backward): the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype."""
-        named = self._transformer_named(heads=False)
-        if not (torch.is_grad_enabled() and any(p.requires_grad for _k, p in named)):
+        """cls_features(x) (the same launches up to two extra outputs, the same bits) as a differentiable function of the transformer's and the stem's
+        parameters: ONE autograd.Function over stem, tokens, blocks and to_latent whose backward accumulates `.grad` on pos_embedding, cls_token, transformer.* and
+        to_latent.* (after train_transformer()) and on stem.* (after train_stem(): the five layer outputs are kept; otherwise nothing of the stem is).
+        x gets no gradient.  When autograd is off or no parameter asks, this is cls_features and nothing is saved; a parameter that asks without its train_*()
+        call is an error, not a gradient that silently stays None.
+        collect (a dict, for tests): the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype, and with a live stem `stem_g`, the
+        gradients of the five pre-activations (`dstem` then costs one more token launch: the stem's backward starts from its gated form)."""
+        named, stem = self._transformer_named(heads=False), self._stem_named()
+        live_t, live_s = any(p.requires_grad for _k, p in named), any(p.requires_grad for _k, p in stem)
+        if not (torch.is_grad_enabled() and (live_t or live_s)):
             return self._cls_features(x)
-        if not self._transformer_grads:
+        if live_t and not self._transformer_grads:
             raise CvaeError("ViTVAEEncoder.cls_features_with_grad: transformer parameters ask for a gradient but train_transformer() was not called "
                             "(or call freeze_transformer())")
+        if live_s and not self._stem_grads:
+            raise CvaeError("ViTVAEEncoder.cls_features_with_grad: stem parameters ask for a gradient but train_stem() was not called (or call freeze_stem())")
         self._check(x)
+        if live_s:
+            named = named + stem
         return _ClsFeaturesWithGrad.apply(x, self, collect, tuple(k for k, _p in named), *[p for _k, p in named])
 
     def encode_with_grad(self, x, collect=None):
@@ -273,9 +346,11 @@ class ViTVAEEncoder(nn.Module):
         return Gin
 
     @torch.no_grad()
-    def _train_walk(self, x):
-        """_cls_features' launches in their training forms -> (cls features [B, 256] fp32, what _train_backward reads)."""
-        stem = self._stem_cl(x)
+    def _train_walk(self, x, keep_stem=False):
+        """_cls_features' launches in their training forms -> (cls features [B, 256] fp32, what _train_backward reads).  keep_stem: the stem's layer outputs and
+        folded weights travel along (the same launches)."""
+        kept = {} if keep_stem else None
+        stem = self._stem_cl(x, kept)
         tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
         B, N, _D = tokens.shape
         steps = []
@@ -284,12 +359,13 @@ class ViTVAEEncoder(nn.Module):
             steps.append(s)
         cls = tokens if tokens.dim() == 2 else tokens[:, 0]
         out = ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
-        return out, (steps, cls, stem.dtype, B, N)
+        return out, (steps, cls, stem.dtype, B, N, kept)
 
     @torch.no_grad()
-    def _train_backward(self, saved, g):
-        """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features."""
-        steps, cls, stem_dtype, B, N = saved
+    def _train_backward(self, saved, g, collect=None):
+        """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features;
+        when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`)."""
+        steps, cls, stem_dtype, B, N, kept = saved
         D, grads = self.embed_dim, {}
         if steps[-1]["q"] is not None:                                  # the forward ran a CLS-only last block: the stream gradient starts as its [B, 256] rows
             G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
@@ -298,18 +374,24 @@ class ViTVAEEncoder(nn.Module):
             _dx, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps, dx=G.view(B, N, D)[:, 0])
         for i in reversed(range(self.depth)):
             G = self._block_backward(self.transformer[i], f"transformer.{i}.", steps[i], G, grads)
-        dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
+        if kept is None:
+            dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
+        else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
+            if collect is not None:
+                grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)[2]
+            dpos, dcls, g_last = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype, gate=kept["ys"][-1].view(B, N - 1, D), gate_act="leaky001")
+            grads.update(self._stem_backward(kept, g_last, collect))
         grads["pos_embedding"], grads["cls_token"] = dpos.view(1, N, D), dcls.view(1, 1, D)
         return grads
 
 
 class _ClsFeaturesWithGrad(torch.autograd.Function):
-    """ViTVAEEncoder.cls_features_with_grad: the transformer's parameters are inputs, so autograd accumulates their gradients, zero_grad works and a parameter
-    rewritten between forward and backward is an error.  x gets no gradient: the stem is a frozen feature extractor (its backward starts from `dstem`)."""
+    """ViTVAEEncoder.cls_features_with_grad: the transformer's parameters (and, after train_stem(), the stem's behind them) are inputs, so autograd accumulates
+    their gradients, zero_grad works and a parameter rewritten between forward and backward is an error.  x gets no gradient."""
 
     @staticmethod
     def forward(ctx, x, model, collect, names, *params):
-        out, saved = model._train_walk(x)
+        out, saved = model._train_walk(x, keep_stem=any(k.startswith("stem.") for k in names))
         ctx.model, ctx.saved, ctx.collect, ctx.names = model, saved, collect, names      # activations of this call: private to the node, freed with it
         ctx.save_for_backward(*params)
         ctx.set_materialize_grads(False)
@@ -321,7 +403,7 @@ class _ClsFeaturesWithGrad(torch.autograd.Function):
         params = ctx.saved_tensors                                     # raises if a parameter was modified in place since the forward
         if g is None:
             return (None,) * (4 + len(params))
-        grads = ctx.model._train_backward(ctx.saved, g.contiguous())
+        grads = ctx.model._train_backward(ctx.saved, g.contiguous(), ctx.collect)
         if ctx.collect is not None:
             ctx.collect["dstem"] = grads["dstem"]
         return (None, None, None, None) + tuple(grads[k].view(p.shape) if need else None for k, p, need in zip(ctx.names, params, ctx.needs_input_grad[4:]))
@@ -542,6 +624,25 @@ class ViTVAE(ViTVAEEncoder):
         _image, saved = self._decode_walk(z.detach(), True)
         return self._decode_backward(saved, grad_image.contiguous())
 
+    # ---- training the whole model (eval mode) --------------------------------------------------------------------------
+    def train_all(self):
+        """train_stem() + train_transformer() + train_decoder(): every parameter asks for a gradient and forward_train's graph reaches every one of them.
+        Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae)."""
+        self.train_stem()
+        self.train_transformer()
+        self.train_decoder()
+        return list(self.parameters())
+
+    def forward_train(self, x, eps=None):
+        """(recons, x, mu, log_var) as forward(), on the autograd graph: encode_with_grad -> ops.Reparameterize -> decode_with_grad.  eps [B, latent_dim] fp32, or
+        None: drawn with torch.randn on x's device.  For the same eps the values are those of the eval path, bit for bit (the same launches)."""
+        mu, log_var = self.encode_with_grad(x)
+        if eps is None:
+            eps = torch.randn(mu.shape, dtype=torch.float32, device=mu.device)
+        elif tuple(eps.shape) != tuple(mu.shape) or eps.dtype != torch.float32:
+            raise CvaeError(f"ViTVAE.forward_train: eps must be a float32 {tuple(mu.shape)} matrix, got {tuple(eps.shape)} {eps.dtype}")
+        return self.decode_with_grad(ops.Reparameterize.apply(mu, log_var, eps)), x, mu, log_var
+
     def reparameterize(self, mu, log_var):
         """vit_backbone.py:181-184: mu + randn_like(std) * std on torch's generator."""
         std = torch.exp(0.5 * log_var)
@@ -602,6 +703,38 @@ def fit_latent(model, x, z0, steps, lr, loss="sse"):
         opt.step()
         losses.append(value.detach())
     return z.detach(), [float(v) for v in torch.stack(losses).cpu()] if losses else []
+
+
+def vit_vae_loss(recons, x, mu, log_var, beta=1.0):
+    """The loss of the reference's ViTVAE loop (latent_translator/engine.py:25-27): mse_loss(recons, x, mean) + beta * (-0.5 * mean(1 + log_var - mu^2 -
+    exp(log_var))).  The image term is ops.sse / numel on the GPU (one reduction, the gradient from one launch); the [B, latent] arithmetic stays in torch.
+    Host tensors (a loss of stored arrays, the CPU tests) take torch's mse_loss: the expression itself, no kernel involved."""
+    recon = ops.sse(recons, x) / x.numel() if recons.is_cuda else F.mse_loss(recons, x, reduction="mean")
+    kld = -0.5 * torch.mean(1 + log_var - mu.pow(2) - log_var.exp())
+    return recon + beta * kld
+
+
+def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0):
+    """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature: per batch["x"], zero_grad, model.forward_train, vit_vae_loss,
+    backward, optimizer.step().  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval mode, so there
+    is no dropout and every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state); all
+    parameters learn (model.train_all() is called, so an optimizer built over model.parameters() fits).  Returns the per-epoch mean losses as a list of floats
+    (sample-weighted, read from the device once per epoch)."""
+    model.eval()
+    model.train_all()
+    history = []
+    for _ep in range(int(epochs)):
+        total, n = [], 0
+        for batch in loader:
+            x = batch["x"].to(device)
+            optimizer.zero_grad()
+            loss = vit_vae_loss(*model.forward_train(x), beta=beta)
+            loss.backward()
+            optimizer.step()
+            total.append(loss.detach() * x.shape[0])
+            n += x.shape[0]
+        history.append(float(torch.stack(total).sum().cpu()) / max(n, 1) if total else 0.0)
+    return history
 
 
 def resize_pos_embedding(pos, src_grid, dst_grid):

@@ -119,6 +119,15 @@ int cvae_conv_up(const void* S, const void* w, const float* bias, const void* ma
                  int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
                  int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, int act,
                  void* workspace, size_t workspace_bytes, int upfull, int xpair, int64_t c1_walk_units, void* stream);
+/* The input gradient of cvae_conv_down (2D, k4/s2/p1) with the derivative of the PRODUCING activation in its epilogue:
+ *   dx = scatter(g, w) * act'(gate), the multiplication on the fp32 accumulator before the one rounding to `dtype`; gate (NULL with CVAE_ACT_NONE) of dx's
+ *   shape and dtype; act'(gate) = gate > 0 ? 1 : slope of gate_act (CVAE_ACT_NONE / RELU / LEAKY02 / LEAKY001), read off the activation's OUTPUT.
+ * g [B][sh][sw][Cs], dx [B][lh][lw][Cl], w the packed `up` weight of cvae_conv_pack_weight(for_up = 1).  cvae_conv_up's tiles, dispatch, workspace and per-call
+ * form overrides (upfull, xpair): NONE and RELU ARE cvae_conv_up launches (without / with `mask`: the same bits); a LeakyReLU slope runs second instances of
+ * the same kernel text that multiply where the first ones zero (the data kernel, the split-K finish, the whole-K parity kernel).  nd = 2, Cs % 16 == 0 and
+ * Cl % 32 == 0, else CVAE_E_UNSUPPORTED (nothing is launched).  The ViT-VAE stem's backward: one launch per layer, no cvae_act_bwd pass. */
+int cvae_conv_down_bwd_data(const void* g, const void* w, const void* gate, void* dx, int64_t B, int64_t sh, int64_t sw, int64_t Cs, int64_t lh, int64_t lw,
+                            int64_t Cl, int nd, int dtype, int gate_act, void* workspace, size_t workspace_bytes, int upfull, int xpair, void* stream);
 /* The first conv of the encoder (Cl == 1) with the IMAGE read in the dtype it is stored in (l_dtype) while S is written in the compute
  * dtype (`dtype`): the fp32 input volume of a bf16 model feeds the kernels directly — no cast pass, no bf16 copy of the batch
  * (causal_cascade/models.py:13: nn.Conv2d(img_channels, 32, 4, 2, 1) on the fp32 batch).  cvae_conv_down_image = cvae_conv_down with
@@ -266,7 +275,8 @@ int cvae_fold_bn_conv(int count, const float* const* w, const int* kind, const i
 /* The way back through the fold, for `count` (1..16) layers in ONE launch: from the gradient of the FOLDED weight dwf and bias dbf [Cout] to the gradients of
  * the module's parameters, with s = gamma rsqrt(var + eps) per BatchNorm channel (running statistics: constants):
  *   dw = s dwf,  db = s dbf,  dgamma = rsqrt(var + eps) (sum dwf w + dbf (bias - mean)),  dbeta = dbf.
- * kind CVAE_FOLD_CONVT_K3S2: dwf is the gradient of the k4 weight [Cin][Cout][4][4], of which the 3 x 3 taps are read; CVAE_FOLD_CONV_K3S1: dwf [Cout][Cin][3][3];
+ * kind CVAE_FOLD_CONVT_K3S2: dwf is the gradient of the k4 weight [Cin][Cout][4][4], of which the 3 x 3 taps are read; CVAE_FOLD_CONV_K3S2 (the ViT-VAE stem): the
+ * gradient of the k4 weight [Cout][Cin][4][4] as cvae_conv_wgrad writes it, read the same way (the fourth row and column are ignored); CVAE_FOLD_CONV_K3S1: dwf [Cout][Cin][3][3];
  * CVAE_FOLD_CONVT_K3S2_SUBPIXEL: dwf [Cin][Cout][3][3] — both as cvae_conv_s1_wgrad writes them.  dw in w's layout.  One workgroup per (layer, channel): a
  * thread's ordered chain, then a fixed tree.  bias entries may be NULL (zeros; db then too); gamma NULL: no BatchNorm (dw = dwf, db = dbf, nothing else). */
 int cvae_fold_bn_conv_bwd(int count, const float* const* w, const int* kind, const int64_t* dims, const float* const* bias, const float* const* gamma,
@@ -330,7 +340,10 @@ int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_
  *   cvae_layernorm256_bwd       dx = rstd (gamma g - mean(gamma g) - xh mean(gamma g xh)) written or (accumulate != 0) added to dx (row stride dx_stride);
  *                               statistics recomputed two-pass from the saved fp32 input x (nothing but x is saved); dgamma = sum_rows g xh, dbeta = sum_rows g
  *                               over slabs of 32 rows, then in slab order
- *   cvae_vit_tokens_bwd         dpos[i] = sum_b dtokens[b][i], dcls = sum_b dtokens[b][0] (b in order), dstem[b][i] = dtokens[b][1 + i] in stem_dtype */
+ *   cvae_vit_tokens_bwd         dpos[i] = sum_b dtokens[b][i], dcls = sum_b dtokens[b][0] (b in order), dstem[b][i] = dtokens[b][1 + i] in stem_dtype; with a gate
+ *                               (optional: the stem output [B][n][256] in stem_dtype, a LeakyReLU output) dstem[b][i] = dtokens[b][1 + i] * act'(gate[b][i]),
+ *                               act'(gate) = gate > 0 ? 1 : slope of gate_act, the product in fp32, then one rounding; gate NULL / CVAE_ACT_NONE: as without;
+ *                               dpos and dcls are never gated */
 int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                         int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype,
                         void* stream);
@@ -349,7 +362,8 @@ int cvae_token_gemm_wgrad(const void* g, int64_t g_stride, int g_dtype, const vo
 size_t cvae_layernorm256_bwd_workspace_bytes(int64_t rows);
 int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtype, const float* x, int64_t x_stride, const float* gamma, float* dx, int64_t dx_stride,
                           int accumulate, float* dgamma, float* dbeta, int64_t rows, float eps, void* workspace, size_t workspace_bytes, void* stream);
-int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, int64_t B, int64_t n_patches, void* stream);
+int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, const void* gate, int gate_act, int64_t B, int64_t n_patches,
+                        void* stream);
 
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order

@@ -9,7 +9,8 @@ What is imported from /root/reference (read-only, nothing is written there):
   * mnist_test/01_baseline_causal_vae/{config,models}.py -> CausalMorphVAE12, LatentDiscriminator (a8)
   * mnist_test/06_model_experiment/{config,models}.py    -> Gaussian-head CausalMorphVAE12
   * vessel_analysis/00_core/models.py: the text of ``CausalVesselVAE`` is compiled with its two unimportable imports dropped (a11)
-  * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode; encode: `python tools/make_golden.py vitvae`, decode: `... vitvae_dec`)
+  * vessel_analysis/00_core/vit_backbone.py -> ViTVAE (eval mode; encode: `python tools/make_golden.py vitvae`, decode: `... vitvae_dec`; the encoder's
+    gradients: `... vitvae_grad` (transformer side), `... vitvae_stem_grad` (the conv stem))
   * vessel_analysis/00_core/models.py: the text of ``CausalViTVAE`` is compiled around that ViTVAE (eval mode; `... causal_vitvae`)
   * vessel_analysis/01_train/train.py: only the text of ``loss_function`` is compiled (the module
     itself cannot be imported: it pulls tifffile/torchvision through ``dataset``) (a10)
@@ -404,6 +405,43 @@ def vitvae_grad_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, seed_
     print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
 
 
+def vitvae_stem_grad_case(name, B, H, W, depth, seed_model, seed_bn, seed_data, seed_cot):
+    """The STEM's gradients of ViTVAE.encode in eval mode at random init: the model, image, loss and seeds of vitvae_grad_case (loss = sum(mu g_mu) +
+    sum(log_var g_lv), one fp32 CPU backward through the reference class).  Stored: the cotangents, the gradient arriving at the stem's output (`out/dstem`,
+    NCHW, from a hook: what the restatement of the stem alone starts from; weights and image as digests: the seeds reproduce them), the fp32 gradients of the 15 small tensors (conv biases, BatchNorm weights and
+    biases) whole and rows grad_rows(Cout) of each conv weight's gradient along dimension 0."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from vit_reference import randomize_stem_bn, vit_inputs
+    (vb,) = import_from(os.path.join(REF, "vessel_analysis", "00_core"), "vit_backbone")
+    torch.manual_seed(seed_model)
+    model = vb.ViTVAE(in_channels=1, latent_dim=128, img_size=(H, W), depth=depth)
+    randomize_stem_bn(model.stem, seed_bn)
+    model.eval()
+    x = vit_inputs(B, H, W, seed_data)
+    g = torch.Generator().manual_seed(seed_cot)
+    g_mu, g_lv = torch.randn(B, 128, generator=g), torch.randn(B, 128, generator=g)
+    acts = {}
+    hook = model.stem.register_forward_hook(lambda _m, _i, o: (acts.__setitem__("stem", o.detach().clone()),
+                                                               o.register_hook(lambda gg: acts.__setitem__("dstem", gg.detach().clone()))) and None)
+    mu, log_var = model.encode(x)
+    hook.remove()
+    torch.autograd.backward([mu, log_var], [g_mu, g_lv])
+    store = {"in/seed": np.array([B, H, W, depth, seed_model, seed_bn, seed_data], dtype=np.int64), "in/seed_cot": np.array([seed_cot], dtype=np.int64)}
+    pack("sd0", {k: v for k, v in model.state_dict().items() if not k.startswith(("decoder_input.", "decoder."))}, store, full_limit=0)
+    pack("in", dict(x=x), store, full_limit=0)                    # weights and image are the seeds' draws: digests only
+    pack("in", dict(g_mu=g_mu, g_lv=g_lv), store)
+    pack("out", dict(mu=mu, log_var=log_var, dstem=acts["dstem"]), store)
+    for k, p in model.stem.named_parameters():
+        if p.dim() == 4:
+            rows = grad_rows(p.shape[0])
+            store[f"grad/stem.{k}#rows"] = np.array(rows, dtype=np.int64)
+            store[f"grad/stem.{k}"] = p.grad[rows].numpy().copy()
+        else:
+            store[f"grad/stem.{k}"] = p.grad.numpy().copy()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **store)
+    print(name, "mu[0,:3]", mu[0, :3].tolist(), "keys", len(store), "bytes", os.path.getsize(os.path.join(OUT, name + ".npz")))
+
+
 def vitvae_dec_case(name, B, H, W, depth, seed_model, seed_bn, seed_dec_bn, seed_z, whole):
     """ViTVAE.decode in eval mode at random init.  The weights are the seed's draws (digests only: the product class draws the same); the stem BatchNorms
     are randomised as in vitvae_case, ALL decoder BatchNorm2d layers (the ones nested in the ResBlocks included) from a further seed
@@ -506,6 +544,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "vitvae_grad":
         vitvae_grad_case("vitvae_enc_grad_64x96", 2, 64, 96, 2, 42, 4242, 1303, 1304)      # 7 tokens
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "vitvae_stem_grad":
+        vitvae_stem_grad_case("vitvae_stem_grad_64x96", 2, 64, 96, 2, 42, 4242, 1303, 1304)  # vitvae_grad's model, image and cotangents
         return
     if len(sys.argv) > 1 and sys.argv[1] == "vessel2d":
         vessel2d_case("vessel2d_b4")
