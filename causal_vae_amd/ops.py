@@ -2006,54 +2006,72 @@ def layernorm256(x, weight, bias, eps, out_dtype):
     return y
 
 
-def token_gemm(x, weight, bias, epilogue=None, resid=None, out=None):
-    """epi(x @ weight.T + bias) (cvae_token_gemm).  x [M, K] fp32 or bf16 (the arithmetic mode), weight [N, K] / bias [N] the fp32 nn.Linear tensors.
-    epilogue None / "gelu": result in x's dtype; "residual": fp32 resid + (x W^T + b), written to `out` (default: resid itself, in place)."""
+def _token_gemm(what, x, weight, bias, epilogue, resid, out, want_pre):
+    """The one body of token_gemm and token_gemm_gelu_train (`what`: the caller's name, for the error text) -> (result, pre-activation or None)."""
     L.require_gpu(x, weight, bias, resid, out)
-    _forward_only("token_gemm", x, weight, bias, resid)
-    _rows2d(x, "token_gemm")
+    _forward_only(what, x, weight, bias, resid)
+    _rows2d(x, what)
     M, K = x.shape
     N = weight.shape[0]
     if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in GEMM_EPI:
-        raise L.CvaeError(f"token_gemm: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r}")
+        raise L.CvaeError(f"{what}: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r}")
     if epilogue == "residual":
         if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm resid", N).shape[0] != M:
             raise L.CvaeError("token_gemm: the residual epilogue needs a fp32 [M, N] residual")
         out = resid if out is None else out
     elif out is None:
         out = _empty((M, N), x.dtype, x)
-    _rows2d(out, "token_gemm out", N)
-    check(lib.cvae_token_gemm(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out),
-                              out.stride(0), M, K, N, GEMM_EPI[epilogue], L.dtype_code(x.dtype), stream()), "token_gemm")
-    return out
+    _rows2d(out, "token_gemm out", N)                     # resid and out come from token_gemm alone: the training form passes neither
+    w, b, dt = weight.detach().contiguous(), bias.detach(), L.dtype_code(x.dtype)
+    if not want_pre:
+        check(lib.cvae_token_gemm(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), M, K, N,
+                                  GEMM_EPI[epilogue], dt, stream()), "token_gemm")
+        return out, None
+    pre = _empty((M, N), x.dtype, x)
+    check(lib.cvae_token_gemm_gelu_train(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(pre), N, ptr(out), out.stride(0), M, K, N, dt, stream()), "token_gemm_gelu_train")
+    return out, pre
+
+
+def token_gemm(x, weight, bias, epilogue=None, resid=None, out=None):
+    """epi(x @ weight.T + bias) (cvae_token_gemm).  x [M, K] fp32 or bf16 (the arithmetic mode), weight [N, K] / bias [N] the fp32 nn.Linear tensors.
+    epilogue None / "gelu": result in x's dtype; "residual": fp32 resid + (x W^T + b), written to `out` (default: resid itself, in place)."""
+    return _token_gemm("token_gemm", x, weight, bias, epilogue, resid, out, False)[0]
+
+
+def _mhsa_views(what, B, rows, *ts):
+    for t, n in zip(ts, rows):
+        sh = t.shape
+        if len(sh) != 3 or sh[2] != 256 or t.stride(2) != 1 or t.dtype != ts[0].dtype or sh[0] != B or sh[1] < n:
+            raise L.CvaeError(f"{what}: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
+
+
+def _mhsa_fwd(what, q, k, v, n_query_rows, want_lse):
+    """The one body of mhsa and mhsa_train (`what`: the caller's name, for the error text) -> (out, lse or None)."""
+    L.require_gpu(q, k, v)
+    _forward_only(what, q, k, v)
+    B, N = k.shape[0], k.shape[1]
+    nq = N if n_query_rows is None else int(n_query_rows)
+    _mhsa_views(what, B, (nq, N, N), q, k, v)
+    if v.shape[1] != N or not 1 <= nq <= N:
+        raise L.CvaeError(f"{what}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, n_query_rows {nq}")
+    out = _empty((B, nq, 256), q.dtype, q)
+    tail = (q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq, L.dtype_code(q.dtype), stream())
+    if not want_lse:
+        check(lib.cvae_mhsa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), *tail), "mhsa_fwd")
+        return out, None
+    lse = _empty((B, 8, nq), torch.float32, q)
+    check(lib.cvae_mhsa_fwd_train(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail), "mhsa_fwd_train")
+    return out, lse
 
 
 def mhsa(q, k, v, n_query_rows=None):
     """Fused 8-head self-attention of width 256 (cvae_mhsa_fwd): q [B, >= n_query_rows, 256], k / v [B, N, 256] — views with unit column stride, e.g. the
     three column panels of the packed in-projection output [B, N, 768].  The first n_query_rows tokens are the queries (default: all N).
     Returns [B, n_query_rows, 256] in the operands' dtype."""
-    L.require_gpu(q, k, v)
-    _forward_only("mhsa", q, k, v)
-    B, N = k.shape[0], k.shape[1]
-    nq = N if n_query_rows is None else int(n_query_rows)
-    for t in (q, k, v):
-        if t.dim() != 3 or t.shape[2] != 256 or t.stride(2) != 1 or t.dtype != q.dtype or t.shape[0] != B:
-            raise L.CvaeError(f"mhsa: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
-    if v.shape[1] != N or not 1 <= nq <= N or q.shape[1] < nq:
-        raise L.CvaeError(f"mhsa: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, n_query_rows {nq}")
-    out = _empty((B, nq, 256), q.dtype, q)
-    check(lib.cvae_mhsa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq,
-                            L.dtype_code(q.dtype), stream()), "mhsa_fwd")
-    return out
+    return _mhsa_fwd("mhsa", q, k, v, n_query_rows, False)[0]
 
 
 # ---- ViT-VAE encoder, training the transformer (csrc/vit.hip, DESIGN §16): the backward building blocks, on raw tensors as the ones above ---------
-def _mhsa_views(what, B, rows, *ts):
-    for t, n in zip(ts, rows):
-        if t.dim() != 3 or t.shape[2] != 256 or t.stride(2) != 1 or t.dtype != ts[0].dtype or t.shape[0] != B or t.shape[1] < n:
-            raise L.CvaeError(f"{what}: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
-
-
 def _overlap(a, b):
     """do two [B, tokens, 256] views with unit column stride share an element?  Panels of one packed buffer interleave: same storage, the same row and batch
     strides and column ranges that meet; anything else is compared by its address range."""
@@ -2070,17 +2088,7 @@ def _overlap(a, b):
 
 def mhsa_train(q, k, v, n_query_rows=None):
     """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train)."""
-    L.require_gpu(q, k, v)
-    _forward_only("mhsa_train", q, k, v)
-    B, N = k.shape[0], k.shape[1]
-    nq = N if n_query_rows is None else int(n_query_rows)
-    if not 1 <= nq <= N or v.shape[1] != N:
-        raise L.CvaeError(f"mhsa_train: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, n_query_rows {nq}")
-    _mhsa_views("mhsa_train", B, (nq, N, N), q, k, v)
-    out, lse = _empty((B, nq, 256), q.dtype, q), _empty((B, 8, nq), torch.float32, q)
-    check(lib.cvae_mhsa_fwd_train(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0), v.stride(0), B, N, nq,
-                                  L.dtype_code(q.dtype), stream()), "mhsa_fwd_train")
-    return out, lse
+    return _mhsa_fwd("mhsa_train", q, k, v, n_query_rows, True)
 
 
 def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv):
@@ -2106,17 +2114,7 @@ def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv):
 
 def token_gemm_gelu_train(x, weight, bias):
     """(gelu(x W^T + b), x W^T + b), both in x's dtype: token_gemm's "gelu" output, bit for bit, and the pre-activation (cvae_token_gemm_gelu_train)."""
-    L.require_gpu(x, weight, bias)
-    _forward_only("token_gemm_gelu_train", x, weight, bias)
-    _rows2d(x, "token_gemm_gelu_train")
-    M, K = x.shape
-    N = weight.shape[0]
-    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32:
-        raise L.CvaeError(f"token_gemm_gelu_train: x {tuple(x.shape)}, weight {tuple(weight.shape)}")
-    y, pre = _empty((M, N), x.dtype, x), _empty((M, N), x.dtype, x)
-    check(lib.cvae_token_gemm_gelu_train(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(pre), N, ptr(y), N, M, K, N,
-                                         L.dtype_code(x.dtype), stream()), "token_gemm_gelu_train")
-    return y, pre
+    return _token_gemm("token_gemm_gelu_train", x, weight, bias, "gelu", None, None, True)
 
 
 def _gemm_mode(what, g, mode):

@@ -10,8 +10,11 @@ the arithmetic runs in libcvae_hip.so:
   tokens      cvae_vit_tokens: CLS + patches + position embedding -> fp32 residual stream
   block       cvae_layernorm256, cvae_token_gemm (packed QKV), cvae_mhsa_fwd, cvae_token_gemm (+ residual), cvae_layernorm256,
               cvae_token_gemm (GELU), cvae_token_gemm (+ residual): 7 launches
-  last block  encode reads x[:, 0] only: K and V of all tokens, everything else for the CLS row alone (n_query_rows = 1)
-ViTVAEEncoder stops there (encode only; it carries no decoder parameters).
+  last block  encode reads x[:, 0] only: K and V of all tokens (one GEMM), the CLS query (one more), everything else for the CLS row alone
+              (n_query_rows = 1): 8 launches
+ViTVAEEncoder stops there (encode only; it carries no decoder parameters).  _walk(x, save) is that sequence, once: save=False is inference (cls_features, encode);
+save=True is the training forward (cls_features_with_grad, encode_with_grad): the same calls with attention and the GELU GEMM in their training forms, the residual
+GEMMs writing fresh tensors, and what the backward reads kept in named records (_BlockStep per block, _Walk, _StemKept).
 
 ViTVAE(ViTVAEEncoder) adds the decoder half (vit_backbone.py:115-156, 181-199): decoder_input and decoder are built AFTER the encoder's modules, in the
 reference's order and with its attribute tree (decoder.{0,1,4,5,8,9,12,13,15,16,18}, decoder.{3,7,11}.conv.{0,1,3,4}), so `torch.manual_seed(s); ViTVAE(...)`
@@ -42,6 +45,17 @@ from .. import ops
 from .._lib import CvaeError, require_gpu
 
 STEM_CHANNELS = (32, 64, 128, 256, 256)
+# What ViTVAEEncoder._walk(save=True) keeps for _walk_backward.
+# _StemKept (only when the stem trains): x (the image as the first conv reads it: its weight-gradient operand), ys (the five layer outputs: each the next
+# layer's input, its weight-gradient operand and its gate), k4 (the folded k4 weights, for the data gradients).
+# _BlockStep, one per transformer block: X (the block's input rows [B N, 256], norm1's input), y (norm1's output: the in-projection's operand), qkv (the packed
+# in-projection output; k and v alone [B, N, 512] in a CLS-only block), q (the CLS-only block's one query row per sample, else None), att / lse (attention's
+# output and row statistic), X1 (the stream after attention: norm2's input), y2 (norm2's output), pre / hid (the MLP's pre-activation and its GELU), B, N,
+# cls_only (everything from the attention's queries on ran for the CLS rows alone: att, X1, y2, pre, hid have B rows, not B N).
+# _Walk: steps (the _BlockSteps in forward order), cls (to_latent's input [B, 256]), stem_dtype (the dtype dstem is returned in), B, N, stem (_StemKept or None).
+_StemKept = namedtuple("_StemKept", "x ys k4")
+_BlockStep = namedtuple("_BlockStep", "X y qkv q att lse X1 y2 pre hid B N cls_only")
+_Walk = namedtuple("_Walk", "steps cls stem_dtype B N stem")
 
 
 class _Block(nn.Module):
@@ -97,15 +111,14 @@ class ViTVAEEncoder(nn.Module):
             raise CvaeError(f"ViTVAEEncoder expects a float32 [B, 1, {self.img_height}, {self.img_width}] batch, got {tuple(x.shape)} {x.dtype}")
         require_gpu(x, self.cls_token)
 
-    def _stem_layers(self):
-        """The stem's five (conv, BatchNorm2d) pairs."""
+    def _stem_fold_table(self):
+        """ops.fold_bn_conv's entry for each of the stem's five (conv, BatchNorm2d) pairs."""
         mods = list(self.stem)
-        return [(mods[i], mods[i + 1]) for i in range(0, len(mods), 3)]
+        return [(mods[i].weight, ops.FOLD_CONV_K3S2, mods[i].bias, mods[i + 1]) for i in range(0, len(mods), 3)]
 
     def _stem_cl(self, x, keep=None):
-        """keep (a dict, the stem's backward): receives `x` (the first conv's operand: the image as it is read), `ys` (the five layer outputs: each the next
-        layer's input, its weight-gradient operand and its gate) and `k4` (the folded k4 weights).  The launches do not depend on it."""
-        folded = ops.fold_bn_conv([(conv.weight, ops.FOLD_CONV_K3S2, conv.bias, bn) for conv, bn in self._stem_layers()])
+        """keep (a dict, the stem's backward): receives _StemKept's fields `x`, `ys` and `k4`.  The launches do not depend on it."""
+        folded = ops.fold_bn_conv(self._stem_fold_table())
         h, first_dtype = hl._image_cl(x, self.compute_dtype)
         if keep is not None:
             keep["x"], keep["ys"], keep["k4"] = h, [], [w for w, _b in folded]
@@ -115,53 +128,74 @@ class ViTVAEEncoder(nn.Module):
                 keep["ys"].append(h)
         return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
 
-    def _block(self, blk, tokens, cls_only):
-        """One transformer block on the fp32 residual stream `tokens` [B, N, 256], in place.  cls_only: returns the block's CLS rows [B, 256]
-        (fp32) and leaves `tokens` as it was; the same sums in the same order as the full block's row 0."""
+    def _block(self, blk, tokens, cls_only, save):
+        """One transformer block on the fp32 residual stream `tokens` [B, N, 256] -> (the stream after it [B, N, 256], or with cls_only the block's CLS rows
+        [B, 256]: the same sums in the same order as the full block's row 0, `tokens` left as it was; _BlockStep or None).
+        save=False (inference): the residual GEMMs of a full block write the stream in place and nothing is kept.  save=True: the same launches with attention
+        and the GELU GEMM in their training forms (the same values plus lse / the pre-activation), and the residual GEMMs write fresh tensors: the block's input
+        and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied."""
         B, N, D = tokens.shape
         dt = self.compute_dtype
         X = tokens.view(B * N, D)
         a = blk.attn
+        attend = ops.mhsa_train if save else ops.mhsa
         y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
         if not cls_only:
-            qkv = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D)
-            att = ops.mhsa(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
-            ops.token_gemm(att.view(B * N, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=X)
-            y2 = ops.layernorm256(X, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-            hid = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu")
-            ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X)
-            return tokens[:, 0]
-        kv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
-        qc = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D])
-        att = ops.mhsa(qc.view(B, 1, D), kv[:, :, :D], kv[:, :, D:], n_query_rows=1)
-        cls = torch.empty(B, D, dtype=torch.float32, device=tokens.device)
-        ops.token_gemm(att.view(B, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=tokens[:, 0], out=cls)
-        y2 = ops.layernorm256(cls, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-        hid = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu")
-        ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=cls)
-        return cls
+            qkv, q = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D), None
+            att = attend(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
+            resid, X1 = X, (torch.empty_like(X) if save else None)      # None: in place on the stream
+        else:
+            qkv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
+            q = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D]).view(B, 1, D)
+            att = attend(q, qkv[:, :, :D], qkv[:, :, D:], n_query_rows=1)
+            resid, X1 = tokens[:, 0], torch.empty(B, D, dtype=torch.float32, device=tokens.device)
+        att, lse = att if save else (att, None)
+        X1 = ops.token_gemm(att.view(-1, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=resid, out=X1)
+        y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
+        if save:
+            hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias)
+        else:
+            hid, pre = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu"), None
+        X2 = ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=torch.empty_like(X1) if save else None)
+        if not save:
+            return (X2 if cls_only else tokens), None                   # a full block wrote the stream itself
+        return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only)
 
     @torch.no_grad()
-    def cls_features(self, x):
-        """to_latent(transformer(tokens)[:, 0]) -> [B, 256] fp32: steps A-D of CausalViTVAE.forward (vessel_analysis/00_core/models.py:262-278)."""
-        return self._cls_features(x)
-
-    @torch.no_grad()
-    def _cls_features(self, x, collect=None):
-        """collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual
-        stream after every block that ran for all tokens)."""
+    def _walk(self, x, save=False, keep_stem=False, collect=None):
+        """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
+        saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
+        collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
+        after every block that ran for all tokens)."""
         self._check(x)
-        stem = self._stem_cl(x)
+        kept = {} if keep_stem else None
+        stem = self._stem_cl(x, kept)
         tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
         if collect is not None:
             collect["stem"], collect["cls_rows"], collect["tokens"] = stem, [], []
+        steps = []
         for i, blk in enumerate(self.transformer):
-            cls = self._block(blk, tokens, cls_only=self._cls_only_last_block and i == self.depth - 1)
+            cls_only = self._cls_only_last_block and i == self.depth - 1
+            out, step = self._block(blk, tokens, cls_only, save)
+            steps.append(step)
+            if cls_only:
+                cls = out
+            else:
+                tokens, cls = out, out[:, 0]
             if collect is not None:
                 collect["cls_rows"].append(cls.clone())
-                if not (self._cls_only_last_block and i == self.depth - 1):
+                if not cls_only:
                     collect["tokens"].append(tokens.clone())
-        return ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
+        out = ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
+        return out, (_Walk(steps, cls, stem.dtype, tokens.shape[0], tokens.shape[1], _StemKept(**kept) if keep_stem else None) if save else None)
+
+    def cls_features(self, x):
+        """to_latent(transformer(tokens)[:, 0]) -> [B, 256] fp32: steps A-D of CausalViTVAE.forward (vessel_analysis/00_core/models.py:262-278)."""
+        return self._walk(x)[0]
+
+    def _cls_features(self, x, collect=None):
+        """cls_features with _walk's collect dict (for tests)."""
+        return self._walk(x, collect=collect)[0]
 
     @torch.no_grad()
     def encode(self, x):
@@ -203,23 +237,18 @@ class ViTVAEEncoder(nn.Module):
         output as its gate), compute dtype.  Per layer, last to first: the folded k4 weight's and bias's gradient from (g_j, the layer's input) at once, then
         g_{j-1} = conv_down_bwd_data(g_j) with leaky001' of the layer's input in the epilogue: no activation-backward launch.  Then ONE launch back through the
         fold.  The image gets no gradient.  collect: receives `stem_g` = [g_0 .. g_4]."""
-        ys, k4, dt = kept["ys"], kept["k4"], self.compute_dtype
+        ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
         g = g.view(ys[-1].shape)
         folded, gs = [None] * len(ys), [None] * len(ys)
         for j in reversed(range(len(ys))):
             gs[j] = g
-            folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept["x"], 2, k4[j].shape, want_sbias=True)
+            folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
             if j:
                 g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), ys[j - 1], "leaky001")
         if collect is not None:
             collect["stem_g"] = gs
-        layers = self._stem_layers()
-        quads = ops.fold_bn_conv_bwd([(conv.weight, ops.FOLD_CONV_K3S2, conv.bias, bn) + tuple(folded[j]) for j, (conv, bn) in enumerate(layers)])
-        grads = {}
-        for j, quad in enumerate(quads):
-            for name, d in zip((f"stem.{3 * j}.weight", f"stem.{3 * j}.bias", f"stem.{3 * j + 1}.weight", f"stem.{3 * j + 1}.bias"), quad):
-                grads[name] = d
-        return grads
+        quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(self._stem_fold_table())])
+        return dict(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
 
     # ---- training the transformer (eval mode; DESIGN §16) -----------------------------------------------------------------------------
     _transformer_grads = False      # train_transformer(): cls_features_with_grad / encode_with_grad accumulate the transformer's gradients
@@ -269,13 +298,12 @@ class ViTVAEEncoder(nn.Module):
         named, stem = self._transformer_named(heads=False), self._stem_named()
         live_t, live_s = any(p.requires_grad for _k, p in named), any(p.requires_grad for _k, p in stem)
         if not (torch.is_grad_enabled() and (live_t or live_s)):
-            return self._cls_features(x)
+            return self.cls_features(x)
         if live_t and not self._transformer_grads:
             raise CvaeError("ViTVAEEncoder.cls_features_with_grad: transformer parameters ask for a gradient but train_transformer() was not called "
                             "(or call freeze_transformer())")
         if live_s and not self._stem_grads:
             raise CvaeError("ViTVAEEncoder.cls_features_with_grad: stem parameters ask for a gradient but train_stem() was not called (or call freeze_stem())")
-        self._check(x)
         if live_s:
             named = named + stem
         return _ClsFeaturesWithGrad.apply(x, self, collect, tuple(k for k, _p in named), *[p for _k, p in named])
@@ -285,89 +313,44 @@ class ViTVAEEncoder(nn.Module):
         c = self.cls_features_with_grad(x, collect)
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
-    def _block_train(self, blk, tokens, cls_only):
-        """_block's launches (attention and the GELU GEMM in their training forms: the same values plus lse / the pre-activation) -> (the next stream
-        [B, N, 256], or the CLS rows [B, 256] with cls_only; what _block_backward reads).  The residual GEMMs write fresh tensors instead of the stream in
-        place: the block's input and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied."""
-        B, N, D = tokens.shape
-        dt = self.compute_dtype
-        X = tokens.view(B * N, D)
-        a = blk.attn
-        y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
-        if not cls_only:
-            qkv = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D)
-            att, lse = ops.mhsa_train(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
-            att2, X1 = att.view(B * N, D), torch.empty_like(X)
-            ops.token_gemm(att2, a.out_proj.weight, a.out_proj.bias, "residual", resid=X, out=X1)
-        else:
-            qkv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
-            qc = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D]).view(B, 1, D)
-            att, lse = ops.mhsa_train(qc, qkv[:, :, :D], qkv[:, :, D:], n_query_rows=1)
-            att2, X1 = att.view(B, D), torch.empty(B, D, dtype=torch.float32, device=tokens.device)
-            ops.token_gemm(att2, a.out_proj.weight, a.out_proj.bias, "residual", resid=tokens[:, 0], out=X1)
-        y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-        hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias)
-        X2 = torch.empty_like(X1)
-        ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=X2)
-        saved = dict(X=X, y=y, qkv=qkv, q=None if not cls_only else qc, att=att, lse=lse, X1=X1, y2=y2, pre=pre, hid=hid, shape=(B, N))
-        return (X2 if cls_only else X2.view(B, N, D)), saved
-
     def _block_backward(self, blk, name, s, G, grads):
-        """One block's backward: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in place where it can be;
-        returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names."""
-        B, N = s["shape"]
-        D, dt, a = self.embed_dim, self.compute_dtype, blk.attn
-        cls_only = s["q"] is not None
-        dpre = ops.token_gemm_bwd_data(G, blk.mlp[3].weight, dt, gate_pre=s["pre"])
-        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(G, s["hid"])
+        """One block's backward from its _BlockStep s: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in
+        place where it can be; returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names."""
+        B, N, D, dt, a = s.B, s.N, self.embed_dim, self.compute_dtype, blk.attn
+        dpre = ops.token_gemm_bwd_data(G, blk.mlp[3].weight, dt, gate_pre=s.pre)
+        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(G, s.hid)
         dy2 = ops.token_gemm_bwd_data(dpre, blk.mlp[0].weight, dt)
-        grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s["y2"])
-        _dx, grads[name + "norm2.weight"], grads[name + "norm2.bias"] = ops.layernorm256_bwd(dy2, s["X1"], blk.norm2.weight, blk.norm2.eps, dx=G, accumulate=True)
+        grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s.y2)
+        _dx, grads[name + "norm2.weight"], grads[name + "norm2.bias"] = ops.layernorm256_bwd(dy2, s.X1, blk.norm2.weight, blk.norm2.eps, dx=G, accumulate=True)
         datt = ops.token_gemm_bwd_data(G, a.out_proj.weight, dt)
-        grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s["att"].view(-1, D))
-        qkv, y = s["qkv"], s["y"]
+        grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s.att.view(-1, D))
+        qkv, y = s.qkv, s.y
         dqkv = torch.empty_like(qkv)
-        if not cls_only:
-            ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s["att"], s["lse"], datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:])
+        if not s.cls_only:
+            ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.att, s.lse, datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:])
             dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 3 * D), a.in_proj_weight, dt)
             grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = ops.token_gemm_wgrad(dqkv.view(B * N, 3 * D), y)
-            _dx, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s["X"], blk.norm1.weight, blk.norm1.eps, dx=G, accumulate=True)
+            _dx, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s.X, blk.norm1.weight, blk.norm1.eps, dx=G, accumulate=True)
             return G
-        dq = torch.empty_like(s["q"])
-        ops.mhsa_bwd(s["q"], qkv[:, :, :D], qkv[:, :, D:], s["att"], s["lse"], datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:])
+        dq = torch.empty_like(s.q)
+        ops.mhsa_bwd(s.q, qkv[:, :, :D], qkv[:, :, D:], s.att, s.lse, datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:])
         dW, db = torch.empty_like(a.in_proj_weight), torch.empty_like(a.in_proj_bias)
         ops.token_gemm_wgrad(dq.view(B, D), y.view(B, N, D)[:, 0], dW[:D], db[:D])
         ops.token_gemm_wgrad(dqkv.view(B * N, 2 * D), y, dW[D:], db[D:])
         grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = dW, db
         dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 2 * D), a.in_proj_weight[D:], dt, out_dtype=torch.float32)
         ops.token_gemm_bwd_data(dq.view(B, D), a.in_proj_weight[:D], dt, resid=dy.view(B, N, D)[:, 0])       # the one q row joins the kv rows' gradient, in place
-        Gin, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s["X"], blk.norm1.weight, blk.norm1.eps)
+        Gin, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s.X, blk.norm1.weight, blk.norm1.eps)
         Gin.view(B, N, D)[:, 0].add_(G)                                 # the skip: only the CLS rows left this block
         return Gin
 
     @torch.no_grad()
-    def _train_walk(self, x, keep_stem=False):
-        """_cls_features' launches in their training forms -> (cls features [B, 256] fp32, what _train_backward reads).  keep_stem: the stem's layer outputs and
-        folded weights travel along (the same launches)."""
-        kept = {} if keep_stem else None
-        stem = self._stem_cl(x, kept)
-        tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
-        B, N, _D = tokens.shape
-        steps = []
-        for i, blk in enumerate(self.transformer):
-            tokens, s = self._block_train(blk, tokens, cls_only=self._cls_only_last_block and i == self.depth - 1)
-            steps.append(s)
-        cls = tokens if tokens.dim() == 2 else tokens[:, 0]
-        out = ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
-        return out, (steps, cls, stem.dtype, B, N, kept)
-
-    @torch.no_grad()
-    def _train_backward(self, saved, g, collect=None):
+    def _walk_backward(self, saved, g, collect=None):
         """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features;
         when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`)."""
         steps, cls, stem_dtype, B, N, kept = saved
         D, grads = self.embed_dim, {}
-        if steps[-1]["q"] is not None:                                  # the forward ran a CLS-only last block: the stream gradient starts as its [B, 256] rows
+        if steps[-1].cls_only:                                          # the forward ran a CLS-only last block: the stream gradient starts as its [B, 256] rows
             G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
         else:
             G = torch.zeros(B * N, D, dtype=torch.float32, device=g.device)
@@ -379,7 +362,7 @@ class ViTVAEEncoder(nn.Module):
         else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
             if collect is not None:
                 grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)[2]
-            dpos, dcls, g_last = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype, gate=kept["ys"][-1].view(B, N - 1, D), gate_act="leaky001")
+            dpos, dcls, g_last = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype, gate=kept.ys[-1].view(B, N - 1, D), gate_act="leaky001")
             grads.update(self._stem_backward(kept, g_last, collect))
         grads["pos_embedding"], grads["cls_token"] = dpos.view(1, N, D), dcls.view(1, 1, D)
         return grads
@@ -391,7 +374,7 @@ class _ClsFeaturesWithGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, model, collect, names, *params):
-        out, saved = model._train_walk(x, keep_stem=any(k.startswith("stem.") for k in names))
+        out, saved = model._walk(x, save=True, keep_stem=any(k.startswith("stem.") for k in names))
         ctx.model, ctx.saved, ctx.collect, ctx.names = model, saved, collect, names      # activations of this call: private to the node, freed with it
         ctx.save_for_backward(*params)
         ctx.set_materialize_grads(False)
@@ -403,7 +386,7 @@ class _ClsFeaturesWithGrad(torch.autograd.Function):
         params = ctx.saved_tensors                                     # raises if a parameter was modified in place since the forward
         if g is None:
             return (None,) * (4 + len(params))
-        grads = ctx.model._train_backward(ctx.saved, g.contiguous(), ctx.collect)
+        grads = ctx.model._walk_backward(ctx.saved, g.contiguous(), ctx.collect)
         if ctx.collect is not None:
             ctx.collect["dstem"] = grads["dstem"]
         return (None, None, None, None) + tuple(grads[k].view(p.shape) if need else None for k, p, need in zip(ctx.names, params, ctx.needs_input_grad[4:]))

@@ -343,6 +343,56 @@ def test_absent_cotangent_and_accumulation():
     assert not model.cls_features_with_grad(x).requires_grad
 
 
+FULL_BLOCK = ["layernorm256", "token_gemm", "mhsa", "token_gemm", "layernorm256", "token_gemm", "token_gemm"]                     # the module docstring's 7
+CLS_BLOCK = ["layernorm256", "token_gemm", "token_gemm", "mhsa", "token_gemm", "layernorm256", "token_gemm", "token_gemm"]       # K and V, then the CLS query: 8
+
+
+def walk_calls(run):
+    """[(ops name, shape of the (first) result, epilogue, whether `out` was left at its default)] of the token-side ops calls `run` makes"""
+    o, log = ops(), []
+    originals = {n: getattr(o, n) for n in ("vit_tokens", "layernorm256", "token_gemm", "mhsa", "mhsa_train", "token_gemm_gelu_train")}
+
+    def wrap(name, fn):
+        def call(*a, **k):
+            out = fn(*a, **k)
+            epilogue, dest = (a[3] if len(a) > 3 else k.get("epilogue")), (a[5] if len(a) > 5 else k.get("out"))
+            log.append((name, tuple((out[0] if isinstance(out, tuple) else out).shape), epilogue if name == "token_gemm" else None, dest is None))
+            return out
+        return call
+
+    try:
+        for n, fn in originals.items():
+            setattr(o, n, wrap(n, fn))
+        result = run()
+    finally:
+        for n, fn in originals.items():
+            setattr(o, n, fn)
+    return result, log
+
+
+@pytest.mark.parametrize("cls_only", [True, False])
+def test_one_walk_two_modes(cls_only):
+    """the saving walk issues the inference walk's ops calls (attention and the GELU GEMM in their training forms), block by block the docstring's 7 / 8; only
+    the inference walk writes a full block's residual GEMMs in place on the stream"""
+    model = encoder((64, 96))
+    model._cls_only_last_block = cls_only
+    x = vr.vit_inputs(2, 64, 96, seed=5).to(DEV)
+    c0, infer = walk_calls(lambda: model.cls_features(x))
+    model.train_transformer()
+    c1, saving = walk_calls(lambda: model.cls_features_with_grad(x))
+    assert c1.requires_grad and torch.equal(c0, c1)
+    alias = {"mhsa_train": "mhsa", "token_gemm_gelu_train": "token_gemm"}
+    plain = lambda log: [(alias.get(n, n), shape) for n, shape, _e, _d in log]
+    assert plain(infer) == plain(saving)
+    assert [n for n, _s in plain(infer)] == ["vit_tokens"] + FULL_BLOCK + (CLS_BLOCK if cls_only else FULL_BLOCK) + ["layernorm256"]
+    assert {n for n, *_r in infer} == {"vit_tokens", "layernorm256", "token_gemm", "mhsa"}
+    assert {n for n, *_r in saving} == {"vit_tokens", "layernorm256", "token_gemm", "mhsa_train", "token_gemm_gelu_train"}
+    full = slice(1, 1 + len(FULL_BLOCK) * (1 if cls_only else 2))           # the calls of the full block(s)
+    in_place = lambda log: [d for _n, _s, e, d in log[full] if e == "residual"]
+    assert in_place(infer) == [True] * len(in_place(infer)) and in_place(saving) == [False] * len(in_place(saving))
+    assert len(in_place(infer)) == len(in_place(saving)) == (2 if cls_only else 4)
+
+
 def test_causal_vitvae_trains_everything_but_the_stem():
     from causal_vae_amd.vessel.train import loss_function, total_loss
     from causal_vae_amd.vit.causal import CausalViTVAE

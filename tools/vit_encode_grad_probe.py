@@ -40,7 +40,8 @@ def eager_step(mods, stem, g):
 
 
 def block_launches(model, x, reps):
-    """[name, median us] per ops-layer call of the LAST FULL block's backward: the calls are wrapped with event pairs for the duration of this function"""
+    """[name, median us] per ops-layer call of the LAST FULL block's backward (from the saving walk's _BlockStep of that block): the calls are wrapped with
+    event pairs for the duration of this function"""
     log, originals = [], {n: getattr(ops, n) for n in TIMED}
 
     def wrap(name, fn):
@@ -55,14 +56,14 @@ def block_launches(model, x, reps):
         return run
 
     with torch.no_grad():
-        _out, (steps, _cls, _dt, B, N) = model._train_walk(x)
+        _out, saved = model._walk(x, save=True)
         i = model.depth - 2
         try:
             for n, fn in originals.items():
                 setattr(ops, n, wrap(n, fn))
             for _ in range(reps):
                 log.append([])
-                model._block_backward(model.transformer[i], f"transformer.{i}.", steps[i], torch.randn(B * N, 256, device=x.device), {})
+                model._block_backward(model.transformer[i], f"transformer.{i}.", saved.steps[i], torch.randn(saved.B * saved.N, 256, device=x.device), {})
             torch.cuda.synchronize()
         finally:
             for n, fn in originals.items():
