@@ -23,8 +23,9 @@
 //     LeakyReLU slope where the first one zeroes (cvae_conv_down_bwd_data: the ViT-VAE stem's input gradients).
 // wgrad — M = Cs, N = Cl, K = positions.  Both operands are [position][channel] in memory, i.e. K-strided: bf16 uses
 //   the gfx950 transposing LDS read (ds_read_b64_tr_b16) to build K-contiguous fragments; fp32's 32x32x2 MFMA takes
-//   one element per lane and needs no transpose.  Every workgroup leaves ONE fp32 slab [kh][kw][64 cs][32 cl] of partial sums with
-//   plain stores; wgrad_reduce_kernel adds the slabs in index order and writes the reference [Cs][Cl][taps] layout (no atomics).
+//   one element per lane and needs no transpose.  Every workgroup leaves ONE fp32 slab [kh][64 cs][32 cl][kw] of partial sums with
+//   plain stores; wgrad_reduce_kernel adds the slabs in index order and writes the reference [Cs][Cl][taps] layout (no atomics).  A layer
+//   with one slab per (kd, channel block) group skips that round trip: its workgroups write the reference layout themselves.
 #include "common.h"
 
 // Development aid (make EXTRA=-DCVAE_STAMP, tools/stamp_probe.py): thread 0 of every workgroup of conv_data_kernel records the
@@ -677,6 +678,7 @@ struct WgradEntry {
     ConvGeom g;
     int n_split, cb, tg, bias_mode;
     int xb;             // 2D layers at most TW / 2 wide: two samples per tile, side by side in x (the 7 x 7 maps of the MNIST model fill 49 of a tile's 128 positions)
+    float* dW;          // n_split == 1: the group's only slab IS the sum, so the workgroup stores it into dW[Cs][Cl][taps] itself (nullptr: slab + reduce pass)
 };
 struct WgradTable { WgradEntry e[WG_MULTI_MAX]; int blk_start[WG_MULTI_MAX + 1]; int count; };
 
@@ -882,8 +884,8 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
 #endif
     }
     STAMP(26);
-    // ---- write-out: this workgroup's partial sums leave as ONE slab [kh][kw][64 cs][32 cl] of plain 128-byte-row stores;
-    // wgrad_reduce_kernel sums the slabs (fp32 atomics here cost more than the MFMA phase: 67 MB of adds at < 1 TB/s) ----
+    // ---- write-out: this workgroup's partial sums leave as ONE slab [kh][64 cs][32 cl][kw] of plain stores; wgrad_reduce_kernel sums the slabs
+    // (fp32 atomics here cost more than the MFMA phase: 67 MB of adds at < 1 TB/s).  A group with a single slab writes dW itself ----
     if (bias_s || bias_l) {                                   // block-uniform
         __syncthreads();                                     // the last tile's readers are done with the S image: reuse it as scratch
         float* red = (float*)s_lds;
@@ -904,13 +906,37 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
         }
     }
     const int col = lane & 31, hq = lane >> 5;
-    float* slab = ws + ((size_t)(bz * grid_y + by) * n_split + bx) * 32768;
-    // slab layout [kh][64 cs][32 cl][kw]: the lane owns the four kw values of (cs row, cl col), so they leave as ONE 16-byte store (32 lanes = 512 contiguous
-    // bytes) and wgrad_reduce_kernel reads them back as one 16-byte load per slab — a quarter of the memory instructions of the [kh][kw][cs][cl] form on both sides
+    if (float* __restrict__ dW = tb.e[ti].dW) {
+        // one slab per group: it IS the sum, so it goes straight to dW[cs][cl][kd][kh][0..3] and the layer has no dW blocks in the reduce pass.  + 0.f: the
+        // reduce pass starts its sum from +0, so a -0 partial comes out as +0 there; every other bit is the same.
+        // A lane holds the four kw of ONE kh: stored as they lie, a wave would write 64 16-byte pieces 256 bytes apart (measured: the launch 1 - 4 us longer, profiles/wgrad_roundtrips.md).  The
+        // images are free after the last tile, so the four kh waves meet in LDS, 4 accumulator rows at a time, and four adjacent lanes store the 64
+        // contiguous bytes of a (cs, cl, kd); the kh slot is xor-ed with cl & 3 against bank conflicts of the 64-byte-strided writes.
+        const int taps = (ND == 3) ? 64 : 16;
+        float4* xch = (float4*)smem;                         // [4 e][2 sg x 2 hq rows][32 cl][4 kh]: 32 KB
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int row = sg * 32 + (e & 3) + 8 * (e >> 2) + 4 * hq;
-        *(float4*)(slab + ((kh * 64 + row) * 32 + col) * 4) = make_float4(acc[0][e], acc[1][e], acc[2][e], acc[3][e]);
+        for (int e0 = 0; e0 < 16; e0 += 4) {
+            __syncthreads();                                 // the last tile's / the previous pass's readers are done
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                xch[((k * 4 + sg * 2 + hq) * 32 + col) * 4 + (kh ^ (col & 3))] = make_float4(acc[0][e0 + k] + 0.f, acc[1][e0 + k] + 0.f, acc[2][e0 + k] + 0.f, acc[3][e0 + k] + 0.f);
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = t + k * NT, khj = j & 3, clj = (j >> 2) & 31, r4 = (j >> 7) & 3, e = e0 + k;
+                const int row = (r4 >> 1) * 32 + (e & 3) + 8 * (e >> 2) + 4 * (r4 & 1);
+                *(float4*)(dW + ((size_t)(cs0 + row) * g.Cl + cl0 + clj) * taps + kd * 16 + khj * 4) = xch[(j & ~3) | (khj ^ (clj & 3))];
+            }
+        }
+    } else {
+        float* slab = ws + ((size_t)(bz * grid_y + by) * n_split + bx) * 32768;
+        // slab layout [kh][64 cs][32 cl][kw]: the lane owns the four kw values of (cs row, cl col), so they leave as ONE 16-byte store (32 lanes = 512 contiguous
+        // bytes) and wgrad_reduce_kernel reads them back as one 16-byte load per slab — a quarter of the memory instructions of the [kh][kw][cs][cl] form on both sides
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int row = sg * 32 + (e & 3) + 8 * (e >> 2) + 4 * hq;
+            *(float4*)(slab + ((kh * 64 + row) * 32 + col) * 4) = make_float4(acc[0][e], acc[1][e], acc[2][e], acc[3][e]);
+        }
     }
     STAMP_END();
 }
@@ -918,6 +944,7 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
 // dW[cs][cl][kd][kh][0..3] = sum over the n_split slabs of group (kd, channel block).  One thread per (kd, kh, cs, cl)
 // sums the 4 kw values (a 16-byte store into the reference layout); 4 thread groups split the slab range, LDS combines.
 // Blocks past the dW range sum the bias partials: block j handles 64 channels, 4 thread groups split the partial rows.
+// A layer with one slab per group has no dW blocks (dw_blocks == 0: conv_wgrad_kernel stored its dW), only its bias blocks.
 struct WgradReduceEntry {
     const float* ws; float* dW; const float* bias_ws; float* dbias;
     int Cs, Cl, n_split, cb, dw_blocks, bias_n, bias_rows, bias_width;
@@ -1021,9 +1048,11 @@ int plan_wgrad(const void* S, const void* L, float* ws, float* dW, float* dbias,
     const long long wgs = (long long)cb * tg * n_split;
     float* bias_ws = ws + (size_t)(wgs > WGRAD_MAX_WG ? wgs : WGRAD_MAX_WG) * 32768;
     if (!dbias) bias_mode = 0;
-    *me = WgradEntry{S, L, ws, bias_ws, g, (int)n_split, cb, tg, bias_mode, xb};
+    // one slab per group: the main kernel writes dW itself and the reduce pass keeps only the layer's bias blocks (a function of the shape alone, like n_split)
+    const bool direct = n_split == 1;
+    *me = WgradEntry{S, L, ws, bias_ws, g, (int)n_split, cb, tg, bias_mode, xb, direct ? dW : nullptr};
     *main_blocks = (int)wgs;
-    const int dw_blocks = cb * tg * 4 * 32;
+    const int dw_blocks = direct ? 0 : cb * tg * 4 * 32;
     const int bias_n = bias_mode == 1 ? g.Cs : (bias_mode == 2 ? g.Cl : 0), bias_width = bias_mode == 1 ? 64 : 32;
     const int bias_rows = (int)n_split * ((bias_mode == 2 && ND == 3) ? 2 : 1);
     *re = WgradReduceEntry{ws, dW, bias_ws, dbias, g.Cs, g.Cl, (int)n_split, cb, dw_blocks, bias_n, bias_rows, bias_width};
@@ -1039,6 +1068,7 @@ int launch_wgrad_tables(WgradTable& mt, WgradReduceTable& rt, hipStream_t stream
     rt.taps = (ND == 3) ? 64 : 16;
     hipLaunchKernelGGL(kern, dim3((unsigned)mt.blk_start[mt.count]), dim3(512), LDS, stream, mt);
     CVAE_CHECK_LAUNCH();
+    if (rt.blk_start[rt.count] == 0) return CVAE_OK;         // every layer stored its dW directly and none has a bias sum
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rt.blk_start[rt.count]), dim3(256), 0, stream, rt);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
