@@ -1135,7 +1135,7 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     if (noise && !noise->call_counter) return CVAE_E_NULLPTR;
     const NoiseDraw nz = noise ? NoiseDraw{eps, (int)(q->M * q->Z), noise->seed, noise->subsequence, noise->call_counter} : NoiseDraw{nullptr, 0, 0, 0, nullptr};
     if (bn_rank_stats && (bn_ranks < 1 || !bn_training)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!w || !sv || !y_cl || !m || !t_onehot || !eps || !xcat || !partial || !dec_cl) return CVAE_E_NULLPTR;
     if (bn_training && q->M * (bn_rank_stats ? bn_ranks : 1) < 2) return CVAE_E_BADSHAPE;
     if (!bn_training && (!running_mean || !running_var)) return CVAE_E_NULLPTR;
@@ -1143,12 +1143,13 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     hipStream_t st = (hipStream_t)stream;
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), KS = fwd_ksplit(K1);
-    with_dtype(dtype, [&](auto tv) {
+    const int rc = with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(pool_cat_fwd_kernel<T>, dim3(S + 1, M), dim3(256), 0, st, (const T*)y_cl, m, t_onehot, (const long long*)t_labels, xcat, (int)q->D, (int)q->H, (int)q->W, C,
                            (int)q->OD, (int)q->OH, (int)q->OW, (int)q->m_dim, (int)q->t_dim, K1, nz);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
+    if (rc != CVAE_OK) return rc;
     const TailDims d = tail_dims(q, KS, 0);
     const TailParams p = tail_params(w);
     const TailSaved s = tail_saved(sv);
@@ -1163,12 +1164,11 @@ extern "C" int cvae_bottleneck_fwd(const cvae_bottleneck_dims* q, const cvae_bot
     hipLaunchKernelGGL(mulv_fwd_kernel, dim3((unsigned)((q->Z + 3) / 4)), dim3(256), mulv_fwd_lds(d), st, d, p, s, eps);
     CVAE_CHECK_LAUNCH();
     const size_t lds_d = dec_input_fwd_lds(M, K4);
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(dec_input_fwd_kernel<T>, dim3(C * S / 64), dim3(256), lds_d, st, (const float*)sv->zm, w->Wd, w->bd, (T*)dec_cl, M, K4, S, C);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }
 
 extern "C" int cvae_bottleneck_bn_bwd_finish(const cvae_bottleneck_dims* q, const cvae_bottleneck_params* w, const cvae_bottleneck_grads* gr, const cvae_bottleneck_saved* sv,
@@ -1192,18 +1192,19 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
                                    float* bn_dy, float* bn_local_sums, void* stream) {
     if (!dims_ok(q)) return CVAE_E_BADSHAPE;
     if ((bn_dy == nullptr) != (bn_local_sums == nullptr)) return CVAE_E_NULLPTR;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!w || !gr || !sv || !g_dec_cl || !t_onehot || !eps || !xcat || !y_cl || !dzm_partial || !g1 || !dx_partial || !dy_cl) return CVAE_E_NULLPTR;
     if (bwd_lds_ready(tail_dims(q, 0, 0)) != CVAE_OK) return CVAE_E_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
     const int M = (int)q->M, S = (int)(q->OD * q->OH * q->OW), C = (int)q->C, F = C * S;
     const int K1 = F + (int)q->m_dim + (int)q->t_dim, K4 = (int)(q->Z + q->m_dim), NS = bwd_nsplit(q->N1), P = S;
     const size_t lds_d = dec_input_bwd_lds(M, K4);
-    with_dtype(dtype, [&](auto tv) {
+    const int rc = with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(dec_input_bwd_kernel<T>, dim3(F / 64), dim3(256), lds_d, st, (const T*)g_dec_cl, (const float*)sv->zm, w->Wd, gr->dWd, gr->dbd, dzm_partial, M, K4, S, C);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
+    if (rc != CVAE_OK) return rc;
     const TailDims d = tail_dims(q, 0, P);
     const TailParams p = tail_params(w);
     const TailGrads g = tail_grads(gr);
@@ -1222,11 +1223,10 @@ extern "C" int cvae_bottleneck_bwd(const cvae_bottleneck_dims* q, const cvae_bot
                            w->W1, gr->dW1, dx_partial, M, K1, (int)q->N1, ((int)q->N1 + NS - 1) / NS, F, S, NS, d, p, g, s, mb);
     });
     CVAE_CHECK_LAUNCH();
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(pool_bwd_kernel<T>, dim3(S, M), dim3(256), 0, st, (const float*)dx_partial, (const T*)y_cl, (T*)dy_cl, NS, M, (int)q->D, (int)q->H, (int)q->W, C,
                            (int)q->OD, (int)q->OH, (int)q->OW, relu_mask);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }

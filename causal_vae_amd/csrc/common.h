@@ -13,10 +13,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define CVAE_WAVE 64
 
+// did the launch just issued fail?  launch_rc() is the answer as a value (the last line of a launch lambda), CVAE_CHECK_LAUNCH() returns on failure
+inline int launch_rc() { return hipGetLastError() == hipSuccess ? CVAE_OK : CVAE_E_LAUNCH; }
 #define CVAE_CHECK_LAUNCH()                                   \
     do {                                                      \
-        hipError_t e__ = hipGetLastError();                   \
-        if (e__ != hipSuccess) return CVAE_E_LAUNCH;          \
+        if (launch_rc() != CVAE_OK) return CVAE_E_LAUNCH;     \
     } while (0)
 
 // Dynamic LDS above the runtime's default limit: a kernel has to have its limit raised first, and that attribute belongs to the CURRENT DEVICE's copy
@@ -230,10 +231,17 @@ template <int EPI> __device__ __forceinline__ float apply_act_t(float v, int act
 }
 #define CVAE_EPI_OF(act) ((act) == CVAE_ACT_NONE ? 0 : ((act) == CVAE_ACT_RELU ? 1 : 2))
 // Runtime -> template lifting on the host, each written once: f receives the value as a std::integral_constant (nd, EPI, a flag) or as a value of the
-// element type (dtype), e.g.  with_epi(act, [&](auto epi) { launch<decltype(epi)::value>(...); return CVAE_OK; })
+// element type (dtype), e.g.  with_epi(act, [&](auto epi) { launch<decltype(epi)::value>(...); return CVAE_OK; }).  This is the ONLY place where a
+// runtime value becomes a template argument: kernel files nest these and name each argument once (constexpr bool VEC = ...), they define no launch
+// macros.  with_dtype answers CVAE_E_DTYPE for every code that is not an element type, so no launch is reachable with one; an
+// entry point whose contract puts the dtype check earlier asks dtype_ok() there.
 template <int V> using Int = std::integral_constant<int, V>;
+inline bool dtype_ok(int dtype) { return dtype == CVAE_F32 || dtype == CVAE_BF16; }
 template <typename F> auto with_nd(int nd, F&& f) { return nd == 3 ? f(Int<3>{}) : f(Int<2>{}); }
-template <typename F> auto with_dtype(int dtype, F&& f) { return dtype == CVAE_BF16 ? f(bf16{}) : f(float{}); }
+template <typename F> int with_dtype(int dtype, F&& f) { return dtype == CVAE_BF16 ? f(bf16{}) : (dtype == CVAE_F32 ? f(float{}) : CVAE_E_DTYPE); }
+template <typename F> int with_dtype2(int da, int db, F&& f) {      // two independent element types, f(a, b)
+    return with_dtype(da, [&](auto a) { return with_dtype(db, [&](auto b) { return f(a, b); }); });
+}
 template <typename F> auto with_epi(int act, F&& f) { return CVAE_EPI_OF(act) == 0 ? f(Int<0>{}) : (CVAE_EPI_OF(act) == 1 ? f(Int<1>{}) : f(Int<2>{})); }
 template <typename F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 // derivative expressed through the activation OUTPUT y

@@ -959,7 +959,6 @@ static bool image_vec_ok(const void* L, int64_t lw, int l_dtype) {
 int cvae_conv_down_c1(const void* L, int l_dtype, const float* w, const float* bias, const void* mask, void* S, int64_t B, int64_t sd, int64_t sh, int64_t sw,
                       int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, int act, hipStream_t stream, F8Side f8) {
     if (Cs != 32) return CVAE_E_UNSUPPORTED;
-    const int epi = CVAE_EPI_OF(act);
     const bool side8 = f8.out8 || f8.amax || f8.bits_out;
     if (side8 && !(dtype == CVAE_BF16 && image_vec_ok(L, lw, l_dtype) && !mask && !f8.mask_bits)) return CVAE_E_UNSUPPORTED;
     if (f8.mask_bits && !(dtype == CVAE_BF16 && image_vec_ok(L, lw, l_dtype))) return CVAE_E_UNSUPPORTED;
@@ -973,36 +972,26 @@ int cvae_conv_down_c1(const void* L, int l_dtype, const float* w, const float* b
         if (ntiles_ll > 0x7fffffff) return CVAE_E_BADSHAPE;
         const int ntiles = (int)ntiles_ll;
         dim3 grid((unsigned)(ntiles < C1_MAX_WG ? ntiles : C1_MAX_WG), 1, 1);       // <= 4 resident workgroups per CU; each walks ntiles / grid tiles
-#define LAUNCH_DOWN_VEC__(TLT, ND, EPI, MASKED, MS, SIDE)                                                                                              \
-    hipLaunchKernelGGL((down_c1_vec_kernel<TLT, ND, EPI, MASKED, MS, SIDE>), grid, dim3(256), 0, stream, (const TLT*)L, w, bias, (const bf16*)mask, (bf16*)S, (int)sd, (int)sh, \
-                       (int)sw, (int)ld, (int)lh, (int)lw, tiles_d, tiles_h, tiles_w, ntiles, act, f8)
-#define LAUNCH_DOWN_VEC_(TLT, ND, EPI, MS) do { if (mask || f8.mask_bits) LAUNCH_DOWN_VEC__(TLT, ND, EPI, true, MS, false); else if (side8) LAUNCH_DOWN_VEC__(TLT, ND, EPI, false, MS, true); \
-                                                else LAUNCH_DOWN_VEC__(TLT, ND, EPI, false, MS, false); } while (0)
-#define LAUNCH_DOWN_VEC(TLT, ND, MS)                                                                                                      \
-    do { if (epi == 0) LAUNCH_DOWN_VEC_(TLT, ND, 0, MS); else if (epi == 1) LAUNCH_DOWN_VEC_(TLT, ND, 1, MS); else LAUNCH_DOWN_VEC_(TLT, ND, 2, MS); } while (0)
-        if (l_dtype == CVAE_F32) { if (nd == 2) LAUNCH_DOWN_VEC(float, 2, 4); else if (ms == 4) LAUNCH_DOWN_VEC(float, 3, 4); else LAUNCH_DOWN_VEC(float, 3, 2); }
-        else { if (nd == 2) LAUNCH_DOWN_VEC(bf16, 2, 4); else if (ms == 4) LAUNCH_DOWN_VEC(bf16, 3, 4); else LAUNCH_DOWN_VEC(bf16, 3, 2); }
-#undef LAUNCH_DOWN_VEC
-#undef LAUNCH_DOWN_VEC_
-#undef LAUNCH_DOWN_VEC__
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(l_dtype, [&](auto tl) { return with_nd(nd, [&](auto n) { return with_bool(ms == 4, [&](auto ms4) { return with_epi(act, [&](auto epi) {
+               return with_bool(mask || f8.mask_bits, [&](auto mk) { return with_bool(side8, [&](auto sd8) {
+            using TL = decltype(tl);
+            constexpr int ND = decltype(n)::value, MS = (ND == 2 || decltype(ms4)::value) ? 4 : 2;      // 2D always takes 512 positions
+            constexpr bool MASKED = decltype(mk)::value, SIDE = !MASKED && decltype(sd8)::value;
+            hipLaunchKernelGGL((down_c1_vec_kernel<TL, ND, decltype(epi)::value, MASKED, MS, SIDE>), grid, dim3(256), 0, stream, (const TL*)L, w, bias, (const bf16*)mask,
+                               (bf16*)S, (int)sd, (int)sh, (int)sw, (int)ld, (int)lh, (int)lw, tiles_d, tiles_h, tiles_w, ntiles, act, f8);
+            return launch_rc();
+        }); }); }); }); }); });
     }
     const int th = (nd == 3) ? 8 : 16, tw = (nd == 3) ? 8 : 16, td = (nd == 3) ? 4 : 1;
     const int tiles_d = (int)((sd + td - 1) / td), tiles_h = (int)((sh + th - 1) / th), tiles_w = (int)((sw + tw - 1) / tw);
     dim3 grid((unsigned)(tiles_d * tiles_h * tiles_w), 1, (unsigned)B);
     if (l_dtype != dtype) return CVAE_E_UNSUPPORTED;         // the element-wise form reads the image in the compute dtype
-#define LAUNCH_DOWN_C1_(T, ND, EPI)                                                                                                   \
-    hipLaunchKernelGGL((down_c1_kernel<T, ND, 32, EPI>), grid, dim3(256), 0, stream, (const T*)L, w, bias, (const T*)mask, (T*)S, (int)sd, (int)sh, \
-                       (int)sw, (int)ld, (int)lh, (int)lw, tiles_h, tiles_w, act)
-#define LAUNCH_DOWN_C1(T, ND)                                                                                                         \
-    do { if (epi == 0) LAUNCH_DOWN_C1_(T, ND, 0); else if (epi == 1) LAUNCH_DOWN_C1_(T, ND, 1); else LAUNCH_DOWN_C1_(T, ND, 2); } while (0)
-    if (dtype == CVAE_BF16) { if (nd == 3) LAUNCH_DOWN_C1(bf16, 3); else LAUNCH_DOWN_C1(bf16, 2); }
-    else { if (nd == 3) LAUNCH_DOWN_C1(float, 3); else LAUNCH_DOWN_C1(float, 2); }
-#undef LAUNCH_DOWN_C1
-#undef LAUNCH_DOWN_C1_
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) { return with_nd(nd, [&](auto n) { return with_epi(act, [&](auto epi) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL((down_c1_kernel<T, decltype(n)::value, 32, decltype(epi)::value>), grid, dim3(256), 0, stream, (const T*)L, w, bias, (const T*)mask, (T*)S, (int)sd,
+                           (int)sh, (int)sw, (int)ld, (int)lh, (int)lw, tiles_h, tiles_w, act);
+        return launch_rc();
+    }); }); });
 }
 
 int cvae_conv_up_c1(const void* S, const float* w, const float* bias, const void* mask, void* L, int64_t B, int64_t sd, int64_t sh, int64_t sw,
@@ -1027,25 +1016,21 @@ int cvae_conv_up_c1(const void* S, const float* w, const float* bias, const void
             return with_epi(act, [&](auto epi) { return with_bool(mask != nullptr, [&](auto masked) {
                 hipLaunchKernelGGL((up_c1_mfma_walk_kernel<decltype(epi)::value, decltype(masked)::value>), wgrid, dim3(256), 0, stream, (const bf16*)S, w, bias,
                                    (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, 1.f);
-                CVAE_CHECK_LAUNCH();
-                return CVAE_OK;
+                return launch_rc();
             }); });
         }
         return with_nd(nd, [&](auto n) { return with_epi(act, [&](auto epi) { return with_bool(mask != nullptr, [&](auto masked) {
             hipLaunchKernelGGL((up_c1_mfma_kernel<decltype(n)::value, decltype(epi)::value, decltype(masked)::value>), mgrid, dim3(256), 0, stream, (const bf16*)S, w, bias,
                                (const bf16*)mask, (bf16*)L, (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, ntiles, act);
-            CVAE_CHECK_LAUNCH();
-            return CVAE_OK;
+            return launch_rc();
         }); }); });
     }
     dim3 grid((unsigned)((2 * n + 255) / 256));
-#define LAUNCH_UP_C1(T, ND)                                                                                                          \
-    hipLaunchKernelGGL((up_c1_kernel<T, ND, 32>), grid, dim3(256), 0, stream, (const T*)S, w, bias, (const T*)mask, (T*)L, (int)B, (int)sd,   \
-                       (int)sh, (int)sw, (int)ld, (int)lh, (int)lw, act)
-    if (nd == 3) LAUNCH_UP_C1(float, 3); else LAUNCH_UP_C1(float, 2);      // bf16 took the MFMA form above
-#undef LAUNCH_UP_C1
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_nd(nd, [&](auto n3) {                         // fp32: bf16 took the MFMA form above
+        hipLaunchKernelGGL((up_c1_kernel<float, decltype(n3)::value, 32>), grid, dim3(256), 0, stream, (const float*)S, w, bias, (const float*)mask, (float*)L, (int)B, (int)sd,
+                           (int)sh, (int)sw, (int)ld, (int)lh, (int)lw, act);
+        return launch_rc();
+    });
 }
 
 // The single-channel ConvTranspose3d end fed by fp8 (e4m3) codes: L (bf16) = act(in_scale * (S8 (*) w) + bias).  3D, Cs == 32, exact 2x.
@@ -1066,8 +1051,7 @@ int cvae_conv_up_c1_fp8in_impl(const void* S8, const float* w, const float* bias
     return with_epi(act, [&](auto epi) {
         hipLaunchKernelGGL((up_c1_mfma_walk_kernel<decltype(epi)::value, false, fp8>), wgrid, dim3(256), 0, stream, (const fp8*)S8, w, bias, (const bf16*)nullptr, (bf16*)L,
                            (int)sd, (int)sh, (int)sw, tiles_d, tiles_h, tiles_w, walk, segs, nunits, act, in_scale);
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return launch_rc();
     });
 }
 
@@ -1098,27 +1082,20 @@ int cvae_conv_wgrad_c1(const void* S, const void* L, int l_dtype, float* dW, flo
     const int rw = ((nd == 3) ? 64 : 32) + 1;
     float* lsum_ws = dbias_l ? ws + (size_t)2048 * 32 * rw : nullptr;
     const bool vec = image_vec_ok(L, lw, l_dtype);
-#define LAUNCH_WG_C1(T, ND)                                                                                                           \
-    if (lsum_ws) LAUNCH_WG_C1_(T, ND, true); else LAUNCH_WG_C1_(T, ND, false)
-#define LAUNCH_WG_C1__(T, TLT, ND, LS, VEC)                                                                                           \
-    hipLaunchKernelGGL((wgrad_c1_kernel<T, TLT, ND, LS, VEC>), grid, dim3(256), 0, stream, (const T*)S, (const TLT*)L, ws, dbias != nullptr, (int)B, (int)sd, (int)sh, \
-                       (int)sw, (int)Cs, (int)ld, (int)lh, (int)lw, tiles_d, tiles_h, tiles_w, (int)n_split, lsum_ws)
-#define LAUNCH_WG_C1_(T, ND, LS)                                                                                                      \
-    do {                                                                                                                              \
-        constexpr bool can_vec = sizeof(T) == 2;                                                                                      \
-        if (l_dtype == dtype) { if (can_vec && vec) LAUNCH_WG_C1__(T, T, ND, LS, can_vec); else LAUNCH_WG_C1__(T, T, ND, LS, false); } \
-        else { if (can_vec && vec) LAUNCH_WG_C1__(T, float, ND, LS, can_vec); else LAUNCH_WG_C1__(T, float, ND, LS, false); }          \
-    } while (0)
-    if (dtype == CVAE_BF16) { if (nd == 3) { LAUNCH_WG_C1(bf16, 3); } else { LAUNCH_WG_C1(bf16, 2); } }
-    else { if (nd == 3) { LAUNCH_WG_C1(float, 3); } else { LAUNCH_WG_C1(float, 2); } }
-#undef LAUNCH_WG_C1
-#undef LAUNCH_WG_C1_
-#undef LAUNCH_WG_C1__
-    CVAE_CHECK_LAUNCH();
+    const int rc = with_dtype(dtype, [&](auto tv) { return with_bool(l_dtype == dtype, [&](auto same) { return with_nd(nd, [&](auto n) {
+                   return with_bool(lsum_ws != nullptr, [&](auto ls) { return with_bool(vec, [&](auto vc) {
+        using T = decltype(tv);
+        using TL = std::conditional_t<decltype(same)::value, T, float>;          // the mixed form reads an fp32 image
+        constexpr bool VEC = sizeof(T) == 2 && decltype(vc)::value;              // the vector form exists for a bf16 gradient only
+        hipLaunchKernelGGL((wgrad_c1_kernel<T, TL, decltype(n)::value, decltype(ls)::value, VEC>), grid, dim3(256), 0, stream, (const T*)S, (const TL*)L, ws, dbias != nullptr,
+                           (int)B, (int)sd, (int)sh, (int)sw, (int)Cs, (int)ld, (int)lh, (int)lw, tiles_d, tiles_h, tiles_w, (int)n_split, lsum_ws);
+        return launch_rc();
+    }); }); }); }); });
+    if (rc != CVAE_OK) return rc;
     const int main_blocks = (32 * rw + 15) / 16;
     dim3 fgrid((unsigned)(main_blocks + (dbias_l ? 1 : 0)), (unsigned)(Cs / 32), 1);
-    if (nd == 3) hipLaunchKernelGGL(wgrad_c1_finish_kernel<3>, fgrid, dim3(256), 0, stream, ws, dW, dbias, (int)n_split, lsum_ws, dbias_l, main_blocks);
-    else hipLaunchKernelGGL(wgrad_c1_finish_kernel<2>, fgrid, dim3(256), 0, stream, ws, dW, dbias, (int)n_split, lsum_ws, dbias_l, main_blocks);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_nd(nd, [&](auto n) {
+        hipLaunchKernelGGL(wgrad_c1_finish_kernel<decltype(n)::value>, fgrid, dim3(256), 0, stream, ws, dW, dbias, (int)n_split, lsum_ws, dbias_l, main_blocks);
+        return launch_rc();
+    });
 }

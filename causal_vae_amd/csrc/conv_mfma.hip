@@ -452,8 +452,7 @@ int launch_up_full(const ConvArgs& a) {
             if (cvae_allow_lds<kern>(LDS) != CVAE_OK) return CVAE_E_LAUNCH;
             hipLaunchKernelGGL(kern, grid, block, LDS, a.stream, (const T*)a.in, (const T*)a.wp, a.bias, (const T*)a.mask, (T*)a.out, g, a.act, npar / psplit,
                                a.acc_scale, a.out_scale);
-            CVAE_CHECK_LAUNCH();
-            return CVAE_OK;
+            return launch_rc();
         });
     }
 }
@@ -1123,11 +1122,11 @@ extern "C" int cvae_conv_pack_weight(const float* w, void* packed, int64_t Cs, i
     if (!w || !packed) return CVAE_E_NULLPTR;
     const int taps = (nd == 3) ? 64 : 16;
     const int64_t n = Cs * Cl * taps;
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL(pack_weight_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (bf16*)packed, (int)Cs, (int)Cl, taps, for_up);
-    else if (dtype == CVAE_F32) hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (float*)packed, (int)Cs, (int)Cl, taps, for_up);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(pack_weight_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (T*)packed, (int)Cs, (int)Cl, taps, for_up);
+        return launch_rc();
+    });
 }
 
 // channel counts an fp8 product accepts (cvae_conv_fp8): conv C_in % 32, C_out % 64; ConvTranspose C_in % 32, C_out % 32, C_out > 1
@@ -1138,7 +1137,7 @@ extern "C" int cvae_conv_pack_weight_pairs(const float* const* w, void* const* p
     if ((nd != 2 && nd != 3) || count < 0) return CVAE_E_BADSHAPE;
     if (count == 0) return CVAE_OK;
     if (!w || !packed_down || !packed_up || !Cs || !Cl) return CVAE_E_NULLPTR;
-    if (dtype != CVAE_BF16 && dtype != CVAE_F32) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     const int tsplit = (nd == 3) ? 4 : 1;                    // blocks per (cs, cl) tile: 16 taps each
     for (int c0 = 0; c0 < count; c0 += PAIR_MAX) {
         PairTable tb;
@@ -1167,14 +1166,12 @@ extern "C" int cvae_conv_pack_weight_pairs(const float* const* w, void* const* p
         tb.count = cnt;
         const dim3 grid((unsigned)blocks);
         hipStream_t st = (hipStream_t)stream;
-        if (dtype == CVAE_BF16) {
-            if (nd == 3) hipLaunchKernelGGL((pack_weight_pairs_kernel<bf16, 64>), grid, dim3(256), 0, st, tb);
-            else hipLaunchKernelGGL((pack_weight_pairs_kernel<bf16, 16>), grid, dim3(256), 0, st, tb);
-        } else {
-            if (nd == 3) hipLaunchKernelGGL((pack_weight_pairs_kernel<float, 64>), grid, dim3(256), 0, st, tb);
-            else hipLaunchKernelGGL((pack_weight_pairs_kernel<float, 16>), grid, dim3(256), 0, st, tb);
-        }
-        CVAE_CHECK_LAUNCH();
+        const int rc = with_dtype(dtype, [&](auto tv) { return with_nd(nd, [&](auto n) {
+            constexpr int TAPS = decltype(n)::value == 3 ? 64 : 16;
+            hipLaunchKernelGGL((pack_weight_pairs_kernel<decltype(tv), TAPS>), grid, dim3(256), 0, st, tb);
+            return launch_rc();
+        }); });
+        if (rc != CVAE_OK) return rc;
     }
     return CVAE_OK;
 }
@@ -1207,7 +1204,7 @@ extern "C" int cvae_conv_down(const void* L, const void* w, const float* bias, c
     UpVariant var;
     var.xpair = xpair;
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
     if (!L || !w || !S) return CVAE_E_NULLPTR;
     hipStream_t st = (hipStream_t)stream;
@@ -1226,7 +1223,7 @@ extern "C" int cvae_conv_image_supported(const void* L, int64_t lw, int l_dtype,
 extern "C" int cvae_conv_down_image(const void* L, int l_dtype, const float* w, const float* bias, const void* mask, void* S,
                                     int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, int act, void* stream) {
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, 1, nd)) return CVAE_E_BADSHAPE;
-    if ((dtype != CVAE_F32 && dtype != CVAE_BF16) || (l_dtype != CVAE_F32 && l_dtype != CVAE_BF16)) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype) || !dtype_ok(l_dtype)) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
     if (!L || !w || !S) return CVAE_E_NULLPTR;
     if (!cvae_conv_image_supported(L, lw, l_dtype, dtype)) return CVAE_E_UNSUPPORTED;
@@ -1236,7 +1233,7 @@ extern "C" int cvae_conv_down_image_f8(const void* L, int l_dtype, const float* 
                                        void* relu_bits_out, int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int act,
                                        void* stream) {
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, 1, nd)) return CVAE_E_BADSHAPE;
-    if (l_dtype != CVAE_F32 && l_dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(l_dtype)) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
     if (!L || !w || !S || (S8 && !inv_scale_dev)) return CVAE_E_NULLPTR;
     if (!cvae_conv_image_supported(L, lw, l_dtype, CVAE_BF16) && l_dtype != CVAE_BF16) return CVAE_E_UNSUPPORTED;
@@ -1247,7 +1244,7 @@ extern "C" int cvae_conv_down_image_f8(const void* L, int l_dtype, const float* 
 extern "C" int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, float* dW, float* dbias, void* workspace, size_t workspace_bytes,
                                      int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, void* stream) {
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, 1, nd)) return CVAE_E_BADSHAPE;
-    if ((dtype != CVAE_F32 && dtype != CVAE_BF16) || (l_dtype != CVAE_F32 && l_dtype != CVAE_BF16)) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype) || !dtype_ok(l_dtype)) return CVAE_E_DTYPE;
     if (!dW) return CVAE_E_NULLPTR;
     const int taps = (nd == 3) ? 64 : 16;
     if (B == 0) {
@@ -1269,7 +1266,7 @@ extern "C" int cvae_conv_up(const void* S, const void* w, const float* bias, con
     UpVariant var;
     var.upfull = upfull; var.xpair = xpair; var.walk_units = c1_walk_units;
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
     if (!S || !w || !L) return CVAE_E_NULLPTR;
     hipStream_t st = (hipStream_t)stream;
@@ -1303,7 +1300,7 @@ extern "C" int cvae_conv_down_bwd_data(const void* grad, const void* w, const vo
     if (upfull < -1 || upfull > 1 || xpair < -1 || xpair > 1) return CVAE_E_BADSHAPE;
     const int64_t sd = 1, ld = 1;
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (B == 0) return CVAE_OK;
     if (!grad || !w || !dx) return CVAE_E_NULLPTR;
     UpVariant var;
@@ -1334,7 +1331,7 @@ extern "C" int cvae_conv_wgrad(const void* S, const void* L, float* dW, float* d
                                int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs,
                                int64_t ld, int64_t lh, int64_t lw, int64_t Cl, int nd, int dtype, void* stream) {
     if (!geom_ok(B, sd, sh, sw, Cs, ld, lh, lw, Cl, nd)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!dW) return CVAE_E_NULLPTR;
     if (dbias_side != 0 && dbias_side != 1) return CVAE_E_BADSHAPE;
     hipStream_t st = (hipStream_t)stream;
@@ -1369,9 +1366,9 @@ extern "C" int cvae_conv_wgrad(const void* S, const void* L, float* dW, float* d
     if (workspace_bytes < need) return CVAE_E_WORKSPACE;
     GEOM_INIT();
     float* db = bias_mode ? dbias : nullptr;
-    if (dtype == CVAE_BF16)
-        return nd == 3 ? launch_wgrad<bf16, 3>(S, L, (float*)workspace, dW, db, bias_mode, g, st) : launch_wgrad<bf16, 2>(S, L, (float*)workspace, dW, db, bias_mode, g, st);
-    return nd == 3 ? launch_wgrad<float, 3>(S, L, (float*)workspace, dW, db, bias_mode, g, st) : launch_wgrad<float, 2>(S, L, (float*)workspace, dW, db, bias_mode, g, st);
+    return with_dtype(dtype, [&](auto tv) { return with_nd(nd, [&](auto n) {
+        return launch_wgrad<decltype(tv), decltype(n)::value>(S, L, (float*)workspace, dW, db, bias_mode, g, st);
+    }); });
 }
 
 template <typename T, int ND>
@@ -1421,7 +1418,7 @@ extern "C" int cvae_conv_wgrad_multi(int count, const void* const* S, const void
                                      void* const* workspace, const size_t* workspace_bytes, const int64_t* dims, int nd, int dtype, void* stream) {
     if (count < 0 || count > WG_MULTI_MAX || (nd != 2 && nd != 3)) return CVAE_E_BADSHAPE;
     if (count == 0) return CVAE_OK;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!S || !L || !dW || !dbias || !dbias_side || !workspace || !workspace_bytes || !dims) return CVAE_E_NULLPTR;
     for (int i = 0; i < count; ++i) {
         const int64_t* d = dims + 9 * i;
@@ -1434,9 +1431,9 @@ extern "C" int cvae_conv_wgrad_multi(int count, const void* const* S, const void
         if (workspace_bytes[i] < cvae_conv_wgrad_workspace_bytes(Cs, Cl, nd)) return CVAE_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16)
-        return nd == 3 ? wgrad_multi_t<bf16, 3>(count, S, L, dW, dbias, dbias_side, workspace, dims, st) : wgrad_multi_t<bf16, 2>(count, S, L, dW, dbias, dbias_side, workspace, dims, st);
-    return nd == 3 ? wgrad_multi_t<float, 3>(count, S, L, dW, dbias, dbias_side, workspace, dims, st) : wgrad_multi_t<float, 2>(count, S, L, dW, dbias, dbias_side, workspace, dims, st);
+    return with_dtype(dtype, [&](auto tv) { return with_nd(nd, [&](auto n) {
+        return wgrad_multi_t<decltype(tv), decltype(n)::value>(count, S, L, dW, dbias, dbias_side, workspace, dims, st);
+    }); });
 }
 
 // ---------------------------------------------------------------------------------------------- fp8 (e4m3) products
@@ -1461,7 +1458,7 @@ __global__ void quantize_fp8_kernel(const void* __restrict__ src, int src_dtype,
 }
 extern "C" int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int64_t n, float inv_scale, const float* inv_scale_dev, void* amax_slots, void* stream) {
     if (n < 0 || (!inv_scale_dev && !(inv_scale > 0.f))) return CVAE_E_BADSHAPE;
-    if (src_dtype != CVAE_F32 && src_dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(src_dtype)) return CVAE_E_DTYPE;
     if (n == 0) return CVAE_OK;
     if (!src || !dst) return CVAE_E_NULLPTR;
     hipLaunchKernelGGL(quantize_fp8_kernel, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, src, src_dtype, (fp8*)dst, n, inv_scale, inv_scale_dev, (unsigned*)amax_slots);
@@ -1470,7 +1467,7 @@ extern "C" int cvae_quantize_fp8(const void* src, int src_dtype, void* dst, int6
 }
 extern "C" int cvae_absmax(const void* src, int dtype, int64_t n, void* amax_slots, void* stream) {
     if (n < 0) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (n == 0) return CVAE_OK;
     if (!src || !amax_slots) return CVAE_E_NULLPTR;
     hipLaunchKernelGGL(absmax_kernel, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, src, dtype, n, (unsigned*)amax_slots);

@@ -814,19 +814,18 @@ extern "C" size_t cvae_conv_s1_wgrad_workspace_bytes(int64_t B, int64_t H, int64
 extern "C" int cvae_conv_s1_wgrad(const void* x, const void* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t C, int form, int dtype,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     if (B <= 0 || !s1_dims_ok(B, H, W) || s1w_tiles(B, H, W) > 0x7fffffff) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     const size_t need = cvae_conv_s1_wgrad_workspace_bytes(B, H, W, C, form);
     if (need == 0) return CVAE_E_UNSUPPORTED;
     if (!x || !g || !dW) return CVAE_E_NULLPTR;
     if (!aligned16(x) || !aligned16(g) || !aligned16(workspace)) return CVAE_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < need) return CVAE_E_WORKSPACE;
     const S1WArgs a{x, g, dW, dbias, (float*)workspace, B, H, W, (hipStream_t)stream};
-    int rc = CVAE_E_UNSUPPORTED;
-    with_dtype(dtype, [&](auto tv) {
-        using T = decltype(tv);
-        s1w_with_layer(C, form, [&](auto cv, auto fv) { rc = conv_s1_wgrad_launch<T, decltype(cv)::value, decltype(fv)::value>(a); });
+    return with_dtype(dtype, [&](auto tv) {
+        int rc = CVAE_E_UNSUPPORTED;
+        s1w_with_layer(C, form, [&](auto cv, auto fv) { rc = conv_s1_wgrad_launch<decltype(tv), decltype(cv)::value, decltype(fv)::value>(a); });
+        return rc;
     });
-    return rc;
 }
 
 extern "C" size_t cvae_conv_s1_c1_wgrad_workspace_bytes(int64_t B, int64_t H, int64_t W) {
@@ -837,7 +836,7 @@ extern "C" size_t cvae_conv_s1_c1_wgrad_workspace_bytes(int64_t B, int64_t H, in
 extern "C" int cvae_conv_s1_c1_wgrad(const void* x, const float* g, float* dW, float* dbias, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, void* workspace,
                                      size_t workspace_bytes, void* stream) {
     if (B <= 0 || !c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
     if (!x || !g || !dW) return CVAE_E_NULLPTR;
     if (!aligned16(x)) return CVAE_E_UNSUPPORTED;
@@ -845,11 +844,12 @@ extern "C" int cvae_conv_s1_c1_wgrad(const void* x, const float* g, float* dW, f
     const int blocks = (int)c1w_blocks(B, H, W);
     const hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    with_dtype(dtype, [&](auto tv) {
+    const int rc = with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(conv_s1_c1_wgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, g, part, B, (int)H, (int)W);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
+    if (rc != CVAE_OK) return rc;
     hipLaunchKernelGGL(c1w_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)part, dW, dbias, blocks);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -857,19 +857,18 @@ extern "C" int cvae_conv_s1_c1_wgrad(const void* x, const float* g, float* dW, f
 
 extern "C" int cvae_latent_to_grid_wgrad(const void* g, const float* z, float* dW, float* dbias, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream) {
     if (B <= 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
     if (!g || !z || !dW) return CVAE_E_NULLPTR;
     if (!aligned16(z) || !aligned16(dW)) return CVAE_E_UNSUPPORTED;
     const int64_t blocks = (P * C + L2GW_ROWS - 1) / L2GW_ROWS;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(l2g_wgrad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)g, z, dW, dbias, B, (int)K, P, (int)C);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }
 
 extern "C" int64_t cvae_conv_s1_weight_elems(int64_t Cin, int64_t Cout, int form) {
@@ -902,7 +901,7 @@ extern "C" int cvae_conv_s1_pack_weights(int count, const float* const* w, void*
 extern "C" int cvae_conv_s1(const void* x, const void* w, const float* bias, const void* resid, void* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                             int form, int dtype, int act, void* stream) {
     if (!s1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL) return CVAE_E_UNSUPPORTED;
     if (cvae_conv_s1_weight_elems(Cin, Cout, form) == 0 || !s1_act_ok(act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
@@ -920,7 +919,7 @@ extern "C" int cvae_conv_s1(const void* x, const void* w, const float* bias, con
 extern "C" int cvae_conv_s1_c1(const void* x, const float* w, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int act,
                                void* stream) {
     if (!c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!x || !w || !y) return CVAE_E_NULLPTR;
@@ -928,17 +927,16 @@ extern "C" int cvae_conv_s1_c1(const void* x, const float* w, const float* bias,
     const int64_t total = B * H * ((W + 3) >> 2), blocks = (total + 255) / 256;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(conv_s1_c1_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, w, bias, y, B, (int)H, (int)W, act);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }
 
 extern "C" int cvae_latent_to_grid(const float* z, const float* W, const float* bias, void* out, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* stream) {
     if (B < 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (B > L2G_BT || K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!z || !W || !out) return CVAE_E_NULLPTR;
@@ -946,18 +944,17 @@ extern "C" int cvae_latent_to_grid(const float* z, const float* W, const float* 
     const int64_t blocks = (P * (C >> 5) + 3) / 4;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(latent_to_grid_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, z, W, bias, (T*)out, (int)B, (int)K, P, (int)C);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }
 
 extern "C" int cvae_conv_s1_bwd_data(const void* g, const void* w, const void* resid, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t C, int form,
                                      int dtype, int gate_act, void* stream) {
     if (!s1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (form != CVAE_CONV_S1_K3 && form != CVAE_CONV_S1_SUBPIXEL_T) return CVAE_E_UNSUPPORTED;
     if (cvae_conv_s1_weight_elems(C, form == CVAE_CONV_S1_K3 ? C : 16, form) == 0 || !s1_act_ok(gate_act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
@@ -976,7 +973,7 @@ extern "C" int cvae_conv_s1_bwd_data(const void* g, const void* w, const void* r
 extern "C" int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const void* gate, void* dx, int64_t B, int64_t H, int64_t W, int64_t Cin, int dtype, int gate_act,
                                         void* stream) {
     if (!c1_dims_ok(B, H, W)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (Cin != C1_CIN) return CVAE_E_UNSUPPORTED;
     if (!s1_act_ok(gate_act)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
@@ -986,12 +983,11 @@ extern "C" int cvae_conv_s1_c1_bwd_data(const float* g, const float* w, const vo
     const int64_t blocks = (B * H * W + 255) / 256;
     if (blocks > 0x7fffffff) return CVAE_E_BADSHAPE;
     const hipStream_t st = (hipStream_t)stream;
-    with_dtype(dtype, [&](auto tv) {
+    return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL(conv_s1_c1_bwd_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, w, (const T*)gate, (T*)dx, B, (int)H, (int)W, gate_act);
+        return launch_rc();
     });
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
 }
 
 extern "C" size_t cvae_latent_to_grid_bwd_workspace_bytes(int64_t B, int64_t K, int64_t P, int64_t C) {
@@ -1002,7 +998,7 @@ extern "C" size_t cvae_latent_to_grid_bwd_workspace_bytes(int64_t B, int64_t K, 
 extern "C" int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz, int64_t B, int64_t K, int64_t P, int64_t C, int dtype, void* workspace,
                                        size_t workspace_bytes, void* stream) {
     if (B < 0 || K <= 0 || P <= 0 || C <= 0 || P * C > ((int64_t)1 << 40)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (B > L2G_BT || K > L2G_KMAX || (K & 3) || (C & 31)) return CVAE_E_UNSUPPORTED;
     if (B == 0) return CVAE_OK;
     if (!g || !W || !dz) return CVAE_E_NULLPTR;
@@ -1018,8 +1014,7 @@ extern "C" int cvae_latent_to_grid_bwd(const void* g, const float* W, float* dz,
         using T = decltype(tv);
         if (cvae_allow_lds<l2g_bwd_kernel<T>>(lds) != CVAE_OK) return CVAE_E_LAUNCH;
         hipLaunchKernelGGL(l2g_bwd_kernel<T>, dim3((unsigned)slabs), dim3(256), lds, st, (const T*)g, W, part, (int)B, (int)K, P, (int)C, kq_pad);
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return launch_rc();
     });
     if (rc != CVAE_OK) return rc;
     const int n = (int)(B * K);

@@ -10,26 +10,16 @@ __global__ void cast_kernel(const TS* __restrict__ src, TD* __restrict__ dst, in
         dst[i] = from_f32<TD>(to_f32(src[i]));
 }
 
-template <typename F>
-static int dispatch2(int sd, int dd, F&& f) {
-    if (sd == CVAE_F32 && dd == CVAE_F32) return f((const float*)0, (float*)0);
-    if (sd == CVAE_F32 && dd == CVAE_BF16) return f((const float*)0, (bf16*)0);
-    if (sd == CVAE_BF16 && dd == CVAE_F32) return f((const bf16*)0, (float*)0);
-    if (sd == CVAE_BF16 && dd == CVAE_BF16) return f((const bf16*)0, (bf16*)0);
-    return CVAE_E_DTYPE;
-}
-
 extern "C" int cvae_cast(const void* src, void* dst, int64_t n, int sd, int dd, void* stream) {
     if (n < 0) return CVAE_E_BADSHAPE;
     if (n == 0) return CVAE_OK;
     if (!src || !dst) return CVAE_E_NULLPTR;
-    return dispatch2(sd, dd, [&](auto* s, auto* d) {
-        using TS = std::remove_const_t<std::remove_pointer_t<decltype(s)>>;
-        using TD = std::remove_pointer_t<decltype(d)>;
+    return with_dtype2(sd, dd, [&](auto s, auto d) {
+        using TS = decltype(s);
+        using TD = decltype(d);
         hipLaunchKernelGGL((cast_kernel<TS, TD>), dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream,
                            (const TS*)src, (TD*)dst, n);
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return launch_rc();
     });
 }
 
@@ -80,14 +70,13 @@ static int transpose_cs(const void* src, void* dst, int64_t B, int64_t C, int64_
     if (!src || !dst) return CVAE_E_NULLPTR;
     if (C == 1) return cvae_cast(src, dst, B * S, sd, dd, stream);
     if (B > 65535 || (C + 63) / 64 > 65535) return CVAE_E_BADSHAPE;
-    return dispatch2(sd, dd, [&](auto* s, auto* d) {
-        using TS = std::remove_const_t<std::remove_pointer_t<decltype(s)>>;
-        using TD = std::remove_pointer_t<decltype(d)>;
+    return with_dtype2(sd, dd, [&](auto s, auto d) {
+        using TS = decltype(s);
+        using TD = decltype(d);
         dim3 grid((unsigned)((S + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)B);
         hipLaunchKernelGGL((transpose_cs_kernel<TS, TD, TO_NSC>), grid, dim3(256), 0, (hipStream_t)stream,
                            (const TS*)src, (TD*)dst, C, S);
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return launch_rc();
     });
 }
 extern "C" int cvae_ncs_to_nsc(const void* src, void* dst, int64_t B, int64_t C, int64_t S, int sd, int dd, void* stream) {
@@ -156,13 +145,11 @@ extern "C" int cvae_act_bwd(const void* dy, const void* y, void* dx, int64_t n, 
     if (n < 0) return CVAE_E_BADSHAPE;
     if (n == 0) return CVAE_OK;
     if (!dy || !y || !dx) return CVAE_E_NULLPTR;
-    if (dtype == CVAE_F32)
-        hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)y, (float*)dx, n, act);
-    else if (dtype == CVAE_BF16)
-        hipLaunchKernelGGL(act_bwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy, (const bf16*)y, (bf16*)dx, n, act);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, n, act);
+        return launch_rc();
+    });
 }
 
 template <typename T>
@@ -174,11 +161,11 @@ extern "C" int cvae_act_fwd(const void* x, void* y, int64_t n, int act, int dtyp
     if (n < 0) return CVAE_E_BADSHAPE;
     if (n == 0) return CVAE_OK;
     if (!x || !y) return CVAE_E_NULLPTR;
-    if (dtype == CVAE_F32) hipLaunchKernelGGL(act_fwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, n, act);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(act_fwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)y, n, act);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(act_fwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, act);
+        return launch_rc();
+    });
 }
 
 // ------------------------------------------------------------------------------------- channel sum
@@ -362,10 +349,9 @@ extern "C" int cvae_channel_sum(const void* x, float* out, int64_t P, int64_t C,
     if (!out) return CVAE_E_NULLPTR;
     if (P == 0) return hipMemsetAsync(out, 0, C * sizeof(float), (hipStream_t)stream) == hipSuccess ? CVAE_OK : CVAE_E_LAUNCH;
     if (!x) return CVAE_E_NULLPTR;
-    int rc;
-    if (dtype == CVAE_F32) rc = channel_sum_launch<float>((const float*)x, out, P, C, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-    else if (dtype == CVAE_BF16) rc = channel_sum_launch<bf16>((const bf16*)x, out, P, C, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-    else return CVAE_E_DTYPE;
+    const int rc = with_dtype(dtype, [&](auto tv) {
+        return channel_sum_launch((const decltype(tv)*)x, out, P, C, (float*)workspace, workspace_bytes, (hipStream_t)stream);
+    });
     if (rc != CVAE_OK) return rc;
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -447,18 +433,18 @@ extern "C" int cvae_adaptive_avgpool_fwd(const void* x, float* out, int64_t B, i
     if (OD == D && OH == H && OW == W && D * H * W < ((int64_t)1 << 22) && C < ((int64_t)1 << 22) && B <= 65535 && dtype != CVAE_FP8) {   // bare Flatten
         const int V = (int)(D * H * W);
         const dim3 grid((unsigned)((V + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)B);
-        if (dtype == CVAE_F32) hipLaunchKernelGGL(flatten_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, out, V, (int)C, out_stride);
-        else if (dtype == CVAE_BF16) hipLaunchKernelGGL(flatten_fwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out, V, (int)C, out_stride);
-        else return CVAE_E_DTYPE;
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(dtype, [&](auto tv) {
+            using T = decltype(tv);
+            hipLaunchKernelGGL(flatten_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, out, V, (int)C, out_stride);
+            return launch_rc();
+        });
     }
     const int64_t n = B * OD * OH * OW * C;
-    if (dtype == CVAE_F32) hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, out, B, D, H, W, C, OD, OH, OW, out_stride);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(avgpool_fwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out, B, D, H, W, C, OD, OH, OW, out_stride);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, out, B, D, H, W, C, OD, OH, OW, out_stride);
+        return launch_rc();
+    });
 }
 
 template <typename T>
@@ -496,18 +482,18 @@ extern "C" int cvae_adaptive_avgpool_bwd(const float* dout, const void* mask, vo
     if (OD == D && OH == H && OW == W && D * H * W < ((int64_t)1 << 22) && C < ((int64_t)1 << 22) && B <= 65535 && dtype != CVAE_FP8) {   // bare Flatten
         const int V = (int)(D * H * W);
         const dim3 grid((unsigned)((V + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)B);
-        if (dtype == CVAE_F32) hipLaunchKernelGGL(flatten_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, dout, (const float*)mask, (float*)dx, V, (int)C, dstride);
-        else if (dtype == CVAE_BF16) hipLaunchKernelGGL(flatten_bwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, dout, (const bf16*)mask, (bf16*)dx, V, (int)C, dstride);
-        else return CVAE_E_DTYPE;
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(dtype, [&](auto tv) {
+            using T = decltype(tv);
+            hipLaunchKernelGGL(flatten_bwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, dout, (const T*)mask, (T*)dx, V, (int)C, dstride);
+            return launch_rc();
+        });
     }
     const int64_t n = B * D * H * W * C;
-    if (dtype == CVAE_F32) hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, dout, (const float*)mask, (float*)dx, B, D, H, W, C, OD, OH, OW, dstride);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(avgpool_bwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, dout, (const bf16*)mask, (bf16*)dx, B, D, H, W, C, OD, OH, OW, dstride);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, dout, (const T*)mask, (T*)dx, B, D, H, W, C, OD, OH, OW, dstride);
+        return launch_rc();
+    });
 }
 
 // ------------------------------------------------------------------------------------- linear resize
@@ -617,18 +603,18 @@ extern "C" int cvae_upsample_linear_fwd(const void* src, float* dst, int64_t B, 
     if (!src || !dst) return CVAE_E_NULLPTR;
     if (is_exact_2x(B, d, h, w, D, H, W, C)) {
         const int64_t n4 = B * D * H * (W / 4);
-        if (dtype == CVAE_F32) hipLaunchKernelGGL(upsample2x_fwd_kernel<float>, dim3(cvae_grid_1d(n4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)src, dst, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
-        else if (dtype == CVAE_BF16) hipLaunchKernelGGL(upsample2x_fwd_kernel<bf16>, dim3(cvae_grid_1d(n4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, dst, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
-        else return CVAE_E_DTYPE;
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(dtype, [&](auto tv) {
+            using T = decltype(tv);
+            hipLaunchKernelGGL(upsample2x_fwd_kernel<T>, dim3(cvae_grid_1d(n4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)src, dst, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
+            return launch_rc();
+        });
     }
     const int64_t n = B * D * H * W * C;
-    if (dtype == CVAE_F32) hipLaunchKernelGGL(upsample_fwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)src, dst, B, d, h, w, D, H, W, C);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(upsample_fwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, dst, B, d, h, w, D, H, W, C);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(upsample_fwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)src, dst, B, d, h, w, D, H, W, C);
+        return launch_rc();
+    });
 }
 
 // Gather form of the transpose: for source index i, the destination indices whose taps touch i lie in
@@ -686,16 +672,16 @@ extern "C" int cvae_upsample_linear_bwd(const float* ddst, void* dsrc, int64_t B
     if (!ddst || !dsrc) return CVAE_E_NULLPTR;
     if (is_exact_2x(B, d, h, w, D, H, W, C)) {
         const int64_t ns = B * d * h * w;
-        if (dtype == CVAE_F32) hipLaunchKernelGGL(upsample2x_bwd_kernel<float>, dim3(cvae_grid_1d(ns, 256, 8192)), dim3(256), 0, (hipStream_t)stream, ddst, (float*)dsrc, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
-        else if (dtype == CVAE_BF16) hipLaunchKernelGGL(upsample2x_bwd_kernel<bf16>, dim3(cvae_grid_1d(ns, 256, 8192)), dim3(256), 0, (hipStream_t)stream, ddst, (bf16*)dsrc, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
-        else return CVAE_E_DTYPE;
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(dtype, [&](auto tv) {
+            using T = decltype(tv);
+            hipLaunchKernelGGL(upsample2x_bwd_kernel<T>, dim3(cvae_grid_1d(ns, 256, 8192)), dim3(256), 0, (hipStream_t)stream, ddst, (T*)dsrc, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W);
+            return launch_rc();
+        });
     }
     const int64_t n = B * d * h * w * C;
-    if (dtype == CVAE_F32) hipLaunchKernelGGL(upsample_bwd_kernel<float>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, ddst, (float*)dsrc, B, d, h, w, D, H, W, C);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(upsample_bwd_kernel<bf16>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, ddst, (bf16*)dsrc, B, d, h, w, D, H, W, C);
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(cvae_grid_1d(n, 256)), dim3(256), 0, (hipStream_t)stream, ddst, (T*)dsrc, B, d, h, w, D, H, W, C);
+        return launch_rc();
+    });
 }

@@ -440,10 +440,12 @@ static int gemm_f32(const float* A, const float* Bm, float* C, const float* bias
         const dim3 grid((unsigned)(tn128 * tm128 * sp));
         const bool akc = sak == 1, bkc = sbk == 1;
         const int n_slow = N > M;
-#define T128(AK, BKC) hipLaunchKernelGGL((gemm_bf16_t128_kernel<AK, BKC, GEMM_T128_BK>), grid, dim3(256), 0, stream, A, Bm, C, bias, M, N, K, sam, sak, sbk, sbn, ldc, kps, act, sl, (int)tn128, (int)tm128, n_slow, sl ? EpiMul{nullptr, 0, 0} : em)
-        if (akc) { if (bkc) T128(true, true); else T128(true, false); } else { if (bkc) T128(false, true); else T128(false, false); }
-#undef T128
-        CVAE_CHECK_LAUNCH();
+        const int rc = with_bool(akc, [&](auto ak) { return with_bool(bkc, [&](auto bk) {
+            hipLaunchKernelGGL((gemm_bf16_t128_kernel<decltype(ak)::value, decltype(bk)::value, GEMM_T128_BK>), grid, dim3(256), 0, stream, A, Bm, C, bias, M, N, K, sam, sak, sbk, sbn,
+                               ldc, kps, act, sl, (int)tn128, (int)tm128, n_slow, sl ? EpiMul{nullptr, 0, 0} : em);
+            return launch_rc();
+        }); });
+        if (rc != CVAE_OK) return rc;
         if (sl) {
             hipLaunchKernelGGL(slab_sum_bias_act_kernel, dim3(cvae_grid_1d(M * N, 256)), dim3(256), 0, stream, (const float*)sl, (int)sp, C, bias, M, N, ldc, act, em);
             CVAE_CHECK_LAUNCH();

@@ -407,23 +407,22 @@ extern "C" int cvae_up2x_fwd(const void* src, float* dst, int64_t B, int64_t d, 
     if (!src || !dst) return CVAE_E_NULLPTR;
     const unsigned grid = (unsigned)((B * d * h * (w / 4) + 255) / 256);
     const bool stream_out = B * D * H * W * 4 >= UP2X_STREAM_BYTES;
-    if (D == 2 * d && d % 2 == 0 && h % 8 == 0 && w % 64 == 0 && (dtype == CVAE_BF16 || dtype == CVAE_F32)) {      // rows of 64: the LDS-tiled form
+    if (D == 2 * d && d % 2 == 0 && h % 8 == 0 && w % 64 == 0) {      // rows of 64: the LDS-tiled form
         const dim3 tgrid((unsigned)(B * (d / 2) * (h / 8) * (w / 64)));
         hipStream_t st = (hipStream_t)stream;
-#define UP2X_TILE(T, NT) hipLaunchKernelGGL((up2x_tile_kernel<T, NT>), tgrid, dim3(256), 0, st, (const T*)src, dst, (int)d, (int)h, (int)w)
-        if (dtype == CVAE_BF16) { if (stream_out) UP2X_TILE(bf16, true); else UP2X_TILE(bf16, false); }
-        else { if (stream_out) UP2X_TILE(float, true); else UP2X_TILE(float, false); }
-#undef UP2X_TILE
-        CVAE_CHECK_LAUNCH();
-        return CVAE_OK;
+        return with_dtype(dtype, [&](auto tv) { return with_bool(stream_out, [&](auto nt) {
+            using T = decltype(tv);
+            hipLaunchKernelGGL((up2x_tile_kernel<T, decltype(nt)::value>), tgrid, dim3(256), 0, st, (const T*)src, dst, (int)d, (int)h, (int)w);
+            return launch_rc();
+        }); });
     }
-#define UP2X_FWD(T, MODE) hipLaunchKernelGGL((up2x_block_kernel<T, MODE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, nullptr, dst, nullptr, nullptr, 0.f, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W, SmallBwd{}, ElboFinish{})
-    if (dtype == CVAE_BF16) { if (stream_out) UP2X_FWD(bf16, 4); else UP2X_FWD(bf16, 0); }
-    else if (dtype == CVAE_F32) { if (stream_out) UP2X_FWD(float, 4); else UP2X_FWD(float, 0); }
-#undef UP2X_FWD
-    else return CVAE_E_DTYPE;
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) { return with_bool(stream_out, [&](auto nt) {
+        using T = decltype(tv);
+        constexpr int MODE = decltype(nt)::value ? 4 : 0;      // plain resize, streamed out or not
+        hipLaunchKernelGGL((up2x_block_kernel<T, MODE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, nullptr, dst, nullptr, nullptr, 0.f, (int)B, (int)d, (int)h,
+                           (int)w, (int)D, (int)H, (int)W, SmallBwd{}, ElboFinish{});
+        return launch_rc();
+    }); });
 }
 
 extern "C" int64_t cvae_elbo_up2x_partials(int64_t B, int64_t d, int64_t h, int64_t w) { return (B * d * h * (w / 4) + 255) / 256; }
@@ -433,16 +432,19 @@ extern "C" int cvae_elbo_up2x_fwd(const void* src, const float* x, const float* 
                                   int64_t n_m, int64_t n_z, int dtype, void* stream) {
     if (!up2x_ok(B, d, h, w, D, H, W) || n_m < 0 || n_z < 0 || n_m > (1 << 24) || n_z > (1 << 24)) return CVAE_E_UNSUPPORTED;
     if (!src || !x || !m_hat || !m || !mu || !logvar || !out4 || !partial) return CVAE_E_NULLPTR;
-    if (dtype != CVAE_BF16 && dtype != CVAE_F32) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (bump && !ticket) return CVAE_E_NULLPTR;              // the counter rides on the in-launch finish
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)cvae_elbo_up2x_partials(B, d, h, w);
     const ElboFinish fin{(unsigned*)ticket, m_hat, m, mu, logvar, out4, bump, gamma, (int)n_m, (int)n_z};
-#define ELBO_FWD(T, MODE) hipLaunchKernelGGL((up2x_block_kernel<T, MODE>), dim3(grid), dim3(256), 0, st, (const T*)src, x, t1, partial, nullptr, 0.f, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, (int)W, SmallBwd{}, fin)
-    if (dtype == CVAE_BF16) { if (t1) ELBO_FWD(bf16, 3); else ELBO_FWD(bf16, 1); }
-    else { if (t1) ELBO_FWD(float, 3); else ELBO_FWD(float, 1); }
-#undef ELBO_FWD
-    CVAE_CHECK_LAUNCH();
+    const int rc = with_dtype(dtype, [&](auto tv) { return with_bool(t1 != nullptr, [&](auto keep) {
+        using T = decltype(tv);
+        constexpr int MODE = decltype(keep)::value ? 3 : 1;    // loss partials, with or without the residual kept for the backward pass
+        hipLaunchKernelGGL((up2x_block_kernel<T, MODE>), dim3(grid), dim3(256), 0, st, (const T*)src, x, t1, partial, nullptr, 0.f, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H,
+                           (int)W, SmallBwd{}, fin);
+        return launch_rc();
+    }); });
+    if (rc != CVAE_OK) return rc;
     if (!ticket) {
         hipLaunchKernelGGL(elbo_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, (int)grid, m_hat, m, mu, logvar, gamma, out4, (int)n_m, (int)n_z);
         CVAE_CHECK_LAUNCH();
@@ -455,12 +457,13 @@ extern "C" int cvae_elbo_up2x_bwd(const float* t1, const float* m_hat, const flo
                                   int64_t n_m, int64_t n_z, int dtype, void* stream) {
     if (!up2x_ok(B, d, h, w, D, H, W) || n_m < 0 || n_z < 0 || n_m > (1 << 24) || n_z > (1 << 24)) return CVAE_E_UNSUPPORTED;
     if (!t1 || !m_hat || !m || !mu || !logvar || !dsrc || !d_mhat || !dmu || !dlv) return CVAE_E_NULLPTR;
-    if (dtype != CVAE_BF16 && dtype != CVAE_F32) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((B * d * h * (w / 4) + 255) / 256);
     const SmallBwd sb{m_hat, m, mu, logvar, d_mhat, dmu, dlv, gamma, (int)n_m, (int)n_z, (int)grid};
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL(up2x_bwd_b_kernel<bf16>, dim3(grid + 1), dim3(256), 0, st, t1, (bf16*)dsrc, g_loss, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, sb);
-    else hipLaunchKernelGGL(up2x_bwd_b_kernel<float>, dim3(grid + 1), dim3(256), 0, st, t1, (float*)dsrc, g_loss, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, sb);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(up2x_bwd_b_kernel<T>, dim3(grid + 1), dim3(256), 0, st, t1, (T*)dsrc, g_loss, (int)B, (int)d, (int)h, (int)w, (int)D, (int)H, sb);
+        return launch_rc();
+    });
 }

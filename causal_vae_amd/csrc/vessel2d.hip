@@ -290,9 +290,10 @@ extern "C" int cvae_bn2d_fwd(const void* x, const float* gamma, const float* bet
         if (workspace_bytes < cvae_bn2d_workspace_bytes(P, C) / 2) return CVAE_E_WORKSPACE;
     }
     float* ws = (float*)workspace;
-    if (dtype == CVAE_BF16) return bn2d_fwd_t<bf16>((const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, training, act, ws, (hipStream_t)stream);
-    if (dtype == CVAE_F32) return bn2d_fwd_t<float>((const float*)x, gamma, beta, (float*)y, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, training, act, ws, (hipStream_t)stream);
-    return CVAE_E_DTYPE;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        return bn2d_fwd_t((const T*)x, gamma, beta, (T*)y, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, training, act, ws, (hipStream_t)stream);
+    });
 }
 extern "C" int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
                              float* dbeta, int64_t P, int64_t C, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
@@ -300,7 +301,8 @@ extern "C" int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const
     if (!x || !dy || !y || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return CVAE_E_NULLPTR;
     if (workspace_bytes < cvae_bn2d_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
     float* ws = (float*)workspace;
-    if (dtype == CVAE_BF16) return bn2d_bwd_t<bf16>((const bf16*)x, (const bf16*)dy, (const bf16*)y, gamma, mean, rstd, (bf16*)dx, dgamma, dbeta, P, (int)C, act, ws, (hipStream_t)stream);
-    if (dtype == CVAE_F32) return bn2d_bwd_t<float>((const float*)x, (const float*)dy, (const float*)y, gamma, mean, rstd, (float*)dx, dgamma, dbeta, P, (int)C, act, ws, (hipStream_t)stream);
-    return CVAE_E_DTYPE;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        return bn2d_bwd_t((const T*)x, (const T*)dy, (const T*)y, gamma, mean, rstd, (T*)dx, dgamma, dbeta, P, (int)C, act, ws, (hipStream_t)stream);
+    });
 }

@@ -503,19 +503,21 @@ extern "C" int cvae_fold_bn_conv_bwd(int count, const float* const* w, const int
 }
 
 extern "C" size_t cvae_row_diff_norms_workspace_bytes(int64_t rows, int64_t n, int dtype) {
-    if (rows <= 0 || n <= 0 || (dtype != CVAE_F32 && dtype != CVAE_BF16)) return 0;
+    if (rows <= 0 || n <= 0 || !dtype_ok(dtype)) return 0;
     return (size_t)rows * row_diff_chunks(n, dtype) * 2 * sizeof(float);
 }
 extern "C" int cvae_row_diff_norms(const void* a, const void* b, const int64_t* ref, float* l2, float* mean_abs, int64_t rows, int64_t b_rows, int64_t n,
                                    int dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (rows <= 0 || b_rows <= 0 || n <= 0 || (!ref && b_rows < rows)) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (row_diff_chunks(n, dtype) > 0x7fffffff) return CVAE_E_BADSHAPE;
     if (!a || !b || !l2 || !workspace) return CVAE_E_NULLPTR;
     if (workspace_bytes < cvae_row_diff_norms_workspace_bytes(rows, n, dtype)) return CVAE_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) return row_diff_t<bf16>((const bf16*)a, (const bf16*)b, ref, l2, mean_abs, rows, b_rows, n, (float*)workspace, st);
-    return row_diff_t<float>((const float*)a, (const float*)b, ref, l2, mean_abs, rows, b_rows, n, (float*)workspace, st);
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        return row_diff_t((const T*)a, (const T*)b, ref, l2, mean_abs, rows, b_rows, n, (float*)workspace, st);
+    });
 }
 
 extern "C" int cvae_stack_mean_std(const float* const* x, int count, float* mean, float* stdv, int64_t n, void* stream) {

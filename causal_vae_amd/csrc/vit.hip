@@ -711,38 +711,40 @@ __global__ __launch_bounds__(256) void vit_attention_bwd_kernel(const AttBwdArgs
 
 }  // namespace
 
+static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
+
 extern "C" int cvae_vit_tokens(const void* stem, int stem_dtype, const float* cls, const float* pos, float* tokens, int64_t B, int64_t n_patches, void* stream) {
     if (B < 1 || n_patches < 1 || B * (n_patches + 1) > ((int64_t)1 << 32)) return CVAE_E_BADSHAPE;
-    if (stem_dtype != CVAE_F32 && stem_dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(stem_dtype)) return CVAE_E_DTYPE;
     if (!stem || !cls || !pos || !tokens) return CVAE_E_NULLPTR;
     if (!aligned16(stem) || !aligned16(cls) || !aligned16(pos) || !aligned16(tokens)) return CVAE_E_UNSUPPORTED;
     const int blocks = cvae_grid_1d(B * (n_patches + 1) * (VIT_DIM / 4), 256, 256 * 32);
-    if (stem_dtype == CVAE_BF16)
-        hipLaunchKernelGGL(vit_tokens_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)stem, cls, pos, tokens, B, n_patches);
-    else
-        hipLaunchKernelGGL(vit_tokens_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)stem, cls, pos, tokens, B, n_patches);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(stem_dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(vit_tokens_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)stem, cls, pos, tokens, B, n_patches);
+        return launch_rc();
+    });
 }
 
 extern "C" int cvae_layernorm256(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* y, int64_t rows, float eps, int out_dtype, void* stream) {
     if (rows < 1 || rows > ((int64_t)1 << 32) || x_stride < VIT_DIM || (x_stride & 3)) return CVAE_E_BADSHAPE;
-    if (out_dtype != CVAE_F32 && out_dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(out_dtype)) return CVAE_E_DTYPE;
     if (!x || !gamma || !beta || !y) return CVAE_E_NULLPTR;
     if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((rows + 3) / 4));
-    if (out_dtype == CVAE_BF16) hipLaunchKernelGGL(vit_layernorm_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, x, x_stride, gamma, beta, (bf16*)y, rows, eps);
-    else hipLaunchKernelGGL(vit_layernorm_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, x_stride, gamma, beta, (float*)y, rows, eps);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(out_dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(vit_layernorm_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, x, x_stride, gamma, beta, (T*)y, rows, eps);
+        return launch_rc();
+    });
 }
 
 static int token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y, int64_t y_stride,
                       int64_t M, int64_t K, int64_t N, int epilogue, int max_epilogue, int dtype, void* pre, int64_t pre_stride, void* stream) {
     if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (epilogue < GEMM_EPI_NONE || epilogue > max_epilogue) return CVAE_E_BADSHAPE;
-    if (!((K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256))) return CVAE_E_UNSUPPORTED;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
     if (!x || !W || !bias || !y) return CVAE_E_NULLPTR;
     if (epilogue == CVAE_GEMM_EPI_RESIDUAL && (!resid || resid_stride < N || (resid_stride & 3) || !aligned16(resid))) return resid ? CVAE_E_BADSHAPE : CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4, ye16 = (epilogue == CVAE_GEMM_EPI_RESIDUAL || dtype == CVAE_F32) ? 4 : 8;
@@ -753,8 +755,9 @@ static int token_gemm(const void* x, int64_t x_stride, const float* W, const flo
         if ((pre_stride % e16) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) return gemm_launch<bf16>((const bf16*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
-    return gemm_launch<float>((const float*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
+    return with_dtype(dtype, [&](auto tv) {
+        return gemm_launch((const decltype(tv)*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
+    });
 }
 
 extern "C" int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y,
@@ -770,7 +773,7 @@ extern "C" int cvae_token_gemm_gelu_train(const void* x, int64_t x_stride, const
 static int mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
                     int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, float* lse, void* stream) {
     if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
-    if (dtype != CVAE_F32 && dtype != CVAE_BF16) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!q || !k || !v || !out) return CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
     if (q_stride < VIT_DIM || k_stride < VIT_DIM || v_stride < VIT_DIM || q_batch_stride < 0 || k_batch_stride < 0 || v_batch_stride < 0) return CVAE_E_BADSHAPE;
@@ -780,15 +783,16 @@ static int mhsa_fwd(const void* q, const void* k, const void* v, void* out, int6
     const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
     const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // 1 / sqrt(32) * log2(e)
     hipStream_t st = (hipStream_t)stream;
-#define ATT_ARGS(T) (const T*)q, (const T*)k, (const T*)v, (T*)out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, (int)n_tokens, \
-                    (int)n_query_rows, scale_log2e
-    if (dtype == CVAE_BF16 && lse) hipLaunchKernelGGL(vit_attention_train_kernel<bf16>, grid, dim3(256), 0, st, ATT_ARGS(bf16), lse);
-    else if (dtype == CVAE_BF16) hipLaunchKernelGGL(vit_attention_kernel<bf16>, grid, dim3(256), 0, st, ATT_ARGS(bf16));
-    else if (lse) hipLaunchKernelGGL(vit_attention_train_kernel<float>, grid, dim3(256), 0, st, ATT_ARGS(float), lse);
-    else hipLaunchKernelGGL(vit_attention_kernel<float>, grid, dim3(256), 0, st, ATT_ARGS(float));
-#undef ATT_ARGS
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) { return with_bool(lse != nullptr, [&](auto train) {
+        using T = decltype(tv);
+        auto launch = [&](auto kernel, auto... saved) {       // the training kernel takes the row statistics it saves as one more argument
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride,
+                               v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, saved...);
+        };
+        if constexpr (decltype(train)::value) launch(vit_attention_train_kernel<T>, lse);
+        else launch(vit_attention_kernel<T>);
+        return launch_rc();
+    }); });
 }
 
 extern "C" int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
@@ -804,13 +808,11 @@ extern "C" int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, 
 }
 
 // ---- backward entries.  Every argument check precedes the first launch; workspaces are the caller's.
-static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
-static bool is_dtype(int d) { return d == CVAE_F32 || d == CVAE_BF16; }
 
 extern "C" int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, const void* gate, int gate_act, int64_t B,
                                    int64_t n_patches, void* stream) {
     if (B < 1 || n_patches < 1 || B * (n_patches + 1) > ((int64_t)1 << 32)) return CVAE_E_BADSHAPE;
-    if (!is_dtype(stem_dtype)) return CVAE_E_DTYPE;
+    if (!dtype_ok(stem_dtype)) return CVAE_E_DTYPE;
     if (!dtokens || !dpos || !dcls || !dstem) return CVAE_E_NULLPTR;
     if (gate_act != CVAE_ACT_NONE && gate_act != CVAE_ACT_RELU && gate_act != CVAE_ACT_LEAKY001 && gate_act != CVAE_ACT_LEAKY02) return CVAE_E_UNSUPPORTED;
     if (gate_act == CVAE_ACT_NONE) gate = nullptr;                          // not read: whatever the caller passed
@@ -818,12 +820,11 @@ extern "C" int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcl
     if (!aligned16(dtokens) || !aligned16(dpos) || !aligned16(dcls) || !aligned16(dstem) || !aligned16(gate)) return CVAE_E_UNSUPPORTED;
     const float slope = gate_act == CVAE_ACT_LEAKY02 ? 0.2f : (gate_act == CVAE_ACT_LEAKY001 ? 0.01f : 0.f);
     const int blocks = cvae_grid_1d((n_patches + 1) * (VIT_DIM / 4), 256, 256 * 32);
-    if (stem_dtype == CVAE_BF16)
-        hipLaunchKernelGGL(vit_tokens_bwd_kernel<bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (bf16*)dstem, B, n_patches, (const bf16*)gate, slope);
-    else
-        hipLaunchKernelGGL(vit_tokens_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (float*)dstem, B, n_patches, (const float*)gate, slope);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(stem_dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(vit_tokens_bwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dtokens, dpos, dcls, (T*)dstem, B, n_patches, (const T*)gate, slope);
+        return launch_rc();
+    });
 }
 
 extern "C" size_t cvae_layernorm256_bwd_workspace_bytes(int64_t rows) {
@@ -833,19 +834,19 @@ extern "C" size_t cvae_layernorm256_bwd_workspace_bytes(int64_t rows) {
 extern "C" int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtype, const float* x, int64_t x_stride, const float* gamma, float* dx, int64_t dx_stride,
                                      int accumulate, float* dgamma, float* dbeta, int64_t rows, float eps, void* workspace, size_t workspace_bytes, void* stream) {
     if (rows < 1 || rows > ((int64_t)1 << 32) || x_stride < VIT_DIM || (x_stride & 3) || dx_stride < VIT_DIM || (dx_stride & 3) || g_stride < VIT_DIM) return CVAE_E_BADSHAPE;
-    if (!is_dtype(g_dtype)) return CVAE_E_DTYPE;
+    if (!dtype_ok(g_dtype)) return CVAE_E_DTYPE;
     if (!g || !x || !gamma || !dx || !dgamma || !dbeta || !workspace) return CVAE_E_NULLPTR;
     if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || !aligned16(g) || !aligned16(x) || !aligned16(gamma) || !aligned16(dx) || !aligned16(workspace)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_layernorm256_bwd_workspace_bytes(rows)) return CVAE_E_WORKSPACE;
     const int64_t nslab = (rows + LN_SLAB - 1) / LN_SLAB;
     hipStream_t st = (hipStream_t)stream;
-    if (g_dtype == CVAE_BF16)
-        hipLaunchKernelGGL(vit_layernorm_bwd_kernel<bf16>, dim3((unsigned)nslab), dim3(256), 0, st, (const bf16*)g, g_stride, x, x_stride, gamma, dx, dx_stride,
-                           (float*)workspace, rows, eps, accumulate);
-    else
-        hipLaunchKernelGGL(vit_layernorm_bwd_kernel<float>, dim3((unsigned)nslab), dim3(256), 0, st, (const float*)g, g_stride, x, x_stride, gamma, dx, dx_stride,
-                           (float*)workspace, rows, eps, accumulate);
-    CVAE_CHECK_LAUNCH();
+    const int rc = with_dtype(g_dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(vit_layernorm_bwd_kernel<T>, dim3((unsigned)nslab), dim3(256), 0, st, (const T*)g, g_stride, x, x_stride, gamma, dx, dx_stride, (float*)workspace, rows,
+                           eps, accumulate);
+        return launch_rc();
+    });
+    if (rc != CVAE_OK) return rc;
     hipLaunchKernelGGL(vit_colsum_finish_kernel, dim3(1), dim3(512), 0, st, (const float*)workspace, nslab, dgamma, dbeta);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -854,7 +855,7 @@ extern "C" int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtyp
 extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
                                         int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
     if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K) return CVAE_E_BADSHAPE;
-    if (!is_dtype(dtype) || !is_dtype(g_dtype) || !is_dtype(dx_dtype)) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype) || !dtype_ok(g_dtype) || !dtype_ok(dx_dtype)) return CVAE_E_DTYPE;
     if (dtype == CVAE_F32 && (g_dtype != CVAE_F32 || dx_dtype != CVAE_F32)) return CVAE_E_DTYPE;
     if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
     if (!g || !W || !dx) return CVAE_E_NULLPTR;
@@ -866,17 +867,14 @@ extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_d
         return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
     hipStream_t st = (hipStream_t)stream;
-#define BWD_DATA(T, TG, TO)                                                                                                                                   \
-    hipLaunchKernelGGL((vit_gemm_bwd_data_kernel<T, TG, TO>), grid, dim3(256), 0, st, (const TG*)g, g_stride, W, (const T*)pre, pre_stride, resid, resid_stride, \
-                       (TO*)dx, dx_stride, M, (int)K, (int)N)
-    if (dtype == CVAE_F32) BWD_DATA(float, float, float);
-    else if (g_dtype == CVAE_BF16 && dx_dtype == CVAE_BF16) BWD_DATA(bf16, bf16, bf16);
-    else if (g_dtype == CVAE_BF16) BWD_DATA(bf16, bf16, float);
-    else if (dx_dtype == CVAE_BF16) BWD_DATA(bf16, float, bf16);
-    else BWD_DATA(bf16, float, float);
-#undef BWD_DATA
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) { return with_dtype2(g_dtype, dx_dtype, [&](auto tg, auto to) {
+        using T = decltype(tv);
+        using TG = std::conditional_t<std::is_same_v<T, float>, float, decltype(tg)>;      // an fp32 product has fp32 ends (checked above): no mixed instance of it
+        using TO = std::conditional_t<std::is_same_v<T, float>, float, decltype(to)>;
+        hipLaunchKernelGGL((vit_gemm_bwd_data_kernel<T, TG, TO>), grid, dim3(256), 0, st, (const TG*)g, g_stride, W, (const T*)pre, pre_stride, resid, resid_stride, (TO*)dx,
+                           dx_stride, M, (int)K, (int)N);
+        return launch_rc();
+    }); });
 }
 
 extern "C" size_t cvae_token_gemm_wgrad_workspace_bytes(int64_t M, int64_t K, int64_t N) {
@@ -887,7 +885,7 @@ extern "C" size_t cvae_token_gemm_wgrad_workspace_bytes(int64_t M, int64_t K, in
 extern "C" int cvae_token_gemm_wgrad(const void* g, int64_t g_stride, int g_dtype, const void* x, int64_t x_stride, float* dW, float* db, int64_t M, int64_t K,
                                      int64_t N, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (M < 1 || M > (int64_t)65535 * WG_SLAB || g_stride < N || x_stride < K) return CVAE_E_BADSHAPE;      // the slab index is grid.z
-    if (!is_dtype(dtype) || !is_dtype(g_dtype) || (dtype == CVAE_F32 && g_dtype != CVAE_F32)) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype) || !dtype_ok(g_dtype) || (dtype == CVAE_F32 && g_dtype != CVAE_F32)) return CVAE_E_DTYPE;
     if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
     if (!g || !x || !dW || !db || !workspace) return CVAE_E_NULLPTR;
     if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || (x_stride % (dtype == CVAE_BF16 ? 8 : 4)) || !aligned16(g) || !aligned16(x) || !aligned16(dW) || !aligned16(workspace))
@@ -898,13 +896,13 @@ extern "C" int cvae_token_gemm_wgrad(const void* g, int64_t g_stride, int g_dtyp
     float* bpart = part + nslab * N * K;
     const dim3 grid((unsigned)(N / 64), (unsigned)(K / 64), (unsigned)nslab);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_F32)
-        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<float, float>), grid, dim3(256), 0, st, (const float*)g, g_stride, (const float*)x, x_stride, part, bpart, M, (int)K, (int)N);
-    else if (g_dtype == CVAE_BF16)
-        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<bf16, bf16>), grid, dim3(256), 0, st, (const bf16*)g, g_stride, (const bf16*)x, x_stride, part, bpart, M, (int)K, (int)N);
-    else
-        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<bf16, float>), grid, dim3(256), 0, st, (const float*)g, g_stride, (const bf16*)x, x_stride, part, bpart, M, (int)K, (int)N);
-    CVAE_CHECK_LAUNCH();
+    const int rc = with_dtype2(dtype, g_dtype, [&](auto tv, auto tg) {
+        using T = decltype(tv);
+        using TG = std::conditional_t<std::is_same_v<T, float>, float, decltype(tg)>;      // as in cvae_token_gemm_bwd_data
+        hipLaunchKernelGGL((vit_gemm_wgrad_kernel<T, TG>), grid, dim3(256), 0, st, (const TG*)g, g_stride, (const T*)x, x_stride, part, bpart, M, (int)K, (int)N);
+        return launch_rc();
+    });
+    if (rc != CVAE_OK) return rc;
     hipLaunchKernelGGL(vit_wgrad_finish_kernel, dim3((unsigned)(N * K / 4 / 256)), dim3(256), 0, st, (const float*)part, (const float*)bpart, dW, db, nslab, N * K, (int)N);
     CVAE_CHECK_LAUNCH();
     return CVAE_OK;
@@ -919,7 +917,7 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
                              int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
                              int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
     if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
-    if (!is_dtype(dtype)) return CVAE_E_DTYPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !workspace) return CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
     const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
@@ -939,11 +937,11 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
                            dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
     const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL((vit_attention_bwd_kernel<bf16, false>), gq, dim3(256), 0, st, aq);
-    else hipLaunchKernelGGL((vit_attention_bwd_kernel<float, false>), gq, dim3(256), 0, st, aq);
-    CVAE_CHECK_LAUNCH();
-    if (dtype == CVAE_BF16) hipLaunchKernelGGL((vit_attention_bwd_kernel<bf16, true>), gk, dim3(256), 0, st, ak);
-    else hipLaunchKernelGGL((vit_attention_bwd_kernel<float, true>), gk, dim3(256), 0, st, ak);
-    CVAE_CHECK_LAUNCH();
-    return CVAE_OK;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL((vit_attention_bwd_kernel<T, false>), gq, dim3(256), 0, st, aq);
+        CVAE_CHECK_LAUNCH();
+        hipLaunchKernelGGL((vit_attention_bwd_kernel<T, true>), gk, dim3(256), 0, st, ak);
+        return launch_rc();
+    });
 }
