@@ -740,51 +740,98 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
     const bool bias_l = bias_mode == 2 && (by / cl_blocks) == 0 && (ND == 2 || kd == 1 || kd == 2);
     float bacc = 0.f;
     // S tile: 128 positions x 64 channels; L tile: planes lz = 2 (o0d + d) - 1 + kd, rows 2 o0h - 1 + y, cols 2 o0w - 1 + x.
-    // Both LDS images are piece-linear (piece `it` at byte 16 it / 32 it).  The global loads of tile i+1 are issued right after
-    // tile i has been stored to LDS, so they are in flight during tile i's MFMA phase; out-of-range pieces are loaded from a
-    // clamped (valid) address and zeroed when they are stored, which keeps the loads unconditional and straight-line.
-    // Addresses are 32-bit offsets inside one sample (geom_ok bounds the sample size) on a wave-uniform 64-bit base.
-    constexpr int SN = (128 * 8) / NT, LNPOS = TD * IH * IW, LN = (LNPOS * 4 + NT - 1) / NT;
+    // The global loads of tile i+1 are issued right after tile i has been stored to LDS, so they are in flight during tile i's
+    // MFMA phase; out-of-range pieces are loaded from a clamped (valid) address and zeroed when they are stored, which keeps the
+    // loads unconditional and straight-line.  Addresses are 32-bit offsets inside one sample (geom_ok bounds the sample size) on a
+    // wave-uniform 64-bit base.
+    // Which pieces a thread moves does not depend on the tile, so everything but the tile origin is worked out once:
+    //  S: pass i of thread t is the 8-channel piece t & 7 of position m = (t >> 3) + 64 i: the same w, and (hh, d) a compile-time step further;
+    //  L: thread t keeps ONE column-piece cp = t % (4 IW) = (x, piece) and takes the lines lg + LG i, lg = t / (4 IW): x, its clamp, its ok bit and
+    //     the sample half are per tile, a pass adds the line's (d, y) — a constant plus one carry — two clamps and one multiply-add chain.
+    // The LDS destination of pass i is a per-thread base plus a compile-time offset.  What a thread needs of this rides in ONE packed
+    // register (lpk) across the MFMA phase; the kernel sits at the 128-VGPR cap and eight hoisted offsets spill.
+    constexpr int SN = (128 * 8) / NT, MSTEP = NT / 8;
+    constexpr int S_HSTEP = (MSTEP / TW) % TH, S_DSTEP = MSTEP / (TW * TH);          // (hh, d) of position m + MSTEP against m
+    static_assert(MSTEP % TW == 0 && (MSTEP / TW < TH ? MSTEP / TW : TH) - 1 + (SN - 1) * S_HSTEP < TH, "S passes step (hh, d) without carries");
+    constexpr int LCP = IW * 4, LG = NT / LCP;                                       // column-pieces of a line; lines per pass
+    constexpr int NLINES = TD * IH, LN = (NLINES + LG - 1) / LG, LN_FULL = NLINES / LG;
+    static_assert(LG >= 1 && LG <= IH && LG <= 7 && LN <= 7 && IW <= 64, "lpk fields; a pass carries into d at most once");
+    static_assert(((LPLANE + LG * LHALF + LHALF) * 4 + 3) * FB < 65536, "the L image offset of a thread's first line fits 16 bits");
     Piece<T> sp[SN], lp[LN];
     unsigned okmask = 0;
     const int s_sample = g.sd * g.sh * g.sw * g.Cs, l_sample = g.ld * g.lh * g.lw * g.Cl;
-    auto load_tile = [&](int tile) {
-        int tt = tile;
-        const int tw_i = tt % g.tiles_w; tt /= g.tiles_w;
-        const int th_i = tt % g.tiles_h; tt /= g.tiles_h;
-        const int td_i = tt % g.tiles_d;
-        const int b = (tt / g.tiles_d) * (1 + xb);            // xb: samples b (tile columns 0 .. TW / 2 - 1) and b + 1 (the other half)
-        const int o0d = td_i * TD, o0h = th_i * TH, o0w = tw_i * TW;
+    unsigned lpk;       // [0, 16) byte offset of (line lg, x, piece) in the L image; [16, 22) x; [22, 24) piece; [24, 27) lg; [27, 30) passes that store (0: a spare thread)
+    {
+        const int cp = t % LCP, lg = t / LCP, x = cp >> 2, piece = cp & 3;
+        const int nl = lg < LG ? (NLINES - lg + LG - 1) / LG : 0;
+        lpk = (unsigned)((l_row(lg, x) * 4 + piece) * FB) | (unsigned)x << 16 | (unsigned)piece << 22 | (unsigned)lg << 24 | (unsigned)nl << 27;
+    }
+    // the tile walk bx, bx + n_split, ... as digits (pair of samples, td, th, tw): load_tile adds the digits of n_split with carries
+    int nx_tw, nx_th, nx_td, nx_b, st_tw, st_th, st_td, st_b;
+    {
+        int r = bx;
+        nx_tw = r % g.tiles_w; r /= g.tiles_w; nx_th = r % g.tiles_h; r /= g.tiles_h; nx_td = r % g.tiles_d; nx_b = r / g.tiles_d;
+        r = n_split;
+        st_tw = r % g.tiles_w; r /= g.tiles_w; st_th = r % g.tiles_h; r /= g.tiles_h; st_td = r % g.tiles_d; st_b = r / g.tiles_d;
+    }
+    auto load_tile = [&]() {                                 // issues the loads of tile (nx_b, nx_td, nx_th, nx_tw), then steps to the workgroup's next tile
+        const int b = nx_b * (1 + xb);                       // xb: samples b (tile columns 0 .. TW / 2 - 1) and b + 1 (the other half)
+        const int o0d = nx_td * TD, o0h = nx_th * TH, o0w = nx_tw * TW;
         const T* Sb = S + (size_t)b * s_sample + cs0;
         const T* Lb = L + (size_t)b * l_sample + cl0;
         const bool b1ok = b + 1 < g.B;
         okmask = 0;
         int tz = t;
-        asm volatile("" : "+v"(tz));                         // opaque: keeps the per-piece index math inside the call (hoisted, it spills)
-#pragma unroll
-        for (int i = 0; i < SN; ++i) {
-            const int it = tz + i * NT, piece = it & 7, m = it >> 3;
-            const int w = m % TW, hh = m / TW % TH, d = m / (TW * TH);
+        unsigned pk = lpk;
+        asm volatile("" : "+v"(tz), "+v"(pk));               // opaque: the unpacked fields live only inside the call (hoisted, they spill)
+        {
+            const int piece = tz & 7, m0 = tz >> 3;
+            const int w = m0 % TW, hh0 = m0 / TW % TH, d0 = m0 / (TW * TH);
             const int sx = (xb && w >= TW / 2) ? 1 : 0;
-            const int od = o0d + d, oh = o0h + hh, ow = o0w + w - sx * (TW / 2);
-            const bool ok = (od < g.sd) & (oh < g.sh) & (ow < g.sw) & (!sx | b1ok);
-            const unsigned off = ((min(od, g.sd - 1) * g.sh + min(oh, g.sh - 1)) * g.sw + min(ow, g.sw - 1)) * g.Cs + piece * 8 + ((sx && b1ok) ? (unsigned)s_sample : 0u);
-            piece_load_raw<T>(sp[i], Sb + off);
-            okmask |= (unsigned)ok << i;
-        }
+            const int ow = o0w + w - sx * (TW / 2);
+            const bool okw = (ow < g.sw) & (!sx | b1ok);
+            const unsigned cw = (unsigned)(min(ow, g.sw - 1) * g.Cs + piece * 8) + ((sx && b1ok) ? (unsigned)s_sample : 0u);
+            const unsigned s_line = (unsigned)(g.sw * g.Cs);
 #pragma unroll
-        for (int i = 0; i < LN; ++i) {
-            const int it = tz + i * NT, piece = it & 3, pos = min(it >> 2, LNPOS - 1);
-            const int x = pos % IW, y = pos / IW % IH, d = pos / (IW * IH);
-            const int sx = (xb && x >= IW / 2) ? 1 : 0;
-            const int lz = (ND == 3) ? 2 * (o0d + d) - 1 + kd : 0, ly = 2 * o0h - 1 + y, lx = 2 * o0w - 1 + x - sx * (IW / 2);
-            const bool ok = (lz >= 0) & (lz < g.ld) & (ly >= 0) & (ly < g.lh) & (lx >= 0) & (lx < g.lw) & (!sx | b1ok) & (xb | (x < IW1));
-            const unsigned off = ((min(max(lz, 0), g.ld - 1) * g.lh + min(max(ly, 0), g.lh - 1)) * g.lw + min(max(lx, 0), g.lw - 1)) * g.Cl + piece * 8 + ((sx && b1ok) ? (unsigned)l_sample : 0u);
-            piece_load_raw<T>(lp[i], Lb + off);
-            okmask |= (unsigned)ok << (SN + i);
+            for (int i = 0; i < SN; ++i) {
+                const int od = o0d + d0 + i * S_DSTEP, oh = o0h + hh0 + i * S_HSTEP;
+                const bool ok = (od < g.sd) & (oh < g.sh) & okw;
+                const unsigned off = (unsigned)(min(od, g.sd - 1) * g.sh + min(oh, g.sh - 1)) * s_line + cw;
+                piece_load_raw<T>(sp[i], Sb + off);
+                okmask |= (unsigned)ok << i;
+            }
         }
+        {
+            const int x = (pk >> 16) & 63, piece = (pk >> 22) & 3, lg = (pk >> 24) & 7;
+            const int sx = (xb && x >= IW / 2) ? 1 : 0;
+            const int lx = 2 * o0w - 1 + x - sx * (IW / 2);
+            const bool okx = ((unsigned)lx < (unsigned)g.lw) & (!sx | b1ok) & (xb | (x < IW1));
+            const unsigned cx = (unsigned)(min(max(lx, 0), g.lw - 1) * g.Cl + piece * 8) + ((sx && b1ok) ? (unsigned)l_sample : 0u);
+            const unsigned l_line = (unsigned)(g.lw * g.Cl);
+            const int lz0 = 2 * o0d - 1 + kd, ly0 = 2 * o0h - 1;
+#pragma unroll
+            for (int i = 0; i < LN; ++i) {                   // line lg + LG i = (d, y): lines past the tile (a thread's last pass) load a clamped address and are never stored
+                const int dq = (i * LG) / IH, yr = (i * LG) % IH;
+                const int carry = (lg + yr >= IH) ? 1 : 0;
+                const int lz = (ND == 3) ? lz0 + 2 * (dq + carry) : 0, ly = ly0 + lg + yr - carry * IH;
+                const bool ok = ((unsigned)lz < (unsigned)g.ld) & ((unsigned)ly < (unsigned)g.lh) & okx;
+                const unsigned off = (unsigned)(min(max(lz, 0), g.ld - 1) * g.lh + min(max(ly, 0), g.lh - 1)) * l_line + cx;
+                piece_load_raw<T>(lp[i], Lb + off);
+                okmask |= (unsigned)ok << (SN + i);
+            }
+        }
+        nx_tw += st_tw;
+        int carry = nx_tw >= g.tiles_w ? 1 : 0;
+        nx_tw -= carry ? g.tiles_w : 0;
+        nx_th += st_th + carry;
+        carry = nx_th >= g.tiles_h ? 1 : 0;
+        nx_th -= carry ? g.tiles_h : 0;
+        nx_td += st_td + carry;
+        carry = nx_td >= g.tiles_d ? 1 : 0;
+        nx_td -= carry ? g.tiles_d : 0;
+        nx_b += st_b + carry;
     };
-    if (bx < total_tiles) load_tile(bx);
+    if (bx < total_tiles) load_tile();
     for (int tile = bx; tile < total_tiles; tile += n_split) {
         __syncthreads();                                     // the previous tile's readers are done with both images
 #ifdef CVAE_STAMP
@@ -792,23 +839,24 @@ __global__ __launch_bounds__(512, sizeof(T) == 2 ? 4 : 2) void conv_wgrad_kernel
 #endif
         {
             int tz = t;
-            asm volatile("" : "+v"(tz));                     // as in load_tile: recompute, do not keep 8 offsets live across the MFMA phase
+            unsigned pk = lpk;
+            asm volatile("" : "+v"(tz), "+v"(pk));           // as in load_tile
+            char* sdst = s_lds + s_byte(tz >> 3, (tz & 7) * 8);
 #pragma unroll
-            for (int i = 0; i < SN; ++i) {
-                const int it = tz + i * NT;
-                piece_store_sel<T>(sp[i], (okmask >> i) & 1, s_lds + s_byte(it >> 3, (it & 7) * 8));
-            }
+            for (int i = 0; i < SN; ++i) piece_store_sel<T>(sp[i], (okmask >> i) & 1, sdst + i * MSTEP * SROW);       // s_byte's swizzle has the period 4 in m
+            char* ldst = l_lds + (pk & 0xffffu);
+            const int nl = (int)(pk >> 27);
+            if (nl) {
 #pragma unroll
-            for (int i = 0; i < LN; ++i) {
-                const int it = tz + i * NT, pos = it >> 2;
-                if (it < LNPOS * 4) piece_store_sel<T>(lp[i], (okmask >> (SN + i)) & 1, l_lds + (l_row(pos / IW, pos % IW) * 4 + (it & 3)) * FB);
+                for (int i = 0; i < LN; ++i)
+                    if (i < LN_FULL || nl > i) piece_store_sel<T>(lp[i], (okmask >> (SN + i)) & 1, ldst + i * LG * LHALF * LROW);
             }
         }
         __syncthreads();
 #ifdef CVAE_STAMP
         if (stamp_it < 8) STAMP(3 + 3 * stamp_it);
 #endif
-        if (tile + n_split < total_tiles) load_tile(tile + n_split);
+        if (tile + n_split < total_tiles) load_tile();
         if (bias_s) {                                        // thread (c, pg): 16 of the tile's 128 positions of channel c
             const int c = t & 63, pg = t >> 6;
 #pragma unroll 4
