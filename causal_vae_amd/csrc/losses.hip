@@ -575,7 +575,7 @@ __global__ void bn1d_bwd_apply_kernel(const float* __restrict__ dy, const float*
 }
 extern "C" int cvae_bn1d_bwd_apply(const float* dy, const float* x, const float* w, const float* save_mean, const float* save_rstd, const float* sums, float inv_n,
                                    float* dx, int64_t B, int64_t F, void* stream) {
-    if (B < 1 || F <= 0 || !(inv_n > 0.f)) return CVAE_E_BADSHAPE;
+    if (B < 1 || F <= 0 || !(inv_n > 0.f) || inv_n > 0.5f) return CVAE_E_BADSHAPE;        // the global batch of cvae_bn1d_apply_stats: >= 2 samples
     if (!dy || !x || !save_mean || !save_rstd || !sums || !dx) return CVAE_E_NULLPTR;
     hipLaunchKernelGGL(bn1d_bwd_apply_kernel, dim3(cvae_grid_1d(B * F, 256)), dim3(256), 0, (hipStream_t)stream, dy, x, w, save_mean, save_rstd, sums, inv_n, dx, B, F);
     CVAE_CHECK_LAUNCH();

@@ -643,7 +643,8 @@ int cvae_bn1d_eval_fwd(const float* x, const float* w, const float* b, const flo
  *   cvae_bn1d_stats        out[f] = sum_b x[b][f] (mean_sum NULL), else sum_b (x[b][f] - mean_sum[f] * inv_n)^2
  *   cvae_bn1d_apply_stats  y, save_mean, save_rstd, running stats from the reduced sums; inv_n = 1 / global batch
  *   cvae_bn1d_bwd_sums     sums[0:F] = sum_b dy (this rank's d beta), sums[F:2F] = sum_b dy * xhat (this rank's d gamma)
- *   cvae_bn1d_bwd_apply    dx from the REDUCED sums */
+ *   cvae_bn1d_bwd_apply    dx from the REDUCED sums
+ * The global batch holds at least 2 samples: inv_n outside (0, 0.5] is CVAE_E_BADSHAPE from cvae_bn1d_apply_stats and cvae_bn1d_bwd_apply. */
 int cvae_bn1d_stats(const float* x, const float* mean_sum, float inv_n, float* out, int64_t B, int64_t F, void* stream);
 int cvae_bn1d_apply_stats(const float* x, const float* w, const float* b, const float* mean_sum, const float* sqdev_sum, float inv_n, float* y,
                           float* save_mean, float* save_rstd, float* running_mean, float* running_var, int64_t B, int64_t F, float momentum,
@@ -738,7 +739,7 @@ int cvae_sqnorm(const float* g, float* out, int64_t n, void* workspace, size_t w
  * the gradient of every term. */
 int cvae_weighted_sum(const float* const* terms, const float* weights, int count, const float* g, float* out, int backward, void* stream);
 /* The same sum over a LIST of tensors (host arrays of `count` device pointers / sizes) in one launch + one finish; workspace: cvae_reduce_workspace_bytes()
- * (CVAE_E_WORKSPACE below count + 1 floats). */
+ * (one block per tensor at least: CVAE_E_WORKSPACE below min(count, 64) + 1 floats, 64 being the tensors of one launch's table; a NULL workspace too). */
 int cvae_sqnorm_multi(const float* const* g, const int64_t* n, int count, float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* g *= *scale  (in place; scale is a device scalar) */
 int cvae_scale(float* g, int64_t n, const float* scale, void* stream);
