@@ -678,7 +678,7 @@ extern "C" int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, 
         if (dx_stride < K || (epi && x_stride < K)) return CVAE_E_BADSHAPE;
         if (M <= SK_M) return CVAE_E_UNSUPPORTED;
         if (epi && !x_in) return CVAE_E_NULLPTR;
-    } else if (M > 0 && M <= SK_M && N > 0 && dx_stride >= K && (K >= 1024 || y_act)) {
+    } else if (M > 0 && M <= SK_M && N > 0 && K > 0 && dx_stride >= K && (K >= 1024 || y_act)) {
         // skinny path: wide layers (K >= 1024) always; narrow ones when the activation gradient is fused (materialise-free)
         if (!dy || !W || !dx) return CVAE_E_NULLPTR;
         hipStream_t st = (hipStream_t)stream;
@@ -703,10 +703,11 @@ extern "C" int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW
                                       void* stream) {
     if (dy_stride < N || x_stride < K) return CVAE_E_BADSHAPE;
     if (bf16_math && M <= SK_M) return CVAE_E_UNSUPPORTED;
-    if (M <= 0) return CVAE_E_BADSHAPE;
+    if (M <= 0 || N <= 0 || K <= 0) return CVAE_E_BADSHAPE;
     if (act == CVAE_ACT_NONE) y_act = nullptr;
     if (y_act && M > SK_M) return CVAE_E_UNSUPPORTED;
-    if (M <= SK_M && N > 0 && K > 0) {
+    if (db && M > SK_M && dy_stride != N) return CVAE_E_UNSUPPORTED;     // (cvae_channel_sum reads dense rows) before any launch: a refused call writes nothing
+    if (M <= SK_M) {
         if (!dy || !x || !dW) return CVAE_E_NULLPTR;
         if (K >= 256 && N <= 65535) {
             int64_t gx = (K + 1023) / 1024;                  // each thread ~4 columns
@@ -719,9 +720,6 @@ extern "C" int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW
     }
     const int rc = gemm_f32(dy, x, dW, nullptr, N, K, M, 1, dy_stride, x_stride, 1, K, CVAE_ACT_NONE, (float*)workspace, workspace_bytes, (hipStream_t)stream, bf16_math != 0);
     if (rc != CVAE_OK) return rc;
-    if (db) {
-        if (dy_stride != N) return CVAE_E_UNSUPPORTED;
-        return cvae_channel_sum(dy, db, M, N, CVAE_F32, workspace, workspace_bytes, stream);    // stream order: the GEMM's slabs are consumed by then
-    }
+    if (db) return cvae_channel_sum(dy, db, M, N, CVAE_F32, workspace, workspace_bytes, stream);    // stream order: the GEMM's slabs are consumed by then
     return CVAE_OK;
 }

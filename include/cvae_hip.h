@@ -611,7 +611,9 @@ int cvae_upsample_linear_bwd(const float* ddst, void* dsrc, int64_t B, int64_t d
  * partial tile in a slab of `workspace` (cvae_linear_workspace_bytes(M, K, N, op); op 0 = fwd, 1 = bwd_data, 2 = bwd_weight) and a finish
  * launch adds the slabs in index order — no float atomics.  workspace may be NULL / smaller: the product then runs unsplit.
  * bf16_math != 0: bf16 MFMA operands (fp32 tensors in memory, rounded to bf16 on the way into LDS, fp32 accumulate and output): 16x the matrix rate of
- * the exact-fp32 form, relative error ~2^-9 per operand.  M > 16 only (smaller batches are HBM-bound skinny kernels: CVAE_E_UNSUPPORTED). */
+ * the exact-fp32 form, relative error ~2^-9 per operand.  M > 16 only (smaller batches are HBM-bound skinny kernels: CVAE_E_UNSUPPORTED).
+ * Row strides are in elements; one below its row length, or K, N <= 0, M < 0 is CVAE_E_BADSHAPE.  M == 0 is CVAE_OK from fwd and bwd_data (nothing is
+ * launched) and CVAE_E_BADSHAPE from bwd_weight (dW of an empty batch is not written as zeros).  Every refusal comes before any launch. */
 size_t cvae_linear_workspace_bytes(int64_t M, int64_t K, int64_t N, int op);
 /* y[M, N] = act(x[M, K] @ W[N, K]^T + b). */
 int cvae_linear_fwd(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N,
@@ -624,7 +626,8 @@ int cvae_linear_fwd(const float* x, const float* W, const float* b, float* y, in
 int cvae_linear_bwd_data(const float* dy, const float* W, float* dx, int64_t M, int64_t K, int64_t N, int64_t dy_stride, int64_t dx_stride,
                          const float* y_act, int act, const float* x_in, int64_t x_stride, int in_act, int bf16_math,
                          void* workspace, size_t workspace_bytes, void* stream);
-/* dW[N, K] = g^T x ; db[N] = column sums of g (db may be NULL).  Both overwritten.  g as above. */
+/* dW[N, K] = g^T x ; db[N] = column sums of g (db may be NULL).  Both overwritten.  g as above (y_act on dy's stride, M <= 16 only).
+ * M > 16 with db needs dense dy rows, dy_stride == N (the column sums are a cvae_channel_sum pass): otherwise CVAE_E_UNSUPPORTED before any launch. */
 int cvae_linear_bwd_weight(const float* dy, const float* x, float* dW, float* db, int64_t M, int64_t K, int64_t N,
                            int64_t dy_stride, int64_t x_stride, const float* y_act, int act, int bf16_math, void* workspace, size_t workspace_bytes,
                            void* stream);
@@ -704,12 +707,16 @@ int cvae_softmax_ce_bwd(const float* logits, const int64_t* target, const float*
 int cvae_uniform_kl_fwd(const float* logits, float* out, int64_t B, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
 int cvae_uniform_kl_bwd(const float* logits, const float* gout, float* dlogits, int64_t B, int64_t C, void* stream);
 
-/* ---- nn.Linear (+ activation) for SMALL layers at LARGE batch (csrc/small_dense.hip): M > 16 rows, K, N <= 512 and N * K <= 12288 weights — the MLP heads of
+/* ---- nn.Linear (+ activation) for SMALL layers at LARGE batch (csrc/small_dense.hip): M > 16 rows (below 2^30), 1 <= K, N <= 128 and N * K <= 12288 weights — the MLP heads of
  * mnist_test/01_baseline_causal_vae/models.py:24-37, 93-111 at batch 1024.  The weight lives in LDS; one launch forward, one for the data gradient, two for the
  * weight + bias gradient (per-workgroup partials in `workspace`, summed in index order: no atomics).  fp32 throughout.
  *   fwd         y = act(x W^T + b)
  *   bwd_data    dx = ((dy * act'(y_act)) W) * in_act'(x_in)     y_act / x_in may be NULL (ACT_NONE): both activation gradients ride in this launch
- *   bwd_weight  dW = (dy * act'(y_act))^T x,  db = column sums of (dy * act'(y_act))  (db may be NULL) */
+ *   bwd_weight  dW = (dy * act'(y_act))^T x,  db = column sums of (dy * act'(y_act))  (db may be NULL)
+ * act and in_act: every CVAE_ACT_* code (NONE, RELU, SIGMOID, LEAKY02, LEAKY001).  cvae_small_dense_supported answers 1 for a shape inside the limits and
+ * cvae_small_dense_workspace_bytes gives what bwd_weight needs (0 outside the limits; CVAE_E_WORKSPACE below it, CVAE_E_NULLPTR without a workspace).  A shape
+ * outside the limits, a row stride below the row length (y_stride / x_stride: only where y_act / x_in is read) or another activation code is CVAE_E_BADSHAPE,
+ * before any launch. */
 int cvae_small_dense_supported(int64_t M, int64_t K, int64_t N);
 size_t cvae_small_dense_workspace_bytes(int64_t M, int64_t K, int64_t N);
 int cvae_small_dense_fwd(const float* x, const float* W, const float* b, float* y, int64_t M, int64_t K, int64_t N, int64_t x_stride, int64_t y_stride, int act, void* stream);

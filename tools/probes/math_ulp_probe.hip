@@ -1,14 +1,15 @@
 // Largest error, in fp32 ulps of the exact result, of the device math functions csrc/losses.hip calls (expf, logf, log1pf, sqrtf, rsqrtf, powf, the
-// fp32 division and 1.f / x), against the float64 function of the same fp32 argument, over the argument ranges of tests/test_loss_reference.py.
-// Compiled with the flags of csrc/Makefile, so the functions are the ones the library gets.  Record: the ULP table of oracle/loss64.py.
+// fp32 division and 1.f / x), against the float64 function of the same fp32 argument, over the argument ranges of tests/test_loss_reference.py; and of
+// __expf, which apply_act (common.h) calls for the sigmoid, over [-8, 8], the range tests/test_dense_reference.py keeps its sigmoid pre-activations in.
+// Compiled with the flags of csrc/Makefile, so the functions are the ones the library gets.  Record: the ULP tables of oracle/loss64.py and oracle/dense64.py.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o math_ulp_probe tools/probes/math_ulp_probe.hip && ./math_ulp_probe
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
-enum { F_EXP, F_LOG, F_LOG1P, F_SQRT, F_RSQRT, F_POW09, F_POW0999, F_DIV, F_RCP, F_COUNT };
-static const char* NAMES[F_COUNT] = {"expf", "logf", "log1pf(-p)", "sqrtf", "rsqrtf", "powf(0.9f, t)", "powf(0.999f, t)", "a / b", "1.f / x"};
+enum { F_EXP, F_LOG, F_LOG1P, F_SQRT, F_RSQRT, F_POW09, F_POW0999, F_DIV, F_RCP, F_FASTEXP, F_COUNT };
+static const char* NAMES[F_COUNT] = {"expf", "logf", "log1pf(-p)", "sqrtf", "rsqrtf", "powf(0.9f, t)", "powf(0.999f, t)", "a / b", "1.f / x", "__expf"};
 
 // |got - want| in ulps of want as an fp32 number (normal range)
 __device__ double ulps(float got, double want) {
@@ -39,6 +40,7 @@ __global__ void probe(int fn, long long n, double lo, double hi, bool geo, doubl
         case F_POW09: { const float t = floorf(x); got = powf(0.9f, t); want = pow((double)0.9f, (double)t); break; }
         case F_POW0999: { const float t = floorf(x); got = powf(0.999f, t); want = pow((double)0.999f, (double)t); break; }
         case F_DIV: { const float b = sample((i * 7919) % n, n, lo, hi, geo); got = x / b; want = (double)x / (double)b; break; }
+        case F_FASTEXP: got = __expf(x); want = exp((double)x); break;
         default: got = 1.f / x; want = 1.0 / (double)x; break;
         }
         if (fabs(want) < 1e-37) continue;                    // subnormal results are not in any case's range
@@ -58,6 +60,7 @@ int main() {
         {F_SQRT, 1e-30, 1e12, true}, {F_RSQRT, 1e-12, 1e12, true}, {F_RSQRT, 1e-6, 4.0, false},
         {F_POW09, 1.0, 2000.0, false}, {F_POW09, 1.0, 100001.0, false}, {F_POW0999, 1.0, 2000.0, false}, {F_POW0999, 1.0, 100001.0, false},
         {F_DIV, 1e-12, 1e12, true}, {F_DIV, 0.5, 2.0, false}, {F_RCP, 1e-12, 1e12, true}, {F_RCP, 0.5, 2.0, false},
+        {F_FASTEXP, -8.0, 8.0, false}, {F_FASTEXP, -1.0, 1.0, false}, {F_FASTEXP, -8.0, -7.0, false}, {F_FASTEXP, 7.0, 8.0, false},
     };
     const int blocks = 1024, threads = 256, T = blocks * threads;
     const long long n = 1LL << 26;
