@@ -6,7 +6,9 @@
 // And its backward, for training the transformer in eval mode on a frozen stem (second half of the file): the training forms of attention (+ one
 // fp32 row statistic) and of the GELU GEMM (+ the pre-activation), a recompute-style attention backward in two passes, the token GEMM's data and weight gradients,
 // the LayerNorm backward and the token assembly's; slabs plus ordered finish launches wherever a sum crosses workgroups.
-// The token GEMM's and the attention's forward kernels live in vit_gemm.inc / vit_attention.inc, each included twice: the inference kernel and its training form.
+// The token GEMM's and the attention's forward kernels live in vit_gemm.inc / vit_attention.inc, each included three times: the inference kernel, its training form
+// and the training form with dropout (Philox masks recomputed in registers, fp32 only); vit_gemm_bwd_data.inc and vit_attention_bwd.inc hold
+// the two backward kernels that have a dropout form, each included twice.
 // Two arithmetic modes from one template: bf16 operands on v_mfma_f32_32x32x16_bf16, or exact fp32 on v_mfma_f32_32x32x2_f32 (the form the conv family uses
 // for fp32); accumulation, softmax, LayerNorm statistics and the residual stream are fp32 in both.  No atomics anywhere: every sum has a fixed order,
 // and an output element's bits do not depend on which other rows share its launch (row r of a one-row call equals row r of a full call: the CLS-only
@@ -24,6 +26,48 @@ namespace {
 #define VIT_HD 32
 
 __device__ __forceinline__ int crow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// ------------------------------------------------------------------------------------------------ dropout masks (include/cvae_hip.h)
+// Counter-based: a mask element is a pure function of (key, site coordinates), recomputed in registers wherever it is needed, never stored.  One
+// Philox4x32-10 call gives the words of four neighbouring elements; an element is kept iff (word >> 8) >= thr, and kept values are multiplied by scale.
+struct DropArgs { uint32_t thr, k0, k1; float scale; };
+__device__ __forceinline__ void drop_words(const DropArgs& d, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t w[4]) {
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = 0u;
+    philox4x32_10(w[0], w[1], w[2], w[3], d.k0, d.k1);
+}
+__device__ __forceinline__ bool drop_keep(const DropArgs& d, uint32_t w) { return (w >> 8) >= d.thr; }
+// row site: the words of columns c .. c + 3 (c % 4 == 0) of logical row R
+__device__ __forceinline__ void drop_row_words(const DropArgs& d, int64_t R, int c, uint32_t w[4]) {
+    drop_words(d, (uint32_t)(c >> 2), (uint32_t)R, (uint32_t)((uint64_t)R >> 32), w);
+}
+__device__ __forceinline__ void drop_apply4(const DropArgs& d, const uint32_t w[4], float v[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = drop_keep(d, w[e]) ? v[e] * d.scale : 0.f;
+}
+// attention site, one element: (batch b, head, query i, key j)
+__device__ __forceinline__ bool drop_keep_attn(const DropArgs& d, uint32_t bh, uint32_t i, uint32_t j) {
+    uint32_t w[4];
+    drop_words(d, j >> 2, i, bh, w);
+    const uint32_t s = j & 3;
+    return drop_keep(d, s == 0 ? w[0] : (s == 1 ? w[1] : (s == 2 ? w[2] : w[3])));
+}
+
+// y[m][c] = keep(R(m), c) ? x[m][c] * scale : 0 on fp32 rows: a thread per four columns
+__global__ __launch_bounds__(256) void vit_dropout_rows_kernel(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t M, int N, const DropArgs drop,
+                                                               int64_t mask_row0, int64_t mask_row_step) {
+    const int n4 = N >> 2;
+    const int64_t total = M * n4;
+    for (int64_t g = blockIdx.x * (int64_t)256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int64_t m = g / n4;
+        const int c = (int)(g - m * n4) * 4;
+        float v[4];
+        uint32_t w[4];
+        load_f32(x + m * ldx + c, v);
+        drop_row_words(drop, mask_row0 + m * mask_row_step, c, w);
+        drop_apply4(drop, w, v);
+        store_from_f32(y + m * ldy + c, v);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ token assembly
 // tokens[b][0] = cls + pos[0]; tokens[b][1 + i] = stem[b][i] + pos[1 + i]  (torch.cat((cls, x), 1) + pos_embedding, one fp32 add per element)
@@ -99,6 +143,11 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + er
 #include "vit_gemm.inc"
 #undef VIT_GEMM_KERNEL
 #undef VIT_GEMM_TRAIN
+#define VIT_GEMM_KERNEL vit_gemm_dropout_kernel
+#define VIT_GEMM_TRAIN 2
+#include "vit_gemm.inc"
+#undef VIT_GEMM_KERNEL
+#undef VIT_GEMM_TRAIN
 
 template <typename T>
 int gemm_launch(const T* x, int64_t ldx, const float* W, const float* bias, const float* resid, int64_t ldr, void* y, int64_t ldy, int64_t M, int K, int N,
@@ -143,6 +192,11 @@ template <> struct AttGeom<float> {
 #undef VIT_ATT_TRAIN
 #define VIT_ATT_KERNEL vit_attention_train_kernel
 #define VIT_ATT_TRAIN 1
+#include "vit_attention.inc"
+#undef VIT_ATT_KERNEL
+#undef VIT_ATT_TRAIN
+#define VIT_ATT_KERNEL vit_attention_dropout_kernel
+#define VIT_ATT_TRAIN 2
 #include "vit_attention.inc"
 #undef VIT_ATT_KERNEL
 #undef VIT_ATT_TRAIN
@@ -257,104 +311,16 @@ __device__ __forceinline__ float gelu_erf_grad(float v) {
     return 0.5f * (1.f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
 }
 
-template <typename T, typename TG, typename TO>
-__global__ __launch_bounds__(256) void vit_gemm_bwd_data_kernel(const TG* __restrict__ g, int64_t ldg, const float* __restrict__ W, const T* __restrict__ pre,
-                                                                int64_t ldp, const float* resid, int64_t ldr, TO* dx, int64_t lddx, int64_t M, int K, int N) {
-    using G = GemmGeom<T>;
-    constexpr int NP = G::KC / 8;                         // 4-element pieces of g per thread and chunk
-    __shared__ __attribute__((aligned(16))) T xs[GEMM_BM * G::PITCH];
-    __shared__ __attribute__((aligned(16))) T ws[GEMM_BN * G::PITCH];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t m0 = blockIdx.x * (int64_t)GEMM_BM;
-    const int k0 = blockIdx.y * GEMM_BN;                  // output columns of this workgroup
-    float rg[NP][4];
-    float4 rw[G::WP];
-    auto fetch = [&](int n0) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
-            const int64_t gm = m0 + row;
-            if (gm < M) load_f32(g + gm * ldg + n0 + piece * 4, rg[i]);
-            else rg[i][0] = rg[i][1] = rg[i][2] = rg[i][3] = 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < G::WP; ++i) {
-            const int p = t + 256 * i, n = p >> 4, piece = p & 15;
-            rw[i] = *(const float4*)(W + (int64_t)(n0 + n) * K + k0 + piece * 4);
-        }
-    };
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-    fetch(0);
-    for (int n0 = 0; n0 < N; n0 += G::KC) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int p = t + 256 * i, row = p / (G::KC / 4), piece = p % (G::KC / 4);
-            lds_put_w(xs + row * G::PITCH + piece * 4, make_float4(rg[i][0], rg[i][1], rg[i][2], rg[i][3]));
-        }
-#pragma unroll
-        for (int i = 0; i < G::WP; ++i) {
-            const int p = t + 256 * i, n = p >> 4, piece = p & 15;
-            ws[(piece * 4 + 0) * G::PITCH + n] = from_f32<T>(rw[i].x);
-            ws[(piece * 4 + 1) * G::PITCH + n] = from_f32<T>(rw[i].y);
-            ws[(piece * 4 + 2) * G::PITCH + n] = from_f32<T>(rw[i].z);
-            ws[(piece * 4 + 3) * G::PITCH + n] = from_f32<T>(rw[i].w);
-        }
-        __syncthreads();
-        if (n0 + G::KC < N) fetch(n0 + G::KC);
-        if constexpr (std::is_same<T, bf16>::value) {
-#pragma unroll
-            for (int s = 0; s < G::KC / 16; ++s) {
-                const bf16x8 b = *(const bf16x8*)(xs + (wave * 32 + r) * G::PITCH + 16 * s + 8 * h);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const bf16x8 a = *(const bf16x8*)(ws + (j * 32 + r) * G::PITCH + 16 * s + 8 * h);
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float b[4], a[2][4];
-                load_f32(xs + (wave * 32 + r) * G::PITCH + 16 * h + 4 * c, b);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) load_f32(ws + (j * 32 + r) * G::PITCH + 16 * h + 4 * c, a[j]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j][u], b[u], acc[j], 0, 0, 0);
-            }
-        }
-    }
-    const int64_t gm = m0 + wave * 32 + r;
-    if (gm >= M) return;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = k0 + j * 32 + 8 * q + 4 * h;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[j][4 * q + e];
-            if (pre) {
-                float pv[4];
-                load_f32(pre + gm * ldp + k, pv);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(pv[e]);
-            }
-            if (resid) {
-                float rv[4];
-                load_f32(resid + gm * ldr + k, rv);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e];
-            }
-            store_from_f32(dx + gm * lddx + k, v);
-        }
-}
+#define VIT_GEMM_BWD_DATA_KERNEL vit_gemm_bwd_data_kernel
+#define VIT_GEMM_BWD_DROP 0
+#include "vit_gemm_bwd_data.inc"
+#undef VIT_GEMM_BWD_DATA_KERNEL
+#undef VIT_GEMM_BWD_DROP
+#define VIT_GEMM_BWD_DATA_KERNEL vit_gemm_bwd_data_dropout_kernel
+#define VIT_GEMM_BWD_DROP 1
+#include "vit_gemm_bwd_data.inc"
+#undef VIT_GEMM_BWD_DATA_KERNEL
+#undef VIT_GEMM_BWD_DROP
 
 // ------------------------------------------------------------------------------------------------ token GEMM, weight gradient
 // dW[N][K] = sum_m g[m][n] x[m][k], db[n] = sum_m g[m][n].  An MFMA GEMM whose reduction index is the token: D = x^T g, so lane (r, h) owns output row
@@ -512,202 +478,16 @@ template <typename T> struct AttBwdGeom;
 template <> struct AttBwdGeom<bf16> { static constexpr int NP = 40, TP = 72, NS = ATT_KT * NP, TS = VIT_HD * TP, NR = 1; };
 template <> struct AttBwdGeom<float> { static constexpr int NP = 40, TP = 0, NS = ATT_KT * NP, TS = 4, NR = 2; };
 
-template <typename T, bool DKV>
-__global__ __launch_bounds__(256) void vit_attention_bwd_kernel(const AttBwdArgs a) {
-    using G = AttBwdGeom<T>;
-    constexpr bool BF = std::is_same<T, bf16>::value;
-    __shared__ __attribute__((aligned(16))) T W1n[G::NS];
-    __shared__ __attribute__((aligned(16))) T W2n[G::NS];
-    __shared__ __attribute__((aligned(16))) T W1t[G::TS];
-    __shared__ __attribute__((aligned(16))) T W2t[G::TS];
-    __shared__ float Ls[ATT_KT], Ds[ATT_KT];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int head = blockIdx.y;
-    const int64_t b = blockIdx.z;
-    const int orow = blockIdx.x * 128 + wave * 32 + r;
-    const int old = orow < a.n_own ? orow : a.n_own - 1;
-    const T* w1 = (const T*)a.walk1 + b * a.bs_w1 + head * VIT_HD;
-    const T* w2 = (const T*)a.walk2 + b * a.bs_w2 + head * VIT_HD;
-    const int64_t stat0 = (b * VIT_HEADS + head) * a.Nq;
-
-    // own fragments, kept for the whole walk: bf16 k order natural (16 s + 8 h + j), fp32 k = 16 h + i
-    bf16x8 f1[2], f2[2];
-    float s1[16], s2[16];
-    float lse_own = 0.f, delta_own = 0.f;
-    {
-        const T* p1 = (const T*)a.own1 + b * a.bs_o1 + (int64_t)old * a.ld_o1 + head * VIT_HD;
-        const T* p2 = (const T*)a.own2 + b * a.bs_o2 + (int64_t)old * a.ld_o2 + head * VIT_HD;
-        if constexpr (BF) {
-            f1[0] = *(const bf16x8*)(p1 + 8 * h);
-            f1[1] = *(const bf16x8*)(p1 + 16 + 8 * h);
-            f2[0] = *(const bf16x8*)(p2 + 8 * h);
-            f2[1] = *(const bf16x8*)(p2 + 16 + 8 * h);
-        } else {
-            load_f32(p1 + 16 * h, s1);
-            load_f32(p2 + 16 * h, s2);
-        }
-        if constexpr (!DKV) {                             // delta of this lane's query row: its half of the 32 columns, then the other half's
-            const T* po = (const T*)a.out + (b * a.Nq + old) * VIT_DIM + head * VIT_HD;
-            float d = 0.f;
-            if constexpr (BF) {
-                float o0[8], o1[8];
-                load_f32(po + 8 * h, o0);
-                load_f32(po + 16 + 8 * h, o1);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) d += (float)f2[0][j] * o0[j];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) d += (float)f2[1][j] * o1[j];
-            } else {
-                float o[16];
-                load_f32(po + 16 * h, o);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) d += s2[j] * o[j];
-            }
-            delta_own = d + __shfl_xor(d, 32, 64);
-            lse_own = a.lse[stat0 + old];
-            if (h == 0 && orow < a.n_own) a.delta[stat0 + orow] = delta_own;
-        }
-    }
-    uint4 r1[G::NR], r2[G::NR];
-    float rl = 0.f, rd = 0.f;
-    auto fetch = [&](int wt0) {
-#pragma unroll
-        for (int i = 0; i < G::NR; ++i) {
-            const int p = t + 256 * i;
-            const int row = BF ? (p >> 2) : (p >> 3), piece = BF ? (p & 3) : (p & 7);
-            const int gr = wt0 + row;
-            if (gr < a.n_walk) {
-                r1[i] = *(const uint4*)(w1 + (int64_t)gr * a.ld_w1 + piece * (16 / (int)sizeof(T)));
-                r2[i] = *(const uint4*)(w2 + (int64_t)gr * a.ld_w2 + piece * (16 / (int)sizeof(T)));
-            } else {
-                r1[i] = make_uint4(0, 0, 0, 0);
-                r2[i] = make_uint4(0, 0, 0, 0);
-            }
-        }
-        if (DKV && t < ATT_KT) {
-            const int gr = wt0 + t;
-            rl = gr < a.n_walk ? a.lse[stat0 + gr] : 0.f;
-            rd = gr < a.n_walk ? a.delta[stat0 + gr] : 0.f;
-        }
-    };
-    f32x16 acc1, acc2;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc1[e] = acc2[e] = 0.f;
-    fetch(0);
-    for (int wt0 = 0; wt0 < a.n_walk; wt0 += ATT_KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < G::NR; ++i) {
-            const int p = t + 256 * i;
-            if constexpr (BF) {
-                const int row = p >> 2, piece = p & 3;
-                *(uint4*)(W1n + row * G::NP + piece * 8) = r1[i];
-                *(uint4*)(W2n + row * G::NP + piece * 8) = r2[i];
-                const bf16x8 v1 = __builtin_bit_cast(bf16x8, r1[i]), v2 = __builtin_bit_cast(bf16x8, r2[i]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    W1t[(piece * 8 + e) * G::TP + row] = v1[e];
-                    if (DKV) W2t[(piece * 8 + e) * G::TP + row] = v2[e];
-                }
-            } else {
-                const int row = p >> 3, piece = p & 7;
-                *(uint4*)(W1n + row * G::NP + piece * 4) = r1[i];
-                *(uint4*)(W2n + row * G::NP + piece * 4) = r2[i];
-            }
-        }
-        if (DKV && t < ATT_KT) {
-            Ls[t] = rl;
-            Ds[t] = rd;
-        }
-        __syncthreads();
-        if (wt0 + ATT_KT < a.n_walk) fetch(wt0 + ATT_KT);
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const int row0 = wt0 + sub * 32;
-            if (row0 >= a.n_walk) break;                    // uniform over the workgroup
-            f32x16 sc, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[e] = dp[e] = 0.f;
-            if constexpr (BF) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const bf16x8 x1 = *(const bf16x8*)(W1n + (sub * 32 + r) * G::NP + 16 * s + 8 * h);
-                    const bf16x8 x2 = *(const bf16x8*)(W2n + (sub * 32 + r) * G::NP + 16 * s + 8 * h);
-                    sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, f1[s], sc, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, f2[s], dp, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float x1[4], x2[4];
-                    load_f32((const float*)W1n + (sub * 32 + r) * G::NP + 16 * h + 4 * c, x1);
-                    load_f32((const float*)W2n + (sub * 32 + r) * G::NP + 16 * h + 4 * c, x2);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        sc = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[u], s1[4 * c + u], sc, 0, 0, 0);
-                        dp = __builtin_amdgcn_mfma_f32_32x32x2f32(x2[u], s2[4 * c + u], dp, 0, 0, 0);
-                    }
-                }
-            }
-            float p[16], ds[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int wr = sub * 32 + crow(e, h);
-                const float lv = DKV ? Ls[wr] : lse_own, dv = DKV ? Ds[wr] : delta_own;
-                p[e] = (wt0 + wr < a.n_walk) ? exp2f(sc[e] * a.scale_log2e - lv) : 0.f;
-                ds[e] = p[e] * (dp[e] - dv) * a.scale;
-            }
-            if constexpr (BF) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const uint4 dk = make_uint4(pack2_bf16(ds[8 * s], ds[8 * s + 1]), pack2_bf16(ds[8 * s + 2], ds[8 * s + 3]),
-                                                pack2_bf16(ds[8 * s + 4], ds[8 * s + 5]), pack2_bf16(ds[8 * s + 6], ds[8 * s + 7]));
-                    const uint2 u0 = *(const uint2*)(W1t + r * G::TP + sub * 32 + 16 * s + 4 * h);
-                    const uint2 u1 = *(const uint2*)(W1t + r * G::TP + sub * 32 + 16 * s + 8 + 4 * h);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(u0.x, u0.y, u1.x, u1.y)), __builtin_bit_cast(bf16x8, dk),
-                                                                   acc1, 0, 0, 0);
-                    if constexpr (DKV) {
-                        const uint4 pk = make_uint4(pack2_bf16(p[8 * s], p[8 * s + 1]), pack2_bf16(p[8 * s + 2], p[8 * s + 3]),
-                                                    pack2_bf16(p[8 * s + 4], p[8 * s + 5]), pack2_bf16(p[8 * s + 6], p[8 * s + 7]));
-                        const uint2 v0 = *(const uint2*)(W2t + r * G::TP + sub * 32 + 16 * s + 4 * h);
-                        const uint2 v1 = *(const uint2*)(W2t + r * G::TP + sub * 32 + 16 * s + 8 + 4 * h);
-                        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, make_uint4(v0.x, v0.y, v1.x, v1.y)),
-                                                                       __builtin_bit_cast(bf16x8, pk), acc2, 0, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float x1 = ((const float*)W1n)[(sub * 32 + crow(e, h)) * G::NP + r];
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, ds[e], acc1, 0, 0, 0);
-                    if constexpr (DKV) {
-                        const float x2 = ((const float*)W2n)[(sub * 32 + crow(e, h)) * G::NP + r];
-                        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x2, p[e], acc2, 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    if (orow >= a.n_own) return;
-    T* o1 = (T*)a.g1 + b * a.bs_g1 + (int64_t)orow * a.ld_g1 + head * VIT_HD;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float w[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = acc1[4 * q + e];
-        store_from_f32(o1 + 8 * q + 4 * h, w);
-    }
-    if constexpr (DKV) {
-        T* o2 = (T*)a.g2 + b * a.bs_g2 + (int64_t)orow * a.ld_g2 + head * VIT_HD;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float w[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = acc2[4 * q + e];
-            store_from_f32(o2 + 8 * q + 4 * h, w);
-        }
-    }
-}
+#define VIT_ATT_BWD_KERNEL vit_attention_bwd_kernel
+#define VIT_ATT_BWD_DROP 0
+#include "vit_attention_bwd.inc"
+#undef VIT_ATT_BWD_KERNEL
+#undef VIT_ATT_BWD_DROP
+#define VIT_ATT_BWD_KERNEL vit_attention_bwd_dropout_kernel
+#define VIT_ATT_BWD_DROP 1
+#include "vit_attention_bwd.inc"
+#undef VIT_ATT_BWD_KERNEL
+#undef VIT_ATT_BWD_DROP
 
 }  // namespace
 
@@ -944,4 +724,131 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
         hipLaunchKernelGGL((vit_attention_bwd_kernel<T, true>), gk, dim3(256), 0, st, ak);
         return launch_rc();
     });
+}
+
+// ---- dropout entries: the training forms above with a Philox mask recomputed in registers.  fp32 only: no dtype code is taken and the float
+// instances are launched directly.  Every argument check precedes the first launch; p = 0 gives the bits of the entry without dropout.
+
+static bool drop_args(float p, uint64_t key, DropArgs* d) {
+    if (!(p >= 0.f && p < 1.f)) return false;
+    d->thr = (uint32_t)((double)p * 16777216.0);
+    d->k0 = (uint32_t)key;
+    d->k1 = (uint32_t)(key >> 32);
+    d->scale = 1.0f / (1.0f - p);
+    return true;
+}
+
+// logical rows R = row0 + m step of a row site: with m < 2^30 they stay far below 2^63
+static bool mask_rows_ok(int64_t row0, int64_t step) { return row0 >= 0 && row0 <= ((int64_t)1 << 40) && step >= 1 && step <= ((int64_t)1 << 30); }
+
+extern "C" int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, uint64_t key, int64_t mask_row0,
+                                 int64_t mask_row_step, void* stream) {
+    DropArgs d;
+    if (M < 1 || M > ((int64_t)1 << 30) || N < 4 || N > ((int64_t)1 << 30) || (N & 3) || x_stride < N || y_stride < N || !drop_args(p, key, &d) ||
+        !mask_rows_ok(mask_row0, mask_row_step))
+        return CVAE_E_BADSHAPE;
+    if (!x || !y) return CVAE_E_NULLPTR;
+    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    const int blocks = cvae_grid_1d(M * (N / 4), 256, 256 * 32);
+    hipLaunchKernelGGL(vit_dropout_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, y, y_stride, M, (int)N, d, mask_row0, mask_row_step);
+    return launch_rc();
+}
+
+extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                                       int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key,
+                                       int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    DropArgs d;
+    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N || !drop_args(p, key, &d) || !mask_rows_ok(mask_row0, mask_row_step)) return CVAE_E_BADSHAPE;
+    if (epilogue != CVAE_GEMM_EPI_GELU && epilogue != CVAE_GEMM_EPI_RESIDUAL) return CVAE_E_BADSHAPE;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
+    if (!x || !W || !bias || !y) return CVAE_E_NULLPTR;
+    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(N / GEMM_BN));
+    hipStream_t st = (hipStream_t)stream;
+    if (epilogue == CVAE_GEMM_EPI_RESIDUAL) {
+        if (!resid) return CVAE_E_NULLPTR;
+        if (resid_stride < N) return CVAE_E_BADSHAPE;
+        if ((resid_stride & 3) || !aligned16(resid)) return CVAE_E_UNSUPPORTED;
+        hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_RESID>), grid, dim3(256), 0, st, x, x_stride, W, bias, resid, resid_stride, (void*)y, y_stride, M,
+                           (int)K, (int)N, (float*)nullptr, (int64_t)0, d, mask_row0, mask_row_step);
+        return launch_rc();
+    }
+    if (!pre) return CVAE_E_NULLPTR;
+    if (pre_stride < N) return CVAE_E_BADSHAPE;
+    if ((pre_stride & 3) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
+    hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_GELU_SAVE>), grid, dim3(256), 0, st, x, x_stride, W, bias, (const float*)nullptr, (int64_t)0, (void*)y,
+                       y_stride, M, (int)K, (int)N, pre, pre_stride, d, mask_row0, mask_row_step);
+    return launch_rc();
+}
+
+extern "C" int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
+                                                int64_t M, int64_t K, int64_t N, float p, uint64_t key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    DropArgs d;
+    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K || (pre && pre_stride < K) || !drop_args(p, key, &d) || !mask_rows_ok(mask_row0, mask_row_step))
+        return CVAE_E_BADSHAPE;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
+    if (!g || !W || !dx) return CVAE_E_NULLPTR;
+    if ((g_stride & 3) || (dx_stride & 3) || (pre && (pre_stride & 3)) || !aligned16(g) || !aligned16(W) || !aligned16(dx) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
+    hipLaunchKernelGGL((vit_gemm_bwd_data_dropout_kernel<float, float, float>), grid, dim3(256), 0, (hipStream_t)stream, g, g_stride, W, pre, pre_stride,
+                       (const float*)nullptr, (int64_t)0, dx, dx_stride, M, (int)K, (int)N, d, mask_row0, mask_row_step);
+    return launch_rc();
+}
+
+// the stride and pointer checks the two attention entries share: `strides` = the n row strides, then the n batch strides
+static int mhsa_dropout_check(int64_t B, int64_t n_tokens, int64_t n_query_rows, const int64_t* strides, int n, const void* const* ptrs, int np) {
+    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+    for (int i = 0; i < np; ++i)
+        if (!ptrs[i]) return CVAE_E_NULLPTR;
+    for (int i = 0; i < 2 * n; ++i)
+        if (strides[i] < (i < n ? VIT_DIM : 0)) return CVAE_E_BADSHAPE;
+    for (int i = 0; i < 2 * n; ++i)
+        if (strides[i] & 3) return CVAE_E_UNSUPPORTED;
+    for (int i = 0; i < np; ++i)
+        if (!aligned16(ptrs[i])) return CVAE_E_UNSUPPORTED;
+    return CVAE_OK;
+}
+
+extern "C" int cvae_mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                           int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                                           float p, uint64_t key, void* stream) {
+    DropArgs d;
+    if (!drop_args(p, key, &d)) return CVAE_E_BADSHAPE;
+    const int64_t strides[6] = {q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride};
+    const void* const ptrs[5] = {q, k, v, out, lse};
+    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 3, ptrs, 5);
+    if (rc != CVAE_OK) return rc;
+    const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
+    const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // as cvae_mhsa_fwd_train
+    hipLaunchKernelGGL(vit_attention_dropout_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride,
+                       k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, lse, d);
+    return launch_rc();
+}
+
+extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
+                                     float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                                     int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride,
+                                     int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    DropArgs d;
+    if (!drop_args(p, key, &d)) return CVAE_E_BADSHAPE;
+    const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
+                                 dq_batch_stride, dk_batch_stride, dv_batch_stride};
+    const void* const ptrs[10] = {q, k, v, out, lse, dout, dq, dk, dv, workspace};
+    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 6, ptrs, 10);
+    if (rc != CVAE_OK) return rc;
+    if (workspace_bytes < cvae_mhsa_bwd_workspace_bytes(B, n_query_rows)) return CVAE_E_WORKSPACE;
+    const int N = (int)n_tokens, Nq = (int)n_query_rows;
+    const int64_t ob = (int64_t)Nq * VIT_DIM;
+    const float scale = 0.17677669529663688110f, scale_log2e = scale * 1.44269504088896340736f;
+    const AttBwdArgs aq = {q, dout, k, v, out, q_stride, VIT_DIM, k_stride, v_stride, q_batch_stride, ob, k_batch_stride, v_batch_stride, lse, (float*)workspace,
+                           dq, nullptr, dq_stride, 0, dq_batch_stride, 0, Nq, N, Nq, scale_log2e, scale};
+    const AttBwdArgs ak = {k, v, q, dout, out, k_stride, v_stride, q_stride, VIT_DIM, k_batch_stride, v_batch_stride, q_batch_stride, ob, lse, (float*)workspace,
+                           dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
+    const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, false>), gq, dim3(256), 0, st, aq, d);
+    CVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, true>), gk, dim3(256), 0, st, ak, d);
+    return launch_rc();
 }

@@ -1,11 +1,16 @@
 // vit_attention.inc — the fused attention kernel's text, included twice by vit.hip: as vit_attention_kernel (VIT_ATT_TRAIN 0: the inference kernel, its signature
-// and machine code as they were) and as vit_attention_train_kernel (VIT_ATT_TRAIN 1: + one fp32 row statistic per (batch, head, query) for the backward).
+// and machine code as they were), as vit_attention_train_kernel (VIT_ATT_TRAIN 1: + one fp32 row statistic per (batch, head, query) for the backward) and as
+// vit_attention_dropout_kernel (VIT_ATT_TRAIN 2: + dropout on the probabilities: the row statistics are those of the undropped row, the dropped p[e] are zeroed
+// between the row sum and the P V product, and the kept ones' scale 1 / (1 - p) multiplies the output row once, next to 1 / l).
 template <typename T>
 __global__ __launch_bounds__(256) void VIT_ATT_KERNEL(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
                                                             int64_t ldq, int64_t ldk, int64_t ldv, int64_t bsq, int64_t bsk, int64_t bsv, int N, int Nq,
                                                             float scale_log2e
 #if VIT_ATT_TRAIN
                                                             , float* __restrict__ lse
+#endif
+#if VIT_ATT_TRAIN == 2
+                                                            , const DropArgs drop
 #endif
 ) {
     using G = AttGeom<T>;
@@ -118,6 +123,15 @@ __global__ __launch_bounds__(256) void VIT_ATT_KERNEL(const T* __restrict__ q, c
             m_run = m_new;
 #pragma unroll
             for (int e = 0; e < 16; ++e) o[e] *= alpha;
+#if VIT_ATT_TRAIN == 2
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {                   // registers 4 g .. 4 g + 3 are keys key0 + 8 g + 4 h + (0 .. 3): one Philox call
+                uint32_t mw[4];
+                drop_words(drop, (uint32_t)((key0 + 8 * g + 4 * h) >> 2), (uint32_t)qld, (uint32_t)(b * VIT_HEADS + head), mw);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) p[4 * g + e] = drop_keep(drop, mw[e]) ? p[4 * g + e] : 0.f;
+            }
+#endif
             if constexpr (BF) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -148,6 +162,10 @@ __global__ __launch_bounds__(256) void VIT_ATT_KERNEL(const T* __restrict__ q, c
         float w[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[e] = o[4 * g + e] / l;
+#if VIT_ATT_TRAIN == 2
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] *= drop.scale;
+#endif
         store_from_f32(op + 8 * g + 4 * h, w);
     }
 }

@@ -1,11 +1,16 @@
 // vit_gemm.inc — the token GEMM kernel's text, included twice by vit.hip: as vit_gemm_kernel (VIT_GEMM_TRAIN 0: the inference kernel, its signature and machine
-// code as they were) and as vit_gemm_train_kernel (VIT_GEMM_TRAIN 1: + the pre-activation's pointer and stride, stored by the GELU_SAVE epilogue).  An include
-// and not a shared device function: the function form moved scalar instructions in every inference instance (tools/kernel_isa_diff.py).
+// code as they were), as vit_gemm_train_kernel (VIT_GEMM_TRAIN 1: + the pre-activation's pointer and stride, stored by the GELU_SAVE epilogue) and as
+// vit_gemm_dropout_kernel (VIT_GEMM_TRAIN 2: + a row-site dropout mask on what the GELU_SAVE epilogue stores as y, or on the product the RESID epilogue adds
+// to the residual).  An include and not a shared device function: the function form moved scalar instructions in every inference instance
+// (tools/kernel_isa_diff.py).
 template <typename T, int EPI>
 __global__ __launch_bounds__(256) void VIT_GEMM_KERNEL(const T* __restrict__ x, int64_t ldx, const float* __restrict__ W, const float* __restrict__ bias,
                                                        const float* resid, int64_t ldr, void* yv, int64_t ldy, int64_t M, int K, int N
 #if VIT_GEMM_TRAIN
                                                        , T* __restrict__ pre, int64_t ldp
+#endif
+#if VIT_GEMM_TRAIN == 2
+                                                       , const DropArgs drop, int64_t mask_row0, int64_t mask_row_step
 #endif
 ) {
     using G = GemmGeom<T>;
@@ -85,8 +90,15 @@ __global__ __launch_bounds__(256) void VIT_GEMM_KERNEL(const T* __restrict__ x, 
             load_f32(bias + n, bv);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[j][4 * g + e] + bv[e];
+#if VIT_GEMM_TRAIN == 2
+            uint32_t mw[4];
+            drop_row_words(drop, mask_row0 + gm * mask_row_step, n, mw);
+#endif
             if (EPI == GEMM_EPI_RESID) {
                 float rv[4];
+#if VIT_GEMM_TRAIN == 2
+                drop_apply4(drop, mw, v);
+#endif
                 load_f32(resid + gm * ldr + n, rv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = rv[e] + v[e];
@@ -99,6 +111,9 @@ __global__ __launch_bounds__(256) void VIT_GEMM_KERNEL(const T* __restrict__ x, 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
                 }
+#if VIT_GEMM_TRAIN == 2
+                drop_apply4(drop, mw, v);
+#endif
                 store_from_f32((T*)yv + gm * ldy + n, v);
             }
         }

@@ -2045,8 +2045,8 @@ def _mhsa_views(what, B, rows, *ts):
             raise L.CvaeError(f"{what}: [B, tokens, 256] views with unit column stride and one dtype expected, got {tuple(t.shape)} {t.dtype}")
 
 
-def _mhsa_fwd(what, q, k, v, n_query_rows, want_lse):
-    """The one body of mhsa and mhsa_train (`what`: the caller's name, for the error text) -> (out, lse or None)."""
+def _mhsa_fwd(what, q, k, v, n_query_rows, want_lse, dropout=None):
+    """The one body of mhsa and mhsa_train (`what`: the caller's name, for the error text) -> (out, lse or None).  dropout (with want_lse): (p, key)."""
     L.require_gpu(q, k, v)
     _forward_only(what, q, k, v)
     B, N = k.shape[0], k.shape[1]
@@ -2060,6 +2060,10 @@ def _mhsa_fwd(what, q, k, v, n_query_rows, want_lse):
         check(lib.cvae_mhsa_fwd(ptr(q), ptr(k), ptr(v), ptr(out), *tail), "mhsa_fwd")
         return out, None
     lse = _empty((B, 8, nq), torch.float32, q)
+    if dropout is not None:
+        p, key = _dropout_site(what, dropout, False, q)
+        check(lib.cvae_mhsa_fwd_train_dropout(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail[:9], p, key, stream()), "mhsa_fwd_train_dropout")
+        return out, lse
     check(lib.cvae_mhsa_fwd_train(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail), "mhsa_fwd_train")
     return out, lse
 
@@ -2086,14 +2090,68 @@ def _overlap(a, b):
     return a0 <= b1 and b0 <= a1
 
 
-def mhsa_train(q, k, v, n_query_rows=None):
-    """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train)."""
-    return _mhsa_fwd("mhsa_train", q, k, v, n_query_rows, True)
+# ---- dropout when training the transformer: masks are recomputed in the kernels from (p, key); the host only hands the keys out ---------
+_M64 = (1 << 64) - 1
 
 
-def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv):
+def _splitmix64(z):
+    """The splitmix64 output function: a bijection of the 64-bit integers."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+class DropoutKeys:
+    """The 64-bit Philox keys of the dropout sites, on the host.  key(step, block, site) = splitmix64(splitmix64(seed) + (step << 20 | block << 4 | site))
+    mod 2^64, for step < 2^44, block < 2^16, site < 16: a pure function of its arguments and the seed, and — splitmix64 being a bijection and the packing
+    one to one — distinct for distinct (step, block, site).  `step` is a Python int that the training forward advances once per call; seed defaults to
+    torch.initial_seed().  Sites of a transformer block: ATTN, MLP_ACT (after the GELU), MLP_OUT (after the second Linear)."""
+    ATTN, MLP_ACT, MLP_OUT = 0, 1, 2
+
+    def __init__(self, seed=None):
+        self.seed = int(torch.initial_seed() if seed is None else seed) & _M64
+        self.step = 0
+
+    def key(self, step, block, site):
+        step, block, site = int(step), int(block), int(site)
+        if not (0 <= step < 1 << 44 and 0 <= block < 1 << 16 and 0 <= site < 16):
+            raise L.CvaeError(f"DropoutKeys.key: step {step} (< 2^44), block {block} (< 2^16), site {site} (< 16) expected")
+        return _splitmix64((_splitmix64(self.seed) + (step << 20 | block << 4 | site)) & _M64)
+
+    def state(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state(self, state):
+        self.seed, self.step = int(state["seed"]) & _M64, int(state["step"])
+        return self
+
+
+def _dropout_site(what, dropout, rows, *tensors):
+    """(p, key) of an attention site or (p, key, row0, row_step) of a row site from the `dropout` argument of an op; the tensors must be fp32."""
+    n = len(dropout) if isinstance(dropout, (tuple, list)) else 0
+    if n not in ((2, 4) if rows else (2,)):
+        raise L.CvaeError(f"{what}: dropout must be (p, key)" + (" or (p, key, row0, row_step)" if rows else "") + f", got {dropout!r}")
+    p, key = float(dropout[0]), int(dropout[1])
+    row0, step = (int(dropout[2]), int(dropout[3])) if n == 4 else (0, 1)
+    if not (0.0 <= p < 1.0 and 0 <= key <= _M64 and row0 >= 0 and step >= 1):
+        raise L.CvaeError(f"{what}: dropout needs 0 <= p < 1, a 64-bit key, row0 >= 0 and row_step >= 1, got {dropout!r}")
+    if any(t is not None and t.dtype != torch.float32 for t in tensors):
+        raise L.CvaeError(f"{what}: dropout is implemented for float32 tensors only (bfloat16 compute dtype: not yet)")
+    return (p, key, row0, step) if rows else (p, key)
+
+
+def mhsa_train(q, k, v, n_query_rows=None, dropout=None):
+    """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train).
+    dropout = (p, key), fp32 only: the probabilities are dropped with the attention-site mask of include/cvae_hip.h before the P V product
+    (cvae_mhsa_fwd_train_dropout); lse stays that of the undropped rows.  None: exactly the path above."""
+    return _mhsa_fwd("mhsa_train", q, k, v, n_query_rows, True, dropout)
+
+
+def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, dropout=None):
     """The gradients of mhsa_train's operands, written into dq [B, n_query_rows, 256] and dk / dv [B, N, 256] — views with unit column stride, e.g. the
-    column panels of the packed in-projection cotangent [B, N, 768] (cvae_mhsa_bwd).  out / dout: contiguous [B, n_query_rows, 256]."""
+    column panels of the packed in-projection cotangent [B, N, 768] (cvae_mhsa_bwd).  out / dout: contiguous [B, n_query_rows, 256].
+    dropout: the (p, key) the forward ran with (cvae_mhsa_bwd_dropout: the mask is recomputed, fp32 only); None: exactly the path without."""
     L.require_gpu(q, k, v, out, lse, dout, dq, dk, dv)
     _forward_only("mhsa_bwd", q, k, v, out, dout)
     B, N, nq = k.shape[0], k.shape[1], out.shape[1]
@@ -2106,6 +2164,12 @@ def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv):
     if any(_overlap(a, b) for i, a in enumerate(outs) for b in outs[i + 1:] + (q, k, v, out, dout)):
         raise L.CvaeError("mhsa_bwd: dq, dk and dv must not overlap each other or an operand")
     _t, wp, wb = _scratch(lib.cvae_mhsa_bwd_workspace_bytes(B, nq), q)
+    if dropout is not None:
+        p, key = _dropout_site("mhsa_bwd", dropout, False, q)
+        check(lib.cvae_mhsa_bwd_dropout(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1),
+                                        q.stride(0), k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0),
+                                        B, N, nq, p, key, wp, wb, stream()), "mhsa_bwd_dropout")
+        return dq, dk, dv
     check(lib.cvae_mhsa_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1), q.stride(0),
                             k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0), B, N, nq,
                             L.dtype_code(q.dtype), wp, wb, stream()), "mhsa_bwd")
@@ -2117,16 +2181,63 @@ def token_gemm_gelu_train(x, weight, bias):
     return _token_gemm("token_gemm_gelu_train", x, weight, bias, "gelu", None, None, True)
 
 
+def token_gemm_dropout(x, weight, bias, epilogue, dropout, resid=None, out=None):
+    """token_gemm on fp32 x with a row-site dropout mask over the output (cvae_token_gemm_dropout).  dropout = (p, key) or (p, key, row0, row_step).
+    epilogue "gelu" -> (gelu(pre) keep s, pre): token_gemm_gelu_train's pair with the first member dropped; "residual" -> resid + (x W^T + b) keep s,
+    written to `out` (default: resid itself, in place).  p = 0 gives the bits of token_gemm_gelu_train / token_gemm."""
+    L.require_gpu(x, weight, bias, resid, out)
+    _forward_only("token_gemm_dropout", x, weight, bias, resid)
+    _rows2d(x, "token_gemm_dropout")
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in ("gelu", "residual"):
+        raise L.CvaeError(f"token_gemm_dropout: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r} ('gelu' or 'residual')")
+    p, key, row0, step = _dropout_site("token_gemm_dropout", dropout, True, x)
+    pre = None
+    if epilogue == "residual":
+        if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_dropout resid", N).shape[0] != M:
+            raise L.CvaeError("token_gemm_dropout: the residual epilogue needs a fp32 [M, N] residual")
+        out = resid if out is None else out
+    else:
+        if resid is not None or out is not None:
+            raise L.CvaeError("token_gemm_dropout: resid and out belong to the residual epilogue")
+        out, pre = _empty((M, N), torch.float32, x), _empty((M, N), torch.float32, x)
+    if _rows2d(out, "token_gemm_dropout out", N).shape[0] != M or out.dtype != torch.float32:
+        raise L.CvaeError(f"token_gemm_dropout: out {tuple(out.shape)} {out.dtype}")
+    check(lib.cvae_token_gemm_dropout(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid), resid.stride(0) if resid is not None else 0,
+                                      ptr(pre), N if pre is not None else 0, ptr(out), out.stride(0), M, K, N, GEMM_EPI[epilogue], p, key, row0, step, stream()),
+          "token_gemm_dropout")
+    return (out, pre) if epilogue == "gelu" else out
+
+
+def dropout_rows(x, dropout, out=None):
+    """x keep s on fp32 [M, N] rows (any row stride, N % 4 == 0) with the row-site mask (cvae_dropout_rows).  dropout = (p, key) or (p, key, row0, row_step);
+    out: where to write (may be x itself; default a new tensor).  On ones it is the mask."""
+    L.require_gpu(x, out)
+    _forward_only("dropout_rows", x)
+    _rows2d(x, "dropout_rows")
+    p, key, row0, step = _dropout_site("dropout_rows", dropout, True, x, out)
+    M, N = x.shape
+    if out is None:
+        out = _empty((M, N), torch.float32, x)
+    if _rows2d(out, "dropout_rows out", N).shape[0] != M:
+        raise L.CvaeError(f"dropout_rows: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    check(lib.cvae_dropout_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, p, key, row0, step, stream()), "dropout_rows")
+    return out
+
+
 def _gemm_mode(what, g, mode):
     """The arithmetic mode of a backward GEMM: fp32 mode takes fp32 cotangents only; bf16 mode takes bf16 ones or the fp32 stream gradient."""
     if mode not in (torch.float32, torch.bfloat16) or g.dtype not in (torch.float32, mode):
         raise L.CvaeError(f"{what}: a {g.dtype} cotangent in {mode} arithmetic")
 
 
-def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=None, out=None):
+def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=None, out=None, dropout=None):
     """dx [M, K] = (g [M, N] @ weight [N, K]) * gelu'(gate_pre) + resid (cvae_token_gemm_bwd_data).  weight: the fp32 nn.Linear tensor or a row slice of it;
     mode: the arithmetic (torch.float32 / torch.bfloat16); g fp32 or `mode`; gate_pre [M, K] in `mode`: the saved pre-activation; resid fp32 [M, K] (any row
-    stride): added, result fp32, written to `out` (default: resid itself, in place).  out_dtype (default `mode`): the result's dtype without resid."""
+    stride): added, result fp32, written to `out` (default: resid itself, in place).  out_dtype (default `mode`): the result's dtype without resid.
+    dropout = (p, key) or (p, key, row0, row_step): dx = (g W) keep s * gelu'(gate_pre) with the row-site mask over dx (cvae_token_gemm_bwd_data_dropout);
+    fp32 throughout, no resid.  None: exactly the path above."""
     L.require_gpu(g, weight, gate_pre, resid, out)
     _forward_only("token_gemm_bwd_data", g, weight, gate_pre, resid)
     _rows2d(g, "token_gemm_bwd_data")
@@ -2145,6 +2256,13 @@ def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=No
         out = _empty((M, K), out_dtype or mode, g)
     if _rows2d(out, "token_gemm_bwd_data out", K).shape[0] != M or out.dtype not in (torch.float32, mode) or (resid is not None and out.dtype != torch.float32):
         raise L.CvaeError(f"token_gemm_bwd_data: out {tuple(out.shape)} {out.dtype}")
+    if dropout is not None:
+        p, key, row0, step = _dropout_site("token_gemm_bwd_data", dropout, True, g, out)
+        if mode != torch.float32 or resid is not None:
+            raise L.CvaeError("token_gemm_bwd_data: dropout runs in fp32 arithmetic and takes no residual")
+        check(lib.cvae_token_gemm_bwd_data_dropout(ptr(g), g.stride(0), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
+                                                   ptr(out), out.stride(0), M, K, N, p, key, row0, step, stream()), "token_gemm_bwd_data_dropout")
+        return out
     check(lib.cvae_token_gemm_bwd_data(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
                                        ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), L.dtype_code(out.dtype), M, K, N,
                                        L.dtype_code(mode), stream()), "token_gemm_bwd_data")

@@ -100,19 +100,23 @@ class CausalViTVAE(nn.Module):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self, decoder=False, transformer=False, stem=False):
+    def train_adapters(self, decoder=False, transformer=False, stem=False, dropout=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
         heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
         a default call after a decoder=True one switches the decoder's gradients off again).
         decoder=True: the backbone's decoder learns too (backbone.train_decoder(): decoder_input and decoder ask for gradients, still in eval mode: BatchNorm2d on
         its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters.
-        transformer=True: the backbone's transformer learns too (backbone.train_transformer(): pos_embedding, cls_token, transformer, to_latent; eval mode, no
-        dropout; the conv stem stays frozen).  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
+        transformer=True: the backbone's transformer learns too (backbone.train_transformer(): pos_embedding, cls_token, transformer, to_latent; eval mode; the
+        conv stem stays frozen).  dropout=True (needs transformer=True; float32 compute dtype): its blocks then drop in the training forward as the
+        reference's do under train() (backbone.train_transformer(dropout=True)); default: no dropout.  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
         backbone's (mu, log_var), so no gradient ever reaches them.  Returns head plus transformer parameters (plus the decoder's with decoder=True).
         stem=True (needs transformer=True): the backbone's conv stem learns too (backbone.train_stem(): eval-mode BatchNorm2d on its running statistics;
         DESIGN §17), the whole backbone is then fine-tuned as vessel_analysis/01_train/train.py does; its parameters are returned too."""
         if stem and not transformer:
             raise CvaeError("CausalViTVAE.train_adapters: stem=True needs transformer=True (the stem's gradient arrives through the transformer)")
+        if dropout and not transformer:
+            raise CvaeError("CausalViTVAE.train_adapters: dropout=True needs transformer=True (the dropout sites are the transformer blocks'; a frozen "
+                            "transformer runs its inference form)")
         self.backbone.requires_grad_(False)
         self.backbone.freeze_decoder()
         self.backbone.freeze_transformer()
@@ -123,7 +127,7 @@ class CausalViTVAE(nn.Module):
         if stem:
             params += self.backbone.train_stem()
         if transformer:
-            params += self.backbone.train_transformer(heads=False)
+            params += self.backbone.train_transformer(heads=False, dropout=dropout)
         if decoder:
             self.backbone.train_decoder()
             params += list(self.backbone.decoder_input.parameters()) + list(self.backbone.decoder.parameters())

@@ -28,7 +28,7 @@ draws the reference's weights and the state_dict key sets are equal.  decode, pe
 decode_with_grad / decode_vjp add the gradient of that image with respect to z through the FROZEN eval-mode decoder: the forward issues
 decode's launches (the fold also writes the backward matrices) and keeps five gate activations and the three ResBlock inner activations; the backward is
 cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
-Training, all in eval mode (no dropout, BatchNorm2d on its running statistics): train_decoder, train_transformer (§16) and train_stem (§17: the
+Training, all in eval mode (BatchNorm2d on its running statistics; dropout only where train_transformer(dropout=True) asks for it): train_decoder, train_transformer (§16) and train_stem (§17: the
 stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then per layer cvae_conv_wgrad and cvae_conv_down_bwd_data with the LeakyReLU
 derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
 are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
@@ -51,10 +51,13 @@ STEM_CHANNELS = (32, 64, 128, 256, 256)
 # _BlockStep, one per transformer block: X (the block's input rows [B N, 256], norm1's input), y (norm1's output: the in-projection's operand), qkv (the packed
 # in-projection output; k and v alone [B, N, 512] in a CLS-only block), q (the CLS-only block's one query row per sample, else None), att / lse (attention's
 # output and row statistic), X1 (the stream after attention: norm2's input), y2 (norm2's output), pre / hid (the MLP's pre-activation and its GELU), B, N,
-# cls_only (everything from the attention's queries on ran for the CLS rows alone: att, X1, y2, pre, hid have B rows, not B N).
+# cls_only (everything from the attention's queries on ran for the CLS rows alone: att, X1, y2, pre, hid have B rows, not B N), drop (the block's three dropout
+# sites as the forward ran them, DESIGN §18: ((p, key) or None) for the attention probabilities, the GELU output and the second Linear's output; hid is then
+# the DROPPED GELU output, att the dropped attention's; the masks themselves are not kept, the backward recomputes them).
 # _Walk: steps (the _BlockSteps in forward order), cls (to_latent's input [B, 256]), stem_dtype (the dtype dstem is returned in), B, N, stem (_StemKept or None).
 _StemKept = namedtuple("_StemKept", "x ys k4")
-_BlockStep = namedtuple("_BlockStep", "X y qkv q att lse X1 y2 pre hid B N cls_only")
+_BlockStep = namedtuple("_BlockStep", "X y qkv q att lse X1 y2 pre hid B N cls_only drop")
+_NO_DROP = (None, None, None)
 _Walk = namedtuple("_Walk", "steps cls stem_dtype B N stem")
 
 
@@ -95,6 +98,7 @@ class ViTVAEEncoder(nn.Module):
         self.to_latent = nn.LayerNorm(embed_dim)
         self.fc_mu = nn.Linear(embed_dim, latent_dim)
         self.fc_var = nn.Linear(embed_dim, latent_dim)
+        self.dropout_keys = ops.DropoutKeys()               # host-side: the Philox keys of train_transformer(dropout=True)'s masks, .step advanced per training forward
 
     def set_compute_dtype(self, dtype):
         if dtype not in (torch.float32, torch.bfloat16):
@@ -128,17 +132,22 @@ class ViTVAEEncoder(nn.Module):
                 keep["ys"].append(h)
         return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
 
-    def _block(self, blk, tokens, cls_only, save):
+    def _block(self, blk, tokens, cls_only, save, drop=_NO_DROP):
         """One transformer block on the fp32 residual stream `tokens` [B, N, 256] -> (the stream after it [B, N, 256], or with cls_only the block's CLS rows
         [B, 256]: the same sums in the same order as the full block's row 0, `tokens` left as it was; _BlockStep or None).
         save=False (inference): the residual GEMMs of a full block write the stream in place and nothing is kept.  save=True: the same launches with attention
         and the GELU GEMM in their training forms (the same values plus lse / the pre-activation), and the residual GEMMs write fresh tensors: the block's input
-        and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied."""
+        and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied.
+        drop (with save): ((p, key) or None) per dropout site — attention probabilities, GELU output, second Linear's output.  A site with a pair
+        runs the dropout form of its launch (as many launches as without); None: the plain launch.  The row sites' mask rows are the token rows b N + i of
+        the [B N, .] stream, so a CLS-only block (rows b) passes (row0, row_step) = (0, N) and its one query row is query 0: the full block's CLS rows."""
         B, N, D = tokens.shape
+        att_d, act_d, out_d = drop
+        rows = (0, N) if cls_only else (0, 1)
         dt = self.compute_dtype
         X = tokens.view(B * N, D)
         a = blk.attn
-        attend = ops.mhsa_train if save else ops.mhsa
+        attend = (lambda *a, **kw: ops.mhsa_train(*a, dropout=att_d, **kw)) if save else ops.mhsa
         y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
         if not cls_only:
             qkv, q = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D), None
@@ -152,22 +161,33 @@ class ViTVAEEncoder(nn.Module):
         att, lse = att if save else (att, None)
         X1 = ops.token_gemm(att.view(-1, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=resid, out=X1)
         y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-        if save:
+        if save and act_d is not None:
+            hid, pre = ops.token_gemm_dropout(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu", act_d + rows)
+        elif save:
             hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias)
         else:
             hid, pre = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu"), None
-        X2 = ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=torch.empty_like(X1) if save else None)
+        if save and out_d is not None:
+            X2 = ops.token_gemm_dropout(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", out_d + rows, resid=X1, out=torch.empty_like(X1))
+        else:
+            X2 = ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=torch.empty_like(X1) if save else None)
         if not save:
             return (X2 if cls_only else tokens), None                   # a full block wrote the stream itself
-        return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only)
+        return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only, drop)
 
     @torch.no_grad()
     def _walk(self, x, save=False, keep_stem=False, collect=None):
         """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
         saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
-        after every block that ran for all tokens)."""
+        after every block that ran for all tokens).
+        After train_transformer(dropout=True) a save=True walk runs every block in its dropout form: one step of self.dropout_keys per walk, the
+        rates read from the block's modules.  save=False never drops."""
         self._check(x)
+        drop_step = None
+        if save and self._dropout:
+            self._check_dropout_dtype()
+            drop_step, self.dropout_keys.step = self.dropout_keys.step, self.dropout_keys.step + 1
         kept = {} if keep_stem else None
         stem = self._stem_cl(x, kept)
         tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
@@ -176,7 +196,7 @@ class ViTVAEEncoder(nn.Module):
         steps = []
         for i, blk in enumerate(self.transformer):
             cls_only = self._cls_only_last_block and i == self.depth - 1
-            out, step = self._block(blk, tokens, cls_only, save)
+            out, step = self._block(blk, tokens, cls_only, save, _NO_DROP if drop_step is None else self._block_dropout(blk, i, drop_step))
             steps.append(step)
             if cls_only:
                 cls = out
@@ -260,31 +280,53 @@ class ViTVAEEncoder(nn.Module):
         roots = self._TRANSFORMER_ROOTS if heads else self._TRANSFORMER_ROOTS[:4]
         return [(k, p) for k, p in self.named_parameters() if k.split(".")[0] in roots]
 
+    _dropout = False                # train_transformer(dropout=True): the training forward drops at the blocks' three sites
+
+    def _check_dropout_dtype(self):
+        if self.compute_dtype != torch.float32:
+            raise CvaeError("ViTVAEEncoder: dropout is implemented for the float32 compute dtype only (the dropout kernels take no bfloat16 operands yet): "
+                            "set_compute_dtype(torch.float32), or train_transformer(dropout=False)")
+
+    def _block_dropout(self, blk, i, step):
+        """((p, key) or None) for block i's three sites at this step: the rates are the modules' (attn.dropout, mlp[2].p, mlp[4].p); a rate of 0 is None."""
+        K = ops.DropoutKeys
+        sites = ((blk.attn.dropout, K.ATTN), (blk.mlp[2].p, K.MLP_ACT), (blk.mlp[4].p, K.MLP_OUT))
+        return tuple((float(p), self.dropout_keys.key(step, i, site)) if p > 0 else None for p, site in sites)
+
     def freeze_transformer(self):
-        """requires_grad_(False) on everything train_transformer() switched on; cls_features_with_grad then equals cls_features and saves nothing."""
+        """requires_grad_(False) on everything train_transformer() switched on, and dropout off; cls_features_with_grad then equals cls_features and saves
+        nothing."""
         for _k, p in self._transformer_named():
             p.requires_grad_(False)
         self._transformer_grads = False
+        self._dropout = False
         return self
 
-    def train_transformer(self, heads=True):
+    def train_transformer(self, heads=True, dropout=False):
         """The counterpart of freeze_transformer(): requires_grad_(True) on transformer.*, pos_embedding, cls_token, to_latent.*, fc_mu.* and fc_var.*
         (heads=False: without fc_mu / fc_var, for a consumer of the cls features that never reaches them; they are frozen), and
         cls_features_with_grad / encode_with_grad from now on accumulate their `.grad`.  Returns those parameters in named_parameters order.  The model stays in
-        EVAL mode (no dropout: the one difference from the reference's vae.train(), next to BatchNorm2d's running statistics) and, unless train_stem() was
-        called, the conv stem stays a frozen feature extractor: a stem parameter that asks for a gradient is then an error here, not a gradient that silently
-        stays None."""
+        EVAL mode and, unless train_stem() was called, the conv stem stays a frozen feature extractor: a stem parameter that asks for a gradient is then an error
+        here, not a gradient that silently stays None.
+        dropout=False (default): no dropout — next to BatchNorm2d's running statistics the difference from the reference's vae.train().  dropout=True (float32
+        compute dtype only, else CvaeError): every training forward (cls_features_with_grad / encode_with_grad with a live graph) drops as the reference's
+        ViTBlock does under train(): the attention probabilities, the GELU output and the second Linear's output, at the rates of blk.attn.dropout, blk.mlp[2].p
+        and blk.mlp[4].p, with Philox masks keyed by self.dropout_keys (one step per forward) — not torch's RNG stream.  The module itself stays
+        in eval mode; cls_features, encode and every other inference entry never drop."""
         if self.training:
-            raise RuntimeError("ViTVAEEncoder.train_transformer: put the model in eval mode first (model.eval()): the transformer trains without dropout, "
-                               "on an eval-mode stem")
+            raise RuntimeError("ViTVAEEncoder.train_transformer: put the model in eval mode first (model.eval()): the transformer trains on an eval-mode "
+                               "stem, and dropout is asked for with dropout=True, not with the module's mode")
         live = [k for k, p in self._stem_named() if p.requires_grad]
         if live and not self._stem_grads:
             raise RuntimeError(f"ViTVAEEncoder.train_transformer: the stem is a frozen feature extractor, but these parameters ask for a gradient: {live} "
                                "(model.stem.requires_grad_(False), or model.train_stem() for their gradients)")
+        if dropout:
+            self._check_dropout_dtype()
         self.freeze_transformer()
         for _k, p in self._transformer_named(heads):
             p.requires_grad_(True)
         self._transformer_grads = True
+        self._dropout = bool(dropout)
         return [p for _k, p in self._transformer_named(heads)]
 
     def cls_features_with_grad(self, x, collect=None):
@@ -313,27 +355,41 @@ class ViTVAEEncoder(nn.Module):
         c = self.cls_features_with_grad(x, collect)
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
+    def _cls_rows_step(self, s):
+        """The record a CLS-only block would have kept, cut from a full block's _BlockStep (the last block of a walk with _cls_only_last_block False): k / v
+        as the column panels of the packed qkv, the CLS query row, and the CLS rows b N of att, lse, X1, y2, pre and hid — views with the stream's row stride,
+        but for att and lse, which the attention backward reads as dense [B, 1, .] tensors (two B-row copies).  Row 0 of a full block equals the CLS-only
+        block's row bit for bit, so _block_backward computes from it what it computes after a CLS-only forward."""
+        B, N, D = s.B, s.N, self.embed_dim
+        row0 = lambda t: t.view(B, N, -1)[:, 0]
+        return s._replace(qkv=s.qkv[:, :, D:], q=s.qkv[:, :1, :D], att=s.att[:, :1].contiguous(), lse=s.lse[:, :, :1].contiguous(), X1=row0(s.X1), y2=row0(s.y2),
+                          pre=row0(s.pre), hid=row0(s.hid), cls_only=True)
+
     def _block_backward(self, blk, name, s, G, grads):
         """One block's backward from its _BlockStep s: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in
         place where it can be; returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names."""
         B, N, D, dt, a = s.B, s.N, self.embed_dim, self.compute_dtype, blk.attn
-        dpre = ops.token_gemm_bwd_data(G, blk.mlp[3].weight, dt, gate_pre=s.pre)
-        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(G, s.hid)
+        att_d, act_d, out_d = s.drop                                    # the forward's dropout sites: the masks are recomputed from (p, key), DESIGN §18
+        rows = (0, N) if s.cls_only else (0, 1)
+        Gm = G if out_d is None else ops.dropout_rows(G, out_d + rows)  # the MLP branch's cotangent; the skip carries G itself
+        dpre = ops.token_gemm_bwd_data(Gm, blk.mlp[3].weight, dt, gate_pre=s.pre, dropout=None if act_d is None else act_d + rows)
+        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(Gm, s.hid)
         dy2 = ops.token_gemm_bwd_data(dpre, blk.mlp[0].weight, dt)
         grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s.y2)
         _dx, grads[name + "norm2.weight"], grads[name + "norm2.bias"] = ops.layernorm256_bwd(dy2, s.X1, blk.norm2.weight, blk.norm2.eps, dx=G, accumulate=True)
         datt = ops.token_gemm_bwd_data(G, a.out_proj.weight, dt)
         grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s.att.view(-1, D))
         qkv, y = s.qkv, s.y
-        dqkv = torch.empty_like(qkv)
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)       # dense, also where qkv is a column panel (_cls_rows_step)
         if not s.cls_only:
-            ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.att, s.lse, datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:])
+            ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.att, s.lse, datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:],
+                         dropout=att_d)
             dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 3 * D), a.in_proj_weight, dt)
             grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = ops.token_gemm_wgrad(dqkv.view(B * N, 3 * D), y)
             _dx, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s.X, blk.norm1.weight, blk.norm1.eps, dx=G, accumulate=True)
             return G
-        dq = torch.empty_like(s.q)
-        ops.mhsa_bwd(s.q, qkv[:, :, :D], qkv[:, :, D:], s.att, s.lse, datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:])
+        dq = torch.empty(s.q.shape, dtype=s.q.dtype, device=s.q.device)
+        ops.mhsa_bwd(s.q, qkv[:, :, :D], qkv[:, :, D:], s.att, s.lse, datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:], dropout=att_d)
         dW, db = torch.empty_like(a.in_proj_weight), torch.empty_like(a.in_proj_bias)
         ops.token_gemm_wgrad(dq.view(B, D), y.view(B, N, D)[:, 0], dW[:D], db[:D])
         ops.token_gemm_wgrad(dqkv.view(B * N, 2 * D), y, dW[D:], db[D:])
@@ -350,13 +406,12 @@ class ViTVAEEncoder(nn.Module):
         when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`)."""
         steps, cls, stem_dtype, B, N, kept = saved
         D, grads = self.embed_dim, {}
-        if steps[-1].cls_only:                                          # the forward ran a CLS-only last block: the stream gradient starts as its [B, 256] rows
-            G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
-        else:
-            G = torch.zeros(B * N, D, dtype=torch.float32, device=g.device)
-            _dx, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps, dx=G.view(B, N, D)[:, 0])
+        # to_latent reads the CLS rows alone, so the last block's cotangent is its [B, 256] CLS rows whichever form its forward ran: the backward of a full
+        # last block is the CLS-only block's, on the CLS rows of what it kept (_cls_rows_step) — the same launches, hence the same bits, in both forms
+        G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
         for i in reversed(range(self.depth)):
-            G = self._block_backward(self.transformer[i], f"transformer.{i}.", steps[i], G, grads)
+            s = steps[i] if (steps[i].cls_only or i < self.depth - 1) else self._cls_rows_step(steps[i])
+            G = self._block_backward(self.transformer[i], f"transformer.{i}.", s, G, grads)
         if kept is None:
             dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
         else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
@@ -608,11 +663,11 @@ class ViTVAE(ViTVAEEncoder):
         return self._decode_backward(saved, grad_image.contiguous())
 
     # ---- training the whole model (eval mode) --------------------------------------------------------------------------
-    def train_all(self):
-        """train_stem() + train_transformer() + train_decoder(): every parameter asks for a gradient and forward_train's graph reaches every one of them.
-        Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae)."""
+    def train_all(self, dropout=False):
+        """train_stem() + train_transformer(dropout=dropout) + train_decoder(): every parameter asks for a gradient and forward_train's graph reaches every one of
+        them.  Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae)."""
         self.train_stem()
-        self.train_transformer()
+        self.train_transformer(dropout=dropout)
         self.train_decoder()
         return list(self.parameters())
 
@@ -697,14 +752,15 @@ def vit_vae_loss(recons, x, mu, log_var, beta=1.0):
     return recon + beta * kld
 
 
-def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0):
-    """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature: per batch["x"], zero_grad, model.forward_train, vit_vae_loss,
-    backward, optimizer.step().  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval mode, so there
-    is no dropout and every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state); all
-    parameters learn (model.train_all() is called, so an optimizer built over model.parameters() fits).  Returns the per-epoch mean losses as a list of floats
-    (sample-weighted, read from the device once per epoch)."""
+def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False):
+    """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature plus `dropout`: per batch["x"], zero_grad, model.forward_train,
+    vit_vae_loss, backward, optimizer.step().  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval
+    mode, so every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state), and there is no
+    dropout unless dropout=True: then the transformer blocks drop as the reference's do under train(), at the modules' rates, with Philox masks
+    (train_transformer(dropout=True); float32 compute dtype).  All parameters learn (model.train_all() is called, so an optimizer built over
+    model.parameters() fits).  Returns the per-epoch mean losses as a list of floats (sample-weighted, read from the device once per epoch)."""
     model.eval()
-    model.train_all()
+    model.train_all(dropout=dropout)
     history = []
     for _ep in range(int(epochs)):
         total, n = [], 0

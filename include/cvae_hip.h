@@ -365,6 +365,46 @@ int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtype, const fl
 int cvae_vit_tokens_bwd(const float* dtokens, float* dpos, float* dcls, void* dstem, int stem_dtype, const void* gate, int gate_act, int64_t B, int64_t n_patches,
                         void* stream);
 
+/* ---- ViT-VAE encoder, dropout when training the transformer (csrc/vit.hip) -------------------------------------------------------
+ * The training entries above with a dropout mask that is never stored: every kernel recomputes it in registers from a counter-based generator, the forward
+ * and the backward alike.  fp32 only: these entries take no dtype code (every tensor is fp32).  Otherwise the contract of their siblings: every check precedes
+ * the first launch, the workspace is the caller's, no atomics, fixed-order sums, pointers and strides multiples of 16 bytes.
+ *
+ * THE MASK.  One Philox4x32-10 call (counter c0..c3, key k0 = low word of `key`, k1 = high word) yields four 32-bit words w[0..3].
+ *   row site        an fp32 matrix [rows][N], N % 4 == 0.  Element (r, c): counter = (c >> 2, low 32 bits of R, high 32 bits of R, 0), word c & 3, where
+ *                   R = mask_row0 + r * mask_row_step is the element's LOGICAL row (0 <= mask_row0 <= 2^40, 1 <= mask_row_step <= 2^30): the rows
+ *                   0, n, 2 n, ... of a [B n][N] site are the [B][N] site with (mask_row0, mask_row_step) = (0, n).
+ *   attention site  element (batch b, head h, query i, key j): counter = (j >> 2, i, b * 8 + h, 0), word j & 3.  i and j are token indices: they do not
+ *                   depend on n_query_rows or on any tile size.
+ *   keep rule       an element is kept iff (w >> 8) >= T, T = (uint32_t)((double)p * 16777216.0); kept values are multiplied by the fp32 constant
+ *                   s = 1.0f / (1.0f - p), dropped ones are 0.  0 <= p < 1, anything else is CVAE_E_BADSHAPE.
+ *   p = 0           T = 0, s = 1: nothing is dropped and every entry below produces the bits of its sibling without dropout.
+ *
+ *   cvae_mhsa_fwd_train_dropout       cvae_mhsa_fwd_train with Pd = softmax(S) keep s in place of P in the P V product.  Row max, row sum and lse are those of
+ *                                     the undropped row (lse: cvae_mhsa_fwd_train's bits); s multiplies the output row once, next to 1 / (row sum).
+ *   cvae_mhsa_bwd_dropout             cvae_mhsa_bwd for that forward (the same p and key): dV = Pd^T dO, dP = (dO V^T) keep s, dS = P (dP - delta) / sqrt(32)
+ *                                     with delta = rowsum(dout * out) of the dropped out.  Workspace: cvae_mhsa_bwd_workspace_bytes.
+ *   cvae_token_gemm_dropout           cvae_token_gemm on fp32 x with a row-site mask over (logical row, output column).  epilogue CVAE_GEMM_EPI_GELU: stores the
+ *                                     pre-activation in `pre` (row stride pre_stride) and y = gelu(pre) keep s; CVAE_GEMM_EPI_RESIDUAL: y = resid +
+ *                                     (x W^T + bias) keep s (y == resid allowed; pre is not read).  Any other epilogue is CVAE_E_BADSHAPE.
+ *   cvae_token_gemm_bwd_data_dropout  dx[M][K] = (g[M][N] W[N][K]) keep s * gelu'(pre), the mask over (logical row, column of dx); pre optional
+ *   cvae_dropout_rows                 y = x keep s on fp32 [M][N] with row strides (y == x allowed; N % 4 == 0, M and N at most 2^30); on an all-ones x it
+ *                                     is the mask itself (times s) */
+int cvae_mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
+                                uint64_t key, void* stream);
+int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv,
+                          int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                          int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
+                          int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                            int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key, int64_t mask_row0,
+                            int64_t mask_row_step, void* stream);
+int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride, int64_t M,
+                                     int64_t K, int64_t N, float p, uint64_t key, int64_t mask_row0, int64_t mask_row_step, void* stream);
+int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, uint64_t key, int64_t mask_row0,
+                      int64_t mask_row_step, void* stream);
+
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
  * (no atomics, no split-K): bit-reproducible, and a sample's bits do not depend on the batch it travels in.  Pointers 16-byte aligned, else CVAE_E_UNSUPPORTED;
