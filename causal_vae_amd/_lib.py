@@ -146,6 +146,12 @@ SIGNATURES = {
     "cvae_token_gemm_dropout": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _f, _u64, _i64, _i64, _p],
     "cvae_token_gemm_bwd_data_dropout": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _f, _u64, _i64, _i64, _p],
     "cvae_dropout_rows": [_p, _i64, _p, _i64, _i64, _i64, _f, _u64, _i64, _i64, _p],
+    "cvae_dropout_keys_step": [_u64, _p, _p, _i, _p],
+    "cvae_mhsa_fwd_train_dropout_devkey": [_p] * 5 + [_i64] * 9 + [_f, _p, _p],
+    "cvae_mhsa_bwd_dropout_devkey": [_p] * 9 + [_i64] * 15 + [_f, _p, _p, _sz, _p],
+    "cvae_token_gemm_dropout_devkey": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _f, _p, _i64, _i64, _p],
+    "cvae_token_gemm_bwd_data_dropout_devkey": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _f, _p, _i64, _i64, _p],
+    "cvae_dropout_rows_devkey": [_p, _i64, _p, _i64, _i64, _i64, _f, _p, _i64, _i64, _p],
     "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
     "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],

@@ -8,7 +8,9 @@
 // the LayerNorm backward and the token assembly's; slabs plus ordered finish launches wherever a sum crosses workgroups.
 // The token GEMM's and the attention's forward kernels live in vit_gemm.inc / vit_attention.inc, each included three times: the inference kernel, its training form
 // and the training form with dropout (Philox masks recomputed in registers, fp32 only); vit_gemm_bwd_data.inc and vit_attention_bwd.inc hold
-// the two backward kernels that have a dropout form, each included twice.
+// the two backward kernels that have a dropout form, each included twice.  The dropout forms take their Philox key by value or (the *_devkey entries, DESIGN.md
+// section 19) read it from device memory at kernel entry, which is what lets a captured training step replay with a new key; vit_dropout_keys_step_kernel derives
+// a step's keys from a device-resident counter and advances it.
 // Two arithmetic modes from one template: bf16 operands on v_mfma_f32_32x32x16_bf16, or exact fp32 on v_mfma_f32_32x32x2_f32 (the form the conv family uses
 // for fp32); accumulation, softmax, LayerNorm statistics and the residual stream are fp32 in both.  No atomics anywhere: every sum has a fixed order,
 // and an output element's bits do not depend on which other rows share its launch (row r of a one-row call equals row r of a full call: the CLS-only
@@ -52,9 +54,20 @@ __device__ __forceinline__ bool drop_keep_attn(const DropArgs& d, uint32_t bh, u
     return drop_keep(d, s == 0 ? w[0] : (s == 1 ? w[1] : (s == 2 ? w[2] : w[3])));
 }
 
+// The key of a launch: the two words the entry passed by value, or (key_dev non-null: the *_devkey entries) the two words of the 64-bit key in
+// device memory, low word first, read when the kernel runs — the same address in every lane, so one load per wave.
+__device__ __forceinline__ DropArgs drop_with_key(DropArgs d, const uint32_t* __restrict__ key_dev) {
+    if (key_dev) {
+        d.k0 = key_dev[0];
+        d.k1 = key_dev[1];
+    }
+    return d;
+}
+
 // y[m][c] = keep(R(m), c) ? x[m][c] * scale : 0 on fp32 rows: a thread per four columns
-__global__ __launch_bounds__(256) void vit_dropout_rows_kernel(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t M, int N, const DropArgs drop,
-                                                               int64_t mask_row0, int64_t mask_row_step) {
+__global__ __launch_bounds__(256) void vit_dropout_rows_kernel(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t M, int N, const DropArgs drop_arg,
+                                                               int64_t mask_row0, int64_t mask_row_step, const uint32_t* key_dev) {
+    const DropArgs drop = drop_with_key(drop_arg, key_dev);
     const int n4 = N >> 2;
     const int64_t total = M * n4;
     for (int64_t g = blockIdx.x * (int64_t)256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
@@ -67,6 +80,22 @@ __global__ __launch_bounds__(256) void vit_dropout_rows_kernel(const float* x, i
         drop_apply4(drop, w, v);
         store_from_f32(y + m * ldy + c, v);
     }
+}
+
+// The keys of one training step, derived where the counter lives (the rule of include/cvae_hip.h, which is ops.DropoutKeys.key):
+// table[4 b + site] = splitmix64(base + (s << 20 | b << 4 | site)), s = *step mod 2^44 as the kernel finds it.  One workgroup: every thread reads s, the
+// barrier orders those reads before the one store of s + 1, so a replayed graph walks the steps without the host.
+__device__ __forceinline__ uint64_t splitmix64_dev(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void vit_dropout_keys_step_kernel(uint64_t base, int64_t* step, uint64_t* table, int n_blocks) {
+    const uint64_t s = (uint64_t)*step & (((uint64_t)1 << 44) - 1);
+    __syncthreads();
+    if (threadIdx.x == 0) *step = (int64_t)(s + 1);
+    for (int i = threadIdx.x; i < 4 * n_blocks; i += 256) table[i] = splitmix64_dev(base + (s << 20 | (uint64_t)(i >> 2) << 4 | (uint64_t)(i & 3)));
 }
 
 // ------------------------------------------------------------------------------------------------ token assembly
@@ -738,31 +767,56 @@ static bool drop_args(float p, uint64_t key, DropArgs* d) {
     return true;
 }
 
+// The key of a dropout entry: a value (the entries of DESIGN §18), or an 8-byte-aligned device pointer that the kernels read when they run (the *_devkey
+// entries of DESIGN §19: a captured graph replays with whatever the pointer holds then).
+struct DropKey {
+    uint64_t value;
+    const uint64_t* dev;
+    bool on_device;
+    bool missing() const { return on_device && !dev; }
+    bool misaligned() const { return on_device && ((uintptr_t)dev & 7); }
+    const uint32_t* words() const { return on_device ? (const uint32_t*)dev : nullptr; }
+};
+static DropKey key_value(uint64_t key) { return {key, nullptr, false}; }
+static DropKey key_device(const uint64_t* key) { return {0, key, true}; }
+
 // logical rows R = row0 + m step of a row site: with m < 2^30 they stay far below 2^63
 static bool mask_rows_ok(int64_t row0, int64_t step) { return row0 >= 0 && row0 <= ((int64_t)1 << 40) && step >= 1 && step <= ((int64_t)1 << 30); }
 
-extern "C" int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, uint64_t key, int64_t mask_row0,
-                                 int64_t mask_row_step, void* stream) {
+static int dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, DropKey key, int64_t mask_row0,
+                        int64_t mask_row_step, void* stream) {
     DropArgs d;
-    if (M < 1 || M > ((int64_t)1 << 30) || N < 4 || N > ((int64_t)1 << 30) || (N & 3) || x_stride < N || y_stride < N || !drop_args(p, key, &d) ||
+    if (M < 1 || M > ((int64_t)1 << 30) || N < 4 || N > ((int64_t)1 << 30) || (N & 3) || x_stride < N || y_stride < N || !drop_args(p, key.value, &d) ||
         !mask_rows_ok(mask_row0, mask_row_step))
         return CVAE_E_BADSHAPE;
-    if (!x || !y) return CVAE_E_NULLPTR;
-    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    if (!x || !y || key.missing()) return CVAE_E_NULLPTR;
+    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(y) || key.misaligned()) return CVAE_E_UNSUPPORTED;
     const int blocks = cvae_grid_1d(M * (N / 4), 256, 256 * 32);
-    hipLaunchKernelGGL(vit_dropout_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, y, y_stride, M, (int)N, d, mask_row0, mask_row_step);
+    hipLaunchKernelGGL(vit_dropout_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, y, y_stride, M, (int)N, d, mask_row0, mask_row_step,
+                       key.words());
     return launch_rc();
 }
 
-extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
-                                       int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key,
-                                       int64_t mask_row0, int64_t mask_row_step, void* stream) {
+extern "C" int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, uint64_t key, int64_t mask_row0,
+                                 int64_t mask_row_step, void* stream) {
+    return dropout_rows(x, x_stride, y, y_stride, M, N, p, key_value(key), mask_row0, mask_row_step, stream);
+}
+
+extern "C" int cvae_dropout_rows_devkey(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, const uint64_t* key,
+                                        int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    return dropout_rows(x, x_stride, y, y_stride, M, N, p, key_device(key), mask_row0, mask_row_step, stream);
+}
+
+static int token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                              int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, DropKey key,
+                              int64_t mask_row0, int64_t mask_row_step, void* stream) {
     DropArgs d;
-    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N || !drop_args(p, key, &d) || !mask_rows_ok(mask_row0, mask_row_step)) return CVAE_E_BADSHAPE;
+    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N || !drop_args(p, key.value, &d) || !mask_rows_ok(mask_row0, mask_row_step))
+        return CVAE_E_BADSHAPE;
     if (epilogue != CVAE_GEMM_EPI_GELU && epilogue != CVAE_GEMM_EPI_RESIDUAL) return CVAE_E_BADSHAPE;
     if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!x || !W || !bias || !y) return CVAE_E_NULLPTR;
-    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    if (!x || !W || !bias || !y || key.missing()) return CVAE_E_NULLPTR;
+    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y) || key.misaligned()) return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(N / GEMM_BN));
     hipStream_t st = (hipStream_t)stream;
     if (epilogue == CVAE_GEMM_EPI_RESIDUAL) {
@@ -770,72 +824,113 @@ extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const f
         if (resid_stride < N) return CVAE_E_BADSHAPE;
         if ((resid_stride & 3) || !aligned16(resid)) return CVAE_E_UNSUPPORTED;
         hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_RESID>), grid, dim3(256), 0, st, x, x_stride, W, bias, resid, resid_stride, (void*)y, y_stride, M,
-                           (int)K, (int)N, (float*)nullptr, (int64_t)0, d, mask_row0, mask_row_step);
+                           (int)K, (int)N, (float*)nullptr, (int64_t)0, d, mask_row0, mask_row_step, key.words());
         return launch_rc();
     }
     if (!pre) return CVAE_E_NULLPTR;
     if (pre_stride < N) return CVAE_E_BADSHAPE;
     if ((pre_stride & 3) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_GELU_SAVE>), grid, dim3(256), 0, st, x, x_stride, W, bias, (const float*)nullptr, (int64_t)0, (void*)y,
-                       y_stride, M, (int)K, (int)N, pre, pre_stride, d, mask_row0, mask_row_step);
+                       y_stride, M, (int)K, (int)N, pre, pre_stride, d, mask_row0, mask_row_step, key.words());
+    return launch_rc();
+}
+
+extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                                       int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key,
+                                       int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    return token_gemm_dropout(x, x_stride, W, bias, resid, resid_stride, pre, pre_stride, y, y_stride, M, K, N, epilogue, p, key_value(key), mask_row0,
+                              mask_row_step, stream);
+}
+
+extern "C" int cvae_token_gemm_dropout_devkey(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride,
+                                              float* pre, int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p,
+                                              const uint64_t* key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    return token_gemm_dropout(x, x_stride, W, bias, resid, resid_stride, pre, pre_stride, y, y_stride, M, K, N, epilogue, p, key_device(key), mask_row0,
+                              mask_row_step, stream);
+}
+
+static int token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
+                                       int64_t M, int64_t K, int64_t N, float p, DropKey key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    DropArgs d;
+    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K || (pre && pre_stride < K) || !drop_args(p, key.value, &d) ||
+        !mask_rows_ok(mask_row0, mask_row_step))
+        return CVAE_E_BADSHAPE;
+    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
+    if (!g || !W || !dx || key.missing()) return CVAE_E_NULLPTR;
+    if ((g_stride & 3) || (dx_stride & 3) || (pre && (pre_stride & 3)) || !aligned16(g) || !aligned16(W) || !aligned16(dx) || !aligned16(pre) || key.misaligned())
+        return CVAE_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
+    hipLaunchKernelGGL((vit_gemm_bwd_data_dropout_kernel<float, float, float>), grid, dim3(256), 0, (hipStream_t)stream, g, g_stride, W, pre, pre_stride,
+                       (const float*)nullptr, (int64_t)0, dx, dx_stride, M, (int)K, (int)N, d, mask_row0, mask_row_step, key.words());
     return launch_rc();
 }
 
 extern "C" int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
                                                 int64_t M, int64_t K, int64_t N, float p, uint64_t key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    DropArgs d;
-    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K || (pre && pre_stride < K) || !drop_args(p, key, &d) || !mask_rows_ok(mask_row0, mask_row_step))
-        return CVAE_E_BADSHAPE;
-    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!g || !W || !dx) return CVAE_E_NULLPTR;
-    if ((g_stride & 3) || (dx_stride & 3) || (pre && (pre_stride & 3)) || !aligned16(g) || !aligned16(W) || !aligned16(dx) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
-    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
-    hipLaunchKernelGGL((vit_gemm_bwd_data_dropout_kernel<float, float, float>), grid, dim3(256), 0, (hipStream_t)stream, g, g_stride, W, pre, pre_stride,
-                       (const float*)nullptr, (int64_t)0, dx, dx_stride, M, (int)K, (int)N, d, mask_row0, mask_row_step);
-    return launch_rc();
+    return token_gemm_bwd_data_dropout(g, g_stride, W, pre, pre_stride, dx, dx_stride, M, K, N, p, key_value(key), mask_row0, mask_row_step, stream);
+}
+
+extern "C" int cvae_token_gemm_bwd_data_dropout_devkey(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx,
+                                                       int64_t dx_stride, int64_t M, int64_t K, int64_t N, float p, const uint64_t* key, int64_t mask_row0,
+                                                       int64_t mask_row_step, void* stream) {
+    return token_gemm_bwd_data_dropout(g, g_stride, W, pre, pre_stride, dx, dx_stride, M, K, N, p, key_device(key), mask_row0, mask_row_step, stream);
 }
 
 // the stride and pointer checks the two attention entries share: `strides` = the n row strides, then the n batch strides
-static int mhsa_dropout_check(int64_t B, int64_t n_tokens, int64_t n_query_rows, const int64_t* strides, int n, const void* const* ptrs, int np) {
+static int mhsa_dropout_check(int64_t B, int64_t n_tokens, int64_t n_query_rows, const int64_t* strides, int n, const void* const* ptrs, int np, DropKey key) {
     if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
     for (int i = 0; i < np; ++i)
         if (!ptrs[i]) return CVAE_E_NULLPTR;
+    if (key.missing()) return CVAE_E_NULLPTR;
     for (int i = 0; i < 2 * n; ++i)
         if (strides[i] < (i < n ? VIT_DIM : 0)) return CVAE_E_BADSHAPE;
     for (int i = 0; i < 2 * n; ++i)
         if (strides[i] & 3) return CVAE_E_UNSUPPORTED;
     for (int i = 0; i < np; ++i)
         if (!aligned16(ptrs[i])) return CVAE_E_UNSUPPORTED;
-    return CVAE_OK;
+    return key.misaligned() ? CVAE_E_UNSUPPORTED : CVAE_OK;
+}
+
+static int mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                  int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
+                                  DropKey key, void* stream) {
+    DropArgs d;
+    if (!drop_args(p, key.value, &d)) return CVAE_E_BADSHAPE;
+    const int64_t strides[6] = {q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride};
+    const void* const ptrs[5] = {q, k, v, out, lse};
+    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 3, ptrs, 5, key);
+    if (rc != CVAE_OK) return rc;
+    const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
+    const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // as cvae_mhsa_fwd_train
+    hipLaunchKernelGGL(vit_attention_dropout_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride,
+                       k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, lse, d, key.words());
+    return launch_rc();
 }
 
 extern "C" int cvae_mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                            int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
                                            float p, uint64_t key, void* stream) {
-    DropArgs d;
-    if (!drop_args(p, key, &d)) return CVAE_E_BADSHAPE;
-    const int64_t strides[6] = {q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride};
-    const void* const ptrs[5] = {q, k, v, out, lse};
-    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 3, ptrs, 5);
-    if (rc != CVAE_OK) return rc;
-    const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
-    const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // as cvae_mhsa_fwd_train
-    hipLaunchKernelGGL(vit_attention_dropout_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride,
-                       k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, lse, d);
-    return launch_rc();
+    return mhsa_fwd_train_dropout(q, k, v, out, lse, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, p,
+                                  key_value(key), stream);
 }
 
-extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
-                                     float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
-                                     int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride,
-                                     int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
+extern "C" int cvae_mhsa_fwd_train_dropout_devkey(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride,
+                                                  int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens,
+                                                  int64_t n_query_rows, float p, const uint64_t* key, void* stream) {
+    return mhsa_fwd_train_dropout(q, k, v, out, lse, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, p,
+                                  key_device(key), stream);
+}
+
+static int mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv,
+                            int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                            int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
+                            int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, DropKey key, void* workspace, size_t workspace_bytes, void* stream) {
     DropArgs d;
-    if (!drop_args(p, key, &d)) return CVAE_E_BADSHAPE;
+    if (!drop_args(p, key.value, &d)) return CVAE_E_BADSHAPE;
     const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
                                  dq_batch_stride, dk_batch_stride, dv_batch_stride};
     const void* const ptrs[10] = {q, k, v, out, lse, dout, dq, dk, dv, workspace};
-    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 6, ptrs, 10);
+    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 6, ptrs, 10, key);
     if (rc != CVAE_OK) return rc;
     if (workspace_bytes < cvae_mhsa_bwd_workspace_bytes(B, n_query_rows)) return CVAE_E_WORKSPACE;
     const int N = (int)n_tokens, Nq = (int)n_query_rows;
@@ -847,8 +942,37 @@ extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float
                            dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
     const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, false>), gq, dim3(256), 0, st, aq, d);
+    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, false>), gq, dim3(256), 0, st, aq, d, key.words());
     CVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, true>), gk, dim3(256), 0, st, ak, d);
+    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, true>), gk, dim3(256), 0, st, ak, d, key.words());
+    return launch_rc();
+}
+
+extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
+                                     float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                                     int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride,
+                                     int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return mhsa_bwd_dropout(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride,
+                            dv_stride, dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, p, key_value(key), workspace, workspace_bytes,
+                            stream);
+}
+
+extern "C" int cvae_mhsa_bwd_dropout_devkey(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
+                                            float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                                            int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride,
+                                            int64_t dk_batch_stride, int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
+                                            const uint64_t* key, void* workspace, size_t workspace_bytes, void* stream) {
+    return mhsa_bwd_dropout(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride,
+                            dv_stride, dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, p, key_device(key), workspace, workspace_bytes,
+                            stream);
+}
+
+// ---- device-resident keys: the keys of one step's sites, derived on the device from a counter that the same launch advances ----------------
+extern "C" int cvae_dropout_keys_step(uint64_t base, int64_t* step, uint64_t* table, int n_blocks, void* stream) {
+    if (n_blocks < 1 || n_blocks > 65536) return CVAE_E_BADSHAPE;
+    if (!step || !table) return CVAE_E_NULLPTR;
+    if (((uintptr_t)step & 7) || ((uintptr_t)table & 7)) return CVAE_E_UNSUPPORTED;
+    hipLaunchKernelGGL(vit_dropout_keys_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, base, step, table, n_blocks);
     return launch_rc();
 }

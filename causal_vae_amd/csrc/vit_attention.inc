@@ -10,9 +10,12 @@ __global__ __launch_bounds__(256) void VIT_ATT_KERNEL(const T* __restrict__ q, c
                                                             , float* __restrict__ lse
 #endif
 #if VIT_ATT_TRAIN == 2
-                                                            , const DropArgs drop
+                                                            , const DropArgs drop_arg, const uint32_t* key_dev
 #endif
 ) {
+#if VIT_ATT_TRAIN == 2
+    const DropArgs drop = drop_with_key(drop_arg, key_dev);
+#endif
     using G = AttGeom<T>;
     constexpr bool BF = std::is_same<T, bf16>::value;
     __shared__ __attribute__((aligned(16))) T Ks[G::KS];

@@ -4,9 +4,12 @@
 template <typename T, bool DKV>
 __global__ __launch_bounds__(256) void VIT_ATT_BWD_KERNEL(const AttBwdArgs a
 #if VIT_ATT_BWD_DROP
-                                                          , const DropArgs drop
+                                                          , const DropArgs drop_arg, const uint32_t* key_dev
 #endif
 ) {
+#if VIT_ATT_BWD_DROP
+    const DropArgs drop = drop_with_key(drop_arg, key_dev);
+#endif
     using G = AttBwdGeom<T>;
     constexpr bool BF = std::is_same<T, bf16>::value;
     __shared__ __attribute__((aligned(16))) T W1n[G::NS];

@@ -10,9 +10,12 @@ __global__ __launch_bounds__(256) void VIT_GEMM_KERNEL(const T* __restrict__ x, 
                                                        , T* __restrict__ pre, int64_t ldp
 #endif
 #if VIT_GEMM_TRAIN == 2
-                                                       , const DropArgs drop, int64_t mask_row0, int64_t mask_row_step
+                                                       , const DropArgs drop_arg, int64_t mask_row0, int64_t mask_row_step, const uint32_t* key_dev
 #endif
 ) {
+#if VIT_GEMM_TRAIN == 2
+    const DropArgs drop = drop_with_key(drop_arg, key_dev);
+#endif
     using G = GemmGeom<T>;
     __shared__ __attribute__((aligned(16))) T xs[GEMM_BM * G::PITCH];
     __shared__ __attribute__((aligned(16))) T ws[GEMM_BN * G::PITCH];

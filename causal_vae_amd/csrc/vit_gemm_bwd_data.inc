@@ -4,9 +4,12 @@ template <typename T, typename TG, typename TO>
 __global__ __launch_bounds__(256) void VIT_GEMM_BWD_DATA_KERNEL(const TG* __restrict__ g, int64_t ldg, const float* __restrict__ W, const T* __restrict__ pre,
                                                                 int64_t ldp, const float* resid, int64_t ldr, TO* dx, int64_t lddx, int64_t M, int K, int N
 #if VIT_GEMM_BWD_DROP
-                                                                , const DropArgs drop, int64_t mask_row0, int64_t mask_row_step
+                                                                , const DropArgs drop_arg, int64_t mask_row0, int64_t mask_row_step, const uint32_t* key_dev
 #endif
 ) {
+#if VIT_GEMM_BWD_DROP
+    const DropArgs drop = drop_with_key(drop_arg, key_dev);
+#endif
     using G = GemmGeom<T>;
     constexpr int NP = G::KC / 8;                         // 4-element pieces of g per thread and chunk
     __shared__ __attribute__((aligned(16))) T xs[GEMM_BM * G::PITCH];

@@ -2061,8 +2061,9 @@ def _mhsa_fwd(what, q, k, v, n_query_rows, want_lse, dropout=None):
         return out, None
     lse = _empty((B, 8, nq), torch.float32, q)
     if dropout is not None:
-        p, key = _dropout_site(what, dropout, False, q)
-        check(lib.cvae_mhsa_fwd_train_dropout(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail[:9], p, key, stream()), "mhsa_fwd_train_dropout")
+        sfx, p, key = _dropout_site(what, dropout, False, q)
+        check(getattr(lib, "cvae_mhsa_fwd_train_dropout" + sfx)(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail[:9], p, key, stream()),
+              "mhsa_fwd_train_dropout" + sfx)
         return out, lse
     check(lib.cvae_mhsa_fwd_train(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), *tail), "mhsa_fwd_train")
     return out, lse
@@ -2127,18 +2128,69 @@ class DropoutKeys:
         return self
 
 
+class DeviceDropoutKeys:
+    """DropoutKeys with the step counter on the device: what a captured training step needs, and usable eagerly as well.  The same seed rule,
+    the same key(seed, step, block, site) integers and the same state() / load_state() dict as DropoutKeys, so checkpoints interchange.
+    advance() is one launch (cvae_dropout_keys_step): it returns a NEW [n_blocks, 4] int64 table holding the keys of the counter's current step — the bit
+    patterns of the unsigned 64-bit keys — and leaves the counter one higher; no value reaches the host.  A table per call keeps two forwards followed by two
+    backwards correct, and under capture the table lives in the graph's pool.  key(table, block, site) is the one-element view the ops take as `key`."""
+    ATTN, MLP_ACT, MLP_OUT = DropoutKeys.ATTN, DropoutKeys.MLP_ACT, DropoutKeys.MLP_OUT
+
+    def __init__(self, n_blocks, device, seed=None, step=0):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise L.CvaeError(f"DeviceDropoutKeys: the counter lives on the GPU, got device {device} (there is no CPU fallback; host keys: ops.DropoutKeys)")
+        if not 1 <= int(n_blocks) <= 1 << 16:
+            raise L.CvaeError(f"DeviceDropoutKeys: 1 <= n_blocks <= 65536 expected, got {n_blocks}")
+        self.n_blocks = int(n_blocks)
+        self.seed = int(torch.initial_seed() if seed is None else seed) & _M64
+        self.counter = torch.full((1,), int(step), dtype=torch.int64, device=device)
+
+    def advance(self):
+        table = torch.empty((self.n_blocks, 4), dtype=torch.int64, device=self.counter.device)
+        with torch.cuda.device(self.counter.device):
+            check(lib.cvae_dropout_keys_step(_splitmix64(self.seed), ptr(self.counter), ptr(table), self.n_blocks, stream()), "dropout_keys_step")
+        return table
+
+    @staticmethod
+    def key(table, block, site):
+        return table[block, site:site + 1]
+
+    def state(self):
+        """{"seed", "step"}: reads the counter back, which synchronizes with the device — never inside a capture."""
+        return {"seed": self.seed, "step": int(self.counter.item())}
+
+    def load_state(self, state):
+        """The counter is rewritten in place: a captured graph keeps reading it.  The seed is a launch argument, so a graph captured before keeps the seed
+        it was captured with."""
+        self.seed = int(state["seed"]) & _M64
+        self.counter.fill_(int(state["step"]))
+        return self
+
+
 def _dropout_site(what, dropout, rows, *tensors):
-    """(p, key) of an attention site or (p, key, row0, row_step) of a row site from the `dropout` argument of an op; the tensors must be fp32."""
+    """(entry suffix, p, key) of an attention site or (entry suffix, p, key, row0, row_step) of a row site from the `dropout` argument of an op; the tensors
+    must be fp32.  key: a Python int (suffix "": passed by value) or a one-element int64 tensor on the operands' device (suffix "_devkey": its address is
+    passed and the kernel reads it when it runs — the value is never brought to the host)."""
     n = len(dropout) if isinstance(dropout, (tuple, list)) else 0
     if n not in ((2, 4) if rows else (2,)):
         raise L.CvaeError(f"{what}: dropout must be (p, key)" + (" or (p, key, row0, row_step)" if rows else "") + f", got {dropout!r}")
-    p, key = float(dropout[0]), int(dropout[1])
+    p, key, suffix = float(dropout[0]), dropout[1], ""
+    if isinstance(key, torch.Tensor):
+        ref = next(t for t in tensors if t is not None)
+        if key.dtype != torch.int64 or key.numel() != 1 or key.device != ref.device or key.data_ptr() % 8:
+            raise L.CvaeError(f"{what}: a tensor key must be one int64 element on the operands' device ({ref.device}), got {tuple(key.shape)} {key.dtype} "
+                              f"on {key.device}")
+        key, suffix, key_ok = key.data_ptr(), "_devkey", True
+    else:
+        key = int(key)
+        key_ok = 0 <= key <= _M64
     row0, step = (int(dropout[2]), int(dropout[3])) if n == 4 else (0, 1)
-    if not (0.0 <= p < 1.0 and 0 <= key <= _M64 and row0 >= 0 and step >= 1):
+    if not (0.0 <= p < 1.0 and key_ok and row0 >= 0 and step >= 1):
         raise L.CvaeError(f"{what}: dropout needs 0 <= p < 1, a 64-bit key, row0 >= 0 and row_step >= 1, got {dropout!r}")
     if any(t is not None and t.dtype != torch.float32 for t in tensors):
         raise L.CvaeError(f"{what}: dropout is implemented for float32 tensors only (bfloat16 compute dtype: not yet)")
-    return (p, key, row0, step) if rows else (p, key)
+    return (suffix, p, key, row0, step) if rows else (suffix, p, key)
 
 
 def mhsa_train(q, k, v, n_query_rows=None, dropout=None):
@@ -2165,10 +2217,10 @@ def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, dropout=None):
         raise L.CvaeError("mhsa_bwd: dq, dk and dv must not overlap each other or an operand")
     _t, wp, wb = _scratch(lib.cvae_mhsa_bwd_workspace_bytes(B, nq), q)
     if dropout is not None:
-        p, key = _dropout_site("mhsa_bwd", dropout, False, q)
-        check(lib.cvae_mhsa_bwd_dropout(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1),
-                                        q.stride(0), k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0),
-                                        B, N, nq, p, key, wp, wb, stream()), "mhsa_bwd_dropout")
+        sfx, p, key = _dropout_site("mhsa_bwd", dropout, False, q)
+        check(getattr(lib, "cvae_mhsa_bwd_dropout" + sfx)(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1),
+                                                          v.stride(1), q.stride(0), k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0),
+                                                          dk.stride(0), dv.stride(0), B, N, nq, p, key, wp, wb, stream()), "mhsa_bwd_dropout" + sfx)
         return dq, dk, dv
     check(lib.cvae_mhsa_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1), q.stride(0),
                             k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0), B, N, nq,
@@ -2192,7 +2244,7 @@ def token_gemm_dropout(x, weight, bias, epilogue, dropout, resid=None, out=None)
     N = weight.shape[0]
     if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in ("gelu", "residual"):
         raise L.CvaeError(f"token_gemm_dropout: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r} ('gelu' or 'residual')")
-    p, key, row0, step = _dropout_site("token_gemm_dropout", dropout, True, x)
+    sfx, p, key, row0, step = _dropout_site("token_gemm_dropout", dropout, True, x)
     pre = None
     if epilogue == "residual":
         if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_dropout resid", N).shape[0] != M:
@@ -2204,9 +2256,9 @@ def token_gemm_dropout(x, weight, bias, epilogue, dropout, resid=None, out=None)
         out, pre = _empty((M, N), torch.float32, x), _empty((M, N), torch.float32, x)
     if _rows2d(out, "token_gemm_dropout out", N).shape[0] != M or out.dtype != torch.float32:
         raise L.CvaeError(f"token_gemm_dropout: out {tuple(out.shape)} {out.dtype}")
-    check(lib.cvae_token_gemm_dropout(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid), resid.stride(0) if resid is not None else 0,
-                                      ptr(pre), N if pre is not None else 0, ptr(out), out.stride(0), M, K, N, GEMM_EPI[epilogue], p, key, row0, step, stream()),
-          "token_gemm_dropout")
+    check(getattr(lib, "cvae_token_gemm_dropout" + sfx)(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid),
+                                                        resid.stride(0) if resid is not None else 0, ptr(pre), N if pre is not None else 0, ptr(out), out.stride(0),
+                                                        M, K, N, GEMM_EPI[epilogue], p, key, row0, step, stream()), "token_gemm_dropout" + sfx)
     return (out, pre) if epilogue == "gelu" else out
 
 
@@ -2216,13 +2268,13 @@ def dropout_rows(x, dropout, out=None):
     L.require_gpu(x, out)
     _forward_only("dropout_rows", x)
     _rows2d(x, "dropout_rows")
-    p, key, row0, step = _dropout_site("dropout_rows", dropout, True, x, out)
+    sfx, p, key, row0, step = _dropout_site("dropout_rows", dropout, True, x, out)
     M, N = x.shape
     if out is None:
         out = _empty((M, N), torch.float32, x)
     if _rows2d(out, "dropout_rows out", N).shape[0] != M:
         raise L.CvaeError(f"dropout_rows: out {tuple(out.shape)} for x {tuple(x.shape)}")
-    check(lib.cvae_dropout_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, p, key, row0, step, stream()), "dropout_rows")
+    check(getattr(lib, "cvae_dropout_rows" + sfx)(ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, p, key, row0, step, stream()), "dropout_rows" + sfx)
     return out
 
 
@@ -2257,11 +2309,12 @@ def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=No
     if _rows2d(out, "token_gemm_bwd_data out", K).shape[0] != M or out.dtype not in (torch.float32, mode) or (resid is not None and out.dtype != torch.float32):
         raise L.CvaeError(f"token_gemm_bwd_data: out {tuple(out.shape)} {out.dtype}")
     if dropout is not None:
-        p, key, row0, step = _dropout_site("token_gemm_bwd_data", dropout, True, g, out)
+        sfx, p, key, row0, step = _dropout_site("token_gemm_bwd_data", dropout, True, g, out)
         if mode != torch.float32 or resid is not None:
             raise L.CvaeError("token_gemm_bwd_data: dropout runs in fp32 arithmetic and takes no residual")
-        check(lib.cvae_token_gemm_bwd_data_dropout(ptr(g), g.stride(0), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
-                                                   ptr(out), out.stride(0), M, K, N, p, key, row0, step, stream()), "token_gemm_bwd_data_dropout")
+        check(getattr(lib, "cvae_token_gemm_bwd_data_dropout" + sfx)(ptr(g), g.stride(0), ptr(weight.detach()), ptr(gate_pre),
+                                                                     gate_pre.stride(0) if gate_pre is not None else 0, ptr(out), out.stride(0), M, K, N, p, key,
+                                                                     row0, step, stream()), "token_gemm_bwd_data_dropout" + sfx)
         return out
     check(lib.cvae_token_gemm_bwd_data(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
                                        ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), L.dtype_code(out.dtype), M, K, N,

@@ -3,7 +3,9 @@ ViTVAEEncoder: image -> (mu, log_var) / CLS features; ViTVAE: the same plus deco
 between the fused adapter heads of the (x, m, t) -> z -> (z, m) -> x model; CausalViTVAE.train_adapters / forward_train train those heads on the frozen
 eval-mode backbone (the reference's vae.train() also trains the backbone and runs its dropout and BatchNorm2d in training mode: here it stays frozen, or
 learns in eval mode: train_decoder / train_transformer / train_stem).  ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae: the reference's ViTVAE
-training loop (latent_translator/engine.py:6-36) end to end, in that eval-mode regime."""
+training loop (latent_translator/engine.py:6-36) end to end, in that eval-mode regime.  vit_vae_train_step / causal_vit_train_step: one step of either
+recipe; GraphedViTTrainStep: that step captured as one HIP graph, which train_vit_vae(graph=True) replays."""
 from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, resize_pos_embedding, fit_latent,   # noqa: F401
-                     vit_vae_loss, train_vit_vae)
+                     vit_vae_loss, train_vit_vae, vit_vae_train_step)
 from .causal import AdapterMLP, CausalViTVAE   # noqa: F401
+from .train import GraphedViTTrainStep, causal_vit_train_step   # noqa: F401

@@ -98,7 +98,10 @@ class ViTVAEEncoder(nn.Module):
         self.to_latent = nn.LayerNorm(embed_dim)
         self.fc_mu = nn.Linear(embed_dim, latent_dim)
         self.fc_var = nn.Linear(embed_dim, latent_dim)
-        self.dropout_keys = ops.DropoutKeys()               # host-side: the Philox keys of train_transformer(dropout=True)'s masks, .step advanced per training forward
+        # the Philox keys of train_transformer(dropout=True)'s masks, one step per training forward: ops.DropoutKeys (host-side, the default) or, after
+        # use_device_dropout_keys(), ops.DeviceDropoutKeys (the step counter on the device: what a captured step needs).  A plain attribute:
+        # its device tensors are no buffers, the state_dict keys stay the reference's.
+        self.dropout_keys = ops.DropoutKeys()
 
     def set_compute_dtype(self, dtype):
         if dtype not in (torch.float32, torch.bfloat16):
@@ -182,12 +185,16 @@ class ViTVAEEncoder(nn.Module):
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
         after every block that ran for all tokens).
         After train_transformer(dropout=True) a save=True walk runs every block in its dropout form: one step of self.dropout_keys per walk, the
-        rates read from the block's modules.  save=False never drops."""
+        rates read from the block's modules.  save=False never drops.  With device keys (use_device_dropout_keys) the step is one more launch
+        and the sites' keys are views of its table: the same masks, and nothing here reads the counter."""
         self._check(x)
         drop_step = None
         if save and self._dropout:
             self._check_dropout_dtype()
-            drop_step, self.dropout_keys.step = self.dropout_keys.step, self.dropout_keys.step + 1
+            if isinstance(self.dropout_keys, ops.DeviceDropoutKeys):
+                drop_step = self.dropout_keys.advance()                 # this walk's [depth, 4] key table: one launch, the counter moves on the device
+            else:
+                drop_step, self.dropout_keys.step = self.dropout_keys.step, self.dropout_keys.step + 1
         kept = {} if keep_stem else None
         stem = self._stem_cl(x, kept)
         tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
@@ -287,8 +294,23 @@ class ViTVAEEncoder(nn.Module):
             raise CvaeError("ViTVAEEncoder: dropout is implemented for the float32 compute dtype only (the dropout kernels take no bfloat16 operands yet): "
                             "set_compute_dtype(torch.float32), or train_transformer(dropout=False)")
 
+    def use_device_dropout_keys(self, on=True):
+        """Swap self.dropout_keys between ops.DropoutKeys (host step counter; the default) and ops.DeviceDropoutKeys (the counter on the parameters' device,
+        advanced by a launch: DESIGN §19), keeping the seed and the step, so the masks of the steps to come are the same either way.  Switching to host
+        keys reads the counter back (a sync).  A model on the CPU has no device to keep the counter on: CvaeError, and the host keys stay."""
+        keys, dev = self.dropout_keys, self.cls_token.device
+        if on and not isinstance(keys, ops.DeviceDropoutKeys):
+            if dev.type != "cuda":
+                raise CvaeError(f"ViTVAEEncoder.use_device_dropout_keys: the model is on {dev}; device keys live on the GPU (there is no CPU fallback: move the "
+                                "model to 'cuda' first)")
+            self.dropout_keys = ops.DeviceDropoutKeys(self.depth, dev, seed=keys.seed, step=keys.step)
+        elif not on and isinstance(keys, ops.DeviceDropoutKeys):
+            self.dropout_keys = ops.DropoutKeys().load_state(keys.state())
+        return self
+
     def _block_dropout(self, blk, i, step):
-        """((p, key) or None) for block i's three sites at this step: the rates are the modules' (attn.dropout, mlp[2].p, mlp[4].p); a rate of 0 is None."""
+        """((p, key) or None) for block i's three sites at this step: the rates are the modules' (attn.dropout, mlp[2].p, mlp[4].p); a rate of 0 is None.
+        step: the step number (host keys: key is an int) or the table of DeviceDropoutKeys.advance() (key is a one-element view of it)."""
         K = ops.DropoutKeys
         sites = ((blk.attn.dropout, K.ATTN), (blk.mlp[2].p, K.MLP_ACT), (blk.mlp[4].p, K.MLP_OUT))
         return tuple((float(p), self.dropout_keys.key(step, i, site)) if p > 0 else None for p, site in sites)
@@ -752,24 +774,50 @@ def vit_vae_loss(recons, x, mu, log_var, beta=1.0):
     return recon + beta * kld
 
 
-def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False):
-    """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature plus `dropout`: per batch["x"], zero_grad, model.forward_train,
-    vit_vae_loss, backward, optimizer.step().  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval
+def vit_vae_train_step(model, optimizer, x, eps=None, beta=1.0):
+    """One iteration of train_vit_vae's loop: zero_grad, model.forward_train(x, eps), vit_vae_loss, backward, optimizer.step() -> the loss, a 0-dim device
+    tensor.  Needs model.train_all() (or the train_*() calls of the parts that learn) first.  Nothing here syncs with the host, so the step can be
+    captured (GraphedViTTrainStep)."""
+    optimizer.zero_grad()
+    loss = vit_vae_loss(*model.forward_train(x, eps), beta=beta)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
+
+
+def _check_graph_optimizer(what, optimizer):
+    from ..optim import FusedAdam
+    if not isinstance(optimizer, FusedAdam) or not optimizer.device_step:
+        raise CvaeError(f"{what} needs FusedAdam(..., device_step=True): a captured step replays with the step count on the device "
+                        f"(got {type(optimizer).__name__}" + (" with device_step=False" if isinstance(optimizer, FusedAdam) else "") + ")")
+
+
+def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False, graph=False):
+    """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature plus `dropout` and `graph`: per batch["x"], zero_grad, model.forward_train,
+    vit_vae_loss, backward, optimizer.step() (vit_vae_train_step).  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval
     mode, so every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state), and there is no
     dropout unless dropout=True: then the transformer blocks drop as the reference's do under train(), at the modules' rates, with Philox masks
     (train_transformer(dropout=True); float32 compute dtype).  All parameters learn (model.train_all() is called, so an optimizer built over
-    model.parameters() fits).  Returns the per-epoch mean losses as a list of floats (sample-weighted, read from the device once per epoch)."""
+    model.parameters() fits).  Returns the per-epoch mean losses as a list of floats (sample-weighted, read from the device once per epoch).
+    graph=True (needs FusedAdam(device_step=True), else CvaeError): the step is captured once, from the first batch, as one HIP graph (GraphedViTTrainStep,
+    DESIGN §19) and replayed for every batch of that shape; a batch of another shape (a ragged last one) takes the eager step.  With dropout the keys then
+    live on the device (model.use_device_dropout_keys()), for the eager steps too."""
+    if graph:
+        _check_graph_optimizer("train_vit_vae(graph=True)", optimizer)
     model.eval()
     model.train_all(dropout=dropout)
-    history = []
+    history, graphed = [], None
     for _ep in range(int(epochs)):
         total, n = [], 0
         for batch in loader:
             x = batch["x"].to(device)
-            optimizer.zero_grad()
-            loss = vit_vae_loss(*model.forward_train(x), beta=beta)
-            loss.backward()
-            optimizer.step()
+            if graph and graphed is None:
+                from .train import GraphedViTTrainStep
+                graphed = GraphedViTTrainStep(model, optimizer, (x,), beta=beta)
+            if graphed is not None and x.shape == graphed.batch[0].shape:
+                loss = graphed(x)
+            else:
+                loss = vit_vae_train_step(model, optimizer, x, beta=beta)
             total.append(loss.detach() * x.shape[0])
             n += x.shape[0]
         history.append(float(torch.stack(total).sum().cpu()) / max(n, 1) if total else 0.0)

@@ -405,6 +405,38 @@ int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const flo
 int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, uint64_t key, int64_t mask_row0,
                       int64_t mask_row_step, void* stream);
 
+/* ---- device-resident dropout keys (csrc/vit.hip) -----------------------------------------------------------------------------------
+ * What a captured training step needs: keys that are not launch arguments.  A graph bakes every by-value argument in, so the five entries above would
+ * replay one mask for ever; the forms below read the key from device memory when the kernel runs, and one more entry derives a step's keys on the device.
+ *
+ * THE KEY OF A SITE (normative; the host's ops.DropoutKeys.key computes the same integers).  With splitmix64(z): z += 0x9E3779B97F4A7C15;
+ * z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31), all mod 2^64:
+ *   key(seed, step, block, site) = splitmix64(splitmix64(seed) + (step << 20 | block << 4 | site)),   step < 2^44, block < 2^16, site < 16.
+ *
+ *   cvae_dropout_keys_step   base = splitmix64(seed), computed by the caller.  One workgroup reads s = *step mod 2^44, writes
+ *                            table[4 b + site] = splitmix64(base + (s << 20 | b << 4 | site)) for b < n_blocks, site < 4, and — after a workgroup barrier
+ *                            that follows every thread's read — stores s + 1 to *step.  1 <= n_blocks <= 65536, else CVAE_E_BADSHAPE; step and table are
+ *                            8-byte-aligned device pointers (null: CVAE_E_NULLPTR), table holds 4 n_blocks words.
+ *   cvae_*_devkey            the five entries above with `uint64_t key` replaced by `const uint64_t* key`: an 8-byte-aligned device pointer to the key
+ *                            (null: CVAE_E_NULLPTR; misaligned: CVAE_E_UNSUPPORTED), read by the kernel when it runs — low word k0, high word k1.  Every
+ *                            other argument, check and output bit is the sibling's: the same key gives the same bits through either form. */
+int cvae_dropout_keys_step(uint64_t base, int64_t* step, uint64_t* table, int n_blocks, void* stream);
+int cvae_mhsa_fwd_train_dropout_devkey(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                       int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                                       float p, const uint64_t* key, void* stream);
+int cvae_mhsa_bwd_dropout_devkey(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv,
+                                 int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                                 int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
+                                 int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, const uint64_t* key, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int cvae_token_gemm_dropout_devkey(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                                   int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, const uint64_t* key,
+                                   int64_t mask_row0, int64_t mask_row_step, void* stream);
+int cvae_token_gemm_bwd_data_dropout_devkey(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
+                                            int64_t M, int64_t K, int64_t N, float p, const uint64_t* key, int64_t mask_row0, int64_t mask_row_step, void* stream);
+int cvae_dropout_rows_devkey(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, const uint64_t* key, int64_t mask_row0,
+                             int64_t mask_row_step, void* stream);
+
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
  * (no atomics, no split-K): bit-reproducible, and a sample's bits do not depend on the batch it travels in.  Pointers 16-byte aligned, else CVAE_E_UNSUPPORTED;
