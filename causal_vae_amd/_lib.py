@@ -152,6 +152,8 @@ SIGNATURES = {
     "cvae_token_gemm_dropout_devkey": [_p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i, _f, _p, _i64, _i64, _p],
     "cvae_token_gemm_bwd_data_dropout_devkey": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _f, _p, _i64, _i64, _p],
     "cvae_dropout_rows_devkey": [_p, _i64, _p, _i64, _i64, _i64, _f, _p, _i64, _i64, _p],
+    "cvae_mhsa_weights": [_p] * 4 + [_i64] * 8 + [_i, _i, _p],
+    "cvae_mhsa_rollout_step": [_p] * 5 + [_i64] * 7 + [_f, _i, _p],
     "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
     "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],

@@ -11,6 +11,8 @@
 // the two backward kernels that have a dropout form, each included twice.  The dropout forms take their Philox key by value or (the *_devkey entries, DESIGN.md
 // section 19) read it from device memory at kernel entry, which is what lets a captured training step replay with a new key; vit_dropout_keys_step_kernel derives
 // a step's keys from a device-resident counter and advances it.
+// vit_attention_probe.inc holds the one forward-only kernel that looks inside: the attention probabilities the fused forward never writes,
+// recomputed from q, k and the training forward's row statistic, stored (per head or head-averaged) or folded into one attention-rollout factor.
 // Two arithmetic modes from one template: bf16 operands on v_mfma_f32_32x32x16_bf16, or exact fp32 on v_mfma_f32_32x32x2_f32 (the form the conv family uses
 // for fp32); accumulation, softmax, LayerNorm statistics and the residual stream are fp32 in both.  No atomics anywhere: every sum has a fixed order,
 // and an output element's bits do not depend on which other rows share its launch (row r of a one-row call equals row r of a full call: the CLS-only
@@ -518,6 +520,9 @@ template <> struct AttBwdGeom<float> { static constexpr int NP = 40, TP = 0, NS 
 #undef VIT_ATT_BWD_KERNEL
 #undef VIT_ATT_BWD_DROP
 
+// ------------------------------------------------------------------------------------------------ attention weights and rollout
+#include "vit_attention_probe.inc"
+
 }  // namespace
 
 static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
@@ -753,6 +758,63 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
         hipLaunchKernelGGL((vit_attention_bwd_kernel<T, true>), gk, dim3(256), 0, st, ak);
         return launch_rc();
     });
+}
+
+// ---- attention weights and attention rollout: forward-only views inside the encoder, recomputed from q, k and cvae_mhsa_fwd_train's lse.
+
+// the checks the two entries share (pointers and strides as cvae_mhsa_fwd); CVAE_OK with B == 0 means: nothing to launch
+static int mhsa_probe_check(const void* q, const void* k, const float* lse, int64_t q_stride, int64_t k_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                            int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype) {
+    if (B < 0 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
+    if (B == 0) return CVAE_OK;
+    if (!q || !k || !lse) return CVAE_E_NULLPTR;
+    const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
+    if (q_stride < VIT_DIM || k_stride < VIT_DIM || q_batch_stride < 0 || k_batch_stride < 0) return CVAE_E_BADSHAPE;
+    if ((q_stride % e16) || (k_stride % e16) || (q_batch_stride % e16) || (k_batch_stride % e16) || !aligned16(q) || !aligned16(k) || ((uintptr_t)lse & 3))
+        return CVAE_E_UNSUPPORTED;
+    return CVAE_OK;
+}
+
+// the one launch of both entries: a workgroup per (128 keys, head in the per-head form, batch row)
+static int mhsa_probe_launch(const AttProbeArgs& a, int mode, int64_t B, int dtype, void* stream) {
+    const dim3 grid((unsigned)((a.N + 127) / 128), mode == PROBE_HEADS ? VIT_HEADS : 1, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        if (mode == PROBE_HEADS) hipLaunchKernelGGL((vit_attention_probe_kernel<T, PROBE_HEADS>), grid, dim3(256), 0, st, a);
+        else if (mode == PROBE_AVERAGE) hipLaunchKernelGGL((vit_attention_probe_kernel<T, PROBE_AVERAGE>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((vit_attention_probe_kernel<T, PROBE_ROLLOUT>), grid, dim3(256), 0, st, a);
+        return launch_rc();
+    });
+}
+
+extern "C" int cvae_mhsa_weights(const void* q, const void* k, const float* lse, float* w, int64_t q_stride, int64_t k_stride, int64_t q_batch_stride,
+                                 int64_t k_batch_stride, int64_t w_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int average_heads, int dtype,
+                                 void* stream) {
+    const int rc = mhsa_probe_check(q, k, lse, q_stride, k_stride, q_batch_stride, k_batch_stride, B, n_tokens, n_query_rows, dtype);
+    if (rc != CVAE_OK || B == 0) return rc;
+    if (!w) return CVAE_E_NULLPTR;
+    if (w_batch_stride < (average_heads ? 1 : VIT_HEADS) * n_query_rows * n_tokens) return CVAE_E_BADSHAPE;
+    if (!aligned16(w)) return CVAE_E_UNSUPPORTED;
+    const AttProbeArgs a = {q, k, q_stride, k_stride, q_batch_stride, k_batch_stride, lse, nullptr, w, w_batch_stride, (int)n_tokens, (int)n_query_rows,
+                            0.17677669529663688110f * 1.44269504088896340736f, 0.f};       // 1 / sqrt(32) * log2(e), as cvae_mhsa_fwd
+    return mhsa_probe_launch(a, average_heads ? PROBE_AVERAGE : PROBE_HEADS, B, dtype, stream);
+}
+
+extern "C" int cvae_mhsa_rollout_step(const void* q, const void* k, const float* lse, const float* r, float* out, int64_t q_stride, int64_t k_stride,
+                                      int64_t q_batch_stride, int64_t k_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float residual, int dtype,
+                                      void* stream) {
+    const int rc = mhsa_probe_check(q, k, lse, q_stride, k_stride, q_batch_stride, k_batch_stride, B, n_tokens, n_query_rows, dtype);
+    if (rc != CVAE_OK) return rc;
+    if (!(residual >= 0.f && residual <= 1.f)) return CVAE_E_BADSHAPE;
+    if (B == 0) return CVAE_OK;
+    if (!r || !out) return CVAE_E_NULLPTR;
+    if (((uintptr_t)r & 3) || ((uintptr_t)out & 3)) return CVAE_E_UNSUPPORTED;
+    if (r < out + B * n_tokens && out < r + B * n_tokens) return CVAE_E_UNSUPPORTED;       // out == r, or any overlap: other workgroups still read r
+    const AttProbeArgs a = {q, k, q_stride, k_stride, q_batch_stride, k_batch_stride, lse, r, out, 0, (int)n_tokens, (int)n_query_rows,
+                            0.17677669529663688110f * 1.44269504088896340736f, residual};
+    return mhsa_probe_launch(a, PROBE_ROLLOUT, B, dtype, stream);
 }
 
 // ---- dropout entries: the training forms above with a Philox mask recomputed in registers.  fp32 only: no dtype code is taken and the float

@@ -2228,6 +2228,66 @@ def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, dropout=None):
     return dq, dk, dv
 
 
+# ---- attention weights and attention rollout (csrc/vit.hip): forward-only, recomputed from q, k and mhsa_train's lse -----------------------
+def _mhsa_probe(what, q, k, lse, n_query_rows):
+    """The checks mhsa_weights and mhsa_rollout_step share -> (B, N, n_query_rows, the stride / size arguments of their entries)."""
+    L.require_gpu(q, k, lse)
+    _forward_only(what, q, k, lse)
+    B, N = k.shape[0], k.shape[1]
+    nq = N if n_query_rows is None else int(n_query_rows)
+    if not 1 <= nq <= N:
+        raise L.CvaeError(f"{what}: 1 <= n_query_rows <= {N} expected, got {nq}")
+    _mhsa_views(what, B, (nq, N), q, k)
+    if lse.shape != (B, 8, nq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise L.CvaeError(f"{what}: lse must be the contiguous float32 [{B}, 8, {nq}] row statistic of mhsa_train, got {tuple(lse.shape)} {lse.dtype}")
+    return B, N, nq, (q.stride(1), k.stride(1), q.stride(0), k.stride(0))
+
+
+def mhsa_weights(q, k, lse, n_query_rows=None, average_heads=True, out=None):
+    """The attention probabilities mhsa never writes (cvae_mhsa_weights): P = 2^(s - lse) recomputed from q [B, >= n_query_rows, 256], k [B, N, 256] (views as
+    mhsa takes them) and lse [B, 8, n_query_rows], the row statistic mhsa_train returned for the same q and k.
+    average_heads=True: fp32 [B, n_query_rows, N], the head-order sum times 1/8 — what nn.MultiheadAttention(need_weights=True) returns in eval mode;
+    False: fp32 [B, 8, n_query_rows, N].  Rows are dense (N floats).  Per head at N = 961 this is 29.6 MB per image: the only N x N object of the ViT path.
+    out: an fp32 tensor of that shape to write into; its batch stride is free, one batch's block must be contiguous and its base 16-byte aligned."""
+    B, N, nq, strides = _mhsa_probe("mhsa_weights", q, k, lse, n_query_rows)
+    shape = (B, nq, N) if average_heads else (B, 8, nq, N)
+    if out is None:
+        out = _empty(shape, torch.float32, q)
+    else:
+        L.require_gpu(out)
+        if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != q.device or (B and not out[0].is_contiguous())
+                or (B > 1 and out.stride(0) < out[0].numel()) or out.data_ptr() % 16):
+            raise L.CvaeError(f"mhsa_weights: out must be a float32 {shape} tensor on {q.device} with contiguous batch blocks and a 16-byte-aligned base, got "
+                              f"{tuple(out.shape)} {out.dtype} strides {tuple(out.stride())}")
+    if B == 0:
+        return out
+    check(lib.cvae_mhsa_weights(ptr(q), ptr(k), ptr(lse), ptr(out), *strides, out.stride(0) if B > 1 else out[0].numel(), B, N, nq, int(bool(average_heads)),
+                                L.dtype_code(q.dtype), stream()), "mhsa_weights")
+    return out
+
+
+def mhsa_rollout_step(q, k, lse, r, n_query_rows=None, residual=0.5, out=None):
+    """One factor of attention rollout applied to a row vector, the N x N matrix never formed (cvae_mhsa_rollout_step):
+    out[b, j] = residual r[b, j] + (1 - residual) / 8 sum_h sum_{i < n_query_rows} r[b, i] P[b, h, i, j], with P as in mhsa_weights.
+    r: fp32 [B, N] contiguous; returns fp32 [B, N] (written to `out` if given: it must not be r or overlap it).  0 <= residual <= 1."""
+    B, N, nq, strides = _mhsa_probe("mhsa_rollout_step", q, k, lse, n_query_rows)
+    L.require_gpu(r, out)
+    residual = float(residual)
+    if not 0.0 <= residual <= 1.0:
+        raise L.CvaeError(f"mhsa_rollout_step: 0 <= residual <= 1 expected, got {residual}")
+    if r.shape != (B, N) or r.dtype != torch.float32 or not r.is_contiguous() or r.device != q.device:
+        raise L.CvaeError(f"mhsa_rollout_step: r must be a contiguous float32 [{B}, {N}] tensor on {q.device}, got {tuple(r.shape)} {r.dtype}")
+    if out is None:
+        out = _empty((B, N), torch.float32, q)
+    elif out.shape != r.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != r.device:
+        raise L.CvaeError(f"mhsa_rollout_step: out must be a contiguous float32 [{B}, {N}] tensor on {q.device}, got {tuple(out.shape)} {out.dtype}")
+    if B == 0:
+        return out
+    check(lib.cvae_mhsa_rollout_step(ptr(q), ptr(k), ptr(lse), ptr(r), ptr(out), *strides, B, N, nq, residual, L.dtype_code(q.dtype), stream()),
+          "mhsa_rollout_step")
+    return out
+
+
 def token_gemm_gelu_train(x, weight, bias):
     """(gelu(x W^T + b), x W^T + b), both in x's dtype: token_gemm's "gelu" output, bit for bit, and the pre-activation (cvae_token_gemm_gelu_train)."""
     return _token_gemm("token_gemm_gelu_train", x, weight, bias, "gelu", None, None, True)

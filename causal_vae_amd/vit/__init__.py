@@ -4,8 +4,13 @@ between the fused adapter heads of the (x, m, t) -> z -> (z, m) -> x model; Caus
 eval-mode backbone (the reference's vae.train() also trains the backbone and runs its dropout and BatchNorm2d in training mode: here it stays frozen, or
 learns in eval mode: train_decoder / train_transformer / train_stem).  ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae: the reference's ViTVAE
 training loop (latent_translator/engine.py:6-36) end to end, in that eval-mode regime.  vit_vae_train_step / causal_vit_train_step: one step of either
-recipe; GraphedViTTrainStep: that step captured as one HIP graph, which train_vit_vae(graph=True) replays."""
-from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, resize_pos_embedding, fit_latent,   # noqa: F401
+recipe; GraphedViTTrainStep: that step captured as one HIP graph, which train_vit_vae(graph=True) replays.
+Looking inside: ViTVAEEncoder.attention_weights / attention_rollout (so ViTVAE's, and CausalViTVAE.attention_rollout through its backbone) and
+extract_vit_attention, the rollout maps of a loader."""
+from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, extract_vit_attention, resize_pos_embedding, fit_latent,   # noqa: F401
                      vit_vae_loss, train_vit_vae, vit_vae_train_step)
 from .causal import AdapterMLP, CausalViTVAE   # noqa: F401
 from .train import GraphedViTTrainStep, causal_vit_train_step   # noqa: F401
+
+__all__ = ["ViTVAE", "ViTVAEEncoder", "load_vitvae_state_dict", "extract_vit_latents", "extract_vit_attention", "resize_pos_embedding", "fit_latent",
+           "vit_vae_loss", "train_vit_vae", "vit_vae_train_step", "AdapterMLP", "CausalViTVAE", "GraphedViTTrainStep", "causal_vit_train_step"]

@@ -211,6 +211,12 @@ class CausalViTVAE(nn.Module):
         m_mu, m_logvar, _z = ops.mlp_heads([t], self.morph_layers(), clamp1=(-10.0, 10.0))
         return m_mu, m_logvar
 
+    def attention_rollout(self, x, **kw):
+        """backbone.attention_rollout(x, **kw): where the encoder's CLS token looks.  The adapters read the CLS features only, so this is the
+        whole image path of encode."""
+        self._require_eval()
+        return self.backbone.attention_rollout(x, **kw)
+
     @torch.no_grad()
     def decode(self, z, m):
         """backbone.decode(dec_adapter(cat[m, z])) -> [B, 1, H, W] (models.py:299-305).  Note the argument order: z first, m second; the concatenation is

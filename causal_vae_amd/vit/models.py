@@ -135,7 +135,7 @@ class ViTVAEEncoder(nn.Module):
                 keep["ys"].append(h)
         return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
 
-    def _block(self, blk, tokens, cls_only, save, drop=_NO_DROP):
+    def _block(self, blk, tokens, cls_only, save, drop=_NO_DROP, attention=None):
         """One transformer block on the fp32 residual stream `tokens` [B, N, 256] -> (the stream after it [B, N, 256], or with cls_only the block's CLS rows
         [B, 256]: the same sums in the same order as the full block's row 0, `tokens` left as it was; _BlockStep or None).
         save=False (inference): the residual GEMMs of a full block write the stream in place and nothing is kept.  save=True: the same launches with attention
@@ -143,14 +143,16 @@ class ViTVAEEncoder(nn.Module):
         and its middle (after attention) are LayerNorm inputs the backward needs, so they are kept rather than copied.
         drop (with save): ((p, key) or None) per dropout site — attention probabilities, GELU output, second Linear's output.  A site with a pair
         runs the dropout form of its launch (as many launches as without); None: the plain launch.  The row sites' mask rows are the token rows b N + i of
-        the [B N, .] stream, so a CLS-only block (rows b) passes (row0, row_step) = (0, N) and its one query row is query 0: the full block's CLS rows."""
+        the [B N, .] stream, so a CLS-only block (rows b) passes (row0, row_step) = (0, N) and its one query row is query 0: the full block's CLS rows.
+        attention (a callable): receives (q, k, lse) of the block's attention, views as ops.mhsa_weights takes them.  An inference block then runs
+        its attention as ops.mhsa_train without dropout (the same `out`, bit for bit, plus lse); nothing else changes."""
         B, N, D = tokens.shape
         att_d, act_d, out_d = drop
         rows = (0, N) if cls_only else (0, 1)
         dt = self.compute_dtype
         X = tokens.view(B * N, D)
         a = blk.attn
-        attend = (lambda *a, **kw: ops.mhsa_train(*a, dropout=att_d, **kw)) if save else ops.mhsa
+        attend = (lambda *a, **kw: ops.mhsa_train(*a, dropout=att_d, **kw)) if save else (ops.mhsa if attention is None else ops.mhsa_train)
         y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
         if not cls_only:
             qkv, q = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D), None
@@ -161,7 +163,9 @@ class ViTVAEEncoder(nn.Module):
             q = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D]).view(B, 1, D)
             att = attend(q, qkv[:, :, :D], qkv[:, :, D:], n_query_rows=1)
             resid, X1 = tokens[:, 0], torch.empty(B, D, dtype=torch.float32, device=tokens.device)
-        att, lse = att if save else (att, None)
+        att, lse = att if (save or attention is not None) else (att, None)
+        if attention is not None:
+            attention(q if cls_only else qkv[:, :, :D], qkv[:, :, :D] if cls_only else qkv[:, :, D:2 * D], lse)
         X1 = ops.token_gemm(att.view(-1, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=resid, out=X1)
         y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
         if save and act_d is not None:
@@ -179,14 +183,16 @@ class ViTVAEEncoder(nn.Module):
         return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only, drop)
 
     @torch.no_grad()
-    def _walk(self, x, save=False, keep_stem=False, collect=None):
+    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None):
         """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
         saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
         after every block that ran for all tokens).
         After train_transformer(dropout=True) a save=True walk runs every block in its dropout form: one step of self.dropout_keys per walk, the
         rates read from the block's modules.  save=False never drops.  With device keys (use_device_dropout_keys) the step is one more launch
-        and the sites' keys are views of its table: the same masks, and nothing here reads the counter."""
+        and the sites' keys are views of its table: the same masks, and nothing here reads the counter.
+        attention (a callable; attention_weights / attention_rollout): called as attention(i, q, k, lse) after block i's attention, see _block.
+        None (the default): exactly the launches above."""
         self._check(x)
         drop_step = None
         if save and self._dropout:
@@ -203,7 +209,8 @@ class ViTVAEEncoder(nn.Module):
         steps = []
         for i, blk in enumerate(self.transformer):
             cls_only = self._cls_only_last_block and i == self.depth - 1
-            out, step = self._block(blk, tokens, cls_only, save, _NO_DROP if drop_step is None else self._block_dropout(blk, i, drop_step))
+            out, step = self._block(blk, tokens, cls_only, save, _NO_DROP if drop_step is None else self._block_dropout(blk, i, drop_step),
+                                    None if attention is None else (lambda q, k, lse, i=i: attention(i, q, k, lse)))
             steps.append(step)
             if cls_only:
                 cls = out
@@ -230,6 +237,60 @@ class ViTVAEEncoder(nn.Module):
         c = self.cls_features(x)
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
 
+    # ---- looking inside: attention weights and attention rollout --------------------------------------------------------
+    @torch.no_grad()
+    def attention_weights(self, x, query="cls", average_heads=True, blocks=None):
+        """The attention probabilities of the transformer blocks for the images x, what the reference's nn.MultiheadAttention returns next to its output
+        (vit_backbone.py:43 drops it): fp32 [B, n_blocks, Nq, N], or [B, n_blocks, 8, Nq, N] with average_heads=False; N = num_patches + 1, token 0 is CLS.
+        query="cls": Nq = 1, the CLS row of every block — the model's own form, the last block running for its CLS row alone.  query="all": Nq = N, every
+        row; for this call only the last block runs for all tokens (its CLS row is the same, bit for bit).  blocks: the block indices to return (default: all,
+        in order).  Size: B n_blocks (8) Nq N floats — per head with query="all" at 961 tokens (768 x 1280) that is 29.6 MB per image and block, 3.7 MB
+        averaged; the CLS form is 3.8 KB (30.8 KB per head).
+        Eval mode, no gradient, never drops, either compute dtype; the walk is cls_features' with each block's attention in its lse-saving form (the same
+        values), and one ops.mhsa_weights launch per selected block.  No state of the model changes."""
+        if query not in ("cls", "all"):
+            raise CvaeError(f"ViTVAEEncoder.attention_weights: query must be \"cls\" or \"all\", got {query!r}")
+        idx = list(range(self.depth)) if blocks is None else [int(i) for i in blocks]
+        if not idx or any(not 0 <= i < self.depth for i in idx):
+            raise CvaeError(f"ViTVAEEncoder.attention_weights: blocks must name at least one of the {self.depth} blocks (0 .. {self.depth - 1}), got {blocks!r}")
+        found = {}
+
+        def probe(i, q, k, lse):
+            if i in idx:
+                nq = k.shape[1] if query == "all" else 1
+                found[i] = ops.mhsa_weights(q, k, lse if lse.shape[2] == nq else lse[:, :, :nq].contiguous(), nq, average_heads)
+
+        own, flag = "_cls_only_last_block" in vars(self), self._cls_only_last_block
+        try:
+            if query == "all":
+                self._cls_only_last_block = False
+            self._walk(x, attention=probe)
+        finally:                                                          # the flag as it was, an instance attribute only if it was one
+            if own:
+                self._cls_only_last_block = flag
+            else:
+                vars(self).pop("_cls_only_last_block", None)
+        return torch.stack([found[i] for i in idx], dim=1)
+
+    @torch.no_grad()
+    def attention_rollout(self, x, residual=0.5, as_grid=True):
+        """Attention rollout (Abnar & Zuidema 2020) from the CLS token: the CLS row of prod_l (residual I + (1 - residual) Abar_l), the last block leftmost,
+        Abar_l = block l's head-averaged attention matrix.  Computed as a row vector: r = e_cls, then one ops.mhsa_rollout_step per block from the last to the
+        first; no N x N matrix is formed.  as_grid=True: the patch columns as fp32 [B, grid_h, grid_w] (the CLS column dropped, nothing renormalised: a map sums to
+        1 minus its CLS entry); False: the whole row [B, N], which sums to 1.  residual in [0, 1]; 1 gives e_cls.
+        Eval mode, no gradient, never drops, either compute dtype; the walk is cls_features' with each block's attention in its lse-saving form.  No state of
+        the model changes."""
+        residual = float(residual)
+        if not 0.0 <= residual <= 1.0:
+            raise CvaeError(f"ViTVAEEncoder.attention_rollout: 0 <= residual <= 1 expected, got {residual}")
+        kept = []
+        self._walk(x, attention=lambda i, q, k, lse: kept.append((q, k, lse)))
+        B, N = x.shape[0], self.num_patches + 1
+        r = torch.zeros(B, N, dtype=torch.float32, device=x.device)
+        r[:, 0] = 1.0
+        for q, k, lse in reversed(kept):
+            r = ops.mhsa_rollout_step(q, k, lse, r, lse.shape[2], residual)
+        return r[:, 1:].reshape(B, self.grid_h, self.grid_w) if as_grid else r
 
     # ---- training the conv stem (eval mode: BatchNorm2d on its running statistics; DESIGN §17) -------------------------------------
     _stem_grads = False             # train_stem(): cls_features_with_grad / encode_with_grad accumulate the stem's gradients
@@ -881,3 +942,13 @@ def extract_vit_latents(model, loader, device):
     model.eval()
     zs = [model.encode(batch["x"].to(device))[0] for batch in loader]
     return torch.cat(zs, dim=0).cpu().numpy() if zs else np.zeros((0, model.latent_dim), dtype=np.float32)
+
+
+@torch.no_grad()
+def extract_vit_attention(model, loader, device, residual=0.5):
+    """attention_rollout(batch["x"], residual) of every batch of the loader (extract_vit_latents' protocol), stacked as one numpy array [n, grid_h, grid_w];
+    model: a ViTVAE / ViTVAEEncoder, or a CausalViTVAE (its backbone's map).  The per-batch maps stay on the device; one host copy is made at the end."""
+    model.eval()
+    enc = getattr(model, "backbone", model)
+    maps = [model.attention_rollout(batch["x"].to(device), residual=residual) for batch in loader]
+    return torch.cat(maps, dim=0).cpu().numpy() if maps else np.zeros((0, enc.grid_h, enc.grid_w), dtype=np.float32)

@@ -437,6 +437,34 @@ int cvae_token_gemm_bwd_data_dropout_devkey(const float* g, int64_t g_stride, co
 int cvae_dropout_rows_devkey(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, const uint64_t* key, int64_t mask_row0,
                              int64_t mask_row_step, void* stream);
 
+/* ---- ViT-VAE encoder, attention weights and attention rollout (csrc/vit.hip) ----------------------------------------------------
+ * What nn.MultiheadAttention returns next to its output and vit_backbone.py:43 drops: the attention probabilities, which cvae_mhsa_fwd never writes.
+ * Both entries recompute them from q, k and the row statistic lse that cvae_mhsa_fwd_train leaves (fp32 [B][8][n_query_rows], log2 of the row sum):
+ *   P[b][h][i][j] = 2^(s - lse[b][h][i]),  s = (q_i . k_j) log2(e) / sqrt(32)  over head h's 32 columns — the expression cvae_mhsa_bwd uses; no max or sum pass.
+ * q / k follow cvae_mhsa_fwd: views into the packed in-projection output, row and batch strides in elements, head h in columns 32 h .. 32 h + 31, the
+ * queries are the FIRST n_query_rows tokens; dtype CVAE_F32 (v_mfma_f32_32x32x2_f32) or CVAE_BF16 (bf16 MFMA); everything after the product is fp32.
+ * Contract: enqueue-only; every check precedes the launch; B == 0 is CVAE_OK (nothing is launched); no atomics; every sum in an order that depends on
+ * n_tokens and n_query_rows only (not on B, not on the run): bit-reproducible, and a batch row's bits do not depend on the other rows of the launch.
+ * q, k 16-byte aligned with strides multiples of 16 bytes (else CVAE_E_UNSUPPORTED), strides at least 256 and batch strides non-negative (else
+ * CVAE_E_BADSHAPE), 1 <= n_query_rows <= n_tokens <= 2^24, B <= 65535.
+ *   cvae_mhsa_weights       average_heads = 0: w fp32 [B][8][n_query_rows][n_tokens] = P.  average_heads != 0: w fp32 [B][n_query_rows][n_tokens] =
+ *                           ((((P_0 + P_1) + P_2) + ... ) + P_7) * 0.125f, plain fp32 adds in head order: what nn.MultiheadAttention(need_weights=True)
+ *                           returns in eval mode.  Rows of w are DENSE: n_tokens floats, no padding, so a row start is in general not 16-byte aligned
+ *                           (n_tokens = 961, 7, 65) and the kernel stores 4-byte elements.  Only the base of w (16-byte aligned, else CVAE_E_UNSUPPORTED)
+ *                           and w_batch_stride (in floats, at least one batch's extent, else CVAE_E_BADSHAPE) are constrained.
+ *   cvae_mhsa_rollout_step  one factor of attention rollout (Abnar & Zuidema 2020) applied to a row vector, the N x N matrix never formed:
+ *                             out[b][j] = residual r[b][j] + (1 - residual) 0.125 sum_{h < 8} sum_{i < n_query_rows} r[b][i] P[b][h][i][j]
+ *                           r, out fp32 [B][n_tokens], contiguous.  The double sum is one fp32 chain per key and lane half in the order (64-query tile,
+ *                           head, query), the two halves (queries 8 g + 0..3 and 8 g + 4..7 of every 32) added at the end.  0 <= residual <= 1, else
+ *                           CVAE_E_BADSHAPE; residual = 1 returns r.  out == r (any overlap) is refused: CVAE_E_UNSUPPORTED.  n_query_rows < n_tokens
+ *                           serves the CLS-only last block: only the first rows of the matrix exist; the residual term still covers all n_tokens. */
+int cvae_mhsa_weights(const void* q, const void* k, const float* lse, float* w, int64_t q_stride, int64_t k_stride, int64_t q_batch_stride,
+                      int64_t k_batch_stride, int64_t w_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int average_heads, int dtype,
+                      void* stream);
+int cvae_mhsa_rollout_step(const void* q, const void* k, const float* lse, const float* r, float* out, int64_t q_stride, int64_t k_stride,
+                           int64_t q_batch_stride, int64_t k_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float residual, int dtype,
+                           void* stream);
+
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
  * (no atomics, no split-K): bit-reproducible, and a sample's bits do not depend on the batch it travels in.  Pointers 16-byte aligned, else CVAE_E_UNSUPPORTED;
