@@ -45,6 +45,7 @@ SIGNATURES = {
     "cvae_conv_down": [_p] * 7 + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _p],
     "cvae_conv_up": [_p] * 7 + [_i64] * 9 + [_i, _i, _i, _p, _sz, _i, _i, _i64, _p],
     "cvae_conv_down_bwd_data": [_p] * 4 + [_i64] * 7 + [_i, _i, _i, _p, _sz, _i, _i, _p],
+    "cvae_conv_down_image_bwd_data": [_p, _p, _p] + [_i64] * 6 + [_i, _i, _f, _i, _p],
     "cvae_quantize_fp8": [_p, _i, _p, _i64, _f, _p, _p, _p],
     "cvae_conv_pack_weight_fp8": [_p, _p, _i64, _i64, _i, _i, _f, _p],
     "cvae_conv_up_c1_fp8in": [_p, _p, _p, _p, _f, _i64, _i64, _i64, _i64, _i64, _i, _i, _p],
@@ -154,6 +155,7 @@ SIGNATURES = {
     "cvae_dropout_rows_devkey": [_p, _i64, _p, _i64, _i64, _i64, _f, _p, _i64, _i64, _p],
     "cvae_mhsa_weights": [_p] * 4 + [_i64] * 8 + [_i, _i, _p],
     "cvae_mhsa_rollout_step": [_p] * 5 + [_i64] * 7 + [_f, _i, _p],
+    "cvae_gradcam256": [_p, _p, _p, _i64, _i64, _i, _i, _p],
     "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
     "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],

@@ -949,7 +949,107 @@ __global__ __launch_bounds__(256) void wgrad_c1_finish_kernel(const float* __res
 }
 
 
+// -------------------------------------------------------------------------------------- the image layer's input gradient (2D, fp32 result)
+// dx[b][2 q + p] = alpha sum_{o, c} g[b][q + o][c] w[c][tap(p, o)] for the first conv of an encoder (Cl == 1): up_c1_kernel's thread map — lanes 2k, 2k + 1
+// are the two 16-channel halves of source position q, each neighbour's 16 channels are loaded once (16-byte loads) and feed every output parity that reads
+// it — with an fp32 [B][2 sh][2 sw] result whatever g's dtype, an alpha / accumulate epilogue and no bias, activation or mask.  The weight stays fp32 in both
+// modes (LDS, [tap][cs], wave-uniform broadcasts): a bf16 g is widened exactly, every product and sum is fp32.
+// Order of the sum of one output (geometry only: no dependence on B, the grid or the run): per parity p the neighbours o = (oy, ox) in row-major order,
+// skipping those outside the source; per neighbour a 16-term fma chain over the lane's channels in index order, started at 0, added to the parity's
+// partial; last the two channel halves, own + other (the same bits in both lanes).  Lane hc stores the outputs with px == hc: one owner per element.
+template <typename T>
+__global__ __launch_bounds__(256) void image_bwd_data_kernel(const T* __restrict__ g, const float* __restrict__ w, float* __restrict__ dx, int n, int sh, int sw,
+                                                             float alpha, int accumulate) {
+    constexpr int CS = 32, TAPS = 16;
+    __shared__ __attribute__((aligned(16))) float wl[TAPS * CS];      // [tap][cs]
+    for (int i = threadIdx.x; i < TAPS * CS; i += 256) { const int tap = i / CS, cs = i % CS; wl[i] = w[cs * TAPS + tap]; }
+    __syncthreads();
+    const int gid = blockIdx.x * 256 + threadIdx.x;          // host: 2 n < 2^31
+    const int q = gid >> 1, hc = gid & 1;
+    const bool live = q < n;
+    int rr = live ? q : 0;
+    const int qx = rr % sw; rr /= sw;
+    const int qy = rr % sh;
+    const int b = rr / sh;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    // parity p of position q: l = 2 q + p reads neighbour q + o through tap k (per dimension): o = -1 <- (p 0, k 3); o = 0 <- (p 0, k 1), (p 1, k 2); o = +1 <- (p 1, k 0)
+#pragma unroll
+    for (int oy = -1; oy <= 1; ++oy) {
+        const int y = qy + oy;
+        if (y < 0 || y >= sh) continue;
+#pragma unroll
+        for (int ox = -1; ox <= 1; ++ox) {
+            const int x = qx + ox;
+            if (x < 0 || x >= sw) continue;
+            float sv[16];
+            load_f32<16>(g + (((size_t)b * sh + y) * sw + x) * CS + 16 * hc, sv);
+#pragma unroll
+            for (int cy = 0; cy < 2; ++cy) {
+                const int py = oy == -1 ? 0 : (oy == 1 ? 1 : cy), kh = oy == -1 ? 3 : (oy == 1 ? 0 : (cy == 0 ? 1 : 2));
+                if (oy != 0 && cy == 1) continue;
+#pragma unroll
+                for (int cx = 0; cx < 2; ++cx) {
+                    const int px = ox == -1 ? 0 : (ox == 1 ? 1 : cx), kw = ox == -1 ? 3 : (ox == 1 ? 0 : (cx == 0 ? 1 : 2));
+                    if (ox != 0 && cx == 1) continue;
+                    const float* wr = &wl[(kh * 4 + kw) * CS + 16 * hc];
+                    float a = 0.f;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) a = fmaf(sv[e], wr[e], a);
+                    acc[py * 2 + px] += a;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) acc[p] += __shfl_xor(acc[p], 1, 64);        // the other channel half
+    if (!live) return;
+    const int lw = 2 * sw;
+#pragma unroll
+    for (int py = 0; py < 2; ++py) {
+        const size_t idx = (((size_t)b * 2 * sh + 2 * qy + py) * lw) + 2 * qx + hc;
+        const float s = hc ? acc[py * 2 + 1] : acc[py * 2];
+        dx[idx] = accumulate ? fmaf(alpha, s, dx[idx]) : alpha * s;
+    }
+}
+
 }  // namespace
+
+// do the byte ranges [a, a + na) and [b, b + nb) meet?
+static bool ranges_meet(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// the argument checks of cvae_conv_down_image_bwd_data, in the documented order; CVAE_OK with B == 0 means: nothing to launch
+static int image_bwd_data_check(const void* g, const float* w, const float* dx, int64_t B, int64_t sh, int64_t sw, int64_t Cs, int64_t lh, int64_t lw, int nd, int dtype) {
+    if (B < 0 || sh < 1 || sw < 1 || Cs < 1 || lh < 1 || lw < 1) return CVAE_E_BADSHAPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
+    if (nd != 2 || Cs != 32 || lh != 2 * sh || lw != 2 * sw) return CVAE_E_UNSUPPORTED;
+    // one thread per (source position, channel half): B sh sw < 2^30, tested factor by factor so that no product overflows
+    if (B >= ((int64_t)1 << 31) || sh >= ((int64_t)1 << 30) || sw >= ((int64_t)1 << 30) || sh * sw >= ((int64_t)1 << 30) || B * sh * sw >= ((int64_t)1 << 30)) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!g || !w || !dx) return CVAE_E_NULLPTR;
+    if (!aligned16(g) || ((uintptr_t)w & 3) || ((uintptr_t)dx & 3)) return CVAE_E_UNSUPPORTED;
+    const size_t n = (size_t)(B * sh * sw), g_bytes = n * 32 * (dtype == CVAE_BF16 ? 2 : 4), dx_bytes = n * 4 * sizeof(float);
+    if (ranges_meet(dx, dx_bytes, g, g_bytes) || ranges_meet(dx, dx_bytes, w, 32 * 16 * sizeof(float))) return CVAE_E_UNSUPPORTED;
+    return CVAE_OK;
+}
+
+static int image_bwd_data_launch(const void* g, const float* w, float* dx, int n, int sh, int sw, int dtype, float alpha, int accumulate, hipStream_t stream) {
+    const dim3 grid((unsigned)((2 * (int64_t)n + 255) / 256));
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(image_bwd_data_kernel<T>, grid, dim3(256), 0, stream, (const T*)g, w, dx, n, sh, sw, alpha, accumulate);
+        return launch_rc();
+    });
+}
+
+extern "C" int cvae_conv_down_image_bwd_data(const void* g, const float* w, float* dx, int64_t B, int64_t sh, int64_t sw, int64_t Cs, int64_t lh, int64_t lw, int nd,
+                                             int dtype, float alpha, int accumulate, void* stream) {
+    const int rc = image_bwd_data_check(g, w, dx, B, sh, sw, Cs, lh, lw, nd, dtype);
+    if (rc != CVAE_OK || B == 0) return rc;
+    return image_bwd_data_launch(g, w, dx, (int)(B * sh * sw), (int)sh, (int)sw, dtype, alpha, accumulate != 0, (hipStream_t)stream);
+}
 
 // 1 when the vector-load form can read this image: whole 16-byte vectors per row and a 16-byte aligned base
 static bool image_vec_ok(const void* L, int64_t lw, int l_dtype) {

@@ -523,6 +523,9 @@ template <> struct AttBwdGeom<float> { static constexpr int NP = 40, TP = 0, NS 
 // ------------------------------------------------------------------------------------------------ attention weights and rollout
 #include "vit_attention_probe.inc"
 
+// ------------------------------------------------------------------------------------------------ Grad-CAM on the stem output
+#include "vit_gradcam.inc"
+
 }  // namespace
 
 static bool gemm_shape_ok(int64_t K, int64_t N) { return (K == 256 && (N == 768 || N == 256 || N == 512)) || (K == 512 && N == 256); }
@@ -815,6 +818,34 @@ extern "C" int cvae_mhsa_rollout_step(const void* q, const void* k, const float*
     const AttProbeArgs a = {q, k, q_stride, k_stride, q_batch_stride, k_batch_stride, lse, r, out, 0, (int)n_tokens, (int)n_query_rows,
                             0.17677669529663688110f * 1.44269504088896340736f, residual};
     return mhsa_probe_launch(a, PROBE_ROLLOUT, B, dtype, stream);
+}
+
+// ---- Grad-CAM on the stem output: forward-only, one workgroup per image.  The checks and the launch, as for the two entries above.
+static int gradcam_check(const void* A, const void* dA, const float* cam, int64_t B, int64_t n, int dtype) {
+    if (B < 0 || n < 1) return CVAE_E_BADSHAPE;
+    if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
+    if (n > GRADCAM_MAX_N || B > 0x7fffffff) return CVAE_E_UNSUPPORTED;
+    if (B == 0) return CVAE_OK;
+    if (!A || !dA || !cam) return CVAE_E_NULLPTR;
+    if (!aligned16(A) || !aligned16(dA) || ((uintptr_t)cam & 3)) return CVAE_E_UNSUPPORTED;
+    const size_t in_bytes = (size_t)(B * n) * VIT_DIM * (dtype == CVAE_BF16 ? 2 : 4), out_bytes = (size_t)(B * n) * sizeof(float);
+    const uintptr_t c0 = (uintptr_t)cam, a0 = (uintptr_t)A, d0 = (uintptr_t)dA;
+    if ((c0 < a0 + in_bytes && a0 < c0 + out_bytes) || (c0 < d0 + in_bytes && d0 < c0 + out_bytes)) return CVAE_E_UNSUPPORTED;      // cam inside an input
+    return CVAE_OK;
+}
+
+static int gradcam_launch(const void* A, const void* dA, float* cam, int64_t B, int n, int normalize, int dtype, void* stream) {
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        hipLaunchKernelGGL(vit_gradcam_kernel<T>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const T*)A, (const T*)dA, cam, n, normalize);
+        return launch_rc();
+    });
+}
+
+extern "C" int cvae_gradcam256(const void* A, const void* dA, float* cam, int64_t B, int64_t n, int normalize, int dtype, void* stream) {
+    const int rc = gradcam_check(A, dA, cam, B, n, dtype);
+    if (rc != CVAE_OK || B == 0) return rc;
+    return gradcam_launch(A, dA, cam, B, (int)n, normalize != 0, dtype, stream);
 }
 
 // ---- dropout entries: the training forms above with a Philox mask recomputed in registers.  fp32 only: no dtype code is taken and the float

@@ -510,6 +510,34 @@ def conv_down_bwd_data(g, w_packed_up, gate, gate_act, variant=None):
     return dx
 
 
+def conv_down_image_bwd_data(g, w_folded, alpha=1.0, out=None, accumulate=False):
+    """The gradient with respect to the IMAGE of the first k4/s2/p1 conv of an encoder (cvae_conv_down_image_bwd_data): fp32 [B, 1, 2 sh, 2 sw] =
+    alpha * scatter(g, w), whatever g's dtype.  g channels-last [B, 1, sh, sw, 32] or [B, sh, sw, 32], fp32 or bf16: the gradient of the layer's pre-activation;
+    w_folded: the fp32 k4 weight [32, 1, 4, 4] as fold_bn_conv leaves it (never rounded: all products and sums are fp32).  out: a contiguous fp32
+    [B, 1, 2 sh, 2 sw] tensor to write; with accumulate (needs out) alpha * scatter is ADDED to it (one fma per element), which is how a path integral sums
+    its steps without a [steps, B, H, W] tensor.  Every element has one owner thread and a sum order that depends on the geometry alone."""
+    L.require_gpu(g, w_folded, out)
+    _forward_only("conv_down_image_bwd_data", g, w_folded, out)
+    if (g.dim() not in (4, 5) or (g.dim() == 5 and g.shape[1] != 1) or g.shape[-1] != 32 or not g.is_contiguous() or g.dtype not in (torch.float32, torch.bfloat16)
+            or g.shape[-3] < 1 or g.shape[-2] < 1):
+        raise L.CvaeError(f"conv_down_image_bwd_data: a contiguous channels-last [B, sh, sw, 32] fp32 or bf16 gradient expected, got {tuple(g.shape)} {g.dtype}")
+    if tuple(w_folded.shape) != (32, 1, 4, 4) or w_folded.dtype != torch.float32 or not w_folded.is_contiguous() or w_folded.device != g.device:
+        raise L.CvaeError(f"conv_down_image_bwd_data: the contiguous fp32 k4 weight [32, 1, 4, 4] on {g.device} expected, got {tuple(w_folded.shape)} {w_folded.dtype}")
+    B, sh, sw = g.shape[0], g.shape[-3], g.shape[-2]
+    shape = (B, 1, 2 * sh, 2 * sw)
+    if out is None:
+        if accumulate:
+            raise L.CvaeError("conv_down_image_bwd_data: accumulate adds to `out`, which was not given")
+        out = _empty(shape, torch.float32, g)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != g.device:
+        raise L.CvaeError(f"conv_down_image_bwd_data: out must be a contiguous float32 {shape} tensor on {g.device}, got {tuple(out.shape)} {out.dtype}")
+    if B == 0:
+        return out
+    check(L.timed(f"conv_down_image_bwd_data B{B} S{sh}x{sw}x32", lib.cvae_conv_down_image_bwd_data, ptr(g), ptr(w_folded), ptr(out), B, sh, sw, 32, 2 * sh, 2 * sw, 2,
+                  L.dtype_code(g.dtype), float(alpha), int(bool(accumulate)), stream()), "conv_down_image_bwd_data")
+    return out
+
+
 DEFER_WGRAD = True     # weight gradients of the MFMA conv layers are queued during a backward pass and computed by ONE grouped launch (+ one
                        # reduce launch) at its end (cvae_conv_wgrad_multi): the small layers run in the shadow of the large ones
 _WG_PENDING = []
@@ -1375,7 +1403,11 @@ class _PairLoss(torch.autograd.Function):
             check(lib.cvae_sse_bwd(ptr(a), ptr(b), ptr(g), 1.0, ptr(da), a.numel(), stream()), "sse_bwd")
         else:
             check(lib.cvae_bce_bwd(ptr(a), ptr(b), ptr(g), ptr(da), a.numel(), stream()), "bce_bwd")
-        return da, None, None
+        db = None
+        if ctx.kind == "sse" and ctx.needs_input_grad[1]:      # a target that asks (an image on the graph): the same launch with the operands swapped
+            db = torch.empty_like(b)
+            check(lib.cvae_sse_bwd(ptr(b), ptr(a), ptr(g), 1.0, ptr(db), a.numel(), stream()), "sse_bwd")
+        return da, db, None
 
 
 class Elbo(torch.autograd.Function):
@@ -2286,6 +2318,27 @@ def mhsa_rollout_step(q, k, lse, r, n_query_rows=None, residual=0.5, out=None):
     check(lib.cvae_mhsa_rollout_step(ptr(q), ptr(k), ptr(lse), ptr(r), ptr(out), *strides, B, N, nq, residual, L.dtype_code(q.dtype), stream()),
           "mhsa_rollout_step")
     return out
+
+
+# ---- Grad-CAM on the stem output (csrc/vit_gradcam.inc): forward-only --------------------------------------------------------------------
+def gradcam(A, dA, normalize=True):
+    """Grad-CAM of a channels-last activation and its gradient (cvae_gradcam256): A, dA [B, n, 256] contiguous, fp32 or bf16, the same dtype (the stem output
+    and `dstem`) -> fp32 [B, n]:  w[b, c] = mean_i dA[b, i, c] (rows added in index order), cam[b, i] = max(0, sum_c w[b, c] A[b, i, c]), and with normalize
+    (cam - min_i cam) / (max_i cam - min_i cam + 1e-8) per image — the reference GradCAM's arithmetic without its resize.  One launch, one workgroup per image."""
+    L.require_gpu(A, dA)
+    _forward_only("gradcam", A, dA)
+    if (A.dim() != 3 or A.shape[2] != 256 or A.shape[1] < 1 or A.dtype not in (torch.float32, torch.bfloat16) or not A.is_contiguous()
+            or tuple(dA.shape) != tuple(A.shape) or dA.dtype != A.dtype or not dA.is_contiguous() or dA.device != A.device):
+        raise L.CvaeError(f"gradcam: two contiguous [B, n, 256] tensors of one dtype (fp32 or bf16) expected, got A {tuple(A.shape)} {A.dtype} and dA "
+                          f"{tuple(dA.shape)} {dA.dtype}")
+    B, n = A.shape[0], A.shape[1]
+    if n > 4096:
+        raise L.CvaeError(f"gradcam: at most 4096 positions per image (the map lives in LDS), got A {tuple(A.shape)}")
+    cam = _empty((B, n), torch.float32, A)
+    if B == 0:
+        return cam
+    check(lib.cvae_gradcam256(ptr(A), ptr(dA), ptr(cam), B, n, int(bool(normalize)), L.dtype_code(A.dtype), stream()), "gradcam")
+    return cam
 
 
 def token_gemm_gelu_train(x, weight, bias):

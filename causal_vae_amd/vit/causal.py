@@ -217,6 +217,16 @@ class CausalViTVAE(nn.Module):
         self._require_eval()
         return self.backbone.attention_rollout(x, **kw)
 
+    def saliency(self, x, **kw):
+        """backbone.saliency(x, **kw): which pixels move the backbone's mu / log_var / cls features, fp32 [B, H, W]."""
+        self._require_eval()
+        return self.backbone.saliency(x, **kw)
+
+    def gradcam(self, x, **kw):
+        """backbone.gradcam(x, **kw): Grad-CAM on the backbone's stem output, fp32 [B, grid_h, grid_w]."""
+        self._require_eval()
+        return self.backbone.gradcam(x, **kw)
+
     @torch.no_grad()
     def decode(self, z, m):
         """backbone.decode(dec_adapter(cat[m, z])) -> [B, 1, H, W] (models.py:299-305).  Note the argument order: z first, m second; the concatenation is

@@ -32,6 +32,9 @@ Training, all in eval mode (BatchNorm2d on its running statistics; dropout only 
 stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then per layer cvae_conv_wgrad and cvae_conv_down_bwd_data with the LeakyReLU
 derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
 are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
+The gradient with respect to the IMAGE: cls_features_vjp / encode_vjp (explicit, no graph), x.grad after cls_features_with_grad / encode_with_grad /
+forward_train of an x that asks, saliency (plain and integrated gradients) and gradcam.  They share a data-only form of the backward (_walk_backward(params=False):
+no weight-gradient launch) whose last hop, 32 channels to the one-channel image, is cvae_conv_down_image_bwd_data (fp32 result in both compute dtypes).
 """
 from collections import namedtuple
 
@@ -54,11 +57,12 @@ STEM_CHANNELS = (32, 64, 128, 256, 256)
 # cls_only (everything from the attention's queries on ran for the CLS rows alone: att, X1, y2, pre, hid have B rows, not B N), drop (the block's three dropout
 # sites as the forward ran them, DESIGN §18: ((p, key) or None) for the attention probabilities, the GELU output and the second Linear's output; hid is then
 # the DROPPED GELU output, att the dropped attention's; the masks themselves are not kept, the backward recomputes them).
-# _Walk: steps (the _BlockSteps in forward order), cls (to_latent's input [B, 256]), stem_dtype (the dtype dstem is returned in), B, N, stem (_StemKept or None).
+# _Walk: steps (the _BlockSteps in forward order), cls (to_latent's input [B, 256]), stem_dtype (the dtype dstem is returned in), B, N, stem (_StemKept or None),
+# stem_out (the stem's channels-last output, what Grad-CAM weighs with dstem).
 _StemKept = namedtuple("_StemKept", "x ys k4")
 _BlockStep = namedtuple("_BlockStep", "X y qkv q att lse X1 y2 pre hid B N cls_only drop")
 _NO_DROP = (None, None, None)
-_Walk = namedtuple("_Walk", "steps cls stem_dtype B N stem")
+_Walk = namedtuple("_Walk", "steps cls stem_dtype B N stem stem_out")
 
 
 class _Block(nn.Module):
@@ -183,7 +187,7 @@ class ViTVAEEncoder(nn.Module):
         return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only, drop)
 
     @torch.no_grad()
-    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None):
+    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None, dropout=True):
         """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
         saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
@@ -192,10 +196,12 @@ class ViTVAEEncoder(nn.Module):
         rates read from the block's modules.  save=False never drops.  With device keys (use_device_dropout_keys) the step is one more launch
         and the sites' keys are views of its table: the same masks, and nothing here reads the counter.
         attention (a callable; attention_weights / attention_rollout): called as attention(i, q, k, lse) after block i's attention, see _block.
-        None (the default): exactly the launches above."""
+        None (the default): exactly the launches above.
+        dropout=False (the *_vjp entries and an image that asks for its gradient through frozen parameters): a save=True walk that never drops and
+        draws no step, whatever train_transformer() asked for."""
         self._check(x)
         drop_step = None
-        if save and self._dropout:
+        if save and self._dropout and dropout:
             self._check_dropout_dtype()
             if isinstance(self.dropout_keys, ops.DeviceDropoutKeys):
                 drop_step = self.dropout_keys.advance()                 # this walk's [depth, 4] key table: one launch, the counter moves on the device
@@ -221,7 +227,7 @@ class ViTVAEEncoder(nn.Module):
                 if not cls_only:
                     collect["tokens"].append(tokens.clone())
         out = ops.layernorm256(cls, self.to_latent.weight, self.to_latent.bias, self.to_latent.eps, torch.float32)
-        return out, (_Walk(steps, cls, stem.dtype, tokens.shape[0], tokens.shape[1], _StemKept(**kept) if keep_stem else None) if save else None)
+        return out, (_Walk(steps, cls, stem.dtype, tokens.shape[0], tokens.shape[1], _StemKept(**kept) if keep_stem else None, stem) if save else None)
 
     def cls_features(self, x):
         """to_latent(transformer(tokens)[:, 0]) -> [B, 256] fp32: steps A-D of CausalViTVAE.forward (vessel_analysis/00_core/models.py:262-278)."""
@@ -320,23 +326,30 @@ class ViTVAEEncoder(nn.Module):
         return [p for _k, p in self._stem_named()]
 
     @torch.no_grad()
-    def _stem_backward(self, kept, g, collect=None):
+    def _stem_backward(self, kept, g, collect=None, params=True, image=None):
         """{state_dict name: gradient} of the 20 stem tensors from g = the gradient of the LAST layer's pre-activation [B, n, 256] (vit_tokens_bwd with the stem
         output as its gate), compute dtype.  Per layer, last to first: the folded k4 weight's and bias's gradient from (g_j, the layer's input) at once, then
         g_{j-1} = conv_down_bwd_data(g_j) with leaky001' of the layer's input in the epilogue: no activation-backward launch.  Then ONE launch back through the
-        fold.  The image gets no gradient.  collect: receives `stem_g` = [g_0 .. g_4]."""
+        fold.  collect: receives `stem_g` = [g_0 .. g_4].
+        image (a dict): the result also holds `dx`, the gradient of the image, fp32 [B, 1, H, W]: the last hop is ops.conv_down_image_bwd_data on g_0
+        and the first folded weight, with the dict as its keyword arguments (alpha, out, accumulate; {}: the plain form).  params=False is the data-only form: no _conv_wgrad launch and no fold_bn_conv_bwd, the data launches — hence every g_j and dx,
+        bit for bit — are those of the full form."""
         ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
         g = g.view(ys[-1].shape)
         folded, gs = [None] * len(ys), [None] * len(ys)
         for j in reversed(range(len(ys))):
             gs[j] = g
-            folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
+            if params:
+                folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
             if j:
                 g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), ys[j - 1], "leaky001")
         if collect is not None:
             collect["stem_g"] = gs
-        quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(self._stem_fold_table())])
-        return dict(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
+        grads = {"dx": ops.conv_down_image_bwd_data(g, k4[0], **image)} if image is not None else {}
+        if params:
+            quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(self._stem_fold_table())])
+            grads.update(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
+        return grads
 
     # ---- training the transformer (eval mode; DESIGN §16) -----------------------------------------------------------------------------
     _transformer_grads = False      # train_transformer(): cls_features_with_grad / encode_with_grad accumulate the transformer's gradients
@@ -416,13 +429,15 @@ class ViTVAEEncoder(nn.Module):
         """cls_features(x) (the same launches up to two extra outputs, the same bits) as a differentiable function of the transformer's and the stem's
         parameters: ONE autograd.Function over stem, tokens, blocks and to_latent whose backward accumulates `.grad` on pos_embedding, cls_token, transformer.* and
         to_latent.* (after train_transformer()) and on stem.* (after train_stem(): the five layer outputs are kept; otherwise nothing of the stem is).
-        x gets no gradient.  When autograd is off or no parameter asks, this is cls_features and nothing is saved; a parameter that asks without its train_*()
-        call is an error, not a gradient that silently stays None.
+        An image that asks (x.requires_grad) is on the graph too and backward fills x.grad, fp32 [B, 1, H, W]: with frozen parameters through the
+        data-only backward (no weight-gradient launch; never drops), with live ones through the full backward plus the one image launch.  The forward values are
+        cls_features(x.detach())'s, bit for bit.  When autograd is off or neither a parameter nor x asks, this is cls_features and nothing is saved; a parameter
+        that asks without its train_*() call is an error, not a gradient that silently stays None.
         collect (a dict, for tests): the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype, and with a live stem `stem_g`, the
         gradients of the five pre-activations (`dstem` then costs one more token launch: the stem's backward starts from its gated form)."""
         named, stem = self._transformer_named(heads=False), self._stem_named()
         live_t, live_s = any(p.requires_grad for _k, p in named), any(p.requires_grad for _k, p in stem)
-        if not (torch.is_grad_enabled() and (live_t or live_s)):
+        if not (torch.is_grad_enabled() and (live_t or live_s or x.requires_grad)):
             return self.cls_features(x)
         if live_t and not self._transformer_grads:
             raise CvaeError("ViTVAEEncoder.cls_features_with_grad: transformer parameters ask for a gradient but train_transformer() was not called "
@@ -431,12 +446,138 @@ class ViTVAEEncoder(nn.Module):
             raise CvaeError("ViTVAEEncoder.cls_features_with_grad: stem parameters ask for a gradient but train_stem() was not called (or call freeze_stem())")
         if live_s:
             named = named + stem
+        if not (live_t or live_s):
+            named = []                                                   # only the image asks: no parameter is an input of the node
         return _ClsFeaturesWithGrad.apply(x, self, collect, tuple(k for k, _p in named), *[p for _k, p in named])
 
     def encode_with_grad(self, x, collect=None):
         """encode(x) with gradients: (mu, log_var) from cls_features_with_grad through the differentiable ops.Linear (fc_mu, fc_var)."""
         c = self.cls_features_with_grad(x, collect)
         return ops.Linear.apply(c, self.fc_mu.weight, self.fc_mu.bias, None), ops.Linear.apply(c, self.fc_var.weight, self.fc_var.bias, None)
+
+    # ---- the gradient with respect to the image: vjp entries, saliency, Grad-CAM (DESIGN §21) ------------------------------------------
+    def _cotangent(self, what, name, g, B, width, device):
+        if g is None:
+            return None
+        if not torch.is_tensor(g) or tuple(g.shape) != (B, width) or g.dtype != torch.float32:
+            raise CvaeError(f"ViTVAEEncoder.{what}: {name} must be a float32 [{B}, {width}] cotangent, got "
+                            f"{(tuple(g.shape), g.dtype) if torch.is_tensor(g) else type(g).__name__}")
+        require_gpu(g)
+        return g.detach().contiguous()
+
+    def _heads_vjp(self, c, g_mu, g_log_var):
+        """The cotangent of the cls features c from those of mu and log_var: ops.Linear's own backward (its data launch alone: the weights are handed over
+        detached) on a two-node graph that lives inside this call, the two results added — what autograd does after encode_with_grad, hence the same bits."""
+        with torch.enable_grad():
+            c = c.detach().requires_grad_(True)
+            pairs = [(ops.Linear.apply(c, fc.weight.detach(), fc.bias.detach(), None), g) for fc, g in ((self.fc_mu, g_mu), (self.fc_var, g_log_var)) if g is not None]
+            return torch.autograd.grad([y for y, _g in pairs], [c], [g for _y, g in pairs])[0]
+
+    @torch.no_grad()
+    def _data_backward(self, x, cotangent, image=None, stem=True):
+        """The eval-mode saving walk (never drops, draws no dropout step) and the data-only backward -> (the walk's _Walk, {`dstem`, and with stem `dx`}).
+        cotangent: a callable, cls features [B, 256] -> their fp32 cotangent.  stem=False keeps nothing of the stem and stops at `dstem` (Grad-CAM)."""
+        out, saved = self._walk(x.detach(), save=True, keep_stem=stem, dropout=False)
+        return saved, self._walk_backward(saved, cotangent(out).contiguous(), params=False, image=({} if image is None else image) if stem else None)
+
+    @torch.no_grad()
+    def cls_features_vjp(self, x, g, _image=None):
+        """dx = (d cls_features(x) / d x)^T g, fp32 [B, 1, H, W], for a float32 [B, 256] cotangent g: the explicit form of what backward leaves in x.grad after
+        cls_features_with_grad(x.requires_grad_()) — the same launches, the same bits — and the counterpart of ViTVAE.decode_vjp: no autograd graph, capturable.
+        Eval mode, either compute dtype; never drops and draws no dropout step, also after train_transformer(dropout=True); works on a fully frozen model and
+        issues no weight-gradient launch (the data-only backward); no parameter's .grad and no state of the model changes."""
+        self._check(x)
+        g = self._cotangent("cls_features_vjp", "g", g, x.shape[0], self.embed_dim, x.device)
+        if g is None:
+            raise CvaeError("ViTVAEEncoder.cls_features_vjp: a float32 [B, 256] cotangent is needed, got None")
+        if x.shape[0] == 0:
+            return torch.zeros_like(x)
+        return self._data_backward(x, lambda _c: g, _image)[1]["dx"]
+
+    @torch.no_grad()
+    def encode_vjp(self, x, g_mu=None, g_log_var=None, _image=None):
+        """dx = (d mu / d x)^T g_mu + (d log_var / d x)^T g_log_var, fp32 [B, 1, H, W]; either cotangent (float32 [B, latent_dim]) may be None, not both.
+        cls_features_vjp behind the two output layers' data gradients: what backward leaves in x.grad after encode_with_grad(x.requires_grad_()), bit for bit."""
+        self._check(x)
+        g_mu = self._cotangent("encode_vjp", "g_mu", g_mu, x.shape[0], self.latent_dim, x.device)
+        g_log_var = self._cotangent("encode_vjp", "g_log_var", g_log_var, x.shape[0], self.latent_dim, x.device)
+        if g_mu is None and g_log_var is None:
+            raise CvaeError("ViTVAEEncoder.encode_vjp: at least one of g_mu and g_log_var is needed")
+        if x.shape[0] == 0:
+            return torch.zeros_like(x)
+        return self._data_backward(x, lambda c: self._heads_vjp(c, g_mu, g_log_var), _image)[1]["dx"]
+
+    def _target_cotangent(self, what, B, target, index, device):
+        """(target, the fp32 [B, width] cotangent that selects `index` of it): all ones for None, else ones in the named columns (their sum)."""
+        if target not in ("mu", "log_var", "cls"):
+            raise CvaeError(f"ViTVAEEncoder.{what}: target must be \"mu\", \"log_var\" or \"cls\", got {target!r}")
+        width = self.embed_dim if target == "cls" else self.latent_dim
+        if index is None:
+            return torch.ones(B, width, dtype=torch.float32, device=device)
+        idx = [index] if isinstance(index, (int, np.integer)) and not isinstance(index, bool) else list(index) if isinstance(index, (list, tuple)) else None
+        if not idx or any(not isinstance(i, (int, np.integer)) or isinstance(i, bool) or not 0 <= i < width for i in idx) or len(set(idx)) != len(idx):
+            raise CvaeError(f"ViTVAEEncoder.{what}: index must be None, an int or a list of distinct ints in 0 .. {width - 1} (target {target!r}), got {index!r}")
+        g = torch.zeros(B, width, dtype=torch.float32, device=device)
+        g[:, [int(i) for i in idx]] = 1.0
+        return g
+
+    def _target_vjp(self, x, target, g, image=None):
+        if target == "cls":
+            return self.cls_features_vjp(x, g, image)
+        return self.encode_vjp(x, g, None, image) if target == "mu" else self.encode_vjp(x, None, g, image)
+
+    @torch.no_grad()
+    def saliency(self, x, target="mu", index=None, method="gradient", steps=16, baseline=None, absolute=True):
+        """Which pixels move a latent coordinate: fp32 [B, H, W], the gradient with respect to the image of sum_{k in index} target[:, k]; target "mu",
+        "log_var" or "cls" (the 256 cls features), index None (all coordinates), an int or a list of ints.
+        method="gradient": one encode_vjp / cls_features_vjp with the matching one-hot / all-ones cotangent.
+        method="integrated": integrated gradients by the midpoint rule, (x - baseline) * (1 / steps) sum_{k = 1..steps} grad(baseline + ((k - 1/2) / steps)
+        (x - baseline)); baseline defaults to zeros.  One walk and one data-only backward per step, NOT batched: the steps meet in the image kernel's
+        accumulate epilogue (alpha = 1 / steps; the first step writes, the others add), so no [steps, B, H, W] tensor and no zero fill exists, and memory is
+        that of one vjp.  x == baseline gives exactly zero.
+        absolute=True takes |.| at the end.  Eval mode, no gradient, never drops, either compute dtype; no state of the model changes."""
+        self._check(x)
+        if method not in ("gradient", "integrated"):
+            raise CvaeError(f"ViTVAEEncoder.saliency: method must be \"gradient\" or \"integrated\", got {method!r}")
+        g = self._target_cotangent("saliency", x.shape[0], target, index, x.device)
+        x = x.detach()
+        if method == "gradient":
+            if baseline is not None:
+                raise CvaeError("ViTVAEEncoder.saliency: a baseline belongs to method=\"integrated\"")
+            out = self._target_vjp(x, target, g)
+        else:
+            if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+                raise CvaeError(f"ViTVAEEncoder.saliency: steps must be an int >= 1, got {steps!r}")
+            if baseline is None:
+                baseline = torch.zeros_like(x)
+            elif not torch.is_tensor(baseline) or tuple(baseline.shape) != tuple(x.shape) or baseline.dtype != torch.float32 or baseline.device != x.device:
+                raise CvaeError(f"ViTVAEEncoder.saliency: baseline must be a float32 {tuple(x.shape)} tensor on {x.device}, got "
+                                f"{(tuple(baseline.shape), baseline.dtype, baseline.device) if torch.is_tensor(baseline) else type(baseline).__name__}")
+            if x.shape[0] == 0:
+                return torch.zeros_like(x[:, 0])
+            diff = x - baseline.detach()
+            out = torch.empty_like(x)
+            for k in range(int(steps)):
+                self._target_vjp(torch.add(baseline, diff, alpha=(k + 0.5) / int(steps)), target, g,
+                                 {"alpha": 1.0 / int(steps), "out": out, "accumulate": k > 0})
+            out = out * diff
+        out = out[:, 0]
+        return out.abs() if absolute else out
+
+    @torch.no_grad()
+    def gradcam(self, x, target="mu", index=None, normalize=True):
+        """Grad-CAM on the stem's output, the last conv activation: fp32 [B, grid_h, grid_w], one value per patch.  The data-only backward of
+        sum_{k in index} target[:, k] (target and index as in saliency) down to `dstem` — nothing of the stem is kept or walked back — then ops.gradcam on the
+        stem output and `dstem`: the channel weights are dstem's means over the patches, the map is relu of the weighted channel sum, and with normalize it
+        is scaled to [0, 1] per image as the reference's GradCAM does.  Eval mode, no gradient, never drops, either compute dtype; no state changes."""
+        self._check(x)
+        g = self._target_cotangent("gradcam", x.shape[0], target, index, x.device)
+        B = x.shape[0]
+        if B == 0:
+            return torch.zeros(0, self.grid_h, self.grid_w, dtype=torch.float32, device=x.device)
+        cot = (lambda _c: g) if target == "cls" else (lambda c: self._heads_vjp(c, g if target == "mu" else None, g if target == "log_var" else None))
+        saved, grads = self._data_backward(x, cot, stem=False)
+        return ops.gradcam(saved.stem_out.view(B, self.num_patches, self.embed_dim), grads["dstem"], normalize).view(B, self.grid_h, self.grid_w)
 
     def _cls_rows_step(self, s):
         """The record a CLS-only block would have kept, cut from a full block's _BlockStep (the last block of a walk with _cls_only_last_block False): k / v
@@ -450,33 +591,41 @@ class ViTVAEEncoder(nn.Module):
 
     def _block_backward(self, blk, name, s, G, grads):
         """One block's backward from its _BlockStep s: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in
-        place where it can be; returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names."""
+        place where it can be; returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names.
+        grads None is the data-only form: no token_gemm_wgrad launch; LayerNorm's parameter sums leave the launch that computes its dx and are
+        dropped.  The data launches, and so the returned gradient's bits, are the same in both forms."""
         B, N, D, dt, a = s.B, s.N, self.embed_dim, self.compute_dtype, blk.attn
+        wgrad, grads = grads is not None, ({} if grads is None else grads)
         att_d, act_d, out_d = s.drop                                    # the forward's dropout sites: the masks are recomputed from (p, key), DESIGN §18
         rows = (0, N) if s.cls_only else (0, 1)
         Gm = G if out_d is None else ops.dropout_rows(G, out_d + rows)  # the MLP branch's cotangent; the skip carries G itself
         dpre = ops.token_gemm_bwd_data(Gm, blk.mlp[3].weight, dt, gate_pre=s.pre, dropout=None if act_d is None else act_d + rows)
-        grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(Gm, s.hid)
+        if wgrad:
+            grads[name + "mlp.3.weight"], grads[name + "mlp.3.bias"] = ops.token_gemm_wgrad(Gm, s.hid)
         dy2 = ops.token_gemm_bwd_data(dpre, blk.mlp[0].weight, dt)
-        grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s.y2)
+        if wgrad:
+            grads[name + "mlp.0.weight"], grads[name + "mlp.0.bias"] = ops.token_gemm_wgrad(dpre, s.y2)
         _dx, grads[name + "norm2.weight"], grads[name + "norm2.bias"] = ops.layernorm256_bwd(dy2, s.X1, blk.norm2.weight, blk.norm2.eps, dx=G, accumulate=True)
         datt = ops.token_gemm_bwd_data(G, a.out_proj.weight, dt)
-        grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s.att.view(-1, D))
+        if wgrad:
+            grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s.att.view(-1, D))
         qkv, y = s.qkv, s.y
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)       # dense, also where qkv is a column panel (_cls_rows_step)
         if not s.cls_only:
             ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.att, s.lse, datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:],
                          dropout=att_d)
             dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 3 * D), a.in_proj_weight, dt)
-            grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = ops.token_gemm_wgrad(dqkv.view(B * N, 3 * D), y)
+            if wgrad:
+                grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = ops.token_gemm_wgrad(dqkv.view(B * N, 3 * D), y)
             _dx, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s.X, blk.norm1.weight, blk.norm1.eps, dx=G, accumulate=True)
             return G
         dq = torch.empty(s.q.shape, dtype=s.q.dtype, device=s.q.device)
         ops.mhsa_bwd(s.q, qkv[:, :, :D], qkv[:, :, D:], s.att, s.lse, datt.view(B, 1, D), dq, dqkv[:, :, :D], dqkv[:, :, D:], dropout=att_d)
-        dW, db = torch.empty_like(a.in_proj_weight), torch.empty_like(a.in_proj_bias)
-        ops.token_gemm_wgrad(dq.view(B, D), y.view(B, N, D)[:, 0], dW[:D], db[:D])
-        ops.token_gemm_wgrad(dqkv.view(B * N, 2 * D), y, dW[D:], db[D:])
-        grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = dW, db
+        if wgrad:
+            dW, db = torch.empty_like(a.in_proj_weight), torch.empty_like(a.in_proj_bias)
+            ops.token_gemm_wgrad(dq.view(B, D), y.view(B, N, D)[:, 0], dW[:D], db[:D])
+            ops.token_gemm_wgrad(dqkv.view(B * N, 2 * D), y, dW[D:], db[D:])
+            grads[name + "attn.in_proj_weight"], grads[name + "attn.in_proj_bias"] = dW, db
         dy = ops.token_gemm_bwd_data(dqkv.view(B * N, 2 * D), a.in_proj_weight[D:], dt, out_dtype=torch.float32)
         ops.token_gemm_bwd_data(dq.view(B, D), a.in_proj_weight[:D], dt, resid=dy.view(B, N, D)[:, 0])       # the one q row joins the kv rows' gradient, in place
         Gin, grads[name + "norm1.weight"], grads[name + "norm1.bias"] = ops.layernorm256_bwd(dy, s.X, blk.norm1.weight, blk.norm1.eps)
@@ -484,36 +633,43 @@ class ViTVAEEncoder(nn.Module):
         return Gin
 
     @torch.no_grad()
-    def _walk_backward(self, saved, g, collect=None):
+    def _walk_backward(self, saved, g, collect=None, params=True, stem_params=None, image=None):
         """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features;
-        when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`)."""
-        steps, cls, stem_dtype, B, N, kept = saved
+        when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`).
+        DESIGN §21: params=False is the data-only form — every block in its data-only form, no parameter's gradient in the result, the same `dstem`.
+        stem_params (default: whether the walk kept the stem) says the same for the stem's 20 tensors; image (a dict, needs a walk that kept the stem): the
+        result also holds `dx`, see _stem_backward."""
+        steps, cls, stem_dtype, B, N, kept = saved[:6]
         D, grads = self.embed_dim, {}
+        stem_params = bool(params) and ((kept is not None) if stem_params is None else bool(stem_params))
         # to_latent reads the CLS rows alone, so the last block's cotangent is its [B, 256] CLS rows whichever form its forward ran: the backward of a full
         # last block is the CLS-only block's, on the CLS rows of what it kept (_cls_rows_step) — the same launches, hence the same bits, in both forms
         G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
         for i in reversed(range(self.depth)):
             s = steps[i] if (steps[i].cls_only or i < self.depth - 1) else self._cls_rows_step(steps[i])
-            G = self._block_backward(self.transformer[i], f"transformer.{i}.", s, G, grads)
-        if kept is None:
+            G = self._block_backward(self.transformer[i], f"transformer.{i}.", s, G, grads if params else None)
+        if kept is None or not (stem_params or image is not None):
             dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
         else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
             if collect is not None:
                 grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)[2]
             dpos, dcls, g_last = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype, gate=kept.ys[-1].view(B, N - 1, D), gate_act="leaky001")
-            grads.update(self._stem_backward(kept, g_last, collect))
+            grads.update(self._stem_backward(kept, g_last, collect, stem_params, image))
         grads["pos_embedding"], grads["cls_token"] = dpos.view(1, N, D), dcls.view(1, 1, D)
-        return grads
+        return grads if params else {k: grads[k] for k in ("dstem", "dx") if k in grads}
 
 
 class _ClsFeaturesWithGrad(torch.autograd.Function):
     """ViTVAEEncoder.cls_features_with_grad: the transformer's parameters (and, after train_stem(), the stem's behind them) are inputs, so autograd accumulates
-    their gradients, zero_grad works and a parameter rewritten between forward and backward is an error.  x gets no gradient."""
+    their gradients, zero_grad works and a parameter rewritten between forward and backward is an error.  An x that asks for its gradient gets it:
+    the stem's gates travel along, the walk reads the detached image (the same launches as for an x that does not ask), and with no parameter among the
+    inputs the backward is the data-only one."""
 
     @staticmethod
     def forward(ctx, x, model, collect, names, *params):
-        out, saved = model._walk(x, save=True, keep_stem=any(k.startswith("stem.") for k in names))
-        ctx.model, ctx.saved, ctx.collect, ctx.names = model, saved, collect, names      # activations of this call: private to the node, freed with it
+        stem_live, wants_x = any(k.startswith("stem.") for k in names), ctx.needs_input_grad[0]
+        out, saved = model._walk(x.detach() if wants_x else x, save=True, keep_stem=stem_live or wants_x, dropout=bool(params))
+        ctx.model, ctx.saved, ctx.collect, ctx.names, ctx.stem_live = model, saved, collect, names, stem_live      # activations of this call: private to the node, freed with it
         ctx.save_for_backward(*params)
         ctx.set_materialize_grads(False)
         return out
@@ -524,10 +680,11 @@ class _ClsFeaturesWithGrad(torch.autograd.Function):
         params = ctx.saved_tensors                                     # raises if a parameter was modified in place since the forward
         if g is None:
             return (None,) * (4 + len(params))
-        grads = ctx.model._walk_backward(ctx.saved, g.contiguous(), ctx.collect)
+        grads = ctx.model._walk_backward(ctx.saved, g.contiguous(), ctx.collect, params=bool(params), stem_params=ctx.stem_live,
+                                         image={} if ctx.needs_input_grad[0] else None)
         if ctx.collect is not None:
             ctx.collect["dstem"] = grads["dstem"]
-        return (None, None, None, None) + tuple(grads[k].view(p.shape) if need else None for k, p, need in zip(ctx.names, params, ctx.needs_input_grad[4:]))
+        return (grads.get("dx"), None, None, None) + tuple(grads[k].view(p.shape) if need else None for k, p, need in zip(ctx.names, params, ctx.needs_input_grad[4:]))
 
 
 class _ResBlock(nn.Module):
@@ -952,3 +1109,13 @@ def extract_vit_attention(model, loader, device, residual=0.5):
     enc = getattr(model, "backbone", model)
     maps = [model.attention_rollout(batch["x"].to(device), residual=residual) for batch in loader]
     return torch.cat(maps, dim=0).cpu().numpy() if maps else np.zeros((0, enc.grid_h, enc.grid_w), dtype=np.float32)
+
+
+@torch.no_grad()
+def extract_vit_saliency(model, loader, device, **kw):
+    """saliency(batch["x"], **kw) of every batch of the loader (extract_vit_latents' protocol), stacked as one numpy array [n, H, W]; model: a ViTVAE /
+    ViTVAEEncoder, or a CausalViTVAE (its backbone's map).  The per-batch maps stay on the device; one host copy is made at the end."""
+    model.eval()
+    enc = getattr(model, "backbone", model)
+    maps = [model.saliency(batch["x"].to(device), **kw) for batch in loader]
+    return torch.cat(maps, dim=0).cpu().numpy() if maps else np.zeros((0, enc.img_height, enc.img_width), dtype=np.float32)

@@ -139,6 +139,20 @@ int cvae_conv_down_image(const void* L, int l_dtype, const float* w, const float
                          int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, int act, void* stream);
 int cvae_conv_wgrad_image(const void* S, const void* L, int l_dtype, float* dW, float* dbias, void* workspace, size_t workspace_bytes,
                           int64_t B, int64_t sd, int64_t sh, int64_t sw, int64_t Cs, int64_t ld, int64_t lh, int64_t lw, int nd, int dtype, void* stream);
+/* The input gradient of that first conv: the gradient with respect to the IMAGE, as an fp32 result whatever the operand dtype (csrc/conv_c1.hip).
+ *   g   channels-last [B][sh][sw][32], `dtype` CVAE_F32 or CVAE_BF16: the gradient of the layer's pre-activation;
+ *   w   the fp32 k4 weight [32][1][4][4] as cvae_fold_bn_conv leaves it.  It is NOT rounded in bf16 mode: a bf16 g is widened exactly and every product and
+ *       sum is fp32, so the result's error is fp32 rounding alone in both modes;
+ *   dx  fp32 [B][1][2 sh][2 sw]:  s[b][y][x] = sum_{c, ky, kx} g[b][sy][sx][c] w[c][0][ky][kx] over the positions with 2 sy - 1 + ky = y and 2 sx - 1 + kx = x
+ *       (at most 2 x 2 source positions x 32 channels);  accumulate == 0: dx = alpha * s;  accumulate != 0: dx = fma(alpha, s, dx).
+ * Every element of dx is written by exactly one thread: no atomics, no workspace.  The order of an element's sum depends on (sh, sw) and its position only — per
+ * neighbouring source position (row-major) a 16-term fma chain per channel half started at 0, added to the element's partial, the two halves added last — so the
+ * result is bit-reproducible and a batch row's bits do not depend on B.
+ * Any sh, sw >= 1 (no tile multiple is asked for).  Every check precedes the launch: negative B or a size < 1: CVAE_E_BADSHAPE; a dtype code other than the two:
+ * CVAE_E_DTYPE; nd != 2, Cs != 32, (lh, lw) != (2 sh, 2 sw) or B sh sw >= 2^30: CVAE_E_UNSUPPORTED; then B == 0 is CVAE_OK (nothing is launched); a null pointer:
+ * CVAE_E_NULLPTR; g not 16-byte aligned, w or dx not 4-byte aligned, or dx overlapping g or w: CVAE_E_UNSUPPORTED. */
+int cvae_conv_down_image_bwd_data(const void* g, const float* w, float* dx, int64_t B, int64_t sh, int64_t sw, int64_t Cs, int64_t lh, int64_t lw, int nd, int dtype,
+                                  float alpha, int accumulate, void* stream);
 /* ---- fp8 (OCP e4m3) products (BASELINE.json configs[4]): the batched counterfactual decode (replaces the per-value decode loop of
  * vessel_analysis/04_generate_counterfactual/generate_counterfactual.py:77-99) and the forward convolutions of the train step
  * (causal_cascade/train.py:19-39 with fp8 conv inputs; the backward pass stays bf16) ----
@@ -464,6 +478,18 @@ int cvae_mhsa_weights(const void* q, const void* k, const float* lse, float* w, 
 int cvae_mhsa_rollout_step(const void* q, const void* k, const float* lse, const float* r, float* out, int64_t q_stride, int64_t k_stride,
                            int64_t q_batch_stride, int64_t k_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float residual, int dtype,
                            void* stream);
+
+/* ---- ViT-VAE encoder, Grad-CAM on the stem output (csrc/vit_gradcam.inc) ---------------------------------------------------------
+ * The arithmetic of the reference's GradCAM.__call__ (mnist_test/02_mechanism_analysis/analyze_gradcam.py:56-73) without its resize, on the channels-last stem
+ * output A and its gradient dA, both [B][n][256] contiguous in `dtype` (CVAE_F32 or CVAE_BF16); cam fp32 [B][n]:
+ *   w[b][c]   = (((dA[b][0][c] + dA[b][1][c]) + ...) + dA[b][n-1][c]) * (1.0f / n)          one fp32 chain per channel, rows in index order
+ *   m[b][i]   = max(0, sum_c w[b][c] A[b][i][c])        per 4 consecutive channels an fma chain started at 0 (64 of them per row), then the xor-shuffle sum
+ *                                                       of the 64 partials (lane offsets 32, 16, 8, 4, 2, 1)
+ *   cam[b][i] = normalize != 0 ? (m[b][i] - min_i m[b]) / (max_i m[b] - min_i m[b] + 1e-8f) : m[b][i]
+ * One launch, one workgroup per image, no workspace, no atomics; an image's bits do not depend on B or on the run.  1 <= n <= 4096 (the map of an image lives in
+ * LDS; the encoder has n <= 961), else CVAE_E_BADSHAPE (n < 1, B < 0) / CVAE_E_UNSUPPORTED (n > 4096); a dtype code other than the two: CVAE_E_DTYPE; then
+ * B == 0 is CVAE_OK; a null pointer: CVAE_E_NULLPTR; A or dA not 16-byte aligned, cam not 4-byte aligned or cam overlapping an input: CVAE_E_UNSUPPORTED. */
+int cvae_gradcam256(const void* A, const void* dA, float* cam, int64_t B, int64_t n, int normalize, int dtype, void* stream);
 
 /* ---- ViT-VAE decoder, eval mode (csrc/conv_s1.hip; vessel_analysis/00_core/vit_backbone.py:7-19, 115-156, 186-193) -------------------------------------
  * Stride-1 window convolutions on channels-last [B][H][W][C] tensors, dtype CVAE_F32 (exact fp32 MFMA) or CVAE_BF16; fp32 accumulation in a fixed order
