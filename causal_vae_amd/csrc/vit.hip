@@ -556,22 +556,81 @@ extern "C" int cvae_layernorm256(const float* x, int64_t x_stride, const float* 
     });
 }
 
+// ---- what a launch that drops carries.  The dropout entries are the entries around them with a Philox mask recomputed in registers: fp32 only (no
+// dtype code is taken, the float instances are launched directly), and p = 0 gives the bits of the entry without dropout.
+
+static bool drop_args(float p, uint64_t key, DropArgs* d) {
+    if (!(p >= 0.f && p < 1.f)) return false;
+    d->thr = (uint32_t)((double)p * 16777216.0);
+    d->k0 = (uint32_t)key;
+    d->k1 = (uint32_t)(key >> 32);
+    d->scale = 1.0f / (1.0f - p);
+    return true;
+}
+
+// The key of a dropout entry: a value (the entries of DESIGN §18), or an 8-byte-aligned device pointer that the kernels read when they run (the *_devkey
+// entries of DESIGN §19: a captured graph replays with whatever the pointer holds then).
+struct DropKey {
+    uint64_t value;
+    const uint64_t* dev;
+    bool on_device;
+    bool missing() const { return on_device && !dev; }
+    bool misaligned() const { return on_device && ((uintptr_t)dev & 7); }
+    const uint32_t* words() const { return on_device ? (const uint32_t*)dev : nullptr; }
+};
+static DropKey key_value(uint64_t key) { return {key, nullptr, false}; }
+static DropKey key_device(const uint64_t* key) { return {0, key, true}; }
+
+// logical rows R = row0 + m step of a row site: with m < 2^30 they stay far below 2^63
+static bool mask_rows_ok(int64_t row0, int64_t step) { return row0 >= 0 && row0 <= ((int64_t)1 << 40) && step >= 1 && step <= ((int64_t)1 << 30); }
+
+// One dropout site as the host bodies below take it, by pointer: null = the launch does not drop.  An attention site has no mask rows (0, 1).
+struct Drop {
+    DropArgs d;
+    DropKey key;
+    int64_t row0, row_step;
+    bool ok;                                                // the rate and the mask rows are in range
+};
+static Drop drop_site(float p, DropKey key, int64_t row0 = 0, int64_t row_step = 1) {
+    Drop s = {{}, key, row0, row_step, false};
+    s.ok = drop_args(p, key.value, &s.d) && mask_rows_ok(row0, row_step);
+    return s;
+}
+static bool drop_bad(const Drop* s) { return s && !s->ok; }                           // CVAE_E_BADSHAPE
+static bool key_missing(const Drop* s) { return s && s->key.missing(); }              // CVAE_E_NULLPTR
+static bool key_misaligned(const Drop* s) { return s && s->key.misaligned(); }        // CVAE_E_UNSUPPORTED
+
+// ---- the token GEMM, forward: cvae_token_gemm, cvae_token_gemm_gelu_train and cvae_token_gemm_dropout[_devkey] (drop: fp32, epilogue RESID or GELU_SAVE)
 static int token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y, int64_t y_stride,
-                      int64_t M, int64_t K, int64_t N, int epilogue, int max_epilogue, int dtype, void* pre, int64_t pre_stride, void* stream) {
-    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N) return CVAE_E_BADSHAPE;
+                      int64_t M, int64_t K, int64_t N, int epilogue, int max_epilogue, int dtype, void* pre, int64_t pre_stride, const Drop* drop, void* stream) {
+    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N || drop_bad(drop)) return CVAE_E_BADSHAPE;
     if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
     if (epilogue < GEMM_EPI_NONE || epilogue > max_epilogue) return CVAE_E_BADSHAPE;
     if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!x || !W || !bias || !y) return CVAE_E_NULLPTR;
-    if (epilogue == CVAE_GEMM_EPI_RESIDUAL && (!resid || resid_stride < N || (resid_stride & 3) || !aligned16(resid))) return resid ? CVAE_E_BADSHAPE : CVAE_E_NULLPTR;
+    if (!x || !W || !bias || !y || key_missing(drop)) return CVAE_E_NULLPTR;
+    if (epilogue == CVAE_GEMM_EPI_RESIDUAL) {
+        if (!resid) return CVAE_E_NULLPTR;
+        if (resid_stride < N) return CVAE_E_BADSHAPE;
+        if ((resid_stride & 3) || !aligned16(resid)) return drop ? CVAE_E_UNSUPPORTED : CVAE_E_BADSHAPE;      // the code each family has always answered
+    }
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4, ye16 = (epilogue == CVAE_GEMM_EPI_RESIDUAL || dtype == CVAE_F32) ? 4 : 8;
-    if ((x_stride % e16) || (y_stride % ye16) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y)) return CVAE_E_UNSUPPORTED;
+    if ((x_stride % e16) || (y_stride % ye16) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y) || key_misaligned(drop)) return CVAE_E_UNSUPPORTED;
     if (epilogue == GEMM_EPI_GELU_SAVE) {
         if (!pre) return CVAE_E_NULLPTR;
         if (pre_stride < N) return CVAE_E_BADSHAPE;
         if ((pre_stride % e16) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
+    if (drop) {                                             // the operand its epilogue does not read is passed as null
+        const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(N / GEMM_BN));
+        auto launch = [&](auto kernel, const float* r, int64_t ldr, float* p, int64_t ldp) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const float*)x, x_stride, W, bias, r, ldr, y, y_stride, M, (int)K, (int)N, p, ldp, drop->d, drop->row0,
+                               drop->row_step, drop->key.words());
+            return launch_rc();
+        };
+        if (epilogue == GEMM_EPI_RESID) return launch(vit_gemm_dropout_kernel<float, GEMM_EPI_RESID>, resid, resid_stride, nullptr, 0);
+        return launch(vit_gemm_dropout_kernel<float, GEMM_EPI_GELU_SAVE>, nullptr, 0, (float*)pre, pre_stride);
+    }
     return with_dtype(dtype, [&](auto tv) {
         return gemm_launch((const decltype(tv)*)x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, (int)K, (int)N, epilogue, pre, pre_stride, st);
     });
@@ -579,49 +638,85 @@ static int token_gemm(const void* x, int64_t x_stride, const float* W, const flo
 
 extern "C" int cvae_token_gemm(const void* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, void* y,
                                int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, int dtype, void* stream) {
-    return token_gemm(x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, K, N, epilogue, CVAE_GEMM_EPI_RESIDUAL, dtype, nullptr, 0, stream);
+    return token_gemm(x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, K, N, epilogue, CVAE_GEMM_EPI_RESIDUAL, dtype, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int cvae_token_gemm_gelu_train(const void* x, int64_t x_stride, const float* W, const float* bias, void* pre, int64_t pre_stride, void* y, int64_t y_stride,
                                           int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
-    return token_gemm(x, x_stride, W, bias, nullptr, 0, y, y_stride, M, K, N, GEMM_EPI_GELU_SAVE, GEMM_EPI_GELU_SAVE, dtype, pre, pre_stride, stream);
+    return token_gemm(x, x_stride, W, bias, nullptr, 0, y, y_stride, M, K, N, GEMM_EPI_GELU_SAVE, GEMM_EPI_GELU_SAVE, dtype, pre, pre_stride, nullptr, stream);
 }
 
+// the dropout entries' epilogue: CVAE_GEMM_EPI_GELU means GELU with the pre-activation saved; anything but it and RESIDUAL is out of range
+static int drop_epilogue(int epilogue) {
+    return epilogue == CVAE_GEMM_EPI_GELU ? GEMM_EPI_GELU_SAVE : (epilogue == CVAE_GEMM_EPI_RESIDUAL ? GEMM_EPI_RESID : -1);
+}
+
+extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
+                                       int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key,
+                                       int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    const Drop s = drop_site(p, key_value(key), mask_row0, mask_row_step);
+    return token_gemm(x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, K, N, drop_epilogue(epilogue), GEMM_EPI_GELU_SAVE, CVAE_F32, pre, pre_stride, &s, stream);
+}
+
+extern "C" int cvae_token_gemm_dropout_devkey(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride,
+                                              float* pre, int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p,
+                                              const uint64_t* key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    const Drop s = drop_site(p, key_device(key), mask_row0, mask_row_step);
+    return token_gemm(x, x_stride, W, bias, resid, resid_stride, y, y_stride, M, K, N, drop_epilogue(epilogue), GEMM_EPI_GELU_SAVE, CVAE_F32, pre, pre_stride, &s, stream);
+}
+
+// ---- fused attention, forward: cvae_mhsa_fwd, cvae_mhsa_fwd_train (lse) and cvae_mhsa_fwd_train_dropout[_devkey] (lse and drop: fp32)
 static int mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
-                    int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, float* lse, void* stream) {
-    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+                    int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, float* lse, const Drop* drop,
+                    void* stream) {
+    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens || drop_bad(drop)) return CVAE_E_BADSHAPE;
     if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
-    if (!q || !k || !v || !out) return CVAE_E_NULLPTR;
+    if (!q || !k || !v || !out || (drop && !lse) || key_missing(drop)) return CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
     if (q_stride < VIT_DIM || k_stride < VIT_DIM || v_stride < VIT_DIM || q_batch_stride < 0 || k_batch_stride < 0 || v_batch_stride < 0) return CVAE_E_BADSHAPE;
     if ((q_stride % e16) || (k_stride % e16) || (v_stride % e16) || (q_batch_stride % e16) || (k_batch_stride % e16) || (v_batch_stride % e16) || !aligned16(q) ||
-        !aligned16(k) || !aligned16(v) || !aligned16(out))
+        !aligned16(k) || !aligned16(v) || !aligned16(out) || (drop && !aligned16(lse)) || key_misaligned(drop))      // lse: judged by the dropout entries alone
         return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
     const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // 1 / sqrt(32) * log2(e)
     hipStream_t st = (hipStream_t)stream;
-    return with_dtype(dtype, [&](auto tv) { return with_bool(lse != nullptr, [&](auto train) {
+    auto launch = [&](auto tv, auto kernel, auto... more) {    // more: the row statistics a training kernel saves, then the mask of one that drops
         using T = decltype(tv);
-        auto launch = [&](auto kernel, auto... saved) {       // the training kernel takes the row statistics it saves as one more argument
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride,
-                               v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, saved...);
-        };
-        if constexpr (decltype(train)::value) launch(vit_attention_train_kernel<T>, lse);
-        else launch(vit_attention_kernel<T>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride,
+                           v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, more...);
         return launch_rc();
-    }); });
+    };
+    if (drop) return launch(float{}, vit_attention_dropout_kernel<float>, lse, drop->d, drop->key.words());
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        return lse ? launch(tv, vit_attention_train_kernel<T>, lse) : launch(tv, vit_attention_kernel<T>);
+    });
 }
 
 extern "C" int cvae_mhsa_fwd(const void* q, const void* k, const void* v, void* out, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride,
                              int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream) {
-    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, nullptr, stream);
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, nullptr, nullptr, stream);
 }
 
 extern "C" int cvae_mhsa_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                    int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype,
                                    void* stream) {
     if (!lse) return CVAE_E_NULLPTR;
-    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, lse, stream);
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, lse, nullptr, stream);
+}
+
+extern "C" int cvae_mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                           int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                                           float p, uint64_t key, void* stream) {
+    const Drop s = drop_site(p, key_value(key));
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, CVAE_F32, lse, &s, stream);
+}
+
+extern "C" int cvae_mhsa_fwd_train_dropout_devkey(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride,
+                                                  int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens,
+                                                  int64_t n_query_rows, float p, const uint64_t* key, void* stream) {
+    const Drop s = drop_site(p, key_device(key));
+    return mhsa_fwd(q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, CVAE_F32, lse, &s, stream);
 }
 
 // ---- backward entries.  Every argument check precedes the first launch; workspaces are the caller's.
@@ -669,21 +764,28 @@ extern "C" int cvae_layernorm256_bwd(const void* g, int64_t g_stride, int g_dtyp
     return CVAE_OK;
 }
 
-extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
-                                        int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
-    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K) return CVAE_E_BADSHAPE;
+// cvae_token_gemm_bwd_data and cvae_token_gemm_bwd_data_dropout[_devkey] (drop: fp32 throughout, no resid)
+static int token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
+                               int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, const Drop* drop,
+                               void* stream) {
+    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K || drop_bad(drop)) return CVAE_E_BADSHAPE;
     if (!dtype_ok(dtype) || !dtype_ok(g_dtype) || !dtype_ok(dx_dtype)) return CVAE_E_DTYPE;
     if (dtype == CVAE_F32 && (g_dtype != CVAE_F32 || dx_dtype != CVAE_F32)) return CVAE_E_DTYPE;
     if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!g || !W || !dx) return CVAE_E_NULLPTR;
+    if (!g || !W || !dx || key_missing(drop)) return CVAE_E_NULLPTR;
     if (resid && (dx_dtype != CVAE_F32 || resid_stride < K || (resid_stride & 3))) return CVAE_E_BADSHAPE;
     if (pre && pre_stride < K) return CVAE_E_BADSHAPE;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
     if ((g_stride % (g_dtype == CVAE_BF16 ? 8 : 4)) || (dx_stride % (dx_dtype == CVAE_BF16 ? 8 : 4)) || (pre && (pre_stride % e16)) || !aligned16(g) || !aligned16(W) ||
-        !aligned16(dx) || !aligned16(pre) || !aligned16(resid))
+        !aligned16(dx) || !aligned16(pre) || !aligned16(resid) || key_misaligned(drop))
         return CVAE_E_UNSUPPORTED;
     const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
     hipStream_t st = (hipStream_t)stream;
+    if (drop) {
+        hipLaunchKernelGGL((vit_gemm_bwd_data_dropout_kernel<float, float, float>), grid, dim3(256), 0, st, (const float*)g, g_stride, W, (const float*)pre, pre_stride, resid,
+                           resid_stride, (float*)dx, dx_stride, M, (int)K, (int)N, drop->d, drop->row0, drop->row_step, drop->key.words());
+        return launch_rc();
+    }
     return with_dtype(dtype, [&](auto tv) { return with_dtype2(g_dtype, dx_dtype, [&](auto tg, auto to) {
         using T = decltype(tv);
         using TG = std::conditional_t<std::is_same_v<T, float>, float, decltype(tg)>;      // an fp32 product has fp32 ends (checked above): no mixed instance of it
@@ -692,6 +794,24 @@ extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_d
                            dx_stride, M, (int)K, (int)N);
         return launch_rc();
     }); });
+}
+
+extern "C" int cvae_token_gemm_bwd_data(const void* g, int64_t g_stride, int g_dtype, const float* W, const void* pre, int64_t pre_stride, const float* resid,
+                                        int64_t resid_stride, void* dx, int64_t dx_stride, int dx_dtype, int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
+    return token_gemm_bwd_data(g, g_stride, g_dtype, W, pre, pre_stride, resid, resid_stride, dx, dx_stride, dx_dtype, M, K, N, dtype, nullptr, stream);
+}
+
+extern "C" int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
+                                                int64_t M, int64_t K, int64_t N, float p, uint64_t key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
+    const Drop s = drop_site(p, key_value(key), mask_row0, mask_row_step);
+    return token_gemm_bwd_data(g, g_stride, CVAE_F32, W, pre, pre_stride, nullptr, 0, dx, dx_stride, CVAE_F32, M, K, N, CVAE_F32, &s, stream);
+}
+
+extern "C" int cvae_token_gemm_bwd_data_dropout_devkey(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx,
+                                                       int64_t dx_stride, int64_t M, int64_t K, int64_t N, float p, const uint64_t* key, int64_t mask_row0,
+                                                       int64_t mask_row_step, void* stream) {
+    const Drop s = drop_site(p, key_device(key), mask_row0, mask_row_step);
+    return token_gemm_bwd_data(g, g_stride, CVAE_F32, W, pre, pre_stride, nullptr, 0, dx, dx_stride, CVAE_F32, M, K, N, CVAE_F32, &s, stream);
 }
 
 extern "C" size_t cvae_token_gemm_wgrad_workspace_bytes(int64_t M, int64_t K, int64_t N) {
@@ -729,13 +849,14 @@ extern "C" size_t cvae_mhsa_bwd_workspace_bytes(int64_t B, int64_t n_query_rows)
     return (B < 1 || n_query_rows < 1) ? 0 : (size_t)(B * VIT_HEADS * n_query_rows) * sizeof(float);
 }
 
-extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* dout, void* dq, void* dk, void* dv,
-                             int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
-                             int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
-                             int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+// cvae_mhsa_bwd and cvae_mhsa_bwd_dropout[_devkey] (drop: fp32)
+static int mhsa_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* dout, void* dq, void* dk, void* dv, int64_t q_stride,
+                    int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride,
+                    int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                    int dtype, const Drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens || drop_bad(drop)) return CVAE_E_BADSHAPE;
     if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
-    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !workspace) return CVAE_E_NULLPTR;
+    if (!q || !k || !v || !out || !lse || !dout || !dq || !dk || !dv || !workspace || key_missing(drop)) return CVAE_E_NULLPTR;
     const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
     const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
                                  dq_batch_stride, dk_batch_stride, dv_batch_stride};
@@ -744,6 +865,7 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
     for (int i = 0; i < 12; ++i)
         if (strides[i] % e16) return CVAE_E_UNSUPPORTED;
     if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv)) return CVAE_E_UNSUPPORTED;
+    if (drop && (!aligned16(lse) || !aligned16(workspace) || key_misaligned(drop))) return CVAE_E_UNSUPPORTED;      // lse, workspace: judged by the dropout entries alone
     if (workspace_bytes < cvae_mhsa_bwd_workspace_bytes(B, n_query_rows)) return CVAE_E_WORKSPACE;
     const int N = (int)n_tokens, Nq = (int)n_query_rows;
     const int64_t ob = (int64_t)Nq * VIT_DIM;
@@ -754,6 +876,12 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
                            dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
     const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
+    if (drop) {
+        hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, false>), gq, dim3(256), 0, st, aq, drop->d, drop->key.words());
+        CVAE_CHECK_LAUNCH();
+        hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, true>), gk, dim3(256), 0, st, ak, drop->d, drop->key.words());
+        return launch_rc();
+    }
     return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         hipLaunchKernelGGL((vit_attention_bwd_kernel<T, false>), gq, dim3(256), 0, st, aq);
@@ -761,6 +889,34 @@ extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const 
         hipLaunchKernelGGL((vit_attention_bwd_kernel<T, true>), gk, dim3(256), 0, st, ak);
         return launch_rc();
     });
+}
+
+extern "C" int cvae_mhsa_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse, const void* dout, void* dq, void* dk, void* dv,
+                             int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
+                             int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
+                             int64_t B, int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    return mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride, dv_stride,
+                    dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, dtype, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
+                                     float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                                     int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride,
+                                     int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    const Drop s = drop_site(p, key_value(key));
+    return mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride, dv_stride,
+                    dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, CVAE_F32, &s, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cvae_mhsa_bwd_dropout_devkey(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
+                                            float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
+                                            int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride,
+                                            int64_t dk_batch_stride, int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
+                                            const uint64_t* key, void* workspace, size_t workspace_bytes, void* stream) {
+    const Drop s = drop_site(p, key_device(key));
+    return mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride, dv_stride,
+                    dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, CVAE_F32, &s, workspace, workspace_bytes, stream);
 }
 
 // ---- attention weights and attention rollout: forward-only views inside the encoder, recomputed from q, k and cvae_mhsa_fwd_train's lse.
@@ -848,33 +1004,7 @@ extern "C" int cvae_gradcam256(const void* A, const void* dA, float* cam, int64_
     return gradcam_launch(A, dA, cam, B, (int)n, normalize != 0, dtype, stream);
 }
 
-// ---- dropout entries: the training forms above with a Philox mask recomputed in registers.  fp32 only: no dtype code is taken and the float
-// instances are launched directly.  Every argument check precedes the first launch; p = 0 gives the bits of the entry without dropout.
-
-static bool drop_args(float p, uint64_t key, DropArgs* d) {
-    if (!(p >= 0.f && p < 1.f)) return false;
-    d->thr = (uint32_t)((double)p * 16777216.0);
-    d->k0 = (uint32_t)key;
-    d->k1 = (uint32_t)(key >> 32);
-    d->scale = 1.0f / (1.0f - p);
-    return true;
-}
-
-// The key of a dropout entry: a value (the entries of DESIGN §18), or an 8-byte-aligned device pointer that the kernels read when they run (the *_devkey
-// entries of DESIGN §19: a captured graph replays with whatever the pointer holds then).
-struct DropKey {
-    uint64_t value;
-    const uint64_t* dev;
-    bool on_device;
-    bool missing() const { return on_device && !dev; }
-    bool misaligned() const { return on_device && ((uintptr_t)dev & 7); }
-    const uint32_t* words() const { return on_device ? (const uint32_t*)dev : nullptr; }
-};
-static DropKey key_value(uint64_t key) { return {key, nullptr, false}; }
-static DropKey key_device(const uint64_t* key) { return {0, key, true}; }
-
-// logical rows R = row0 + m step of a row site: with m < 2^30 they stay far below 2^63
-static bool mask_rows_ok(int64_t row0, int64_t step) { return row0 >= 0 && row0 <= ((int64_t)1 << 40) && step >= 1 && step <= ((int64_t)1 << 30); }
+// ---- dropout on rows: the one dropout entry that is no form of another.  Every argument check precedes the launch.
 
 static int dropout_rows(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, DropKey key, int64_t mask_row0,
                         int64_t mask_row_step, void* stream) {
@@ -898,167 +1028,6 @@ extern "C" int cvae_dropout_rows(const float* x, int64_t x_stride, float* y, int
 extern "C" int cvae_dropout_rows_devkey(const float* x, int64_t x_stride, float* y, int64_t y_stride, int64_t M, int64_t N, float p, const uint64_t* key,
                                         int64_t mask_row0, int64_t mask_row_step, void* stream) {
     return dropout_rows(x, x_stride, y, y_stride, M, N, p, key_device(key), mask_row0, mask_row_step, stream);
-}
-
-static int token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
-                              int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, DropKey key,
-                              int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    DropArgs d;
-    if (M < 1 || M > ((int64_t)1 << 30) || x_stride < K || y_stride < N || !drop_args(p, key.value, &d) || !mask_rows_ok(mask_row0, mask_row_step))
-        return CVAE_E_BADSHAPE;
-    if (epilogue != CVAE_GEMM_EPI_GELU && epilogue != CVAE_GEMM_EPI_RESIDUAL) return CVAE_E_BADSHAPE;
-    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!x || !W || !bias || !y || key.missing()) return CVAE_E_NULLPTR;
-    if ((x_stride & 3) || (y_stride & 3) || !aligned16(x) || !aligned16(W) || !aligned16(bias) || !aligned16(y) || key.misaligned()) return CVAE_E_UNSUPPORTED;
-    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(N / GEMM_BN));
-    hipStream_t st = (hipStream_t)stream;
-    if (epilogue == CVAE_GEMM_EPI_RESIDUAL) {
-        if (!resid) return CVAE_E_NULLPTR;
-        if (resid_stride < N) return CVAE_E_BADSHAPE;
-        if ((resid_stride & 3) || !aligned16(resid)) return CVAE_E_UNSUPPORTED;
-        hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_RESID>), grid, dim3(256), 0, st, x, x_stride, W, bias, resid, resid_stride, (void*)y, y_stride, M,
-                           (int)K, (int)N, (float*)nullptr, (int64_t)0, d, mask_row0, mask_row_step, key.words());
-        return launch_rc();
-    }
-    if (!pre) return CVAE_E_NULLPTR;
-    if (pre_stride < N) return CVAE_E_BADSHAPE;
-    if ((pre_stride & 3) || !aligned16(pre)) return CVAE_E_UNSUPPORTED;
-    hipLaunchKernelGGL((vit_gemm_dropout_kernel<float, GEMM_EPI_GELU_SAVE>), grid, dim3(256), 0, st, x, x_stride, W, bias, (const float*)nullptr, (int64_t)0, (void*)y,
-                       y_stride, M, (int)K, (int)N, pre, pre_stride, d, mask_row0, mask_row_step, key.words());
-    return launch_rc();
-}
-
-extern "C" int cvae_token_gemm_dropout(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride, float* pre,
-                                       int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p, uint64_t key,
-                                       int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    return token_gemm_dropout(x, x_stride, W, bias, resid, resid_stride, pre, pre_stride, y, y_stride, M, K, N, epilogue, p, key_value(key), mask_row0,
-                              mask_row_step, stream);
-}
-
-extern "C" int cvae_token_gemm_dropout_devkey(const float* x, int64_t x_stride, const float* W, const float* bias, const float* resid, int64_t resid_stride,
-                                              float* pre, int64_t pre_stride, float* y, int64_t y_stride, int64_t M, int64_t K, int64_t N, int epilogue, float p,
-                                              const uint64_t* key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    return token_gemm_dropout(x, x_stride, W, bias, resid, resid_stride, pre, pre_stride, y, y_stride, M, K, N, epilogue, p, key_device(key), mask_row0,
-                              mask_row_step, stream);
-}
-
-static int token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
-                                       int64_t M, int64_t K, int64_t N, float p, DropKey key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    DropArgs d;
-    if (M < 1 || M > ((int64_t)1 << 30) || g_stride < N || dx_stride < K || (pre && pre_stride < K) || !drop_args(p, key.value, &d) ||
-        !mask_rows_ok(mask_row0, mask_row_step))
-        return CVAE_E_BADSHAPE;
-    if (!gemm_shape_ok(K, N)) return CVAE_E_UNSUPPORTED;
-    if (!g || !W || !dx || key.missing()) return CVAE_E_NULLPTR;
-    if ((g_stride & 3) || (dx_stride & 3) || (pre && (pre_stride & 3)) || !aligned16(g) || !aligned16(W) || !aligned16(dx) || !aligned16(pre) || key.misaligned())
-        return CVAE_E_UNSUPPORTED;
-    const dim3 grid((unsigned)((M + GEMM_BM - 1) / GEMM_BM), (unsigned)(K / GEMM_BN));
-    hipLaunchKernelGGL((vit_gemm_bwd_data_dropout_kernel<float, float, float>), grid, dim3(256), 0, (hipStream_t)stream, g, g_stride, W, pre, pre_stride,
-                       (const float*)nullptr, (int64_t)0, dx, dx_stride, M, (int)K, (int)N, d, mask_row0, mask_row_step, key.words());
-    return launch_rc();
-}
-
-extern "C" int cvae_token_gemm_bwd_data_dropout(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx, int64_t dx_stride,
-                                                int64_t M, int64_t K, int64_t N, float p, uint64_t key, int64_t mask_row0, int64_t mask_row_step, void* stream) {
-    return token_gemm_bwd_data_dropout(g, g_stride, W, pre, pre_stride, dx, dx_stride, M, K, N, p, key_value(key), mask_row0, mask_row_step, stream);
-}
-
-extern "C" int cvae_token_gemm_bwd_data_dropout_devkey(const float* g, int64_t g_stride, const float* W, const float* pre, int64_t pre_stride, float* dx,
-                                                       int64_t dx_stride, int64_t M, int64_t K, int64_t N, float p, const uint64_t* key, int64_t mask_row0,
-                                                       int64_t mask_row_step, void* stream) {
-    return token_gemm_bwd_data_dropout(g, g_stride, W, pre, pre_stride, dx, dx_stride, M, K, N, p, key_device(key), mask_row0, mask_row_step, stream);
-}
-
-// the stride and pointer checks the two attention entries share: `strides` = the n row strides, then the n batch strides
-static int mhsa_dropout_check(int64_t B, int64_t n_tokens, int64_t n_query_rows, const int64_t* strides, int n, const void* const* ptrs, int np, DropKey key) {
-    if (B < 1 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
-    for (int i = 0; i < np; ++i)
-        if (!ptrs[i]) return CVAE_E_NULLPTR;
-    if (key.missing()) return CVAE_E_NULLPTR;
-    for (int i = 0; i < 2 * n; ++i)
-        if (strides[i] < (i < n ? VIT_DIM : 0)) return CVAE_E_BADSHAPE;
-    for (int i = 0; i < 2 * n; ++i)
-        if (strides[i] & 3) return CVAE_E_UNSUPPORTED;
-    for (int i = 0; i < np; ++i)
-        if (!aligned16(ptrs[i])) return CVAE_E_UNSUPPORTED;
-    return key.misaligned() ? CVAE_E_UNSUPPORTED : CVAE_OK;
-}
-
-static int mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                                  int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
-                                  DropKey key, void* stream) {
-    DropArgs d;
-    if (!drop_args(p, key.value, &d)) return CVAE_E_BADSHAPE;
-    const int64_t strides[6] = {q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride};
-    const void* const ptrs[5] = {q, k, v, out, lse};
-    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 3, ptrs, 5, key);
-    if (rc != CVAE_OK) return rc;
-    const dim3 grid((unsigned)((n_query_rows + 127) / 128), VIT_HEADS, (unsigned)B);
-    const float scale_log2e = 0.17677669529663688110f * 1.44269504088896340736f;       // as cvae_mhsa_fwd_train
-    hipLaunchKernelGGL(vit_attention_dropout_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, q, k, v, out, q_stride, k_stride, v_stride, q_batch_stride,
-                       k_batch_stride, v_batch_stride, (int)n_tokens, (int)n_query_rows, scale_log2e, lse, d, key.words());
-    return launch_rc();
-}
-
-extern "C" int cvae_mhsa_fwd_train_dropout(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                                           int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
-                                           float p, uint64_t key, void* stream) {
-    return mhsa_fwd_train_dropout(q, k, v, out, lse, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, p,
-                                  key_value(key), stream);
-}
-
-extern "C" int cvae_mhsa_fwd_train_dropout_devkey(const float* q, const float* k, const float* v, float* out, float* lse, int64_t q_stride, int64_t k_stride,
-                                                  int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens,
-                                                  int64_t n_query_rows, float p, const uint64_t* key, void* stream) {
-    return mhsa_fwd_train_dropout(q, k, v, out, lse, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, B, n_tokens, n_query_rows, p,
-                                  key_device(key), stream);
-}
-
-static int mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv,
-                            int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride,
-                            int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride, int64_t dv_batch_stride,
-                            int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, DropKey key, void* workspace, size_t workspace_bytes, void* stream) {
-    DropArgs d;
-    if (!drop_args(p, key.value, &d)) return CVAE_E_BADSHAPE;
-    const int64_t strides[12] = {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride, q_batch_stride, k_batch_stride, v_batch_stride,
-                                 dq_batch_stride, dk_batch_stride, dv_batch_stride};
-    const void* const ptrs[10] = {q, k, v, out, lse, dout, dq, dk, dv, workspace};
-    const int rc = mhsa_dropout_check(B, n_tokens, n_query_rows, strides, 6, ptrs, 10, key);
-    if (rc != CVAE_OK) return rc;
-    if (workspace_bytes < cvae_mhsa_bwd_workspace_bytes(B, n_query_rows)) return CVAE_E_WORKSPACE;
-    const int N = (int)n_tokens, Nq = (int)n_query_rows;
-    const int64_t ob = (int64_t)Nq * VIT_DIM;
-    const float scale = 0.17677669529663688110f, scale_log2e = scale * 1.44269504088896340736f;
-    const AttBwdArgs aq = {q, dout, k, v, out, q_stride, VIT_DIM, k_stride, v_stride, q_batch_stride, ob, k_batch_stride, v_batch_stride, lse, (float*)workspace,
-                           dq, nullptr, dq_stride, 0, dq_batch_stride, 0, Nq, N, Nq, scale_log2e, scale};
-    const AttBwdArgs ak = {k, v, q, dout, out, k_stride, v_stride, q_stride, VIT_DIM, k_batch_stride, v_batch_stride, q_batch_stride, ob, lse, (float*)workspace,
-                           dk, dv, dk_stride, dv_stride, dk_batch_stride, dv_batch_stride, N, Nq, Nq, scale_log2e, scale};
-    const dim3 gq((unsigned)((Nq + 127) / 128), VIT_HEADS, (unsigned)B), gk((unsigned)((N + 127) / 128), VIT_HEADS, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, false>), gq, dim3(256), 0, st, aq, d, key.words());
-    CVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL((vit_attention_bwd_dropout_kernel<float, true>), gk, dim3(256), 0, st, ak, d, key.words());
-    return launch_rc();
-}
-
-extern "C" int cvae_mhsa_bwd_dropout(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
-                                     float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
-                                     int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride, int64_t dk_batch_stride,
-                                     int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p, uint64_t key, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    return mhsa_bwd_dropout(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride,
-                            dv_stride, dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, p, key_value(key), workspace, workspace_bytes,
-                            stream);
-}
-
-extern "C" int cvae_mhsa_bwd_dropout_devkey(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* dout, float* dq, float* dk,
-                                            float* dv, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride,
-                                            int64_t v_batch_stride, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride, int64_t dq_batch_stride,
-                                            int64_t dk_batch_stride, int64_t dv_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float p,
-                                            const uint64_t* key, void* workspace, size_t workspace_bytes, void* stream) {
-    return mhsa_bwd_dropout(q, k, v, out, lse, dout, dq, dk, dv, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, dq_stride, dk_stride,
-                            dv_stride, dq_batch_stride, dk_batch_stride, dv_batch_stride, B, n_tokens, n_query_rows, p, key_device(key), workspace, workspace_bytes,
-                            stream);
 }
 
 // ---- device-resident keys: the keys of one step's sites, derived on the device from a counter that the same launch advances ----------------

@@ -2038,36 +2038,52 @@ def layernorm256(x, weight, bias, eps, out_dtype):
     return y
 
 
-def _token_gemm(what, x, weight, bias, epilogue, resid, out, want_pre):
-    """The one body of token_gemm and token_gemm_gelu_train (`what`: the caller's name, for the error text) -> (result, pre-activation or None)."""
+def _token_gemm(what, x, weight, bias, epilogue, resid, out, want_pre, dropout=None):
+    """The one body of token_gemm, token_gemm_gelu_train and token_gemm_dropout (`what`: the caller's name, for the error text) -> (result, pre-activation or
+    None).  dropout: None, or the row site (p, key) / (p, key, row0, row_step) of cvae_token_gemm_dropout[_devkey]: fp32 only, epilogue "gelu" (the
+    pre-activation is always saved, resid and out are not taken) or "residual"."""
     L.require_gpu(x, weight, bias, resid, out)
     _forward_only(what, x, weight, bias, resid)
     _rows2d(x, what)
     M, K = x.shape
     N = weight.shape[0]
-    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in GEMM_EPI:
-        raise L.CvaeError(f"{what}: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r}")
+    epilogues = GEMM_EPI if dropout is None else ("gelu", "residual")
+    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in epilogues:
+        raise L.CvaeError(f"{what}: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r}" + (" ('gelu' or 'residual')" if dropout is not None else ""))
+    site = None if dropout is None else _dropout_site(what, dropout, True, x)
     if epilogue == "residual":
-        if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm resid", N).shape[0] != M:
-            raise L.CvaeError("token_gemm: the residual epilogue needs a fp32 [M, N] residual")
+        if resid is None or resid.dtype != torch.float32 or _rows2d(resid, f"{what} resid", N).shape[0] != M:
+            raise L.CvaeError(f"{what}: the residual epilogue needs a fp32 [M, N] residual")
         out = resid if out is None else out
+    elif site is not None and (resid is not None or out is not None):
+        raise L.CvaeError(f"{what}: resid and out belong to the residual epilogue")
     elif out is None:
         out = _empty((M, N), x.dtype, x)
-    _rows2d(out, "token_gemm out", N)                     # resid and out come from token_gemm alone: the training form passes neither
+    _rows2d(out, f"{what} out", N)                        # resid and out come from token_gemm[_dropout] alone: the training form passes neither
+    if site is not None and (out.shape[0] != M or out.dtype != torch.float32):
+        raise L.CvaeError(f"{what}: out {tuple(out.shape)} {out.dtype}")
     w, b, dt = weight.detach().contiguous(), bias.detach(), L.dtype_code(x.dtype)
+    resid_stride = resid.stride(0) if resid is not None else 0
+    if site is not None:
+        sfx, p, key, row0, step = site
+        pre = _empty((M, N), x.dtype, x) if epilogue == "gelu" else None
+        check(getattr(lib, "cvae_token_gemm_dropout" + sfx)(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(resid), resid_stride, ptr(pre), N if pre is not None else 0, ptr(out),
+                                                            out.stride(0), M, K, N, GEMM_EPI[epilogue], p, key, row0, step, stream()), "token_gemm_dropout" + sfx)
+        return out, pre
     if not want_pre:
-        check(lib.cvae_token_gemm(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), M, K, N,
-                                  GEMM_EPI[epilogue], dt, stream()), "token_gemm")
+        check(lib.cvae_token_gemm(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(resid), resid_stride, ptr(out), out.stride(0), M, K, N, GEMM_EPI[epilogue], dt, stream()),
+              "token_gemm")
         return out, None
     pre = _empty((M, N), x.dtype, x)
     check(lib.cvae_token_gemm_gelu_train(ptr(x), x.stride(0), ptr(w), ptr(b), ptr(pre), N, ptr(out), out.stride(0), M, K, N, dt, stream()), "token_gemm_gelu_train")
     return out, pre
 
 
-def token_gemm(x, weight, bias, epilogue=None, resid=None, out=None):
+def token_gemm(x, weight, bias, epilogue=None, resid=None, out=None, dropout=None):
     """epi(x @ weight.T + bias) (cvae_token_gemm).  x [M, K] fp32 or bf16 (the arithmetic mode), weight [N, K] / bias [N] the fp32 nn.Linear tensors.
-    epilogue None / "gelu": result in x's dtype; "residual": fp32 resid + (x W^T + b), written to `out` (default: resid itself, in place)."""
-    return _token_gemm("token_gemm", x, weight, bias, epilogue, resid, out, False)[0]
+    epilogue None / "gelu": result in x's dtype; "residual": fp32 resid + (x W^T + b), written to `out` (default: resid itself, in place).
+    dropout = (p, key) or (p, key, row0, row_step): token_gemm_dropout's result (its first member with "gelu"); None: exactly the path above."""
+    return _token_gemm("token_gemm", x, weight, bias, epilogue, resid, out, False, dropout)[0]
 
 
 def _mhsa_views(what, B, rows, *ts):
@@ -2108,19 +2124,19 @@ def mhsa(q, k, v, n_query_rows=None):
     return _mhsa_fwd("mhsa", q, k, v, n_query_rows, False)[0]
 
 
-# ---- ViT-VAE encoder, training the transformer (csrc/vit.hip): the backward building blocks, on raw tensors as the ones above ---------
-def _overlap(a, b):
-    """do two [B, tokens, 256] views with unit column stride share an element?  Panels of one packed buffer interleave: same storage, the same row and batch
-    strides and column ranges that meet; anything else is compared by its address range."""
-    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
-        return False
-    if a.stride() == b.stride() and a.stride(1) >= 256:
-        off = (b.storage_offset() - a.storage_offset()) % a.stride(1)
-        if min(off, a.stride(1) - off) >= 256:
-            return False                                                    # disjoint column panels of the same rows
-    span = lambda t: (t.storage_offset(), t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride())))
-    (a0, a1), (b0, b1) = span(a), span(b)
-    return a0 <= b1 and b0 <= a1
+# ---- ViT-VAE encoder, the training forms of the two fused building blocks: the same values, plus what the backward needs --------------------------------
+def token_gemm_gelu_train(x, weight, bias, dropout=None):
+    """(gelu(x W^T + b), x W^T + b), both in x's dtype: token_gemm's "gelu" output, bit for bit, and the pre-activation (cvae_token_gemm_gelu_train).
+    dropout = (p, key) or (p, key, row0, row_step), fp32 only: the first member is dropped with the row-site mask (cvae_token_gemm_dropout); None: exactly
+    the path above."""
+    return _token_gemm("token_gemm_gelu_train", x, weight, bias, "gelu", None, None, True, dropout)
+
+
+def mhsa_train(q, k, v, n_query_rows=None, dropout=None):
+    """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train).
+    dropout = (p, key), fp32 only: the probabilities are dropped with the attention-site mask of include/cvae_hip.h before the P V product
+    (cvae_mhsa_fwd_train_dropout); lse stays that of the undropped rows.  None: exactly the path above."""
+    return _mhsa_fwd("mhsa_train", q, k, v, n_query_rows, True, dropout)
 
 
 # ---- dropout when training the transformer (DESIGN §18): masks are recomputed in the kernels from (p, key); the host only hands the keys out ---------
@@ -2225,11 +2241,45 @@ def _dropout_site(what, dropout, rows, *tensors):
     return (suffix, p, key, row0, step) if rows else (suffix, p, key)
 
 
-def mhsa_train(q, k, v, n_query_rows=None, dropout=None):
-    """mhsa (the same output, bit for bit) that also returns lse fp32 [B, 8, n_query_rows], the row statistic mhsa_bwd needs (cvae_mhsa_fwd_train).
-    dropout = (p, key), fp32 only: the probabilities are dropped with the attention-site mask of include/cvae_hip.h before the P V product
-    (cvae_mhsa_fwd_train_dropout); lse stays that of the undropped rows.  None: exactly the path above."""
-    return _mhsa_fwd("mhsa_train", q, k, v, n_query_rows, True, dropout)
+def token_gemm_dropout(x, weight, bias, epilogue, dropout, resid=None, out=None):
+    """token_gemm on fp32 x with a row-site dropout mask over the output (cvae_token_gemm_dropout).  dropout = (p, key) or (p, key, row0, row_step).
+    epilogue "gelu" -> (gelu(pre) keep s, pre): token_gemm_gelu_train's pair with the first member dropped; "residual" -> resid + (x W^T + b) keep s,
+    written to `out` (default: resid itself, in place).  p = 0 gives the bits of token_gemm_gelu_train / token_gemm."""
+    if not isinstance(dropout, (tuple, list)):
+        raise L.CvaeError(f"token_gemm_dropout: dropout must be (p, key) or (p, key, row0, row_step), got {dropout!r}")
+    res = _token_gemm("token_gemm_dropout", x, weight, bias, epilogue, resid, out, False, dropout)
+    return res if epilogue == "gelu" else res[0]
+
+
+def dropout_rows(x, dropout, out=None):
+    """x keep s on fp32 [M, N] rows (any row stride, N % 4 == 0) with the row-site mask (cvae_dropout_rows).  dropout = (p, key) or (p, key, row0, row_step);
+    out: where to write (may be x itself; default a new tensor).  On ones it is the mask."""
+    L.require_gpu(x, out)
+    _forward_only("dropout_rows", x)
+    _rows2d(x, "dropout_rows")
+    sfx, p, key, row0, step = _dropout_site("dropout_rows", dropout, True, x, out)
+    M, N = x.shape
+    if out is None:
+        out = _empty((M, N), torch.float32, x)
+    if _rows2d(out, "dropout_rows out", N).shape[0] != M:
+        raise L.CvaeError(f"dropout_rows: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    check(getattr(lib, "cvae_dropout_rows" + sfx)(ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, p, key, row0, step, stream()), "dropout_rows" + sfx)
+    return out
+
+
+# ---- ViT-VAE encoder, training the transformer (csrc/vit.hip, DESIGN §16): the backward building blocks, on raw tensors as the ones above ---------
+def _overlap(a, b):
+    """do two [B, tokens, 256] views with unit column stride share an element?  Panels of one packed buffer interleave: same storage, the same row and batch
+    strides and column ranges that meet; anything else is compared by its address range."""
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+    if a.stride() == b.stride() and a.stride(1) >= 256:
+        off = (b.storage_offset() - a.storage_offset()) % a.stride(1)
+        if min(off, a.stride(1) - off) >= 256:
+            return False                                                    # disjoint column panels of the same rows
+    span = lambda t: (t.storage_offset(), t.storage_offset() + sum((n - 1) * st for n, st in zip(t.shape, t.stride())))
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 <= b1 and b0 <= a1
 
 
 def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, dropout=None):
@@ -2248,16 +2298,120 @@ def mhsa_bwd(q, k, v, out, lse, dout, dq, dk, dv, dropout=None):
     if any(_overlap(a, b) for i, a in enumerate(outs) for b in outs[i + 1:] + (q, k, v, out, dout)):
         raise L.CvaeError("mhsa_bwd: dq, dk and dv must not overlap each other or an operand")
     _t, wp, wb = _scratch(lib.cvae_mhsa_bwd_workspace_bytes(B, nq), q)
+    head = (ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1), q.stride(0), k.stride(0),
+            v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0), B, N, nq)
     if dropout is not None:
         sfx, p, key = _dropout_site("mhsa_bwd", dropout, False, q)
-        check(getattr(lib, "cvae_mhsa_bwd_dropout" + sfx)(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1),
-                                                          v.stride(1), q.stride(0), k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0),
-                                                          dk.stride(0), dv.stride(0), B, N, nq, p, key, wp, wb, stream()), "mhsa_bwd_dropout" + sfx)
-        return dq, dk, dv
-    check(lib.cvae_mhsa_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(dout), ptr(dq), ptr(dk), ptr(dv), q.stride(1), k.stride(1), v.stride(1), q.stride(0),
-                            k.stride(0), v.stride(0), dq.stride(1), dk.stride(1), dv.stride(1), dq.stride(0), dk.stride(0), dv.stride(0), B, N, nq,
-                            L.dtype_code(q.dtype), wp, wb, stream()), "mhsa_bwd")
+        check(getattr(lib, "cvae_mhsa_bwd_dropout" + sfx)(*head, p, key, wp, wb, stream()), "mhsa_bwd_dropout" + sfx)
+    else:
+        check(lib.cvae_mhsa_bwd(*head, L.dtype_code(q.dtype), wp, wb, stream()), "mhsa_bwd")
     return dq, dk, dv
+
+
+def _gemm_mode(what, g, mode):
+    """The arithmetic mode of a backward GEMM: fp32 mode takes fp32 cotangents only; bf16 mode takes bf16 ones or the fp32 stream gradient."""
+    if mode not in (torch.float32, torch.bfloat16) or g.dtype not in (torch.float32, mode):
+        raise L.CvaeError(f"{what}: a {g.dtype} cotangent in {mode} arithmetic")
+
+
+def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=None, out=None, dropout=None):
+    """dx [M, K] = (g [M, N] @ weight [N, K]) * gelu'(gate_pre) + resid (cvae_token_gemm_bwd_data).  weight: the fp32 nn.Linear tensor or a row slice of it;
+    mode: the arithmetic (torch.float32 / torch.bfloat16); g fp32 or `mode`; gate_pre [M, K] in `mode`: the saved pre-activation; resid fp32 [M, K] (any row
+    stride): added, result fp32, written to `out` (default: resid itself, in place).  out_dtype (default `mode`): the result's dtype without resid.
+    dropout = (p, key) or (p, key, row0, row_step): dx = (g W) keep s * gelu'(gate_pre) with the row-site mask over dx (cvae_token_gemm_bwd_data_dropout);
+    fp32 throughout, no resid.  None: exactly the path above."""
+    L.require_gpu(g, weight, gate_pre, resid, out)
+    _forward_only("token_gemm_bwd_data", g, weight, gate_pre, resid)
+    _rows2d(g, "token_gemm_bwd_data")
+    _gemm_mode("token_gemm_bwd_data", g, mode)
+    M, N = g.shape
+    K = weight.shape[1] if weight.dim() == 2 else -1
+    if weight.dim() != 2 or weight.shape[0] != N or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise L.CvaeError(f"token_gemm_bwd_data: g {tuple(g.shape)}, weight {tuple(weight.shape)} {weight.dtype} (contiguous fp32 [N, K] rows expected)")
+    if gate_pre is not None and (gate_pre.dtype != mode or _rows2d(gate_pre, "token_gemm_bwd_data gate_pre", K).shape[0] != M):
+        raise L.CvaeError(f"token_gemm_bwd_data: gate_pre {tuple(gate_pre.shape)} {gate_pre.dtype}")
+    if resid is not None:
+        if resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_bwd_data resid", K).shape[0] != M or out_dtype not in (None, torch.float32):
+            raise L.CvaeError("token_gemm_bwd_data: the residual needs a fp32 [M, K] tensor and a fp32 result")
+        out = resid if out is None else out
+    elif out is None:
+        out = _empty((M, K), out_dtype or mode, g)
+    if _rows2d(out, "token_gemm_bwd_data out", K).shape[0] != M or out.dtype not in (torch.float32, mode) or (resid is not None and out.dtype != torch.float32):
+        raise L.CvaeError(f"token_gemm_bwd_data: out {tuple(out.shape)} {out.dtype}")
+    cot, wgate, dx = (ptr(g), g.stride(0)), (ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0), (ptr(out), out.stride(0))
+    if dropout is not None:
+        sfx, p, key, row0, step = _dropout_site("token_gemm_bwd_data", dropout, True, g, out)
+        if mode != torch.float32 or resid is not None:
+            raise L.CvaeError("token_gemm_bwd_data: dropout runs in fp32 arithmetic and takes no residual")
+        check(getattr(lib, "cvae_token_gemm_bwd_data_dropout" + sfx)(*cot, *wgate, *dx, M, K, N, p, key, row0, step, stream()), "token_gemm_bwd_data_dropout" + sfx)
+    else:
+        check(lib.cvae_token_gemm_bwd_data(*cot, L.dtype_code(g.dtype), *wgate, ptr(resid), resid.stride(0) if resid is not None else 0, *dx, L.dtype_code(out.dtype),
+                                           M, K, N, L.dtype_code(mode), stream()), "token_gemm_bwd_data")
+    return out
+
+
+def token_gemm_wgrad(g, x, dW=None, db=None):
+    """(dW [N, K], db [N]) fp32 of token_gemm's nn.Linear from its input x [M, K] (fp32 or bf16: the arithmetic mode) and the cotangent g [M, N] of its output
+    (x's dtype, or the fp32 stream gradient) (cvae_token_gemm_wgrad).  dW / db: where to write, e.g. a row slice of the packed in-projection gradient."""
+    L.require_gpu(g, x, dW, db)
+    _forward_only("token_gemm_wgrad", g, x)
+    _rows2d(g, "token_gemm_wgrad g")
+    _rows2d(x, "token_gemm_wgrad x")
+    _gemm_mode("token_gemm_wgrad", g, x.dtype)
+    (M, N), K = g.shape, x.shape[1]
+    nbytes = lib.cvae_token_gemm_wgrad_workspace_bytes(M, K, N)
+    if x.shape[0] != M or not nbytes:
+        raise L.CvaeError(f"token_gemm_wgrad: g {tuple(g.shape)}, x {tuple(x.shape)}: {L.strerror(-3)}")
+    dW = _empty((N, K), torch.float32, x) if dW is None else dW
+    db = _empty((N,), torch.float32, x) if db is None else db
+    if dW.shape != (N, K) or db.shape != (N,) or dW.dtype != torch.float32 or db.dtype != torch.float32 or not dW.is_contiguous() or not db.is_contiguous():
+        raise L.CvaeError(f"token_gemm_wgrad: contiguous fp32 dW [{N}, {K}] and db [{N}] expected, got {tuple(dW.shape)} and {tuple(db.shape)}")
+    _t, wp, wb = _scratch(nbytes, x)
+    check(lib.cvae_token_gemm_wgrad(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(dW), ptr(db), M, K, N, L.dtype_code(x.dtype), wp, wb, stream()),
+          "token_gemm_wgrad")
+    return dW, db
+
+
+def layernorm256_bwd(g, x, weight, eps, dx=None, accumulate=False):
+    """(dx, dgamma, dbeta) of layernorm256 from its fp32 input x [rows, 256] (any row stride) and the cotangent g [rows, 256] of its output (fp32 or bf16)
+    (cvae_layernorm256_bwd).  dx: fp32 [rows, 256] with any row stride, written — or, with accumulate, added to (the stream gradient takes the LayerNorm
+    branch next to the skip); default: a fresh tensor."""
+    L.require_gpu(g, x, weight, dx)
+    _forward_only("layernorm256_bwd", g, x, weight)
+    _rows2d(g, "layernorm256_bwd g", 256)
+    _rows2d(x, "layernorm256_bwd x", 256)
+    rows = x.shape[0]
+    if weight.shape != (256,) or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise L.CvaeError(f"layernorm256_bwd: a contiguous fp32 [256] weight expected, got {tuple(weight.shape)} {weight.dtype}")
+    if x.dtype != torch.float32 or g.shape[0] != rows or g.dtype not in (torch.float32, torch.bfloat16) or (dx is None and accumulate):
+        raise L.CvaeError(f"layernorm256_bwd: x {tuple(x.shape)} {x.dtype}, g {tuple(g.shape)} {g.dtype}, accumulate {accumulate} into {None if dx is None else tuple(dx.shape)}")
+    dx = _empty((rows, 256), torch.float32, x) if dx is None else dx
+    if dx.dtype != torch.float32 or _rows2d(dx, "layernorm256_bwd dx", 256).shape[0] != rows:
+        raise L.CvaeError(f"layernorm256_bwd: dx {tuple(dx.shape)} {dx.dtype}")
+    dgamma, dbeta = _empty((256,), torch.float32, x), _empty((256,), torch.float32, x)
+    _t, wp, wb = _scratch(lib.cvae_layernorm256_bwd_workspace_bytes(rows), x)
+    check(lib.cvae_layernorm256_bwd(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(weight.detach()), ptr(dx), dx.stride(0), int(bool(accumulate)),
+                                    ptr(dgamma), ptr(dbeta), rows, float(eps), wp, wb, stream()), "layernorm256_bwd")
+    return dx, dgamma, dbeta
+
+
+def vit_tokens_bwd(dtokens, stem_dtype, gate=None, gate_act=None):
+    """(dpos [n + 1, 256], dcls [256], dstem [B, n, 256] in stem_dtype) from the fp32 residual-stream gradient [B, n + 1, 256] (cvae_vit_tokens_bwd).
+    gate / gate_act (optional, together): the stem's output [B, n, 256] in stem_dtype, the output of the activation gate_act; dstem is then multiplied by
+    act'(gate) = gate > 0 ? 1 : slope in fp32 before its one rounding — the gradient of the stem's last PRE-activation.  dpos and dcls are never gated."""
+    L.require_gpu(dtokens, gate)
+    _forward_only("vit_tokens_bwd", dtokens, gate)
+    if (gate is None) != (gate_act in (None, "none")) or gate_act not in _GATE_ACTS:
+        raise L.CvaeError(f"vit_tokens_bwd: gate and gate_act ({_GATE_ACTS[2:]}) come together, got gate_act={gate_act!r}")
+    if dtokens.dim() != 3 or dtokens.shape[1] < 2 or dtokens.shape[2] != 256 or dtokens.dtype != torch.float32 or not dtokens.is_contiguous():
+        raise L.CvaeError(f"vit_tokens_bwd: a contiguous fp32 [B, n + 1, 256] gradient expected, got {tuple(dtokens.shape)} {dtokens.dtype}")
+    B, n = dtokens.shape[0], dtokens.shape[1] - 1
+    dpos, dcls, dstem = _empty((n + 1, 256), torch.float32, dtokens), _empty((256,), torch.float32, dtokens), _empty((B, n, 256), stem_dtype, dtokens)
+    if gate is not None:
+        _like_operands("vit_tokens_bwd", (B, n, 256), stem_dtype, gate=gate)
+    check(lib.cvae_vit_tokens_bwd(ptr(dtokens), ptr(dpos), ptr(dcls), ptr(dstem), L.dtype_code(stem_dtype), ptr(gate), L.act_code(gate_act), B, n, stream()),
+          "vit_tokens_bwd")
+    return dpos, dcls, dstem
 
 
 # ---- attention weights and attention rollout (csrc/vit.hip, DESIGN §20): forward-only, recomputed from q, k and mhsa_train's lse -----------------------
@@ -2339,164 +2493,6 @@ def gradcam(A, dA, normalize=True):
         return cam
     check(lib.cvae_gradcam256(ptr(A), ptr(dA), ptr(cam), B, n, int(bool(normalize)), L.dtype_code(A.dtype), stream()), "gradcam")
     return cam
-
-
-def token_gemm_gelu_train(x, weight, bias):
-    """(gelu(x W^T + b), x W^T + b), both in x's dtype: token_gemm's "gelu" output, bit for bit, and the pre-activation (cvae_token_gemm_gelu_train)."""
-    return _token_gemm("token_gemm_gelu_train", x, weight, bias, "gelu", None, None, True)
-
-
-def token_gemm_dropout(x, weight, bias, epilogue, dropout, resid=None, out=None):
-    """token_gemm on fp32 x with a row-site dropout mask over the output (cvae_token_gemm_dropout).  dropout = (p, key) or (p, key, row0, row_step).
-    epilogue "gelu" -> (gelu(pre) keep s, pre): token_gemm_gelu_train's pair with the first member dropped; "residual" -> resid + (x W^T + b) keep s,
-    written to `out` (default: resid itself, in place).  p = 0 gives the bits of token_gemm_gelu_train / token_gemm."""
-    L.require_gpu(x, weight, bias, resid, out)
-    _forward_only("token_gemm_dropout", x, weight, bias, resid)
-    _rows2d(x, "token_gemm_dropout")
-    M, K = x.shape
-    N = weight.shape[0]
-    if weight.shape != (N, K) or bias is None or bias.shape != (N,) or weight.dtype != torch.float32 or epilogue not in ("gelu", "residual"):
-        raise L.CvaeError(f"token_gemm_dropout: x {tuple(x.shape)}, weight {tuple(weight.shape)}, epilogue {epilogue!r} ('gelu' or 'residual')")
-    sfx, p, key, row0, step = _dropout_site("token_gemm_dropout", dropout, True, x)
-    pre = None
-    if epilogue == "residual":
-        if resid is None or resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_dropout resid", N).shape[0] != M:
-            raise L.CvaeError("token_gemm_dropout: the residual epilogue needs a fp32 [M, N] residual")
-        out = resid if out is None else out
-    else:
-        if resid is not None or out is not None:
-            raise L.CvaeError("token_gemm_dropout: resid and out belong to the residual epilogue")
-        out, pre = _empty((M, N), torch.float32, x), _empty((M, N), torch.float32, x)
-    if _rows2d(out, "token_gemm_dropout out", N).shape[0] != M or out.dtype != torch.float32:
-        raise L.CvaeError(f"token_gemm_dropout: out {tuple(out.shape)} {out.dtype}")
-    check(getattr(lib, "cvae_token_gemm_dropout" + sfx)(ptr(x), x.stride(0), ptr(weight.detach().contiguous()), ptr(bias.detach()), ptr(resid),
-                                                        resid.stride(0) if resid is not None else 0, ptr(pre), N if pre is not None else 0, ptr(out), out.stride(0),
-                                                        M, K, N, GEMM_EPI[epilogue], p, key, row0, step, stream()), "token_gemm_dropout" + sfx)
-    return (out, pre) if epilogue == "gelu" else out
-
-
-def dropout_rows(x, dropout, out=None):
-    """x keep s on fp32 [M, N] rows (any row stride, N % 4 == 0) with the row-site mask (cvae_dropout_rows).  dropout = (p, key) or (p, key, row0, row_step);
-    out: where to write (may be x itself; default a new tensor).  On ones it is the mask."""
-    L.require_gpu(x, out)
-    _forward_only("dropout_rows", x)
-    _rows2d(x, "dropout_rows")
-    sfx, p, key, row0, step = _dropout_site("dropout_rows", dropout, True, x, out)
-    M, N = x.shape
-    if out is None:
-        out = _empty((M, N), torch.float32, x)
-    if _rows2d(out, "dropout_rows out", N).shape[0] != M:
-        raise L.CvaeError(f"dropout_rows: out {tuple(out.shape)} for x {tuple(x.shape)}")
-    check(getattr(lib, "cvae_dropout_rows" + sfx)(ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, p, key, row0, step, stream()), "dropout_rows" + sfx)
-    return out
-
-
-def _gemm_mode(what, g, mode):
-    """The arithmetic mode of a backward GEMM: fp32 mode takes fp32 cotangents only; bf16 mode takes bf16 ones or the fp32 stream gradient."""
-    if mode not in (torch.float32, torch.bfloat16) or g.dtype not in (torch.float32, mode):
-        raise L.CvaeError(f"{what}: a {g.dtype} cotangent in {mode} arithmetic")
-
-
-def token_gemm_bwd_data(g, weight, mode, out_dtype=None, gate_pre=None, resid=None, out=None, dropout=None):
-    """dx [M, K] = (g [M, N] @ weight [N, K]) * gelu'(gate_pre) + resid (cvae_token_gemm_bwd_data).  weight: the fp32 nn.Linear tensor or a row slice of it;
-    mode: the arithmetic (torch.float32 / torch.bfloat16); g fp32 or `mode`; gate_pre [M, K] in `mode`: the saved pre-activation; resid fp32 [M, K] (any row
-    stride): added, result fp32, written to `out` (default: resid itself, in place).  out_dtype (default `mode`): the result's dtype without resid.
-    dropout = (p, key) or (p, key, row0, row_step): dx = (g W) keep s * gelu'(gate_pre) with the row-site mask over dx (cvae_token_gemm_bwd_data_dropout);
-    fp32 throughout, no resid.  None: exactly the path above."""
-    L.require_gpu(g, weight, gate_pre, resid, out)
-    _forward_only("token_gemm_bwd_data", g, weight, gate_pre, resid)
-    _rows2d(g, "token_gemm_bwd_data")
-    _gemm_mode("token_gemm_bwd_data", g, mode)
-    M, N = g.shape
-    K = weight.shape[1] if weight.dim() == 2 else -1
-    if weight.dim() != 2 or weight.shape[0] != N or weight.dtype != torch.float32 or not weight.is_contiguous():
-        raise L.CvaeError(f"token_gemm_bwd_data: g {tuple(g.shape)}, weight {tuple(weight.shape)} {weight.dtype} (contiguous fp32 [N, K] rows expected)")
-    if gate_pre is not None and (gate_pre.dtype != mode or _rows2d(gate_pre, "token_gemm_bwd_data gate_pre", K).shape[0] != M):
-        raise L.CvaeError(f"token_gemm_bwd_data: gate_pre {tuple(gate_pre.shape)} {gate_pre.dtype}")
-    if resid is not None:
-        if resid.dtype != torch.float32 or _rows2d(resid, "token_gemm_bwd_data resid", K).shape[0] != M or out_dtype not in (None, torch.float32):
-            raise L.CvaeError("token_gemm_bwd_data: the residual needs a fp32 [M, K] tensor and a fp32 result")
-        out = resid if out is None else out
-    elif out is None:
-        out = _empty((M, K), out_dtype or mode, g)
-    if _rows2d(out, "token_gemm_bwd_data out", K).shape[0] != M or out.dtype not in (torch.float32, mode) or (resid is not None and out.dtype != torch.float32):
-        raise L.CvaeError(f"token_gemm_bwd_data: out {tuple(out.shape)} {out.dtype}")
-    if dropout is not None:
-        sfx, p, key, row0, step = _dropout_site("token_gemm_bwd_data", dropout, True, g, out)
-        if mode != torch.float32 or resid is not None:
-            raise L.CvaeError("token_gemm_bwd_data: dropout runs in fp32 arithmetic and takes no residual")
-        check(getattr(lib, "cvae_token_gemm_bwd_data_dropout" + sfx)(ptr(g), g.stride(0), ptr(weight.detach()), ptr(gate_pre),
-                                                                     gate_pre.stride(0) if gate_pre is not None else 0, ptr(out), out.stride(0), M, K, N, p, key,
-                                                                     row0, step, stream()), "token_gemm_bwd_data_dropout" + sfx)
-        return out
-    check(lib.cvae_token_gemm_bwd_data(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(weight.detach()), ptr(gate_pre), gate_pre.stride(0) if gate_pre is not None else 0,
-                                       ptr(resid), resid.stride(0) if resid is not None else 0, ptr(out), out.stride(0), L.dtype_code(out.dtype), M, K, N,
-                                       L.dtype_code(mode), stream()), "token_gemm_bwd_data")
-    return out
-
-
-def token_gemm_wgrad(g, x, dW=None, db=None):
-    """(dW [N, K], db [N]) fp32 of token_gemm's nn.Linear from its input x [M, K] (fp32 or bf16: the arithmetic mode) and the cotangent g [M, N] of its output
-    (x's dtype, or the fp32 stream gradient) (cvae_token_gemm_wgrad).  dW / db: where to write, e.g. a row slice of the packed in-projection gradient."""
-    L.require_gpu(g, x, dW, db)
-    _forward_only("token_gemm_wgrad", g, x)
-    _rows2d(g, "token_gemm_wgrad g")
-    _rows2d(x, "token_gemm_wgrad x")
-    _gemm_mode("token_gemm_wgrad", g, x.dtype)
-    (M, N), K = g.shape, x.shape[1]
-    nbytes = lib.cvae_token_gemm_wgrad_workspace_bytes(M, K, N)
-    if x.shape[0] != M or not nbytes:
-        raise L.CvaeError(f"token_gemm_wgrad: g {tuple(g.shape)}, x {tuple(x.shape)}: {L.strerror(-3)}")
-    dW = _empty((N, K), torch.float32, x) if dW is None else dW
-    db = _empty((N,), torch.float32, x) if db is None else db
-    if dW.shape != (N, K) or db.shape != (N,) or dW.dtype != torch.float32 or db.dtype != torch.float32 or not dW.is_contiguous() or not db.is_contiguous():
-        raise L.CvaeError(f"token_gemm_wgrad: contiguous fp32 dW [{N}, {K}] and db [{N}] expected, got {tuple(dW.shape)} and {tuple(db.shape)}")
-    _t, wp, wb = _scratch(nbytes, x)
-    check(lib.cvae_token_gemm_wgrad(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(dW), ptr(db), M, K, N, L.dtype_code(x.dtype), wp, wb, stream()),
-          "token_gemm_wgrad")
-    return dW, db
-
-
-def layernorm256_bwd(g, x, weight, eps, dx=None, accumulate=False):
-    """(dx, dgamma, dbeta) of layernorm256 from its fp32 input x [rows, 256] (any row stride) and the cotangent g [rows, 256] of its output (fp32 or bf16)
-    (cvae_layernorm256_bwd).  dx: fp32 [rows, 256] with any row stride, written — or, with accumulate, added to (the stream gradient takes the LayerNorm
-    branch next to the skip); default: a fresh tensor."""
-    L.require_gpu(g, x, weight, dx)
-    _forward_only("layernorm256_bwd", g, x, weight)
-    _rows2d(g, "layernorm256_bwd g", 256)
-    _rows2d(x, "layernorm256_bwd x", 256)
-    rows = x.shape[0]
-    if weight.shape != (256,) or weight.dtype != torch.float32 or not weight.is_contiguous():
-        raise L.CvaeError(f"layernorm256_bwd: a contiguous fp32 [256] weight expected, got {tuple(weight.shape)} {weight.dtype}")
-    if x.dtype != torch.float32 or g.shape[0] != rows or g.dtype not in (torch.float32, torch.bfloat16) or (dx is None and accumulate):
-        raise L.CvaeError(f"layernorm256_bwd: x {tuple(x.shape)} {x.dtype}, g {tuple(g.shape)} {g.dtype}, accumulate {accumulate} into {None if dx is None else tuple(dx.shape)}")
-    dx = _empty((rows, 256), torch.float32, x) if dx is None else dx
-    if dx.dtype != torch.float32 or _rows2d(dx, "layernorm256_bwd dx", 256).shape[0] != rows:
-        raise L.CvaeError(f"layernorm256_bwd: dx {tuple(dx.shape)} {dx.dtype}")
-    dgamma, dbeta = _empty((256,), torch.float32, x), _empty((256,), torch.float32, x)
-    _t, wp, wb = _scratch(lib.cvae_layernorm256_bwd_workspace_bytes(rows), x)
-    check(lib.cvae_layernorm256_bwd(ptr(g), g.stride(0), L.dtype_code(g.dtype), ptr(x), x.stride(0), ptr(weight.detach()), ptr(dx), dx.stride(0), int(bool(accumulate)),
-                                    ptr(dgamma), ptr(dbeta), rows, float(eps), wp, wb, stream()), "layernorm256_bwd")
-    return dx, dgamma, dbeta
-
-
-def vit_tokens_bwd(dtokens, stem_dtype, gate=None, gate_act=None):
-    """(dpos [n + 1, 256], dcls [256], dstem [B, n, 256] in stem_dtype) from the fp32 residual-stream gradient [B, n + 1, 256] (cvae_vit_tokens_bwd).
-    gate / gate_act (optional, together): the stem's output [B, n, 256] in stem_dtype, the output of the activation gate_act; dstem is then multiplied by
-    act'(gate) = gate > 0 ? 1 : slope in fp32 before its one rounding — the gradient of the stem's last PRE-activation.  dpos and dcls are never gated."""
-    L.require_gpu(dtokens, gate)
-    _forward_only("vit_tokens_bwd", dtokens, gate)
-    if (gate is None) != (gate_act in (None, "none")) or gate_act not in _GATE_ACTS:
-        raise L.CvaeError(f"vit_tokens_bwd: gate and gate_act ({_GATE_ACTS[2:]}) come together, got gate_act={gate_act!r}")
-    if dtokens.dim() != 3 or dtokens.shape[1] < 2 or dtokens.shape[2] != 256 or dtokens.dtype != torch.float32 or not dtokens.is_contiguous():
-        raise L.CvaeError(f"vit_tokens_bwd: a contiguous fp32 [B, n + 1, 256] gradient expected, got {tuple(dtokens.shape)} {dtokens.dtype}")
-    B, n = dtokens.shape[0], dtokens.shape[1] - 1
-    dpos, dcls, dstem = _empty((n + 1, 256), torch.float32, dtokens), _empty((256,), torch.float32, dtokens), _empty((B, n, 256), stem_dtype, dtokens)
-    if gate is not None:
-        _like_operands("vit_tokens_bwd", (B, n, 256), stem_dtype, gate=gate)
-    check(lib.cvae_vit_tokens_bwd(ptr(dtokens), ptr(dpos), ptr(dcls), ptr(dstem), L.dtype_code(stem_dtype), ptr(gate), L.act_code(gate_act), B, n, stream()),
-          "vit_tokens_bwd")
-    return dpos, dcls, dstem
 
 
 # ---- ViT-VAE decoder (csrc/conv_s1.hip): forward-only building blocks on raw tensors -------------------------------------------------

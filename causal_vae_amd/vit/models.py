@@ -151,43 +151,41 @@ class ViTVAEEncoder(nn.Module):
         attention (a callable): receives (q, k, lse) of the block's attention, views as ops.mhsa_weights takes them.  An inference block then runs
         its attention as ops.mhsa_train without dropout (the same `out`, bit for bit, plus lse); nothing else changes."""
         B, N, D = tokens.shape
-        att_d, act_d, out_d = drop
+        att_d, act_d, out_d = drop if save else _NO_DROP
         rows = (0, N) if cls_only else (0, 1)
+        act_d, out_d = (None if d is None else d + rows for d in (act_d, out_d))       # the row sites as the ops take them
         dt = self.compute_dtype
         X = tokens.view(B * N, D)
         a = blk.attn
-        attend = (lambda *a, **kw: ops.mhsa_train(*a, dropout=att_d, **kw)) if save else (ops.mhsa if attention is None else ops.mhsa_train)
         y = ops.layernorm256(X, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
         if not cls_only:
             qkv, q = ops.token_gemm(y, a.in_proj_weight, a.in_proj_bias).view(B, N, 3 * D), None
-            att = attend(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:])
+            heads, nq = (qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:]), None
             resid, X1 = X, (torch.empty_like(X) if save else None)      # None: in place on the stream
         else:
             qkv = ops.token_gemm(y, a.in_proj_weight[D:], a.in_proj_bias[D:]).view(B, N, 2 * D)
             q = ops.token_gemm(y.view(B, N, D)[:, 0], a.in_proj_weight[:D], a.in_proj_bias[:D]).view(B, 1, D)
-            att = attend(q, qkv[:, :, :D], qkv[:, :, D:], n_query_rows=1)
+            heads, nq = (q, qkv[:, :, :D], qkv[:, :, D:]), 1
             resid, X1 = tokens[:, 0], torch.empty(B, D, dtype=torch.float32, device=tokens.device)
-        att, lse = att if (save or attention is not None) else (att, None)
+        if save or attention is not None:
+            att, lse = ops.mhsa_train(*heads, nq, dropout=att_d)
+        else:
+            att, lse = ops.mhsa(*heads, nq), None
         if attention is not None:
-            attention(q if cls_only else qkv[:, :, :D], qkv[:, :, :D] if cls_only else qkv[:, :, D:2 * D], lse)
+            attention(heads[0], heads[1], lse)
         X1 = ops.token_gemm(att.view(-1, D), a.out_proj.weight, a.out_proj.bias, "residual", resid=resid, out=X1)
         y2 = ops.layernorm256(X1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-        if save and act_d is not None:
-            hid, pre = ops.token_gemm_dropout(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu", act_d + rows)
-        elif save:
-            hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias)
+        if save:
+            hid, pre = ops.token_gemm_gelu_train(y2, blk.mlp[0].weight, blk.mlp[0].bias, dropout=act_d)
         else:
             hid, pre = ops.token_gemm(y2, blk.mlp[0].weight, blk.mlp[0].bias, "gelu"), None
-        if save and out_d is not None:
-            X2 = ops.token_gemm_dropout(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", out_d + rows, resid=X1, out=torch.empty_like(X1))
-        else:
-            X2 = ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=torch.empty_like(X1) if save else None)
+        X2 = ops.token_gemm(hid, blk.mlp[3].weight, blk.mlp[3].bias, "residual", resid=X1, out=torch.empty_like(X1) if save else None, dropout=out_d)
         if not save:
             return (X2 if cls_only else tokens), None                   # a full block wrote the stream itself
         return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only, drop)
 
     @torch.no_grad()
-    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None, dropout=True):
+    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None, dropout=True, cls_only_last=None):
         """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
         saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
@@ -198,8 +196,10 @@ class ViTVAEEncoder(nn.Module):
         attention (a callable; attention_weights / attention_rollout): called as attention(i, q, k, lse) after block i's attention, see _block.
         None (the default): exactly the launches above.
         dropout=False (the *_vjp entries and an image that asks for its gradient through frozen parameters): a save=True walk that never drops and
-        draws no step, whatever train_transformer() asked for."""
+        draws no step, whatever train_transformer() asked for.
+        cls_only_last: whether the last block runs for its CLS row alone (the same CLS row, bit for bit); None (the default): self._cls_only_last_block."""
         self._check(x)
+        cls_only_last = self._cls_only_last_block if cls_only_last is None else cls_only_last
         drop_step = None
         if save and self._dropout and dropout:
             self._check_dropout_dtype()
@@ -214,7 +214,7 @@ class ViTVAEEncoder(nn.Module):
             collect["stem"], collect["cls_rows"], collect["tokens"] = stem, [], []
         steps = []
         for i, blk in enumerate(self.transformer):
-            cls_only = self._cls_only_last_block and i == self.depth - 1
+            cls_only = cls_only_last and i == self.depth - 1
             out, step = self._block(blk, tokens, cls_only, save, _NO_DROP if drop_step is None else self._block_dropout(blk, i, drop_step),
                                     None if attention is None else (lambda q, k, lse, i=i: attention(i, q, k, lse)))
             steps.append(step)
@@ -266,16 +266,7 @@ class ViTVAEEncoder(nn.Module):
                 nq = k.shape[1] if query == "all" else 1
                 found[i] = ops.mhsa_weights(q, k, lse if lse.shape[2] == nq else lse[:, :, :nq].contiguous(), nq, average_heads)
 
-        own, flag = "_cls_only_last_block" in vars(self), self._cls_only_last_block
-        try:
-            if query == "all":
-                self._cls_only_last_block = False
-            self._walk(x, attention=probe)
-        finally:                                                          # the flag as it was, an instance attribute only if it was one
-            if own:
-                self._cls_only_last_block = flag
-            else:
-                vars(self).pop("_cls_only_last_block", None)
+        self._walk(x, attention=probe, cls_only_last=False if query == "all" else None)
         return torch.stack([found[i] for i in idx], dim=1)
 
     @torch.no_grad()

@@ -128,7 +128,7 @@ def test_the_table_covers_every_entry_that_lifts_a_dtype():
     import re
     csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
     helpers = {"token_gemm": ("cvae_token_gemm", "cvae_token_gemm_gelu_train"), "mhsa_fwd": ("cvae_mhsa_fwd", "cvae_mhsa_fwd_train"),
-               "transpose_cs": ("cvae_ncs_to_nsc", "cvae_nsc_to_ncs")}
+               "mhsa_bwd": ("cvae_mhsa_bwd",), "token_gemm_bwd_data": ("cvae_token_gemm_bwd_data",), "transpose_cs": ("cvae_ncs_to_nsc", "cvae_nsc_to_ncs")}
     want = set()
     for f in sorted(os.listdir(csrc)):
         if not f.endswith(".hip"):
