@@ -156,6 +156,9 @@ SIGNATURES = {
     "cvae_mhsa_weights": [_p] * 4 + [_i64] * 8 + [_i, _i, _p],
     "cvae_mhsa_rollout_step": [_p] * 5 + [_i64] * 7 + [_f, _i, _p],
     "cvae_gradcam256": [_p, _p, _p, _i64, _i64, _i, _i, _p],
+    "cvae_mhsa_weight_grads": [_p] * 3 + [_i64] * 6 + [_i, _p],
+    "cvae_mhsa_relevance_step_workspace_bytes": [_i64] * 3,
+    "cvae_mhsa_relevance_step": [_p] * 7 + [_i64] * 9 + [_i, _p, _sz, _p],
     "cvae_conv_s1_weight_elems": [_i64, _i64, _i],
     "cvae_conv_s1_pack_weights": [_i, _p, _p, _p, _p],
     "cvae_conv_s1": [_p] * 5 + [_i64] * 5 + [_i, _i, _i, _p],
@@ -191,7 +194,8 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_mlp_heads_train_workspace_bytes": _sz, "cvae_mlp_heads_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz, "cvae_mhsa_bwd_workspace_bytes": _sz,
-            "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz}
+            "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz,
+            "cvae_mhsa_relevance_step_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

@@ -13,6 +13,8 @@
 // a step's keys from a device-resident counter and advances it.
 // vit_attention_probe.inc holds the one forward-only kernel that looks inside: the attention probabilities the fused forward never writes,
 // recomputed from q, k and the training forward's row statistic, stored (per head or head-averaged) or folded into one attention-rollout factor.
+// vit_attention_grad_probe.inc is its counterpart on the backward's side: the gradient with respect to those probabilities, dO V^T, stored
+// per head or folded with P into one step of gradient-weighted attention relevance, the query tiles split over workgroups and added by an ordered finish launch.
 // Two arithmetic modes from one template: bf16 operands on v_mfma_f32_32x32x16_bf16, or exact fp32 on v_mfma_f32_32x32x2_f32 (the form the conv family uses
 // for fp32); accumulation, softmax, LayerNorm statistics and the residual stream are fp32 in both.  No atomics anywhere: every sum has a fixed order,
 // and an output element's bits do not depend on which other rows share its launch (row r of a one-row call equals row r of a full call: the CLS-only
@@ -523,6 +525,9 @@ template <> struct AttBwdGeom<float> { static constexpr int NP = 40, TP = 0, NS 
 // ------------------------------------------------------------------------------------------------ attention weights and rollout
 #include "vit_attention_probe.inc"
 
+// ------------------------------------------------------------------------------------------------ attention gradients and relevance
+#include "vit_attention_grad_probe.inc"
+
 // ------------------------------------------------------------------------------------------------ Grad-CAM on the stem output
 #include "vit_gradcam.inc"
 
@@ -976,7 +981,82 @@ extern "C" int cvae_mhsa_rollout_step(const void* q, const void* k, const float*
     return mhsa_probe_launch(a, PROBE_ROLLOUT, B, dtype, stream);
 }
 
-// ---- Grad-CAM on the stem output: forward-only, one workgroup per image.  The checks and the launch, as for the two entries above.
+// ---- attention gradients and gradient-weighted relevance: forward-only, from the data-only backward's datt and the walk's q, k, v, lse.
+
+// the checks of dout (dense [B][n_query_rows][256]) and the v view.  cvae_mhsa_relevance_step runs them after mhsa_probe_check's; cvae_mhsa_weight_grads has no q, k
+// or lse and passes its sizes (sizes = true): the same size and dtype checks first; CVAE_OK with B == 0 means: nothing to launch
+static int mhsa_grad_probe_check(const void* dout, const void* v, int64_t v_stride, int64_t v_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows,
+                                 int dtype, bool sizes) {
+    if (sizes) {
+        if (B < 0 || B > 65535 || n_tokens < 1 || n_tokens > ((int64_t)1 << 24) || n_query_rows < 1 || n_query_rows > n_tokens) return CVAE_E_BADSHAPE;
+        if (!dtype_ok(dtype)) return CVAE_E_DTYPE;
+        if (B == 0) return CVAE_OK;
+    }
+    if (!dout || !v) return CVAE_E_NULLPTR;
+    const int64_t e16 = dtype == CVAE_BF16 ? 8 : 4;
+    if (v_stride < VIT_DIM || v_batch_stride < 0) return CVAE_E_BADSHAPE;
+    if ((v_stride % e16) || (v_batch_stride % e16) || !aligned16(dout) || !aligned16(v)) return CVAE_E_UNSUPPORTED;
+    return CVAE_OK;
+}
+
+// the one launch of both entries: a workgroup per (128 keys, head or chunk of query tiles, batch row)
+static int mhsa_grad_probe_launch(const AttGradProbeArgs& a, int mode, unsigned grid_y, int64_t B, int dtype, hipStream_t st) {
+    const dim3 grid((unsigned)((a.N + 127) / 128), grid_y, (unsigned)B);
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        if (mode == GRADP_HEADS) hipLaunchKernelGGL((vit_attention_grad_probe_kernel<T, GRADP_HEADS>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((vit_attention_grad_probe_kernel<T, GRADP_RELEVANCE>), grid, dim3(256), 0, st, a);
+        return launch_rc();
+    });
+}
+
+// query tiles -> chunks of the relevance step: a function of n_query_rows alone
+static int64_t relevance_chunks(int64_t n_query_rows) {
+    const int64_t tiles = (n_query_rows + ATT_KT - 1) / ATT_KT;
+    return (tiles + GRADP_CHUNK_TILES - 1) / GRADP_CHUNK_TILES;
+}
+
+extern "C" int cvae_mhsa_weight_grads(const void* dout, const void* v, float* w, int64_t v_stride, int64_t v_batch_stride, int64_t w_batch_stride, int64_t B,
+                                      int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream) {
+    const int rc = mhsa_grad_probe_check(dout, v, v_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, true);
+    if (rc != CVAE_OK || B == 0) return rc;
+    if (!w) return CVAE_E_NULLPTR;
+    if (w_batch_stride < VIT_HEADS * n_query_rows * n_tokens) return CVAE_E_BADSHAPE;
+    if (!aligned16(w)) return CVAE_E_UNSUPPORTED;
+    const AttGradProbeArgs a = {nullptr, nullptr, v, dout, 0, 0, v_stride, 0, 0, v_batch_stride, nullptr, nullptr, w, w_batch_stride, (int)n_tokens,
+                                (int)n_query_rows, 0.f};
+    return mhsa_grad_probe_launch(a, GRADP_HEADS, VIT_HEADS, B, dtype, (hipStream_t)stream);
+}
+
+extern "C" size_t cvae_mhsa_relevance_step_workspace_bytes(int64_t B, int64_t n_tokens, int64_t n_query_rows) {
+    if (B < 1 || n_tokens < 1 || n_query_rows < 1 || n_query_rows > n_tokens) return 0;
+    const int64_t S = relevance_chunks(n_query_rows);
+    return S < 2 ? 0 : (size_t)(B * S * n_tokens) * sizeof(float);      // one chunk writes out itself
+}
+
+extern "C" int cvae_mhsa_relevance_step(const void* q, const void* k, const void* v, const float* lse, const void* dout, const float* r, float* out, int64_t q_stride,
+                                        int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B,
+                                        int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = mhsa_probe_check(q, k, lse, q_stride, k_stride, q_batch_stride, k_batch_stride, B, n_tokens, n_query_rows, dtype);
+    if (rc != CVAE_OK || B == 0) return rc;
+    rc = mhsa_grad_probe_check(dout, v, v_stride, v_batch_stride, B, n_tokens, n_query_rows, dtype, false);
+    if (rc != CVAE_OK) return rc;
+    const int64_t S = relevance_chunks(n_query_rows);
+    if (!r || !out || (S > 1 && !workspace)) return CVAE_E_NULLPTR;
+    if (((uintptr_t)r & 3) || ((uintptr_t)out & 3) || ((uintptr_t)workspace & 3) || S > 65535) return CVAE_E_UNSUPPORTED;      // the chunk index is grid.y
+    if (r < out + B * n_tokens && out < r + B * n_tokens) return CVAE_E_UNSUPPORTED;       // out == r, or any overlap: other workgroups still read r
+    if (workspace_bytes < cvae_mhsa_relevance_step_workspace_bytes(B, n_tokens, n_query_rows)) return CVAE_E_WORKSPACE;
+    const AttGradProbeArgs a = {q, k, v, dout, q_stride, k_stride, v_stride, q_batch_stride, k_batch_stride, v_batch_stride, lse, r,
+                                S > 1 ? (float*)workspace : out, 0, (int)n_tokens, (int)n_query_rows, 0.17677669529663688110f * 1.44269504088896340736f};
+    hipStream_t st = (hipStream_t)stream;
+    rc = mhsa_grad_probe_launch(a, GRADP_RELEVANCE, (unsigned)S, B, dtype, st);
+    if (rc != CVAE_OK || S == 1) return rc;
+    const int64_t total = B * n_tokens;
+    hipLaunchKernelGGL(vit_relevance_finish_kernel, dim3(cvae_grid_1d(total, 256, 256 * 32)), dim3(256), 0, st, (const float*)workspace, r, out, (int)S, (int)n_tokens, total);
+    return launch_rc();
+}
+
+// ---- Grad-CAM on the stem output: forward-only, one workgroup per image.  The checks and the launch, as for the probe entries above.
 static int gradcam_check(const void* A, const void* dA, const float* cam, int64_t B, int64_t n, int dtype) {
     if (B < 0 || n < 1) return CVAE_E_BADSHAPE;
     if (!dtype_ok(dtype)) return CVAE_E_DTYPE;

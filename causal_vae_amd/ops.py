@@ -2474,6 +2474,67 @@ def mhsa_rollout_step(q, k, lse, r, n_query_rows=None, residual=0.5, out=None):
     return out
 
 
+# ---- attention gradients and gradient-weighted relevance (csrc/vit_attention_grad_probe.inc): forward-only ---------------------------------
+def _mhsa_dout(what, dout, like, B, nq):
+    """dout as mhsa_bwd takes it: the contiguous [B, n_query_rows, 256] cotangent of the attention output, in the operands' dtype."""
+    if tuple(dout.shape) != (B, nq, 256) or dout.dtype != like.dtype or not dout.is_contiguous() or dout.device != like.device:
+        raise L.CvaeError(f"{what}: dout must be a contiguous {like.dtype} [{B}, {nq}, 256] tensor on {like.device}, got {tuple(dout.shape)} {dout.dtype}")
+
+
+def mhsa_weight_grads(dout, v, n_query_rows=None, out=None):
+    """The gradient with respect to the attention probabilities taken as a free variable (cvae_mhsa_weight_grads) — what a hook on the softmax output
+    receives: gA[b, h, i, j] = sum_{d < 32} dout[b, i, 32 h + d] v[b, j, 32 h + d].  dout: the contiguous [B, n_query_rows, 256] cotangent of mhsa's output;
+    v [B, N, 256], a view as mhsa takes it.  Returns fp32 [B, 8, n_query_rows, N] with dense rows (`out`: as in mhsa_weights)."""
+    L.require_gpu(dout, v)
+    _forward_only("mhsa_weight_grads", dout, v)
+    B, N = v.shape[0], v.shape[1]
+    nq = N if n_query_rows is None else int(n_query_rows)
+    if not 1 <= nq <= N:
+        raise L.CvaeError(f"mhsa_weight_grads: 1 <= n_query_rows <= {N} expected, got {nq}")
+    _mhsa_views("mhsa_weight_grads", B, (N,), v)
+    _mhsa_dout("mhsa_weight_grads", dout, v, B, nq)
+    shape = (B, 8, nq, N)
+    if out is None:
+        out = _empty(shape, torch.float32, v)
+    else:
+        L.require_gpu(out)
+        if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != v.device or (B and not out[0].is_contiguous())
+                or (B > 1 and out.stride(0) < out[0].numel()) or out.data_ptr() % 16):
+            raise L.CvaeError(f"mhsa_weight_grads: out must be a float32 {shape} tensor on {v.device} with contiguous batch blocks and a 16-byte-aligned base, "
+                              f"got {tuple(out.shape)} {out.dtype} strides {tuple(out.stride())}")
+    if B == 0:
+        return out
+    check(lib.cvae_mhsa_weight_grads(ptr(dout), ptr(v), ptr(out), v.stride(1), v.stride(0), out.stride(0) if B > 1 else out[0].numel(), B, N, nq,
+                                     L.dtype_code(v.dtype), stream()), "mhsa_weight_grads")
+    return out
+
+
+def mhsa_relevance_step(q, k, v, lse, dout, r, n_query_rows=None, out=None):
+    """One step of gradient-weighted attention relevance (Chefer, Gur & Wolf 2021, the self-attention rule) applied to a row vector, no N x N matrix formed
+    (cvae_mhsa_relevance_step):  out[b, j] = r[b, j] + sum_{i < n_query_rows} r[b, i] Abar[b, i, j],  Abar = 1/8 sum_h max(0, gA P),
+    with P as in mhsa_weights (from q, k, lse) and gA as in mhsa_weight_grads (from dout, v).  r: fp32 [B, N] contiguous; returns fp32 [B, N] (written to `out`
+    if given: it must not be r or overlap it)."""
+    B, N, nq, (qs, ks, qb, kb) = _mhsa_probe("mhsa_relevance_step", q, k, lse, n_query_rows)
+    L.require_gpu(v, dout, r, out)
+    _forward_only("mhsa_relevance_step", v, dout)
+    _mhsa_views("mhsa_relevance_step", B, (nq, N, N), q, k, v)
+    if v.shape[1] != N:
+        raise L.CvaeError(f"mhsa_relevance_step: k {tuple(k.shape)} and v {tuple(v.shape)} must hold the same tokens")
+    _mhsa_dout("mhsa_relevance_step", dout, q, B, nq)
+    if r.shape != (B, N) or r.dtype != torch.float32 or not r.is_contiguous() or r.device != q.device:
+        raise L.CvaeError(f"mhsa_relevance_step: r must be a contiguous float32 [{B}, {N}] tensor on {q.device}, got {tuple(r.shape)} {r.dtype}")
+    if out is None:
+        out = _empty((B, N), torch.float32, q)
+    elif out.shape != r.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != r.device:
+        raise L.CvaeError(f"mhsa_relevance_step: out must be a contiguous float32 [{B}, {N}] tensor on {q.device}, got {tuple(out.shape)} {out.dtype}")
+    if B == 0:
+        return out
+    _t, wp, wb = _scratch(lib.cvae_mhsa_relevance_step_workspace_bytes(B, N, nq), q)
+    check(lib.cvae_mhsa_relevance_step(ptr(q), ptr(k), ptr(v), ptr(lse), ptr(dout), ptr(r), ptr(out), qs, ks, v.stride(1), qb, kb, v.stride(0), B, N, nq,
+                                       L.dtype_code(q.dtype), wp, wb, stream()), "mhsa_relevance_step")
+    return out
+
+
 # ---- Grad-CAM on the stem output (csrc/vit_gradcam.inc, DESIGN §21): forward-only --------------------------------------------------------------------
 def gradcam(A, dA, normalize=True):
     """Grad-CAM of a channels-last activation and its gradient (cvae_gradcam256): A, dA [B, n, 256] contiguous, fp32 or bf16, the same dtype (the stem output

@@ -8,11 +8,13 @@ recipe; GraphedViTTrainStep: that step captured as one HIP graph, 
 Looking inside: ViTVAEEncoder.attention_weights / attention_rollout (so ViTVAE's, and CausalViTVAE.attention_rollout through its backbone) and
 extract_vit_attention, the rollout maps of a loader.  The gradient with respect to the image: ViTVAEEncoder.cls_features_vjp / encode_vjp, x.grad
 after cls_features_with_grad / encode_with_grad / ViTVAE.forward_train of an image that asks, saliency (plain and integrated gradients) and gradcam (both also
-on CausalViTVAE, through its backbone), and extract_vit_saliency for a loader."""
-from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, extract_vit_attention, extract_vit_saliency, resize_pos_embedding,   # noqa: F401
-                     fit_latent, vit_vae_loss, train_vit_vae, vit_vae_train_step)
+on CausalViTVAE, through its backbone), and extract_vit_saliency for a loader.  Looking inside with a target: ViTVAEEncoder.attention_gradients
+(the gradient with respect to the attention probabilities) and attention_relevance (gradient-weighted attention relevance), both also on CausalViTVAE, and
+extract_vit_relevance for a loader."""
+from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, extract_vit_attention, extract_vit_saliency, extract_vit_relevance,   # noqa: F401
+                     resize_pos_embedding, fit_latent, vit_vae_loss, train_vit_vae, vit_vae_train_step)
 from .causal import AdapterMLP, CausalViTVAE   # noqa: F401
 from .train import GraphedViTTrainStep, causal_vit_train_step   # noqa: F401
 
-__all__ = ["ViTVAE", "ViTVAEEncoder", "load_vitvae_state_dict", "extract_vit_latents", "extract_vit_attention", "extract_vit_saliency", "resize_pos_embedding", "fit_latent",
+__all__ = ["ViTVAE", "ViTVAEEncoder", "load_vitvae_state_dict", "extract_vit_latents", "extract_vit_attention", "extract_vit_saliency", "extract_vit_relevance", "resize_pos_embedding", "fit_latent",
            "vit_vae_loss", "train_vit_vae", "vit_vae_train_step", "AdapterMLP", "CausalViTVAE", "GraphedViTTrainStep", "causal_vit_train_step"]

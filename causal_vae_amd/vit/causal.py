@@ -227,6 +227,16 @@ class CausalViTVAE(nn.Module):
         self._require_eval()
         return self.backbone.gradcam(x, **kw)
 
+    def attention_gradients(self, x, **kw):
+        """backbone.attention_gradients(x, **kw): the gradient of a backbone target with respect to the attention probabilities."""
+        self._require_eval()
+        return self.backbone.attention_gradients(x, **kw)
+
+    def attention_relevance(self, x, **kw):
+        """backbone.attention_relevance(x, **kw): gradient-weighted attention relevance of a backbone target, fp32 [B, grid_h, grid_w]."""
+        self._require_eval()
+        return self.backbone.attention_relevance(x, **kw)
+
     @torch.no_grad()
     def decode(self, z, m):
         """backbone.decode(dec_adapter(cat[m, z])) -> [B, 1, H, W] (models.py:299-305).  Note the argument order: z first, m second; the concatenation is

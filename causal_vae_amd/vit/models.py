@@ -35,6 +35,8 @@ are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
 The gradient with respect to the IMAGE: cls_features_vjp / encode_vjp (explicit, no graph), x.grad after cls_features_with_grad / encode_with_grad /
 forward_train of an x that asks, saliency (plain and integrated gradients) and gradcam.  They share a data-only form of the backward (_walk_backward(params=False):
 no weight-gradient launch) whose last hop, 32 channels to the one-channel image, is cvae_conv_down_image_bwd_data (fp32 result in both compute dtypes).
+Looking inside with a target: that backward hands each block's attention cotangent to an optional hook; attention_gradients (d target / d attention
+probabilities, cvae_mhsa_weight_grads) and attention_relevance (gradient-weighted attention relevance, one cvae_mhsa_relevance_step per block) are built on it.
 """
 from collections import namedtuple
 
@@ -465,11 +467,13 @@ class ViTVAEEncoder(nn.Module):
             return torch.autograd.grad([y for y, _g in pairs], [c], [g for _y, g in pairs])[0]
 
     @torch.no_grad()
-    def _data_backward(self, x, cotangent, image=None, stem=True):
+    def _data_backward(self, x, cotangent, image=None, stem=True, attention_grad=None, cls_only_last=None):
         """The eval-mode saving walk (never drops, draws no dropout step) and the data-only backward -> (the walk's _Walk, {`dstem`, and with stem `dx`}).
-        cotangent: a callable, cls features [B, 256] -> their fp32 cotangent.  stem=False keeps nothing of the stem and stops at `dstem` (Grad-CAM)."""
-        out, saved = self._walk(x.detach(), save=True, keep_stem=stem, dropout=False)
-        return saved, self._walk_backward(saved, cotangent(out).contiguous(), params=False, image=({} if image is None else image) if stem else None)
+        cotangent: a callable, cls features [B, 256] -> their fp32 cotangent.  stem=False keeps nothing of the stem and stops at `dstem` (Grad-CAM).
+        attention_grad: passed to _walk_backward; cls_only_last: passed to _walk (both DESIGN §22; the defaults issue exactly the launches above)."""
+        out, saved = self._walk(x.detach(), save=True, keep_stem=stem, dropout=False, cls_only_last=cls_only_last)
+        return saved, self._walk_backward(saved, cotangent(out).contiguous(), params=False, image=({} if image is None else image) if stem else None,
+                                          attention_grad=attention_grad)
 
     @torch.no_grad()
     def cls_features_vjp(self, x, g, _image=None):
@@ -566,9 +570,73 @@ class ViTVAEEncoder(nn.Module):
         B = x.shape[0]
         if B == 0:
             return torch.zeros(0, self.grid_h, self.grid_w, dtype=torch.float32, device=x.device)
-        cot = (lambda _c: g) if target == "cls" else (lambda c: self._heads_vjp(c, g if target == "mu" else None, g if target == "log_var" else None))
-        saved, grads = self._data_backward(x, cot, stem=False)
+        saved, grads = self._data_backward(x, self._head_cotangent(target, g), stem=False)
         return ops.gradcam(saved.stem_out.view(B, self.num_patches, self.embed_dim), grads["dstem"], normalize).view(B, self.grid_h, self.grid_w)
+
+    # ---- looking inside, with a target: attention gradients and gradient-weighted relevance ------------------------------
+    def _head_cotangent(self, target, g):
+        """_data_backward's `cotangent` for the selector g of _target_cotangent."""
+        if target == "cls":
+            return lambda _c: g
+        return lambda c: self._heads_vjp(c, g if target == "mu" else None, g if target == "log_var" else None)
+
+    @torch.no_grad()
+    def attention_gradients(self, x, target="mu", index=None, query="cls", blocks=None):
+        """The gradient of sum_{k in index} target[:, k] (target and index as in saliency) with respect to the attention probabilities of the transformer
+        blocks, taken as a free variable — what retain_grad() on a hook at the softmax output of the reference's blocks leaves: fp32 [B, n_blocks, 8, Nq, N],
+        gA[b, l, h, i, j] = sum_d datt_l[b, i, 32 h + d] v_l[b, j, 32 h + d].  query and blocks as in attention_weights; with query="all" the last block's rows
+        >= 1 are zeros, exactly: only its CLS output reaches any target.  One saving walk, the data-only backward down to `dstem` (nothing of the stem is
+        walked back, no weight-gradient launch) and one ops.mhsa_weight_grads launch per selected block.
+        Eval mode, no gradient, never drops, either compute dtype; no state of the model changes."""
+        g = self._target_cotangent("attention_gradients", x.shape[0], target, index, x.device)
+        if query not in ("cls", "all"):
+            raise CvaeError(f"ViTVAEEncoder.attention_gradients: query must be \"cls\" or \"all\", got {query!r}")
+        idx = list(range(self.depth)) if blocks is None else [int(i) for i in blocks]
+        if not idx or any(not 0 <= i < self.depth for i in idx):
+            raise CvaeError(f"ViTVAEEncoder.attention_gradients: blocks must name at least one of the {self.depth} blocks (0 .. {self.depth - 1}), got {blocks!r}")
+        self._check(x)
+        B, N = x.shape[0], self.num_patches + 1
+        Nq = N if query == "all" else 1
+        if B == 0:
+            return torch.zeros(0, len(idx), 8, Nq, N, dtype=torch.float32, device=x.device)
+        found = {}
+
+        def probe(i, q, k, v, lse, datt, nq):
+            if i not in idx:
+                return
+            if nq == Nq:
+                found[i] = ops.mhsa_weight_grads(datt, v, nq)
+            elif nq == 1:                                               # the last block under query="all": only its CLS row exists
+                found[i] = torch.zeros(B, 8, Nq, N, dtype=torch.float32, device=x.device)
+                found[i][:, :, :1] = ops.mhsa_weight_grads(datt, v, 1)
+            else:                                                       # the CLS row of a block that ran for all tokens
+                found[i] = ops.mhsa_weight_grads(datt[:, :1].contiguous(), v, 1)
+
+        self._data_backward(x, self._head_cotangent(target, g), stem=False, attention_grad=probe, cls_only_last=False if query == "all" else None)
+        return torch.stack([found[i] for i in idx], dim=1)
+
+    @torch.no_grad()
+    def attention_relevance(self, x, target="mu", index=None, as_grid=True):
+        """Gradient-weighted attention relevance (Chefer, Gur & Wolf 2021, the self-attention rule) of sum_{k in index} target[:, k] from the CLS token:
+        R = I, then R <- R + Abar_l R over the blocks, Abar_l = 1/8 sum_h max(0, gA_l P_l) with gA as in attention_gradients and P as in attention_weights;
+        the map is R's CLS row.  Computed as a row vector, r = e_cls, then one ops.mhsa_relevance_step per block from the last to the first, inside the
+        backward that forms each block's datt; no N x N matrix is formed.  Unlike attention_rollout the map depends on the target and on the sign of a head's
+        contribution.  as_grid=True: the patch columns as fp32 [B, grid_h, grid_w] (the CLS column dropped, nothing renormalised); False: the whole row [B, N].
+        One saving walk and the data-only backward down to `dstem`.  Eval mode, no gradient, never drops, either compute dtype; no state changes."""
+        g = self._target_cotangent("attention_relevance", x.shape[0], target, index, x.device)
+        self._check(x)
+        B, N = x.shape[0], self.num_patches + 1
+        r = torch.zeros(B, N, dtype=torch.float32, device=x.device)
+        if B:
+            r[:, 0] = 1.0
+            row = [r]
+
+            def step(_i, q, k, v, lse, datt, nq):
+                row[0] = ops.mhsa_relevance_step(q, k, v, lse, datt, row[0], nq)
+
+            self._data_backward(x, self._head_cotangent(target, g), stem=False, attention_grad=step)
+            r = row[0]
+        return r[:, 1:].reshape(B, self.grid_h, self.grid_w) if as_grid else r
 
     def _cls_rows_step(self, s):
         """The record a CLS-only block would have kept, cut from a full block's _BlockStep (the last block of a walk with _cls_only_last_block False): k / v
@@ -580,11 +648,13 @@ class ViTVAEEncoder(nn.Module):
         return s._replace(qkv=s.qkv[:, :, D:], q=s.qkv[:, :1, :D], att=s.att[:, :1].contiguous(), lse=s.lse[:, :, :1].contiguous(), X1=row0(s.X1), y2=row0(s.y2),
                           pre=row0(s.pre), hid=row0(s.hid), cls_only=True)
 
-    def _block_backward(self, blk, name, s, G, grads):
+    def _block_backward(self, blk, name, s, G, grads, attention_grad=None):
         """One block's backward from its _BlockStep s: G = the fp32 gradient of the block's output ([B N, 256], or [B, 256] from a CLS-only block), updated in
         place where it can be; returns the gradient of the block's input [B N, 256] and leaves the parameter gradients in `grads` under their state_dict names.
         grads None is the data-only form: no token_gemm_wgrad launch; LayerNorm's parameter sums leave the launch that computes its dx and are
-        dropped.  The data launches, and so the returned gradient's bits, are the same in both forms."""
+        dropped.  The data launches, and so the returned gradient's bits, are the same in both forms.
+        attention_grad (a callable): receives (q, k, v, lse, datt, n_query_rows) once datt, the cotangent of the attention output, is formed — the
+        views ops.mhsa_weight_grads / mhsa_relevance_step take.  None (the default): exactly the launches above."""
         B, N, D, dt, a = s.B, s.N, self.embed_dim, self.compute_dtype, blk.attn
         wgrad, grads = grads is not None, ({} if grads is None else grads)
         att_d, act_d, out_d = s.drop                                    # the forward's dropout sites: the masks are recomputed from (p, key), DESIGN §18
@@ -601,6 +671,11 @@ class ViTVAEEncoder(nn.Module):
         if wgrad:
             grads[name + "attn.out_proj.weight"], grads[name + "attn.out_proj.bias"] = ops.token_gemm_wgrad(G, s.att.view(-1, D))
         qkv, y = s.qkv, s.y
+        if attention_grad is not None:
+            if s.cls_only:
+                attention_grad(s.q, qkv[:, :, :D], qkv[:, :, D:], s.lse, datt.view(B, 1, D), 1)
+            else:
+                attention_grad(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.lse, datt.view(B, N, D), N)
         dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)       # dense, also where qkv is a column panel (_cls_rows_step)
         if not s.cls_only:
             ops.mhsa_bwd(qkv[:, :, :D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:], s.att, s.lse, datt.view(B, N, D), dqkv[:, :, :D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:],
@@ -624,12 +699,14 @@ class ViTVAEEncoder(nn.Module):
         return Gin
 
     @torch.no_grad()
-    def _walk_backward(self, saved, g, collect=None, params=True, stem_params=None, image=None):
+    def _walk_backward(self, saved, g, collect=None, params=True, stem_params=None, image=None, attention_grad=None):
         """{state_dict name: gradient} of pos_embedding, cls_token, transformer.* and to_latent.*, plus `dstem`, from the cotangent g [B, 256] of the cls features;
         when the walk kept the stem's activations, of stem.* too (then `dstem` is there only with a collect dict, which also receives `stem_g`).
         DESIGN §21: params=False is the data-only form — every block in its data-only form, no parameter's gradient in the result, the same `dstem`.
         stem_params (default: whether the walk kept the stem) says the same for the stem's 20 tensors; image (a dict, needs a walk that kept the stem): the
-        result also holds `dx`, see _stem_backward."""
+        result also holds `dx`, see _stem_backward.
+        attention_grad (a callable; attention_gradients / attention_relevance): called as attention_grad(i, q, k, v, lse, datt, n_query_rows) in
+        block i's backward, from the last block to the first, see _block_backward.  None (the default): exactly the launches above."""
         steps, cls, stem_dtype, B, N, kept = saved[:6]
         D, grads = self.embed_dim, {}
         stem_params = bool(params) and ((kept is not None) if stem_params is None else bool(stem_params))
@@ -638,7 +715,8 @@ class ViTVAEEncoder(nn.Module):
         G, grads["to_latent.weight"], grads["to_latent.bias"] = ops.layernorm256_bwd(g, cls, self.to_latent.weight, self.to_latent.eps)
         for i in reversed(range(self.depth)):
             s = steps[i] if (steps[i].cls_only or i < self.depth - 1) else self._cls_rows_step(steps[i])
-            G = self._block_backward(self.transformer[i], f"transformer.{i}.", s, G, grads if params else None)
+            G = self._block_backward(self.transformer[i], f"transformer.{i}.", s, G, grads if params else None,
+                                     None if attention_grad is None else (lambda *a, i=i: attention_grad(i, *a)))
         if kept is None or not (stem_params or image is not None):
             dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
         else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
@@ -1110,3 +1188,14 @@ def extract_vit_saliency(model, loader, device, **kw):
     enc = getattr(model, "backbone", model)
     maps = [model.saliency(batch["x"].to(device), **kw) for batch in loader]
     return torch.cat(maps, dim=0).cpu().numpy() if maps else np.zeros((0, enc.img_height, enc.img_width), dtype=np.float32)
+
+
+@torch.no_grad()
+def extract_vit_relevance(model, loader, device, **kw):
+    """attention_relevance(batch["x"], **kw) of every batch of the loader (extract_vit_attention's protocol), stacked as one numpy array [n, grid_h, grid_w]
+    ([n, N] with as_grid=False); model: a ViTVAE / ViTVAEEncoder, or a CausalViTVAE (its backbone's map).  One host copy is made at the end."""
+    model.eval()
+    enc = getattr(model, "backbone", model)
+    maps = [model.attention_relevance(batch["x"].to(device), **kw) for batch in loader]
+    empty = (0, enc.grid_h, enc.grid_w) if kw.get("as_grid", True) else (0, enc.num_patches + 1)
+    return torch.cat(maps, dim=0).cpu().numpy() if maps else np.zeros(empty, dtype=np.float32)

@@ -479,6 +479,43 @@ int cvae_mhsa_rollout_step(const void* q, const void* k, const float* lse, const
                            int64_t q_batch_stride, int64_t k_batch_stride, int64_t B, int64_t n_tokens, int64_t n_query_rows, float residual, int dtype,
                            void* stream);
 
+/* ---- ViT-VAE encoder, attention gradients and gradient-weighted attention relevance (csrc/vit_attention_grad_probe.inc) ------------
+ * The counterpart of the two entries above on the backward's side: the gradient of a target with respect to the attention probabilities, which never exist in
+ * memory, and one step of the relevance rule of Chefer, Gur & Wolf (ICCV 2021, "Generic Attention-model Explainability ...", self-attention).  Per block, for
+ * batch row b and head h of 8 (head h reads feature columns 32 h .. 32 h + 31):
+ *   P[b][h][i][j]  = 2^(q_i . k_j  log2(e) / sqrt(32) - lse[b][h][i])      as above: recomputed, never stored
+ *   dO             = the cotangent of the attention output [B][n_query_rows][256] (before out_proj), in the compute dtype
+ *   gA[b][h][i][j] = sum_{d < 32} dO[b][i][32 h + d] V[b][j][32 h + d]      the gradient with respect to the probabilities taken as a free variable (out = A V):
+ *                                                                          what a hook on the softmax output receives; it needs neither q, k nor lse
+ *   Abar[b][i][j]  = 0.125 ((((t_0 + t_1) + t_2) + ...) + t_7),  t_h = max(0, gA[b][h][i][j] P[b][h][i][j])       heads summed in order 0..7, plain fp32 adds
+ *   relevance:       R = I, then R <- R + Abar_l R for l = first .. last block; the map is R's CLS row.  As a row vector: r = e_cls, then for l = last .. first
+ *                    r <- r + r Abar_l — the left-multiplication of the rollout, so no N x N object is formed.  In the last block only the CLS output reaches a
+ *                    target, so only row 0 of its Abar is non-zero (exactly): that step runs with n_query_rows = 1 on the CLS-only record.
+ * dout is dense [B][n_query_rows][256] as cvae_mhsa_bwd takes it; q, k, v are views as cvae_mhsa_fwd takes them (row and batch strides in elements); dtype
+ * CVAE_F32 (v_mfma_f32_32x32x2_f32) or CVAE_BF16 (bf16 MFMA) for q, k, v and dout alike; everything after the two products is fp32.
+ * Contract, as above: enqueue-only; every check precedes the first launch; B == 0 is CVAE_OK (nothing is launched); no atomics and no "last workgroup"
+ * ticket; every sum in an order that depends on n_tokens and n_query_rows only, so a batch row's bits do not depend on B or on the run, and
+ * n_query_rows = 1 gives the bits that row 0 contributes in a full call.  1 <= n_query_rows <= n_tokens <= 2^24, 0 <= B <= 65535, strides at least 256 and
+ * batch strides non-negative (else CVAE_E_BADSHAPE); an unknown dtype code: CVAE_E_DTYPE; a null pointer: CVAE_E_NULLPTR; q, k, v, dout not 16-byte aligned
+ * or a stride not a multiple of 16 bytes, lse / r / out / workspace not 4-byte aligned: CVAE_E_UNSUPPORTED.
+ *   cvae_mhsa_weight_grads    w fp32 [B][8][n_query_rows][n_tokens] = gA.  Rows of w are dense (n_tokens floats), stored 4 bytes at a time; only w's base
+ *                             (16-byte aligned, else CVAE_E_UNSUPPORTED) and w_batch_stride (in floats, at least 8 n_query_rows n_tokens, else
+ *                             CVAE_E_BADSHAPE) are constrained.  One launch, grid (ceil(n_tokens / 128), 8, B).
+ *   cvae_mhsa_relevance_step  out[b][j] = r[b][j] + sum_{i < n_query_rows} r[b][i] Abar[b][i][j];  r, out fp32 [B][n_tokens], contiguous; out == r (any overlap)
+ *                             is refused: CVAE_E_UNSUPPORTED.  The query rows are split into S = ceil(n_query_rows / 64) chunks (a function of n_query_rows
+ *                             alone), one workgroup per (128 keys, chunk, batch row).  Within a chunk the sum is one fp32 chain per key and lane half,
+ *                             col += r[i] * (Abar[i][j]) in query order (queries 8 g + 0..3 and 8 g + 4..7 of every 32), the halves added once.  S > 1: the
+ *                             chunk sums go to `workspace` as fp32 [B][S][n_tokens] (cvae_mhsa_relevance_step_workspace_bytes; CVAE_E_WORKSPACE below
+ *                             it, CVAE_E_NULLPTR without one) and a second small launch computes out = r + (((c_0 + c_1) + ...) + c_{S-1}).  S == 1 (at most
+ *                             64 query rows: the CLS-only last block): one launch writes out = r + c_0 itself, no workspace is read (0 bytes asked).
+ *                             S > 65535: CVAE_E_UNSUPPORTED.  dout == 0 returns r bit for bit. */
+int cvae_mhsa_weight_grads(const void* dout, const void* v, float* w, int64_t v_stride, int64_t v_batch_stride, int64_t w_batch_stride, int64_t B,
+                           int64_t n_tokens, int64_t n_query_rows, int dtype, void* stream);
+size_t cvae_mhsa_relevance_step_workspace_bytes(int64_t B, int64_t n_tokens, int64_t n_query_rows);
+int cvae_mhsa_relevance_step(const void* q, const void* k, const void* v, const float* lse, const void* dout, const float* r, float* out, int64_t q_stride,
+                             int64_t k_stride, int64_t v_stride, int64_t q_batch_stride, int64_t k_batch_stride, int64_t v_batch_stride, int64_t B,
+                             int64_t n_tokens, int64_t n_query_rows, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- ViT-VAE encoder, Grad-CAM on the stem output (csrc/vit_gradcam.inc) ---------------------------------------------------------
  * The arithmetic of the reference's GradCAM.__call__ (mnist_test/02_mechanism_analysis/analyze_gradcam.py:56-73) without its resize, on the channels-last stem
  * output A and its gradient dA, both [B][n][256] contiguous in `dtype` (CVAE_F32 or CVAE_BF16); cam fp32 [B][n]:

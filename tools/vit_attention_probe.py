@@ -1,12 +1,14 @@
-"""What looking inside the encoder costs (DESIGN §20): ViTVAE at 768 x 1280, depth 6, B = 1 and 8, fp32 and bf16, printed as ONE JSON line.
-Three calls on one model and one batch, interleaved in one process after warm-up:
+"""What looking inside the encoder costs (DESIGN §20, §22): ViTVAE at 768 x 1280, depth 6, B = 1 and 8, fp32 and bf16, printed as ONE JSON line.
+Five calls on one model and one batch, interleaved in one process after warm-up:
   cls_features(x) ........... the encoder itself, the yardstick
   attention_weights(x) ...... the CLS rows of every block, head-averaged: the same walk with lse saved + one mhsa_weights launch per block
   attention_rollout(x) ...... the same walk + one mhsa_rollout_step launch per block
+  gradcam(x) ................ the saving walk + the data-only backward down to dstem + one Grad-CAM launch: the backward attention_relevance rides on
+  attention_relevance(x) .... that walk and backward + one mhsa_relevance_step (kernel and, past 64 query rows, its finish launch) per block
 A round is `--steps` calls of one of them issued back to back and ended by ONE synchronize; the figure is the host wall time over the round per call, the
 median over `--rounds` rounds (minimum and maximum next to it).
-`--only NAME` (cls_features / attention_weights / attention_rollout) runs a few calls of that one in bf16 at B = 8: the shape for a separate
-`rocprofv3 --kernel-trace --stats` run."""
+`--only NAME [NAME ...]` (of the five) runs a few calls of those, alternating, in bf16 at B = 8: the shape for a separate
+`rocprofv3 --kernel-trace --stats` run; two names put both calls' kernels into one trace."""
 import argparse
 import json
 import os
@@ -22,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import vit_reference as vr                            # noqa: E402
 from causal_vae_amd.vit import ViTVAE                 # noqa: E402
 
-CALLS = ("cls_features", "attention_weights", "attention_rollout")
+CALLS = ("cls_features", "attention_weights", "attention_rollout", "gradcam", "attention_relevance")
 
 
 def main():
@@ -30,7 +32,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", choices=CALLS)
+    ap.add_argument("--only", choices=CALLS, nargs="+")
     a = ap.parse_args()
     torch.manual_seed(42)
     model = ViTVAE()
@@ -40,7 +42,8 @@ def main():
         model.set_compute_dtype(torch.bfloat16)
         x = vr.vit_inputs(8, 768, 1280, 1302).cuda()
         for _ in range(a.warmup + a.steps):
-            getattr(model, a.only)(x)
+            for name in a.only:
+                getattr(model, name)(x)
         torch.cuda.synchronize()
         return
     out = {"probe": "vit_attention", "img": [768, 1280], "depth": model.depth, "steps_per_round": a.steps, "rounds": a.rounds,
