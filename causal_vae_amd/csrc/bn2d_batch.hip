@@ -1,0 +1,184 @@
+// bn2d_batch.hip — batch-statistics BatchNorm2d (+ the activation behind it) on a channels-last tensor [P = B H W][C], forward only, for the ViT-VAE stem's
+// training walk.  The tensor is read TWICE (cvae_bn2d_fwd(training=1) in vessel2d.hip reads it three times in five launches):
+//   moments  each workgroup reads ONE contiguous chunk of rows once and leaves (mean, M2) of the chunk per channel, from SHIFTED sums
+//            s1 = sum (y - K), s2 = sum (y - K)^2 with K = the chunk's first row: mean = K + s1 / n, M2 = s2 - s1^2 / n.  K lies inside the data, so the
+//            subtraction in M2 cancels a few times the chunk's variance at most, never the square of its mean (E[y^2] - E[y]^2 would).
+//   finish   merges the chunks IN INDEX ORDER with the pairwise update (Chan et al.): n = na + nb, d = mb - ma, mean = ma + d nb / n,
+//            M2 = M2a + M2b + d^2 na nb / n; writes mean, rstd = 1 / sqrt(M2 / P + eps) and, when given, the running statistics (unbiased variance).
+//   apply    a = act((y - mean) rstd gamma + beta): one read of y, one write of a.
+// No float atomics and no "last workgroup": the chunking depends on P alone (never on the device), every sum has one fixed order, so the bits are the same
+// from run to run and from device to device.  The backward is cvae_bn2d_bwd (vessel2d.hip) on (x = y, dy, y = a, gamma, mean, rstd).
+#include "common.h"
+
+namespace {
+
+constexpr int BNB_ROWS = 256;          // a chunk is a multiple of this many rows ..
+constexpr int BNB_MAX_PARTS = 1024;    // .. the smallest that leaves at most this many chunks
+constexpr int BNB_SEGS = 16;           // finish: a channel's chunks are merged in BNB_SEGS consecutive runs (one thread each), then the runs in order
+
+int64_t bnb_chunk(int64_t P) {
+    const int64_t unit = (int64_t)BNB_ROWS * BNB_MAX_PARTS;
+    return BNB_ROWS * ((P + unit - 1) / unit);
+}
+int64_t bnb_parts(int64_t P) {
+    const int64_t chunk = bnb_chunk(P);
+    return (P + chunk - 1) / chunk;
+}
+
+// A lane owns 8 consecutive channels (16 bytes of bf16, 32 of fp32); the 256 threads are R = 256 / (C / 8) row groups of C / 8 lanes (threads past R groups
+// idle: C / 8 need not divide 256).  Row group rg reads rows p0 + rg, p0 + rg + R, ... of the chunk, four rows in flight.  `part` row 2 g = the chunk's
+// mean, row 2 g + 1 = its M2; its count follows from g (bnb_chunk).
+template <typename T>
+__global__ __launch_bounds__(256) void bn2d_batch_moments_kernel(const T* __restrict__ y, float* __restrict__ part, int64_t P, int C, int64_t chunk) {
+    __shared__ float red[2][256][8 + 1];
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = (p0 + chunk < P) ? p0 + chunk : P;
+    float K[8], s1[8], s2[8];
+    load_f32<8>(y + p0 * C + c0, K);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    if (rg < R) {
+        int64_t p = p0 + rg;
+        for (; p + 3 * (int64_t)R < p1; p += 4 * (int64_t)R) {
+            float v[4][8];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) load_f32<8>(y + (p + (int64_t)u * R) * C + c0, v[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float d = v[u][e] - K[e]; s1[e] += d; s2[e] += d * d; }
+        }
+        for (; p < p1; p += R) {
+            float v[8];
+            load_f32<8>(y + p * C + c0, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float d = v[e] - K[e]; s1[e] += d; s2[e] += d * d; }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[0][t][e] = s1[e]; red[1][t][e] = s2[e]; }
+    __syncthreads();
+    // thread c < C adds its channel's R row-group sums in group order: they share the shift K, so they add as they are
+    const float n = (float)(p1 - p0);
+    for (int c = t; c < C; c += 256) {
+        const int l = c >> 3, e = c & 7;
+        float a1 = 0.f, a2 = 0.f;
+        for (int q = 0; q < R; ++q) { a1 += red[0][q * lanes + l][e]; a2 += red[1][q * lanes + l][e]; }
+        const float m1 = a1 / n;
+        part[((size_t)blockIdx.x * 2) * C + c] = to_f32(y[p0 * C + c]) + m1;
+        part[((size_t)blockIdx.x * 2 + 1) * C + c] = fmaxf(a2 - a1 * m1, 0.f);
+    }
+}
+
+// (na, ma, M2a) <- (na, ma, M2a) merged with (nb, mb, M2b); an empty side leaves the other as it is
+__device__ __forceinline__ void bnb_merge(float& na, float& ma, float& M2a, float nb, float mb, float M2b) {
+    if (nb == 0.f) return;
+    if (na == 0.f) { na = nb; ma = mb; M2a = M2b; return; }
+    const float n = na + nb, d = mb - ma, f = nb / n;
+    ma += d * f;
+    M2a += M2b + d * d * (na * f);
+    na = n;
+}
+// A block serves 16 channels: thread (s, cc) merges run s of channel cc's chunks (ceil(G / BNB_SEGS) consecutive ones) in index order, then thread (0, cc)
+// merges the BNB_SEGS runs in order.  The order is a function of G alone.
+__global__ __launch_bounds__(256) void bn2d_batch_finish_kernel(const float* __restrict__ part, int G, float* __restrict__ mean, float* __restrict__ rstd,
+                                                                 float* __restrict__ running_mean, float* __restrict__ running_var, int64_t P, int C, int64_t chunk,
+                                                                 float eps, float momentum) {
+    __shared__ float sn[BNB_SEGS][16], sm[BNB_SEGS][16], sq[BNB_SEGS][16];
+    const int cc = threadIdx.x & 15, s = threadIdx.x >> 4, c = blockIdx.x * 16 + cc;
+    const int per = (G + BNB_SEGS - 1) / BNB_SEGS, g0 = s * per, g1 = (g0 + per < G) ? g0 + per : G;
+    float n = 0.f, m = 0.f, M2 = 0.f;
+    if (c < C)
+        for (int g = g0; g < g1; ++g) {
+            const int64_t r0 = (int64_t)g * chunk, r1 = (r0 + chunk < P) ? r0 + chunk : P;
+            bnb_merge(n, m, M2, (float)(r1 - r0), part[((size_t)g * 2) * C + c], part[((size_t)g * 2 + 1) * C + c]);
+        }
+    sn[s][cc] = n; sm[s][cc] = m; sq[s][cc] = M2;
+    __syncthreads();
+    if (s != 0 || c >= C) return;
+    for (int q = 1; q < BNB_SEGS; ++q) bnb_merge(n, m, M2, sn[q][cc], sm[q][cc], sq[q][cc]);
+    const float fP = (float)P, var = M2 / fP;
+    mean[c] = m;
+    rstd[c] = 1.f / sqrtf(var + eps);
+    if (running_mean) {
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (fP / (fP - 1.f));
+    }
+}
+
+// the moments kernel's thread layout; a row group keeps its 8 channels' (mean, rstd gamma, beta) in registers and walks rows with the grid's stride
+template <typename T, int EPI>
+__global__ __launch_bounds__(256) void bn2d_batch_apply_kernel(const T* __restrict__ y, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ a, int64_t P, int C,
+                                                                int act) {
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    if (rg >= R) return;
+    float mu[8], k[8], b[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; k[e] = rstd[c0 + e] * gamma[c0 + e]; b[e] = beta[c0 + e]; }
+    const int64_t step = (int64_t)gridDim.x * R;
+    int64_t p = (int64_t)blockIdx.x * R + rg;
+    for (; p + 3 * step < P; p += 4 * step) {
+        float v[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) load_f32<8>(y + (p + u * step) * C + c0, v[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[u][e] = apply_act_t<EPI>((v[u][e] - mu[e]) * k[e] + b[e], act);
+            store_from_f32<8>(a + (p + u * step) * C + c0, v[u]);
+        }
+    }
+    for (; p < P; p += step) {
+        float v[8];
+        load_f32<8>(y + p * C + c0, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = apply_act_t<EPI>((v[e] - mu[e]) * k[e] + b[e], act);
+        store_from_f32<8>(a + p * C + c0, v);
+    }
+}
+
+// the three launches; the entry point has checked everything but the dtype code, which with_dtype refuses before the first launch
+int bn2d_batch_launch(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean, float* running_var, int64_t P,
+                      int C, float momentum, float eps, int act, int dtype, float* part, hipStream_t st) {
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        const int64_t chunk = bnb_chunk(P);
+        const int G = (int)bnb_parts(P), R = 256 / (C >> 3);
+        hipLaunchKernelGGL(bn2d_batch_moments_kernel<T>, dim3((unsigned)G), dim3(256), 0, st, (const T*)y, part, P, C, chunk);
+        hipLaunchKernelGGL(bn2d_batch_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float*)part, G, mean, rstd, running_mean, running_var,
+                           P, C, chunk, eps, momentum);
+        return with_epi(act, [&](auto epi) {
+            hipLaunchKernelGGL((bn2d_batch_apply_kernel<T, decltype(epi)::value>), dim3(cvae_grid_1d((P + R - 1) / R, 4, 2048)), dim3(256), 0, st, (const T*)y,
+                               (const float*)mean, (const float*)rstd, gamma, beta, (T*)a, P, C, act);
+            return launch_rc();
+        });
+    });
+}
+
+bool bnb_shape_ok(int64_t P, int64_t C) { return P >= 2 && P <= ((int64_t)1 << 40) && C >= 8 && C % 8 == 0 && C <= 2048; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+}  // namespace
+
+extern "C" size_t cvae_bn2d_batch_workspace_bytes(int64_t P, int64_t C) {
+    if (!bnb_shape_ok(P, C)) return 0;
+    // monotone in P: the chunk count itself drops where the chunk grows (1024 chunks of 256 rows at P = 262144, 513 of 512 one row later)
+    const int64_t units = (P + BNB_ROWS - 1) / BNB_ROWS;
+    return (size_t)2 * (units < BNB_MAX_PARTS ? units : BNB_MAX_PARTS) * C * sizeof(float);
+}
+extern "C" int cvae_bn2d_batch_fwd(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
+                                   float* running_var, int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    if (!bnb_shape_ok(P, C)) return CVAE_E_BADSHAPE;
+    if (!(momentum >= 0.f && momentum <= 1.f) || !(eps > 0.f)) return CVAE_E_BADSHAPE;       // written so that a NaN is refused too
+    if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_UNSUPPORTED;
+    if (!y || !gamma || !beta || !a || !mean || !rstd || !workspace || (running_mean == nullptr) != (running_var == nullptr)) return CVAE_E_NULLPTR;
+    if (!aligned16(y) || !aligned16(a) || !aligned4(gamma) || !aligned4(beta) || !aligned4(mean) || !aligned4(rstd) || !aligned4(running_mean) ||
+        !aligned4(running_var) || !aligned4(workspace))
+        return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_bn2d_batch_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
+    return bn2d_batch_launch(y, gamma, beta, a, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, act, dtype, (float*)workspace, (hipStream_t)stream);
+}

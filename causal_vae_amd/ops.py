@@ -1840,6 +1840,60 @@ class BatchNorm2dAct(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None
 
 
+def _bn2d_rows(what, t, **like):
+    """(P, C) of the channels-last tensor t as the BatchNorm2d entries address it; every tensor of `like` has t's shape, dtype and device."""
+    if t.dim() < 2 or not t.is_contiguous() or t.dtype not in (torch.float32, torch.bfloat16) or t.shape[-1] % 8 or t.numel() == 0:
+        raise L.CvaeError(f"{what}: a contiguous channels-last [.., C] fp32 or bf16 tensor with C % 8 == 0 expected, got {tuple(t.shape)} {t.dtype}")
+    for k, v in like.items():
+        if tuple(v.shape) != tuple(t.shape) or v.dtype != t.dtype or v.device != t.device or not v.is_contiguous():
+            raise L.CvaeError(f"{what}: {k} must be a contiguous {tuple(t.shape)} {t.dtype} tensor on {t.device}, got {tuple(v.shape)} {v.dtype} on {v.device}")
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def bn2d_batch_fwd(y, bn, act):
+    """(a, mean, rstd) = nn.BatchNorm2d `bn` on the statistics of THIS batch, then the activation `act` (None / "relu" / "sigmoid" / "leaky02" / "leaky001"), on
+    the channels-last conv output y [.., C] (fp32 or bf16): cvae_bn2d_batch_fwd (csrc/bn2d_batch.hip, DESIGN §23), which reads y twice.  a has y's shape and dtype;
+    mean and rstd (fp32 [C]: the batch mean and 1 / sqrt(biased variance + eps)) are what bn2d_bwd reads.  With bn.track_running_stats its running_mean and
+    running_var are updated in place as torch does in training mode (momentum, unbiased variance) and num_batches_tracked advances by one with an in-place device
+    add, so a captured step replays it.  The module's own mode is not consulted and not changed.  momentum=None (torch's cumulative average): CvaeError."""
+    L.require_gpu(y, bn.weight, bn.bias)
+    _forward_only("bn2d_batch_fwd", y, bn.weight, bn.bias)
+    P, Cc = _bn2d_rows("bn2d_batch_fwd", y)
+    if bn.weight is None or bn.bias is None or bn.num_features != Cc or bn.weight.dtype != torch.float32:
+        raise L.CvaeError(f"bn2d_batch_fwd: an affine fp32 BatchNorm2d over {Cc} channels expected, got num_features={bn.num_features}, affine={bn.weight is not None}")
+    if bn.momentum is None:
+        raise L.CvaeError("bn2d_batch_fwd: momentum=None (the cumulative moving average) is not implemented; give the BatchNorm2d a momentum in [0, 1]")
+    track = bool(bn.track_running_stats) and bn.running_mean is not None
+    if track and (bn.running_mean.dtype != torch.float32 or bn.running_var.dtype != torch.float32):
+        raise L.CvaeError("bn2d_batch_fwd: fp32 running statistics expected")
+    a = torch.empty_like(y)
+    mean, rstd = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+    _t, wp, wb = _scratch(lib.cvae_bn2d_batch_workspace_bytes(P, Cc), y)
+    check(L.timed(f"bn2d_batch_fwd P{P} C{Cc}", lib.cvae_bn2d_batch_fwd, ptr(y), ptr(bn.weight), ptr(bn.bias), ptr(a), ptr(mean), ptr(rstd),
+                  ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None, P, Cc, float(bn.momentum), float(bn.eps), L.act_code(act),
+                  L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_batch_fwd")
+    if track and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return a, mean, rstd
+
+
+def bn2d_bwd(y, g, a, weight, mean, rstd, act):
+    """(g_y, dgamma, dbeta) of a = act((y - mean) rstd weight + bias) with batch statistics (cvae_bn2d_bwd, csrc/vessel2d.hip): y the normalisation's input, g the
+    gradient of a, a the forward's output (for act'), mean / rstd as bn2d_batch_fwd (or BatchNorm2dAct's training forward) left them."""
+    L.require_gpu(y, g, a, weight, mean, rstd)
+    _forward_only("bn2d_bwd", y, g, a, weight, mean, rstd)
+    P, Cc = _bn2d_rows("bn2d_bwd", y, g=g, a=a)
+    for k, v in (("weight", weight), ("mean", mean), ("rstd", rstd)):
+        if tuple(v.shape) != (Cc,) or v.dtype != torch.float32 or not v.is_contiguous():
+            raise L.CvaeError(f"bn2d_bwd: {k} must be a contiguous fp32 [{Cc}] vector, got {tuple(v.shape)} {v.dtype}")
+    gy = torch.empty_like(y)
+    dw, db = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+    _t, wp, wb = _scratch(lib.cvae_bn2d_workspace_bytes(P, Cc), y)
+    check(L.timed(f"bn2d_bwd P{P} C{Cc}", lib.cvae_bn2d_bwd, ptr(y), ptr(g), ptr(a), ptr(weight), ptr(mean), ptr(rstd), ptr(gy), ptr(dw), ptr(db), P, Cc,
+                  L.act_code(act), L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_bwd")
+    return gy, dw, db
+
+
 class Clamp(torch.autograd.Function):
     """torch.clamp(x, min, max) with its pass-through gradient mask (vessel_analysis/00_core/models.py:148-149,156)."""
 

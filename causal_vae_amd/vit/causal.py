@@ -100,7 +100,7 @@ class CausalViTVAE(nn.Module):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self, decoder=False, transformer=False, stem=False, dropout=False):
+    def train_adapters(self, decoder=False, transformer=False, stem=False, dropout=False, stem_batch_stats=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
         heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
         a default call after a decoder=True one switches the decoder's gradients off again).
@@ -111,9 +111,13 @@ class CausalViTVAE(nn.Module):
         reference's do under train() (backbone.train_transformer(dropout=True)); default: no dropout.  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
         backbone's (mu, log_var), so no gradient ever reaches them.  Returns head plus transformer parameters (plus the decoder's with decoder=True).
         stem=True (needs transformer=True): the backbone's conv stem learns too (backbone.train_stem(): eval-mode BatchNorm2d on its running statistics;
-        DESIGN §17), the whole backbone is then fine-tuned as vessel_analysis/01_train/train.py does; its parameters are returned too."""
+        DESIGN §17), the whole backbone is then fine-tuned as vessel_analysis/01_train/train.py does; its parameters are returned too.  stem_batch_stats=True
+        (needs stem=True): the stem's BatchNorm2d layers normalise with batch statistics in the training forward and update their running statistics, as that
+        script's .train() does (backbone.train_stem(batch_stats=True); the backbone module itself stays in eval mode)."""
         if stem and not transformer:
             raise CvaeError("CausalViTVAE.train_adapters: stem=True needs transformer=True (the stem's gradient arrives through the transformer)")
+        if stem_batch_stats and not stem:
+            raise CvaeError("CausalViTVAE.train_adapters: stem_batch_stats=True needs stem=True (a frozen stem runs the fold on its running statistics)")
         if dropout and not transformer:
             raise CvaeError("CausalViTVAE.train_adapters: dropout=True needs transformer=True (the dropout sites are the transformer blocks'; a frozen "
                             "transformer runs its inference form)")
@@ -125,7 +129,7 @@ class CausalViTVAE(nn.Module):
         self.train()
         params = self.head_parameters()
         if stem:
-            params += self.backbone.train_stem()
+            params += self.backbone.train_stem(batch_stats=stem_batch_stats)
         if transformer:
             params += self.backbone.train_transformer(heads=False, dropout=dropout)
         if decoder:

@@ -30,7 +30,8 @@ decode's launches (the fold also writes the backward matrices) and keeps five ga
 cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
 Training, all in eval mode (BatchNorm2d on its running statistics; dropout only where train_transformer(dropout=True) asks for it): train_decoder, train_transformer (§16) and train_stem (§17: the
 stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then per layer cvae_conv_wgrad and cvae_conv_down_bwd_data with the LeakyReLU
-derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
+derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch; train_stem(batch_stats=True), DESIGN §23: the stem alone on
+batch statistics, the module still in eval mode — per layer the raw conv, cvae_bn2d_batch_fwd, and cvae_bn2d_bwd on the way back); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
 are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
 The gradient with respect to the IMAGE: cls_features_vjp / encode_vjp (explicit, no graph), x.grad after cls_features_with_grad / encode_with_grad /
 forward_train of an x that asks, saliency (plain and integrated gradients) and gradcam.  They share a data-only form of the backward (_walk_backward(params=False):
@@ -52,7 +53,9 @@ from .._lib import CvaeError, require_gpu
 STEM_CHANNELS = (32, 64, 128, 256, 256)
 # What ViTVAEEncoder._walk(save=True) keeps for _walk_backward.
 # _StemKept (only when the stem trains): x (the image as the first conv reads it: its weight-gradient operand), ys (the five layer outputs: each the next
-# layer's input, its weight-gradient operand and its gate), k4 (the folded k4 weights, for the data gradients).
+# layer's input, its weight-gradient operand and its gate), k4 (the folded k4 weights, for the data gradients).  The batch-statistics walk (train_stem(batch_stats=
+# True)) fills the rest: ys are then the BatchNorm + LeakyReLU outputs a_j, k4 the RAW k4 weights (the k3 -> k4 zero-embedding, no scale), pre the five raw
+# conv outputs y_j, mean / rstd each layer's batch statistics as cvae_bn2d_bwd reads them; pre is None in the eval-mode (folded) walk, which is how the backward tells.
 # _BlockStep, one per transformer block: X (the block's input rows [B N, 256], norm1's input), y (norm1's output: the in-projection's operand), qkv (the packed
 # in-projection output; k and v alone [B, N, 512] in a CLS-only block), q (the CLS-only block's one query row per sample, else None), att / lse (attention's
 # output and row statistic), X1 (the stream after attention: norm2's input), y2 (norm2's output), pre / hid (the MLP's pre-activation and its GELU), B, N,
@@ -61,7 +64,7 @@ STEM_CHANNELS = (32, 64, 128, 256, 256)
 # the DROPPED GELU output, att the dropped attention's; the masks themselves are not kept, the backward recomputes them).
 # _Walk: steps (the _BlockSteps in forward order), cls (to_latent's input [B, 256]), stem_dtype (the dtype dstem is returned in), B, N, stem (_StemKept or None),
 # stem_out (the stem's channels-last output, what Grad-CAM weighs with dstem).
-_StemKept = namedtuple("_StemKept", "x ys k4")
+_StemKept = namedtuple("_StemKept", "x ys k4 pre mean rstd", defaults=(None, None, None))
 _BlockStep = namedtuple("_BlockStep", "X y qkv q att lse X1 y2 pre hid B N cls_only drop")
 _NO_DROP = (None, None, None)
 _Walk = namedtuple("_Walk", "steps cls stem_dtype B N stem stem_out")
@@ -129,14 +132,25 @@ class ViTVAEEncoder(nn.Module):
         mods = list(self.stem)
         return [(mods[i].weight, ops.FOLD_CONV_K3S2, mods[i].bias, mods[i + 1]) for i in range(0, len(mods), 3)]
 
-    def _stem_cl(self, x, keep=None):
-        """keep (a dict, the stem's backward): receives _StemKept's fields `x`, `ys` and `k4`.  The launches do not depend on it."""
-        folded = ops.fold_bn_conv(self._stem_fold_table())
+    def _stem_cl(self, x, keep=None, batch_stats=False):
+        """keep (a dict, the stem's backward): receives _StemKept's fields `x`, `ys` and `k4`.  The launches do not depend on it.
+        batch_stats (the training walk after train_stem(batch_stats=True)): no fold — per layer the conv on the RAW weight and bias without an
+        activation (the fold's launch with no BatchNorm: the k3 -> k4 zero-embedding at scale 1; the bias cancels in the normalised value but running_mean
+        must contain it), then ops.bn2d_batch_fwd: this batch's statistics, LeakyReLU(0.01), the running statistics and counters updated in place.  keep then
+        also receives `pre`, `mean` and `rstd`."""
+        table = self._stem_fold_table()
+        folded = ops.fold_bn_conv([(w, kind, b, None) for w, kind, b, _bn in table] if batch_stats else table)
         h, first_dtype = hl._image_cl(x, self.compute_dtype)
         if keep is not None:
             keep["x"], keep["ys"], keep["k4"] = h, [], [w for w, _b in folded]
+            if batch_stats:
+                keep["pre"], keep["mean"], keep["rstd"] = [], [], []
         for j, (w, b) in enumerate(folded):
-            h = ops.ConvDown.apply(h, w, b, 2, "leaky001", False, False, None, first_dtype if j == 0 else None)
+            h = ops.ConvDown.apply(h, w, b, 2, None if batch_stats else "leaky001", False, False, None, first_dtype if j == 0 else None)
+            if batch_stats:
+                pre, (h, mean, rstd) = h, ops.bn2d_batch_fwd(h, table[j][3], "leaky001")
+                if keep is not None:
+                    keep["pre"].append(pre), keep["mean"].append(mean), keep["rstd"].append(rstd)
             if keep is not None:
                 keep["ys"].append(h)
         return h                                                        # [B, 1, grid_h, grid_w, 256], compute dtype
@@ -187,7 +201,7 @@ class ViTVAEEncoder(nn.Module):
         return (X2 if cls_only else X2.view(B, N, D)), _BlockStep(X, y, qkv, q, att, lse, X1, y2, pre, hid, B, N, cls_only, drop)
 
     @torch.no_grad()
-    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None, dropout=True, cls_only_last=None):
+    def _walk(self, x, save=False, keep_stem=False, collect=None, attention=None, dropout=True, cls_only_last=None, stem_batch_stats=False):
         """The encoder's launches up to to_latent -> (cls features [B, 256] fp32, saved).  save=False: inference, saved = None.  save=True: every block in its
         saving form and saved = _Walk for _walk_backward; keep_stem (with save): the stem's layer outputs and folded weights travel along (the same launches).
         collect (a dict, for tests): receives `stem` (channels-last stem output), `cls_rows` (the CLS row after every block) and `tokens` (the residual stream
@@ -199,7 +213,11 @@ class ViTVAEEncoder(nn.Module):
         None (the default): exactly the launches above.
         dropout=False (the *_vjp entries and an image that asks for its gradient through frozen parameters): a save=True walk that never drops and
         draws no step, whatever train_transformer() asked for.
-        cls_only_last: whether the last block runs for its CLS row alone (the same CLS row, bit for bit); None (the default): self._cls_only_last_block."""
+        cls_only_last: whether the last block runs for its CLS row alone (the same CLS row, bit for bit); None (the default): self._cls_only_last_block.
+        stem_batch_stats (with save and keep_stem; the training forward after train_stem(batch_stats=True)): the stem normalises with this
+        batch's statistics and updates its running buffers, see _stem_cl.  False (every inference and probe entry): the fold, no buffer changes."""
+        if stem_batch_stats and not (save and keep_stem):
+            raise CvaeError("ViTVAEEncoder._walk: the batch-statistics stem is the training walk's (save=True, keep_stem=True)")
         self._check(x)
         cls_only_last = self._cls_only_last_block if cls_only_last is None else cls_only_last
         drop_step = None
@@ -210,7 +228,7 @@ class ViTVAEEncoder(nn.Module):
             else:
                 drop_step, self.dropout_keys.step = self.dropout_keys.step, self.dropout_keys.step + 1
         kept = {} if keep_stem else None
-        stem = self._stem_cl(x, kept)
+        stem = self._stem_cl(x, kept, stem_batch_stats)
         tokens = ops.vit_tokens(stem, self.cls_token, self.pos_embedding[0])
         if collect is not None:
             collect["stem"], collect["cls_rows"], collect["tokens"] = stem, [], []
@@ -293,6 +311,7 @@ class ViTVAEEncoder(nn.Module):
 
     # ---- training the conv stem (eval mode: BatchNorm2d on its running statistics) -------------------------------------
     _stem_grads = False             # train_stem(): cls_features_with_grad / encode_with_grad accumulate the stem's gradients
+    _stem_batch_stats = False       # train_stem(batch_stats=True): their training forward normalises the stem with batch statistics
 
     def _stem_named(self):
         """(name, parameter) of the 20 stem tensors (conv weight and bias, BatchNorm2d weight and bias per layer) in named_parameters order."""
@@ -302,20 +321,25 @@ class ViTVAEEncoder(nn.Module):
         """requires_grad_(False) on everything train_stem() switched on: the stem is a frozen feature extractor again and its activations are not kept."""
         self.stem.requires_grad_(False)
         self._stem_grads = False
+        self._stem_batch_stats = False
         return self
 
-    def train_stem(self):
+    def train_stem(self, batch_stats=False):
         """The counterpart of freeze_stem(): requires_grad_(True) on the stem's 20 tensors, and cls_features_with_grad / encode_with_grad from now on accumulate
-        their `.grad`.  Returns those parameters in named_parameters order.  The model stays in EVAL mode: BatchNorm2d normalises with its running
-        statistics, which are not updated; its weight and bias learn, and so do the conv weights and biases, through the fold.  (The reference's vae.train() uses
-        batch statistics: the one difference of this path, as in train_decoder().)  Independent of train_transformer(): alone it gives stem gradients only — at
+        their `.grad`.  Returns those parameters in named_parameters order.  The model stays in EVAL mode.  batch_stats=False (default):
+        BatchNorm2d normalises with its running statistics, which are not updated; its weight and bias learn, and so do the conv weights and biases, through
+        the fold.  batch_stats=True: the training forward normalises every stem layer with the statistics of its batch and updates running_mean,
+        running_var and num_batches_tracked, as the reference's vae.train() does — asked for by keyword, as dropout is, not with the module's mode (the module
+        and its BatchNorm2d children stay in eval mode; cls_features, encode and every other inference or probe entry keep the fold on the running statistics
+        and change no buffer).  freeze_stem() clears it.  Independent of train_transformer(): alone it gives stem gradients only — at
         the cost of the whole backward all the same: the gradient reaches the stem through the transformer, and the one backward chain computes the
         transformer's weight gradients on its way and drops them."""
         if self.training:
             raise RuntimeError("ViTVAEEncoder.train_stem: put the model in eval mode first (model.eval()): the stem trains on eval-mode BatchNorm2d "
-                               "(running statistics); batch statistics are not implemented")
+                               "(running statistics), and batch statistics are asked for with batch_stats=True, not with the module's mode")
         self.stem.requires_grad_(True)
         self._stem_grads = True
+        self._stem_batch_stats = bool(batch_stats)
         return [p for _k, p in self._stem_named()]
 
     @torch.no_grad()
@@ -326,7 +350,11 @@ class ViTVAEEncoder(nn.Module):
         fold.  collect: receives `stem_g` = [g_0 .. g_4].
         image (a dict): the result also holds `dx`, the gradient of the image, fp32 [B, 1, H, W]: the last hop is ops.conv_down_image_bwd_data on g_0
         and the first folded weight, with the dict as its keyword arguments (alpha, out, accumulate; {}: the plain form).  params=False is the data-only form: no _conv_wgrad launch and no fold_bn_conv_bwd, the data launches — hence every g_j and dx,
-        bit for bit — are those of the full form."""
+        bit for bit — are those of the full form.
+        A walk that kept batch statistics (kept.pre): g is the gradient of the last ACTIVATION (no gate on the token launch), see
+        _stem_backward_batch_stats."""
+        if kept.pre is not None:
+            return self._stem_backward_batch_stats(kept, g, collect, params, image)
         ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
         g = g.view(ys[-1].shape)
         folded, gs = [None] * len(ys), [None] * len(ys)
@@ -341,6 +369,32 @@ class ViTVAEEncoder(nn.Module):
         grads = {"dx": ops.conv_down_image_bwd_data(g, k4[0], **image)} if image is not None else {}
         if params:
             quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(self._stem_fold_table())])
+            grads.update(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
+        return grads
+
+    @torch.no_grad()
+    def _stem_backward_batch_stats(self, kept, g, collect, params, image):
+        """_stem_backward after the batch-statistics walk.  g: the gradient of the last activation a_4.  Per layer, last to first: ops.bn2d_bwd (cvae_bn2d_bwd on
+        (y_j, g, a_j, gamma, mean, rstd)) turns it into g_y, the gradient of the raw conv output, plus dgamma and dbeta; _conv_wgrad(g_y, a_{j-1}) gives the raw
+        k4 weight's gradient, whose k3 part (the inverse of the zero-embedding) is the 3 x 3 weight's, and the conv bias's — zero in exact arithmetic (the
+        mean is subtracted), computed and returned all the same, as autograd does; conv_down_bwd_data on the raw weight, with no gate, hands the gradient of
+        a_{j-1} down.  collect: `stem_g` = the five g_y.  params=False: the data launches alone (bn2d_bwd's two sums are part of g_y)."""
+        ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
+        bns = [bn for _w, _kind, _b, bn in self._stem_fold_table()]
+        g = g.view(ys[-1].shape)
+        quads, gs = [None] * len(ys), [None] * len(ys)
+        for j in reversed(range(len(ys))):
+            g, dgamma, dbeta = ops.bn2d_bwd(kept.pre[j], g.contiguous(), ys[j], bns[j].weight, kept.mean[j], kept.rstd[j], "leaky001")
+            gs[j] = g
+            if params:
+                dk4, dbias = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
+                quads[j] = (dk4[:, :, :3, :3].contiguous(), dbias, dgamma, dbeta)
+            if j:
+                g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), None, None)
+        if collect is not None:
+            collect["stem_g"] = gs
+        grads = {"dx": ops.conv_down_image_bwd_data(g, k4[0], **image)} if image is not None else {}
+        if params:
             grads.update(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
         return grads
 
@@ -424,9 +478,11 @@ class ViTVAEEncoder(nn.Module):
         to_latent.* (after train_transformer()) and on stem.* (after train_stem(): the five layer outputs are kept; otherwise nothing of the stem is).
         An image that asks (x.requires_grad) is on the graph too and backward fills x.grad, fp32 [B, 1, H, W]: with frozen parameters through the
         data-only backward (no weight-gradient launch; never drops), with live ones through the full backward plus the one image launch.  The forward values are
-        cls_features(x.detach())'s, bit for bit.  When autograd is off or neither a parameter nor x asks, this is cls_features and nothing is saved; a parameter
+        cls_features(x.detach())'s, bit for bit — except after train_stem(batch_stats=True): with a live stem the forward then normalises the stem
+        with this batch's statistics (and moves the running buffers), so it no longer equals cls_features, which keeps the running statistics.  When autograd
+        is off or neither a parameter nor x asks, this is cls_features and nothing is saved; a parameter
         that asks without its train_*() call is an error, not a gradient that silently stays None.
-        collect (a dict, for tests): the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype, and with a live stem `stem_g`, the
+        collect (a dict, for tests): the forward leaves `stem`, the stem's channels-last output as this walk computed it; the backward leaves `dstem`, the gradient of the stem's output [B, n, 256] in its dtype, and with a live stem `stem_g`, the
         gradients of the five pre-activations (`dstem` then costs one more token launch: the stem's backward starts from its gated form)."""
         named, stem = self._transformer_named(heads=False), self._stem_named()
         live_t, live_s = any(p.requires_grad for _k, p in named), any(p.requires_grad for _k, p in stem)
@@ -719,6 +775,9 @@ class ViTVAEEncoder(nn.Module):
                                      None if attention_grad is None else (lambda *a, i=i: attention_grad(i, *a)))
         if kept is None or not (stem_params or image is not None):
             dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
+        elif kept.pre is not None:                                      # batch statistics: the LeakyReLU derivative is cvae_bn2d_bwd's, so no gate
+            dpos, dcls, grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)
+            grads.update(self._stem_backward(kept, grads["dstem"], collect, stem_params, image))
         else:                                                           # the stem's last activation is a LeakyReLU output: its derivative rides on the token launch
             if collect is not None:
                 grads["dstem"] = ops.vit_tokens_bwd(G.view(B, N, D), stem_dtype)[2]
@@ -737,7 +796,10 @@ class _ClsFeaturesWithGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, model, collect, names, *params):
         stem_live, wants_x = any(k.startswith("stem.") for k in names), ctx.needs_input_grad[0]
-        out, saved = model._walk(x.detach() if wants_x else x, save=True, keep_stem=stem_live or wants_x, dropout=bool(params))
+        out, saved = model._walk(x.detach() if wants_x else x, save=True, keep_stem=stem_live or wants_x, dropout=bool(params),
+                                 stem_batch_stats=stem_live and model._stem_batch_stats)
+        if collect is not None:
+            collect["stem"] = saved.stem_out
         ctx.model, ctx.saved, ctx.collect, ctx.names, ctx.stem_live = model, saved, collect, names, stem_live      # activations of this call: private to the node, freed with it
         ctx.save_for_backward(*params)
         ctx.set_materialize_grads(False)
@@ -972,10 +1034,11 @@ class ViTVAE(ViTVAEEncoder):
         return self._decode_backward(saved, grad_image.contiguous())
 
     # ---- training the whole model (eval mode) --------------------------------------------------------------------------
-    def train_all(self, dropout=False):
-        """train_stem() + train_transformer(dropout=dropout) + train_decoder(): every parameter asks for a gradient and forward_train's graph reaches every one of
-        them.  Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae)."""
-        self.train_stem()
+    def train_all(self, dropout=False, stem_batch_stats=False):
+        """train_stem(batch_stats=stem_batch_stats) + train_transformer(dropout=dropout) + train_decoder(): every parameter asks for a gradient and forward_train's
+        graph reaches every one of them.  Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae);
+        stem_batch_stats=True: the stem's BatchNorm2d layers train on batch statistics all the same; the decoder's stay on running statistics."""
+        self.train_stem(batch_stats=stem_batch_stats)
         self.train_transformer(dropout=dropout)
         self.train_decoder()
         return list(self.parameters())
@@ -1079,12 +1142,14 @@ def _check_graph_optimizer(what, optimizer):
                         f"(got {type(optimizer).__name__}" + (" with device_step=False" if isinstance(optimizer, FusedAdam) else "") + ")")
 
 
-def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False, graph=False):
+def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False, graph=False, stem_batch_stats=False):
     """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature plus `dropout` and `graph`: per batch["x"], zero_grad, model.forward_train,
     vit_vae_loss, backward, optimizer.step() (vit_vae_train_step).  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval
     mode, so every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state), and there is no
     dropout unless dropout=True: then the transformer blocks drop as the reference's do under train(), at the modules' rates, with Philox masks
-    (train_transformer(dropout=True); float32 compute dtype).  All parameters learn (model.train_all() is called, so an optimizer built over
+    (train_transformer(dropout=True); float32 compute dtype).  stem_batch_stats=True: the conv stem's five BatchNorm2d layers normalise with
+    batch statistics and update their running statistics, as the reference's do (train_stem(batch_stats=True)); the decoder's stay on running
+    statistics.  All parameters learn (model.train_all() is called, so an optimizer built over
     model.parameters() fits).  Returns the per-epoch mean losses as a list of floats (sample-weighted, read from the device once per epoch).
     graph=True (needs FusedAdam(device_step=True), else CvaeError): the step is captured once, from the first batch, as one HIP graph (GraphedViTTrainStep,
     DESIGN §19) and replayed for every batch of that shape; a batch of another shape (a ragged last one) takes the eager step.  With dropout the keys then
@@ -1092,7 +1157,7 @@ def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=Fa
     if graph:
         _check_graph_optimizer("train_vit_vae(graph=True)", optimizer)
     model.eval()
-    model.train_all(dropout=dropout)
+    model.train_all(dropout=dropout, stem_batch_stats=stem_batch_stats)
     history, graphed = [], None
     for _ep in range(int(epochs)):
         total, n = [], 0

@@ -245,6 +245,20 @@ int cvae_bn2d_fwd(const void* x, const float* gamma, const float* beta, void* y,
 /* training-mode backward through the activation and the normalisation: dx, dgamma, dbeta (y = the forward's output, for act') */
 int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
                   float* dbeta, int64_t P, int64_t C, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* Batch-statistics BatchNorm2d forward that reads its input twice (csrc/bn2d_batch.hip): the ViT-VAE stem's training walk.
+ *   y channels-last [P][C] in `dtype` (CVAE_F32 / CVAE_BF16): the conv output; a = act((y - mean) rstd gamma + beta), same shape and dtype; mean, rstd fp32 [C]
+ *   are OUTPUTS (the batch's mean and 1 / sqrt(biased variance + eps)): with (x = y, y = a) they are what cvae_bn2d_bwd reads.  running_mean / running_var
+ *   (both or neither): updated in place as torch does, r = (1 - momentum) r + momentum * (mean | unbiased variance).
+ * Three launches: per-chunk (mean, M2) from sums shifted by the chunk's first row (one read of y), the chunks merged in index order with the pairwise
+ * update, then the apply pass (one read of y, one write of a).  The chunking is a function of P alone; no float atomics: bit-reproducible on every device.
+ * workspace: cvae_bn2d_batch_workspace_bytes(P, C) (0 for a shape the entry refuses), 4-byte aligned.
+ * Every check precedes the first launch: P < 2 (torch: "Expected more than 1 value per channel"), P > 2^40, C < 8, C % 8 != 0, C > 2048, momentum outside
+ * [0, 1] or NaN, eps <= 0 or NaN: CVAE_E_BADSHAPE; an act code that is no CVAE_ACT_*: CVAE_E_UNSUPPORTED; a null pointer (the workspace included, or one
+ * running buffer without the other): CVAE_E_NULLPTR; y or a not 16-byte aligned, a float array not 4-byte aligned: CVAE_E_UNSUPPORTED; a workspace below the
+ * query: CVAE_E_WORKSPACE; a dtype code other than the two: CVAE_E_DTYPE. */
+size_t cvae_bn2d_batch_workspace_bytes(int64_t P, int64_t C);
+int cvae_bn2d_batch_fwd(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean, float* running_var,
+                        int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- CausalVesselVAE inference (csrc/vessel_infer.hip): eval-mode BatchNorm2d folded into the convs, sweep reductions ---------------------
  * Fold a table of `count` (1..16, else CVAE_E_UNSUPPORTED) conv layers with the eval-mode BatchNorm2d behind them in ONE launch (host arrays
