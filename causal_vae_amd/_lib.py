@@ -128,6 +128,9 @@ SIGNATURES = {
     "cvae_bn2d_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
     "cvae_bn2d_batch_workspace_bytes": [_i64, _i64],
     "cvae_bn2d_batch_fwd": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _p, _sz, _p],
+    "cvae_bn2d_batch_fwd_res": [_p] * 8 + [_i64, _i64, _f, _f, _i, _i, _p, _sz, _p, _p],
+    "cvae_bn2d_batch_bwd_workspace_bytes": [_i64, _i64],
+    "cvae_bn2d_batch_bwd": [_p] * 9 + [_i64, _i64, _i, _i, _p, _sz, _p],
     "cvae_fold_bn_conv": [_i] + [_p] * 11 + [_p],
     "cvae_fold_bn_conv_bwd": [_i] + [_p] * 14 + [_p],
     "cvae_vit_tokens": [_p, _i, _p, _p, _p, _i64, _i64, _p],
@@ -192,6 +195,7 @@ SIGNATURES = {
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
             "cvae_linear_workspace_bytes": _sz, "cvae_reduce_workspace_bytes": _sz, "cvae_bn2d_workspace_bytes": _sz, "cvae_bn2d_batch_workspace_bytes": _sz,
+            "cvae_bn2d_batch_bwd_workspace_bytes": _sz,
             "cvae_small_dense_workspace_bytes": _sz, "cvae_row_diff_norms_workspace_bytes": _sz,
             "cvae_mlp_heads_train_workspace_bytes": _sz, "cvae_mlp_heads_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,

@@ -1,5 +1,5 @@
-// bn2d_batch.hip — batch-statistics BatchNorm2d (+ the activation behind it) on a channels-last tensor [P = B H W][C], forward only, for the ViT-VAE stem's
-// training walk.  The tensor is read TWICE (cvae_bn2d_fwd(training=1) in vessel2d.hip reads it three times in five launches):
+// bn2d_batch.hip — batch-statistics BatchNorm2d (+ the activation behind it) on a channels-last tensor [P = B H W][C]: the forward for the ViT-VAE stem's
+// training walk; its residual form and the backward for the decoder's (section 24, below).  The tensor is read TWICE (cvae_bn2d_fwd(training=1) in vessel2d.hip reads it three times in five launches):
 //   moments  each workgroup reads ONE contiguous chunk of rows once and leaves (mean, M2) of the chunk per channel, from SHIFTED sums
 //            s1 = sum (y - K), s2 = sum (y - K)^2 with K = the chunk's first row: mean = K + s1 / n, M2 = s2 - s1^2 / n.  K lies inside the data, so the
 //            subtraction in M2 cancels a few times the chunk's variance at most, never the square of its mean (E[y^2] - E[y]^2 would).
@@ -7,7 +7,16 @@
 //            M2 = M2a + M2b + d^2 na nb / n; writes mean, rstd = 1 / sqrt(M2 / P + eps) and, when given, the running statistics (unbiased variance).
 //   apply    a = act((y - mean) rstd gamma + beta): one read of y, one write of a.
 // No float atomics and no "last workgroup": the chunking depends on P alone (never on the device), every sum has one fixed order, so the bits are the same
-// from run to run and from device to device.  The backward is cvae_bn2d_bwd (vessel2d.hip) on (x = y, dy, y = a, gamma, mean, rstd).
+// from run to run and from device to device.  The stem's backward is cvae_bn2d_bwd (vessel2d.hip) on (x = y, dy, y = a, gamma, mean, rstd).
+//
+// For the ViT-VAE decoder's training walk:
+//   cvae_bn2d_batch_fwd_res   the same moments and finish launches, and an apply instance a = resid + ((y - mean) rstd gamma + beta) for the BatchNorm that ends
+//                             a ResBlock: y and resid read once, the sum formed in fp32 and rounded once.
+//   cvae_bn2d_batch_bwd       (y, dy, a, gamma, mean, rstd) -> (dx, dgamma, dbeta) in three launches on the forward's chunking and thread layout.  With
+//                             g = dy act'(a) (act' read off the activation's OUTPUT) and xh = (y - mean) rstd:
+//     sums     one workgroup per chunk reads the chunk once and leaves (sum g, sum g xh) per channel: row-group sums added through LDS in group order;
+//     finish   adds the partials in an order set by the chunk count alone (BNB_SEGS runs per channel, then the runs in order) -> dbeta, dgamma;
+//     apply    dx = gamma rstd (g - dbeta / P - xh dgamma / P): y, dy and a read once, dx written once, a row group's constants in registers.
 #include "common.h"
 
 namespace {
@@ -140,9 +149,171 @@ __global__ __launch_bounds__(256) void bn2d_batch_apply_kernel(const T* __restri
     }
 }
 
+// ---- the residual form of the apply pass: a = resid + ((y - mean) rstd gamma + beta), no activation (the BatchNorm that ends a ResBlock) ----
+template <typename T>
+__global__ __launch_bounds__(256) void bn2d_batch_apply_res_kernel(const T* __restrict__ y, const T* __restrict__ resid, const float* __restrict__ mean,
+                                                                    const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                    T* __restrict__ a, int64_t P, int C) {
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    if (rg >= R) return;
+    float mu[8], k[8], b[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; k[e] = rstd[c0 + e] * gamma[c0 + e]; b[e] = beta[c0 + e]; }
+    const int64_t step = (int64_t)gridDim.x * R;
+    int64_t p = (int64_t)blockIdx.x * R + rg;
+    for (; p + step < P; p += 2 * step) {
+        float v[2][8], r[2][8];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) { load_f32<8>(y + (p + u * step) * C + c0, v[u]); load_f32<8>(resid + (p + u * step) * C + c0, r[u]); }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[u][e] = r[u][e] + ((v[u][e] - mu[e]) * k[e] + b[e]);
+            store_from_f32<8>(a + (p + u * step) * C + c0, v[u]);
+        }
+    }
+    for (; p < P; p += step) {
+        float v[8], r[8];
+        load_f32<8>(y + p * C + c0, v);
+        load_f32<8>(resid + p * C + c0, r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = r[e] + ((v[e] - mu[e]) * k[e] + b[e]);
+        store_from_f32<8>(a + p * C + c0, v);
+    }
+}
+
+// ---- the backward ----
+// sums: the moments kernel's chunks and thread layout.  `part` row 2 g = the chunk's sum of g, row 2 g + 1 = its sum of g xh.  GATED: g = dy act'(a), else g = dy
+// and `a` is not read.
+template <typename T, bool GATED>
+__global__ __launch_bounds__(256) void bn2d_batch_bwd_sums_kernel(const T* __restrict__ y, const T* __restrict__ dy, const T* __restrict__ a,
+                                                                   const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ part,
+                                                                   int64_t P, int C, int64_t chunk, int act) {
+    __shared__ float red[2][256][8 + 1];
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = (p0 + chunk < P) ? p0 + chunk : P;
+    float s1[8], s2[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    if (rg < R) {
+        float mu[8], rs[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; rs[e] = rstd[c0 + e]; }
+        int64_t p = p0 + rg;
+        for (; p + (int64_t)R < p1; p += 2 * (int64_t)R) {
+            float v[2][8], d[2][8], o[2][8];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                load_f32<8>(y + (p + (int64_t)u * R) * C + c0, v[u]);
+                load_f32<8>(dy + (p + (int64_t)u * R) * C + c0, d[u]);
+                if (GATED) load_f32<8>(a + (p + (int64_t)u * R) * C + c0, o[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float g = GATED ? d[u][e] * act_grad_from_out(o[u][e], act) : d[u][e];
+                    s1[e] += g;
+                    s2[e] += g * ((v[u][e] - mu[e]) * rs[e]);
+                }
+        }
+        for (; p < p1; p += R) {
+            float v[8], d[8], o[8];
+            load_f32<8>(y + p * C + c0, v);
+            load_f32<8>(dy + p * C + c0, d);
+            if (GATED) load_f32<8>(a + p * C + c0, o);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float g = GATED ? d[e] * act_grad_from_out(o[e], act) : d[e];
+                s1[e] += g;
+                s2[e] += g * ((v[e] - mu[e]) * rs[e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[0][t][e] = s1[e]; red[1][t][e] = s2[e]; }
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {                                  // thread c < C adds its channel's R row-group sums in group order
+        const int l = c >> 3, e = c & 7;
+        float a1 = 0.f, a2 = 0.f;
+        for (int q = 0; q < R; ++q) { a1 += red[0][q * lanes + l][e]; a2 += red[1][q * lanes + l][e]; }
+        part[((size_t)blockIdx.x * 2) * C + c] = a1;
+        part[((size_t)blockIdx.x * 2 + 1) * C + c] = a2;
+    }
+}
+
+// finish: the forward finish's runs (thread (s, cc) adds run s of channel cc's partials in index order, thread (0, cc) the BNB_SEGS runs in order), plain sums
+__global__ __launch_bounds__(256) void bn2d_batch_bwd_finish_kernel(const float* __restrict__ part, int G, float* __restrict__ dbeta, float* __restrict__ dgamma,
+                                                                     int C) {
+    __shared__ float sb[BNB_SEGS][16], sg[BNB_SEGS][16];
+    const int cc = threadIdx.x & 15, s = threadIdx.x >> 4, c = blockIdx.x * 16 + cc;
+    const int per = (G + BNB_SEGS - 1) / BNB_SEGS, g0 = s * per, g1 = (g0 + per < G) ? g0 + per : G;
+    float b = 0.f, w = 0.f;
+    if (c < C)
+        for (int g = g0; g < g1; ++g) { b += part[((size_t)g * 2) * C + c]; w += part[((size_t)g * 2 + 1) * C + c]; }
+    sb[s][cc] = b; sg[s][cc] = w;
+    __syncthreads();
+    if (s != 0 || c >= C) return;
+    for (int q = 1; q < BNB_SEGS; ++q) { b += sb[q][cc]; w += sg[q][cc]; }
+    dbeta[c] = b;
+    dgamma[c] = w;
+}
+
+// apply: the forward apply's layout; a row group keeps (mean, rstd, gamma rstd, dbeta / P, dgamma / P) of its 8 channels in registers
+template <typename T, bool GATED>
+__global__ __launch_bounds__(256) void bn2d_batch_bwd_apply_kernel(const T* __restrict__ y, const T* __restrict__ dy, const T* __restrict__ a,
+                                                                    const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ dbeta, const float* __restrict__ dgamma, T* __restrict__ dx, int64_t P,
+                                                                    int C, int act) {
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    if (rg >= R) return;
+    float mu[8], rs[8], k[8], mb[8], mg[8];
+    const float fP = (float)P;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        mu[e] = mean[c0 + e]; rs[e] = rstd[c0 + e]; k[e] = gamma[c0 + e] * rs[e]; mb[e] = dbeta[c0 + e] / fP; mg[e] = dgamma[c0 + e] / fP;
+    }
+    const int64_t step = (int64_t)gridDim.x * R;
+    int64_t p = (int64_t)blockIdx.x * R + rg;
+    for (; p + step < P; p += 2 * step) {
+        float v[2][8], d[2][8], o[2][8];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            load_f32<8>(y + (p + u * step) * C + c0, v[u]);
+            load_f32<8>(dy + (p + u * step) * C + c0, d[u]);
+            if (GATED) load_f32<8>(a + (p + u * step) * C + c0, o[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float g = GATED ? d[u][e] * act_grad_from_out(o[u][e], act) : d[u][e];
+                v[u][e] = k[e] * ((g - mb[e]) - ((v[u][e] - mu[e]) * rs[e]) * mg[e]);
+            }
+            store_from_f32<8>(dx + (p + u * step) * C + c0, v[u]);
+        }
+    }
+    for (; p < P; p += step) {
+        float v[8], d[8], o[8];
+        load_f32<8>(y + p * C + c0, v);
+        load_f32<8>(dy + p * C + c0, d);
+        if (GATED) load_f32<8>(a + p * C + c0, o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float g = GATED ? d[e] * act_grad_from_out(o[e], act) : d[e];
+            v[e] = k[e] * ((g - mb[e]) - ((v[e] - mu[e]) * rs[e]) * mg[e]);
+        }
+        store_from_f32<8>(dx + p * C + c0, v);
+    }
+}
+
 // the three launches; the entry point has checked everything but the dtype code, which with_dtype refuses before the first launch
-int bn2d_batch_launch(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean, float* running_var, int64_t P,
-                      int C, float momentum, float eps, int act, int dtype, float* part, hipStream_t st) {
+// resid (non-null only with act == CVAE_ACT_NONE): the residual instance of the apply pass
+int bn2d_batch_launch(const void* y, const void* resid, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
+                      float* running_var, int64_t P, int C, float momentum, float eps, int act, int dtype, float* part, hipStream_t st) {
     return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
         const int64_t chunk = bnb_chunk(P);
@@ -150,9 +321,33 @@ int bn2d_batch_launch(const void* y, const float* gamma, const float* beta, void
         hipLaunchKernelGGL(bn2d_batch_moments_kernel<T>, dim3((unsigned)G), dim3(256), 0, st, (const T*)y, part, P, C, chunk);
         hipLaunchKernelGGL(bn2d_batch_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float*)part, G, mean, rstd, running_mean, running_var,
                            P, C, chunk, eps, momentum);
+        if (resid) {
+            hipLaunchKernelGGL(bn2d_batch_apply_res_kernel<T>, dim3(cvae_grid_1d((P + R - 1) / R, 2, 2048)), dim3(256), 0, st, (const T*)y, (const T*)resid,
+                               (const float*)mean, (const float*)rstd, gamma, beta, (T*)a, P, C);
+            return launch_rc();
+        }
         return with_epi(act, [&](auto epi) {
             hipLaunchKernelGGL((bn2d_batch_apply_kernel<T, decltype(epi)::value>), dim3(cvae_grid_1d((P + R - 1) / R, 4, 2048)), dim3(256), 0, st, (const T*)y,
                                (const float*)mean, (const float*)rstd, gamma, beta, (T*)a, P, C, act);
+            return launch_rc();
+        });
+    });
+}
+
+// the backward's three launches; as above, with_dtype refuses a dtype code before the first of them
+int bn2d_batch_bwd_launch(const void* y, const void* dy, const void* a, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+                          float* dbeta, int64_t P, int C, int act, int dtype, float* part, hipStream_t st) {
+    return with_dtype(dtype, [&](auto tv) {
+        using T = decltype(tv);
+        return with_bool(act != CVAE_ACT_NONE, [&](auto gated) {
+            constexpr bool GATED = decltype(gated)::value;
+            const int64_t chunk = bnb_chunk(P);
+            const int G = (int)bnb_parts(P), R = 256 / (C >> 3);
+            hipLaunchKernelGGL((bn2d_batch_bwd_sums_kernel<T, GATED>), dim3((unsigned)G), dim3(256), 0, st, (const T*)y, (const T*)dy, (const T*)a, mean, rstd, part,
+                               P, C, chunk, act);
+            hipLaunchKernelGGL(bn2d_batch_bwd_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float*)part, G, dbeta, dgamma, C);
+            hipLaunchKernelGGL((bn2d_batch_bwd_apply_kernel<T, GATED>), dim3(cvae_grid_1d((P + R - 1) / R, 2, 2048)), dim3(256), 0, st, (const T*)y, (const T*)dy,
+                               (const T*)a, mean, rstd, gamma, (const float*)dbeta, (const float*)dgamma, (T*)dx, P, C, act);
             return launch_rc();
         });
     });
@@ -169,16 +364,45 @@ extern "C" size_t cvae_bn2d_batch_workspace_bytes(int64_t P, int64_t C) {
     const int64_t units = (P + BNB_ROWS - 1) / BNB_ROWS;
     return (size_t)2 * (units < BNB_MAX_PARTS ? units : BNB_MAX_PARTS) * C * sizeof(float);
 }
-extern "C" int cvae_bn2d_batch_fwd(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
-                                   float* running_var, int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
+// the forward's checks, shared by the plain and the residual entry (resid == nullptr: the plain one)
+static int bn2d_batch_fwd_checked(const void* y, const void* resid, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
+                                  float* running_var, int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
     if (!bnb_shape_ok(P, C)) return CVAE_E_BADSHAPE;
     if (!(momentum >= 0.f && momentum <= 1.f) || !(eps > 0.f)) return CVAE_E_BADSHAPE;       // written so that a NaN is refused too
     if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_UNSUPPORTED;
+    if (resid && act != CVAE_ACT_NONE) return CVAE_E_UNSUPPORTED;       // behind an activation `a` would no longer carry the sign the backward reads
     if (!y || !gamma || !beta || !a || !mean || !rstd || !workspace || (running_mean == nullptr) != (running_var == nullptr)) return CVAE_E_NULLPTR;
-    if (!aligned16(y) || !aligned16(a) || !aligned4(gamma) || !aligned4(beta) || !aligned4(mean) || !aligned4(rstd) || !aligned4(running_mean) ||
-        !aligned4(running_var) || !aligned4(workspace))
+    if (!aligned16(y) || !aligned16(resid) || !aligned16(a) || !aligned4(gamma) || !aligned4(beta) || !aligned4(mean) || !aligned4(rstd) ||
+        !aligned4(running_mean) || !aligned4(running_var) || !aligned4(workspace))
         return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_bn2d_batch_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
-    return bn2d_batch_launch(y, gamma, beta, a, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, act, dtype, (float*)workspace, (hipStream_t)stream);
+    return bn2d_batch_launch(y, resid, gamma, beta, a, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, act, dtype, (float*)workspace,
+                             (hipStream_t)stream);
+}
+extern "C" int cvae_bn2d_batch_fwd(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
+                                   float* running_var, int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    return bn2d_batch_fwd_checked(y, nullptr, gamma, beta, a, mean, rstd, running_mean, running_var, P, C, momentum, eps, act, dtype, workspace, workspace_bytes,
+                                  stream);
+}
+extern "C" int cvae_bn2d_batch_fwd_res(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
+                                       float* running_var, int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace,
+                                       size_t workspace_bytes, void* stream, const void* resid) {
+    return bn2d_batch_fwd_checked(y, resid, gamma, beta, a, mean, rstd, running_mean, running_var, P, C, momentum, eps, act, dtype, workspace, workspace_bytes,
+                                  stream);
+}
+
+extern "C" size_t cvae_bn2d_batch_bwd_workspace_bytes(int64_t P, int64_t C) { return cvae_bn2d_batch_workspace_bytes(P, C); }      // two rows per chunk here too
+extern "C" int cvae_bn2d_batch_bwd(const void* y, const void* dy, const void* a, const float* gamma, const float* mean, const float* rstd, void* dx,
+                                   float* dgamma, float* dbeta, int64_t P, int64_t C, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!bnb_shape_ok(P, C)) return CVAE_E_BADSHAPE;
+    if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_UNSUPPORTED;
+    const bool gated = act != CVAE_ACT_NONE;
+    if (!y || !dy || (gated && !a) || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return CVAE_E_NULLPTR;
+    if (!aligned16(y) || !aligned16(dy) || (gated && !aligned16(a)) || !aligned16(dx) || !aligned4(gamma) || !aligned4(mean) || !aligned4(rstd) ||
+        !aligned4(dgamma) || !aligned4(dbeta) || !aligned4(workspace))
+        return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_bn2d_batch_bwd_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
+    return bn2d_batch_bwd_launch(y, dy, a, gamma, mean, rstd, dx, dgamma, dbeta, P, (int)C, act, dtype, (float*)workspace, (hipStream_t)stream);
 }

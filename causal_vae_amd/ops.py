@@ -1850,15 +1850,40 @@ def _bn2d_rows(what, t, **like):
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
-def bn2d_batch_fwd(y, bn, act):
+def bn2d_batch_bwd(y, g, a, weight, mean, rstd, act):
+    """bn2d_bwd's function on the forward's chunking (cvae_bn2d_batch_bwd, csrc/bn2d_batch.hip): (g_y, dgamma, dbeta) of
+    a = act((y - mean) rstd weight + bias) with batch statistics, in three launches that read y, g and a twice and add their partial sums in a fixed order of
+    16 runs per channel.  a may be None when act is None (it is then not read): the BatchNorm that ends a ResBlock, whose output carries the residual."""
+    gated = act not in (None, "none")
+    L.require_gpu(y, g, a, weight, mean, rstd)
+    _forward_only("bn2d_batch_bwd", y, g, a, weight, mean, rstd)
+    if gated and a is None:
+        raise L.CvaeError(f"bn2d_batch_bwd: the activation's output `a` is needed for act={act!r}")
+    P, Cc = _bn2d_rows("bn2d_batch_bwd", y, g=g, **({"a": a} if gated else {}))
+    for k, v in (("weight", weight), ("mean", mean), ("rstd", rstd)):
+        if tuple(v.shape) != (Cc,) or v.dtype != torch.float32 or not v.is_contiguous():
+            raise L.CvaeError(f"bn2d_batch_bwd: {k} must be a contiguous fp32 [{Cc}] vector, got {tuple(v.shape)} {v.dtype}")
+    gy = torch.empty_like(y)
+    dw, db = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+    _t, wp, wb = _scratch(lib.cvae_bn2d_batch_bwd_workspace_bytes(P, Cc), y)
+    check(L.timed(f"bn2d_batch_bwd P{P} C{Cc}", lib.cvae_bn2d_batch_bwd, ptr(y), ptr(g), ptr(a) if gated else None, ptr(weight), ptr(mean), ptr(rstd), ptr(gy),
+                  ptr(dw), ptr(db), P, Cc, L.act_code(act), L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_batch_bwd")
+    return gy, dw, db
+
+
+def bn2d_batch_fwd(y, bn, act, resid=None):
     """(a, mean, rstd) = nn.BatchNorm2d `bn` on the statistics of THIS batch, then the activation `act` (None / "relu" / "sigmoid" / "leaky02" / "leaky001"), on
     the channels-last conv output y [.., C] (fp32 or bf16): cvae_bn2d_batch_fwd (csrc/bn2d_batch.hip, DESIGN §23), which reads y twice.  a has y's shape and dtype;
     mean and rstd (fp32 [C]: the batch mean and 1 / sqrt(biased variance + eps)) are what bn2d_bwd reads.  With bn.track_running_stats its running_mean and
     running_var are updated in place as torch does in training mode (momentum, unbiased variance) and num_batches_tracked advances by one with an in-place device
-    add, so a captured step replays it.  The module's own mode is not consulted and not changed.  momentum=None (torch's cumulative average): CvaeError."""
+    add, so a captured step replays it.  The module's own mode is not consulted and not changed.  momentum=None (torch's cumulative average): CvaeError.
+    resid (y's shape and dtype, with act None only): a = resid + bn(y), summed in fp32 and rounded once (cvae_bn2d_batch_fwd_res) — the
+    BatchNorm that ends a ResBlock."""
     L.require_gpu(y, bn.weight, bn.bias)
-    _forward_only("bn2d_batch_fwd", y, bn.weight, bn.bias)
-    P, Cc = _bn2d_rows("bn2d_batch_fwd", y)
+    _forward_only("bn2d_batch_fwd", y, bn.weight, bn.bias, resid)
+    P, Cc = _bn2d_rows("bn2d_batch_fwd", y) if resid is None else _bn2d_rows("bn2d_batch_fwd", y, resid=resid)
+    if resid is not None and act not in (None, "none"):
+        raise L.CvaeError(f"bn2d_batch_fwd: a residual goes with no activation (behind one, `a` would not carry the sign the backward reads), got act={act!r}")
     if bn.weight is None or bn.bias is None or bn.num_features != Cc or bn.weight.dtype != torch.float32:
         raise L.CvaeError(f"bn2d_batch_fwd: an affine fp32 BatchNorm2d over {Cc} channels expected, got num_features={bn.num_features}, affine={bn.weight is not None}")
     if bn.momentum is None:
@@ -1869,9 +1894,12 @@ def bn2d_batch_fwd(y, bn, act):
     a = torch.empty_like(y)
     mean, rstd = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
     _t, wp, wb = _scratch(lib.cvae_bn2d_batch_workspace_bytes(P, Cc), y)
-    check(L.timed(f"bn2d_batch_fwd P{P} C{Cc}", lib.cvae_bn2d_batch_fwd, ptr(y), ptr(bn.weight), ptr(bn.bias), ptr(a), ptr(mean), ptr(rstd),
-                  ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None, P, Cc, float(bn.momentum), float(bn.eps), L.act_code(act),
-                  L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_batch_fwd")
+    args = (ptr(y), ptr(bn.weight), ptr(bn.bias), ptr(a), ptr(mean), ptr(rstd), ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
+            P, Cc, float(bn.momentum), float(bn.eps), L.act_code(act), L.dtype_code(y.dtype), wp, wb, stream())
+    if resid is None:
+        check(L.timed(f"bn2d_batch_fwd P{P} C{Cc}", lib.cvae_bn2d_batch_fwd, *args), "bn2d_batch_fwd")
+    else:
+        check(L.timed(f"bn2d_batch_fwd_res P{P} C{Cc}", lib.cvae_bn2d_batch_fwd_res, *args, ptr(resid)), "bn2d_batch_fwd_res")
     if track and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return a, mean, rstd

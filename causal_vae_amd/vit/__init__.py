@@ -2,8 +2,8 @@
 ViTVAEEncoder: image -> (mu, log_var) / CLS features; ViTVAE: the same plus decode / forward / reconstruct; CausalViTVAE (vessel_analysis/00_core/models.py:181-307): that backbone
 between the fused adapter heads of the (x, m, t) -> z -> (z, m) -> x model; CausalViTVAE.train_adapters / forward_train train those heads on the frozen
 eval-mode backbone (the reference's vae.train() also trains the backbone and runs its dropout and BatchNorm2d in training mode: here it stays frozen, or
-learns in eval mode: train_decoder / train_transformer / train_stem; the stem's BatchNorm2d layers train on batch statistics when asked by keyword,
-train_stem(batch_stats=True) / stem_batch_stats=True; the decoder's stay on running statistics).  ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae: the reference's ViTVAE
+learns in eval mode: train_decoder / train_transformer / train_stem; the BatchNorm2d layers train on batch statistics when asked by keyword: the stem's with
+train_stem(batch_stats=True) / stem_batch_stats=True, DESIGN §23, the decoder's with train_decoder(batch_stats=True) / decoder_batch_stats=True).  ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae: the reference's ViTVAE
 training loop (latent_translator/engine.py:6-36) end to end, in that eval-mode regime.  vit_vae_train_step / causal_vit_train_step: one step of either
 recipe; GraphedViTTrainStep: that step captured as one HIP graph, which train_vit_vae(graph=True) replays.
 Looking inside: ViTVAEEncoder.attention_weights / attention_rollout (so ViTVAE's, and CausalViTVAE.attention_rollout through its backbone) and

@@ -100,12 +100,14 @@ class CausalViTVAE(nn.Module):
         return [p for mod in (self.enc_adapter, self.dec_adapter, self.morph_predictor_shared, self.morph_predictor_mu, self.morph_predictor_logvar)
                 for p in mod.parameters()]
 
-    def train_adapters(self, decoder=False, transformer=False, stem=False, dropout=False, stem_batch_stats=False):
+    def train_adapters(self, decoder=False, transformer=False, stem=False, dropout=False, stem_batch_stats=False, decoder_batch_stats=False):
         """Freeze the backbone (requires_grad_(False) on every backbone parameter, eval mode) and keep it in eval mode through later model.train() calls; the
         heads go to training mode.  Returns the list of head parameters, for the optimizer.  Every call starts from the frozen state (backbone.freeze_decoder(), so
         a default call after a decoder=True one switches the decoder's gradients off again).
         decoder=True: the backbone's decoder learns too (backbone.train_decoder(): decoder_input and decoder ask for gradients, still in eval mode: BatchNorm2d on
-        its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters.
+        its running statistics, which are not updated); the encoder stays frozen.  Returns head plus decoder parameters.  decoder_batch_stats=True (needs
+        decoder=True): the decoder's 11 BatchNorm2d layers normalise with batch statistics in the training forward and update their running statistics
+        (backbone.train_decoder(batch_stats=True); the backbone module itself stays in eval mode).
         transformer=True: the backbone's transformer learns too (backbone.train_transformer(): pos_embedding, cls_token, transformer, to_latent; eval mode; the
         conv stem stays frozen).  dropout=True (needs transformer=True; float32 compute dtype): its blocks then drop in the training forward as the
         reference's do under train() (backbone.train_transformer(dropout=True)); default: no dropout.  fc_mu and fc_var stay frozen and are not returned: this model reads the cls features, not the
@@ -118,6 +120,8 @@ class CausalViTVAE(nn.Module):
             raise CvaeError("CausalViTVAE.train_adapters: stem=True needs transformer=True (the stem's gradient arrives through the transformer)")
         if stem_batch_stats and not stem:
             raise CvaeError("CausalViTVAE.train_adapters: stem_batch_stats=True needs stem=True (a frozen stem runs the fold on its running statistics)")
+        if decoder_batch_stats and not decoder:
+            raise CvaeError("CausalViTVAE.train_adapters: decoder_batch_stats=True needs decoder=True (a frozen decoder runs the fold on its running statistics)")
         if dropout and not transformer:
             raise CvaeError("CausalViTVAE.train_adapters: dropout=True needs transformer=True (the dropout sites are the transformer blocks'; a frozen "
                             "transformer runs its inference form)")
@@ -133,7 +137,7 @@ class CausalViTVAE(nn.Module):
         if transformer:
             params += self.backbone.train_transformer(heads=False, dropout=dropout)
         if decoder:
-            self.backbone.train_decoder()
+            self.backbone.train_decoder(batch_stats=decoder_batch_stats)
             params += list(self.backbone.decoder_input.parameters()) + list(self.backbone.decoder.parameters())
         return params
 

@@ -30,8 +30,10 @@ decode's launches (the fold also writes the backward matrices) and keeps five ga
 cvae_conv_s1_c1_bwd_data, cvae_conv_s1_bwd_data (every LeakyReLU derivative in an epilogue), cvae_conv_down on the k4 weights and cvae_latent_to_grid_bwd.
 Training, all in eval mode (BatchNorm2d on its running statistics; dropout only where train_transformer(dropout=True) asks for it): train_decoder, train_transformer (§16) and train_stem (§17: the
 stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then per layer cvae_conv_wgrad and cvae_conv_down_bwd_data with the LeakyReLU
-derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch; train_stem(batch_stats=True), DESIGN §23: the stem alone on
-batch statistics, the module still in eval mode — per layer the raw conv, cvae_bn2d_batch_fwd, and cvae_bn2d_bwd on the way back); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
+derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch; train_stem(batch_stats=True), DESIGN §23: the stem on
+batch statistics, the module still in eval mode — per layer the raw conv, cvae_bn2d_batch_fwd, and cvae_bn2d_bwd on the way back; train_decoder(batch_stats=
+True), DESIGN §24: the same for the decoder's 11 BatchNorm2d layers, with cvae_bn2d_batch_fwd_res at the end of a ResBlock and cvae_bn2d_batch_bwd on the
+way back); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
 are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
 The gradient with respect to the IMAGE: cls_features_vjp / encode_vjp (explicit, no graph), x.grad after cls_features_with_grad / encode_with_grad /
 forward_train of an x that asks, saliency (plain and integrated gradients) and gradcam.  They share a data-only form of the backward (_walk_backward(params=False):
@@ -833,8 +835,11 @@ DECODER_CHANNELS = (128, 64, 32, 16, 16)     # outputs of the five transposed co
 _Stage = namedtuple("_Stage", "kind layers fold gates")
 # What _decode_walk keeps of a stage for _decode_backward: gate_in (the stage's input when the stage before it gates, else None), inner (a ResBlock's inner
 # activation), mats (the backward matrix of every GEMM layer, in layer order), k4 (an "up" stage's folded k4 weight), x (the stage's input, kept only when
-# weight gradients are wanted: a ResBlock sum and the grid are no gates, so gate_in does not cover them).
-_Step = namedtuple("_Step", "stage gate_in inner mats k4 x")
+# weight gradients are wanted: a ResBlock sum and the grid are no gates, so gate_in does not cover them).  The batch-statistics walk (train_decoder(batch_stats=
+# True)) fills the rest: pre = the raw conv output of every layer of the stage, mean / rstd = each layer's batch statistics as cvae_bn2d_batch_bwd
+# reads them, out = the stage's output activation; there k4 and mats come from the RAW weights and gate_in is never read.  pre is None in the eval-mode
+# (folded) walk, which is how the backward tells.
+_Step = namedtuple("_Step", "stage gate_in inner mats k4 x pre mean rstd out", defaults=(None, None, None, None))
 
 
 class ViTVAE(ViTVAEEncoder):
@@ -886,16 +891,25 @@ class ViTVAE(ViTVAEEncoder):
         return self._decode_walk(z, False, collect)[0]
 
     @torch.no_grad()
-    def _decode_walk(self, z, save, collect=None, keep_inputs=False):
+    def _decode_walk(self, z, save, collect=None, keep_inputs=False, batch_stats=False):
         """The decoder's launches -> (image, saved).  save=False: the forward fold kinds, in bf16 one pack of the 8 GEMM matrices, saved = None.  save=True: the
         same launches with the fold's _GRAD kinds (one pack of 16: forward and backward matrices) and saved = ([_Step per stage], the output conv, its gate)
         for _decode_backward: DESIGN §13's set (the gates are the outputs of stages 0, 2, 4, 6 and 7; a ResBlock sum and the grid are no gates).
         keep_inputs (with save): every step also keeps its stage's input, what the weight gradients are multiplied with; the launches are the same.
         collect (a dict, for tests): receives `grid` (decoder_input's output, channels-last [B, gh, gw, 256]), `stages` (the channels-last activation after
-        each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order) and `res_inner` (the three ResBlock inner activations)."""
+        each of the 8 stages: 5 transposed convs, 3 ResBlocks, in execution order) and `res_inner` (the three ResBlock inner activations).
+        batch_stats (with save and keep_inputs: _DecodeWithGrad's training walk after train_decoder(batch_stats=True)): no fold of statistics — the
+        fold's launch with no BatchNorm gives the raw k4 weights and the raw forward / backward matrices; every conv runs with its own bias (it cancels in the
+        normalised value, but running_mean must contain it) and no activation, and ops.bn2d_batch_fwd behind it normalises with THIS batch's statistics, applies
+        the activation (a ResBlock's second layer: adds the block's input instead) and updates the layer's running statistics and counter in place."""
         dt = self.compute_dtype
         plan, out_conv = self._decoder_plan()
-        folded = ops.fold_bn_conv(self._fold_table(plan, save))        # one launch, on every call: parameters may have been rewritten
+        if batch_stats and not (save and keep_inputs):
+            raise CvaeError("ViTVAE._decode_walk: batch statistics belong to the training walk (save=True, keep_inputs=True): inference keeps the running statistics")
+        table = self._fold_table(plan, save)
+        if batch_stats:
+            table = [(w, kind, b, None) for w, kind, b, _bn in table]
+        folded = ops.fold_bn_conv(table)                               # one launch, on every call: parameters may have been rewritten
         gemm = [k for st in plan if st.kind != "up" for k in st.fold]
         fwd, bwd = [folded[k][0] for k in gemm], [folded[k][2] for k in gemm] if save else []
         if dt == torch.bfloat16:                                       # one launch for all of them
@@ -910,6 +924,33 @@ class ViTVAE(ViTVAEEncoder):
         for st in plan:
             y = k4 = None
             x_in = h if keep_inputs else None
+            if batch_stats:
+                bns = [bn for _conv, bn in st.layers]
+                if st.kind == "up":
+                    k4, b = folded[st.fold[0]]
+                    _B, hh, ww, c = h.shape
+                    pre = [ops.ConvUp.apply(h.view(B, 1, hh, ww, c), k4, b, 2, None, False, False, None).view(B, 2 * hh, 2 * ww, k4.shape[1])]
+                    h, mean, rstd = ops.bn2d_batch_fwd(pre[0], bns[0], "leaky001")
+                    stats = [(mean, rstd)]
+                elif st.kind == "sub":
+                    k, = st.fold
+                    pre = [ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, None)]
+                    h, mean, rstd = ops.bn2d_batch_fwd(pre[0], bns[0], "leaky001")
+                    stats = [(mean, rstd)]
+                else:
+                    k0, k1 = st.fold
+                    y1 = ops.conv_s1(h, mats[k0], folded[k0][1], ops.CONV_S1_K3, None)
+                    y, mean1, rstd1 = ops.bn2d_batch_fwd(y1, bns[0], "leaky02")
+                    y2 = ops.conv_s1(y, mats[k1], folded[k1][1], ops.CONV_S1_K3, None)
+                    h, mean2, rstd2 = ops.bn2d_batch_fwd(y2, bns[1], None, resid=h)
+                    pre, stats = [y1, y2], [(mean1, rstd1), (mean2, rstd2)]
+                    if collect is not None:
+                        collect["res_inner"].append(y)
+                steps.append(_Step(st, None, y, [bmats[k] for k in st.fold if k in bmats], k4, x_in, pre, [m for m, _r in stats], [r for _m, r in stats], h))
+                gate = h
+                if collect is not None:
+                    collect["stages"].append(h)
+                continue
             if st.kind == "up":
                 k4, b = folded[st.fold[0]]
                 _B, hh, ww, c = h.shape
@@ -932,22 +973,28 @@ class ViTVAE(ViTVAEEncoder):
 
     # ---- the gradient with respect to the latent (frozen decoder, eval mode) -----------------------------------------------------
     _decoder_grads = False          # train_decoder(): decode_with_grad also accumulates the decoder parameters' gradients
+    _decoder_batch_stats = False    # train_decoder(batch_stats=True): its training walk normalises the decoder with batch statistics
 
     def freeze_decoder(self):
         """requires_grad_(False) on decoder_input and decoder: what decode_with_grad asks for when it is to return no weight gradients."""
         self.decoder_input.requires_grad_(False)
         self.decoder.requires_grad_(False)
         self._decoder_grads = False
+        self._decoder_batch_stats = False
         return self
 
-    def train_decoder(self):
+    def train_decoder(self, batch_stats=False):
         """The counterpart of freeze_decoder(): requires_grad_(True) on decoder_input and decoder, and decode_with_grad from now on accumulates `.grad` on every
-        decoder parameter next to dz (DESIGN §15).  The decoder stays in EVAL mode: BatchNorm2d normalises with its running statistics, which are not updated;
-        its weight and bias learn, and so do the conv weights and biases, through the fold.  (The reference's vae.train() uses batch statistics: the one
-        difference of this path.)"""
+        decoder parameter next to dz.  The decoder stays in EVAL mode.  batch_stats=False (default): BatchNorm2d normalises with its running
+        statistics, which are not updated; its weight and bias learn, and so do the conv weights and biases, through the fold.  batch_stats=True:
+        decode_with_grad's walk normalises each of the decoder's 11 BatchNorm2d layers with the statistics of its batch and updates running_mean, running_var
+        and num_batches_tracked, as the reference's vae.train() does — asked for by keyword, as dropout and the stem's batch statistics are, not with the
+        module's mode.  decode, decode_vjp, reconstruct, forward and fit_latent keep the fold on the running statistics and change no buffer.
+        freeze_decoder() clears it."""
         self.decoder_input.requires_grad_(True)
         self.decoder.requires_grad_(True)
         self._decoder_grads = True
+        self._decoder_batch_stats = bool(batch_stats)
         return self
 
     def _decoder_params(self):
@@ -975,6 +1022,8 @@ class ViTVAE(ViTVAEEncoder):
         z (the walk's latent; the walk ran with keep_inputs): returns (dz, gradients of _decoder_params() in that order) — the same launches for dz, and next to
         them each layer's weight gradient from its input and the `g` of its pre-activation, then ONE launch back through the fold."""
         steps, out_conv, out_gate = saved
+        if steps[0].pre is not None:
+            return self._decode_backward_batch_stats(saved, g_img, z)
         dt = self.compute_dtype
         B = g_img.shape[0]
         folded = {}                                                    # fold-table position -> (gradient of the folded weight, of the folded bias)
@@ -1009,11 +1058,53 @@ class ViTVAE(ViTVAEEncoder):
             grads += quad
         return dz, grads + list(d_out)
 
+    def _decode_backward_batch_stats(self, saved, g_img, z):
+        """_decode_backward after the batch-statistics walk -> (dz, gradients of _decoder_params() in that order).  `g` is the gradient of a
+        stage's output ACTIVATION: no data-gradient launch carries a gate, the activation's derivative is ops.bn2d_batch_bwd's, which turns g into the gradient
+        of the raw conv output plus dgamma and dbeta.  The weight gradients are the raw weights' ("up": the 3 x 3 part of the k4 weight's, as
+        cvae_fold_bn_conv_bwd picks it); the conv biases' are zero in exact arithmetic (the mean is subtracted), computed and returned all the same, as autograd
+        does.  No fold_bn_conv_bwd launch."""
+        steps, out_conv, out_in = saved
+        dt = self.compute_dtype
+        B = g_img.shape[0]
+        quads = {}                                                     # fold-table position -> (dW, dbias, dgamma, dbeta)
+        d_out = ops.conv_s1_c1_wgrad(out_in, g_img)
+        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, None, None, dt)
+        for s in reversed(steps):
+            st = s.stage
+            bns = [bn for _conv, bn in st.layers]
+            if st.kind == "res":
+                g2, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[1], g, None, bns[1].weight, s.mean[1], s.rstd[1], None)
+                quads[st.fold[1]] = tuple(ops.conv_s1_wgrad(s.inner, g2, ops.CONV_S1_K3)) + (dgamma, dbeta)
+                t = ops.conv_s1_bwd_data(g2, s.mats[1], ops.CONV_S1_K3)
+                g1, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[0], t, s.inner, bns[0].weight, s.mean[0], s.rstd[0], "leaky02")
+                quads[st.fold[0]] = tuple(ops.conv_s1_wgrad(s.x, g1, ops.CONV_S1_K3)) + (dgamma, dbeta)
+                g = ops.conv_s1_bwd_data(g1, s.mats[0], ops.CONV_S1_K3, resid=g)
+                continue
+            gy, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[0], g, s.out, bns[0].weight, s.mean[0], s.rstd[0], "leaky001")
+            if st.kind == "sub":
+                quads[st.fold[0]] = tuple(ops.conv_s1_wgrad(s.x, gy, ops.CONV_S1_SUBPIXEL)) + (dgamma, dbeta)
+                g = ops.conv_s1_bwd_data(gy, s.mats[0], ops.CONV_S1_SUBPIXEL_T, cin=st.layers[0][0].in_channels)
+            else:
+                w = s.k4
+                _B, hh, ww, c = gy.shape
+                dk4, dbias = ops._conv_wgrad(s.x.view(B, 1, hh // 2, ww // 2, w.shape[0]), gy.view(B, 1, hh, ww, c), 2, w.shape, want_lbias=True)
+                quads[st.fold[0]] = (dk4[:, :, :3, :3].contiguous(), dbias, dgamma, dbeta)
+                g = ops._conv_down(gy.view(B, 1, hh, ww, c), ops.pack_weight(w, 2, False, dt), None, None, w.shape[0], 2, None).view(B, hh // 2, ww // 2, w.shape[0])
+        g = g.view(B, self.grid_h * self.grid_w, self.embed_dim)
+        dz = ops.latent_to_grid_bwd(g, self.decoder_input.weight)
+        grads = list(ops.latent_to_grid_wgrad(g, z))
+        for k in sorted(quads):
+            grads += quads[k]
+        return dz, grads + list(d_out)
+
     def decode_with_grad(self, z, collect=None):
         """decode(z) (the same launches, the same bits) as a differentiable function of z: backward returns d image / d z through the frozen eval-mode
         decoder, and nothing else — a decoder parameter with requires_grad=True is an error (freeze_decoder()).  Not twice differentiable.
         After train_decoder(): the same image and the same dz, bit for bit (the same walk, the same launches), and backward also accumulates `.grad` on every
-        decoder parameter: the decoder in eval mode (running statistics, not updated), conv and BatchNorm parameters learning through the fold."""
+        decoder parameter: the decoder in eval mode (running statistics, not updated), conv and BatchNorm parameters learning through the fold.
+        After train_decoder(batch_stats=True): the walk normalises with the batch's statistics and moves the running statistics, so the image is
+        no longer decode's bit for bit; the gradients are those of the reference's decoder under .train()."""
         self._check_grad_path(z)
         if self._decoder_grads:
             return _DecodeWithGrad.apply(z, self, collect, *self._decoder_params())
@@ -1034,13 +1125,14 @@ class ViTVAE(ViTVAEEncoder):
         return self._decode_backward(saved, grad_image.contiguous())
 
     # ---- training the whole model (eval mode) --------------------------------------------------------------------------
-    def train_all(self, dropout=False, stem_batch_stats=False):
-        """train_stem(batch_stats=stem_batch_stats) + train_transformer(dropout=dropout) + train_decoder(): every parameter asks for a gradient and forward_train's
-        graph reaches every one of them.  Returns all parameters (named_parameters order), for the optimizer.  The model stays in EVAL mode (see train_vit_vae);
-        stem_batch_stats=True: the stem's BatchNorm2d layers train on batch statistics all the same; the decoder's stay on running statistics."""
+    def train_all(self, dropout=False, stem_batch_stats=False, decoder_batch_stats=False):
+        """train_stem(batch_stats=stem_batch_stats) + train_transformer(dropout=dropout) + train_decoder(batch_stats=decoder_batch_stats): every parameter asks for
+        a gradient and forward_train's graph reaches every one of them.  Returns all parameters (named_parameters order), for the optimizer.  The model stays
+        in EVAL mode (see train_vit_vae); stem_batch_stats=True: the stem's BatchNorm2d layers train on batch statistics all the same (DESIGN §23);
+        decoder_batch_stats=True: so do the decoder's.  With both, every BatchNorm2d of the model trains as under the reference's .train()."""
         self.train_stem(batch_stats=stem_batch_stats)
         self.train_transformer(dropout=dropout)
-        self.train_decoder()
+        self.train_decoder(batch_stats=decoder_batch_stats)
         return list(self.parameters())
 
     def forward_train(self, x, eps=None):
@@ -1077,7 +1169,7 @@ class _DecodeWithGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, model, collect, *params):
         zd = z.detach()
-        image, saved = model._decode_walk(zd, True, collect, keep_inputs=bool(params))
+        image, saved = model._decode_walk(zd, True, collect, keep_inputs=bool(params), batch_stats=bool(params) and model._decoder_batch_stats)
         ctx.model, ctx.saved = model, saved                            # activations and folded matrices of this call: private to the node, freed with it
         ctx.z = zd.contiguous() if params else None
         ctx.save_for_backward(*params)
@@ -1105,13 +1197,17 @@ def fit_latent(model, x, z0, steps, lr, loss="sse"):
     z = z0.detach().clone().requires_grad_(True)
     opt = torch.optim.Adam([z], lr=lr)
     losses = []
-    for _ in range(int(steps)):
-        opt.zero_grad(set_to_none=True)
-        recon = model.decode_with_grad(z)
-        value = ops.sse(recon, x) if loss == "sse" else sum(ops.VesselRecon.apply(recon, x))
-        value.backward()
-        opt.step()
-        losses.append(value.detach())
+    batch_stats, model._decoder_batch_stats = model._decoder_batch_stats, False      # a latent is fitted to the decoder as inference runs it: the fold, no buffer moved
+    try:
+        for _ in range(int(steps)):
+            opt.zero_grad(set_to_none=True)
+            recon = model.decode_with_grad(z)
+            value = ops.sse(recon, x) if loss == "sse" else sum(ops.VesselRecon.apply(recon, x))
+            value.backward()
+            opt.step()
+            losses.append(value.detach())
+    finally:
+        model._decoder_batch_stats = batch_stats
     return z.detach(), [float(v) for v in torch.stack(losses).cpu()] if losses else []
 
 
@@ -1142,14 +1238,14 @@ def _check_graph_optimizer(what, optimizer):
                         f"(got {type(optimizer).__name__}" + (" with device_step=False" if isinstance(optimizer, FusedAdam) else "") + ")")
 
 
-def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False, graph=False, stem_batch_stats=False):
+def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=False, graph=False, stem_batch_stats=False, decoder_batch_stats=False):
     """The reference's ViTVAE training loop (latent_translator/engine.py:6-36), same signature plus `dropout` and `graph`: per batch["x"], zero_grad, model.forward_train,
     vit_vae_loss, backward, optimizer.step() (vit_vae_train_step).  It runs in THIS project's training regime, which is not the reference's model.train(): the model is put in eval
     mode, so every BatchNorm2d normalises with its running statistics, which are not updated (as train_decoder() and train_stem() state), and there is no
     dropout unless dropout=True: then the transformer blocks drop as the reference's do under train(), at the modules' rates, with Philox masks
     (train_transformer(dropout=True); float32 compute dtype).  stem_batch_stats=True: the conv stem's five BatchNorm2d layers normalise with
-    batch statistics and update their running statistics, as the reference's do (train_stem(batch_stats=True)); the decoder's stay on running
-    statistics.  All parameters learn (model.train_all() is called, so an optimizer built over
+    batch statistics and update their running statistics, as the reference's do (train_stem(batch_stats=True)); decoder_batch_stats=True: so do the
+    decoder's eleven (train_decoder(batch_stats=True)).  With both, BatchNorm2d runs as under the reference's model.train().  All parameters learn (model.train_all() is called, so an optimizer built over
     model.parameters() fits).  Returns the per-epoch mean losses as a list of floats (sample-weighted, read from the device once per epoch).
     graph=True (needs FusedAdam(device_step=True), else CvaeError): the step is captured once, from the first batch, as one HIP graph (GraphedViTTrainStep,
     DESIGN §19) and replayed for every batch of that shape; a batch of another shape (a ragged last one) takes the eager step.  With dropout the keys then
@@ -1157,7 +1253,7 @@ def train_vit_vae(model, loader, optimizer, device, epochs, beta=1.0, dropout=Fa
     if graph:
         _check_graph_optimizer("train_vit_vae(graph=True)", optimizer)
     model.eval()
-    model.train_all(dropout=dropout, stem_batch_stats=stem_batch_stats)
+    model.train_all(dropout=dropout, stem_batch_stats=stem_batch_stats, decoder_batch_stats=decoder_batch_stats)
     history, graphed = [], None
     for _ep in range(int(epochs)):
         total, n = [], 0

@@ -259,6 +259,24 @@ int cvae_bn2d_bwd(const void* x, const void* dy, const void* y, const float* gam
 size_t cvae_bn2d_batch_workspace_bytes(int64_t P, int64_t C);
 int cvae_bn2d_batch_fwd(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean, float* running_var,
                         int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* The forward with a residual (the BatchNorm that ends a ResBlock): cvae_bn2d_batch_fwd's arguments plus `resid`, of y's shape and dtype,
+ * 16-byte aligned.  a = resid + ((y - mean) rstd gamma + beta), the sum formed in fp32 and rounded once; the same moments and finish launches, an apply
+ * instance that reads y and resid once and writes a once.  resid with act != CVAE_ACT_NONE: CVAE_E_UNSUPPORTED (behind an activation `a` would no longer
+ * carry the sign the backward reads).  resid == NULL: cvae_bn2d_batch_fwd.  Every other check and code as there. */
+int cvae_bn2d_batch_fwd_res(const void* y, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean, float* running_var,
+                            int64_t P, int64_t C, float momentum, float eps, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream,
+                            const void* resid);
+/* The backward of a = act((y - mean) rstd gamma + beta) with batch statistics, on the forward's chunking: y, dy, a, dx channels-last [P][C]
+ * in `dtype`; gamma, mean, rstd fp32 [C] (mean / rstd as the forward left them); dgamma, dbeta fp32 [C].  With g = dy act'(a) (act' read off the activation's
+ * output a; a may be NULL when act == CVAE_ACT_NONE and is then not read) and xh = (y - mean) rstd: dbeta = sum g, dgamma = sum g xh,
+ * dx = gamma rstd (g - dbeta / P - xh dgamma / P).  Three launches: per-chunk sums (one workgroup per chunk, the chunk read once), the partials added in an
+ * order set by the chunk count alone, the apply pass (y, dy, a read once, dx written once).  No float atomics: bit-reproducible on every device.
+ * workspace: cvae_bn2d_batch_bwd_workspace_bytes(P, C) (0 for a shape the entry refuses), 4-byte aligned.  Checks, all before the first launch, with the
+ * forward's codes: shape CVAE_E_BADSHAPE; act code CVAE_E_UNSUPPORTED; a null pointer CVAE_E_NULLPTR; y, dy, a, dx not 16-byte aligned or a float array not
+ * 4-byte aligned CVAE_E_UNSUPPORTED; a short workspace CVAE_E_WORKSPACE; a dtype code other than the two CVAE_E_DTYPE. */
+size_t cvae_bn2d_batch_bwd_workspace_bytes(int64_t P, int64_t C);
+int cvae_bn2d_batch_bwd(const void* y, const void* dy, const void* a, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+                        float* dbeta, int64_t P, int64_t C, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- CausalVesselVAE inference (csrc/vessel_infer.hip): eval-mode BatchNorm2d folded into the convs, sweep reductions ---------------------
  * Fold a table of `count` (1..16, else CVAE_E_UNSUPPORTED) conv layers with the eval-mode BatchNorm2d behind them in ONE launch (host arrays
