@@ -34,14 +34,39 @@ int64_t bnb_parts(int64_t P) {
     return (P + chunk - 1) / chunk;
 }
 
-// A lane owns 8 consecutive channels (16 bytes of bf16, 32 of fp32); the 256 threads are R = 256 / (C / 8) row groups of C / 8 lanes (threads past R groups
-// idle: C / 8 need not divide 256).  Row group rg reads rows p0 + rg, p0 + rg + R, ... of the chunk, four rows in flight.  `part` row 2 g = the chunk's
-// mean, row 2 g + 1 = its M2; its count follows from g (bnb_chunk).
+// The thread layout of every kernel that walks rows.  A lane owns 8 consecutive channels c0 .. c0 + 7 (16 bytes of bf16, 32 of fp32); the 256 threads are
+// R = 256 / (C / 8) row groups of C / 8 lanes (threads past R groups idle: C / 8 need not divide 256); thread t is lane cl of row group rg.
+struct BnbLayout { int lanes, R, cl, rg, c0; };
+__device__ __forceinline__ BnbLayout bnb_layout(int C) {
+    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
+    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    return {lanes, R, cl, rg, c0};
+}
+
+// Two sums per channel over a workgroup's rows: each thread leaves its 8 channels' pair in LDS, then thread c < C adds its channel's R row-group sums in
+// group order and hands them to write(c, sum1, sum2).  BNB_INLINE: the callable is inlined with the helper, as if its text stood in the kernel.
+#define BNB_INLINE __attribute__((always_inline))
+template <typename Write>
+__device__ __forceinline__ void bnb_group_sums(float (&red)[2][256][8 + 1], const float (&s1)[8], const float (&s2)[8], const BnbLayout& L, int C, Write write) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[0][t][e] = s1[e]; red[1][t][e] = s2[e]; }
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {
+        const int l = c >> 3, e = c & 7;
+        float a1 = 0.f, a2 = 0.f;
+        for (int q = 0; q < L.R; ++q) { a1 += red[0][q * L.lanes + l][e]; a2 += red[1][q * L.lanes + l][e]; }
+        write(c, a1, a2);
+    }
+}
+
+// Row group rg reads rows p0 + rg, p0 + rg + R, ... of the chunk, four rows in flight.  `part` row 2 g = the chunk's mean, row 2 g + 1 = its M2; its count
+// follows from g (bnb_chunk).
 template <typename T>
 __global__ __launch_bounds__(256) void bn2d_batch_moments_kernel(const T* __restrict__ y, float* __restrict__ part, int64_t P, int C, int64_t chunk) {
     __shared__ float red[2][256][8 + 1];
-    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
-    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const BnbLayout L = bnb_layout(C);
+    const int R = L.R, rg = L.rg, c0 = L.c0;
     const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = (p0 + chunk < P) ? p0 + chunk : P;
     float K[8], s1[8], s2[8];
     load_f32<8>(y + p0 * C + c0, K);
@@ -65,19 +90,12 @@ __global__ __launch_bounds__(256) void bn2d_batch_moments_kernel(const T* __rest
             for (int e = 0; e < 8; ++e) { const float d = v[e] - K[e]; s1[e] += d; s2[e] += d * d; }
         }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][t][e] = s1[e]; red[1][t][e] = s2[e]; }
-    __syncthreads();
-    // thread c < C adds its channel's R row-group sums in group order: they share the shift K, so they add as they are
     const float n = (float)(p1 - p0);
-    for (int c = t; c < C; c += 256) {
-        const int l = c >> 3, e = c & 7;
-        float a1 = 0.f, a2 = 0.f;
-        for (int q = 0; q < R; ++q) { a1 += red[0][q * lanes + l][e]; a2 += red[1][q * lanes + l][e]; }
+    bnb_group_sums(red, s1, s2, L, C, [&](int c, float a1, float a2) BNB_INLINE {          // the row groups share the shift K, so their sums add as they are
         const float m1 = a1 / n;
         part[((size_t)blockIdx.x * 2) * C + c] = to_f32(y[p0 * C + c]) + m1;
         part[((size_t)blockIdx.x * 2 + 1) * C + c] = fmaxf(a2 - a1 * m1, 0.f);
-    }
+    });
 }
 
 // (na, ma, M2a) <- (na, ma, M2a) merged with (nb, mb, M2b); an empty side leaves the other as it is
@@ -91,12 +109,18 @@ __device__ __forceinline__ void bnb_merge(float& na, float& ma, float& M2a, floa
 }
 // A block serves 16 channels: thread (s, cc) merges run s of channel cc's chunks (ceil(G / BNB_SEGS) consecutive ones) in index order, then thread (0, cc)
 // merges the BNB_SEGS runs in order.  The order is a function of G alone.
+struct BnbRun { int cc, s, c, g0, g1; };        // thread (s, cc) of a finish kernel: its channel c and its run [g0, g1) of the G chunks
+__device__ __forceinline__ BnbRun bnb_run(int G) {
+    const int cc = threadIdx.x & 15, s = threadIdx.x >> 4, c = blockIdx.x * 16 + cc;
+    const int per = (G + BNB_SEGS - 1) / BNB_SEGS, g0 = s * per, g1 = (g0 + per < G) ? g0 + per : G;
+    return {cc, s, c, g0, g1};
+}
 __global__ __launch_bounds__(256) void bn2d_batch_finish_kernel(const float* __restrict__ part, int G, float* __restrict__ mean, float* __restrict__ rstd,
                                                                  float* __restrict__ running_mean, float* __restrict__ running_var, int64_t P, int C, int64_t chunk,
                                                                  float eps, float momentum) {
     __shared__ float sn[BNB_SEGS][16], sm[BNB_SEGS][16], sq[BNB_SEGS][16];
-    const int cc = threadIdx.x & 15, s = threadIdx.x >> 4, c = blockIdx.x * 16 + cc;
-    const int per = (G + BNB_SEGS - 1) / BNB_SEGS, g0 = s * per, g1 = (g0 + per < G) ? g0 + per : G;
+    const BnbRun run = bnb_run(G);
+    const int cc = run.cc, s = run.s, c = run.c, g0 = run.g0, g1 = run.g1;
     float n = 0.f, m = 0.f, M2 = 0.f;
     if (c < C)
         for (int g = g0; g < g1; ++g) {
@@ -121,8 +145,8 @@ template <typename T, int EPI>
 __global__ __launch_bounds__(256) void bn2d_batch_apply_kernel(const T* __restrict__ y, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ a, int64_t P, int C,
                                                                 int act) {
-    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
-    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const BnbLayout L = bnb_layout(C);
+    const int R = L.R, rg = L.rg, c0 = L.c0;
     if (rg >= R) return;
     float mu[8], k[8], b[8];
 #pragma unroll
@@ -154,8 +178,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void bn2d_batch_apply_res_kernel(const T* __restrict__ y, const T* __restrict__ resid, const float* __restrict__ mean,
                                                                     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                     T* __restrict__ a, int64_t P, int C) {
-    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
-    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const BnbLayout L = bnb_layout(C);
+    const int R = L.R, rg = L.rg, c0 = L.c0;
     if (rg >= R) return;
     float mu[8], k[8], b[8];
 #pragma unroll
@@ -191,8 +215,8 @@ __global__ __launch_bounds__(256) void bn2d_batch_bwd_sums_kernel(const T* __res
                                                                    const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ part,
                                                                    int64_t P, int C, int64_t chunk, int act) {
     __shared__ float red[2][256][8 + 1];
-    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
-    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const BnbLayout L = bnb_layout(C);
+    const int R = L.R, rg = L.rg, c0 = L.c0;
     const int64_t p0 = (int64_t)blockIdx.x * chunk, p1 = (p0 + chunk < P) ? p0 + chunk : P;
     float s1[8], s2[8];
 #pragma unroll
@@ -232,24 +256,18 @@ __global__ __launch_bounds__(256) void bn2d_batch_bwd_sums_kernel(const T* __res
             }
         }
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][t][e] = s1[e]; red[1][t][e] = s2[e]; }
-    __syncthreads();
-    for (int c = t; c < C; c += 256) {                                  // thread c < C adds its channel's R row-group sums in group order
-        const int l = c >> 3, e = c & 7;
-        float a1 = 0.f, a2 = 0.f;
-        for (int q = 0; q < R; ++q) { a1 += red[0][q * lanes + l][e]; a2 += red[1][q * lanes + l][e]; }
+    bnb_group_sums(red, s1, s2, L, C, [&](int c, float a1, float a2) BNB_INLINE {
         part[((size_t)blockIdx.x * 2) * C + c] = a1;
         part[((size_t)blockIdx.x * 2 + 1) * C + c] = a2;
-    }
+    });
 }
 
 // finish: the forward finish's runs (thread (s, cc) adds run s of channel cc's partials in index order, thread (0, cc) the BNB_SEGS runs in order), plain sums
 __global__ __launch_bounds__(256) void bn2d_batch_bwd_finish_kernel(const float* __restrict__ part, int G, float* __restrict__ dbeta, float* __restrict__ dgamma,
                                                                      int C) {
     __shared__ float sb[BNB_SEGS][16], sg[BNB_SEGS][16];
-    const int cc = threadIdx.x & 15, s = threadIdx.x >> 4, c = blockIdx.x * 16 + cc;
-    const int per = (G + BNB_SEGS - 1) / BNB_SEGS, g0 = s * per, g1 = (g0 + per < G) ? g0 + per : G;
+    const BnbRun run = bnb_run(G);
+    const int cc = run.cc, s = run.s, c = run.c, g0 = run.g0, g1 = run.g1;
     float b = 0.f, w = 0.f;
     if (c < C)
         for (int g = g0; g < g1; ++g) { b += part[((size_t)g * 2) * C + c]; w += part[((size_t)g * 2 + 1) * C + c]; }
@@ -267,8 +285,8 @@ __global__ __launch_bounds__(256) void bn2d_batch_bwd_apply_kernel(const T* __re
                                                                     const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                     const float* __restrict__ dbeta, const float* __restrict__ dgamma, T* __restrict__ dx, int64_t P,
                                                                     int C, int act) {
-    const int lanes = C >> 3, R = 256 / lanes, t = threadIdx.x;
-    const int cl = t % lanes, rg = t / lanes, c0 = cl * 8;
+    const BnbLayout L = bnb_layout(C);
+    const int R = L.R, rg = L.rg, c0 = L.c0;
     if (rg >= R) return;
     float mu[8], rs[8], k[8], mb[8], mg[8];
     const float fP = (float)P;
@@ -310,25 +328,35 @@ __global__ __launch_bounds__(256) void bn2d_batch_bwd_apply_kernel(const T* __re
     }
 }
 
+// The launch geometry of both directions: one workgroup per chunk (moments, sums), one per 16 channels (the finish kernels), and for an apply kernel a grid
+// over the passes of R rows, `unroll` passes per workgroup.
+struct BnbGeom {
+    int64_t chunk, passes;
+    int G;
+    dim3 chunks, finish;
+    BnbGeom(int64_t P, int C) : chunk(bnb_chunk(P)), passes((P + 256 / (C >> 3) - 1) / (256 / (C >> 3))), G((int)bnb_parts(P)), chunks((unsigned)G),
+                                finish((unsigned)((C + 15) / 16)) {}
+    dim3 apply(int unroll) const { return dim3(cvae_grid_1d(passes, unroll, 2048)); }
+};
+
 // the three launches; the entry point has checked everything but the dtype code, which with_dtype refuses before the first launch
 // resid (non-null only with act == CVAE_ACT_NONE): the residual instance of the apply pass
 int bn2d_batch_launch(const void* y, const void* resid, const float* gamma, const float* beta, void* a, float* mean, float* rstd, float* running_mean,
                       float* running_var, int64_t P, int C, float momentum, float eps, int act, int dtype, float* part, hipStream_t st) {
     return with_dtype(dtype, [&](auto tv) {
         using T = decltype(tv);
-        const int64_t chunk = bnb_chunk(P);
-        const int G = (int)bnb_parts(P), R = 256 / (C >> 3);
-        hipLaunchKernelGGL(bn2d_batch_moments_kernel<T>, dim3((unsigned)G), dim3(256), 0, st, (const T*)y, part, P, C, chunk);
-        hipLaunchKernelGGL(bn2d_batch_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float*)part, G, mean, rstd, running_mean, running_var,
-                           P, C, chunk, eps, momentum);
+        const BnbGeom geo(P, C);
+        hipLaunchKernelGGL(bn2d_batch_moments_kernel<T>, geo.chunks, dim3(256), 0, st, (const T*)y, part, P, C, geo.chunk);
+        hipLaunchKernelGGL(bn2d_batch_finish_kernel, geo.finish, dim3(256), 0, st, (const float*)part, geo.G, mean, rstd, running_mean, running_var, P, C, geo.chunk,
+                           eps, momentum);
         if (resid) {
-            hipLaunchKernelGGL(bn2d_batch_apply_res_kernel<T>, dim3(cvae_grid_1d((P + R - 1) / R, 2, 2048)), dim3(256), 0, st, (const T*)y, (const T*)resid,
-                               (const float*)mean, (const float*)rstd, gamma, beta, (T*)a, P, C);
+            hipLaunchKernelGGL(bn2d_batch_apply_res_kernel<T>, geo.apply(2), dim3(256), 0, st, (const T*)y, (const T*)resid, (const float*)mean, (const float*)rstd,
+                               gamma, beta, (T*)a, P, C);
             return launch_rc();
         }
         return with_epi(act, [&](auto epi) {
-            hipLaunchKernelGGL((bn2d_batch_apply_kernel<T, decltype(epi)::value>), dim3(cvae_grid_1d((P + R - 1) / R, 4, 2048)), dim3(256), 0, st, (const T*)y,
-                               (const float*)mean, (const float*)rstd, gamma, beta, (T*)a, P, C, act);
+            hipLaunchKernelGGL((bn2d_batch_apply_kernel<T, decltype(epi)::value>), geo.apply(4), dim3(256), 0, st, (const T*)y, (const float*)mean,
+                               (const float*)rstd, gamma, beta, (T*)a, P, C, act);
             return launch_rc();
         });
     });
@@ -341,13 +369,12 @@ int bn2d_batch_bwd_launch(const void* y, const void* dy, const void* a, const fl
         using T = decltype(tv);
         return with_bool(act != CVAE_ACT_NONE, [&](auto gated) {
             constexpr bool GATED = decltype(gated)::value;
-            const int64_t chunk = bnb_chunk(P);
-            const int G = (int)bnb_parts(P), R = 256 / (C >> 3);
-            hipLaunchKernelGGL((bn2d_batch_bwd_sums_kernel<T, GATED>), dim3((unsigned)G), dim3(256), 0, st, (const T*)y, (const T*)dy, (const T*)a, mean, rstd, part,
-                               P, C, chunk, act);
-            hipLaunchKernelGGL(bn2d_batch_bwd_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float*)part, G, dbeta, dgamma, C);
-            hipLaunchKernelGGL((bn2d_batch_bwd_apply_kernel<T, GATED>), dim3(cvae_grid_1d((P + R - 1) / R, 2, 2048)), dim3(256), 0, st, (const T*)y, (const T*)dy,
-                               (const T*)a, mean, rstd, gamma, (const float*)dbeta, (const float*)dgamma, (T*)dx, P, C, act);
+            const BnbGeom geo(P, C);
+            hipLaunchKernelGGL((bn2d_batch_bwd_sums_kernel<T, GATED>), geo.chunks, dim3(256), 0, st, (const T*)y, (const T*)dy, (const T*)a, mean, rstd, part, P, C,
+                               geo.chunk, act);
+            hipLaunchKernelGGL(bn2d_batch_bwd_finish_kernel, geo.finish, dim3(256), 0, st, (const float*)part, geo.G, dbeta, dgamma, C);
+            hipLaunchKernelGGL((bn2d_batch_bwd_apply_kernel<T, GATED>), geo.apply(2), dim3(256), 0, st, (const T*)y, (const T*)dy, (const T*)a, mean, rstd, gamma,
+                               (const float*)dbeta, (const float*)dgamma, (T*)dx, P, C, act);
             return launch_rc();
         });
     });

@@ -1850,21 +1850,26 @@ def _bn2d_rows(what, t, **like):
     return t.numel() // t.shape[-1], t.shape[-1]
 
 
+def _bn2d_bwd_prepare(what, y, g, a, weight, mean, rstd, act, a_optional=False):
+    """What bn2d_bwd and bn2d_batch_bwd (`what`, for the messages) share: the argument checks -> (P, C, whether `a` is read, g_y, dgamma, dbeta), the three
+    outputs unwritten.  a_optional: `a` is read behind an activation only, and may be None without one."""
+    reads_a = not a_optional or act not in (None, "none")
+    L.require_gpu(y, g, a, weight, mean, rstd)
+    _forward_only(what, y, g, a, weight, mean, rstd)
+    if a_optional and reads_a and a is None:
+        raise L.CvaeError(f"{what}: the activation's output `a` is needed for act={act!r}")
+    P, Cc = _bn2d_rows(what, y, g=g, **({"a": a} if reads_a else {}))
+    for k, v in (("weight", weight), ("mean", mean), ("rstd", rstd)):
+        if tuple(v.shape) != (Cc,) or v.dtype != torch.float32 or not v.is_contiguous():
+            raise L.CvaeError(f"{what}: {k} must be a contiguous fp32 [{Cc}] vector, got {tuple(v.shape)} {v.dtype}")
+    return P, Cc, reads_a, torch.empty_like(y), _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+
+
 def bn2d_batch_bwd(y, g, a, weight, mean, rstd, act):
     """bn2d_bwd's function on the forward's chunking (cvae_bn2d_batch_bwd, csrc/bn2d_batch.hip): (g_y, dgamma, dbeta) of
     a = act((y - mean) rstd weight + bias) with batch statistics, in three launches that read y, g and a twice and add their partial sums in a fixed order of
     16 runs per channel.  a may be None when act is None (it is then not read): the BatchNorm that ends a ResBlock, whose output carries the residual."""
-    gated = act not in (None, "none")
-    L.require_gpu(y, g, a, weight, mean, rstd)
-    _forward_only("bn2d_batch_bwd", y, g, a, weight, mean, rstd)
-    if gated and a is None:
-        raise L.CvaeError(f"bn2d_batch_bwd: the activation's output `a` is needed for act={act!r}")
-    P, Cc = _bn2d_rows("bn2d_batch_bwd", y, g=g, **({"a": a} if gated else {}))
-    for k, v in (("weight", weight), ("mean", mean), ("rstd", rstd)):
-        if tuple(v.shape) != (Cc,) or v.dtype != torch.float32 or not v.is_contiguous():
-            raise L.CvaeError(f"bn2d_batch_bwd: {k} must be a contiguous fp32 [{Cc}] vector, got {tuple(v.shape)} {v.dtype}")
-    gy = torch.empty_like(y)
-    dw, db = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+    P, Cc, gated, gy, dw, db = _bn2d_bwd_prepare("bn2d_batch_bwd", y, g, a, weight, mean, rstd, act, a_optional=True)
     _t, wp, wb = _scratch(lib.cvae_bn2d_batch_bwd_workspace_bytes(P, Cc), y)
     check(L.timed(f"bn2d_batch_bwd P{P} C{Cc}", lib.cvae_bn2d_batch_bwd, ptr(y), ptr(g), ptr(a) if gated else None, ptr(weight), ptr(mean), ptr(rstd), ptr(gy),
                   ptr(dw), ptr(db), P, Cc, L.act_code(act), L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_batch_bwd")
@@ -1908,14 +1913,7 @@ def bn2d_batch_fwd(y, bn, act, resid=None):
 def bn2d_bwd(y, g, a, weight, mean, rstd, act):
     """(g_y, dgamma, dbeta) of a = act((y - mean) rstd weight + bias) with batch statistics (cvae_bn2d_bwd, csrc/vessel2d.hip): y the normalisation's input, g the
     gradient of a, a the forward's output (for act'), mean / rstd as bn2d_batch_fwd (or BatchNorm2dAct's training forward) left them."""
-    L.require_gpu(y, g, a, weight, mean, rstd)
-    _forward_only("bn2d_bwd", y, g, a, weight, mean, rstd)
-    P, Cc = _bn2d_rows("bn2d_bwd", y, g=g, a=a)
-    for k, v in (("weight", weight), ("mean", mean), ("rstd", rstd)):
-        if tuple(v.shape) != (Cc,) or v.dtype != torch.float32 or not v.is_contiguous():
-            raise L.CvaeError(f"bn2d_bwd: {k} must be a contiguous fp32 [{Cc}] vector, got {tuple(v.shape)} {v.dtype}")
-    gy = torch.empty_like(y)
-    dw, db = _empty((Cc,), torch.float32, y), _empty((Cc,), torch.float32, y)
+    P, Cc, _reads_a, gy, dw, db = _bn2d_bwd_prepare("bn2d_bwd", y, g, a, weight, mean, rstd, act)
     _t, wp, wb = _scratch(lib.cvae_bn2d_workspace_bytes(P, Cc), y)
     check(L.timed(f"bn2d_bwd P{P} C{Cc}", lib.cvae_bn2d_bwd, ptr(y), ptr(g), ptr(a), ptr(weight), ptr(mean), ptr(rstd), ptr(gy), ptr(dw), ptr(db), P, Cc,
                   L.act_code(act), L.dtype_code(y.dtype), wp, wb, stream()), "bn2d_bwd")

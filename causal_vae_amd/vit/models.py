@@ -33,7 +33,8 @@ stem's backward is cvae_vit_tokens_bwd with the stem output as its gate, then pe
 derivative of the producing layer in its epilogue, then one cvae_fold_bn_conv_bwd launch; train_stem(batch_stats=True), DESIGN §23: the stem on
 batch statistics, the module still in eval mode — per layer the raw conv, cvae_bn2d_batch_fwd, and cvae_bn2d_bwd on the way back; train_decoder(batch_stats=
 True), DESIGN §24: the same for the decoder's 11 BatchNorm2d layers, with cvae_bn2d_batch_fwd_res at the end of a ResBlock and cvae_bn2d_batch_bwd on the
-way back); ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
+way back; folded and batch-statistics training share one stage loop in _decode_walk and one reverse loop each in _decode_backward and _stem_backward);
+ViTVAE.train_all / forward_train, vit_vae_loss and train_vit_vae
 are the reference's ViTVAE training loop (latent_translator/engine.py:6-36).
 The gradient with respect to the IMAGE: cls_features_vjp / encode_vjp (explicit, no graph), x.grad after cls_features_with_grad / encode_with_grad /
 forward_train of an x that asks, saliency (plain and integrated gradients) and gradcam.  They share a data-only form of the backward (_walk_backward(params=False):
@@ -57,7 +58,8 @@ STEM_CHANNELS = (32, 64, 128, 256, 256)
 # _StemKept (only when the stem trains): x (the image as the first conv reads it: its weight-gradient operand), ys (the five layer outputs: each the next
 # layer's input, its weight-gradient operand and its gate), k4 (the folded k4 weights, for the data gradients).  The batch-statistics walk (train_stem(batch_stats=
 # True)) fills the rest: ys are then the BatchNorm + LeakyReLU outputs a_j, k4 the RAW k4 weights (the k3 -> k4 zero-embedding, no scale), pre the five raw
-# conv outputs y_j, mean / rstd each layer's batch statistics as cvae_bn2d_bwd reads them; pre is None in the eval-mode (folded) walk, which is how the backward tells.
+# conv outputs y_j, mean / rstd each layer's batch statistics as cvae_bn2d_bwd reads them; pre is None in the eval-mode (folded) walk, which is how _stem_backward's
+# one loop tells whether ops.bn2d_bwd stands in front of a layer, and how _walk_backward tells whether the token launch carries the gate.
 # _BlockStep, one per transformer block: X (the block's input rows [B N, 256], norm1's input), y (norm1's output: the in-projection's operand), qkv (the packed
 # in-projection output; k and v alone [B, N, 512] in a CLS-only block), q (the CLS-only block's one query row per sample, else None), att / lse (attention's
 # output and row statistic), X1 (the stream after attention: norm2's input), y2 (norm2's output), pre / hid (the MLP's pre-activation and its GELU), B, N,
@@ -353,50 +355,31 @@ class ViTVAEEncoder(nn.Module):
         image (a dict): the result also holds `dx`, the gradient of the image, fp32 [B, 1, H, W]: the last hop is ops.conv_down_image_bwd_data on g_0
         and the first folded weight, with the dict as its keyword arguments (alpha, out, accumulate; {}: the plain form).  params=False is the data-only form: no _conv_wgrad launch and no fold_bn_conv_bwd, the data launches — hence every g_j and dx,
         bit for bit — are those of the full form.
-        A walk that kept batch statistics (kept.pre): g is the gradient of the last ACTIVATION (no gate on the token launch), see
-        _stem_backward_batch_stats."""
-        if kept.pre is not None:
-            return self._stem_backward_batch_stats(kept, g, collect, params, image)
+        A walk that kept batch statistics (kept.pre): the same loop; g is the gradient of the last ACTIVATION a_4 (no gate on the token launch), and
+        per layer ops.bn2d_bwd (cvae_bn2d_bwd on (y_j, g, a_j, gamma, mean, rstd)) turns it into g_j, the gradient of the raw conv output, plus dgamma and dbeta
+        (with params=False its two sums are still part of g_j); conv_down_bwd_data runs on the raw weight with no gate.  _conv_wgrad then gives the raw k4
+        weight's gradient, whose k3 part (the inverse of the zero-embedding) is the 3 x 3 weight's, and the conv bias's — zero in exact arithmetic (the mean is
+        subtracted), computed and returned all the same, as autograd does.  No fold_bn_conv_bwd launch."""
         ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
+        batch, table = kept.pre is not None, self._stem_fold_table()
         g = g.view(ys[-1].shape)
-        folded, gs = [None] * len(ys), [None] * len(ys)
+        folded, norms, gs = [None] * len(ys), [None] * len(ys), [None] * len(ys)
         for j in reversed(range(len(ys))):
+            if batch:
+                g, *norms[j] = ops.bn2d_bwd(kept.pre[j], g.contiguous(), ys[j], table[j][3].weight, kept.mean[j], kept.rstd[j], "leaky001")
             gs[j] = g
             if params:
                 folded[j] = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
             if j:
-                g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), ys[j - 1], "leaky001")
+                g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), *((None, None) if batch else (ys[j - 1], "leaky001")))
         if collect is not None:
             collect["stem_g"] = gs
         grads = {"dx": ops.conv_down_image_bwd_data(g, k4[0], **image)} if image is not None else {}
         if params:
-            quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(self._stem_fold_table())])
-            grads.update(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
-        return grads
-
-    @torch.no_grad()
-    def _stem_backward_batch_stats(self, kept, g, collect, params, image):
-        """_stem_backward after the batch-statistics walk.  g: the gradient of the last activation a_4.  Per layer, last to first: ops.bn2d_bwd (cvae_bn2d_bwd on
-        (y_j, g, a_j, gamma, mean, rstd)) turns it into g_y, the gradient of the raw conv output, plus dgamma and dbeta; _conv_wgrad(g_y, a_{j-1}) gives the raw
-        k4 weight's gradient, whose k3 part (the inverse of the zero-embedding) is the 3 x 3 weight's, and the conv bias's — zero in exact arithmetic (the
-        mean is subtracted), computed and returned all the same, as autograd does; conv_down_bwd_data on the raw weight, with no gate, hands the gradient of
-        a_{j-1} down.  collect: `stem_g` = the five g_y.  params=False: the data launches alone (bn2d_bwd's two sums are part of g_y)."""
-        ys, k4, dt = kept.ys, kept.k4, self.compute_dtype
-        bns = [bn for _w, _kind, _b, bn in self._stem_fold_table()]
-        g = g.view(ys[-1].shape)
-        quads, gs = [None] * len(ys), [None] * len(ys)
-        for j in reversed(range(len(ys))):
-            g, dgamma, dbeta = ops.bn2d_bwd(kept.pre[j], g.contiguous(), ys[j], bns[j].weight, kept.mean[j], kept.rstd[j], "leaky001")
-            gs[j] = g
-            if params:
-                dk4, dbias = ops._conv_wgrad(g, ys[j - 1] if j else kept.x, 2, k4[j].shape, want_sbias=True)
-                quads[j] = (dk4[:, :, :3, :3].contiguous(), dbias, dgamma, dbeta)
-            if j:
-                g = ops.conv_down_bwd_data(g, ops.pack_weight(k4[j], 2, True, dt), None, None)
-        if collect is not None:
-            collect["stem_g"] = gs
-        grads = {"dx": ops.conv_down_image_bwd_data(g, k4[0], **image)} if image is not None else {}
-        if params:
+            if batch:
+                quads = [(dk4[:, :, :3, :3].contiguous(), dbias, *norms[j]) for j, (dk4, dbias) in enumerate(folded)]
+            else:
+                quads = ops.fold_bn_conv_bwd([entry + tuple(folded[j]) for j, entry in enumerate(table)])
             grads.update(zip((k for k, _p in self._stem_named()), (d for quad in quads for d in quad)))      # four per layer, in named_parameters order
         return grads
 
@@ -837,8 +820,8 @@ _Stage = namedtuple("_Stage", "kind layers fold gates")
 # activation), mats (the backward matrix of every GEMM layer, in layer order), k4 (an "up" stage's folded k4 weight), x (the stage's input, kept only when
 # weight gradients are wanted: a ResBlock sum and the grid are no gates, so gate_in does not cover them).  The batch-statistics walk (train_decoder(batch_stats=
 # True)) fills the rest: pre = the raw conv output of every layer of the stage, mean / rstd = each layer's batch statistics as cvae_bn2d_batch_bwd
-# reads them, out = the stage's output activation; there k4 and mats come from the RAW weights and gate_in is never read.  pre is None in the eval-mode
-# (folded) walk, which is how the backward tells.
+# reads them, out = the stage's output activation; there k4 and mats come from the RAW weights and gate_in stays None (no data launch carries a gate).  pre is
+# None in the eval-mode (folded) walk, which is how _decode_backward's one loop tells where ops.bn2d_batch_bwd stands and which ending to take.
 _Step = namedtuple("_Step", "stage gate_in inner mats k4 x pre mean rstd out", defaults=(None, None, None, None))
 
 
@@ -920,52 +903,40 @@ class ViTVAE(ViTVAEEncoder):
         h = ops.latent_to_grid(z, self.decoder_input.weight, self.decoder_input.bias, self.embed_dim, dt).view(B, self.grid_h, self.grid_w, self.embed_dim)
         if collect is not None:
             collect["grid"], collect["stages"], collect["res_inner"] = h, [], []
+
+        def layer(conv, bn, act, resid=None):
+            """One conv layer and what stands behind it -> (h, pre, mean, rstd); conv(act, resid) is the layer's launch.  Folded: the launch carries the
+            activation and the residual.  Batch statistics: the raw conv, then ops.bn2d_batch_fwd with both."""
+            if not batch_stats:
+                return conv(act, resid), None, None, None
+            pre = conv(None, None)
+            a, mean, rstd = ops.bn2d_batch_fwd(pre, bn, act, resid=resid)
+            return a, pre, mean, rstd
+
         steps, gate = [], None                                         # gate: the stage's input when that is a LeakyReLU(0.01) output
         for st in plan:
-            y = k4 = None
+            inner = k4 = None
             x_in = h if keep_inputs else None
-            if batch_stats:
-                bns = [bn for _conv, bn in st.layers]
-                if st.kind == "up":
-                    k4, b = folded[st.fold[0]]
-                    _B, hh, ww, c = h.shape
-                    pre = [ops.ConvUp.apply(h.view(B, 1, hh, ww, c), k4, b, 2, None, False, False, None).view(B, 2 * hh, 2 * ww, k4.shape[1])]
-                    h, mean, rstd = ops.bn2d_batch_fwd(pre[0], bns[0], "leaky001")
-                    stats = [(mean, rstd)]
-                elif st.kind == "sub":
-                    k, = st.fold
-                    pre = [ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, None)]
-                    h, mean, rstd = ops.bn2d_batch_fwd(pre[0], bns[0], "leaky001")
-                    stats = [(mean, rstd)]
-                else:
-                    k0, k1 = st.fold
-                    y1 = ops.conv_s1(h, mats[k0], folded[k0][1], ops.CONV_S1_K3, None)
-                    y, mean1, rstd1 = ops.bn2d_batch_fwd(y1, bns[0], "leaky02")
-                    y2 = ops.conv_s1(y, mats[k1], folded[k1][1], ops.CONV_S1_K3, None)
-                    h, mean2, rstd2 = ops.bn2d_batch_fwd(y2, bns[1], None, resid=h)
-                    pre, stats = [y1, y2], [(mean1, rstd1), (mean2, rstd2)]
-                    if collect is not None:
-                        collect["res_inner"].append(y)
-                steps.append(_Step(st, None, y, [bmats[k] for k in st.fold if k in bmats], k4, x_in, pre, [m for m, _r in stats], [r for _m, r in stats], h))
-                gate = h
-                if collect is not None:
-                    collect["stages"].append(h)
-                continue
+            bns = [bn for _conv, bn in st.layers]
             if st.kind == "up":
                 k4, b = folded[st.fold[0]]
                 _B, hh, ww, c = h.shape
-                h = ops.ConvUp.apply(h.view(B, 1, hh, ww, c), k4, b, 2, "leaky001", False, False, None).view(B, 2 * hh, 2 * ww, k4.shape[1])
+                x5, shape = h.view(B, 1, hh, ww, c), (B, 2 * hh, 2 * ww, k4.shape[1])
+                outs = [layer(lambda act, _r: ops.ConvUp.apply(x5, k4, b, 2, act, False, False, None).view(shape), bns[0], "leaky001")]
             elif st.kind == "sub":
                 k, = st.fold
-                h = ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, "leaky001")
+                outs = [layer(lambda act, _r: ops.conv_s1(h, mats[k], folded[k][1], ops.CONV_S1_SUBPIXEL, act), bns[0], "leaky001")]
             else:
                 k0, k1 = st.fold
-                y = ops.conv_s1(h, mats[k0], folded[k0][1], ops.CONV_S1_K3, "leaky02")
-                h = ops.conv_s1(y, mats[k1], folded[k1][1], ops.CONV_S1_K3, None, resid=h)
+                first = layer(lambda act, _r: ops.conv_s1(h, mats[k0], folded[k0][1], ops.CONV_S1_K3, act), bns[0], "leaky02")
+                inner = first[0]
+                outs = [first, layer(lambda act, r: ops.conv_s1(inner, mats[k1], folded[k1][1], ops.CONV_S1_K3, act, resid=r), bns[1], None, resid=h)]
                 if collect is not None:
-                    collect["res_inner"].append(y)
-            if save:
-                steps.append(_Step(st, gate, y, [bmats[k] for k in st.fold if k in bmats], k4, x_in))
+                    collect["res_inner"].append(inner)
+            h = outs[-1][0]
+            if save:                                                   # the batch-statistics walk alone fills pre, mean, rstd and out, and keeps no gate
+                stats = dict(pre=[o[1] for o in outs], mean=[o[2] for o in outs], rstd=[o[3] for o in outs], out=h) if batch_stats else {}
+                steps.append(_Step(st, None if batch_stats else gate, inner, [bmats[k] for k in st.fold if k in bmats], k4, x_in, **stats))
             gate = h if st.gates else None
             if collect is not None:
                 collect["stages"].append(h)
@@ -1020,27 +991,43 @@ class ViTVAE(ViTVAEEncoder):
         with respect to a transposed conv's PRE-activation (the producing epilogue applied leaky001' from the saved output) or to a ResBlock's output; no
         activation-backward launch.
         z (the walk's latent; the walk ran with keep_inputs): returns (dz, gradients of _decoder_params() in that order) — the same launches for dz, and next to
-        them each layer's weight gradient from its input and the `g` of its pre-activation, then ONE launch back through the fold."""
+        them each layer's weight gradient from its input and the `g` of its pre-activation, then ONE launch back through the fold.
+        After the batch-statistics walk (steps[..].pre; always with z): the same loop, and `g` is the gradient of a stage's output ACTIVATION — no
+        data-gradient launch carries a gate (gate_in is None there, a ResBlock's inner gate is left out); the activation's derivative is ops.bn2d_batch_bwd's,
+        which turns g into the gradient of the raw conv output plus dgamma and dbeta.  The weight gradients are then the raw weights' ("up": the 3 x 3 part of
+        the k4 weight's, as cvae_fold_bn_conv_bwd picks it); the conv biases' are zero in exact arithmetic (the mean is subtracted), computed and returned all
+        the same, as autograd does.  No fold_bn_conv_bwd launch."""
         steps, out_conv, out_gate = saved
-        if steps[0].pre is not None:
-            return self._decode_backward_batch_stats(saved, g_img, z)
+        batch = steps[0].pre is not None
         dt = self.compute_dtype
         B = g_img.shape[0]
-        folded = {}                                                    # fold-table position -> (gradient of the folded weight, of the folded bias)
+        folded, norms = {}, {}                                         # fold-table position -> (gradient of the layer's weight, of its bias); -> (dgamma, dbeta)
+
+        def through_norm(s, i, g, a, act):
+            """The gradient of layer i's conv output from g, the gradient of the activation `a` behind its BatchNorm2d; the folded walk has no such hop."""
+            if batch:
+                g, *norms[s.stage.fold[i]] = ops.bn2d_batch_bwd(s.pre[i], g, a, s.stage.layers[i][1].weight, s.mean[i], s.rstd[i], act)
+            return g
+
         d_out = ops.conv_s1_c1_wgrad(out_gate, g_img) if z is not None else None
-        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, out_gate, "leaky001", dt)
+        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, *((None, None) if batch else (out_gate, "leaky001")), dt)
         for s in reversed(steps):
             act = "leaky001" if s.gate_in is not None else None
+            if s.stage.kind == "res":
+                g2 = through_norm(s, 1, g, None, None)
+                t = ops.conv_s1_bwd_data(g2, s.mats[1], ops.CONV_S1_K3, **({} if batch else {"gate": s.inner, "gate_act": "leaky02"}))
+                if z is not None:
+                    folded[s.stage.fold[1]] = ops.conv_s1_wgrad(s.inner, g2, ops.CONV_S1_K3)
+                t = through_norm(s, 0, t, s.inner, "leaky02")
+                if z is not None:
+                    folded[s.stage.fold[0]] = ops.conv_s1_wgrad(s.x, t, ops.CONV_S1_K3)
+                g = ops.conv_s1_bwd_data(t, s.mats[0], ops.CONV_S1_K3, resid=g, gate=s.gate_in, gate_act=act)
+                continue
+            g = through_norm(s, 0, g, s.out, "leaky001")
             if s.stage.kind == "sub":
                 if z is not None:
                     folded[s.stage.fold[0]] = ops.conv_s1_wgrad(s.x, g, ops.CONV_S1_SUBPIXEL)
                 g = ops.conv_s1_bwd_data(g, s.mats[0], ops.CONV_S1_SUBPIXEL_T, cin=s.stage.layers[0][0].in_channels, gate=s.gate_in, gate_act=act)
-            elif s.stage.kind == "res":
-                t = ops.conv_s1_bwd_data(g, s.mats[1], ops.CONV_S1_K3, gate=s.inner, gate_act="leaky02")
-                if z is not None:
-                    folded[s.stage.fold[1]] = ops.conv_s1_wgrad(s.inner, g, ops.CONV_S1_K3)
-                    folded[s.stage.fold[0]] = ops.conv_s1_wgrad(s.x, t, ops.CONV_S1_K3)
-                g = ops.conv_s1_bwd_data(t, s.mats[0], ops.CONV_S1_K3, resid=g, gate=s.gate_in, gate_act=act)
             else:
                 w = s.k4
                 _B, hh, ww, c = g.shape
@@ -1052,50 +1039,15 @@ class ViTVAE(ViTVAEEncoder):
         if z is None:
             return dz
         grads = list(ops.latent_to_grid_wgrad(g, z))
-        kinds = {"up": ops.FOLD_CONVT_K3S2, "sub": ops.FOLD_CONVT_K3S2_SUBPIXEL, "res": ops.FOLD_CONV_K3S1}
-        table = [(conv.weight, kinds[s.stage.kind], conv.bias, bn) + tuple(folded[k]) for s in steps for (conv, bn), k in zip(s.stage.layers, s.stage.fold)]
-        for quad in ops.fold_bn_conv_bwd(table):
-            grads += quad
-        return dz, grads + list(d_out)
-
-    def _decode_backward_batch_stats(self, saved, g_img, z):
-        """_decode_backward after the batch-statistics walk -> (dz, gradients of _decoder_params() in that order).  `g` is the gradient of a
-        stage's output ACTIVATION: no data-gradient launch carries a gate, the activation's derivative is ops.bn2d_batch_bwd's, which turns g into the gradient
-        of the raw conv output plus dgamma and dbeta.  The weight gradients are the raw weights' ("up": the 3 x 3 part of the k4 weight's, as
-        cvae_fold_bn_conv_bwd picks it); the conv biases' are zero in exact arithmetic (the mean is subtracted), computed and returned all the same, as autograd
-        does.  No fold_bn_conv_bwd launch."""
-        steps, out_conv, out_in = saved
-        dt = self.compute_dtype
-        B = g_img.shape[0]
-        quads = {}                                                     # fold-table position -> (dW, dbias, dgamma, dbeta)
-        d_out = ops.conv_s1_c1_wgrad(out_in, g_img)
-        g = ops.conv_s1_c1_bwd_data(g_img, out_conv.weight, None, None, dt)
-        for s in reversed(steps):
-            st = s.stage
-            bns = [bn for _conv, bn in st.layers]
-            if st.kind == "res":
-                g2, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[1], g, None, bns[1].weight, s.mean[1], s.rstd[1], None)
-                quads[st.fold[1]] = tuple(ops.conv_s1_wgrad(s.inner, g2, ops.CONV_S1_K3)) + (dgamma, dbeta)
-                t = ops.conv_s1_bwd_data(g2, s.mats[1], ops.CONV_S1_K3)
-                g1, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[0], t, s.inner, bns[0].weight, s.mean[0], s.rstd[0], "leaky02")
-                quads[st.fold[0]] = tuple(ops.conv_s1_wgrad(s.x, g1, ops.CONV_S1_K3)) + (dgamma, dbeta)
-                g = ops.conv_s1_bwd_data(g1, s.mats[0], ops.CONV_S1_K3, resid=g)
-                continue
-            gy, dgamma, dbeta = ops.bn2d_batch_bwd(s.pre[0], g, s.out, bns[0].weight, s.mean[0], s.rstd[0], "leaky001")
-            if st.kind == "sub":
-                quads[st.fold[0]] = tuple(ops.conv_s1_wgrad(s.x, gy, ops.CONV_S1_SUBPIXEL)) + (dgamma, dbeta)
-                g = ops.conv_s1_bwd_data(gy, s.mats[0], ops.CONV_S1_SUBPIXEL_T, cin=st.layers[0][0].in_channels)
-            else:
-                w = s.k4
-                _B, hh, ww, c = gy.shape
-                dk4, dbias = ops._conv_wgrad(s.x.view(B, 1, hh // 2, ww // 2, w.shape[0]), gy.view(B, 1, hh, ww, c), 2, w.shape, want_lbias=True)
-                quads[st.fold[0]] = (dk4[:, :, :3, :3].contiguous(), dbias, dgamma, dbeta)
-                g = ops._conv_down(gy.view(B, 1, hh, ww, c), ops.pack_weight(w, 2, False, dt), None, None, w.shape[0], 2, None).view(B, hh // 2, ww // 2, w.shape[0])
-        g = g.view(B, self.grid_h * self.grid_w, self.embed_dim)
-        dz = ops.latent_to_grid_bwd(g, self.decoder_input.weight)
-        grads = list(ops.latent_to_grid_wgrad(g, z))
-        for k in sorted(quads):
-            grads += quads[k]
+        layers = [(s.stage.kind, conv, bn, k) for s in steps for (conv, bn), k in zip(s.stage.layers, s.stage.fold)]
+        if batch:
+            for kind, _conv, _bn, k in layers:
+                dw, dbias = folded[k]
+                grads += [dw[:, :, :3, :3].contiguous() if kind == "up" else dw, dbias, *norms[k]]
+        else:
+            kinds = {"up": ops.FOLD_CONVT_K3S2, "sub": ops.FOLD_CONVT_K3S2_SUBPIXEL, "res": ops.FOLD_CONV_K3S1}
+            for quad in ops.fold_bn_conv_bwd([(conv.weight, kinds[kind], conv.bias, bn) + tuple(folded[k]) for kind, conv, bn, k in layers]):
+                grads += quad
         return dz, grads + list(d_out)
 
     def decode_with_grad(self, z, collect=None):
