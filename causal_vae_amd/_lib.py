@@ -28,7 +28,7 @@ if not os.path.exists(LIB_PATH):
         "(or `make -C causal_vae_amd/csrc`).  causal_vae_amd has no CPU / eager fallback.")
 lib = C.CDLL(LIB_PATH)
 
-_p, _i64, _i, _f, _sz, _u64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t, C.c_uint64
+_p, _i64, _i, _f, _sz, _u64, _d = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t, C.c_uint64, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/cvae_hip.h one to one.
 SIGNATURES = {
@@ -191,6 +191,16 @@ SIGNATURES = {
     "cvae_bottleneck_bwd": [_p] * 12 + [_i, _p, _p, _p, _p, _i, _p, _p, _p],
     "cvae_bottleneck_bn_local_stats": [_p] * 5 + [_i64, _i64, _i64, _p],
     "cvae_bottleneck_bn_bwd_finish": [_p] * 7 + [_i, _p],
+    "cvae_col_means_f64_workspace_bytes": [_i64, _i64],
+    "cvae_col_means_f64": [_p, _i64, _i64, _i64, _p, _p, _sz, _p],
+    "cvae_ridge_gram_f64_workspace_bytes": [_i64] * 3,
+    "cvae_ridge_gram_f64": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _d, _p, _p, _p, _sz, _p],
+    "cvae_chol_f64": [_p, _i64, _p, _p],
+    "cvae_trsm_f64": [_p, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i, _p],
+    "cvae_ridge_loo_f64": [_p, _i64, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p],
+    "cvae_ridge_predict_f64": [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _p],
+    "cvae_ranking_stats_f64": [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p],
+    "cvae_group_means_resampled_f64": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p],
 }
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
@@ -201,7 +211,7 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz, "cvae_mhsa_bwd_workspace_bytes": _sz,
             "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz,
-            "cvae_mhsa_relevance_step_workspace_bytes": _sz}
+            "cvae_mhsa_relevance_step_workspace_bytes": _sz, "cvae_col_means_f64_workspace_bytes": _sz, "cvae_ridge_gram_f64_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

@@ -3103,3 +3103,143 @@ def mlp_heads_train(panels, layers, split=None, clamp0=None, clamp1=None, eps=No
     values), act{l}, preclamp (the last layer's output before the clamps)."""
     call = _HeadsCall("mlp_heads_train", True, panels, layers, split, clamp0, clamp1, eps)
     return _MlpHeadsTrain.apply(call, collect, *panels, *call.params)
+
+
+# ---- the latent translator (csrc/ridge.hip, DESIGN §25): float64 throughout ----
+class RidgeFit:
+    """What ridge_fit_loo returns: coef [F, d], intercept [F], fitted [N, F], loo [N, F] (the leave-one-out predictions), leverage [N], r2 [F], corr [F]:
+    float64 device tensors; info: the Cholesky's status (0: factorised)."""
+    __slots__ = ("coef", "intercept", "fitted", "loo", "leverage", "r2", "corr", "info")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def _f64_rows(what, name, t, cols=None):
+    """a float64 matrix with contiguous rows -> its row stride in elements"""
+    if t.dim() != 2 or t.dtype != torch.float64 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise L.CvaeError(f"{what}: {name} must be a float64 matrix with contiguous rows, got {tuple(t.shape)} {t.dtype} strides {tuple(t.stride())}")
+    if cols is not None and t.shape[1] != cols:
+        raise L.CvaeError(f"{what}: {name} must have {cols} columns, got {tuple(t.shape)}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _f64_ws(nbytes, like):
+    t = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=like.device)
+    return t, t.data_ptr(), nbytes
+
+
+def col_means_f64(x):
+    """Column means of a float64 matrix with contiguous rows (cvae_col_means_f64): per-chunk sums in row order, the chunks added in order."""
+    zs = _f64_rows("col_means_f64", "x", x)
+    N, Cc = x.shape
+    if N < 1 or Cc < 1:
+        raise L.CvaeError(f"col_means_f64: a non-empty matrix expected, got {tuple(x.shape)}")
+    L.require_gpu(x)
+    mean = _empty((Cc,), torch.float64, x)
+    _t, wp, wb = _f64_ws(lib.cvae_col_means_f64_workspace_bytes(N, Cc), x)
+    check(lib.cvae_col_means_f64(ptr(x), N, Cc, zs, ptr(mean), wp, wb, stream()), "col_means_f64")
+    return mean
+
+
+def ranking_stats_f64(Y, P):
+    """(r2 [F], corr [F]) of the predictions P against the truth Y, both float64 [N, F] (cvae_ranking_stats_f64): the rules of the reference's
+    latent_translator/analysis.py:55-68, sklearn's r2 for a constant truth and a correlation of 0 below a standard deviation of 1e-12 included."""
+    ys, ps = _f64_rows("ranking_stats_f64", "Y", Y), _f64_rows("ranking_stats_f64", "P", P, cols=Y.shape[1])
+    N, F = Y.shape
+    if P.shape[0] != N or N < 1 or F < 1:
+        raise L.CvaeError(f"ranking_stats_f64: two non-empty matrices of one shape expected, got {tuple(Y.shape)} and {tuple(P.shape)}")
+    L.require_gpu(Y, P)
+    r2, corr = _empty((F,), torch.float64, Y), _empty((F,), torch.float64, Y)
+    check(lib.cvae_ranking_stats_f64(ptr(Y), ys, ptr(P), ps, N, F, ptr(r2), ptr(corr), stream()), "ranking_stats_f64")
+    return r2, corr
+
+
+def ridge_fit_loo(Z, M, alpha):
+    """The Ridge translator Z [N, d] -> M [N, F] with an unpenalised intercept (sklearn's Ridge(alpha, fit_intercept=True)) and its EXACT leave-one-out
+    predictions from one Cholesky factorisation (the reference refits N times, latent_translator/analysis.py:36-48), all in float64 on the device:
+    column means, the centred Gram matrix A = Xc^T Xc + alpha I on the fp64 MFMA, A = L L^T, T = L^-1 Xc^T (the leverages h = 1 / N + column norms of T),
+    W = A^-1 Xc^T Yc by two more solves, then fitted = mbar + Xc W, loo = M - (M - fitted) / (1 - h) and the ranking statistics of loo against M.
+    Z: float32 or float64 (float32 is widened with .double(), which is exact); M is converted to float64.  Returns a RidgeFit.  The one host read is the
+    Cholesky's info, at the end: non-zero (a pivot <= 0 or NaN, e.g. a NaN in Z) is a CvaeError naming the column."""
+    what = "ridge_fit_loo"
+    if Z.dim() != 2 or M.dim() != 2:
+        raise L.CvaeError(f"{what}: Z [N, d] and M [N, F] expected, got {tuple(Z.shape)} and {tuple(M.shape)}")
+    if Z.dtype not in (torch.float32, torch.float64):
+        raise L.CvaeError(f"{what}: Z must be float32 or float64, got {Z.dtype}")
+    N, d = Z.shape
+    F = M.shape[1]
+    if M.shape[0] != N:
+        raise L.CvaeError(f"{what}: Z has {N} rows, M has {M.shape[0]}")
+    if N < 2:
+        raise L.CvaeError(f"{what}: at least 2 samples expected (leave-one-out leaves N - 1), got N = {N}")
+    if d < 1 or d > 1024:
+        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected (the blocked Cholesky's limit), got d = {d}")
+    if F < 1:
+        raise L.CvaeError(f"{what}: at least one feature column expected, got M {tuple(M.shape)}")
+    alpha = float(alpha)
+    if not (alpha > 0.0 and math.isfinite(alpha)):
+        raise L.CvaeError(f"{what}: alpha must be positive and finite (the centred Gram matrix is singular without it), got {alpha}")
+    L.require_gpu(Z, M)
+    Z, M = Z.detach().double().contiguous(), M.detach().double().contiguous()
+    zs, ms = _f64_rows(what, "Z", Z), _f64_rows(what, "M", M)
+    zbar, mbar = col_means_f64(Z), col_means_f64(M)
+    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    A, R = new(d, d), new(d, F)
+    _t, wp, wb = _f64_ws(lib.cvae_ridge_gram_f64_workspace_bytes(N, d, F), Z)
+    check(L.timed(f"ridge_gram N{N} d{d} F{F}", lib.cvae_ridge_gram_f64, ptr(Z), zs, ptr(zbar), ptr(M), ms, ptr(mbar), N, d, F, alpha, ptr(A), ptr(R), wp, wb,
+                  stream()), "ridge_gram_f64")
+    info = _empty((1,), torch.int32, Z)
+    check(L.timed(f"chol d{d}", lib.cvae_chol_f64, ptr(A), d, ptr(info), stream()), "chol_f64")
+    T = new(d, N)
+    check(lib.cvae_trsm_f64(ptr(A), d, ptr(Z), 1, zs, ptr(zbar), ptr(T), N, d, N, 0, stream()), "trsm_f64")          # T = L^-1 Xc^T
+    check(lib.cvae_trsm_f64(ptr(A), d, ptr(R), F, 1, None, ptr(R), F, d, F, 0, stream()), "trsm_f64")                 # R <- L^-1 R
+    check(lib.cvae_trsm_f64(ptr(A), d, ptr(R), F, 1, None, ptr(R), F, d, F, 1, stream()), "trsm_f64")                 # R <- L^-T R = W
+    out = dict(leverage=new(N), fitted=new(N, F), loo=new(N, F), coef=new(F, d), intercept=new(F))
+    check(lib.cvae_ridge_loo_f64(ptr(Z), zs, ptr(zbar), ptr(M), ms, ptr(mbar), ptr(R), ptr(T), N, d, F, ptr(out["leverage"]), ptr(out["fitted"]), ptr(out["loo"]),
+                                 ptr(out["coef"]), ptr(out["intercept"]), stream()), "ridge_loo_f64")
+    out["r2"], out["corr"] = ranking_stats_f64(M, out["loo"])
+    code = int(info.item())
+    if code != 0:
+        raise L.CvaeError(f"{what}: the Cholesky factorisation of Xc^T Xc + alpha I failed at column {code - 1} (info = {code}): a pivot that is <= 0 or NaN "
+                          "(a NaN or an infinity in Z?)")
+    return RidgeFit(info=code, **out)
+
+
+def ridge_predict(Z, coef, intercept):
+    """intercept + Z coef^T in float64 (cvae_ridge_predict_f64): Z [N, d] float32 or float64, coef [F, d], intercept [F] float64 -> [N, F] float64."""
+    what = "ridge_predict"
+    if Z.dim() != 2 or coef.dim() != 2 or intercept.dim() != 1 or coef.shape[1] != Z.shape[1] or intercept.shape[0] != coef.shape[0]:
+        raise L.CvaeError(f"{what}: Z [N, d], coef [F, d] and intercept [F] expected, got {tuple(Z.shape)}, {tuple(coef.shape)}, {tuple(intercept.shape)}")
+    if Z.dtype not in (torch.float32, torch.float64) or coef.dtype != torch.float64 or intercept.dtype != torch.float64:
+        raise L.CvaeError(f"{what}: Z float32 or float64 and float64 coefficients expected, got {Z.dtype}, {coef.dtype}, {intercept.dtype}")
+    N, d = Z.shape
+    F = coef.shape[0]
+    if d < 1 or d > 1024 or F < 1:
+        raise L.CvaeError(f"{what}: 1 <= d <= 1024 and F >= 1 expected, got d = {d}, F = {F}")
+    L.require_gpu(Z, coef, intercept)
+    Z, coef, intercept = Z.detach().double().contiguous(), coef.contiguous(), intercept.contiguous()
+    out = _empty((N, F), torch.float64, Z)
+    check(lib.cvae_ridge_predict_f64(ptr(Z), d, ptr(coef), ptr(intercept), N, d, F, ptr(out), stream()), "ridge_predict_f64")
+    return out
+
+
+def group_means_resampled(Z, codes, idx, G):
+    """(means [n_boot, G, d] float64, counts [n_boot, G] int32): for every bootstrap b and group g the mean, in index order, of the rows Z[idx[b, i]] whose
+    codes[idx[b, i]] == g (cvae_group_means_resampled_f64; the reference's compute_group_means(Z[idx], groups[idx]) for every draw at once,
+    latent_translator/analysis.py:139-142).  Z [N, d] float32 or float64, codes [N] and idx [n_boot, N] integer tensors.  An empty group: a zero row, count 0."""
+    what = "group_means_resampled"
+    if Z.dim() != 2 or codes.dim() != 1 or idx.dim() != 2 or codes.shape[0] != Z.shape[0] or idx.shape[1] != Z.shape[0]:
+        raise L.CvaeError(f"{what}: Z [N, d], codes [N] and idx [n_boot, N] expected, got {tuple(Z.shape)}, {tuple(codes.shape)}, {tuple(idx.shape)}")
+    if Z.dtype not in (torch.float32, torch.float64) or codes.dtype.is_floating_point or idx.dtype.is_floating_point:
+        raise L.CvaeError(f"{what}: Z float32 or float64, integer codes and indices expected, got {Z.dtype}, {codes.dtype}, {idx.dtype}")
+    N, d = Z.shape
+    n_boot, G = idx.shape[0], int(G)
+    if N < 1 or d < 1 or d > 65536 or G < 1 or G > 65535 or n_boot > 65535:
+        raise L.CvaeError(f"{what}: N >= 1, 1 <= d <= 65536, 1 <= G <= 65535 and n_boot <= 65535 expected, got N = {N}, d = {d}, G = {G}, n_boot = {n_boot}")
+    L.require_gpu(Z, codes, idx)
+    Z, codes, idx = Z.detach().double().contiguous(), codes.to(torch.int32).contiguous(), idx.to(torch.int32).contiguous()
+    out, counts = _empty((n_boot, G, d), torch.float64, Z), _empty((n_boot, G), torch.int32, Z)
+    check(lib.cvae_group_means_resampled_f64(ptr(Z), d, ptr(codes), ptr(idx), N, d, G, n_boot, ptr(out), ptr(counts), stream()), "group_means_resampled_f64")
+    return out, counts

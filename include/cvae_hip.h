@@ -948,6 +948,55 @@ int cvae_scale(float* g, int64_t n, const float* scale, void* stream);
 /* *scale = min(1, max_norm / (sqrt(*sqnorm) + 1e-6))   (clip_grad_norm_ coefficient, on device) */
 int cvae_clip_coef(const float* sqnorm, float* scale, float max_norm, void* stream);
 
+/* ---- The latent translator (csrc/ridge.hip): the reference's latent_translator/analysis.py:11-82 (a Ridge regression from the latents
+ * Z [N][d] to the morphology table M [N][F], its leave-one-out ranking) and the group means of :91-165 (the group-contrast bootstrap).  FLOAT64 ONLY: every
+ * array below is double, row-major, 8-byte aligned (else CVAE_E_UNSUPPORTED); row strides are in elements and at least the row length (else CVAE_E_BADSHAPE).
+ * Contract, as everywhere: enqueue-only on `stream`; the caller owns every buffer and workspace; every check precedes the first launch; no float atomics, no
+ * workgroup waits on another, every sum in one fixed order, every grid a function of the shape alone: two runs give equal bits.
+ * Limits: 2 <= N < 2^31, 1 <= d <= 1024, 1 <= F < 2^21, N F < 2^38 (else CVAE_E_BADSHAPE); a null pointer: CVAE_E_NULLPTR; a workspace below its query:
+ * CVAE_E_WORKSPACE.
+ * The leave-one-out prediction of a ridge with an unpenalised intercept is exact in closed form: with Xc = Z - zbar, A = Xc^T Xc + alpha I = L L^T,
+ * W = A^-1 Xc^T (M - mbar), Yhat = mbar + Xc W and h_i = 1 / N + xc_i^T A^-1 xc_i = 1 / N + |L^-1 xc_i|^2, the fit without row i predicts
+ * p_i = y_i - (y_i - yhat_i) / (1 - h_i).  One Gram matrix, one factorisation and three triangular solves replace the reference's N fits.
+ *   cvae_col_means_f64       mean[c] = (sum over rows, chunk by chunk in row order, the chunks in order) / N of x [N][C] (1 <= N, C < 2^31).
+ *   cvae_ridge_gram_f64      A [d][d] = Xc^T Xc + alpha I (both triangles written, bitwise symmetric) and R [d][F] = Xc^T (M - mbar) on v_mfma_f64_16x16x4_f64.  The
+ *                            means are subtracted on load (mean first, then centred products).  The rows are split into ceil(N / chunk) <= 16 chunks, chunk the
+ *                            smallest multiple of 256 that allows it; the chunks' partial products [chunks][d][d + F] go to `workspace` and a finish launch adds
+ *                            them in chunk order.  alpha <= 0, NaN or infinite: CVAE_E_BADSHAPE (the centred Gram matrix is singular without it).
+ *   cvae_chol_f64            A = L L^T in place, lower triangle (the strict upper triangle is left as it was), 1 <= d <= 1024, in blocks of 64 columns: the
+ *                            panel (one workgroup), the rows below it, the trailing update — three launches per block and nothing that waits across workgroups.
+ *                            *info (device int) = 0, or column + 1 of the first pivot that is <= 0 or NaN; the entry then still runs to its end without
+ *                            faulting and that column and every later one are NaN.
+ *   cvae_trsm_f64            transpose == 0: L T = B by forward substitution; transpose == 1: L^T W = B by back substitution; L [d][>= d] lower triangular (its
+ *                            upper triangle is not read), B and the result [d][n], 1 <= n < 2^31, one thread per column.  B is read as
+ *                            in[k * in_row_stride + c * in_col_stride] - row_shift[k] (row_shift may be NULL), so the right-hand side Xc^T is Z itself with
+ *                            strides (1, z_stride) and row_shift = zbar.  in == out is allowed element for element only (in_row_stride == ldo, in_col_stride == 1).
+ *   cvae_ridge_loo_f64       from W [d][F] (the solution) and T [d][N] = L^-1 Xc^T: leverage [N] = 1 / N + sum_k T[k][i]^2, fitted [N][F] = mbar + Xc W,
+ *                            loo [N][F] = M - (M - fitted) / (1 - leverage), coef [F][d] = W^T, intercept [F] = mbar - zbar^T W.  Three launches.
+ *   cvae_ridge_predict_f64   out [N][F] = intercept + Z coef^T (N == 0 is CVAE_OK, nothing is launched).
+ *   cvae_ranking_stats_f64   per feature j of Y (the truth) and P (the leave-one-out predictions), both [N][F], the rules of analysis.py:55-68:
+ *                            r2 = 1 - sum (y - p)^2 / sum (y - ybar)^2, and where that denominator is 0 sklearn's value (1 if the numerator is 0 too, else 0);
+ *                            corr = the Pearson correlation, clipped to [-1, 1] as numpy.corrcoef does, and 0 where the population standard deviation of either
+ *                            side is below 1e-12.  One workgroup per feature, 1 <= N.
+ *   cvae_group_means_resampled_f64   out [n_boot][G][d] = the mean over i, in index order, of Z[idx[b][i]] whose codes[idx[b][i]] == g, counts [n_boot][G] (int)
+ *                            how many there were; an empty group gives a zero row and count 0.  codes [N] and idx [n_boot][N] are int (4-byte aligned); an index
+ *                            outside [0, N) or a code outside [0, G) belongs to no group.  1 <= d <= 65536, 1 <= G <= 65535, n_boot <= 65535 (0: CVAE_OK, nothing
+ *                            is launched). */
+size_t cvae_col_means_f64_workspace_bytes(int64_t N, int64_t C);
+int cvae_col_means_f64(const double* x, int64_t N, int64_t C, int64_t stride, double* mean, void* workspace, size_t workspace_bytes, void* stream);
+size_t cvae_ridge_gram_f64_workspace_bytes(int64_t N, int64_t d, int64_t F);
+int cvae_ridge_gram_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N, int64_t d,
+                        int64_t F, double alpha, double* A, double* R, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_chol_f64(double* A, int64_t d, int* info, void* stream);
+int cvae_trsm_f64(const double* L, int64_t ldl, const double* in, int64_t in_row_stride, int64_t in_col_stride, const double* row_shift, double* out, int64_t ldo,
+                  int64_t d, int64_t n, int transpose, void* stream);
+int cvae_ridge_loo_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, const double* W,
+                       const double* T, int64_t N, int64_t d, int64_t F, double* leverage, double* fitted, double* loo, double* coef, double* intercept, void* stream);
+int cvae_ridge_predict_f64(const double* Z, int64_t z_stride, const double* coef, const double* intercept, int64_t N, int64_t d, int64_t F, double* out, void* stream);
+int cvae_ranking_stats_f64(const double* Y, int64_t y_stride, const double* P, int64_t p_stride, int64_t N, int64_t F, double* r2, double* corr, void* stream);
+int cvae_group_means_resampled_f64(const double* Z, int64_t z_stride, const int* codes, const int* idx, int64_t N, int64_t d, int64_t G, int64_t n_boot, double* out,
+                                   int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
