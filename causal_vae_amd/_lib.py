@@ -201,6 +201,14 @@ SIGNATURES = {
     "cvae_ridge_predict_f64": [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _p],
     "cvae_ranking_stats_f64": [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p],
     "cvae_group_means_resampled_f64": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p],
+    "cvae_eigh_max_sweeps": [],
+    "cvae_eigh_f64_workspace_bytes": [_i64],
+    "cvae_eigh_f64": [_p, _i64, _i64, _p, _p, _i64, _p, _p, _sz, _p],
+    "cvae_centered_gram_f64_workspace_bytes": [_i64] * 3,
+    "cvae_centered_gram_f64": [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p],
+    "cvae_centered_matmul_f64": [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p],
+    "cvae_ridge_path_f64": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "cvae_pca_components_f64": [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
@@ -211,7 +219,8 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_s1_weight_elems": _i64, "cvae_latent_to_grid_bwd_workspace_bytes": _sz,
             "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz, "cvae_mhsa_bwd_workspace_bytes": _sz,
             "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz,
-            "cvae_mhsa_relevance_step_workspace_bytes": _sz, "cvae_col_means_f64_workspace_bytes": _sz, "cvae_ridge_gram_f64_workspace_bytes": _sz}
+            "cvae_mhsa_relevance_step_workspace_bytes": _sz, "cvae_col_means_f64_workspace_bytes": _sz, "cvae_ridge_gram_f64_workspace_bytes": _sz,
+            "cvae_eigh_f64_workspace_bytes": _sz, "cvae_centered_gram_f64_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

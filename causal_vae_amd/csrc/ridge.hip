@@ -1,6 +1,7 @@
 // ridge.hip — the latent translator (the reference's latent_translator/analysis.py:11-82, 91-165): a Ridge regression from the
 // latents Z [N, d] to the morphology table M [N, F] with an unpenalised intercept, its EXACT leave-one-out predictions from one factorisation, the ranking
-// statistics of those predictions, and the resampled group means of the group-contrast bootstrap.  Everything here is float64, the library's only fp64 code.
+// statistics of those predictions, and the resampled group means of the group-contrast bootstrap; and, on the eigendecomposition of eigh.hip (DESIGN.md
+// section 26), the leave-one-out predictions of a whole grid of alphas and the latent PCA.  Everything here is float64; with eigh.hip the library's only fp64 code.
 //   col means    zbar, mbar: per-chunk column sums, added in chunk order, divided by N
 //   gram         A = Xc^T Xc + alpha I [d, d] and R = Xc^T Yc [d, F] with Xc = Z - zbar, Yc = M - mbar: the centring happens on load (mean first, then the
 //                centred products; never E[xy] - E[x] E[y]).  v_mfma_f64_16x16x4_f64: a wave owns a 32 x 32 tile of the [d, d + F] product, the four rows of a
@@ -12,6 +13,9 @@
 //   loo          h_i = 1 / N + sum_k T[k, i]^2;  Yhat = mbar + Xc W;  P = M - (M - Yhat) / (1 - h);  coef = W^T, intercept = mbar - zbar^T W
 //   stats        per feature: R^2 and Pearson correlation of P against M under the reference's rules
 //   group means  out[b, g] = mean over i, in index order, of Z[idx[b, i]] whose group code is g
+//   matmul       out = (X - mean) B on the fp64 MFMA, the mean subtracted on load, either operand a transpose in place: P = Xc V, Q = V^T Xc^T Yc, PCA's transform
+//   path         per alpha of a grid in device memory: h = 1 / N + sum_k P_k^2 / (lambda_k + alpha), loo from Yhat = mbar + P diag(1 / (lambda + alpha)) Q, sse
+//   pca          the top components in descending order with sklearn's sign rule, their variances, ratios and singular values
 // No float atomics, no workgroup waits on another, every sum has one fixed order and every grid is a function of the shape alone: two runs give equal bits.
 #include "common.h"
 
@@ -353,6 +357,140 @@ __global__ __launch_bounds__(64) void group_means_resampled_kernel(const double*
     if (c == 0) counts[b * G + g] = cnt;
 }
 
+// ---- the alpha path and the latent PCA on an eigendecomposition of the centred Gram matrix ----
+// out [R][C] = (X - mean) B on the fp64 MFMA: X is read as x[i * xrs + k * xcs] - mean[k] (mean may be null), B as b[k * brs + j * bcs], so either operand may be
+// a transpose in place.  The mean is subtracted on load (centre first, then multiply).  grid (ceil(C / 64), ceil(R / 64)), 4 waves, a wave owns a 32 x 32 tile
+// and walks the whole of K in order: no split, one fixed order.
+__global__ __launch_bounds__(256) void centered_matmul_kernel(const double* __restrict__ x, int64_t xrs, int64_t xcs, const double* __restrict__ mean,
+                                                              const double* __restrict__ b, int64_t brs, int64_t bcs, int64_t R, int K, int64_t C,
+                                                              double* __restrict__ out, int64_t ldo) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+    const int64_t i0 = (int64_t)blockIdx.y * 64 + (w >> 1) * 32, j0 = (int64_t)blockIdx.x * 64 + (w & 1) * 32;
+    if (i0 >= R || j0 >= C) return;          // wave-uniform; the kernel has no barrier
+    const double* pa[2];
+    const double* pb[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int64_t i = i0 + 16 * u + lr, j = j0 + 16 * u + lr;
+        pa[u] = i < R ? x + i * xrs : nullptr;
+        pb[u] = j < C ? b + j * bcs : nullptr;
+    }
+    f64x4 acc[2][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v) acc[u][v] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += 4) {
+        const int k = k0 + lk;
+        const bool in = k < K;
+        const double mk = (in && mean) ? mean[k] : 0.0;
+        double a[2], bb[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            a[u] = (in && pa[u]) ? pa[u][k * xcs] - mk : 0.0;
+            bb[u] = (in && pb[u]) ? pb[u][k * brs] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int v = 0; v < 2; ++v) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], bb[v], acc[u][v], 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * u + lk + 4 * r, j = j0 + 16 * v + lr;
+                if (i < R && j < C) out[i * ldo + j] = acc[u][v][r];
+            }
+}
+
+// the path: with P = Xc V [N, d], Q = V^T Xc^T Yc [d, F] and the eigenvalues clamped at 0 from below (the Gram matrix is positive semidefinite by construction),
+//   h[g, i] = 1 / N + sum_k P[i, k]^2 / (lambda_k + alpha_g),  yhat = mbar + sum_k P[i, k] Q[k, j] / (lambda_k + alpha_g),  loo = y - (y - yhat) / (1 - h)
+// every sum over k in index order.  grid (ceil(N / 256), G); the threads of row 0 also write the clamped eigenvalues.
+__global__ __launch_bounds__(256) void ridge_path_leverage_kernel(const double* __restrict__ P, const double* __restrict__ lam, const double* __restrict__ alphas,
+                                                                  int64_t N, int d, double* __restrict__ h, double* __restrict__ lam_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int g = blockIdx.y;
+    if (g == 0 && blockIdx.x == 0)
+        for (int k = threadIdx.x; k < d; k += 256) lam_out[k] = lam[k] > 0.0 ? lam[k] : 0.0;
+    if (i >= N) return;
+    const double alpha = alphas[g];
+    double s = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double v = P[i * d + k], l = lam[k] > 0.0 ? lam[k] : 0.0;
+        s += v * v / (l + alpha);
+    }
+    h[(size_t)g * N + i] = 1.0 / (double)N + s;
+}
+// grid (ceil(N F / 256), G)
+__global__ __launch_bounds__(256) void ridge_path_loo_kernel(const double* __restrict__ P, const double* __restrict__ Q, const double* __restrict__ lam,
+                                                             const double* __restrict__ alphas, const double* __restrict__ M, int64_t ms,
+                                                             const double* __restrict__ mbar, const double* __restrict__ h, int64_t N, int d, int F,
+                                                             double* __restrict__ loo) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int g = blockIdx.y;
+    if (e >= N * F) return;
+    const int64_t i = e / F;
+    const int j = (int)(e % F);
+    const double alpha = alphas[g];
+    double s = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double l = lam[k] > 0.0 ? lam[k] : 0.0;
+        s += P[i * d + k] * Q[(size_t)k * F + j] / (l + alpha);
+    }
+    const double yh = mbar[j] + s, y = M[i * ms + j];
+    loo[(size_t)g * N * F + e] = y - (y - yh) / (1.0 - h[(size_t)g * N + i]);
+}
+// grid (F, G): one workgroup per (feature, alpha); a thread adds its rows in row order, the 256 partial sums are added in a fixed tree
+__global__ __launch_bounds__(256) void ridge_path_sse_kernel(const double* __restrict__ M, int64_t ms, const double* __restrict__ loo, int64_t N, int F,
+                                                             double* __restrict__ sse) {
+    __shared__ double red[256];
+    const int j = blockIdx.x, g = blockIdx.y;
+    const double* lg = loo + (size_t)g * N * F;
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < N; i += 256) {
+        const double r = M[i * ms + j] - lg[i * F + j];
+        s += r * r;
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) sse[(size_t)g * F + j] = s;
+}
+
+// PCA's components from an ascending eigendecomposition (w [d], V [d][d], column k the eigenvector of w[k]): workgroup c takes column d - 1 - c (descending
+// order), finds its entry of largest |value| (lowest index on a tie) and writes the column, signed so that this entry is positive, as row c of comp [k][d];
+// thread 0 writes the variance w / (N - 1), its share of the sum of all d eigenvalues (added in index order) and the singular value sqrt(w), w clamped at 0.
+__global__ __launch_bounds__(256) void pca_components_kernel(const double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int d, int64_t N,
+                                                             double* __restrict__ comp, double* __restrict__ var, double* __restrict__ ratio,
+                                                             double* __restrict__ sing) {
+    __shared__ double bv[256];
+    __shared__ int bi[256];
+    const int c = blockIdx.x, t = threadIdx.x, col = d - 1 - c;
+    double best = -1.0;
+    int at = d;
+    for (int i = t; i < d; i += 256) {          // ascending i within a thread: a strict > keeps the lowest index
+        const double a = fabs(V[(size_t)i * ldv + col]);
+        if (a > best) { best = a; at = i; }
+    }
+    bv[t] = best; bi[t] = at;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s && (bv[t + s] > bv[t] || (bv[t + s] == bv[t] && bi[t + s] < bi[t]))) { bv[t] = bv[t + s]; bi[t] = bi[t + s]; }
+        __syncthreads();
+    }
+    const int lead = bi[0];
+    const double sign = (lead < d && V[(size_t)lead * ldv + col] < 0.0) ? -1.0 : 1.0;
+    for (int i = t; i < d; i += 256) comp[(size_t)c * d + i] = sign * V[(size_t)i * ldv + col];
+    if (t != 0) return;
+    double total = 0.0;
+    for (int k = 0; k < d; ++k) total += w[k] > 0.0 ? w[k] : 0.0;
+    const double l = w[col] > 0.0 ? w[col] : 0.0;
+    var[c] = l / (double)(N - 1);
+    ratio[c] = l / total;
+    sing[c] = sqrt(l);
+}
+
 inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 constexpr int64_t RIDGE_MAX_ROWS = (int64_t)1 << 31;      // N and n stay below 2^31, F below 2^21 and N F below 2^38 (a grid of 256-thread workgroups over it)
@@ -474,5 +612,70 @@ extern "C" int cvae_group_means_resampled_f64(const double* Z, int64_t z_stride,
     if (!aligned8(Z) || !aligned4(codes) || !aligned4(idx) || !aligned8(out) || !aligned4(counts)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(group_means_resampled_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)G, (unsigned)n_boot), dim3(64), 0, (hipStream_t)stream, Z, z_stride, codes,
                        idx, N, (int)d, (int)G, out, counts);
+    return launch_rc();
+}
+
+// ---- the alpha path and the latent PCA ----
+namespace {
+bool gram_shape_ok(int64_t N, int64_t d, int64_t F) { return N >= 1 && N < RIDGE_MAX_ROWS && d >= 1 && d <= 1024 && F >= 0 && F < RIDGE_MAX_ROWS / 1024; }
+}  // namespace
+
+extern "C" size_t cvae_centered_gram_f64_workspace_bytes(int64_t N, int64_t d, int64_t F) {
+    if (!gram_shape_ok(N, d, F)) return 0;
+    return (size_t)rg_parts(N) * d * (d + F) * sizeof(double);
+}
+extern "C" int cvae_centered_gram_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N,
+                                      int64_t d, int64_t F, double* G, double* R, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!gram_shape_ok(N, d, F) || z_stride < d || (F > 0 && m_stride < F)) return CVAE_E_BADSHAPE;
+    if (!Z || !z_mean || !G || !workspace || (F > 0 && (!M || !m_mean || !R))) return CVAE_E_NULLPTR;
+    if (!aligned8(Z) || !aligned8(z_mean) || !aligned8(G) || !aligned8(workspace) || (F > 0 && (!aligned8(M) || !aligned8(m_mean) || !aligned8(R))))
+        return CVAE_E_UNSUPPORTED;
+    if (workspace_bytes < cvae_centered_gram_f64_workspace_bytes(N, d, F)) return CVAE_E_WORKSPACE;
+    const int parts = (int)rg_parts(N);
+    const int64_t W = d + F;
+    hipLaunchKernelGGL(ridge_gram_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)parts), dim3(256), 0, (hipStream_t)stream, Z, z_stride,
+                       z_mean, M, m_stride, m_mean, N, (int)d, (int)F, rg_chunk(N), (double*)workspace);
+    hipLaunchKernelGGL(ridge_gram_finish_kernel, dim3(blocks256(d * W)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, parts, (int)d, (int)F, 0.0, G, R);
+    return launch_rc();
+}
+
+extern "C" int cvae_centered_matmul_f64(const double* x, int64_t x_row_stride, int64_t x_col_stride, const double* mean, const double* b, int64_t b_row_stride,
+                                        int64_t b_col_stride, int64_t R, int64_t K, int64_t C, double* out, int64_t ldo, void* stream) {
+    if (R < 1 || R >= RIDGE_MAX_ROWS || K < 1 || K > 1024 || C < 1 || C >= RIDGE_MAX_ROWS / 1024 || ldo < C || x_row_stride < 1 || x_col_stride < 1 ||
+        b_row_stride < 1 || b_col_stride < 1)
+        return CVAE_E_BADSHAPE;
+    if (!x || !b || !out) return CVAE_E_NULLPTR;
+    if (!aligned8(x) || !aligned8(mean) || !aligned8(b) || !aligned8(out)) return CVAE_E_UNSUPPORTED;
+    if (out == x || out == b) return CVAE_E_UNSUPPORTED;
+    hipLaunchKernelGGL(centered_matmul_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64)), dim3(256), 0, (hipStream_t)stream, x, x_row_stride,
+                       x_col_stride, mean, b, b_row_stride, b_col_stride, R, (int)K, C, out, ldo);
+    return launch_rc();
+}
+
+extern "C" int cvae_ridge_path_f64(const double* P, const double* Q, const double* lambda, const double* alphas, const double* M, int64_t m_stride,
+                                   const double* m_mean, int64_t N, int64_t d, int64_t F, int64_t G, double* eigenvalues, double* leverage, double* loo, double* sse,
+                                   void* stream) {
+    if (!ridge_shape_ok(N, d, F) || m_stride < F || G < 1 || G > 64) return CVAE_E_BADSHAPE;
+    if (!P || !Q || !lambda || !alphas || !M || !m_mean || !eigenvalues || !leverage || !loo || !sse) return CVAE_E_NULLPTR;
+    if (!aligned8(P) || !aligned8(Q) || !aligned8(lambda) || !aligned8(alphas) || !aligned8(M) || !aligned8(m_mean) || !aligned8(eigenvalues) || !aligned8(leverage) ||
+        !aligned8(loo) || !aligned8(sse))
+        return CVAE_E_UNSUPPORTED;
+    if (eigenvalues == lambda) return CVAE_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ridge_path_leverage_kernel, dim3(blocks256(N), (unsigned)G), dim3(256), 0, st, P, lambda, alphas, N, (int)d, leverage, eigenvalues);
+    hipLaunchKernelGGL(ridge_path_loo_kernel, dim3(blocks256(N * F), (unsigned)G), dim3(256), 0, st, P, Q, lambda, alphas, M, m_stride, m_mean,
+                       (const double*)leverage, N, (int)d, (int)F, loo);
+    hipLaunchKernelGGL(ridge_path_sse_kernel, dim3((unsigned)F, (unsigned)G), dim3(256), 0, st, M, m_stride, (const double*)loo, N, (int)F, sse);
+    return launch_rc();
+}
+
+extern "C" int cvae_pca_components_f64(const double* w, const double* V, int64_t ldv, int64_t d, int64_t k, int64_t N, double* components,
+                                       double* explained_variance, double* explained_variance_ratio, double* singular_values, void* stream) {
+    if (d < 1 || d > 1024 || ldv < d || N < 2 || N >= RIDGE_MAX_ROWS || k < 1 || k > d || k > N - 1) return CVAE_E_BADSHAPE;
+    if (!w || !V || !components || !explained_variance || !explained_variance_ratio || !singular_values) return CVAE_E_NULLPTR;
+    if (!aligned8(w) || !aligned8(V) || !aligned8(components) || !aligned8(explained_variance) || !aligned8(explained_variance_ratio) || !aligned8(singular_values))
+        return CVAE_E_UNSUPPORTED;
+    hipLaunchKernelGGL(pca_components_kernel, dim3((unsigned)k), dim3(256), 0, (hipStream_t)stream, w, V, ldv, (int)d, N, components, explained_variance,
+                       explained_variance_ratio, singular_values);
     return launch_rc();
 }

@@ -3243,3 +3243,184 @@ def group_means_resampled(Z, codes, idx, G):
     out, counts = _empty((n_boot, G, d), torch.float64, Z), _empty((n_boot, G), torch.int32, Z)
     check(lib.cvae_group_means_resampled_f64(ptr(Z), d, ptr(codes), ptr(idx), N, d, G, n_boot, ptr(out), ptr(counts), stream()), "group_means_resampled_f64")
     return out, counts
+
+
+# ---- the symmetric eigensolver, the ridge alpha path and the latent PCA (csrc/eigh.hip, csrc/ridge.hip): float64 throughout ----
+EIGH_MAX_N = 1024
+RIDGE_PATH_MAX_ALPHAS = 64
+
+
+def eigh_f64(A):
+    """(w [n] ascending, V [n, n] with column k the eigenvector of w[k], sweeps) of a symmetric float64 matrix on the device, 1 <= n <= 1024
+    (cvae_eigh_f64: a two-sided Jacobi method in round-robin order; the lower triangle of A is read; numpy.linalg.eigh's convention).  Not enqueue-only: the
+    entry synchronises the stream once per sweep.  The status is read once, here: CvaeError if the sweep cap was reached (info 1) or a non-finite entry was met
+    (info 2)."""
+    what = "eigh_f64"
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.dtype != torch.float64:
+        raise L.CvaeError(f"{what}: a square float64 matrix expected, got {tuple(A.shape)} {A.dtype}")
+    n = A.shape[0]
+    if n < 1 or n > EIGH_MAX_N:
+        raise L.CvaeError(f"{what}: 1 <= n <= {EIGH_MAX_N} expected, got n = {n}")
+    L.require_gpu(A)
+    A = A.detach().contiguous()
+    w, V, info = _empty((n,), torch.float64, A), _empty((n, n), torch.float64, A), _empty((2,), torch.int32, A)
+    _t, wp, wb = _f64_ws(lib.cvae_eigh_f64_workspace_bytes(n), A)
+    check(L.timed(f"eigh n{n}", lib.cvae_eigh_f64, ptr(A), n, n, ptr(w), ptr(V), n, ptr(info), wp, wb, stream()), "eigh_f64")
+    code, sweeps = (int(v) for v in info.cpu().tolist())
+    if code == 1:
+        raise L.CvaeError(f"{what}: no convergence within the cap of {lib.cvae_eigh_max_sweeps()} sweeps (info = 1)")
+    if code != 0:
+        raise L.CvaeError(f"{what}: a non-finite entry was met (info = {code}): a NaN or an infinity in the matrix?")
+    return w, V, sweeps
+
+
+def centered_gram_f64(Z, zbar, M=None, mbar=None):
+    """(G [d, d] = Xc^T Xc, R [d, F] = Xc^T Yc or None without M) with Xc = Z - zbar, Yc = M - mbar (cvae_centered_gram_f64: the kernels of the ridge's Gram
+    matrix without the shift).  Float64 device tensors with contiguous rows."""
+    what = "centered_gram_f64"
+    zs = _f64_rows(what, "Z", Z)
+    N, d = Z.shape
+    F = 0 if M is None else M.shape[1]
+    ms = 0 if M is None else _f64_rows(what, "M", M)
+    if N < 1 or d < 1 or d > 1024 or (M is not None and (M.shape[0] != N or mbar is None or mbar.shape != (F,))) or zbar.shape != (d,):
+        raise L.CvaeError(f"{what}: Z [N, d] with 1 <= d <= 1024, zbar [d] and optionally M [N, F], mbar [F] expected, got {tuple(Z.shape)}, {tuple(zbar.shape)}")
+    L.require_gpu(Z, zbar)
+    G = _empty((d, d), torch.float64, Z)
+    R = _empty((d, F), torch.float64, Z) if F > 0 else None
+    _t, wp, wb = _f64_ws(lib.cvae_centered_gram_f64_workspace_bytes(N, d, F), Z)
+    check(L.timed(f"centered_gram N{N} d{d} F{F}", lib.cvae_centered_gram_f64, ptr(Z), zs, ptr(zbar), ptr(M) if F > 0 else None, ms, ptr(mbar) if F > 0 else None,
+                  N, d, F, ptr(G), ptr(R) if F > 0 else None, wp, wb, stream()), "centered_gram_f64")
+    return G, R
+
+
+def centered_matmul_f64(x, mean, b, x_t=False, b_t=False):
+    """(X - mean) B in float64 on the fp64 MFMA (cvae_centered_matmul_f64), the mean (a vector over X's columns, or None) subtracted on load.  X = x, or x^T with
+    x_t; B = b, or b^T with b_t: a transpose is read in place through the strides.  x and b: contiguous float64 device matrices."""
+    what = "centered_matmul_f64"
+    for name, t in (("x", x), ("b", b)):
+        if t.dim() != 2 or t.dtype != torch.float64 or not t.is_contiguous():
+            raise L.CvaeError(f"{what}: {name} must be a contiguous float64 matrix, got {tuple(t.shape)} {t.dtype}")
+    (R, K), (xrs, xcs) = ((x.shape[1], x.shape[0]), (1, x.shape[1])) if x_t else (tuple(x.shape), (x.shape[1], 1))
+    (Kb, Cc), (brs, bcs) = ((b.shape[1], b.shape[0]), (1, b.shape[1])) if b_t else (tuple(b.shape), (b.shape[1], 1))
+    if Kb != K or K < 1 or K > 1024 or R < 1 or Cc < 1 or (mean is not None and (mean.dtype != torch.float64 or mean.shape != (K,))):
+        raise L.CvaeError(f"{what}: [R, K] times [K, C] with 1 <= K <= 1024 and a float64 mean [K] expected, got [{R}, {K}] times [{Kb}, {Cc}]")
+    L.require_gpu(x, b)
+    out = _empty((R, Cc), torch.float64, x)
+    check(lib.cvae_centered_matmul_f64(ptr(x), max(xrs, 1), max(xcs, 1), None if mean is None else ptr(mean.contiguous()), ptr(b), max(brs, 1), max(bcs, 1), R, K, Cc,
+                                       ptr(out), Cc, stream()), "centered_matmul_f64")
+    return out
+
+
+class RidgePath:
+    """What ridge_loo_path returns, float64 device tensors: alphas [G], eigenvalues [d] (of the centred Gram matrix, ascending, clamped at 0), leverage [G, N],
+    loo [G, N, F] (the leave-one-out predictions), sse [G, F] (sum over the rows of (M - loo)^2), r2 [G, F] and corr [G, F] (cvae_ranking_stats_f64's);
+    sweeps: how many Jacobi sweeps the eigensolver used."""
+    __slots__ = ("alphas", "eigenvalues", "leverage", "loo", "sse", "r2", "corr", "sweeps")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def ridge_path_alphas(what, alphas):
+    """the grid as a list of Python floats, or CvaeError: empty, more than 64, or an alpha that is not positive and finite"""
+    try:
+        grid = [float(a) for a in alphas]
+    except TypeError:
+        raise L.CvaeError(f"{what}: alphas must be a sequence of numbers, got {alphas!r}") from None
+    if not grid:
+        raise L.CvaeError(f"{what}: alphas is empty")
+    if len(grid) > RIDGE_PATH_MAX_ALPHAS:
+        raise L.CvaeError(f"{what}: at most {RIDGE_PATH_MAX_ALPHAS} alphas expected, got {len(grid)}")
+    for a in grid:
+        if not (a > 0.0 and math.isfinite(a)):
+            raise L.CvaeError(f"{what}: every alpha must be positive and finite (the centred Gram matrix is singular without it), got {a}")
+    return grid
+
+
+def ridge_loo_path(Z, M, alphas):
+    """The exact leave-one-out predictions of the Ridge translator Z [N, d] -> M [N, F] (ridge_fit_loo's model) for a whole grid of alphas from ONE
+    eigendecomposition (what sklearn's RidgeCV does): column means, the centred Gram matrix G = Xc^T Xc = V diag(lambda) V^T (cvae_eigh_f64, lambda
+    clamped at 0), P = Xc V, Q = V^T Xc^T Yc, then per alpha h = 1 / N + sum_k P_k^2 / (lambda_k + alpha), Yhat = mbar + P diag(1 / (lambda + alpha)) Q,
+    loo = M - (M - Yhat) / (1 - h), and the ranking statistics of every loo against M.  Z: float32 or float64; M is converted to float64.  Every refusal
+    (ridge_fit_loo's for the shapes and dtypes; an empty grid, more than 64 alphas, an alpha that is not positive and finite) comes before the first launch.
+    Returns a RidgePath.  The one host read is the eigensolver's status."""
+    what = "ridge_loo_path"
+    grid = ridge_path_args(what, Z, M, alphas)
+    (N, d), F = Z.shape, M.shape[1]
+    L.require_gpu(Z, M)
+    Z, M = Z.detach().double().contiguous(), M.detach().double().contiguous()
+    ms = _f64_rows(what, "M", M)
+    Gn = len(grid)
+    zbar, mbar = col_means_f64(Z), col_means_f64(M)
+    gram, R = centered_gram_f64(Z, zbar, M, mbar)
+    w, V, sweeps = eigh_f64(gram)
+    P = centered_matmul_f64(Z, zbar, V)                  # Xc V
+    Q = centered_matmul_f64(V, None, R, x_t=True)        # V^T (Xc^T Yc)
+    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    a_dev = torch.tensor(grid, dtype=torch.float64, device=Z.device)
+    out = dict(eigenvalues=new(d), leverage=new(Gn, N), loo=new(Gn, N, F), sse=new(Gn, F), r2=new(Gn, F), corr=new(Gn, F))
+    check(L.timed(f"ridge_path N{N} d{d} F{F} G{Gn}", lib.cvae_ridge_path_f64, ptr(P), ptr(Q), ptr(w), ptr(a_dev), ptr(M), ms, ptr(mbar), N, d, F, Gn,
+                  ptr(out["eigenvalues"]), ptr(out["leverage"]), ptr(out["loo"]), ptr(out["sse"]), stream()), "ridge_path_f64")
+    for g in range(Gn):
+        check(lib.cvae_ranking_stats_f64(ptr(M), ms, ptr(out["loo"][g]), F, N, F, ptr(out["r2"][g]), ptr(out["corr"][g]), stream()), "ranking_stats_f64")
+    return RidgePath(alphas=a_dev, sweeps=sweeps, **out)
+
+
+def ridge_path_args(what, Z, M, alphas):
+    """every refusal of ridge_loo_path, none of which needs a device: ridge_fit_loo's for the shapes and dtypes, then the grid's -> the grid as Python floats"""
+    if Z.dim() != 2 or M.dim() != 2:
+        raise L.CvaeError(f"{what}: Z [N, d] and M [N, F] expected, got {tuple(Z.shape)} and {tuple(M.shape)}")
+    if Z.dtype not in (torch.float32, torch.float64):
+        raise L.CvaeError(f"{what}: Z must be float32 or float64, got {Z.dtype}")
+    N, d = Z.shape
+    F = M.shape[1]
+    if M.shape[0] != N:
+        raise L.CvaeError(f"{what}: Z has {N} rows, M has {M.shape[0]}")
+    if N < 2:
+        raise L.CvaeError(f"{what}: at least 2 samples expected (leave-one-out leaves N - 1), got N = {N}")
+    if d < 1 or d > 1024:
+        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected (the eigensolver's limit), got d = {d}")
+    if F < 1:
+        raise L.CvaeError(f"{what}: at least one feature column expected, got M {tuple(M.shape)}")
+    return ridge_path_alphas(what, alphas)
+
+
+def pca_args(what, Z, n_components):
+    """every refusal of pca_fit_f64, none of which needs a device -> n_components as an int"""
+    if Z.dim() != 2 or Z.dtype not in (torch.float32, torch.float64):
+        raise L.CvaeError(f"{what}: a float32 or float64 matrix Z [N, d] expected, got {tuple(Z.shape)} {Z.dtype}")
+    N, d = Z.shape
+    if d < 1 or d > 1024:
+        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected (the eigensolver's limit), got d = {d}")
+    if int(n_components) != n_components or n_components < 1 or n_components > min(N - 1, d):
+        raise L.CvaeError(f"{what}: 1 <= n_components <= min(N - 1, d) = {min(N - 1, d)} expected, got {n_components}")
+    return int(n_components)
+
+
+def pca_fit_f64(Z, n_components):
+    """sklearn's PCA(n_components).fit on the device in float64: column means, the centred Gram matrix, cvae_eigh_f64, then
+    cvae_pca_components_f64 (the top components in descending order, each signed so that its entry of largest |value| is positive).  Z [N, d] float32 or
+    float64, 1 <= n_components <= min(N - 1, d), d <= 1024.  Returns a dict of float64 device tensors: mean [d], components [k, d], explained_variance [k],
+    explained_variance_ratio [k], singular_values [k]."""
+    k = pca_args("pca_fit_f64", Z, n_components)
+    N, d = Z.shape
+    L.require_gpu(Z)
+    Z = Z.detach().double().contiguous()
+    mean = col_means_f64(Z)
+    gram, _r = centered_gram_f64(Z, mean)
+    w, V, _sweeps = eigh_f64(gram)
+    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    out = dict(components=new(k, d), explained_variance=new(k), explained_variance_ratio=new(k), singular_values=new(k))
+    check(lib.cvae_pca_components_f64(ptr(w), ptr(V), d, d, k, N, ptr(out["components"]), ptr(out["explained_variance"]), ptr(out["explained_variance_ratio"]),
+                                      ptr(out["singular_values"]), stream()), "pca_components_f64")
+    return dict(mean=mean, **out)
+
+
+def pca_transform_f64(Z, mean, components):
+    """(Z - mean) components^T in float64 (cvae_centered_matmul_f64): Z [N, d] float32 or float64, mean [d], components [k, d] -> [N, k]"""
+    what = "pca_transform_f64"
+    if Z.dim() != 2 or Z.dtype not in (torch.float32, torch.float64) or components.dim() != 2 or Z.shape[1] != components.shape[1] or Z.shape[0] < 1:
+        raise L.CvaeError(f"{what}: Z [N >= 1, d] float32 or float64 and components [k, d] expected, got {tuple(Z.shape)} {Z.dtype}, {tuple(components.shape)}")
+    L.require_gpu(Z, mean, components)
+    return centered_matmul_f64(Z.detach().double().contiguous(), mean, components.contiguous(), b_t=True)

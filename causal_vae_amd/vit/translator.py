@@ -83,11 +83,56 @@ def fit_translator_ridge(Z, M, Z_test=None, M_test=None, feature_names=(), alpha
     return _fit(Zh.to(device), Mh.to(device), names, alpha, device)
 
 
+def _select_alpha(path, Md, names, select):
+    """the rows of `path` (one dict per alpha, Python floats) and the index of the chosen alpha, from ONE host read: the mean squared leave-one-out residual over
+    all rows and features ("mse", RidgeCV's criterion) or the mean leave-one-out R² over the features that are not constant ("r2"); a tie takes the first"""
+    G, N = path.leverage.shape
+    F = len(names)
+    varies = (Md.max(dim=0).values != Md.min(dim=0).values).to(torch.float64)
+    host = torch.cat([path.alphas[:, None], path.leverage.max(dim=1).values[:, None], path.sse, path.r2, varies[None, :].expand(G, F)], dim=1).cpu().numpy()
+    alphas, max_h, sse, r2, keep = host[:, 0], host[:, 1], host[:, 2:2 + F], host[:, 2 + F:2 + 2 * F], host[0, 2 + 2 * F:] != 0
+    rows = []
+    for g in range(G):
+        mean_r2 = float(np.sum(r2[g][keep]) / keep.sum()) if keep.any() else 0.0
+        rows.append({"alpha": float(alphas[g]), "mse": float(np.sum(sse[g]) / (N * F)), "mean_r2": mean_r2, "max_leverage": float(max_h[g]),
+                     "r2": {n: float(v) for n, v in zip(names, r2[g])}})
+    score = [r["mse"] for r in rows] if select == "mse" else [-r["mean_r2"] for r in rows]
+    return rows, min(range(G), key=lambda g: score[g])          # min() keeps the first of equals
+
+
+def _fit_cv(Zd, Md, names, grid, select, device):
+    rows, best = _select_alpha(ops.ridge_loo_path(Zd, Md, grid), Md.double(), names, select)
+    return _fit(Zd, Md, names, grid[best], device) + (rows,)
+
+
+def _cv_args(what, Zh, Mh, alphas, feature_names, select):
+    """every refusal that needs no device -> (names, the grid as Python floats)"""
+    if select not in ("mse", "r2"):
+        raise CvaeError(f'{what}: select must be "mse" or "r2", got {select!r}')
+    grid = ops.ridge_path_args(what, Zh, Mh, alphas)
+    return _feature_names(feature_names, Mh.shape[1]), grid
+
+
+def fit_translator_ridge_cv(Z, M, alphas=(0.1, 1.0, 10.0), feature_names=(), select="mse", device="cuda"):
+    """fit_translator_ridge with alpha chosen from a grid by exact leave-one-out (sklearn's RidgeCV, whose default grid and criterion these are):
+    (translator, ranking, Mhat_full, W, path).  The leave-one-out predictions of every alpha come from one eigendecomposition of the centred Gram matrix
+    (ops.ridge_loo_path).  select="mse": the alpha with the smallest mean squared leave-one-out residual over all rows and features; select="r2": the largest
+    mean leave-one-out R² over the features that are not constant (scale-free; what the ranking is by).  A tie takes the first alpha in the order given.  The
+    chosen alpha is then fitted by fit_translator_ridge's own route, so the first four values are bit for bit fit_translator_ridge(..., alpha=chosen)'s and
+    translator.alpha is the choice.  path: one dict per alpha, in the order given: "alpha", "mse", "mean_r2", "max_leverage" and "r2" (a dict by feature name),
+    all Python floats."""
+    what = "fit_translator_ridge_cv"
+    Zh, Mh = _matrix(Z, "Z")[0], _matrix(M, "M")[0]
+    names, grid = _cv_args(what, Zh, Mh, alphas, feature_names, select)
+    return _fit_cv(Zh.to(device), Mh.to(device), names, grid, select, device)
+
+
 @torch.no_grad()
-def translate_vit_latents(model, loader, M, device, feature_names=(), alpha=1.0):
+def translate_vit_latents(model, loader, M, device, feature_names=(), alpha=1.0, alphas=None, select="mse"):
     """Steps 2 and 3 of the pipeline in one: (Z, translator, ranking, Mhat_full, W).  extract_vit_latents' protocol (eval mode, mu of every batch["x"]), but the
     per-batch mu stay on the device and go straight into the fit; Z [N, latent_dim] float32 numpy is copied to the host once, for the return value.
-    model: a ViTVAE or a ViTVAEEncoder."""
+    model: a ViTVAE or a ViTVAEEncoder.  With a grid `alphas`, alpha is chosen from it as fit_translator_ridge_cv does (`alpha` is then not used) and the
+    path is appended: (Z, translator, ranking, Mhat_full, W, path)."""
     model.eval()
     zs = [model.encode(batch["x"].to(device))[0] for batch in loader]
     if not zs:
@@ -96,7 +141,10 @@ def translate_vit_latents(model, loader, M, device, feature_names=(), alpha=1.0)
     Md, _ = _to_device(M, device, "M")
     if Md.shape[0] != Zd.shape[0]:
         raise CvaeError(f"translate_vit_latents: the loader gave {Zd.shape[0]} samples, M has {Md.shape[0]} rows")
-    return (Zd.cpu().numpy(),) + _fit(Zd, Md, _feature_names(feature_names, Md.shape[1]), alpha, device)
+    if alphas is None:
+        return (Zd.cpu().numpy(),) + _fit(Zd, Md, _feature_names(feature_names, Md.shape[1]), alpha, device)
+    names, grid = _cv_args("translate_vit_latents", Zd, Md, alphas, feature_names, select)
+    return (Zd.cpu().numpy(),) + _fit_cv(Zd, Md, names, grid, select, device)
 
 
 def _unique_in_order(groups):

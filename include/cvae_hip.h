@@ -997,6 +997,45 @@ int cvae_ranking_stats_f64(const double* Y, int64_t y_stride, const double* P, i
 int cvae_group_means_resampled_f64(const double* Z, int64_t z_stride, const int* codes, const int* idx, int64_t N, int64_t d, int64_t G, int64_t n_boot, double* out,
                                    int* counts, void* stream);
 
+/* ---- The symmetric eigensolver, the ridge alpha path and the latent PCA (csrc/eigh.hip, csrc/ridge.hip).  FLOAT64 ONLY, with the conventions
+ * of the section above (8-byte aligned row-major doubles, strides in elements, every check before the first launch, no float atomics, fixed orders, equal bits).
+ *   cvae_eigh_f64            A [n][>= lda] symmetric (the lower triangle is read), 1 <= n <= 1024: w [n] ascending (ties by original index) and V [n][>= ldv] with
+ *                            column k the eigenvector of w[k] (numpy.linalg.eigh's convention).  A two-sided Jacobi method in round-robin order: n - 1 (n even) or
+ *                            n (n odd, one pair a bye) rounds per sweep, one launch per round in which all the round's disjoint pairs rotate, between two buffers
+ *                            of `workspace` (cvae_eigh_f64_workspace_bytes: 4 n^2 doubles and a little).  A sweep in which no rotated |a_pq| exceeded
+ *                            2^-53 max |A| is the last.  NOT enqueue-only: the host reads one word from the device before the first sweep and after every sweep
+ *                            (a stream synchronisation each; the entry cannot be captured into a graph) and stops launching when it is set; at most
+ *                            cvae_eigh_max_sweeps() sweeps.  info (device int [2], 4-byte aligned): info[0] = 0 converged, 1 the sweep cap was reached, 2 a
+ *                            non-finite entry was met (in A, or on the diagonal after a sweep; w and V are then unspecified); info[1] = the sweeps used (the
+ *                            last one, which only confirms, included).  No loop in any kernel has a trip count that depends on data: the entry returns for
+ *                            every input.  Eigenvalues are not clamped.
+ *   cvae_centered_gram_f64   cvae_ridge_gram_f64 without the shift and with F >= 0: G [d][d] = Xc^T Xc, R [d][F] = Xc^T (M - mbar), the same two launches; with
+ *                            F == 0, M, m_mean and R are not read and may be NULL.  1 <= N.
+ *   cvae_centered_matmul_f64 out [R][>= ldo] = (X - mean) B on v_mfma_f64_16x16x4_f64, X read as x[i x_row_stride + k x_col_stride] - mean[k] (mean [K] may be
+ *                            NULL: nothing is subtracted), B as b[k b_row_stride + j b_col_stride]: either operand may be a transpose in place.  The mean is
+ *                            subtracted on load.  1 <= K <= 1024, 1 <= R < 2^31, 1 <= C < 2^21; out must not be x or b.  One launch, K walked in order.
+ *   cvae_ridge_path_f64      with P [N][d] = Xc V, Q [d][F] = V^T Xc^T Yc, lambda [d] the eigenvalues of Xc^T Xc (clamped at 0 from below here, and written so to
+ *                            eigenvalues [d], which must not be lambda) and alphas [G] in device memory, 1 <= G <= 64:
+ *                            leverage [G][N] = 1 / N + sum_k P[i][k]^2 / (lambda_k + alpha_g), loo [G][N][F] = M - (M - Yhat) / (1 - leverage) with
+ *                            Yhat = mbar + sum_k P[i][k] Q[k][j] / (lambda_k + alpha_g), sse [G][F] = sum_i (M - loo)^2 (a thread's rows in row order, the 256
+ *                            partial sums in a fixed tree).  Three launches.  The alphas are not checked on the device.
+ *   cvae_pca_components_f64  from cvae_eigh_f64's w [d] and V of the centred Gram matrix of N rows: components [k][d] = the k last columns of V in descending
+ *                            order of eigenvalue, each signed so that its entry of largest |value| (lowest index on a tie) is positive; explained_variance [k] =
+ *                            w / (N - 1), explained_variance_ratio [k] = w / (the sum of all d, in index order), singular_values [k] = sqrt(w), w clamped at 0.
+ *                            1 <= k <= min(N - 1, d). */
+int cvae_eigh_max_sweeps(void);
+size_t cvae_eigh_f64_workspace_bytes(int64_t n);
+int cvae_eigh_f64(const double* A, int64_t lda, int64_t n, double* w, double* V, int64_t ldv, int* info, void* workspace, size_t workspace_bytes, void* stream);
+size_t cvae_centered_gram_f64_workspace_bytes(int64_t N, int64_t d, int64_t F);
+int cvae_centered_gram_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N, int64_t d,
+                           int64_t F, double* G, double* R, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_centered_matmul_f64(const double* x, int64_t x_row_stride, int64_t x_col_stride, const double* mean, const double* b, int64_t b_row_stride,
+                             int64_t b_col_stride, int64_t R, int64_t K, int64_t C, double* out, int64_t ldo, void* stream);
+int cvae_ridge_path_f64(const double* P, const double* Q, const double* lambda, const double* alphas, const double* M, int64_t m_stride, const double* m_mean,
+                        int64_t N, int64_t d, int64_t F, int64_t G, double* eigenvalues, double* leverage, double* loo, double* sse, void* stream);
+int cvae_pca_components_f64(const double* w, const double* V, int64_t ldv, int64_t d, int64_t k, int64_t N, double* components, double* explained_variance,
+                            double* explained_variance_ratio, double* singular_values, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
