@@ -209,6 +209,15 @@ SIGNATURES = {
     "cvae_centered_matmul_f64": [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "cvae_ridge_path_f64": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "cvae_pca_components_f64": [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "cvae_tsne_sqdist_f64": [_p, _i, _i64, _i64, _i64, _p, _p],
+    "cvae_tsne_affinities_f64": [_p, _i64, _d, _d, _p, _p, _p, _p],
+    "cvae_tsne_joint_f64_workspace_bytes": [_i64],
+    "cvae_tsne_joint_f64": [_p, _p, _i64, _p, _p, _p, _sz, _p],
+    "cvae_tsne_forces_f64": [_p, _p, _i64, _p, _p, _p, _p, _p],
+    "cvae_tsne_grad_f64": [_p, _p, _p, _p, _i64, _d, _p, _p, _p],
+    "cvae_tsne_update_f64": [_p] * 7 + [_i64, _d, _d, _d, _p, _p, _p, _p, _p],
+    "cvae_tsne_fit_f64_workspace_bytes": [_i64],
+    "cvae_tsne_fit_f64": [_p, _p, _i64, _d, _d, _i64, _i64, _d, _p, _p, _p, _sz, _p],
 }
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
@@ -220,7 +229,8 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_s1_wgrad_workspace_bytes": _sz, "cvae_conv_s1_c1_wgrad_workspace_bytes": _sz, "cvae_mhsa_bwd_workspace_bytes": _sz,
             "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz,
             "cvae_mhsa_relevance_step_workspace_bytes": _sz, "cvae_col_means_f64_workspace_bytes": _sz, "cvae_ridge_gram_f64_workspace_bytes": _sz,
-            "cvae_eigh_f64_workspace_bytes": _sz, "cvae_centered_gram_f64_workspace_bytes": _sz}
+            "cvae_eigh_f64_workspace_bytes": _sz, "cvae_centered_gram_f64_workspace_bytes": _sz, "cvae_tsne_joint_f64_workspace_bytes": _sz,
+            "cvae_tsne_fit_f64_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

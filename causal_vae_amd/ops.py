@@ -3424,3 +3424,171 @@ def pca_transform_f64(Z, mean, components):
         raise L.CvaeError(f"{what}: Z [N >= 1, d] float32 or float64 and components [k, d] expected, got {tuple(Z.shape)} {Z.dtype}, {tuple(components.shape)}")
     L.require_gpu(Z, mean, components)
     return centered_matmul_f64(Z.detach().double().contiguous(), mean, components.contiguous(), b_t=True)
+
+
+# ---- the exact t-SNE of the latents (csrc/tsne.hip): float64 throughout ----
+TSNE_MIN_N, TSNE_MAX_N = 3, 4096
+TSNE_STOP_REASONS = ("max_iter iterations ran", "the gradient norm fell to min_grad_norm", "no progress within n_iter_without_progress iterations")
+
+
+class TsneFit:
+    """What tsne_fit_f64 returns: Y [N, 2] (float64, on the device), kl (a float: the KL divergence of P from the embedding's Q), n_iter (the index of the last
+    iteration run, sklearn's n_iter_), reason (an index into TSNE_STOP_REASONS), checks (how many times the host read the device's record)."""
+    __slots__ = ("Y", "kl", "n_iter", "reason", "checks")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def tsne_args(what, Z, perplexity=30.0, n_components=2, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, init="pca", tol=1e-5,
+              n_iter_without_progress=300, distances=False):
+    """Every refusal of the t-SNE entries, none of which needs a device.  Z: the tensor to embed, [N, d] float32 / float64, or with distances=True the squared
+    distances [N, N].  Returns (N, the learning rate as a float)."""
+    if not torch.is_tensor(Z) or Z.dim() != 2 or Z.dtype not in (torch.float32, torch.float64):
+        got = f"{tuple(Z.shape)} {Z.dtype}" if torch.is_tensor(Z) else type(Z).__name__
+        raise L.CvaeError(f"{what}: a float32 or float64 matrix expected, got {got}")
+    N, d = Z.shape
+    if N < TSNE_MIN_N or N > TSNE_MAX_N:
+        raise L.CvaeError(f"{what}: {TSNE_MIN_N} <= N <= {TSNE_MAX_N} points expected (the exact method holds the N x N affinities), got N = {N}")
+    if d < 1 or (distances and d != N):
+        raise L.CvaeError(f"{what}: {'a square matrix of squared distances' if distances else 'at least one column'} expected, got {tuple(Z.shape)}")
+    if n_components != 2:
+        raise L.CvaeError(f"{what}: n_components must be 2, got {n_components}")
+    if not (0.0 < float(perplexity) < N):
+        raise L.CvaeError(f"{what}: perplexity must be in (0, N) = (0, {N}), got {perplexity}")
+    if not (float(early_exaggeration) > 0.0 and math.isfinite(float(early_exaggeration))):
+        raise L.CvaeError(f"{what}: early_exaggeration must be positive and finite, got {early_exaggeration}")
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise L.CvaeError(f"{what}: learning_rate must be a positive number or 'auto', got {learning_rate!r}")
+        lr = max(N / float(early_exaggeration) / 4.0, 50.0)
+    else:
+        lr = float(learning_rate)
+    if not (lr > 0.0 and math.isfinite(lr)):
+        raise L.CvaeError(f"{what}: learning_rate must be positive and finite, got {learning_rate}")
+    if int(max_iter) != max_iter or max_iter < 0:
+        raise L.CvaeError(f"{what}: max_iter must be a non-negative integer, got {max_iter}")
+    if int(n_iter_without_progress) != n_iter_without_progress or n_iter_without_progress < 0:
+        raise L.CvaeError(f"{what}: n_iter_without_progress must be a non-negative integer, got {n_iter_without_progress}")
+    if not (float(tol) >= 0.0):
+        raise L.CvaeError(f"{what}: tol must be >= 0, got {tol}")
+    if isinstance(init, str):
+        if init not in ("pca", "random"):
+            raise L.CvaeError(f"{what}: init must be 'pca', 'random' or an array [N, 2], got {init!r}")
+        if init == "pca" and distances:
+            raise L.CvaeError(f"{what}: init='pca' cannot be used with precomputed distances (there are no coordinates to project); use 'random' or an array")
+    elif init is not None and tuple(getattr(init, "shape", ())) != (N, 2):
+        raise L.CvaeError(f"{what}: an init array must have shape [N, 2] = [{N}, 2], got {tuple(getattr(init, 'shape', ()))}")
+    return N, lr
+
+
+def _tsne_f64(what, name, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
+        got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+        raise L.CvaeError(f"{what}: {name} must be a float64 tensor {list(shape)}, got {got}")
+    return t.detach().contiguous()
+
+
+def tsne_sqdist_f64(Z):
+    """D [N, N] float64 = the squared distances between the rows of Z [N, d] (float32 or float64, read as it is) from differences (cvae_tsne_sqdist_f64):
+    bitwise symmetric, a zero diagonal."""
+    what = "tsne_sqdist_f64"
+    N, _lr = tsne_args(what, Z, perplexity=1.0)
+    L.require_gpu(Z)
+    Z = Z.detach()
+    if Z.stride(1) != 1 or Z.stride(0) < Z.shape[1]:
+        Z = Z.contiguous()
+    D = _empty((N, N), torch.float64, Z)
+    check(L.timed(f"tsne_sqdist N{N} d{Z.shape[1]}", lib.cvae_tsne_sqdist_f64, ptr(Z), int(Z.dtype == torch.float32), Z.stride(0), N, Z.shape[1], ptr(D), stream()),
+          what)
+    return D
+
+
+def tsne_affinities_f64(D, perplexity, tol=1e-5):
+    """(P, Pc, beta, steps) from squared distances D [N, N] float64: per row sklearn's search for the beta whose conditional distribution Pc[i] has the
+    perplexity (cvae_tsne_affinities_f64; at most 100 steps, the first with |H - log perplexity| <= tol the last), then P = max((Pc + Pc^T) / sum, 2^-52)
+    (cvae_tsne_joint_f64).  One host read, the status: a non-finite entry of D, Pc or the sum is a CvaeError (info = 2)."""
+    what = "tsne_affinities_f64"
+    N, _lr = tsne_args(what, D, perplexity=perplexity, tol=tol, init=None, distances=True)
+    D = _tsne_f64(what, "D", D, (N, N))
+    L.require_gpu(D)
+    Pc, P = _empty((N, N), torch.float64, D), _empty((N, N), torch.float64, D)
+    beta, steps, info = _empty((N,), torch.float64, D), _empty((N,), torch.int32, D), _empty((1,), torch.int32, D)
+    check(L.timed(f"tsne_affinities N{N}", lib.cvae_tsne_affinities_f64, ptr(D), N, float(perplexity), float(tol), ptr(Pc), ptr(beta), ptr(steps), stream()),
+          "tsne_affinities_f64")
+    _t, wp, wb = _f64_ws(lib.cvae_tsne_joint_f64_workspace_bytes(N), D)
+    check(L.timed(f"tsne_joint N{N}", lib.cvae_tsne_joint_f64, ptr(D), ptr(Pc), N, ptr(P), ptr(info), wp, wb, stream()), "tsne_joint_f64")
+    code = int(info.item())
+    if code != 0:
+        raise L.CvaeError(f"cvae_tsne_joint_f64: a non-finite entry in the distances or the affinities (info = {code}): a NaN or an infinity in the input?")
+    return P, Pc, beta, steps
+
+
+def _tsne_pair_pass(what, Y, P, want_kl):
+    N = Y.shape[0]
+    new = lambda *shape: _empty(shape, torch.float64, Y)          # noqa: E731
+    A, R, S = new(N, 2), new(N, 2), new(N)
+    klp = new(3, N) if want_kl else None
+    check(L.timed(f"tsne_forces N{N}", lib.cvae_tsne_forces_f64, ptr(Y), ptr(P), N, ptr(A), ptr(R), ptr(S), ptr(klp), stream()), "tsne_forces_f64")
+    return A, R, S, klp
+
+
+def _tsne_state(what, P, **mats):
+    if not torch.is_tensor(P) or P.dim() != 2 or P.shape[0] != P.shape[1]:
+        raise L.CvaeError(f"{what}: P must be a square float64 tensor, got {tuple(P.shape) if torch.is_tensor(P) else type(P).__name__}")
+    N = P.shape[0]
+    if N < TSNE_MIN_N or N > TSNE_MAX_N:
+        raise L.CvaeError(f"{what}: {TSNE_MIN_N} <= N <= {TSNE_MAX_N} points expected, got N = {N}")
+    out = [_tsne_f64(what, "P", P, (N, N))] + [_tsne_f64(what, k, v, (N, 2)) for k, v in mats.items()]
+    L.require_gpu(*out)
+    return N, out
+
+
+def tsne_forces_f64(Y, P, exaggeration=1.0):
+    """(kl, grad): the KL divergence of exaggeration * P from the embedding's Q (a float64 tensor [1]) and its gradient [N, 2], sklearn's _kl_divergence without
+    the clamp of Q (cvae_tsne_forces_f64, the pair pass, then cvae_tsne_grad_f64).  Y [N, 2] and P [N, N] float64; P positive off the diagonal."""
+    what = "tsne_forces_f64"
+    if not (float(exaggeration) > 0.0):
+        raise L.CvaeError(f"{what}: exaggeration must be positive, got {exaggeration}")
+    N, (P, Y) = _tsne_state(what, P, Y=Y)
+    A, R, S, klp = _tsne_pair_pass(what, Y, P, True)
+    grad, kl = _empty((N, 2), torch.float64, Y), _empty((1,), torch.float64, Y)
+    check(lib.cvae_tsne_grad_f64(ptr(A), ptr(R), ptr(S), ptr(klp), N, float(exaggeration), ptr(grad), ptr(kl), stream()), "tsne_grad_f64")
+    return kl, grad
+
+
+def tsne_step_f64(Y, update, gains, P, exaggeration, momentum, learning_rate):
+    """One iteration of sklearn's _gradient_descent from a given state: (Y, update, gains) after it, as new tensors, and (kl, grad_norm), float64 tensors [1]:
+    the KL of exaggeration * P at the Y handed in and |gains grad| (cvae_tsne_forces_f64, then cvae_tsne_update_f64 with a record)."""
+    what = "tsne_step_f64"
+    if not (float(exaggeration) > 0.0 and float(learning_rate) > 0.0):
+        raise L.CvaeError(f"{what}: exaggeration and learning_rate must be positive, got {exaggeration}, {learning_rate}")
+    N, (P, Y, update, gains) = _tsne_state(what, P, Y=Y, update=update, gains=gains)
+    A, R, S, klp = _tsne_pair_pass(what, Y, P, True)
+    Yn, un, gn = _empty((N, 2), torch.float64, Y), _empty((N, 2), torch.float64, Y), _empty((N, 2), torch.float64, Y)
+    rec = _empty((4,), torch.float64, Y)
+    check(lib.cvae_tsne_update_f64(ptr(Y), ptr(update), ptr(gains), ptr(A), ptr(R), ptr(S), ptr(klp), N, float(exaggeration), float(momentum), float(learning_rate),
+                                   ptr(Yn), ptr(un), ptr(gn), ptr(rec), stream()), "tsne_update_f64")
+    return Yn, un, gn, (rec[0:1], rec[1:2].sqrt())
+
+
+def tsne_fit_f64(P, Y0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7):
+    """sklearn's TSNE._tsne with method="exact" from the joint affinities P [N, N] and the start Y0 [N, 2] (float64, on the device; neither is written):
+    min(250, max_iter) iterations at early_exaggeration and momentum 0.5, then to max_iter at 1 and 0.8; every 50 iterations the host reads the device's
+    record and stops on sklearn's two tests (cvae_tsne_fit_f64; NOT enqueue-only).  Two differences from sklearn, both stated in DESIGN §27: a gradient norm at
+    or below min_grad_norm ends the fit, and the KL returned is that of P at the returned Y.  A non-finite embedding is a CvaeError (info = 2)."""
+    what = "tsne_fit_f64"
+    N, (P, Y0) = _tsne_state(what, P, Y0=Y0)
+    _n, lr = tsne_args(what, P, perplexity=1.0, early_exaggeration=early_exaggeration, learning_rate=learning_rate, max_iter=max_iter, init=None,
+                       n_iter_without_progress=n_iter_without_progress, distances=True)
+    Y = Y0.clone()
+    kl, info = _empty((1,), torch.float64, Y), _empty((4,), torch.int32, Y)
+    _t, wp, wb = _f64_ws(lib.cvae_tsne_fit_f64_workspace_bytes(N), Y)
+    check(L.timed(f"tsne_fit N{N}", lib.cvae_tsne_fit_f64, ptr(P), ptr(Y), N, float(early_exaggeration), lr, int(max_iter), int(n_iter_without_progress),
+                  float(min_grad_norm), ptr(kl), ptr(info), wp, wb, stream()), "tsne_fit_f64")
+    code, n_iter, reason, checks = (int(v) for v in info.cpu().tolist())
+    if code != 0:
+        raise L.CvaeError(f"cvae_tsne_fit_f64: the embedding or its KL divergence stopped being finite by iteration {n_iter} (info = {code}): a NaN in P or Y0, "
+                          "or a learning rate that is too large?")
+    return TsneFit(Y=Y, kl=float(kl.item()), n_iter=n_iter, reason=reason, checks=checks)

@@ -14,7 +14,8 @@ on CausalViTVAE, through its backbone), and extract_vit_saliency for a loader.  
 extract_vit_relevance for a loader.  The latent translator (translator.py): fit_translator_ridge / translate_vit_latents (a float64 Ridge from the
 latents to the morphology table, ranked by exact leave-one-out R²) and bootstrap_feature_stability with its helpers, the reference's
 latent_translator/analysis.py.  Choosing alpha and looking at the latents: fit_translator_ridge_cv (alpha from a grid by exact leave-one-out on one
-eigendecomposition; translate_vit_latents takes the grid too) and latent_pca / pca_vit_latents (the reference's PCA of its latents, pca.py)."""
+eigendecomposition; translate_vit_latents takes the grid too) and latent_pca / pca_vit_latents (the reference's PCA of its latents, pca.py).  The non-linear
+view (tsne.py): latent_tsne / tsne_vit_latents, the reference's TSNE calls as the exact method in float64."""
 from .models import (ViTVAE, ViTVAEEncoder, load_vitvae_state_dict, extract_vit_latents, extract_vit_attention, extract_vit_saliency, extract_vit_relevance,   # noqa: F401
                      resize_pos_embedding, fit_latent, vit_vae_loss, train_vit_vae, vit_vae_train_step)
 from .causal import AdapterMLP, CausalViTVAE   # noqa: F401
@@ -22,8 +23,10 @@ from .train import GraphedViTTrainStep, causal_vit_train_step   # noqa: F401
 from .translator import (RidgeTranslator, fit_translator_ridge, fit_translator_ridge_cv, translate_vit_latents, compute_group_means, pairwise_contrasts, contrast_delta,   # noqa: F401
                          topk_features, bootstrap_feature_stability)
 from .pca import LatentPCA, latent_pca, pca_vit_latents   # noqa: F401
+from .tsne import LatentTSNE, latent_tsne, tsne_vit_latents   # noqa: F401
 
 __all__ = ["ViTVAE", "ViTVAEEncoder", "load_vitvae_state_dict", "extract_vit_latents", "extract_vit_attention", "extract_vit_saliency", "extract_vit_relevance", "resize_pos_embedding", "fit_latent",
            "vit_vae_loss", "train_vit_vae", "vit_vae_train_step", "AdapterMLP", "CausalViTVAE", "GraphedViTTrainStep", "causal_vit_train_step",
            "RidgeTranslator", "fit_translator_ridge", "translate_vit_latents", "compute_group_means", "pairwise_contrasts", "contrast_delta", "topk_features",
-           "bootstrap_feature_stability", "fit_translator_ridge_cv", "LatentPCA", "latent_pca", "pca_vit_latents"]
+           "bootstrap_feature_stability", "fit_translator_ridge_cv", "LatentPCA", "latent_pca", "pca_vit_latents",
+           "LatentTSNE", "latent_tsne", "tsne_vit_latents"]

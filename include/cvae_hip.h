@@ -1036,6 +1036,55 @@ int cvae_ridge_path_f64(const double* P, const double* Q, const double* lambda, 
 int cvae_pca_components_f64(const double* w, const double* V, int64_t ldv, int64_t d, int64_t k, int64_t N, double* components, double* explained_variance,
                             double* explained_variance_ratio, double* singular_values, void* stream);
 
+/* ---- Exact t-SNE of the latents (csrc/tsne.hip): sklearn's method="exact" pipeline, two components, one degree of freedom.  FLOAT64 ONLY, with
+ * the conventions of the two sections above (8-byte aligned row-major doubles, every check before the first launch, no float atomics, fixed orders, equal bits).
+ * 3 <= N <= 4096 everywhere; square matrices are dense [N][N]; Y, update, gains, A, R and grad are [N][2].
+ *   cvae_tsne_sqdist_f64     Z [N][>= z_stride] float64, or float32 with z_is_f32 (converted on load), d >= 1: D[i][j] = sum_k (z_ik - z_jk)^2 from differences,
+ *                            k in index order, one fma per term; D is bitwise symmetric and its diagonal is 0.  32 x 32 tiles, the rows staged in LDS 32 columns
+ *                            at a time.
+ *   cvae_tsne_affinities_f64 per row i over j != i with d' = D[i][j] - min_j D[i][j]: e_j = exp(-beta d'_j), S = sum e_j, H = log S + beta (sum d'_j e_j) / S;
+ *                            beta by sklearn's search (from 1; while H > log perplexity the lower bound moves up and beta doubles until an upper bound exists, then
+ *                            takes midpoints; the mirror image below), at most 100 steps, the first step with |H - log perplexity| <= tol the last (tol = 0: all
+ *                            100 unless H hits the target).  Pc[i][j] = e_j / S at the last beta evaluated, Pc[i][i] = 0; beta [N]; steps [N] (int) = the steps
+ *                            taken.  0 < perplexity < N, tol >= 0.  One workgroup per row, the shifted row in LDS; the trip count is at most 100 for every
+ *                            input, non-finite ones included.  Pc must not be D.
+ *   cvae_tsne_joint_f64      P = max((Pc + Pc^T) / s, 2^-52) off the diagonal, 0 on it, s = the sum of all entries of Pc + Pc^T (32 x 32 tile sums, added in
+ *                            order by one workgroup); P is bitwise symmetric.  info (device int [1]): 0, or 2 if an entry of D, Pc or the sum is not finite (P is
+ *                            then unspecified).  workspace: cvae_tsne_joint_f64_workspace_bytes(N).  Three launches.  P must be neither Pc nor D.
+ *   cvae_tsne_forces_f64     the pair pass: per row i over j != i, w = 1 / (1 + |y_i - y_j|^2): S [N] = sum w, A = sum P w (y_i - y_j), R = sum w^2 (y_i - y_j)
+ *                            and, unless kl_partials is NULL, kl_partials [3][N] = (sum P log P, sum P log w, sum P).  P must be positive off the diagonal for the
+ *                            partials (cvae_tsne_joint_f64's is).  A few rows per workgroup, the columns strided over its threads, Y in LDS.
+ *   cvae_tsne_grad_f64       Zs = sum S in a fixed order, grad = 4 (exaggeration A - R / Zs) and, unless kl is NULL, kl [1] = the KL divergence of
+ *                            exaggeration P from Q = w / Zs: exaggeration (sum P log P + (log exaggeration + log Zs) sum P - sum P log w).  sklearn's clamp of Q
+ *                            at 2^-52 is not applied.
+ *   cvae_tsne_update_f64     one iteration of sklearn's _gradient_descent on every element: with grad as above, gains = (update grad < 0) ? gains + 0.2 :
+ *                            0.8 gains, at least 0.01; update = momentum update - learning_rate gains grad; Y += update; written to Y_out, update_out, gains_out
+ *                            (which must not be the inputs: nothing is updated in place).  Unless record is NULL, record [4] = (that KL, |gains grad|^2, 1.0 if
+ *                            a new position, the KL or the norm is not finite else 0.0, Zs).
+ *   cvae_tsne_fit_f64        TSNE._tsne from P and Y (in: the start, out: the embedding): min(250, max_iter) iterations at early_exaggeration and momentum 0.5,
+ *                            then up to max_iter at 1 and 0.8, two launches per iteration (forces, update) between two sets of buffers in `workspace`
+ *                            (cvae_tsne_fit_f64_workspace_bytes).  NOT enqueue-only: after every iteration i with (i + 1) % 50 == 0 the host reads the record
+ *                            (a stream synchronisation each; the entry cannot be captured into a graph) and applies sklearn's tests in sklearn's order: a KL that
+ *                            is not a new best for more than 250 (first phase) or n_iter_without_progress (second) iterations ends the phase; a |gains grad| <=
+ *                            min_grad_norm ends the fit (sklearn would go on to the second phase and stop at its first check).  kl [1] = the KL of P
+ *                            (exaggeration 1) at the returned Y, from one more pair pass (sklearn reports the KL before the last update); max_iter = 0 returns Y
+ *                            unchanged with its KL.  info (device int [4]): info[0] = 0, or 2 if a position, the KL or the norm stopped being finite (seen at a
+ *                            check or at the end); info[1] = the index of the last iteration run (sklearn's n_iter_; 0 if none ran); info[2] = why the descent
+ *                            ended: 0 the iterations ran out, 1 the gradient norm, 2 no progress in the second phase; info[3] = the records read. */
+int cvae_tsne_sqdist_f64(const void* Z, int z_is_f32, int64_t z_stride, int64_t N, int64_t d, double* D, void* stream);
+int cvae_tsne_affinities_f64(const double* D, int64_t N, double perplexity, double tol, double* Pc, double* beta, int* steps, void* stream);
+size_t cvae_tsne_joint_f64_workspace_bytes(int64_t N);
+int cvae_tsne_joint_f64(const double* D, const double* Pc, int64_t N, double* P, int* info, void* workspace, size_t workspace_bytes, void* stream);
+int cvae_tsne_forces_f64(const double* Y, const double* P, int64_t N, double* A, double* R, double* S, double* kl_partials, void* stream);
+int cvae_tsne_grad_f64(const double* A, const double* R, const double* S, const double* kl_partials, int64_t N, double exaggeration, double* grad, double* kl,
+                       void* stream);
+int cvae_tsne_update_f64(const double* Y, const double* update, const double* gains, const double* A, const double* R, const double* S, const double* kl_partials,
+                         int64_t N, double exaggeration, double momentum, double learning_rate, double* Y_out, double* update_out, double* gains_out, double* record,
+                         void* stream);
+size_t cvae_tsne_fit_f64_workspace_bytes(int64_t N);
+int cvae_tsne_fit_f64(const double* P, double* Y, int64_t N, double early_exaggeration, double learning_rate, int64_t max_iter, int64_t n_iter_without_progress,
+                      double min_grad_norm, double* kl, int* info, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
