@@ -218,6 +218,8 @@ SIGNATURES = {
     "cvae_tsne_update_f64": [_p] * 7 + [_i64, _d, _d, _d, _p, _p, _p, _p, _p],
     "cvae_tsne_fit_f64_workspace_bytes": [_i64],
     "cvae_tsne_fit_f64": [_p, _p, _i64, _d, _d, _i64, _i64, _d, _p, _p, _p, _sz, _p],
+    "cvae_morph12_threads": [_i64, _i64],
+    "cvae_morph12_f32": [_p, _i64, _i64, _i64, _f, _d, _d, _d, _d, _p, _p, _p],
 }
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,

@@ -3592,3 +3592,53 @@ def tsne_fit_f64(P, Y0, early_exaggeration=12.0, learning_rate="auto", max_iter=
         raise L.CvaeError(f"cvae_tsne_fit_f64: the embedding or its KL divergence stopped being finite by iteration {n_iter} (info = {code}): a NaN in P or Y0, "
                           "or a learning rate that is too large?")
     return TsneFit(Y=Y, kl=float(kl.item()), n_iter=n_iter, reason=reason, checks=checks)
+
+
+# ---- the 12 morphology features of small grey images (csrc/morphology.hip) ----
+MORPH_MAX_SIDE, MORPH_RAW_WORDS = 64, 32
+MORPH_NORMS = (784.0, 100.0, 5.0, 28.0)          # area, perimeter, thickness, major axis: the reference's divisors for 28 x 28 digits
+MORPH_EMPTY, MORPH_NO_BACKGROUND = 1, 2          # bits of raw[:, 0]
+
+
+def morph_args(what, x, threshold=0.2, norms=MORPH_NORMS):
+    """Every refusal of morph_features12, raised before any launch; the device is asked about last, so that the others can be met without one.  Returns (B, H, W)."""
+    if not torch.is_tensor(x) or x.dim() not in (3, 4):
+        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise L.CvaeError(f"{what}: images [B, H, W] or [B, 1, H, W] expected, got {got}")
+    if x.dim() == 4 and x.shape[1] != 1:
+        raise L.CvaeError(f"{what}: one channel expected (grey images [B, 1, H, W]), got {x.shape[1]} in {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise L.CvaeError(f"{what}: float32, bfloat16 or float16 images expected (uint8 images: divide by 255 first, as ToTensor does), got {x.dtype}")
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if B < 1 or H < 1 or W < 1:
+        raise L.CvaeError(f"{what}: at least one image of at least one pixel expected, got {tuple(x.shape)}")
+    if H > MORPH_MAX_SIDE or W > MORPH_MAX_SIDE:
+        raise L.CvaeError(f"{what}: H, W <= {MORPH_MAX_SIDE} expected (an image and its working arrays stay in one workgroup's LDS), got {H} x {W}")
+    try:
+        norms = tuple(float(v) for v in norms)
+    except (TypeError, ValueError):
+        norms = ()
+    if len(norms) != 4 or not all(v > 0.0 and math.isfinite(v) for v in norms):
+        raise L.CvaeError(f"{what}: norms must be four positive finite numbers (area, perimeter, thickness, axis), got {norms!r}")
+    if not math.isfinite(float(threshold)):
+        raise L.CvaeError(f"{what}: threshold must be finite, got {threshold}")
+    L.require_gpu(x)
+    return B, H, W
+
+
+def morph_features12(x, threshold=0.2, norms=MORPH_NORMS, return_raw=False):
+    """feats [B, 12] float32: the reference's extract_refined_features of every image of x ([B, H, W] or [B, 1, H, W] on the device, H, W <= 64; float32 as
+    it is, bfloat16 / float16 converted first), in its order (Area, Perimeter, Thickness, MajorAxis, Eccentricity, Orientation, Solidity, Extent, AspectRatio,
+    Euler, H_Symmetry, V_Symmetry); cvae_morph12_f32: one launch, one workgroup per image, enqueue-only.  threshold is compared in float32.  An empty mask
+    gives twelve zeros; a mask without a background pixel a NaN thickness.  return_raw: (feats, raw), raw int32 [B, 32] = the integers behind the features
+    (include/cvae_hip.h, CVAE_MORPH_RAW_*)."""
+    what = "morph_features12"
+    B, H, W = morph_args(what, x, threshold, norms)
+    xx = x.detach().reshape(B, H, W)
+    if xx.dtype != torch.float32:
+        xx = xx.float()
+    xx = xx.contiguous()
+    feats = _empty((B, 12), torch.float32, xx)
+    raw = _empty((B, MORPH_RAW_WORDS), torch.int32, xx) if return_raw else None
+    check(L.timed(f"morph12 B{B} {H}x{W}", lib.cvae_morph12_f32, ptr(xx), B, H, W, float(threshold), *(float(v) for v in norms), ptr(feats), ptr(raw), stream()), what)
+    return (feats, raw) if return_raw else feats

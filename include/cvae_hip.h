@@ -1085,6 +1085,51 @@ size_t cvae_tsne_fit_f64_workspace_bytes(int64_t N);
 int cvae_tsne_fit_f64(const double* P, double* Y, int64_t N, double early_exaggeration, double learning_rate, int64_t max_iter, int64_t n_iter_without_progress,
                       double min_grad_norm, double* kl, int* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Morphology of small grey images (csrc/morphology.hip): the 12 features of the reference's extract_refined_features
+ * (mnist_test/01_baseline_causal_vae/dataset.py:11-99) for a batch, ONE launch, one workgroup per image, everything in LDS; enqueue-only (no host read, no
+ * allocation: the call can be captured into a graph).  x [B][H][W] fp32 contiguous, 1 <= H, W <= CVAE_MORPH_MAX_SIDE, B >= 1; feats [B][12] fp32; raw NULL or
+ * int [B][CVAE_MORPH_RAW_WORDS].  Coordinates are (r, c).  Per image, in integers: mask = x > threshold (fp32; a NaN is background); 8-connected components,
+ * labelled in raster order of their first pixel; the measured component is the one of largest area, ties to the lowest label; its area, bounding box and raw
+ * sums; its perimeter histogram (border = component minus its erosion by the 4-neighbour cross, outside = background; code = 1 + 2 (4-neighbours in border) +
+ * 10 (diagonal neighbours in border)); the largest squared Euclidean distance from a pixel of the WHOLE mask to the nearest background pixel of the image;
+ * the number of pixel centres inside or on the convex hull of the points (r +- 1/2, c), (r, c +- 1/2) of the component's pixels; the bit-quad counts of the
+ * zero-padded component.  The features, formed in fp64 and rounded once, in the reference's order:
+ *   A / area_norm;  (n[5,7,15,17,25,27] + sqrt 2 n[21,33] + (1 + sqrt 2) / 2 n[13,23]) / perimeter_norm;  sqrt(max d^2) / thickness_norm;
+ *   4 sqrt(lambda1) / axis_norm;  sqrt(disc / lambda1) (0 if lambda1 = 0);  (orientation + pi / 2) / pi;  A / convex;  A / (h w);  (w / h) / 3;  (euler + 2) / 4;
+ *   1 - mean |x - fliplr x|;  1 - mean |x - flipud x|   (over the whole grey image, fp32 differences added in fp64 in a fixed order)
+ * with a = mu02 / A, c = mu20 / A, b = -mu11 / A, disc = sqrt((a - c)^2 + 4 b^2), lambda1 = (a + c + disc) / 2, orientation = atan2(-2 b, c - a) / 2, or
+ * -pi / 4 (b < 0) / +pi / 4 when a == c exactly.  An empty mask gives twelve zeros; a mask without a background pixel gives a NaN thickness.  An image's output
+ * bits depend on the image alone.  Codes: B, H or W < 1, a norm that is not positive, a NaN threshold: CVAE_E_BADSHAPE; H or W above the limit, B >= 2^31:
+ * CVAE_E_UNSUPPORTED; x or feats NULL: CVAE_E_NULLPTR.  cvae_morph12_threads: the threads per image this build uses for a shape (CVAE_MORPH_THREADS up to
+ * CVAE_MORPH_SMALL_PIXELS pixels, CVAE_MORPH_THREADS_LARGE above); the output does not depend on it. */
+#define CVAE_MORPH_MAX_SIDE 64
+#define CVAE_MORPH_RAW_WORDS 32
+#define CVAE_MORPH_RAW_STATUS 0      /* bits: CVAE_MORPH_EMPTY, CVAE_MORPH_NO_BACKGROUND */
+#define CVAE_MORPH_RAW_COMPONENTS 1  /* 8-connected components of the mask */
+#define CVAE_MORPH_RAW_FIRST 2       /* raster index r W + c of the measured component's first pixel; -1 for an empty mask */
+#define CVAE_MORPH_RAW_AREA 3
+#define CVAE_MORPH_RAW_MINR 4        /* the bounding box as skimage gives it: min row, min column, max row + 1, max column + 1 */
+#define CVAE_MORPH_RAW_MINC 5
+#define CVAE_MORPH_RAW_MAXR 6
+#define CVAE_MORPH_RAW_MAXC 7
+#define CVAE_MORPH_RAW_SR 8          /* sum r, sum c, sum r^2, sum c^2, sum r c over the component */
+#define CVAE_MORPH_RAW_SC 9
+#define CVAE_MORPH_RAW_SRR 10
+#define CVAE_MORPH_RAW_SCC 11
+#define CVAE_MORPH_RAW_SRC 12
+#define CVAE_MORPH_RAW_PERIM 13      /* ten counts, of the codes 5, 7, 15, 17, 25, 27 (weight 1), 21, 33 (sqrt 2), 13, 23 ((1 + sqrt 2) / 2) */
+#define CVAE_MORPH_RAW_MAXD2 23      /* -1 without a background pixel */
+#define CVAE_MORPH_RAW_CONVEX 24
+#define CVAE_MORPH_RAW_Q1 25         /* bit-quads with one, three, two diagonal pixels set; euler = (Q1 - Q3 - 2 QD) / 4 */
+#define CVAE_MORPH_RAW_Q3 26
+#define CVAE_MORPH_RAW_QD 27
+#define CVAE_MORPH_RAW_EULER 28      /* words 29 .. 31 are 0; an empty mask leaves every word but STATUS and FIRST 0 */
+#define CVAE_MORPH_EMPTY 1
+#define CVAE_MORPH_NO_BACKGROUND 2
+int cvae_morph12_threads(int64_t H, int64_t W);
+int cvae_morph12_f32(const float* x, int64_t B, int64_t H, int64_t W, float threshold, double area_norm, double perimeter_norm, double thickness_norm,
+                     double axis_norm, float* feats, int* raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
