@@ -456,16 +456,14 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dout, const T* __re
         const int64_t w = p % W, h = (p / W) % H, d = p / (W * H);
         float acc = 0.f;
         if (!mask || to_f32(mask[i]) > 0.f) {
-            const int64_t odc = (d * OD) / D, ohc = (h * OH) / H, owc = (w * OW) / W;
-            for (int64_t od = max(odc - 1, (int64_t)0); od <= min(odc + 1, OD - 1); ++od) {
+            // the windows that contain index i of an axis are exactly o = floor(i O / I) .. ceil((i + 1) O / I) - 1 (window o is [floor(o I / O), ceil((o + 1) I / O)):
+            // i >= lo(o) <=> o <= floor(((i + 1) O - 1) / I), i < hi(o) <=> o >= floor(i O / I)), for any I and O: no membership test, ascending order as before
+            for (int64_t od = (d * OD) / D; od <= ((d + 1) * OD - 1) / D; ++od) {
                 const int64_t d0 = pool_lo(od, D, OD), d1 = pool_hi(od, D, OD);
-                if (d < d0 || d >= d1) continue;
-                for (int64_t oh = max(ohc - 1, (int64_t)0); oh <= min(ohc + 1, OH - 1); ++oh) {
+                for (int64_t oh = (h * OH) / H; oh <= ((h + 1) * OH - 1) / H; ++oh) {
                     const int64_t h0 = pool_lo(oh, H, OH), h1 = pool_hi(oh, H, OH);
-                    if (h < h0 || h >= h1) continue;
-                    for (int64_t ow = max(owc - 1, (int64_t)0); ow <= min(owc + 1, OW - 1); ++ow) {
+                    for (int64_t ow = (w * OW) / W; ow <= ((w + 1) * OW - 1) / W; ++ow) {
                         const int64_t w0 = pool_lo(ow, W, OW), w1 = pool_hi(ow, W, OW);
-                        if (w < w0 || w >= w1) continue;
                         acc += dout[b * dstride + c * OV + (od * OH + oh) * OW + ow] / (float)((d1 - d0) * (h1 - h0) * (w1 - w0));
                     }
                 }

@@ -60,7 +60,10 @@ __global__ __launch_bounds__(256) void k4_to_conv3_grad_kernel(const float* __re
 
 // ------------------------------------------------------------------------------------------------ clamp
 __global__ void clamp_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float lo, float hi, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = fminf(fmaxf(x[i], lo), hi);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = x[i];
+        y[i] = v != v ? v : fminf(fmaxf(v, lo), hi);         // torch.clamp keeps a NaN; fmaxf(NaN, lo) alone would answer lo
+    }
 }
 // torch.clamp backward: the gradient passes where lo <= x <= hi
 __global__ void clamp_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ dx, float lo, float hi, int64_t n) {
@@ -152,10 +155,9 @@ __global__ void bn2d_finalize_rstd_kernel(const float* __restrict__ part, int ro
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     const float var = bn2d_row_sum(part, rows, C, c) / P;
-    if (running_mean) {
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean[c];
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (P / (P - 1.f));
-    }
+    // each pointer on its own (the header lets either be NULL; running_var used to be written whenever running_mean was given)
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean[c];
+    if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (P / (P - 1.f));
     rstd[c] = 1.f / sqrtf(var + eps);
 }
 __global__ void bn2d_finalize_grads_kernel(const float* __restrict__ part_b, const float* __restrict__ part_g, int rows, float* __restrict__ dbeta,

@@ -234,11 +234,15 @@ int cvae_k4_to_conv3_grad(const float* dk4, float* dw3, int64_t Cout, int64_t Ci
 /* torch.clamp(x, lo, hi) and its backward (the gradient passes where lo <= x <= hi); fp32 */
 int cvae_clamp_fwd(const float* x, float* y, float lo, float hi, int64_t n, void* stream);
 int cvae_clamp_bwd(const float* x, const float* g, float* dx, float lo, float hi, int64_t n, void* stream);
-/* nn.BatchNorm2d (+ fused activation `act`) on a channels-last tensor [P = B*H*W][C] (C % 8 == 0).  training: two-pass batch
- * statistics (mean, then sum of squared deviations) into mean / rstd, running_* updated with the unbiased variance (may be NULL);
- * otherwise mean / rstd are inputs (running mean, 1/sqrt(running_var + eps)).  y = act((x - mean) rstd gamma + beta). */
-/* workspace: cvae_bn2d_workspace_bytes(P, C) — per-workgroup partial rows of the channel statistics, added in index order by the
- * finalize launches (no float atomics; required in training mode and by the backward). */
+/* nn.BatchNorm2d (+ fused activation `act`) on a channels-last tensor [P = B*H*W][C], P >= 1 (training: P >= 2), 8 <= C <= 2048 and
+ * C % 8 == 0, else CVAE_E_BADSHAPE; x, dy, y, dx 16-byte aligned (16-byte loads and stores without a fallback).  training: two-pass batch
+ * statistics (mean, then sum of squared deviations) into mean / rstd, running_mean / running_var updated with the unbiased variance
+ * (either may be NULL, each on its own); otherwise mean / rstd are inputs (running mean, 1/sqrt(running_var + eps)) and the running
+ * statistics and the workspace are not touched.  y = act((x - mean) rstd gamma + beta). */
+/* workspace: cvae_bn2d_workspace_bytes(P, C) (0 for a shape the entries refuse) — per-workgroup partial rows of the channel statistics,
+ * added in index order by the finalize launches (no float atomics; required in training mode and by the backward: NULL is
+ * CVAE_E_NULLPTR, too small CVAE_E_WORKSPACE, both before any launch; the forward uses one set of rows and is satisfied with half of
+ * cvae_bn2d_workspace_bytes, the backward needs all of it). */
 size_t cvae_bn2d_workspace_bytes(int64_t P, int64_t C);
 int cvae_bn2d_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, float* running_mean, float* running_var,
                   int64_t P, int64_t C, float momentum, float eps, int training, int act, int dtype, void* workspace, size_t workspace_bytes, void* stream);
