@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVAE_HIP_LIB") or os.path.join(_HERE, "libcvae_hip.so")
 
 F32, BF16, FP8 = 0, 1, 2
+U16 = 3          # CVAE_U16: cvae_mip_max's source only
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY02, ACT_LEAKY001 = 0, 1, 2, 3, 4
 _ACT = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "leaky02": ACT_LEAKY02, "leaky001": ACT_LEAKY001}
 
@@ -220,6 +221,12 @@ SIGNATURES = {
     "cvae_tsne_fit_f64": [_p, _p, _i64, _d, _d, _i64, _i64, _d, _p, _p, _p, _sz, _p],
     "cvae_morph12_threads": [_i64, _i64],
     "cvae_morph12_f32": [_p, _i64, _i64, _i64, _f, _d, _d, _d, _d, _p, _p, _p],
+    "cvae_mip_max": [_p, _p, _i64, _i64, _i64, _i64, _i, _p],
+    "cvae_resize_bilinear_aa_f32": [_p, _p, _i64, _i64, _i64, _i64, _i64, _p],
+    "cvae_minmax_binarise_workspace_bytes": [_i64, _i64, _i64],
+    "cvae_minmax_binarise": [_p, _p, _p, _i64, _i64, _i64, _i, _i, _p, _sz, _p],
+    "cvae_percentile_clip_scale_workspace_bytes": [_i64, _i64],
+    "cvae_percentile_clip_scale": [_p, _p, _p, _i64, _i64, _p, _p, _p, _sz, _p],
 }
 _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_conv_data_workspace_bytes": _sz, "cvae_elbo_up2x_partials": _i64, "cvae_channel_sum_workspace_bytes": _sz,
@@ -232,7 +239,7 @@ _RESTYPE = {"cvae_strerror": C.c_char_p, "cvae_conv_wgrad_workspace_bytes": _sz,
             "cvae_token_gemm_wgrad_workspace_bytes": _sz, "cvae_layernorm256_bwd_workspace_bytes": _sz,
             "cvae_mhsa_relevance_step_workspace_bytes": _sz, "cvae_col_means_f64_workspace_bytes": _sz, "cvae_ridge_gram_f64_workspace_bytes": _sz,
             "cvae_eigh_f64_workspace_bytes": _sz, "cvae_centered_gram_f64_workspace_bytes": _sz, "cvae_tsne_joint_f64_workspace_bytes": _sz,
-            "cvae_tsne_fit_f64_workspace_bytes": _sz}
+            "cvae_tsne_fit_f64_workspace_bytes": _sz, "cvae_minmax_binarise_workspace_bytes": _sz, "cvae_percentile_clip_scale_workspace_bytes": _sz}
 
 for _name, _args in SIGNATURES.items():
     _fn = getattr(lib, _name)          # AttributeError here = header and library disagree: fail at import

@@ -6,6 +6,7 @@ activations are channels-last [B, D, H, W, C] (D = 1 for 2D) in the compute dtyp
 losses, BN and sampling are fp32.
 """
 import ctypes as C_
+import functools
 import math
 
 import torch
@@ -3642,3 +3643,205 @@ def morph_features12(x, threshold=0.2, norms=MORPH_NORMS, return_raw=False):
     raw = _empty((B, MORPH_RAW_WORDS), torch.int32, xx) if return_raw else None
     check(L.timed(f"morph12 B{B} {H}x{W}", lib.cvae_morph12_f32, ptr(xx), B, H, W, float(threshold), *(float(v) for v in norms), ptr(feats), ptr(raw), stream()), what)
     return (feats, raw) if return_raw else feats
+
+
+# ---- vessel image preparation (csrc/image_prep.hip) ----
+PREP_CONSTANT, PREP_NONFINITE = 1, 2          # CVAE_PREP_*: bits of a record's flag word
+PREP_MAX_BATCH, PREP_MAX_PIXELS = 65535, 2 ** 31 - 1
+
+
+def _prep_images(what, x, dims, dtypes, names):
+    """the refusals the four image_prep ops share: a tensor of `dims` axes, one of `dtypes`, no empty axis, at most PREP_MAX_BATCH images of less than 2^31 pixels"""
+    if not torch.is_tensor(x) or x.dim() != dims:
+        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise L.CvaeError(f"{what}: a tensor {names} expected, got {got}")
+    if x.dtype not in dtypes:
+        raise L.CvaeError(f"{what}: {' or '.join(str(d).replace('torch.', '') for d in dtypes)} expected, got {x.dtype}")
+    if min(x.shape) < 1:
+        raise L.CvaeError(f"{what}: no axis of {names} may be empty, got {tuple(x.shape)}")
+    if x.shape[0] > PREP_MAX_BATCH or x.shape[-2] * x.shape[-1] > PREP_MAX_PIXELS:
+        raise L.CvaeError(f"{what}: at most {PREP_MAX_BATCH} images of less than 2^31 pixels per call, got {tuple(x.shape)}")
+
+
+def _prep_size(what, size):
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise L.CvaeError(f"{what}: size must be (H, W), got {size!r}") from None
+    if H < 1 or W < 1 or H * W > PREP_MAX_PIXELS:
+        raise L.CvaeError(f"{what}: size must be (H, W) with H, W >= 1 and less than 2^31 pixels, got {size!r}")
+    return H, W
+
+
+def mip_args(what, x):
+    """Every refusal of mip_max, raised before any launch; the device is asked about last.  Returns (B, D, Hs, Ws)."""
+    _prep_images(what, x, 4, (torch.uint16, torch.float32), "[B, D, Hs, Ws]")
+    L.require_gpu(x)
+    return tuple(x.shape)
+
+
+def mip_max(x):
+    """[B, D, Hs, Ws] uint16 or float32 on the device -> float32 [B, Hs, Ws], the maximum over D (np.max(axis=0) of each stack: a NaN propagates);
+    cvae_mip_max, one launch, enqueue-only."""
+    what = "mip_max"
+    B, D, Hs, Ws = mip_args(what, x)
+    xx = x.detach().contiguous()
+    out = _empty((B, Hs, Ws), torch.float32, xx)
+    check(L.timed(f"mip_max B{B} D{D} {Hs}x{Ws}", lib.cvae_mip_max, ptr(xx), ptr(out), B, D, Hs, Ws, L.U16 if xx.dtype == torch.uint16 else L.F32, stream()), what)
+    return out
+
+
+# the antialiased resize stages a tile's source rows in LDS: AA_TILE_H rows of output need about (AA_TILE_H + 2) * max(Hs / H, 1) + 2 of them, AA_TILE_W floats each
+AA_TILE_W, AA_TILE_H, AA_LDS_BYTES = 64, 8, 160 * 1024
+
+
+def _aa_window(i, n_in, n_out):
+    scale = n_in / n_out
+    support = max(scale, 1.0)
+    c = scale * (i + 0.5)
+    return max(0, int(c - support + 0.5)), min(int(c + support + 0.5), n_in)
+
+
+@functools.lru_cache(maxsize=64)
+def aa_lds_bytes(Hs, Ws, H, W):
+    """the LDS one workgroup of cvae_resize_bilinear_aa_f32 needs for this shape (the entry point's own arithmetic; remembered per shape: the walk over
+    the outputs costs half a millisecond of host time at 768 x 1280, several times the kernel)"""
+    kw = max(b - a for a, b in (_aa_window(i, Ws, W) for i in range(W)))
+    kh = max(b - a for a, b in (_aa_window(i, Hs, H) for i in range(H)))
+    rows = max(_aa_window(min(o + AA_TILE_H, H) - 1, Hs, H)[1] - _aa_window(o, Hs, H)[0] for o in range(0, H, AA_TILE_H))
+    return 4 * (rows * AA_TILE_W + kw * AA_TILE_W + kh * AA_TILE_H + 2 * AA_TILE_W + 2 * AA_TILE_H)
+
+
+def resize_aa_args(what, x, size):
+    """Every refusal of resize_bilinear_aa, raised before any launch; the device is asked about last.  Returns (B, Hs, Ws, H, W)."""
+    _prep_images(what, x, 3, (torch.float32,), "[B, Hs, Ws]")
+    H, W = _prep_size(what, size)
+    B, Hs, Ws = x.shape
+    need = aa_lds_bytes(Hs, Ws, H, W)
+    if need > AA_LDS_BYTES or -(-H // AA_TILE_H) > 65535:
+        raise L.CvaeError(f"{what}: {Hs} x {Ws} -> {H} x {W} needs {need} bytes of LDS for the source rows of one output tile, above the {AA_LDS_BYTES} of a "
+                          "workgroup (a height ratio above about 50): reduce in two steps")
+    L.require_gpu(x)
+    return B, Hs, Ws, H, W
+
+
+def resize_bilinear_aa(x, size):
+    """F.interpolate(x[:, None], size, mode="bilinear", antialias=True, align_corners=False)[:, 0] (torchvision's Resize(antialias=True)) of float32
+    [B, Hs, Ws] on the device -> float32 [B, H, W]; cvae_resize_bilinear_aa_f32: one launch, both passes, enqueue-only.  Weights are formed in float64 and
+    rounded once, the sums run in float32.  Equal sizes copy."""
+    what = "resize_bilinear_aa"
+    B, Hs, Ws, H, W = resize_aa_args(what, x, size)
+    xx = x.detach().contiguous()
+    out = _empty((B, H, W), torch.float32, xx)
+    check(L.timed(f"resize_aa B{B} {Hs}x{Ws}->{H}x{W}", lib.cvae_resize_bilinear_aa_f32, ptr(xx), ptr(out), B, Hs, Ws, H, W, stream()), what)
+    return out
+
+
+class BinariseStats:
+    """cvae_binarise_record per source image, as device tensors [B]: mn, mx float32, thr float64, ones int64 (of the unflipped variant), flags int32"""
+
+    def __init__(self, rec):
+        self.thr, self.ones = rec.view(torch.float64)[:, 0], rec.view(torch.int64)[:, 1]
+        f = rec.view(torch.float32)
+        self.mn, self.mx, self.flags = f[:, 4], f[:, 5], rec.view(torch.int32)[:, 6]
+
+
+def binarise_args(what, y, augment=False, dtype=torch.float32):
+    """Every refusal of minmax_binarise, raised before any launch; the device is asked about last.  Returns (B, H, W)."""
+    _prep_images(what, y, 3, (torch.float32,), "[B, H, W]")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise L.CvaeError(f"{what}: the masks are written as float32 or bfloat16, got dtype={dtype}")
+    L.require_gpu(y)
+    return tuple(y.shape)
+
+
+def minmax_binarise(y, augment=False, dtype=torch.float32):
+    """The tail of the reference's VesselDataset.__getitem__ for float32 [B, H, W] on the device: per image v = (y - min) / (max - min) in float32, the mask
+    v > mean(v) (the mean: a float64 sum in a fixed order), as [B * A, 1, H, W] of 0 / 1 in `dtype`; augment: A = 4, image b's variants at 4 b + a, a = 0 as it
+    is, 1 flipped horizontally, 2 vertically, 3 both (the dataset's index real_idx * 4 + aug_mode).  A constant image gives zeros (flag PREP_CONSTANT), and so
+    does one with a NaN or an infinity (PREP_NONFINITE).  Returns (masks, BinariseStats).  cvae_minmax_binarise: three launches, enqueue-only."""
+    what = "minmax_binarise"
+    B, H, W = binarise_args(what, y, augment, dtype)
+    yy = y.detach().contiguous()
+    A = 4 if augment else 1
+    out = _empty((B * A, 1, H, W), dtype, yy)
+    rec = _empty((B, 32), torch.uint8, yy)
+    nbytes = lib.cvae_minmax_binarise_workspace_bytes(B, H, W)
+    ws = _empty((nbytes // 8 + 1,), torch.float64, yy)
+    check(L.timed(f"minmax_binarise B{B} {H}x{W} A{A}", lib.cvae_minmax_binarise, ptr(yy), ptr(out), ptr(rec), B, H, W, int(bool(augment)), L.dtype_code(dtype),
+                  ptr(ws), ws.numel() * 8, stream()), what)
+    return out, BinariseStats(rec)
+
+
+def percentile_ranks(n, p):
+    """numpy's "linear" percentile pair [100 - p, p] of n values as 0-based order statistics: ((lo, lo', hi, hi'), (t_lo, t_hi)) with the value of a percentile
+    = lerp(x[k], x[k'], t).  The virtual index is (n - 1) q with q = percent / 100, the expression numpy 2.x uses for this method (its _QuantileMethods table;
+    the general form n q + (alpha + q (1 - alpha - beta)) - 1 at alpha = beta = 1 differs from it in the last bits and does NOT reproduce np.percentile:
+    tests/test_image_prep_cpu.py).  Beyond the ends both neighbours are the end (numpy's _get_indexes), and t is taken against the neighbour as numpy indexes
+    it (-1 for the last)."""
+    ranks, ts = [], []
+    for pct in (100 - p, p):
+        q = pct / 100
+        vi = (n - 1) * q
+        if vi >= n - 1:
+            prev, k0, k1 = -1, n - 1, n - 1
+        elif vi < 0:
+            prev, k0, k1 = 0, 0, 0
+        else:
+            prev = k0 = math.floor(vi)
+            k1 = k0 + 1
+        ranks += [k0, k1]
+        ts.append(vi - prev)
+    return tuple(ranks), tuple(ts)
+
+
+def percentile_args(what, x, p=99.5):
+    """Every refusal of percentile_clip_scale, raised before any launch; the device is asked about last.  Returns (B, N)."""
+    if not torch.is_tensor(x) or x.dim() not in (2, 3):
+        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+        raise L.CvaeError(f"{what}: a tensor [B, N] or [B, H, W] expected, got {got}")
+    _prep_images(what, x if x.dim() == 3 else x[:, None, :], 3, (torch.float32,), "[B, N] or [B, H, W]")
+    try:
+        ok = 50.0 <= float(p) <= 100.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise L.CvaeError(f"{what}: a clip percentile in [50, 100] expected, got {p!r}")
+    L.require_gpu(x)
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+class ClipStats:
+    """cvae_clip_record per image, as device tensors [B]: vmin, vmax float64, flags int32"""
+
+    def __init__(self, rec):
+        d = rec.view(torch.float64)
+        self.vmin, self.vmax, self.flags = d[:, 0], d[:, 1], rec.view(torch.int32)[:, 4]
+
+
+def percentile_clip_scale(x, p=99.5, check_finite=True):
+    """The reference's normalize_image for float32 [B, N] (or [B, H, W]) on the device: vmin, vmax = np.percentile(x_b, [100 - p, p]) found EXACTLY (a radix
+    select of the four order statistics, numpy's interpolation in float64), then (clip(x, vmin, vmax) - vmin) / (vmax - vmin, or 1e-5 when that is 0) in
+    float64, rounded once to float32.  Returns (out of x's shape, ClipStats).  cvae_percentile_clip_scale: nine launches, enqueue-only; check_finite reads the
+    flag words back afterwards (one host read) and raises for an image with a NaN or an infinity, which the reference would silently turn into NaNs; with
+    check_finite=False the caller looks at ClipStats.flags when it suits."""
+    what = "percentile_clip_scale"
+    B, N = percentile_args(what, x, p)
+    xx = x.detach().contiguous()
+    out = torch.empty_like(xx)
+    rec = _empty((B, 24), torch.uint8, xx)
+    ranks, ts = percentile_ranks(N, float(p))
+    nbytes = lib.cvae_percentile_clip_scale_workspace_bytes(B, N)
+    ws = _empty((nbytes // 8 + 1,), torch.float64, xx)
+    check(L.timed(f"percentile_clip_scale B{B} N{N}", lib.cvae_percentile_clip_scale, ptr(xx), ptr(out), ptr(rec), B, N, (C_.c_int64 * 4)(*ranks),
+                  (C_.c_double * 2)(*ts), ptr(ws), ws.numel() * 8, stream()), what)
+    stats = ClipStats(rec)
+    if check_finite:
+        raise_nonfinite(what, stats.flags)
+    return out, stats
+
+
+def raise_nonfinite(what, flags):
+    bad = torch.nonzero(flags.cpu() & PREP_NONFINITE).flatten().tolist()
+    if bad:
+        raise L.CvaeError(f"{what}: image(s) {bad} of the batch hold a NaN or an infinity; the percentiles of such an image are not defined")

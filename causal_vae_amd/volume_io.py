@@ -168,7 +168,8 @@ def write_tiff_stack(path, vol, compress=False):
 
 
 def mip(vol):
-    """The reference's projection (causal_cascade/dataset.py:103-109): element-wise maximum over the pages."""
+    """The reference's projection (causal_cascade/dataset.py:103-109): element-wise maximum over the pages.  On the host, in numpy; a batch of stacks
+    already on the device is projected by ops.mip_max (vessel.images prepares a model's input from it without coming back)."""
     return np.asarray(vol).max(axis=0)
 
 

@@ -1134,6 +1134,45 @@ int cvae_morph12_threads(int64_t H, int64_t W);
 int cvae_morph12_f32(const float* x, int64_t B, int64_t H, int64_t W, float threshold, double area_norm, double perimeter_norm, double thickness_norm,
                      double axis_norm, float* feats, int* raw, void* stream);
 
+/* ---- Vessel image preparation (csrc/image_prep.hip): the reference's two image transforms (vessel_analysis/00_core/dataset.py:192-237,
+ * latent_translator/utils.py:18-60) for a batch.  Every entry is enqueue-only (no host read, no allocation).  Grids depend on the shapes alone, there is no float
+ * atomic, and every sum that crosses workgroups is merged in a fixed order: an image's output bits depend on the image alone, not on B or its place in the batch.
+ * Common codes: a size < 1: CVAE_E_BADSHAPE; a dtype code the entry does not take: CVAE_E_DTYPE; B > 65535 or an image of 2^31 pixels or more:
+ * CVAE_E_UNSUPPORTED; a NULL pointer: CVAE_E_NULLPTR; a workspace that is NULL or too small: CVAE_E_WORKSPACE.  Nothing is launched on a refusal.
+ *
+ * cvae_mip_max: src [B][D][Hs][Ws] of uint16 (CVAE_U16) or fp32 (CVAE_F32) -> dst fp32 [B][Hs][Ws] = the maximum over D; a NaN propagates (np.max).
+ *
+ * cvae_resize_bilinear_aa_f32: torch's F.interpolate(mode="bilinear", antialias=True, align_corners=False) of src fp32 [B][Hs][Ws] -> dst fp32 [B][H][W], ONE
+ * launch: a workgroup owns an output tile, filters the source rows its tile needs along W into LDS and then along H from LDS.  Per axis n_in -> n_out, in fp64:
+ * scale = n_in / n_out, support = max(scale, 1), c = scale (i + 1/2), xmin = max(0, (int)(c - support + 1/2)), xmax = min((int)(c + support + 1/2), n_in),
+ * w_j = max(0, 1 - |(j - c + 1/2) / support|) over xmin <= j < xmax divided by their sum and rounded to fp32; the products are added in fp32 in ascending j.
+ * Equal sizes copy the bits.  A shape whose tile needs more source rows than LDS holds (a height ratio above about 50) is CVAE_E_UNSUPPORTED.
+ *
+ * cvae_minmax_binarise: y fp32 [B][H][W] -> out [B A][H][W] of 0 / 1 in fp32 or bf16 (out_dtype), A = 1 or 4 (image b's variants at b A + a: a = 0 as it is,
+ * 1 flipped along W, 2 along H, 3 both), and rec[b].  mn, mx = the image's extremes; v = fl32((y - mn) / fl32(mx - mn)) (two correctly rounded fp32
+ * operations); thr = (the fp64 sum of v in a fixed order) / (H W) in fp64; pixel = (double)v > thr.  mx == mn: zeros and CVAE_PREP_CONSTANT; a NaN or an
+ * infinity anywhere in the image: zeros and CVAE_PREP_NONFINITE.  Three launches (extremes, sum, apply); the statistics are formed once per source image.
+ *
+ * cvae_percentile_clip_scale: x fp32 [B][N] -> out fp32 [B][N] and rec[b].  ranks[4] = the 0-based order statistics (lo, lo', hi, hi') and t[2] the two
+ * fractions of numpy's "linear" percentile pair, computed by the caller; a radix select (4 passes of 8 bits over the order-preserving uint32 image of the
+ * floats, per-workgroup LDS histograms merged in order) finds the four values exactly; vmin = lerp(x_lo, x_lo', t[0]), vmax = lerp(x_hi, x_hi', t[1]) with
+ * numpy's lerp(a, b, t) = a + d t, or b - d (1 - t) when t >= 1/2, d = (double)fl32(b - a), in fp64 without contraction; denom = vmax - vmin, 1e-5 when 0;
+ * out = fl32((min(max((double)x, vmin), vmax) - vmin) / denom).  A NaN or an infinity in the image sets CVAE_PREP_NONFINITE (its output is unspecified).
+ * A rank outside [0, N): CVAE_E_BADSHAPE. */
+#define CVAE_U16 3                   /* dtype code of cvae_mip_max's source only */
+#define CVAE_PREP_CONSTANT 1
+#define CVAE_PREP_NONFINITE 2
+typedef struct { double thr; int64_t ones; float mn, mx; int32_t flags, reserved; } cvae_binarise_record;          /* 32 bytes; ones counts variant 0 */
+typedef struct { double vmin, vmax; int32_t flags, reserved; } cvae_clip_record;                                   /* 24 bytes */
+int cvae_mip_max(const void* src, float* dst, int64_t B, int64_t D, int64_t Hs, int64_t Ws, int src_dtype, void* stream);
+int cvae_resize_bilinear_aa_f32(const float* src, float* dst, int64_t B, int64_t Hs, int64_t Ws, int64_t H, int64_t W, void* stream);
+size_t cvae_minmax_binarise_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int cvae_minmax_binarise(const float* y, void* out, cvae_binarise_record* rec, int64_t B, int64_t H, int64_t W, int augment4, int out_dtype, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t cvae_percentile_clip_scale_workspace_bytes(int64_t B, int64_t N);
+int cvae_percentile_clip_scale(const float* x, float* out, cvae_clip_record* rec, int64_t B, int64_t N, const int64_t* ranks, const double* t, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
