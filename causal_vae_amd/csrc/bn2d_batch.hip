@@ -381,7 +381,6 @@ int bn2d_batch_bwd_launch(const void* y, const void* dy, const void* a, const fl
 }
 
 bool bnb_shape_ok(int64_t P, int64_t C) { return P >= 2 && P <= ((int64_t)1 << 40) && C >= 8 && C % 8 == 0 && C <= 2048; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 }  // namespace
 
@@ -399,10 +398,8 @@ static int bn2d_batch_fwd_checked(const void* y, const void* resid, const float*
     if (!(momentum >= 0.f && momentum <= 1.f) || !(eps > 0.f)) return CVAE_E_BADSHAPE;       // written so that a NaN is refused too
     if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_UNSUPPORTED;
     if (resid && act != CVAE_ACT_NONE) return CVAE_E_UNSUPPORTED;       // behind an activation `a` would no longer carry the sign the backward reads
-    if (!y || !gamma || !beta || !a || !mean || !rstd || !workspace || (running_mean == nullptr) != (running_var == nullptr)) return CVAE_E_NULLPTR;
-    if (!aligned16(y) || !aligned16(resid) || !aligned16(a) || !aligned4(gamma) || !aligned4(beta) || !aligned4(mean) || !aligned4(rstd) ||
-        !aligned4(running_mean) || !aligned4(running_var) || !aligned4(workspace))
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(y, gamma, beta, a, mean, rstd, workspace) || (running_mean == nullptr) != (running_var == nullptr)) return CVAE_E_NULLPTR;
+    if (!all_aligned<16>(y, resid, a) || !all_aligned<4>(gamma, beta, mean, rstd, running_mean, running_var, workspace)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_bn2d_batch_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
     return bn2d_batch_launch(y, resid, gamma, beta, a, mean, rstd, running_mean, running_var, P, (int)C, momentum, eps, act, dtype, (float*)workspace,
                              (hipStream_t)stream);
@@ -426,10 +423,8 @@ extern "C" int cvae_bn2d_batch_bwd(const void* y, const void* dy, const void* a,
     if (!bnb_shape_ok(P, C)) return CVAE_E_BADSHAPE;
     if (act < CVAE_ACT_NONE || act > CVAE_ACT_LEAKY001) return CVAE_E_UNSUPPORTED;
     const bool gated = act != CVAE_ACT_NONE;
-    if (!y || !dy || (gated && !a) || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned16(y) || !aligned16(dy) || (gated && !aligned16(a)) || !aligned16(dx) || !aligned4(gamma) || !aligned4(mean) || !aligned4(rstd) ||
-        !aligned4(dgamma) || !aligned4(dbeta) || !aligned4(workspace))
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(y, dy, gamma, mean, rstd, dx, dgamma, dbeta, workspace) || (gated && !a)) return CVAE_E_NULLPTR;
+    if (!all_aligned<16>(y, dy, dx) || (gated && !aligned16(a)) || !all_aligned<4>(gamma, mean, rstd, dgamma, dbeta, workspace)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_bn2d_batch_bwd_workspace_bytes(P, C)) return CVAE_E_WORKSPACE;
     return bn2d_batch_bwd_launch(y, dy, a, gamma, mean, rstd, dx, dgamma, dbeta, P, (int)C, act, dtype, (float*)workspace, (hipStream_t)stream);
 }

@@ -107,6 +107,13 @@ template <int N> __device__ __forceinline__ void store_from_f32(bf16* p, const f
     *(vec*)p = q;
 }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+// The refusal chains of the entry points: if (any_null(a, b)) return CVAE_E_NULLPTR; if (!all_aligned<8>(a, b, opt)) return CVAE_E_UNSUPPORTED;
+// A null pointer is aligned, so an optional argument goes into all_aligned as it is and stays out of any_null.
+template <typename... P> inline bool any_null(const P*... p) { return (... || (p == nullptr)); }
+template <int A, typename... P> inline bool all_aligned(const P*... p) { return (... && (((uintptr_t)p & (A - 1)) == 0)); }
+__host__ __device__ __forceinline__ bool finite_f64(double x) { return fabs(x) <= 1.7976931348623157e308; }          // DBL_MAX; false for a NaN
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -129,6 +136,56 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     if (threadIdx.x == 0)
         for (int i = 0; i < nw; ++i) r += red[i];
     return r;
+}
+
+// ---- The two fixed-order workgroup reductions of the analysis kernels (ridge, eigh, tsne, image_prep: "two runs give equal bits").  Each combines the
+// threads' values in ONE order that depends on the workgroup size alone.  The two orders differ, so their sums differ in the low bits: a call site keeps
+// the one it has and never switches.
+// (1) The LDS tree: thread t's value goes to red[t], then for s = NT / 2 .. 1 red[t] = op(red[t], red[t + s]) in the threads t < s; every thread
+// returns red[0].  Any type and any op (sum, max, an arg-max on a {value, index} pair).  A barrier at the head, none at the tail: `red` (NT elements of
+// LDS) is free to reuse after the call returns only behind the barrier at the head of the next call.
+template <int NT, typename T, typename Op> __device__ __forceinline__ T block_tree(T v, T* red, Op op) {
+    const int t = threadIdx.x;
+    __syncthreads();
+    red[t] = v;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (t < s) red[t] = op(red[t], red[t + s]);
+        __syncthreads();
+    }
+    return red[0];
+}
+// (2) The butterfly: a 64-lane xor butterfly (offsets 32 .. 1) inside each wave, then the four waves of a 256-thread workgroup in wave order.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// NV sums over a 256-thread workgroup, the result in every thread: red holds 4 NV doubles
+template <int NV> __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* red) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = wave_sum_f64(v[k]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) red[4 * k + wid] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = ((red[4 * k] + red[4 * k + 1]) + red[4 * k + 2]) + red[4 * k + 3];
+}
+// sum of x[0 .. n) by a 256-thread workgroup: a thread's strided terms in index order, then the butterfly
+__device__ __forceinline__ double ordered_sum_f64(const double* __restrict__ x, int n, double* red) {
+    double v[1] = {0.0};
+    for (int j = threadIdx.x; j < n; j += 256) v[0] += x[j];
+    block_sum_f64(v, red);
+    return v[0];
 }
 
 // 8 floats -> 8 fp8 (e4m3) codes of v * mul, saturating at +-448 (v_cvt_pk_fp8_f32 alone would produce NaN past the range)

@@ -13,7 +13,8 @@
 //                reduces the tiles, and the sweep in which no |a_pq| exceeded 2^-53 max |A| is the last.  The host reads that one word after every sweep (never
 //                inside one) and stops launching; EIGH_MAX_SWEEPS bounds the loop.  No kernel has a loop whose trip count depends on data.
 //   sort         ascending by rank counting in one workgroup, ties by original index; a gather launch permutes the columns of V
-// No float atomics, no workgroup waits on another, every grid and the pair order are functions of n alone: two runs give equal bits.
+// No float atomics, no workgroup waits on another, every grid and the pair order are functions of n alone: two runs give equal bits.  The only reductions
+// are maxima (common.h's block_tree at the start, plain loops in one thread after that), whose result no order can change.
 #include "common.h"
 
 namespace {
@@ -44,7 +45,9 @@ eigh_layout eigh_plan(int64_t n) {
     return L;
 }
 
-__device__ __forceinline__ bool finite_f64(double x) { return fabs(x) <= 1.7976931348623157e308; }          // false for a NaN
+struct MaxF64 {          // block_tree's op for the two maxima
+    __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; }
+};
 
 // (x, y) -> (c x - s y, s x + c y)
 __device__ __forceinline__ void rot2(double x, double y, double c, double s, double& lo, double& hi) {
@@ -67,13 +70,8 @@ __global__ __launch_bounds__(256) void eigh_init_kernel(const double* __restrict
         v0[e] = (i == j) ? 1.0 : 0.0;
         m = finite_f64(a) ? fabs(a) : __builtin_inf();
     }
-    red[t] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t + s] > red[t] ? red[t + s] : red[t];
-        __syncthreads();
-    }
-    if (t == 0) part[blockIdx.x] = red[0];
+    m = block_tree<256>(m, red, MaxF64{});
+    if (t == 0) part[blockIdx.x] = m;
 }
 // one workgroup: the threshold 2^-53 max |A|, the state words, the per-tile maxima cleared.  A non-finite entry ends the run here (info 2).
 __global__ __launch_bounds__(256) void eigh_setup_kernel(const double* __restrict__ part, int parts, double* __restrict__ off, double* __restrict__ tol,
@@ -82,16 +80,11 @@ __global__ __launch_bounds__(256) void eigh_setup_kernel(const double* __restric
     const int t = threadIdx.x;
     double m = 0.0;
     for (int g = t; g < parts; g += 256) m = part[g] > m ? part[g] : m;
-    red[t] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t + s] > red[t] ? red[t + s] : red[t];
-        __syncthreads();
-    }
+    m = block_tree<256>(m, red, MaxF64{});
     if (t < EIGH_MAX_N / 2 / EIGH_TILE) off[t] = 0.0;
     if (t == 0) {
-        const bool bad = !finite_f64(red[0]);
-        *tol = EIGH_U * red[0];
+        const bool bad = !finite_f64(m);
+        *tol = EIGH_U * m;
         state[ST_DONE] = bad ? 1 : 0;
         state[ST_INFO] = bad ? 2 : 0;
         state[ST_SWEEPS] = 0;
@@ -222,9 +215,6 @@ __global__ __launch_bounds__(256) void eigh_gather_kernel(const double* __restri
     out[(size_t)i * ldv + r] = (src >= 0 && src < n) ? v[(size_t)i * n + src] : 0.0;
 }
 
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 }  // namespace
 
 extern "C" int cvae_eigh_max_sweeps(void) { return EIGH_MAX_SWEEPS; }
@@ -237,8 +227,8 @@ extern "C" size_t cvae_eigh_f64_workspace_bytes(int64_t n) {
 extern "C" int cvae_eigh_f64(const double* A, int64_t lda, int64_t n, double* w, double* V, int64_t ldv, int* info, void* workspace, size_t workspace_bytes,
                              void* stream) {
     if (n < 1 || n > EIGH_MAX_N || lda < n || ldv < n) return CVAE_E_BADSHAPE;
-    if (!A || !w || !V || !info || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned8(A) || !aligned8(w) || !aligned8(V) || !aligned4(info) || !aligned8(workspace)) return CVAE_E_UNSUPPORTED;
+    if (any_null(A, w, V, info, workspace)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(A, w, V, workspace) || !aligned4(info)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_eigh_f64_workspace_bytes(n)) return CVAE_E_WORKSPACE;
     const eigh_layout L = eigh_plan(n);
     char* base = (char*)workspace;

@@ -11,7 +11,7 @@
 //                                 chunk order, pick each rank's digit); ranks whose prefixes still agree share one histogram.  Then numpy's lerp, clip and scale
 //                                 in fp64, rounded once.
 // No float atomics; a chunk is a fixed number of pixels, so grids and every order of summation depend on the image's shape alone: an image's bits depend on
-// nothing but the image.  The only global atomic is the INTEGER count of ones.  fp contraction is off for the whole file: numpy and torch do not fuse, and
+// nothing but the image (a workgroup combines its threads' values with common.h's LDS tree, block_tree).  The only global atomic is the INTEGER count of ones.  fp contraction is off for the whole file: numpy and torch do not fuse, and
 // the host replays the window arithmetic of the resize; the fp32 filter sums ask for their fma by name.
 #include <float.h>
 #include <math.h>
@@ -44,20 +44,6 @@ template <bool VEC> __device__ __forceinline__ int load4(const float* __restrict
     const int c = (int)(n - i < 4 ? n - i : 4);
     for (int e = 0; e < c; ++e) v[e] = p[i + e];
     return c;
-}
-
-// v of every thread combined by a tree of one fixed shape; every thread returns the result.  `red`: NT elements of LDS, free to reuse after the call returns
-// only behind the barrier at the head of the next call.
-template <typename T, typename Op> __device__ __forceinline__ T block_tree(T v, T* red, Op op) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = op(red[t], red[t + s]);
-        __syncthreads();
-    }
-    return red[0];
 }
 
 // ------------------------------------------------------------------------------------------------ maximum-intensity projection
@@ -203,9 +189,9 @@ template <bool VEC> __global__ __launch_bounds__(NT) void bin_extremes_kernel(co
         const int c = load4<VEC>(yi, (int64_t)g * PREP_CHUNK + (int64_t)(k * NT + t) * 4, n, v);
         for (int e = 0; e < c; ++e) { mn = fminf(mn, v[e]); mx = fmaxf(mx, v[e]); bad |= !finite_f32(v[e]); }
     }
-    mn = block_tree(mn, red.f, [](float a, float b) { return fminf(a, b); });
-    mx = block_tree(mx, red.f, [](float a, float b) { return fmaxf(a, b); });
-    bad = block_tree(bad, red.i, [](int a, int b) { return a | b; });
+    mn = block_tree<NT>(mn, red.f, [](float a, float b) { return fminf(a, b); });
+    mx = block_tree<NT>(mx, red.f, [](float a, float b) { return fmaxf(a, b); });
+    bad = block_tree<NT>(bad, red.i, [](int a, int b) { return a | b; });
     if (t == 0) {
         const size_t at = (size_t)blockIdx.y * G + g;
         ws.pmn[at] = mn; ws.pmx[at] = mx; ws.pbad[at] = bad;
@@ -216,9 +202,9 @@ __device__ __forceinline__ void bin_merge_extremes(const BinWs& ws, int G, BinRe
     const size_t at = (size_t)blockIdx.y * G;
     mn = INFINITY; mx = -INFINITY; bad = 0;
     for (int j = threadIdx.x; j < G; j += NT) { mn = fminf(mn, ws.pmn[at + j]); mx = fmaxf(mx, ws.pmx[at + j]); bad |= ws.pbad[at + j]; }
-    mn = block_tree(mn, red.f, [](float a, float b) { return fminf(a, b); });
-    mx = block_tree(mx, red.f, [](float a, float b) { return fmaxf(a, b); });
-    bad = block_tree(bad, red.i, [](int a, int b) { return a | b; });
+    mn = block_tree<NT>(mn, red.f, [](float a, float b) { return fminf(a, b); });
+    mx = block_tree<NT>(mx, red.f, [](float a, float b) { return fmaxf(a, b); });
+    bad = block_tree<NT>(bad, red.i, [](int a, int b) { return a | b; });
 }
 template <bool VEC> __global__ __launch_bounds__(NT) void bin_sum_kernel(const float* __restrict__ y, int64_t n, int G, BinWs ws, cvae_binarise_record* __restrict__ rec) {
     __shared__ BinRed red;
@@ -235,7 +221,7 @@ template <bool VEC> __global__ __launch_bounds__(NT) void bin_sum_kernel(const f
             const int c = load4<VEC>(yi, (int64_t)g * PREP_CHUNK + (int64_t)(k * NT + t) * 4, n, v);
             for (int e = 0; e < c; ++e) acc += (double)((v[e] - mn) / range);
         }
-    acc = block_tree(acc, red.d, [](double a, double b) { return a + b; });
+    acc = block_tree<NT>(acc, red.d, [](double a, double b) { return a + b; });
     if (t == 0) {
         ws.psum[(size_t)blockIdx.y * G + g] = acc;
         if (g == 0) rec[blockIdx.y].ones = 0;          // the apply launch counts into it
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(NT) void bin_apply_kernel(const float* __restrict__
     bin_merge_extremes(ws, G, red, mn, mx, bad);
     double total = 0.0;
     for (int j = t; j < G; j += NT) total += ws.psum[(size_t)b * G + j];
-    total = block_tree(total, red.d, [](double a, double c) { return a + c; });
+    total = block_tree<NT>(total, red.d, [](double a, double c) { return a + c; });
     const int flags = bad ? CVAE_PREP_NONFINITE : (mx > mn ? 0 : CVAE_PREP_CONSTANT);
     const double thr = flags ? 0.0 : total / (double)n;
     const float range = mx - mn;
@@ -450,7 +436,7 @@ extern "C" int cvae_mip_max(const void* src, float* dst, int64_t B, int64_t D, i
     if (B < 1 || D < 1 || Hs < 1 || Ws < 1) return CVAE_E_BADSHAPE;
     if (src_dtype != CVAE_F32 && src_dtype != CVAE_U16) return CVAE_E_DTYPE;
     if (Hs > MAX_PIXELS || Ws > MAX_PIXELS || D > MAX_PIXELS || prep_shape_rc(B, Hs * Ws) != CVAE_OK) return CVAE_E_UNSUPPORTED;
-    if (!src || !dst) return CVAE_E_NULLPTR;
+    if (any_null(src, dst)) return CVAE_E_NULLPTR;
     const int64_t P = Hs * Ws;
     const dim3 grid((unsigned)((P + NT * 8 - 1) / (NT * 8)), (unsigned)B);
     return with_bool(src_dtype == CVAE_U16, [&](auto u16) {
@@ -480,7 +466,7 @@ extern "C" int cvae_resize_bilinear_aa_f32(const float* src, float* dst, int64_t
     }
     const size_t lds = aa_lds_bytes(R, KW, KH);
     if (lds > CVAE_LDS_MAX) return CVAE_E_UNSUPPORTED;
-    if (!src || !dst) return CVAE_E_NULLPTR;
+    if (any_null(src, dst)) return CVAE_E_NULLPTR;
     if (cvae_allow_lds<resize_aa_kernel>(lds) != CVAE_OK) return CVAE_E_LAUNCH;
     hipLaunchKernelGGL(resize_aa_kernel, dim3((unsigned)((W + TW - 1) / TW), (unsigned)((H + TH - 1) / TH), (unsigned)B), dim3(NT), lds, (hipStream_t)stream, src, dst,
                        (int)Hs, (int)Ws, (int)H, (int)W, R, KW, KH);
@@ -496,9 +482,9 @@ extern "C" int cvae_minmax_binarise(const float* y, void* out, cvae_binarise_rec
     if (B < 1 || H < 1 || W < 1) return CVAE_E_BADSHAPE;
     if (out_dtype != CVAE_F32 && out_dtype != CVAE_BF16) return CVAE_E_DTYPE;
     if (H > MAX_PIXELS || W > MAX_PIXELS || prep_shape_rc(B, H * W) != CVAE_OK) return CVAE_E_UNSUPPORTED;
-    if (!y || !out || !rec) return CVAE_E_NULLPTR;
+    if (any_null(y, out, rec)) return CVAE_E_NULLPTR;
     const int64_t n = H * W;
-    if (!workspace || workspace_bytes < bin_ws_bytes(B, n) || ((uintptr_t)workspace & 7)) return CVAE_E_WORKSPACE;
+    if (!workspace || workspace_bytes < bin_ws_bytes(B, n) || !aligned8(workspace)) return CVAE_E_WORKSPACE;
     const int G = (int)bin_chunks(n), A = augment4 ? 4 : 1;
     const BinWs ws = bin_ws(workspace, B, n);
     const dim3 grid((unsigned)G, (unsigned)B);
@@ -527,14 +513,14 @@ extern "C" int cvae_percentile_clip_scale(const float* x, float* out, cvae_clip_
                                           size_t workspace_bytes, void* stream) {
     if (B < 1 || N < 1) return CVAE_E_BADSHAPE;
     if (prep_shape_rc(B, N) != CVAE_OK) return CVAE_E_UNSUPPORTED;
-    if (!x || !out || !rec || !ranks || !t) return CVAE_E_NULLPTR;
+    if (any_null(x, out, rec, ranks, t)) return CVAE_E_NULLPTR;
     SelRanks first;
     for (int r = 0; r < 4; ++r) {
         if (ranks[r] < 0 || ranks[r] >= N) return CVAE_E_BADSHAPE;
         first.k[r] = ranks[r];
     }
     if (!(t[0] == t[0]) || !(t[1] == t[1])) return CVAE_E_BADSHAPE;
-    if (!workspace || workspace_bytes < sel_ws_bytes(B, N) || ((uintptr_t)workspace & 7)) return CVAE_E_WORKSPACE;
+    if (!workspace || workspace_bytes < sel_ws_bytes(B, N) || !aligned8(workspace)) return CVAE_E_WORKSPACE;
     const int G = (int)sel_chunks(N);
     const SelWs ws = sel_ws(workspace, B, N);
     hipStream_t st = (hipStream_t)stream;

@@ -17,6 +17,7 @@
 //   path         per alpha of a grid in device memory: h = 1 / N + sum_k P_k^2 / (lambda_k + alpha), loo from Yhat = mbar + P diag(1 / (lambda + alpha)) Q, sse
 //   pca          the top components in descending order with sklearn's sign rule, their variances, ratios and singular values
 // No float atomics, no workgroup waits on another, every sum has one fixed order and every grid is a function of the shape alone: two runs give equal bits.
+// A sum is a thread's terms in index order, chunks in chunk order, and across a workgroup common.h's LDS tree (block_tree: stats, sse, PCA's arg-max).
 #include "common.h"
 
 namespace {
@@ -39,19 +40,11 @@ int64_t rg_parts(int64_t N) {
     return (N + chunk - 1) / chunk;
 }
 
-// the sum of v over the 256 threads of a workgroup, in a fixed tree order; every thread gets it
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
+// the sum of v over the 256 threads of a workgroup by common.h's LDS tree; every thread gets it
+__device__ __forceinline__ double tree_sum256(double v, double* red) {
+    return block_tree<256>(v, red, [](double a, double b) { return a + b; });
 }
+__device__ __forceinline__ double clamp0(double x) { return x > 0.0 ? x : 0.0; }          // an eigenvalue of a positive semidefinite matrix
 
 // ---- column means ----
 // grid (ceil(C / 256), parts): thread c adds its column over the chunk's rows in row order
@@ -321,13 +314,13 @@ __global__ __launch_bounds__(256) void ranking_stats_kernel(const double* __rest
     const int j = blockIdx.x, t = threadIdx.x;
     double sy = 0.0, sp = 0.0;
     for (int64_t i = t; i < N; i += 256) { sy += Y[i * ys + j]; sp += P[i * ps + j]; }
-    const double my = block_sum256(sy, red) / (double)N, mp = block_sum256(sp, red) / (double)N;
+    const double my = tree_sum256(sy, red) / (double)N, mp = tree_sum256(sp, red) / (double)N;
     double res = 0.0, syy = 0.0, spp = 0.0, syp = 0.0;
     for (int64_t i = t; i < N; i += 256) {
         const double y = Y[i * ys + j], p = P[i * ps + j], dy = y - my, dp = p - mp;
         res += (y - p) * (y - p); syy += dy * dy; spp += dp * dp; syp += dy * dp;
     }
-    res = block_sum256(res, red); syy = block_sum256(syy, red); spp = block_sum256(spp, red); syp = block_sum256(syp, red);
+    res = tree_sum256(res, red); syy = tree_sum256(syy, red); spp = tree_sum256(spp, red); syp = tree_sum256(syp, red);
     if (t != 0) return;
     r2[j] = (syy == 0.0) ? (res == 0.0 ? 1.0 : 0.0) : 1.0 - res / syy;      // a constant truth: sklearn's r2_score gives 1 for a perfect prediction, else 0
     double c = 0.0;
@@ -414,12 +407,12 @@ __global__ __launch_bounds__(256) void ridge_path_leverage_kernel(const double* 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int g = blockIdx.y;
     if (g == 0 && blockIdx.x == 0)
-        for (int k = threadIdx.x; k < d; k += 256) lam_out[k] = lam[k] > 0.0 ? lam[k] : 0.0;
+        for (int k = threadIdx.x; k < d; k += 256) lam_out[k] = clamp0(lam[k]);
     if (i >= N) return;
     const double alpha = alphas[g];
     double s = 0.0;
     for (int k = 0; k < d; ++k) {
-        const double v = P[i * d + k], l = lam[k] > 0.0 ? lam[k] : 0.0;
+        const double v = P[i * d + k], l = clamp0(lam[k]);
         s += v * v / (l + alpha);
     }
     h[(size_t)g * N + i] = 1.0 / (double)N + s;
@@ -437,7 +430,7 @@ __global__ __launch_bounds__(256) void ridge_path_loo_kernel(const double* __res
     const double alpha = alphas[g];
     double s = 0.0;
     for (int k = 0; k < d; ++k) {
-        const double l = lam[k] > 0.0 ? lam[k] : 0.0;
+        const double l = clamp0(lam[k]);
         s += P[i * d + k] * Q[(size_t)k * F + j] / (l + alpha);
     }
     const double yh = mbar[j] + s, y = M[i * ms + j];
@@ -454,49 +447,56 @@ __global__ __launch_bounds__(256) void ridge_path_sse_kernel(const double* __res
         const double r = M[i * ms + j] - lg[i * F + j];
         s += r * r;
     }
-    s = block_sum256(s, red);
+    s = tree_sum256(s, red);
     if (threadIdx.x == 0) sse[(size_t)g * F + j] = s;
 }
 
 // PCA's components from an ascending eigendecomposition (w [d], V [d][d], column k the eigenvector of w[k]): workgroup c takes column d - 1 - c (descending
 // order), finds its entry of largest |value| (lowest index on a tie) and writes the column, signed so that this entry is positive, as row c of comp [k][d];
 // thread 0 writes the variance w / (N - 1), its share of the sum of all d eigenvalues (added in index order) and the singular value sqrt(w), w clamped at 0.
+struct ArgMax { double v; int i; };
 __global__ __launch_bounds__(256) void pca_components_kernel(const double* __restrict__ w, const double* __restrict__ V, int64_t ldv, int d, int64_t N,
                                                              double* __restrict__ comp, double* __restrict__ var, double* __restrict__ ratio,
                                                              double* __restrict__ sing) {
-    __shared__ double bv[256];
-    __shared__ int bi[256];
+    __shared__ ArgMax red[256];
     const int c = blockIdx.x, t = threadIdx.x, col = d - 1 - c;
-    double best = -1.0;
-    int at = d;
+    ArgMax best = {-1.0, d};
     for (int i = t; i < d; i += 256) {          // ascending i within a thread: a strict > keeps the lowest index
         const double a = fabs(V[(size_t)i * ldv + col]);
-        if (a > best) { best = a; at = i; }
+        if (a > best.v) best = {a, i};
     }
-    bv[t] = best; bi[t] = at;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s && (bv[t + s] > bv[t] || (bv[t + s] == bv[t] && bi[t + s] < bi[t]))) { bv[t] = bv[t + s]; bi[t] = bi[t + s]; }
-        __syncthreads();
-    }
-    const int lead = bi[0];
+    // a larger value wins, at equal value the lower index
+    const int lead = block_tree<256>(best, red, [](ArgMax a, ArgMax b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }).i;
     const double sign = (lead < d && V[(size_t)lead * ldv + col] < 0.0) ? -1.0 : 1.0;
     for (int i = t; i < d; i += 256) comp[(size_t)c * d + i] = sign * V[(size_t)i * ldv + col];
     if (t != 0) return;
     double total = 0.0;
-    for (int k = 0; k < d; ++k) total += w[k] > 0.0 ? w[k] : 0.0;
-    const double l = w[col] > 0.0 ? w[col] : 0.0;
+    for (int k = 0; k < d; ++k) total += clamp0(w[k]);
+    const double l = clamp0(w[col]);
     var[c] = l / (double)(N - 1);
     ratio[c] = l / total;
     sing[c] = sqrt(l);
 }
 
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 constexpr int64_t RIDGE_MAX_ROWS = (int64_t)1 << 31;      // N and n stay below 2^31, F below 2^21 and N F below 2^38 (a grid of 256-thread workgroups over it)
 bool rows_features_ok(int64_t N, int64_t F) { return N < RIDGE_MAX_ROWS && F >= 1 && F < RIDGE_MAX_ROWS / 1024 && N * F < ((int64_t)1 << 38); }
 bool ridge_shape_ok(int64_t N, int64_t d, int64_t F) { return N >= 2 && d >= 1 && d <= 1024 && rows_features_ok(N, F); }
+bool gram_shape_ok(int64_t N, int64_t d, int64_t F) { return N >= 1 && N < RIDGE_MAX_ROWS && d >= 1 && d <= 1024 && F >= 0 && F < RIDGE_MAX_ROWS / 1024; }
 unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// behind both Gram entries, each of which has made its own checks of shape, pointers and alignment: the workspace (one [d, d + F] partial product per row
+// chunk), the chunks' products, and their sum in chunk order with `shift` added to the diagonal
+size_t gram_ws_bytes(int64_t N, int64_t d, int64_t F) { return (size_t)rg_parts(N) * d * (d + F) * sizeof(double); }
+int gram_launch(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N, int64_t d, int64_t F,
+                double shift, double* A, double* R, void* workspace, size_t workspace_bytes, void* stream) {
+    if (workspace_bytes < gram_ws_bytes(N, d, F)) return CVAE_E_WORKSPACE;
+    const int parts = (int)rg_parts(N);
+    const int64_t W = d + F;
+    hipLaunchKernelGGL(ridge_gram_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)parts), dim3(256), 0, (hipStream_t)stream, Z, z_stride,
+                       z_mean, M, m_stride, m_mean, N, (int)d, (int)F, rg_chunk(N), (double*)workspace);
+    hipLaunchKernelGGL(ridge_gram_finish_kernel, dim3(blocks256(d * W)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, parts, (int)d, (int)F, shift, A, R);
+    return launch_rc();
+}
 
 }  // namespace
 
@@ -506,8 +506,8 @@ extern "C" size_t cvae_col_means_f64_workspace_bytes(int64_t N, int64_t C) {
 }
 extern "C" int cvae_col_means_f64(const double* x, int64_t N, int64_t C, int64_t stride, double* mean, void* workspace, size_t workspace_bytes, void* stream) {
     if (N < 1 || N >= RIDGE_MAX_ROWS || C < 1 || C >= RIDGE_MAX_ROWS || stride < C) return CVAE_E_BADSHAPE;
-    if (!x || !mean || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned8(x) || !aligned8(mean) || !aligned8(workspace)) return CVAE_E_UNSUPPORTED;
+    if (any_null(x, mean, workspace)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(x, mean, workspace)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_col_means_f64_workspace_bytes(N, C)) return CVAE_E_WORKSPACE;
     const int parts = (int)rg_parts(N);
     hipLaunchKernelGGL(col_sums_kernel, dim3(blocks256(C), (unsigned)parts), dim3(256), 0, (hipStream_t)stream, x, N, (int)C, stride, rg_chunk(N), (double*)workspace);
@@ -517,26 +517,20 @@ extern "C" int cvae_col_means_f64(const double* x, int64_t N, int64_t C, int64_t
 
 extern "C" size_t cvae_ridge_gram_f64_workspace_bytes(int64_t N, int64_t d, int64_t F) {
     if (!ridge_shape_ok(N, d, F)) return 0;
-    return (size_t)rg_parts(N) * d * (d + F) * sizeof(double);
+    return gram_ws_bytes(N, d, F);
 }
 extern "C" int cvae_ridge_gram_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N,
                                    int64_t d, int64_t F, double alpha, double* A, double* R, void* workspace, size_t workspace_bytes, void* stream) {
     if (!ridge_shape_ok(N, d, F) || z_stride < d || m_stride < F) return CVAE_E_BADSHAPE;
-    if (!(alpha > 0.0) || !(alpha <= 1.7976931348623157e308)) return CVAE_E_BADSHAPE;      // a NaN or an infinity too: the centred Gram matrix is singular without alpha
-    if (!Z || !z_mean || !M || !m_mean || !A || !R || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned8(Z) || !aligned8(z_mean) || !aligned8(M) || !aligned8(m_mean) || !aligned8(A) || !aligned8(R) || !aligned8(workspace)) return CVAE_E_UNSUPPORTED;
-    if (workspace_bytes < cvae_ridge_gram_f64_workspace_bytes(N, d, F)) return CVAE_E_WORKSPACE;
-    const int parts = (int)rg_parts(N);
-    const int64_t W = d + F;
-    hipLaunchKernelGGL(ridge_gram_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)parts), dim3(256), 0, (hipStream_t)stream, Z, z_stride,
-                       z_mean, M, m_stride, m_mean, N, (int)d, (int)F, rg_chunk(N), (double*)workspace);
-    hipLaunchKernelGGL(ridge_gram_finish_kernel, dim3(blocks256(d * W)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, parts, (int)d, (int)F, alpha, A, R);
-    return launch_rc();
+    if (!(alpha > 0.0) || !finite_f64(alpha)) return CVAE_E_BADSHAPE;      // a NaN or an infinity too: the centred Gram matrix is singular without alpha
+    if (any_null(Z, z_mean, M, m_mean, A, R, workspace)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Z, z_mean, M, m_mean, A, R, workspace)) return CVAE_E_UNSUPPORTED;
+    return gram_launch(Z, z_stride, z_mean, M, m_stride, m_mean, N, d, F, alpha, A, R, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cvae_chol_f64(double* A, int64_t d, int* info, void* stream) {
     if (d < 1 || d > 1024) return CVAE_E_BADSHAPE;
-    if (!A || !info) return CVAE_E_NULLPTR;
+    if (any_null(A, info)) return CVAE_E_NULLPTR;
     if (!aligned8(A) || !aligned4(info)) return CVAE_E_UNSUPPORTED;
     const int n = (int)d;
     for (int k0 = 0; k0 < n; k0 += CH_NB) {
@@ -558,25 +552,22 @@ extern "C" int cvae_trsm_f64(const double* L, int64_t ldl, const double* in, int
                              int64_t ldo, int64_t d, int64_t n, int transpose, void* stream) {
     if (d < 1 || d > 1024 || n < 1 || n >= RIDGE_MAX_ROWS || ldl < d || ldo < n || in_row_stride < 1 || in_col_stride < 1) return CVAE_E_BADSHAPE;
     if (transpose != 0 && transpose != 1) return CVAE_E_UNSUPPORTED;
-    if (!L || !in || !out) return CVAE_E_NULLPTR;
-    if (!aligned8(L) || !aligned8(in) || !aligned8(row_shift) || !aligned8(out)) return CVAE_E_UNSUPPORTED;
+    if (any_null(L, in, out)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(L, in, row_shift, out)) return CVAE_E_UNSUPPORTED;
     if (in == out && (in_row_stride != ldo || in_col_stride != 1)) return CVAE_E_UNSUPPORTED;      // in place only element for element
-    const dim3 grid((unsigned)((n + TR_COLS - 1) / TR_COLS));
-    if (transpose)
-        hipLaunchKernelGGL(trsm_kernel<true>, grid, dim3(TR_COLS), 0, (hipStream_t)stream, L, ldl, in, in_row_stride, in_col_stride, row_shift, out, ldo, (int64_t)1, (int)d, n);
-    else
-        hipLaunchKernelGGL(trsm_kernel<false>, grid, dim3(TR_COLS), 0, (hipStream_t)stream, L, ldl, in, in_row_stride, in_col_stride, row_shift, out, ldo, (int64_t)1, (int)d, n);
-    return launch_rc();
+    return with_bool(transpose != 0, [&](auto rev) {
+        hipLaunchKernelGGL(trsm_kernel<decltype(rev)::value>, dim3((unsigned)((n + TR_COLS - 1) / TR_COLS)), dim3(TR_COLS), 0, (hipStream_t)stream, L, ldl, in,
+                           in_row_stride, in_col_stride, row_shift, out, ldo, (int64_t)1, (int)d, n);
+        return launch_rc();
+    });
 }
 
 extern "C" int cvae_ridge_loo_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, const double* W,
                                   const double* T, int64_t N, int64_t d, int64_t F, double* leverage, double* fitted, double* loo, double* coef, double* intercept,
                                   void* stream) {
     if (!ridge_shape_ok(N, d, F) || z_stride < d || m_stride < F) return CVAE_E_BADSHAPE;
-    if (!Z || !z_mean || !M || !m_mean || !W || !T || !leverage || !fitted || !loo || !coef || !intercept) return CVAE_E_NULLPTR;
-    if (!aligned8(Z) || !aligned8(z_mean) || !aligned8(M) || !aligned8(m_mean) || !aligned8(W) || !aligned8(T) || !aligned8(leverage) || !aligned8(fitted) ||
-        !aligned8(loo) || !aligned8(coef) || !aligned8(intercept))
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(Z, z_mean, M, m_mean, W, T, leverage, fitted, loo, coef, intercept)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Z, z_mean, M, m_mean, W, T, leverage, fitted, loo, coef, intercept)) return CVAE_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ridge_leverage_kernel, dim3(blocks256(N)), dim3(256), 0, st, T, N, (int)d, leverage);
     hipLaunchKernelGGL(ridge_fit_kernel, dim3(blocks256(N * F)), dim3(256), 0, st, Z, z_stride, z_mean, M, m_stride, m_mean, W, (const double*)leverage, N, (int)d,
@@ -589,8 +580,8 @@ extern "C" int cvae_ridge_predict_f64(const double* Z, int64_t z_stride, const d
                                       void* stream) {
     if (N < 0 || d < 1 || d > 1024 || !rows_features_ok(N, F) || z_stride < d) return CVAE_E_BADSHAPE;
     if (N == 0) return CVAE_OK;
-    if (!Z || !coef || !intercept || !out) return CVAE_E_NULLPTR;
-    if (!aligned8(Z) || !aligned8(coef) || !aligned8(intercept) || !aligned8(out)) return CVAE_E_UNSUPPORTED;
+    if (any_null(Z, coef, intercept, out)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Z, coef, intercept, out)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(ridge_predict_kernel, dim3(blocks256(N * F)), dim3(256), 0, (hipStream_t)stream, Z, z_stride, coef, intercept, N, (int)d, (int)F, out);
     return launch_rc();
 }
@@ -598,8 +589,8 @@ extern "C" int cvae_ridge_predict_f64(const double* Z, int64_t z_stride, const d
 extern "C" int cvae_ranking_stats_f64(const double* Y, int64_t y_stride, const double* P, int64_t p_stride, int64_t N, int64_t F, double* r2, double* corr,
                                       void* stream) {
     if (N < 1 || !rows_features_ok(N, F) || y_stride < F || p_stride < F) return CVAE_E_BADSHAPE;
-    if (!Y || !P || !r2 || !corr) return CVAE_E_NULLPTR;
-    if (!aligned8(Y) || !aligned8(P) || !aligned8(r2) || !aligned8(corr)) return CVAE_E_UNSUPPORTED;
+    if (any_null(Y, P, r2, corr)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Y, P, r2, corr)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(ranking_stats_kernel, dim3((unsigned)F), dim3(256), 0, (hipStream_t)stream, Y, y_stride, P, p_stride, N, r2, corr);
     return launch_rc();
 }
@@ -608,35 +599,24 @@ extern "C" int cvae_group_means_resampled_f64(const double* Z, int64_t z_stride,
                                               double* out, int* counts, void* stream) {
     if (N < 1 || N >= RIDGE_MAX_ROWS || d < 1 || d > 65536 || G < 1 || G > 65535 || n_boot < 0 || n_boot > 65535 || z_stride < d) return CVAE_E_BADSHAPE;
     if (n_boot == 0) return CVAE_OK;
-    if (!Z || !codes || !idx || !out || !counts) return CVAE_E_NULLPTR;
-    if (!aligned8(Z) || !aligned4(codes) || !aligned4(idx) || !aligned8(out) || !aligned4(counts)) return CVAE_E_UNSUPPORTED;
+    if (any_null(Z, codes, idx, out, counts)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Z, out) || !all_aligned<4>(codes, idx, counts)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(group_means_resampled_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)G, (unsigned)n_boot), dim3(64), 0, (hipStream_t)stream, Z, z_stride, codes,
                        idx, N, (int)d, (int)G, out, counts);
     return launch_rc();
 }
 
 // ---- the alpha path and the latent PCA ----
-namespace {
-bool gram_shape_ok(int64_t N, int64_t d, int64_t F) { return N >= 1 && N < RIDGE_MAX_ROWS && d >= 1 && d <= 1024 && F >= 0 && F < RIDGE_MAX_ROWS / 1024; }
-}  // namespace
-
 extern "C" size_t cvae_centered_gram_f64_workspace_bytes(int64_t N, int64_t d, int64_t F) {
     if (!gram_shape_ok(N, d, F)) return 0;
-    return (size_t)rg_parts(N) * d * (d + F) * sizeof(double);
+    return gram_ws_bytes(N, d, F);
 }
 extern "C" int cvae_centered_gram_f64(const double* Z, int64_t z_stride, const double* z_mean, const double* M, int64_t m_stride, const double* m_mean, int64_t N,
                                       int64_t d, int64_t F, double* G, double* R, void* workspace, size_t workspace_bytes, void* stream) {
     if (!gram_shape_ok(N, d, F) || z_stride < d || (F > 0 && m_stride < F)) return CVAE_E_BADSHAPE;
-    if (!Z || !z_mean || !G || !workspace || (F > 0 && (!M || !m_mean || !R))) return CVAE_E_NULLPTR;
-    if (!aligned8(Z) || !aligned8(z_mean) || !aligned8(G) || !aligned8(workspace) || (F > 0 && (!aligned8(M) || !aligned8(m_mean) || !aligned8(R))))
-        return CVAE_E_UNSUPPORTED;
-    if (workspace_bytes < cvae_centered_gram_f64_workspace_bytes(N, d, F)) return CVAE_E_WORKSPACE;
-    const int parts = (int)rg_parts(N);
-    const int64_t W = d + F;
-    hipLaunchKernelGGL(ridge_gram_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((d + 63) / 64), (unsigned)parts), dim3(256), 0, (hipStream_t)stream, Z, z_stride,
-                       z_mean, M, m_stride, m_mean, N, (int)d, (int)F, rg_chunk(N), (double*)workspace);
-    hipLaunchKernelGGL(ridge_gram_finish_kernel, dim3(blocks256(d * W)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, parts, (int)d, (int)F, 0.0, G, R);
-    return launch_rc();
+    if (any_null(Z, z_mean, G, workspace) || (F > 0 && any_null(M, m_mean, R))) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Z, z_mean, G, workspace) || (F > 0 && !all_aligned<8>(M, m_mean, R))) return CVAE_E_UNSUPPORTED;
+    return gram_launch(Z, z_stride, z_mean, M, m_stride, m_mean, N, d, F, 0.0, G, R, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cvae_centered_matmul_f64(const double* x, int64_t x_row_stride, int64_t x_col_stride, const double* mean, const double* b, int64_t b_row_stride,
@@ -644,8 +624,8 @@ extern "C" int cvae_centered_matmul_f64(const double* x, int64_t x_row_stride, i
     if (R < 1 || R >= RIDGE_MAX_ROWS || K < 1 || K > 1024 || C < 1 || C >= RIDGE_MAX_ROWS / 1024 || ldo < C || x_row_stride < 1 || x_col_stride < 1 ||
         b_row_stride < 1 || b_col_stride < 1)
         return CVAE_E_BADSHAPE;
-    if (!x || !b || !out) return CVAE_E_NULLPTR;
-    if (!aligned8(x) || !aligned8(mean) || !aligned8(b) || !aligned8(out)) return CVAE_E_UNSUPPORTED;
+    if (any_null(x, b, out)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(x, mean, b, out)) return CVAE_E_UNSUPPORTED;
     if (out == x || out == b) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(centered_matmul_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((R + 63) / 64)), dim3(256), 0, (hipStream_t)stream, x, x_row_stride,
                        x_col_stride, mean, b, b_row_stride, b_col_stride, R, (int)K, C, out, ldo);
@@ -656,10 +636,8 @@ extern "C" int cvae_ridge_path_f64(const double* P, const double* Q, const doubl
                                    const double* m_mean, int64_t N, int64_t d, int64_t F, int64_t G, double* eigenvalues, double* leverage, double* loo, double* sse,
                                    void* stream) {
     if (!ridge_shape_ok(N, d, F) || m_stride < F || G < 1 || G > 64) return CVAE_E_BADSHAPE;
-    if (!P || !Q || !lambda || !alphas || !M || !m_mean || !eigenvalues || !leverage || !loo || !sse) return CVAE_E_NULLPTR;
-    if (!aligned8(P) || !aligned8(Q) || !aligned8(lambda) || !aligned8(alphas) || !aligned8(M) || !aligned8(m_mean) || !aligned8(eigenvalues) || !aligned8(leverage) ||
-        !aligned8(loo) || !aligned8(sse))
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(P, Q, lambda, alphas, M, m_mean, eigenvalues, leverage, loo, sse)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(P, Q, lambda, alphas, M, m_mean, eigenvalues, leverage, loo, sse)) return CVAE_E_UNSUPPORTED;
     if (eigenvalues == lambda) return CVAE_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ridge_path_leverage_kernel, dim3(blocks256(N), (unsigned)G), dim3(256), 0, st, P, lambda, alphas, N, (int)d, leverage, eigenvalues);
@@ -672,9 +650,8 @@ extern "C" int cvae_ridge_path_f64(const double* P, const double* Q, const doubl
 extern "C" int cvae_pca_components_f64(const double* w, const double* V, int64_t ldv, int64_t d, int64_t k, int64_t N, double* components,
                                        double* explained_variance, double* explained_variance_ratio, double* singular_values, void* stream) {
     if (d < 1 || d > 1024 || ldv < d || N < 2 || N >= RIDGE_MAX_ROWS || k < 1 || k > d || k > N - 1) return CVAE_E_BADSHAPE;
-    if (!w || !V || !components || !explained_variance || !explained_variance_ratio || !singular_values) return CVAE_E_NULLPTR;
-    if (!aligned8(w) || !aligned8(V) || !aligned8(components) || !aligned8(explained_variance) || !aligned8(explained_variance_ratio) || !aligned8(singular_values))
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(w, V, components, explained_variance, explained_variance_ratio, singular_values)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(w, V, components, explained_variance, explained_variance_ratio, singular_values)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(pca_components_kernel, dim3((unsigned)k), dim3(256), 0, (hipStream_t)stream, w, V, ldv, (int)d, N, components, explained_variance,
                        explained_variance_ratio, singular_values);
     return launch_rc();

@@ -12,8 +12,8 @@
 //                workgroup 0 can recompute every row for the record: KL of the exaggerated P, |gains grad|^2, a non-finite flag, Zs)
 //   fit          the host loop of TSNE._tsne: two launches per iteration; the host reads the record (4 doubles) at every multiple of 50 iterations and stops
 //                launching.  NOT enqueue-only.
-// No atomics, no workgroup waits on another.  Every sum: a thread's strided terms in index order, a 64-lane xor butterfly, the four waves in order; ordered
-// finishes across workgroups.  Grids are functions of N alone: two runs give equal bits.
+// No atomics, no workgroup waits on another.  Every sum: a thread's strided terms in index order, then common.h's butterfly (block_sum_f64, ordered_sum_f64:
+// a 64-lane xor butterfly, the four waves in order); ordered finishes across workgroups.  Grids are functions of N alone: two runs give equal bits.
 #include <float.h>
 #include "common.h"
 
@@ -29,35 +29,6 @@ constexpr double TSNE_EPS = 2.220446049250313e-16;          // 2^-52, sklearn's 
 constexpr int FR = (int)TSNE_FORCE_ROWS;
 static_assert(FR >= 1 && FR <= 8, "TSNE_FORCE_ROWS: 1 .. 8");
 enum { REC_KL = 0, REC_GN2 = 1, REC_BAD = 2, REC_ZS = 3, REC_WORDS = 4 };
-
-__device__ __forceinline__ bool finite_f64(double x) { return fabs(x) <= DBL_MAX; }          // false for a NaN
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// NV sums over a 256-thread workgroup, the result in every thread: red holds 4 NV doubles
-template <int NV> __device__ __forceinline__ void block_sum_f64(double (&v)[NV], double* red) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_sum_f64(v[k]);
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[4 * k + wid] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = ((red[4 * k] + red[4 * k + 1]) + red[4 * k + 2]) + red[4 * k + 3];
-}
-// sum of x[0 .. n) in the one order every caller uses
-__device__ __forceinline__ double ordered_sum_f64(const double* __restrict__ x, int n, double* red) {
-    double v[1] = {0.0};
-    for (int j = threadIdx.x; j < n; j += 256) v[0] += x[j];
-    block_sum_f64(v, red);
-    return v[0];
-}
 
 // ---- distances ----
 template <typename T> __global__ __launch_bounds__(256) void tsne_sqdist_kernel(const T* __restrict__ Z, int64_t ldz, int N, int d, double* __restrict__ D) {
@@ -106,8 +77,7 @@ __global__ __launch_bounds__(256) void tsne_affinities_kernel(const double* __re
         tsne_row[j] = v;
         if (j != i) mn = fmin(mn, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
+    mn = wave_min_f64(mn);
     if ((t & 63) == 0) red[t >> 6] = mn;
     __syncthreads();
     mn = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
@@ -364,8 +334,6 @@ __global__ __launch_bounds__(256) void tsne_fit_end_kernel(const double* __restr
     }
 }
 
-inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 inline bool tsne_n_ok(int64_t N) { return N >= TSNE_MIN_N && N <= TSNE_MAX_N; }
 inline unsigned tsne_tiles(int64_t N) { return (unsigned)((N + TSNE_TILE - 1) / TSNE_TILE); }
 inline unsigned tsne_elem_blocks(int64_t N) { return (unsigned)((2 * N + 255) / 256); }
@@ -411,7 +379,7 @@ tsne_fit_layout tsne_fit_plan(int64_t N) {
 
 extern "C" int cvae_tsne_sqdist_f64(const void* Z, int z_is_f32, int64_t z_stride, int64_t N, int64_t d, double* D, void* stream) {
     if (!tsne_n_ok(N) || d < 1 || d > INT32_MAX || z_stride < d) return CVAE_E_BADSHAPE;
-    if (!Z || !D) return CVAE_E_NULLPTR;
+    if (any_null(Z, D)) return CVAE_E_NULLPTR;
     if (!(z_is_f32 ? aligned4(Z) : aligned8(Z)) || !aligned8(D)) return CVAE_E_UNSUPPORTED;
     const dim3 grid(tsne_tiles(N), tsne_tiles(N));
     if (z_is_f32) hipLaunchKernelGGL(tsne_sqdist_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)Z, z_stride, (int)N, (int)d, D);
@@ -421,8 +389,8 @@ extern "C" int cvae_tsne_sqdist_f64(const void* Z, int z_is_f32, int64_t z_strid
 
 extern "C" int cvae_tsne_affinities_f64(const double* D, int64_t N, double perplexity, double tol, double* Pc, double* beta, int* steps, void* stream) {
     if (!tsne_n_ok(N) || !(perplexity > 0.0 && perplexity < (double)N) || !(tol >= 0.0)) return CVAE_E_BADSHAPE;
-    if (!D || !Pc || !beta || !steps) return CVAE_E_NULLPTR;
-    if (!aligned8(D) || !aligned8(Pc) || !aligned8(beta) || !aligned4(steps) || D == Pc) return CVAE_E_UNSUPPORTED;
+    if (any_null(D, Pc, beta, steps)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(D, Pc, beta) || !aligned4(steps) || D == Pc) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(tsne_affinities_kernel, dim3((unsigned)N), dim3(256), (size_t)N * sizeof(double), (hipStream_t)stream, D, (int)N, log(perplexity), tol, Pc,
                        beta, steps);
     return launch_rc();
@@ -435,8 +403,8 @@ extern "C" size_t cvae_tsne_joint_f64_workspace_bytes(int64_t N) {
 
 extern "C" int cvae_tsne_joint_f64(const double* D, const double* Pc, int64_t N, double* P, int* info, void* workspace, size_t workspace_bytes, void* stream) {
     if (!tsne_n_ok(N)) return CVAE_E_BADSHAPE;
-    if (!D || !Pc || !P || !info || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned8(D) || !aligned8(Pc) || !aligned8(P) || !aligned4(info) || !aligned8(workspace) || P == Pc || P == D) return CVAE_E_UNSUPPORTED;
+    if (any_null(D, Pc, P, info, workspace)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(D, Pc, P, workspace) || !aligned4(info) || P == Pc || P == D) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_tsne_joint_f64_workspace_bytes(N)) return CVAE_E_WORKSPACE;
     const unsigned T = tsne_tiles(N);
     double* part = (double*)workspace;
@@ -450,8 +418,8 @@ extern "C" int cvae_tsne_joint_f64(const double* D, const double* Pc, int64_t N,
 
 extern "C" int cvae_tsne_forces_f64(const double* Y, const double* P, int64_t N, double* A, double* R, double* S, double* kl_partials, void* stream) {
     if (!tsne_n_ok(N)) return CVAE_E_BADSHAPE;
-    if (!Y || !P || !A || !R || !S) return CVAE_E_NULLPTR;
-    if (!aligned8(Y) || !aligned8(P) || !aligned8(A) || !aligned8(R) || !aligned8(S) || !aligned8(kl_partials)) return CVAE_E_UNSUPPORTED;
+    if (any_null(Y, P, A, R, S)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Y, P, A, R, S, kl_partials)) return CVAE_E_UNSUPPORTED;
     const int rc = launch_forces(Y, P, (int)N, A, R, S, kl_partials, (hipStream_t)stream);
     return rc != CVAE_OK ? rc : launch_rc();
 }
@@ -459,8 +427,8 @@ extern "C" int cvae_tsne_forces_f64(const double* Y, const double* P, int64_t N,
 extern "C" int cvae_tsne_grad_f64(const double* A, const double* R, const double* S, const double* kl_partials, int64_t N, double exaggeration, double* grad,
                                   double* kl, void* stream) {
     if (!tsne_n_ok(N) || !(exaggeration > 0.0)) return CVAE_E_BADSHAPE;
-    if (!A || !R || !S || !grad || (kl && !kl_partials)) return CVAE_E_NULLPTR;
-    if (!aligned8(A) || !aligned8(R) || !aligned8(S) || !aligned8(kl_partials) || !aligned8(grad) || !aligned8(kl)) return CVAE_E_UNSUPPORTED;
+    if (any_null(A, R, S, grad) || (kl && !kl_partials)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(A, R, S, kl_partials, grad, kl)) return CVAE_E_UNSUPPORTED;
     hipLaunchKernelGGL(tsne_grad_kernel, dim3(tsne_elem_blocks(N)), dim3(256), 0, (hipStream_t)stream, A, R, S, kl_partials, (int)N, exaggeration, grad, kl);
     return launch_rc();
 }
@@ -469,10 +437,9 @@ extern "C" int cvae_tsne_update_f64(const double* Y, const double* update, const
                                     const double* kl_partials, int64_t N, double exaggeration, double momentum, double learning_rate, double* Y_out,
                                     double* update_out, double* gains_out, double* record, void* stream) {
     if (!tsne_n_ok(N) || !(exaggeration > 0.0)) return CVAE_E_BADSHAPE;
-    if (!Y || !update || !gains || !A || !R || !S || !Y_out || !update_out || !gains_out || (record && !kl_partials)) return CVAE_E_NULLPTR;
-    if (!aligned8(Y) || !aligned8(update) || !aligned8(gains) || !aligned8(A) || !aligned8(R) || !aligned8(S) || !aligned8(kl_partials) || !aligned8(Y_out) ||
-        !aligned8(update_out) || !aligned8(gains_out) || !aligned8(record) || Y_out == Y || update_out == update || gains_out == gains)
-        return CVAE_E_UNSUPPORTED;
+    if (any_null(Y, update, gains, A, R, S, Y_out, update_out, gains_out) || (record && !kl_partials)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(Y, update, gains, A, R, S, kl_partials, Y_out, update_out, gains_out, record)) return CVAE_E_UNSUPPORTED;
+    if (Y_out == Y || update_out == update || gains_out == gains) return CVAE_E_UNSUPPORTED;
     launch_update(Y, update, gains, A, R, S, kl_partials, (int)N, exaggeration, momentum, learning_rate, Y_out, update_out, gains_out, record, (hipStream_t)stream);
     return launch_rc();
 }
@@ -487,8 +454,8 @@ extern "C" int cvae_tsne_fit_f64(const double* P, double* Y, int64_t N, double e
                                  void* stream) {
     if (!tsne_n_ok(N) || !(early_exaggeration > 0.0) || !(learning_rate > 0.0) || max_iter < 0 || max_iter > INT32_MAX || n_iter_without_progress < 0)
         return CVAE_E_BADSHAPE;
-    if (!P || !Y || !kl || !info || !workspace) return CVAE_E_NULLPTR;
-    if (!aligned8(P) || !aligned8(Y) || !aligned8(kl) || !aligned4(info) || !aligned8(workspace)) return CVAE_E_UNSUPPORTED;
+    if (any_null(P, Y, kl, info, workspace)) return CVAE_E_NULLPTR;
+    if (!all_aligned<8>(P, Y, kl, workspace) || !aligned4(info)) return CVAE_E_UNSUPPORTED;
     if (workspace_bytes < cvae_tsne_fit_f64_workspace_bytes(N)) return CVAE_E_WORKSPACE;
     const tsne_fit_layout L = tsne_fit_plan(N);
     char* base = (char*)workspace;

@@ -3107,14 +3107,34 @@ def mlp_heads_train(panels, layers, split=None, clamp0=None, clamp1=None, eps=No
 
 
 # ---- the latent translator (csrc/ridge.hip): float64 throughout ----
-class RidgeFit:
-    """What ridge_fit_loo returns: coef [F, d], intercept [F], fitted [N, F], loo [N, F] (the leave-one-out predictions), leverage [N], r2 [F], corr [F]:
-    float64 device tensors; info: the Cholesky's status (0: factorised)."""
-    __slots__ = ("coef", "intercept", "fitted", "loo", "leverage", "r2", "corr", "info")
+class _Result:
+    """what an analysis call returns: the fields a subclass names in __slots__, every one of them given by keyword"""
+    __slots__ = ()
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw[k])
+
+
+class RidgeFit(_Result):
+    """What ridge_fit_loo returns: coef [F, d], intercept [F], fitted [N, F], loo [N, F] (the leave-one-out predictions), leverage [N], r2 [F], corr [F]:
+    float64 device tensors; info: the Cholesky's status (0: factorised)."""
+    __slots__ = ("coef", "intercept", "fitted", "loo", "leverage", "r2", "corr", "info")
+
+
+def _got(x):
+    """what a refusal says it was handed: a tensor's shape and dtype, anything else's type"""
+    return f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
+
+
+def _f64c(t):
+    """detached, float64 (widening float32 is exact), contiguous"""
+    return t.detach().double().contiguous()
+
+
+def _f64_like(like):
+    """new(*shape): an uninitialised float64 tensor on like's device"""
+    return lambda *shape: _empty(shape, torch.float64, like)
 
 
 def _f64_rows(what, name, t, cols=None):
@@ -3157,14 +3177,8 @@ def ranking_stats_f64(Y, P):
     return r2, corr
 
 
-def ridge_fit_loo(Z, M, alpha):
-    """The Ridge translator Z [N, d] -> M [N, F] with an unpenalised intercept (sklearn's Ridge(alpha, fit_intercept=True)) and its EXACT leave-one-out
-    predictions from one Cholesky factorisation (DESIGN §25; the reference refits N times, latent_translator/analysis.py:36-48), all in float64 on the device:
-    column means, the centred Gram matrix A = Xc^T Xc + alpha I on the fp64 MFMA, A = L L^T, T = L^-1 Xc^T (the leverages h = 1 / N + column norms of T),
-    W = A^-1 Xc^T Yc by two more solves, then fitted = mbar + Xc W, loo = M - (M - fitted) / (1 - h) and the ranking statistics of loo against M.
-    Z: float32 or float64 (float32 is widened with .double(), which is exact); M is converted to float64.  Returns a RidgeFit.  The one host read is the
-    Cholesky's info, at the end: non-zero (a pivot <= 0 or NaN, e.g. a NaN in Z) is a CvaeError naming the column."""
-    what = "ridge_fit_loo"
+def _ridge_shapes(what, Z, M, limit):
+    """the refusals of ridge_fit_loo and ridge_loo_path for the shapes and dtypes, none of which needs a device; limit: whose bound d <= 1024 is -> (N, d, F)"""
     if Z.dim() != 2 or M.dim() != 2:
         raise L.CvaeError(f"{what}: Z [N, d] and M [N, F] expected, got {tuple(Z.shape)} and {tuple(M.shape)}")
     if Z.dtype not in (torch.float32, torch.float64):
@@ -3176,17 +3190,34 @@ def ridge_fit_loo(Z, M, alpha):
     if N < 2:
         raise L.CvaeError(f"{what}: at least 2 samples expected (leave-one-out leaves N - 1), got N = {N}")
     if d < 1 or d > 1024:
-        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected (the blocked Cholesky's limit), got d = {d}")
+        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected ({limit}), got d = {d}")
     if F < 1:
         raise L.CvaeError(f"{what}: at least one feature column expected, got M {tuple(M.shape)}")
-    alpha = float(alpha)
-    if not (alpha > 0.0 and math.isfinite(alpha)):
-        raise L.CvaeError(f"{what}: alpha must be positive and finite (the centred Gram matrix is singular without it), got {alpha}")
+    return N, d, F
+
+
+def _ridge_alpha(what, name, a):
+    """a (a Python float), or CvaeError unless it is positive and finite; name: 'alpha' or 'every alpha', how the message begins"""
+    if not (a > 0.0 and math.isfinite(a)):
+        raise L.CvaeError(f"{what}: {name} must be positive and finite (the centred Gram matrix is singular without it), got {a}")
+    return a
+
+
+def ridge_fit_loo(Z, M, alpha):
+    """The Ridge translator Z [N, d] -> M [N, F] with an unpenalised intercept (sklearn's Ridge(alpha, fit_intercept=True)) and its EXACT leave-one-out
+    predictions from one Cholesky factorisation (DESIGN §25; the reference refits N times, latent_translator/analysis.py:36-48), all in float64 on the device:
+    column means, the centred Gram matrix A = Xc^T Xc + alpha I on the fp64 MFMA, A = L L^T, T = L^-1 Xc^T (the leverages h = 1 / N + column norms of T),
+    W = A^-1 Xc^T Yc by two more solves, then fitted = mbar + Xc W, loo = M - (M - fitted) / (1 - h) and the ranking statistics of loo against M.
+    Z: float32 or float64 (float32 is widened with .double(), which is exact); M is converted to float64.  Returns a RidgeFit.  The one host read is the
+    Cholesky's info, at the end: non-zero (a pivot <= 0 or NaN, e.g. a NaN in Z) is a CvaeError naming the column."""
+    what = "ridge_fit_loo"
+    N, d, F = _ridge_shapes(what, Z, M, "the blocked Cholesky's limit")
+    alpha = _ridge_alpha(what, "alpha", float(alpha))
     L.require_gpu(Z, M)
-    Z, M = Z.detach().double().contiguous(), M.detach().double().contiguous()
+    Z, M = _f64c(Z), _f64c(M)
     zs, ms = _f64_rows(what, "Z", Z), _f64_rows(what, "M", M)
     zbar, mbar = col_means_f64(Z), col_means_f64(M)
-    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    new = _f64_like(Z)
     A, R = new(d, d), new(d, F)
     _t, wp, wb = _f64_ws(lib.cvae_ridge_gram_f64_workspace_bytes(N, d, F), Z)
     check(L.timed(f"ridge_gram N{N} d{d} F{F}", lib.cvae_ridge_gram_f64, ptr(Z), zs, ptr(zbar), ptr(M), ms, ptr(mbar), N, d, F, alpha, ptr(A), ptr(R), wp, wb,
@@ -3220,7 +3251,7 @@ def ridge_predict(Z, coef, intercept):
     if d < 1 or d > 1024 or F < 1:
         raise L.CvaeError(f"{what}: 1 <= d <= 1024 and F >= 1 expected, got d = {d}, F = {F}")
     L.require_gpu(Z, coef, intercept)
-    Z, coef, intercept = Z.detach().double().contiguous(), coef.contiguous(), intercept.contiguous()
+    Z, coef, intercept = _f64c(Z), coef.contiguous(), intercept.contiguous()
     out = _empty((N, F), torch.float64, Z)
     check(lib.cvae_ridge_predict_f64(ptr(Z), d, ptr(coef), ptr(intercept), N, d, F, ptr(out), stream()), "ridge_predict_f64")
     return out
@@ -3240,7 +3271,7 @@ def group_means_resampled(Z, codes, idx, G):
     if N < 1 or d < 1 or d > 65536 or G < 1 or G > 65535 or n_boot > 65535:
         raise L.CvaeError(f"{what}: N >= 1, 1 <= d <= 65536, 1 <= G <= 65535 and n_boot <= 65535 expected, got N = {N}, d = {d}, G = {G}, n_boot = {n_boot}")
     L.require_gpu(Z, codes, idx)
-    Z, codes, idx = Z.detach().double().contiguous(), codes.to(torch.int32).contiguous(), idx.to(torch.int32).contiguous()
+    Z, codes, idx = _f64c(Z), codes.to(torch.int32).contiguous(), idx.to(torch.int32).contiguous()
     out, counts = _empty((n_boot, G, d), torch.float64, Z), _empty((n_boot, G), torch.int32, Z)
     check(lib.cvae_group_means_resampled_f64(ptr(Z), d, ptr(codes), ptr(idx), N, d, G, n_boot, ptr(out), ptr(counts), stream()), "group_means_resampled_f64")
     return out, counts
@@ -3312,15 +3343,11 @@ def centered_matmul_f64(x, mean, b, x_t=False, b_t=False):
     return out
 
 
-class RidgePath:
+class RidgePath(_Result):
     """What ridge_loo_path returns, float64 device tensors: alphas [G], eigenvalues [d] (of the centred Gram matrix, ascending, clamped at 0), leverage [G, N],
     loo [G, N, F] (the leave-one-out predictions), sse [G, F] (sum over the rows of (M - loo)^2), r2 [G, F] and corr [G, F] (cvae_ranking_stats_f64's);
     sweeps: how many Jacobi sweeps the eigensolver used."""
     __slots__ = ("alphas", "eigenvalues", "leverage", "loo", "sse", "r2", "corr", "sweeps")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw[k])
 
 
 def ridge_path_alphas(what, alphas):
@@ -3333,10 +3360,7 @@ def ridge_path_alphas(what, alphas):
         raise L.CvaeError(f"{what}: alphas is empty")
     if len(grid) > RIDGE_PATH_MAX_ALPHAS:
         raise L.CvaeError(f"{what}: at most {RIDGE_PATH_MAX_ALPHAS} alphas expected, got {len(grid)}")
-    for a in grid:
-        if not (a > 0.0 and math.isfinite(a)):
-            raise L.CvaeError(f"{what}: every alpha must be positive and finite (the centred Gram matrix is singular without it), got {a}")
-    return grid
+    return [_ridge_alpha(what, "every alpha", a) for a in grid]
 
 
 def ridge_loo_path(Z, M, alphas):
@@ -3350,7 +3374,7 @@ def ridge_loo_path(Z, M, alphas):
     grid = ridge_path_args(what, Z, M, alphas)
     (N, d), F = Z.shape, M.shape[1]
     L.require_gpu(Z, M)
-    Z, M = Z.detach().double().contiguous(), M.detach().double().contiguous()
+    Z, M = _f64c(Z), _f64c(M)
     ms = _f64_rows(what, "M", M)
     Gn = len(grid)
     zbar, mbar = col_means_f64(Z), col_means_f64(M)
@@ -3358,7 +3382,7 @@ def ridge_loo_path(Z, M, alphas):
     w, V, sweeps = eigh_f64(gram)
     P = centered_matmul_f64(Z, zbar, V)                  # Xc V
     Q = centered_matmul_f64(V, None, R, x_t=True)        # V^T (Xc^T Yc)
-    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    new = _f64_like(Z)
     a_dev = torch.tensor(grid, dtype=torch.float64, device=Z.device)
     out = dict(eigenvalues=new(d), leverage=new(Gn, N), loo=new(Gn, N, F), sse=new(Gn, F), r2=new(Gn, F), corr=new(Gn, F))
     check(L.timed(f"ridge_path N{N} d{d} F{F} G{Gn}", lib.cvae_ridge_path_f64, ptr(P), ptr(Q), ptr(w), ptr(a_dev), ptr(M), ms, ptr(mbar), N, d, F, Gn,
@@ -3370,20 +3394,7 @@ def ridge_loo_path(Z, M, alphas):
 
 def ridge_path_args(what, Z, M, alphas):
     """every refusal of ridge_loo_path, none of which needs a device: ridge_fit_loo's for the shapes and dtypes, then the grid's -> the grid as Python floats"""
-    if Z.dim() != 2 or M.dim() != 2:
-        raise L.CvaeError(f"{what}: Z [N, d] and M [N, F] expected, got {tuple(Z.shape)} and {tuple(M.shape)}")
-    if Z.dtype not in (torch.float32, torch.float64):
-        raise L.CvaeError(f"{what}: Z must be float32 or float64, got {Z.dtype}")
-    N, d = Z.shape
-    F = M.shape[1]
-    if M.shape[0] != N:
-        raise L.CvaeError(f"{what}: Z has {N} rows, M has {M.shape[0]}")
-    if N < 2:
-        raise L.CvaeError(f"{what}: at least 2 samples expected (leave-one-out leaves N - 1), got N = {N}")
-    if d < 1 or d > 1024:
-        raise L.CvaeError(f"{what}: 1 <= d <= 1024 latent dimensions expected (the eigensolver's limit), got d = {d}")
-    if F < 1:
-        raise L.CvaeError(f"{what}: at least one feature column expected, got M {tuple(M.shape)}")
+    _ridge_shapes(what, Z, M, "the eigensolver's limit")
     return ridge_path_alphas(what, alphas)
 
 
@@ -3407,11 +3418,11 @@ def pca_fit_f64(Z, n_components):
     k = pca_args("pca_fit_f64", Z, n_components)
     N, d = Z.shape
     L.require_gpu(Z)
-    Z = Z.detach().double().contiguous()
+    Z = _f64c(Z)
     mean = col_means_f64(Z)
     gram, _r = centered_gram_f64(Z, mean)
     w, V, _sweeps = eigh_f64(gram)
-    new = lambda *shape: _empty(shape, torch.float64, Z)          # noqa: E731
+    new = _f64_like(Z)
     out = dict(components=new(k, d), explained_variance=new(k), explained_variance_ratio=new(k), singular_values=new(k))
     check(lib.cvae_pca_components_f64(ptr(w), ptr(V), d, d, k, N, ptr(out["components"]), ptr(out["explained_variance"]), ptr(out["explained_variance_ratio"]),
                                       ptr(out["singular_values"]), stream()), "pca_components_f64")
@@ -3424,7 +3435,7 @@ def pca_transform_f64(Z, mean, components):
     if Z.dim() != 2 or Z.dtype not in (torch.float32, torch.float64) or components.dim() != 2 or Z.shape[1] != components.shape[1] or Z.shape[0] < 1:
         raise L.CvaeError(f"{what}: Z [N >= 1, d] float32 or float64 and components [k, d] expected, got {tuple(Z.shape)} {Z.dtype}, {tuple(components.shape)}")
     L.require_gpu(Z, mean, components)
-    return centered_matmul_f64(Z.detach().double().contiguous(), mean, components.contiguous(), b_t=True)
+    return centered_matmul_f64(_f64c(Z), mean, components.contiguous(), b_t=True)
 
 
 # ---- the exact t-SNE of the latents (csrc/tsne.hip): float64 throughout ----
@@ -3432,14 +3443,10 @@ TSNE_MIN_N, TSNE_MAX_N = 3, 4096
 TSNE_STOP_REASONS = ("max_iter iterations ran", "the gradient norm fell to min_grad_norm", "no progress within n_iter_without_progress iterations")
 
 
-class TsneFit:
+class TsneFit(_Result):
     """What tsne_fit_f64 returns: Y [N, 2] (float64, on the device), kl (a float: the KL divergence of P from the embedding's Q), n_iter (the index of the last
     iteration run, sklearn's n_iter_), reason (an index into TSNE_STOP_REASONS), checks (how many times the host read the device's record)."""
     __slots__ = ("Y", "kl", "n_iter", "reason", "checks")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw[k])
 
 
 def tsne_args(what, Z, perplexity=30.0, n_components=2, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, init="pca", tol=1e-5,
@@ -3447,8 +3454,7 @@ def tsne_args(what, Z, perplexity=30.0, n_components=2, early_exaggeration=12.0,
     """Every refusal of the t-SNE entries, none of which needs a device.  Z: the tensor to embed, [N, d] float32 / float64, or with distances=True the squared
     distances [N, N].  Returns (N, the learning rate as a float)."""
     if not torch.is_tensor(Z) or Z.dim() != 2 or Z.dtype not in (torch.float32, torch.float64):
-        got = f"{tuple(Z.shape)} {Z.dtype}" if torch.is_tensor(Z) else type(Z).__name__
-        raise L.CvaeError(f"{what}: a float32 or float64 matrix expected, got {got}")
+        raise L.CvaeError(f"{what}: a float32 or float64 matrix expected, got {_got(Z)}")
     N, d = Z.shape
     if N < TSNE_MIN_N or N > TSNE_MAX_N:
         raise L.CvaeError(f"{what}: {TSNE_MIN_N} <= N <= {TSNE_MAX_N} points expected (the exact method holds the N x N affinities), got N = {N}")
@@ -3486,8 +3492,7 @@ def tsne_args(what, Z, perplexity=30.0, n_components=2, early_exaggeration=12.0,
 
 def _tsne_f64(what, name, t, shape):
     if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
-        got = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
-        raise L.CvaeError(f"{what}: {name} must be a float64 tensor {list(shape)}, got {got}")
+        raise L.CvaeError(f"{what}: {name} must be a float64 tensor {list(shape)}, got {_got(t)}")
     return t.detach().contiguous()
 
 
@@ -3528,7 +3533,7 @@ def tsne_affinities_f64(D, perplexity, tol=1e-5):
 
 def _tsne_pair_pass(what, Y, P, want_kl):
     N = Y.shape[0]
-    new = lambda *shape: _empty(shape, torch.float64, Y)          # noqa: E731
+    new = _f64_like(Y)
     A, R, S = new(N, 2), new(N, 2), new(N)
     klp = new(3, N) if want_kl else None
     check(L.timed(f"tsne_forces N{N}", lib.cvae_tsne_forces_f64, ptr(Y), ptr(P), N, ptr(A), ptr(R), ptr(S), ptr(klp), stream()), "tsne_forces_f64")
@@ -3604,8 +3609,7 @@ MORPH_EMPTY, MORPH_NO_BACKGROUND = 1, 2          # bits of raw[:, 0]
 def morph_args(what, x, threshold=0.2, norms=MORPH_NORMS):
     """Every refusal of morph_features12, raised before any launch; the device is asked about last, so that the others can be met without one.  Returns (B, H, W)."""
     if not torch.is_tensor(x) or x.dim() not in (3, 4):
-        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise L.CvaeError(f"{what}: images [B, H, W] or [B, 1, H, W] expected, got {got}")
+        raise L.CvaeError(f"{what}: images [B, H, W] or [B, 1, H, W] expected, got {_got(x)}")
     if x.dim() == 4 and x.shape[1] != 1:
         raise L.CvaeError(f"{what}: one channel expected (grey images [B, 1, H, W]), got {x.shape[1]} in {tuple(x.shape)}")
     if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -3653,8 +3657,7 @@ PREP_MAX_BATCH, PREP_MAX_PIXELS = 65535, 2 ** 31 - 1
 def _prep_images(what, x, dims, dtypes, names):
     """the refusals the four image_prep ops share: a tensor of `dims` axes, one of `dtypes`, no empty axis, at most PREP_MAX_BATCH images of less than 2^31 pixels"""
     if not torch.is_tensor(x) or x.dim() != dims:
-        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise L.CvaeError(f"{what}: a tensor {names} expected, got {got}")
+        raise L.CvaeError(f"{what}: a tensor {names} expected, got {_got(x)}")
     if x.dtype not in dtypes:
         raise L.CvaeError(f"{what}: {' or '.join(str(d).replace('torch.', '') for d in dtypes)} expected, got {x.dtype}")
     if min(x.shape) < 1:
@@ -3766,10 +3769,9 @@ def minmax_binarise(y, augment=False, dtype=torch.float32):
     A = 4 if augment else 1
     out = _empty((B * A, 1, H, W), dtype, yy)
     rec = _empty((B, 32), torch.uint8, yy)
-    nbytes = lib.cvae_minmax_binarise_workspace_bytes(B, H, W)
-    ws = _empty((nbytes // 8 + 1,), torch.float64, yy)
+    _t, wp, wb = _f64_ws(lib.cvae_minmax_binarise_workspace_bytes(B, H, W), yy)
     check(L.timed(f"minmax_binarise B{B} {H}x{W} A{A}", lib.cvae_minmax_binarise, ptr(yy), ptr(out), ptr(rec), B, H, W, int(bool(augment)), L.dtype_code(dtype),
-                  ptr(ws), ws.numel() * 8, stream()), what)
+                  wp, wb, stream()), what)
     return out, BinariseStats(rec)
 
 
@@ -3798,8 +3800,7 @@ def percentile_ranks(n, p):
 def percentile_args(what, x, p=99.5):
     """Every refusal of percentile_clip_scale, raised before any launch; the device is asked about last.  Returns (B, N)."""
     if not torch.is_tensor(x) or x.dim() not in (2, 3):
-        got = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise L.CvaeError(f"{what}: a tensor [B, N] or [B, H, W] expected, got {got}")
+        raise L.CvaeError(f"{what}: a tensor [B, N] or [B, H, W] expected, got {_got(x)}")
     _prep_images(what, x if x.dim() == 3 else x[:, None, :], 3, (torch.float32,), "[B, N] or [B, H, W]")
     try:
         ok = 50.0 <= float(p) <= 100.0
@@ -3831,10 +3832,9 @@ def percentile_clip_scale(x, p=99.5, check_finite=True):
     out = torch.empty_like(xx)
     rec = _empty((B, 24), torch.uint8, xx)
     ranks, ts = percentile_ranks(N, float(p))
-    nbytes = lib.cvae_percentile_clip_scale_workspace_bytes(B, N)
-    ws = _empty((nbytes // 8 + 1,), torch.float64, xx)
+    _t, wp, wb = _f64_ws(lib.cvae_percentile_clip_scale_workspace_bytes(B, N), xx)
     check(L.timed(f"percentile_clip_scale B{B} N{N}", lib.cvae_percentile_clip_scale, ptr(xx), ptr(out), ptr(rec), B, N, (C_.c_int64 * 4)(*ranks),
-                  (C_.c_double * 2)(*ts), ptr(ws), ws.numel() * 8, stream()), what)
+                  (C_.c_double * 2)(*ts), wp, wb, stream()), what)
     stats = ClipStats(rec)
     if check_finite:
         raise_nonfinite(what, stats.flags)
